@@ -8,10 +8,13 @@ the reference mount; x0 ~ N(0,1) centred; in-kernel Philox noise.  One "step" = 
 once: score-network forward + VJP + BAOAB update.  Steps are issued as persistent-kernel launches of `--chunk` steps
 (default 250 = save_interval: one saved frame per launch), state resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]           (N>1: under torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]     (N>1: under torch.distributed.run)
 
-The timed region is never shorter than 8 launches: `--steps` / `--warmup` are rounded UP to whole launches and the
-line reports the steps actually run (`steps`, `warmup`) next to the request (`steps_requested`, `warmup_requested`).
+Exactly K timed and W warm-up steps run: launches of `--chunk` steps, the last one of each region carrying the remainder
+(each launch saves its last frame).  `--dump-outputs DIR` writes what the timed launches computed, as the caller of that
+path receives it, after the timed region: the frame and kinetic energies saved by the last step and the final positions /
+velocities, float32 `.npy` (rank r > 0 of a multi-GPU job: `<name>_rank<r>.npy`).  Inputs (weights, x0, Philox seed and
+step offsets) depend on the arguments only, so two builds run with the same arguments can be compared array for array.
 
 Prints ONE JSON line (rank 0).  `value` is the whole-job aggregate in batch-256 MD-steps/s (weak scaling: every rank
 advances its own 256 trajectories; no data-path collective -- the only collective is the final all_gather of frames,
@@ -46,7 +49,7 @@ NORM_STD = {"chignolin": 3.113133430480957, "villin": 6.082900047302246, "protei
 TEMP = {"chignolin": 340, "villin": 360, "protein_g": 350, "ala2": 300, "trp_cage": 290, "bba": 325}
 PEAK_FP32_TFLOPS = 157.3            # MI355X_MICROARCH.md: f32 vector = f32 MFMA peak
 PEAK_BF16_DENSE_TFLOPS = 2500.0     # dense bf16 / fp16 MFMA peak; an fp32-exact product costs six bf16 products or three fp16 ones
-MIN_LAUNCHES = 8
+MIN_LAUNCHES = 8   # timed launches of each `also` entry
 # DFF_FORCE_DIST=1: run the N > 1 code (process group over RCCL, barriers, max-over-ranks all_reduce, the frame all_gather)
 # at ANY world size -- with one rank under torchrun this loads RCCL and executes every collective of the job on the one GPU
 # a test box has (tests/test_gpu_parity.py::test_bench_rccl_world_one), before the first 8-GPU run does.
@@ -131,7 +134,7 @@ NOTES = {
                 "= 416.7 TFLOP/s, the rest at 157.3).  traffic (HBM bytes per launch), hbm_tbps, mfma_busy, l2_hit: rocprofv3 PMC passes of "
                 "the same workload under `profile`; None + profile_stale when that profile's sources (src_sha) are not the running library's",
     "fold_kv": "hidden == head dim: k / v projections folded into q / out (exact); ~26 % fewer MFMAs issued than the FLOP count used",
-    "timing": "persistent launches of `chunk` fused steps; --steps / --warmup rounded up to whole launches, >= 8 timed",
+    "timing": "persistent launches of `chunk` fused steps (the last one: the remainder); exactly --steps timed, --warmup warm",
     "cpu": "oracle/reference_twin.py (torch CPU port of the reference, materialised formulation), thread count picked by a probe",
     "also": "roofline objects there omit bound / peak / unit (= the headline's)",
 }
@@ -158,22 +161,26 @@ def weight_gemm_mflop(cfg):
     return 2.0 * L * (8.0 * N * H * 512 + 16.0 * N * H * H) / 1e6
 
 
-def mixed_peak_frac(cfg, P, steps_per_launch, avg_launch_ms, kname):
+def mixed_peak_frac(cfg, P, steps, ms, kname):
     """Against the running engine's OWN roof: the time one launch would take with its weight-GEMM FLOPs at the split products'
     rate (dense fp16 / 3 = 833 TFLOP/s, bf16 / 6 = 416.7; the fp32 engine: 157.3) and every other FLOP (attention, gates,
-    heads) at the fp32 rate, over the measured time.  `frac` (all FLOPs at 157.3) stays the headline figure."""
+    heads) at the fp32 rate, over the measured time (`steps` fused steps in `ms` of launch time).  `frac` (all FLOPs
+    at 157.3) stays the headline figure."""
     g = weight_gemm_mflop(cfg) * 1e6
     rest = MFLOP_PER_CALL[cfg] * 1e6 - g
     rate = PEAK_BF16_DENSE_TFLOPS / 3.0 if "split_f16" in kname else PEAK_BF16_DENSE_TFLOPS / 6.0 if "split_bf16" in kname else PEAK_FP32_TFLOPS
-    ideal_s = (g / (rate * 1e12) + rest / (PEAK_FP32_TFLOPS * 1e12)) * P * steps_per_launch
-    return ideal_s / (avg_launch_ms * 1e-3)
+    ideal_s = (g / (rate * 1e12) + rest / (PEAK_FP32_TFLOPS * 1e12)) * P * steps
+    return ideal_s / (ms * 1e-3)
 
 
-def roofline(cfg, P, steps_per_launch, launch_ms, kname, brief=False):
-    """bound = fp32 compute: achieved algorithmic TFLOP/s of one launch against 157.3."""
+def roofline(cfg, P, steps_per_launch, launch_ms, kname, brief=False, launch_steps=None):
+    """bound = fp32 compute: achieved algorithmic TFLOP/s of the timed launches against 157.3.
+    `launch_steps`: steps of each launch when they differ (a remainder launch); default `steps_per_launch` for all."""
     avg = float(np.mean(launch_ms))
+    steps = sum(launch_steps) if launch_steps is not None else steps_per_launch * len(launch_ms)
+    total_ms = float(np.sum(launch_ms))
     flops = MFLOP_PER_CALL[cfg] * 1e6 * P * steps_per_launch
-    ach = flops / (avg * 1e-3) / 1e12
+    ach = MFLOP_PER_CALL[cfg] * 1e6 * P * steps / (total_ms * 1e-3) / 1e12
     pf = profile_figures(kname, cfg, P, steps_per_launch)
     r = {"bound": "mfma", "achieved": round(ach, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
          "frac": round(ach / PEAK_FP32_TFLOPS, 4), "traffic": pf["traffic"], "hbm_tbps": pf["hbm_tbps"],
@@ -190,7 +197,7 @@ def roofline(cfg, P, steps_per_launch, launch_ms, kname, brief=False):
                 del r[k]
     else:
         r["algorithmic_flops_per_launch"] = flops
-    r["mixed_peak_frac"] = round(mixed_peak_frac(cfg, P, steps_per_launch, avg, kname), 4)
+    r["mixed_peak_frac"] = round(mixed_peak_frac(cfg, P, steps, total_ms, kname), 4)
     return r
 
 
@@ -321,8 +328,14 @@ class Timer:
         return elapsed, [a.elapsed_time(b) for a, b in ev]
 
 
-def langevin_entry(cfg, P, chunk, n_warm, n_timed, dev, rank, world, noise_level=20, group=0, fp32_engine=False):
-    """Langevin MD-steps/s of `cfg` at P trajectories per GPU: n_timed launches of `chunk` fused steps each."""
+def launch_sizes(steps, chunk):
+    """`steps` split into launches of `chunk` steps, the last one carrying the remainder."""
+    return [chunk] * (steps // chunk) + ([steps % chunk] if steps % chunk else [])
+
+
+def langevin_entry(cfg, P, chunk, warm_steps, timed_steps, dev, rank, world, noise_level=20, group=0, fp32_engine=False):
+    """Langevin MD-steps/s of `cfg` at P trajectories per GPU: `timed_steps` fused steps in launches of at most `chunk`
+    (launch_sizes), after `warm_steps` untimed ones.  Every launch saves the frame and kinetic energies of its last step."""
     from dff_amd.langevin import LangevinDiffusion
     model, diff, (N, H, L) = make_model(cfg, dev, fp32_engine)
     if group:
@@ -330,22 +343,29 @@ def langevin_entry(cfg, P, chunk, n_warm, n_timed, dev, rank, world, noise_level
     x0 = torch.randn(P, N, 3, generator=torch.Generator().manual_seed(2024 + rank))
     x0 = (x0 - x0.mean(1, keepdim=True)) * NORM_STD[cfg]
     masses = [12.8 if cfg == "ala2" else 12.0] * N
-    total = (n_warm + n_timed) * chunk
-    ld = LangevinDiffusion(diff, x0, total, save_interval=chunk, t=noise_level, temp_data=TEMP[cfg],
+    warm, timed = launch_sizes(warm_steps, chunk), launch_sizes(timed_steps, chunk)
+    sizes = warm + timed
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(int).tolist()
+    total = offsets[-1]
+    ld = LangevinDiffusion(diff, x0, total, save_interval=total, t=noise_level, temp_data=TEMP[cfg],
                            temp_sim=TEMP[cfg], dt=None, masses=masses, friction=1.0, seed=1234, verbose=False)
-    frames = torch.empty(n_warm + n_timed, P, N, 3, device=dev)
-    ke = torch.empty(n_warm + n_timed, P, device=dev)
+    frames = torch.empty(len(sizes), P, N, 3, device=dev)
+    ke = torch.empty(len(sizes), P, device=dev)
 
     def run_chunk(i):
-        model.native.langevin_run(ld.params, ld.x, ld.v, chunk, chunk, noise=None, seed=1234,
-                                  traj_offset=rank * P, step_offset=i * chunk, frames=frames[i:i + 1], ke=ke[i:i + 1])
+        n = sizes[i]
+        model.native.langevin_run(ld.params, ld.x, ld.v, n, n, noise=None, seed=1234,
+                                  traj_offset=rank * P, step_offset=offsets[i], frames=frames[i:i + 1], ke=ke[i:i + 1])
 
-    elapsed, launch_ms = Timer(dev, world).run(run_chunk, n_warm, n_timed)
-    K = n_timed * chunk
+    elapsed, launch_ms = Timer(dev, world).run(run_chunk, len(warm), len(timed))
     kname, grid, lds = model.native.last_launch()
     ok = bool(torch.isfinite(frames).all().item()) and bool(torch.isfinite(ld.x).all().item())
-    return {"cfg": cfg, "N": N, "H": H, "L": L, "P": P, "K": K, "elapsed": elapsed, "launch_ms": launch_ms, "kernel": kname,
-            "grid": grid, "lds": lds, "finite": ok, "frames": frames, "chunk": chunk}
+    # what the caller of the timed path receives from its last step (LangevinDiffusion.sample: frames in Angstrom, kinetic
+    # energies) and the state it leaves behind (normalised positions, velocities)
+    outputs = {"frame_last": frames[-1] * NORM_STD[cfg], "ke_last": ke[-1], "x_final": ld.x, "v_final": ld.v}
+    return {"cfg": cfg, "N": N, "H": H, "L": L, "P": P, "K": timed_steps, "elapsed": elapsed, "launch_ms": launch_ms,
+            "launch_steps": timed, "kernel": kname, "grid": grid, "lds": lds, "finite": ok, "frames": frames, "chunk": chunk,
+            "outputs": outputs}
 
 
 def iid_entry(cfg, P, n_warm, n_timed, dev, rank, world):
@@ -353,11 +373,37 @@ def iid_entry(cfg, P, n_warm, n_timed, dev, rank, world):
     noise levels is built by the warm-up call)."""
     model, diff, (N, H, L) = make_model(cfg, dev)
     diff.seed(77 + rank)
-    elapsed, launch_ms = Timer(dev, world).run(lambda i: diff.sample(P), n_warm, n_timed)
+    last = {}
+
+    def chain(i):
+        last["samples"] = diff.sample(P)
+
+    elapsed, launch_ms = Timer(dev, world).run(chain, n_warm, n_timed)
     diff.check_clamp()
     kname, grid, lds = model.native.last_launch()
     return {"cfg": cfg, "N": N, "H": H, "L": L, "P": P, "elapsed": elapsed, "launch_ms": launch_ms, "kernel": kname,
-            "grid": grid, "lds": lds, "chains": n_timed}
+            "grid": grid, "lds": lds, "chains": n_timed, "outputs": {"samples": last["samples"]}}
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, outputs, rank):
+    """outputs (name -> tensor, all indexed by trajectory / sample along dim 0) as float32 `d/<name>.npy` (`<name>_rank<r>.npy`
+    on ranks > 0).  Above DUMP_BYTES in all, a fixed seeded sample of rows is written, its row numbers in `rows.npy`."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: t.detach().to("cpu", torch.float32).contiguous().numpy() for k, t in outputs.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    assert len(rows) == 1, "outputs must share their leading dimension"
+    n = rows.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES * n // total - 1)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["rows"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}_rank{rank}.npy" if rank else f"{name}.npy"), a)
 
 
 def main():
@@ -374,7 +420,13 @@ def main():
                     help="iid: time complete 1000-step reverse DDPM chains of --cfg at --parallel_sim per GPU instead (profiling runs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
     ap.add_argument("--no-extras", action="store_true", help="skip the other north-star figures (`also`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.chunk < 1:
+        raise SystemExit("--steps and --chunk must be >= 1, --warmup >= 0")
+    if args.mode == "iid" and args.steps % 1000:
+        raise SystemExit("--mode iid times complete 1000-step chains: --steps must be a multiple of 1000")
 
     import dff_amd  # noqa: F401  (loads libdff_amd.so: loud failure if the HIP extension is missing)
     from dff_amd.sampling import dist_backend, dist_env
@@ -398,12 +450,14 @@ def main():
 
     cfg, P, chunk = args.cfg, args.parallel_sim, args.chunk
     if args.mode == "iid":   # the i.i.d. workload on its own (what tools_rocprof.sh profiles for `also.*_iid.roofline.traffic`)
-        nt = max(4, -(-args.steps // 1000))
-        e = iid_entry(cfg, P, 1, nt, dev, rank, world)
+        nt, nw = args.steps // 1000, -(-args.warmup // 1000)   # warm-up: whole chains (the first builds the layer-0 table)
+        e = iid_entry(cfg, P, nw, nt, dev, rank, world)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, e["outputs"], rank)
         if rank == 0:
             print(json.dumps({"metric": f"i.i.d. samples/sec at batch {P} per GPU ({cfg}: complete 1000-step reverse DDPM chains)",
                               "value": world * P * nt / e["elapsed"], "unit": "samples/s (whole job)", "n_gpus": world,
-                              "steps": nt * 1000, "warmup": 1000, "ms_per_step": 1e3 * e["elapsed"] / (nt * 1000),
+                              "steps": nt * 1000, "warmup": nw * 1000, "ms_per_step": 1e3 * e["elapsed"] / (nt * 1000),
                               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": kernel_dtype(e["kernel"]),
                               "data": "synthetic (seeded weights, in-kernel Philox noise)",
                               "config": {"workload": f"{cfg} iid, batch {P}/GPU, 1000 reverse steps per launch", "kernel": e["kernel"]},
@@ -412,10 +466,10 @@ def main():
             import torch.distributed as dist
             dist.destroy_process_group()
         return
-    n_timed = max(MIN_LAUNCHES, -(-args.steps // chunk))
-    n_warm = max(1, -(-args.warmup // chunk)) if args.warmup > 0 else 0
-    h = langevin_entry(cfg, P, chunk, n_warm, n_timed, dev, rank, world, args.noise_level, args.group)
-    K, W = h["K"], n_warm * chunk
+    h = langevin_entry(cfg, P, chunk, args.warmup, args.steps, dev, rank, world, args.noise_level, args.group)
+    K, W = h["K"], args.warmup
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h["outputs"], rank)
     # the job's only collective: gather the saved frames (xGMI); not part of a "step"
     gather_ms = 0.0
     if use_dist:
@@ -438,7 +492,7 @@ def main():
                                                 ("chignolin_langevin_fp32_engine", "chignolin", 256, 250, MIN_LAUNCHES, True),
                                                 # the reference's published protocol: --parallel_sim 100 (evaluate/sampling_commands.md:13)
                                                 ("chignolin_langevin_p100", "chignolin", 100, 250, MIN_LAUNCHES, False)):
-                e = langevin_entry(c2, P2, ch2, 1, nt, dev, rank, world, fp32_engine=f32e)
+                e = langevin_entry(c2, P2, ch2, ch2, nt * ch2, dev, rank, world, fp32_engine=f32e)
                 also[name] = {
                     "workload": f"{c2} ({e['N']} beads, H={e['H']}, L={e['L']}) Langevin, {P2}/GPU" + (", DFF_SPLIT_BF16=0" if f32e else ""),
                     "dtype": kernel_dtype(e["kernel"]),
@@ -471,10 +525,10 @@ def main():
             "config": {"workload": f"BASELINE configs[1]: {cfg} ({N} beads, H={H}, L={L}) Langevin, parallel_sim={P}/GPU, "
                                    f"noise_level={args.noise_level}, save_interval={chunk}, 1 persistent launch per {chunk} steps",
                        "parallelism": f"{world} x independent trajectory shards (no data-path collective)",
-                       "kernel": h["kernel"], "grid": h["grid"], "lds_bytes": h["lds"], "launches_timed": n_timed,
+                       "kernel": h["kernel"], "grid": h["grid"], "lds_bytes": h["lds"], "launches_timed": len(h["launch_steps"]),
                        "collective_backend": backend},
             "trajectory_steps_per_s": traj_steps, "finite": h["finite"], "gather_ms": gather_ms,
-            "roofline": roofline(cfg, P, chunk, h["launch_ms"], h["kernel"]),
+            "roofline": roofline(cfg, P, h["launch_steps"][0], h["launch_ms"], h["kernel"], launch_steps=h["launch_steps"]),
         }
         if world == 1 and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(cfg, P, args.noise_level)

@@ -26,7 +26,10 @@ import sys
 import types
 
 import numpy as np
-import torch
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
+from oracle import cpu_repro  # noqa: E402
+cpu_repro.pin()   # host-independent float32 arithmetic: the twin is held to these vectors bit for bit under the same pin
+import torch  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 REF = "/root/reference"
@@ -43,7 +46,6 @@ from oracle import reference_twin as twin  # noqa: E402
 from oracle import synth  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
-torch.set_num_threads(8)
 
 NORM_STD = {"chignolin": 3.113133430480957, "villin": 6.082900047302246,
             "protein_g": 6.354289531707764, "ala2": 0.9449278712272644,
@@ -165,13 +167,15 @@ def g4_ploop():
     noises = torch.from_numpy(synth.normal((5, 4, N, 3), 999, 31).astype(np.float32))
     mol = x.clone()
     import warnings
+    randn_like = torch.randn_like
     for k, i in enumerate(range(4, -1, -1)):
         # body of GaussianDiffusion.p_sample_loop (ddpm.py:244-251) driven by the reference's
-        # own p_sample; the randn_like draw is replaced by seeding so that noise[k] is known.
-        torch.manual_seed(5000 + k)
-        noises[k] = torch.randn_like(mol)
-        torch.manual_seed(5000 + k)
-        mol = ddpm.p_sample(mol, torch.full((4,), i, dtype=torch.long))
+        # own p_sample; its randn_like draw returns noise[k] (numpy-drawn: the same on every host).
+        torch.randn_like = lambda _x, _k=k: noises[_k].clone()
+        try:
+            mol = ddpm.p_sample(mol, torch.full((4,), i, dtype=torch.long))
+        finally:
+            torch.randn_like = randn_like
         if (mol.max() > 1000) or (mol.min() < -1000):
             warnings.warn("Large molecule encountered in sampling")
             mol = torch.clamp(mol, min=-1000, max=1000)

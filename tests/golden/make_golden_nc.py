@@ -13,7 +13,10 @@ import sys
 import types
 
 import numpy as np
-import torch
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
+from oracle import cpu_repro  # noqa: E402
+cpu_repro.pin()   # host-independent float32 arithmetic: the twin is held to these vectors bit for bit under the same pin
+import torch  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 REF = "/root/reference"
@@ -29,7 +32,6 @@ from oracle import reference_twin as twin  # noqa: E402
 from oracle import synth  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
-torch.set_num_threads(8)
 
 
 def build(cfg, dtype=torch.float32, decoder_scale=1.0):

@@ -15,7 +15,10 @@ import sys
 import types
 
 import numpy as np
-import torch
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
+from oracle import cpu_repro  # noqa: E402
+cpu_repro.pin()   # host-independent float32 arithmetic: the twin is held to these vectors bit for bit under the same pin
+import torch  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 REF = "/root/reference"
@@ -31,7 +34,6 @@ from oracle import reference_twin as twin  # noqa: E402
 from oracle import synth  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
-torch.set_num_threads(8)
 SHAPES = {"smoke": (10, 256, 5, False), "cons": (20, 256, 2, True)}   # N, H, L, conservative
 
 

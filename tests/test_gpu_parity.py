@@ -924,7 +924,7 @@ def test_bench_two_ranks_on_one_gpu(dff):
     import socket
     import subprocess
     import sys
-    args = ["--steps", "500", "--warmup", "250", "--no-cpu", "--no-extras"]
+    args = ["--steps", "2000", "--warmup", "250", "--no-cpu", "--no-extras"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, capture_output=True, text=True,
                          timeout=600, env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert one.returncode == 0, one.stdout[-1500:] + one.stderr[-1500:]
@@ -950,6 +950,31 @@ def test_bench_two_ranks_on_one_gpu(dff):
     ratio = r2["value"] / r1["value"]
     print(f"bench 2 ranks on 1 GPU: value {r2['value']:.1f} vs 1 rank {r1['value']:.1f} (ratio {ratio:.2f})")
     assert 0.45 < ratio < 1.35, ratio
+
+
+@pytest.mark.gpu
+def test_bench_exact_steps_and_reproducible_dump(dff, tmp_path):
+    """bench.py times exactly --steps steps (a remainder launch after the whole ones) and --dump-outputs writes what the last
+    timed step computed; with the same arguments two runs write the same arrays, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "270", "--warmup", "5",
+                            "--no-cpu", "--no-extras", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600,
+                           env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["steps"] == 270 and j["warmup"] == 5 and j["config"]["launches_timed"] == 2 and j["finite"]
+        runs.append({n: np.load(d / f"{n}.npy") for n in ("frame_last", "ke_last", "x_final", "v_final")})
+    a, b = runs
+    assert a["frame_last"].shape == a["x_final"].shape == a["v_final"].shape == (256, 10, 3) and a["ke_last"].shape == (256,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    # the frame saved by the last step is the final state, in Angstrom
+    assert np.allclose(a["frame_last"], a["x_final"] * 3.113133430480957, rtol=1e-6, atol=1e-6)
 
 
 @pytest.mark.gpu
@@ -1136,7 +1161,7 @@ def test_bench_rccl_world_one(dff):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DFF_TEST_KNOBS", "DFF_DIST_BACKEND", "DFF_DEVICE")}
     env.update(DFF_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "500", "--warmup", "250",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2000", "--warmup", "250",
                         "--no-cpu", "--no-extras"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
 
@@ -28,7 +29,8 @@ def test_twin_matches_reference(name, golden):
     g = golden(f"score_h256_{name}.npz")
     N, H, L, cons = SHAPES[name]
     p = params_for(name)
-    f = twin.score(twin.to_torch(p), torch.from_numpy(g["x"]), torch.from_numpy(g["t"]), L, conservative=cons).numpy()
+    # host-independent float32 arithmetic (oracle/cpu_repro.py), as the golden vectors were recorded
+    f = cpu_repro.call(twin.score, twin.to_torch(p), torch.from_numpy(g["x"]), torch.from_numpy(g["t"]), L, conservative=cons).numpy()
     assert np.array_equal(f, g["forces32"])
     f64 = twin.score(twin.to_torch(p, torch.float64), torch.from_numpy(g["x"]).double(), torch.from_numpy(g["t"]).double(),
                      L, conservative=cons).numpy()

@@ -232,6 +232,38 @@ def test_bench_finds_the_profiled_traffic_for_the_shipped_kernels():
     assert abs(bench.MFLOP_PER_CALL["chignolin"] * 1e6 * 256 * 250 - 1.408e12) < 1e6
 
 
+def test_bench_exact_step_split_and_bounded_dump(tmp_path):
+    """--steps K runs exactly K timed steps: whole launches of --chunk plus one remainder launch, the roofline over all of
+    them.  --dump-outputs stays under 64 MB: above it a fixed seeded sample of rows is written, row numbers alongside."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.launch_sizes(20, 250) == [20] and bench.launch_sizes(500, 250) == [250, 250]
+    assert bench.launch_sizes(2100, 250) == [250] * 8 + [100] and bench.launch_sizes(0, 250) == []
+    kn = "dff_small_kernel<64,8,split_f16,fold_kv>"
+    even = bench.roofline("chignolin", 256, 250, [10.0] * 2, kn)
+    rem = bench.roofline("chignolin", 256, 250, [10.0, 10.0, 4.0], kn, launch_steps=[250, 250, 100])
+    assert rem["frac"] == even["frac"] and rem["mixed_peak_frac"] == even["mixed_peak_frac"]   # same rate per step
+    small = {"x": torch.arange(24, dtype=torch.float64).reshape(4, 2, 3), "e": torch.ones(4)}
+    bench.dump_outputs(str(tmp_path / "a"), small, 0)
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, small["x"].numpy()) and not (tmp_path / "a" / "rows.npy").exists()
+    bench.dump_outputs(str(tmp_path / "a"), small, 1)
+    assert (tmp_path / "a" / "e_rank1.npy").exists()
+    bench.DUMP_BYTES = 1000
+    big = {"x": torch.randn(1000, 10, 3), "e": torch.randn(1000)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 0)
+    files = {f: np.load(tmp_path / "b" / f) for f in ("x.npy", "e.npy", "rows.npy")}
+    assert sum(a.nbytes for f, a in files.items() if f != "rows.npy") <= 1000
+    rows = files["rows.npy"].astype(int)
+    assert np.array_equal(files["x.npy"], big["x"].numpy()[rows]) and np.array_equal(files["e.npy"], big["e"].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "c" / "rows.npy"), files["rows.npy"])   # the same sample every run
+
+
 def test_bench_drops_profile_counters_taken_on_other_sources(tmp_path):
     """a traffic.json is tied to the sources it profiled (src_sha = sha256 over csrc/* + include/dff.h,
     compiled into the library by build.sh, stamped by tools_profile_report.py).  bench.py reports the rocprofv3 counters

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
 
@@ -27,7 +28,8 @@ def rel(a, b):
 def test_twin_matches_reference(cfg, golden):
     g = golden(f"score_nc_{cfg}.npz")
     p, (N, H, L) = params_for(cfg)
-    f = twin.score(twin.to_torch(p), torch.from_numpy(g["x"]), torch.from_numpy(g["t"]), L, conservative=False).numpy()
+    # host-independent float32 arithmetic (oracle/cpu_repro.py), as the golden vectors were recorded
+    f = cpu_repro.call(twin.score, twin.to_torch(p), torch.from_numpy(g["x"]), torch.from_numpy(g["t"]), L, conservative=False).numpy()
     assert np.array_equal(f, g["forces32"])
     f64 = twin.score(twin.to_torch(p, torch.float64), torch.from_numpy(g["x"]).double(), torch.from_numpy(g["t"]).double(),
                      L, conservative=False).numpy()

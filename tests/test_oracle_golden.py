@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
 
@@ -105,7 +106,9 @@ def test_p_sample(cfg, golden):
 def test_p_sample_loop_with_clamp(golden):
     g = golden("ploop_chignolin.npz")
     p, (N, H, L) = _params("chignolin")
-    y = twin.p_sample_loop(p, twin.make_schedule(), torch.from_numpy(g["x5"]), torch.from_numpy(g["noises"]), 4, L)
+    # host-independent float32 arithmetic (oracle/cpu_repro.py), as the golden vectors were recorded: the clamped chain
+    # amplifies the host's own last-bit differences past the tolerance
+    y = cpu_repro.call(cpu_repro.twin_p_sample_loop, p, torch.from_numpy(g["x5"]), torch.from_numpy(g["noises"]), 4, L)
     np.testing.assert_allclose(y.numpy(), g["x0"], rtol=1e-5, atol=1e-5)
     assert np.abs(y.numpy().mean(1)).max() < 1e-3  # assert_center_zero, utils.py:73-86
 

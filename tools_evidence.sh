@@ -3,7 +3,7 @@
 # tools_profile_report.py afterwards).  usage: tools_evidence.sh <round tag, e.g. r04>
 set -u
 TAG=${1:-r06}
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$(readlink -f "$0")")"
 mkdir -p gpurun_out
 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
 python tools_bench_configs.py > gpurun_out/${TAG}_configs.jsonl 2>/dev/null

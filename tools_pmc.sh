@@ -3,7 +3,7 @@
 # main kernel, appended to gpurun_out/pmc.jsonl.   usage: tools_pmc.sh <exp name | base> "<counters>" [bench args...]
 set -u
 NAME=$1; CTRS=$2; shift 2
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT="$(dirname "$(readlink -f "$0")")"
 LIB=$ROOT/build/exp/$NAME/libdff_amd.so; [ "$NAME" = base ] && LIB=$ROOT/two-for-one-diffusion_amd/libdff_amd.so
 cd /tmp && export TMPDIR=/tmp
 OUT=/tmp/pmc_$NAME; rm -rf $OUT

@@ -4,8 +4,8 @@
 # Counters are collected in their own runs (no trace domains together with --pmc).
 set -u
 TAG=${1:-r01}; shift || true
+ROOT="$(dirname "$(readlink -f "$0")")"
 cd /tmp && export TMPDIR=/tmp
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 BENCH="python $ROOT/bench.py --steps 1000 --warmup 250 --no-cpu --no-extras $*"
