@@ -145,10 +145,19 @@ def _unheads(t):  # (B,8,N,64) -> (B,N,512)
 
 
 # ----------------------------------------------------------------------------- forward
+def cast(fw: dict, dtype) -> dict:
+    """The folded matrices rounded to `dtype`: forward() of the result runs in that precision (np.float32: the float32 twin of
+    every stage, the yardstick of the kernels' stage-level errors)."""
+    out = {k: np.asarray(v, dtype) for k, v in fw.items() if k != "layers"}
+    out["layers"] = [{k: np.asarray(v, dtype) for k, v in lw.items()} for lw in fw["layers"]]
+    return out
+
+
 def forward(fw: dict, x: np.ndarray, t: np.ndarray):
-    """x (B,N,3) ALREADY centred, t (B,) normalised time.  Returns (energy (B,N), stash)."""
-    x = np.asarray(x, np.float64)
-    t = np.asarray(t, np.float64).reshape(-1)
+    """x (B,N,3) ALREADY centred, t (B,) normalised time.  Returns (energy (B,N), stash), in the precision of fw's matrices."""
+    dt = np.result_type(fw["W_node"], np.float32)
+    x = np.asarray(x, dt)
+    t = np.asarray(t, dt).reshape(-1)
     B, N, _ = x.shape
     Wn = fw["W_node"]  # (H, N+1): one-hot(bead) columns then the t column
     nodes = Wn[:, :N].T[None] + t[:, None, None] * Wn[:, N][None, None] + fw["b_node"]

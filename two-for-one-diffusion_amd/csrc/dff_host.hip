@@ -376,6 +376,11 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
                 return mx;
             };
             double worst = 0;
+            // ... and the low end: a piece resolves 2^-25 / 2^11 = 2^-36 absolutely (fp16's subnormal spacing below 2^-14), so an
+            // operand whose largest entry is below 2^-12 no longer gets the format's 2^-22 relative accuracy.  `least` is the
+            // smallest of the GEMM weights' max|w| (exact zeros are exact pieces: skipped) and of the LayerNorm rows' bounds.
+            double least = INFINITY;
+            auto low = [&](double v) { if (v > 0) least = std::min(least, v); };
             for (int l = 0; l < L; ++l) {
                 const float* Wq = skip((size_t)I * H); const float* bq = skip(I);
                 const float* Wkv = skip((size_t)2 * I * H); const float* bkv = skip(2 * I);
@@ -393,14 +398,15 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
                 const double hb = rowl1(W1, F, H) * m2 + amax(b1, F);                            // |h_pre| >= |GELU(h_pre)|
                 worst = std::max(std::max(worst, m1), std::max(std::max(m2, vb), hb));
                 // the weights themselves become fp16 pieces too (f32_to_f16_rn maps |w| >= 65520 to infinity)
-                worst = std::max(worst, std::max(std::max(amax(Wq, (size_t)I * H), amax(Wkv, (size_t)2 * I * H)),
-                                                 std::max(std::max(amax(Wek, (size_t)I * H), amax(Wo, (size_t)H * I)),
-                                                          std::max(amax(W1, (size_t)F * H), amax(W2, (size_t)H * F)))));
+                const double aq = amax(Wq, (size_t)I * H), ak = amax(Wkv, (size_t)I * H), av = amax(Wkv + (size_t)I * H, (size_t)I * H),
+                             ae = amax(Wek, (size_t)I * H), ao = amax(Wo, (size_t)H * I), a1 = amax(W1, (size_t)F * H), a2 = amax(W2, (size_t)H * F);
+                worst = std::max(worst, std::max(std::max(std::max(aq, std::max(ak, av)), std::max(ae, ao)), std::max(a1, a2)));
+                low(m1); low(m2); low(aq); low(ak); low(av); low(ae); low(ao); low(a1); low(a2);
                 if (H == DFF_DH && L <= 3) {
                     // the k / v fold's kernel (round 6) splits two more activations as they are: q' = W_k,h^T (W_q,h n + b_q,h), an operand
                     // of the logits -- |q'| <= (L1 norm of a row of W_k,h^T W_q,h) max|n| + |W_k,h^T b_q,h| -- and the rows of
                     // G = dattn (W_o,h W_v,h), an operand of dA, whose input rows arrive scaled to a maximum below 32
-                    double qb = 0, gb = 0;
+                    double qb = 0, gb = 0, qm = 0, om = 0;   // (qm, om: max|W_k,h^T W_q,h|, max|W_o,h W_v,h| -- the folded images)
                     for (int h = 0; h < DFF_HEADS; ++h)
                         for (int e = 0; e < DFF_DH; ++e) {
                             double l1 = 0, cqv = 0, g1 = 0;
@@ -411,16 +417,21 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
                                     so += (double)Wo[(size_t)c * I + h * 64 + dd] * Wkv[(size_t)(I + h * 64 + dd) * H + e];
                                 }
                                 l1 += fabs(sq); g1 += fabs(so);
+                                qm = std::max(qm, fabs(sq)); om = std::max(om, fabs(so));
                             }
                             for (int dd = 0; dd < DFF_DH; ++dd) cqv += (double)Wkv[(size_t)(h * 64 + dd) * H + e] * bq[h * 64 + dd];
                             qb = std::max(qb, l1 * m1 + fabs(cqv));
                             gb = std::max(gb, 32.0 * g1);
                         }
                     worst = std::max(worst, std::max(qb, gb));
+                    low(qm); low(om);
                 }
             }
             if (!(worst < 1.6e4)) {
                 fprintf(stderr, "dff: forward activations of this model may reach %.3g (> 1.6e4): the fp16 split engine is off, weight GEMMs run on the fp32 matrix pipe\n", worst);
+                m->split = false;
+            } else if (least < 0x1p-12) {
+                fprintf(stderr, "dff: a weight matrix or LayerNorm row of this model is bounded by %.3g (< 2^-12): below the fp16 split engine's range, weight GEMMs run on the fp32 matrix pipe\n", least);
                 m->split = false;
             }
         }
