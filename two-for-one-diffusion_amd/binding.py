@@ -66,6 +66,11 @@ SYMBOLS = {
     "dff_pwd_num_pairs": (C.c_int, [C.c_int, C.c_int]),
     "dff_pwd_max": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P]),
     "dff_pwd_hist": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "dff_struct_rmsd": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, _P]),
+    "dff_struct_dihedrals": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P]),
+    "dff_struct_tic_num_features": (C.c_int, [C.c_int]),
+    "dff_struct_tic": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "dff_struct_contacts": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_float, _P, C.c_int, _P, _P, _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -346,3 +351,74 @@ def pwd_hist(x, offset: int, nbins, hmax):
     _check(lib, lib.dff_pwd_hist(x.device.index, _ptr(x), n, N, int(offset), _ptr(nb_d), _ptr(hm_d), max_bins,
                                  max_bins, _ptr(out), stream), "dff_pwd_hist")
     return out
+
+
+# ---- structure metrics (dff_struct_*): stateless entry points, no model handle ----
+def _stream(x):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def struct_rmsd(x, ref):
+    """Optimal-rotation RMSD (Angstrom) of every frame of x (n, N, 3) to ref (N, 3) -> float32 CUDA tensor (n,);
+    NaN for frames with a non-finite coordinate."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    r = torch.as_tensor(ref, dtype=torch.float32).reshape(N, 3).to(x.device).contiguous()
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    _check(lib, lib.dff_struct_rmsd(x.device.index, _ptr(x), n, N, _ptr(r), _ptr(out), _stream(x)), "dff_struct_rmsd")
+    return out
+
+
+def struct_dihedrals(x):
+    """Dihedrals (radians) of the consecutive bead quadruples of x (n, N, 3) -> float32 CUDA tensor (n, N - 3)."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((n, max(N - 3, 0)), dtype=torch.float32, device=x.device)
+    _check(lib, lib.dff_struct_dihedrals(x.device.index, _ptr(x), n, N, _ptr(out), _stream(x)), "dff_struct_dihedrals")
+    return out
+
+
+def struct_tic_num_features(n_beads: int) -> int:
+    return int(load_library().dff_struct_tic_num_features(int(n_beads)))
+
+
+def struct_tic(x, mean, coeff):
+    """TIC projection (feat - mean) @ coeff of the N - 3 dihedrals + N (N - 1) / 2 pair distances of every frame of
+    x (n, N, 3); mean (F,), coeff (F, k) -> float64 CUDA tensor (n, k)."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    F = struct_tic_num_features(N)
+    m = torch.as_tensor(mean, dtype=torch.float64).to(x.device).contiguous()
+    A = torch.as_tensor(coeff, dtype=torch.float64).to(x.device).contiguous()
+    if m.shape != (F,) or A.dim() != 2 or A.shape[0] != F:
+        raise ValueError(f"mean must be ({F},) and coeff ({F}, k) for {N} beads")
+    k = int(A.shape[1])
+    out = torch.empty((n, k), dtype=torch.float64, device=x.device)
+    _check(lib, lib.dff_struct_tic(x.device.index, _ptr(x), n, N, _ptr(m), _ptr(A), k, _ptr(out), _stream(x)),
+           "dff_struct_tic")
+    return out
+
+
+def struct_contacts(x, cutoff: float, folded=None, offset: int = 3):
+    """Contacts d_ij < cutoff of the frames x (n, N, 3): (counts, mismatch) with counts an int64 CUDA tensor (N, N)
+    summed over frames and mismatch, when the folded contact map (N, N) is given, an int64 CUDA tensor (n,) of pairs
+    j >= i + offset whose contact differs from it (None otherwise)."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    f = None
+    if folded is not None:
+        f = torch.as_tensor(folded).reshape(N, N).to(device=x.device, dtype=torch.uint8).contiguous()
+    counts = torch.empty((N, N), dtype=torch.int32, device=x.device)
+    mism = torch.empty(n, dtype=torch.int32, device=x.device) if f is not None else None
+    _check(lib, lib.dff_struct_contacts(x.device.index, _ptr(x), n, N, float(cutoff), _ptr(f), int(offset),
+                                        _ptr(counts), _ptr(mism), _stream(x)), "dff_struct_contacts")
+    return counts.to(torch.int64), (mism.to(torch.int64) if mism is not None else None)

@@ -15,6 +15,7 @@
 // lookups, dff_device.h); the small PWD kernels are compiled here
 #include "dff_device.h"
 #include "dff_pwd.hip"
+#include "dff_struct.hip"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...) {
@@ -1404,6 +1405,92 @@ extern "C" int dff_pwd_hist(int device, const float* x, long long n, int N, int 
     const int vec4 = ((uintptr_t)x % 16) == 0;
     hipLaunchKernelGGL(dff_pwd_hist_kernel, dim3((unsigned)grid), dim3(DFF_PWD_HIST_THREADS), lds, stream, x, n, N, offset,
                        npairs, nbins, hmax, ld, pc_log2, npc, chunk, ldl, hist, vec4, tile_n);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Structure metrics: RMSD, dihedrals, TIC projection, contacts (dff_struct.hip)
+// ---------------------------------------------------------------------------------------------
+static int struct_check(const float* x, long long n, int N, const void* out, const char* what) {
+    if ((!x && n > 0) || n < 0) return fail(DFF_EINVAL, "%s: null input / negative count", what);
+    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    if (!out && n > 0) return fail(DFF_EINVAL, "%s: null output", what);
+    if (n > 0x7fffffffLL * DFF_STRUCT_TILE) return fail(DFF_EINVAL, "%s: too many frames", what);
+    return DFF_OK;
+}
+
+// one wave per workgroup: enough of them to keep every CU streaming, each walking tiles with a grid stride
+static unsigned struct_grid(long long n, long long cap) {
+    const long long ntiles = (n + DFF_STRUCT_TILE - 1) / DFF_STRUCT_TILE;
+    return (unsigned)(ntiles < cap ? ntiles : cap);
+}
+static unsigned struct_magic(int N) { return (unsigned)((0x100000000ULL + 3 * N - 1) / (3 * N)); }
+static unsigned struct_tile_bytes(int N) { return (unsigned)(DFF_STRUCT_TILE * ((3 * N) | 1) * sizeof(float)); }
+
+extern "C" int dff_struct_rmsd(int device, const float* x, long long n, int N, const float* ref, float* rmsd,
+                               void* stream_) {
+    int rc = struct_check(x, n, N, rmsd, "struct_rmsd");
+    if (rc) return rc;
+    if (!ref) return fail(DFF_EINVAL, "struct_rmsd: null reference structure");
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    const unsigned lds = (unsigned)(((6 * N + 3) & ~3) * sizeof(float)) + struct_tile_bytes(N);
+    hipLaunchKernelGGL(dff_struct_rmsd_kernel, dim3(struct_grid(n, 8192)), dim3(DFF_STRUCT_TILE), lds,
+                       (hipStream_t)stream_, x, n, N, ref, rmsd, struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_struct_dihedrals(int device, const float* x, long long n, int N, float* out, void* stream_) {
+    int rc = struct_check(x, n, N, out, "struct_dihedrals");
+    if (rc) return rc;
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    const unsigned lds = struct_tile_bytes(N) + (unsigned)(DFF_STRUCT_TILE * (N - 3) * sizeof(float));
+    hipLaunchKernelGGL(dff_struct_dihedrals_kernel, dim3(struct_grid(n, 8192)), dim3(DFF_STRUCT_TILE), lds,
+                       (hipStream_t)stream_, x, n, N, out, struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_struct_tic_num_features(int n_beads) {
+    return n_beads < 4 ? 0 : (n_beads - 3) + n_beads * (n_beads - 1) / 2;
+}
+
+extern "C" int dff_struct_tic(int device, const float* x, long long n, int N, const double* mean, const double* coeff,
+                              int k, double* out, void* stream_) {
+    int rc = struct_check(x, n, N, out, "struct_tic");
+    if (rc) return rc;
+    if (!mean || !coeff) return fail(DFF_EINVAL, "struct_tic: null mean / coefficients");
+    if (k < 1 || k > DFF_TIC_MAXK) return fail(DFF_EINVAL, "struct_tic: k must be 1..%d", DFF_TIC_MAXK);
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipLaunchKernelGGL(dff_struct_tic_kernel, dim3(struct_grid(n, 8192)), dim3(DFF_STRUCT_TILE), struct_tile_bytes(N),
+                       (hipStream_t)stream_, x, n, N, mean, coeff, k, out, struct_magic(N),
+                       (int)(((uintptr_t)x % 16) == 0));
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_struct_contacts(int device, const float* x, long long n, int N, float cutoff, const uint8_t* folded,
+                                   int offset, uint32_t* counts, uint32_t* mismatch, void* stream_) {
+    int rc = struct_check(x, n, N, counts, "struct_contacts");
+    if (rc) return rc;
+    if (!counts) return fail(DFF_EINVAL, "struct_contacts: null counts");
+    if (mismatch && !folded) return fail(DFF_EINVAL, "struct_contacts: per-frame mismatches need a folded contact map");
+    if (offset < 0) return fail(DFF_EINVAL, "struct_contacts: negative offset");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)N * N * sizeof(uint32_t), stream));
+    if (n == 0) return DFF_OK;
+    const unsigned lds = (unsigned)(N * N * sizeof(unsigned) + ((N * N + 15) & ~15)) + struct_tile_bytes(N);
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void*)&dff_struct_contacts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    // every workgroup flushes up to N (N + 1) / 2 counters: fewer, longer workgroups than the other metrics
+    hipLaunchKernelGGL(dff_struct_contacts_kernel, dim3(struct_grid(n, 2048)), dim3(DFF_STRUCT_TILE), lds, stream, x, n,
+                       N, cutoff, folded, offset, counts, mismatch, struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

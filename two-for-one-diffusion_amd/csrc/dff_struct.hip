@@ -1,0 +1,253 @@
+// dff_struct.hip -- per-frame structure metrics of the reference's evaluators on the GPU.
+//
+// Replaces, for (n, N, 3) structures already resident in HBM:
+//   md.rmsd(traj, folded) * 10                   evaluate/evaluators.py:656-662  (RmsdEvaluator.eval)
+//   md.compute_dihedrals(traj, [[i..i+3]])       evaluate/evaluators_CGflowmatching.py:30-36, evaluators.py:433-445
+//   tica.transform(get_tic_features(xyz))        evaluate/evaluators.py:433-445, :460-461  (TicEvaluator)
+//   _get_samp_contacts + sum / _eval_bce_dynamics evaluate/evaluators.py:781-806, :829-859  (ContactEvaluator)
+// The small histogram and divergence reductions stay on the host (evaluate.py); only (n,) / (n, k)-sized
+// results and one (N, N) count matrix come back.
+//
+// Layout of every kernel: one wave per workgroup, one lane per frame.  A tile of 64 frames is streamed
+// into LDS with coalesced 16-byte loads; frame s of the tile sits at tile[s * ld], ld = 3N | 1 (an odd
+// stride: the 64 lanes read 64 different banks).  Everything that loops over beads, pairs or features is
+// then uniform across the wave, so per-bead / per-feature constants (the reference structure, the TICA
+// mean and coefficients, the folded contact map) are wave-uniform loads.  No MFMA: this is HBM-bound work
+// (TIC at protein-G size is bound by its fp64 loop instead).
+//
+// Arithmetic:
+//   distance   pwd_dist2 (dff_pwd.hip): sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) in fp32, bit-equal to torch.norm
+//   dihedral   mdtraj's formula in fp32: b1 = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2,
+//              phi = atan2((b1 . c1) |b2|, c1 . c2)
+//   RMSD       fp64 centring, 3x3 correlation and inner products; lambda_max of Horn's 4x4 key matrix by Newton on
+//              its characteristic quartic (QCP, Theobald 2005) -- the optimal PROPER rotation, as mdtraj
+//   TIC        features (N - 3 dihedrals, then the N (N - 1) / 2 distances in triu_indices(N, N, 1) order) in fp32,
+//              never stored; out[s, c] = sum_f ((double) feat_f - mean_f) * A[f, c] accumulated in fp64
+#pragma once
+#include "dff_internal.h"
+
+#define DFF_STRUCT_TILE 64     // frames per tile = lanes per workgroup (one wave)
+#define DFF_TIC_MAXK 8         // TIC components per call
+
+__device__ __forceinline__ int struct_ld(int N) { return (3 * N) | 1; }
+
+// coalesced load of cnt frames starting at s0 into tile[s * ld + k].  magic = ceil(2^32 / 3N): the frame of
+// flat element e < 64 * 3N is __umulhi(e, magic) exactly (the rounding error e / 2^32 < 1 / 3N).
+__device__ __forceinline__ void struct_load_tile(float* tile, const float* __restrict__ x, long long s0, int cnt,
+                                                 int N3, int ld, unsigned magic, bool vec4) {
+    const float* src = x + s0 * N3;
+    const int nf = cnt * N3;
+    int k0 = 0;
+    if (vec4) {
+        const int n4 = nf >> 2;
+        for (int k = threadIdx.x; k < n4; k += DFF_STRUCT_TILE) {
+            const f32x4 v = __builtin_nontemporal_load((const f32x4*)src + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned f = (unsigned)(4 * k + e);
+                const unsigned s = __umulhi(f, magic);
+                tile[s * ld + (f - s * N3)] = v[e];
+            }
+        }
+        k0 = n4 << 2;
+    }
+    for (int k = k0 + threadIdx.x; k < nf; k += DFF_STRUCT_TILE) {
+        const unsigned s = __umulhi((unsigned)k, magic);
+        tile[s * ld + (k - s * N3)] = src[k];
+    }
+}
+
+__device__ __forceinline__ float struct_dihedral(const float* xs, int i) {
+    const float* p = xs + 3 * i;
+    const float b1x = p[3] - p[0], b1y = p[4] - p[1], b1z = p[5] - p[2];
+    const float b2x = p[6] - p[3], b2y = p[7] - p[4], b2z = p[8] - p[5];
+    const float b3x = p[9] - p[6], b3y = p[10] - p[7], b3z = p[11] - p[8];
+    const float c1x = b2y * b3z - b2z * b3y, c1y = b2z * b3x - b2x * b3z, c1z = b2x * b3y - b2y * b3x;
+    const float c2x = b1y * b2z - b1z * b2y, c2y = b1z * b2x - b1x * b2z, c2z = b1x * b2y - b1y * b2x;
+    const float p1 = (b1x * c1x + b1y * c1y + b1z * c1z) * sqrtf(b2x * b2x + b2y * b2y + b2z * b2z);
+    const float p2 = c1x * c2x + c1y * c2y + c1z * c2z;
+    return atan2f(p1, p2);
+}
+
+// grid-stride loop over tiles: body(s0, cnt, lane, live, xs) once per tile, xs = this lane's frame in LDS
+template <class Body>
+__device__ __forceinline__ void struct_tiles(float* tile, const float* __restrict__ x, long long n, int N, unsigned magic,
+                                             int vec4, Body body) {
+    const int N3 = 3 * N, ld = struct_ld(N);
+    const long long ntiles = (n + DFF_STRUCT_TILE - 1) / DFF_STRUCT_TILE;
+    const int lane = threadIdx.x;
+    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const long long s0 = t * DFF_STRUCT_TILE;
+        const int cnt = (int)(n - s0 < DFF_STRUCT_TILE ? n - s0 : DFF_STRUCT_TILE);
+        __syncthreads();
+        struct_load_tile(tile, x, s0, cnt, N3, ld, magic, vec4 != 0);
+        __syncthreads();
+        body(s0, cnt, lane, lane < cnt, (const float*)(tile + lane * ld));
+    }
+}
+
+// ---- RMSD to a reference structure (fp64 QCP).  LDS: tile | centred reference (N x 3 doubles)
+__device__ __forceinline__ double det3(double a, double b, double c, double d, double e, double f, double g, double h,
+                                       double i) {
+    return a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+}
+
+__global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_rmsd_kernel(const float* __restrict__ x, long long n,
+                                                                           int N, const float* __restrict__ ref,
+                                                                           float* __restrict__ out, unsigned magic,
+                                                                           int vec4) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    double* rc = (double*)smem;                              // N * 3 centred reference coordinates
+    float* tile = smem + ((6 * N + 3) & ~3);
+    // centre the reference (every lane the same sums, in order: no reduction order to depend on)
+    double m0 = 0, m1 = 0, m2 = 0;
+    for (int b = 0; b < N; ++b) { m0 += ref[3 * b]; m1 += ref[3 * b + 1]; m2 += ref[3 * b + 2]; }
+    m0 /= N; m1 /= N; m2 /= N;
+    for (int b = threadIdx.x; b < N; b += DFF_STRUCT_TILE) {
+        rc[3 * b] = ref[3 * b] - m0;
+        rc[3 * b + 1] = ref[3 * b + 1] - m1;
+        rc[3 * b + 2] = ref[3 * b + 2] - m2;
+    }
+    __syncthreads();
+    double Gb = 0;
+    for (int b = 0; b < N; ++b) Gb += rc[3 * b] * rc[3 * b] + rc[3 * b + 1] * rc[3 * b + 1] + rc[3 * b + 2] * rc[3 * b + 2];
+    struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
+        if (live) {
+            bool finite = true;
+            double c0 = 0, c1 = 0, c2 = 0;
+            for (int b = 0; b < N; ++b) {
+                const float a0 = xs[3 * b], a1 = xs[3 * b + 1], a2 = xs[3 * b + 2];
+                finite = finite && isfinite(a0) && isfinite(a1) && isfinite(a2);
+                c0 += a0; c1 += a1; c2 += a2;
+            }
+            c0 /= N; c1 /= N; c2 /= N;
+            double Ga = 0, Sxx = 0, Sxy = 0, Sxz = 0, Syx = 0, Syy = 0, Syz = 0, Szx = 0, Szy = 0, Szz = 0;
+            for (int b = 0; b < N; ++b) {
+                const double a0 = xs[3 * b] - c0, a1 = xs[3 * b + 1] - c1, a2 = xs[3 * b + 2] - c2;
+                const double r0 = rc[3 * b], r1 = rc[3 * b + 1], r2 = rc[3 * b + 2];
+                Ga = fma(a0, a0, fma(a1, a1, fma(a2, a2, Ga)));
+                Sxx = fma(a0, r0, Sxx); Sxy = fma(a0, r1, Sxy); Sxz = fma(a0, r2, Sxz);
+                Syx = fma(a1, r0, Syx); Syy = fma(a1, r1, Syy); Syz = fma(a1, r2, Syz);
+                Szx = fma(a2, r0, Szx); Szy = fma(a2, r1, Szy); Szz = fma(a2, r2, Szz);
+            }
+            // Horn's symmetric key matrix K (trace 0); lambda_max(K) = max over proper rotations of tr(R S)
+            const double k00 = Sxx + Syy + Szz, k01 = Syz - Szy, k02 = Szx - Sxz, k03 = Sxy - Syx;
+            const double k11 = Sxx - Syy - Szz, k12 = Sxy + Syx, k13 = Szx + Sxz;
+            const double k22 = -Sxx + Syy - Szz, k23 = Syz + Szy;
+            const double k33 = -Sxx - Syy + Szz;
+            // characteristic polynomial l^4 + C2 l^2 + C1 l + C0: C2 = -||K||^2 / 2 = -2 ||S||^2, C1 = -8 det S, C0 = det K
+            const double C2 = -2.0 * (Sxx * Sxx + Sxy * Sxy + Sxz * Sxz + Syx * Syx + Syy * Syy + Syz * Syz + Szx * Szx +
+                                      Szy * Szy + Szz * Szz);
+            const double C1 = -8.0 * det3(Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz);
+            const double C0 = k00 * det3(k11, k12, k13, k12, k22, k23, k13, k23, k33) -
+                              k01 * det3(k01, k12, k13, k02, k22, k23, k03, k23, k33) +
+                              k02 * det3(k01, k11, k13, k02, k12, k23, k03, k13, k33) -
+                              k03 * det3(k01, k11, k12, k02, k12, k22, k03, k13, k23);
+            // Newton from (Ga + Gb) / 2 >= lambda_max: monotone descent onto the largest root
+            double l = 0.5 * (Ga + Gb);
+            for (int it = 0; it < 50 && finite; ++it) {
+                const double l2 = l * l, bq = (l2 + C2) * l, aq = bq + C1;
+                const double P = aq * l + C0, dP = 2.0 * l2 * l + bq + aq;
+                if (!(dP != 0.0)) break;
+                const double ln = l - P / dP;
+                const bool done = fabs(l - ln) <= 1e-13 * fabs(ln);
+                l = ln;
+                if (done) break;
+            }
+            const double msd = (Ga + Gb - 2.0 * l) / N;
+            out[s0 + lane] = finite ? (float)sqrt(msd > 0.0 ? msd : 0.0) : __builtin_nanf("");
+        }
+    });
+}
+
+// ---- dihedrals of consecutive quadruples.  LDS: tile | out staging (64 x (N - 3))
+__global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_dihedrals_kernel(const float* __restrict__ x, long long n,
+                                                                                int N, float* __restrict__ out,
+                                                                                unsigned magic, int vec4) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* tile = smem;
+    const int nd = N - 3;
+    float* stage = smem + DFF_STRUCT_TILE * struct_ld(N);
+    struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
+        if (live)
+            for (int i = 0; i < nd; ++i) stage[lane * nd + i] = struct_dihedral(xs, i);
+        __syncthreads();
+        float* dst = out + s0 * nd;
+        for (int k = lane; k < cnt * nd; k += DFF_STRUCT_TILE) dst[k] = stage[k];
+    });
+}
+
+// ---- TIC projection.  LDS: tile.  mean (F,), A (F, k) row-major: wave-uniform loads
+__global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_kernel(const float* __restrict__ x, long long n, int N,
+                                                                          const double* __restrict__ mean,
+                                                                          const double* __restrict__ A, int k,
+                                                                          double* __restrict__ out, unsigned magic,
+                                                                          int vec4) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* tile = smem;
+    struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
+        if (live) {
+            double acc[DFF_TIC_MAXK];
+#pragma unroll
+            for (int c = 0; c < DFF_TIC_MAXK; ++c) acc[c] = 0.0;
+            int f = 0;
+            for (; f < N - 3; ++f) {
+                const double v = (double)struct_dihedral(xs, f) - mean[f];
+#pragma unroll
+                for (int c = 0; c < DFF_TIC_MAXK; ++c)
+                    if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
+            }
+            for (int i = 0; i < N - 1; ++i)
+                for (int j = i + 1; j < N; ++j, ++f) {
+                    const double v = (double)pwd_dist2(xs, 3 * i, 3 * j) - mean[f];
+#pragma unroll
+                    for (int c = 0; c < DFF_TIC_MAXK; ++c)
+                        if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
+                }
+            double* o = out + (s0 + lane) * k;
+#pragma unroll
+            for (int c = 0; c < DFF_TIC_MAXK; ++c)
+                if (c < k) o[c] = acc[c];
+        }
+    });
+}
+
+// ---- contacts d_ij < cutoff.  LDS: tile | counts (N x N, upper triangle incl. diagonal) | folded map (N x N bytes)
+// The contact bit of pair (i, j) is uniform in (i, j): the wave's count over its 64 frames is one ballot + popcount,
+// added by lane 0 to the workgroup's private LDS counter; the counters go out with one atomic each at the end.
+__global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_contacts_kernel(const float* __restrict__ x, long long n,
+                                                                               int N, float cutoff,
+                                                                               const unsigned char* __restrict__ folded,
+                                                                               int offset, unsigned* __restrict__ counts,
+                                                                               unsigned* __restrict__ mismatch,
+                                                                               unsigned magic, int vec4) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    unsigned* cl = (unsigned*)smem;                                  // N * N
+    unsigned char* fl = (unsigned char*)(cl + N * N);               // N * N (rounded up to 16 bytes)
+    float* tile = (float*)(fl + ((N * N + 15) & ~15));
+    for (int k = threadIdx.x; k < N * N; k += DFF_STRUCT_TILE) {
+        cl[k] = 0u;
+        fl[k] = folded ? folded[k] : (unsigned char)0;
+    }
+    struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
+        unsigned mis = 0;
+        for (int i = 0; i < N; ++i)
+            for (int j = i; j < N; ++j) {
+                const bool c = live && pwd_dist2(xs, 3 * i, 3 * j) < cutoff;
+                const unsigned long long bal = __ballot(c);
+                if (lane == 0 && bal) cl[i * N + j] += (unsigned)__popcll(bal);
+                if (j >= i + offset) mis += (unsigned)(c != (fl[i * N + j] != 0));
+            }
+        if (mismatch && live) mismatch[s0 + lane] = mis;
+    });
+    __syncthreads();
+    for (int k = threadIdx.x; k < N * N; k += DFF_STRUCT_TILE) {
+        const int i = k / N, j = k - i * N;
+        if (j < i) continue;
+        const unsigned v = cl[k];
+        if (v) {
+            atomicAdd(&counts[k], v);
+            if (j != i) atomicAdd(&counts[j * N + i], v);
+        }
+    }
+}

@@ -12,6 +12,8 @@ evaluator raises DffLibraryError.
 """
 from __future__ import annotations
 
+import io
+import json
 import os
 import pickle
 
@@ -110,3 +112,388 @@ class PwdEvaluator:
         if plot_pwds:
             raise NotImplementedError("plotting (evaluators.py:289-349) is outside the hot path")
         return self.js_divergence_pwd(self.gt_hist, all_mol, self.gt_max, self.resolution)
+
+
+# =====================================================================================================
+# Structure metrics of the reference's evaluators (evaluate/evaluators.py: Evaluator :28-111,
+# DihedralEnergiesEvaluator :114-176, TicEvaluator :340-500, RmsdEvaluator :608-679, ContactEvaluator
+# :735-859) on top of the HIP kernels dff_struct_* (csrc/dff_struct.hip).  Per-frame work (RMSD, dihedrals,
+# TIC projections, contacts) runs on the GPU; the histogram and divergence reductions below run in numpy,
+# written as the reference writes them, and are kept as functions of their own so that they can be checked
+# on given per-frame values.  Plotting raises NotImplementedError; without the HIP library the evaluators
+# raise DffLibraryError.
+# =====================================================================================================
+# PDB identifiers of the folded structures (datasets/dataset_utils_empty.py: Molecules) and the RMSD axis of
+# the reference's saved free-energy curves (evaluators.py:624-633)
+PROTEIN_IDS = {"chignolin": "CLN025", "trp_cage": "2JOF", "bba": "1FME", "villin": "2F4K", "protein_g": "NuG2"}
+RMSD_CUTOFF_REF = {"chignolin": 10, "trp_cage": 12, "bba": 14, "villin": 14, "protein_g": 20}
+RMSD_NBINS_REF = 100
+K_BT_IN_KCAL_PER_MOL = 1.380650324e-23 * 300 * 6.02214076e23 / 1000 / 4.184   # evaluators_CGflowmatching.py:11-15
+
+
+# ---- restricted unpickler: the reference's saved references without deeptime and without running code ----
+class _Inert:
+    """Stand-in for a deeptime class in a saved TICA pickle: keeps the pickled state as attributes, runs nothing."""
+
+    def __new__(cls, *args, **kwargs):
+        return object.__new__(cls)
+
+    def __init__(self, *args, **kwargs):
+        pass
+
+    def __setstate__(self, state):
+        if isinstance(state, dict):
+            self.__dict__.update(state)
+        else:
+            self.__dict__["_state"] = state
+
+
+_DEEPTIME_CLASSES = {
+    ("deeptime.decomposition._tica", "TICA"),
+    ("deeptime.decomposition._koopman", "CovarianceKoopmanModel"),
+    ("deeptime.covariance._covariance", "WhiteningTransform"),
+    ("deeptime.covariance._covariance", "CovarianceModel"),
+    ("deeptime.basis._base", "Concatenation"),
+    ("deeptime.basis._monomials", "Identity"),
+}
+_NUMPY_GLOBALS = {"ndarray", "dtype", "_reconstruct", "scalar"}
+
+
+class RestrictedUnpickler(pickle.Unpickler):
+    """Unpickler for the reference's saved references: numpy arrays, dtypes and scalars, and the six deeptime classes
+    of a saved TICA model (mapped to inert stubs).  Any other global is refused."""
+
+    def find_class(self, module, name):
+        if (module, name) in _DEEPTIME_CLASSES:
+            return type(name, (_Inert,), {"__module__": "dff_amd.evaluate.inert"})
+        if module in ("numpy", "numpy.core.multiarray", "numpy._core.multiarray") and name in _NUMPY_GLOBALS:
+            if name in ("ndarray", "dtype"):
+                return getattr(np, name)
+            core = np._core.multiarray if hasattr(np, "_core") else np.core.multiarray
+            return getattr(core, name)
+        raise pickle.UnpicklingError(f"saved reference names a global that is not allowed: {module}.{name}")
+
+
+def restricted_load(path):
+    with open(path, "rb") as f:
+        return RestrictedUnpickler(io.BytesIO(f.read())).load()
+
+
+def load_tica_reference(path, dim=2):
+    """A saved TICA reference as plain arrays: {"mean" (F,), "coeff" (F, dim), "singular_values", "gt_prob",
+    "bin_edges_x", "bin_edges_y"} (+ "cov_00" from a pickle).  `path` is the reference's own
+    saved_TICA_*.pickle (read through RestrictedUnpickler) or an .npz holding those arrays.  The projection is
+    (f - mean) @ coeff, coeff = the instantaneous whitening's sqrt_inv_cov[:, :dim] (kinetic-map scaling)."""
+    if str(path).endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            out = {k: np.asarray(z[k]) for k in z.files}
+        out["coeff"] = out["coeff"][:, :dim]
+        return out
+    tica, gt_prob, edges_x, edges_y = restricted_load(path)
+    model = tica._model
+    white = model._whitening_instantaneous
+    out = {"mean": np.asarray(white.mean, np.float64), "coeff": np.asarray(white.sqrt_inv_cov, np.float64)[:, :dim],
+           "singular_values": np.asarray(model._singular_values, np.float64),
+           "gt_prob": np.asarray(gt_prob), "bin_edges_x": np.asarray(edges_x), "bin_edges_y": np.asarray(edges_y)}
+    cov = getattr(model, "_cov", None)
+    if cov is not None and hasattr(cov, "_cov_00"):
+        out["cov_00"] = np.asarray(cov._cov_00, np.float64)
+    return out
+
+
+# ---- host reductions, as the reference writes them ----
+def get_prob(tors_data, n_bins=61):
+    """evaluators_CGflowmatching.py:39-49: phi / psi histogram on linspace(-pi, pi, n_bins), normalised to sum 1."""
+    bin_edges = np.linspace(-np.pi, np.pi, n_bins)
+    hist, _, _ = np.histogram2d(tors_data[:, 0], tors_data[:, 1], bins=bin_edges, density=True)
+    return hist / hist.sum()
+
+
+def mse_free_energy(density1, density2):
+    """evaluators_CGflowmatching.py:19-28 (mse)."""
+    with np.errstate(divide="ignore"):
+        U1 = K_BT_IN_KCAL_PER_MOL * np.log(density1)
+        U2 = K_BT_IN_KCAL_PER_MOL * np.log(density2)
+    U1 = np.where(np.isinf(U1), np.nan, U1)
+    U2 = np.where(np.isinf(U2), np.nan, U2)
+    count = np.sum(np.isfinite(U1 - U2))
+    return np.nansum(np.square(U1 - U2)) / count
+
+
+def kl_div(density1, density2):
+    """evaluators_CGflowmatching.py:52-60."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = density2 / density1
+    ratio[density1 == 0] = 1
+    ratio[density2 == 0] = 1
+    return -np.nansum(density1 * np.log(ratio))
+
+
+def dihedral_scores(probs, gt_probs):
+    """(mse, js, kl_1, kl_2) of DihedralEnergiesEvaluator.eval (evaluators.py:153-157)."""
+    return (mse_free_energy(probs, gt_probs), js_divergence(probs, gt_probs), kl_div(probs, gt_probs),
+            kl_div(gt_probs, probs))
+
+
+def tic_js(proj, gt_prob, bin_edges_x, bin_edges_y):
+    """TicEvaluator.eval's reduction (evaluators.py:463-470) of the (n, 2) projections: (js, prob_samp)."""
+    prob_samp, _, _ = np.histogram2d(proj[:, 0], proj[:, 1], bins=[bin_edges_x, bin_edges_y], density=True)
+    return js_divergence(gt_prob.flatten(), prob_samp.flatten()), prob_samp
+
+
+def rmsd_curve(rmsd, nbins, cutoff=None):
+    """RmsdEvaluator.eval's free-energy curve (evaluators.py:664-676) of per-frame RMSDs (NaN = invalid frame)."""
+    rmsd = np.asarray(rmsd, np.float64)
+    if cutoff is None:
+        cutoff = rmsd[~np.isnan(rmsd)].max()
+    h, bin_edges = np.histogram(rmsd, bins=nbins, range=[0, cutoff], density=True)
+    out = {"bin_mids": (bin_edges[:-1] + bin_edges[1:]) / 2.0}
+    with np.errstate(divide="ignore"):
+        out["energies"] = -np.log(h)
+    return out
+
+
+def contact_bce_from_mismatch(mismatch, n_pairs):
+    """Per-frame binary cross-entropy of _eval_bce_dynamics (evaluators.py:836-845) from mismatch counts, and its
+    mean: contacts are 0 / 1 and torch clamps log at -100, so a mismatch costs exactly 100 and the float32 mean over
+    the pairs is float32(100 m) / float32(n_pairs)."""
+    m = torch.as_tensor(np.asarray(mismatch)).to(torch.float32)
+    bce = (m * 100.0) / float(n_pairs)
+    return bce.numpy(), bce.mean()
+
+
+# ---- folded structures ----
+_SOLVENT = {"HOH", "WAT", "SOL", "TIP", "TIP3", "NA", "CL", "K", "CA", "MG", "ZN", "SO4", "NA+", "CL-"}
+
+
+def folded_ca(pdb_path, mol_name):
+    """C-alpha coordinates (Angstrom, float64 (N, 3)) of a folded PDB by process_pdb's rule (evaluators.py:862-872):
+    atoms named CA of the first model, solvent and ions removed; protein G keeps C-alphas [5:61]."""
+    xyz = []
+    with open(pdb_path) as f:
+        for line in f:
+            if line.startswith("ENDMDL"):
+                break
+            if not line.startswith(("ATOM  ", "HETATM")):
+                continue
+            if line[12:16].strip() != "CA" or line[17:21].strip() in _SOLVENT or line[16] not in " A":
+                continue
+            xyz.append([float(line[30:38]), float(line[38:46]), float(line[46:54])])
+    xyz = np.asarray(xyz, np.float64)
+    if mol_name.upper() == "PROTEIN_G":
+        xyz = xyz[5:61]
+    return xyz
+
+
+def _folded_coords(folded, mol_name):
+    if isinstance(folded, (str, os.PathLike)):
+        return folded_ca(folded, mol_name)
+    return np.asarray(torch.as_tensor(folded).cpu(), np.float64).reshape(-1, 3)
+
+
+def _frames(x, device):
+    x = torch.as_tensor(x)
+    if x.dim() != 3 or x.shape[-1] != 3:
+        raise ValueError("structures must be (n, n_beads, 3)")
+    return x.to(device=device, dtype=torch.float32).contiguous()
+
+
+class DihedralEnergiesEvaluator:
+    """Drop-in for evaluate.evaluators.DihedralEnergiesEvaluator (alanine dipeptide phi / psi free energy).
+    `topology` is unused: the quadruples are the reference's [[0, 1, 2, 3], [1, 2, 3, 4]]."""
+
+    def __init__(self, val_data, topology=None, plots_folder=None, n_bins=61,
+                 saved_ref="./saved_references/saved_dih_probs_ala2_testset.pickle", *, device="cuda:0"):
+        self.topology = topology
+        self.plots_folder = plots_folder
+        self.n_bins = n_bins
+        self.device = torch.device(device)
+        binding.load_library()
+        if os.path.exists(saved_ref):
+            self.gt_probs = np.asarray(restricted_load(saved_ref))
+        else:
+            self.gt_probs = get_prob(self.torsions(val_data), n_bins=self.n_bins)
+            d = os.path.dirname(saved_ref)
+            if d == "" or os.path.isdir(d):
+                with open(saved_ref, "wb") as f:
+                    pickle.dump(self.gt_probs, f)
+
+    def torsions(self, xyz):
+        """(n, 2) phi / psi in radians (get_torsions, evaluators_CGflowmatching.py:30-36), on the GPU."""
+        return binding.struct_dihedrals(_frames(xyz, self.device))[:, :2].cpu().numpy()
+
+    def eval(self, all_mol, plot_freeE=False, milestone=0, plot_title="Ramachandran plot", save_plot=True):
+        if plot_freeE:
+            raise NotImplementedError("plotting (evaluators.py:159-175) is outside the hot path")
+        probs = get_prob(self.torsions(all_mol), n_bins=self.n_bins)
+        return dihedral_scores(probs, self.gt_probs)
+
+
+class TicEvaluator:
+    """Drop-in for evaluate.evaluators.TicEvaluator with a saved reference (the reference's own
+    saved_TICA_*.pickle, read without deeptime, or an .npz of its arrays).  eval() returns (tic_js, None)."""
+
+    def __init__(self, val_data, mol_name, eval_folder=None, data_folder=None, folded_pdb_folder="./datasets/folded_pdbs",
+                 bins=101, saved_ref="none", evalset="testset", *, device="cuda:0"):
+        self.mol_name = mol_name
+        self.plots_folder = eval_folder
+        self.bins = bins
+        self.device = torch.device(device)
+        binding.load_library()
+        if saved_ref == "none":
+            saved_ref = f"./saved_references/saved_TICA_{mol_name.upper()}_{evalset}.pickle"
+        if not os.path.exists(saved_ref):
+            raise NotImplementedError(
+                f"no saved TICA reference at {saved_ref}: fitting a new TICA model (evaluators.py:384-410) needs the "
+                f"training dataset and deeptime and is not supported; pass the reference's saved_TICA_*.pickle or an "
+                f".npz with mean, coeff, gt_prob, bin_edges_x, bin_edges_y")
+        ref = load_tica_reference(saved_ref)
+        self.mean, self.coeff = ref["mean"], ref["coeff"]
+        self.gt_prob, self.bin_edges_x, self.bin_edges_y = ref["gt_prob"], ref["bin_edges_x"], ref["bin_edges_y"]
+        self.bin_mids_x = (self.bin_edges_x[1:] + self.bin_edges_x[:-1]) / 2
+        self.bin_mids_y = (self.bin_edges_y[1:] + self.bin_edges_y[:-1]) / 2
+        self.bin_x_folded = self.bin_y_folded = None
+        protid = PROTEIN_IDS.get(mol_name.lower())
+        folded_pdb = f"{folded_pdb_folder}/{protid}.pdb"
+        if protid is not None and os.path.exists(folded_pdb):      # the folded structure's bins (plots only)
+            ft = self.transform(folded_ca(folded_pdb, mol_name)[None])[0]
+            self.bin_x_folded = np.argmin(abs(self.bin_mids_x - ft[0]))
+            self.bin_y_folded = np.argmin(abs(self.bin_mids_y - ft[1]))
+
+    def transform(self, xyz):
+        """(n, dim) float64 TIC projections of the structures xyz (n, N, 3) in Angstrom, on the GPU."""
+        return binding.struct_tic(_frames(xyz, self.device), self.mean, self.coeff).cpu().numpy()
+
+    def eval(self, xyz_samples, title="", plot_tic=False, save_object=False, path=None, cmap="OrRd", gradient=True,
+             steps=3, linewidth=2):
+        if plot_tic:
+            raise NotImplementedError("plotting (evaluators.py:472-500) is outside the hot path")
+        js, prob_samp = tic_js(self.transform(xyz_samples), self.gt_prob, self.bin_edges_x, self.bin_edges_y)
+        if save_object:
+            for name, arr in (("prob_samp.npy", prob_samp), ("bin_mids_x.npy", self.bin_mids_x),
+                              ("bin_mids_y.npy", self.bin_mids_y)):
+                with open(name, "wb") as f:
+                    np.save(f, arr)
+        return js, None
+
+
+class RmsdEvaluator:
+    """Drop-in for evaluate.evaluators.RmsdEvaluator.  `folded_pdb` is a PDB path (C-alphas by process_pdb's rule)
+    or the folded C-alpha coordinates (N, 3) in Angstrom."""
+
+    def __init__(self, mol_name, folded_pdb, eval_folder=None, *, saved_ref_dir="./saved_references", device="cuda:0"):
+        self.plots_folder = eval_folder
+        self.folded = _folded_coords(folded_pdb, mol_name)
+        self.plot_dict = {}
+        self.mol_name = mol_name
+        self.device = torch.device(device)
+        binding.load_library()
+        self.saved_ref = os.path.join(saved_ref_dir, f"saved_rmsd_{mol_name.upper()}_reference_total.pickle")
+        self.cutoff_dict_ref = dict(RMSD_CUTOFF_REF)
+        self.cutoff_ref = self.cutoff_dict_ref[mol_name.lower()]
+        self.nbins_ref = RMSD_NBINS_REF
+
+    def rmsd(self, xyz):
+        """(n,) float64 C-alpha RMSD (Angstrom) to the folded structure, NaN for frames with non-finite coordinates."""
+        x = _frames(xyz, self.device)
+        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float()).cpu().numpy().astype(np.float64)
+
+    def eval(self, method, xyz, nbins, cutoff=None, save_dynamics=False):
+        if method == "Reference" and os.path.exists(self.saved_ref):
+            assert nbins == self.nbins_ref and cutoff == self.cutoff_ref, \
+                f"Reference data only exists for nbins={self.nbins_ref} and cutoff={self.cutoff_ref}"
+            self.plot_dict[method] = dict(restricted_load(self.saved_ref))
+            return
+        rmsd = self.rmsd(xyz)
+        self.plot_dict[method] = {}
+        if save_dynamics:
+            self.plot_dict[method]["rmsd"] = rmsd
+        self.plot_dict[method].update(rmsd_curve(rmsd, nbins, cutoff))
+        if method == "Reference" and os.path.isdir(os.path.dirname(self.saved_ref) or "."):
+            with open(self.saved_ref, "wb") as f:
+                pickle.dump(self.plot_dict[method], f)
+
+    def _plot_rmsd(self, *args, **kwargs):
+        raise NotImplementedError("plotting (evaluators.py:681-708) is outside the hot path")
+
+
+class ContactEvaluator:
+    """Drop-in for evaluate.evaluators.ContactEvaluator's numbers: the normalised contact count (:794-806) and the
+    contact BCE to the folded structure (:829-859), without the plots."""
+
+    def __init__(self, mol_name, folded_pdb, eval_folder=None, contact_cutoff=10, *, device="cuda:0"):
+        self.mol_name = mol_name
+        self.contact_cutoff = contact_cutoff
+        self.plots_folder = eval_folder
+        self.device = torch.device(device)
+        binding.load_library()
+        self.folded = torch.from_numpy(_folded_coords(folded_pdb, mol_name)).float()
+        self.pwd_folded = torch.norm(self.folded[:, None, :] - self.folded[None, :, :], dim=-1)
+        self.contacts_folded = self.pwd_folded < self.contact_cutoff
+
+    def contact_counts(self, xyz, offset=3):
+        """(counts (N, N) int64 over frames, mismatch (n,) int64 over pairs j >= i + offset), on the GPU."""
+        counts, mism = binding.struct_contacts(_frames(xyz, self.device), self.contact_cutoff,
+                                               self.contacts_folded.to(torch.uint8), offset)
+        return counts.cpu(), mism.cpu()
+
+    def normalized_contact_count(self, xyz):
+        """norm_sum = contacts_samp.sum(dim=0) / len(contacts_samp), float32 (N, N)."""
+        x = _frames(xyz, self.device)
+        counts, _ = binding.struct_contacts(x, self.contact_cutoff)
+        return counts.cpu() / len(x)
+
+    def contact_bce(self, xyz):
+        """(per-frame BCE float32 (n,), its mean) of _eval_bce_dynamics (offset 3)."""
+        N = self.contacts_folded.shape[-1]
+        _, mism = self.contact_counts(xyz, 3)
+        return contact_bce_from_mismatch(mism.numpy(), binding.pwd_num_pairs(N, 3))
+
+
+class Evaluator:
+    """Drop-in for evaluate.evaluators.Evaluator: Dihedral JS (alanine), TIC JS (every protein but protein G) and
+    PWD JS (all but protein G), composed as the reference composes them.  ref_data may be None when the saved
+    references exist (found under `saved_ref_dir`).  The reference hands `evalsetname` to its TIC and PWD
+    evaluators, which name it `evalset`; here it is passed on as evalset, "" meaning their default "testset"."""
+
+    def __init__(self, ref_data, topology=None, mol_name="alanine", eval_folder=None,
+                 folded_pdb_folder="./datasets/folded_pdbs", data_folder="./data", evalsetname="", *,
+                 saved_ref_dir="./saved_references", device="cuda:0"):
+        if ref_data is not None and not isinstance(ref_data, torch.Tensor):
+            ref_data = ref_data[:][0]
+        self.ref_data = ref_data
+        self.topology = topology
+        self.eval_folder = eval_folder
+        self.folded_pdb_folder = folded_pdb_folder
+        self.mol_name = mol_name
+        evalset = evalsetname or "testset"
+        if "alanine" in mol_name:
+            self.dihedral_evaluator = DihedralEnergiesEvaluator(
+                ref_data, topology, eval_folder,
+                saved_ref=os.path.join(saved_ref_dir, "saved_dih_probs_ala2_testset.pickle"), device=device)
+        elif "protein_g" != mol_name.lower():
+            tic_ref = os.path.join(saved_ref_dir, f"saved_TICA_{mol_name.upper()}_{evalset}")
+            tic_ref = tic_ref + ".npz" if os.path.exists(tic_ref + ".npz") else tic_ref + ".pickle"
+            self.tic = TicEvaluator(ref_data, mol_name, eval_folder=eval_folder, data_folder=data_folder,
+                                    folded_pdb_folder=folded_pdb_folder, saved_ref=tic_ref, evalset=evalset,
+                                    device=device)
+        if "protein_g" != mol_name.lower():
+            pwd_ref = os.path.join(saved_ref_dir, f"saved_pwd_{mol_name.upper()}_{evalset}_offset_0.pickle")
+            if ref_data is None and not os.path.exists(pwd_ref):
+                raise ValueError(f"PWD evaluation needs ref_data or a saved reference at {pwd_ref}")
+            self.pwd_evaluator = PwdEvaluator(ref_data, eval_folder, mol_name, saved_ref=pwd_ref, evalset=evalset,
+                                              device=device)
+
+    def eval(self, sampled_mol, milestone=0, save_plots=False):
+        dict_results = {}
+        if "alanine" in self.mol_name:
+            _, dihedral_js, _, _ = self.dihedral_evaluator.eval(sampled_mol, save_plots, milestone)
+            dict_results["Dihedral JS"] = float(dihedral_js)
+        elif "protein_g" != self.mol_name.lower():
+            dict_results["TIC JS"] = float(self.tic.eval(sampled_mol, title=f"tic_{milestone}", plot_tic=save_plots)[0])
+        if "protein_g" != self.mol_name.lower():
+            dict_results["PWD JS"] = float(self.pwd_evaluator.eval(sampled_mol))
+        if self.eval_folder is not None:
+            with open(os.path.join(self.eval_folder, f"results-{milestone}.json"), "w") as f:
+                json.dump(dict_results, f)
+        return dict_results
