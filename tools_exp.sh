@@ -19,7 +19,6 @@ if [ "$cmd" = build ]; then
     # the stage ticks need the host half built with them too
     printf '#define DFF_BUILD_FLAGS "%s"\n' "$(printf '%s' "$flags" | sed 's/[\\"]/\\&/g')" > $d/dff_build_info.h
     pf=""; case "$flags" in *DFF_PROF=1*) pf="-DDFF_PROF=1";; esac
-    case "$flags" in *DFF_EXPERIMENT*) pf="$pf -DDFF_EXPERIMENT";; esac
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result $pf -DDFF_SRC_SHA=exp-$name -include $d/dff_build_info.h -c $SRC/dff_host.hip -o $d/dff_host.o
     host=$d/dff_host.o
     hipcc --offload-arch=gfx950 -shared -fPIC build/obj/dff_kernels.o $objs $host -o $d/libdff_amd.so

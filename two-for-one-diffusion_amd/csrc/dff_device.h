@@ -9,7 +9,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define DEVI __device__ __forceinline__
 
 #define DFF_QKVW 208    // stash row of one head: [q_ext 80 | k 64 | v 64]
-// Row padding (bf16 elements) of every split A operand in LDS.  A row stride of 8 dwords mod 64 makes the ds_read_b128
+// Row padding (16-bit elements) of every split A operand in LDS.  A row stride of 8 dwords mod 64 makes the ds_read_b128
 // fragment reads conflict-free: the 16 lanes of a read group are rows {0-3, 12-15} of one 8-element k-group and rows
 // {4-11} of the next, i.e. bank slots (2 row + kg) mod 16 = all even | all odd.  (8 elements = 4 dwords mod 64 put row 11
 // of k-group 1 on row 12 of k-group 0: 41 % conflict cycles in profiles/r02/villin.)
@@ -28,21 +28,18 @@ typedef f32x4 __attribute__((address_space(1))) gf32x4;
 // instead of a 64-bit per-lane pointer per stream (a VGPR pair each, v_mad_u64_u32 / v_lshl_add_u64 / quarter-rate
 // v_mul_lo_u32 per load, 64-bit VALU adds wherever consecutive loads are further apart than the 4 KB immediate reaches;
 // 303 of the 311 wide loads of villin's kernel, 21 % of its dynamic VALU was INT32).  Writing the address as
-// (uniform base + uniform index)[32-bit lane] is not enough (DFF_SADDR=1): the compiler merges base, index and lane into one
-// vector pointer and offsets that.  DFF_SADDR=0: the per-lane pointers of rounds 1-4.
-#ifndef DFF_SADDR
-#define DFF_SADDR 2
-#endif
+// (uniform base + uniform index)[32-bit lane] is not enough: the compiler merges base, index and lane into one vector pointer
+// and offsets that.
 template <class T> struct WVal;
 template <> struct WVal<f32x4 __attribute__((address_space(1)))> { typedef f32x4 type; };
 typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 template <> struct WVal<u32x4_ __attribute__((address_space(1)))> { typedef u32x4_ type; };
-// MODE: 2 buffer, 1 saddr-shaped pointer arithmetic, 0 per-lane pointer.  DFF_WMODE(MT): what a GEMM core with MT row tiles uses
-// -- measured (round 5, us / step, buffer vs per-lane pointers): BBA's shape (96,2,2) 281 vs 291.5, trp-cage's (128,2,2) 300.5
-// vs 304.8, villin's (128,3,1) 487-495 vs 487-490, protein G's (128,4,1) 469-472 vs 465-467: the shapes with three and four
-// row tiles keep the per-lane pointers (their cores hold more streams' worth of SGPR offsets than they have SGPRs for).
-#define DFF_WMODE(MT) (DFF_SADDR == 2 ? ((MT) <= 2 ? 2 : 0) : DFF_SADDR)
-template <class GT, int MODE = DFF_SADDR>
+// MODE: 2 buffer, 0 per-lane pointer.  dff_wmode(MT): what a GEMM core with MT row tiles uses -- measured (round 5, us / step,
+// buffer vs per-lane pointers): BBA's shape (96,2,2) 281 vs 291.5, trp-cage's (128,2,2) 300.5 vs 304.8, villin's (128,3,1)
+// 487-495 vs 487-490, protein G's (128,4,1) 469-472 vs 465-467: the shapes with three and four row tiles keep the per-lane
+// pointers (their cores hold more streams' worth of SGPR offsets than they have SGPRs for).
+constexpr int dff_wmode(int mt) { return mt <= 2 ? 2 : 0; }
+template <class GT, int MODE>
 struct WPtr;
 template <class GT>
 struct WPtr<GT, 2> {
@@ -55,55 +52,38 @@ struct WPtr<GT, 2> {
     }
     DEVI float first_float(size_t i) const { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, lob, (unsigned)i * 16u, 0)); }
 };
-template <class GT, int MODE>
-struct WPtr {
+template <class GT>
+struct WPtr<GT, 0> {
     typedef typename WVal<GT>::type V;
     const GT* base;   // wave-uniform
     unsigned lo;      // this lane's element offset (< 64: cannot wrap)
     DEVI WPtr(const GT* b, unsigned lane) : base(b), lo(lane) {}
-    DEVI V operator[](size_t i) const {
-        if constexpr (MODE == 1) return (base + i)[lo];
-        else return (base + lo)[i];
-    }
+    DEVI V operator[](size_t i) const { return (base + lo)[i]; }
     DEVI float first_float(size_t i) const { return *(const gfloat*)(base + i + lo); }
 };
 // Cache policy of the stash traffic that is written once and read once (per head: q_ext | k | v rows, P, gelu'(h_pre) out; the
-// backward's head reload and its gelu' rows in).  POL bit 0: non-temporal LOADS, bit 1: non-temporal STORES.  Round 5, us / step
-// (sites: 1 head reload, 2 q|k|v out, 4 P out, 8 gelu' out, 16 gelu' in; DFF_STASH_SITES forces a site mask):
+// backward's head reload and its gelu' rows in).  Round 5, us / step (sites: 1 head reload, 2 q|k|v out, 4 P out, 8 gelu' out,
+// 16 gelu' in):
 //   villin (three row tiles, 1.3 MB of stash per protein and step)   none 493-504 | 1: 478 | 1+16: 477.6 | 1+2 / 1+4 / 1+8: 480-481 | all stores too: 488.5
 //   protein G, two workgroups per protein (four row tiles)           none 482-488 | 1: 473-475 | 1+16: 426-430 | 1+2: 428.5 | 1+4: 428-433 | 1+2+4+8: 432 | all: 434
 //   protein G at 256 per GPU (one workgroup per protein)             none 818-825 | 1+2+4+8: 745 | all: 748
 //   trp-cage / BBA (two row tiles), loads | stores non-temporal: +1 % | +2-3.5 %  -> default policy
 // A stash line that is read exactly once should not stay in the XCD's 4 MB L2 next to the weight images every workgroup
 // streams: with three / four row tiles the resident workgroups' stash outgrows it (L2 hit rate 0.87 / 0.76 in profiles/r04).
-// Both load sites go non-temporal there, the stores keep the default policy (they are what the loads then find in the MALL).
-// DFF_STASH_NT >= 0 forces one policy everywhere (0 = default, 1 = loads, 2 = stores, 3 = both).  The <= 16-row kernels keep
-// the default (round 2: -3 % with both non-temporal; the headline variant has no stash traffic in the sampling loops at all).
-#ifndef DFF_STASH_NT
-#define DFF_STASH_NT -1
-#endif
-#define DFF_STASH_POL(MT) (DFF_STASH_NT >= 0 ? DFF_STASH_NT : ((MT) >= 3 ? 1 : 0))
-// per-site form for experiments: DFF_STASH_SITES = bit mask of the sites that go non-temporal (whatever MT) --
-//   1 head reload (q_ext | k | v | P in), 2 q_ext | k | v out, 4 P out, 8 gelu' out, 16 gelu' in;  < 0: DFF_STASH_POL(MT) at every site
-#ifndef DFF_STASH_SITES
-#define DFF_STASH_SITES -1
-#endif
-#define DFF_SITE_LD(MT, bit) (DFF_STASH_SITES >= 0 ? ((DFF_STASH_SITES & (bit)) ? 1 : 0) : (DFF_STASH_POL(MT) & 1))
-#define DFF_SITE_ST(MT, bit) (DFF_STASH_SITES >= 0 ? ((DFF_STASH_SITES & (bit)) ? 2 : 0) : (DFF_STASH_POL(MT) & 2))
-template <int POL = 0> DEVI void st_ntg(gfloat* p, float v) {
-    if constexpr (POL & 2) __builtin_nontemporal_store(v, p); else *p = v;
-}
-template <int POL = 0> DEVI float ld_ntg(const gfloat* p) { if constexpr (POL & 1) return __builtin_nontemporal_load(p); else return *p; }
-template <int POL = 0> DEVI f32x4 ld_ntg4(const gfloat* p) {
-    if constexpr (POL & 1) return __builtin_nontemporal_load((const gf32x4*)p); else return *(const gf32x4*)p;
-}
-template <int POL = 0> DEVI void st_ntg4(gfloat* p, const f32x4 v) {
-    if constexpr (POL & 2) __builtin_nontemporal_store(v, (gf32x4*)p); else *(gf32x4*)p = v;
+// Both load sites go non-temporal there (dff_stash_ntl(MT)); the stores keep the default policy (they are what the loads then
+// find in the MALL).  The <= 16-row kernels keep the default (round 2: -3 % with both non-temporal; the headline variant has no
+// stash traffic in the sampling loops at all).
+constexpr bool dff_stash_ntl(int mt) { return mt >= 3; }
+DEVI void st_ntg(gfloat* p, float v) { *p = v; }
+DEVI void st_ntg4(gfloat* p, const f32x4 v) { *(gf32x4*)p = v; }
+template <bool NT = false> DEVI float ld_ntg(const gfloat* p) { if constexpr (NT) return __builtin_nontemporal_load(p); else return *p; }
+template <bool NT = false> DEVI f32x4 ld_ntg4(const gfloat* p) {
+    if constexpr (NT) return __builtin_nontemporal_load((const gf32x4*)p); else return *(const gf32x4*)p;
 }
 // four consecutive floats (16-byte aligned) into a scalar aux array of an epilogue
-template <int POL = 0>
+template <bool NT = false>
 DEVI void ld4_aux(float* aux, const gfloat* p) {
-    const f32x4 v = ld_ntg4<POL>(p);
+    const f32x4 v = ld_ntg4<NT>(p);
     aux[0] = v[0]; aux[1] = v[1]; aux[2] = v[2]; aux[3] = v[3];
 }
 
@@ -149,9 +129,6 @@ __host__ __device__ inline StashLayout dff_stash_layout(int N, int G, int H, int
 // Head-group region Rg: four (R x LQ) buffers Q_ext | K_ext | V_ext | G_ext, a head being 80
 // columns [64 | 16 extension]; Pbuf / dSbuf: per head of the group a (16MT x PL) tile array.
 // ------------------------------------------------------------------------------------------
-#ifndef DFF_KVSPLIT
-#define DFF_KVSPLIT 1
-#endif
 template <int H, int MT, int HGS, bool SPILL>
 struct LdsLayout {
     static constexpr int LH = H + 4;
@@ -160,18 +137,18 @@ struct LdsLayout {
     static constexpr int FC = (F % 256 == 0) ? 256 : 128;
     static constexpr int LF = FC + 4;
     static constexpr int NREG = MT < 4 ? 5 : 4;   // a fifth head-group buffer (backward: dQ_ext) where LDS allows
-    static constexpr int LHS2 = (H + DFF_SPAD) / 2;   // dwords per row of a bf16 piece of the split A operand (SPW variants)
-    // SPW variants with the fifth buffer: dK / dV leave their producer as bf16 pieces (co_dv_dk), [h | m] in place of the
-    // fp32 row, dK's l pieces in the extension columns of the R1 / R2 rows, dV's in `lsplit` (LSV dwords per row) where the
-    // LDS has room for it (DFF_KVSPLIT, VSP)
-    static constexpr bool KVS = NREG == 5 && DFF_KVSPLIT;
+    static constexpr int LHS2 = (H + DFF_SPAD) / 2;   // dwords per row of a 16-bit piece of the split A operand (SPW variants)
+    // SPW variants with the fifth buffer: dK / dV leave their producer as fp16 pieces (co_dv_dk), [h | l'] in place of the
+    // fp32 row -- dV where the LDS has room for the `lsplit` area the three-piece format of round 4 kept its l pieces in (VSP;
+    // the area is still allocated: the launch's LDS size stays what it was)
+    static constexpr bool KVS = NREG == 5;
     static constexpr bool VSP = KVS;   // (round 4: also BBA's shape (96,2,2) -- the fp32 abuf the split engine no longer has paid for the area)
     static constexpr int LSV = 32 * HGS + 4;
     // P / dS tile arrays.  Default: 16 MT rows x (16 MT + 4) floats per head.  TIGHT (split engine at four row tiles, i.e.
     // protein G: 56 rows; round 4): the workgroup's ALLOCATED rows only, 16 MT - 4 = 60 floats each -- columns 60..63 do not
     // exist (the phases that would touch them are guarded: they hold pad beads, exact zeros) -- and the regions are ordered
     //   [... | asplit | Rg = R0 R1 R2 R3 | dSbuf | Pbuf]
-    // so that what outgrows R3 / Rg in this variant continues into buffers that are idle then: the bf16 pieces of o (forward,
+    // so that what outgrows R3 / Rg in this variant continues into buffers that are idle then: the pieces of o (forward,
     // 3 x R x 40 dwords from R3 on: dSbuf is idle) and of the FFN hidden chunk (3 x R x 136 dwords from R0 on: dSbuf and Pbuf
     // are idle).  That, and the fp32 abuf the split engine no longer has, is what lets the split A operand (48 KB at 56
     // rows) into the 160 KB next to four head buffers.
@@ -196,7 +173,7 @@ struct LdsLayout {
         rsc = o;   if (spw) o += 64;           // fp16 engine: inverse row scales of the backward chain in flight (round 5)
         dxw = o;   o += DFF_NWAVES * R * 4;   // per-wave partial dE/dx (summed once per step)
         m12 = o;   if (!tight) o += HGS * R * 4;   // GEN: reloaded [m1 | m2] of the head group (backward); no GEN variant is TIGHT
-        abuf = o;  if (!spw) o += R * LH;   // (split engine: the row stages write the bf16 pieces themselves, no fp32 copy)
+        abuf = o;  if (!spw) o += R * LH;   // (split engine: the row stages write the fp16 pieces themselves, no fp32 copy)
         resbuf = o; if (!SPILL) o += R * LH;
         if (tight) {
             asplit = o; o += 3u * R * LHS2;
@@ -217,9 +194,9 @@ struct LdsLayout {
         if (R * LH > rsz) rsz = R * LH;
         o += rsz + 64;  // slack: clamped A-fragment reads never leave the allocation
         asplit = o;
-        if (spw) o += 3u * R * LHS2;   // [h | m | l] bf16 pieces of abuf (R x H each, row stride H + 8)
+        if (spw) o += 3u * R * LHS2;   // pieces of abuf (R x H each, row stride H + 8; [h | l'] + the third piece's area of round 4)
         lsplit = o;
-        if (spw && VSP) o += 2 * R * LSV;   // l pieces of dV, then of dQ (co_ds; round 4)
+        if (spw && VSP) o += 2 * R * LSV;   // (round 4: l pieces of dV, then of dQ; unused since the fp16 engine, kept as allocated)
         junk = o;  o += 64;                    // landing pad of the L2 warm-up loads (l2_touch)
         total = o;
     }
@@ -286,37 +263,13 @@ DEVI void gelu_both(float x, float& g, float& gp) {
 // scale: they sit on serial row-stage paths and in the softmax of every head, where libm's expf / IEEE division / sqrtf
 // cost 10-25 instructions apiece.  The extra error is of the order of one fp32 rounding (forces vs the reference's
 // float64 run stay within the tolerances of tests/test_gpu_parity.py).
-#ifndef DFF_LIBM_ROWMATH
-#define DFF_LIBM_ROWMATH 0   // 1: expf / division / sqrtf as in round 1
-#endif
-DEVI float fast_exp(float x) {   // e^x
-#if DFF_LIBM_ROWMATH
-    return expf(x);
-#else
-    return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
-#endif
-}
-DEVI float fast_rcp(float x) {
-#if DFF_LIBM_ROWMATH
-    return 1.0f / x;
-#else
-    return __builtin_amdgcn_rcpf(x);
-#endif
-}
-DEVI float fast_rsqrt(float x) {
-#if DFF_LIBM_ROWMATH
-    return 1.0f / sqrtf(x);
-#else
-    return __builtin_amdgcn_rsqf(x);
-#endif
-}
+DEVI float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }   // e^x
+DEVI float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+DEVI float fast_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
 DEVI float sigmoid_f(float z) { return fast_rcp(1.0f + fast_exp(-z)); }
 DEVI void st_nt(float* p, float v) { __builtin_nontemporal_store(v, p); }
 DEVI float ld_nt(const float* p) { return __builtin_nontemporal_load(p); }
 
-#ifndef DFF_LIBM_NORMAL
-#define DFF_LIBM_NORMAL 0   // 1: logf / sqrtf / sinf / cosf of libm (rounds 1-2)
-#endif
 // Philox4x32-10 (Salmon et al. 2011), counter-based: the same (key, counter) always gives the
 // same 4 words, so a trajectory's noise does not depend on how the batch is sharded.
 DEVI void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
@@ -342,39 +295,27 @@ DEVI float philox_normal(uint64_t seed, uint64_t item, uint64_t step, uint32_t b
     const float inv = 2.3283064365386963e-10f;  // 2^-32
     const float u0 = ((float)w[(c >> 1) * 2] + 0.5f) * inv;          // (0,1]
     const float u1 = ((float)w[(c >> 1) * 2 + 1] + 0.5f) * inv;
-#if DFF_LIBM_NORMAL
-    const float r = sqrtf(-2.0f * logf(u0));
-    const float th = 6.28318530717958647692f * u1;
-    return (c & 1) ? r * sinf(th) : r * cosf(th);
-#else
     // Box-Muller on the hardware transcendentals: v_log_f32 (log2), v_sqrt_f32, v_sin_f32 / v_cos_f32 (argument in
     // revolutions: u1 itself) -- ~10 instructions instead of ~200 for libm's logf / sinf / cosf with their range reductions.
     // The draws are standard normals to ~1e-6 either way; every kernel draws through this one function, so trajectories stay
     // independent of sharding, chunking and kernel variant.
     const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u0));   // sqrt(-2 ln u0)
     return r * ((c & 1) ? __builtin_amdgcn_sinf(u1) : __builtin_amdgcn_cosf(u1));
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
-// SPW variants (opt-in, DFF_SPLIT_BF16=1): the K = H weight GEMMs on the bf16 matrix pipe at fp32 accuracy.
-// An fp32 value is the exact sum of three bf16 pieces (truncation split: h = top 16 bits, r = a - h exactly, ...);
-// a.b ~ ah.bh + (am.bh + ah.bm) + (al.bh + ah.bl + am.bm) drops only terms of order 2^-24 (tools_ubench/split_bf16.hip:
-// error vs fp64 <= that of v_mfma_f32_16x16x4_f32).  The weights are split on the host (dff_host.hip pack_b_split),
-// the activations by split_rows once per GEMM input; six v_mfma_f32_16x16x32_bf16 (16 cycles each, and they leave the
-// vector port free: tools_ubench/overlap3.hip) replace eight v_mfma_f32_16x16x4_f32 (32 cycles each).
+// SPW variants (DFF_SPLIT_BF16=1 selects them; the name is historical): the weight GEMMs on the fp16 matrix pipe at fp32
+// accuracy.  The weights are split on the host (dff_host.hip pack_b_split_f16 / pack_units_f16), the activations by the row
+// stages or by the consuming wave; three v_mfma_f32_16x16x32_f16 (16 cycles each, and they leave the vector port free:
+// tools_ubench/overlap3.hip) replace eight v_mfma_f32_16x16x4_f32 (32 cycles each).
 // ------------------------------------------------------------------------------------------
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) unsigned lu32;
 typedef __attribute__((address_space(3))) u32x4 lu32x4;
 typedef __attribute__((address_space(3))) unsigned short lu16;
 typedef __attribute__((address_space(1))) u32x4 gu32x4;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x2 lu32x2;
-DEVI f32x4 mfma_bf16(const u32x4 a, const u32x4 b, const f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // ---- two-piece fp16 split (round 5): x = h + l' / 2048 with h = RN_f16(x), l' = RN_f16((x - h) 2048), both rounded to nearest
 // (split2h), and  a.b ~ ah.bh + (ah.bl' + al'.bh) / 2048  -- THREE v_mfma_f32_16x16x32_f16 instead of six bf16 ones and 4 instead
@@ -402,7 +343,7 @@ DEVI void split2h(float e0, float e1, unsigned& h, unsigned& l) {
     h = __builtin_bit_cast(unsigned, ph);
     l = __builtin_bit_cast(unsigned, __builtin_convertvector(((f32x2_){r0 * DFF_F16_LSCALE, r1 * DFF_F16_LSCALE}), f16x2_));
 }
-// eight consecutive fp32 -> the two fp16 operands (the layout of split8 below)
+// eight consecutive fp32 (x0 = k 0..3, x1 = k 4..7) -> the two fp16 operands; element j sits in half j & 1 of dword j >> 1
 DEVI void split8h(const f32x4& x0, const f32x4& x1, u32x4& h, u32x4& l) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -427,20 +368,6 @@ DEVI void pow2_scale(float mx, float& s, float& inv) {
     inv = __uint_as_float((unsigned)(ex - 4) << 23);     // 2^((ex - 127) - 4)            -> biased ex - 4
 }
 
-// eight consecutive fp32 (x0 = k 0..3, x1 = k 4..7) -> the three bf16-pair operands of v_mfma_f32_16x16x32_bf16 (~44 VALU)
-DEVI void split8(const f32x4& x0, const f32x4& x1, u32x4& h, u32x4& m, u32x4& l) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float e0 = q < 2 ? x0[2 * q] : x1[2 * q - 4], e1 = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
-        const unsigned b0 = __float_as_uint(e0), b1 = __float_as_uint(e1);
-        const float r0 = e0 - __uint_as_float(b0 & 0xffff0000u), r1 = e1 - __uint_as_float(b1 & 0xffff0000u);
-        const unsigned c0 = __float_as_uint(r0), c1 = __float_as_uint(r1);
-        const float s0 = r0 - __uint_as_float(c0 & 0xffff0000u), s1 = r1 - __uint_as_float(c1 & 0xffff0000u);
-        h[q] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        m[q] = __builtin_amdgcn_perm(c1, c0, 0x07060302u);
-        l[q] = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // DFF_PROF=1 (./build.sh with DFF_EXTRA_FLAGS=-DDFF_PROF=1; tools_profile_stages.py needs such a build): the stage ticks are
@@ -477,7 +404,7 @@ struct Ctx {
     int b0;
     float *xst, *xs, *dxs, *vst, *cm, *tn, *abuf, *resbuf, *Pbuf, *dSbuf, *Rg;
     float* rsc;    // fp16 engine (LdsLayout::rsc): rsc[row] = 1 / (power-of-two scale of the row's backward GEMM input)
-    lu32* asp;     // split engine: the bf16 pieces of the K = H GEMM input (LdsLayout::asplit), RNa allocated rows
+    lu32* asp;     // split engine: the fp16 pieces of the K = H GEMM input (LdsLayout::asplit), RNa allocated rows
     int RNa;
     float* stash;  // this workgroup's slot
     const float* l0;   // layer-0 slot the x-independent nodes_in / q|u|k|v are READ from (table entry or own stash)
@@ -547,7 +474,7 @@ struct Variant {
 };
 const Variant* dff_fused_variants(int* count);                                  // dff_kernels.hip
 int dff_debug_gemm_launch(int K, const float* dA, const float* dW, int M, int Nout, float* dO, size_t lds);   // dff_kernels.hip
-// the <= 16-row kernel for (H, NW waves, input-branch variant, split-bf16 weight GEMMs); false if not built
+// the <= 16-row kernel for (H, NW waves, input-branch variant, split weight GEMMs); false if not built
 // (one translation unit per sampler mode, DFF_MODE_SCORE / LANGEVIN / DDPM = 0 / 1 / 2: dff_small.hip compiled three times)
 // (pair: the two-workgroups-per-protein variant -- the FOLD kernel of the sampling loops only; 4 waves per workgroup)
 bool dff_small_pick_m0(int H, int NW, bool gen, bool spw, const void** fn, unsigned* lds_floats, const char** name, bool fold, bool pair);

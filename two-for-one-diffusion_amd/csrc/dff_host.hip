@@ -75,38 +75,12 @@ static std::vector<float> pack_b(int K, int Nout, const std::function<double(int
     return out;
 }
 
-// B operand of v_mfma_f32_16x16x32_bf16 for the split-bf16 GEMMs (dff_kernels.hip gemm_wide_split): per (tile,
-// 32-row k-block, piece h | m | l, lane) eight bf16 = W[32 kb + 8 (lane >> 4) + j][16 nt + (lane & 15)], j = 0..7,
-// two per dword (even j in the low half).  w = h + m + l exactly (truncation split of the fp32 weight).
-static std::vector<uint32_t> pack_b_split(int K, int Nout, const std::function<double(int, int)>& w) {
-    const int KB = K / 32, NT = (Nout + 15) / 16;
-    std::vector<uint32_t> out((size_t)NT * KB * 3 * 64 * 4, 0u);
-    auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-    auto flt = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * kb + 8 * (lane >> 4) + j, n = 16 * nt + (lane & 15);
-                    const float v = n < Nout ? (float)w(k, n) : 0.f;
-                    const uint32_t h = bits(v) & 0xffff0000u;
-                    const float r = v - flt(h);
-                    const uint32_t mm = bits(r) & 0xffff0000u;
-                    const float r2 = r - flt(mm);
-                    const uint32_t pc[3] = {h >> 16, mm >> 16, bits(r2) >> 16};
-                    for (int p = 0; p < 3; ++p)
-                        out[((((size_t)nt * KB + kb) * 3 + p) * 64 + lane) * 4 + (j >> 1)] |= pc[p] << (16 * (j & 1));
-                }
-    return out;
-}
-
-// Split-bf16 images for the <= 16-row kernel's SPW variants (dff_small.hip, split engine): a sequence of UNITS, each one
-// 16-column output tile nt x 32 A-columns starting at c0, stored [piece h | m | l][lane][8 bf16].  Element j of lane
-// (n = lane & 15, kg = lane >> 4) is W(c0 + 16 (j >> 2) + 4 kg + (j & 3), 16 nt + n): the k order in which that kernel's A
-// fragments hold a 32-column block (two ds_read_b128, at columns 4 kg and 16 + 4 kg).  w = h + m + l exactly.
 static uint16_t f32_to_f16_rn(float f);
 static float f16_to_f32(uint16_t h);
-// pack_b_split in the two-piece fp16 format of the round-5 engine: per (tile, 32-row k-block, piece h | l', lane) eight fp16
+// B operand of v_mfma_f32_16x16x32_f16 for the split GEMMs of the <= 64-row kernel (dff_kernels.hip gemm_wide_split_st and
+// friends), two fp16 pieces per weight: per (tile, 32-row k-block, piece h | l', lane) eight fp16 =
+// W[32 kb + 8 (lane >> 4) + j][16 nt + (lane & 15)], j = 0..7, two per dword (even j in the low half);
+// h = RN_f16(w), l' = RN_f16((w - h) 2048).
 static std::vector<uint32_t> pack_b_split_f16(int K, int Nout, const std::function<double(int, int)>& w) {
     const int KB = K / 32, NT = (Nout + 15) / 16;
     std::vector<uint32_t> out((size_t)NT * KB * 2 * 64 * 4, 0u);
@@ -121,27 +95,6 @@ static std::vector<uint32_t> pack_b_split_f16(int K, int Nout, const std::functi
                     out[((((size_t)nt * KB + kb) * 2 + 0) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)h << (16 * (j & 1));
                     out[((((size_t)nt * KB + kb) * 2 + 1) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)l << (16 * (j & 1));
                 }
-    return out;
-}
-static std::vector<uint32_t> pack_units(const std::vector<std::pair<int, int>>& units, int Nout,
-                                        const std::function<double(int, int)>& w) {
-    std::vector<uint32_t> out(units.size() * 3 * 64 * 4, 0u);
-    auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-    auto flt = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    for (size_t u = 0; u < units.size(); ++u) {
-        const int nt = units[u].first, c0 = units[u].second;
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-                const int c = c0 + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3), n = 16 * nt + (lane & 15);
-                const float v = n < Nout ? (float)w(c, n) : 0.f;
-                const uint32_t h = bits(v) & 0xffff0000u;
-                const float r = v - flt(h);
-                const uint32_t mm = bits(r) & 0xffff0000u;
-                const float r2 = r - flt(mm);
-                const uint32_t pc[3] = {h >> 16, mm >> 16, bits(r2) >> 16};
-                for (int q = 0; q < 3; ++q) out[((u * 3 + q) * 64 + lane) * 4 + (j >> 1)] |= pc[q] << (16 * (j & 1));
-            }
-    }
     return out;
 }
 // fp32 -> fp16 (binary16), round to nearest even, subnormals kept: what v_cvt_pk_f16_f32 does on the device (dff_device.h split2h)
@@ -169,8 +122,11 @@ static float f16_to_f32(uint16_t h) {
     memcpy(&f, &u, 4);
     return f;
 }
-// The same unit sequence as TWO fp16 pieces per weight for the <= 16-row FOLD kernel's fp16 engine (dff_small.hip, stream kind
-// -1): [piece h | l'][lane][8 fp16], h = RN_f16(w), l' = RN_f16((w - h) 2048): w = h + l' / 2048 to 2^-22 relative (3e-11 absolute).
+// Split images for the <= 16-row kernel's SPW variants (dff_small.hip): a sequence of UNITS, each one 16-column output tile nt x
+// 32 A-columns starting at c0, stored [piece h | l'][lane][8 fp16], h = RN_f16(w), l' = RN_f16((w - h) 2048): w = h + l' / 2048
+// to 2^-22 relative (3e-11 absolute).  Element j of lane (n = lane & 15, kg = lane >> 4) is W(c0 + 16 (j >> 2) + 4 kg + (j & 3),
+// 16 nt + n): the k order in which that kernel's A fragments hold a 32-column block (two ds_read_b128, at columns 4 kg and
+// 16 + 4 kg).
 static std::vector<uint32_t> pack_units_f16(const std::vector<std::pair<int, int>>& units, int Nout,
                                             const std::function<double(int, int)>& w) {
     std::vector<uint32_t> out(units.size() * 2 * 64 * 4, 0u);
@@ -240,7 +196,7 @@ struct dff_model {
     bool l0_off = false;                       // debugging: never use the table
     int max_wgs = 2048;                        // workgroups per launch: bounds the stash (grid x stash slot) for big batches
     int last_base = 0;
-    bool split = false;                        // split-bf16 images exist, SPW variants preferred (DFF_SPLIT_BF16=0 at model creation: never)
+    bool split = false;                        // split (fp16) images exist, SPW variants preferred (DFF_SPLIT_BF16=0 at model creation: never)
     bool small_split = false;                  // ... and the <= 16-row kernel has an SPW variant for this model
     bool fold_kv = false;                      // H == 64: k = v = LayerNorm output (W_k folded into W_q, W_v into W_o); DFF_FOLD_KV=0: never
     // PAIR variants (two workgroups per protein): partial-tile exchange slots and flags
@@ -357,7 +313,7 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
     m->cfg = *cfg;
     m->device = device;
     HIPCHK(hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    {   // weight GEMMs on the fp16 / bf16 pipe via the split of every fp32 operand, wherever a kernel variant exists for the
+    {   // weight GEMMs on the fp16 pipe via the split of every fp32 operand, wherever a kernel variant exists for the
         // shape (default); DFF_SPLIT_BF16=0: every GEMM on v_mfma_f32_16x16x4_f32
         const char* e = getenv("DFF_SPLIT_BF16");
         m->split = !(e && e[0] == '0');
@@ -626,21 +582,16 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
         d.Wqkvx_s = d.W1_s = d.W2T_s = d.WoxT_s = d.W2_s = d.W1T_s = d.Wox_s = d.WqkvxT_s = nullptr;
         if (m->split) {
             int rc_;
-            // image format per GEMM group: two fp16 pieces where the kernels' engine takes them (dff_fused_f16_mask)
-            const int f16m = dff_fused_f16_mask();
-            auto PB = [&](int bit, int K_, int Nout_, const std::function<double(int, int)>& wf) {
-                return (f16m & bit) ? pack_b_split_f16(K_, Nout_, wf) : pack_b_split(K_, Nout_, wf);
-            };
-            if ((rc_ = upload_u32(m, PB(1, H, 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_s))) return rc_;
-            if ((rc_ = upload_u32(m, PB(1, H, F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_s))) return rc_;
-            if ((rc_ = upload_u32(m, PB(2, H, F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_s))) return rc_;
-            if ((rc_ = upload_u32(m, PB(4, H, 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_s))) return rc_;
-            if ((rc_ = upload_u32(m, PB(1, F, H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_s))) return rc_;
-            if ((rc_ = upload_u32(m, PB(2, F, H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(H, 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(H, F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(H, F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(H, 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(F, H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(F, H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_s))) return rc_;
             // the 64 regular rows of every head of [W_o ; W_oc] (the extension rows stay on the fp32 image)
-            if ((rc_ = upload_u32(m, PB(1, 8 * 64, H, [&](int k, int n) { return wox((k / 64) * 80 + k % 64, n); }), &d.Wox_s))) return rc_;
+            if ((rc_ = upload_u32(m, pack_b_split_f16(8 * 64, H, [&](int k, int n) { return wox((k / 64) * 80 + k % 64, n); }), &d.Wox_s))) return rc_;
             // ... and the 192 regular rows [q | k | v] of every head of QKV_ext^T
-            if ((rc_ = upload_u32(m, PB(8, 8 * 192, H, [&](int c, int n) {
+            if ((rc_ = upload_u32(m, pack_b_split_f16(8 * 192, H, [&](int c, int n) {
                      const int h = c / 192, cc = c % 192;
                      return wqkvx(h * 208 + (cc < 64 ? cc : cc + 16), n); }), &d.WqkvxT_s))) return rc_;
         }
@@ -650,26 +601,21 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
             // fold_kv on the shipped input branch: the <= 16-row kernel's FOLD variant streams [q' | u] (5 tiles per head) and
             // back-projects dQ only (2 k-blocks per head); k = v = LayerNorm output never goes through a GEMM there
             const bool sfold = m->fold_kv && intr && !dist && !ab;
-            // the FOLD variant's engine decides the image format: two fp16 pieces (round 5) or three bf16 pieces
-            const bool f16img = dff_small_f16_level() >= 2 || (sfold && dff_small_f16_level() == 1);
-            auto PU = [&](const std::vector<std::pair<int, int>>& un, int nout, const std::function<double(int, int)>& wf) {
-                return f16img ? pack_units_f16(un, nout, wf) : pack_units(un, nout, wf);
-            };
             if (sfold) {
-                if ((rc_ = upload_u32(m, PU(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wqkvx((n / 80) * 208 + n % 80, k); }), &d.Wqkvx_w))) return rc_;
+                if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wqkvx((n / 80) * 208 + n % 80, k); }), &d.Wqkvx_w))) return rc_;
             } else
-            if ((rc_ = upload_u32(m, PU(units_wide(H, 8 * 208), 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_w))) return rc_;
-            if ((rc_ = upload_u32(m, PU(units_wide(H, F), F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_w))) return rc_;
-            if ((rc_ = upload_u32(m, PU(units_wide(H, F), F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_w))) return rc_;
-            if ((rc_ = upload_u32(m, PU(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_w))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 208), 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_w))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, F), F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_w))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, F), F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_w))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_w))) return rc_;
             // Nout = H: the 64 regular rows of every head of [W_o ; W_oc] / [q | k | v] (extension rows: fp32 k-step off the fp32 images)
-            if ((rc_ = upload_u32(m, PU(units_tall(8 * 64, H), H, [&](int c, int n) { return wox((c / 64) * 80 + c % 64, n); }), &d.Wox_t))) return rc_;
-            if ((rc_ = upload_u32(m, PU(units_tall(F, H), H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_t))) return rc_;
-            if ((rc_ = upload_u32(m, PU(units_tall(F, H), H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_t))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 64, H), H, [&](int c, int n) { return wox((c / 64) * 80 + c % 64, n); }), &d.Wox_t))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(F, H), H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_t))) return rc_;
+            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(F, H), H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_t))) return rc_;
             if (sfold) {
-                if ((rc_ = upload_u32(m, PU(units_tall(8 * 64, H), H, [&](int c, int n) { return wqkvx((c / 64) * 208 + c % 64, n); }), &d.WqkvxT_t))) return rc_;
+                if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 64, H), H, [&](int c, int n) { return wqkvx((c / 64) * 208 + c % 64, n); }), &d.WqkvxT_t))) return rc_;
             } else
-            if ((rc_ = upload_u32(m, PU(units_tall(8 * 192, H), H, [&](int c, int n) {
+            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 192, H), H, [&](int c, int n) {
                      const int h = c / 192, cc = c % 192;
                      return wqkvx(h * 208 + (cc < 64 ? cc : cc + 16), n); }), &d.WqkvxT_t))) return rc_;
         }
@@ -1504,15 +1450,9 @@ extern "C" const char* dff_last_error(void) { return g_err.c_str(); }
 #define DFF_STR(x) DFF_STR2(x)
 // DFF_BUILD_FLAGS (build.sh, generated header): DFF_EXTRA_FLAGS / scheduler overrides the translation units were compiled with -- a
 // development build names its knobs; they are hashed into DFF_SRC_SHA as well, so that it never shares the product build's hash.
-// DFF_EXPERIMENT: the build says of itself that it may compute wrong numbers (timing experiments).
 #ifndef DFF_BUILD_FLAGS
 #define DFF_BUILD_FLAGS ""
 #endif
-#ifdef DFF_EXPERIMENT
-#define DFF_EXP_TAG " EXPERIMENT"
-#else
-#define DFF_EXP_TAG ""
-#endif
 extern "C" const char* dff_version(void) {
-    return "dff-amd 0.1 (gfx950; f16-split / f32 MFMA)" DFF_EXP_TAG " flags=[" DFF_BUILD_FLAGS "] src=" DFF_STR(DFF_SRC_SHA);
+    return "dff-amd 0.1 (gfx950; f16-split / f32 MFMA) flags=[" DFF_BUILD_FLAGS "] src=" DFF_STR(DFF_SRC_SHA);
 }

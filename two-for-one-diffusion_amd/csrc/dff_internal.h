@@ -33,11 +33,11 @@ struct DffLayerDev {
     const float *g2;
     // backward (transposed orientation)
     const float *W2T_p;           // K=H, Nout=4H   dh  = dff  W2
-    // opt-in (DFF_SPLIT_BF16=1): the K = H images as three bf16 pieces per weight (dff_host.hip pack_b_split)
+    // split engine (DFF_SPLIT_BF16=1): the weight images as two fp16 pieces per weight (dff_host.hip pack_b_split_f16)
     const unsigned *Wqkvx_s, *W1_s, *W2T_s, *WoxT_s, *W2_s, *W1T_s, *Wox_s, *WqkvxT_s;
     const float *W1T_p;           // K=4H, Nout=H   df  = dhp  W1
-    // split-bf16 images of all eight weight GEMMs for the <= 16-row kernel (dff_small.hip SPW variants; dff_host.hip
-    // pack_units): *_w K = H, units ordered [tile][k-block]; *_t Nout = H, units ordered [k-block][tile]
+    // split images (two fp16 pieces per weight) of all eight weight GEMMs for the <= 16-row kernel (dff_small.hip SPW variants;
+    // dff_host.hip pack_units_f16): *_w K = H, units ordered [tile][k-block]; *_t Nout = H, units ordered [k-block][tile]
     const unsigned *Wqkvx_w, *W1_w, *W2T_w, *WoxT_w, *Wox_t, *W2_t, *W1T_t, *WqkvxT_t;
     // "extended head" images: per head 80 = 64 + 16 extension columns / rows ([u (3) | s | 0...], [xrel (3) | D | 0...])
     const float *Wqkvx_p, *bqkvx; // K=H, Nout=8*208, per head [q 64 | ext 16 | k 64 | v 64]
@@ -107,11 +107,3 @@ struct DffRunArgs {
     int xpairs;
     int xslow;       // tests: never take the same-XCD fast path of the exchanges (the agent-scope protocol a cross-XCD pair runs)
 };
-
-// which split variants of the <= 16-row kernel were compiled with the two-piece fp16 engine (dff_small.hip DFF_F16): 0 none,
-// 1 the FOLD variant, 2 all -- the host packs their weight images accordingly (dff_host.hip pack_units_f16)
-int dff_small_f16_level();
-
-// bit mask of the <= 64-row split variants' GEMM groups that take two-piece fp16 images (dff_kernels.hip DFF_F16G):
-// 1 = forward (Wqkvx_s, Wox_s, W1_s, W2_s), 2 = FFN backward (W2T_s, W1T_s), 4 = G_ext (WoxT_s), 8 = QKV_ext^T (WqkvxT_s)
-int dff_fused_f16_mask();

@@ -26,41 +26,14 @@
 // their transposes for the VJP) run on v_mfma_f32_16x16x4_f32 (exact fp32 == fmaf chain);
 // softmax / LayerNorm / GELU / gates / the N x N contractions run on the VALU out of LDS.
 #include "dff_device.h"
-// DFF_F16G (round 5): which weight GEMMs of the split variants run on the two-piece fp16 format (4 B per weight, three MFMAs per
-// unit and row tile; dff_device.h split8h) instead of the three-piece bf16 one: bit 0 = the forward images (Wqkvx, Wox, W1, W2;
-// their A operands are O(1) activations: no scaling), bit 1 = the FFN backward (W2T, W1T; row-scaled), bit 2 = G_ext (WoxT).
-#ifndef DFF_F16G
-#define DFF_F16G 15   // ... bit 3 = the QKV_ext^T back-projection (WqkvxT; dQ / dK / dV scaled by one power of two per workgroup)
-#endif
-#define DFF_QT16 ((DFF_F16G & 12) == 12)   // (the block scale is derived from the row scales of G_ext's input: bit 2 as well)
 #include <type_traits>
-#ifndef DFF_AUXLATE
-#define DFF_AUXLATE 1   // wide split GEMMs: the tiles' auxiliary rows are requested behind the ring's first entries (protein G -1.1 %, trp-cage -0.5 %, villin / BBA -0.2 %)
-#endif
-#ifndef DFF_APRE
-#define DFF_APRE 1
-#endif
-#ifndef DFF_PIPEB_128_2
-#define DFF_PIPEB_128_2 1   // trp-cage's shape in the backward head pipeline (half-unit ring entries)
-#endif
-#ifndef DFF_QTPRE
-#define DFF_QTPRE 1
-#endif
-#ifndef DFF_TPRE_MT
-#define DFF_TPRE_MT 3   // tall split GEMMs: A fragments one k-block ahead, up to this many row tiles (four: measured neutral)
-#endif
-#ifndef DFF_K2_MT
-#define DFF_K2_MT 3    // two output tiles per wave in the wide split GEMMs from this many row tiles on (three: -0.3 % with the fp16 engine; it spilled with three pieces)
-#endif
-#ifndef DFF_ARES_LIM
-#define DFF_ARES_LIM 8 // A operand register-resident in the wide split GEMMs while MT * KB32 <= this
-#endif
-#ifndef DFF_ARES
-#define DFF_ARES 1
-#endif
-// The image formats of the host (dff_fused_f16_mask) and the kernels are coupled through DFF_F16G: the QKV_ext^T image is read as
-// fp16 pieces only when the G_ext group is too (DFF_QT16) -- a build with bit 3 but not bit 2 would multiply a two-piece image as three
-static_assert((DFF_F16G & 8) == 0 || (DFF_F16G & 4) != 0, "DFF_F16G: bit 3 (QKV_ext^T) needs bit 2 (G_ext)");
+// Every weight GEMM of the split variants runs on the two-piece fp16 format (round 5: 4 B per weight, three MFMAs per unit and
+// row tile; dff_device.h split8h).  The forward images (Wqkvx, Wox, W1, W2) take O(1) activations unscaled; the FFN backward
+// (W2T, W1T) and G_ext (WoxT) take row-scaled operands; the QKV_ext^T back-projection (WqkvxT) takes dQ / dK / dV scaled by one
+// power of two per workgroup, derived from the row scales of G_ext's input.
+constexpr int TPRE_MT = 3;   // tall split GEMMs: A fragments one k-block ahead, up to this many row tiles (four: measured neutral)
+constexpr int K2_MT = 3;     // two output tiles per wave in the wide split GEMMs from this many row tiles on (three: -0.3 %)
+constexpr int ARES_LIM = 8;  // A operand register-resident in the wide split GEMMs while MT * KB32 <= this
 
 // ------------------------------------------------------------------------------------------
 // MFMA GEMM stages.  A (rows x K) lives in LDS with leading dimension lda (multiple of 4);
@@ -112,7 +85,7 @@ DEVI void gemm_wide(const lfloat* A, int lda, int rowsA, const float* __restrict
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) ah[HOLD ? mt : 0][HOLD ? kb : 0] = *(const lf32x4*)(A + rowoff[mt] + 16 * kb);
     }
-    const WPtr<gf32x4, DFF_WMODE(MT)> wp((const gf32x4*)Wp + (size_t)kb0 * 64, (unsigned)lane & 63u);
+    const WPtr<gf32x4, dff_wmode(MT)> wp((const gf32x4*)Wp + (size_t)kb0 * 64, (unsigned)lane & 63u);
     const int cnt = wave < ntn ? (ntn - wave + DFF_NWAVES - 1) / DFF_NWAVES : 0;
     f32x4 b[D][KB];
     float aux[D][NAUX];
@@ -177,7 +150,7 @@ DEVI void gemm_wide_st(const lfloat* A, int lda, int rowsA, const float* __restr
     int rowoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) rowoff[mt] = min(mt * 16 + mm, rowsA - 1) * lda + 4 * kk;
-    const WPtr<gf32x4, DFF_WMODE(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gf32x4, dff_wmode(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
     f32x4 b[DR][HB];
     float aux[NA][NAUX];
     auto tile_of = [&](int i) { return min(wave + DFF_NWAVES * i, NTN - 1); };
@@ -226,8 +199,8 @@ DEVI void gemm_wide_st(const lfloat* A, int lda, int rowsA, const float* __restr
     }
 }
 
-// gemm_wide on the split operands (Wp = pack_b_split image: [tile][k32-block][piece][lane] x 8 bf16; as = the piece arrays the
-// row stages write, rstore_a), loop-free: NTN is a compile-time tile count, every wave runs ceil(NTN / 8) tiles (a wave without a tile
+// gemm_wide on the split operands (Wp = pack_b_split_f16 image: [tile][k32-block][h | l'][lane] x 8 fp16; as = the piece arrays
+// the row stages write, rstore_a: as[0] = h, as[1] = l'), loop-free: NTN is a compile-time tile count, every wave runs ceil(NTN / 8) tiles (a wave without a tile
 // of its own in the last round repeats tile NTN - 1 with valid = false: it would idle at the barrier anyway), and
 // pre / epi issue the SAME global loads and stores for every tile (epilogues redirect what must not be stored to the
 // stash's junk slot).  With no control flow around VMEM the compiler counts the operations in flight exactly;
@@ -235,19 +208,18 @@ DEVI void gemm_wide_st(const lfloat* A, int lda, int rowsA, const float* __restr
 // (s_waitcnt vmcnt(0) in front of every MFMA block).  epi(nt, mt, acc, aux, valid).
 // Waves W0 .. W0 + NWV - 1 share the tiles (the others must not call); epi also gets the round index i (compile time
 // after unrolling: an epilogue may park the tile in registers, see the head loop of the forward pass).
-// F16 (round 5): the two-piece fp16 format (dff_device.h split8h) -- image [tile][k-block][h | l'][lane], A pieces as[0] = h, as[1] = l',
-// three v_mfma_f32_16x16x32_f16 per (unit, row tile): cb = h.h, cs = the two 2^11-scaled cross terms, result cb + cs / 2048.
-template <int MT, int KB32, int NTN, int NAUX, int W0 = 0, int NWV = DFF_NWAVES, int DRMAX = 3, bool F16 = false, class Pre, class Epi>
+// The two-piece fp16 format (dff_device.h split8h): three v_mfma_f32_16x16x32_f16 per (unit, row tile): cb = h.h, cs = the two
+// 2^11-scaled cross terms, result cb + cs / 2048.
+template <int MT, int KB32, int NTN, int NAUX, int W0 = 0, int NWV = DFF_NWAVES, int DRMAX = 3, class Pre, class Epi>
 DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* __restrict__ Wp, int nt0, Pre pre, Epi epi) {
-    constexpr int NP = F16 ? 2 : 3;
     constexpr bool HALVES = KB32 % 2 == 0 && KB32 >= 4;
     constexpr int NHALF = HALVES ? 2 : 1, HB = KB32 / NHALF, LHS2 = (32 * KB32 + DFF_SPAD) / 2;
     constexpr int CNT = (NTN + NWV - 1) / NWV, NE = CNT * NHALF;
-    // ARES (two row tiles at most): the whole split A operand -- 12 MT KB32 registers -- is read from LDS ONCE and stays in
+    // ARES (two row tiles at most): the whole split A operand -- 8 MT KB32 registers -- is read from LDS ONCE and stays in
     // registers while the wave's tiles stream by.  Otherwise every wave re-reads all of A for every tile: at MT = 2 that is
     // as many LDS cycles as the GEMM has MFMA cycles, and the two do not overlap (trp-cage's QKV_ext GEMM: 14.5 k cycles per
     // call against 5 k of products).
-    constexpr bool ARES = MT * KB32 <= DFF_ARES_LIM && DFF_ARES;
+    constexpr bool ARES = MT * KB32 <= ARES_LIM;
     constexpr int DR0 = HALVES ? (DRMAX < 3 ? DRMAX : 3) : 2, DR = NE < DR0 ? NE : DR0;
     constexpr int NA = 3;
     const int tid_ = tid_now();
@@ -256,8 +228,8 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
     int rowoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) rowoff[mt] = min(mt * 16 + mm, rowsA - 1) * LHS2 + 4 * kg;
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
-    u32x4 b[DR][HB][3];
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    u32x4 b[DR][HB][3];   // ([2] used: the third entry keeps the register assignment of the three-piece ring, see gemm_tall_qkvT_split)
     float aux[NA][NAUX];
     auto tile_of = [&](int i) { return min(wave + NWV * i, NTN - 1); };
     auto fill = [&](u32x4 (&slot)[HB][3], int e) {
@@ -265,25 +237,20 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
 #pragma unroll
         for (int kb = 0; kb < HB; ++kb)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) slot[kb][p] = wp[((tile * KB32 + (e % NHALF) * HB + kb) * NP + p) * 64];
+            for (int p = 0; p < 2; ++p) slot[kb][p] = wp[((tile * KB32 + (e % NHALF) * HB + kb) * 2 + p) * 64];
     };
-    // DFF_AUXLATE: the ring's first entries are requested BEFORE the tiles' auxiliary rows.  Loads return in order, and an
-    // auxiliary row may come from HBM (the backward's gelu' rows out of the stash): requested in between, every ring entry
-    // behind it waits a memory latency the first entries' products could have covered.
+    // The ring's first entries are requested BEFORE the tiles' auxiliary rows (protein G -1.1 %, trp-cage -0.5 %, villin / BBA
+    // -0.2 %).  Loads return in order, and an auxiliary row may come from HBM (the backward's gelu' rows out of the stash):
+    // requested in between, every ring entry behind it waits a memory latency the first entries' products could have covered.
 #pragma unroll
-    for (int j = 0; j < DR; ++j) {
-        fill(b[j], j);
-        if constexpr (!DFF_AUXLATE) if (j % NHALF == 0) pre(tile_of(j / NHALF), aux[(j / NHALF) % NA]);
-    }
-    if constexpr (DFF_AUXLATE) {
+    for (int j = 0; j < DR; ++j) fill(b[j], j);
 #pragma unroll
-        for (int j = 0; j < DR; ++j)
-            if (j % NHALF == 0) pre(tile_of(j / NHALF), aux[(j / NHALF) % NA]);
-    }
+    for (int j = 0; j < DR; ++j)
+        if (j % NHALF == 0) pre(tile_of(j / NHALF), aux[(j / NHALF) % NA]);
     // the loads above are issued HERE: left alone, the scheduler sinks each next to its first use (one L2 latency
     // per k-block instead of one per GEMM)
     __builtin_amdgcn_sched_barrier(0);
-    u32x4 ares[ARES ? MT : 1][ARES ? KB32 : 1][3];
+    u32x4 ares[ARES ? MT : 1][ARES ? KB32 : 1][2];
     if constexpr (ARES) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -292,15 +259,12 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
                 const int o = rowoff[mt] + 16 * kb;
                 ares[mt][kb][0] = *(const lu32x4*)(as + o);
                 ares[mt][kb][1] = *(const lu32x4*)(as + R * LHS2 + o);
-                if constexpr (!F16) ares[mt][kb][2] = *(const lu32x4*)(as + 2 * R * LHS2 + o);
             }
     }
-    constexpr bool APRE = !ARES && DFF_APRE;
-    u32x4 apre[3];
-    if constexpr (APRE) {
+    u32x4 apre[2];
+    if constexpr (!ARES) {
         apre[0] = *(const volatile lu32x4*)(as + rowoff[0]);
         apre[1] = *(const volatile lu32x4*)(as + R * LHS2 + rowoff[0]);
-        if constexpr (!F16) apre[2] = *(const volatile lu32x4*)(as + 2 * R * LHS2 + rowoff[0]);
     }
     f32x4 cs[MT], cb[MT];
 #pragma unroll
@@ -317,38 +281,22 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
             for (int kb = 0; kb < HB; ++kb) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-                    const int o = rowoff[mt] + 16 * (half * HB + kb);
-                    u32x4 ah, am, al;
+                    u32x4 ah, al;
                     if constexpr (ARES) {
-                        ah = ares[mt][half * HB + kb][0]; am = ares[mt][half * HB + kb][1]; al = ares[mt][half * HB + kb][F16 ? 1 : 2];
-                    } else if constexpr (APRE) {
+                        ah = ares[mt][half * HB + kb][0]; al = ares[mt][half * HB + kb][1];
+                    } else {
                         // this unit's fragments were requested a unit ago; request the next unit's (the first of the next
                         // entry after the last of this one: A is the same for every tile) before this unit's products
-                        ah = apre[0]; am = apre[1]; al = apre[F16 ? 1 : 2];
-                        constexpr int dummy = 0; (void)dummy;
+                        ah = apre[0]; al = apre[1];
                         const int mtn = (mt + 1) % MT, kbn = (mt + 1 == MT) ? kb + 1 : kb;
                         const int kabs = (kbn == HB) ? ((half + 1) % NHALF) * HB : half * HB + kbn;
                         const int on = rowoff[mtn] + 16 * kabs;
                         apre[0] = *(const volatile lu32x4*)(as + on);
                         apre[1] = *(const volatile lu32x4*)(as + R * LHS2 + on);
-                        if constexpr (!F16) apre[2] = *(const volatile lu32x4*)(as + 2 * R * LHS2 + on);
-                    } else {
-                        ah = *(const lu32x4*)(as + o);
-                        am = *(const lu32x4*)(as + R * LHS2 + o);
-                        if constexpr (!F16) al = *(const lu32x4*)(as + 2 * R * LHS2 + o);
                     }
-                    if constexpr (F16) {
-                        cs[mt] = mfma_f16(b[slot][kb][0], am, cs[mt]);
-                        cs[mt] = mfma_f16(b[slot][kb][1], ah, cs[mt]);
-                        cb[mt] = mfma_f16(b[slot][kb][0], ah, cb[mt]);
-                    } else {
-                    cs[mt] = mfma_bf16(b[slot][kb][0], al, cs[mt]);
-                    cb[mt] = mfma_bf16(b[slot][kb][0], am, cb[mt]);
-                    cs[mt] = mfma_bf16(b[slot][kb][2], ah, cs[mt]);
-                    cb[mt] = mfma_bf16(b[slot][kb][1], ah, cb[mt]);
-                    cs[mt] = mfma_bf16(b[slot][kb][1], am, cs[mt]);
-                    cb[mt] = mfma_bf16(b[slot][kb][0], ah, cb[mt]);
-                    }
+                    cs[mt] = mfma_f16(b[slot][kb][0], al, cs[mt]);
+                    cs[mt] = mfma_f16(b[slot][kb][1], ah, cs[mt]);
+                    cb[mt] = mfma_f16(b[slot][kb][0], ah, cb[mt]);
                 }
             }
         }
@@ -360,7 +308,7 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
         if (half == NHALF - 1) {
             const bool valid = wave + NWV * i < NTN;
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) epi(tile_of(i), mt, F16 ? cb[mt] + cs[mt] * DFF_F16_LINV : cb[mt] + cs[mt], aux[i % NA], valid, i);
+            for (int mt = 0; mt < MT; ++mt) epi(tile_of(i), mt, cb[mt] + cs[mt] * DFF_F16_LINV, aux[i % NA], valid, i);
         }
     }
 }
@@ -370,9 +318,8 @@ DEVI void gemm_wide_split_st(const lu32* as, int R, int rowsA, const unsigned* _
 // it, and three ds_read_b128 per six 16-cycle products make the LDS as busy as the matrix pipes (8 waves x 24 LDS cycles
 // against 2 waves x 96 pipe cycles per SIMD): the two limits add up instead of overlapping.  Pairs q = wave + 8 i cover
 // tiles 2 q and 2 q + 1 (a surplus tile repeats NTN - 1 with valid = false); ring of two k-blocks (both tiles' pieces).
-template <int MT, int KB32, int NTN, int NAUX, bool F16 = false, class Pre, class Epi>
+template <int MT, int KB32, int NTN, int NAUX, class Pre, class Epi>
 DEVI void gemm_wide_split_k2(const lu32* as, int R, int rowsA, const unsigned* __restrict__ Wp, int nt0, Pre pre, Epi epi) {
-    constexpr int NPC = F16 ? 2 : 3;   // pieces per weight
     constexpr int LHS2 = (32 * KB32 + DFF_SPAD) / 2, NP = (NTN + 1) / 2, CNT = (NP + DFF_NWAVES - 1) / DFF_NWAVES, DR = 2;
     static_assert(KB32 >= DR, "ring");
     const int tid_ = tid_now();
@@ -381,23 +328,23 @@ DEVI void gemm_wide_split_k2(const lu32* as, int R, int rowsA, const unsigned* _
     int rowoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) rowoff[mt] = min(mt * 16 + mm, rowsA - 1) * LHS2 + 4 * kg;
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
 #pragma unroll
     for (int i = 0; i < CNT; ++i) {
         const int q = wave + DFF_NWAVES * i;
         const int t0 = min(2 * q, NTN - 1), t1 = min(2 * q + 1, NTN - 1);
         const bool v0 = 2 * q < NTN, v1 = 2 * q + 1 < NTN;
-        u32x4 b[DR][2][3];
+        u32x4 b[DR][2][2];
         float aux[2][NAUX];
-        auto fill = [&](u32x4 (&slot)[2][3], int kb) {
+        auto fill = [&](u32x4 (&slot)[2][2], int kb) {
 #pragma unroll
-            for (int p = 0; p < NPC; ++p) slot[0][p] = wp[(((size_t)(nt0 + t0) * KB32 + kb) * NPC + p) * 64];
+            for (int p = 0; p < 2; ++p) slot[0][p] = wp[(((size_t)(nt0 + t0) * KB32 + kb) * 2 + p) * 64];
 #pragma unroll
-            for (int p = 0; p < NPC; ++p) slot[1][p] = wp[(((size_t)(nt0 + t1) * KB32 + kb) * NPC + p) * 64];
+            for (int p = 0; p < 2; ++p) slot[1][p] = wp[(((size_t)(nt0 + t1) * KB32 + kb) * 2 + p) * 64];
         };
 #pragma unroll
         for (int d = 0; d < DR; ++d) fill(b[d], d);
-        if constexpr (!(DFF_AUXLATE && KB32 > DR)) {
+        if constexpr (KB32 <= DR) {
             pre(t0, aux[0]);
             pre(t1, aux[1]);
         }
@@ -407,81 +354,60 @@ DEVI void gemm_wide_split_k2(const lu32* as, int R, int rowsA, const unsigned* _
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) { cs[t][mt] = (f32x4){0.f, 0.f, 0.f, 0.f}; cb[t][mt] = cs[t][mt]; }
-        u32x4 apre[3];
+        u32x4 apre[2];
         apre[0] = *(const volatile lu32x4*)(as + rowoff[0]);
         apre[1] = *(const volatile lu32x4*)(as + R * LHS2 + rowoff[0]);
-        if constexpr (!F16) apre[2] = *(const volatile lu32x4*)(as + 2 * R * LHS2 + rowoff[0]);
         if (v0) {   // (wave-uniform; a wave without a pair skips the products)
 #pragma unroll
             for (int kb = 0; kb < KB32; ++kb) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-                    const u32x4 ah = apre[0], am = apre[1], al = apre[F16 ? 1 : 2];
+                    const u32x4 ah = apre[0], al = apre[1];
                     const int mtn = (mt + 1) % MT, kbn = (mt + 1 == MT) ? (kb + 1) % KB32 : kb;
                     const int on = rowoff[mtn] + 16 * kbn;
                     apre[0] = *(const volatile lu32x4*)(as + on);
                     apre[1] = *(const volatile lu32x4*)(as + R * LHS2 + on);
-                    if constexpr (!F16) apre[2] = *(const volatile lu32x4*)(as + 2 * R * LHS2 + on);
-                    if constexpr (F16) {
 #pragma unroll
-                        for (int t = 0; t < 2; ++t) cs[t][mt] = mfma_f16(b[kb % DR][t][0], am, cs[t][mt]);
+                    for (int t = 0; t < 2; ++t) cs[t][mt] = mfma_f16(b[kb % DR][t][0], al, cs[t][mt]);
 #pragma unroll
-                        for (int t = 0; t < 2; ++t) cs[t][mt] = mfma_f16(b[kb % DR][t][1], ah, cs[t][mt]);
+                    for (int t = 0; t < 2; ++t) cs[t][mt] = mfma_f16(b[kb % DR][t][1], ah, cs[t][mt]);
 #pragma unroll
-                        for (int t = 0; t < 2; ++t) cb[t][mt] = mfma_f16(b[kb % DR][t][0], ah, cb[t][mt]);
-                    } else {
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        cs[t][mt] = mfma_bf16(b[kb % DR][t][0], al, cs[t][mt]);
-                        cb[t][mt] = mfma_bf16(b[kb % DR][t][0], am, cb[t][mt]);
-                    }
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        cs[t][mt] = mfma_bf16(b[kb % DR][t][2], ah, cs[t][mt]);
-                        cb[t][mt] = mfma_bf16(b[kb % DR][t][1], ah, cb[t][mt]);
-                    }
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        cs[t][mt] = mfma_bf16(b[kb % DR][t][1], am, cs[t][mt]);
-                        cb[t][mt] = mfma_bf16(b[kb % DR][t][0], ah, cb[t][mt]);
-                    }
-                    }
+                    for (int t = 0; t < 2; ++t) cb[t][mt] = mfma_f16(b[kb % DR][t][0], ah, cb[t][mt]);
                 }
                 if (kb + DR < KB32) {
                     fill(b[kb % DR], kb + DR);
-                    if constexpr (DFF_AUXLATE) if (kb == 0) { pre(t0, aux[0]); pre(t1, aux[1]); }   // (behind three k-blocks, see gemm_wide_split_st)
+                    if (kb == 0) { pre(t0, aux[0]); pre(t1, aux[1]); }   // (behind three k-blocks, see gemm_wide_split_st)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-        } else if constexpr (DFF_AUXLATE && KB32 > DR) {
+        } else if constexpr (KB32 > DR) {
             pre(t0, aux[0]);
             pre(t1, aux[1]);
         }
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) epi(t0, mt, F16 ? cb[0][mt] + cs[0][mt] * DFF_F16_LINV : cb[0][mt] + cs[0][mt], aux[0], v0, i);
+        for (int mt = 0; mt < MT; ++mt) epi(t0, mt, cb[0][mt] + cs[0][mt] * DFF_F16_LINV, aux[0], v0, i);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) epi(t1, mt, F16 ? cb[1][mt] + cs[1][mt] * DFF_F16_LINV : cb[1][mt] + cs[1][mt], aux[1], v1, i);
+        for (int mt = 0; mt < MT; ++mt) epi(t1, mt, cb[1][mt] + cs[1][mt] * DFF_F16_LINV, aux[1], v1, i);
     }
 }
 
 // gemm_wide_units on the split operands (few output tiles: (tile, row-tile) units round-robin over the waves, loop-free).
 // Up to two units per wave: all weights requested up front.  More (four row tiles: 5 tiles x 4 = 20 units, three per
-// wave): a ring of two units -- three units of K = 128 weights at once are 144 registers.
-template <int MT, int KB32, int NTN, bool F16 = false, class Epi>
+// wave): a ring of two units -- three units of K = 128 weights at once are 96 registers.
+template <int MT, int KB32, int NTN, class Epi>
 DEVI void gemm_wide_units_split(const lu32* as, int R, int rowsA, const unsigned* __restrict__ Wp, int nt0, Epi epi) {
-    constexpr int NPC = F16 ? 2 : 3;
     const int tid_ = tid_now();
     constexpr int NU = NTN * MT, DU = (NU + DFF_NWAVES - 1) / DFF_NWAVES, DRU = DU < 2 ? DU : 2, LHS2 = (32 * KB32 + DFF_SPAD) / 2;
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
     const int kg = lane >> 4, mm = lane & 15;
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
-    u32x4 b[DRU][KB32][3];
-    auto fill = [&](u32x4 (&slot)[KB32][3], int d) {
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    u32x4 b[DRU][KB32][2];
+    auto fill = [&](u32x4 (&slot)[KB32][2], int d) {
         const int nt = min(wave + DFF_NWAVES * d, NU - 1) / MT;
 #pragma unroll
         for (int kb = 0; kb < KB32; ++kb)
 #pragma unroll
-            for (int p = 0; p < NPC; ++p) slot[kb][p] = wp[(((size_t)(nt0 + nt) * KB32 + kb) * NPC + p) * 64];
+            for (int p = 0; p < 2; ++p) slot[kb][p] = wp[(((size_t)(nt0 + nt) * KB32 + kb) * 2 + p) * 64];
     };
 #pragma unroll
     for (int d = 0; d < DRU; ++d) fill(b[d], d);
@@ -492,143 +418,94 @@ DEVI void gemm_wide_units_split(const lu32* as, int R, int rowsA, const unsigned
         if (u < NU) {
             const int nt = u / MT, mt = u - nt * MT;
             const int ro = min(mt * 16 + mm, rowsA - 1) * LHS2 + 4 * kg;
-            f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f}, cs2 = cs, cb2 = cs;
+            f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f}, cs2 = cs;
 #pragma unroll
-            for (int kb = 0; kb < KB32; ++kb) {
+            for (int kb = 0; kb < KB32; ++kb) {   // cs / cs2: the 2^11-scaled cross terms, cb: h.h
                 const u32x4 ah = *(const lu32x4*)(as + ro + 16 * kb);
-                const u32x4 am = *(const lu32x4*)(as + R * LHS2 + ro + 16 * kb);
-                if constexpr (F16) {   // cs / cs2: the 2^11-scaled cross terms, cb: h.h
-                    cs = mfma_f16(b[d % DRU][kb][0], am, cs);
-                    cs2 = mfma_f16(b[d % DRU][kb][1], ah, cs2);
-                    cb = mfma_f16(b[d % DRU][kb][0], ah, cb);
-                } else {
-                const u32x4 al = *(const lu32x4*)(as + 2 * R * LHS2 + ro + 16 * kb);
-                cs = mfma_bf16(b[d % DRU][kb][0], al, cs);
-                cb = mfma_bf16(b[d % DRU][kb][0], am, cb);
-                cs2 = mfma_bf16(b[d % DRU][kb][2], ah, cs2);
-                cb2 = mfma_bf16(b[d % DRU][kb][1], ah, cb2);
-                cs = mfma_bf16(b[d % DRU][kb][1], am, cs);
-                cb = mfma_bf16(b[d % DRU][kb][0], ah, cb);
-                }
+                const u32x4 al = *(const lu32x4*)(as + R * LHS2 + ro + 16 * kb);
+                cs = mfma_f16(b[d % DRU][kb][0], al, cs);
+                cs2 = mfma_f16(b[d % DRU][kb][1], ah, cs2);
+                cb = mfma_f16(b[d % DRU][kb][0], ah, cb);
             }
             if constexpr (DU > DRU) {
                 if (d + DRU < DU) { fill(b[d % DRU], d + DRU); __builtin_amdgcn_sched_barrier(0); }
             }
-            if constexpr (F16) epi(nt, mt, cb + (cs + cs2) * DFF_F16_LINV);
-            else epi(nt, mt, (cb + cb2) + (cs + cs2));
+            epi(nt, mt, cb + (cs + cs2) * DFF_F16_LINV);
         }
     }
 }
 
 // The (tile, row-tile) units of a head group's G_ext GEMM (NT = 5 HGS column tiles x MT row tiles) on waves W0 .. W0 + NWV - 1 only,
 // results parked in registers (backward head pipeline: the other waves are busy with dS meanwhile).  Unit u = w + NWV d.
-template <int MT, int KB32, int NT, int W0, int NWV, bool F16 = false>
+template <int MT, int KB32, int NT, int W0, int NWV>
 DEVI void gx_units_hold(const lu32* as, int R, int rowsA, const unsigned* __restrict__ Wp, int nt0,
                         f32x4 (&held)[(NT * MT + NWV - 1) / NWV]) {
-    constexpr int NPC = F16 ? 2 : 3;
     constexpr int NU = NT * MT, DU = (NU + NWV - 1) / NWV, LHS2 = (32 * KB32 + DFF_SPAD) / 2;
-    // ring of two entries; at K = 128 an entry is HALF a unit (two k-blocks, 24 registers): whole units -- 96 registers in
-    // flight -- were what made trp-cage's shape spill with this pipeline
+    // ring of two entries; at K = 128 an entry is HALF a unit (two k-blocks, 16 registers): whole units in flight were what made
+    // trp-cage's shape spill with this pipeline
     constexpr int NHALF = (KB32 % 2 == 0 && KB32 >= 4) ? 2 : 1, KH = KB32 / NHALF, NE = DU * NHALF;
     const int tid_ = tid_now();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6) - W0;
     const int kg = lane >> 4, mm = lane & 15;
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
-    u32x4 b[2][KH][3];
-    auto fill = [&](u32x4 (&slot)[KH][3], int e) {
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    u32x4 b[2][KH][2];
+    auto fill = [&](u32x4 (&slot)[KH][2], int e) {
         const int nt = min(wave + NWV * (e / NHALF), NU - 1) / MT;
 #pragma unroll
         for (int kb = 0; kb < KH; ++kb)
 #pragma unroll
-            for (int p = 0; p < NPC; ++p) slot[kb][p] = wp[(((size_t)(nt0 + nt) * KB32 + (e % NHALF) * KH + kb) * NPC + p) * 64];
+            for (int p = 0; p < 2; ++p) slot[kb][p] = wp[(((size_t)(nt0 + nt) * KB32 + (e % NHALF) * KH + kb) * 2 + p) * 64];
     };
     fill(b[0], 0);
     if (NE > 1) fill(b[1], 1);
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 cs, cb, cs2, cb2;
+    f32x4 cs, cb, cs2;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         const int d = e / NHALF, h = e % NHALF;
         const int u = min(wave + NWV * d, NU - 1);
         const int mt = u - (u / MT) * MT;
         const int ro = min(mt * 16 + mm, rowsA - 1) * LHS2 + 4 * kg;
-        if (h == 0) { cs = (f32x4){0.f, 0.f, 0.f, 0.f}; cb = cs; cs2 = cs; cb2 = cs; }
+        if (h == 0) { cs = (f32x4){0.f, 0.f, 0.f, 0.f}; cb = cs; cs2 = cs; }
 #pragma unroll
         for (int kb = 0; kb < KH; ++kb) {
             const int ka = h * KH + kb;
             const u32x4 ah = *(const lu32x4*)(as + ro + 16 * ka);
-            const u32x4 am = *(const lu32x4*)(as + R * LHS2 + ro + 16 * ka);
-            if constexpr (F16) {
-                cs = mfma_f16(b[e % 2][kb][0], am, cs);
-                cs2 = mfma_f16(b[e % 2][kb][1], ah, cs2);
-                cb = mfma_f16(b[e % 2][kb][0], ah, cb);
-            } else {
-            const u32x4 al = *(const lu32x4*)(as + 2 * R * LHS2 + ro + 16 * ka);
-            cs = mfma_bf16(b[e % 2][kb][0], al, cs);
-            cb = mfma_bf16(b[e % 2][kb][0], am, cb);
-            cs2 = mfma_bf16(b[e % 2][kb][2], ah, cs2);
-            cb2 = mfma_bf16(b[e % 2][kb][1], ah, cb2);
-            cs = mfma_bf16(b[e % 2][kb][1], am, cs);
-            cb = mfma_bf16(b[e % 2][kb][0], ah, cb);
-            }
+            const u32x4 al = *(const lu32x4*)(as + R * LHS2 + ro + 16 * ka);
+            cs = mfma_f16(b[e % 2][kb][0], al, cs);
+            cs2 = mfma_f16(b[e % 2][kb][1], ah, cs2);
+            cb = mfma_f16(b[e % 2][kb][0], ah, cb);
         }
         if (e + 2 < NE) { fill(b[e % 2], e + 2); __builtin_amdgcn_sched_barrier(0); }
-        if (h == NHALF - 1) held[d] = F16 ? cb + (cs + cs2) * DFF_F16_LINV : (cb + cb2) + (cs + cs2);
+        if (h == NHALF - 1) held[d] = cb + (cs + cs2) * DFF_F16_LINV;
     }
 }
 
-// One element of a split A operand: three 16-bit stores (row-major bf16 pieces [piece][R][LS], LS in bf16 units).
-template <bool F16 = false>
+// One element of a split A operand: two 16-bit stores of its fp16 pieces (h, l': dff_device.h split1h; row-major
+// [piece][R][LS], LS in 16-bit units).
 DEVI void store_split(lu16* as16, int R, int LS, int row, int col, float v) {
-    if constexpr (F16) {   // two fp16 pieces (h, l'): dff_device.h split1h
-        unsigned short hh, ll;
-        split1h(v, hh, ll);
-        as16[(0 * R + row) * LS + col] = hh;
-        as16[(1 * R + row) * LS + col] = ll;
-        return;
-    }
-    const unsigned uh = __float_as_uint(v) & 0xffff0000u;
-    const float r = v - __uint_as_float(uh);
-    const unsigned um = __float_as_uint(r) & 0xffff0000u;
-    const float r2 = r - __uint_as_float(um);
-    as16[(0 * R + row) * LS + col] = (unsigned short)(uh >> 16);
-    as16[(1 * R + row) * LS + col] = (unsigned short)(um >> 16);
-    as16[(2 * R + row) * LS + col] = (unsigned short)(__float_as_uint(r2) >> 16);
+    unsigned short hh, ll;
+    split1h(v, hh, ll);
+    as16[(0 * R + row) * LS + col] = hh;
+    as16[(1 * R + row) * LS + col] = ll;
 }
 // Four consecutive columns (col % 4 == 0) of one row: one 8-byte store per piece (LS2 = dwords per piece row, even).
-template <bool F16 = false>
 DEVI void store_split4(lu32* as, int R, int LS2, int row, int col, const f32x4 v) {
-    if constexpr (F16) {
-        unsigned h0, l0, h1, l1;
-        split2h(v[0], v[1], h0, l0);
-        split2h(v[2], v[3], h1, l1);
-        const int o = row * LS2 + (col >> 1);
-        *(lu32x2*)(as + 0 * R * LS2 + o) = (u32x2){h0, h1};
-        *(lu32x2*)(as + 1 * R * LS2 + o) = (u32x2){l0, l1};
-        return;
-    }
-    unsigned hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const unsigned uh = __float_as_uint(v[q]) & 0xffff0000u;
-        const float r = v[q] - __uint_as_float(uh);
-        const unsigned um = __float_as_uint(r) & 0xffff0000u;
-        const float r2 = r - __uint_as_float(um);
-        hh[q] = uh; mm[q] = um; ll[q] = __float_as_uint(r2);
-    }
+    unsigned h0, l0, h1, l1;
+    split2h(v[0], v[1], h0, l0);
+    split2h(v[2], v[3], h1, l1);
     const int o = row * LS2 + (col >> 1);
-    *(lu32x2*)(as + 0 * R * LS2 + o) = (u32x2){__builtin_amdgcn_perm(hh[1], hh[0], 0x07060302u), __builtin_amdgcn_perm(hh[3], hh[2], 0x07060302u)};
-    *(lu32x2*)(as + 1 * R * LS2 + o) = (u32x2){__builtin_amdgcn_perm(mm[1], mm[0], 0x07060302u), __builtin_amdgcn_perm(mm[3], mm[2], 0x07060302u)};
-    *(lu32x2*)(as + 2 * R * LS2 + o) = (u32x2){__builtin_amdgcn_perm(ll[1], ll[0], 0x07060302u), __builtin_amdgcn_perm(ll[3], ll[2], 0x07060302u)};
+    *(lu32x2*)(as + 0 * R * LS2 + o) = (u32x2){h0, h1};
+    *(lu32x2*)(as + 1 * R * LS2 + o) = (u32x2){l0, l1};
 }
 // The same with a compile-time k-block count: loop-free, so that the ring (D k-blocks ahead) is waited for exactly.
 // (PRE: the ring's first D k-blocks were requested by tall_ring_fill before the barrier in front of this GEMM)
-template <int NTW, int D, int MT = 1, bool F16 = false>
-DEVI void tall_ring_fill(u32x4 (&b)[D][NTW][3], const unsigned* __restrict__ Wp, int KBtot, int kb0, int ntiles) {
-    constexpr int NP = F16 ? 2 : 3;
+template <int NTW, int D, int MT = 1>
+DEVI void tall_ring_fill(u32x4 (&b)[D][NTW][2], const unsigned* __restrict__ Wp, int KBtot, int kb0, int ntiles) {
+    constexpr int NP = 2;
     const int tid_ = tid_now();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         const int nt = wave + DFF_NWAVES * i;
@@ -640,12 +517,12 @@ DEVI void tall_ring_fill(u32x4 (&b)[D][NTW][3], const unsigned* __restrict__ Wp,
     }
     asm volatile("" ::: "memory");
 }
-// F16: two-piece fp16 operands (see gemm_wide_split_st); the 2^11-scaled cross terms collect in a second accumulator set that is
+// Two-piece fp16 operands (see gemm_wide_split_st); the 2^11-scaled cross terms collect in a second accumulator set that is
 // folded into `acc` before the function returns (acc lives across head groups / FFN chunks in the callers).
-template <int MT, int NTW, int NKB, bool PRE = false, bool F16 = false>
+template <int MT, int NTW, int NKB, bool PRE = false>
 DEVI void gemm_tall_split_st_b(f32x4 (&acc)[NTW][MT], int LS2 /* dwords per piece row */, const lu32* as, int R, int rowsA,
-                             const unsigned* __restrict__ Wp, int KBtot, int kb0, int ntiles, u32x4 (&b)[NKB < 4 ? NKB : 4][NTW][3]) {
-    constexpr int NP = F16 ? 2 : 3;
+                             const unsigned* __restrict__ Wp, int KBtot, int kb0, int ntiles, u32x4 (&b)[NKB < 4 ? NKB : 4][NTW][2]) {
+    constexpr int NP = 2;
     const int tid_ = tid_now();
     constexpr int D = NKB < 4 ? NKB : 4;
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
@@ -653,7 +530,7 @@ DEVI void gemm_tall_split_st_b(f32x4 (&acc)[NTW][MT], int LS2 /* dwords per piec
     int rowoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) rowoff[mt] = min(mt * 16 + mm, rowsA - 1) * LS2 + 4 * kg;
-    const WPtr<gu32x4, DFF_WMODE(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gu32x4, dff_wmode(MT)> wp((const gu32x4*)Wp, (unsigned)lane & 63u);
     size_t tbase[NTW];
     bool tok[NTW];
 #pragma unroll
@@ -671,69 +548,46 @@ DEVI void gemm_tall_split_st_b(f32x4 (&acc)[NTW][MT], int LS2 /* dwords per piec
 #pragma unroll
                 for (int p = 0; p < NP; ++p) b[d][i][p] = wp[(tbase[i] + NP * d + p) * 64];
     }
-    f32x4 acc2[F16 ? NTW : 1][F16 ? MT : 1];
-    if constexpr (F16) {
+    f32x4 acc2[NTW][MT];
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
+    for (int i = 0; i < NTW; ++i)
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+        for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_sched_barrier(0);   // issue the ring's loads here (see gemm_wide_split_st)
-    // TPRE (up to three row tiles: 24 .. 36 more registers; trp-cage -1.3 %, villin -0.8 %, BBA and protein G neutral): the A fragments of k-block kb + 1 are requested before the products of
-    // k-block kb -- otherwise every k-block starts on the LDS latency of its own operands
-    constexpr bool TPRE = MT <= DFF_TPRE_MT;
-    u32x4 nh[TPRE ? MT : 1], nm[TPRE ? MT : 1], nl[TPRE ? MT : 1];
-    auto a_load = [&](u32x4 (&xl)[TPRE ? MT : 1], u32x4 (&xh)[TPRE ? MT : 1], u32x4 (&xm)[TPRE ? MT : 1], int kb) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) if constexpr (!F16) xl[mt] = *(const volatile lu32x4*)(as + 2 * R * LS2 + rowoff[mt] + 16 * kb);
+    // TPRE (up to three row tiles; trp-cage -1.3 %, villin -0.8 %, BBA and protein G neutral): the A fragments of k-block kb + 1
+    // are requested before the products of k-block kb -- otherwise every k-block starts on the LDS latency of its own operands
+    constexpr bool TPRE = MT <= TPRE_MT;
+    u32x4 nh[TPRE ? MT : 1], nl[TPRE ? MT : 1];
+    auto a_load = [&](u32x4 (&xh)[TPRE ? MT : 1], u32x4 (&xl)[TPRE ? MT : 1], int kb) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) xh[mt] = *(const volatile lu32x4*)(as + rowoff[mt] + 16 * kb);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) xm[mt] = *(const volatile lu32x4*)(as + R * LS2 + rowoff[mt] + 16 * kb);
+        for (int mt = 0; mt < MT; ++mt) xl[mt] = *(const volatile lu32x4*)(as + R * LS2 + rowoff[mt] + 16 * kb);
     };
-    if constexpr (TPRE) a_load(nl, nh, nm, 0);
+    if constexpr (TPRE) a_load(nh, nl, 0);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
         const int d = kb % D;
-        u32x4 ah[MT], am[MT], al[MT];
-        // (requested in the order the products consume them -- l, h, m pieces -- so that the first product waits for one
-        // read, not for nine)
+        u32x4 ah[MT], al[MT];
         if constexpr (TPRE) {
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) { al[mt] = nl[mt]; ah[mt] = nh[mt]; am[mt] = nm[mt]; }
-            if (kb + 1 < NKB) a_load(nl, nh, nm, kb + 1);
+            for (int mt = 0; mt < MT; ++mt) { ah[mt] = nh[mt]; al[mt] = nl[mt]; }
+            if (kb + 1 < NKB) a_load(nh, nl, kb + 1);
         } else {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) if constexpr (!F16) al[mt] = *(const volatile lu32x4*)(as + 2 * R * LS2 + rowoff[mt] + 16 * kb);
+            for (int mt = 0; mt < MT; ++mt) ah[mt] = *(const volatile lu32x4*)(as + rowoff[mt] + 16 * kb);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) ah[mt] = *(const volatile lu32x4*)(as + rowoff[mt] + 16 * kb);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) am[mt] = *(const volatile lu32x4*)(as + R * LS2 + rowoff[mt] + 16 * kb);
+            for (int mt = 0; mt < MT; ++mt) al[mt] = *(const volatile lu32x4*)(as + R * LS2 + rowoff[mt] + 16 * kb);
         }
 #pragma unroll
         for (int i = 0; i < NTW; ++i)
             if (i == 0 || tok[i]) {
-                if constexpr (F16) {
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][0], am[mt], acc2[i][mt]);
+                for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][0], al[mt], acc2[i][mt]);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][1], ah[mt], acc2[i][mt]);
+                for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][1], ah[mt], acc2[i][mt]);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_f16(b[d][i][0], ah[mt], acc[i][mt]);
-                } else {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], al[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][2], ah[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][1], am[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], am[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][1], ah[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], ah[mt], acc[i][mt]);
-                }
+                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_f16(b[d][i][0], ah[mt], acc[i][mt]);
             }
         if (kb + D < NKB) {
 #pragma unroll
@@ -743,61 +597,19 @@ DEVI void gemm_tall_split_st_b(f32x4 (&acc)[NTW][MT], int LS2 /* dwords per piec
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    if constexpr (F16) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
+    for (int i = 0; i < NTW; ++i)
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[i][mt] += acc2[i][mt] * DFF_F16_LINV;
-    }
+        for (int mt = 0; mt < MT; ++mt) acc[i][mt] += acc2[i][mt] * DFF_F16_LINV;
 }
 
-template <int MT, int NTW, int NKB, bool F16 = false>
+template <int MT, int NTW, int NKB>
 DEVI void gemm_tall_split_st(f32x4 (&acc)[NTW][MT], int LS2, const lu32* as, int R, int rowsA,
                              const unsigned* __restrict__ Wp, int KBtot, int kb0, int ntiles) {
-    u32x4 b[NKB < 4 ? NKB : 4][NTW][3];
-    gemm_tall_split_st_b<MT, NTW, NKB, false, F16>(acc, LS2, as, R, rowsA, Wp, KBtot, kb0, ntiles, b);
+    u32x4 b[NKB < 4 ? NKB : 4][NTW][2];
+    gemm_tall_split_st_b<MT, NTW, NKB, false>(acc, LS2, as, R, rowsA, Wp, KBtot, kb0, ntiles, b);
 }
 
-#ifndef DFF_WOPRE
-#define DFF_WOPRE 1
-#endif
-#ifndef DFF_L2W
-#define DFF_L2W 1
-#endif
-#ifndef DFF_PSPLIT
-#define DFF_PSPLIT 1   // co_dqkv_rows: dQ / dK as bf16 pieces
-#endif
-#ifndef DFF_DQKV_ROWS
-#define DFF_DQKV_ROWS 1   // four row tiles: a wave owns a row tile's column tiles in the three-phase dV / dQ / dK products
-#endif
-#ifndef DFF_GXTILE0
-#define DFF_GXTILE0 1
-#endif
-#ifndef DFF_GXTILE
-#define DFF_GXTILE 1   // backward head pipeline: a spare wave parks a whole G_ext tile (all row tiles) where tiles == spare waves
-#endif
-#ifndef DFF_XFAST
-#define DFF_XFAST 1   // PAIR: plain stores / L2-served loads when both blocks of a pair report the same XCD (0: always sc1)
-#endif
-#ifndef DFF_GXT
-#define DFF_GXT 1
-#endif
-#ifndef DFF_K2
-#define DFF_K2 1   // wide split GEMMs at four row tiles: two output tiles per wave off one A read (gemm_wide_split_k2; three row tiles: measured 0.6 % slower, 204 B of scratch)
-#endif
-#ifndef DFF_EXTPRE
-#define DFF_EXTPRE 1   // extension-block weights of the tall GEMMs requested before the split GEMM (0: behind it, as until round 3)
-#endif
-#ifndef DFF_QSP
-#define DFF_QSP 1   // dQ leaves co_ds as bf16 pieces (0: fp32, split by every wave of the back-projection)
-#endif
-// The knobs above are measured decisions (DESIGN.md / DESIGN_HISTORY.md name each A/B); a build that changes one is a development
-// build and has to say so: -DDFF_EXPERIMENT, which dff_version() reports next to the flags.
-#if !defined(DFF_EXPERIMENT) && (DFF_F16G != 15 || DFF_AUXLATE != 1 || DFF_APRE != 1 || DFF_PIPEB_128_2 != 1 || DFF_QTPRE != 1 || DFF_TPRE_MT != 3 || \
-     DFF_K2_MT != 3 || DFF_ARES_LIM != 8 || DFF_ARES != 1 || DFF_WOPRE != 1 || DFF_L2W != 1 || DFF_PSPLIT != 1 || DFF_DQKV_ROWS != 1 || \
-     DFF_GXTILE0 != 1 || DFF_GXTILE != 1 || DFF_XFAST != 1 || DFF_GXT != 1 || DFF_K2 != 1 || DFF_EXTPRE != 1 || DFF_QSP != 1)
-#error "non-default tuning knobs: a development build -- add -DDFF_EXPERIMENT (dff_version() then says so)"
-#endif
 // L2 warm-up.  The weights of a phase are what all 32 workgroups of an XCD ask their L2 for at about the same time; they are
 // 15 MB per step (villin) against 4 MB of L2, so whoever is first pays the trip to memory and the others queue behind the
 // same lines: the convoy moves at the pace of a miss per phase.  Here each workgroup requests 1/32 of the NEXT phase's lines
@@ -821,14 +633,15 @@ DEVI void l2_touch(unsigned junk_byte, const void* base, int ntiles, size_t stri
     }
 }
 
-// QSP (round 4): dQ arrives as pieces as well (co_ds: [h | m] in place of the fp32 row of buffer regQ, l in `lsq`).
-// F16 (round 5): two-piece fp16 operands -- the in-place pieces are [h | l'] (put_piece16), nothing lives in lsp / lsq, operands
-// that arrive as fp32 rows are scaled by qs and split here (split8h); `acc` collects scaled units (the caller's row stage
-// multiplies the inverse back).
-template <int MT, int NTW, int HGS, bool KVS = false, bool VSP = false, int PRE = 0, bool QSP = false, bool F16 = false>
+// The ring b keeps a third (unused) entry per unit, as when the format had three pieces: with two the register allocator
+// assigns the accumulators differently (the same instructions, reordered registers).
+// Two-piece fp16 operands: dQ (QSP, co_ds), dK (KVS) and dV (VSP) arrive as pieces [h | l'] in place of their fp32 rows
+// (put_piece16); operands that arrive as fp32 rows are scaled by qs and split here (split8h).  `acc` collects scaled units (the
+// caller's row stage multiplies the inverse back).
+template <int MT, int NTW, int HGS, bool KVS = false, bool VSP = false, int PRE = 0, bool QSP = false>
 DEVI void gemm_tall_qkvT_split(f32x4 (&acc)[NTW][MT], const lfloat* Rg, int regQ, int RN, const unsigned* __restrict__ Ws,
-                               int head0, int ntiles, const lu32* lsp, u32x4 (&b)[4][NTW][3], const lu32* lsq = nullptr, float qs = 1.0f) {
-    constexpr int LQ = 80 * HGS + 4, NKB = 6 * HGS, D = 4, KBtot = 6 * DFF_HEADS, NPC = F16 ? 2 : 3;
+                               int head0, int ntiles, u32x4 (&b)[4][NTW][3], float qs) {
+    constexpr int LQ = 80 * HGS + 4, NKB = 6 * HGS, D = 4, KBtot = 6 * DFF_HEADS, NPC = 2;
     const int tid_ = tid_now();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
     const int kg = lane >> 4, mm = lane & 15;
@@ -853,89 +666,58 @@ DEVI void gemm_tall_qkvT_split(f32x4 (&acc)[NTW][MT], const lfloat* Rg, int regQ
 #pragma unroll
                 for (int p = 0; p < NPC; ++p) b[d][i][p] = wp[(tbase[i] + NPC * d + p) * 64];
     }
-    f32x4 acc2[F16 ? NTW : 1][F16 ? MT : 1];
-    if constexpr (F16) {
+    f32x4 acc2[NTW][MT];
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
+    for (int i = 0; i < NTW; ++i)
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+        for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_sched_barrier(0);
     // QTPRE: every operand arrives as pieces (dQ, dK and dV all split by their producers) and the shape has up to three row
     // tiles: the fragments of k-block kb + 1 are requested before the products of kb (as in gemm_tall_split_st_b)
-    constexpr bool QTPRE = KVS && VSP && QSP && MT <= DFF_TPRE_MT && DFF_QTPRE;
-    u32x4 nh[QTPRE ? MT : 1], nm[QTPRE ? MT : 1], nl[QTPRE ? MT : 1];
-    auto p_load = [&](u32x4 (&xl)[QTPRE ? MT : 1], u32x4 (&xh)[QTPRE ? MT : 1], u32x4 (&xm)[QTPRE ? MT : 1], int kb) {
-        constexpr int LSV = 32 * HGS + 4;
+    constexpr bool QTPRE = KVS && VSP && QSP && MT <= TPRE_MT;
+    u32x4 nh[QTPRE ? MT : 1], nl[QTPRE ? MT : 1];
+    auto p_load = [&](u32x4 (&xh)[QTPRE ? MT : 1], u32x4 (&xl)[QTPRE ? MT : 1], int kb) {
         const int hh = kb / 6, part = (kb % 6) / 2, half = kb % 2;
         const lu32* const hb = (const lu32*)(Rg + (part == 0 ? regQ : part) * RN * LQ + hh * 80) + 16 * half;
-        const lu32* const lb = part == 1 ? (const lu32*)(Rg + (1 + half) * RN * LQ + hh * 80 + 64)
-                                         : (part == 2 ? lsp : lsq) + hh * 32 + 16 * half;
-        const int lmul = part == 1 ? LQ : LSV;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) if constexpr (!F16) xl[mt] = *(const volatile lu32x4*)(lb + min(mt * 16 + mm, RN - 1) * lmul + 4 * kg);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) xh[mt] = *(const volatile lu32x4*)(hb + rowoff[mt] - 4 * kg);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) xm[mt] = *(const volatile lu32x4*)(hb + 32 + rowoff[mt] - 4 * kg);
+        for (int mt = 0; mt < MT; ++mt) xl[mt] = *(const volatile lu32x4*)(hb + 32 + rowoff[mt] - 4 * kg);
     };
-    if constexpr (QTPRE) p_load(nl, nh, nm, 0);
+    if constexpr (QTPRE) p_load(nh, nl, 0);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
         const int d = kb % D;
         const int hh = kb / 6, part = (kb % 6) / 2, half = kb % 2;
         const int aoff = (part == 0 ? regQ : part) * RN * LQ + hh * 80 + 32 * half;
-        u32x4 ah[MT], am[MT], al[MT];
+        u32x4 ah[MT], al[MT];
         if constexpr (QTPRE) {
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) { al[mt] = nl[mt]; ah[mt] = nh[mt]; am[mt] = nm[mt]; }
-            if (kb + 1 < NKB) p_load(nl, nh, nm, kb + 1);
+            for (int mt = 0; mt < MT; ++mt) { ah[mt] = nh[mt]; al[mt] = nl[mt]; }
+            if (kb + 1 < NKB) p_load(nh, nl, kb + 1);
         } else if (KVS && (part == 1 || (VSP && part == 2) || (QSP && part == 0))) {
-            constexpr int LSV = 32 * HGS + 4;
             const lu32* const hb = (const lu32*)(Rg + (part == 0 ? regQ : part) * RN * LQ + hh * 80) + 16 * half;
-            const lu32* const lb = part == 1 ? (const lu32*)(Rg + (1 + half) * RN * LQ + hh * 80 + 64)
-                                             : (part == 2 ? lsp : lsq) + hh * 32 + 16 * half;
-            const int lmul = part == 1 ? LQ : LSV;
-            // (l, h, m: the order the products consume them)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) if constexpr (!F16) al[mt] = *(const volatile lu32x4*)(lb + min(mt * 16 + mm, RN - 1) * lmul + 4 * kg);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) ah[mt] = *(const volatile lu32x4*)(hb + rowoff[mt] - 4 * kg);   // row * LQ + 4 kg
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) am[mt] = *(const volatile lu32x4*)(hb + 32 + rowoff[mt] - 4 * kg);
+            for (int mt = 0; mt < MT; ++mt) al[mt] = *(const volatile lu32x4*)(hb + 32 + rowoff[mt] - 4 * kg);
         } else {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const lfloat* ap = Rg + aoff + rowoff[mt];
                 const f32x4 x0 = *(const lf32x4*)ap, x1 = *(const lf32x4*)(ap + 4);
-                if constexpr (F16) split8h(x0 * qs, x1 * qs, ah[mt], am[mt]);
-                else split8(x0, x1, ah[mt], am[mt], al[mt]);
+                split8h(x0 * qs, x1 * qs, ah[mt], al[mt]);
             }
         }
 #pragma unroll
         for (int i = 0; i < NTW; ++i)
             if (i == 0 || tok[i]) {
-                if constexpr (F16) {
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][0], am[mt], acc2[i][mt]);
+                for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][0], al[mt], acc2[i][mt]);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][1], ah[mt], acc2[i][mt]);
+                for (int mt = 0; mt < MT; ++mt) acc2[i][mt] = mfma_f16(b[d][i][1], ah[mt], acc2[i][mt]);
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_f16(b[d][i][0], ah[mt], acc[i][mt]);
-                } else {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], al[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][2], ah[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][1], am[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], am[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][1], ah[mt], acc[i][mt]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_bf16(b[d][i][0], ah[mt], acc[i][mt]);
-                }
+                for (int mt = 0; mt < MT; ++mt) acc[i][mt] = mfma_f16(b[d][i][0], ah[mt], acc[i][mt]);
             }
         if (kb + D < NKB) {
 #pragma unroll
@@ -945,12 +727,10 @@ DEVI void gemm_tall_qkvT_split(f32x4 (&acc)[NTW][MT], const lfloat* Rg, int regQ
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    if constexpr (F16) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i)
+    for (int i = 0; i < NTW; ++i)
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[i][mt] += acc2[i][mt] * DFF_F16_LINV;
-    }
+        for (int mt = 0; mt < MT; ++mt) acc[i][mt] += acc2[i][mt] * DFF_F16_LINV;
 }
 
 // wide GEMM with few output tiles (NTN * MT (tile, row-tile) units <= a few per wave): the UNITS, not the tiles, go
@@ -963,7 +743,7 @@ DEVI void gemm_wide_units(const lfloat* A, int lda, int rowsA, const float* __re
     constexpr int NU = NTN * MT, DU = (NU + DFF_NWAVES - 1) / DFF_NWAVES;
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
     const int kk = lane >> 4, mm = lane & 15;
-    const WPtr<gf32x4, DFF_WMODE(MT)> wp((const gf32x4*)Wp + (size_t)kb0 * 64, (unsigned)lane & 63u);
+    const WPtr<gf32x4, dff_wmode(MT)> wp((const gf32x4*)Wp + (size_t)kb0 * 64, (unsigned)lane & 63u);
     f32x4 b[DU][KB];
 #pragma unroll
     for (int d = 0; d < DU; ++d) {
@@ -1007,7 +787,7 @@ DEVI void gemm_tall_kb_st(f32x4 (&acc)[NTW][MT], KF kf, const lfloat* A, int lda
     int rowoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) rowoff[mt] = min(mt * 16 + mm, rowsA - 1) * lda + 4 * kk;
-    const WPtr<gf32x4, DFF_WMODE(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gf32x4, dff_wmode(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
     size_t tbase[NTW];
     bool tok[NTW];
 #pragma unroll
@@ -1077,7 +857,7 @@ template <int NTW, int NH, int MT = 1, class WK>
 DEVI void ext_fetch(ExtW<NTW, NH>& e, WK wk, const float* __restrict__ Wp, int KBtot, int ntiles) {
     const int tid_ = tid_now();
     const int lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
-    const WPtr<gf32x4, DFF_WMODE(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
+    const WPtr<gf32x4, dff_wmode(MT)> wp((const gf32x4*)Wp, (unsigned)lane & 63u);
 #pragma unroll
     for (int i = 0; i < NH; ++i)
 #pragma unroll
@@ -1186,10 +966,10 @@ DEVI void rstore(float* p, const float (&x)[H / LP], int sub) {
         else *(f32x2*)q = (f32x2){x[2 * j], x[2 * j + 1]};
     }
 }
-// A row stage's K = H GEMM input.  fp32 engine: the fp32 row into abuf.  Split engine (round 4): the three bf16 pieces
-// straight into the split A operand (as[piece][row][LHS2], what split_rows used to make of abuf in a pass -- and a workgroup
-// barrier -- of its own, four times per layer); abuf does not exist in those variants.
-template <int H, int LP, bool SPW, bool F16 = false>
+// A row stage's K = H GEMM input.  fp32 engine: the fp32 row into abuf.  Split engine: the two fp16 pieces straight into the
+// split A operand (as[piece][row][LHS2], what split_rows used to make of abuf in a pass -- and a workgroup barrier -- of its own,
+// four times per layer); abuf does not exist in those variants.
+template <int H, int LP, bool SPW>
 DEVI void rstore_a(const Ctx& c, int row, const float (&x)[H / LP], int sub) {
     using M = RowMap<H, LP>;
     if constexpr (!SPW) {
@@ -1200,27 +980,13 @@ DEVI void rstore_a(const Ctx& c, int row, const float (&x)[H / LP], int sub) {
         for (int j = 0; j < M::NV; ++j) {
             const int col = M::VW * sub + M::VW * LP * j;
             if constexpr (M::VW == 4) {
-                store_split4<F16>(c.asp, c.RNa, LHS2, row, col, (f32x4){x[4 * j], x[4 * j + 1], x[4 * j + 2], x[4 * j + 3]});
-            } else if constexpr (F16) {
+                store_split4(c.asp, c.RNa, LHS2, row, col, (f32x4){x[4 * j], x[4 * j + 1], x[4 * j + 2], x[4 * j + 3]});
+            } else {
                 unsigned h, l;
                 split2h(x[2 * j], x[2 * j + 1], h, l);
                 const int o = row * LHS2 + (col >> 1);
                 c.asp[0 * c.RNa * LHS2 + o] = h;
                 c.asp[1 * c.RNa * LHS2 + o] = l;
-            } else {
-                unsigned hh[2], mm[2], ll[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const float v = x[2 * j + q];
-                    const unsigned uh = __float_as_uint(v) & 0xffff0000u;
-                    const float r = v - __uint_as_float(uh);
-                    const unsigned um = __float_as_uint(r) & 0xffff0000u;
-                    hh[q] = uh; mm[q] = um; ll[q] = __float_as_uint(r - __uint_as_float(um));
-                }
-                const int o = row * LHS2 + (col >> 1);
-                c.asp[0 * c.RNa * LHS2 + o] = __builtin_amdgcn_perm(hh[1], hh[0], 0x07060302u);
-                c.asp[1 * c.RNa * LHS2 + o] = __builtin_amdgcn_perm(mm[1], mm[0], 0x07060302u);
-                c.asp[2 * c.RNa * LHS2 + o] = __builtin_amdgcn_perm(ll[1], ll[0], 0x07060302u);
             }
         }
     }
@@ -1305,8 +1071,8 @@ DEVI void gate_weights(float (&w)[3][H / LP], const float* g, int sub) {
 }
 
 // R0: nodes (resbuf) -> stash nodes_in ; LN1 -> abuf
-template <int H, int LP, bool SPW, bool F16 = false>
-DEVI void row_ln1(const Ctx& c, const DffLayerDev& lw, int l) {   // (F16: the GEMM behind it takes two-piece fp16 operands)
+template <int H, int LP, bool SPW>
+DEVI void row_ln1(const Ctx& c, const DffLayerDev& lw, int l) {
     const int tid_ = tid_now();
     constexpr int HC = H / LP, LH = H + 4;
     const int grp = tid_ / LP, sub = tid_ % LP;
@@ -1320,12 +1086,12 @@ DEVI void row_ln1(const Ctx& c, const DffLayerDev& lw, int l) {   // (F16: the G
         ln_stats<H, LP>(x, mean, rstd);
 #pragma unroll
         for (int i = 0; i < HC; ++i) x[i] = (x[i] - mean) * rstd * gam[i] + bet[i];
-        rstore_a<H, LP, SPW, F16>(c, row, x, sub);
+        rstore_a<H, LP, SPW>(c, row, x, sub);
     }
 }
 
 // R1: tbuf = attn_out, resbuf = nodes -> nodes1 (resbuf), stash attn_out, LN2 -> abuf
-template <int H, int LP, bool SPW, bool F16 = false>
+template <int H, int LP, bool SPW>
 DEVI void row_gate1_ln2(const Ctx& c, const DffLayerDev& lw, int l, const float* tbuf) {
     const int tid_ = tid_now();
     constexpr int HC = H / LP, LH = H + 4;
@@ -1346,7 +1112,7 @@ DEVI void row_gate1_ln2(const Ctx& c, const DffLayerDev& lw, int l, const float*
         ln_stats<H, LP>(n1, mean, rstd);
 #pragma unroll
         for (int i = 0; i < HC; ++i) n1[i] = (n1[i] - mean) * rstd * gam[i] + bet[i];
-        rstore_a<H, LP, SPW, F16>(c, row, n1, sub);
+        rstore_a<H, LP, SPW>(c, row, n1, sub);
     }
 }
 
@@ -1398,7 +1164,7 @@ DEVI void row_gate2(const Ctx& c, const DffModelDev& m, const DffLayerDev& lw, i
 }
 
 // RB1: dn (resbuf) through gate2 -> dff (abuf), dn1 partial (resbuf)
-template <int H, int LP, bool SPW, bool F16 = false>
+template <int H, int LP, bool SPW>
 DEVI void rowb_gate2(const Ctx& c, const DffLayerDev& lw, int l) {
     const int tid_ = tid_now();
     constexpr int HC = H / LP, LH = H + 4;
@@ -1426,14 +1192,14 @@ DEVI void rowb_gate2(const Ctx& c, const DffLayerDev& lw, int l) {
             ao[i] = dn[i] * g2 + dz * (w2[0][i] + w2[2][i]);
             nin[i] = dn[i] * (1.0f - g2) + dz * (w2[1][i] - w2[2][i]);
         }
-        if constexpr (F16) row_pow2_scale<H, LP>(c, row, ao, sub);   // (the FFN backward chain runs in scaled units)
-        rstore_a<H, LP, SPW, F16>(c, row, ao, sub);
+        if constexpr (SPW) row_pow2_scale<H, LP>(c, row, ao, sub);   // (the FFN backward chain runs in scaled units)
+        rstore_a<H, LP, SPW>(c, row, ao, sub);
         rstore<H, LP>(c.resbuf + row * LH, nin, sub);
     }
 }
 
 // RB2: tbuf = df ; dn1 = resbuf + LN2bwd(df) ; gate1 bwd -> dattn (abuf), dn_in partial (resbuf)
-template <int H, int LP, bool SPW, bool FIN = false, bool FOUT = false>
+template <int H, int LP, bool SPW>
 DEVI void rowb_ln2_gate1(const Ctx& c, const DffLayerDev& lw, int l, const float* tbuf) {
     const int tid_ = tid_now();
     constexpr int HC = H / LP, LH = H + 4;
@@ -1446,7 +1212,7 @@ DEVI void rowb_ln2_gate1(const Ctx& c, const DffLayerDev& lw, int l, const float
         gate_weights<H, LP>(w, lw.g1, sub);
         rload<H, LP>(gam, lw.ln2_g, sub);
         rload<H, LP>(df, tbuf + row * LH, sub);
-        if constexpr (FIN) {   // fp16 engine: the FFN backward chain ran in this row's scaled units (rowb_gate2)
+        if constexpr (SPW) {   // fp16 engine: the FFN backward chain ran in this row's scaled units (rowb_gate2)
             const float rinv = c.rsc[row];
 #pragma unroll
             for (int i = 0; i < HC; ++i) df[i] *= rinv;
@@ -1481,8 +1247,8 @@ DEVI void rowb_ln2_gate1(const Ctx& c, const DffLayerDev& lw, int l, const float
             ao[i] = d1[i] * g1 + dz * (w[0][i] + w[2][i]);
             nin[i] = d1[i] * (1.0f - g1) + dz * (w[1][i] - w[2][i]);
         }
-        if constexpr (FOUT) row_pow2_scale<H, LP>(c, row, ao, sub);   // (dattn row-scaled: the G_ext GEMM's epilogues multiply the inverse back)
-        rstore_a<H, LP, SPW, FOUT>(c, row, ao, sub);
+        if constexpr (SPW) row_pow2_scale<H, LP>(c, row, ao, sub);   // (dattn row-scaled: the G_ext GEMM's epilogues multiply the inverse back)
+        rstore_a<H, LP, SPW>(c, row, ao, sub);
         rstore<H, LP>(c.resbuf + row * LH, nin, sub);
     }
 }
@@ -1676,8 +1442,6 @@ DEVI void co_mm5(f32x4 (&c)[5], const lfloat* T, int mo, const lfloat* B, int ld
 // by the wave that owns the row tile, right before it uses them.
 struct CoGeo {
     lfloat *Rg, *Pbuf, *dSbuf, *xs, *dxw;   // dxw: this wave's partial dE/dx
-    lu32* lsp;                              // l pieces of dV (LdsLayout::lsplit)
-    lu32* lsq;                              // l pieces of dQ (behind them)
     lfloat* m12;                            // GEN: [m1 | m2] rows of the head group (backward)
     const int __attribute__((address_space(3))) * prow;   // protein index of each row, -1 for pad rows
     int N, RN, rows;
@@ -1696,8 +1460,7 @@ DEVI void block_pow2_scale(const lfloat* rsc, float& qs, float& qsi) {
     qs = __uint_as_float((unsigned)(246 - ex) << 23);    // 2^-(ex - 127) 2^-8
     qsi = __uint_as_float((unsigned)(ex + 8) << 23);     // 2^(ex - 127) 2^8
 }
-// one element of dQ / dK / dV as the pieces the back-projection multiplies, in place of its fp32 row: [h | m] + l elsewhere (bf16), or
-// -- fp16 engine -- [h | l'] of the scaled value and nothing elsewhere
+// one element of dQ / dK / dV as the pieces the back-projection multiplies, in place of its fp32 row: [h | l'] of the scaled value
 DEVI void put_piece16(lu16* hm, float v, float qs) {
     unsigned short hh, ll;
     split1h(v * qs, hh, ll);
@@ -1769,7 +1532,7 @@ DEVI void co_fix_g(const CoGeo& g, int hh, int it, int lane) {   // G_ext ext: [
 // the same wave (its 16 probability rows are all it needs, so no barrier):
 // o_ext = P V_ext -> R0 rows of this tile (Q_ext rows of the tile are dead after its logits);
 // extension tile: xrel_i = sum_j a_ij x_j - x_i
-// SPW: the 64 regular columns of o_ext are written as bf16 pieces ([piece][RN][64 HGS + 8], into R3 | R4, free in the
+// SPW: the 64 regular columns of o_ext are written as fp16 pieces ([piece][RN][64 HGS + 8], into R3 | R4, free in the
 // forward pass) for gemm_tall_split; the extension columns stay fp32 in R0.
 template <int MT, int HGS, bool GEN, bool SPW = false, int PL_ = 16 * MT + 4>
 DEVI void co_softmax_pv(const CoGeo& g, gfloat* sP /* P block of head hg*HGS */, gfloat* sM /* m12 block of head hg*HGS (GEN) */,
@@ -1813,7 +1576,7 @@ DEVI void co_softmax_pv(const CoGeo& g, gfloat* sP /* P block of head hg*HGS */,
                 for (int jt = 0; jt < MT; ++jt) {
                     const float p = gi >= 0 ? e[jt] * rden : 0.f;
                     if (!TIGHT || (i < g.RN && 16 * jt + col < PL)) pl[16 * jt] = p;
-                    if (gi >= 0) st_ntg<DFF_SITE_ST(MT, 4)>(ps + 16 * jt, p);
+                    if (gi >= 0) st_ntg(ps + 16 * jt, p);
                 }
             }
         }
@@ -1826,7 +1589,7 @@ DEVI void co_softmax_pv(const CoGeo& g, gfloat* sP /* P block of head hg*HGS */,
                 lfloat* d = g.Rg + row * LQ + hh * 80 + col;
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) {
-                    if constexpr (SPW) store_split<(DFF_F16G & 1) != 0>((lu16*)(g.Rg + 3 * g.RN * LQ), g.RN, 64 * HGS + DFF_SPAD, row, hh * 64 + 16 * nt + col, o[nt][r]);
+                    if constexpr (SPW) store_split((lu16*)(g.Rg + 3 * g.RN * LQ), g.RN, 64 * HGS + DFF_SPAD, row, hh * 64 + 16 * nt + col, o[nt][r]);
                     else d[16 * nt] = o[nt][r];
                 }
                 if (!GEN) {
@@ -1845,7 +1608,7 @@ DEVI void co_softmax_pv(const CoGeo& g, gfloat* sP /* P block of head hg*HGS */,
                 const float D = quad_sum(tq);
                 if (row < g.rows) {
                     g.Rg[row * LQ + hh * 80 + 64 + col] = col < 3 ? e - xr : col == 3 ? D : 0.f;
-                    if (col < 4) st_ntg<DFF_SITE_ST(MT, 4)>(sM + ((size_t)hh * g.RN + row) * 4 + col, e);
+                    if (col < 4) st_ntg(sM + ((size_t)hh * g.RN + row) * 4 + col, e);
                 }
             }
         }
@@ -1936,7 +1699,7 @@ DEVI void co_softmax_pv_t(const CoGeo& g, gfloat* sP /* P block of head hg*HGS *
             const auto c01 = __builtin_amdgcn_permlane16_swap(a02[0], a13[0], false, false);
             const auto c23 = __builtin_amdgcn_permlane16_swap(a02[1], a13[1], false, false);
             const f32x4 row4 = {__uint_as_float(c01[0]), __uint_as_float(c01[1]), __uint_as_float(c23[0]), __uint_as_float(c23[1])};
-            st_ntg4<DFF_SITE_ST(MT, 4)>(gi >= 0 ? ps + 16 * jt : junk, row4);
+            st_ntg4(gi >= 0 ? ps + 16 * jt : junk, row4);
         }
         // o^T = (P V_ext)^T: first operand = V_ext (k = bead, column n), second = P from the registers
         f32x4 o[5];
@@ -1969,7 +1732,7 @@ DEVI void co_softmax_pv_t(const CoGeo& g, gfloat* sP /* P block of head hg*HGS *
         if (i < g.rows) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                if constexpr (SPW) store_split4<(DFF_F16G & 1) != 0>((lu32*)(g.Rg + 3 * g.RN * LQ), g.RN, (64 * HGS + DFF_SPAD) / 2, i, hh * 64 + 16 * nt + 4 * quad, o[nt]);
+                if constexpr (SPW) store_split4((lu32*)(g.Rg + 3 * g.RN * LQ), g.RN, (64 * HGS + DFF_SPAD) / 2, i, hh * 64 + 16 * nt + 4 * quad, o[nt]);
                 else *(lf32x4*)(g.Rg + i * LQ + hh * 80 + 16 * nt + 4 * quad) = o[nt];
             }
             // extension tile: xrel_i = sum_j a_ij x_j - x_i (columns 0..2; the others as the C-layout version leaves them)
@@ -2034,7 +1797,7 @@ DEVI void co_ds(const CoGeo& g) {
                     if (!TIGHT || (i < g.RN && 16 * jt + col < PL)) dl[16 * jt] = 0.125f * (p[jt] * (acc[jt][r] - sm));
             }
         }
-        if constexpr (DQ && QSP && DFF_QT16 && !GEN) {
+        if constexpr (DQ && QSP && !GEN) {
             // transposed tiles: this lane holds row 16 it + col, columns 16 nt + 4 quad .. + 3 of dQ_ext
             f32x4 dq[5];
             co_mm5<MT, false, 16 * MT + 4, NoStepHook, true>(dq, g.dSbuf + hh * PT, it, g.Rg + g.RN * LQ + hh * 80, LQ, g.RN, g.rows, lane);
@@ -2056,24 +1819,11 @@ DEVI void co_ds(const CoGeo& g) {
                 if (row < g.rows) {
                     lfloat* d = g.Rg + 4 * g.RN * LQ + row * LQ + hh * 80 + col;
                     if constexpr (QSP) {
-                        // the 64 regular columns leave as the bf16 pieces the back-projection multiplies (see co_dv_dk): split once
-                        // here instead of by each of the eight waves that read them
-                        constexpr int LSV = 32 * HGS + 4;
+                        // the 64 regular columns leave as the fp16 pieces the back-projection multiplies (see co_dv_dk): split
+                        // once here instead of by each of the eight waves that read them
                         lu16* const hm = (lu16*)(g.Rg + 4 * g.RN * LQ + hh * 80) + col;
-                        lu16* const lb0 = (lu16*)(g.lsq + hh * 32) + col;
-                        lu16* const lb1 = (lu16*)(g.lsq + hh * 32 + 16) + col;
 #pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const float v = dq[nt][r];
-                            if constexpr (DFF_QT16) { put_piece16(hm + row * 2 * LQ + 16 * nt, v, g.qs); continue; }
-                            const unsigned uh = __float_as_uint(v) & 0xffff0000u;
-                            const float r1 = v - __uint_as_float(uh);
-                            const unsigned um = __float_as_uint(r1) & 0xffff0000u;
-                            const float r2 = r1 - __uint_as_float(um);
-                            hm[row * 2 * LQ + 16 * nt] = (unsigned short)(uh >> 16);
-                            hm[row * 2 * LQ + 64 + 16 * nt] = (unsigned short)(um >> 16);
-                            (nt < 2 ? lb0 : lb1)[row * 2 * LSV + 16 * (nt & 1)] = (unsigned short)(__float_as_uint(r2) >> 16);
-                        }
+                        for (int nt = 0; nt < 4; ++nt) put_piece16(hm + row * 2 * LQ + 16 * nt, dq[nt][r], g.qs);
                         d[64] = dq[4][r];
                     } else {
 #pragma unroll
@@ -2118,7 +1868,7 @@ DEVI void co_dv_dk(const CoGeo& g, SH hook = SH()) {
             const int hh = r0 / MT, mo = r0 - hh * MT;
             const lfloat* T = (which ? g.dSbuf : g.Pbuf) + hh * PT;
             f32x4 acc[5];
-            if constexpr (KVS && VSP && DFF_QT16 && !GEN) {
+            if constexpr (KVS && VSP && !GEN) {
                 // transposed tiles (see co_ds): row 16 mo + col, columns 16 nt + 4 quad .. + 3; the extension tile's columns 0..2 = quad 0
                 co_mm5<MT, true, 16 * MT + 4, SH, true>(acc, T, mo, g.Rg + (which ? 0 : 3) * g.RN * LQ + hh * 80, LQ, g.RN, g.rows, lane, hook);
                 const int row = 16 * mo + col;
@@ -2137,28 +1887,13 @@ DEVI void co_dv_dk(const CoGeo& g, SH hook = SH()) {
             co_mm5<MT, true>(acc, T, mo, g.Rg + (which ? 0 : 3) * g.RN * LQ + hh * 80, LQ, g.RN, g.rows, lane, hook);
             lfloat* const dst = g.Rg + (which ? 1 : 2) * g.RN * LQ + hh * 80 + col;
             lu16* const hm = (lu16*)(g.Rg + (which ? 1 : 2) * g.RN * LQ + hh * 80) + col;
-            constexpr int LSV = 32 * HGS + 4;
-            // l pieces: columns 0..31 from lb0, 32..63 from lb1, row stride ls (16-bit units)
-            lu16* const lb0 = (which ? (lu16*)(g.Rg + 1 * g.RN * LQ + hh * 80 + 64) : (lu16*)(g.lsp + hh * 32)) + col;
-            lu16* const lb1 = (which ? (lu16*)(g.Rg + 2 * g.RN * LQ + hh * 80 + 64) : (lu16*)(g.lsp + hh * 32 + 16)) + col;
-            const int ls = which ? 2 * LQ : 2 * LSV;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 16 * mo + 4 * quad + r;
                 if (row < g.rows) {
                     if (KVS && (VSP || which)) {
 #pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const float v = acc[nt][r];
-                            if constexpr (DFF_QT16) { put_piece16(hm + row * 2 * LQ + 16 * nt, v, g.qs); continue; }
-                            const unsigned uh = __float_as_uint(v) & 0xffff0000u;
-                            const float r1 = v - __uint_as_float(uh);
-                            const unsigned um = __float_as_uint(r1) & 0xffff0000u;
-                            const float r2 = r1 - __uint_as_float(um);
-                            hm[row * 2 * LQ + 16 * nt] = (unsigned short)(uh >> 16);
-                            hm[row * 2 * LQ + 64 + 16 * nt] = (unsigned short)(um >> 16);
-                            (nt < 2 ? lb0 : lb1)[row * ls + 16 * (nt & 1)] = (unsigned short)(__float_as_uint(r2) >> 16);
-                        }
+                        for (int nt = 0; nt < 4; ++nt) put_piece16(hm + row * 2 * LQ + 16 * nt, acc[nt][r], g.qs);
                     } else {
 #pragma unroll
                         for (int nt = 0; nt < 4; ++nt) dst[row * LQ + 16 * nt] = acc[nt][r];
@@ -2208,9 +1943,8 @@ DEVI void co_dqkv(const CoGeo& g) {
 // single-tile items over 8 waves (three rounds of LDS-latency-bound 16 x 16 products: 24 scalar reads for 14 k-steps), wave w
 // takes row tile w & 3 and runs its column tiles {0, 1, 2} (w < 4) or {3, 4} (w >= 4) side by side off ONE read of the
 // tile-array operand: the two waves of a SIMD share a row tile's five products.
-// PSPLIT (split engine): dQ and dK leave as the bf16 pieces the back-projection multiplies ([h | m] in place of the fp32 row; dQ's
-// l pieces in g.lsq = the P tile array, dead after the dV phase; dK's in the extension columns of the R1 / R2 rows, as co_dv_dk
-// does); dV, whose phase has no dead buffer to put l pieces in, stays fp32 and is split by the back-projection's waves.
+// PSPLIT (split engine): dQ and dK leave as the fp16 pieces the back-projection multiplies ([h | l'] in place of the fp32 row, as
+// co_dv_dk does); dV stays fp32 and is split by the back-projection's waves.
 template <int MT, int WHICH, int PL_, bool PSPLIT = false>
 DEVI void co_dqkv_rows(const CoGeo& g) {
     static_assert(MT == 4 && DFF_NWAVES == 8, "two waves per row tile");
@@ -2220,34 +1954,18 @@ DEVI void co_dqkv_rows(const CoGeo& g) {
     const int tid_ = tid_now(), lane = tid_ & 63, wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
     const int quad = lane >> 4, col = lane & 15, mo = wave & (MT - 1);
     const lfloat* const T = WHICH == 0 ? g.Pbuf : g.dSbuf;
-    constexpr int LSV = 36;   // dwords per row of dQ's l pieces (LdsLayout::LSV at one head per group)
     auto put = [&](int nt, const f32x4& acc) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 16 * mo + 4 * quad + r;
             if (row < g.rows) {
                 if (WHICH != 1 && nt == 4) { if (col < 3) g.dxw[row * 4 + col] += acc[r]; }
-                else if (PSPLIT && WHICH != 0 && nt < 4) {
-                    lu16* const hm = (lu16*)(g.Rg + DST * g.RN * LQ) + col;
-                    lu16* const lb = (WHICH == 1 ? (lu16*)(g.lsq + (nt < 2 ? 0 : 16)) : (lu16*)(g.Rg + (nt < 2 ? 1 : 2) * g.RN * LQ + 64)) + col;
-                    const int ls = WHICH == 1 ? 2 * LSV : 2 * LQ;
-                    const float v = acc[r];
-                    if constexpr (DFF_QT16) put_piece16(hm + row * 2 * LQ + 16 * nt, v, g.qs);
-                    else {
-                    const unsigned uh = __float_as_uint(v) & 0xffff0000u;
-                    const float r1 = v - __uint_as_float(uh);
-                    const unsigned um = __float_as_uint(r1) & 0xffff0000u;
-                    const float r2 = r1 - __uint_as_float(um);
-                    hm[row * 2 * LQ + 16 * nt] = (unsigned short)(uh >> 16);
-                    hm[row * 2 * LQ + 64 + 16 * nt] = (unsigned short)(um >> 16);
-                    lb[row * ls + 16 * (nt & 1)] = (unsigned short)(__float_as_uint(r2) >> 16);
-                    }
-                } else g.Rg[DST * g.RN * LQ + row * LQ + 16 * nt + col] = acc[r];
+                else g.Rg[DST * g.RN * LQ + row * LQ + 16 * nt + col] = acc[r];
             }
         }
     };
     // fp16 engine: dQ / dK as transposed tiles (co_mmN<..., SWAP>): this lane holds row 16 mo + col, columns 16 nt + 4 quad .. + 3
-    constexpr bool SW = PSPLIT && WHICH != 0 && DFF_QT16;
+    constexpr bool SW = PSPLIT && WHICH != 0;
     auto put_t = [&](int nt, const f32x4& acc) {
         const int row = 16 * mo + col;
         if (row >= g.rows) return;
@@ -2323,7 +2041,7 @@ DEVI void co_reload_issue(CoReload<MT, HGS>& rl, const gfloat* sqkv /* head hg*H
     for (int u = 0; u < RL::U; ++u) {
         const unsigned code = rl.code[u];
         const gfloat* const base = (code >> 28 & 1u) ? sqkv : sP;
-        rl.t[u] = ld_ntg4<DFF_SITE_LD(MT, 1)>(base + 4 * (code & 0x3fffu));
+        rl.t[u] = ld_ntg4<dff_stash_ntl(MT)>(base + 4 * (code & 0x3fffu));
     }
     // without this the compiler sinks the loads down to their use in co_reload_commit (no global store in between)
     asm volatile("" ::: "memory");
@@ -2398,38 +2116,30 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
     // The last wave asks.  When matters: vmcnt retires in order, so the wave's next wait for a load of its own also waits
     // for the (missing) warm-up lines -- in the pipelined attention phases it asks after its own work, in the slack the
     // row-tile waves leave it before the barrier.
-    constexpr size_t UB = SPW ? 3072 : 1024;          // bytes of one (tile, k-block) unit
-    constexpr bool FWD16 = SPW && (DFF_F16G & 1);     // forward weight GEMMs on the two-piece fp16 format
-    constexpr size_t UBF = FWD16 ? 2048 : UB;         // ... whose images have 2 KB units
-    constexpr bool FFB16 = SPW && (DFF_F16G & 2);     // FFN backward (W2T, W1T) likewise, on row-scaled operands
-    constexpr size_t UBB2 = FFB16 ? 2048 : UB;
-    constexpr bool GX16 = SPW && (DFF_F16G & 4);      // G_ext (WoxT) likewise: dattn row-scaled, unscaled by the GEMM's epilogues
-    constexpr size_t UBG = GX16 ? 2048 : UB;
+    constexpr size_t UB = SPW ? 2048 : 1024;          // bytes of one (tile, k-block) unit
     lfloat* const rscl = (lfloat*)smem + ll.rsc;
-    constexpr bool QT16 = SPW && DFF_QT16 && GX16;    // QKV_ext^T likewise (needs the row scales of G_ext's input to derive its block scale)
-    constexpr size_t UBQ = QT16 ? 2048 : UB;
     constexpr int KQ = SPW ? 32 : 16;                 // rows of a k-block
     const int wave_l2 = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     auto l2w = [&](const void* base, size_t off, int ntiles, size_t stride, size_t bytes) {
-        if constexpr (SPW && DFF_L2W)   // (the fp32 variants are MFMA-bound: protein G measured 578.8 with, 578.6 us without)
+        if constexpr (SPW)   // (the fp32 variants are MFMA-bound: protein G measured 578.8 with, 578.6 us without)
             if (wave_l2 == DFF_NWAVES - 1) l2_touch(junk_b, (const char*)base + off, ntiles, stride, (int)(bytes >> 7));
     };
     auto l2w_flat = [&](const void* base, size_t off, size_t bytes) { l2w(base, off, 8, bytes / 8, bytes / 8); };
-    constexpr size_t QKV_HG = (size_t)HGS * 13 * (H / KQ) * UBF;    // Wqkvx: a head group's 13 HGS tiles, contiguous
-    constexpr size_t GX_HG = (size_t)HGS * 5 * (H / KQ) * UBG;      // WoxT: its 5 HGS tiles
-    constexpr size_t FFW_CH = (size_t)(LL::FC / 16) * (H / KQ) * UBB2;  // W2T: a chunk's tiles
-    constexpr size_t FFW1_CH = (size_t)(LL::FC / 16) * (H / KQ) * UBF;  // W1: likewise
+    constexpr size_t QKV_HG = (size_t)HGS * 13 * (H / KQ) * UB;    // Wqkvx: a head group's 13 HGS tiles, contiguous
+    constexpr size_t GX_HG = (size_t)HGS * 5 * (H / KQ) * UB;      // WoxT: its 5 HGS tiles
+    constexpr size_t FFW_CH = (size_t)(LL::FC / 16) * (H / KQ) * UB;  // W2T: a chunk's tiles
+    constexpr size_t FFW1_CH = (size_t)(LL::FC / 16) * (H / KQ) * UB;  // W1: likewise
     auto l2_wqkv = [&](const DffLayerDev& w, int hg) { l2w_flat(SPW ? (const void*)w.Wqkvx_s : (const void*)w.Wqkvx_p, hg * QKV_HG, QKV_HG); };
     auto l2_wgx = [&](const DffLayerDev& w, int hg) { l2w_flat(SPW ? (const void*)w.WoxT_s : (const void*)w.WoxT_p, hg * GX_HG, GX_HG); };
     auto l2_w1 = [&](const DffLayerDev& w, int ch) { l2w_flat(SPW ? (const void*)w.W1_s : (const void*)w.W1_p, ch * FFW1_CH, FFW1_CH); };
     auto l2_w2t = [&](const DffLayerDev& w, int ch) { l2w_flat(SPW ? (const void*)w.W2T_s : (const void*)w.W2T_p, ch * FFW_CH, FFW_CH); };
     // "tall" images (Nout = H): a few k-blocks of every one of the H / 16 tiles
     auto l2_tall = [&](const void* base, int kb0, int nkb, int kbtot, size_t ub = (SPW ? 3072 : 1024)) { l2w(base, (size_t)kb0 * ub, H / 16, (size_t)kbtot * ub, (size_t)nkb * ub); };
-    auto l2_w2 = [&](const DffLayerDev& w, int ch) { l2_tall(SPW ? (const void*)w.W2_s : (const void*)w.W2_p, ch * (LL::FC / KQ), LL::FC / KQ, LL::F / KQ, UBF); };
-    auto l2_w1t = [&](const DffLayerDev& w, int ch) { l2_tall(SPW ? (const void*)w.W1T_s : (const void*)w.W1T_p, ch * (LL::FC / KQ), LL::FC / KQ, LL::F / KQ, UBB2); };
+    auto l2_w2 = [&](const DffLayerDev& w, int ch) { l2_tall(SPW ? (const void*)w.W2_s : (const void*)w.W2_p, ch * (LL::FC / KQ), LL::FC / KQ, LL::F / KQ, UB); };
+    auto l2_w1t = [&](const DffLayerDev& w, int ch) { l2_tall(SPW ? (const void*)w.W1T_s : (const void*)w.W1T_p, ch * (LL::FC / KQ), LL::FC / KQ, LL::F / KQ, UB); };
     constexpr int WO_KB = SPW ? 2 : 5, WQT_KB = SPW ? 6 : 13;       // k-blocks per head (split: the 64 regular rows only)
-    auto l2_wo = [&](const DffLayerDev& w, int hg) { l2_tall(SPW ? (const void*)w.Wox_s : (const void*)w.Wox_p, hg * HGS * WO_KB, HGS * WO_KB, DFF_HEADS * WO_KB, UBF); };
-    auto l2_wqkvT = [&](const DffLayerDev& w, int hg) { l2_tall(SPW ? (const void*)w.WqkvxT_s : (const void*)w.WqkvxT_p, hg * HGS * WQT_KB, HGS * WQT_KB, DFF_HEADS * WQT_KB, UBQ); };
+    auto l2_wo = [&](const DffLayerDev& w, int hg) { l2_tall(SPW ? (const void*)w.Wox_s : (const void*)w.Wox_p, hg * HGS * WO_KB, HGS * WO_KB, DFF_HEADS * WO_KB, UB); };
+    auto l2_wqkvT = [&](const DffLayerDev& w, int hg) { l2_tall(SPW ? (const void*)w.WqkvxT_s : (const void*)w.WqkvxT_p, hg * HGS * WQT_KB, HGS * WQT_KB, DFF_HEADS * WQT_KB, UB); };
     c.xst = smem + ll.xst; c.xs = smem + ll.xs; c.dxs = smem + ll.dxs; c.vst = smem + ll.vst;
     c.cm = smem + ll.cm; c.tn = smem + ll.tn;
     c.abuf = smem + ll.abuf;
@@ -2522,9 +2232,6 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
         geo.Rg = sm + ll.Rg; geo.Pbuf = sm + ll.Pbuf; geo.dSbuf = sm + ll.dSbuf; geo.xs = sm + ll.xs;
         geo.dxw = sm + ll.dxw + wave_ * RN * 4;
         geo.m12 = sm + ll.m12;
-        geo.lsp = (lu32*)(sm + ll.lsplit);
-        geo.lsq = geo.lsp + RN * LL::LSV;
-        if constexpr (LL::TIGHT_OK && SPW) geo.lsq = (lu32*)(sm + ll.Pbuf);   // (tight layout: the P tile array, dead after the dV phase)
         geo.prow = (const int __attribute__((address_space(3)))*)(sm + ll.prow);
         geo.N = N; geo.RN = RN; geo.rows = rows;
     }
@@ -2570,7 +2277,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
     // actually runs on (s_getreg_b32 HW_REG_XCC_ID) and reads its partner's, once per launch: when they agree, the one L2
     // they share IS their coherence point, and the tiles and flags travel as plain stores (acknowledged by that L2:
     // s_waitcnt vmcnt(0)) and L1-bypassing loads that hit it; otherwise the sc1 protocol runs as before.
-    if constexpr (PAIR && DFF_XFAST) {
+    if constexpr (PAIR) {
         unsigned* const xw = a.xflag + 1 + 2 * a.xpairs + 2 * unit;
         if (tid == 0) {
             const unsigned my_xcc = (__builtin_amdgcn_s_getreg(20 | ((4 - 1) << 11)) & 15u) + 1u;
@@ -2681,7 +2388,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 }
             } else {
                 l2_wqkv(lw, hg_lo);
-                row_ln1<H, LPG, SPW, FWD16>(c, lw, l);
+                row_ln1<H, LPG, SPW>(c, lw, l);
                 wg_sync<SPILL>();
             }
             pf.tick(1);
@@ -2695,12 +2402,11 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
             constexpr bool PIPE = SPW && !GEN && HGS == 1 && MT < 4;   // HGS = 2: the parked tiles (7 x MT) do not fit the register file; MT = 4: 16 parked tiles neither
             lfloat* const oxt = PIPE ? geo.dSbuf : nullptr;
             constexpr int DWO = 2 * HGS < 4 ? 2 * HGS : 4;
-            auto wo_gemm = [&](int hg, auto pre, u32x4 (&bw)[DWO][NTW][3]) {
+            auto wo_gemm = [&](int hg, auto pre, u32x4 (&bw)[DWO][NTW][2]) {
                 ExtW<NTW, HGS> ew;
-                if constexpr (DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 5 + 4; }, lw.Wox_p, DFF_HEADS * 5, NT_H);
-                gemm_tall_split_st_b<MT, NTW, 2 * HGS, decltype(pre)::value, FWD16>(acc_o, (64 * HGS + DFF_SPAD) / 2, (const lu32*)(geo.Rg + 3 * RN * LQ), RN, RN,
+                ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 5 + 4; }, lw.Wox_p, DFF_HEADS * 5, NT_H);
+                gemm_tall_split_st_b<MT, NTW, 2 * HGS, decltype(pre)::value>(acc_o, (64 * HGS + DFF_SPAD) / 2, (const lu32*)(geo.Rg + 3 * RN * LQ), RN, RN,
                                                      lw.Wox_s, 2 * DFF_HEADS, hg * HGS * 2, NT_H, bw);
-                if constexpr (!DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 5 + 4; }, lw.Wox_p, DFF_HEADS * 5, NT_H);
                 if (oxt) ext_apply<MT, NTW, HGS>(acc_o, ew, [=](int i) { return i * 16; }, oxt, 16 * HGS, RN, NT_H);
                 else ext_apply<MT, NTW, HGS>(acc_o, ew, [=](int i) { return i * 80 + 64; }, geo.Rg, LQ, RN, NT_H);
             };
@@ -2722,10 +2428,10 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                         const bool ok = valid && row < rows;
                         const f32x4 v = acc + (f32x4){aux[0], aux[1], aux[2], aux[3]};
                         if (ok) *(lf32x4*)(Rl + reg * RN * LQ + row * LQ + hh * 80 + 16 * (tt - 5 * reg + (reg >> 1)) + c4) = v;
-                        st_ntg4<DFF_SITE_ST(MT, 2)>(ok ? sq + (size_t)hh * RN * DFF_QKVW + (size_t)row * DFF_QKVW + 16 * tt + c4 : junk, v);
+                        st_ntg4(ok ? sq + (size_t)hh * RN * DFF_QKVW + (size_t)row * DFF_QKVW + 16 * tt + c4 : junk, v);
                     };
                 };
-                gemm_wide_split_st<MT, H / 32, NTQ, 4, 0, DFF_NWAVES, 3, FWD16>(asplit, RN, RN, lw.Wqkvx_s, hg_lo * NTQ, mk_pre(hg_lo), mk_epi(hg_lo));
+                gemm_wide_split_st<MT, H / 32, NTQ, 4, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.Wqkvx_s, hg_lo * NTQ, mk_pre(hg_lo), mk_epi(hg_lo));
                 co_fill_x<HGS, GEN>(geo);   // once per layer: the forward pass never overwrites the K_ext / V_ext extension columns
                 wg_sync<SPILL>();
                 pf.tick(3);
@@ -2735,7 +2441,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     if (wave_ < NI) {
                         co_softmax_pv_t<MT, HGS, SPW>(geo, sPl + (size_t)hg * HGS * RN * c.sl.PS, oxt, junk);
                     } else if (more) {
-                        gemm_wide_split_st<MT, H / 32, NTQ, 1, NI, NWH, 2, FWD16>(asplit, RN, RN, lw.Wqkvx_s, (hg + 1) * NTQ,
+                        gemm_wide_split_st<MT, H / 32, NTQ, 1, NI, NWH, 2>(asplit, RN, RN, lw.Wqkvx_s, (hg + 1) * NTQ,
                             [](int, float (&)[1]) {},
                             [&](int, int mt, const f32x4& acc, const float (&)[1], bool, int i) { held[i][mt] = acc; });
                     }
@@ -2744,9 +2450,8 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     l2_wo(lw, hg);
                     if (hg + 2 < hg_hi) l2_wqkv(lw, hg + 2);
                     else if (!more) l2_w1(lw, ch_lo);
-                    u32x4 bw[DWO][NTW][3];
-                    constexpr bool WOPRE = DFF_WOPRE;   // W_o's operands cross the barrier in registers
-                    if constexpr (WOPRE) tall_ring_fill<NTW, DWO, MT, FWD16>(bw, lw.Wox_s, 2 * DFF_HEADS, hg * HGS * 2, NT_H);
+                    u32x4 bw[DWO][NTW][2];   // W_o's operands cross the barrier in registers
+                    tall_ring_fill<NTW, DWO, MT>(bw, lw.Wox_s, 2 * DFF_HEADS, hg * HGS * 2, NT_H);
                     wg_sync<SPILL>();
                     pf.tick(4);
                     float bias4[CNTH][4];
@@ -2755,7 +2460,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
 #pragma unroll
                         for (int i = 0; i < CNTH; ++i) pre(min(wave_ - NI + NWH * i, NTQ - 1), bias4[i]);
                     }
-                    wo_gemm(hg, std::integral_constant<bool, WOPRE>(), bw);
+                    wo_gemm(hg, std::true_type(), bw);
                     if (more && wave_ >= NI) {
                         auto epi = mk_epi(hg + 1);
 #pragma unroll
@@ -2792,11 +2497,11 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                             const bool ok = valid && row < rows;
                             const f32x4 v = acc + (f32x4){aux[0], aux[1], aux[2], aux[3]};
                             if (ok) *(lf32x4*)(Rl + reg * RN * LQ + row * LQ + hh * 80 + 16 * (tt - 5 * reg + (reg >> 1)) + c4) = v;
-                            st_ntg4<DFF_SITE_ST(MT, 2)>(ok ? sq + (size_t)hh * RN * DFF_QKVW + (size_t)row * DFF_QKVW + 16 * tt + c4 : junk, v);
+                            st_ntg4(ok ? sq + (size_t)hh * RN * DFF_QKVW + (size_t)row * DFF_QKVW + 16 * tt + c4 : junk, v);
                         };
                     if constexpr (SPW)
-                        if constexpr (MT >= DFF_K2_MT && DFF_K2) gemm_wide_split_k2<MT, H / 32, HGS * 13, 4, FWD16>(asplit, RN, RN, lw.Wqkvx_s, hg * HGS * 13, qkv_pre, qkv_epi);
-                        else gemm_wide_split_st<MT, H / 32, HGS * 13, 4, 0, DFF_NWAVES, 3, FWD16>(asplit, RN, RN, lw.Wqkvx_s, hg * HGS * 13, qkv_pre, qkv_epi);
+                        if constexpr (MT >= K2_MT) gemm_wide_split_k2<MT, H / 32, HGS * 13, 4>(asplit, RN, RN, lw.Wqkvx_s, hg * HGS * 13, qkv_pre, qkv_epi);
+                        else gemm_wide_split_st<MT, H / 32, HGS * 13, 4, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.Wqkvx_s, hg * HGS * 13, qkv_pre, qkv_epi);
                     else
                         gemm_wide_st<MT, NT_H, HGS * 13, 4>(abufL, LH, RN, lw.Wqkvx_p, hg * HGS * 13, qkv_pre, qkv_epi);
                 }
@@ -2816,7 +2521,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 if (hg + 1 < hg_hi) { if (!cached) l2_wqkv(lw, hg + 1); }
                 else l2_w1(lw, ch_lo);
                 if constexpr (SPW) {   // 64 regular rows per head on the split path, the extension block on the fp32 one
-                    { u32x4 bw[DWO][NTW][3]; wo_gemm(hg, std::false_type(), bw); }
+                    { u32x4 bw[DWO][NTW][2]; wo_gemm(hg, std::false_type(), bw); }
                 } else
                 gemm_tall_kb_st<MT, NTW, 5, 5 * HGS>(acc_o,
                     [=](int i, int& aoff, int& wkb) {
@@ -2831,7 +2536,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
             store_tall<MT, NTW>(acc_o, tbuf, LH, rows, NT_H, hf == 0 ? lw.bo : nullptr);
             pair_exchange(tbuf, H, LH);
             wg_sync<SPILL>();
-            row_gate1_ln2<H, LPG, SPW, FWD16>(c, lw, l, tbuf);
+            row_gate1_ln2<H, LPG, SPW>(c, lw, l, tbuf);
             wg_sync<SPILL>();
             pf.tick(7);
             // FFN: Linear(H,4H) -> GELU(erf) -> Linear(4H,H)   (graph_transformer.py:264-267)
@@ -2851,16 +2556,16 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                             f32x4 gv, gp;
 #pragma unroll
                             for (int r = 0; r < 4; ++r) { float v_, p_; gelu_both(acc[r] + aux[r], v_, p_); gv[r] = v_; gp[r] = p_; }
-                            st_ntg4<DFF_SITE_ST(MT, 8)>(ok ? shp + (size_t)row * F + cl : junk, gp);   // the slot "h_pre" holds gelu'(h_pre)
+                            st_ntg4(ok ? shp + (size_t)row * F + cl : junk, gp);   // the slot "h_pre" holds gelu'(h_pre)
                             if (ok) {
-                                if constexpr (SPW) store_split4<FWD16>((lu32*)hl, RN, (FC + DFF_SPAD) / 2, row, cl, gv);
+                                if constexpr (SPW) store_split4((lu32*)hl, RN, (FC + DFF_SPAD) / 2, row, cl, gv);
                                 else *(lf32x4*)(hl + row * LF + cl) = gv;
                             }
                         };
                     l2_w2(lw, ch);
                     if constexpr (SPW)
-                        if constexpr (MT >= DFF_K2_MT && DFF_K2) gemm_wide_split_k2<MT, H / 32, FC / 16, 4, FWD16>(asplit, RN, RN, lw.W1_s, ch * (FC / 16), w1_pre, w1_epi);
-                        else gemm_wide_split_st<MT, H / 32, FC / 16, 4, 0, DFF_NWAVES, 3, FWD16>(asplit, RN, RN, lw.W1_s, ch * (FC / 16), w1_pre, w1_epi);
+                        if constexpr (MT >= K2_MT) gemm_wide_split_k2<MT, H / 32, FC / 16, 4>(asplit, RN, RN, lw.W1_s, ch * (FC / 16), w1_pre, w1_epi);
+                        else gemm_wide_split_st<MT, H / 32, FC / 16, 4, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.W1_s, ch * (FC / 16), w1_pre, w1_epi);
                     else
                         gemm_wide_st<MT, NT_H, FC / 16, 4>(abufL, LH, RN, lw.W1_p, ch * (FC / 16), w1_pre, w1_epi);
                 }
@@ -2869,7 +2574,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 if (ch + 1 < ch_hi) l2_w1(lw, ch + 1);
                 else if (l == m.L - 1 && m.conservative) l2_w2t(lw, ch_lo);
                 if constexpr (SPW)
-                    gemm_tall_split_st<MT, NTW, FC / 32, FWD16>(acc_f, (FC + DFF_SPAD) / 2, (const lu32*)geo.Rg, RN, RN, lw.W2_s, F / 32, ch * (FC / 32), NT_H);
+                    gemm_tall_split_st<MT, NTW, FC / 32>(acc_f, (FC + DFF_SPAD) / 2, (const lu32*)geo.Rg, RN, RN, lw.W2_s, F / 32, ch * (FC / 32), NT_H);
                 else
                 gemm_tall_kb_st<MT, NTW, 0, FC / 16>(acc_f,
                     [=](int i, int& aoff, int& wkb) { aoff = 16 * i; wkb = ch * (FC / 16) + i; },
@@ -2890,7 +2595,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
             const DffLayerDev& lw = m.layer[l];
             const float* sb = c.stash + (size_t)l * c.sl.layer_stride;
             if (l < m.L - 1) l2_w2t(lw, ch_lo);
-            rowb_gate2<H, LPG, SPW, FFB16>(c, lw, l);
+            rowb_gate2<H, LPG, SPW>(c, lw, l);
             wg_sync<SPILL>();
             pf.tick(11);
             // dh = dff W2 ; dh_pre = dh * gelu'(h_pre) ; df = dh_pre W1
@@ -2905,20 +2610,20 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                             const int lane = tid & 63, cl = 16 * nt + 4 * (lane >> 4);
 #pragma unroll
                             for (int mt = 0; mt < MT; ++mt)
-                                ld4_aux<DFF_SITE_LD(MT, 16)>(aux + 4 * mt, shp + (size_t)min(mt * 16 + (lane & 15), rows - 1) * F + cl);
+                                ld4_aux<dff_stash_ntl(MT)>(aux + 4 * mt, shp + (size_t)min(mt * 16 + (lane & 15), rows - 1) * F + cl);
                         };
                     auto w2t_epi = [=](int nt, int mt, const f32x4& acc, const float (&aux)[4 * MT], bool valid, int) {
                             const int lane = tid & 63, cl = 16 * nt + 4 * (lane >> 4), row = mt * 16 + (lane & 15);
                             if (valid && row < rows) {
                                 const f32x4 v = acc * (f32x4){aux[mt * 4], aux[mt * 4 + 1], aux[mt * 4 + 2], aux[mt * 4 + 3]};
-                                if constexpr (SPW) store_split4<FFB16>((lu32*)hl, RN, (FC + DFF_SPAD) / 2, row, cl, v);
+                                if constexpr (SPW) store_split4((lu32*)hl, RN, (FC + DFF_SPAD) / 2, row, cl, v);
                                 else *(lf32x4*)(hl + row * LF + cl) = v;
                             }
                         };
                     l2_w1t(lw, ch);
                     if constexpr (SPW)
-                        if constexpr (MT >= DFF_K2_MT && DFF_K2) gemm_wide_split_k2<MT, H / 32, FC / 16, 4 * MT, FFB16>(asplit, RN, RN, lw.W2T_s, ch * (FC / 16), w2t_pre, w2t_epi);
-                        else gemm_wide_split_st<MT, H / 32, FC / 16, 4 * MT, 0, DFF_NWAVES, 3, FFB16>(asplit, RN, RN, lw.W2T_s, ch * (FC / 16), w2t_pre, w2t_epi);
+                        if constexpr (MT >= K2_MT) gemm_wide_split_k2<MT, H / 32, FC / 16, 4 * MT>(asplit, RN, RN, lw.W2T_s, ch * (FC / 16), w2t_pre, w2t_epi);
+                        else gemm_wide_split_st<MT, H / 32, FC / 16, 4 * MT, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.W2T_s, ch * (FC / 16), w2t_pre, w2t_epi);
                     else
                         gemm_wide_st<MT, NT_H, FC / 16, 4 * MT>(abufL, LH, RN, lw.W2T_p, ch * (FC / 16), w2t_pre, w2t_epi);
                 }
@@ -2927,7 +2632,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 if (ch + 1 < ch_hi) l2_w2t(lw, ch + 1);
                 else l2_wgx(lw, hg_lo);
                 if constexpr (SPW)
-                    gemm_tall_split_st<MT, NTW, FC / 32, FFB16>(acc_f, (FC + DFF_SPAD) / 2, (const lu32*)geo.Rg, RN, RN, lw.W1T_s, F / 32, ch * (FC / 32), NT_H);
+                    gemm_tall_split_st<MT, NTW, FC / 32>(acc_f, (FC + DFF_SPAD) / 2, (const lu32*)geo.Rg, RN, RN, lw.W1T_s, F / 32, ch * (FC / 32), NT_H);
                 else
                 gemm_tall_kb_st<MT, NTW, 0, FC / 16>(acc_f,
                     [=](int i, int& aoff, int& wkb) { aoff = 16 * i; wkb = ch * (FC / 16) + i; },
@@ -2946,9 +2651,9 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
             CoReload<MT, HGS> rl;
             co_reload_plan<MT, HGS, PLT>(rl, geo, true, tid_now());
             co_reload_issue<MT, HGS>(rl, sqkv + (size_t)hg_lo * HGS * RN * DFF_QKVW, sPl + (size_t)hg_lo * HGS * RN * c.sl.PS);
-            rowb_ln2_gate1<H, LPG, SPW, FFB16, GX16>(c, lw, l, tbuf);
+            rowb_ln2_gate1<H, LPG, SPW>(c, lw, l, tbuf);
             wg_sync<SPILL>();
-            if constexpr (QT16) block_pow2_scale(rscl, geo.qs, geo.qsi);   // (this layer's dQ / dK / dV scale, from dattn's row scales)
+            if constexpr (SPW) block_pow2_scale(rscl, geo.qs, geo.qsi);   // (this layer's dQ / dK / dV scale, from dattn's row scales)
             pf.tick(14);
             f32x4 acc_a[NTW][MT];
             acc_zero<MT, NTW>(acc_a);
@@ -2956,10 +2661,9 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
             // Backward head pipeline of the variants that have one in the forward pass (SPW, !GEN, HGS = 1): dS / dQ keep only
             // MT waves busy, so the others compute G_ext of the NEXT head meanwhile (5 MT units, parked in registers) and
             // write it once dV / dK and the back-projection of the current head are done with R3.
-            // Measured per shape: (128,3,1) villin 631 -> 586 us, (96,2,2) BBA 338 -> 329; (128,2,2) trp-cage 363 -> 391 (the 20 parked
-            // units + two K = 128 weight tiles in flight spill: 248 B of scratch), so that shape keeps the serial loop.
-            constexpr bool PIPEB = SPW && !GEN && MT < 4 && HGS * MT < DFF_NWAVES && (5 * HGS * MT) % (DFF_NWAVES - HGS * MT) == 0 &&
-                                   (DFF_PIPEB_128_2 || !(H == 128 && HGS == 2));
+            // Measured per shape: (128,3,1) villin 631 -> 586 us, (96,2,2) BBA 338 -> 329; (128,2,2) trp-cage runs it with half-unit
+            // ring entries (gx_units_hold: whole units spilled there, 363 -> 391).
+            constexpr bool PIPEB = SPW && !GEN && MT < 4 && HGS * MT < DFF_NWAVES && (5 * HGS * MT) % (DFF_NWAVES - HGS * MT) == 0;
             if constexpr (PIPEB) {
                 constexpr int NI = HGS * MT, NWH = DFF_NWAVES - NI, NTG = 5 * HGS, DU = NTG * MT / NWH;
                 const int tid = tid_now();
@@ -2968,7 +2672,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 auto gx_epi = [=](int nt, int mt, const f32x4& acc0) {
                         const int lane = tid & 63, quad = lane >> 4, row = mt * 16 + (lane & 15);
                         const int hh = nt / 5, tt = nt - 5 * hh;
-                        const f32x4 acc = GX16 ? acc0 * rscl[row] : acc0;   // (fp16 engine: back to true units)
+                        const f32x4 acc = SPW ? acc0 * rscl[row] : acc0;   // (fp16 engine: back to true units)
                         if (row < rows) {
                             *(lf32x4*)(Gl + row * LQ + hh * 80 + 16 * tt + 4 * quad) = acc;
                             if (tt == 4 && quad == 0) {   // r = dE/dxrel: columns 64..66 of the head
@@ -2985,11 +2689,11 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                                                  sPl + (size_t)(hg + 1) * HGS * RN * c.sl.PS);
                     co_fill_x<HGS, GEN>(geo);
                 };
-                if constexpr (NTG == NWH && DFF_GXTILE0)   // (the first head's G_ext, all waves: whole tiles as well)
-                    gemm_wide_split_st<MT, H / 32, NTG, 1, 0, DFF_NWAVES, 3, GX16>(asplit, RN, RN, lw.WoxT_s, hg_lo * NTG, [](int, float (&)[1]) {},
+                if constexpr (NTG == NWH)   // (the first head's G_ext, all waves: whole tiles as well)
+                    gemm_wide_split_st<MT, H / 32, NTG, 1, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.WoxT_s, hg_lo * NTG, [](int, float (&)[1]) {},
                         [&](int nt, int mt, const f32x4& acc, const float (&)[1], bool valid, int) { if (valid) gx_epi(nt, mt, acc); });
                 else
-                gemm_wide_units_split<MT, H / 32, NTG, GX16>(asplit, RN, RN, lw.WoxT_s, hg_lo * NTG, gx_epi);
+                gemm_wide_units_split<MT, H / 32, NTG>(asplit, RN, RN, lw.WoxT_s, hg_lo * NTG, gx_epi);
                 commit_issue(hg_lo);
                 wg_sync<SPILL>();
                 pf.tick(16);
@@ -2998,18 +2702,18 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     const bool more = hg + 1 < hg_hi;
                     // (GXTILE: as many spare waves as G_ext has tiles -- villin's shape -- : a wave takes a whole TILE, all row tiles,
                     // so its 12 KB of weights cross the CU once; as (tile, row-tile) units three waves stream each tile)
-                    constexpr bool GXTILE = (NTG == NWH || DFF_GXTILE > 1) && DFF_GXTILE;
+                    constexpr bool GXTILE = NTG == NWH;
                     constexpr int CNTG = (NTG + NWH - 1) / NWH;   // tiles per spare wave (GXTILE)
                     f32x4 gheld[GXTILE ? CNTG * MT : DU];
                     if (wave_ < NI) {
-                        if (deep) co_ds<MT, HGS, true, GEN, PLT, LL::KVS && DFF_QSP>(geo);
+                        if (deep) co_ds<MT, HGS, true, GEN, PLT, LL::KVS>(geo);
                         else co_ds<MT, HGS, false, GEN>(geo);
                     } else if (more) {
                         if constexpr (GXTILE)
-                            gemm_wide_split_st<MT, H / 32, NTG, 1, NI, NWH, 2, GX16>(asplit, RN, RN, lw.WoxT_s, (hg + 1) * NTG, [](int, float (&)[1]) {},
+                            gemm_wide_split_st<MT, H / 32, NTG, 1, NI, NWH, 2>(asplit, RN, RN, lw.WoxT_s, (hg + 1) * NTG, [](int, float (&)[1]) {},
                                 [&](int, int mt, const f32x4& acc, const float (&)[1], bool, int i) { gheld[i * MT + mt] = acc; });
                         else
-                        gx_units_hold<MT, H / 32, NTG, NI, NWH, GX16>(asplit, RN, RN, lw.WoxT_s, (hg + 1) * NTG, gheld);
+                        gx_units_hold<MT, H / 32, NTG, NI, NWH>(asplit, RN, RN, lw.WoxT_s, (hg + 1) * NTG, gheld);
                     }
                     if (deep) l2_wqkvT(lw, hg);
                     if (hg + 2 < hg_hi) l2_wgx(lw, hg + 2);
@@ -3017,15 +2721,14 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     wg_sync<SPILL>();
                     pf.tick(17);
                     if (deep) {
-                        u32x4 bq[4][NTW][3];
+                        u32x4 bq[4][NTW][3];   // ([2] used: see gemm_tall_qkvT_split)
                         co_dv_dk<MT, HGS, false, GEN, LL::KVS, LL::VSP>(geo);
                         wg_sync<SPILL>();
                         pf.tick(18);
                         ExtW<NTW, HGS> ew;
-                        if constexpr (DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
-                        gemm_tall_qkvT_split<MT, NTW, HGS, LL::KVS, LL::VSP, 0, LL::KVS && DFF_QSP, QT16>(acc_a, geo.Rg, 4, RN, lw.WqkvxT_s, hg * HGS, NT_H, geo.lsp, bq, geo.lsq, geo.qs);
-                        if constexpr (!DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
-                        ext_apply<MT, NTW, HGS>(acc_a, ew, [=](int i) { return 4 * RN * LQ + i * 80 + 64; }, geo.Rg, LQ, RN, NT_H, QT16 ? geo.qs : 1.0f);
+                        ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
+                        gemm_tall_qkvT_split<MT, NTW, HGS, LL::KVS, LL::VSP, 0, LL::KVS>(acc_a, geo.Rg, 4, RN, lw.WqkvxT_s, hg * HGS, NT_H, bq, geo.qs);
+                        ext_apply<MT, NTW, HGS>(acc_a, ew, [=](int i) { return 4 * RN * LQ + i * 80 + 64; }, geo.Rg, LQ, RN, NT_H, SPW ? geo.qs : 1.0f);
                     } else {
                         co_dv_dk<MT, HGS, true, GEN>(geo);
                     }
@@ -3060,7 +2763,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     auto gx_epi = [=](int nt, int mt, const f32x4& acc0) {
                             const int lane = tid & 63, quad = lane >> 4, row = mt * 16 + (lane & 15);
                             const int hh = nt / 5, tt = nt - 5 * hh;
-                            const f32x4 acc = GX16 ? acc0 * rscl[row] : acc0;   // (fp16 engine: back to true units)
+                            const f32x4 acc = SPW ? acc0 * rscl[row] : acc0;   // (fp16 engine: back to true units)
                             if (row < rows) {
                                 *(lf32x4*)(Gl + row * LQ + hh * 80 + 16 * tt + 4 * quad) = acc;
                                 if (tt == 4 && quad == 0) {   // r = dE/dxrel: columns 64..66 of the head
@@ -3071,20 +2774,20 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                             }
                         };
                     if (l > 0 || full0) l2_wqkvT(lw, hg);
-                    if constexpr (SPW && MT == 4 && DFF_GXT)
+                    if constexpr (SPW && MT == 4)
                         // four row tiles: a wave takes a whole TILE (all row tiles), so its 12 KB of weights come through the CU
                         // once; as (tile, row-tile) units four waves each stream the same tile
-                        gemm_wide_split_st<MT, H / 32, HGS * 5, 1, 0, DFF_NWAVES, 3, GX16>(asplit, RN, RN, lw.WoxT_s, hg * HGS * 5, [](int, float (&)[1]) {},
+                        gemm_wide_split_st<MT, H / 32, HGS * 5, 1, 0, DFF_NWAVES, 3>(asplit, RN, RN, lw.WoxT_s, hg * HGS * 5, [](int, float (&)[1]) {},
                             [&](int nt, int mt, const f32x4& acc, const float (&)[1], bool valid, int) { if (valid) gx_epi(nt, mt, acc); });
                     else if constexpr (SPW)
-                        gemm_wide_units_split<MT, H / 32, HGS * 5, GX16>(asplit, RN, RN, lw.WoxT_s, hg * HGS * 5, gx_epi);
+                        gemm_wide_units_split<MT, H / 32, HGS * 5>(asplit, RN, RN, lw.WoxT_s, hg * HGS * 5, gx_epi);
                     else
                         gemm_wide_units<MT, NT_H, HGS * 5>(abufL, LH, RN, lw.WoxT_p, NT_H, 0, hg * HGS * 5, gx_epi, NoHook());
                     co_reload_commit<MT, HGS>(rl, geo);
                     if (GEN) {   // [m1 | m2] rows of this head group (contiguous in the stash and in LDS); before the
                                  // next group's rows are requested: a load issued after them would wait for them
                         const gfloat* const sM = (const gfloat*)sb + c.sl.m12 + (size_t)hg * HGS * RN * 4;
-                        for (int i2 = tid; i2 < HGS * RN * 4; i2 += DFF_NTHREADS) geo.m12[i2] = ld_ntg<DFF_SITE_LD(MT, 1)>(sM + i2);
+                        for (int i2 = tid; i2 < HGS * RN * 4; i2 += DFF_NTHREADS) geo.m12[i2] = ld_ntg<dff_stash_ntl(MT)>(sM + i2);
                     }
                     if (hg + 1 < hg_hi)
                         co_reload_issue<MT, HGS>(rl, sqkv + (size_t)(hg + 1) * HGS * RN * DFF_QKVW,
@@ -3095,18 +2798,18 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 pf.tick(16);
                 constexpr bool FIVE = LL::NREG == 5;
                 if (l > 0 || full0) {
-                    co_ds<MT, HGS, FIVE, GEN, PLT, SPW && LL::KVS && DFF_QSP>(geo);
+                    co_ds<MT, HGS, FIVE, GEN, PLT, SPW && LL::KVS>(geo);
                     wg_sync<SPILL>();
                     pf.tick(17);
                     if (FIVE) {
                         co_dv_dk<MT, HGS, false, GEN, SPW && LL::KVS, SPW && LL::VSP>(geo);
                     } else {
-                        if constexpr (MT == 4 && HGS == 1 && !GEN && DFF_DQKV_ROWS) {
+                        if constexpr (MT == 4 && HGS == 1 && !GEN) {
                             co_dqkv_rows<MT, 0, PLT>(geo);
                             wg_sync<SPILL>();
-                            co_dqkv_rows<MT, 1, PLT, SPW && DFF_PSPLIT>(geo);
+                            co_dqkv_rows<MT, 1, PLT, SPW>(geo);
                             wg_sync<SPILL>();
-                            co_dqkv_rows<MT, 2, PLT, SPW && DFF_PSPLIT>(geo);
+                            co_dqkv_rows<MT, 2, PLT, SPW>(geo);
                         } else {
                         co_dqkv<MT, HGS, 0, GEN, PLT>(geo);
                         wg_sync<SPILL>();
@@ -3121,15 +2824,14 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                     if (hg + 1 < hg_hi) l2_wgx(lw, hg + 1);
                     else if (l > 0) l2_w2t(m.layer[l - 1], ch_lo);
                     if constexpr (SPW) {
-                        u32x4 bq[4][NTW][3];
+                        u32x4 bq[4][NTW][3];   // ([2] used: see gemm_tall_qkvT_split)
                         ExtW<NTW, HGS> ew;
-                        if constexpr (DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
+                        ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
                         {
-                            constexpr bool RP = MT == 4 && HGS == 1 && !GEN && DFF_DQKV_ROWS && DFF_PSPLIT;   // co_dqkv_rows<..., PSPLIT>
-                            gemm_tall_qkvT_split<MT, NTW, HGS, LL::KVS || RP, LL::VSP, 0, (LL::KVS && DFF_QSP) || RP, QT16>(acc_a, geo.Rg, FIVE ? 4 : 3, RN, lw.WqkvxT_s, hg * HGS, NT_H, geo.lsp, bq, geo.lsq, geo.qs);
+                            constexpr bool RP = MT == 4 && HGS == 1 && !GEN;   // co_dqkv_rows<..., PSPLIT>
+                            gemm_tall_qkvT_split<MT, NTW, HGS, LL::KVS || RP, LL::VSP, 0, LL::KVS || RP>(acc_a, geo.Rg, FIVE ? 4 : 3, RN, lw.WqkvxT_s, hg * HGS, NT_H, bq, geo.qs);
                         }
-                        if constexpr (!DFF_EXTPRE) ext_fetch<NTW, HGS, MT>(ew, [=](int i) { return (hg * HGS + i) * 13 + 4; }, lw.WqkvxT_p, DFF_HEADS * 13, NT_H);
-                        ext_apply<MT, NTW, HGS>(acc_a, ew, [=](int i) { return (FIVE ? 4 : 3) * RN * LQ + i * 80 + 64; }, geo.Rg, LQ, RN, NT_H, QT16 ? geo.qs : 1.0f);
+                        ext_apply<MT, NTW, HGS>(acc_a, ew, [=](int i) { return (FIVE ? 4 : 3) * RN * LQ + i * 80 + 64; }, geo.Rg, LQ, RN, NT_H, SPW ? geo.qs : 1.0f);
                     } else
                     gemm_tall_kb_st<MT, NTW, 13, 13 * HGS>(acc_a,
                         [=](int i, int& aoff, int& wkb) {
@@ -3153,7 +2855,7 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_fused_kernel(const DffModelD
                 store_tall<MT, NTW>(acc_a, tbuf, LH, rows, NT_H, nullptr);
                 pair_exchange(tbuf, H, LH);
                 wg_sync<SPILL>();
-                rowb_ln1<H, LPG>(c, lw, l, tbuf, QT16 ? geo.qsi : 1.0f);
+                rowb_ln1<H, LPG>(c, lw, l, tbuf, SPW ? geo.qsi : 1.0f);
                 wg_sync<SPILL>();
                 pf.tick(20);
             }
@@ -3307,12 +3009,6 @@ __global__ __launch_bounds__(DFF_NTHREADS) void dff_debug_gemm_kernel(const floa
 // ------------------------------------------------------------------------------------------
 // variant table handed to the host dispatcher (dff_host.hip); taking the kernels' addresses instantiates them
 // ------------------------------------------------------------------------------------------
-// how the split variants name their engine: every weight GEMM on the two-piece fp16 format, or (any other DFF_F16G) "split_bf16"
-#if DFF_F16G == 15
-#define DFF_SPN "split_f16"
-#else
-#define DFF_SPN "split_bf16"
-#endif
 template <int H, int MT, int HGS, bool SP, bool SPW>
 static unsigned lds_floats_of(int N, int G) {
     // The TIGHT tile arrays (LdsLayout: 16 MT - 4 = 60 columns, no pad rows) are correct for at most 16 MT - 4 bead rows:
@@ -3329,21 +3025,21 @@ static unsigned lds_floats_of(int N, int G) {
       &lds_floats_of<H, MT, HGS, SP, false>, "dff_fused_kernel<" #H "," #MT "," #HGS "," #SP ",gen>" }
 #define VAR_SPW(H, MT, HGS)                                                                                     \
     { H, MT, HGS, false, false, true, (const void*)&dff_fused_kernel<H, MT, HGS, false, false, true>,           \
-      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false," DFF_SPN ">" },  \
+      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false,split_f16>" },  \
     { H, MT, HGS, false, true, true, (const void*)&dff_fused_kernel<H, MT, HGS, false, true, true>,             \
-      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false,gen," DFF_SPN ">" }
+      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false,gen,split_f16>" }
 #define VAR_SPW_SPILL(H, MT, HGS)                                                                               \
     { H, MT, HGS, true, false, true, (const void*)&dff_fused_kernel<H, MT, HGS, true, false, true>,             \
-      &lds_floats_of<H, MT, HGS, true, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",true," DFF_SPN ">" }
+      &lds_floats_of<H, MT, HGS, true, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",true,split_f16>" }
 #define VAR_PAIR_SPW_SPILL(H, MT, HGS)                                                                            \
     { H, MT, HGS, true, false, true, (const void*)&dff_fused_kernel<H, MT, HGS, true, false, true, true>,         \
-      &lds_floats_of<H, MT, HGS, true, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",true," DFF_SPN ",pair>", true }
+      &lds_floats_of<H, MT, HGS, true, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",true,split_f16,pair>", true }
 #define VAR_PAIR(H, MT, HGS, SP)                                                                                  \
     { H, MT, HGS, SP, false, false, (const void*)&dff_fused_kernel<H, MT, HGS, SP, false, false, true>,           \
       &lds_floats_of<H, MT, HGS, SP, false>, "dff_fused_kernel<" #H "," #MT "," #HGS "," #SP ",pair>", true }
 #define VAR_PAIR_SPW(H, MT, HGS)                                                                                  \
     { H, MT, HGS, false, false, true, (const void*)&dff_fused_kernel<H, MT, HGS, false, false, true, true>,       \
-      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false," DFF_SPN ",pair>", true }
+      &lds_floats_of<H, MT, HGS, false, true>, "dff_fused_kernel<" #H "," #MT "," #HGS ",false,split_f16,pair>", true }
 static const Variant g_variants[] = {
 #ifndef DFF_FAST_BUILD
     VAR(64, 1, 4, false),  VAR(64, 2, 2, false),  VAR(96, 1, 4, false),  VAR(96, 2, 2, false),
@@ -3360,7 +3056,6 @@ static const Variant g_variants[] = {
     VAR(64, 1, 4, false),
 #endif
 };
-int dff_fused_f16_mask() { return DFF_F16G; }
 const Variant* dff_fused_variants(int* count) {
     *count = (int)(sizeof(g_variants) / sizeof(g_variants[0]));
     return g_variants;

@@ -19,8 +19,8 @@
 //     du and both x-gradient terms of SURVEY.md section 8a "Derived math" fall out of the same
 //     16x16x4 MFMA tiles; no VALU contraction is left in the attention block.
 //
-// The attention products run on v_mfma_f32_16x16x4_f32, the weight GEMMs of the SPW variants on v_mfma_f32_16x16x32_bf16
-// through an exact three-way bf16 split (split engine below); VALU work is softmax (in the MFMA C layout), LayerNorm,
+// The attention products run on v_mfma_f32_16x16x4_f32, the weight GEMMs of the SPW variants on v_mfma_f32_16x16x32_f16
+// through a two-piece fp16 split at fp32 accuracy (split engine below); VALU work is softmax (in the MFMA C layout), LayerNorm,
 // gates, GELU and the integrator update.  One kernel per sampler mode (MODE template argument).
 // The FOLD variant (hidden == head dimension, <= 3 layers: chignolin) keeps everything a step produces in LDS / registers
 // in the sampling loops: no stash traffic (SmallLds<..., FOLD>, KEEPROWS).
@@ -31,16 +31,9 @@
 #else
 #define DFF_MARK(n) ((void)0)
 #endif
-// DFF_F16 (round 5): the split variants run their weight GEMMs on the TWO-piece fp16 split (dff_device.h split8h): stream kind -1 =
-// host-split fp16 image, 4 B per weight, 2 KB units, three v_mfma_f32_16x16x32_f16 per unit.  1: the FOLD variant only (chignolin:
-// the headline), 2: every split variant of this kernel, 0: the three-piece bf16 engine of rounds 2-4.
-#ifndef DFF_F16
-#define DFF_F16 2
-#endif
-#define DFF_F16_ON(FOLD_) (DFF_F16 >= 2 || (DFF_F16 == 1 && (FOLD_)))
-#ifndef DFF_SDR
-#define DFF_SDR 4   // split-ring depth in units (SPW variants)
-#endif
+// The split variants run their weight GEMMs on the two-piece fp16 split (round 5; dff_device.h split8h): host-split fp16 images,
+// 4 B per weight, 2 KB units, three v_mfma_f32_16x16x32_f16 per unit.
+constexpr int SDR = 4;   // split-ring depth in units (SPW variants)
 // NW = waves per workgroup.  NW = 4: one wave per SIMD, two heads per wave, 16-row head buffers.
 // NW = 8: two waves per SIMD (each hides the other's stalls), one head per wave; to fit 8 wave
 // regions in 160 KB the head buffers hold RLA = 11 rows (10 real + 1 dummy row that absorbs the
@@ -66,7 +59,7 @@ struct SmallLds {
     // GPS floats each (row GPR - 1 absorbs the pad lanes' stores) -- the last layer's tile lives behind the wave's 11-row
     // partial-sum tile inside G | dS, so that in the sampling loops of a <= 3-layer model GELU' never leaves the LDS (it was
     // 57 % of the kernel's stash traffic, profiles/r02).  The one shared copy of the LayerNorm rows (K_ext = V_ext) has its
-    // own region `nx`; the fp32 K = H GEMM input `abuf` does not exist (the row stages write bf16 pieces into `asp`).
+    // own region `nx`; the fp32 K = H GEMM input `abuf` does not exist (the row stages write fp16 pieces into `asp`).
     static constexpr int GPR = 11, GPS = 32;
     static constexpr unsigned GPT = GPR * GPS;
     static constexpr unsigned GP_LAST = RLA * LH;   // offset of the last layer's tile inside G | dS (behind the partial-sum tile)
@@ -78,10 +71,10 @@ struct SmallLds {
     static constexpr unsigned xst = 0, xs = 64, dxs = 128, vst = 192, cm = 256, tn = 384, prof = 400,
                               dxw = 448,                      // [NW][128] per-wave dx partials (+ dummies)
                               abuf = 448 + NWR * 128, resbuf = abuf + (FOLD ? 0 : 16 * LH),
-                              // SPW variants (8 waves): the K = H GEMM input as bf16 pieces, written by the row stages:
-                              // [piece 3][k-block H/32][kg 4][row 16][4 dwords] -- a wave's ds_read_b128 of (row, kg)
+                              // SPW variants (8 waves): the K = H GEMM input as fp16 pieces, written by the row stages:
+                              // [piece][k-block H/32][kg 4][row 16][4 dwords] -- a wave's ds_read_b128 of (row, kg)
                               // then touches 16 rows x 4 dwords = every bank once, whatever the lane group
-                              asp = resbuf + (FOLD ? RLA : 16) * LH, asp_size = (NW == 8 && H == 64) ? ((FOLD && DFF_F16_ON(true)) ? 2 * (H / 32) * 256 + 64 : 3 * (H / 32) * 256) : 0,   // (only H = 64 has SPW variants; the fp16 engine has two pieces + the row scales)
+                              asp = resbuf + (FOLD ? RLA : 16) * LH, asp_size = (NW == 8 && H == 64) ? (FOLD ? 2 * (H / 32) * 256 + 64 : 3 * (H / 32) * 256) : 0,   // (only H = 64 has SPW variants: two pieces + the row scales; the unfolded ones keep the three-piece area)
                               // source-offset table of the LDS-DMA head fetch (head_dma): DMA_N instructions x 64 lanes
                               dmatab = asp + asp_size, dmatab_size = (NW == 8 && H == 64) ? DMA_N * 64 : 0,
                               // FOLD: the fp16 pieces of the LayerNorm rows `nx` holds in fp32 ([h | l'], the layout of `asp`): the A operand
@@ -91,7 +84,7 @@ struct SmallLds {
                               // ... and the same rows' 64 regular columns once more, TRANSPOSED: [h | l'][16-column tile][4 rows kg][column][row & 3] --
                               // lane (column m, kg) of a v_mfma_f32_16x16x16_f16 reads its four contraction-index values (rows 4 kg ..) as
                               // 8 bytes: the operand of O^T = V^T P^T and of dQ^T = K^T dS^T on the fp16 pipe (round 6)
-                              nst = nsp + nsp_size, nst_size = (FOLD && DFF_F16_ON(true)) ? 2 * (H / 16) * 4 * 16 * 2 : 0,
+                              nst = nsp + nsp_size, nst_size = FOLD ? 2 * (H / 16) * 4 * 16 * 2 : 0,
                               // (nx stays in front of the wave regions: operand reads of its rows 11..15 land in wave 0's Q region, fp32 data)
                               nx = nst + nst_size, nx_size = FOLD ? RS : 0,
                               wreg = nx + nx_size, total = wreg + NWR * WREG + 64;
@@ -246,238 +239,134 @@ DEVI void tall_run(Ring<E, DR>& ring, f32x4 (&acc)[E], const FA fa, const WStrea
     if constexpr (REM > 2) tall_step<(PH + 2) % DR, N, E, XKB>(ring, acc, a, fa, w, wn, lane, NREV * DR + 2);
 }
 
-// ---------------------------------------------------------------- split-bf16 engine (SPW variants)
-// The weight GEMMs on the bf16 matrix pipe at fp32 accuracy: an fp32 value is the exact sum of three bf16 pieces
-// (truncation split h | m | l) and  a.b ~ ah.bh + (am.bh + ah.bm) + (al.bh + ah.bl + am.bm)  drops only terms of relative
-// order 2^-24 (tools_ubench/split_bf16.hip: error vs fp64 <= that of v_mfma_f32_16x16x4_f32).  Six
-// v_mfma_f32_16x16x32_bf16 (16 cycles each, and they leave the SIMD's vector port to the sibling wave) replace eight
-// v_mfma_f32_16x16x4_f32 (32 cycles each).  The weights are split on the host (dff_host.hip pack_units); the A operand
-// stays fp32 in LDS, exactly where the fp32 engine reads it, and is split in registers by the wave that consumes it
-// (split8: ~44 VALU per 32-column block, amortised over the 4..13 tiles that use the block).
-// One ring entry = one UNIT = (16-column output tile, 32-row k-block) = three pieces x 16 B per lane; every stream is
-// a linear sequence of units ([tile][k-block] for the K = H GEMMs, [k-block][tile] for the Nout = H ones), the ring holds
-// DR = H/16 units, and the last DR refills of a GEMM fetch the first units of the stream that follows, placed so that
-// the following GEMM starts at ring phase PHN (blocks separated by a barrier always start at phase 0).
+// ---------------------------------------------------------------- split engine (SPW variants)
+// The weight GEMMs on the fp16 matrix pipe at fp32 accuracy (the two-piece split of dff_device.h split8h): three
+// v_mfma_f32_16x16x32_f16 per unit instead of eight v_mfma_f32_16x16x4_f32.  The weights are split on the host (dff_host.hip
+// pack_units_f16); the row stages write the A operand as pieces (asp), or the consuming wave splits an fp32 operand in registers.
+// One ring entry = one UNIT = (16-column output tile, 32-row k-block) = two pieces x 16 B per lane; every stream is a linear
+// sequence of units ([tile][k-block] for the K = H GEMMs, [k-block][tile] for the Nout = H ones), the ring holds DR units, and
+// the last DR refills of a GEMM fetch the first units of the stream that follows, placed so that the following GEMM starts at
+// ring phase PHN (blocks separated by a barrier always start at phase 0).
+// (A ring entry keeps a third, unused slot, as when units had three pieces: with two the register allocator assigns the ring
+// differently -- the same instructions, reordered registers.)
 template <int DR>
 struct SRing {
     u32x4 b[DR][3];
 };
 struct SStream {
-    const gu32x4* base;   // wave-uniform; unit j at base + 192 j, piece p at + 64 p, lane at + lane
+    const gu32x4* base;   // wave-uniform; unit j at base + 128 j, piece p at + 64 p, lane at + lane
 };
-DEVI SStream sstream(const unsigned* Wp, int unit0, int ust = 192) { return SStream{(const gu32x4*)Wp + (size_t)unit0 * ust}; }
-DEVI void sfill(u32x4 (&slot)[3], const gu32x4* p, int lane) {
-    const unsigned lo = (unsigned)lane & 63u;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) slot[q] = (p + 64 * q)[lo];
-}
+DEVI SStream sstream(const unsigned* Wp, int unit0) { return SStream{(const gu32x4*)Wp + (size_t)unit0 * 128}; }
 // The weights a wave needs between two workgroup barriers form ONE sequence of units: N0 units of stream s0 followed by
 // N1 units of s1 (e.g. QKV_ext then [W_o;W_oc]; W1 then W2), and after them the first DR units of the NEXT block (M0
 // units of n0, then units of n1), which the last DR refills of this block request -- so they are in flight during the row
 // stage in between.  Unit i of the block lives in ring slot i % DR; all indices are compile-time (every GEMM below is
 // fully unrolled, which also lets the compiler count the outstanding loads exactly: in a rolled loop the epilogue operands
 // requested two tiles ahead are loop-carried, and the s_waitcnt that joins them drains the whole ring every revolution).
-// eight fp32 values of a 32-column block (x0: columns 4 kg .. + 3, x1: columns 16 + 4 kg .. + 3 -- what two ds_read_b128
-// of the fp32 engine's A pattern deliver) -> the three bf16 piece operands; element j sits in half j & 1 of dword j >> 1
-template <int KB32>
-DEVI void split_afrag(const f32x4 (&a)[2 * KB32], u32x4 (&ah)[KB32], u32x4 (&am)[KB32], u32x4 (&al)[KB32]) {
-#pragma unroll
-    for (int kb = 0; kb < KB32; ++kb) split8(a[2 * kb], a[2 * kb + 1], ah[kb], am[kb], al[kb]);
-}
-// A stream is one of two KINDS.  Kind 0: a host-split image (three bf16 pieces per weight, 6 B; dff_host.hip pack_units),
-// units linear.  Kind > 0: the fp32 image of the fp32 engine (4 B per weight; pack_b), whose two 16-row blocks of a unit
-// the consuming wave splits in registers (split8, ~44 VALU per unit): fewer bytes for the GEMMs that are bound by the
-// L2 -> CU weight stream (QKV_ext, its transpose, [W_o;W_oc]), where the SIMDs idle anyway.  Kind 1: K = H image
-// ([tile][16-row block]: unit j at + 128 j); kind KBtot (> 1): Nout = H image with KBtot 16-row blocks per tile, unit
-// (kb, nt) at + nt KBtot 64 + 64 blk(kb), blk(kb) = 2 kb, or 2 kb + 1 from kb = 2 on in the QKV_ext^T image (KBtot =
-// 104), whose heads are [q 0..3 | ext 4 | k 5..8 | v 9..12].
-template <int KIND, int E>
-DEVI const gu32x4* unit_addr(const SStream& w, int j) {
-    if constexpr (KIND == 0) return w.base + (size_t)j * 192;
-    else if constexpr (KIND == 1 || KIND == -1) return w.base + (size_t)j * 128;   // (-1: fp16 image, two pieces per unit)
-    else {
-        const int kb = j / E, nt = j - kb * E;
-        return w.base + (size_t)nt * KIND * 64 + (size_t)(2 * kb + (KIND == DFF_HEADS * 13 && kb >= 2 ? 1 : 0)) * 64;
-    }
-}
-template <int KIND>
+DEVI const gu32x4* unit_addr(const SStream& w, int j) { return w.base + (size_t)j * 128; }
 DEVI void sfill_k(u32x4 (&slot)[3], const gu32x4* p, int lane) {
     const unsigned lo = (unsigned)lane & 63u;
     slot[0] = p[lo];
     slot[1] = (p + 64)[lo];
-    if constexpr (KIND == 0) slot[2] = (p + 128)[lo];
 }
 // a unit of a head's EXTENSION output tile ([u | s | 0 ...], [r | g_D | 0 ...]): only output columns 0..3 have weights, i.e.
 // only lanes with (lane & 15) < 4 hold anything but zeros -- they alone load (256 B instead of 1 KiB per piece: these
 // tiles are 1/13 of the QKV_ext stream and 1/5 of the [W_o;W_oc]^T stream)
-template <int KIND = 0>
 DEVI void sfill_ext(u32x4 (&slot)[3], const gu32x4* p, int lane) {
     const unsigned lo = (unsigned)lane & 63u;
     const bool has = (lane & 15) < 4;
 #pragma unroll
-    for (int q = 0; q < (KIND < 0 ? 2 : 3); ++q) {
+    for (int q = 0; q < 2; ++q) {
         u32x4 v = {0u, 0u, 0u, 0u};
         if (has) v = (p + 64 * q)[lo];
         slot[q] = v;
     }
 }
-// the three piece operands of the unit held by a slot
-template <int KIND>
-DEVI void unit_pieces(const u32x4 (&slot)[3], u32x4& bh, u32x4& bm, u32x4& bl) {
-    if constexpr (KIND < 0) { bh = slot[0]; bm = slot[1]; bl = slot[1]; }   // (fp16: h | l', no third piece)
-    else if constexpr (KIND == 0) { bh = slot[0]; bm = slot[1]; bl = slot[2]; }
-    else split8(__builtin_bit_cast(f32x4, slot[0]), __builtin_bit_cast(f32x4, slot[1]), bh, bm, bl);
-}
-template <int N0_, int N1_, int M0_, int K0_, int K1_, int KN0_, int KN1_, int E_, int XU_ = -1>
+template <int N0_, int N1_, int M0_, int E_, int XU_ = -1>
 struct SSeq {
-    static constexpr int N0 = N0_, N1 = N1_, M0 = M0_, K0 = K0_, K1 = K1_, KN0 = KN0_, KN1 = KN1_, E = E_;
-    static constexpr int XU = XU_;   // units XU, XU + 1 of s0 (kind 0) are an extension output tile (sfill_ext), or -1
+    static constexpr int N0 = N0_, N1 = N1_, M0 = M0_, E = E_;
+    static constexpr int XU = XU_;   // units XU, XU + 1 of s0 are an extension output tile (sfill_ext), or -1
     SStream s0, s1, n0, n1;
-    static constexpr int kind(int i) { return i < N0 ? K0 : K1; }   // of unit i of this block
 };
 // The ring's refill loads must be ISSUED where they are written: left alone, the scheduler sinks a load whose slot is free
 // down to the products that consume it a ring's depth later (it saves the slot's live range -- and exposes an L2 latency
 // per unit).  A scheduling barrier that everything but VMEM may cross pins the load without fencing the products.
-#ifndef DFF_PIN
-#define DFF_PIN 1
-#endif
-#if DFF_PIN
 #define DFF_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x078F)
-#else
-#define DFF_PIN_VMEM() ((void)0)
-#endif
 template <int DR, int I, class Q>
 DEVI void seq_refill(SRing<DR>& ring, const Q& q, int lane) {   // slot of unit I <- unit I + DR (or the next block's)
     constexpr int slot = I % DR, J = I + DR;
-    if constexpr (J < Q::N0 && Q::K0 <= 0 && Q::XU >= 0 && (J == Q::XU || J == Q::XU + 1)) sfill_ext<Q::K0>(ring.b[slot], unit_addr<Q::K0, Q::E>(q.s0, J), lane);
-    else if constexpr (J < Q::N0) sfill_k<Q::K0>(ring.b[slot], unit_addr<Q::K0, Q::E>(q.s0, J), lane);
-    else if constexpr (J < Q::N0 + Q::N1) sfill_k<Q::K1>(ring.b[slot], unit_addr<Q::K1, Q::E>(q.s1, J - Q::N0), lane);
-    else if constexpr (slot < Q::M0) sfill_k<Q::KN0>(ring.b[slot], unit_addr<Q::KN0, Q::E>(q.n0, slot), lane);
-    else sfill_k<Q::KN1>(ring.b[slot], unit_addr<Q::KN1, Q::E>(q.n1, slot - Q::M0), lane);
+    if constexpr (J < Q::N0 && Q::XU >= 0 && (J == Q::XU || J == Q::XU + 1)) sfill_ext(ring.b[slot], unit_addr(q.s0, J), lane);
+    else if constexpr (J < Q::N0) sfill_k(ring.b[slot], unit_addr(q.s0, J), lane);
+    else if constexpr (J < Q::N0 + Q::N1) sfill_k(ring.b[slot], unit_addr(q.s1, J - Q::N0), lane);
+    else if constexpr (slot < Q::M0) sfill_k(ring.b[slot], unit_addr(q.n0, slot), lane);
+    else sfill_k(ring.b[slot], unit_addr(q.n1, slot - Q::M0), lane);
     DFF_PIN_VMEM();
 }
-// first DR units of a block (step start), all from one stream of kind KIND
-template <int DR, int KIND, int E>
+// first DR units of a block (step start), all from one stream
+template <int DR>
 DEVI void sring_prefetch(SRing<DR>& r, const SStream& n0, int lane) {
 #pragma unroll
-    for (int j = 0; j < DR; ++j) sfill_k<KIND>(r.b[j], unit_addr<KIND, E>(n0, j), lane);
+    for (int j = 0; j < DR; ++j) sfill_k(r.b[j], unit_addr(n0, j), lane);
 }
 // wide GEMM (K = H = 32 KB32) of one wave on split operands: N output tiles, KB32 units each, the first one unit I0 of
 // the block.  aux[t % 2][..]: epilogue operands of the tiles in flight (the caller preloads tiles 0 and 1,
 // pre(t + 2, aux[t % 2]) requests the next ones right after tile t's were copied out).
 template <int I0, int T, int N, int KB32, int NAUX, int DR, class Q, class Pre, class Epi>
-DEVI void swide_from(SRing<DR>& ring, float (&aux)[2][NAUX], const u32x4 (&ah)[KB32], const u32x4 (&am)[KB32],
-                     const u32x4 (&al)[KB32], const Q& q, int lane, const Pre& pre, const Epi& epi) {
+DEVI void swide_from(SRing<DR>& ring, float (&aux)[2][NAUX], const u32x4 (&ah)[KB32], const u32x4 (&al)[KB32], const Q& q, int lane,
+                     const Pre& pre, const Epi& epi) {
     if constexpr (T < N) {
-        f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f};   // small terms / big terms
+        f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f};   // the 2^11-scaled cross terms / h.h
 #pragma unroll
         for (int kb = 0; kb < KB32; ++kb) {
-            u32x4 bh, bm, bl;
-            unit_pieces<Q::kind(I0 + T * KB32)>(ring.b[(I0 + T * KB32 + kb) % DR], bh, bm, bl);
-            // a slot whose weights were split into temporaries is refilled before its MFMAs are issued
-            if constexpr (Q::kind(I0 + T * KB32) > 0) {
-                if (kb == 0) seq_refill<DR, I0 + T * KB32 + 0>(ring, q, lane);
-                if (kb == 1) seq_refill<DR, I0 + T * KB32 + (KB32 > 1 ? 1 : 0)>(ring, q, lane);
-            }
-            if constexpr (Q::kind(I0 + T * KB32) < 0) {   // fp16: am / bm hold the l' pieces; cs collects the 2^11-scaled cross terms
-                cs = mfma_f16(am[kb], bh, cs);
-                cs = mfma_f16(ah[kb], bm, cs);
-                cb = mfma_f16(ah[kb], bh, cb);
-            } else {
-            cs = mfma_bf16(al[kb], bh, cs);
-            cb = mfma_bf16(am[kb], bh, cb);
-            cs = mfma_bf16(ah[kb], bl, cs);
-            cb = mfma_bf16(ah[kb], bm, cb);
-            cs = mfma_bf16(am[kb], bm, cs);
-            cb = mfma_bf16(ah[kb], bh, cb);
-            }
+            const u32x4 (&u)[3] = ring.b[(I0 + T * KB32 + kb) % DR];
+            cs = mfma_f16(al[kb], u[0], cs);
+            cs = mfma_f16(ah[kb], u[1], cs);
+            cb = mfma_f16(ah[kb], u[0], cb);
         }
-        if constexpr (Q::kind(I0 + T * KB32) <= 0) {
-            if constexpr (KB32 >= 1) seq_refill<DR, I0 + T * KB32 + 0>(ring, q, lane);
-            if constexpr (KB32 >= 2) seq_refill<DR, I0 + T * KB32 + 1>(ring, q, lane);
-        }
+        if constexpr (KB32 >= 1) seq_refill<DR, I0 + T * KB32 + 0>(ring, q, lane);
+        if constexpr (KB32 >= 2) seq_refill<DR, I0 + T * KB32 + 1>(ring, q, lane);
         float auxc[NAUX];
 #pragma unroll
         for (int i = 0; i < NAUX; ++i) auxc[i] = aux[T % 2][i];
         if constexpr (T + 2 < N) pre(T + 2, aux[T % 2]);
-        if constexpr (Q::kind(I0 + T * KB32) < 0) epi(T, cb + cs * DFF_F16_LINV, auxc);
-        else epi(T, cb + cs, auxc);
-        swide_from<I0, T + 1, N, KB32, NAUX>(ring, aux, ah, am, al, q, lane, pre, epi);
+        epi(T, cb + cs * DFF_F16_LINV, auxc);
+        swide_from<I0, T + 1, N, KB32, NAUX>(ring, aux, ah, al, q, lane, pre, epi);
     }
 }
 template <int I0, int N, int KB32, int NAUX, int DR, class Q, class Pre, class Epi>
-DEVI void swide_run(SRing<DR>& ring, float (&aux)[2][NAUX], const u32x4 (&ah)[KB32], const u32x4 (&am)[KB32],
-                    const u32x4 (&al)[KB32], const Q& q, int lane, const Pre pre, const Epi epi) {
+DEVI void swide_run(SRing<DR>& ring, float (&aux)[2][NAUX], const u32x4 (&ah)[KB32], const u32x4 (&al)[KB32], const Q& q, int lane,
+                    const Pre pre, const Epi epi) {
     static_assert(KB32 <= 2, "refill list");
-    swide_from<I0, 0, N, KB32, NAUX>(ring, aux, ah, am, al, q, lane, pre, epi);
+    swide_from<I0, 0, N, KB32, NAUX>(ring, aux, ah, al, q, lane, pre, epi);
 }
 // tall GEMM (Nout = H = 16 E) of one wave on split operands: acc[nt] += A(:, 32-column block kb) . W(unit (kb, nt)),
 // kb < NKB, unit (kb, nt) = unit I0 + kb E + nt of the block; fa(kb) = this lane's four floats at columns 4 quad of block
-// kb (the second four are 16 floats on).  The next block's A is read from LDS before the MFMAs of this one are issued.
+// kb (the second four are 16 floats on), split in registers (scaled by sa first).  The next block's A is read from LDS before
+// the MFMAs of this one are issued.
 // EXT: one fp32 k-step on top for a head's extension columns (of which only 0..3 carry data): A element *ext_a, weights
 // ext_w[nt * ext_ts] (the s = 0 slots of the fp32 image's extension block, dff_host.hip pack_b), requested first, used last.
 template <int I0, int KB, int NKB, int E, int DR, class Q, class FA>
 DEVI void stall_from(SRing<DR>& ring, f32x4 (&acc)[E], f32x4 (&acc2)[E], f32x4& x0, f32x4& x1, const FA& fa, const Q& q, int lane, float sa) {
     if constexpr (KB < NKB) {
-        constexpr int KD = Q::kind(I0 + KB * E);
-        u32x4 ah, am, al;
-        if constexpr (KD < 0) { split8h(x0, x1, ah, am); al = am; }   // fp16: (h, l')
-        else split8(x0, x1, ah, am, al);
+        u32x4 ah, al;
+        split8h(x0, x1, ah, al);
         if constexpr (KB + 1 < NKB) {
             const lfloat* pn = fa(KB + 1);
             x0 = *(const lf32x4*)pn; x1 = *(const lf32x4*)(pn + 16);
-            if constexpr (KD < 0) { x0 *= sa; x1 *= sa; }
+            x0 *= sa; x1 *= sa;
         }
-        if constexpr (KD < 0) {
-            // acc: h.h ; acc2: the two cross terms, 2^11 too large (stall_run folds them in at the end)
+        // acc: h.h ; acc2: the two cross terms, 2^11 too large (stall_run folds them in at the end)
 #pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc2[nt] = mfma_f16(am, ring.b[(I0 + KB * E + nt) % DR][0], acc2[nt]);
+        for (int nt = 0; nt < E; ++nt) acc2[nt] = mfma_f16(al, ring.b[(I0 + KB * E + nt) % DR][0], acc2[nt]);
 #pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc2[nt] = mfma_f16(ah, ring.b[(I0 + KB * E + nt) % DR][1], acc2[nt]);
+        for (int nt = 0; nt < E; ++nt) acc2[nt] = mfma_f16(ah, ring.b[(I0 + KB * E + nt) % DR][1], acc2[nt]);
 #pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_f16(ah, ring.b[(I0 + KB * E + nt) % DR][0], acc[nt]);
-            static_assert(E == 4, "refill list");
-            seq_refill<DR, I0 + KB * E + 0>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 1>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 2>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 3>(ring, q, lane);
-        } else if constexpr (KD == 0) {
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(al, ring.b[(I0 + KB * E + nt) % DR][0], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(ah, ring.b[(I0 + KB * E + nt) % DR][2], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(am, ring.b[(I0 + KB * E + nt) % DR][1], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(am, ring.b[(I0 + KB * E + nt) % DR][0], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(ah, ring.b[(I0 + KB * E + nt) % DR][1], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_bf16(ah, ring.b[(I0 + KB * E + nt) % DR][0], acc[nt]);
-            static_assert(E == 4, "refill list");
-            seq_refill<DR, I0 + KB * E + 0>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 1>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 2>(ring, q, lane);
-            seq_refill<DR, I0 + KB * E + 3>(ring, q, lane);
-        } else {
-            // fp32 units: split, refill the slot at once, then the unit's six products on two chains
-            auto one = [&](auto nti) {
-                constexpr int nt = decltype(nti)::value;
-                u32x4 bh, bm, bl;
-                unit_pieces<Q::kind(I0 + KB * E)>(ring.b[(I0 + KB * E + nt) % DR], bh, bm, bl);
-                seq_refill<DR, I0 + KB * E + nt>(ring, q, lane);
-                f32x4 cs = {0.f, 0.f, 0.f, 0.f};
-                cs = mfma_bf16(al, bh, cs);
-                acc[nt] = mfma_bf16(am, bh, acc[nt]);
-                cs = mfma_bf16(ah, bl, cs);
-                acc[nt] = mfma_bf16(ah, bm, acc[nt]);
-                cs = mfma_bf16(am, bm, cs);
-                acc[nt] = mfma_bf16(ah, bh, acc[nt]);
-                acc[nt] += cs;
-            };
-            one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{});
-            one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{});
-        }
+        for (int nt = 0; nt < E; ++nt) acc[nt] = mfma_f16(ah, ring.b[(I0 + KB * E + nt) % DR][0], acc[nt]);
+        static_assert(E == 4, "refill list");
+        seq_refill<DR, I0 + KB * E + 0>(ring, q, lane);
+        seq_refill<DR, I0 + KB * E + 1>(ring, q, lane);
+        seq_refill<DR, I0 + KB * E + 2>(ring, q, lane);
+        seq_refill<DR, I0 + KB * E + 3>(ring, q, lane);
         stall_from<I0, KB + 1, NKB, E>(ring, acc, acc2, x0, x1, fa, q, lane, sa);
     }
 }
@@ -488,7 +377,6 @@ template <int I0, int NKB, int E, bool EXT, int DR, class Q, class FA>
 DEVI void stall_run(SRing<DR>& ring, f32x4 (&acc)[E], const FA fa, const Q& q, int lane,
                     const lfloat* ext_a = nullptr, const gfloat* ext_w = nullptr, int ext_ts = 0, const lfloat* rsc = nullptr,
                     bool common = false) {
-    constexpr bool F16 = Q::kind(I0) < 0;
     float bx[E];
     if constexpr (EXT) {
 #pragma unroll
@@ -496,7 +384,7 @@ DEVI void stall_run(SRing<DR>& ring, f32x4 (&acc)[E], const FA fa, const Q& q, i
     }
     float sa = 1.0f;
     f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, si4 = {1.f, 1.f, 1.f, 1.f};
-    if (F16 && rsc) {
+    if (rsc) {
         if (common) {
             // rows that mix the rows of the chain's input (dK, dV of the unfolded variants: sums over i) cannot carry per-row
             // scales: ONE power of two for the tile -- the smallest row scale (= 1 / the largest inverse), times 2^-8 of headroom
@@ -519,18 +407,16 @@ DEVI void stall_run(SRing<DR>& ring, f32x4 (&acc)[E], const FA fa, const Q& q, i
     for (int nt = 0; nt < E; ++nt) acc2[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const lfloat* p0 = fa(0);
     f32x4 x0 = *(const lf32x4*)p0, x1 = *(const lf32x4*)(p0 + 16);
-    if constexpr (F16) { x0 *= sa; x1 *= sa; }
+    x0 *= sa; x1 *= sa;
     stall_from<I0, 0, NKB, E>(ring, acc, acc2, x0, x1, fa, q, lane, sa);
-    if constexpr (F16) {
 #pragma unroll
-        for (int nt = 0; nt < E; ++nt) acc[nt] += acc2[nt] * DFF_F16_LINV;
-    }
+    for (int nt = 0; nt < E; ++nt) acc[nt] += acc2[nt] * DFF_F16_LINV;
     if constexpr (EXT) {
         const float ax = *ext_a * sa;
 #pragma unroll
         for (int nt = 0; nt < E; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ax, bx[nt], acc[nt], 0, 0, 0);
     }
-    if (F16 && rsc) {
+    if (rsc) {
 #pragma unroll
         for (int nt = 0; nt < E; ++nt) acc[nt] *= si4;
     }
@@ -546,7 +432,7 @@ template <int I0, int T, int N, int KB32, bool BIAS = true, int DR, class Q>
 DEVI void swideT_from(SRing<DR>& ring, f32x4 (&out)[N], f32x4 (&bq)[2], const gfloat* bp, const u32x4 (&ah)[KB32], const u32x4 (&al)[KB32],
                       const Q& q, int lane) {
     if constexpr (T < N) {
-        static_assert(Q::kind(I0 + T * KB32) < 0 && KB32 == 2, "fp16 units, H = 64");
+        static_assert(KB32 == 2, "H = 64");
         f32x4 cs = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < KB32; ++kb) {
@@ -570,7 +456,7 @@ DEVI void swideT_from(SRing<DR>& ring, f32x4 (&out)[N], f32x4 (&bq)[2], const gf
 template <int I0, int KB, int NKB, int E, int DR, class Q>
 DEVI void stallR_from(SRing<DR>& ring, f32x4 (&acc)[E], f32x4 (&acc2)[E], const f32x4 (&xr)[2 * NKB], const Q& q, int lane, float sa) {
     if constexpr (KB < NKB) {
-        static_assert(Q::kind(I0 + KB * E) < 0 && E == 4, "fp16 units, H = 64");
+        static_assert(E == 4, "H = 64");
         u32x4 ah, al;
         split8h(xr[2 * KB] * sa, xr[2 * KB + 1] * sa, ah, al);
 #pragma unroll
@@ -682,9 +568,6 @@ DEVI f32x4 wv_dot_rows(const lfloat* A, const lfloat* B, int lane) {
 // C[m][16nt+n] = sum_{k<16} Aop[m][k] B[k][16nt+n] for tiles nt in [NT0, NT1).
 // TRANS = false: Aop[m][k] = T[m][k] (T = 16x16 tile, ld DFF_PLD);  true: Aop[m][k] = T[k][m].
 // ks = k-steps that can be non-zero: columns / rows of T at or beyond the real rows are exact zeros (P, dS).
-#ifndef DFF_WVMM_VOL
-#define DFF_WVMM_VOL 1
-#endif
 template <int NT0, int NT1, bool TRANS, int XLD = DFF_XLD, class Epi>
 DEVI void wv_mm(const lfloat* T, const lfloat* B, int lane, int ks, Epi epi) {
     const int kk = lane >> 4, mm = lane & 15;
@@ -692,11 +575,7 @@ DEVI void wv_mm(const lfloat* T, const lfloat* B, int lane, int ks, Epi epi) {
     // k-step s covers k = 4 s .. 4 s + 3 (lane: k = 4 s + kk), so trailing all-zero k-steps can be dropped
     // (volatile: the operands of k-steps 1..3 are only used inside the row-count branches below, and the compiler sinks a
     // plain LDS read into the branch that uses it -- every product then waits out the latency of its own operands)
-#if DFF_WVMM_VOL
     typedef const volatile lfloat* vlp;
-#else
-    typedef const lfloat* vlp;
-#endif
     float as[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) as[s] = TRANS ? *(vlp)(T + (4 * s + kk) * TP + mm) : *(vlp)(T + mm * DFF_PLD + 4 * s + kk);
@@ -720,10 +599,7 @@ DEVI void wv_mm(const lfloat* T, const lfloat* B, int lane, int ks, Epi epi) {
 }
 
 // all five tiles of a head product; SPLIT: as {0, 1, 2} | {3, 4} -- 28 instead of 44 operand + accumulator registers live at once
-// (the hidden-96 kernels sit at the 256-VGPR limit of two waves per SIMD in exactly these phases: DFF_MM_SPLIT)
-#ifndef DFF_MM_SPLIT
-#define DFF_MM_SPLIT 1
-#endif
+// (the hidden-96 kernels sit at the 256-VGPR limit of two waves per SIMD in exactly these phases: SPLIT above hidden 64)
 template <bool SPLIT, bool TRANS, int XLD = DFF_XLD, class Epi>
 DEVI void wv_mm5(const lfloat* T, const lfloat* B, int lane, int ks, Epi epi) {
     if constexpr (SPLIT) {
@@ -864,7 +740,7 @@ DEVI void head_dma(const lu32* tab, const lfloat* Qx /* wave-uniform; the region
 // ---------------------------------------------------------------- the kernel
 // FOLD (hidden == head dimension, dff_host.hip folds W_k into W_q and W_v into W_o): keys and values ARE the LayerNorm rows,
 // so the QKV_ext GEMM has 5 tiles per head instead of 13 (q' | u), K_ext = V_ext is ONE shared fp32 copy of the LayerNorm
-// output (+ x), written by the row stages next to its bf16 pieces, dK and dV go straight into the wave's partial of
+// output (+ x), written by the row stages next to its fp16 pieces, dK and dV go straight into the wave's partial of
 // d(LayerNorm output) (identity back-projection) and the QKV_ext^T GEMM keeps only its dQ blocks; only q' is stashed.
 // MODE (DFF_MODE_SCORE / LANGEVIN / DDPM) is a template argument: one kernel per sampler mode.  With the three update stages
 // and their mode tests inside one step loop the register allocator and the scheduler paid for all of them everywhere
@@ -880,7 +756,7 @@ DEVI void head_dma(const lu32* tab, const lfloat* Qx /* wave-uniform; the region
 template <int H, int NW, bool GEN, bool SPW, bool FOLD, int MODE, bool PAIR = false>
 __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const DffModelDev m, const DffRunArgs a) {
     static_assert(!FOLD || (SPW && !GEN && H == DFF_DH), "FOLD: the split, shipped-branch, hidden == 64 variant");
-    static_assert(!PAIR || (FOLD && NW == 8 && DFF_F16_ON(FOLD)), "PAIR: the FOLD kernel on the fp16 engine");
+    static_assert(!PAIR || (FOLD && NW == 8), "PAIR: the FOLD kernel");
     constexpr int NWR = PAIR ? 4 : NW;       // waves of this workgroup
     using LL = SmallLds<H, NW, FOLD, NWR>;
     constexpr int LH = LL::LH, F = 4 * H, E = H / 16;
@@ -892,8 +768,8 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     constexpr int RS = RLA * XLD;            // floats between the Q / K / V / G buffers of a wave
     constexpr int FS = F / NW, NTS = FS / 16, LF = FS + 4;   // FFN hidden slice of a wave
     static_assert(HPW == 1 || HPW == 2, "4 or 8 waves");
-    constexpr int KB32 = H / 32, SDR = DFF_SDR;   // SPW: 32-row k-blocks of a K = H GEMM, split-ring depth in units
-    static_assert(!SPW || (NW == 8 && H == 64 && FS == 32), "split-bf16 variant: one head per wave; the unit counts below are H = 64's");
+    constexpr int KB32 = H / 32;   // SPW: 32-row k-blocks of a K = H GEMM
+    static_assert(!SPW || (NW == 8 && H == 64 && FS == 32), "split variant: one head per wave; the unit counts below are H = 64's");
     // units per GEMM of a wave (H = 64): QKV_ext 13 tiles x 2, [W_o;W_oc] 2 k-blocks x 4, W1 / W2^T 2 x 2, W2 / W1^T 1 x 4,
     // [W_o;W_oc]^T 5 x 2, QKV_ext^T 6 x 4
     constexpr int NQT = FOLD ? 5 : 13;        // output tiles per head of the QKV_ext GEMM ([q' | u] or [q | u | k | v])
@@ -929,15 +805,13 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     // (the row stages' stores of the K = H GEMM input -- fp32 `abuf`, or its pieces at the position the consuming waves' A fragments
     // expect: element j of lane (row, kg) of k-block kb is column 32 kb + 16 (j >> 2) + 4 kg + (j & 3) -- are a_put / n_put below)
     // ... and a wave's A fragments of it (SPW): pieces of k-block kb for row lane & 15, k-group lane >> 4
-    auto a_load = [=](u32x4 (&ah)[H / 32], u32x4 (&am)[H / 32], u32x4 (&al)[H / 32], int lane) {
+    auto a_load = [=](u32x4 (&ah)[H / 32], u32x4 (&al)[H / 32], int lane) {
         const lu32* const q = (const lu32*)asp16 + ((lane >> 4) * 16 + (lane & 15)) * 4;
         constexpr int PS = (H / 32) * 256;
 #pragma unroll
         for (int kb = 0; kb < H / 32; ++kb) {
             ah[kb] = *(const lu32x4*)(q + kb * 256);
-            am[kb] = *(const lu32x4*)(q + PS + kb * 256);
-            if constexpr (SPW && DFF_F16_ON(FOLD)) al[kb] = am[kb];   // (two pieces: h, l')
-            else al[kb] = *(const lu32x4*)(q + 2 * PS + kb * 256);
+            al[kb] = *(const lu32x4*)(q + PS + kb * 256);
         }
     };
     lfloat* const dxw = sm + LL::dxw + rwave * 128;
@@ -945,7 +819,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     // FOLD: K_ext = V_ext = ONE shared fp32 copy of the LayerNorm rows (+ x in the extension columns), region `nx`
     lfloat* const Nx = sm + LL::nx;
     lfloat* const Qx = wr; lfloat* const Kx = FOLD ? Nx : wr + RS; lfloat* const Vx = FOLD ? Nx : wr + 2 * RS;
-    constexpr bool NSP = FOLD && SPW && DFF_F16_ON(FOLD);   // the attention input's fp16 pieces live in their own region (SmallLds::nsp)
+    constexpr bool NSP = FOLD && SPW;   // the attention input's fp16 pieces live in their own region (SmallLds::nsp)
     lu16* const nsp16 = (lu16*)(sm + LL::nsp);
     lu16* const nst16 = (lu16*)(sm + LL::nst);
     // lane (column m = lane & 15 of tile nt, kg = lane >> 4): rows 4 kg .. + 3 of that column as the A operand of a 16x16x16 fp16 MFMA
@@ -980,17 +854,9 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
         if constexpr (SPW) {
             lu16* const q = asp16 + rs_a + RS_AOFF(i);
             constexpr int PS = (H / 32) * 256 * 2;
-            if constexpr (DFF_F16_ON(FOLD)) {
-                unsigned short hh, ll;
-                split1h(v, hh, ll);
-                q[0] = hh; q[PS] = ll;
-            } else {
-                const unsigned b = __float_as_uint(v);
-                const float r = v - __uint_as_float(b & 0xffff0000u);
-                const unsigned c = __float_as_uint(r);
-                const float s2 = r - __uint_as_float(c & 0xffff0000u);
-                q[0] = (unsigned short)(b >> 16); q[PS] = (unsigned short)(c >> 16); q[2 * PS] = (unsigned short)(__float_as_uint(s2) >> 16);
-            }
+            unsigned short hh, ll;
+            split1h(v, hh, ll);
+            q[0] = hh; q[PS] = ll;
         } else abuf[rs_o + RSL * i] = v;
     };
     auto n_put = [&](int i, float v) {
@@ -1291,15 +1157,8 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     // In-kernel noise (Philox + Box-Muller: a ~300-instruction dependent chain per lane) does not depend on the forces: when
     // the last wave has no rows in the row stages (chignolin: rows 0..9 are waves 0..4) it draws the step's normals during
     // row stage A, off everybody's critical path, and the update just reads them.
-#ifndef DFF_XI_PRE
-#define DFF_XI_PRE 1
-#endif
-#ifndef DFF_XI_STAGE
-#define DFF_XI_STAGE 0
-#endif
-    const bool xi_pre = DFF_XI_PRE && MODE != DFF_MODE_SCORE && !a.noise && rows * LPR <= (NWR - 1) * 64;
+    const bool xi_pre = MODE != DFF_MODE_SCORE && !a.noise && rows * LPR <= (NWR - 1) * 64;
     static_assert(H % LPR == 0, "row layout");
-    // (DFF_XI_STAGE: the row stage of layer 0 in whose shadow the idle wave draws -- 0: A, 1: B, 2: C)
     // (the seed through an opaque copy: the ten round keys derived from it are otherwise computed once per kernel, spilled to VGPR
     // lanes -- twenty SGPRs the register file does not have -- and read back with a v_readlane + wait state each, per draw)
     auto seed_now = [&]() {
@@ -1341,7 +1200,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     auto a_store_row = [&](int rrow, int sub, const float (&v)[HC], float& inv, bool publish) {
         float sc = 1.0f;
         inv = 1.0f;
-        if constexpr (SPW && DFF_F16_ON(FOLD)) {
+        if constexpr (SPW) {
             // the row maximum of |v| as an UNSIGNED-INTEGER maximum of the bit patterns (non-negative floats order like their bits): one
             // v_max_u32 per reduction step where fmaxf costs three (it canonicalises both inputs); only the exponent is used
             unsigned um = 0u;
@@ -1525,19 +1384,15 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
     // the same streams of the split images (units, see the split engine above)
     // (every stream is a host-split image: fp32 images split in registers by the consuming wave -- 4 B per weight, +44 VALU per unit --
     // measured 90.3 - 94.1 us / step against 90.1 in round 3: the extra VALU costs what the smaller stream saves)
-    constexpr bool F16E = SPW && DFF_F16_ON(FOLD);   // fp16 two-piece engine (kind -1 streams)
-    constexpr int KS = F16E ? -1 : 0;        // kind of the host-split images
-    constexpr int KQ = KS, KO = KS, KT = KS;
-    constexpr int UST = F16E ? 128 : 192;    // 16-byte slots per unit of a host-split image
-    constexpr bool EARLY = SPW && KQ == KS && KO == KS;   // a block's tail refills can fetch either first stream of a step (one unit format)
-    auto ss_qkv = [&](const DffLayerDev& lw, int h) { return sstream(lw.Wqkvx_w, h * U_QKV, UST); };
-    auto ss_wox = [&](const DffLayerDev& lw, int h) { return sstream(lw.Wox_t, h * 2 * E, UST); };
-    auto ss_w1 = [&](const DffLayerDev& lw) { return sstream(lw.W1_w, wave * NTS * KB32, UST); };
-    auto ss_w2 = [&](const DffLayerDev& lw) { return sstream(lw.W2_t, wave * (FS / 32) * E, UST); };
-    auto ss_w2t = [&](const DffLayerDev& lw) { return sstream(lw.W2T_w, wave * NTS * KB32, UST); };
-    auto ss_w1t = [&](const DffLayerDev& lw) { return sstream(lw.W1T_t, wave * (FS / 32) * E, UST); };
-    auto ss_woxt = [&](const DffLayerDev& lw, int h) { return sstream(lw.WoxT_w, h * 5 * KB32, UST); };
-    auto ss_qkvt = [&](const DffLayerDev& lw, int h) { return sstream(lw.WqkvxT_t, h * U_QKVT, UST); };
+    constexpr bool EARLY = SPW;   // a block's tail refills can fetch either first stream of a step (one unit format)
+    auto ss_qkv = [&](const DffLayerDev& lw, int h) { return sstream(lw.Wqkvx_w, h * U_QKV); };
+    auto ss_wox = [&](const DffLayerDev& lw, int h) { return sstream(lw.Wox_t, h * 2 * E); };
+    auto ss_w1 = [&](const DffLayerDev& lw) { return sstream(lw.W1_w, wave * NTS * KB32); };
+    auto ss_w2 = [&](const DffLayerDev& lw) { return sstream(lw.W2_t, wave * (FS / 32) * E); };
+    auto ss_w2t = [&](const DffLayerDev& lw) { return sstream(lw.W2T_w, wave * NTS * KB32); };
+    auto ss_w1t = [&](const DffLayerDev& lw) { return sstream(lw.W1T_t, wave * (FS / 32) * E); };
+    auto ss_woxt = [&](const DffLayerDev& lw, int h) { return sstream(lw.WoxT_w, h * 5 * KB32); };
+    auto ss_qkvt = [&](const DffLayerDev& lw, int h) { return sstream(lw.WqkvxT_t, h * U_QKVT); };
     // extension-block weights of the tall GEMMs for the fp32 k-step (s = 0 slots of the fp32 images)
     auto wox_ext = [&](const DffLayerDev& lw, int h, int lane) { return (const gfloat*)lw.Wox_p + ((size_t)(5 * h + 4) * 64 + lane) * 4; };
     auto qkvt_ext = [&](const DffLayerDev& lw, int h, int lane) { return (const gfloat*)lw.WqkvxT_p + ((size_t)(13 * h + 4) * 64 + lane) * 4; };
@@ -1663,9 +1518,9 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
         if constexpr (SPW) {
             const int lane = lane_id();
             if (cached0_) {
-                sring_prefetch<SDR, KO, E>(sring, ss_wox(m.layer[0], wave), lane);
+                sring_prefetch<SDR>(sring, ss_wox(m.layer[0], wave), lane);
                 if constexpr (HDMA) dma_nop(l0e_ + sl.qkv + (size_t)wave * (RA + 1) * DFF_QKVW, lane);
-            } else sring_prefetch<SDR, KQ, E>(sring, ss_qkv(m.layer[0], wave), lane);
+            } else sring_prefetch<SDR>(sring, ss_qkv(m.layer[0], wave), lane);
         }
     };
     // this (bead, component) thread's mass and noise amplitude, once per launch: indexed per lane they are global loads from the
@@ -1802,7 +1657,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     if constexpr (KEEPROWS) { keep_put(0, KN{}, x); keep_put(0, KL{}, nva); }
                 }
                 if (ract) pre_B(lw, sub);
-                if constexpr (DFF_XI_STAGE == 0) draw_xi(t_int, step);
+                draw_xi(t_int, step);
                 __syncthreads();
             }
             pf.tick(1); DFF_MARK(1);
@@ -1854,7 +1709,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     if (p0keep) p0_copy(true, pcij);
                     else if (st_qkv) *(gf32x4*)(sb + sl.P + (size_t)h * 256 + 4 * lane) = *(const lf32x4*)(pb + (lane >> 2) * DFF_PLD + 4 * (lane & 3));
                     // O_ext = P V_ext (5 tiles) -> Q region; extension columns become xrel = xbar - x_i
-                    wv_mm5<(DFF_MM_SPLIT && H > 64), false, XLD>(pb, Vx, lane, ks4, [&](int nt, const f32x4& acc) {
+                    wv_mm5<(H > 64), false, XLD>(pb, Vx, lane, ks4, [&](int nt, const f32x4& acc) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float v = acc[r];
@@ -1885,7 +1740,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 // probabilities are, as they stand, the B operand of O^T = V_ext^T P^T (k-step r contracts j = 4 kk + r: any
                 // permutation of the contraction index does, applied to both operands) -- whose output tiles are the A fragments of
                 // the output projection.  q' and P still go to LDS (the backward's operands), off the chain.
-                constexpr bool REGCHAIN = FOLD && F16E;
+                constexpr bool REGCHAIN = FOLD;
                 const int lroT = min(col, RLA - 1) * XLD;   // this lane's row in the transposed-output tiles (pad rows -> the dummy row)
                 auto head_rest = [&](int h, const f32x4 Sb, f32x4 (&ot)[5]) {
                     // extension k-step: S^T[j][i] += x_j . u_i
@@ -1972,7 +1827,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         }
                         head_rest(wave, Sb, ot);
                         pf.tick(13); DFF_MARK(13);
-                        const SSeq<U_WOX, 0, MW, KO, KO, KS, KS, E> sq{ss_wox(lw, wave), ss_wox(lw, wave), sn0, sn1};
+                        const SSeq<U_WOX, 0, MW, E> sq{ss_wox(lw, wave), ss_wox(lw, wave), sn0, sn1};
                         const f32x4 (&o4)[4] = *reinterpret_cast<const f32x4 (*)[4]>(&ot[0]);
                         stallR_run<0, 2, E, true>(sring, acc_o, o4, sq, lane, wox_xa, wox_ext(lw, wave, lane), DFF_HEADS * 5 * 256);
                         pf.tick(14); DFF_MARK(14);
@@ -1982,7 +1837,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         const gfloat* const bp = (const gfloat*)lw.bqkvx + wave * 13 * 16 + 4 * quad;
                         f32x4 bq[2] = {*(const gf32x4*)bp, *(const gf32x4*)(bp + 16)};
                         pf.tick(1); DFF_MARK(1);
-                        const SSeq<U_QKV, U_WOX, MW, KQ, KO, KS, KS, E, 4 * KB32> sq{ss_qkv(lw, wave), ss_wox(lw, wave), sn0, sn1};   // tile 4 of 5: [u | s]
+                        const SSeq<U_QKV, U_WOX, MW, E, 4 * KB32> sq{ss_qkv(lw, wave), ss_wox(lw, wave), sn0, sn1};   // tile 4 of 5: [u | s]
                         f32x4 qt[5];
                         swideT_from<0, 0, NQT, KB32>(sring, qt, bq, bp, ah, am, sq, lane);
                         // q'_ext rows -> Q region: the backward's dK operand, the source of the stash / Qsave copies and of the
@@ -2025,12 +1880,12 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         pf.tick(12); DFF_MARK(12);
                         head_math(wave);
                         pf.tick(13); DFF_MARK(13);
-                        const SSeq<U_WOX, 0, MW, KO, KO, KS, KS, E> sq{ss_wox(lw, wave), ss_wox(lw, wave), sn0, sn1};
+                        const SSeq<U_WOX, 0, MW, E> sq{ss_wox(lw, wave), ss_wox(lw, wave), sn0, sn1};
                         stall_run<0, 2, E, true>(sring, acc_o, wox_fa32, sq, lane, wox_xa, wox_ext(lw, wave, lane), DFF_HEADS * 5 * 256);
                         pf.tick(14); DFF_MARK(14);
                     } else {
-                        u32x4 ah[KB32], am[KB32], al[KB32];
-                        a_load(ah, am, al, lane);
+                        u32x4 ah[KB32], al[KB32];
+                        a_load(ah, al, lane);
                         const gfloat* const bqkvx = (const gfloat*)lw.bqkvx;
                         const int l0 = lro[0], l1 = lro[1], l2 = lro[2], l3 = lro[3];
                         const gfloat* const bh = bqkvx + wave * 13 * 16 + col;
@@ -2038,8 +1893,8 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         float bq[2][1];
                         bq[0][0] = bh[0]; bq[1][0] = bh[16];
                         pf.tick(1); DFF_MARK(1);
-                        const SSeq<U_QKV, U_WOX, MW, KQ, KO, KS, KS, E, 4 * KB32> sq{ss_qkv(lw, wave), ss_wox(lw, wave), sn0, sn1};   // tile 4 of 13: [u | s]
-                        swide_run<0, NQT, KB32, 1>(sring, bq, ah, am, al, sq, lane,
+                        const SSeq<U_QKV, U_WOX, MW, E, 4 * KB32> sq{ss_qkv(lw, wave), ss_wox(lw, wave), sn0, sn1};   // tile 4 of 13: [u | s]
+                        swide_run<0, NQT, KB32, 1>(sring, bq, ah, al, sq, lane,
                             [=](int t, float (&ax)[1]) { ax[0] = bh[t * 16]; },
                             [=](int t, const f32x4& acc, const float (&ax)[1]) {
                                 const int reg = (t >= 5) + (t >= 9);
@@ -2169,8 +2024,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 ro_load(0, lw.b2, sub); ro_load3(1, lw.g2, sub);
                 if (l + 1 < m.L) { ro_load(4, m.layer[l + 1].ln1_g, sub); ro_load(5, m.layer[l + 1].ln1_b, sub); }
             } }
-            if constexpr (DFF_XI_STAGE == 1) { if (l == 0) draw_xi(t_int, step); }
-            else { if (l == 0 && skipA) draw_xi(t_int, step); }   // (no stage A to draw under)
+            if (l == 0 && skipA) draw_xi(t_int, step);   // (no stage A to draw under)
             __syncthreads();
             pf.tick(3); DFF_MARK(3);
             // ---- FFN: wave w owns hidden columns [w H, (w+1) H) ----
@@ -2181,8 +2035,8 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 const WStream after = lastl ? s_w2t(lw) : s_qkv(m.layer[lastl ? l : l + 1], wave);
                 // what follows: the last layer's FFN backward (W2^T, W1^T) or the next layer's QKV_ext (whose units MW.. are "n1")
                 const SStream qn = ss_qkv(m.layer[lastl ? l : l + 1], wave);
-                const SSeq<U_W1, U_W2, MW, KS, KS, KS, KS, E> sqf_last{ss_w1(lw), ss_w2(lw), ss_w2t(lw), ss_w1t(lw)};
-                const SSeq<U_W1, U_W2, SDR, KS, KS, KQ, KQ, E> sqf_next{ss_w1(lw), ss_w2(lw), qn, qn};
+                const SSeq<U_W1, U_W2, MW, E> sqf_last{ss_w1(lw), ss_w2(lw), ss_w2t(lw), ss_w1t(lw)};
+                const SSeq<U_W1, U_W2, SDR, E> sqf_next{ss_w1(lw), ss_w2(lw), qn, qn};
                 f32x4 afr[E];
                 if constexpr (!SPW) load_afrag<E>(afr, abuf, LH, lane);
                 float b1r[DR][1];
@@ -2214,11 +2068,11 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     if constexpr (NSP) {
                         // (register chain, below)
                     } else if constexpr (SPW) {
-                        u32x4 ah[KB32], am[KB32], al[KB32];
-                        a_load(ah, am, al, lane);
+                        u32x4 ah[KB32], al[KB32];
+                        a_load(ah, al, lane);
                         pf.tick(19); DFF_MARK(19);
-                        if (lastl) swide_run<0, NTS, KB32, 1>(sring, b1r, ah, am, al, sqf_last, lane, w1_pre, w1_epi);
-                        else swide_run<0, NTS, KB32, 1>(sring, b1r, ah, am, al, sqf_next, lane, w1_pre, w1_epi);
+                        if (lastl) swide_run<0, NTS, KB32, 1>(sring, b1r, ah, al, sqf_last, lane, w1_pre, w1_epi);
+                        else swide_run<0, NTS, KB32, 1>(sring, b1r, ah, al, sqf_next, lane, w1_pre, w1_epi);
                         pf.tick(20); DFF_MARK(20);
                     } else
                     wide_run<0, NTS, E, 1>(ring, b1r, afr, s_w1(lw), s_w2(lw), lane, w1_pre, w1_epi);
@@ -2233,14 +2087,14 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         // columns 16 t + 4 quad .. of that row -- the A fragment of W2's one 32-column block; GELU' goes to its LDS tile
                         // ([row][32 hidden columns], as before) with one 16-byte store per tile
                         static_assert(NTS == 2 && FS == 32, "one 32-column k-block per wave");
-                        u32x4 ah[KB32], am[KB32], al[KB32];
-                        a_load(ah, am, al, lane);
+                        u32x4 ah[KB32], al[KB32];
+                        a_load(ah, al, lane);
                         const gfloat* const b1q = (const gfloat*)lw.b1 + wave * FS + 4 * quad;
                         f32x4 bq[2] = {*(const gf32x4*)b1q, *(const gf32x4*)(b1q + 16)};
                         pf.tick(19); DFF_MARK(19);
                         f32x4 ht[2], gd[2];
-                        if (lastl) swideT_from<0, 0, NTS, KB32>(sring, ht, bq, b1q, ah, am, sqf_last, lane);
-                        else swideT_from<0, 0, NTS, KB32>(sring, ht, bq, b1q, ah, am, sqf_next, lane);
+                        if (lastl) swideT_from<0, 0, NTS, KB32>(sring, ht, bq, b1q, ah, al, sqf_last, lane);
+                        else swideT_from<0, 0, NTS, KB32>(sring, ht, bq, b1q, ah, al, sqf_next, lane);
 #pragma unroll
                         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -2345,7 +2199,6 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     pre_B(m.layer[l + 1], sub);
                 }
             } }
-            if constexpr (DFF_XI_STAGE == 2) { if (l == 0) draw_xi(t_int, step); }
             // the stash written in the forward pass is re-read below by other lanes / waves
             if (l == m.L - 1) __threadfence_block();
             __syncthreads();
@@ -2425,7 +2278,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 ro_touch();
                 const WStream after = s_woxt(lw, wave);
                 const SStream gn = ss_woxt(lw, wave);   // this layer's attention backward follows (G_ext GEMM: U_GX >= SDR units)
-                const SSeq<U_W1, U_W2, SDR, KS, KS, KS, KS, E> sqb{ss_w2t(lw), ss_w1t(lw), gn, gn};
+                const SSeq<U_W1, U_W2, SDR, E> sqb{ss_w2t(lw), ss_w1t(lw), gn, gn};
                 f32x4 afr[E];
                 if constexpr (!SPW) load_afrag<E>(afr, abuf, LH, lane);
                 float hp[DR][4];
@@ -2467,9 +2320,9 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     if constexpr (NSP) {
                         // (register chain, below)
                     } else if constexpr (SPW) {
-                        u32x4 ah[KB32], am[KB32], al[KB32];
-                        a_load(ah, am, al, lane);
-                        swide_run<0, NTS, KB32, 4>(sring, hp, ah, am, al, sqb, lane, hp_load, w2t_epi);
+                        u32x4 ah[KB32], al[KB32];
+                        a_load(ah, al, lane);
+                        swide_run<0, NTS, KB32, 4>(sring, hp, ah, al, sqb, lane, hp_load, w2t_epi);
                     } else
                     wide_run<0, NTS, E, 4>(ring, hp, afr, s_w2t(lw), s_w1t(lw), lane, hp_load, w2t_epi);
                 }
@@ -2489,10 +2342,10 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                             const gfloat* const gq = sb + sl.h_pre + (size_t)(col < rows ? col : RA) * F + wave * FS + 4 * quad;
                             gd[0] = ld_ntg4(gq); gd[1] = ld_ntg4(gq + 16);
                         }
-                        u32x4 ah[KB32], am[KB32], al[KB32];
-                        a_load(ah, am, al, lane);
+                        u32x4 ah[KB32], al[KB32];
+                        a_load(ah, al, lane);
                         f32x4 dh[2], nob[2];
-                        swideT_from<0, 0, NTS, KB32, false>(sring, dh, nob, nullptr, ah, am, sqb, lane);
+                        swideT_from<0, 0, NTS, KB32, false>(sring, dh, nob, nullptr, ah, al, sqb, lane);
                         dh[0] *= gd[0]; dh[1] *= gd[1];
                         stallR_run<U_W1, 1, E, false>(sring, acc_f, dh, sqb, lane);
                     } else
@@ -2537,7 +2390,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 rows_of(sl_, ao, ni, nullptr, 0);
                 if constexpr (PAIR) { for (int i = 0; i < HC; ++i) ps[i] = psx[i]; } else
                 psum_all(ps, rs_o);
-                if constexpr (SPW && DFF_F16_ON(FOLD)) {   // the FFN backward chain ran in this row's scaled units
+                if constexpr (SPW) {   // the FFN backward chain ran in this row's scaled units
 #pragma unroll
                     for (int i = 0; i < HC; ++i) ps[i] *= invD;
                 }
@@ -2636,16 +2489,16 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 (void)more;
                 // what follows: FFN backward of layer l - 1 (W2^T, W1^T); after layer 0 the next step re-stages its own first units
                 const DffLayerDev& lwp = m.layer[l > 0 ? l - 1 : 0];
-                const SSeq<U_GX, U_QKVT, MW, KS, KT, KS, KS, E, 4 * KB32> sqa{ss_woxt(lw, wave), ss_qkvt(lw, wave), ss_w2t(lwp), ss_w1t(lwp)};   // tile 4 of 5: [r | g_D]
+                const SSeq<U_GX, U_QKVT, MW, E, 4 * KB32> sqa{ss_woxt(lw, wave), ss_qkvt(lw, wave), ss_w2t(lwp), ss_w1t(lwp)};   // tile 4 of 5: [r | g_D]
                 // ... and after layer 0 (x-independent inputs: no back-projection) the NEXT STEP's first units -- [W_o;W_oc] of layer 0
                 // when its q' comes from the table / the stash, QKV_ext otherwise -- requested by the G_ext GEMM's last refills,
                 // a whole update stage before the step that needs them begins (they used to be requested at the END of the update
                 // stage: with no row stage A in front of it -- Langevin, `skipA` -- the first attention block then opened with
                 // an exposed L2 round trip)
                 const SStream nx0 = EARLY ? (c0n ? ss_wox(m.layer[0], wave) : ss_qkv(m.layer[0], wave)) : ss_w2t(lwp);
-                const SSeq<U_GX, 0, EARLY ? SDR : MW, KS, KS, KS, KS, E, 4 * KB32> sqa0{ss_woxt(lw, wave), ss_woxt(lw, wave), nx0, EARLY ? nx0 : ss_w1t(lwp)};
-                u32x4 dah[KB32], dam[KB32], dal[KB32];   // SPW: dattn as bf16 pieces
-                if constexpr (SPW) a_load(dah, dam, dal, lane);
+                const SSeq<U_GX, 0, EARLY ? SDR : MW, E, 4 * KB32> sqa0{ss_woxt(lw, wave), ss_woxt(lw, wave), nx0, EARLY ? nx0 : ss_w1t(lwp)};
+                u32x4 dah[KB32], dal[KB32];   // SPW: dattn as fp16 pieces
+                if constexpr (SPW) a_load(dah, dal, lane);
                 // this lane's share of the head's dE/dx terms (extension tiles of G_ext, dV_ext, dK_ext: rows quad * 4 + r,
                 // column col): summed in registers and added to the wave's dxw ONCE per layer -- as three LDS
                 // read-modify-writes per layer they were four dependent round trips each (the compiler cannot tell that
@@ -2673,11 +2526,11 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                     f32x4* const dxrp = &dxr;
                     // fp16 engine: dattn came in row-scaled (stage E): G_ext leaves the GEMM in true units again
                     f32x4 gi4 = {1.f, 1.f, 1.f, 1.f};
-                    if constexpr (F16E) gi4 = *(const lf32x4*)(rsc + 16 + 4 * quad);
-                    swide_run<0, 5, KB32, 1>(sring, none, dah, dam, dal, sq, lane,
+                    if constexpr (SPW) gi4 = *(const lf32x4*)(rsc + 16 + 4 * quad);
+                    swide_run<0, 5, KB32, 1>(sring, none, dah, dal, sq, lane,
                         [=](int, float (&)[1]) {},
                         [=](int t, const f32x4& acc0, const float (&)[1]) {
-                            const f32x4 acc = F16E ? acc0 * gi4 : acc0;
+                            const f32x4 acc = SPW ? acc0 * gi4 : acc0;
                             gb[l0 + 16 * t] = acc[0]; gb[l1 + 16 * t] = acc[1];
                             gb[l2 + 16 * t] = acc[2]; gb[l3 + 16 * t] = acc[3];
                             if (t == 4) *dxrp -= acc;
@@ -2708,7 +2561,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 const lfloat* const qkvt_xa = Gx + col * XLD + 64 + quad;
                 auto dqkv = [&]() {
                     // dV_ext = P^T G_ext -> V region (ext columns: dx term sum_i a_ij r_i)
-                    constexpr bool MMS = DFF_MM_SPLIT && H > 64;
+                    constexpr bool MMS = H > 64;
                     wv_mm5<MMS, true, XLD>(pb, Gx, lane, ks4, [&](int nt, const f32x4& acc) {
                         if constexpr (FOLD) { if (nt < 4) acc_a[nt < 4 ? nt : 0] += acc; }   // v = n: dV IS a term of d(LayerNorm output)
 #pragma unroll
@@ -2771,7 +2624,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                 // G_ext^T -> true-unit rows in the G region (all tiles, or the extension tile only), dxT -= r_i, returns dS^T
                 auto gds_T = [&](const auto& sq, bool all_tiles) -> f32x4 {
                     f32x4 gt[5], nob[2];
-                    swideT_from<0, 0, 5, KB32, false>(sring, gt, nob, nullptr, dah, dam, sq, lane);
+                    swideT_from<0, 0, 5, KB32, false>(sring, gt, nob, nullptr, dah, dal, sq, lane);
                     const float gi = rsc[16 + min(col, RLA - 1)];   // dattn came in row-scaled (stage E): 1 / scale of row i
                     if (all_tiles) {
 #pragma unroll
@@ -2933,7 +2786,7 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
                         dqkv();
                         pf.tick(17); DFF_MARK(17);
                         if constexpr (SPW) stall_run<U_GX, NKT, E, true>(sring, acc_a, qkvt_fa32, sqa, lane, qkvt_xa, qkvt_ext(lw, wave, lane), DFF_HEADS * 13 * 256,
-                                                                         F16E ? rsc : nullptr, !FOLD);   // (dQ' rows re-scaled by their dattn row's scale; unfolded: [dQ | dK | dV] by one common scale)
+                                                                         rsc, !FOLD);   // (dQ' rows re-scaled by their dattn row's scale; unfolded: [dQ | dK | dV] by one common scale)
                         else tall_run<5 % DR, 13, E, 4>(ring, acc_a, qkvt_fa, s_qkvt(lw, wave), after, lane);   // 18 entries: phase 0
                         pf.tick(18); DFF_MARK(18);
                     }
@@ -3252,16 +3105,13 @@ __global__ __launch_bounds__((PAIR ? 4 : NW) * 64) void dff_small_kernel(const D
 #ifndef DFF_SMALL_MODE
 #error "compile dff_small.hip with -DDFF_SMALL_MODE=0|1|2 (DFF_MODE_SCORE / LANGEVIN / DDPM): build.sh builds all three"
 #endif
-#if DFF_SMALL_MODE == 0
-int dff_small_f16_level() { return DFF_F16; }
-#endif
 #define DFF_CAT2(a, b) a##b
 #define DFF_CAT(a, b) DFF_CAT2(a, b)
 bool DFF_CAT(dff_small_pick_m, DFF_SMALL_MODE)(int H, int NW, bool gen, bool spw, const void** fn, unsigned* lds_floats, const char** name, bool fold,
                                                bool pair) {
     constexpr int MD = DFF_SMALL_MODE;
     if (pair) {   // two workgroups per protein: the FOLD kernel on the fp16 engine, sampling loops only
-#if DFF_F16 >= 1 && DFF_SMALL_MODE != 0
+#if DFF_SMALL_MODE != 0
         if (H == 64 && NW == 8 && spw && fold && !gen) {
             *fn = (const void*)&dff_small_kernel<64, 8, false, true, true, MD, true>;
             *lds_floats = SmallLds<64, 8, true, 4>::total;
@@ -3274,14 +3124,13 @@ bool DFF_CAT(dff_small_pick_m, DFF_SMALL_MODE)(int H, int NW, bool gen, bool spw
     if (H == 64 && NW == 8 && spw && fold && !gen) {
         *fn = (const void*)&dff_small_kernel<64, 8, false, true, true, MD>;
         *lds_floats = SmallLds<64, 8, true>::total;
-        *name = DFF_F16 ? "dff_small_kernel<64,8,split_f16,fold_kv>" : "dff_small_kernel<64,8,split_bf16,fold_kv>";
+        *name = "dff_small_kernel<64,8,split_f16,fold_kv>";
         return true;
     }
     if (H == 64 && NW == 8 && spw) {
         *fn = gen ? (const void*)&dff_small_kernel<64, 8, true, true, false, MD> : (const void*)&dff_small_kernel<64, 8, false, true, false, MD>;
         *lds_floats = SmallLds<64, 8>::total;
-        *name = DFF_F16 >= 2 ? (gen ? "dff_small_kernel<64,8,gen,split_f16>" : "dff_small_kernel<64,8,split_f16>")
-                             : (gen ? "dff_small_kernel<64,8,gen,split_bf16>" : "dff_small_kernel<64,8,split_bf16>");
+        *name = gen ? "dff_small_kernel<64,8,gen,split_f16>" : "dff_small_kernel<64,8,split_f16>";
         return true;
     }
 #define SMALL_CASE(H_, NW_)                                                                                          \
