@@ -215,7 +215,8 @@ int dff_pwd_hist(int device, const float* x_dev, long long n, int n_beads, int o
  * independent.  Only per-frame results (and one N x N count matrix) are written; the histogram and divergence
  * reductions stay on the host (two-for-one-diffusion_amd/evaluate.py).  No synchronisation on the launch path. */
 /* rmsd_dev[s] = minimum over proper rotations of the RMSD between frame s and ref_dev (N, 3), both centred on their
- * unweighted mean; fp64 accumulation + QCP.  NaN for a frame with any non-finite coordinate.
+ * unweighted mean; fp64 accumulation, largest eigenvalue of Horn's 4x4 key matrix by cyclic Jacobi.  NaN for a frame
+ * with any non-finite coordinate.
  * Replaces md.rmsd(traj, folded) * 10 with its valid_mask, evaluate/evaluators.py:656-662. */
 int dff_struct_rmsd(int device, const float* x_dev, long long n, int n_beads, const float* ref_dev,
                     float* rmsd_dev, void* stream);

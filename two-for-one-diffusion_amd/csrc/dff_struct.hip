@@ -19,8 +19,12 @@
 //   distance   pwd_dist2 (dff_pwd.hip): sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) in fp32, bit-equal to torch.norm
 //   dihedral   mdtraj's formula in fp32: b1 = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2,
 //              phi = atan2((b1 . c1) |b2|, c1 . c2)
-//   RMSD       fp64 centring, 3x3 correlation and inner products; lambda_max of Horn's 4x4 key matrix by Newton on
-//              its characteristic quartic (QCP, Theobald 2005) -- the optimal PROPER rotation, as mdtraj
+//   RMSD       fp64 centring, 3x3 correlation and inner products; lambda_max of Horn's symmetric 4x4 key matrix K by
+//              cyclic Jacobi in fp64 (<= 8 sweeps, stop when the off-diagonal is below 1e-15 ||K||) -- the optimal PROPER
+//              rotation, as mdtraj.  Not Newton on K's characteristic quartic (QCP, Theobald 2005): for an elongated
+//              frame or reference the two largest eigenvalues nearly coincide, the quartic has a near-double root that
+//              it fixes only to ~sqrt(eps) lambda, and Newton stopped up to 4.4e-2 A off on straight chains.  Jacobi
+//              is backward-stable: lambda_max to ~eps ||K||, whatever the spacing of the eigenvalues.
 //   TIC        features (N - 3 dihedrals, then the N (N - 1) / 2 distances in triu_indices(N, N, 1) order) in fp32,
 //              never stored; out[s, c] = sum_f ((double) feat_f - mean_f) * A[f, c] accumulated in fp64
 #pragma once
@@ -86,10 +90,43 @@ __device__ __forceinline__ void struct_tiles(float* tile, const float* __restric
     }
 }
 
-// ---- RMSD to a reference structure (fp64 QCP).  LDS: tile | centred reference (N x 3 doubles)
-__device__ __forceinline__ double det3(double a, double b, double c, double d, double e, double f, double g, double h,
-                                       double i) {
-    return a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+// ---- RMSD to a reference structure (fp64, Horn's key matrix).  LDS: tile | centred reference (N x 3 doubles)
+// one Jacobi rotation of the symmetric 4x4 matrix in the (p, q) plane: a_pq -> 0.  (r, s) are the other two indices;
+// arp = a_rp, arq = a_rq, asp = a_sp, asq = a_sq.  t = tan of the rotation angle, the smaller root of t^2 + 2 theta t = 1;
+// 1 / (2 theta) when theta^2 would overflow (a_pq negligible next to a_qq - a_pp).
+__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& asp,
+                                           double& asq) {
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = fabs(theta) > 1e150 ? 0.5 / theta : copysign(1.0, theta) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+    const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0.0;
+    const double g = arp, h = arq, u = asp, v = asq;
+    arp = c * g - s * h;
+    arq = s * g + c * h;
+    asp = c * u - s * v;
+    asq = s * u + c * v;
+}
+
+// largest eigenvalue of the symmetric 4x4 [[a00 a01 a02 a03] [. a11 a12 a13] [. . a22 a23] [. . . a33]]: cyclic Jacobi.
+// The off-diagonal mass falls quadratically, so a few sweeps reach the stop; the cap only bounds the loop.
+__device__ __forceinline__ double sym4_lambda_max(double a00, double a01, double a02, double a03, double a11, double a12,
+                                                  double a13, double a22, double a23, double a33) {
+    const double nrm = a00 * a00 + a11 * a11 + a22 * a22 + a33 * a33 +
+                       2.0 * (a01 * a01 + a02 * a02 + a03 * a03 + a12 * a12 + a13 * a13 + a23 * a23);
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        const double off = a01 * a01 + a02 * a02 + a03 * a03 + a12 * a12 + a13 * a13 + a23 * a23;
+        if (!(off > 1e-30 * nrm)) break;                       // also ends at once on K = 0
+        jacobi_rot(a00, a11, a01, a02, a12, a03, a13);         // (0, 1): others 2, 3
+        jacobi_rot(a00, a22, a02, a01, a12, a03, a23);         // (0, 2): others 1, 3
+        jacobi_rot(a00, a33, a03, a01, a13, a02, a23);         // (0, 3): others 1, 2
+        jacobi_rot(a11, a22, a12, a01, a02, a13, a23);         // (1, 2): others 0, 3
+        jacobi_rot(a11, a33, a13, a01, a03, a12, a23);         // (1, 3): others 0, 2
+        jacobi_rot(a22, a33, a23, a02, a03, a12, a13);         // (2, 3): others 0, 1
+    }
+    return fmax(fmax(a00, a11), fmax(a22, a33));
 }
 
 __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_rmsd_kernel(const float* __restrict__ x, long long n,
@@ -135,25 +172,7 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_rmsd_kernel(const 
             const double k11 = Sxx - Syy - Szz, k12 = Sxy + Syx, k13 = Szx + Sxz;
             const double k22 = -Sxx + Syy - Szz, k23 = Syz + Szy;
             const double k33 = -Sxx - Syy + Szz;
-            // characteristic polynomial l^4 + C2 l^2 + C1 l + C0: C2 = -||K||^2 / 2 = -2 ||S||^2, C1 = -8 det S, C0 = det K
-            const double C2 = -2.0 * (Sxx * Sxx + Sxy * Sxy + Sxz * Sxz + Syx * Syx + Syy * Syy + Syz * Syz + Szx * Szx +
-                                      Szy * Szy + Szz * Szz);
-            const double C1 = -8.0 * det3(Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz);
-            const double C0 = k00 * det3(k11, k12, k13, k12, k22, k23, k13, k23, k33) -
-                              k01 * det3(k01, k12, k13, k02, k22, k23, k03, k23, k33) +
-                              k02 * det3(k01, k11, k13, k02, k12, k23, k03, k13, k33) -
-                              k03 * det3(k01, k11, k12, k02, k12, k22, k03, k13, k23);
-            // Newton from (Ga + Gb) / 2 >= lambda_max: monotone descent onto the largest root
-            double l = 0.5 * (Ga + Gb);
-            for (int it = 0; it < 50 && finite; ++it) {
-                const double l2 = l * l, bq = (l2 + C2) * l, aq = bq + C1;
-                const double P = aq * l + C0, dP = 2.0 * l2 * l + bq + aq;
-                if (!(dP != 0.0)) break;
-                const double ln = l - P / dP;
-                const bool done = fabs(l - ln) <= 1e-13 * fabs(ln);
-                l = ln;
-                if (done) break;
-            }
+            const double l = finite ? sym4_lambda_max(k00, k01, k02, k03, k11, k12, k13, k22, k23, k33) : 0.0;
             const double msd = (Ga + Gb - 2.0 * l) / N;
             out[s0 + lane] = finite ? (float)sqrt(msd > 0.0 ? msd : 0.0) : __builtin_nanf("");
         }
