@@ -239,6 +239,35 @@ int dff_struct_tic(int device, const float* x_dev, long long n, int n_beads, con
 int dff_struct_contacts(int device, const float* x_dev, long long n, int n_beads, float cutoff,
                         const uint8_t* folded_dev, int offset, uint32_t* counts_dev, uint32_t* mismatch_dev,
                         void* stream);
+/* out_dev (n, F) fp32: the TIC features of every frame, N - 3 dihedrals then the pair distances in
+ * torch.triu_indices(N, N, 1) order -- bit for bit the values dff_struct_tic projects.
+ * Replaces get_tic_features, evaluate/evaluators.py:433-445. */
+int dff_struct_tic_features(int device, const float* x_dev, long long n, int n_beads, float* out_dev, void* stream);
+
+/* ---- TICA fitting: lag-tau second moments of the TIC features (csrc/dff_tica.hip) ----
+ * The GPU half of TICA(lagtime, dim).fit_transform(get_tic_features(sorted data)), evaluate/evaluators.py:384-420: the
+ * running sums of deeptime's symmetrised covariance estimator.  The covariances and the decomposition stay on the host
+ * (two-for-one-diffusion_amd/evaluate.py).
+ * Bytes of device workspace dff_tica_moments needs for calls of up to n_frames_max frames; -1 on bad arguments. */
+long long dff_tica_workspace_bytes(int n_beads, long long n_frames_max, int lagtime);
+/* x_dev (n, N, 3) fp32 holds n_traj time-ordered trajectories back to back, lengths_host[i] frames each (sum = n).
+ * With g_t = feat(t) - shift_dev (fp64, F = dff_struct_tic_num_features(N)) and a_t = 1 when t lies in the first
+ * L_i - lagtime frames of its trajectory (pairs never cross a trajectory; L_i <= lagtime contributes nothing), the call
+ * ADDS, in fp64 (products on the f64 matrix cores), to the device accumulators
+ *   sx_dev (F) += sum a_t g_t,   sy_dev (F) += sum a_t g_{t+lag},
+ *   m0_dev (F, F) += sum a_t (g_t g_t^T + g_{t+lag} g_{t+lag}^T),   mt_dev (F, F) += sum a_t (g_t g_{t+lag}^T + g_{t+lag} g_t^T),
+ * the matrices row-major, upper triangle (i <= j) only: the lower triangle is not touched.  Consecutive calls stream
+ * trajectories (deeptime's partial_fit).  Deterministic: bit-identical from call to call, no atomics.
+ * workspace_dev: >= dff_tica_workspace_bytes(N, n, lagtime) bytes.  4 <= N <= 64, lagtime >= 1. */
+int dff_tica_moments(int device, const float* x_dev, long long n, int n_beads, const long long* lengths_host, int n_traj,
+                     int lagtime, const double* shift_dev, void* workspace_dev, size_t workspace_bytes, double* sx_dev,
+                     double* sy_dev, double* m0_dev, double* mt_dev, void* stream);
+/* Host only, for tests: the chunk plan dff_tica_moments follows for these lengths (chunk_pairs > 0 overrides the chunk
+ * size C, <= 0 takes the one of n_beads).  Writes up to max_runs records of 6 values, one per run of consecutive pair starts:
+ * (chunk, chunk's first frame f0, chunk's feature rows, chunk's pairs, run's first pair start - f0, run's pairs); returns
+ * the number of runs, -1 on bad arguments. */
+int dff_tica_debug_plan(int n_beads, const long long* lengths_host, int n_traj, int lagtime, long long chunk_pairs,
+                        long long* out_host, int max_runs);
 
 const char* dff_last_error(void);
 const char* dff_version(void);

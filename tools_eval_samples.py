@@ -5,6 +5,11 @@ evaluate/saved_references, or .npz TICA models), and prints Evaluator.eval() as 
 the RMSD free-energy curve and the contact BCE to the folded structure of a folded PDB.
 
     python tools_eval_samples.py SAMPLES.pt MOL SAVED_REF_DIR [--ref-data VAL.pt] [--folded-pdb PDB]
+                                 [--tica-fit-data TRAJ.pt [--lagtime 100]]
+
+Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
+list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
+validation data it is histogrammed on.
 """
 import argparse
 import json
@@ -25,12 +30,20 @@ def main():
                                                      "reference exists (PWD at offset 0)")
     ap.add_argument("--evalset", default="testset")
     ap.add_argument("--folded-pdb", default=None, help="folded PDB: also report the RMSD curve and the contact BCE")
+    ap.add_argument("--tica-fit-data", default=None, help="time-ordered trajectories (.pt: (n, N, 3) Angstrom or a list "
+                                                          "of them) to fit a TICA model on where none is saved")
+    ap.add_argument("--lagtime", type=int, default=100, help="TICA lag time in frames (with --tica-fit-data)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
+    fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
+    if isinstance(fit, torch.Tensor):
+        fit = fit.float()
+    elif fit is not None:
+        fit = [torch.as_tensor(t).float() for t in fit]
     res = evaluate.Evaluator(ref, None, a.mol, evalsetname=a.evalset, saved_ref_dir=a.saved_ref_dir,
-                             device=a.device).eval(x, 0)
+                             tica_fit_data=fit, tica_lagtime=a.lagtime, device=a.device).eval(x, 0)
     if a.folded_pdb:
         mol = a.mol.lower()
         re = evaluate.RmsdEvaluator(mol, a.folded_pdb, saved_ref_dir=a.saved_ref_dir, device=a.device)

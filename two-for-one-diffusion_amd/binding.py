@@ -71,6 +71,11 @@ SYMBOLS = {
     "dff_struct_tic_num_features": (C.c_int, [C.c_int]),
     "dff_struct_tic": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, _P, _P]),
     "dff_struct_contacts": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_float, _P, C.c_int, _P, _P, _P]),
+    "dff_struct_tic_features": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P]),
+    "dff_tica_workspace_bytes": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "dff_tica_moments": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_size_t,
+                                   _P, _P, _P, _P, _P]),
+    "dff_tica_debug_plan": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_longlong, _P, C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -422,3 +427,66 @@ def struct_contacts(x, cutoff: float, folded=None, offset: int = 3):
     _check(lib, lib.dff_struct_contacts(x.device.index, _ptr(x), n, N, float(cutoff), _ptr(f), int(offset),
                                         _ptr(counts), _ptr(mism), _stream(x)), "dff_struct_contacts")
     return counts.to(torch.int64), (mism.to(torch.int64) if mism is not None else None)
+
+
+def struct_tic_features(x):
+    """TIC features (N - 3 dihedrals, then the pair distances in triu_indices order) of every frame of x (n, N, 3)
+    -> float32 CUDA tensor (n, F): get_tic_features, the values struct_tic projects."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((n, struct_tic_num_features(N)), dtype=torch.float32, device=x.device)
+    _check(lib, lib.dff_struct_tic_features(x.device.index, _ptr(x), n, N, _ptr(out), _stream(x)),
+           "dff_struct_tic_features")
+    return out
+
+
+# ---- TICA moments (dff_tica_*) ----
+def tica_workspace_bytes(n_beads: int, n_frames_max: int, lagtime: int) -> int:
+    lib = load_library()
+    b = int(lib.dff_tica_workspace_bytes(int(n_beads), int(n_frames_max), int(lagtime)))
+    if b < 0:
+        _check(lib, 1, "dff_tica_workspace_bytes")
+    return b
+
+
+def tica_moments(x, lengths, lagtime: int, shift, sx, sy, m0, mt, workspace=None):
+    """Add the lag-`lagtime` moments of the trajectories x (n, N, 3) (back to back, `lengths` frames each) to the
+    float64 CUDA accumulators sx, sy (F,) and m0, mt (F, F) (upper triangles): dff_tica_moments.  g = features - shift
+    (float64 (F,) CUDA).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    F = struct_tic_num_features(N)
+    for name, t, shape in (("shift", shift, (F,)), ("sx", sx, (F,)), ("sy", sy, (F,)), ("m0", m0, (F, F)),
+                           ("mt", mt, (F, F))):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == x.device
+                and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{name} must be a contiguous float64 tensor {shape} on {x.device}")
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    if workspace is None:
+        workspace = torch.empty(max(tica_workspace_bytes(N, n, lagtime), 1), dtype=torch.uint8, device=x.device)
+    _check(lib, lib.dff_tica_moments(x.device.index, _ptr(x), n, N, ln.ctypes.data_as(C.c_void_p), int(ln.size),
+                                     int(lagtime), _ptr(shift), _ptr(workspace),
+                                     int(workspace.numel() * workspace.element_size()), _ptr(sx),
+                                     _ptr(sy), _ptr(m0), _ptr(mt), _stream(x)), "dff_tica_moments")
+    return workspace
+
+
+def tica_debug_plan(n_beads: int, lengths, lagtime: int, chunk_pairs: int = 0) -> np.ndarray:
+    """The chunk plan of dff_tica_moments (host only): int64 (runs, 6) of (chunk, f0, rows, chunk pairs, run start - f0,
+    run pairs)."""
+    lib = load_library()
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    cap = 1024
+    while True:
+        out = np.zeros((cap, 6), np.int64)
+        k = lib.dff_tica_debug_plan(int(n_beads), ln.ctypes.data_as(C.c_void_p), int(ln.size), int(lagtime),
+                                    int(chunk_pairs), out.ctypes.data_as(C.c_void_p), cap)
+        if k < 0:
+            _check(lib, 1, "dff_tica_debug_plan")
+        if k <= cap:
+            return out[:k]
+        cap = k

@@ -16,6 +16,7 @@
 #include "dff_device.h"
 #include "dff_pwd.hip"
 #include "dff_struct.hip"
+#include "dff_tica.hip"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...) {
@@ -1439,6 +1440,169 @@ extern "C" int dff_struct_contacts(int device, const float* x, long long n, int 
                        N, cutoff, folded, offset, counts, mismatch, struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
     HIPCHK(hipGetLastError());
     return DFF_OK;
+}
+
+extern "C" int dff_struct_tic_features(int device, const float* x, long long n, int N, float* out, void* stream_) {
+    int rc = struct_check(x, n, N, out, "struct_tic_features");
+    if (rc) return rc;
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    const unsigned lds = struct_tile_bytes(N) + (unsigned)(DFF_STRUCT_TILE * (DFF_TICA_FCH + 1) * sizeof(float));
+    hipLaunchKernelGGL(dff_tica_features_kernel, dim3(struct_grid(n, 8192)), dim3(DFF_STRUCT_TILE), lds,
+                       (hipStream_t)stream_, x, n, N, out, struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// TICA moments (dff_tica.hip)
+// ---------------------------------------------------------------------------------------------
+// Shapes of the moments pipeline, from the bead count and the largest call only: F features, NB 64-feature blocks, NT
+// upper-triangular tiles, C pair starts per chunk (256 MB of fp32 feature rows), at most `slices` pair slices per launch
+// (NT * slices ~ DFF_TICA_WGS workgroups, and no more slices than a call of n_max frames has stages of pairs).
+struct TicaShape {
+    int F, NB, NT, slices;
+    long long C;
+    TicaShape(int N, long long n_max) {
+        F = dff_struct_tic_num_features(N);
+        NB = (F + DFF_TICA_T - 1) / DFF_TICA_T;
+        NT = NB * (NB + 1) / 2;
+        C = (1LL << 28) / (4LL * F) / DFF_TICA_K * DFF_TICA_K;
+        const long long stages = ((n_max < C ? n_max : C) + DFF_TICA_K - 1) / DFF_TICA_K;
+        const int want = (DFF_TICA_WGS + NT - 1) / NT;
+        slices = stages < want ? (int)(stages > 1 ? stages : 1) : want;
+    }
+    size_t part_bytes() const { return (size_t)slices * NT * 2 * DFF_TICA_T * DFF_TICA_T * sizeof(double); }
+    size_t psum_bytes() const { return (size_t)slices * NB * 2 * DFF_TICA_T * sizeof(double); }
+    size_t feat_bytes(long long n_max, int lag) const {
+        const long long rows = n_max < C + lag ? n_max : C + lag;
+        return ((size_t)rows * F * sizeof(float) + 255) & ~(size_t)255;
+    }
+};
+
+// The chunks of one call: runs of consecutive pair starts t (t and t + lag in one trajectory), at most DFF_TICA_RUNS runs
+// per chunk, every pair start of a chunk below f0 + C (f0 = the chunk's first pair start), so that the chunk's feature
+// rows f0 .. last pair start + lag number at most C + lag.  A run that would start at or past f0 + C opens a new chunk:
+// frames that start no pair (a trajectory's last lag frames, trajectories of <= lag frames) may lie across that limit.
+// chunk(f0, rows, runs, pairs) is called once per chunk, pairs > 0.
+template <class Chunk>
+static int tica_plan(long long C, const long long* lengths, int n_traj, int lag, Chunk chunk) {
+    TicaRuns runs;
+    runs.n = 0;
+    long long f0 = 0, last = 0;
+    int pairs = 0, rc;
+    auto flush = [&]() -> int {
+        runs.cum[runs.n] = pairs;
+        const int r = chunk(f0, last + lag - f0, runs, pairs);
+        runs.n = 0;
+        pairs = 0;
+        return r;
+    };
+    long long o = 0;
+    for (int i = 0; i < n_traj; o += lengths[i], ++i) {
+        long long a = o;
+        const long long b = o + lengths[i] - lag;       // pair starts [a, b)
+        while (a < b) {
+            if (runs.n == DFF_TICA_RUNS || (runs.n && a >= f0 + C))
+                if ((rc = flush())) return rc;
+            if (runs.n == 0) f0 = a;
+            const long long e = b < f0 + C ? b : f0 + C;  // > a: a < f0 + C here
+            runs.row[runs.n] = (int)(a - f0);
+            runs.cum[runs.n] = pairs;
+            pairs += (int)(e - a);
+            ++runs.n;
+            last = e;                                   // one past the chunk's last pair start
+            a = e;
+        }
+    }
+    if (runs.n && (rc = flush())) return rc;
+    return DFF_OK;
+}
+
+extern "C" long long dff_tica_workspace_bytes(int n_beads, long long n_frames_max, int lagtime) {
+    if (n_beads < 4 || n_beads > DFF_MAX_BEADS) return fail(DFF_EINVAL, "tica: n_beads must be 4..%d", DFF_MAX_BEADS), -1;
+    if (lagtime < 1) return fail(DFF_EINVAL, "tica: lagtime must be >= 1"), -1;
+    if (n_frames_max < 0) return fail(DFF_EINVAL, "tica: negative frame count"), -1;
+    const TicaShape sh(n_beads, n_frames_max);
+    return (long long)(sh.feat_bytes(n_frames_max, lagtime) + sh.part_bytes() + sh.psum_bytes());
+}
+
+static int tica_check_lengths(const long long* lengths, int n_traj, long long n, int lagtime, const char* what) {
+    if (lagtime < 1) return fail(DFF_EINVAL, "%s: lagtime must be >= 1", what);
+    if (n_traj < 0 || (n_traj > 0 && !lengths)) return fail(DFF_EINVAL, "%s: null / negative trajectory lengths", what);
+    long long total = 0;
+    for (int i = 0; i < n_traj; ++i) {
+        if (lengths[i] < 0) return fail(DFF_EINVAL, "%s: trajectory %d has negative length", what, i);
+        total += lengths[i];
+    }
+    if (total != n) return fail(DFF_EINVAL, "%s: trajectory lengths sum to %lld, not n = %lld", what, total, n);
+    return DFF_OK;
+}
+
+extern "C" int dff_tica_moments(int device, const float* x, long long n, int N, const long long* lengths, int n_traj,
+                                int lagtime, const double* shift, void* workspace, size_t workspace_bytes, double* sx,
+                                double* sy, double* m0, double* mt, void* stream_) {
+    int rc = struct_check(x, n, N, m0, "tica_moments");
+    if (rc) return rc;
+    if ((rc = tica_check_lengths(lengths, n_traj, n, lagtime, "tica_moments"))) return rc;
+    if (!shift || !sx || !sy || !m0 || !mt) return fail(DFF_EINVAL, "tica_moments: null shift / accumulator");
+    const long long need = dff_tica_workspace_bytes(N, n, lagtime);
+    if (!workspace || (long long)workspace_bytes < need)
+        return fail(DFF_EINVAL, "tica_moments: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const TicaShape sh(N, n);
+    float* feat = (float*)workspace;
+    double* part = (double*)((char*)workspace + sh.feat_bytes(n, lagtime));
+    double* psum = (double*)((char*)part + sh.part_bytes());
+    HIPCHK(hipFuncSetAttribute((const void*)&dff_tica_moments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               DFF_TICA_LDS_BYTES));
+    const unsigned feat_lds = struct_tile_bytes(N) + (unsigned)(DFF_STRUCT_TILE * (DFF_TICA_FCH + 1) * sizeof(float));
+    const unsigned magic = struct_magic(N);
+    return tica_plan(sh.C, lengths, n_traj, lagtime, [&](long long f0, long long rows, const TicaRuns& runs, int pairs) -> int {
+        // the plan's guarantees, on which every index below rests (workspace rows, slices, grid)
+        if (pairs <= 0 || pairs > sh.C || rows > sh.C + lagtime || rows > n - f0 || f0 < 0)
+            return fail(DFF_EINVAL, "tica_moments: internal chunk plan error (f0 %lld, rows %lld, pairs %d)", f0, rows, pairs);
+        const float* xc = x + f0 * 3 * N;
+        hipLaunchKernelGGL(dff_tica_features_kernel, dim3(struct_grid(rows, 8192)), dim3(DFF_STRUCT_TILE), feat_lds,
+                           stream, xc, rows, N, feat, magic, (int)(((uintptr_t)xc % 16) == 0));
+        HIPCHK(hipGetLastError());
+        const int kst = (pairs + DFF_TICA_K - 1) / DFF_TICA_K;          // stages of pairs
+        const int ns0 = kst < sh.slices ? kst : sh.slices;
+        const int per = (kst + ns0 - 1) / ns0 * DFF_TICA_K;              // pairs per slice, a multiple of the stage
+        const int ns = (pairs + per - 1) / per;                          // 1 .. sh.slices
+        hipLaunchKernelGGL(dff_tica_moments_kernel, dim3((unsigned)(ns * sh.NT)), dim3(DFF_TICA_THREADS),
+                           DFF_TICA_LDS_BYTES, stream, feat, sh.F, lagtime, shift, runs, pairs, per, sh.NB, sh.NT, part,
+                           psum);
+        HIPCHK(hipGetLastError());
+        const long long nred = (long long)sh.NT * DFF_TICA_T * DFF_TICA_T + (long long)sh.NB * DFF_TICA_T;
+        hipLaunchKernelGGL(dff_tica_reduce_kernel, dim3((unsigned)((nred + DFF_TICA_THREADS - 1) / DFF_TICA_THREADS)),
+                           dim3(DFF_TICA_THREADS), 0, stream, part, psum, sh.F, sh.NB, sh.NT, ns, sx, sy, m0, mt);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    });
+}
+
+extern "C" int dff_tica_debug_plan(int n_beads, const long long* lengths, int n_traj, int lagtime, long long chunk_pairs,
+                                   long long* out_host, int max_runs) {
+    if (n_beads < 4 || n_beads > DFF_MAX_BEADS) return fail(DFF_EINVAL, "tica_debug_plan: n_beads must be 4..%d", DFF_MAX_BEADS), -1;
+    long long n = 0;
+    for (int i = 0; i < n_traj && lengths; ++i) n += lengths[i] > 0 ? lengths[i] : 0;
+    if (tica_check_lengths(lengths, n_traj, n, lagtime, "tica_debug_plan")) return -1;
+    if (!out_host || max_runs < 0) return fail(DFF_EINVAL, "tica_debug_plan: null output"), -1;
+    const long long C = chunk_pairs > 0 ? chunk_pairs : TicaShape(n_beads, n).C;
+    int nrec = 0, chunk_id = 0;
+    const int rc = tica_plan(C, lengths, n_traj, lagtime, [&](long long f0, long long rows, const TicaRuns& runs, int pairs) -> int {
+        for (int r = 0; r < runs.n; ++r, ++nrec)
+            if (nrec < max_runs) {
+                long long* o = out_host + 6LL * nrec;
+                o[0] = chunk_id; o[1] = f0; o[2] = rows; o[3] = pairs; o[4] = runs.row[r]; o[5] = runs.cum[r + 1] - runs.cum[r];
+            }
+        ++chunk_id;
+        return DFF_OK;
+    });
+    return rc ? -1 : nrec;
 }
 
 extern "C" const char* dff_last_error(void) { return g_err.c_str(); }

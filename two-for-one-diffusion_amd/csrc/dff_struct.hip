@@ -18,7 +18,7 @@
 // Arithmetic:
 //   distance   pwd_dist2 (dff_pwd.hip): sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) in fp32, bit-equal to torch.norm
 //   dihedral   mdtraj's formula in fp32: b1 = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2,
-//              phi = atan2((b1 . c1) |b2|, c1 . c2)
+//              phi = atan2((b1 . c1) |b2|, c1 . c2), no FMA contraction (the same bits in every kernel that uses it)
 //   RMSD       fp64 centring, 3x3 correlation and inner products; lambda_max of Horn's symmetric 4x4 key matrix K by
 //              cyclic Jacobi in fp64 (<= 8 sweeps, stop when the off-diagonal is below 1e-15 ||K||) -- the optimal PROPER
 //              rotation, as mdtraj.  Not Newton on K's characteristic quartic (QCP, Theobald 2005): for an elongated
@@ -61,7 +61,11 @@ __device__ __forceinline__ void struct_load_tile(float* tile, const float* __res
     }
 }
 
+// Each product and sum rounded on its own, as numpy's float32 formula (mdtraj) rounds it: without the pragma, which
+// products the compiler fuses into FMAs depends on how it packs the code around the call, and the TIC projection,
+// the dihedral and the TIC feature kernels would differ from one another by a few ulps.
 __device__ __forceinline__ float struct_dihedral(const float* xs, int i) {
+#pragma clang fp contract(off)
     const float* p = xs + 3 * i;
     const float b1x = p[3] - p[0], b1y = p[4] - p[1], b1z = p[5] - p[2];
     const float b2x = p[6] - p[3], b2y = p[7] - p[4], b2z = p[8] - p[5];

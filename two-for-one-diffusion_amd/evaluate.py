@@ -201,6 +201,179 @@ def load_tica_reference(path, dim=2):
     return out
 
 
+# ---- TICA fitting: TICA(lagtime=100, dim=2).fit_transform(get_tic_features(...)) of evaluators.py:384-420 ----
+# deeptime 0.4.4's estimator as the reference's pickles record it: symmetrised, mean removed, no Bessel correction
+# (mean_t == mean_0, cov_tt == cov_00), kinetic-map scaling.  The sums come from the GPU (binding.tica_moments); the
+# covariances and the decomposition below are float64 numpy.
+TICA_MAX_DIM = 8          # components dff_struct_tic projects per call
+
+
+def tica_covariances(sx, sy, m0, mt, w, shift):
+    """(mean, cov_00, cov_0t) from the sums of dff_tica_moments over w frame pairs, features shifted by `shift`:
+    mu' = (S_x + S_y) / 2w, mean = shift + mu', C00 = M_0 / 2w - mu' mu'^T, C0t = M_tau / 2w - mu' mu'^T.  m0 / mt
+    hold upper triangles; they are mirrored."""
+    w = int(w)
+    if w <= 0:
+        raise ValueError("TICA: no frame pairs at this lag time (every trajectory has <= lagtime frames)")
+    sx, sy, shift = (np.asarray(a, np.float64) for a in (sx, sy, shift))
+    mu = (sx + sy) / (2.0 * w)
+    mm = np.outer(mu, mu)
+
+    def sym(m):
+        u = np.triu(np.asarray(m, np.float64))
+        return u + np.triu(u, 1).T
+
+    return shift + mu, sym(m0) / (2.0 * w) - mm, sym(mt) / (2.0 * w) - mm
+
+
+def tica_from_covariances(cov_00, cov_0t, mean, dim=2, epsilon=1e-6, scaling="kinetic_map"):
+    """TICA decomposition of symmetric C00 / C0t: {"mean", "coeff" (F, dim), "full_coeff" (F, rank),
+    "singular_values" (rank,), "rank"}.
+      1. eigh(C00), keep the eigenvalues > epsilon (their count is the rank), S = V diag(ev^-1/2);
+      2. K = S^T C0t S, eigh(K), sorted by |eigenvalue| descending (the singular values, signed);
+      3. kinetic-map coefficients W = S U diag(singular values).
+    Column signs: the entry of largest magnitude of each column of W is positive (deeptime's signs follow no rule; a
+    TIC's sign is arbitrary).  The projection is (f - mean) @ coeff."""
+    if scaling != "kinetic_map":
+        raise ValueError(f"TICA: only kinetic_map scaling is supported, not {scaling!r}")
+    dim = int(dim)
+    if not 1 <= dim <= TICA_MAX_DIM:
+        raise ValueError(f"TICA: dim must be 1..{TICA_MAX_DIM}, not {dim}")
+    c00 = np.asarray(cov_00, np.float64)
+    c0t = np.asarray(cov_0t, np.float64)
+    ev, V = np.linalg.eigh(c00)
+    keep = ev > epsilon
+    rank = int(keep.sum())
+    if dim > rank:
+        raise ValueError(f"TICA: dim = {dim} exceeds the rank {rank} of C00 at epsilon = {epsilon}")
+    S = V[:, keep] / np.sqrt(ev[keep])
+    K = S.T @ c0t @ S
+    s, U = np.linalg.eigh((K + K.T) / 2)
+    order = np.argsort(-np.abs(s), kind="stable")
+    s, U = s[order], U[:, order]
+    W = (S @ U) * s
+    big = np.argmax(np.abs(W), axis=0)
+    W = W * np.where(W[big, np.arange(W.shape[1])] < 0, -1.0, 1.0)
+    return {"mean": np.asarray(mean, np.float64), "coeff": W[:, :dim].copy(), "full_coeff": W, "singular_values": s,
+            "rank": rank}
+
+
+def tica_timescales(singular_values, lagtime):
+    """Implied timescales -lagtime / ln|s_i| (in frames)."""
+    return -float(lagtime) / np.log(np.abs(np.asarray(singular_values, np.float64)))
+
+
+class TICA:
+    """TICA(lagtime, dim) fitted on the GPU: features and lag-tau moments by the HIP kernels (dff_tica_moments),
+    covariances and decomposition in float64 numpy (tica_covariances, tica_from_covariances).
+
+    partial_fit(traj) streams one time-ordered trajectory (n, N, 3) in Angstrom; fit(data, traj_lengths=None) starts
+    afresh on an array (one trajectory, or back-to-back trajectories of `traj_lengths` frames) or a list of arrays (one
+    trajectory each).  LangevinDiffusion.sample() returns its frames simulation-major: traj_lengths =
+    [n_timesteps // save_interval] * parallel_sim fits the sampler's own runs.  Features are shifted by those of the
+    first frame fitted, for the conditioning of the sums."""
+
+    def __init__(self, lagtime, dim=2, epsilon=1e-6, *, device="cuda:0"):
+        if int(lagtime) < 1:
+            raise ValueError("TICA: lagtime must be >= 1")
+        if not 1 <= int(dim) <= TICA_MAX_DIM:
+            raise ValueError(f"TICA: dim must be 1..{TICA_MAX_DIM}")
+        self.lagtime, self.dim, self.epsilon = int(lagtime), int(dim), float(epsilon)
+        self.device = torch.device(device)
+        binding.load_library()
+        self._workspace = None
+        self.reset()
+
+    def reset(self):
+        self.n_beads = None
+        self._shift = self._acc = self._model = None
+        self.n_pairs = 0
+        return self
+
+    def _accumulate(self, xyz, lengths):
+        x = _frames(xyz, self.device)
+        n, N = int(x.shape[0]), int(x.shape[1])
+        lengths = [int(v) for v in lengths]
+        if sum(lengths) != n or min(lengths, default=0) < 0:
+            raise ValueError(f"TICA: trajectory lengths {lengths} do not add up to the {n} frames given")
+        if n == 0:
+            return self
+        if self.n_beads is None:
+            F = binding.struct_tic_num_features(N)
+            if F == 0:
+                raise ValueError("TICA: structures need at least 4 beads")
+            self.n_beads = N
+            self._shift = binding.struct_tic_features(x[:1])[0].double()
+            self._acc = [torch.zeros(shape, dtype=torch.float64, device=self.device) for shape in ((F,), (F,), (F, F), (F, F))]
+        elif N != self.n_beads:
+            raise ValueError(f"TICA: fitted on {self.n_beads} beads, got {N}")
+        need = binding.tica_workspace_bytes(N, n, self.lagtime)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        binding.tica_moments(x, lengths, self.lagtime, self._shift, *self._acc, workspace=self._workspace)
+        self.n_pairs += sum(max(L - self.lagtime, 0) for L in lengths)
+        self._model = None
+        return self
+
+    def partial_fit(self, traj):
+        """Add one time-ordered trajectory (n, N, 3) to the running sums."""
+        return self._accumulate(traj, [len(traj)])
+
+    def fit(self, data, traj_lengths=None):
+        self.reset()
+        if isinstance(data, (list, tuple)):
+            if traj_lengths is not None:
+                raise ValueError("TICA.fit: traj_lengths applies to a single array, not to a list of trajectories")
+            for traj in data:
+                self.partial_fit(traj)
+        else:
+            self._accumulate(data, [len(data)] if traj_lengths is None else traj_lengths)
+        self._estimate()
+        return self
+
+    def _estimate(self):
+        if self._model is None:
+            if self._acc is None:
+                raise ValueError("TICA: no data fitted")
+            sx, sy, m0, mt = (a.cpu().numpy() for a in self._acc)
+            mean, c00, c0t = tica_covariances(sx, sy, m0, mt, self.n_pairs, self._shift.cpu().numpy())
+            m = tica_from_covariances(c00, c0t, mean, self.dim, self.epsilon)
+            m["cov_00"], m["cov_0t"] = c00, c0t
+            self._model = m
+        return self._model
+
+    mean = property(lambda self: self._estimate()["mean"])
+    cov_00 = property(lambda self: self._estimate()["cov_00"])
+    cov_0t = property(lambda self: self._estimate()["cov_0t"])
+    singular_values = property(lambda self: self._estimate()["singular_values"])
+    coeff = property(lambda self: self._estimate()["coeff"])
+    rank = property(lambda self: self._estimate()["rank"])
+
+    def timescales(self):
+        return tica_timescales(self.singular_values, self.lagtime)
+
+    def transform(self, xyz):
+        """(n, dim) float64 TIC projections of the structures xyz (n, N, 3) in Angstrom, on the GPU."""
+        return binding.struct_tic(_frames(xyz, self.device), self.mean, self.coeff).cpu().numpy()
+
+    def fit_transform(self, data, traj_lengths=None):
+        self.fit(data, traj_lengths)
+        x = torch.cat([_frames(d, self.device) for d in data]) if isinstance(data, (list, tuple)) else data
+        return self.transform(x)
+
+    def save(self, path, **extra):
+        """Write an .npz that load_tica_reference reads (save_tica_model)."""
+        save_tica_model(path, self._estimate(), self.lagtime, **extra)
+
+
+def save_tica_model(path, model, lagtime, **extra):
+    """Write a fitted model (tica_from_covariances' dict, + cov_00 / cov_0t when present) to `path` as an .npz of mean,
+    coeff, singular_values, [cov_00, cov_0t,] lagtime and the `extra` arrays: what load_tica_reference reads."""
+    arrays = {k: model[k] for k in ("mean", "coeff", "singular_values", "cov_00", "cov_0t") if k in model}
+    with open(path, "wb") as f:
+        np.savez(f, lagtime=np.int64(lagtime), **arrays, **extra)
+
+
 # ---- host reductions, as the reference writes them ----
 def get_prob(tors_data, n_bins=61):
     """evaluators_CGflowmatching.py:39-49: phi / psi histogram on linspace(-pi, pi, n_bins), normalised to sum 1."""
@@ -331,10 +504,16 @@ class DihedralEnergiesEvaluator:
 
 class TicEvaluator:
     """Drop-in for evaluate.evaluators.TicEvaluator with a saved reference (the reference's own
-    saved_TICA_*.pickle, read without deeptime, or an .npz of its arrays).  eval() returns (tic_js, None)."""
+    saved_TICA_*.pickle, read without deeptime, or an .npz of its arrays).  eval() returns (tic_js, None).
+
+    Without a saved reference, `fit_data` (keyword-only: one time-ordered trajectory (n, N, 3) in Angstrom, or a list
+    of them) fits TICA(lagtime, dim=2) on the GPU as evaluators.py:384-420 does on the sorted dataset, projects
+    val_data, takes gt_prob = histogram2d(..., bins, density=True) and writes <saved_ref stem>.npz.  A later construction
+    loads that .npz when it is named as saved_ref, or when it is given fit_data again (it does not refit then).  Without
+    fit_data and without the saved_ref file, NotImplementedError as before."""
 
     def __init__(self, val_data, mol_name, eval_folder=None, data_folder=None, folded_pdb_folder="./datasets/folded_pdbs",
-                 bins=101, saved_ref="none", evalset="testset", *, device="cuda:0"):
+                 bins=101, saved_ref="none", evalset="testset", *, fit_data=None, lagtime=100, device="cuda:0"):
         self.mol_name = mol_name
         self.plots_folder = eval_folder
         self.bins = bins
@@ -342,12 +521,20 @@ class TicEvaluator:
         binding.load_library()
         if saved_ref == "none":
             saved_ref = f"./saved_references/saved_TICA_{mol_name.upper()}_{evalset}.pickle"
-        if not os.path.exists(saved_ref):
+        ref = None
+        if not os.path.exists(saved_ref) and fit_data is not None:
+            fitted_ref = os.path.splitext(saved_ref)[0] + ".npz"
+            if os.path.exists(fitted_ref):           # fitted by an earlier construction: load it, do not refit
+                saved_ref = fitted_ref
+            else:
+                ref = self._fit(val_data, fit_data, lagtime, fitted_ref)
+        elif not os.path.exists(saved_ref):
             raise NotImplementedError(
                 f"no saved TICA reference at {saved_ref}: fitting a new TICA model (evaluators.py:384-410) needs the "
                 f"training dataset and deeptime and is not supported; pass the reference's saved_TICA_*.pickle or an "
                 f".npz with mean, coeff, gt_prob, bin_edges_x, bin_edges_y")
-        ref = load_tica_reference(saved_ref)
+        if ref is None:
+            ref = load_tica_reference(saved_ref)
         self.mean, self.coeff = ref["mean"], ref["coeff"]
         self.gt_prob, self.bin_edges_x, self.bin_edges_y = ref["gt_prob"], ref["bin_edges_x"], ref["bin_edges_y"]
         self.bin_mids_x = (self.bin_edges_x[1:] + self.bin_edges_x[:-1]) / 2
@@ -359,6 +546,21 @@ class TicEvaluator:
             ft = self.transform(folded_ca(folded_pdb, mol_name)[None])[0]
             self.bin_x_folded = np.argmin(abs(self.bin_mids_x - ft[0]))
             self.bin_y_folded = np.argmin(abs(self.bin_mids_y - ft[1]))
+
+    def _fit(self, val_data, fit_data, lagtime, path):
+        """evaluators.py:384-420 on the GPU: fit, project val_data, histogram; write `path` (.npz) when its folder
+        exists, and return the reference as load_tica_reference would read it back."""
+        if val_data is None:
+            raise ValueError("TicEvaluator: fitting a TICA model needs val_data for the reference histogram")
+        trajs = list(fit_data) if isinstance(fit_data, (list, tuple)) else [fit_data]
+        tica = TICA(lagtime, dim=2, device=self.device).fit(trajs)
+        proj = tica.transform(val_data)
+        gt_prob, edges_x, edges_y = np.histogram2d(proj[:, 0], proj[:, 1], bins=self.bins, density=True)
+        d = os.path.dirname(path)
+        if d == "" or os.path.isdir(d):
+            tica.save(path, gt_prob=gt_prob, bin_edges_x=edges_x, bin_edges_y=edges_y)
+        return {"mean": tica.mean, "coeff": tica.coeff, "gt_prob": gt_prob, "bin_edges_x": edges_x,
+                "bin_edges_y": edges_y}
 
     def transform(self, xyz):
         """(n, dim) float64 TIC projections of the structures xyz (n, N, 3) in Angstrom, on the GPU."""
@@ -454,11 +656,13 @@ class Evaluator:
     """Drop-in for evaluate.evaluators.Evaluator: Dihedral JS (alanine), TIC JS (every protein but protein G) and
     PWD JS (all but protein G), composed as the reference composes them.  ref_data may be None when the saved
     references exist (found under `saved_ref_dir`).  The reference hands `evalsetname` to its TIC and PWD
-    evaluators, which name it `evalset`; here it is passed on as evalset, "" meaning their default "testset"."""
+    evaluators, which name it `evalset`; here it is passed on as evalset, "" meaning their default "testset".
+    `tica_fit_data` (keyword-only) is TicEvaluator's fit_data: the trajectories a TICA model is fitted on when no saved
+    TICA reference exists, at lag time `tica_lagtime` frames."""
 
     def __init__(self, ref_data, topology=None, mol_name="alanine", eval_folder=None,
                  folded_pdb_folder="./datasets/folded_pdbs", data_folder="./data", evalsetname="", *,
-                 saved_ref_dir="./saved_references", device="cuda:0"):
+                 saved_ref_dir="./saved_references", tica_fit_data=None, tica_lagtime=100, device="cuda:0"):
         if ref_data is not None and not isinstance(ref_data, torch.Tensor):
             ref_data = ref_data[:][0]
         self.ref_data = ref_data
@@ -476,7 +680,7 @@ class Evaluator:
             tic_ref = tic_ref + ".npz" if os.path.exists(tic_ref + ".npz") else tic_ref + ".pickle"
             self.tic = TicEvaluator(ref_data, mol_name, eval_folder=eval_folder, data_folder=data_folder,
                                     folded_pdb_folder=folded_pdb_folder, saved_ref=tic_ref, evalset=evalset,
-                                    device=device)
+                                    fit_data=tica_fit_data, lagtime=tica_lagtime, device=device)
         if "protein_g" != mol_name.lower():
             pwd_ref = os.path.join(saved_ref_dir, f"saved_pwd_{mol_name.upper()}_{evalset}_offset_0.pickle")
             if ref_data is None and not os.path.exists(pwd_ref):
