@@ -269,6 +269,43 @@ int dff_tica_moments(int device, const float* x_dev, long long n, int n_beads, c
 int dff_tica_debug_plan(int n_beads, const long long* lengths_host, int n_traj, int lagtime, long long chunk_pairs,
                         long long* out_host, int max_runs);
 
+/* ---- states in TIC space and the transitions between them (csrc/dff_states.hip) ----
+ * The "Dynamics" section of evaluate/evaluate_fastfolders.ipynb (cells 20-24) on the device.  Stateless like
+ * dff_struct_*: device pointers, enqueued on `stream`, no synchronisation on the launch path; n == 0 is a valid no-op
+ * (outputs that a call zeroes or overwrites are zeroed).
+ * Assignment rule of both assigning calls: d2_c = sum_j (p_j - centre_cj)^2 in fp64 (one FMA per coordinate, in order);
+ * the label is the centre of smallest d2, the lowest index among equals.  A point with a non-finite coordinate gets
+ * label -1 and d2 = NaN.
+ *
+ * Frames -> state labels in one pass: the projection of dff_struct_tic (same features, same FMA order: proj_dev, when
+ * given, is bit-identical to its output), then the nearest of the K centres centers_dev (K, k).  labels_dev (n);
+ * proj_dev (n, k) and dist2_dev (n) may be NULL.  1 <= k <= 8, 1 <= K <= 64, 4 <= n_beads <= 64.
+ * Replaces tic_evaluator.tica(get_tic_features(sampled_mol)) + MiniBatchKMeans(max_iter=0,
+ * initial_centers=...).fit_transform of cell 22. */
+int dff_struct_tic_assign(int device, const float* x_dev, long long n, int n_beads, const double* mean_dev,
+                          const double* coeff_dev, int k, const double* centers_dev, int K, int32_t* labels_dev,
+                          double* proj_dev, double* dist2_dev, void* stream);
+/* Bytes of device workspace dff_kmeans_step needs for n points when it accumulates; -1 on bad arguments. */
+long long dff_kmeans_workspace_bytes(long long n, int d, int K);
+/* One Lloyd iteration over points pts_dev (n, d) fp64 already projected, 1 <= d <= 8, 1 <= K <= 64: labels_dev (n) and
+ * dist2_dev (n) by the rule above, and -- OVERWRITTEN, over the points with finite coordinates -- sums_dev (K, d) the
+ * per-cluster coordinate sums, counts_dev (K) the member counts, inertia_dev (1) the sum of the smallest d2.  Every
+ * output may be NULL; with the three accumulators NULL the call only assigns and needs no workspace.  Deterministic:
+ * per-workgroup partials in the workspace, added in a fixed order by a second stage, no floating-point atomics --
+ * bit-identical from call to call.  The k-means the presets of cell 21 were "determined via". */
+int dff_kmeans_step(int device, const double* pts_dev, long long n, int d, const double* centers_dev, int K,
+                    int32_t* labels_dev, double* dist2_dev, double* sums_dev, uint64_t* counts_dev, double* inertia_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Sliding-window transition counts for n_lags lag times in one pass: counts_dev (n_lags, K, K), zeroed by the call;
+ * counts[l][i][j] = number of t with labels[t] = i, labels[t + lags[l]] = j, t and t + lags[l] in the same trajectory.
+ * labels_dev (n) holds n_traj trajectories back to back, lengths_host[i] frames each (sum = n), as dff_tica_moments
+ * takes them; a pair with a label outside 0 .. K - 1 (the -1 of a non-finite frame) is skipped.  lags >= 1,
+ * 1 <= n_lags <= 8, 1 <= K <= 64.  Integer counting: exact, the same from call to call.
+ * Replaces TransitionCountEstimator.count("sliding", [assignments], lagtime=1) of cell 22 (one trajectory of n frames
+ * is that call; the notebook hands it all simulations as one trajectory). */
+int dff_transition_counts(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj,
+                          const int32_t* lags_host, int n_lags, int K, uint64_t* counts_dev, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -6,19 +6,51 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
 
     python tools_eval_samples.py SAMPLES.pt MOL SAVED_REF_DIR [--ref-data VAL.pt] [--folded-pdb PDB]
                                  [--tica-fit-data TRAJ.pt [--lagtime 100]]
+                                 [--transitions [--traj-lengths L | --parallel-sim P] [--lagtimes 1,10,100]
+                                  [--n-clusters K --centers-fit-data TRAJ.pt]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
 validation data it is histogrammed on.
+
+--transitions adds the dynamics analysis of evaluate_fastfolders.ipynb (StateTransitionEvaluator) for time-ordered
+Langevin samples: state assignments in the plane of MOL's TICA model, transition counts and probabilities per lag time.
+Without --traj-lengths / --parallel-sim the samples count as ONE trajectory, as in the notebook; --parallel-sim P splits
+them into P simulations of equal length (sample.py's simulation-major output), --traj-lengths L into runs of L frames.
+The states are the notebook's presets for MOL, or are fitted by k-means (--n-clusters K) on --centers-fit-data.
 """
 import argparse
 import json
+import os
 
 import numpy as np
 import torch
 
 import dff_amd  # noqa: F401
 from dff_amd import evaluate
+
+
+def traj_lengths(a, n):
+    if a.traj_lengths is not None and a.parallel_sim is not None:
+        raise SystemExit("--traj-lengths and --parallel-sim exclude each other")
+    L = a.traj_lengths if a.traj_lengths is not None else (n // a.parallel_sim if a.parallel_sim else None)
+    if L is None:
+        return None
+    if L < 1 or n % L:
+        raise SystemExit(f"{n} frames do not split into trajectories of {L} frames")
+    return [L] * (n // L)
+
+
+def transitions(a, x):
+    mol = a.mol.lower()
+    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
+    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+    fit = torch.load(a.centers_fit_data, map_location="cpu").float() if a.centers_fit_data else None
+    st = evaluate.StateTransitionEvaluator(mol, tica, n_clusters=a.n_clusters, fit_data=fit, device=a.device)
+    r = st.eval(x, traj_lengths=traj_lengths(a, len(x)), lagtimes=[int(v) for v in a.lagtimes.split(",")])
+    return {"centers": st.centers.tolist(), "lagtimes": r["lagtimes"], "populations": r["populations"].tolist(),
+            "count_matrices": r["count_matrices"].tolist(), "transition_matrices": r["transition_matrices"].tolist(),
+            "timescales": [[None if not np.isfinite(v) else float(v) for v in t] for t in r["timescales"]]}
 
 
 def main():
@@ -33,6 +65,14 @@ def main():
     ap.add_argument("--tica-fit-data", default=None, help="time-ordered trajectories (.pt: (n, N, 3) Angstrom or a list "
                                                           "of them) to fit a TICA model on where none is saved")
     ap.add_argument("--lagtime", type=int, default=100, help="TICA lag time in frames (with --tica-fit-data)")
+    ap.add_argument("--transitions", action="store_true", help="also report state populations, transition counts and "
+                                                               "probabilities (time-ordered Langevin samples)")
+    ap.add_argument("--traj-lengths", type=int, default=None, help="frames per trajectory of the samples")
+    ap.add_argument("--parallel-sim", type=int, default=None, help="number of equal-length simulations in the samples")
+    ap.add_argument("--lagtimes", default="1", help="comma-separated lag times in frames (with --transitions)")
+    ap.add_argument("--n-clusters", type=int, default=None, help="fit this many state centres on --centers-fit-data")
+    ap.add_argument("--centers-fit-data", default=None, help="structures (.pt, (n, N, 3) Angstrom) to fit the state "
+                                                             "centres on instead of the presets")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
@@ -54,6 +94,8 @@ def main():
                              "energies": [None if not np.isfinite(v) else float(v) for v in curve["energies"]]}
         _, mean = evaluate.ContactEvaluator(mol, a.folded_pdb, device=a.device).contact_bce(x)
         res["Contact BCE"] = float(mean)
+    if a.transitions:
+        res["Transitions"] = transitions(a, x)
     print(json.dumps(res))
 
 

@@ -12,7 +12,7 @@ from .sampling import SamplerWrapper, num_to_groups, sample_from_model  # noqa: 
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",
-           "LangevinDiffusion", "ForcesWrapper"]
+           "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -25,4 +25,7 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
     if name in ("LangevinDiffusion", "ForcesWrapper"):
         from . import langevin
         return getattr(langevin, name)
+    if name in ("KMeans", "StateTransitionEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(name)

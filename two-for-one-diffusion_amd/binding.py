@@ -76,6 +76,11 @@ SYMBOLS = {
     "dff_tica_moments": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_size_t,
                                    _P, _P, _P, _P, _P]),
     "dff_tica_debug_plan": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_longlong, _P, C.c_int]),
+    "dff_struct_tic_assign": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "dff_kmeans_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "dff_kmeans_step": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                  _P]),
+    "dff_transition_counts": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -490,3 +495,94 @@ def tica_debug_plan(n_beads: int, lengths, lagtime: int, chunk_pairs: int = 0) -
         if k <= cap:
             return out[:k]
         cap = k
+
+
+# ---- states in TIC space and their transitions (dff_struct_tic_assign, dff_kmeans_*, dff_transition_counts) ----
+def _centers(centers, d, device):
+    import torch
+    c = torch.as_tensor(centers, dtype=torch.float64).to(device).contiguous()
+    if c.dim() != 2 or c.shape[1] != d:
+        raise ValueError(f"centers must be (K, {d})")
+    return c
+
+
+def struct_tic_assign(x, mean, coeff, centers, return_proj=False, return_dist2=False):
+    """State label of every frame of x (n, N, 3): the TIC projection of struct_tic (mean (F,), coeff (F, k)), then the
+    nearest of centers (K, k) -> int32 CUDA tensor (n,), -1 for a frame with a non-finite projection.  With return_proj /
+    return_dist2 a tuple (labels[, proj float64 (n, k)][, dist2 float64 (n,)])."""
+    import torch
+    lib = load_library()
+    x = _coords(x)
+    n, N = int(x.shape[0]), int(x.shape[1])
+    F = struct_tic_num_features(N)
+    m = torch.as_tensor(mean, dtype=torch.float64).to(x.device).contiguous()
+    A = torch.as_tensor(coeff, dtype=torch.float64).to(x.device).contiguous()
+    if m.shape != (F,) or A.dim() != 2 or A.shape[0] != F:
+        raise ValueError(f"mean must be ({F},) and coeff ({F}, k) for {N} beads")
+    k = int(A.shape[1])
+    c = _centers(centers, k, x.device)
+    labels = torch.empty(n, dtype=torch.int32, device=x.device)
+    proj = torch.empty((n, k), dtype=torch.float64, device=x.device) if return_proj else None
+    dist2 = torch.empty(n, dtype=torch.float64, device=x.device) if return_dist2 else None
+    _check(lib, lib.dff_struct_tic_assign(x.device.index, _ptr(x), n, N, _ptr(m), _ptr(A), k, _ptr(c), int(c.shape[0]),
+                                          _ptr(labels), _ptr(proj), _ptr(dist2), _stream(x)), "dff_struct_tic_assign")
+    out = (labels,) + ((proj,) if return_proj else ()) + ((dist2,) if return_dist2 else ())
+    return out if len(out) > 1 else labels
+
+
+def kmeans_workspace_bytes(n: int, d: int, K: int) -> int:
+    lib = load_library()
+    b = int(lib.dff_kmeans_workspace_bytes(int(n), int(d), int(K)))
+    if b < 0:
+        _check(lib, 1, "dff_kmeans_workspace_bytes")
+    return b
+
+
+def kmeans_step(points, centers, accumulate=True, workspace=None):
+    """One Lloyd step over points (n, d) (contiguous float64 CUDA) with centers (K, d): a dict of labels int32 (n,),
+    dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64 (1,) over the
+    finite points (dff_kmeans_step: deterministic).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64
+            and points.is_contiguous() and points.dim() == 2):
+        raise ValueError("points must be a contiguous float64 CUDA tensor of shape (n, d)")
+    n, d = int(points.shape[0]), int(points.shape[1])
+    c = _centers(centers, d, points.device)
+    K = int(c.shape[0])
+    out = {"labels": torch.empty(n, dtype=torch.int32, device=points.device),
+           "dist2": torch.empty(n, dtype=torch.float64, device=points.device)}
+    ws_bytes = 0
+    if accumulate:
+        out["sums"] = torch.empty((K, d), dtype=torch.float64, device=points.device)
+        out["counts"] = torch.empty(K, dtype=torch.int64, device=points.device)
+        out["inertia"] = torch.empty(1, dtype=torch.float64, device=points.device)
+        if workspace is None:
+            workspace = torch.empty(max(kmeans_workspace_bytes(n, d, K), 1), dtype=torch.uint8, device=points.device)
+        ws_bytes = int(workspace.numel() * workspace.element_size())
+    else:
+        workspace = None
+    _check(lib, lib.dff_kmeans_step(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
+                                    _ptr(out["dist2"]), _ptr(out.get("sums")), _ptr(out.get("counts")),
+                                    _ptr(out.get("inertia")), _ptr(workspace), ws_bytes, _stream(points)),
+           "dff_kmeans_step")
+    return out
+
+
+def transition_counts(labels, lengths, lagtimes, n_states: int):
+    """Sliding-window transition counts of the int32 CUDA labels (n,) -- trajectories back to back, `lengths` frames
+    each -- at every lag time of `lagtimes` -> int64 CUDA tensor (n_lags, K, K); pairs with a label outside 0 .. K - 1
+    are skipped (dff_transition_counts)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
+            and labels.is_contiguous() and labels.dim() == 1):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
+    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
+    K = int(n_states)
+    out = torch.empty((max(int(lg.size), 1), max(K, 1), max(K, 1)), dtype=torch.int64, device=labels.device)
+    _check(lib, lib.dff_transition_counts(labels.device.index, _ptr(labels), int(labels.numel()),
+                                          ln.ctypes.data_as(C.c_void_p), int(ln.size), lg.ctypes.data_as(C.c_void_p),
+                                          int(lg.size), K, _ptr(out), _stream(labels)), "dff_transition_counts")
+    return out

@@ -17,6 +17,7 @@
 #include "dff_pwd.hip"
 #include "dff_struct.hip"
 #include "dff_tica.hip"
+#include "dff_states.hip"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...) {
@@ -1603,6 +1604,140 @@ extern "C" int dff_tica_debug_plan(int n_beads, const long long* lengths, int n_
         return DFF_OK;
     });
     return rc ? -1 : nrec;
+}
+
+// ---------------------------------------------------------------------------------------------
+// States in TIC space and the transitions between them (dff_states.hip)
+// ---------------------------------------------------------------------------------------------
+static int states_check_centers(const double* centers, int K, const char* what) {
+    if (!centers) return fail(DFF_EINVAL, "%s: null centres", what);
+    if (K < 1 || K > DFF_STATES_MAXK) return fail(DFF_EINVAL, "%s: the number of centres must be 1..%d", what, DFF_STATES_MAXK);
+    return DFF_OK;
+}
+
+extern "C" int dff_struct_tic_assign(int device, const float* x, long long n, int N, const double* mean,
+                                     const double* coeff, int k, const double* centers, int K, int32_t* labels,
+                                     double* proj, double* dist2, void* stream_) {
+    int rc = struct_check(x, n, N, labels, "struct_tic_assign");
+    if (rc) return rc;
+    if (!mean || !coeff) return fail(DFF_EINVAL, "struct_tic_assign: null mean / coefficients");
+    if (k < 1 || k > DFF_TIC_MAXK) return fail(DFF_EINVAL, "struct_tic_assign: k must be 1..%d", DFF_TIC_MAXK);
+    if ((rc = states_check_centers(centers, K, "struct_tic_assign"))) return rc;
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipLaunchKernelGGL(dff_struct_tic_assign_kernel, dim3(struct_grid(n, 8192)), dim3(DFF_STRUCT_TILE),
+                       struct_tile_bytes(N), (hipStream_t)stream_, x, n, N, mean, coeff, k, centers, K, labels, proj, dist2,
+                       struct_magic(N), (int)(((uintptr_t)x % 16) == 0));
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// workgroups of the k-means step: a function of n alone (the order of every sum follows from it)
+static int kmeans_grid(long long n) {
+    const long long g = (n + DFF_KM_THREADS - 1) / DFF_KM_THREADS;
+    return (int)(g < DFF_KM_WGS ? g : DFF_KM_WGS);
+}
+
+static int kmeans_check_shape(long long n, int d, int K, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative point count", what);
+    if (d < 1 || d > DFF_KM_MAXD) return fail(DFF_EINVAL, "%s: d must be 1..%d", what, DFF_KM_MAXD);
+    if (K < 1 || K > DFF_STATES_MAXK) return fail(DFF_EINVAL, "%s: the number of centres must be 1..%d", what, DFF_STATES_MAXK);
+    return DFF_OK;
+}
+
+extern "C" long long dff_kmeans_workspace_bytes(long long n, int d, int K) {
+    if (kmeans_check_shape(n, d, K, "kmeans_workspace_bytes")) return -1;
+    return (long long)kmeans_grid(n) * (K * d + K + 1) * (long long)sizeof(double);
+}
+
+extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d, const double* centers, int K,
+                               int32_t* labels, double* dist2, double* sums, uint64_t* counts, double* inertia,
+                               void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = kmeans_check_shape(n, d, K, "kmeans_step");
+    if (rc) return rc;
+    if (!pts && n > 0) return fail(DFF_EINVAL, "kmeans_step: null points");
+    if ((rc = states_check_centers(centers, K, "kmeans_step"))) return rc;
+    const bool accumulate = sums || counts || inertia;
+    const long long need = accumulate ? dff_kmeans_workspace_bytes(n, d, K) : 0;
+    if (accumulate && n > 0 && (!workspace || (long long)workspace_bytes < need))
+        return fail(DFF_EINVAL, "kmeans_step: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n == 0) {
+        if (sums) HIPCHK(hipMemsetAsync(sums, 0, (size_t)K * d * sizeof(double), stream));
+        if (counts) HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(uint64_t), stream));
+        if (inertia) HIPCHK(hipMemsetAsync(inertia, 0, sizeof(double), stream));
+        return DFF_OK;
+    }
+    if (!accumulate && !labels && !dist2) return DFF_OK;
+    const int per = K * d + K + 1, grid = kmeans_grid(n);
+    double* part = accumulate ? (double*)workspace : nullptr;
+    hipLaunchKernelGGL(dff_kmeans_step_kernel, dim3(grid), dim3(DFF_KM_THREADS),
+                       (unsigned)(4 * per * sizeof(double)), stream, pts, n, d, centers, K, labels, dist2, part);
+    HIPCHK(hipGetLastError());
+    if (accumulate) {
+        hipLaunchKernelGGL(dff_kmeans_reduce_kernel, dim3(per), dim3(64), 0, stream, part, grid, d, K, sums,
+                           (unsigned long long*)counts, inertia);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+extern "C" int dff_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
+                                     const int32_t* lags, int n_lags, int K, uint64_t* counts, void* stream_) {
+    if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "transition_counts: null labels / negative count");
+    if (K < 1 || K > DFF_STATES_MAXK) return fail(DFF_EINVAL, "transition_counts: the number of states must be 1..%d", DFF_STATES_MAXK);
+    if (!lags || n_lags < 1 || n_lags > DFF_TC_MAXLAGS)
+        return fail(DFF_EINVAL, "transition_counts: the number of lag times must be 1..%d", DFF_TC_MAXLAGS);
+    for (int l = 0; l < n_lags; ++l)
+        if (lags[l] < 1) return fail(DFF_EINVAL, "transition_counts: lag time %d is %d, must be >= 1", l, (int)lags[l]);
+    int rc = tica_check_lengths(lengths, n_traj, n, 1, "transition_counts");
+    if (rc) return rc;
+    if (!counts) return fail(DFF_EINVAL, "transition_counts: null counts");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)n_lags * K * K * sizeof(uint64_t), stream));
+    if (n == 0) return DFF_OK;
+    // equal lengths (what the sampler produces; empty trajectories hold no frame and are left out): one launch per lag group
+    long long period = 0;
+    bool equal = true;
+    for (int i = 0; i < n_traj; ++i)
+        if (lengths[i] > 0) {
+            if (period == 0) period = lengths[i];
+            else if (lengths[i] != period) equal = false;
+        }
+    const int per_group = DFF_TC_LDS_COUNTERS / (K * K) < n_lags ? DFF_TC_LDS_COUNTERS / (K * K) : n_lags;   // >= 2
+    auto launch = [&](const TransRuns& runs) -> int {
+        const long long wgs = (runs.end - runs.begin + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
+        for (int l0 = 0; l0 < n_lags; l0 += per_group) {
+            TransLags g;
+            g.n = n_lags - l0 < per_group ? n_lags - l0 : per_group;
+            for (int l = 0; l < DFF_TC_MAXLAGS; ++l) g.lag[l] = l < g.n ? lags[l0 + l] : 0;
+            hipLaunchKernelGGL(dff_transition_counts_kernel, dim3((unsigned)(wgs < DFF_TC_WGS ? wgs : DFF_TC_WGS)),
+                               dim3(DFF_TC_THREADS), (unsigned)(g.n * K * K * sizeof(unsigned)), stream, labels, K, runs, g,
+                               (unsigned long long*)counts + (size_t)l0 * K * K);
+            HIPCHK(hipGetLastError());
+        }
+        return DFF_OK;
+    };
+    TransRuns runs;
+    memset(&runs, 0, sizeof runs);
+    if (equal) {
+        runs.begin = 0; runs.end = n; runs.period = period;
+        return launch(runs);
+    }
+    long long o = 0;
+    for (int i = 0; i < n_traj; o += lengths[i], ++i) {
+        if (lengths[i] == 0) continue;
+        if (runs.n == 0) runs.begin = o;
+        runs.start[runs.n++] = o;
+        runs.start[runs.n] = runs.end = o + lengths[i];
+        if (runs.n == DFF_TC_RUNS) {
+            if ((rc = launch(runs))) return rc;
+            runs.n = 0;
+        }
+    }
+    return runs.n ? launch(runs) : DFF_OK;
 }
 
 extern "C" const char* dff_last_error(void) { return g_err.c_str(); }

@@ -128,6 +128,17 @@ class PwdEvaluator:
 PROTEIN_IDS = {"chignolin": "CLN025", "trp_cage": "2JOF", "bba": "1FME", "villin": "2F4K", "protein_g": "NuG2"}
 RMSD_CUTOFF_REF = {"chignolin": 10, "trp_cage": 12, "bba": 14, "villin": 14, "protein_g": 20}
 RMSD_NBINS_REF = 100
+# State presets of the reference's dynamics analysis (evaluate_fastfolders.ipynb, cell 21): the number of k-means
+# clusters per protein and their centres in the plane of the first two TICs.  They belong to the reference's OWN saved
+# TICA models (saved_TICA_*.pickle): a model fitted with evaluate.TICA has its own TIC signs and scale, and needs
+# centres fitted on its own projections (StateTransitionEvaluator(fit_data=...)).  No preset exists for protein G.
+STATE_COUNTS = {"chignolin": 3, "villin": 3, "trp_cage": 3, "bba": 4}
+STATE_CENTERS = {
+    "chignolin": ((0.69400153, -0.34598462), (-0.48732213, 0.00642035), (1.87483537, 0.06285344)),
+    "trp_cage": ((-2.15921372, 0.0062795), (0.47752285, -0.38050238), (0.40182245, 2.0690773)),
+    "bba": ((-0.5756589, -0.60663654), (1.7861676, -0.87717611), (0.91295128, 1.07518898), (-0.49210152, 0.40313689)),
+    "villin": ((1.08971813, -0.98522752), (-2.49001353, -2.31375028), (-0.12929561, 0.53703407)),
+}
 K_BT_IN_KCAL_PER_MOL = 1.380650324e-23 * 300 * 6.02214076e23 / 1000 / 4.184   # evaluators_CGflowmatching.py:11-15
 
 
@@ -701,3 +712,220 @@ class Evaluator:
             with open(os.path.join(self.eval_folder, f"results-{milestone}.json"), "w") as f:
                 json.dump(dict_results, f)
         return dict_results
+
+
+# =====================================================================================================
+# Dynamics: states in TIC space and the transitions between them (evaluate_fastfolders.ipynb, cells 20-24)
+# deeptime 0.4.4 and its MiniBatchKMeans / TransitionCountEstimator are not installed where this was written, so they
+# could not be run side by side; what follows restates their documented semantics: fit_transform with max_iter=0 and
+# initial_centers assigns every point to its nearest centre (Euclidean, lowest index on a tie), and count("sliding",
+# dtrajs, lagtime) counts every pair (t, t + lagtime) inside each discrete trajectory.
+def transition_matrix(counts):
+    """Row-normalise count matrices (..., K, K) to transition probabilities, as sklearn.preprocessing.normalize(counts,
+    axis=1, norm="l1") does: every row is divided by the sum of its absolute values, an all-zero row stays zero."""
+    c = np.asarray(counts, np.float64)
+    norm = np.abs(c).sum(axis=-1, keepdims=True)
+    norm[norm == 0.0] = 1.0
+    return c / norm
+
+
+def msm_timescales(T, lagtime):
+    """Implied timescales -lagtime / ln|lambda_i|, i >= 2, of the eigenvalues of the transition matrix T (K, K) sorted
+    by magnitude, largest first (in frames; the stationary eigenvalue lambda_1 is left out)."""
+    lam = np.abs(np.linalg.eigvals(np.asarray(T, np.float64)))
+    lam = np.sort(lam)[::-1][1:]
+    with np.errstate(divide="ignore"):
+        return -float(lagtime) / np.log(lam)
+
+
+def _points(points, device):
+    p = torch.as_tensor(points)
+    if p.dim() != 2:
+        raise ValueError("points must be (n, d)")
+    return p.to(device=device, dtype=torch.float64).contiguous()
+
+
+class KMeans:
+    """Lloyd's k-means on the GPU (dff_kmeans_step per iteration; centres and the stopping rule on the host in float64).
+
+    A centre is the mean of its members; a cluster that lost all members keeps its centre.  Iteration i assigns to the
+    current centres (inertia_i = the sum of the squared distances to them), then moves them; it stops after the
+    iteration with |inertia_{i-1} - inertia_i| <= tolerance * inertia_{i-1}, or after max_iter iterations.  `inertia` is
+    that of the final centres.  init="kmeans++": the first centre is drawn uniformly, every further one with probability
+    proportional to the squared distance to the nearest centre drawn so far (torch on the device, generator seeded by
+    `seed`); initial_centers (K, d) overrides it.  max_iter=0 with initial_centers only assigns: the reference's
+    MiniBatchKMeans(max_iter=0, initial_centers=...).fit_transform call.  Points with a non-finite coordinate get label
+    -1 and take part in nothing."""
+
+    def __init__(self, n_clusters, max_iter=100, tolerance=1e-5, init="kmeans++", initial_centers=None, seed=0, *,
+                 device="cuda:0"):
+        self.n_clusters, self.max_iter, self.tolerance = int(n_clusters), int(max_iter), float(tolerance)
+        if not 1 <= self.n_clusters <= 64:
+            raise ValueError("KMeans: n_clusters must be 1..64")
+        if self.max_iter < 0:
+            raise ValueError("KMeans: max_iter must be >= 0")
+        if initial_centers is None and init != "kmeans++":
+            raise ValueError(f"KMeans: init must be 'kmeans++' (or give initial_centers), not {init!r}")
+        self.init, self.seed = init, int(seed)
+        self.initial_centers = None
+        if initial_centers is not None:
+            c = np.array(initial_centers, np.float64)
+            if c.ndim != 2 or c.shape[0] != self.n_clusters or not np.all(np.isfinite(c)):
+                raise ValueError(f"KMeans: initial_centers must be finite and ({self.n_clusters}, d)")
+            self.initial_centers = c
+        self.device = torch.device(device)
+        binding.load_library()
+        self.cluster_centers = self.inertia = None
+        self.n_iter = 0
+
+    def _seed_centers(self, pts):
+        n, K = int(pts.shape[0]), self.n_clusters
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(self.seed)
+        finite = torch.isfinite(pts).all(dim=1)
+        idx = torch.nonzero(finite).reshape(-1)
+        if idx.numel() < K:
+            raise ValueError(f"KMeans: {int(idx.numel())} finite points for {K} clusters")
+        first = idx[torch.randint(int(idx.numel()), (1,), generator=gen, device=self.device)]
+        centers = pts[first].clone()
+        for _ in range(1, K):
+            d2 = torch.nan_to_num(binding.kmeans_step(pts, centers, accumulate=False)["dist2"], nan=0.0)
+            cum = torch.cumsum(d2, 0)
+            u = torch.rand(1, dtype=torch.float64, generator=gen, device=self.device) * cum[-1]
+            nxt = torch.searchsorted(cum, u, right=True).clamp_(max=n - 1)
+            if not bool(d2[nxt] > 0):                 # every point sits on a centre already: any finite point will do
+                nxt = first
+            centers = torch.cat([centers, pts[nxt]])
+        return centers.cpu().numpy()
+
+    def fit(self, points):
+        pts = _points(points, self.device)
+        n, d = int(pts.shape[0]), int(pts.shape[1])
+        if self.initial_centers is not None:
+            if self.initial_centers.shape[1] != d:
+                raise ValueError(f"KMeans: initial_centers are {self.initial_centers.shape}, points have d = {d}")
+            centers = self.initial_centers.copy()
+        else:
+            centers = self._seed_centers(pts)
+        ws = torch.empty(max(binding.kmeans_workspace_bytes(n, d, self.n_clusters), 1), dtype=torch.uint8,
+                         device=self.device)
+        prev, self.n_iter = None, 0
+        for _ in range(self.max_iter):
+            r = binding.kmeans_step(pts, centers, workspace=ws)
+            sums, counts, inertia = r["sums"].cpu().numpy(), r["counts"].cpu().numpy(), float(r["inertia"][0])
+            has = counts > 0
+            centers = centers.copy()
+            centers[has] = sums[has] / counts[has, None]
+            self.n_iter += 1
+            if prev is not None and abs(prev - inertia) <= self.tolerance * prev:
+                break
+            prev = inertia
+        self.cluster_centers = centers
+        self.inertia = float(binding.kmeans_step(pts, centers, workspace=ws)["inertia"][0])
+        return self
+
+    def _assign(self, pts):
+        if self.cluster_centers is None:
+            raise ValueError("KMeans: not fitted")
+        return binding.kmeans_step(pts, self.cluster_centers, accumulate=False)["labels"]
+
+    def transform(self, points):
+        """(n,) int32 labels of the nearest centre."""
+        return self._assign(_points(points, self.device)).cpu().numpy()
+
+    def fit_transform(self, points):
+        pts = _points(points, self.device)
+        return self.fit(pts)._assign(pts).cpu().numpy()
+
+
+def kmeans_inertias(points, ks, *, max_iter=100, tolerance=1e-5, seed=0, device="cuda:0"):
+    """The inertia of KMeans(k).fit(points) for every k of `ks` (float64 array): the curve of the elbow method."""
+    pts = _points(points, torch.device(device))
+    return np.array([KMeans(k, max_iter, tolerance, seed=seed, device=device).fit(pts).inertia for k in ks])
+
+
+def _tica_arrays(tica, dim=2):
+    if isinstance(tica, (str, os.PathLike)):
+        ref = load_tica_reference(tica, dim)
+        return ref["mean"], ref["coeff"]
+    if isinstance(tica, (tuple, list)) and len(tica) == 2:
+        return np.asarray(tica[0], np.float64), np.asarray(tica[1], np.float64)
+    if hasattr(tica, "mean") and hasattr(tica, "coeff"):             # TicEvaluator, TICA
+        return np.asarray(tica.mean, np.float64), np.asarray(tica.coeff, np.float64)
+    raise ValueError("tica must be a TicEvaluator, a TICA, a saved-reference path or a (mean, coeff) pair")
+
+
+def _check_lengths(traj_lengths, n):
+    lengths = [int(n)] if traj_lengths is None else [int(v) for v in traj_lengths]
+    if sum(lengths) != n or min(lengths, default=0) < 0:
+        raise ValueError(f"trajectory lengths add up to {sum(lengths)}, not to the {n} frames given")
+    return lengths
+
+
+class StateTransitionEvaluator:
+    """The reference's dynamics analysis (evaluate_fastfolders.ipynb, cells 20-24) on the GPU: frames -> TIC projection
+    -> nearest state centre (one fused kernel) -> sliding-window transition counts -> transition probabilities.
+
+    `tica` is a TicEvaluator, an evaluate.TICA, the path of a saved reference, or a (mean, coeff) pair.  `centers`
+    (K, k) are the states; None takes the reference's preset for `mol_name` (STATE_CENTERS: only meaningful with the
+    reference's own saved TICA model) or, with `fit_data` (structures (n, N, 3) in Angstrom), fits
+    KMeans(n_clusters) on the projections of fit_data (n_clusters defaults to STATE_COUNTS[mol_name]).
+    eval(xyz, traj_lengths=None, ...) treats the frames as ONE trajectory, which reproduces the notebook exactly -- it
+    also counts the jump from the last frame of one simulation to the first of the next; traj_lengths =
+    [n_timesteps // save_interval] * parallel_sim gives the correct counts for LangevinDiffusion.sample()'s
+    simulation-major output.  A traj_lengths given at construction is eval's default."""
+
+    def __init__(self, mol_name, tica, centers=None, *, n_clusters=None, fit_data=None, traj_lengths=None,
+                 seed=0, device="cuda:0"):
+        self.mol_name = mol_name
+        self.device = torch.device(device)
+        self.traj_lengths = traj_lengths
+        mol = str(mol_name).lower()
+        if centers is None and fit_data is None:
+            if n_clusters is not None:
+                raise ValueError("StateTransitionEvaluator: n_clusters needs fit_data to fit the centres on")
+            if mol not in STATE_CENTERS:
+                raise ValueError(f"StateTransitionEvaluator: no preset state centres for {mol_name!r}; pass centers, or "
+                                 f"fit_data and n_clusters")
+            centers = STATE_CENTERS[mol]
+        self.mean, self.coeff = _tica_arrays(tica)
+        if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],):
+            raise ValueError("StateTransitionEvaluator: mean must be (F,) and coeff (F, k)")
+        binding.load_library()
+        self.kmeans = None
+        if centers is None:
+            k = n_clusters if n_clusters is not None else STATE_COUNTS.get(mol)
+            if k is None:
+                raise ValueError(f"StateTransitionEvaluator: n_clusters is needed to fit centres for {mol_name!r}")
+            proj = binding.struct_tic(_frames(fit_data, self.device), self.mean, self.coeff)
+            self.kmeans = KMeans(k, seed=seed, device=self.device).fit(proj)
+            centers = self.kmeans.cluster_centers
+        self.centers = np.array(centers, np.float64)
+        if self.centers.ndim != 2 or self.centers.shape[1] != self.coeff.shape[1] or not np.all(np.isfinite(self.centers)):
+            raise ValueError(f"StateTransitionEvaluator: centers must be finite and (K, {self.coeff.shape[1]})")
+        if n_clusters is not None and int(n_clusters) != len(self.centers):
+            raise ValueError(f"StateTransitionEvaluator: {len(self.centers)} centers given, n_clusters = {n_clusters}")
+        self.n_states = len(self.centers)
+
+    def _assign(self, xyz):
+        return binding.struct_tic_assign(_frames(xyz, self.device), self.mean, self.coeff, self.centers)
+
+    def assign(self, xyz):
+        """(n,) int32 state labels of the structures xyz (n, N, 3) in Angstrom; -1 for a frame with a non-finite
+        projection."""
+        return self._assign(xyz).cpu().numpy()
+
+    def eval(self, xyz, traj_lengths=None, lagtimes=(1,), plot_assignments=False, plot_transitions=False):
+        if plot_assignments or plot_transitions:
+            raise NotImplementedError("plotting (evaluate_fastfolders.ipynb, cells 23-24) is outside the hot path")
+        n = len(xyz)
+        lengths = _check_lengths(self.traj_lengths if traj_lengths is None else traj_lengths, n)
+        lagtimes = [int(v) for v in lagtimes]
+        labels = self._assign(xyz)
+        counts = binding.transition_counts(labels, lengths, lagtimes, self.n_states).cpu().numpy()
+        lab = labels.cpu().numpy()
+        pop = np.bincount(lab[lab >= 0], minlength=self.n_states).astype(np.float64)
+        T = transition_matrix(counts)
+        return {"assignments": lab, "populations": pop / max(pop.sum(), 1.0), "count_matrices": counts,
+                "transition_matrices": T, "lagtimes": lagtimes,
+                "timescales": [msm_timescales(T[i], lag) for i, lag in enumerate(lagtimes)]}
