@@ -1,7 +1,7 @@
 #!/bin/bash
-# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Five translation units compiled in
-# parallel: the <= 64-row kernel, the <= 16-row kernel once per sampler mode (score / Langevin / DDPM), and the host half
-# (ABI, dispatch, PWD kernels).
+# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Six translation units compiled in
+# parallel: the <= 64-row kernel, the <= 16-row kernel once per sampler mode (score / Langevin / DDPM), the host half
+# (model, dispatch, sampler ABI) and the sample-analysis half (PWD / structure / TICA / state kernels and their ABI).
 #   DFF_EXTRA_FLAGS="-DDFF_FAST_BUILD"   development build: headline variants only (fast to compile)
 set -e
 cd "$(dirname "$(readlink -f "$0")")"
@@ -19,9 +19,19 @@ BUILD_FLAGS="${DFF_EXTRA_FLAGS}${DFF_SMALL_SCHED+ sched:${DFF_SMALL_SCHED}}${DFF
 SRC_SHA=$( (cat $(ls $SRC/* | LC_ALL=C sort) include/dff.h; printf '%s' "$BUILD_FLAGS") | sha256sum | cut -c1-16)
 printf '#define DFF_BUILD_FLAGS "%s"\n' "$(printf '%s' "$BUILD_FLAGS" | sed 's/[\\"]/\\&/g')" > $OBJ/dff_build_info.h.tmp
 cmp -s $OBJ/dff_build_info.h.tmp $OBJ/dff_build_info.h || mv $OBJ/dff_build_info.h.tmp $OBJ/dff_build_info.h
+# a unit is stale when a file it was compiled from (the compiler's own list, $OBJ/<unit>.d; system headers left out) is newer
+# than its object or gone, or when the list is missing
+stale() {
+    [ -f "$OBJ/$1.o" ] && [ -f "$OBJ/$1.d" ] || return 0
+    for f in $(sed -e 's/^[^:]*://' -e 's/\\$//' "$OBJ/$1.d"); do
+        case $f in /*) continue;; esac
+        [ -e "$f" ] && [ ! "$f" -nt "$OBJ/$1.o" ] || return 0
+    done
+    return 1
+}
 pids=()
-for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host; do
-    # rebuild a unit only when one of the sources is newer than its object (or the flags changed)
+for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host dff_analysis; do
+    # rebuild a unit only when one of its own sources is newer than its object (or the flags changed)
     stamp="$OBJ/$tu.flags"
     src=$tu; extra=""
     # the <= 16-row kernels are scheduled for ILP with the AMDGPU register-pressure trackers (measured on the headline kernel:
@@ -32,14 +42,13 @@ for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host; do
     # trp-cage -0.65 %, BBA / protein G +-0.2 % (profiles/r06/qkv_all_heads/compiler_flags.txt); it LOSES 1.6 % on the <= 16-row kernel
     case $tu in dff_kernels) extra="${DFF_KERNELS_SCHED--mllvm -disable-machine-licm}";; esac
     case $tu in dff_small_m*) src=dff_small; extra="-DDFF_SMALL_MODE=${tu#dff_small_m} ${DFF_SMALL_SCHED--mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-use-amdgpu-trackers}";; esac
-    if [ ! -f "$OBJ/$tu.o" ] || [ "$(cat $stamp 2>/dev/null)" != "$FLAGS $extra" ] || \
-       [ -n "$(find $SRC include -newer $OBJ/$tu.o \( -name '*.hip' -o -name '*.h' \) | head -1)" ]; then
-        ( hipcc $FLAGS $extra -c $SRC/$src.hip -o $OBJ/$tu.o.tmp && mv $OBJ/$tu.o.tmp $OBJ/$tu.o && echo "$FLAGS $extra" > $stamp ) &
+    if [ "$(cat $stamp 2>/dev/null)" != "$FLAGS $extra" ] || stale $tu; then
+        ( hipcc $FLAGS $extra -MD -MF $OBJ/$tu.d -c $SRC/$src.hip -o $OBJ/$tu.o.tmp && mv $OBJ/$tu.o.tmp $OBJ/$tu.o && echo "$FLAGS $extra" > $stamp ) &
         pids+=($!)
     fi
 done
 rc=0
 for p in "${pids[@]}"; do wait $p || rc=1; done
 [ $rc = 0 ] || { echo "compile failed"; exit 1; }
-hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/dff_kernels.o $OBJ/dff_small_m0.o $OBJ/dff_small_m1.o $OBJ/dff_small_m2.o $OBJ/dff_host.o -o $OUT
+hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/dff_kernels.o $OBJ/dff_small_m0.o $OBJ/dff_small_m1.o $OBJ/dff_small_m2.o $OBJ/dff_host.o $OBJ/dff_analysis.o -o $OUT
 echo "built $OUT"

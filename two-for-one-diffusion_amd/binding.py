@@ -321,7 +321,24 @@ def _coords(x):
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
             and x.dim() == 3 and x.shape[-1] == 3):
         raise ValueError("structures must be a contiguous float32 CUDA tensor of shape (n, n_beads, 3)")
-    return x
+    return x, int(x.shape[0]), int(x.shape[1])
+
+
+def _stream(x):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def _lengths(lengths):
+    return np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+
+
+def _workspace_bytes(name, *args):
+    lib = load_library()
+    b = int(getattr(lib, name)(*args))
+    if b < 0:
+        _check(lib, 1, name)
+    return b
 
 
 def pwd_num_pairs(n_beads: int, offset: int) -> int:
@@ -332,11 +349,9 @@ def pwd_max(x, offset: int):
     """Per-pair maximum distance over the structures x (n, N, 3) -> float32 CUDA tensor (n_pairs,)."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     out = torch.empty(pwd_num_pairs(N, offset), dtype=torch.float32, device=x.device)
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _check(lib, lib.dff_pwd_max(x.device.index, _ptr(x), n, N, int(offset), _ptr(out), stream), "dff_pwd_max")
+    _check(lib, lib.dff_pwd_max(x.device.index, _ptr(x), n, N, int(offset), _ptr(out), _stream(x)), "dff_pwd_max")
     return out
 
 
@@ -345,8 +360,7 @@ def pwd_hist(x, offset: int, nbins, hmax):
     pairwise distances of x (n, N, 3) -> int32 CUDA tensor (n_pairs, max(nbins)) of counts."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     npairs = pwd_num_pairs(N, offset)
     nb = torch.as_tensor(nbins, dtype=torch.int32).reshape(-1)
     hm = torch.as_tensor(hmax, dtype=torch.float32).reshape(-1)
@@ -357,25 +371,18 @@ def pwd_hist(x, offset: int, nbins, hmax):
     max_bins = int(nb.max())
     nb_d, hm_d = nb.to(x.device), hm.to(x.device)
     out = torch.empty((npairs, max_bins), dtype=torch.int32, device=x.device)
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     _check(lib, lib.dff_pwd_hist(x.device.index, _ptr(x), n, N, int(offset), _ptr(nb_d), _ptr(hm_d), max_bins,
-                                 max_bins, _ptr(out), stream), "dff_pwd_hist")
+                                 max_bins, _ptr(out), _stream(x)), "dff_pwd_hist")
     return out
 
 
 # ---- structure metrics (dff_struct_*): stateless entry points, no model handle ----
-def _stream(x):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-
-
 def struct_rmsd(x, ref):
     """Optimal-rotation RMSD (Angstrom) of every frame of x (n, N, 3) to ref (N, 3) -> float32 CUDA tensor (n,);
     NaN for frames with a non-finite coordinate."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     r = torch.as_tensor(ref, dtype=torch.float32).reshape(N, 3).to(x.device).contiguous()
     out = torch.empty(n, dtype=torch.float32, device=x.device)
     _check(lib, lib.dff_struct_rmsd(x.device.index, _ptr(x), n, N, _ptr(r), _ptr(out), _stream(x)), "dff_struct_rmsd")
@@ -386,8 +393,7 @@ def struct_dihedrals(x):
     """Dihedrals (radians) of the consecutive bead quadruples of x (n, N, 3) -> float32 CUDA tensor (n, N - 3)."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     out = torch.empty((n, max(N - 3, 0)), dtype=torch.float32, device=x.device)
     _check(lib, lib.dff_struct_dihedrals(x.device.index, _ptr(x), n, N, _ptr(out), _stream(x)), "dff_struct_dihedrals")
     return out
@@ -397,19 +403,24 @@ def struct_tic_num_features(n_beads: int) -> int:
     return int(load_library().dff_struct_tic_num_features(int(n_beads)))
 
 
-def struct_tic(x, mean, coeff):
-    """TIC projection (feat - mean) @ coeff of the N - 3 dihedrals + N (N - 1) / 2 pair distances of every frame of
-    x (n, N, 3); mean (F,), coeff (F, k) -> float64 CUDA tensor (n, k)."""
+def _tic_model(x, N, mean, coeff):
+    """mean (F,) and coeff (F, k) of a TIC model for N-bead frames x, as contiguous float64 tensors on x's device, and k."""
     import torch
-    lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
     F = struct_tic_num_features(N)
     m = torch.as_tensor(mean, dtype=torch.float64).to(x.device).contiguous()
     A = torch.as_tensor(coeff, dtype=torch.float64).to(x.device).contiguous()
     if m.shape != (F,) or A.dim() != 2 or A.shape[0] != F:
         raise ValueError(f"mean must be ({F},) and coeff ({F}, k) for {N} beads")
-    k = int(A.shape[1])
+    return m, A, int(A.shape[1])
+
+
+def struct_tic(x, mean, coeff):
+    """TIC projection (feat - mean) @ coeff of the N - 3 dihedrals + N (N - 1) / 2 pair distances of every frame of
+    x (n, N, 3); mean (F,), coeff (F, k) -> float64 CUDA tensor (n, k)."""
+    import torch
+    lib = load_library()
+    x, n, N = _coords(x)
+    m, A, k = _tic_model(x, N, mean, coeff)
     out = torch.empty((n, k), dtype=torch.float64, device=x.device)
     _check(lib, lib.dff_struct_tic(x.device.index, _ptr(x), n, N, _ptr(m), _ptr(A), k, _ptr(out), _stream(x)),
            "dff_struct_tic")
@@ -422,8 +433,7 @@ def struct_contacts(x, cutoff: float, folded=None, offset: int = 3):
     j >= i + offset whose contact differs from it (None otherwise)."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     f = None
     if folded is not None:
         f = torch.as_tensor(folded).reshape(N, N).to(device=x.device, dtype=torch.uint8).contiguous()
@@ -439,8 +449,7 @@ def struct_tic_features(x):
     -> float32 CUDA tensor (n, F): get_tic_features, the values struct_tic projects."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     out = torch.empty((n, struct_tic_num_features(N)), dtype=torch.float32, device=x.device)
     _check(lib, lib.dff_struct_tic_features(x.device.index, _ptr(x), n, N, _ptr(out), _stream(x)),
            "dff_struct_tic_features")
@@ -449,11 +458,7 @@ def struct_tic_features(x):
 
 # ---- TICA moments (dff_tica_*) ----
 def tica_workspace_bytes(n_beads: int, n_frames_max: int, lagtime: int) -> int:
-    lib = load_library()
-    b = int(lib.dff_tica_workspace_bytes(int(n_beads), int(n_frames_max), int(lagtime)))
-    if b < 0:
-        _check(lib, 1, "dff_tica_workspace_bytes")
-    return b
+    return _workspace_bytes("dff_tica_workspace_bytes", int(n_beads), int(n_frames_max), int(lagtime))
 
 
 def tica_moments(x, lengths, lagtime: int, shift, sx, sy, m0, mt, workspace=None):
@@ -462,15 +467,14 @@ def tica_moments(x, lengths, lagtime: int, shift, sx, sy, m0, mt, workspace=None
     (float64 (F,) CUDA).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
+    x, n, N = _coords(x)
     F = struct_tic_num_features(N)
     for name, t, shape in (("shift", shift, (F,)), ("sx", sx, (F,)), ("sy", sy, (F,)), ("m0", m0, (F, F)),
                            ("mt", mt, (F, F))):
         if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == x.device
                 and t.is_contiguous() and tuple(t.shape) == shape):
             raise ValueError(f"{name} must be a contiguous float64 tensor {shape} on {x.device}")
-    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    ln = _lengths(lengths)
     if workspace is None:
         workspace = torch.empty(max(tica_workspace_bytes(N, n, lagtime), 1), dtype=torch.uint8, device=x.device)
     _check(lib, lib.dff_tica_moments(x.device.index, _ptr(x), n, N, ln.ctypes.data_as(C.c_void_p), int(ln.size),
@@ -484,7 +488,7 @@ def tica_debug_plan(n_beads: int, lengths, lagtime: int, chunk_pairs: int = 0) -
     """The chunk plan of dff_tica_moments (host only): int64 (runs, 6) of (chunk, f0, rows, chunk pairs, run start - f0,
     run pairs)."""
     lib = load_library()
-    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    ln = _lengths(lengths)
     cap = 1024
     while True:
         out = np.zeros((cap, 6), np.int64)
@@ -512,14 +516,8 @@ def struct_tic_assign(x, mean, coeff, centers, return_proj=False, return_dist2=F
     return_dist2 a tuple (labels[, proj float64 (n, k)][, dist2 float64 (n,)])."""
     import torch
     lib = load_library()
-    x = _coords(x)
-    n, N = int(x.shape[0]), int(x.shape[1])
-    F = struct_tic_num_features(N)
-    m = torch.as_tensor(mean, dtype=torch.float64).to(x.device).contiguous()
-    A = torch.as_tensor(coeff, dtype=torch.float64).to(x.device).contiguous()
-    if m.shape != (F,) or A.dim() != 2 or A.shape[0] != F:
-        raise ValueError(f"mean must be ({F},) and coeff ({F}, k) for {N} beads")
-    k = int(A.shape[1])
+    x, n, N = _coords(x)
+    m, A, k = _tic_model(x, N, mean, coeff)
     c = _centers(centers, k, x.device)
     labels = torch.empty(n, dtype=torch.int32, device=x.device)
     proj = torch.empty((n, k), dtype=torch.float64, device=x.device) if return_proj else None
@@ -531,11 +529,7 @@ def struct_tic_assign(x, mean, coeff, centers, return_proj=False, return_dist2=F
 
 
 def kmeans_workspace_bytes(n: int, d: int, K: int) -> int:
-    lib = load_library()
-    b = int(lib.dff_kmeans_workspace_bytes(int(n), int(d), int(K)))
-    if b < 0:
-        _check(lib, 1, "dff_kmeans_workspace_bytes")
-    return b
+    return _workspace_bytes("dff_kmeans_workspace_bytes", int(n), int(d), int(K))
 
 
 def kmeans_step(points, centers, accumulate=True, workspace=None):
@@ -578,7 +572,7 @@ def transition_counts(labels, lengths, lagtimes, n_states: int):
     if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
             and labels.is_contiguous() and labels.dim() == 1):
         raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
-    ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    ln = _lengths(lengths)
     lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
     K = int(n_states)
     out = torch.empty((max(int(lg.size), 1), max(K, 1), max(K, 1)), dtype=torch.int64, device=labels.device)

@@ -13,8 +13,8 @@
 // non-finite coordinate gets label -1 and d2 = NaN and takes part in no sum.
 //
 // dff_struct_tic_assign_kernel   the layout of dff_struct_tic_kernel (one wave per workgroup, one lane per frame, tiles
-//     through LDS) and its projection loop (the same statements, the same bits); the k projections stay in registers, the
-//     K centres are wave-uniform loads.
+//     through LDS) and its projection (the same function, struct_tic_project: the same bits); the k projections stay in
+//     registers, the K centres are wave-uniform loads.
 // dff_kmeans_step_kernel         256 threads, one point per lane, grid-stride.  Per 64 points and per cluster present among
 //     them (ballot), the members' coordinates are summed by a butterfly over the wave -- a fixed tree, every lane ends
 //     with the same bits -- and lane 0 adds them to its wave's LDS accumulators in the order the wave meets its points.
@@ -75,24 +75,8 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_assign_kernel(
     float* tile = smem;
     struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
         if (live) {
-            // the loop of dff_struct_tic_kernel, statement for statement: the projections carry its bits
             double acc[DFF_TIC_MAXK];
-#pragma unroll
-            for (int c = 0; c < DFF_TIC_MAXK; ++c) acc[c] = 0.0;
-            int f = 0;
-            for (; f < N - 3; ++f) {
-                const double v = (double)struct_dihedral(xs, f) - mean[f];
-#pragma unroll
-                for (int c = 0; c < DFF_TIC_MAXK; ++c)
-                    if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
-            }
-            for (int i = 0; i < N - 1; ++i)
-                for (int j = i + 1; j < N; ++j, ++f) {
-                    const double v = (double)pwd_dist2(xs, 3 * i, 3 * j) - mean[f];
-#pragma unroll
-                    for (int c = 0; c < DFF_TIC_MAXK; ++c)
-                        if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
-                }
+            struct_tic_project(xs, N, mean, A, k, acc);
             double best;
             labels[s0 + lane] = state_nearest<DFF_TIC_MAXK>(acc, k, centers, K, best);
             if (dist2) dist2[s0 + lane] = best;
@@ -107,7 +91,8 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_assign_kernel(
 }
 
 // sum over the wave by a butterfly: the same tree, and the same bits, in every lane
-__device__ __forceinline__ double wave_sum_f64(double v) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
@@ -150,12 +135,12 @@ __global__ __launch_bounds__(DFF_KM_THREADS) void dff_kmeans_step_kernel(const d
 #pragma unroll
                 for (int j = 0; j < DFF_KM_MAXD; ++j)
                     if (j < d) {
-                        const double s = wave_sum_f64(mine ? p[j] : 0.0);
+                        const double s = wave_sum(mine ? p[j] : 0.0);
                         if (lane == 0) wacc[c * d + j] += s;
                     }
                 if (lane == 0) wcnt[c] += (unsigned long long)__popcll(bal);
             }
-            const double s = wave_sum_f64(lab >= 0 ? best : 0.0);
+            const double s = wave_sum(lab >= 0 ? best : 0.0);
             if (lane == 0) wacc[nsum + K] += s;
         }
     }
@@ -183,13 +168,12 @@ __global__ __launch_bounds__(64) void dff_kmeans_reduce_kernel(const double* __r
     if (i >= nsum && i < nsum + K) {
         unsigned long long c = 0ull;
         for (int g = lane; g < nslots; g += 64) c += ((const unsigned long long*)part)[(size_t)g * per + i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+        c = wave_sum(c);
         if (counts && lane == 0) counts[i - nsum] = c;
     } else {
         double s = 0.0;
         for (int g = lane; g < nslots; g += 64) s += part[(size_t)g * per + i];
-        s = wave_sum_f64(s);
+        s = wave_sum(s);
         if (lane == 0) {
             if (i < nsum) { if (sums) sums[i] = s; }
             else if (inertia) inertia[0] = s;
@@ -240,12 +224,7 @@ __global__ __launch_bounds__(DFF_TC_THREADS) void dff_transition_counts_kernel(c
                 if (runs.period > 0) {
                     e = runs.begin + ((t - runs.begin) / runs.period + 1) * runs.period;
                 } else {
-                    int lo = 0, hi = runs.n - 1;                    // the last r with start[r] <= t
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (runs.start[mid] <= t) lo = mid; else hi = mid - 1;
-                    }
-                    e = runs.start[lo + 1];
+                    e = runs.start[last_le(runs.start, runs.n, t) + 1];
                 }
 #pragma unroll
                 for (int l = 0; l < DFF_TC_MAXLAGS; ++l)

@@ -33,7 +33,21 @@
 #define DFF_STRUCT_TILE 64     // frames per tile = lanes per workgroup (one wave)
 #define DFF_TIC_MAXK 8         // TIC components per call
 
-__device__ __forceinline__ int struct_ld(int N) { return (3 * N) | 1; }
+__host__ __device__ __forceinline__ int struct_ld(int N) { return (3 * N) | 1; }
+
+// TIC features of an N-bead frame (N >= 4): the dihedrals and the pair distances
+__host__ __device__ inline int struct_tic_num_features(int N) { return (N - 3) + N * (N - 1) / 2; }
+
+// the last r in 0 .. n - 1 with start[r] <= v (start ascending, start[0] <= v)
+template <class T>
+__device__ __forceinline__ int last_le(const T* start, int n, T v) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (start[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 
 // coalesced load of cnt frames starting at s0 into tile[s * ld + k].  magic = ceil(2^32 / 3N): the frame of
 // flat element e < 64 * 3N is __umulhi(e, magic) exactly (the rounding error e / 2^32 < 1 / 3N).
@@ -75,6 +89,29 @@ __device__ __forceinline__ float struct_dihedral(const float* xs, int i) {
     const float p1 = (b1x * c1x + b1y * c1y + b1z * c1z) * sqrtf(b2x * b2x + b2y * b2y + b2z * b2z);
     const float p2 = c1x * c2x + c1y * c2y + c1z * c2z;
     return atan2f(p1, p2);
+}
+
+// the TIC features of the frame xs in order, fn(f, value): dihedrals 0 .. N - 4, then the distances in
+// triu_indices(N, N, 1) order
+template <class Fn>
+__device__ __forceinline__ void struct_tic_walk(const float* xs, int N, Fn fn) {
+    int f = 0;
+    for (; f < N - 3; ++f) fn(f, struct_dihedral(xs, f));
+    for (int i = 0; i < N - 1; ++i)
+        for (int j = i + 1; j < N; ++j, ++f) fn(f, pwd_dist2(xs, 3 * i, 3 * j));
+}
+
+// acc[c] = sum_f ((double) feat_f - mean_f) * A[f, c], c < k: one fp64 FMA per feature and component, in feature order
+__device__ __forceinline__ void struct_tic_project(const float* xs, int N, const double* __restrict__ mean,
+                                                   const double* __restrict__ A, int k, double (&acc)[DFF_TIC_MAXK]) {
+#pragma unroll
+    for (int c = 0; c < DFF_TIC_MAXK; ++c) acc[c] = 0.0;
+    struct_tic_walk(xs, N, [&](int f, float feat) {
+        const double v = (double)feat - mean[f];
+#pragma unroll
+        for (int c = 0; c < DFF_TIC_MAXK; ++c)
+            if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
+    });
 }
 
 // grid-stride loop over tiles: body(s0, cnt, lane, live, xs) once per tile, xs = this lane's frame in LDS
@@ -211,22 +248,7 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_kernel(const f
     struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
         if (live) {
             double acc[DFF_TIC_MAXK];
-#pragma unroll
-            for (int c = 0; c < DFF_TIC_MAXK; ++c) acc[c] = 0.0;
-            int f = 0;
-            for (; f < N - 3; ++f) {
-                const double v = (double)struct_dihedral(xs, f) - mean[f];
-#pragma unroll
-                for (int c = 0; c < DFF_TIC_MAXK; ++c)
-                    if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
-            }
-            for (int i = 0; i < N - 1; ++i)
-                for (int j = i + 1; j < N; ++j, ++f) {
-                    const double v = (double)pwd_dist2(xs, 3 * i, 3 * j) - mean[f];
-#pragma unroll
-                    for (int c = 0; c < DFF_TIC_MAXK; ++c)
-                        if (c < k) acc[c] = fma(v, A[(size_t)f * k + c], acc[c]);
-                }
+            struct_tic_project(xs, N, mean, A, k, acc);
             double* o = out + (s0 + lane) * k;
 #pragma unroll
             for (int c = 0; c < DFF_TIC_MAXK; ++c)

@@ -18,7 +18,9 @@
 //
 // Pipeline, per chunk of <= C pair starts (C from the feature count only):
 //   1. dff_tica_features_kernel writes the fp32 features of the chunk's frames, tau frames of overlap included, into the
-//      workspace (row-major, F per row).
+//      workspace (row-major, F per row).  Its feature loop is deliberately a second one next to struct_tic_walk
+//      (dff_struct.hip): it stops every DFF_TICA_FCH features, in the middle of the distance block, to flush its LDS
+//      stage, and carries the pair (i, j) across the stops.  Both call struct_dihedral / pwd_dist2: the same bits.
 //   2. dff_tica_moments_kernel: one workgroup (4 waves) per (64 x 64 upper-triangular output tile, slice of pairs).  Per
 //      stage of 32 pairs it converts rows t and t + tau of the tile's two 64-feature blocks to fp64 u, v in LDS, then
 //      each wave runs v_mfma_f64_16x16x4_f64 on its 32 x 32 quarter (2 x 2 blocks, P and Q).  It writes its partial tile
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_tica_features_kernel(cons
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* tile = smem;
     float* stage = smem + DFF_STRUCT_TILE * struct_ld(N);
-    const int F = (N - 3) + N * (N - 1) / 2;
+    const int F = struct_tic_num_features(N);
     constexpr int ls = DFF_TICA_FCH + 1;
     struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
         int i = 0, j = 1;                                   // next pair of the distance features (wave-uniform)
@@ -132,11 +134,7 @@ __global__ __launch_bounds__(DFF_TICA_THREADS) void dff_tica_moments_kernel(cons
             const int p = 4 * m + wave, q = q0 + p;
             double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
             if (q < q_end) {
-                int lo = 0, hi = runs.n - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (runs.cum[mid] <= q) lo = mid; else hi = mid - 1;
-                }
+                const int lo = last_le(runs.cum, runs.n, q);
                 const float* f0 = feat + (long long)(runs.row[lo] + (q - runs.cum[lo])) * F;
                 if (fI) { a = (double)f0[I0 + lane] - shI; b = (double)f0[ldlag + I0 + lane] - shI; }
                 if (!diag && fJ) { c = (double)f0[J0 + lane] - shJ; d = (double)f0[ldlag + J0 + lane] - shJ; }
