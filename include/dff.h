@@ -110,7 +110,14 @@ typedef struct {
  * written to frames_dev (n_steps/save_interval, n_traj, N, 3) and 0.5 sum m v^2 to ke_dev
  * (n_steps/save_interval, n_traj) -- the layout of Langevin.simulated_coords /
  * .kinetic_energies before _swap_and_export (langevin_cgnet.py:410-425,502-542).  Either may be
- * NULL.  n_steps must be a multiple of save_interval when frames_dev != NULL. */
+ * NULL.  n_steps must be a multiple of save_interval when frames_dev != NULL.
+ * In-kernel noise: the draw for (trajectory, step, bead, component) is the Philox4x32-10 block of key = (seed low word, seed
+ * high word), counter = (index low word, (index >> 32) ^ (bead << 8), step low word, step high word), index = traj_offset + i,
+ * step = step_offset + s, through a Box-Muller: components 0 / 1 = r(w0) cos / sin(2 pi u(w1)), component 2 = r(w2) cos(2 pi u(w3)),
+ * u(w) = (float(w) + 0.5) 2^-32, r(w) = sqrt(-2 ln u(w)) (oracle/noise.py is the host reference; tests/test_noise_stream.py
+ * holds every kernel variant to it).  It does not depend on how a batch is sharded, chunked, grouped or on the kernel variant.
+ * LIMIT: the bead index shares counter word 1 with bits 32.. of the trajectory index, so with noise_dev == NULL
+ * traj_offset + n_traj must not exceed 2^40 (DFF_EINVAL otherwise: beyond it two trajectories would share draws). */
 int dff_langevin_run(dff_model* m, const dff_langevin_params* p, int n_traj, float* x_dev,
                      float* v_dev, const float* noise_dev, uint64_t seed, uint64_t traj_offset,
                      uint64_t step_offset, int n_steps, int save_interval, float* frames_dev,
@@ -121,7 +128,9 @@ int dff_langevin_run(dff_model* m, const dff_langevin_params* p, int n_traj, flo
  * centring.  x_dev (batch,N,3) in/out in normalised units; if init_prior != 0 x is first set to
  * center_zero(randn) in-kernel (ddpm.py:242).  noise_dev: (t_start-t_end+1,batch,N,3) draws for
  * randn_like (ddpm.py:228), or NULL for in-kernel Philox keyed by (seed; sample
- * sample_offset+i, t).  *clamp_flag_dev (optional) is set to 1 if any coordinate was clamped
+ * sample_offset+i, t) as dff_langevin_run keys its draws, with step = t for the reverse step of level t and step = 0xFFFFFFFF
+ * for the prior; likewise sample_offset + batch must not exceed 2^40 when noise_dev == NULL (DFF_EINVAL otherwise).
+ * *clamp_flag_dev (optional) is set to 1 if any coordinate was clamped
  * (the reference's "Large molecule encountered" warning, ddpm.py:248-250). */
 int dff_ddpm_run(dff_model* m, int batch, float* x_dev, const float* noise_dev, uint64_t seed,
                  uint64_t sample_offset, int t_start, int t_end, int init_prior,

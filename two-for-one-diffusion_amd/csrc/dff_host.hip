@@ -1081,12 +1081,22 @@ extern "C" int dff_score(dff_model* m, const float* x, const float* tnorm, int b
     return launch(m, a, (hipStream_t)stream);
 }
 
+// In-kernel noise (philox_normal, dff_device.h): counter word 1 is (item >> 32) ^ (bead << 8), so the item indices offset ..
+// offset + count - 1 of a call must stay below 2^40, or (item ^ (d << 40), bead) would draw what (item, bead ^ d) draws.
+static bool noise_items_ok(uint64_t offset, int count) {
+    const uint64_t lim = 1ull << 40;
+    return offset <= lim && (uint64_t)count <= lim - offset;
+}
+
 extern "C" int dff_langevin_run(dff_model* m, const dff_langevin_params* p, int n_traj, float* x, float* v,
                                 const float* noise, uint64_t seed, uint64_t traj_offset, uint64_t step_offset,
                                 int n_steps, int save_interval, float* frames, float* ke, void* stream) {
     if (!m || !p || !x) return fail(DFF_EINVAL, "null argument");
     if (!p->overdamped && !v) return fail(DFF_EINVAL, "v_dev required unless overdamped");
     if (n_traj <= 0 || n_steps < 0) return fail(DFF_EINVAL, "bad sizes");
+    if (!noise && !noise_items_ok(traj_offset, n_traj))
+        return fail(DFF_EINVAL, "traj_offset + n_traj = %llu + %d exceeds 2^40: the in-kernel noise is keyed by 40 bits of the trajectory index",
+                    (unsigned long long)traj_offset, n_traj);
     if (n_steps == 0) return DFF_OK;
     if (save_interval <= 0) save_interval = n_steps;
     // "The save_interval must be a factor of the simulation length" (langevin_cgnet.py:305-309)
@@ -1117,6 +1127,9 @@ extern "C" int dff_ddpm_run(dff_model* m, int batch, float* x, const float* nois
     if (!m || !x) return fail(DFF_EINVAL, "null argument");
     if (batch <= 0) return batch == 0 ? DFF_OK : fail(DFF_EINVAL, "negative batch");
     if (t_start >= m->cfg.timesteps || t_end < 0 || t_end > t_start) return fail(DFF_EINVAL, "bad timestep range");
+    if (!noise && !noise_items_ok(sample_offset, batch))
+        return fail(DFF_EINVAL, "sample_offset + batch = %llu + %d exceeds 2^40: the in-kernel noise is keyed by 40 bits of the sample index",
+                    (unsigned long long)sample_offset, batch);
     DffRunArgs a;
     memset(&a, 0, sizeof a);
     a.mode = DFF_MODE_DDPM; a.B = batch; a.n_steps = t_start - t_end + 1;
