@@ -70,7 +70,7 @@ def fold_weights(p: Dict[str, np.ndarray], n_layers: int) -> dict:
 
 
 def fold_kv(fw: dict) -> dict:
-    """H == head dimension only: the same network with k = v = LayerNorm output (what dff_host.hip does when
+    """H == head dimension only: the same network with k = v = LayerNorm output (what dff_prep.hip does when
     hidden == 64): q'_h = W_k,h^T (W_q,h n + b_q,h) (the j-constant part of the logits drops out of the softmax),
     W_o,h' = W_o,h W_v,h, b_o' += W_o b_v.  W_u / W_oc stay those of the ORIGINAL q and W_o.  forward() / backward()
     on the result give the same energies and forces; the stashed q, k, v are q', n, n."""

@@ -21,7 +21,7 @@ if [ "$cmd" = build ]; then
     pf=""; case "$flags" in *DFF_PROF=1*) pf="-DDFF_PROF=1";; esac
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result $pf -DDFF_SRC_SHA=exp-$name -include $d/dff_build_info.h -c $SRC/dff_host.hip -o $d/dff_host.o
     host=$d/dff_host.o
-    hipcc --offload-arch=gfx950 -shared -fPIC build/obj/dff_kernels.o $objs $host build/obj/dff_analysis.o -o $d/libdff_amd.so
+    hipcc --offload-arch=gfx950 -shared -fPIC build/obj/dff_kernels.o $objs $host build/obj/dff_prep.o build/obj/dff_analysis.o -o $d/libdff_amd.so
     echo "$flags" > $d/flags
     echo "built $d ($flags)"
 elif [ "$cmd" = buildk ]; then   # the <= 64-row kernel TU instead (e.g. flags: -DDFF_FAST_BUILD -DDFF_ONLY="VAR_SPW(128,3,1)")
@@ -32,7 +32,7 @@ elif [ "$cmd" = buildk ]; then   # the <= 64-row kernel TU instead (e.g. flags: 
     case "$flags" in *DFF_PROF=1*)   # the host half refuses dff_debug_profile unless it was built with the stage ticks too
         hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result -DDFF_PROF=1 -c $SRC/dff_host.hip -o $d/dff_host.o; host=$d/dff_host.o;; esac
     wait
-    hipcc --offload-arch=gfx950 -shared -fPIC $d/dff_kernels.o build/obj/dff_small_m0.o build/obj/dff_small_m1.o build/obj/dff_small_m2.o $host build/obj/dff_analysis.o -o $d/libdff_amd.so
+    hipcc --offload-arch=gfx950 -shared -fPIC $d/dff_kernels.o build/obj/dff_small_m0.o build/obj/dff_small_m1.o build/obj/dff_small_m2.o $host build/obj/dff_prep.o build/obj/dff_analysis.o -o $d/libdff_amd.so
     echo "$flags" > $d/flags
     echo "built $d ($flags)"
 elif [ "$cmd" = buildall ]; then   # EVERY translation unit with the flags (e.g. prof -DDFF_PROF=1: the stage profiles of tools_evidence.sh)
@@ -43,9 +43,10 @@ elif [ "$cmd" = buildall ]; then   # EVERY translation unit with the flags (e.g.
     $C ${DFF_KERNELS_SCHED--mllvm -disable-machine-licm} -c $SRC/dff_kernels.hip -o $d/dff_kernels.o &
     for k in 0 1 2; do $C -DDFF_SMALL_MODE=$k ${DFF_SMALL_SCHED--mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-use-amdgpu-trackers} -c $SRC/dff_small.hip -o $d/dff_small_m$k.o & done
     $C -DDFF_SRC_SHA=exp-$name -include $d/dff_build_info.h -c $SRC/dff_host.hip -o $d/dff_host.o &
+    $C -c $SRC/dff_prep.hip -o $d/dff_prep.o &
     $C -c $SRC/dff_analysis.hip -o $d/dff_analysis.o &
     wait
-    hipcc --offload-arch=gfx950 -shared -fPIC $d/dff_kernels.o $d/dff_small_m0.o $d/dff_small_m1.o $d/dff_small_m2.o $d/dff_host.o $d/dff_analysis.o -o $d/libdff_amd.so
+    hipcc --offload-arch=gfx950 -shared -fPIC $d/dff_kernels.o $d/dff_small_m0.o $d/dff_small_m1.o $d/dff_small_m2.o $d/dff_host.o $d/dff_prep.o $d/dff_analysis.o -o $d/libdff_amd.so
     echo "$flags" > $d/flags
     echo "built $d ($flags)"
 elif [ "$cmd" = run ]; then

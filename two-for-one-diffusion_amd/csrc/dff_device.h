@@ -305,7 +305,7 @@ DEVI float philox_normal(uint64_t seed, uint64_t item, uint64_t step, uint32_t b
 
 // ------------------------------------------------------------------------------------------
 // SPW variants (DFF_SPLIT_BF16=1 selects them; the name is historical): the weight GEMMs on the fp16 matrix pipe at fp32
-// accuracy.  The weights are split on the host (dff_host.hip pack_b_split_f16 / pack_units_f16), the activations by the row
+// accuracy.  The weights are split on the host (dff_prep.hip pack_b_split_f16 / pack_units_f16), the activations by the row
 // stages or by the consuming wave; three v_mfma_f32_16x16x32_f16 (16 cycles each, and they leave the vector port free:
 // tools_ubench/overlap3.hip) replace eight v_mfma_f32_16x16x4_f32 (32 cycles each).
 // ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// dff_host.hip -- host half of libdff_amd.so: weight folding + MFMA packing, schedule tables,
-// scratch management, kernel dispatch and the model's part of the extern "C" ABI declared in include/dff.h
+// dff_host.hip -- host half of libdff_amd.so: the model handle (upload of the images dff_prep.hip prepares), scratch
+// management, kernel dispatch and the model's part of the extern "C" ABI declared in include/dff.h
 // (the stateless sample-analysis entry points are dff_analysis.hip).
 #include "../../include/dff.h"
 #include "dff_internal.h"
@@ -8,7 +8,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -16,6 +15,7 @@
 // lookups, dff_device.h); the sample-analysis entry points and their kernels are a third (dff_analysis.hip)
 #include "dff_device.h"
 #include "dff_host_common.h"
+#include "dff_prep.h"
 
 static thread_local std::string g_err;
 int fail(int code, const char* fmt, ...) {
@@ -26,109 +26,6 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code;
-}
-
-// ------------------------------------------------------------------------------------------
-// packing for the v_mfma_f32_16x16x4_f32 B operand (layout: dff_internal.h)
-// ------------------------------------------------------------------------------------------
-// xper > 0: k-blocks with kb % xper == 4 are head EXTENSION blocks, of which only rows 0..3 are ever non-zero
-// (u | s, xrel | D, du | ds): they are packed with row (lane >> 4) in k-step 0 and zeros in k-steps 1..3, and the
-// kernels issue one MFMA for them instead of four (A operand: column lane >> 4 of the block).
-static std::vector<float> pack_b(int K, int Nout, const std::function<double(int, int)>& w, int xper = 0) {
-    const int KB = (K + 15) / 16, NT = (Nout + 15) / 16;
-    std::vector<float> out((size_t)KB * NT * 256, 0.f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb) {
-            const bool ext = xper > 0 && kb % xper == 4;
-            for (int lane = 0; lane < 64; ++lane)
-                for (int s = 0; s < (ext ? 1 : 4); ++s) {
-                    const int k = 16 * kb + (ext ? lane >> 4 : 4 * (lane >> 4) + s), n = 16 * nt + (lane & 15);
-                    if (k < K && n < Nout) out[(((size_t)nt * KB + kb) * 64 + lane) * 4 + s] = (float)w(k, n);
-                }
-        }
-    return out;
-}
-
-static uint16_t f32_to_f16_rn(float f);
-static float f16_to_f32(uint16_t h);
-// B operand of v_mfma_f32_16x16x32_f16 for the split GEMMs of the <= 64-row kernel (dff_kernels.hip gemm_wide_split_st and
-// friends), two fp16 pieces per weight: per (tile, 32-row k-block, piece h | l', lane) eight fp16 =
-// W[32 kb + 8 (lane >> 4) + j][16 nt + (lane & 15)], j = 0..7, two per dword (even j in the low half);
-// h = RN_f16(w), l' = RN_f16((w - h) 2048).
-static std::vector<uint32_t> pack_b_split_f16(int K, int Nout, const std::function<double(int, int)>& w) {
-    const int KB = K / 32, NT = (Nout + 15) / 16;
-    std::vector<uint32_t> out((size_t)NT * KB * 2 * 64 * 4, 0u);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 32 * kb + 8 * (lane >> 4) + j, n = 16 * nt + (lane & 15);
-                    const float v = n < Nout ? (float)w(k, n) : 0.f;
-                    const uint16_t h = f32_to_f16_rn(v);
-                    const uint16_t l = f32_to_f16_rn((v - f16_to_f32(h)) * 2048.0f);
-                    out[((((size_t)nt * KB + kb) * 2 + 0) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)h << (16 * (j & 1));
-                    out[((((size_t)nt * KB + kb) * 2 + 1) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)l << (16 * (j & 1));
-                }
-    return out;
-}
-// fp32 -> fp16 (binary16), round to nearest even, subnormals kept: what v_cvt_pk_f16_f32 does on the device (dff_device.h split2h)
-static uint16_t f32_to_f16_rn(float f) {
-    uint32_t u; memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-    if (a >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | ((a > 0x7f800000u) ? 0x200u : 0u));   // inf / nan
-    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);             // >= 65520 rounds to infinity (the range guard keeps models away)
-    const int e = (int)(a >> 23) - 127;
-    if (e < -25) return (uint16_t)sign;                                   // < 2^-25: zero
-    uint32_t r, rem, half;
-    if (e >= -14) { r = (uint32_t)(e + 15) << 10 | ((a >> 13) & 0x3ffu); rem = a & 0x1fffu; half = 0x1000u; }
-    else {                                                                // subnormal: value = mant 2^(e - 23) = r 2^-24
-        const uint32_t mant = (a & 0x7fffffu) | 0x800000u; const int sh = -e - 1;   // 14 .. 24
-        r = mant >> sh; rem = mant & ((1u << sh) - 1u); half = 1u << (sh - 1);
-    }
-    if (rem > half || (rem == half && (r & 1u))) ++r;                     // (a carry out of the mantissa lands in the exponent: right)
-    return (uint16_t)(sign | r);
-}
-static float f16_to_f32(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, mnt = h & 0x3ffu;
-    float f;
-    if (e == 0) { f = (float)mnt * 5.9604644775390625e-08f; uint32_t u; memcpy(&u, &f, 4); u |= sign; memcpy(&f, &u, 4); return f; }
-    const uint32_t u = sign | ((e == 31 ? 255u : e + 112u) << 23) | (mnt << 13);
-    memcpy(&f, &u, 4);
-    return f;
-}
-// Split images for the <= 16-row kernel's SPW variants (dff_small.hip): a sequence of UNITS, each one 16-column output tile nt x
-// 32 A-columns starting at c0, stored [piece h | l'][lane][8 fp16], h = RN_f16(w), l' = RN_f16((w - h) 2048): w = h + l' / 2048
-// to 2^-22 relative (3e-11 absolute).  Element j of lane (n = lane & 15, kg = lane >> 4) is W(c0 + 16 (j >> 2) + 4 kg + (j & 3),
-// 16 nt + n): the k order in which that kernel's A fragments hold a 32-column block (two ds_read_b128, at columns 4 kg and
-// 16 + 4 kg).
-static std::vector<uint32_t> pack_units_f16(const std::vector<std::pair<int, int>>& units, int Nout,
-                                            const std::function<double(int, int)>& w) {
-    std::vector<uint32_t> out(units.size() * 2 * 64 * 4, 0u);
-    for (size_t u = 0; u < units.size(); ++u) {
-        const int nt = units[u].first, c0 = units[u].second;
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-                const int c = c0 + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3), n = 16 * nt + (lane & 15);
-                const float v = n < Nout ? (float)w(c, n) : 0.f;
-                const uint16_t h = f32_to_f16_rn(v);
-                const uint16_t l = f32_to_f16_rn((v - f16_to_f32(h)) * 2048.0f);
-                out[((u * 2 + 0) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)h << (16 * (j & 1));
-                out[((u * 2 + 1) * 64 + lane) * 4 + (j >> 1)] |= (uint32_t)l << (16 * (j & 1));
-            }
-    }
-    return out;
-}
-static std::vector<std::pair<int, int>> units_wide(int K, int Nout) {   // [tile][k-block]
-    std::vector<std::pair<int, int>> u;
-    for (int nt = 0; nt < (Nout + 15) / 16; ++nt)
-        for (int kb = 0; kb < K / 32; ++kb) u.push_back({nt, 32 * kb});
-    return u;
-}
-static std::vector<std::pair<int, int>> units_tall(int K, int Nout) {   // [k-block][tile]
-    std::vector<std::pair<int, int>> u;
-    for (int kb = 0; kb < K / 32; ++kb)
-        for (int nt = 0; nt < (Nout + 15) / 16; ++nt) u.push_back({nt, 32 * kb});
-    return u;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -187,21 +84,14 @@ struct dff_model {
     int n_cus = 0;                             // hipDeviceAttributeMultiprocessorCount of `device`
 };
 
-static int upload_u32(dff_model* m, const std::vector<uint32_t>& h, const unsigned** out) {
+template <class T> static int upload(dff_model* m, const std::vector<T>& h, const T** out) {
+    *out = nullptr;
+    if (h.empty()) return DFF_OK;   // an image of an engine this model does not run
     void* p = nullptr;
-    HIPCHK(hipMalloc(&p, h.size() * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&p, h.size() * sizeof(T)));
     m->allocs.push_back(p);
-    HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    *out = (const unsigned*)p;
-    return DFF_OK;
-}
-
-static int upload(dff_model* m, const std::vector<float>& h, const float** out) {
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, h.size() * sizeof(float)));
-    m->allocs.push_back(p);
-    HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = (const float*)p;
+    HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = (const T*)p;
     return DFF_OK;
 }
 #define UP(vec, dst)                                  \
@@ -210,54 +100,12 @@ static int upload(dff_model* m, const std::vector<float>& h, const float** out) 
         if (rc_) return rc_;                          \
     } while (0)
 
-extern "C" size_t dff_weight_count(const dff_config* c) {
-    if (!c) return 0;
-    const size_t H = c->hidden, N = c->n_beads, I = DFF_INNER, F = 4 * H;
-    const size_t dec = c->conservative ? 1 : 3;   // node_decoder: Linear(H, 1) or Linear(H, 3)
-    const size_t nin = N + 1 + (c->use_abs_coords ? 3 : 0);                                  // graph_transformer.py:53
-    size_t nfe = (c->use_intrinsic_coords ? 3 : 0) + (c->use_distances ? 1 : 0);             // :54-58
-    if (nfe == 0) nfe = 1;
-    size_t n = H * nin + H + H * nfe + H + dec * H + dec;
-    const size_t per_layer = I * H + I + 2 * I * H + 2 * I + I * H + I + H * I + H + H + H + 3 * H +
-                             F * H + F + H * F + H + H + H + 3 * H;
-    return n + per_layer * c->n_layers;
+static bool env_flag(const char* name, char ch) {   // the variable is set and starts with `ch`
+    const char* e = getenv(name);
+    return e && e[0] == ch;
 }
-
-// cosine schedule + derived tables, float64 -> float32  (utils.py:52-62, models/ddpm.py:52-99)
-static void build_schedule(int T, std::vector<std::vector<float>>& out) {
-    const double s = 0.008, pi = 3.14159265358979323846;
-    std::vector<double> ac0(T + 1), betas(T), alphas(T), ac(T), acp(T);
-    for (int i = 0; i <= T; ++i) {
-        const double x = (double)i;  // torch.linspace(0, T, T+1) is exact for integer steps
-        const double cv = std::cos(((x / T) + s) / (1 + s) * pi * 0.5);
-        ac0[i] = cv * cv;
-    }
-    for (int i = T; i >= 0; --i) ac0[i] = ac0[i] / ac0[0];
-    for (int i = 0; i < T; ++i) {
-        double b = 1 - (ac0[i + 1] / ac0[i]);
-        betas[i] = b < 0 ? 0 : (b > 0.999 ? 0.999 : b);
-        alphas[i] = 1.0 - betas[i];
-    }
-    double cp = 1.0;
-    for (int i = 0; i < T; ++i) { cp *= alphas[i]; ac[i] = cp; }
-    for (int i = 0; i < T; ++i) acp[i] = i == 0 ? 1.0 : ac[i - 1];
-    out.assign(12, std::vector<float>(T));
-    for (int i = 0; i < T; ++i) {
-        const double pv = betas[i] * (1.0 - acp[i]) / (1.0 - ac[i]);
-        out[0][i] = (float)betas[i];
-        out[1][i] = (float)ac[i];
-        out[2][i] = (float)acp[i];
-        out[3][i] = (float)std::sqrt(ac[i]);
-        out[4][i] = (float)std::sqrt(1.0 - ac[i]);
-        out[5][i] = (float)std::log(1.0 - ac[i]);
-        out[6][i] = (float)std::sqrt(1.0 / ac[i]);
-        out[7][i] = (float)std::sqrt(1.0 / ac[i] - 1);
-        out[8][i] = (float)pv;
-        out[9][i] = (float)std::log(pv < 1e-20 ? 1e-20 : pv);
-        out[10][i] = (float)(betas[i] * std::sqrt(acp[i]) / (1.0 - ac[i]));
-        out[11][i] = (float)((1.0 - acp[i]) * std::sqrt(alphas[i]) / (1.0 - ac[i]));
-    }
-}
+// input branches other than the shipped one (intrinsic coordinates only) run the GEN variants
+static bool is_gen(const dff_config& c) { return !(c.use_intrinsic_coords == 1 && c.use_distances == 0 && c.use_abs_coords == 0); }
 
 extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_weights, int device,
                                 dff_model** out) {
@@ -265,7 +113,7 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
     auto is01 = [](int v) { return v == 0 || v == 1; };
     if (!(is01(cfg->use_intrinsic_coords) && is01(cfg->use_distances) && is01(cfg->use_abs_coords) && is01(cfg->conservative)))
         return fail(DFF_EINVAL, "use_intrinsic_coords, use_distances, use_abs_coords and conservative must be 0 or 1");
-    const int H = cfg->hidden, N = cfg->n_beads, L = cfg->n_layers, I = DFF_INNER, F = 4 * H;
+    const int H = cfg->hidden, N = cfg->n_beads, L = cfg->n_layers;
     // hidden sizes with kernel variants: the shipped 64 / 96 / 128, and 256 (the reference's own smoke test,
     // models/graph_transformer.py:332-359; fp32 engine, <= 32 beads)
     if (!(H == 64 || H == 96 || H == 128 || H == 256)) return fail(DFF_EINVAL, "hidden must be 64, 96, 128 or 256 (got %d)", H);
@@ -287,318 +135,39 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
     m->cfg = *cfg;
     m->device = device;
     HIPCHK(hipDeviceGetAttribute(&m->n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    {   // weight GEMMs on the fp16 pipe via the split of every fp32 operand, wherever a kernel variant exists for the
-        // shape (default); DFF_SPLIT_BF16=0: every GEMM on v_mfma_f32_16x16x4_f32
-        const char* e = getenv("DFF_SPLIT_BF16");
-        m->split = !(e && e[0] == '0');
-        // The fp16 pieces of the FORWARD GEMM inputs are taken of the activations as they are (dff_device.h split8h): LayerNorm
-        // outputs, attention outputs (averages of v), GELU(hidden).  Their worst-case magnitudes follow from the weights alone;
-        // a model that could take them past fp16's range (|x| < 1.6e4 keeps x and its 2^11-scaled low piece finite) runs the
-        // fp32 engine instead.  (The backward's inputs are scaled on the device.)  Trained models are orders of magnitude away.
-        if (m->split) {
-            const float* q = w;
-            auto skip = [&](size_t n) { const float* r = q; q += n; return r; };
-            const int NI_ = N + 1 + 3 * cfg->use_abs_coords, nfe_ = (3 * cfg->use_intrinsic_coords + cfg->use_distances) ? (3 * cfg->use_intrinsic_coords + cfg->use_distances) : 1;
-            skip((size_t)H * NI_); skip(H); skip((size_t)H * nfe_); skip(H); skip((size_t)(cfg->conservative ? 1 : 3) * H); skip(cfg->conservative ? 1 : 3);
-            auto amax = [](const float* a, size_t n) { double mx = 0; for (size_t i = 0; i < n; ++i) mx = std::max(mx, (double)fabsf(a[i])); return mx; };
-            auto rowl1 = [](const float* a, int rows, int cols) {   // largest L1 norm of a row of a (rows x cols) matrix
-                double mx = 0;
-                for (int r = 0; r < rows; ++r) { double t = 0; for (int c = 0; c < cols; ++c) t += fabs((double)a[(size_t)r * cols + c]); mx = std::max(mx, t); }
-                return mx;
-            };
-            double worst = 0;
-            // ... and the low end: a piece resolves 2^-25 / 2^11 = 2^-36 absolutely (fp16's subnormal spacing below 2^-14), so an
-            // operand whose largest entry is below 2^-12 no longer gets the format's 2^-22 relative accuracy.  `least` is the
-            // smallest of the GEMM weights' max|w| (exact zeros are exact pieces: skipped) and of the LayerNorm rows' bounds.
-            double least = INFINITY;
-            auto low = [&](double v) { if (v > 0) least = std::min(least, v); };
-            for (int l = 0; l < L; ++l) {
-                const float* Wq = skip((size_t)I * H); const float* bq = skip(I);
-                const float* Wkv = skip((size_t)2 * I * H); const float* bkv = skip(2 * I);
-                const float* Wek = skip((size_t)I * H); skip(I);
-                const float* Wo = skip((size_t)H * I); skip(H);
-                const float* ln1g = skip(H); const float* ln1b = skip(H);
-                skip(3 * H);
-                const float* W1 = skip((size_t)F * H); const float* b1 = skip(F);
-                const float* W2 = skip((size_t)H * F); skip(H);
-                const float* ln2g = skip(H); const float* ln2b = skip(H);
-                skip(3 * H);
-                const double m1 = sqrt((double)H) * amax(ln1g, H) + amax(ln1b, H);
-                const double m2 = sqrt((double)H) * amax(ln2g, H) + amax(ln2b, H);
-                const double vb = rowl1(Wkv + (size_t)I * H, I, H) * m1 + amax(bkv + I, I);   // |v| (and their attention averages)
-                const double hb = rowl1(W1, F, H) * m2 + amax(b1, F);                            // |h_pre| >= |GELU(h_pre)|
-                worst = std::max(std::max(worst, m1), std::max(std::max(m2, vb), hb));
-                // the weights themselves become fp16 pieces too (f32_to_f16_rn maps |w| >= 65520 to infinity)
-                const double aq = amax(Wq, (size_t)I * H), ak = amax(Wkv, (size_t)I * H), av = amax(Wkv + (size_t)I * H, (size_t)I * H),
-                             ae = amax(Wek, (size_t)I * H), ao = amax(Wo, (size_t)H * I), a1 = amax(W1, (size_t)F * H), a2 = amax(W2, (size_t)H * F);
-                worst = std::max(worst, std::max(std::max(std::max(aq, std::max(ak, av)), std::max(ae, ao)), std::max(a1, a2)));
-                low(m1); low(m2); low(aq); low(ak); low(av); low(ae); low(ao); low(a1); low(a2);
-                if (H == DFF_DH && L <= 3) {
-                    // the k / v fold's kernel (round 6) splits two more activations as they are: q' = W_k,h^T (W_q,h n + b_q,h), an operand
-                    // of the logits -- |q'| <= (L1 norm of a row of W_k,h^T W_q,h) max|n| + |W_k,h^T b_q,h| -- and the rows of
-                    // G = dattn (W_o,h W_v,h), an operand of dA, whose input rows arrive scaled to a maximum below 32
-                    double qb = 0, gb = 0, qm = 0, om = 0;   // (qm, om: max|W_k,h^T W_q,h|, max|W_o,h W_v,h| -- the folded images)
-                    for (int h = 0; h < DFF_HEADS; ++h)
-                        for (int e = 0; e < DFF_DH; ++e) {
-                            double l1 = 0, cqv = 0, g1 = 0;
-                            for (int c = 0; c < H; ++c) {
-                                double sq = 0, so = 0;
-                                for (int dd = 0; dd < DFF_DH; ++dd) {
-                                    sq += (double)Wkv[(size_t)(h * 64 + dd) * H + e] * Wq[(size_t)(h * 64 + dd) * H + c];
-                                    so += (double)Wo[(size_t)c * I + h * 64 + dd] * Wkv[(size_t)(I + h * 64 + dd) * H + e];
-                                }
-                                l1 += fabs(sq); g1 += fabs(so);
-                                qm = std::max(qm, fabs(sq)); om = std::max(om, fabs(so));
-                            }
-                            for (int dd = 0; dd < DFF_DH; ++dd) cqv += (double)Wkv[(size_t)(h * 64 + dd) * H + e] * bq[h * 64 + dd];
-                            qb = std::max(qb, l1 * m1 + fabs(cqv));
-                            gb = std::max(gb, 32.0 * g1);
-                        }
-                    worst = std::max(worst, std::max(qb, gb));
-                    low(qm); low(om);
-                }
-            }
-            if (!(worst < 1.6e4)) {
-                fprintf(stderr, "dff: forward activations of this model may reach %.3g (> 1.6e4): the fp16 split engine is off, weight GEMMs run on the fp32 matrix pipe\n", worst);
-                m->split = false;
-            } else if (least < 0x1p-12) {
-                fprintf(stderr, "dff: a weight matrix or LayerNorm row of this model is bounded by %.3g (< 2^-12): below the fp16 split engine's range, weight GEMMs run on the fp32 matrix pipe\n", least);
-                m->split = false;
-            }
-        }
-        // Two workgroups per protein (PAIR variants) need both blocks of a pair resident at once, and the launches are not cooperative
-        // (ADVICE r05): never where the GPU is known to be shared -- more local ranks than visible devices (torchrun's
-        // LOCAL_WORLD_SIZE) -- or where the caller says so (DFF_PAIR=0).  dff_debug_pair(m, 1) turns them back on.
-        {
-            const char* ep = getenv("DFF_PAIR");
-            const char* lw = getenv("LOCAL_WORLD_SIZE");
-            int ndev = 0;
-            if (ep && ep[0] == '0') m->pair_off = true;
-            else if (lw && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && atoi(lw) > ndev) {
-                m->pair_off = true;
-                static bool said = false;
-                if (!said) { said = true; fprintf(stderr, "dff: %s local ranks share %d GPU(s): the two-workgroups-per-protein kernels are off\n", lw, ndev); }
-            }
-        }
-        const char* ef = getenv("DFF_FOLD_KV");
-        // (the <= 16-row FOLD kernel keeps a model's forward activations in LDS / registers: built for <= 3 layers, which is
-        // every shipped configuration; a deeper hidden-64 model runs the unfolded kernels)
-        m->fold_kv = H == DFF_DH && L <= 3 && !(ef && ef[0] == '0');
-        const void* fn_; unsigned lds_; const char* nm_;
-        m->small_split = m->split && N <= 10 && dff_small_pick(DFF_MODE_SCORE, H, 8, false, true, &fn_, &lds_, &nm_);
+    // weight GEMMs on the fp16 pipe (default) unless DFF_SPLIT_BF16=0: every GEMM on v_mfma_f32_16x16x4_f32; DFF_FOLD_KV=0: no k / v
+    // fold.  The range guard (dff_prep.hip) has the last word on the engine, and says so on stderr.
+    const void* fn_; unsigned lds_; const char* nm_;
+    dff_prep::DffPrep p = dff_prep::dff_prepare(*cfg, w, !env_flag("DFF_SPLIT_BF16", '0'), !env_flag("DFF_FOLD_KV", '0'),
+                                                N <= 10 && dff_small_pick(DFF_MODE_SCORE, H, 8, false, true, &fn_, &lds_, &nm_));
+    fputs(p.note.c_str(), stderr);
+    m->split = p.split; m->small_split = p.small_split; m->fold_kv = p.fold_kv;
+    // Two workgroups per protein (PAIR variants) need both blocks of a pair resident at once, and the launches are not cooperative
+    // (ADVICE r05): never where the GPU is known to be shared -- more local ranks than visible devices (torchrun's
+    // LOCAL_WORLD_SIZE) -- or where the caller says so (DFF_PAIR=0).  dff_debug_pair(m, 1) turns them back on.
+    const char* lw = getenv("LOCAL_WORLD_SIZE");
+    int ndev = 0;
+    if (env_flag("DFF_PAIR", '0')) m->pair_off = true;
+    else if (lw && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && atoi(lw) > ndev) {
+        m->pair_off = true;
+        static bool said = false;
+        if (!said) { said = true; fprintf(stderr, "dff: %s local ranks share %d GPU(s): the two-workgroups-per-protein kernels are off\n", lw, ndev); }
     }
     memset(&m->dev, 0, sizeof m->dev);
     m->dev.N = N; m->dev.H = H; m->dev.L = L; m->dev.T = cfg->timesteps;
-
-    const float* p = w;
-    auto take = [&](size_t n) { const float* r = p; p += n; return r; };
-    const int intr = cfg->use_intrinsic_coords, dist = cfg->use_distances, ab = cfg->use_abs_coords;
-    const int NI = N + 1 + 3 * ab;                 // node inputs: one-hot (N) | x (3, with abs coords) | t
-    const int nfe_used = 3 * intr + dist;          // edge inputs: x_j - x_i (3) | |x_j - x_i|^2 ; neither -> one zero feature
-    const int nfe = nfe_used ? nfe_used : 1;
-    const float* Wn = take((size_t)H * NI);
-    const float* bn = take(H);
-    const float* We = take((size_t)H * nfe);
-    const float* be = take(H);
-    const int dec = cfg->conservative ? 1 : 3;
-    const float* wd = take((size_t)dec * H);
-    const float* bd = take(dec);
-    {
-        std::vector<float> WnT((size_t)NI * H);
-        for (int c = 0; c < H; ++c)
-            for (int i = 0; i < NI; ++i) WnT[(size_t)i * H + c] = Wn[(size_t)c * NI + i];
-        m->dev.in_intr = intr; m->dev.in_dist = dist; m->dev.in_abs = ab;
-        m->dev.wn_t = NI - 1;
-        UP(WnT, m->dev.WnT);
-        UP(std::vector<float>(bn, bn + H), m->dev.bn);
-        UP(std::vector<float>(wd, wd + (size_t)dec * H), m->dev.wdec);
-        m->dev.conservative = cfg->conservative;
-        m->dev.bdec = bd[0];
-        for (int c2 = 0; c2 < 3; ++c2) m->dev.bdec3[c2] = dec == 3 ? bd[c2] : 0.f;
-    }
+    m->dev.in_intr = cfg->use_intrinsic_coords; m->dev.in_dist = cfg->use_distances; m->dev.in_abs = cfg->use_abs_coords;
+    m->dev.wn_t = N + 3 * cfg->use_abs_coords;
+    m->dev.conservative = cfg->conservative;
+    m->dev.bdec = p.bdec;
+    memcpy(m->dev.bdec3, p.bdec3, sizeof p.bdec3);
+    UP(p.WnT, m->dev.WnT); UP(p.bn, m->dev.bn); UP(p.wdec, m->dev.wdec);
     for (int l = 0; l < L; ++l) {
-        const float* Wq = take((size_t)I * H);  const float* bq = take(I);
-        const float* Wkv = take((size_t)2 * I * H); const float* bkv = take(2 * I);
-        const float* Wek = take((size_t)I * H); const float* bek = take(I);
-        const float* Wo = take((size_t)H * I);  const float* bo = take(H);
-        const float* ln1g = take(H); const float* ln1b = take(H);
-        const float* g1 = take(3 * H);
-        const float* W1 = take((size_t)F * H);  const float* b1 = take(F);
-        const float* W2 = take((size_t)H * F);  const float* b2 = take(H);
-        const float* ln2g = take(H); const float* ln2b = take(H);
-        const float* g2 = take(3 * H);
         DffLayerDev& d = m->dev.layer[l];
-        // ---- fold edge_embedding into edges_to_kv (float64): W_c (512x3), b_c (512) ----
-        // W_c3 (512x3): the intrinsic-coordinate columns (zero without them); cd (512): the distance column
-        std::vector<double> Wc((size_t)I * 3, 0.0), cd(I, 0.0), bc(I);
-        for (int r = 0; r < I; ++r) {
-            double s0 = 0, s1 = 0, s2 = 0, sd = 0, sb = 0;
-            for (int c = 0; c < H; ++c) {
-                const double e = Wek[(size_t)r * H + c];
-                if (intr) { s0 += e * We[c * nfe + 0]; s1 += e * We[c * nfe + 1]; s2 += e * We[c * nfe + 2]; }
-                if (dist) sd += e * We[c * nfe + 3 * intr];
-                sb += e * be[c];
-            }
-            Wc[r * 3 + 0] = s0; Wc[r * 3 + 1] = s1; Wc[r * 3 + 2] = s2;
-            cd[r] = sd;
-            bc[r] = sb + bek[r];
-        }
-        // distance term: s_ih = c_h . q_ih -> W_s (8xH), b_s (8) ; D_ih feeds the output through w_od,h = W_o,h c_h (Hx8)
-        std::vector<double> Wsd((size_t)8 * H, 0.0), bsd(8, 0.0), Wod((size_t)H * 8, 0.0);
-        for (int h = 0; h < DFF_HEADS; ++h) {
-            for (int c = 0; c < H; ++c) {
-                double s = 0, t = 0;
-                for (int dd = 0; dd < DFF_DH; ++dd) {
-                    s += cd[h * 64 + dd] * Wq[(size_t)(h * 64 + dd) * H + c];
-                    t += (double)Wo[(size_t)c * I + h * 64 + dd] * cd[h * 64 + dd];
-                }
-                Wsd[(size_t)h * H + c] = s;
-                Wod[(size_t)c * 8 + h] = t;
-            }
-            double s = 0;
-            for (int dd = 0; dd < DFF_DH; ++dd) s += cd[h * 64 + dd] * bq[h * 64 + dd];
-            bsd[h] = s;
-        }
-        // W_u (24xH), b_u (24): u_ih = W_c,h^T q_ih ; W_oc (Hx24) = W_o,h W_c,h ; b_o' = b_o + W_o b_c
-        std::vector<double> Wu((size_t)24 * H, 0.0), bu(24, 0.0), Woc((size_t)H * 24, 0.0), bof(H);
-        for (int h = 0; h < DFF_HEADS; ++h)
-            for (int cc = 0; cc < 3; ++cc) {
-                for (int c = 0; c < H; ++c) {
-                    double s = 0;
-                    for (int dd = 0; dd < DFF_DH; ++dd) s += Wc[(h * 64 + dd) * 3 + cc] * Wq[(size_t)(h * 64 + dd) * H + c];
-                    Wu[(size_t)(3 * h + cc) * H + c] = s;
-                }
-                double s = 0;
-                for (int dd = 0; dd < DFF_DH; ++dd) s += Wc[(h * 64 + dd) * 3 + cc] * bq[h * 64 + dd];
-                bu[3 * h + cc] = s;
-                for (int c = 0; c < H; ++c) {
-                    double t = 0;
-                    for (int dd = 0; dd < DFF_DH; ++dd) t += (double)Wo[(size_t)c * I + h * 64 + dd] * Wc[(h * 64 + dd) * 3 + cc];
-                    Woc[(size_t)c * 24 + 3 * h + cc] = t;
-                }
-            }
-        for (int c = 0; c < H; ++c) {
-            double s = bo[c];
-            for (int r = 0; r < I; ++r) s += (double)Wo[(size_t)c * I + r] * bc[r];
-            bof[c] = s;
-        }
-        // ---- H == head dimension: fold W_k into W_q and W_v into W_o (float64) ----
-        // logits: q.k_j = (W_k,h^T q_i).n_j + [constant in j], so with q'_ih = W_k,h^T (W_q,h n_i + b_q,h) the keys are the
-        // LayerNorm rows n_j themselves; values: W_o,h sum_j a_ij (W_v,h n_j + b_v,h) = (W_o,h W_v,h) sum_j a_ij n_j + W_o,h b_v,h.
-        // The kernels keep their [q | u | k | v] layout: the k and v blocks of the images become identities (exactly
-        // representable, so k = v = n bit for bit) and the <= 16-row kernel skips them altogether.  u, s, W_oc, W_od above
-        // are built from the ORIGINAL q and W_o: the edge terms are untouched.
-        std::vector<double> Mq, cq, Wof;
-        if (m->fold_kv) {
-            Mq.assign((size_t)I * H, 0.0); cq.assign(I, 0.0); Wof.assign((size_t)H * I, 0.0);
-            for (int h = 0; h < DFF_HEADS; ++h)
-                for (int e = 0; e < DFF_DH; ++e) {
-                    for (int c = 0; c < H; ++c) {
-                        double sq = 0;
-                        for (int dd = 0; dd < DFF_DH; ++dd)
-                            sq += (double)Wkv[(size_t)(h * 64 + dd) * H + e] * Wq[(size_t)(h * 64 + dd) * H + c];
-                        Mq[(size_t)(h * 64 + e) * H + c] = sq;
-                    }
-                    double sc = 0;
-                    for (int dd = 0; dd < DFF_DH; ++dd) sc += (double)Wkv[(size_t)(h * 64 + dd) * H + e] * bq[h * 64 + dd];
-                    cq[h * 64 + e] = sc;
-                    for (int c = 0; c < H; ++c) {
-                        double so = 0;
-                        for (int dd = 0; dd < DFF_DH; ++dd)
-                            so += (double)Wo[(size_t)c * I + h * 64 + dd] * Wkv[(size_t)(I + h * 64 + dd) * H + e];
-                        Wof[(size_t)c * I + h * 64 + e] = so;
-                    }
-                }
-            for (int c = 0; c < H; ++c) {
-                double sbv = 0;
-                for (int r = 0; r < I; ++r) sbv += (double)Wo[(size_t)c * I + r] * bkv[I + r];
-                bof[c] += sbv;
-            }
-        }
-        const bool fold = m->fold_kv;
-        std::vector<float> bo32(H);
-        for (int c = 0; c < H; ++c) bo32[c] = (float)bof[c];
-
-        UP(std::vector<float>(ln1g, ln1g + H), d.ln1_g); UP(std::vector<float>(ln1b, ln1b + H), d.ln1_b);
-        UP(bo32, d.bo);
-        UP(std::vector<float>(g1, g1 + 3 * H), d.g1);
-        UP(std::vector<float>(ln2g, ln2g + H), d.ln2_g); UP(std::vector<float>(ln2b, ln2b + H), d.ln2_b);
-        UP(pack_b(H, F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), d.W1_p);
-        UP(std::vector<float>(b1, b1 + F), d.b1);
-        UP(pack_b(F, H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), d.W2_p);
-        UP(std::vector<float>(b2, b2 + H), d.b2);
-        UP(std::vector<float>(g2, g2 + 3 * H), d.g2);
-        // transposed orientation for the VJP
-        UP(pack_b(H, F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), d.W2T_p);
-        UP(pack_b(F, H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), d.W1T_p);
-        // extended-head images: column e of head h: [0,64) q, [64,67) u, [67,80) 0, [80,144) k, [144,208) v
-        auto wqkvx = [&](int col, int c) -> double {
-            const int h = col / 208, e = col % 208;
-            if (e < 64) return fold ? Mq[(size_t)(h * 64 + e) * H + c] : (double)Wq[(size_t)(h * 64 + e) * H + c];
-            if (e < 80) return e < 67 ? Wu[(size_t)(3 * h + e - 64) * H + c] : e == 67 ? Wsd[(size_t)h * H + c] : 0.0;
-            if (fold) return (e < 144 ? e - 80 : e - 144) == c ? 1.0 : 0.0;
-            if (e < 144) return Wkv[(size_t)(h * 64 + e - 80) * H + c];
-            return Wkv[(size_t)(I + h * 64 + e - 144) * H + c];
-        };
-        std::vector<float> bqkvx(8 * 208, 0.f);
-        for (int col = 0; col < 8 * 208; ++col) {
-            const int h = col / 208, e = col % 208;
-            bqkvx[col] = e < 64 ? (fold ? (float)cq[h * 64 + e] : bq[h * 64 + e]) : e < 67 ? (float)bu[3 * h + e - 64] : e == 67 ? (float)bsd[h]
-                         : e < 80 ? 0.f : fold ? 0.f : e < 144 ? bkv[h * 64 + e - 80] : bkv[I + h * 64 + e - 144];
-        }
-        // output projection with the xrel rows: row e of head h: [0,64) W_o[:, h*64+e], [64,67) W_oc[:, 3h+e-64]
-        auto wox = [&](int krow, int c) -> double {
-            const int h = krow / 80, e = krow % 80;
-            if (e < 64) return fold ? Wof[(size_t)c * I + h * 64 + e] : (double)Wo[(size_t)c * I + h * 64 + e];
-            return e < 67 ? Woc[(size_t)c * 24 + 3 * h + e - 64] : e == 67 ? Wod[(size_t)c * 8 + h] : 0.0;
-        };
-        UP(pack_b(H, 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), d.Wqkvx_p);
-        d.Wqkvx_s = d.W1_s = d.W2T_s = d.WoxT_s = d.W2_s = d.W1T_s = d.Wox_s = d.WqkvxT_s = nullptr;
-        if (m->split) {
-            int rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(H, 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_s))) return rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(H, F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_s))) return rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(H, F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_s))) return rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(H, 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_s))) return rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(F, H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_s))) return rc_;
-            if ((rc_ = upload_u32(m, pack_b_split_f16(F, H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_s))) return rc_;
-            // the 64 regular rows of every head of [W_o ; W_oc] (the extension rows stay on the fp32 image)
-            if ((rc_ = upload_u32(m, pack_b_split_f16(8 * 64, H, [&](int k, int n) { return wox((k / 64) * 80 + k % 64, n); }), &d.Wox_s))) return rc_;
-            // ... and the 192 regular rows [q | k | v] of every head of QKV_ext^T
-            if ((rc_ = upload_u32(m, pack_b_split_f16(8 * 192, H, [&](int c, int n) {
-                     const int h = c / 192, cc = c % 192;
-                     return wqkvx(h * 208 + (cc < 64 ? cc : cc + 16), n); }), &d.WqkvxT_s))) return rc_;
-        }
-        d.Wqkvx_w = d.W1_w = d.W2T_w = d.WoxT_w = d.Wox_t = d.W2_t = d.W1T_t = d.WqkvxT_t = nullptr;
-        if (m->small_split) {
-            int rc_;
-            // fold_kv on the shipped input branch: the <= 16-row kernel's FOLD variant streams [q' | u] (5 tiles per head) and
-            // back-projects dQ only (2 k-blocks per head); k = v = LayerNorm output never goes through a GEMM there
-            const bool sfold = m->fold_kv && intr && !dist && !ab;
-            if (sfold) {
-                if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wqkvx((n / 80) * 208 + n % 80, k); }), &d.Wqkvx_w))) return rc_;
-            } else
-            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 208), 8 * 208, [&](int k, int n) { return wqkvx(n, k); }), &d.Wqkvx_w))) return rc_;
-            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, F), F, [&](int k, int n) { return (double)W1[(size_t)n * H + k]; }), &d.W1_w))) return rc_;
-            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, F), F, [&](int k, int n) { return (double)W2[(size_t)k * F + n]; }), &d.W2T_w))) return rc_;
-            if ((rc_ = upload_u32(m, pack_units_f16(units_wide(H, 8 * 80), 8 * 80, [&](int k, int n) { return wox(n, k); }), &d.WoxT_w))) return rc_;
-            // Nout = H: the 64 regular rows of every head of [W_o ; W_oc] / [q | k | v] (extension rows: fp32 k-step off the fp32 images)
-            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 64, H), H, [&](int c, int n) { return wox((c / 64) * 80 + c % 64, n); }), &d.Wox_t))) return rc_;
-            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(F, H), H, [&](int k, int n) { return (double)W2[(size_t)n * F + k]; }), &d.W2_t))) return rc_;
-            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(F, H), H, [&](int k, int n) { return (double)W1[(size_t)k * H + n]; }), &d.W1T_t))) return rc_;
-            if (sfold) {
-                if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 64, H), H, [&](int c, int n) { return wqkvx((c / 64) * 208 + c % 64, n); }), &d.WqkvxT_t))) return rc_;
-            } else
-            if ((rc_ = upload_u32(m, pack_units_f16(units_tall(8 * 192, H), H, [&](int c, int n) {
-                     const int h = c / 192, cc = c % 192;
-                     return wqkvx(h * 208 + (cc < 64 ? cc : cc + 16), n); }), &d.WqkvxT_t))) return rc_;
-        }
-        UP(bqkvx, d.bqkvx);
-        UP(pack_b(8 * 80, H, [&](int k, int n) { return wox(k, n); }, 5), d.Wox_p);
-        UP(pack_b(H, 8 * 80, [&](int k, int n) { return wox(n, k); }), d.WoxT_p);
-        UP(pack_b(8 * 208, H, [&](int k, int n) { return wqkvx(k, n); }, 13), d.WqkvxT_p);
+#define X(T, n) UP(p.layer[l].n, d.n);
+        DFF_LAYER_IMAGES(X)
+#undef X
     }
-    build_schedule(cfg->timesteps, m->sched);
+    m->sched = std::move(p.sched);
     UP(m->sched[6], m->dev.sqrt_recip_ac);
     UP(m->sched[7], m->dev.sqrt_recipm1_ac);
     UP(m->sched[10], m->dev.post_c1);
@@ -728,142 +297,121 @@ extern "C" int dff_last_launch(const dff_model* m, const char** name, int* grid,
     return DFF_OK;
 }
 
-static int ensure_stash(dff_model* m, size_t need) {
-    if (need > m->stash_floats) {
-        if (m->stash) HIPCHK(hipFree(m->stash));
-        m->stash = nullptr; m->stash_floats = 0;
-        HIPCHK(hipMalloc((void**)&m->stash, need * sizeof(float)));
-        m->stash_floats = need;
-    }
+static int grow(float*& p, size_t& have, size_t need) {   // a device buffer of at least `need` floats (contents are not kept)
+    if (need <= have) return DFF_OK;
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr; have = 0;
+    HIPCHK(hipMalloc((void**)&p, need * sizeof(float)));
+    have = need;
     return DFF_OK;
 }
 
+// Two workgroups per protein need both blocks of a pair RESIDENT at once, and the launch is not cooperative: a PAIR grid (blocks b
+// and b + 8 share a protein, 16 blocks per 8 groups) must fit the device's CUs one block each, in ONE launch
+static bool pairs_fit(const dff_model* m, int ngroups) {
+    return 2 * 8 * ((ngroups + 7) / 8) <= (m->n_cus < m->max_wgs ? m->n_cus : m->max_wgs);
+}
+
+// what the launch path needs to know of a kernel variant at a group size
+struct LaunchSpec {
+    const void* fn;
+    const char* name;
+    unsigned lds;                 // bytes
+    int nthreads;
+    bool pair, small;             // two workgroups per protein; the <= 16-row kernel (stash layout of the debug reads)
+    int mt, prof_waves;           // row tiles (<= 64-row kernel); waves dff_debug_profile can pick from (<= 16-row kernel; else wave 0)
+    size_t stash, layer_stride;   // floats per workgroup, and per layer of it
+    size_t xchg;                  // PAIR: exchange floats per pair
+};
+
 // rows <= 16: one-head-per-wave kernel (dff_small.hip)
-static int ensure_pair_buffers(dff_model* m, int npairs, size_t need, hipStream_t stream);
-// pair: two workgroups per protein (dff_small_kernel<..., PAIR>: blocks b and b + 8 share a protein, 16 blocks per 8 proteins, ONE
-// launch -- the caller has checked that every block gets a CU of its own)
+static int small_spec(const dff_model* m, int mode, int G, bool pair, LaunchSpec* s) {
+    const int N = m->cfg.n_beads, H = m->cfg.hidden;
+    // 8 waves (two per SIMD, one head per wave) when the rows fit its 11-row head buffers
+    const bool eight = (H == 64 || H == 96) && G * N <= 10 && m->small_waves != 4;
+    const int NW = eight ? 8 : 4;
+    if (!dff_small_pick(mode, H, NW, is_gen(m->cfg), eight && m->small_split, &s->fn, &s->lds, &s->name, m->fold_kv, pair))
+        return fail(DFF_EINVAL, "no <= 16-row kernel for hidden=%d waves=%d in this build", H, NW);
+    s->lds *= (unsigned)sizeof(float);
+    if (s->lds > 160 * 1024) return fail(DFF_EINVAL, "LDS budget exceeded (%u bytes)", s->lds);
+    const SmallStash sl = dff_small_stash(N, G, H, m->cfg.n_layers);
+    s->nthreads = pair ? 256 : NW * 64; s->pair = pair; s->small = true; s->mt = 1; s->prof_waves = NW;
+    s->stash = sl.total; s->layer_stride = sl.layer_stride;
+    s->xchg = 4 * 1024;   // [half][parity][256 threads x 4 floats]
+    return DFF_OK;
+}
 static bool small_pair_available(const dff_model* m, int mode, int G) {
     const int N = m->cfg.n_beads, H = m->cfg.hidden;
     const void* fn; unsigned lds; const char* name;
-    const bool gen = !(m->cfg.use_intrinsic_coords == 1 && m->cfg.use_distances == 0 && m->cfg.use_abs_coords == 0);
     // OPT-IN (DFF_SMALL_PAIR=1, read per launch): built and measured in round 6 -- chignolin at 128 / 100 / 32 per GPU 45.8 / 45.9 / 45.4 us
     // per step against 44.4 with one workgroup per protein.  The wave-private blocks do shrink (-19 k cycles per step: four waves,
     // one per SIMD), but each of the 12 exchanges costs ~1.8 k cycles inside its row stage -- a store's s_waitcnt vmcnt(0) also
     // waits for the weight units the wave has just requested for the next block (loads and stores retire through one in-order
     // counter), 0.25 - 0.45 us in tools_ubench/pair_exchange.hip without that -- and the 16-lanes-per-row stages issue more per thread
     // (profiles/r06/pair_small/).  Kept as a tested variant; not the default.
-    const char* const en = getenv("DFF_SMALL_PAIR");
-    if (!(en && en[0] == '1')) return false;
-    return H == 64 && G * N <= 10 && m->small_waves == 0 && m->small_split && m->fold_kv && !gen && m->cfg.conservative &&
+    if (!env_flag("DFF_SMALL_PAIR", '1')) return false;
+    return H == 64 && G * N <= 10 && m->small_waves == 0 && m->small_split && m->fold_kv && !is_gen(m->cfg) && m->cfg.conservative &&
            dff_small_pick(mode, H, 8, false, true, &fn, &lds, &name, true, true);
 }
-static int launch_small(dff_model* m, DffRunArgs& a, int G, hipStream_t stream, bool pair = false) {
-    const int N = m->cfg.n_beads, H = m->cfg.hidden, L = m->cfg.n_layers;
-    const void* fn; unsigned lds; const char* name; int nthreads = 256;
-    // 8 waves (two per SIMD, one head per wave) when the rows fit its 11-row head buffers
-    const bool eight = (H == 64 || H == 96) && G * N <= 10 && m->small_waves != 4;
-    const bool gen = !(m->cfg.use_intrinsic_coords == 1 && m->cfg.use_distances == 0 && m->cfg.use_abs_coords == 0);
-    const int NW = eight ? 8 : 4;
-    const bool spw = eight && m->small_split;
-    if (!dff_small_pick(a.mode, H, NW, gen, spw, &fn, &lds, &name, m->fold_kv, pair))
-        return fail(DFF_EINVAL, "no <= 16-row kernel for hidden=%d waves=%d in this build", H, NW);
-    nthreads = pair ? 256 : NW * 64;
-    lds *= (unsigned)sizeof(float);
-    if (lds > 160 * 1024) return fail(DFF_EINVAL, "LDS budget exceeded (%u bytes)", lds);
+// generic kernel (rows <= 64), variant already chosen
+static int generic_spec(const dff_model* m, int G, const Variant* v, LaunchSpec* s) {
+    const int N = m->cfg.n_beads, H = m->cfg.hidden;
+    s->lds = v->lds_floats(N, G) * (unsigned)sizeof(float);
+    if (s->lds > 160 * 1024) return fail(DFF_EINVAL, "LDS budget exceeded (%u bytes) for N=%d G=%d H=%d", s->lds, N, G, H);
+    const StashLayout sl = dff_stash_layout(N, G, H, m->cfg.n_layers, v->MT);
+    s->fn = v->fn; s->name = v->name; s->nthreads = DFF_NTHREADS; s->pair = v->pair; s->small = false; s->mt = v->MT; s->prof_waves = 0;
+    s->stash = sl.total; s->layer_stride = sl.layer_stride;
+    s->xchg = 4 * (size_t)(G * N) * (H + 4);   // [half][parity][rows x (H + 4)]
+    return DFF_OK;
+}
+
+// one launch path for both kernels: grid, stash, PAIR buffers, the launches, the last_* record
+static int run(dff_model* m, DffRunArgs& a, int G, const LaunchSpec& s, hipStream_t stream) {
+    // PAIR: 16 blocks per 8 groups (a pair shares a GROUP of G proteins: ala2 two or three to a 16-row tile), ONE launch -- the caller
+    // has checked pairs_fit
     const int ngroups = (a.B + G - 1) / G;
-    const int npairs = pair ? 8 * ((ngroups + 7) / 8) : 0;
-    const int grid_all = pair ? 2 * npairs : ngroups;
-    const int grid_max = pair ? grid_all : (grid_all < m->max_wgs ? grid_all : m->max_wgs);
-    const SmallStash sl = dff_small_stash(N, G, H, L);
-    int rc = ensure_stash(m, (size_t)grid_max * sl.total);
+    const int npairs = s.pair ? 8 * ((ngroups + 7) / 8) : 0;
+    const int grid_all = s.pair ? 2 * npairs : ngroups;
+    // (so a PAIR grid is the single pass w0 = 0 of the loop below: b_base = w0 * G is the 0 the <= 16-row PAIR kernel expects)
+    const int grid_max = s.pair ? grid_all : (grid_all < m->max_wgs ? grid_all : m->max_wgs);
+    int rc = grow(m->stash, m->stash_floats, (size_t)grid_max * s.stash);
     if (rc) return rc;
     a.xchg = nullptr; a.xflag = nullptr; a.xpairs = npairs; a.xslow = m->pair_slow;
-    if (pair) {
-        rc = ensure_pair_buffers(m, npairs, (size_t)npairs * 4 * 1024, stream);   // [pair][half][parity][256 threads x 4 floats]
-        if (rc) return rc;
+    if (s.pair) {
+        // the exchange slots and the flag words -- error word, [pair][half] sequence flags, [pair][half] XCD ids; the sequence
+        // numbers restart at every launch, the error word at [0] is NOT touched
+        const size_t nflag = (size_t)4 * npairs + 1;
+        if ((rc = grow(m->xchg, m->xchg_floats, (size_t)npairs * s.xchg))) return rc;
+        if (!m->xflag) {   // once per model, sized for the largest grid a PAIR launch can have (one block per CU): no
+                           // re-allocation -- and so no synchronisation -- on the launch path afterwards
+            const size_t cap = 2 * (size_t)(m->n_cus > 256 ? m->n_cus : 256) + 1;   // 4 words per pair, at most n_cus / 2 pairs
+            HIPCHK(hipMalloc((void**)&m->xflag, cap * sizeof(unsigned)));
+            HIPCHK(hipMemsetAsync(m->xflag, 0, sizeof(unsigned), stream));
+            m->xflag_n = cap;
+        }
+        if (nflag > m->xflag_n) return fail(DFF_EINVAL, "PAIR grid of %d pairs exceeds the flag array", npairs);
+        HIPCHK(hipMemsetAsync(m->xflag + 1, 0, (nflag - 1) * sizeof(unsigned), stream));
         a.xchg = m->xchg; a.xflag = m->xflag;
     }
-    m->last_pair = pair;
+    m->last_small = s.small; m->last_pair = s.pair; m->last_mt = s.mt;
     a.G = G;
     a.prof = m->prof_on ? m->prof : nullptr;
-    a.prof_wave = m->prof_wave < NW ? m->prof_wave : 0;
+    a.prof_wave = m->prof_wave < s.prof_waves ? m->prof_wave : 0;
     a.stash = m->stash;
-    a.stash_stride = sl.total;
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    a.stash_stride = s.stash;
+    HIPCHK(hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
     // independent proteins: a batch larger than max_wgs workgroups runs as consecutive launches (same stream,
     // same stash), each over the whole step range
     for (int w0 = 0; w0 < grid_all; w0 += grid_max) {
         const int grid = grid_all - w0 < grid_max ? grid_all - w0 : grid_max;
-        a.b_base = pair ? 0 : w0 * G;
+        a.b_base = w0 * G;
         void* args[] = {(void*)&m->dev, (void*)&a};
-        HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(nthreads), args, lds, stream));
+        HIPCHK(hipLaunchKernel(s.fn, dim3(grid), dim3(s.nthreads), args, s.lds, stream));
         m->last_grid = grid; m->last_base = a.b_base;
         a.prof = nullptr;   // per-stage cycles: first launch only
     }
-    m->last_kernel = name; m->last_lds = (int)lds; m->last_G = G; m->last_B = a.B;
-    m->last_stride = sl.total; m->last_small = true;
-    return DFF_OK;
-}
-
-// PAIR launches (either kernel): the exchange slots (`need` floats) and the flag words -- error word, [pair][half] sequence flags,
-// [pair][half] XCD ids; the sequence numbers restart at every launch, the error word at [0] is NOT touched
-static int ensure_pair_buffers(dff_model* m, int npairs, size_t need, hipStream_t stream) {
-    const size_t nflag = (size_t)4 * npairs + 1;
-    if (need > m->xchg_floats) {
-        if (m->xchg) HIPCHK(hipFree(m->xchg));
-        m->xchg = nullptr; m->xchg_floats = 0;
-        HIPCHK(hipMalloc((void**)&m->xchg, need * sizeof(float)));
-        m->xchg_floats = need;
-    }
-    if (!m->xflag) {   // once per model, sized for the largest grid a PAIR launch can have (one block per CU): no
-                       // re-allocation -- and so no synchronisation -- on the launch path afterwards
-        const size_t cap = 2 * (size_t)(m->n_cus > 256 ? m->n_cus : 256) + 1;   // 4 words per pair, at most n_cus / 2 pairs
-        HIPCHK(hipMalloc((void**)&m->xflag, cap * sizeof(unsigned)));
-        HIPCHK(hipMemsetAsync(m->xflag, 0, sizeof(unsigned), stream));
-        m->xflag_n = cap;
-    }
-    if (nflag > m->xflag_n) return fail(DFF_EINVAL, "PAIR grid of %d pairs exceeds the flag array", npairs);
-    HIPCHK(hipMemsetAsync(m->xflag + 1, 0, (nflag - 1) * sizeof(unsigned), stream));
-    return DFF_OK;
-}
-
-// generic kernel (rows <= 64), variant already chosen
-static int launch_generic(dff_model* m, DffRunArgs& a, int G, const Variant* v, hipStream_t stream) {
-    const int N = m->cfg.n_beads, H = m->cfg.hidden, L = m->cfg.n_layers;
-    const unsigned lds = v->lds_floats(N, G) * (unsigned)sizeof(float);
-    if (lds > 160 * 1024) return fail(DFF_EINVAL, "LDS budget exceeded (%u bytes) for N=%d G=%d H=%d", lds, N, G, H);
-    // PAIR variants: blocks b and b + 8 share a protein (dff_kernels.hip), 16 blocks per 8 proteins, ONE launch: the caller
-    // has checked that every block gets a CU of its own (both blocks of a pair must be resident at once)
-    const int ngroups = (a.B + G - 1) / G;   // (a pair shares a GROUP of G proteins: ala2 two or three to a 16-row tile)
-    const int npairs = v->pair ? 8 * ((ngroups + 7) / 8) : 0;
-    const int grid_all = v->pair ? 2 * npairs : ngroups;
-    const int grid_max = v->pair ? grid_all : (grid_all < m->max_wgs ? grid_all : m->max_wgs);
-    const StashLayout sl = dff_stash_layout(N, G, H, L, v->MT);
-    { int rc = ensure_stash(m, (size_t)grid_max * sl.total); if (rc) return rc; }
-    a.xchg = nullptr; a.xflag = nullptr; a.xpairs = npairs; a.xslow = m->pair_slow;
-    if (v->pair) {
-        const int rc = ensure_pair_buffers(m, npairs, (size_t)npairs * 4 * (size_t)(G * N) * (H + 4), stream);
-        if (rc) return rc;
-        a.xchg = m->xchg; a.xflag = m->xflag;
-    }
-    m->last_small = false;
-    m->last_pair = v->pair;
-    m->last_mt = v->MT;
-    a.G = G;
-    a.prof = m->prof_on ? m->prof : nullptr;
-    a.stash = m->stash;
-    a.stash_stride = sl.total;
-    HIPCHK(hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (int w0 = 0; w0 < grid_all; w0 += grid_max) {   // see launch_small
-        const int grid = grid_all - w0 < grid_max ? grid_all - w0 : grid_max;
-        a.b_base = w0 * G;
-        void* args[] = {(void*)&m->dev, (void*)&a};
-        HIPCHK(hipLaunchKernel(v->fn, dim3(grid), dim3(DFF_NTHREADS), args, lds, stream));
-        m->last_grid = grid; m->last_base = a.b_base;
-        a.prof = nullptr;
-    }
-    m->last_kernel = v->name; m->last_lds = (int)lds; m->last_G = G; m->last_B = a.B;
-    m->last_stride = sl.total;
+    m->last_kernel = s.name; m->last_lds = (int)s.lds; m->last_G = G; m->last_B = a.B;
+    m->last_stride = s.stash;
     return DFF_OK;
 }
 
@@ -876,7 +424,7 @@ static int launch_generic(dff_model* m, DffRunArgs& a, int G, const Variant* v, 
 // built in chunks so that the stash does not grow beyond what sampling needs anyway.
 // v == nullptr: rows<=16 kernel, else that variant of the generic kernel.
 static int ensure_l0_table(dff_model* m, int kind, float t_norm, int G, const Variant* v, hipStream_t stream, const float** out) {
-    const int N = m->cfg.n_beads, H = m->cfg.hidden, L = m->cfg.n_layers, T = m->cfg.timesteps;
+    const int N = m->cfg.n_beads, T = m->cfg.timesteps;
     dff_model::L0Table* slot = nullptr;
     for (auto& c : m->l0[kind - 1]) {
         if (c.valid && c.G == G && c.waves == m->small_waves && c.variant == (const void*)v && c.split == m->small_split &&
@@ -890,17 +438,12 @@ static int ensure_l0_table(dff_model* m, int kind, float t_norm, int G, const Va
     dff_model::L0Table& tb = *slot;
     *out = nullptr;
     const int nent = kind == 2 ? T : 1;
-    size_t layer_stride, total;
-    if (v) { const StashLayout sl = dff_stash_layout(N, G, H, L, v->MT); layer_stride = sl.layer_stride; total = sl.total; }
-    else   { const SmallStash sl = dff_small_stash(N, G, H, L); layer_stride = sl.layer_stride; total = sl.total; }
-    const size_t need = (size_t)nent * layer_stride;
     tb.valid = false;   // invalid until filled
-    if (need > tb.floats) {
-        if (tb.tab) HIPCHK(hipFree(tb.tab));
-        tb.tab = nullptr; tb.floats = 0;
-        HIPCHK(hipMalloc((void**)&tb.tab, need * sizeof(float)));
-        tb.floats = need;
-    }
+    LaunchSpec s;
+    int rc = v ? generic_spec(m, G, v, &s) : small_spec(m, DFF_MODE_SCORE, G, false, &s);
+    if (rc) return rc;
+    const size_t layer_stride = s.layer_stride, total = s.stash;
+    if ((rc = grow(tb.tab, tb.floats, (size_t)nent * layer_stride))) return rc;
     int CH = nent < 256 ? nent : 256;         // noise levels (= workgroups) per build launch ...
     if (CH > m->max_wgs) CH = m->max_wgs;     // ... each of which must be ONE kernel launch (its stash is copied out)
     const int Bmax = CH * G;
@@ -924,8 +467,7 @@ static int ensure_l0_table(dff_model* m, int kind, float t_norm, int G, const Va
         memset(&a, 0, sizeof(a));
         a.mode = DFF_MODE_SCORE; a.B = ne * G; a.n_steps = 1; a.save_interval = 1;
         a.x_in = tmp.xz; a.tnorm = tmp.tnd; a.force_out = tmp.fo;
-        const int rc = v ? launch_generic(m, a, G, v, stream) : launch_small(m, a, G, stream);
-        if (rc) return rc;
+        if ((rc = run(m, a, G, s, stream))) return rc;
         // only the layer-0 slot of each workgroup's stash is kept
         HIPCHK(hipMemcpy2DAsync(tb.tab + (size_t)e0 * layer_stride, layer_stride * sizeof(float), m->stash,
                                 total * sizeof(float), layer_stride * sizeof(float), (size_t)ne,
@@ -940,7 +482,7 @@ static int ensure_l0_table(dff_model* m, int kind, float t_norm, int G, const Va
 
 // choose proteins-per-workgroup and the kernel variant, make sure scratch is large enough, launch
 static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
-    const int N = m->cfg.n_beads, H = m->cfg.hidden, L = m->cfg.n_layers;
+    const int N = m->cfg.n_beads, H = m->cfg.hidden;
     ON_DEVICE(m->device);
     const int mt_min = (N + 15) / 16;
     // Proteins per workgroup, by measurement (profiles/r02/packing.jsonl).  Packing only ever pays inside the padded rows a
@@ -960,7 +502,7 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
     if (mt > 4) { G = 64 / N; mt = (G * N + 15) / 16; }
     // input branches other than the shipped one run the GEN variants of the generic kernel; with absolute
     // coordinates layer 0 depends on x, so there is no layer-0 table
-    const bool gen = !(m->cfg.use_intrinsic_coords == 1 && m->cfg.use_distances == 0 && m->cfg.use_abs_coords == 0);
+    const bool gen = is_gen(m->cfg);
     const bool want_tab = a.mode != DFF_MODE_SCORE && !m->l0_off && !m->cfg.use_abs_coords;
     a.l0_tab = nullptr;
     const void* sfn_; unsigned slds_; const char* snm_;
@@ -971,7 +513,7 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
     // (round 5: 81 vs 86 us / step at 256 per GPU, 89 vs 138 at 768 -- three proteins per workgroup --, 60 vs 85 at 128, where it
     // runs as two workgroups per protein; hidden 128 at 5 / 10 / 16 rows: 90 / 150 / 157 vs 184 / 300 / 307).  DFF_SMALL_H96=1 keeps the
     // <= 16-row kernel.
-    static const bool small_h96 = [] { const char* e = getenv("DFF_SMALL_H96"); return e && e[0] == '1'; }();
+    static const bool small_h96 = env_flag("DFF_SMALL_H96", '1');
     const bool prefer_generic = (H == 96 || H == 128) && m->split && !small_h96 && m->small_waves == 0;   // (dff_debug_small_waves(m, 4 | 8) asks for the <= 16-row kernel)
     if (G * N <= 16 && !m->force_generic && have_small && !prefer_generic) {
         if (want_tab) {
@@ -981,11 +523,11 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
         // Two workgroups per protein when one per protein would leave at least half the CUs idle (round 6: the reference's published
         // protocol runs 100 trajectories, evaluate/sampling_commands.md:13; config 2 over 8 GPUs is 32 per GPU) -- same conditions as
         // the <= 64-row PAIR variants below: the whole grid resident one block per CU, no failure word seen, not switched off.
-        const int cu_cap_s = m->n_cus < m->max_wgs ? m->n_cus : m->max_wgs;
-        const int ngr_s = (a.B + G - 1) / G;
-        const bool spair = a.mode != DFF_MODE_SCORE && !m->pair_off && !m->sticky && 2 * 8 * ((ngr_s + 7) / 8) <= cu_cap_s &&
+        const bool spair = a.mode != DFF_MODE_SCORE && !m->pair_off && !m->sticky && pairs_fit(m, (a.B + G - 1) / G) &&
                            small_pair_available(m, a.mode, G);
-        return launch_small(m, a, G, stream, spair);
+        LaunchSpec s;
+        const int rc = small_spec(m, a.mode, G, spair, &s);
+        return rc ? rc : run(m, a, G, s, stream);
     }
     const Variant* v = nullptr;
     auto pick = [&](int mt_) {
@@ -1030,7 +572,6 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
     // Proteins that share a row tile anyway (ala2: up to three in 16 rows) are paired as a GROUP: the smallest group size
     // whose pairs fit the CUs -- ala2 at 256 per GPU runs as 128 groups of two on 256 workgroups instead of 256 single
     // proteins on 256 workgroups that each do all the heads.
-    const int cu_cap = m->n_cus < m->max_wgs ? m->n_cus : m->max_wgs;
     const Variant* vp = nullptr;
     // (no device access here: the launch path stays asynchronous.  A failure word the HOST has seen -- an earlier PAIR launch
     // timed out waiting for its partner: the GPU is shared or partitioned -- takes the PAIR variants out of the choice: the model
@@ -1049,8 +590,7 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
         const int g_lo = auto_group ? 1 : G, g_hi = auto_group ? (cap > 1 ? cap : 1) : G;
         const int G0 = G;
         for (int g = g_lo; cand && g <= g_hi; ++g) {
-            const int ngr = (a.B + g - 1) / g;
-            if (2 * 8 * ((ngr + 7) / 8) > cu_cap || (g * N + 15) / 16 > mt || cand->lds_floats(N, g) * sizeof(float) > 160u * 1024u) continue;
+            if (!pairs_fit(m, (a.B + g - 1) / g) || (g * N + 15) / 16 > mt || cand->lds_floats(N, g) * sizeof(float) > 160u * 1024u) continue;
             // the one-workgroup variant of the same shape builds the layer-0 table at THIS group size: it must fit there too
             // (it had been picked and LDS-checked at the old G)
             G = g;
@@ -1064,8 +604,9 @@ static int launch(dff_model* m, DffRunArgs& a, hipStream_t stream) {
         int rc = ensure_l0_table(m, a.mode == DFF_MODE_DDPM ? 2 : 1, a.t_norm, G, v, stream, &a.l0_tab);
         if (rc) return rc;
     }
-    if (vp) v = vp;
-    return launch_generic(m, a, G, v, stream);
+    LaunchSpec s;
+    const int rc = generic_spec(m, G, vp ? vp : v, &s);
+    return rc ? rc : run(m, a, G, s, stream);
 }
 
 extern "C" int dff_score(dff_model* m, const float* x, const float* tnorm, int batch, float* force,
@@ -1142,7 +683,7 @@ extern "C" int dff_debug_gemm(int device, const float* A, const float* W, int M,
     if (!A || !W || !out || M < 1 || M > 64 || Nout % 16 || !(K == 64 || K == 128))
         return fail(DFF_EINVAL, "dff_debug_gemm: M<=64, K in {64,128}, Nout%%16==0");
     ON_DEVICE(device);
-    std::vector<float> Wp = pack_b(K, Nout, [&](int k, int n) { return (double)W[(size_t)k * Nout + n]; });
+    std::vector<float> Wp = dff_prep::pack_b({K, Nout, [&](int k, int n) { return (double)W[(size_t)k * Nout + n]; }});
     float *dA, *dW, *dO;
     HIPCHK(hipMalloc((void**)&dA, (size_t)M * K * 4));
     HIPCHK(hipMalloc((void**)&dW, Wp.size() * 4));

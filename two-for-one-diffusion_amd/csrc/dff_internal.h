@@ -1,4 +1,4 @@
-// dff_internal.h -- structures shared by the host API (dff_host.hip) and the device code
+// dff_internal.h -- structures shared by the host API (dff_host.hip, dff_prep.hip) and the device code
 // (dff_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@
 #define DFF_NPROF 24       // per-stage cycle counters (debug)
 #define DFF_SMALL_LD 36   // leading dim of the 32-column u / xrel / r / du buffers
 
-// Packed B-operand layout for v_mfma_f32_16x16x4_f32 (see pack_b in dff_host.hip):
+// Packed B-operand layout for v_mfma_f32_16x16x4_f32 (see pack_b in dff_prep.hip):
 //   block (nt, kb) = 256 floats holding W[16kb .. 16kb+15][16nt .. 16nt+15];
 //   inside a block lane l = (kk = l>>4, nn = l&15) owns 4 consecutive floats
 //   s = 0..3  <->  W[16kb + 4kk + s][16nt + nn];   blocks ordered [nt][kb].
@@ -33,11 +33,11 @@ struct DffLayerDev {
     const float *g2;
     // backward (transposed orientation)
     const float *W2T_p;           // K=H, Nout=4H   dh  = dff  W2
-    // split engine (DFF_SPLIT_BF16=1): the weight images as two fp16 pieces per weight (dff_host.hip pack_b_split_f16)
+    // split engine (DFF_SPLIT_BF16=1): the weight images as two fp16 pieces per weight (dff_prep.hip pack_b_split_f16)
     const unsigned *Wqkvx_s, *W1_s, *W2T_s, *WoxT_s, *W2_s, *W1T_s, *Wox_s, *WqkvxT_s;
     const float *W1T_p;           // K=4H, Nout=H   df  = dhp  W1
     // split images (two fp16 pieces per weight) of all eight weight GEMMs for the <= 16-row kernel (dff_small.hip SPW variants;
-    // dff_host.hip pack_units_f16): *_w K = H, units ordered [tile][k-block]; *_t Nout = H, units ordered [k-block][tile]
+    // dff_prep.hip pack_units_f16): *_w K = H, units ordered [tile][k-block]; *_t Nout = H, units ordered [k-block][tile]
     const unsigned *Wqkvx_w, *W1_w, *W2T_w, *WoxT_w, *Wox_t, *W2_t, *W1T_t, *WqkvxT_t;
     // "extended head" images: per head 80 = 64 + 16 extension columns / rows ([u (3) | s | 0...], [xrel (3) | D | 0...])
     const float *Wqkvx_p, *bqkvx; // K=H, Nout=8*208, per head [q 64 | ext 16 | k 64 | v 64]

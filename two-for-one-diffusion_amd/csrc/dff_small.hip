@@ -199,7 +199,7 @@ DEVI void wide_run(Ring<E, DR>& ring, float (&aux)[DR][NAUX], const f32x4 (&a)[E
 // The A fragment of k-block kb + 1 is read from LDS BEFORE the MFMAs of k-block kb are issued (`a` is the
 // fragment of this step, loaded one step ago): otherwise every step starts with an exposed LDS round trip.
 // XKB >= 0: k-block XKB (> 0) is a head's extension block, whose weight rows 4..15 are zero: one k-step over its
-// columns 0..3 instead of four (the packed image holds row lane >> 4 in k-step 0, dff_host.hip pack_b).
+// columns 0..3 instead of four (the packed image holds row lane >> 4 in k-step 0, dff_prep.hip pack_b).
 template <int SLOT, int N, int E, int XKB, int DR, class FA>
 DEVI void tall_step(Ring<E, DR>& ring, f32x4 (&acc)[E], f32x4& a, const FA& fa, const WStream& w, const WStream& wn, int lane, int kb) {
     f32x4 (&b)[E] = ring.b[SLOT];
@@ -241,7 +241,7 @@ DEVI void tall_run(Ring<E, DR>& ring, f32x4 (&acc)[E], const FA fa, const WStrea
 
 // ---------------------------------------------------------------- split engine (SPW variants)
 // The weight GEMMs on the fp16 matrix pipe at fp32 accuracy (the two-piece split of dff_device.h split8h): three
-// v_mfma_f32_16x16x32_f16 per unit instead of eight v_mfma_f32_16x16x4_f32.  The weights are split on the host (dff_host.hip
+// v_mfma_f32_16x16x32_f16 per unit instead of eight v_mfma_f32_16x16x4_f32.  The weights are split on the host (dff_prep.hip
 // pack_units_f16); the row stages write the A operand as pieces (asp), or the consuming wave splits an fp32 operand in registers.
 // One ring entry = one UNIT = (16-column output tile, 32-row k-block) = two pieces x 16 B per lane; every stream is a linear
 // sequence of units ([tile][k-block] for the K = H GEMMs, [k-block][tile] for the Nout = H ones), the ring holds DR units, and
@@ -344,7 +344,7 @@ DEVI void swide_run(SRing<DR>& ring, float (&aux)[2][NAUX], const u32x4 (&ah)[KB
 // kb (the second four are 16 floats on), split in registers (scaled by sa first).  The next block's A is read from LDS before
 // the MFMAs of this one are issued.
 // EXT: one fp32 k-step on top for a head's extension columns (of which only 0..3 carry data): A element *ext_a, weights
-// ext_w[nt * ext_ts] (the s = 0 slots of the fp32 image's extension block, dff_host.hip pack_b), requested first, used last.
+// ext_w[nt * ext_ts] (the s = 0 slots of the fp32 image's extension block, dff_prep.hip pack_b), requested first, used last.
 template <int I0, int KB, int NKB, int E, int DR, class Q, class FA>
 DEVI void stall_from(SRing<DR>& ring, f32x4 (&acc)[E], f32x4 (&acc2)[E], f32x4& x0, f32x4& x1, const FA& fa, const Q& q, int lane, float sa) {
     if constexpr (KB < NKB) {
@@ -738,7 +738,7 @@ DEVI void head_dma(const lu32* tab, const lfloat* Qx /* wave-uniform; the region
 }
 
 // ---------------------------------------------------------------- the kernel
-// FOLD (hidden == head dimension, dff_host.hip folds W_k into W_q and W_v into W_o): keys and values ARE the LayerNorm rows,
+// FOLD (hidden == head dimension, dff_prep.hip folds W_k into W_q and W_v into W_o): keys and values ARE the LayerNorm rows,
 // so the QKV_ext GEMM has 5 tiles per head instead of 13 (q' | u), K_ext = V_ext is ONE shared fp32 copy of the LayerNorm
 // output (+ x), written by the row stages next to its fp16 pieces, dK and dV go straight into the wave's partial of
 // d(LayerNorm output) (identity back-projection) and the QKV_ext^T GEMM keeps only its dQ blocks; only q' is stashed.
