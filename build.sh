@@ -1,8 +1,8 @@
 #!/bin/bash
-# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Seven translation units compiled in
+# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Eight translation units compiled in
 # parallel: the <= 64-row kernel, the <= 16-row kernel once per sampler mode (score / Langevin / DDPM), the host half
-# (model, dispatch, sampler ABI), weight preparation (folds, range guard, operand images: pure CPU work) and the sample-analysis
-# half (PWD / structure / TICA / state kernels and their ABI).
+# (model, dispatch, sampler ABI), weight preparation (folds, range guard, operand images: pure CPU work), the sample-analysis
+# half (PWD / structure / TICA / state kernels and their ABI) and the forward process with its loss (dff_loss: q_sample, p_losses).
 #   DFF_EXTRA_FLAGS="-DDFF_FAST_BUILD"   development build: headline variants only (fast to compile)
 set -e
 cd "$(dirname "$(readlink -f "$0")")"
@@ -31,7 +31,7 @@ stale() {
     return 1
 }
 pids=()
-for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host dff_prep dff_analysis; do
+for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host dff_prep dff_analysis dff_loss; do
     # rebuild a unit only when one of its own sources is newer than its object (or the flags changed)
     stamp="$OBJ/$tu.flags"
     src=$tu; extra=""
@@ -51,5 +51,5 @@ done
 rc=0
 for p in "${pids[@]}"; do wait $p || rc=1; done
 [ $rc = 0 ] || { echo "compile failed"; exit 1; }
-hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/dff_kernels.o $OBJ/dff_small_m0.o $OBJ/dff_small_m1.o $OBJ/dff_small_m2.o $OBJ/dff_host.o $OBJ/dff_prep.o $OBJ/dff_analysis.o -o $OUT
+hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/dff_kernels.o $OBJ/dff_small_m0.o $OBJ/dff_small_m1.o $OBJ/dff_small_m2.o $OBJ/dff_host.o $OBJ/dff_prep.o $OBJ/dff_analysis.o $OBJ/dff_loss.o -o $OUT
 echo "built $OUT"

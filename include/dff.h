@@ -117,7 +117,9 @@ typedef struct {
  * u(w) = (float(w) + 0.5) 2^-32, r(w) = sqrt(-2 ln u(w)) (oracle/noise.py is the host reference; tests/test_noise_stream.py
  * holds every kernel variant to it).  It does not depend on how a batch is sharded, chunked, grouped or on the kernel variant.
  * LIMIT: the bead index shares counter word 1 with bits 32.. of the trajectory index, so with noise_dev == NULL
- * traj_offset + n_traj must not exceed 2^40 (DFF_EINVAL otherwise: beyond it two trajectories would share draws). */
+ * traj_offset + n_traj must not exceed 2^40 (DFF_EINVAL otherwise: beyond it two trajectories would share draws).
+ * Steps in use: step_offset + s here; the level t (0 .. T - 1) and 0xFFFFFFFF (the prior) in dff_ddpm_run; 0xFFFFFFFE00000000 | draw
+ * for the forward process (dff_q_sample / dff_denoise_loss), reserved for it: a step_offset that high would alias those draws. */
 int dff_langevin_run(dff_model* m, const dff_langevin_params* p, int n_traj, float* x_dev,
                      float* v_dev, const float* noise_dev, uint64_t seed, uint64_t traj_offset,
                      uint64_t step_offset, int n_steps, int save_interval, float* frames_dev,
@@ -135,6 +137,44 @@ int dff_langevin_run(dff_model* m, const dff_langevin_params* p, int n_traj, flo
 int dff_ddpm_run(dff_model* m, int batch, float* x_dev, const float* noise_dev, uint64_t seed,
                  uint64_t sample_offset, int t_start, int t_end, int init_prior,
                  int* clamp_flag_dev, void* stream);
+
+/* ---- the forward process and its loss (csrc/dff_loss.hip) ----
+ * GaussianDiffusion.q_sample followed by the center_zero of p_losses (models/ddpm.py:265-274, 292-296):
+ *   xt[b] = center_zero(sqrt_alphas_cumprod[t_b] x0[b] + sqrt_one_minus_alphas_cumprod[t_b] center_zero(z[b])),
+ * fp32 on the model's own schedule tables, and tnorm[b] = float(t_b) / float(T) (tnorm_dev may be NULL).  x0_dev (batch,N,3)
+ * is used as given: centring it and dividing by norm_factor are the caller's job, as in GaussianDiffusion.forward.
+ * t_dev (batch) int32 levels, 0 <= t_b < T; nothing is read back to check them: a level outside the range gives NaN in that
+ * sample's outputs (and only there).  z: noise_dev (batch,N,3), or NULL for in-kernel Philox draws keyed as
+ * dff_langevin_run keys its draws with item = sample_offset + b and
+ *   step = 0xFFFFFFFE00000000 | draw
+ * -- a step value RESERVED for the forward process: the DDPM loop uses steps 0 .. T - 1 and 0xFFFFFFFF, Langevin
+ * step_offset + s; a Langevin run whose step_offset reaches 0xFFFFFFFE00000000 would alias it.  `draw` noises one structure
+ * several times independently.  The same 2^40 item limit applies: sample_offset + batch must not exceed 2^40 when
+ * noise_dev == NULL (DFF_EINVAL otherwise).  The draws do not depend on how a batch is split over calls. */
+int dff_q_sample(dff_model* m, const float* x0_dev, const int32_t* t_dev, int batch,
+                 const float* noise_dev, uint64_t seed, uint64_t sample_offset, uint32_t draw,
+                 float* xt_dev, float* tnorm_dev, void* stream);
+
+/* Bytes of device workspace dff_denoise_loss needs for `batch` samples: x_t, tnorm and the model output of one pass of at
+ * most 16384 samples plus 256 partial sums -- bounded, whatever the batch; -1 on bad arguments. */
+long long dff_denoise_workspace_bytes(const dff_model* m, int batch);
+/* GaussianDiffusion.p_losses for objective = "pred_noise" (models/ddpm.py:288-315) in one call: dff_q_sample into the workspace,
+ * the score op on the launch path of dff_score (every configuration dff_score accepts, the same kernels), then
+ *   loss_dev[b] = mean over the 3 N entries of |d| (loss_type 1, l1) or d^2 (2, l2),  d = center_zero(model_out[b]) - center_zero(z[b])
+ * -- the mean of row b of the reference's reduce(loss, "b ... -> b (...)", "mean"), whose mean over b p_losses returns; the
+ * centring, d and the mean are taken in fp64 and rounded to fp32 once.  With noise_dev == NULL the target is drawn again from Philox where it is used: the noise never exists in memory.
+ * A level outside 0 .. T - 1 gives loss_dev[b] = NaN.
+ * total_dev (2 doubles, may be NULL) is ADDED to: total[0] += the fp64 sum of loss_dev, total[1] += batch (a non-finite loss
+ * adds to both).  The sum is a two-stage reduction in a fixed order without floating-point atomics: bit-identical from call to
+ * call, as dff_kmeans_step's.  Results do not depend on dff_debug_max_workgroups.
+ * xt_out_dev / model_out_dev (batch,N,3), optional: copies of x_t and of the score output before its centring.
+ * workspace_dev: >= dff_denoise_workspace_bytes(m, batch) bytes, 8-byte aligned; a batch beyond one pass runs as consecutive
+ * passes over it. */
+int dff_denoise_loss(dff_model* m, const float* x0_dev, const int32_t* t_dev, int batch,
+                     const float* noise_dev, uint64_t seed, uint64_t sample_offset, uint32_t draw,
+                     int loss_type /* 1 = l1, 2 = l2 */, float* loss_dev /* (batch) */,
+                     double* total_dev /* (2), may be NULL */, float* xt_out_dev, float* model_out_dev /* may be NULL */,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Sticky status word of everything this model has launched so far (synchronises the device).  0 = fine.  Bit 0: a launch
  * of a two-workgroups-per-protein kernel variant (chosen automatically for batches that would leave half the CUs idle, see

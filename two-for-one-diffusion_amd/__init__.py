@@ -12,7 +12,7 @@ from .sampling import SamplerWrapper, num_to_groups, sample_from_model  # noqa: 
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",
-           "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator"]
+           "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator", "eval_loss", "loss_profile"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -28,4 +28,7 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
     if name in ("KMeans", "StateTransitionEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("eval_loss", "loss_profile"):
+        from . import losses
+        return getattr(losses, name)
     raise AttributeError(name)

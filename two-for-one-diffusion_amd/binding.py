@@ -14,6 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DFF_LIB_PATH") or os.path.join(_HERE, "libdff_amd.so")   # DFF_LIB_PATH: development builds
 DFF_MAX_BEADS = 64
+FORWARD_STEP = 0xFFFFFFFE00000000    # Philox step of the forward-process draws is FORWARD_STEP | draw (include/dff.h)
+LOSS_TYPES = {"l1": 1, "l2": 2}
 
 SCHEDULE_NAMES = (
     "betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod",
@@ -53,6 +55,10 @@ SYMBOLS = {
                                    C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
     "dff_ddpm_run": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                _P, _P]),
+    "dff_q_sample": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "dff_denoise_workspace_bytes": (C.c_longlong, [_P, C.c_int]),
+    "dff_denoise_loss": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P, _P,
+                                   _P, C.c_size_t, _P]),
     "dff_set_group": (C.c_int, [_P, C.c_int]),
     "dff_debug_force_generic": (C.c_int, [_P, C.c_int]),
     "dff_debug_small_waves": (C.c_int, [_P, C.c_int]),
@@ -275,6 +281,67 @@ class Model:
         rc = self.lib.dff_ddpm_run(self.handle, B, _ptr(x), _ptr(noise), seed & (2 ** 64 - 1), sample_offset,
                                    t_start, t_end, int(init_prior), _ptr(clamp_flag), self._stream())
         _check(self.lib, rc, "dff_ddpm_run")
+
+    # ---- the forward process and its loss
+    def _levels(self, t, B):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and tuple(t.shape) == (B,)
+                and not t.is_floating_point()):
+            raise ValueError(f"t must be an integer CUDA tensor of shape ({B},) on cuda:{self.device}")
+        return t.to(torch.int32).contiguous()
+
+    def q_sample(self, x0, t, noise=None, seed: int = 0, sample_offset: int = 0, draw: int = 0, return_tnorm=False):
+        """x_t = center_zero(sqrt_ac[t] x0 + sqrt_1mac[t] center_zero(z)) (dff_q_sample): z = `noise`, or in-kernel Philox
+        draws keyed by (seed; sample_offset + b, FORWARD_STEP | draw).  t: integer levels (B,); NaN rows for a level
+        outside 0 .. T - 1."""
+        import torch
+        B = x0.shape[0]
+        self._dev_tensor(x0, (B, self.n_beads, 3), "x0")
+        t32 = self._levels(t, B)
+        if noise is not None:
+            self._dev_tensor(noise, (B, self.n_beads, 3), "noise")
+        xt = torch.empty_like(x0)
+        tn = torch.empty(B, dtype=torch.float32, device=x0.device) if return_tnorm else None
+        rc = self.lib.dff_q_sample(self.handle, _ptr(x0), _ptr(t32), B, _ptr(noise), seed & (2 ** 64 - 1), sample_offset,
+                                   draw, _ptr(xt), _ptr(tn), self._stream())
+        _check(self.lib, rc, "dff_q_sample")
+        return (xt, tn) if return_tnorm else xt
+
+    def denoise_workspace_bytes(self, batch: int) -> int:
+        b = int(self.lib.dff_denoise_workspace_bytes(self.handle, int(batch)))
+        if b < 0:
+            _check(self.lib, 1, "dff_denoise_workspace_bytes")
+        return b
+
+    def denoise_loss(self, x0, t, noise=None, seed: int = 0, sample_offset: int = 0, draw: int = 0, loss_type="l2",
+                     total=None, return_xt=False, return_model_out=False):
+        """Per-sample denoising loss (dff_denoise_loss) -> float32 CUDA tensor (B,), or a tuple (loss[, x_t][, model_out]).
+        `total`, a float64 CUDA tensor (2,), is added to on the device: (sum of the losses, B).  The workspace is
+        allocated once and kept (it is bounded: one pass of the library's chunk size)."""
+        import torch
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"invalid loss type {loss_type}")
+        B = x0.shape[0]
+        self._dev_tensor(x0, (B, self.n_beads, 3), "x0")
+        t32 = self._levels(t, B)
+        if noise is not None:
+            self._dev_tensor(noise, (B, self.n_beads, 3), "noise")
+        if total is not None and not (isinstance(total, torch.Tensor) and total.is_cuda and total.dtype == torch.float64
+                                      and total.device.index == self.device and total.is_contiguous() and total.numel() == 2):
+            raise ValueError("total must be a contiguous float64 CUDA tensor of 2 elements on the model's device")
+        need = self.denoise_workspace_bytes(B)
+        ws = getattr(self, "_loss_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._loss_ws = torch.empty(need, dtype=torch.uint8, device=x0.device)
+        loss = torch.empty(B, dtype=torch.float32, device=x0.device)
+        xt = torch.empty_like(x0) if return_xt else None
+        out = torch.empty_like(x0) if return_model_out else None
+        rc = self.lib.dff_denoise_loss(self.handle, _ptr(x0), _ptr(t32), B, _ptr(noise), seed & (2 ** 64 - 1), sample_offset,
+                                       draw, LOSS_TYPES[loss_type], _ptr(loss), _ptr(total), _ptr(xt), _ptr(out), _ptr(ws),
+                                       ws.numel(), self._stream())
+        _check(self.lib, rc, "dff_denoise_loss")
+        res = (loss,) + ((xt,) if return_xt else ()) + ((out,) if return_model_out else ())
+        return res if len(res) > 1 else loss
 
     # ---- debugging
     PROFILE_STAGES = ("centre", "embed+ln1", "gemm_u", "gemm_qkv", "softmax", "pv+xrel", "gemm_wo", "gate1+ln2",

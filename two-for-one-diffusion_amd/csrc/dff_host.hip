@@ -82,6 +82,7 @@ struct dff_model {
     unsigned sticky = 0;                       // the sticky error word as the host last read it (read_status): a non-zero one
                                                // refuses further PAIR launches WITHOUT touching the device
     int n_cus = 0;                             // hipDeviceAttributeMultiprocessorCount of `device`
+    const float *sqrt_ac = nullptr, *sqrt_1mac = nullptr;   // forward-process tables on the device (dff_loss.hip; the kernels' DffModelDev has no use for them)
 };
 
 template <class T> static int upload(dff_model* m, const std::vector<T>& h, const T** out) {
@@ -173,6 +174,8 @@ extern "C" int dff_model_create(const dff_config* cfg, const float* w, size_t n_
     UP(m->sched[10], m->dev.post_c1);
     UP(m->sched[11], m->dev.post_c2);
     UP(m->sched[9], m->dev.post_logvar);
+    UP(m->sched[3], m->sqrt_ac);
+    UP(m->sched[4], m->sqrt_1mac);
     undo.m = nullptr;
     *out = m;
     return DFF_OK;
@@ -193,6 +196,14 @@ extern "C" void dff_model_destroy(dff_model* m) {
 extern "C" int dff_schedule(const dff_model* m, int which, float* out_host) {
     if (!m || !out_host || which < 0 || which >= 12) return fail(DFF_EINVAL, "bad schedule request");
     memcpy(out_host, m->sched[which].data(), m->sched[which].size() * sizeof(float));
+    return DFF_OK;
+}
+
+// what the forward-process unit (dff_loss.hip) needs of the handle, which is private to this file
+int dff_model_loss_view(const dff_model* m, DffLossView* v) {
+    if (!m || !v) return fail(DFF_EINVAL, "null argument");
+    v->device = m->device; v->n_beads = m->cfg.n_beads; v->timesteps = m->cfg.timesteps;
+    v->sqrt_ac = m->sqrt_ac; v->sqrt_1mac = m->sqrt_1mac;
     return DFF_OK;
 }
 

@@ -1,4 +1,4 @@
-"""Host mirror of ``GaussianDiffusion`` (models/ddpm.py:20-263), sampling half.
+"""Host mirror of ``GaussianDiffusion`` (models/ddpm.py:20-337): the sampling half and the forward process with its loss.
 
 The reverse loop itself -- 1000 score-network calls, each followed by the posterior update,
 the +-1000 clamp and the centring -- runs inside ONE persistent HIP kernel launch
@@ -7,6 +7,7 @@ step: utils.py:79, ddpm.py:248).
 """
 from __future__ import annotations
 
+import math
 import warnings
 from typing import Optional
 
@@ -36,11 +37,47 @@ def assert_center_zero(x, eps=1e-3):
         raise AssertionError(f"Center not at zero: abs max at {center_max}")
 
 
+def _cosine_schedule64(timesteps: int, s: float = 0.008):
+    """(betas, alphas_cumprod) of the cosine schedule in float64, operation by operation as utils.py:52-62 and
+    ddpm.py:52-53 compute them: the loss-weight tables are functions of these, not of their float32 roundings."""
+    x = torch.linspace(0, timesteps, timesteps + 1, dtype=torch.float64)
+    ac = torch.cos(((x / timesteps) + s) / (1 + s) * math.pi * 0.5) ** 2
+    ac = ac / ac[0]
+    betas = torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999)
+    return betas, torch.cumprod(1.0 - betas, dim=0)
+
+
+def p2_loss_weight_table(loss_weights="ones", timesteps: int = 1000, p2_loss_weight_gamma: float = 0.0,
+                         p2_loss_weight_k: float = 1):
+    """The float32 ``p2_loss_weight`` buffer of ddpm.py:100-138 (CPU tensor): the distribution ``forward`` draws the
+    noise levels from.  Branch order, parsing and the exception are the reference's."""
+    betas, ac = _cosine_schedule64(timesteps)
+    if loss_weights == "ones":
+        w = (p2_loss_weight_k + ac / (1 - ac)) ** -p2_loss_weight_gamma
+    elif loss_weights == "score_matching":
+        w = 1.0 / (1 - ac)                      # (the reference registers the unnormalised weights)
+    elif "higheruntil_" in loss_weights:
+        threshold = int(loss_weights.split("_")[1])
+        w = torch.Tensor([len(ac) / threshold] * threshold + [len(ac) / (len(ac) - threshold)] * (len(ac) - threshold))
+    elif "lower_bound" in loss_weights:
+        clamp_val = int(loss_weights.split("_")[2])
+        unnormalized = (1.0 / ((1 - ac) * (1 - betas))).clip(0, clamp_val)
+        w = unnormalized / sum(unnormalized) * len(betas)   # (Python's sum: element by element, as the reference adds)
+    else:
+        raise Exception(f"Wrong loss_weights: {loss_weights}")
+    return w.to(torch.float32)
+
+
+def p2_loss_weight_tables(requests):
+    """[p2_loss_weight_table(*r) for r in requests] as numpy arrays (one call for several tables)."""
+    return [p2_loss_weight_table(*r).numpy() for r in requests]
+
+
 class GaussianDiffusion:
     def __init__(self, model: GraphTransformer, features=None, num_atoms: Optional[int] = None,
                  timesteps: int = 1000, loss_type="l2", objective="pred_noise", beta_schedule="cosine",
-                 p2_loss_weight_gamma: float = 0.0, p2_loss_weight_k: float = 1,   # training-only (ddpm.py:32-33): accepted in
-                 norm_factor: float = 1, loss_weights="ones", seed: int = 0,       # their reference positions, unused here
+                 p2_loss_weight_gamma: float = 0.0, p2_loss_weight_k: float = 1,
+                 norm_factor: float = 1, loss_weights="ones", seed: int = 0,
                  defer_checks: bool = False):
         if objective != "pred_noise" or beta_schedule != "cosine":
             raise ValueError("only objective='pred_noise', beta_schedule='cosine' (the shipped configs) are supported")
@@ -55,10 +92,14 @@ class GaussianDiffusion:
             raise ValueError("model was built for a different number of diffusion steps")
         self.norm_factor = norm_factor
         self.loss_weights = loss_weights
+        self.loss_type = loss_type
+        self.p2_loss_weight = p2_loss_weight_table(loss_weights, self.num_timesteps, p2_loss_weight_gamma,
+                                                   p2_loss_weight_k).to(self.device)
         for name in binding.SCHEDULE_NAMES:  # the 12 float32 buffers of ddpm.py:61-99
             setattr(self, name, torch.from_numpy(model.native.schedule(name)).to(self.device))
         self._seed = int(seed)
         self._samples_drawn = 0
+        self._noised = 0   # structures noised so far by q_sample / p_losses with in-kernel draws: their Philox item offset
         self.last_clamped = False
         # ONE device flag word for the lifetime of the object, handed to every fused launch and never reset by the
         # kernels: bit 0 = the +-1000 clamp fired somewhere (ddpm.py:248-250 warns per step), bit 1 = a chain ended with
@@ -78,7 +119,7 @@ class GaussianDiffusion:
         return self
 
     def seed(self, seed: int):
-        self._seed, self._samples_drawn = int(seed), 0
+        self._seed, self._samples_drawn, self._noised = int(seed), 0, 0
 
     @torch.no_grad()
     def p_mean_variance(self, x, t):
@@ -159,3 +200,70 @@ class GaussianDiffusion:
     def sample(self, batch_size):
         """ddpm.py:256-263: (batch_size, N, 3) in Angstrom (x norm_factor), device tensor."""
         return self.p_sample_loop((batch_size, self.num_atoms, self.dims)) * self.norm_factor
+
+    # ---- the forward process and its loss (ddpm.py:164-193, 265-337)
+    @torch.no_grad()
+    def q_mean_variance(self, x_start, t):
+        """ddpm.py:163-171."""
+        mean = extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = extract(1.0 - self.alphas_cumprod, t, x_start.shape)
+        log_variance = extract(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    @torch.no_grad()
+    def assert_normal_kl(self, x_start, t, eps=1e-4):
+        """ddpm.py:173-193: KL(q(x_T | x_0) || N(0, 1)) must be close to zero (enough diffusion steps for data of this
+        scale).  One host read."""
+        assert_center_zero(x_start)
+        mean1, _, logvar1 = self.q_mean_variance(x_start, t)
+        logvar1 = logvar1.squeeze()
+        mean2, logvar2 = torch.zeros_like(mean1), torch.zeros_like(logvar1)
+        meandifsq = ((mean1 - mean2) ** 2).sum(dim=(-2, -1))
+        normal_kl = 0.5 * (-1.0 + logvar2 - logvar1 + torch.exp(logvar1 - logvar2) + meandifsq * torch.exp(-logvar2))
+        kl = normal_kl.abs().max().item()
+        assert kl <= eps, f"Normal KL check at T failed, max value: {kl}"
+
+    def _forward_inputs(self, x_start, t, noise, sample_offset):
+        x_start = x_start.detach().to(self.device, torch.float32).contiguous()
+        t = torch.as_tensor(t).to(self.device)
+        if noise is not None:
+            noise = noise.detach().to(self.device, torch.float32).contiguous()
+        elif sample_offset is None:      # in-kernel draws: this call's structures take the next items of the object's stream
+            sample_offset = self._noised
+            self._noised += x_start.shape[0]
+        return x_start, t, noise, sample_offset or 0
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, sample_offset=None, draw: int = 0):
+        """ddpm.py:265-274 followed by the centring of p_losses (:296), on the device (``dff_q_sample``).  Without
+        ``noise`` the draws come from the object's Philox stream (``seed``): every call advances a counter by its batch, so
+        two calls never share noise; ``sample_offset`` / ``draw`` name the items explicitly instead (no counter)."""
+        x_start, t, noise, off = self._forward_inputs(x_start, t, noise, sample_offset)
+        return self.model.native.q_sample(x_start, t, noise=noise, seed=self._seed, sample_offset=off, draw=draw)
+
+    @torch.no_grad()
+    def p_losses(self, x_start, t, noise=None, sample_offset=None, draw: int = 0, total=None):
+        """ddpm.py:288-315 for objective "pred_noise": the mean over the batch of the per-sample l1 / l2 loss, a 0-d
+        tensor.  Diffusion, score and loss are one library call (``dff_denoise_loss``); noise as in ``q_sample``.
+        ``total`` (float64 CUDA tensor of 2) accumulates (sum of the per-sample losses, batch) on the device."""
+        if self.loss_type not in binding.LOSS_TYPES:
+            raise ValueError(f"invalid loss type {self.loss_type}")
+        x_start, t, noise, off = self._forward_inputs(x_start, t, noise, sample_offset)
+        loss = self.model.native.denoise_loss(x_start, t, noise=noise, seed=self._seed, sample_offset=off, draw=draw,
+                                              loss_type=self.loss_type, total=total)
+        return loss.mean()
+
+    @torch.no_grad()
+    def forward(self, mol, *args, t_diff_range=None, **kwargs):
+        """ddpm.py:317-337: centre ``mol`` (Angstrom), divide by norm_factor, draw one noise level per structure from
+        ``p2_loss_weight``, check the KL to the prior at T - 1, return ``p_losses``.  ``t_diff_range`` is accepted and
+        unused, exactly as in the reference (ddpm.py:317: the trainer passes it, nothing reads it)."""
+        mol = center_zero(mol.detach().to(self.device, torch.float32)) / self.norm_factor
+        assert_center_zero(mol)
+        b, n, d = mol.shape
+        assert n == self.num_atoms and d == self.dims, f"Molecule shape must be {(self.num_atoms, self.dims)}"
+        t = torch.multinomial(self.p2_loss_weight, b, replacement=True).long()
+        self.assert_normal_kl(x_start=mol, t=torch.full((b,), self.num_timesteps - 1, device=self.device, dtype=torch.long))
+        return self.p_losses(mol, t, *args, **kwargs)
+
+    __call__ = forward
