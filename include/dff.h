@@ -355,6 +355,39 @@ int dff_kmeans_step(int device, const double* pts_dev, long long n, int d, const
 int dff_transition_counts(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj,
                           const int32_t* lags_host, int n_lags, int K, uint64_t* counts_dev, void* stream);
 
+/* ---- RMSD between two ensembles: nearest structure and dense matrix (csrc/dff_ensemble.hip) ----
+ * Novelty (samples -> nearest training structure), coverage (held-out structures -> nearest sample) and diversity
+ * (samples -> nearest other sample).  Stateless like dff_struct_*: x_dev (n, n_beads, 3) the queries and y_dev
+ * (m, n_beads, 3) the candidates, fp32 in Angstrom on the device, 4 <= n_beads <= 64; enqueued on `stream`, no
+ * synchronisation on the launch path; n == 0 is a valid no-op.
+ * The distance of a pair is the quantity dff_struct_rmsd computes: the minimum over PROPER rotations (a mirror image does
+ * not match) of the RMSD of the two frames, each centred on its unweighted mean in fp64; the 3 x 3 correlation in fp64
+ * on the matrix cores, the largest eigenvalue of Horn's 4 x 4 key matrix by cyclic Jacobi, sqrt(max(msd, 0)) rounded to
+ * fp32 once.  Every pair is computed (no pruning), and its value does not depend on what else is in the call.
+ * Both calls replace md.rmsd(traj, frame) * 10 of evaluate/evaluators.py:656-662 applied once per candidate frame (with
+ * dff_struct_rmsd: m launches, each reading all n queries again).
+ *
+ * Bytes of device workspace dff_rmsd_nearest needs (one 64-bit key per query of a pass of at most 2^20 queries: bounded
+ * in n, independent of m); -1 on bad arguments. */
+long long dff_rmsd_nearest_workspace_bytes(long long n, long long m, int n_beads);
+/* rmsd_dev[s] = the smallest fp32-rounded RMSD of query s to a candidate, index_dev[s] (may be NULL) that candidate.
+ * Tie rule: among candidates at the same fp32 RMSD the LOWEST index wins.  Non-finite rule: a query with a non-finite
+ * coordinate gets NaN and -1; a candidate with a non-finite coordinate is never nearest; with no usable candidate
+ * (m == 0, all candidates non-finite, or only the excluded one) the result is NaN and -1.
+ * self_first >= 0 declares that query s IS candidate self_first + s: that pair is skipped (diversity, and chunked calls
+ * within one ensemble); -1: no such pair.
+ * Equal BIT FOR BIT to the row minimum and the first argmin of dff_rmsd_matrix (one per-pair routine serves both), and
+ * bit-identical from call to call whatever the split of queries or candidates over workgroups and calls: the reduction is
+ * an integer minimum over the keys (fp32 bits << 32 | index), no floating-point atomics.  m <= 2^31 - 1.
+ * workspace_dev: >= dff_rmsd_nearest_workspace_bytes(n, m, n_beads) bytes. */
+int dff_rmsd_nearest(int device, const float* x_dev, long long n, const float* y_dev, long long m, int n_beads,
+                     long long self_first, float* rmsd_dev, long long* index_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+/* The dense block for small problems (clustering, tests): out_dev[s * m + r] = RMSD of query s to candidate r, NaN where
+ * either frame has a non-finite coordinate.  n * m <= 2^28 (DFF_EINVAL beyond). */
+int dff_rmsd_matrix(int device, const float* x_dev, long long n, const float* y_dev, long long m, int n_beads,
+                    float* out_dev, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

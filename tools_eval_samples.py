@@ -8,6 +8,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--tica-fit-data TRAJ.pt [--lagtime 100]]
                                  [--transitions [--traj-lengths L | --parallel-sim P] [--lagtimes 1,10,100]
                                   [--n-clusters K --centers-fit-data TRAJ.pt]]
+                                 [--coverage REF.pt [--rmsd-thresholds 1,2,4] [--coverage-subsample K]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -18,6 +19,12 @@ Langevin samples: state assignments in the plane of MOL's TICA model, transition
 Without --traj-lengths / --parallel-sim the samples count as ONE trajectory, as in the notebook; --parallel-sim P splits
 them into P simulations of equal length (sample.py's simulation-major output), --traj-lengths L into runs of L frames.
 The states are the notebook's presets for MOL, or are fitted by k-means (--n-clusters K) on --centers-fit-data.
+
+--coverage REF.pt adds, under "coverage", the nearest-structure RMSD statistics of the samples against the ensemble REF.pt
+((m, N, 3) Angstrom; EnsembleCoverageEvaluator): novelty / precision (samples -> nearest structure of REF), coverage /
+recall (REF -> nearest sample), diversity / duplicates (samples -> nearest other sample), at the thresholds (Angstrom) of
+--rmsd-thresholds.  Every pair is superposed: n * m + n * n optimal rotations.  --coverage-subsample K keeps at most K
+evenly spaced frames of each ensemble.
 """
 import argparse
 import json
@@ -53,7 +60,32 @@ def transitions(a, x):
             "timescales": [[None if not np.isfinite(v) else float(v) for v in t] for t in r["timescales"]]}
 
 
-def main():
+def rmsd_thresholds(text):
+    """"1,2,4" -> (1.0, 2.0, 4.0): positive, comma-separated"""
+    try:
+        t = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma-separated list of numbers: {text!r}")
+    if not t or min(t) <= 0:
+        raise argparse.ArgumentTypeError("thresholds must be positive")
+    return t
+
+
+def subsample(x, k):
+    """at most k evenly spaced frames of x, the first and the last among them (all of x when k is None or >= len(x))"""
+    if k is None or k >= len(x):
+        return x
+    return x[torch.linspace(0, len(x) - 1, k).round().long()]
+
+
+def coverage(a, x):
+    ref = torch.load(a.coverage, map_location="cpu").float()
+    ev = evaluate.EnsembleCoverageEvaluator(subsample(ref, a.coverage_subsample), a.mol.lower(), a.rmsd_thresholds,
+                                            device=a.device)
+    return ev.eval(subsample(x, a.coverage_subsample))
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("samples", help="sample-{mode}.pt written by sample.py")
     ap.add_argument("mol", help="molecule name as sample.py's --mol (alanine_dipeptide_*, chignolin, ...)")
@@ -73,8 +105,21 @@ def main():
     ap.add_argument("--n-clusters", type=int, default=None, help="fit this many state centres on --centers-fit-data")
     ap.add_argument("--centers-fit-data", default=None, help="structures (.pt, (n, N, 3) Angstrom) to fit the state "
                                                              "centres on instead of the presets")
+    ap.add_argument("--coverage", default=None, metavar="REF.pt",
+                    help="ensemble (.pt, (m, N, 3) Angstrom) to report novelty / coverage / diversity against")
+    ap.add_argument("--rmsd-thresholds", type=rmsd_thresholds, default=(1.0, 2.0, 4.0),
+                    help="comma-separated RMSD thresholds in Angstrom (with --coverage)")
+    ap.add_argument("--coverage-subsample", type=int, default=None, metavar="K",
+                    help="keep at most K evenly spaced frames of each ensemble (with --coverage)")
     ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
+    if a.coverage_subsample is not None and a.coverage_subsample < 1:
+        ap.error("--coverage-subsample must be >= 1")
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -96,6 +141,8 @@ def main():
         res["Contact BCE"] = float(mean)
     if a.transitions:
         res["Transitions"] = transitions(a, x)
+    if a.coverage:
+        res["coverage"] = coverage(a, x)
     print(json.dumps(res))
 
 

@@ -12,7 +12,8 @@ from .sampling import SamplerWrapper, num_to_groups, sample_from_model  # noqa: 
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",
-           "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator", "eval_loss", "loss_profile"]
+           "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator", "eval_loss", "loss_profile",
+           "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -25,7 +26,7 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
     if name in ("LangevinDiffusion", "ForcesWrapper"):
         from . import langevin
         return getattr(langevin, name)
-    if name in ("KMeans", "StateTransitionEvaluator"):
+    if name in ("KMeans", "StateTransitionEvaluator", "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

@@ -87,6 +87,10 @@ SYMBOLS = {
     "dff_kmeans_step": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                   _P]),
     "dff_transition_counts": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "dff_rmsd_nearest_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int]),
+    "dff_rmsd_nearest": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_longlong, _P, _P, _P,
+                                   C.c_size_t, _P]),
+    "dff_rmsd_matrix": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_longlong, C.c_int, _P, _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -646,4 +650,49 @@ def transition_counts(labels, lengths, lagtimes, n_states: int):
     _check(lib, lib.dff_transition_counts(labels.device.index, _ptr(labels), int(labels.numel()),
                                           ln.ctypes.data_as(C.c_void_p), int(ln.size), lg.ctypes.data_as(C.c_void_p),
                                           int(lg.size), K, _ptr(out), _stream(labels)), "dff_transition_counts")
+    return out
+
+
+# ---- RMSD between two ensembles (dff_rmsd_nearest, dff_rmsd_matrix) ----
+def _two_ensembles(x, y):
+    x, n, N = _coords(x)
+    y, m, Ny = _coords(y)
+    if y.device != x.device:
+        raise ValueError(f"queries are on {x.device}, candidates on {y.device}")
+    if Ny != N:
+        raise ValueError(f"queries have {N} beads, candidates {Ny}")
+    return x, n, y, m, N
+
+
+def rmsd_nearest_workspace_bytes(n: int, m: int, n_beads: int) -> int:
+    return _workspace_bytes("dff_rmsd_nearest_workspace_bytes", int(n), int(m), int(n_beads))
+
+
+def rmsd_nearest(x, y, self_first: int = -1, workspace=None):
+    """For every frame of x (n, N, 3) the RMSD (Angstrom, optimal proper rotation) to its nearest frame of y (m, N, 3)
+    and that frame's index -> (float32 CUDA tensor (n,), int64 CUDA tensor (n,)); NaN / -1 for a query with a non-finite
+    coordinate or without a usable candidate; the lowest index among equal RMSDs.  self_first >= 0: query s is candidate
+    self_first + s, and that pair is skipped.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    x, n, y, m, N = _two_ensembles(x, y)
+    need = rmsd_nearest_workspace_bytes(n, m, N)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    rmsd = torch.empty(n, dtype=torch.float32, device=x.device)
+    index = torch.empty(n, dtype=torch.int64, device=x.device)
+    _check(lib, lib.dff_rmsd_nearest(x.device.index, _ptr(x), n, _ptr(y), m, N, int(self_first), _ptr(rmsd), _ptr(index),
+                                     _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(x)),
+           "dff_rmsd_nearest")
+    return rmsd, index
+
+
+def rmsd_matrix(x, y):
+    """RMSD (Angstrom, optimal proper rotation) of every frame of x (n, N, 3) to every frame of y (m, N, 3) -> float32
+    CUDA tensor (n, m), NaN where either frame has a non-finite coordinate.  n * m <= 2^28."""
+    import torch
+    lib = load_library()
+    x, n, y, m, N = _two_ensembles(x, y)
+    out = torch.empty((n, m), dtype=torch.float32, device=x.device)
+    _check(lib, lib.dff_rmsd_matrix(x.device.index, _ptr(x), n, _ptr(y), m, N, _ptr(out), _stream(x)), "dff_rmsd_matrix")
     return out

@@ -1,12 +1,13 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 
 #include "dff_pwd.hip"
 #include "dff_struct.hip"
 #include "dff_tica.hip"
 #include "dff_states.hip"
+#include "dff_ensemble.hip"
 
 // ---------------------------------------------------------------------------------------------
 // PWD histograms (dff_pwd.hip)
@@ -472,4 +473,76 @@ extern "C" int dff_transition_counts(int device, const int32_t* labels, long lon
         }
     }
     return runs.n ? launch(runs) : DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// RMSD between two ensembles: dense matrix and nearest candidate (dff_ensemble.hip)
+// ---------------------------------------------------------------------------------------------
+static int ens_check_shape(long long n, long long m, int N, const char* what) {
+    if (n < 0 || m < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    if (m > 0x7fffffffLL) return fail(DFF_EINVAL, "%s: more than 2^31 - 1 candidates (the index half of the key is 32 bits)", what);
+    return DFF_OK;
+}
+
+// One launch over queries x (n) and candidates y (m), both > 0.  The grid follows from the shapes alone -- and the result
+// does not depend on it: one workgroup per (32-candidate tile, slice of the query tiles), enough slices to reach
+// DFF_ENS_WGS workgroups, never more than there are groups of four query tiles.
+template <bool NEAREST>
+static int ens_launch(hipStream_t stream, const float* x, long long n, const float* y, long long m, int N,
+                      long long self_first, float* out, unsigned long long* keys) {
+    const long long nct = (m + DFF_ENS_TC - 1) / DFF_ENS_TC;
+    const long long nq4 = ((n + DFF_ENS_TQ - 1) / DFF_ENS_TQ + 3) / 4;
+    long long qsplit = (DFF_ENS_WGS + nct - 1) / nct;
+    if (qsplit > nq4) qsplit = nq4;
+    hipLaunchKernelGGL(dff_ens_rmsd_kernel<NEAREST>, dim3((unsigned)(nct * qsplit)), dim3(DFF_ENS_THREADS),
+                       (unsigned)(ens_lds_doubles(ens_np(N)) * sizeof(double)), stream, x, n, y, m, N, (int)qsplit, self_first,
+                       out, keys);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" long long dff_rmsd_nearest_workspace_bytes(long long n, long long m, int n_beads) {
+    if (ens_check_shape(n, m, n_beads, "rmsd_nearest_workspace_bytes")) return -1;
+    return (n < DFF_ENS_QCHUNK ? n : DFF_ENS_QCHUNK) * (long long)sizeof(unsigned long long);
+}
+
+extern "C" int dff_rmsd_nearest(int device, const float* x, long long n, const float* y, long long m, int N,
+                                long long self_first, float* rmsd, long long* index, void* workspace,
+                                size_t workspace_bytes, void* stream_) {
+    int rc = ens_check_shape(n, m, N, "rmsd_nearest");
+    if (rc) return rc;
+    if ((!x && n > 0) || (!y && m > 0)) return fail(DFF_EINVAL, "rmsd_nearest: null frames");
+    if (!rmsd && n > 0) return fail(DFF_EINVAL, "rmsd_nearest: null output");
+    if (self_first < -1) return fail(DFF_EINVAL, "rmsd_nearest: self_first must be -1 or a candidate index");
+    const long long need = dff_rmsd_nearest_workspace_bytes(n, m, N);
+    if (need > 0 && (!workspace || (long long)workspace_bytes < need))
+        return fail(DFF_EINVAL, "rmsd_nearest: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if (n == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    unsigned long long* keys = (unsigned long long*)workspace;
+    for (long long o = 0; o < n; o += DFF_ENS_QCHUNK) {
+        const long long c = n - o < DFF_ENS_QCHUNK ? n - o : DFF_ENS_QCHUNK;
+        HIPCHK(hipMemsetAsync(keys, 0xff, (size_t)c * sizeof(unsigned long long), stream));
+        if (m > 0 && (rc = ens_launch<true>(stream, x + o * 3 * N, c, y, m, N, self_first >= 0 ? self_first + o : -1,
+                                            nullptr, keys)))
+            return rc;
+        hipLaunchKernelGGL(dff_ens_finish_kernel, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, stream, keys, c, rmsd + o,
+                           index ? index + o : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+extern "C" int dff_rmsd_matrix(int device, const float* x, long long n, const float* y, long long m, int N, float* out,
+                               void* stream_) {
+    int rc = ens_check_shape(n, m, N, "rmsd_matrix");
+    if (rc) return rc;
+    if ((!x && n > 0) || (!y && m > 0)) return fail(DFF_EINVAL, "rmsd_matrix: null frames");
+    if (n > 0 && m > (1LL << 28) / n) return fail(DFF_EINVAL, "rmsd_matrix: n * m = %lld x %lld exceeds 2^28 entries", n, m);
+    if (n == 0 || m == 0) return DFF_OK;
+    if (!out) return fail(DFF_EINVAL, "rmsd_matrix: null output");
+    ON_DEVICE(device);
+    return ens_launch<false>((hipStream_t)stream_, x, n, y, m, N, -1, out, nullptr);
 }

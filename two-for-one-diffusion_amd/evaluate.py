@@ -929,3 +929,146 @@ class StateTransitionEvaluator:
         return {"assignments": lab, "populations": pop / max(pop.sum(), 1.0), "count_matrices": counts,
                 "transition_matrices": T, "lagtimes": lagtimes,
                 "timescales": [msm_timescales(T[i], lag) for i, lag in enumerate(lagtimes)]}
+
+
+# =====================================================================================================
+# Novelty, coverage and diversity: nearest-structure RMSD between two ensembles (dff_rmsd_nearest / dff_rmsd_matrix,
+# csrc/dff_ensemble.hip).  The reference has no counterpart: its only RMSD is md.rmsd to ONE folded structure
+# (evaluators.py:656-662); this applies the same distance between every sample and every reference frame.
+# =====================================================================================================
+NEAREST_CHUNK = 1 << 18        # queries per dff_rmsd_nearest call of nearest_rmsd (12 N bytes of fp32 frames each)
+
+
+def nearest_rmsd(xyz, refs, *, exclude_self=False, chunk=None, device="cuda:0"):
+    """For every structure of xyz (n, N, 3) the RMSD (Angstrom, optimal proper rotation) to its nearest structure of refs
+    (m, N, 3), and that structure's index -> (rmsd float32 (n,), index int64 (n,)), torch tensors on `device`.  NaN / -1
+    for a structure with a non-finite coordinate or without a usable candidate; non-finite candidates are never nearest;
+    the lowest index wins among equal RMSDs.  The queries go to the device `chunk` at a time (default NEAREST_CHUNK), refs
+    once; the result does not depend on `chunk`.  exclude_self=True (xyz is refs, or the same shape: the same ensemble)
+    leaves out the pair of a structure with itself: the nearest OTHER structure."""
+    dev = torch.device(device)
+    same = xyz is refs
+    y = _frames(refs, dev)
+    xs = y
+    if not same:
+        xs = torch.as_tensor(xyz)
+        if xs.dim() != 3 or xs.shape[-1] != 3:
+            raise ValueError("structures must be (n, n_beads, 3)")
+        if int(xs.shape[1]) != int(y.shape[1]):
+            raise ValueError(f"xyz has {int(xs.shape[1])} beads, refs {int(y.shape[1])}")
+        if exclude_self and tuple(xs.shape) != tuple(y.shape):
+            raise ValueError("exclude_self needs xyz and refs to be the same ensemble (xyz is refs, or equal shapes)")
+    chunk = NEAREST_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    n = len(xs)
+    rmsd = torch.empty(n, dtype=torch.float32, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    ws = None
+    for o in range(0, n, chunk):
+        xc = _frames(xs[o:o + chunk], dev)
+        if ws is None:
+            ws = torch.empty(max(binding.rmsd_nearest_workspace_bytes(len(xc), len(y), int(y.shape[1])), 1),
+                             dtype=torch.uint8, device=dev)
+        r, i = binding.rmsd_nearest(xc, y, self_first=o if exclude_self else -1, workspace=ws)
+        rmsd[o:o + len(xc)] = r
+        index[o:o + len(xc)] = i
+    return rmsd, index
+
+
+def rmsd_matrix(a, b, *, device="cuda:0"):
+    """RMSD (Angstrom, optimal proper rotation) between every structure of a (n, N, 3) and every structure of b (m, N, 3)
+    -> float32 tensor (n, m) on `device`; for small sets (n * m <= 2^28).  nearest_rmsd is its row minimum, bit for bit."""
+    dev = torch.device(device)
+    return binding.rmsd_matrix(_frames(a, dev), _frames(b, dev))
+
+
+def nearest_summary(d, prefix, stats=("mean", "median")):
+    """{prefix_rmsd_<stat>: float} over the entries of the nearest-RMSD tensor d (n,) that are not NaN (NaN = a frame left
+    out); NaN when none is left.  stats out of mean, median (the mean of the two middle values for an even count, as
+    numpy), min, max.  Reduced where d lives: only scalars are read."""
+    v = d[~torch.isnan(d)].double()
+    k = int(v.numel())
+    out = {}
+    for s in stats:
+        if k == 0:
+            val = float("nan")
+        elif s == "median":
+            sv = torch.sort(v).values
+            val = float((sv[(k - 1) // 2] + sv[k // 2]) / 2)
+        else:
+            val = float(getattr(v, s)())
+        out[f"{prefix}_rmsd_{s}"] = val
+    return out
+
+
+def share_within(d, delta, inclusive=True):
+    """Share of the non-NaN entries of d at most (inclusive) or strictly less than (not inclusive) delta; NaN when every
+    entry is NaN."""
+    ok = ~torch.isnan(d)
+    k = int(ok.sum())
+    if k == 0:
+        return float("nan")
+    hit = (d <= delta) if inclusive else (d < delta)          # NaN compares false
+    return float(hit.sum()) / k
+
+
+def _count_nonfinite(x):
+    return int((~torch.isfinite(x).all(dim=2).all(dim=1)).sum())
+
+
+class EnsembleCoverageEvaluator:
+    """How a sampled ensemble sits against a reference ensemble, by nearest-structure RMSD on the GPU.
+
+    ref_data (m, N, 3) in Angstrom: the training structures (for novelty) or a held-out set (for coverage); it is
+    uploaded once.  eval(samples) returns a plain dict of floats, d in Angstrom and delta running over `thresholds`:
+      novelty_rmsd_{mean,median,min}    samples -> their nearest reference structure
+      precision@delta                   share of samples with a reference structure within delta (d <= delta)
+      coverage_rmsd_{mean,median,max}   reference structures -> their nearest sample
+      recall@delta                      share of reference structures with a sample within delta (d <= delta)
+      diversity_rmsd_{mean,median}      samples -> their nearest OTHER sample
+      duplicates@delta_min              share of samples with another sample closer than the smallest threshold (d < delta_min)
+      samples_nonfinite, refs_nonfinite frames with a non-finite coordinate: left out of every statistic on their side
+                                        and never anybody's nearest structure
+    Shares and means are over the frames that are left.  Without the HIP library: DffLibraryError."""
+
+    def __init__(self, ref_data, mol_name="", thresholds=(1.0, 2.0, 4.0), *, chunk=None, device="cuda:0"):
+        self.mol_name = mol_name
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not self.thresholds or min(self.thresholds) <= 0:
+            raise ValueError("EnsembleCoverageEvaluator: thresholds must be positive")
+        self.chunk = chunk
+        self.device = torch.device(device)
+        binding.load_library()
+        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+            ref_data = ref_data[:][0]
+        self.refs = _frames(ref_data, self.device)
+        self.refs_nonfinite = _count_nonfinite(self.refs)
+
+    def nearest(self, samples):
+        """The three nearest-RMSD tensors on the device: {"novelty" (n,), "coverage" (m,), "diversity" (n,)}."""
+        x = _frames(samples, self.device)
+        if x.shape[1] != self.refs.shape[1]:
+            raise ValueError(f"samples have {int(x.shape[1])} beads, the reference ensemble {int(self.refs.shape[1])}")
+        kw = dict(chunk=self.chunk, device=self.device)
+        return x, {"novelty": nearest_rmsd(x, self.refs, **kw)[0], "coverage": nearest_rmsd(self.refs, x, **kw)[0],
+                   "diversity": nearest_rmsd(x, x, exclude_self=True, **kw)[0]}
+
+    def summarize(self, novelty, coverage, diversity, samples_nonfinite=0, refs_nonfinite=0):
+        """eval()'s dict from the three nearest-RMSD tensors (NaN = a frame left out)."""
+        out = nearest_summary(novelty, "novelty", ("mean", "median", "min"))
+        for t in self.thresholds:
+            out[f"precision@{t:g}"] = share_within(novelty, t)
+        out.update(nearest_summary(coverage, "coverage", ("mean", "median", "max")))
+        for t in self.thresholds:
+            out[f"recall@{t:g}"] = share_within(coverage, t)
+        out.update(nearest_summary(diversity, "diversity", ("mean", "median")))
+        tmin = min(self.thresholds)
+        out[f"duplicates@{tmin:g}"] = share_within(diversity, tmin, inclusive=False)
+        out["samples_nonfinite"] = float(samples_nonfinite)
+        out["refs_nonfinite"] = float(refs_nonfinite)
+        return out
+
+    def eval(self, samples):
+        x, d = self.nearest(samples)
+        return self.summarize(d["novelty"], d["coverage"], d["diversity"], _count_nonfinite(x), self.refs_nonfinite)
