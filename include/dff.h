@@ -11,7 +11,17 @@
  * Conventions
  *   - every *_dev pointer is device memory on the model's GPU, fp32, row-major, owned by the
  *     caller (e.g. torch-ROCm tensors); the library owns only its packed weights and scratch;
- *   - calls enqueue on `stream` (a hipStream_t, NULL = default stream) and do not synchronise;
+ *   - calls enqueue on `stream` (a hipStream_t, NULL = default stream) and do not synchronise: every kernel, memset and
+ *     copy of a call is ordered on `stream` and on no other, and the call returns without waiting for the device
+ *     (tests/test_stream_order.py holds every entry point to both).  The calls that DO block the host say so below:
+ *     dff_model_create, the status calls, the dff_debug_* calls, and the FIRST ("cold") dff_score / dff_langevin_run /
+ *     dff_ddpm_run / dff_denoise_loss of a model at a new batch size, group size, kernel variant or noise level -- it grows the
+ *     model's scratch (hipFree / hipMalloc) and, in the sampling loops, builds the layer-0 table of that noise level (allocations,
+ *     a host-to-device copy, hipStreamSynchronize(stream) between its chunks).  The identical call repeated never blocks;
+ *   - ONE model on TWO streams at once is not supported: its scratch stash, layer-0 tables and flag words are shared by all
+ *     of its launches, and only the order of one stream keeps them apart.  Different models, and the stateless dff_pwd_* /
+ *     dff_struct_* / dff_tica_* / dff_kmeans_* / dff_transition_counts / dff_rmsd_* calls, may run on different streams at
+ *     once (the caller's workspace must not be shared between them);
  *   - return 0 on success, a DFF_E* / hipError_t-derived code otherwise; dff_last_error()
  *     gives the message.  No exceptions cross the ABI;
  *   - one handle per device; not thread-safe per handle (the reference is single-threaded per
