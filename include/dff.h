@@ -236,6 +236,31 @@ int dff_debug_pair_status(dff_model* m, int* status);
 int dff_debug_poke_status(dff_model* m, unsigned word);
 /* Name of the kernel the last call launched, grid size and dynamic LDS bytes. */
 int dff_last_launch(const dff_model* m, const char** kernel_name, int* grid, int* lds_bytes);
+/* Everything kernel selection reads of a model besides its dff_config: the engines weight preparation chose, the device's
+ * CU count, the debug knobs above, the sticky word as the host last read it, and the two environment opt-ins. */
+typedef struct {
+    int32_t split, small_split, fold_kv;   /* fp16 images exist; ... also for the <= 16-row kernel; k / v folded (hidden 64) */
+    int32_t n_cus;                         /* hipDeviceAttributeMultiprocessorCount */
+    int32_t group_override, small_waves, max_wgs, force_generic, l0_off, pair_off;   /* dff_set_group, dff_debug_* */
+    int32_t sticky;                        /* dff_model_status word the host has seen */
+    int32_t small_pair, small_h96;         /* DFF_SMALL_PAIR=1 (read at every launch), DFF_SMALL_H96=1 (once per process) */
+} dff_dispatch;
+/* What a call of `mode` (0 dff_score, 1 dff_langevin_run, 2 dff_ddpm_run) over `batch` proteins launches. */
+typedef struct {
+    const char* kernel;                    /* static string, as dff_last_launch reports it */
+    int32_t G;                             /* proteins per workgroup */
+    int32_t workgroups, launches;          /* in all, over `launches` consecutive kernel launches */
+    int32_t last_grid;                     /* workgroups of the last launch: the grid dff_last_launch reports */
+    int32_t lds_bytes, threads, pair;      /* dynamic LDS, threads per workgroup, 1: two workgroups per protein */
+    int32_t table;                         /* layer-0 table: 0 none, 1 one entry (Langevin), 2 one entry per level (DDPM) */
+    const char* table_kernel;              /* the kernel that builds it ("" when table == 0) */
+} dff_launch_plan;
+/* Host only, for tests: the model's dff_dispatch as the next launch would see it (the environment opt-ins read now).
+ * No device access, no synchronisation. */
+int dff_debug_dispatch(const dff_model* m, dff_dispatch* out);
+/* Host only, for tests, no GPU needed: the launch plan of a model of this config and dispatch -- the function every
+ * launch goes through, without a handle.  cfg is checked as dff_model_create checks it. */
+int dff_debug_plan_launch(const dff_config* cfg, const dff_dispatch* dispatch, int mode, int batch, dff_launch_plan* out);
 /* Run one MFMA GEMM stage out(M,Nout) = A(M,K) W(K,Nout) through the same device routine and
  * weight packing the score kernel uses (M <= 64; K, Nout multiples of 16).  Host pointers. */
 int dff_debug_gemm(int device, const float* A_host, const float* W_host, int M, int K, int Nout,

@@ -43,6 +43,18 @@ class DffLangevinParams(C.Structure):
                 ("masses", C.c_float * DFF_MAX_BEADS)]
 
 
+class DffDispatch(C.Structure):
+    """dff_dispatch: what kernel selection reads of a model besides its config (Model.dispatch, plan_launch)."""
+    _fields_ = [(n, C.c_int32) for n in ("split", "small_split", "fold_kv", "n_cus", "group_override", "small_waves",
+                                         "max_wgs", "force_generic", "l0_off", "pair_off", "sticky", "small_pair",
+                                         "small_h96")]
+
+
+class DffLaunchPlan(C.Structure):
+    _fields_ = [("kernel", C.c_char_p)] + [(n, C.c_int32) for n in ("G", "workgroups", "launches", "last_grid", "lds_bytes",
+                                                                     "threads", "pair", "table")] + [("table_kernel", C.c_char_p)]
+
+
 # every symbol include/dff.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -65,6 +77,9 @@ SYMBOLS = {
     "dff_debug_l0_table": (C.c_int, [_P, C.c_int]),
     "dff_debug_max_workgroups": (C.c_int, [_P, C.c_int]),
     "dff_last_launch": (C.c_int, [_P, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dff_debug_dispatch": (C.c_int, [_P, C.POINTER(DffDispatch)]),
+    "dff_debug_plan_launch": (C.c_int, [C.POINTER(DffConfig), C.POINTER(DffDispatch), C.c_int, C.c_int,
+                                        C.POINTER(DffLaunchPlan)]),
     "dff_debug_gemm": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "dff_debug_stash": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
     "dff_debug_profile": (C.c_int, [_P, C.c_int]),
@@ -245,6 +260,12 @@ class Model:
         _check(self.lib, self.lib.dff_last_launch(self.handle, C.byref(name), C.byref(grid), C.byref(lds)), "dff_last_launch")
         return (name.value or b"").decode(), grid.value, lds.value
 
+    def dispatch(self) -> dict:
+        """What kernel selection reads of this model, as the next launch would see it (dff_debug_dispatch; host only)."""
+        d = DffDispatch()
+        _check(self.lib, self.lib.dff_debug_dispatch(self.handle, C.byref(d)), "dff_debug_dispatch")
+        return {n: getattr(d, n) for n, _ in DffDispatch._fields_}
+
     # ---- the three entry points
     def score(self, x, tnorm, return_energy=False):
         import torch
@@ -370,6 +391,16 @@ class Model:
         rc = self.lib.dff_debug_stash(self.handle, b, layer, code, out.ctypes.data_as(C.c_void_p), out.size)
         _check(self.lib, rc, "dff_debug_stash")
         return out
+
+
+def plan_launch(cfg: DffConfig, dispatch: dict, mode: int, batch: int) -> dict:
+    """The launch plan of a call of `mode` (0 score, 1 Langevin, 2 DDPM) over `batch` proteins for a model of config `cfg`
+    and dispatch `dispatch` (the fields of DffDispatch; missing ones are 0): dff_debug_plan_launch, host only, no GPU."""
+    lib = load_library()
+    plan = DffLaunchPlan()
+    _check(lib, lib.dff_debug_plan_launch(C.byref(cfg), C.byref(DffDispatch(**dispatch)), int(mode), int(batch), C.byref(plan)),
+           "dff_debug_plan_launch")
+    return {n: v.decode() if isinstance(v, bytes) else v for n, v in ((n, getattr(plan, n)) for n, _ in DffLaunchPlan._fields_)}
 
 
 def debug_gemm(A: np.ndarray, W: np.ndarray, device: int = 0) -> np.ndarray:
