@@ -423,6 +423,44 @@ int dff_rmsd_nearest(int device, const float* x_dev, long long n, const float* y
 int dff_rmsd_matrix(int device, const float* x_dev, long long n, const float* y_dev, long long m, int n_beads,
                     float* out_dev, void* stream);
 
+/* ---- superposition on a reference: rotations, aligned frames, mean-structure and RMSF sums (csrc/dff_superpose.hip) ----
+ * The rotation that every RMSD call above solves for and discards.  Stateless like dff_struct_*: x_dev (n, n_beads, 3)
+ * and ref_dev (n_beads, 3) fp32 in Angstrom on the device, 4 <= n_beads <= 64, frames independent; enqueued on `stream`
+ * only, no synchronisation on the launch path; bad arguments are refused on the host before any device call.
+ * R of a frame is the PROPER rotation (det R = +1: a mirror image is not matched) that minimises
+ * sum_b |R a_b - r_b|^2, a_b = x_b - c_x and r_b = ref_b - c_ref the beads relative to the unweighted centroids; fp64
+ * throughout: Horn's 4 x 4 key matrix as in dff_struct_rmsd, cyclic Jacobi with accumulated eigenvectors, R from the
+ * formula quadratic in the unit quaternion (a half turn, q0 = 0, is an ordinary input).
+ * Replaces traj.superpose(traj, 0), datasets/dataset_utils_empty.py:319-321 (ref_dev = frame 0).
+ *
+ * Bytes of device workspace dff_superpose needs for n frames when it accumulates statistics (one slice of 4 N + 1 doubles
+ * per workgroup, at most 4096 workgroups: bounded in n); -1 on bad arguments. */
+long long dff_superpose_workspace_bytes(long long n, int n_beads);
+/* Every output may be NULL.
+ *   aligned_dev (n, N, 3) fp32   R a_b + c_ref, rounded to fp32 once: frames land ON THE REFERENCE'S CENTROID, as mdtraj's
+ *                                superpose leaves them.  In place: aligned_dev == x_dev (exactly the same pointer) is
+ *                                supported -- a tile of 64 frames is read completely before any of it is written, and
+ *                                tiles are disjoint; a PARTIAL overlap of the two arrays is undefined.
+ *   rot_dev (n, 9) fp64          R, row-major.
+ *   rmsd_dev (n) fp32            the quantity dff_struct_rmsd returns.
+ *   dsum_dev (N, 3) fp64, dsq_dev (N) fp64, count_dev (1) uint64 -- OVERWRITTEN by the call, over the finite frames, with
+ *                                d_b = (R a_b + c_ref) - ref_b in fp64, BEFORE the fp32 rounding of aligned_dev:
+ *                                dsum = sum d_b, dsq = sum |d_b|^2, count = the number of finite frames.
+ *                                mean structure = ref + dsum / count; RMSF_b^2 = dsq_b / count - |dsum_b / count|^2.
+ * Non-finite rule: a frame with any non-finite coordinate gets NaN in all its aligned / rot / rmsd entries and takes part
+ * in no sum; a reference with a non-finite coordinate makes every frame such a frame (count = 0).  Nothing is read back.
+ * Degenerate rule: a frame whose key matrix is zero (all beads coincident: R = I) or whose largest eigenvalue is
+ * degenerate (collinear frame or reference) gets A maximiser: finite, a proper rotation, reaching the minimal RMSD -- but
+ * one of a continuum, not comparable entry by entry with another solver's.
+ * n == 0 is a valid no-op that zeroes dsum / dsq / count.  With the three statistics NULL no workspace is needed;
+ * otherwise workspace_dev: >= dff_superpose_workspace_bytes(n, n_beads) bytes, 8-byte aligned, contents irrelevant.
+ * Deterministic: per-workgroup partials in the workspace, added in a fixed order by a second stage, no floating-point
+ * atomics -- bit-identical from call to call with the same arguments (the rule of dff_kmeans_step). */
+int dff_superpose(int device, const float* x_dev, long long n, int n_beads, const float* ref_dev,
+                  float* aligned_dev, double* rot_dev, float* rmsd_dev,
+                  double* dsum_dev, double* dsq_dev, uint64_t* count_dev,
+                  void* workspace_dev, size_t workspace_bytes, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -9,6 +9,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--transitions [--traj-lengths L | --parallel-sim P] [--lagtimes 1,10,100]
                                   [--n-clusters K --centers-fit-data TRAJ.pt]]
                                  [--coverage REF.pt [--rmsd-thresholds 1,2,4] [--coverage-subsample K]]
+                                 [--flexibility HELDOUT.pt] [--write-aligned OUT.pt]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -25,6 +26,11 @@ The states are the notebook's presets for MOL, or are fitted by k-means (--n-clu
 recall (REF -> nearest sample), diversity / duplicates (samples -> nearest other sample), at the thresholds (Angstrom) of
 --rmsd-thresholds.  Every pair is superposed: n * m + n * n optimal rotations.  --coverage-subsample K keeps at most K
 evenly spaced frames of each ensemble.
+
+--flexibility HELDOUT.pt adds, under "flexibility", the per-bead RMSF comparison of the samples with the ensemble HELDOUT.pt
+((m, N, 3) Angstrom; FlexibilityEvaluator): both ensembles superposed on the folded structure of --folded-pdb when given,
+otherwise on HELDOUT's mean structure.  --write-aligned OUT.pt saves the samples superposed on the folded structure of
+--folded-pdb ((n, N, 3) float32, on the folded structure's centroid; NaN rows for non-finite samples).
 """
 import argparse
 import json
@@ -85,6 +91,20 @@ def coverage(a, x):
     return ev.eval(subsample(x, a.coverage_subsample))
 
 
+def flexibility(a, x):
+    ref = torch.load(a.flexibility, map_location="cpu").float()
+    ev = evaluate.FlexibilityEvaluator(ref, a.mol.lower(), a.folded_pdb, device=a.device)
+    res = ev.eval(x)
+    res["rmsf_samples"] = ev.profiles["samples"]["rmsf"].tolist()
+    res["rmsf_refs"] = ev.profiles["refs"]["rmsf"].tolist()
+    return res
+
+
+def write_aligned(a, x):
+    folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
+    torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("samples", help="sample-{mode}.pt written by sample.py")
@@ -111,6 +131,10 @@ def build_parser():
                     help="comma-separated RMSD thresholds in Angstrom (with --coverage)")
     ap.add_argument("--coverage-subsample", type=int, default=None, metavar="K",
                     help="keep at most K evenly spaced frames of each ensemble (with --coverage)")
+    ap.add_argument("--flexibility", default=None, metavar="HELDOUT.pt",
+                    help="ensemble (.pt, (m, N, 3) Angstrom) to compare the per-bead RMSF and the mean structure with")
+    ap.add_argument("--write-aligned", default=None, metavar="OUT.pt",
+                    help="save the samples superposed on the folded structure (needs --folded-pdb)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -120,6 +144,8 @@ def main():
     a = ap.parse_args()
     if a.coverage_subsample is not None and a.coverage_subsample < 1:
         ap.error("--coverage-subsample must be >= 1")
+    if a.write_aligned and not a.folded_pdb:
+        ap.error("--write-aligned needs --folded-pdb")
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -143,6 +169,10 @@ def main():
         res["Transitions"] = transitions(a, x)
     if a.coverage:
         res["coverage"] = coverage(a, x)
+    if a.flexibility:
+        res["flexibility"] = flexibility(a, x)
+    if a.write_aligned:
+        write_aligned(a, x)
     print(json.dumps(res))
 
 

@@ -14,6 +14,7 @@ __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_libr
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",
            "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator", "eval_loss", "loss_profile",
            "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"]
+__all__ += ["superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -27,6 +28,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import langevin
         return getattr(langevin, name)
     if name in ("KMeans", "StateTransitionEvaluator", "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

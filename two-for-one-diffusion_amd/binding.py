@@ -106,6 +106,8 @@ SYMBOLS = {
     "dff_rmsd_nearest": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_longlong, _P, _P, _P,
                                    C.c_size_t, _P]),
     "dff_rmsd_matrix": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_longlong, C.c_int, _P, _P]),
+    "dff_superpose_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "dff_superpose": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -727,3 +729,46 @@ def rmsd_matrix(x, y):
     out = torch.empty((n, m), dtype=torch.float32, device=x.device)
     _check(lib, lib.dff_rmsd_matrix(x.device.index, _ptr(x), n, _ptr(y), m, N, _ptr(out), _stream(x)), "dff_rmsd_matrix")
     return out
+
+
+# ---- superposition on a reference (dff_superpose) ----
+def superpose_workspace_bytes(n: int, n_beads: int) -> int:
+    return _workspace_bytes("dff_superpose_workspace_bytes", int(n), int(n_beads))
+
+
+def superpose(x, ref, aligned=True, rot=False, rmsd=False, stats=False, out=None, workspace=None):
+    """Optimal proper rotation of every frame of x (n, N, 3) onto ref (N, 3) (dff_superpose) -> a dict of CUDA tensors with the
+    outputs asked for: "aligned" float32 (n, N, 3), the frames rotated and moved onto ref's centroid (written to `out` when
+    given; out = x aligns in place); "rot" float64 (n, 3, 3); "rmsd" float32 (n,); with `stats` "dsum" float64 (N, 3),
+    "dsq" float64 (N,) and "count" int64 (1,) over the finite frames, d = aligned - ref in float64.  NaN rows for a frame
+    with a non-finite coordinate.  Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    x, n, N = _coords(x)
+    r = torch.as_tensor(ref, dtype=torch.float32).reshape(N, 3).to(x.device).contiguous()
+    res = {}
+    if out is not None:
+        o, no, No = _coords(out)
+        if (no, No) != (n, N) or o.device != x.device:
+            raise ValueError(f"out must be a ({n}, {N}, 3) tensor on {x.device}")
+        res["aligned"] = o
+    elif aligned:
+        res["aligned"] = torch.empty_like(x)
+    if rot:
+        res["rot"] = torch.empty((n, 3, 3), dtype=torch.float64, device=x.device)
+    if rmsd:
+        res["rmsd"] = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws_bytes = 0
+    if stats:
+        res["dsum"] = torch.empty((N, 3), dtype=torch.float64, device=x.device)
+        res["dsq"] = torch.empty(N, dtype=torch.float64, device=x.device)
+        res["count"] = torch.empty(1, dtype=torch.int64, device=x.device)
+        if workspace is None:
+            workspace = torch.empty(max(superpose_workspace_bytes(n, N), 8), dtype=torch.uint8, device=x.device)
+        ws_bytes = int(workspace.numel() * workspace.element_size())
+    else:
+        workspace = None
+    _check(lib, lib.dff_superpose(x.device.index, _ptr(x), n, N, _ptr(r), _ptr(res.get("aligned")), _ptr(res.get("rot")),
+                                  _ptr(res.get("rmsd")), _ptr(res.get("dsum")), _ptr(res.get("dsq")), _ptr(res.get("count")),
+                                  _ptr(workspace), ws_bytes, _stream(x)), "dff_superpose")
+    return res

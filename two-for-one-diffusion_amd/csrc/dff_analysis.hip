@@ -8,6 +8,7 @@
 #include "dff_tica.hip"
 #include "dff_states.hip"
 #include "dff_ensemble.hip"
+#include "dff_superpose.hip"
 
 // ---------------------------------------------------------------------------------------------
 // PWD histograms (dff_pwd.hip)
@@ -545,4 +546,66 @@ extern "C" int dff_rmsd_matrix(int device, const float* x, long long n, const fl
     if (!out) return fail(DFF_EINVAL, "rmsd_matrix: null output");
     ON_DEVICE(device);
     return ens_launch<false>((hipStream_t)stream_, x, n, y, m, N, -1, out, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Superposition on a reference: rotations, aligned frames, ensemble statistics (dff_superpose.hip)
+// ---------------------------------------------------------------------------------------------
+// workgroups of a call: a function of n alone (the slices of the workspace, and the order of every sum, follow from it)
+static long long superpose_grid(long long n) {
+    const long long ntiles = (n + DFF_STRUCT_TILE - 1) / DFF_STRUCT_TILE;
+    return ntiles < DFF_SUP_WGS ? ntiles : DFF_SUP_WGS;
+}
+
+static int superpose_check_shape(long long n, int N, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    if (n > 0x7fffffffLL * DFF_STRUCT_TILE) return fail(DFF_EINVAL, "%s: too many frames", what);
+    return DFF_OK;
+}
+
+extern "C" long long dff_superpose_workspace_bytes(long long n, int n_beads) {
+    if (superpose_check_shape(n, n_beads, "superpose_workspace_bytes")) return -1;
+    return superpose_grid(n) * superpose_per(n_beads) * (long long)sizeof(double);     // <= 4096 slices of 4 N + 1 doubles
+}
+
+extern "C" int dff_superpose(int device, const float* x, long long n, int N, const float* ref, float* aligned, double* rot,
+                             float* rmsd, double* dsum, double* dsq, uint64_t* count, void* workspace,
+                             size_t workspace_bytes, void* stream_) {
+    int rc = superpose_check_shape(n, N, "superpose");
+    if (rc) return rc;
+    if (!x && n > 0) return fail(DFF_EINVAL, "superpose: null frames");
+    if (!ref && n > 0) return fail(DFF_EINVAL, "superpose: null reference structure");
+    const bool stats = dsum || dsq || count;
+    const long long need = stats ? dff_superpose_workspace_bytes(n, N) : 0;
+    if (need > 0 && (!workspace || (long long)workspace_bytes < need))
+        return fail(DFF_EINVAL, "superpose: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if (need > 0 && (uintptr_t)workspace % sizeof(double))
+        return fail(DFF_EINVAL, "superpose: the workspace must be 8-byte aligned");
+    if (!stats && !aligned && !rot && !rmsd) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n == 0) {
+        if (dsum) HIPCHK(hipMemsetAsync(dsum, 0, (size_t)3 * N * sizeof(double), stream));
+        if (dsq) HIPCHK(hipMemsetAsync(dsq, 0, (size_t)N * sizeof(double), stream));
+        if (count) HIPCHK(hipMemsetAsync(count, 0, sizeof(uint64_t), stream));
+        return DFF_OK;
+    }
+    // LDS: centred reference | tile | with statistics: staging buffer | accumulators (the table in dff_superpose.hip:
+    // 8 176 / 25 392 bytes at N = 10, 50 944 / 69 888 at N = 64); above 64 KB the kernel has to be told
+    unsigned lds = (unsigned)(superpose_ref_doubles(N) * sizeof(double)) + struct_tile_bytes(N);
+    if (stats) lds += (unsigned)((DFF_STRUCT_TILE * DFF_SUP_LDS + 4 * N) * sizeof(double));
+    if (lds > 160 * 1024) return fail(DFF_EINVAL, "superpose: LDS budget exceeded (%u bytes)", lds);
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void*)&dff_superpose_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    double* part = stats ? (double*)workspace : nullptr;
+    if ((rc = struct_launch(dff_superpose_kernel, DFF_SUP_WGS, lds, stream_, x, n, N, ref, aligned, rot, rmsd, part,
+                            (int)(((uintptr_t)aligned % 16) == 0))))
+        return rc;
+    if (stats) {
+        hipLaunchKernelGGL(dff_superpose_reduce_kernel, dim3(superpose_per(N)), dim3(64), 0, stream, part,
+                           (int)superpose_grid(n), N, dsum, dsq, (unsigned long long*)count);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
 }

@@ -1072,3 +1072,195 @@ class EnsembleCoverageEvaluator:
     def eval(self, samples):
         x, d = self.nearest(samples)
         return self.summarize(d["novelty"], d["coverage"], d["diversity"], _count_nonfinite(x), self.refs_nonfinite)
+
+
+# =====================================================================================================
+# Superposition on a reference: aligned frames, mean structure, per-bead fluctuation (dff_superpose, csrc/dff_superpose.hip).
+# The reference's data pipeline puts a trajectory into a common frame with traj.superpose(traj, 0)
+# (datasets/dataset_utils_empty.py:319-321); its evaluators have no per-bead flexibility metric.
+# =====================================================================================================
+SUPERPOSE_CHUNK = 1 << 20      # frames per dff_superpose call of superpose / superpose_stats
+
+
+def _superpose_chunks(xyz, ref, chunk, device):
+    """(device, reference (N, 3) float32 on it, the frames as given, chunk size) after the argument checks"""
+    dev = torch.device(device)
+    xs = torch.as_tensor(xyz)
+    if xs.dim() != 3 or xs.shape[-1] != 3:
+        raise ValueError("structures must be (n, n_beads, 3)")
+    r = torch.as_tensor(ref)
+    if tuple(r.shape) != (int(xs.shape[1]), 3):
+        raise ValueError(f"xyz has {int(xs.shape[1])} beads, the reference structure has shape {tuple(r.shape)}")
+    chunk = SUPERPOSE_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    return dev, r.to(device=dev, dtype=torch.float32).contiguous(), xs, chunk
+
+
+def superpose(xyz, ref, *, return_rotations=False, chunk=None, device="cuda:0"):
+    """Every structure of xyz (n, N, 3) rotated (optimal proper rotation) and moved onto ref (N, 3): float32 tensor
+    (n, N, 3) on `device`, the frames on ref's centroid as mdtraj's superpose leaves them; with return_rotations also the
+    rotations, float64 (n, 3, 3).  NaN rows for a structure with a non-finite coordinate.  The frames go to the device
+    `chunk` at a time (default SUPERPOSE_CHUNK); the result does not depend on `chunk`."""
+    dev, r, xs, chunk = _superpose_chunks(xyz, ref, chunk, device)
+    n, N = int(xs.shape[0]), int(xs.shape[1])
+    aligned = torch.empty((n, N, 3), dtype=torch.float32, device=dev)
+    rot = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if return_rotations else None
+    for o in range(0, n, chunk):
+        xc = _frames(xs[o:o + chunk], dev)
+        res = binding.superpose(xc, r, rot=return_rotations, out=aligned[o:o + len(xc)])
+        if return_rotations:
+            rot[o:o + len(xc)] = res["rot"]
+    return (aligned, rot) if return_rotations else aligned
+
+
+def superpose_stats(xyz, ref, *, chunk=None, device="cuda:0"):
+    """The sums a mean structure and an RMSF are made of, over the finite structures of xyz (n, N, 3) superposed on ref
+    (N, 3, used as float32): (dsum float64 (N, 3), dsq float64 (N,), count int) with d = aligned - ref in float64 on the
+    device.  One dff_superpose call per chunk with no aligned output; the chunks' sums are added here in float64."""
+    dev, r, xs, chunk = _superpose_chunks(xyz, ref, chunk, device)
+    N = int(xs.shape[1])
+    dsum, dsq, count = np.zeros((N, 3)), np.zeros(N), 0
+    ws = None
+    for o in range(0, len(xs), chunk):
+        xc = _frames(xs[o:o + chunk], dev)
+        if ws is None:
+            ws = torch.empty(max(binding.superpose_workspace_bytes(len(xc), N), 8), dtype=torch.uint8, device=dev)
+        res = binding.superpose(xc, r, aligned=False, stats=True, workspace=ws)
+        dsum += res["dsum"].cpu().numpy()
+        dsq += res["dsq"].cpu().numpy()
+        count += int(res["count"])
+    return dsum, dsq, count
+
+
+def _first_finite_frame(xyz):
+    xs = torch.as_tensor(xyz)
+    ok = torch.isfinite(xs).reshape(len(xs), -1).all(dim=1)
+    if not bool(ok.any()):
+        raise ValueError("no structure with finite coordinates")
+    return xs[int(torch.nonzero(ok)[0])]
+
+
+def _as_ref32(ref):
+    """the reference as the kernel sees it (float32), in float64"""
+    return np.asarray(torch.as_tensor(ref).detach().cpu().to(torch.float32), np.float64).reshape(-1, 3)
+
+
+def mean_structure(xyz, ref=None, max_iter=10, tol=1e-4, *, chunk=None, device="cuda:0", aligner=None):
+    """Mean structure of the ensemble xyz (n, N, 3) by generalised Procrustes -> (mean float64 (N, 3), n_iter).
+    All finite structures are superposed on the current reference (ref, or the first finite structure when None), the mean
+    of the superposed structures -- reference + dsum / count -- becomes the next reference, until the RMSD between
+    successive means (they share a frame: no further rotation) falls below tol Angstrom; n_iter counts the passes over
+    the ensemble, each one dff_superpose call per chunk with no aligned output.  Without convergence in max_iter passes
+    the last mean is returned with a RuntimeWarning.  aligner(xyz, ref) -> (dsum, dsq, count) replaces superpose_stats
+    (for tests of this loop without a GPU)."""
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    if aligner is None:
+        def aligner(x, r):
+            return superpose_stats(x, r, chunk=chunk, device=device)
+    cur = _as_ref32(_first_finite_frame(xyz) if ref is None else ref)
+    for it in range(1, max_iter + 1):
+        dsum, _, count = aligner(xyz, cur)
+        if count == 0:
+            raise ValueError("no structure with finite coordinates (or a non-finite reference)")
+        step = np.asarray(dsum, np.float64) / count
+        cur = _as_ref32(cur) + step
+        if np.sqrt((step * step).sum() / len(cur)) < tol:
+            return cur, it
+    import warnings
+    warnings.warn(f"mean_structure: successive means still {np.sqrt((step * step).sum() / len(cur)):.3g} A apart after "
+                  f"{max_iter} passes (tol {tol:g})", RuntimeWarning)
+    return cur, max_iter
+
+
+def rmsf_from_sums(dsum, dsq, count):
+    """Per-bead fluctuation sqrt(<|d|^2> - |<d>|^2) (Angstrom, float64 (N,)) from the sums of superpose_stats."""
+    if count == 0:
+        return np.full(len(dsq), np.nan)
+    m = np.asarray(dsum, np.float64) / count
+    return np.sqrt(np.maximum(np.asarray(dsq, np.float64) / count - (m * m).sum(1), 0.0))
+
+
+def rmsf(xyz, ref="mean", *, max_iter=10, tol=1e-4, chunk=None, device="cuda:0", aligner=None):
+    """Root-mean-square fluctuation of every bead (Angstrom, float64 (N,)) of the ensemble xyz (n, N, 3) about its own
+    mean position, after superposing every finite structure on ref: a structure (N, 3), or "mean" for the converged
+    mean_structure of xyz."""
+    if aligner is None:
+        def aligner(x, r):
+            return superpose_stats(x, r, chunk=chunk, device=device)
+    if isinstance(ref, str):
+        if ref != "mean":
+            raise ValueError('ref must be a structure (N, 3) or "mean"')
+        ref, _ = mean_structure(xyz, None, max_iter, tol, aligner=aligner)
+    return rmsf_from_sums(*aligner(xyz, _as_ref32(ref)))
+
+
+def kabsch_rmsd64(a, b):
+    """RMSD (optimal proper rotation, float64, numpy) between two structures (N, 3): for the two mean structures of
+    FlexibilityEvaluator.summarize, not for ensembles."""
+    a = np.asarray(a, np.float64) - np.mean(a, 0)
+    b = np.asarray(b, np.float64) - np.mean(b, 0)
+    U, S, Vt = np.linalg.svd(a.T @ b)
+    S[-1] *= np.sign(np.linalg.det(U @ Vt))
+    return float(np.sqrt(max(((a * a).sum() + (b * b).sum() - 2.0 * S.sum()) / len(a), 0.0)))
+
+
+class FlexibilityEvaluator:
+    """Per-bead flexibility of a sampled ensemble against a reference ensemble (MD data), on the GPU.
+
+    ref_data (m, N, 3) in Angstrom.  Both ensembles are superposed on `folded` (a structure (N, 3) or a folded PDB) when
+    given, otherwise on the reference ensemble's mean structure (mean_structure).  eval(samples) returns a plain dict of
+    floats:
+      rmsf_mae, rmsf_max_abs      mean and largest |RMSF_samples - RMSF_refs| over the beads (Angstrom)
+      rmsf_pearson                correlation of the two RMSF profiles (NaN when one of them is constant)
+      mean_structure_rmsd         RMSD (optimal proper rotation) between the two ensembles' mean structures
+      samples_nonfinite, refs_nonfinite   frames with a non-finite coordinate: left out on their side
+    and keeps the two profiles on .profiles: {"samples" / "refs": {"rmsf" (N,), "mean" (N, 3), "count"}}.
+    Without the HIP library: DffLibraryError."""
+
+    def __init__(self, ref_data, mol_name="", folded=None, *, max_iter=10, tol=1e-4, chunk=None, device="cuda:0"):
+        self.mol_name = mol_name
+        self.chunk = chunk
+        self.device = torch.device(device)
+        binding.load_library()
+        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+            ref_data = ref_data[:][0]
+        self.refs = _frames(ref_data, self.device)
+        self.refs_nonfinite = _count_nonfinite(self.refs)
+        if folded is not None:
+            self.align_on = _as_ref32(_folded_coords(folded, mol_name))
+        else:
+            self.align_on, _ = mean_structure(self.refs, None, max_iter, tol, chunk=chunk, device=self.device)
+        if len(self.align_on) != int(self.refs.shape[1]):
+            raise ValueError(f"the structure to align on has {len(self.align_on)} beads, the reference ensemble "
+                             f"{int(self.refs.shape[1])}")
+        self.profiles = {"refs": self.profile(self.refs)}
+
+    def profile(self, x):
+        """{"rmsf" (N,), "mean" (N, 3), "count"} of the frames x superposed on the evaluator's structure"""
+        dsum, dsq, count = superpose_stats(x, self.align_on, chunk=self.chunk, device=self.device)
+        mean = _as_ref32(self.align_on) + dsum / count if count else np.full_like(dsum, np.nan)
+        return {"rmsf": rmsf_from_sums(dsum, dsq, count), "mean": mean, "count": count}
+
+    @staticmethod
+    def summarize(rmsf_samples, rmsf_refs, mean_samples, mean_refs, samples_nonfinite=0, refs_nonfinite=0):
+        """eval()'s dict from the two RMSF profiles (N,) and the two mean structures (N, 3): numpy only."""
+        a, b = np.asarray(rmsf_samples, np.float64), np.asarray(rmsf_refs, np.float64)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("the two RMSF profiles must be (N,) both")
+        diff = np.abs(a - b)
+        pearson = float("nan")
+        if len(a) > 1 and a.std() > 0 and b.std() > 0:
+            pearson = float(np.corrcoef(a, b)[0, 1])
+        return {"rmsf_mae": float(diff.mean()), "rmsf_max_abs": float(diff.max()), "rmsf_pearson": pearson,
+                "mean_structure_rmsd": kabsch_rmsd64(mean_samples, mean_refs),
+                "samples_nonfinite": float(samples_nonfinite), "refs_nonfinite": float(refs_nonfinite)}
+
+    def eval(self, samples):
+        x = _frames(samples, self.device)
+        if x.shape[1] != self.refs.shape[1]:
+            raise ValueError(f"samples have {int(x.shape[1])} beads, the reference ensemble {int(self.refs.shape[1])}")
+        s, r = self.profile(x), self.profiles["refs"]
+        self.profiles["samples"] = s
+        return self.summarize(s["rmsf"], r["rmsf"], s["mean"], r["mean"], _count_nonfinite(x), self.refs_nonfinite)
