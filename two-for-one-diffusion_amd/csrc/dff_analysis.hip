@@ -11,6 +11,28 @@
 #include "dff_superpose.hip"
 
 // ---------------------------------------------------------------------------------------------
+// Argument checks that several entry points share; `what` is the caller's name in the message
+// ---------------------------------------------------------------------------------------------
+// the bead range of everything that works on dihedrals or superpositions
+static int check_beads(int N, const char* what) {
+    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    return DFF_OK;
+}
+
+// a caller's workspace against the bytes its *_workspace_bytes function asks for (none needed: nothing to check)
+static int check_workspace(const void* workspace, size_t workspace_bytes, long long need, const char* what) {
+    if (need > 0 && (!workspace || (long long)workspace_bytes < need))
+        return fail(DFF_EINVAL, "%s: workspace of %zu bytes, %lld needed", what, workspace_bytes, need);
+    return DFF_OK;
+}
+
+// the frames of every tile kernel (struct_tiles): their tiles are counted in 32 bits
+static int check_frames(long long n, const char* what) {
+    if (n > 0x7fffffffLL * DFF_STRUCT_TILE) return fail(DFF_EINVAL, "%s: too many frames", what);
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // PWD histograms (dff_pwd.hip)
 // ---------------------------------------------------------------------------------------------
 extern "C" int dff_pwd_num_pairs(int n_beads, int offset) {
@@ -108,10 +130,9 @@ extern "C" int dff_pwd_hist(int device, const float* x, long long n, int N, int 
 // ---------------------------------------------------------------------------------------------
 static int struct_check(const float* x, long long n, int N, const void* out, const char* what) {
     if ((!x && n > 0) || n < 0) return fail(DFF_EINVAL, "%s: null input / negative count", what);
-    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    if (int rc = check_beads(N, what)) return rc;
     if (!out && n > 0) return fail(DFF_EINVAL, "%s: null output", what);
-    if (n > 0x7fffffffLL * DFF_STRUCT_TILE) return fail(DFF_EINVAL, "%s: too many frames", what);
-    return DFF_OK;
+    return check_frames(n, what);
 }
 
 static unsigned struct_tile_bytes(int N) { return (unsigned)(DFF_STRUCT_TILE * struct_ld(N) * sizeof(float)); }
@@ -264,7 +285,7 @@ static int tica_plan(long long C, const long long* lengths, int n_traj, int lag,
 }
 
 extern "C" long long dff_tica_workspace_bytes(int n_beads, long long n_frames_max, int lagtime) {
-    if (n_beads < 4 || n_beads > DFF_MAX_BEADS) return fail(DFF_EINVAL, "tica: n_beads must be 4..%d", DFF_MAX_BEADS), -1;
+    if (check_beads(n_beads, "tica")) return -1;
     if (lagtime < 1) return fail(DFF_EINVAL, "tica: lagtime must be >= 1"), -1;
     if (n_frames_max < 0) return fail(DFF_EINVAL, "tica: negative frame count"), -1;
     const TicaShape sh(n_beads, n_frames_max);
@@ -292,8 +313,7 @@ extern "C" int dff_tica_moments(int device, const float* x, long long n, int N, 
     if ((rc = traj_check_lengths(lengths, n_traj, n, "tica_moments"))) return rc;
     if (!shift || !sx || !sy || !m0 || !mt) return fail(DFF_EINVAL, "tica_moments: null shift / accumulator");
     const long long need = dff_tica_workspace_bytes(N, n, lagtime);
-    if (!workspace || (long long)workspace_bytes < need)
-        return fail(DFF_EINVAL, "tica_moments: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "tica_moments"))) return rc;
     if (n == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -327,7 +347,7 @@ extern "C" int dff_tica_moments(int device, const float* x, long long n, int N, 
 
 extern "C" int dff_tica_debug_plan(int n_beads, const long long* lengths, int n_traj, int lagtime, long long chunk_pairs,
                                    long long* out_host, int max_runs) {
-    if (n_beads < 4 || n_beads > DFF_MAX_BEADS) return fail(DFF_EINVAL, "tica_debug_plan: n_beads must be 4..%d", DFF_MAX_BEADS), -1;
+    if (check_beads(n_beads, "tica_debug_plan")) return -1;
     long long n = 0;
     for (int i = 0; i < n_traj && lengths; ++i) n += lengths[i] > 0 ? lengths[i] : 0;
     if (lagtime < 1) return fail(DFF_EINVAL, "tica_debug_plan: lagtime must be >= 1"), -1;
@@ -395,9 +415,8 @@ extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d
     if (!pts && n > 0) return fail(DFF_EINVAL, "kmeans_step: null points");
     if (!centers) return fail(DFF_EINVAL, "kmeans_step: null centres");
     const bool accumulate = sums || counts || inertia;
-    const long long need = accumulate ? dff_kmeans_workspace_bytes(n, d, K) : 0;
-    if (accumulate && n > 0 && (!workspace || (long long)workspace_bytes < need))
-        return fail(DFF_EINVAL, "kmeans_step: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    const long long need = accumulate ? dff_kmeans_workspace_bytes(n, d, K) : 0;       // 0 at n = 0
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "kmeans_step"))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) {
@@ -481,7 +500,7 @@ extern "C" int dff_transition_counts(int device, const int32_t* labels, long lon
 // ---------------------------------------------------------------------------------------------
 static int ens_check_shape(long long n, long long m, int N, const char* what) {
     if (n < 0 || m < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
-    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
+    if (int rc = check_beads(N, what)) return rc;
     if (m > 0x7fffffffLL) return fail(DFF_EINVAL, "%s: more than 2^31 - 1 candidates (the index half of the key is 32 bits)", what);
     return DFF_OK;
 }
@@ -517,8 +536,7 @@ extern "C" int dff_rmsd_nearest(int device, const float* x, long long n, const f
     if (!rmsd && n > 0) return fail(DFF_EINVAL, "rmsd_nearest: null output");
     if (self_first < -1) return fail(DFF_EINVAL, "rmsd_nearest: self_first must be -1 or a candidate index");
     const long long need = dff_rmsd_nearest_workspace_bytes(n, m, N);
-    if (need > 0 && (!workspace || (long long)workspace_bytes < need))
-        return fail(DFF_EINVAL, "rmsd_nearest: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "rmsd_nearest"))) return rc;
     if (n == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -559,9 +577,8 @@ static long long superpose_grid(long long n) {
 
 static int superpose_check_shape(long long n, int N, const char* what) {
     if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
-    if (N < 4 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "%s: n_beads must be 4..%d", what, DFF_MAX_BEADS);
-    if (n > 0x7fffffffLL * DFF_STRUCT_TILE) return fail(DFF_EINVAL, "%s: too many frames", what);
-    return DFF_OK;
+    if (int rc = check_beads(N, what)) return rc;
+    return check_frames(n, what);
 }
 
 extern "C" long long dff_superpose_workspace_bytes(long long n, int n_beads) {
@@ -578,8 +595,7 @@ extern "C" int dff_superpose(int device, const float* x, long long n, int N, con
     if (!ref && n > 0) return fail(DFF_EINVAL, "superpose: null reference structure");
     const bool stats = dsum || dsq || count;
     const long long need = stats ? dff_superpose_workspace_bytes(n, N) : 0;
-    if (need > 0 && (!workspace || (long long)workspace_bytes < need))
-        return fail(DFF_EINVAL, "superpose: workspace of %zu bytes, %lld needed", workspace_bytes, need);
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "superpose"))) return rc;
     if (need > 0 && (uintptr_t)workspace % sizeof(double))
         return fail(DFF_EINVAL, "superpose: the workspace must be 8-byte aligned");
     if (!stats && !aligned && !rot && !rmsd) return DFF_OK;

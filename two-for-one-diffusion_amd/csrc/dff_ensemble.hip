@@ -12,9 +12,8 @@
 //                v_mfma_f64_16x16x4_f64 (operand and result maps: dff_tica.hip's header).  Beads are padded to Np, the
 //                next multiple of 4, with zero rows; bead b always sits in k-step b / 4, slot b % 4, so the value of a
 //                pair does not depend on the tile, the wave or the workgroup that computes it.
-//   lambda_max   of Horn's symmetric 4x4 key matrix by sym4_lambda_max (cyclic Jacobi, dff_struct.hip: its header says why
-//                not Newton on the quartic)
-//   RMSD         msd = (Ga + Gb - 2 lambda) / N, sqrt(max(msd, 0)) in fp64, rounded to fp32 once.
+//   RMSD         from S, Ga and Gb by the solver of dff_kabsch.h: lambda_max of Horn's symmetric 4x4 key matrix by cyclic
+//                Jacobi (its header says why not Newton on the quartic), msd = (Ga + Gb - 2 lambda) / N
 //
 // Layout.  One workgroup = 4 waves holds DFF_ENS_TC = 32 candidates, centred, in LDS while 16-query tiles stream past it.
 //   LDS image yc[sub][c][bead][16] (sub = which 16 of the 32 candidates, c = x / y / z; frame index fastest), fp64: the B
@@ -37,6 +36,8 @@
 //   is the same for every grid size, every split of the candidates and every run.  No floating-point atomics.
 #pragma once
 #include "dff_internal.h"
+#include "dff_kabsch.h"
+#include "dff_tica.hip"   // f64x4
 
 #define DFF_ENS_THREADS 256
 #define DFF_ENS_TC 32              // candidates per workgroup: two 16-column MFMA tiles
@@ -49,20 +50,9 @@ __host__ __device__ __forceinline__ int ens_np(int N) { return (N + 3) & ~3; }
 // LDS doubles: yc | centres | Gb
 __host__ __device__ __forceinline__ int ens_lds_doubles(int Np) { return DFF_ENS_TC * 3 * Np + 3 * DFF_ENS_TC + DFF_ENS_TC; }
 
-// The RMSD of one pair from its correlation matrix S (row = component of the query, column = component of the candidate)
-// and the two inner products; shared by the matrix and the nearest-candidate paths, so that they agree bit for bit.
-__device__ __forceinline__ float ens_pair_rmsd(double Sxx, double Sxy, double Sxz, double Syx, double Syy, double Syz,
-                                               double Szx, double Szy, double Szz, double Ga, double Gb, int N) {
-    const double k00 = Sxx + Syy + Szz, k01 = Syz - Szy, k02 = Szx - Sxz, k03 = Sxy - Syx;
-    const double k11 = Sxx - Syy - Szz, k12 = Sxy + Syx, k13 = Szx + Sxz;
-    const double k22 = -Sxx + Syy - Szz, k23 = Syz + Szy;
-    const double k33 = -Sxx - Syy + Szz;
-    const double l = sym4_lambda_max(k00, k01, k02, k03, k11, k12, k13, k22, k23, k33);
-    const double msd = (Ga + Gb - 2.0 * l) / N;
-    return (float)sqrt(msd > 0.0 ? msd : 0.0);
-}
-
 // grid = nct * qsplit: workgroup (ct, qs) pairs candidate tile ct with the query tiles qs * 4 + wave, + 4 qsplit, ...
+// The RMSD of a pair comes from its correlation matrix S (row = component of the query, column = component of the
+// candidate) by the same calls on both paths, so that they agree bit for bit.
 // NEAREST: keys[q] = min(keys[q], key of the pair), the pair (q, self_first + q) left out when self_first >= 0.
 // else:    out[q * m + cand] = RMSD, NaN where either frame has a non-finite coordinate.
 template <bool NEAREST>
@@ -175,9 +165,11 @@ __global__ __launch_bounds__(DFF_ENS_THREADS) void dff_ens_rmsd_kernel(const flo
                 const int row = kq + 4 * r;                // result row: the query
                 const bool fin = GaR[r] == GaR[r] && Gb == Gb;
                 float d = __builtin_nanf("");
-                if (fin)
-                    d = ens_pair_rmsd(S[0][0][r], S[0][1][r], S[0][2][r], S[1][0][r], S[1][1][r], S[1][2][r], S[2][0][r],
-                                      S[2][1][r], S[2][2][r], GaR[r], Gb, N);
+                if (fin) {
+                    const Sym4 K = horn_key(S[0][0][r], S[0][1][r], S[0][2][r], S[1][0][r], S[1][1][r], S[1][2][r], S[2][0][r],
+                                            S[2][1][r], S[2][2][r]);
+                    d = kabsch_rmsd(GaR[r], Gb, sym4_jacobi<false>(K), N);
+                }
                 if (NEAREST) {
                     if (fin && !(self_first >= 0 && cand == self_first + q0 + row)) {
                         const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)cand;

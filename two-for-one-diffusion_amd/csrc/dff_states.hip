@@ -29,7 +29,7 @@
 //     every 2^31 frames a workgroup has seen (a counter grows by at most one per frame).  Integer sums do not depend
 //     on their order: the result is exact and reproducible.
 #pragma once
-#include "dff_internal.h"
+#include "dff_struct.hip"   // struct_tiles, struct_tic_project, last_le, wave_sum
 
 #define DFF_STATES_MAXK 64         // states / cluster centres
 #define DFF_KM_MAXD 8              // coordinates per point (= DFF_TIC_MAXK)
@@ -88,14 +88,6 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_assign_kernel(
             }
         }
     });
-}
-
-// sum over the wave by a butterfly: the same tree, and the same bits, in every lane
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 // ---- one Lloyd step.  Per-workgroup partials: part[block * per + i], per = K d + K + 1: the K x d coordinate sums, the

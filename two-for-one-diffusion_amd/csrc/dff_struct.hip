@@ -19,16 +19,14 @@
 //   distance   pwd_dist2 (dff_pwd.hip): sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) in fp32, bit-equal to torch.norm
 //   dihedral   mdtraj's formula in fp32: b1 = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2,
 //              phi = atan2((b1 . c1) |b2|, c1 . c2), no FMA contraction (the same bits in every kernel that uses it)
-//   RMSD       fp64 centring, 3x3 correlation and inner products; lambda_max of Horn's symmetric 4x4 key matrix K by
-//              cyclic Jacobi in fp64 (<= 8 sweeps, stop when the off-diagonal is below 1e-15 ||K||) -- the optimal PROPER
-//              rotation, as mdtraj.  Not Newton on K's characteristic quartic (QCP, Theobald 2005): for an elongated
-//              frame or reference the two largest eigenvalues nearly coincide, the quartic has a near-double root that
-//              it fixes only to ~sqrt(eps) lambda, and Newton stopped up to 4.4e-2 A off on straight chains.  Jacobi
-//              is backward-stable: lambda_max to ~eps ||K||, whatever the spacing of the eigenvalues.
+//   RMSD       fp64 centring, 3x3 correlation and inner products; the minimum over proper rotations by the solver of
+//              dff_kabsch.h (lambda_max of Horn's key matrix by cyclic Jacobi: its header says why not Newton)
 //   TIC        features (N - 3 dihedrals, then the N (N - 1) / 2 distances in triu_indices(N, N, 1) order) in fp32,
 //              never stored; out[s, c] = sum_f ((double) feat_f - mean_f) * A[f, c] accumulated in fp64
 #pragma once
 #include "dff_internal.h"
+#include "dff_kabsch.h"
+#include "dff_pwd.hip"   // pwd_dist2, f32x4
 
 #define DFF_STRUCT_TILE 64     // frames per tile = lanes per workgroup (one wave)
 #define DFF_TIC_MAXK 8         // TIC components per call
@@ -49,30 +47,61 @@ __device__ __forceinline__ int last_le(const T* start, int n, T v) {
     return lo;
 }
 
-// coalesced load of cnt frames starting at s0 into tile[s * ld + k].  magic = ceil(2^32 / 3N): the frame of
-// flat element e < 64 * 3N is __umulhi(e, magic) exactly (the rounding error e / 2^32 < 1 / 3N).
-__device__ __forceinline__ void struct_load_tile(float* tile, const float* __restrict__ x, long long s0, int cnt,
-                                                 int N3, int ld, unsigned magic, bool vec4) {
-    const float* src = x + s0 * N3;
+// sum over the wave by a butterfly: the same tree, and the same bits, in every lane
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// The flat elements 0 .. cnt * 3N - 1 of a tile's frames in global memory, dealt to the 64 lanes in coalesced order:
+// quad(k, at) for elements 4 k .. 4 k + 3 (one 16-byte access; vec4 only), one(k, at(k)) for the rest.  at(f) is where flat
+// element f sits in LDS, s * ld + offset within frame s.  magic = ceil(2^32 / 3N): the frame of flat element f < 64 * 3N is
+// __umulhi(f, magic) exactly (the rounding error f / 2^32 < 1 / 3N).
+template <class Quad, class One>
+__device__ __forceinline__ void struct_tile_walk(int cnt, int N3, int ld, unsigned magic, bool vec4, Quad quad, One one) {
+    const auto at = [=](unsigned f) {
+        const unsigned s = __umulhi(f, magic);
+        return s * ld + (f - s * N3);
+    };
     const int nf = cnt * N3;
     int k0 = 0;
     if (vec4) {
         const int n4 = nf >> 2;
-        for (int k = threadIdx.x; k < n4; k += DFF_STRUCT_TILE) {
-            const f32x4 v = __builtin_nontemporal_load((const f32x4*)src + k);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned f = (unsigned)(4 * k + e);
-                const unsigned s = __umulhi(f, magic);
-                tile[s * ld + (f - s * N3)] = v[e];
-            }
-        }
+        for (int k = threadIdx.x; k < n4; k += DFF_STRUCT_TILE) quad(k, at);
         k0 = n4 << 2;
     }
-    for (int k = k0 + threadIdx.x; k < nf; k += DFF_STRUCT_TILE) {
-        const unsigned s = __umulhi((unsigned)k, magic);
-        tile[s * ld + (k - s * N3)] = src[k];
-    }
+    for (int k = k0 + threadIdx.x; k < nf; k += DFF_STRUCT_TILE) one(k, at((unsigned)k));
+}
+
+// coalesced load of cnt frames starting at s0 into tile[s * ld + k]
+__device__ __forceinline__ void struct_load_tile(float* tile, const float* __restrict__ x, long long s0, int cnt,
+                                                 int N3, int ld, unsigned magic, bool vec4) {
+    const float* src = x + s0 * N3;
+    struct_tile_walk(
+        cnt, N3, ld, magic, vec4,
+        [&](int k, auto at) {
+            const f32x4 v = __builtin_nontemporal_load((const f32x4*)src + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tile[at((unsigned)(4 * k + e))] = v[e];
+        },
+        [&](int k, unsigned o) { tile[o] = src[k]; });
+}
+
+// its counterpart: coalesced store of the cnt frames in tile to dst + s0 * 3N
+__device__ __forceinline__ void struct_store_tile(const float* tile, float* dst, long long s0, int cnt, int N3, int ld,
+                                                  unsigned magic, bool vec4) {
+    dst += s0 * N3;
+    struct_tile_walk(
+        cnt, N3, ld, magic, vec4,
+        [&](int k, auto at) {
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = tile[at((unsigned)(4 * k + e))];
+            *((f32x4*)dst + k) = v;
+        },
+        [&](int k, unsigned o) { dst[k] = tile[o]; });
 }
 
 // Each product and sum rounded on its own, as numpy's float32 formula (mdtraj) rounds it: without the pragma, which
@@ -131,43 +160,50 @@ __device__ __forceinline__ void struct_tiles(float* tile, const float* __restric
     }
 }
 
-// ---- RMSD to a reference structure (fp64, Horn's key matrix).  LDS: tile | centred reference (N x 3 doubles)
-// one Jacobi rotation of the symmetric 4x4 matrix in the (p, q) plane: a_pq -> 0.  (r, s) are the other two indices;
-// arp = a_rp, arq = a_rq, asp = a_sp, asq = a_sq.  t = tan of the rotation angle, the smaller root of t^2 + 2 theta t = 1;
-// 1 / (2 theta) when theta^2 would overflow (a_pq negligible next to a_qq - a_pp).
-__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq, double& asp,
-                                           double& asq) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = fabs(theta) > 1e150 ? 0.5 / theta : copysign(1.0, theta) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
-    const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double g = arp, h = arq, u = asp, v = asq;
-    arp = c * g - s * h;
-    arq = s * g + c * h;
-    asp = c * u - s * v;
-    asq = s * u + c * v;
+// ---- RMSD to a reference structure (fp64; the solver is dff_kabsch.h).  LDS: tile | centred reference (N x 3 doubles)
+// Centre the reference into rc (every lane the same sums, in bead order: no reduction order to depend on) and hand out
+// its centroid.  The caller synchronises before rc is read.
+__device__ __forceinline__ void struct_centre_ref(const float* __restrict__ ref, int N, double* rc, double& m0, double& m1,
+                                                  double& m2) {
+    m0 = 0; m1 = 0; m2 = 0;
+    for (int b = 0; b < N; ++b) { m0 += ref[3 * b]; m1 += ref[3 * b + 1]; m2 += ref[3 * b + 2]; }
+    m0 /= N; m1 /= N; m2 /= N;
+    for (int b = threadIdx.x; b < N; b += DFF_STRUCT_TILE) {
+        rc[3 * b] = ref[3 * b] - m0;
+        rc[3 * b + 1] = ref[3 * b + 1] - m1;
+        rc[3 * b + 2] = ref[3 * b + 2] - m2;
+    }
 }
 
-// largest eigenvalue of the symmetric 4x4 [[a00 a01 a02 a03] [. a11 a12 a13] [. . a22 a23] [. . . a33]]: cyclic Jacobi.
-// The off-diagonal mass falls quadratically, so a few sweeps reach the stop; the cap only bounds the loop.
-__device__ __forceinline__ double sym4_lambda_max(double a00, double a01, double a02, double a03, double a11, double a12,
-                                                  double a13, double a22, double a23, double a33) {
-    const double nrm = a00 * a00 + a11 * a11 + a22 * a22 + a33 * a33 +
-                       2.0 * (a01 * a01 + a02 * a02 + a03 * a03 + a12 * a12 + a13 * a13 + a23 * a23);
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        const double off = a01 * a01 + a02 * a02 + a03 * a03 + a12 * a12 + a13 * a13 + a23 * a23;
-        if (!(off > 1e-30 * nrm)) break;                       // also ends at once on K = 0
-        jacobi_rot(a00, a11, a01, a02, a12, a03, a13);         // (0, 1): others 2, 3
-        jacobi_rot(a00, a22, a02, a01, a12, a03, a23);         // (0, 2): others 1, 3
-        jacobi_rot(a00, a33, a03, a01, a13, a02, a23);         // (0, 3): others 1, 2
-        jacobi_rot(a11, a22, a12, a01, a02, a13, a23);         // (1, 2): others 0, 3
-        jacobi_rot(a11, a33, a13, a01, a03, a12, a23);         // (1, 3): others 0, 2
-        jacobi_rot(a22, a33, a23, a02, a03, a12, a13);         // (2, 3): others 0, 1
+// Gb = sum |r_b|^2 of the centred reference
+__device__ __forceinline__ double struct_ref_norm2(const double* rc, int N) {
+    double Gb = 0;
+    for (int b = 0; b < N; ++b) Gb += rc[3 * b] * rc[3 * b] + rc[3 * b + 1] * rc[3 * b + 1] + rc[3 * b + 2] * rc[3 * b + 2];
+    return Gb;
+}
+
+// One frame xs against the centred reference rc: Horn's key matrix of their correlation.  Also hands out the frame's
+// centroid c and Ga = sum |a_b|^2 of the centred frame, and clears `finite` when a coordinate is not finite.
+__device__ __forceinline__ Sym4 struct_frame_key(const float* xs, const double* rc, int N, bool& finite, double& c0,
+                                                 double& c1, double& c2, double& Ga) {
+    c0 = 0; c1 = 0; c2 = 0;
+    for (int b = 0; b < N; ++b) {
+        const float a0 = xs[3 * b], a1 = xs[3 * b + 1], a2 = xs[3 * b + 2];
+        finite = finite && isfinite(a0) && isfinite(a1) && isfinite(a2);
+        c0 += a0; c1 += a1; c2 += a2;
     }
-    return fmax(fmax(a00, a11), fmax(a22, a33));
+    c0 /= N; c1 /= N; c2 /= N;
+    Ga = 0;
+    double Sxx = 0, Sxy = 0, Sxz = 0, Syx = 0, Syy = 0, Syz = 0, Szx = 0, Szy = 0, Szz = 0;
+    for (int b = 0; b < N; ++b) {
+        const double a0 = xs[3 * b] - c0, a1 = xs[3 * b + 1] - c1, a2 = xs[3 * b + 2] - c2;
+        const double r0 = rc[3 * b], r1 = rc[3 * b + 1], r2 = rc[3 * b + 2];
+        Ga = fma(a0, a0, fma(a1, a1, fma(a2, a2, Ga)));
+        Sxx = fma(a0, r0, Sxx); Sxy = fma(a0, r1, Sxy); Sxz = fma(a0, r2, Sxz);
+        Syx = fma(a1, r0, Syx); Syy = fma(a1, r1, Syy); Syz = fma(a1, r2, Syz);
+        Szx = fma(a2, r0, Szx); Szy = fma(a2, r1, Szy); Szz = fma(a2, r2, Szz);
+    }
+    return horn_key(Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz);
 }
 
 __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_rmsd_kernel(const float* __restrict__ x, long long n,
@@ -177,45 +213,17 @@ __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_rmsd_kernel(const 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     double* rc = (double*)smem;                              // N * 3 centred reference coordinates
     float* tile = smem + ((6 * N + 3) & ~3);
-    // centre the reference (every lane the same sums, in order: no reduction order to depend on)
-    double m0 = 0, m1 = 0, m2 = 0;
-    for (int b = 0; b < N; ++b) { m0 += ref[3 * b]; m1 += ref[3 * b + 1]; m2 += ref[3 * b + 2]; }
-    m0 /= N; m1 /= N; m2 /= N;
-    for (int b = threadIdx.x; b < N; b += DFF_STRUCT_TILE) {
-        rc[3 * b] = ref[3 * b] - m0;
-        rc[3 * b + 1] = ref[3 * b + 1] - m1;
-        rc[3 * b + 2] = ref[3 * b + 2] - m2;
-    }
+    double m0, m1, m2;
+    struct_centre_ref(ref, N, rc, m0, m1, m2);
     __syncthreads();
-    double Gb = 0;
-    for (int b = 0; b < N; ++b) Gb += rc[3 * b] * rc[3 * b] + rc[3 * b + 1] * rc[3 * b + 1] + rc[3 * b + 2] * rc[3 * b + 2];
+    const double Gb = struct_ref_norm2(rc, N);
     struct_tiles(tile, x, n, N, magic, vec4, [&](long long s0, int cnt, int lane, bool live, const float* xs) {
         if (live) {
             bool finite = true;
-            double c0 = 0, c1 = 0, c2 = 0;
-            for (int b = 0; b < N; ++b) {
-                const float a0 = xs[3 * b], a1 = xs[3 * b + 1], a2 = xs[3 * b + 2];
-                finite = finite && isfinite(a0) && isfinite(a1) && isfinite(a2);
-                c0 += a0; c1 += a1; c2 += a2;
-            }
-            c0 /= N; c1 /= N; c2 /= N;
-            double Ga = 0, Sxx = 0, Sxy = 0, Sxz = 0, Syx = 0, Syy = 0, Syz = 0, Szx = 0, Szy = 0, Szz = 0;
-            for (int b = 0; b < N; ++b) {
-                const double a0 = xs[3 * b] - c0, a1 = xs[3 * b + 1] - c1, a2 = xs[3 * b + 2] - c2;
-                const double r0 = rc[3 * b], r1 = rc[3 * b + 1], r2 = rc[3 * b + 2];
-                Ga = fma(a0, a0, fma(a1, a1, fma(a2, a2, Ga)));
-                Sxx = fma(a0, r0, Sxx); Sxy = fma(a0, r1, Sxy); Sxz = fma(a0, r2, Sxz);
-                Syx = fma(a1, r0, Syx); Syy = fma(a1, r1, Syy); Syz = fma(a1, r2, Syz);
-                Szx = fma(a2, r0, Szx); Szy = fma(a2, r1, Szy); Szz = fma(a2, r2, Szz);
-            }
-            // Horn's symmetric key matrix K (trace 0); lambda_max(K) = max over proper rotations of tr(R S)
-            const double k00 = Sxx + Syy + Szz, k01 = Syz - Szy, k02 = Szx - Sxz, k03 = Sxy - Syx;
-            const double k11 = Sxx - Syy - Szz, k12 = Sxy + Syx, k13 = Szx + Sxz;
-            const double k22 = -Sxx + Syy - Szz, k23 = Syz + Szy;
-            const double k33 = -Sxx - Syy + Szz;
-            const double l = finite ? sym4_lambda_max(k00, k01, k02, k03, k11, k12, k13, k22, k23, k33) : 0.0;
-            const double msd = (Ga + Gb - 2.0 * l) / N;
-            out[s0 + lane] = finite ? (float)sqrt(msd > 0.0 ? msd : 0.0) : __builtin_nanf("");
+            double c0, c1, c2, Ga;
+            const Sym4 K = struct_frame_key(xs, rc, N, finite, c0, c1, c2, Ga);
+            const double l = finite ? sym4_jacobi<false>(K) : 0.0;
+            out[s0 + lane] = finite ? kabsch_rmsd(Ga, Gb, l, N) : __builtin_nanf("");
         }
     });
 }

@@ -30,7 +30,7 @@
 // v_mfma_f64_16x16x4_f64 operands: A[i][k] = lane (i = lane & 15, k = lane >> 4), B[k][j] likewise, one f64 each;
 // C/D: register r of lane l is D[row = (l >> 4) + 4 r][col = l & 15] -- NOT the f32 16x16x4 map (row = 4 (l >> 4) + r).
 #pragma once
-#include "dff_internal.h"
+#include "dff_struct.hip"   // struct_tiles, struct_dihedral, pwd_dist2
 
 #define DFF_TICA_T 64          // output tile edge (features)
 #define DFF_TICA_K 32          // pairs per LDS stage
