@@ -14,6 +14,22 @@ CPU restatements of the reference's sampling hot path (microsoft/two-for-one-dif
   reference's state-dict layout.  The shipped checkpoints are absent from the reference
   mount (``/root/reference/.MISSING_LARGE_BLOBS:7-15``), so parity is pinned on these.
 
+* ``pwd_metric``      -- numpy restatement of the reference's pairwise-distance Jensen-Shannon
+  metric in torch's float32 arithmetic, pinned by ``tests/golden/pwd_*.npz``.
+* ``noise``           -- the in-kernel noise stream on the host: Philox4x32-10 and Box-Muller.
+* ``struct_metric``   -- float64 numpy oracles of the structure kernels: dihedrals, TIC features
+  and projection, contacts (torch's float32 formula), and the one Kabsch superposition by SVD
+  (``kabsch64`` per frame, ``kabsch64_batch``, ``kabsch_matrix``, ``superpose64`` / ``stats64``
+  with Horn's eigenvalue gap).
+* ``tica_fit``        -- float64 sums of ``dff_tica_moments`` and the model comparisons of the
+  TICA tests.
+* ``states``          -- float64 restatements of the nearest-centre rule, Lloyd's loop and the
+  transition counts (deeptime's documented semantics).
+* ``frames``          -- the seeded input generators of the analysis tests (rotations, walks,
+  needles, chains, Ornstein-Uhlenbeck trajectories, blobs, labels).
+
+The analysis modules need numpy and torch-CPU only and never import ``dff_amd``.
+
 Pinning: the reference has no tests / golden vectors for this path.  The
 twin is pinned against the reference ITSELF, imported in the build container, by
 ``tests/golden/make_golden.py``; the resulting input/output vectors are committed under

@@ -1,0 +1,133 @@
+"""What the test modules share that is not an oracle (those are in oracle/): the device fixture and the lazy accessors of
+the package, the upload helpers, the constants and bars that more than one file holds a kernel to, and the assertions on
+top of them.  Fixtures are imported by name (`from support import dev  # noqa: F401`).  Pytest does not rewrite the
+asserts of this module, so each of them carries the values it compares in its message."""
+import argparse
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import reference_twin as twin
+from oracle import synth
+
+MOLS = ["chignolin", "trp_cage", "bba", "villin", "protein_g"]
+N_BEADS = {"chignolin": 10, "trp_cage": 20, "bba": 28, "villin": 35, "protein_g": 56}
+RMSD_ATOL, RMSD_RTOL = 1e-5, 1e-6          # the bar of test_struct_metrics.py::test_rmsd_vs_kabsch
+MIRROR = np.array([-1.0, 1.0, 1.0])
+GAP_MIN = 1e-2            # strict superposition comparisons run on frames with (l1 - l2) / (l1 - l4) >= GAP_MIN
+MAX_EXCLUDED = 0.02       # at most this share of a data set may fall below it
+GUARD = 2.0        # rel(hip, ref64) <= GUARD * rel(ref32, ref64): the split engine (every shipped architecture's default path)
+GUARD_FP32 = 2.5   # ... the fp32-MFMA engine (DFF_SPLIT_BF16=0, `gen` branches, hidden 256)
+
+
+# ---------------------------------------------------------------- the package and the device
+@pytest.fixture(scope="module")
+def dev():
+    import dff_amd
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    dff_amd.load_library()
+    return torch.device("cuda:0")
+
+
+def B():
+    from dff_amd import binding
+    return binding
+
+
+def ev():
+    from dff_amd import evaluate
+    return evaluate
+
+
+def up(a, dev):
+    """a copy of the host frames on the device (the shared sets are read-only)"""
+    return torch.tensor(np.asarray(a), dtype=torch.float32, device=dev)
+
+
+def to_dev(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return (t if dtype is None else t.to(dtype)).cuda()
+
+
+def on_device(x, dev, vec4):
+    """x on the device at a 16-byte aligned address (vec4) or 4 bytes past one (the kernels' scalar tile loads)"""
+    flat = torch.empty(x.size + 4, dtype=torch.float32, device=dev)
+    off = 0 if vec4 else 1
+    assert flat.data_ptr() % 16 == 0, f"a fresh allocation at {flat.data_ptr():#x} is not 16-byte aligned"
+    t = flat[off:off + x.size].view(x.shape)
+    t.copy_(torch.from_numpy(x))
+    assert x.size == 0 or (t.data_ptr() % 16 == 0) == vec4, f"vec4 {vec4} but the view is at {t.data_ptr():#x}"
+    return t
+
+
+# ---------------------------------------------------------------- golden frames
+def x_rmsd(g):
+    x = g["x"].copy()
+    x[tuple(g["nonfinite_at"].T)] = g["nonfinite_val"]
+    return x
+
+
+def golden_frames(golden, mol):
+    """(frames with the golden's injected non-finite coordinates, folded structure float32)"""
+    f = golden("struct_folded.npz")[mol].astype(np.float32)
+    x = golden("struct_ref_ala2.npz")["x"] if mol == "ala2" else x_rmsd(golden(f"struct_ref_{mol}.npz"))
+    return x, f
+
+
+# ---------------------------------------------------------------- bars
+def assert_rmsd(got, ref, what=""):
+    got = np.asarray(got, np.float64)
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), (f"{what}: NaN at frames {np.flatnonzero(np.isnan(got))[:8]}, "
+                                                           f"the oracle's at {np.flatnonzero(np.isnan(ref))[:8]}")
+    ok = ~np.isnan(ref)
+    err = np.abs(got[ok] - ref[ok])
+    bad = err > RMSD_ATOL + RMSD_RTOL * ref[ok]
+    assert not bad.any(), (f"{what}: {bad.sum()} of {ok.sum()} frames off, worst |err| {err.max():.3e} A "
+                           f"at rmsd {ref[ok][np.argmax(err)]:.3e}")
+
+
+def assert_close(got, want, what=""):
+    got = np.asarray(got, np.float64)
+    assert got.shape == want.shape, f"{what}: shape {got.shape}, the oracle's {want.shape}"
+    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: {np.isnan(got).sum()} NaN, the oracle has {np.isnan(want).sum()}"
+    ok = ~np.isnan(want)
+    err = np.abs(got[ok] - want[ok])
+    bad = err > RMSD_ATOL + RMSD_RTOL * want[ok]
+    worst = err.max() if err.size else 0.0
+    print(f"{what}: {ok.sum()} pairs, worst |err| {worst:.3e} A")
+    assert not bad.any(), f"{what}: {bad.sum()} of {ok.sum()} pairs off, worst |err| {worst:.3e} A"
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def guard_for(kname):
+    """The bar that goes with the kernel that ran (its name says which engine multiplied the weights)."""
+    return GUARD if "split_" in kname else GUARD_FP32
+
+
+# ---------------------------------------------------------------- a model on disk
+def write_model_dir(path, cfg, decoder_scale=1e-2):
+    """A saved_models/<mol>-style directory in the reference's format: args.pickle (argparse
+    Namespace that also pickles an nn.Module, as the shipped ones do) + model-best.pt whose
+    ["ema"] entry is an EMA(GaussianDiffusion) state-dict (trainer.py:181-206, sample.py:154-167)."""
+    mol, N, H, L = synth.SHIPPED_CONFIGS[cfg]
+    ns = argparse.Namespace(mol=mol, mean0=True, fold=1, shuffle_data_before_splitting=True, scale_data=True,
+                            backbone_network="graph-transformer", hidden_features_gnn=H, num_layers_gnn=L,
+                            use_intrinsic_coords=True, use_abs_coords=False, use_distances=False, conservative=True,
+                            diffusion_steps=1000, loss_weights="higheruntil_100", activation=torch.nn.Tanh())
+    with open(path / "args.pickle", "wb") as f:
+        pickle.dump(ns, f)
+    params = synth.synth_gnn_params(N, H, L, decoder_scale=decoder_scale)
+    gd = {k: v.clone() for k, v in twin.make_schedule().items()}
+    gd["p2_loss_weight"] = torch.ones(1000)
+    gd.update({"model." + k: torch.from_numpy(v) for k, v in params.items()})
+    ema = {"initted": torch.tensor([True]), "step": torch.tensor([123])}
+    ema.update({"ema_model." + k: v for k, v in gd.items()})
+    ema.update({"online_model." + k: torch.zeros_like(v) for k, v in gd.items()})
+    torch.save({"step": 123, "model": {k: torch.zeros_like(v) for k, v in gd.items()}, "ema": ema}, path / "model-best.pt")
+    return params, (N, H, L)

@@ -25,6 +25,7 @@ import torch
 
 from oracle import noise
 from oracle import synth
+from support import guard_for, rel, write_model_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -298,7 +299,6 @@ def test_regenerated_target_equals_supplied_draws(name):
 # ------------------------------------------------------------------------------------------------ 4: against the reference
 def reference_bounds(g, kname, out64, z, fwd=False):
     """Per-sample (l1, l2) bounds from the score bar (module docstring)."""
-    from test_gpu_parity import guard_for, rel
     o32 = g["fwd_out32" if fwd else "out32"]
     bar = guard_for(kname) * rel(o32, out64)
     B, N = out64.shape[:2]
@@ -310,7 +310,6 @@ def reference_bounds(g, kname, out64, z, fwd=False):
 @pytest.mark.parametrize("cfg", ["ala2", "chignolin", "trp_cage"])
 def test_losses_against_the_reference(cfg, golden):
     from dff_amd.ddpm import GaussianDiffusion
-    from test_gpu_parity import rel
     g = golden(f"ploss_{cfg}.npz")
     model, N = get_model(cfg), n_beads(cfg)
     nat = model.native
@@ -399,8 +398,7 @@ def test_loss_profile_equals_explicit_p_losses():
 
 def test_tools_eval_loss_end_to_end(tmp_path, capsys):
     import tools_eval_loss
-    from test_gpu_parity import _write_model_dir
-    params, (N, H, L) = _write_model_dir(tmp_path, "chignolin")
+    params, (N, H, L) = write_model_dir(tmp_path, "chignolin")
     data = (synth.normal((12, N, 3), 556, 1) * 3.113133430480957).astype(np.float32)
     np.save(tmp_path / "val.npy", data)
     out = tools_eval_loss.main(["--model_path", str(tmp_path), "--data", str(tmp_path / "val.npy"), "--levels", "0:60:20",

@@ -1,8 +1,8 @@
 """Nearest-structure RMSD between two ensembles on the GPU (dff_rmsd_matrix, dff_rmsd_nearest; csrc/dff_ensemble.hip).
 
-The reference throughout is the float64 Kabsch / SVD model of test_struct_edges.py (kabsch64_batch, with the determinant
-correction), applied once per candidate, at that file's bar: |err| <= RMSD_ATOL + RMSD_RTOL * rmsd.  Bead counts 4 and 64
-are the limits, 5, 10 and 35 need the zero-padded k-steps; frame counts 1, 15, 16, 17, 65, 257 cross the 16-frame MFMA
+The reference throughout is the float64 Kabsch / SVD model of oracle/struct_metric.py (kabsch64_batch, with the determinant
+correction), applied once per candidate (kabsch_matrix), at the bar of tests/support.py: |err| <= RMSD_ATOL + RMSD_RTOL * rmsd.
+Bead counts 4 and 64 are the limits, 5, 10 and 35 need the zero-padded k-steps; frame counts 1, 15, 16, 17, 65, 257 cross the 16-frame MFMA
 tile, the 32-candidate workgroup tile, the 64-lane wave and one workgroup.  The value of a pair does not depend on what
 else is in the call, so the small shapes are checked bit for bit against blocks of the 257 x 257 matrix, and that matrix
 once against Kabsch."""
@@ -13,54 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-from test_struct_edges import MIRROR, RMSD_ATOL, RMSD_RTOL, kabsch64_batch, needle, rand_rot
-from test_struct_metrics import x_rmsd
+from oracle.frames import needle, rand_rot, walks
+from oracle.struct_metric import kabsch_matrix
+from support import MIRROR, RMSD_ATOL, RMSD_RTOL, B, assert_close, dev, up, x_rmsd  # noqa: F401  (dev: fixture)
 
 pytestmark = pytest.mark.gpu
 
 BEADS = [4, 5, 10, 35, 64]
 COUNTS = [1, 15, 16, 17, 65, 257]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
-def B():
-    from dff_amd import binding
-    return binding
-
-
-def walks(rng, n, N):
-    """random walks with 3.8 A bonds, each at a random place: float32 (n, N, 3)"""
-    step = rng.standard_normal((n, N, 3))
-    step *= 3.8 / np.linalg.norm(step, axis=-1, keepdims=True)
-    return (np.cumsum(step, 1) + 20 * rng.standard_normal((n, 1, 3))).astype(np.float32)
-
-
-def kabsch_matrix(x, y):
-    """(n, m) float64: kabsch64_batch(x, y[r]) for every candidate r; NaN columns for non-finite candidates"""
-    out = np.full((len(x), len(y)), np.nan)
-    for r, ref in enumerate(y):
-        if np.isfinite(ref).all():
-            out[:, r] = kabsch64_batch(x, ref)
-    return out
-
-
-def assert_close(got, want, what=""):
-    got = np.asarray(got, np.float64)
-    assert got.shape == want.shape, what
-    assert np.array_equal(np.isnan(got), np.isnan(want)), what
-    ok = ~np.isnan(want)
-    err = np.abs(got[ok] - want[ok])
-    bad = err > RMSD_ATOL + RMSD_RTOL * want[ok]
-    worst = err.max() if err.size else 0.0
-    print(f"{what}: {ok.sum()} pairs, worst |err| {worst:.3e} A")
-    assert not bad.any(), f"{what}: {bad.sum()} of {ok.sum()} pairs off, worst |err| {worst:.3e} A"
 
 
 def row_min(M):
@@ -73,11 +33,6 @@ def row_min(M):
     val = M[np.arange(len(M)), idx]
     none = np.isnan(M).all(1)
     return np.where(none, np.float32(np.nan), val).astype(np.float32), np.where(none, -1, idx)
-
-
-def up(a, dev):
-    """a copy of the host frames on the device (the shared sets are read-only)"""
-    return torch.tensor(np.asarray(a), dtype=torch.float32, device=dev)
 
 
 def matrix(x, y, dev):

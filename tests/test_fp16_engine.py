@@ -30,10 +30,10 @@ import torch
 
 from oracle import reference_twin as twin
 from oracle import synth
+from support import GUARD, GUARD_FP32, rel
 
 pytestmark = pytest.mark.gpu
 
-GUARD, GUARD_FP32 = 2.0, 2.5   # tests/test_gpu_parity.py
 NORM_STD = {"chignolin": 3.113133430480957, "villin": 6.082900047302246}
 TEMP = {"chignolin": 340, "villin": 360}
 
@@ -44,11 +44,6 @@ def dff():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     dff_amd.load_library()
     return dff_amd
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
 def bf16_grid(w):

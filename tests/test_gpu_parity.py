@@ -22,6 +22,7 @@ import torch
 from oracle import kernel_model as km
 from oracle import reference_twin as twin
 from oracle import synth
+from support import GUARD, GUARD_FP32, guard_for, rel, write_model_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -54,19 +55,7 @@ def get_model(dff, cfg, decoder_scale=1.0):
     return _models[key]
 
 
-GUARD = 2.0        # rel(hip, ref64) <= GUARD * rel(ref32, ref64): the split engine (every shipped architecture's default path)
-GUARD_FP32 = 2.5   # ... the fp32-MFMA engine (DFF_SPLIT_BF16=0, `gen` branches, hidden 256)
-
-
-def guard_for(kname):
-    """The bar that goes with the kernel that ran (its name says which engine multiplied the weights)."""
-    return GUARD if "split_" in kname else GUARD_FP32
 STEP_TOL = 5e-6    # per fused step, relative to the trajectory's largest entry
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
 def twin_refs(params, x, t, L):
@@ -332,34 +321,10 @@ def test_iid_sample_properties(dff):
     assert a.std().item() > 1e-3
 
 
-def _write_model_dir(path, cfg, decoder_scale=1e-2):
-    """A saved_models/<mol>-style directory in the reference's format: args.pickle (argparse
-    Namespace that also pickles an nn.Module, as the shipped ones do) + model-best.pt whose
-    ["ema"] entry is an EMA(GaussianDiffusion) state-dict (trainer.py:181-206, sample.py:154-167)."""
-    import argparse
-    import pickle
-    mol, N, H, L = synth.SHIPPED_CONFIGS[cfg]
-    ns = argparse.Namespace(mol=mol, mean0=True, fold=1, shuffle_data_before_splitting=True, scale_data=True,
-                            backbone_network="graph-transformer", hidden_features_gnn=H, num_layers_gnn=L,
-                            use_intrinsic_coords=True, use_abs_coords=False, use_distances=False, conservative=True,
-                            diffusion_steps=1000, loss_weights="higheruntil_100", activation=torch.nn.Tanh())
-    with open(path / "args.pickle", "wb") as f:
-        pickle.dump(ns, f)
-    params = synth.synth_gnn_params(N, H, L, decoder_scale=decoder_scale)
-    gd = {k: v.clone() for k, v in twin.make_schedule().items()}
-    gd["p2_loss_weight"] = torch.ones(1000)
-    gd.update({"model." + k: torch.from_numpy(v) for k, v in params.items()})
-    ema = {"initted": torch.tensor([True]), "step": torch.tensor([123])}
-    ema.update({"ema_model." + k: v for k, v in gd.items()})
-    ema.update({"online_model." + k: torch.zeros_like(v) for k, v in gd.items()})
-    torch.save({"step": 123, "model": {k: torch.zeros_like(v) for k, v in gd.items()}, "ema": ema}, path / "model-best.pt")
-    return params, (N, H, L)
-
-
 def test_cli_end_to_end(dff, tmp_path):
     """sample.py flags, input files and output files of the reference (sample.py:101-249)."""
     from dff_amd import cli
-    params, (N, H, L) = _write_model_dir(tmp_path, "chignolin")
+    params, (N, H, L) = write_model_dir(tmp_path, "chignolin")
     out = cli.main(["--model_path", str(tmp_path), "--gen_mode", "iid", "--num_samples_eval", "10",
                     "--batch_size_gen", "4", "--seed", "3"])
     f = tmp_path / "main_eval_output_iid" / "sample-iid.pt"
@@ -387,7 +352,7 @@ def test_cli_end_to_end(dff, tmp_path):
 
 def test_checkpoint_loading_matches_direct_params(dff, tmp_path):
     from dff_amd import cli
-    params, (N, H, L) = _write_model_dir(tmp_path, "ala2", decoder_scale=1.0)
+    params, (N, H, L) = write_model_dir(tmp_path, "ala2", decoder_scale=1.0)
     args = cli.load_training_args(str(tmp_path))
     ddpm, mol = cli.build_diffusion(args, str(tmp_path), "best", torch.device("cuda", 0))
     assert ddpm.norm_factor == 0.9449278712272644 and mol.n_beads == 5
@@ -887,7 +852,7 @@ def test_two_ranks_on_one_gpu_equal_one_rank(dff, tmp_path, mode, monkeypatch):
     import subprocess
     import sys
     from dff_amd import cli
-    params, (N, H, L) = _write_model_dir(tmp_path, "chignolin")
+    params, (N, H, L) = write_model_dir(tmp_path, "chignolin")
     # (ranks that share a GPU run the one-workgroup kernels -- sampling.dist_env, DFF_PAIR=0 -- and so does the one-rank reference
     # here: the two-workgroups variants sum a protein's heads in another order)
     monkeypatch.setenv("DFF_PAIR", "0")

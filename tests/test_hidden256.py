@@ -9,6 +9,7 @@ import torch
 from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
+from support import rel
 
 SHAPES = {"smoke": (10, 256, 5, False), "cons": (20, 256, 2, True)}   # N, H, L, conservative
 
@@ -16,11 +17,6 @@ SHAPES = {"smoke": (10, 256, 5, False), "cons": (20, 256, 2, True)}   # N, H, L,
 def params_for(name, decoder_scale=1.0):
     N, H, L, cons = SHAPES[name]
     return synth.synth_gnn_params(N, H, L, seed=2560 + N, decoder_scale=decoder_scale, decoder_out=1 if cons else 3)
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
 # ------------------------------------------------------------------ CPU

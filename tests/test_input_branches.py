@@ -11,6 +11,7 @@ from oracle import cpu_repro
 from oracle import kernel_model_gen as kg
 from oracle import reference_twin as twin
 from oracle import synth
+from support import rel
 
 COMBOS = [(0, 1, 1), (1, 1, 1), (1, 0, 1), (1, 1, 0), (0, 1, 0)]
 CFGS = ["chignolin", "trp_cage"]
@@ -20,11 +21,6 @@ SEED = 2468
 def params_for(cfg, intr, dist, ab):
     _, N, H, L = synth.SHIPPED_CONFIGS[cfg]
     return synth.synth_gnn_params(N, H, L, seed=SEED, node_in=N + 1 + 3 * ab, edge_in=(3 * intr + dist) or 1), (N, H, L)
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
 @pytest.mark.parametrize("cfg", CFGS)
@@ -88,7 +84,7 @@ def test_hip_forces_vs_reference(cfg, flags, golden):
         print(f"{cfg} intr={intr} dist={dist} abs={ab} [{name}] {model.native.last_launch()[0]}: rel64 {r64:.2e} abs32 {a32:.2e}")
         assert "gen" in model.native.last_launch()[0]
         np.testing.assert_allclose(e, g["energy32"], rtol=0, atol=2e-5 * max(1.0, np.abs(g["energy32"]).max()))
-        # round 6: the hot path's bar (tests/test_gpu_parity.py GUARD_FP32) instead of an absolute 2e-5 -- the `gen` kernels sit at
+        # round 6: the hot path's bar (tests/support.py GUARD_FP32) instead of an absolute 2e-5 -- the `gen` kernels sit at
         # 0.75 - 0.9 x the reference's own float32 distance in the median over 479 random models (profiles/r05/fuzz*.txt; <= 2.2 x up
         # to 1.5 sigma); what is ill-conditioned is the INPUT at >= 3 sigma with distance features, for the reference's float32
         # run as much as for this one (profiles/r06/gen_conditioning.txt, tests/gen_conditioning.py)

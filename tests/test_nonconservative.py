@@ -9,6 +9,7 @@ import torch
 from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
+from support import rel
 
 CFGS = ["ala2", "chignolin", "trp_cage", "villin"]
 
@@ -16,11 +17,6 @@ CFGS = ["ala2", "chignolin", "trp_cage", "villin"]
 def params_for(cfg, decoder_scale=1.0):
     _, N, H, L = synth.SHIPPED_CONFIGS[cfg]
     return synth.synth_gnn_params(N, H, L, seed=4321, decoder_scale=decoder_scale, decoder_out=3), (N, H, L)
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
 
 
 # ------------------------------------------------------------------ CPU

@@ -1,9 +1,8 @@
 """States in TIC space and the transitions between them (csrc/dff_states.hip, evaluate.KMeans /
 StateTransitionEvaluator): the dynamics analysis of the reference's evaluate_fastfolders.ipynb, cells 20-24.
 
-Every oracle is float64 numpy written in this file.  deeptime is not installed, so MiniBatchKMeans and
-TransitionCountEstimator are restated from their documented semantics (nearest centre, lowest index on a tie;
-every pair (t, t + lag) inside a discrete trajectory).
+Every oracle is float64 numpy (oracle/states.py: deeptime is not installed, so MiniBatchKMeans and
+TransitionCountEstimator are restated there from their documented semantics).
 
 Labels are compared with the argmin of float64 distances computed from dff_struct_tic's projections.  A frame whose
 best and second-best squared distance differ by less than 1e-9 relative is a legitimate disagreement of summation
@@ -20,22 +19,15 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from oracle.frames import blobs, chain_frames, two_state_trajectories
+from oracle.states import counts64, dist2_64, lloyd64
+from support import dev, ev, on_device  # noqa: F401  (dev: fixture)
 
 AMBIGUOUS_REL = 1e-9
 AMBIGUOUS_CAP = 1e-5
 
 
-def ev():
-    from dff_amd import evaluate
-    return evaluate
-
-
-# ================================================================ oracles (float64 numpy)
-def dist2_64(p, centers):
-    p, c = np.asarray(p, np.float64), np.asarray(centers, np.float64)
-    return ((p[:, None, :] - c[None, :, :]) ** 2).sum(-1)
-
-
+# ================================================================ the label rule
 def check_labels(labels, p, centers):
     """labels == argmin of the float64 distances, but for the (capped) frames whose two best distances nearly tie;
     returns the oracle's labels with those frames taken from `labels`."""
@@ -57,48 +49,6 @@ def check_labels(labels, p, centers):
     assert np.array_equal(labels[~amb], want[~amb])
     assert np.all((labels[amb] >= 0) & (labels[amb] < K))
     return np.where(amb, labels, want).astype(np.int64)
-
-
-def counts64(labels, lengths, lags, K):
-    labels = np.asarray(labels, np.int64)
-    C = np.zeros((len(lags), K, K), np.int64)
-    skipped = np.zeros(len(lags), np.int64)
-    o = 0
-    for L in lengths:
-        seg = labels[o:o + L]
-        o += L
-        for li, lag in enumerate(lags):
-            if L > lag:
-                a, b = seg[:-lag], seg[lag:]
-                ok = (a >= 0) & (b >= 0)
-                np.add.at(C[li], (a[ok], b[ok]), 1)
-                skipped[li] += int((~ok).sum())
-    return C, skipped
-
-
-def lloyd64(p, centers, max_iter, tol):
-    """KMeans.fit's documented loop; returns (centres, n_iter, inertia of the final centres)."""
-    p, c = np.asarray(p, np.float64), np.array(centers, np.float64)
-    prev, n_iter = None, 0
-    for _ in range(max_iter):
-        d2 = dist2_64(p, c)
-        lab = d2.argmin(1)
-        inertia = d2[np.arange(len(p)), lab].sum()
-        for k in range(len(c)):
-            if np.any(lab == k):
-                c[k] = p[lab == k].sum(0) / (lab == k).sum()
-        n_iter += 1
-        if prev is not None and abs(prev - inertia) <= tol * prev:
-            break
-        prev = inertia
-    return c, n_iter, dist2_64(p, c).min(1).sum()
-
-
-def blobs(K, d, per, seed, sep=50.0, sigma=0.5):
-    rng = np.random.default_rng(seed)
-    true = (rng.permutation(K)[:, None] * sep + rng.uniform(5.0, 15.0, (K, d)))
-    which = rng.integers(0, K, K * per)
-    return true, true[which] + rng.standard_normal((K * per, d)) * sigma, which
 
 
 # ================================================================ CPU
@@ -171,30 +121,6 @@ def test_refusals_without_device():
 
 
 # ================================================================ GPU
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
-def chain_frames(n, N, seed):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal((n, N, 3)) * 4 + np.arange(N)[None, :, None] * 3.0).astype(np.float32)
-
-
-def on_device(x, dev, vec4):
-    """x on the device at a 16-byte aligned address (vec4) or 4 bytes past one (the kernels' scalar tile loads)"""
-    flat = torch.empty(x.size + 4, dtype=torch.float32, device=dev)
-    off = 0 if vec4 else 1
-    assert flat.data_ptr() % 16 == 0
-    t = flat[off:off + x.size].view(x.shape)
-    t.copy_(torch.from_numpy(x))
-    assert x.size == 0 or (t.data_ptr() % 16 == 0) == vec4
-    return t
-
-
 def tic_model(N, k, seed, x):
     """a random projection whose coordinates are O(1) on the frames x, and K centres among the projected frames"""
     from dff_amd import binding
@@ -384,27 +310,6 @@ def test_transition_counts(dev, K, lags):
     # no frames at all
     z = binding.transition_counts(torch.empty(0, dtype=torch.int32, device=dev), [], lags, K)
     assert z.shape == (len(lags), K, K) and not z.any()
-
-
-def two_state_trajectories(folded, lengths, seed, amp=4.0, sigma=0.4):
-    """seeded Ornstein-Uhlenbeck trajectories around a folded structure, as tests/test_tica_fit.py builds them (3N
-    modes of a random orthonormal basis with autocorrelations from 0.995 to 0.6 per frame), the slowest mode driving a
-    two-state switch: the structure is displaced by +-amp along that mode according to the sign of its OU coordinate."""
-    rng = np.random.default_rng(seed)
-    f = np.asarray(folded, np.float64).reshape(-1)
-    D = f.size
-    Q, _ = np.linalg.qr(rng.standard_normal((D, D)))
-    rho = np.geomspace(0.995, 0.6, D)
-    out = []
-    for L in lengths:
-        z = np.empty((L, D))
-        z[0] = rng.standard_normal(D) * sigma
-        eps = rng.standard_normal((L, D)) * sigma * np.sqrt(1 - rho ** 2)
-        for t in range(1, L):
-            z[t] = rho * z[t - 1] + eps[t]
-        z[:, 0] = np.where(z[:, 0] > 0, amp, -amp) + 0.25 * z[:, 0]
-        out.append((f + z @ Q.T).reshape(L, -1, 3).astype(np.float32))
-    return out
 
 
 @pytest.mark.gpu

@@ -1,212 +1,29 @@
-"""Every ABI call is ordered on the caller's stream, and only on it (include/dff.h: "calls enqueue on `stream` ... and do not
-synchronise"; README: "the launch path never synchronises").
-
-Every other GPU test runs on PyTorch's default stream, where a memset, a copy or a launch that went to the null stream, or a
-stray device synchronisation, changes nothing.  Here every call runs on a side stream behind a GATE: torch.cuda._sleep, a
-device-side spin that involves none of this project's code.  Behind the gate, on the same stream, the real inputs are copied
-over buffers that hold POISON (a legal input that gives another output: NaN coordinates, constant labels / levels / bin counts,
-other finite constants for limits, means and matrices -- never an index out of range) and the outputs are filled with a
-SENTINEL (123.0, 0x7b7b7b7b).  Anything the call enqueues elsewhere runs during the gate: a misplaced kernel reads poison or
-is overwritten by the sentinel fill, a misplaced zeroing memset leaves sentinel + counts, a copy not ordered after its producer
-copies stale data.  The result must equal the default-stream result bit for bit (run twice there, so that a non-deterministic
-call cannot pass by luck), no sentinel may survive where the call writes, and -- for every call that is not in BLOCKING -- the
-call must have returned while the gate was still spinning (the gate's event not yet complete): it synchronised nothing.  The
-failure of a misordered call is deterministic; nothing here tries to win a race.  test_control_* shows that the harness itself
-sees work on the wrong stream.
+"""Every ABI call is ordered on the caller's stream, and only on it, by the protocol of tests/stream_gate.py (the gate, the
+poison, the sentinel and what is asserted are described there): the harness's own controls, the model calls, the forward
+process, the analysis calls, and two calls on two streams at once.  (dff_superpose: tests/test_superpose.py.)
 
 The model calls run on the kernel variants of tests/test_noise_stream.py (same synthetic models, same knobs; every case asserts
 the kernel that ran).  A fresh model's first call ("cold") allocates, builds the layer-0 table and synchronises the stream:
 only its results are asserted; the identical second call ("warm") on the same model and stream must not block.
-
-The gate is a stimulus, not a tolerance: about 100 ms against the tens of microseconds of an enqueue; a calibration that gives
-less than 50 ms fails every test with "gate too short".
-MEASURED on the MI355X: _sleep of 2 000 000 cycles = 0.847 ms, of 20 000 000 cycles = 8.335 ms -> 2.404e6 cycles / ms (the 2.4 GHz
-shader clock); the gate of 240 362 198 cycles = 100.0 ms.
-MEASURED on the MI355X: every call of this file returned inside its gate except the cold model calls (BLOCKING); a test takes
-0.25 - 0.45 s (two gates and a model upload for the model calls), the file 18 s.
 """
 import contextlib
 import ctypes as C
 
 import numpy as np
 import pytest
+import torch
 
 from oracle import synth
+from oracle.frames import splitmix_labels, synth_chain_frames
+from stream_gate import BLOCKING, GATE_MIN_MS, N_FRAMES, Run, Spec, analysis_call, gated, ptr, raw, reference, stream_of
+from stream_gate import gate, side  # noqa: F401  (fixtures)
+from support import to_dev
 
 pytestmark = pytest.mark.gpu
 
-# Calls that must block the host, with the reason (include/dff.h says so for each).  Everything else in this file is asserted
-# to return while its gate is still spinning.  A WARM dff_score / dff_langevin_run / dff_ddpm_run may not be listed here.
-BLOCKING = {
-    ("dff_score", "cold"): "the first call at a batch size grows the model's scratch (hipFree / hipMalloc)",
-    ("dff_langevin_run", "cold"): "the first call at a noise level builds the layer-0 table: allocations, a host-to-device copy of "
-                                  "the levels and stream synchronisations between its chunks",
-    ("dff_ddpm_run", "cold"): "as dff_langevin_run, one table entry per noise level",
-}
-
-GATE_MS = 100.0          # the gate aimed at
-GATE_MIN_MS = 50.0       # "gate too short" below this
-F_SENTINEL = 123.0
-I_SENTINEL = 0x7B7B7B7B
 SEED = (0x9E3779B9 << 32) | 0x2545F491
 HI = 2 ** 32
 T = 1000
-
-
-def _torch():
-    import torch
-    return torch
-
-
-# ------------------------------------------------------------------------------------------------ the gate
-class Gate:
-    def __init__(self, rate, cycles, ms):
-        self.rate, self.cycles, self.ms = rate, cycles, ms
-
-
-def _time_sleep(stream, cycles):
-    torch = _torch()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(stream):
-        e0.record()
-        torch.cuda._sleep(int(cycles))
-        e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-@pytest.fixture(scope="module")
-def gate():
-    """torch.cuda._sleep alone at two cycle counts -> cycles per millisecond -> the cycle count of a GATE_MS gate, timed once."""
-    torch = _torch()
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    s = torch.cuda.Stream()
-    _time_sleep(s, 1000)                       # (loads the spin kernel)
-    c1, c2 = 2_000_000, 20_000_000
-    t1, t2 = _time_sleep(s, c1), _time_sleep(s, c2)
-    rate = (c2 - c1) / max(t2 - t1, 1e-6)      # cycles per ms
-    cycles = int(rate * GATE_MS)
-    ms = _time_sleep(s, cycles)
-    print(f"[stream] _sleep: {c1} cycles = {t1:.3f} ms, {c2} cycles = {t2:.3f} ms -> {rate:.4g} cycles / ms; "
-          f"gate of {cycles} cycles = {ms:.1f} ms")
-    return Gate(rate, cycles, ms)
-
-
-# ------------------------------------------------------------------------------------------------ one gated call
-class Spec:
-    """One call: `ins` name -> (real device tensor, poison: a scalar or a tensor), `outs` name -> (shape, dtype) of the pure
-    outputs, `inout` the inputs the call also writes, `work` name -> workspace tensor, fn(nat, bufs) the call itself on the
-    current stream (nat: the model, None for the stateless calls), `unwritten` the outputs whose sentinel may survive,
-    wrap(nat, bufs) -> name -> tensor: the binding's allocating wrapper of the same call, when it reads nothing back."""
-
-    def __init__(self, name, ins, outs, fn, inout=(), work=None, unwritten=(), wrap=None):
-        self.name, self.ins, self.outs, self.fn, self.inout = name, ins, outs, fn, tuple(inout)
-        self.work, self.unwritten, self.wrap = work or {}, tuple(unwritten), wrap
-
-    @property
-    def results(self):
-        return tuple(self.outs) + self.inout
-
-
-def _sentinel(dtype):
-    return F_SENTINEL if dtype.is_floating_point else (0x7B if dtype == _torch().uint8 else I_SENTINEL)
-
-
-def _bits_equal(a, b):
-    torch = _torch()
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _poisoned(real, poison):
-    torch = _torch()
-    if isinstance(poison, torch.Tensor):
-        assert poison.shape == real.shape and poison.dtype == real.dtype
-        return poison.clone()
-    return torch.full_like(real, poison)
-
-
-def reference(spec, nat=None):
-    """Step 1: the call on the default stream with the real inputs, twice, bit-equal -> name -> result."""
-    torch = _torch()
-    runs = []
-    for _ in range(2):
-        bufs = {k: real.clone() for k, (real, _) in spec.ins.items()}
-        for k, (shape, dtype) in spec.outs.items():
-            bufs[k] = torch.full(shape, _sentinel(dtype), dtype=dtype, device="cuda")
-        bufs.update(spec.work)
-        spec.fn(nat, bufs)
-        torch.cuda.synchronize()
-        runs.append({k: bufs[k].clone() for k in spec.results})
-    for k in spec.results:
-        assert _bits_equal(runs[0][k], runs[1][k]), f"{spec.name}: {k} differs between two default-stream calls"
-    torch.cuda.synchronize()
-    return runs[0]
-
-
-class Run:
-    """Steps 2 - 4 of one gated call, split so that two of them can be in flight on two streams."""
-
-    def __init__(self, spec, nat=None):
-        torch = _torch()
-        self.spec, self.nat = spec, nat
-        self.real = {k: real.clone() for k, (real, _) in spec.ins.items()}
-        self.bufs = {k: _poisoned(real, poison) for k, (real, poison) in spec.ins.items()}
-        for k, (shape, dtype) in spec.outs.items():
-            self.bufs[k] = torch.zeros(shape, dtype=dtype, device="cuda")
-        self.bufs.update(spec.work)
-        self.got = {k: torch.empty_like(self.bufs[k]) for k in spec.results}
-        self.wrapped = None
-        self.ev_gate, self.ev_done = torch.cuda.Event(), torch.cuda.Event()
-        self.returned_early = None
-
-    def enqueue(self, stream, gate):
-        torch = _torch()
-        assert gate.ms >= GATE_MIN_MS, f"gate too short: {gate.ms:.1f} ms ({gate.cycles} cycles at {gate.rate:.4g} cycles / ms)"
-        spec = self.spec
-        with torch.cuda.stream(stream):
-            torch.cuda._sleep(gate.cycles)
-            self.ev_gate.record()
-            for k in spec.ins:
-                self.bufs[k].copy_(self.real[k])
-            for k, (_, dtype) in spec.outs.items():
-                self.bufs[k].fill_(_sentinel(dtype))
-            for k in spec.work:         # a workspace arrives dirty: zeros are what a minimum over keys cannot recover from
-                self.bufs[k].zero_()
-            spec.fn(self.nat, self.bufs)
-            self.returned_early = not self.ev_gate.query()      # step 5: before anything else touches the device
-            for k in spec.results:
-                self.got[k].copy_(self.bufs[k])
-            if spec.wrap is not None:
-                self.wrapped = spec.wrap(self.nat, self.bufs)
-            self.ev_done.record()
-        return self
-
-    def check(self, stream, ref, nonblocking, tag=""):
-        spec = self.spec
-        what = f"{spec.name}{tag}"
-        if nonblocking:
-            assert self.returned_early, f"{what}: the call returned only after the gate had finished: it synchronised"
-        stream.synchronize()
-        for k in spec.results:
-            assert _bits_equal(self.got[k], ref[k]), f"{what}: {k} on the side stream differs from the default-stream result"
-        for k, (_, dtype) in spec.outs.items():
-            if k not in spec.unwritten:
-                assert not bool((self.got[k] == _sentinel(dtype)).any()), f"{what}: a sentinel survives in {k}"
-        for k, v in (self.wrapped or {}).items():
-            assert _bits_equal(v, ref[k]), f"{what}: {k} of the binding's wrapper differs from the default-stream result"
-
-
-def gated(spec, stream, gate, ref, nat=None, nonblocking=True, tag=""):
-    torch = _torch()
-    run = Run(spec, nat)
-    torch.cuda.synchronize()
-    run.enqueue(stream, gate).check(stream, ref, nonblocking, tag)
-    return run
-
-
-@pytest.fixture(scope="module")
-def side():
-    return _torch().cuda.Stream()
 
 
 # ------------------------------------------------------------------------------------------------ the harness itself
@@ -214,7 +31,6 @@ def test_control_a_default_stream_op_does_not_wait_for_the_gate(gate, side):
     """No library call: with the gate queued on the side stream, y = x * 2 on the DEFAULT stream sees the poison (it ran during
     the gate), the same operation on the side stream sees the real value.  If side streams ever blocked the null stream here,
     the first assertion fails: this file cannot pass without testing anything."""
-    torch = _torch()
     assert gate.ms >= GATE_MIN_MS, f"gate too short: {gate.ms:.1f} ms"
     real = torch.arange(1024, dtype=torch.float32, device="cuda") + 1.0
     x = torch.full_like(real, -7.0)
@@ -239,7 +55,6 @@ def test_control_a_default_stream_op_does_not_wait_for_the_gate(gate, side):
 def test_control_the_protocol_catches_a_call_on_the_wrong_stream(gate, side):
     """The protocol on a stand-in `call` (plain torch): enqueued on the default stream instead of the current one it must fail
     the bit-equality, and one that synchronises must fail the non-blocking check."""
-    torch = _torch()
     real = torch.arange(256, dtype=torch.float32, device="cuda") * 0.5 + 0.25      # (x + 1 is never the sentinel)
 
     def good(_, b):
@@ -278,7 +93,6 @@ _params, _shared = {}, {}
 
 def new_native(name):
     """A fresh model (nothing warmed).  Synchronises (uploads): never behind a gate."""
-    torch = _torch()
     from dff_amd.score import GraphTransformer
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     N, H, L, (intr, dist, ab), cons, wseed = MODELS[name]
@@ -334,19 +148,12 @@ case_param = pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 noise_param = pytest.mark.parametrize("supplied", [False, True], ids=["philox", "supplied-noise"])
 
 
-def dev(a, dtype=None):
-    torch = _torch()
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
 def _centred(B, N, stream):
     x = synth.normal((B, N, 3), 20261, stream)
     return (x - x.mean(1, keepdims=True)).astype(np.float32)
 
 
 def score_spec(case):
-    torch = _torch()
     B, N = case.B, case.N
     from dff_amd import binding
 
@@ -358,7 +165,7 @@ def score_spec(case):
         f, e = nat.score(b["x"], b["tnorm"], return_energy=True)
         return {"force": f, "energy": e}
     tn = (0.02 + 0.9 * np.arange(B) / B).astype(np.float32)
-    return Spec("dff_score", {"x": (dev(_centred(B, N, 11) + np.float32(0.25)), float("nan")), "tnorm": (dev(tn), float("nan"))},
+    return Spec("dff_score", {"x": (to_dev(_centred(B, N, 11) + np.float32(0.25)), float("nan")), "tnorm": (to_dev(tn), float("nan"))},
                 {"force": ((B, N, 3), torch.float32), "energy": ((B, N), torch.float32)}, fn, wrap=wrap)
 
 
@@ -375,13 +182,12 @@ def _langevin_params(N):
 
 
 def langevin_spec(case, supplied):
-    torch = _torch()
     B, N = case.B, case.N
     p = _langevin_params(N)
-    ins = {"x": (dev(_centred(B, N, 12)), float("nan")),
-           "v": (dev((0.25 * synth.normal((B, N, 3), 20261, 13)).astype(np.float32)), float("nan"))}
+    ins = {"x": (to_dev(_centred(B, N, 12)), float("nan")),
+           "v": (to_dev((0.25 * synth.normal((B, N, 3), 20261, 13)).astype(np.float32)), float("nan"))}
     if supplied:
-        ins["noise"] = (dev(synth.normal((N_STEPS, B, N, 3), 20261, 14).astype(np.float32)), float("nan"))
+        ins["noise"] = (to_dev(synth.normal((N_STEPS, B, N, 3), 20261, 14).astype(np.float32)), float("nan"))
 
     def fn(nat, b):
         nat.langevin_run(p, b["x"], b["v"], N_STEPS, SAVE, noise=b.get("noise"), seed=SEED, traj_offset=case.offset,
@@ -396,11 +202,10 @@ T_START, T_END = 3, 0
 def ddpm_spec(case, supplied):
     """Levels 3 .. 0 from the in-kernel prior: x is an output (sentinel); the clamp flag is only ever SET, so it is an input too
     (real 0, poison 1)."""
-    torch = _torch()
     B, N = case.B, case.N
     ins = {"clamp_flag": (torch.zeros(1, dtype=torch.int32, device="cuda"), 1)}
     if supplied:
-        ins["noise"] = (dev(synth.normal((T_START - T_END + 1, B, N, 3), 20261, 15).astype(np.float32)), float("nan"))
+        ins["noise"] = (to_dev(synth.normal((T_START - T_END + 1, B, N, 3), 20261, 15).astype(np.float32)), float("nan"))
 
     def fn(nat, b):
         nat.ddpm_run(b["x"], T_START, T_END, noise=b.get("noise"), seed=SEED, sample_offset=case.offset, init_prior=True,
@@ -411,7 +216,6 @@ def ddpm_spec(case, supplied):
 def _model_call(case, spec, gate, side):
     """Reference on the shared model (default stream); then a FRESH model: the cold call behind a gate (results only), the
     identical warm call on the same model and stream (results, and it may not block)."""
-    torch = _torch()
     assert (spec.name, "warm") not in BLOCKING
     A = shared_native(case.model)
     with case.knobs(A):
@@ -457,14 +261,13 @@ def _forward_inputs(model, B, supplied):
     N = MODELS[model][0]
     x0 = (synth.normal((B, N, 3), 9090, 21) + np.array([0.4, -0.3, 0.2])).astype(np.float32)
     t = np.array([0, T - 1, 1, 500], np.int32)[np.arange(B) % 4]
-    ins = {"x0": (dev(x0), float("nan")), "t": (dev(t), 0)}
+    ins = {"x0": (to_dev(x0), float("nan")), "t": (to_dev(t), 0)}
     if supplied:
-        ins["noise"] = (dev(synth.normal((B, N, 3), 9090, 71).astype(np.float32)), float("nan"))
+        ins["noise"] = (to_dev(synth.normal((B, N, 3), 9090, 71).astype(np.float32)), float("nan"))
     return N, ins
 
 
 def q_sample_spec(model, B, supplied):
-    torch = _torch()
     from dff_amd import binding
     N, ins = _forward_inputs(model, B, supplied)
 
@@ -480,7 +283,6 @@ def q_sample_spec(model, B, supplied):
 
 
 def denoise_loss_spec(nat, model, B, supplied, loss_type="l2", wrapper=True):
-    torch = _torch()
     from dff_amd import binding
     N, ins = _forward_inputs(model, B, supplied)
     ins["total"] = (torch.tensor([0.25, 3.0], dtype=torch.float64, device="cuda"), float("nan"))
@@ -502,7 +304,6 @@ def denoise_loss_spec(nat, model, B, supplied, loss_type="l2", wrapper=True):
 
 
 def _forward_call(model, spec, gate, side):
-    torch = _torch()
     nat = shared_native(model)
     ref = reference(spec, nat)
     if spec.name == "dff_denoise_loss":
@@ -535,71 +336,45 @@ def test_denoise_loss_two_passes_over_one_workspace(gate, side):
 
 
 # ------------------------------------------------------------------------------------------------ the analysis calls
-N_FRAMES = 1000
 beads_param = pytest.mark.parametrize("N", [10, 35])
 
 
-def _frames(n, N, stream):
-    """Chain-like frames in Angstrom: beads 2 apart along x plus O(3) noise."""
-    return (synth.normal((n, N, 3), 777, stream) * 3 + np.arange(N)[None, :, None] * 2.0).astype(np.float32)
-
-
-def _raw(name, *args):
-    from dff_amd import binding
-    lib = binding.load_library()
-    binding._check(lib, getattr(lib, name)(*args), name)
-
-
-def _p(t):
-    from dff_amd import binding
-    return binding._ptr(t)
-
-
-def _st(t):
-    from dff_amd import binding
-    return binding._stream(t)
-
-
 def pwd_max_spec(N):
-    torch = _torch()
     from dff_amd import binding
     off = 3
     npairs = binding.pwd_num_pairs(N, off)
-    return Spec("dff_pwd_max", {"x": (dev(_frames(N_FRAMES, N, 31)), float("nan"))}, {"max": ((npairs,), torch.float32)},
-                lambda _, b: _raw("dff_pwd_max", 0, _p(b["x"]), N_FRAMES, N, off, _p(b["max"]), _st(b["x"])),
+    return Spec("dff_pwd_max", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 31)), float("nan"))}, {"max": ((npairs,), torch.float32)},
+                lambda _, b: raw("dff_pwd_max", 0, ptr(b["x"]), N_FRAMES, N, off, ptr(b["max"]), stream_of(b["x"])),
                 wrap=lambda _, b: {"max": binding.pwd_max(b["x"], off)})
 
 
 def pwd_hist_spec(N):
     """(raw call only: the wrapper reads the bin counts back)"""
-    torch = _torch()
     from dff_amd import binding
     off = 3
     npairs = binding.pwd_num_pairs(N, off)
     nbins = (5 + np.arange(npairs) % 17).astype(np.int32)
     hmax = (12.0 + 0.37 * (np.arange(npairs) % 29)).astype(np.float32)
     mb = int(nbins.max())
-    return Spec("dff_pwd_hist", {"x": (dev(_frames(N_FRAMES, N, 32)), float("nan")), "nbins": (dev(nbins), 1), "hmax": (dev(hmax), 1.0)},
+    return Spec("dff_pwd_hist", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 32)), float("nan")), "nbins": (to_dev(nbins), 1), "hmax": (to_dev(hmax), 1.0)},
                 {"hist": ((npairs, mb + 2), torch.int32)},
-                lambda _, b: _raw("dff_pwd_hist", 0, _p(b["x"]), N_FRAMES, N, off, _p(b["nbins"]), _p(b["hmax"]), mb, mb + 2,
-                                  _p(b["hist"]), _st(b["x"])))
+                lambda _, b: raw("dff_pwd_hist", 0, ptr(b["x"]), N_FRAMES, N, off, ptr(b["nbins"]), ptr(b["hmax"]), mb, mb + 2,
+                                 ptr(b["hist"]), stream_of(b["x"])))
 
 
 def struct_rmsd_spec(N):
-    torch = _torch()
     from dff_amd import binding
-    ref = _frames(1, N, 33)[0]
-    return Spec("dff_struct_rmsd", {"x": (dev(_frames(N_FRAMES, N, 34)), float("nan")), "ref": (dev(ref), dev(ref * 0.5 + 1.0))},
+    ref = synth_chain_frames(1, N, 33)[0]
+    return Spec("dff_struct_rmsd", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 34)), float("nan")), "ref": (to_dev(ref), to_dev(ref * 0.5 + 1.0))},
                 {"rmsd": ((N_FRAMES,), torch.float32)},
-                lambda _, b: _raw("dff_struct_rmsd", 0, _p(b["x"]), N_FRAMES, N, _p(b["ref"]), _p(b["rmsd"]), _st(b["x"])),
+                lambda _, b: raw("dff_struct_rmsd", 0, ptr(b["x"]), N_FRAMES, N, ptr(b["ref"]), ptr(b["rmsd"]), stream_of(b["x"])),
                 wrap=lambda _, b: {"rmsd": binding.struct_rmsd(b["x"], b["ref"])})
 
 
 def struct_dihedrals_spec(N):
-    torch = _torch()
     from dff_amd import binding
-    return Spec("dff_struct_dihedrals", {"x": (dev(_frames(N_FRAMES, N, 35)), float("nan"))}, {"dih": ((N_FRAMES, N - 3), torch.float32)},
-                lambda _, b: _raw("dff_struct_dihedrals", 0, _p(b["x"]), N_FRAMES, N, _p(b["dih"]), _st(b["x"])),
+    return Spec("dff_struct_dihedrals", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 35)), float("nan"))}, {"dih": ((N_FRAMES, N - 3), torch.float32)},
+                lambda _, b: raw("dff_struct_dihedrals", 0, ptr(b["x"]), N_FRAMES, N, ptr(b["dih"]), stream_of(b["x"])),
                 wrap=lambda _, b: {"dih": binding.struct_dihedrals(b["x"])})
 
 
@@ -608,94 +383,80 @@ def _tic_model(N, k=2):
     F = binding.struct_tic_num_features(N)
     mean = synth.uniform((F,), 778, 1, 0.0, 10.0)
     coeff = synth.uniform((F, k), 778, 2, -0.1, 0.1)
-    return F, k, dev(mean), dev(coeff)
+    return F, k, to_dev(mean), to_dev(coeff)
 
 
 def struct_tic_spec(N):
-    torch = _torch()
     from dff_amd import binding
     F, k, mean, coeff = _tic_model(N)
-    return Spec("dff_struct_tic", {"x": (dev(_frames(N_FRAMES, N, 36)), float("nan")), "mean": (mean, 1.0), "coeff": (coeff, 0.5)},
+    return Spec("dff_struct_tic", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 36)), float("nan")), "mean": (mean, 1.0), "coeff": (coeff, 0.5)},
                 {"proj": ((N_FRAMES, k), torch.float64)},
-                lambda _, b: _raw("dff_struct_tic", 0, _p(b["x"]), N_FRAMES, N, _p(b["mean"]), _p(b["coeff"]), k, _p(b["proj"]),
-                                  _st(b["x"])),
+                lambda _, b: raw("dff_struct_tic", 0, ptr(b["x"]), N_FRAMES, N, ptr(b["mean"]), ptr(b["coeff"]), k, ptr(b["proj"]),
+                                 stream_of(b["x"])),
                 wrap=lambda _, b: {"proj": binding.struct_tic(b["x"], b["mean"], b["coeff"])})
 
 
 def struct_contacts_spec(N):
-    torch = _torch()
     folded = (synth.uniform((N, N), 779, 1) > 0).astype(np.uint8)
-    return Spec("dff_struct_contacts", {"x": (dev(_frames(N_FRAMES, N, 37)), float("nan")), "folded": (dev(folded), 0)},
+    return Spec("dff_struct_contacts", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 37)), float("nan")), "folded": (to_dev(folded), 0)},
                 {"counts": ((N, N), torch.int32), "mismatch": ((N_FRAMES,), torch.int32)},
-                lambda _, b: _raw("dff_struct_contacts", 0, _p(b["x"]), N_FRAMES, N, 8.0, _p(b["folded"]), 3, _p(b["counts"]),
-                                  _p(b["mismatch"]), _st(b["x"])))
+                lambda _, b: raw("dff_struct_contacts", 0, ptr(b["x"]), N_FRAMES, N, 8.0, ptr(b["folded"]), 3, ptr(b["counts"]),
+                                 ptr(b["mismatch"]), stream_of(b["x"])))
 
 
 def struct_tic_features_spec(N):
-    torch = _torch()
     from dff_amd import binding
     F = binding.struct_tic_num_features(N)
-    return Spec("dff_struct_tic_features", {"x": (dev(_frames(N_FRAMES, N, 38)), float("nan"))}, {"feat": ((N_FRAMES, F), torch.float32)},
-                lambda _, b: _raw("dff_struct_tic_features", 0, _p(b["x"]), N_FRAMES, N, _p(b["feat"]), _st(b["x"])),
+    return Spec("dff_struct_tic_features", {"x": (to_dev(synth_chain_frames(N_FRAMES, N, 38)), float("nan"))}, {"feat": ((N_FRAMES, F), torch.float32)},
+                lambda _, b: raw("dff_struct_tic_features", 0, ptr(b["x"]), N_FRAMES, N, ptr(b["feat"]), stream_of(b["x"])),
                 wrap=lambda _, b: {"feat": binding.struct_tic_features(b["x"])})
 
 
 def struct_tic_assign_spec(N):
-    torch = _torch()
     from dff_amd import binding
     F, k, mean, coeff = _tic_model(N)
     K = 4
-    x = dev(_frames(N_FRAMES, N, 39))
+    x = to_dev(synth_chain_frames(N_FRAMES, N, 39))
     proj = binding.struct_tic(x, mean, coeff)
     torch.cuda.synchronize()
     centers = proj[[3, 250, 600, 901]].clone()                       # four of the projections: every state is populated
     return Spec("dff_struct_tic_assign", {"x": (x, float("nan")), "mean": (mean, 1.0), "coeff": (coeff, 0.5), "centers": (centers, 0.0)},
                 {"labels": ((N_FRAMES,), torch.int32), "proj": ((N_FRAMES, k), torch.float64), "dist2": ((N_FRAMES,), torch.float64)},
-                lambda _, b: _raw("dff_struct_tic_assign", 0, _p(b["x"]), N_FRAMES, N, _p(b["mean"]), _p(b["coeff"]), k,
-                                  _p(b["centers"]), K, _p(b["labels"]), _p(b["proj"]), _p(b["dist2"]), _st(b["x"])),
+                lambda _, b: raw("dff_struct_tic_assign", 0, ptr(b["x"]), N_FRAMES, N, ptr(b["mean"]), ptr(b["coeff"]), k,
+                                 ptr(b["centers"]), K, ptr(b["labels"]), ptr(b["proj"]), ptr(b["dist2"]), stream_of(b["x"])),
                 wrap=lambda _, b: dict(zip(("labels", "proj", "dist2"),
                                            binding.struct_tic_assign(b["x"], b["mean"], b["coeff"], b["centers"], True, True))))
 
 
 def kmeans_step_spec():
-    torch = _torch()
     from dff_amd import binding
     n, d, K = N_FRAMES, 2, 4
     pts = synth.normal((n, d), 780, 1) + np.array([[2.0, -1.0]]) * (np.arange(n) % 4)[:, None]
     centers = pts[[1, 2, 3, 4]].copy()
     ws = torch.empty(max(binding.kmeans_workspace_bytes(n, d, K), 1), dtype=torch.uint8, device="cuda")
-    return Spec("dff_kmeans_step", {"pts": (dev(pts), float("nan")), "centers": (dev(centers), 0.5)},
+    return Spec("dff_kmeans_step", {"pts": (to_dev(pts), float("nan")), "centers": (to_dev(centers), 0.5)},
                 {"labels": ((n,), torch.int32), "dist2": ((n,), torch.float64), "sums": ((K, d), torch.float64),
                  "counts": ((K,), torch.int64), "inertia": ((1,), torch.float64)},
-                lambda _, b: _raw("dff_kmeans_step", 0, _p(b["pts"]), n, d, _p(b["centers"]), K, _p(b["labels"]), _p(b["dist2"]),
-                                  _p(b["sums"]), _p(b["counts"]), _p(b["inertia"]), _p(b["ws"]), b["ws"].numel(), _st(b["pts"])),
+                lambda _, b: raw("dff_kmeans_step", 0, ptr(b["pts"]), n, d, ptr(b["centers"]), K, ptr(b["labels"]), ptr(b["dist2"]),
+                                 ptr(b["sums"]), ptr(b["counts"]), ptr(b["inertia"]), ptr(b["ws"]), b["ws"].numel(), stream_of(b["pts"])),
                 work={"ws": ws})
 
 
 def transition_counts_spec():
-    torch = _torch()
     K, lags, lengths = 4, np.array([1, 7], np.int32), np.array([400, 250, 350], np.int64)
     labels = (splitmix_labels(N_FRAMES, K))
-    return Spec("dff_transition_counts", {"labels": (dev(labels), 0)}, {"counts": ((2, K, K), torch.int64)},
-                lambda _, b: _raw("dff_transition_counts", 0, _p(b["labels"]), N_FRAMES, lengths.ctypes.data_as(C.c_void_p), 3,
-                                  lags.ctypes.data_as(C.c_void_p), 2, K, _p(b["counts"]), _st(b["labels"])))
-
-
-def splitmix_labels(n, K):
-    """Labels 0 .. K - 1 with a few -1 (the label of a non-finite frame)."""
-    lab = np.floor(synth.uniform((n,), 781, 1, 0.0, float(K))).astype(np.int32)
-    lab[::97] = -1
-    return lab
+    return Spec("dff_transition_counts", {"labels": (to_dev(labels), 0)}, {"counts": ((2, K, K), torch.int64)},
+                lambda _, b: raw("dff_transition_counts", 0, ptr(b["labels"]), N_FRAMES, lengths.ctypes.data_as(C.c_void_p), 3,
+                                 lags.ctypes.data_as(C.c_void_p), 2, K, ptr(b["counts"]), stream_of(b["labels"])))
 
 
 def tica_moments_spec(N, lengths, lag):
     """The accumulators are ADDED to: inputs as well as outputs (real: small non-zero values; poison NaN)."""
-    torch = _torch()
     from dff_amd import binding
     n = int(sum(lengths))
     F = binding.struct_tic_num_features(N)
     ln = np.ascontiguousarray(lengths, dtype=np.int64)
-    x = dev(_frames(n, N, 40))
+    x = to_dev(synth_chain_frames(n, N, 40))
     feat0 = binding.struct_tic_features(x[:1]).double().reshape(F).clone()
     torch.cuda.synchronize()
     ws = torch.empty(binding.tica_workspace_bytes(N, n, lag), dtype=torch.uint8, device="cuda")
@@ -704,9 +465,9 @@ def tica_moments_spec(N, lengths, lag):
     ins = {"x": (x, float("nan")), "shift": (feat0, 0.0)}
     ins.update({k: (v, float("nan")) for k, v in acc.items()})
     return Spec("dff_tica_moments", ins, {},
-                lambda _, b: _raw("dff_tica_moments", 0, _p(b["x"]), n, N, ln.ctypes.data_as(C.c_void_p), int(ln.size), lag,
-                                  _p(b["shift"]), _p(b["ws"]), b["ws"].numel(), _p(b["sx"]), _p(b["sy"]), _p(b["m0"]), _p(b["mt"]),
-                                  _st(b["x"])),
+                lambda _, b: raw("dff_tica_moments", 0, ptr(b["x"]), n, N, ln.ctypes.data_as(C.c_void_p), int(ln.size), lag,
+                                 ptr(b["shift"]), ptr(b["ws"]), b["ws"].numel(), ptr(b["sx"]), ptr(b["sy"]), ptr(b["m0"]), ptr(b["mt"]),
+                                 stream_of(b["x"])),
                 inout=("sx", "sy", "m0", "mt"), work={"ws": ws})
 
 
@@ -714,37 +475,29 @@ N_ENS = 257
 
 
 def rmsd_matrix_spec(N):
-    torch = _torch()
     from dff_amd import binding
-    return Spec("dff_rmsd_matrix", {"x": (dev(_frames(N_ENS, N, 41)), float("nan")), "y": (dev(_frames(N_ENS, N, 42)), float("nan"))},
+    return Spec("dff_rmsd_matrix", {"x": (to_dev(synth_chain_frames(N_ENS, N, 41)), float("nan")), "y": (to_dev(synth_chain_frames(N_ENS, N, 42)), float("nan"))},
                 {"out": ((N_ENS, N_ENS), torch.float32)},
-                lambda _, b: _raw("dff_rmsd_matrix", 0, _p(b["x"]), N_ENS, _p(b["y"]), N_ENS, N, _p(b["out"]), _st(b["x"])),
+                lambda _, b: raw("dff_rmsd_matrix", 0, ptr(b["x"]), N_ENS, ptr(b["y"]), N_ENS, N, ptr(b["out"]), stream_of(b["x"])),
                 wrap=lambda _, b: {"out": binding.rmsd_matrix(b["x"], b["y"])})
 
 
 def rmsd_nearest_spec(N, exclude_self):
     """exclude_self: the candidates ARE the queries (self_first = 0) -- without the exclusion every query would find itself."""
-    torch = _torch()
     from dff_amd import binding
-    x = _frames(N_ENS, N, 41)
-    y = x if exclude_self else _frames(N_ENS, N, 42)
+    x = synth_chain_frames(N_ENS, N, 41)
+    y = x if exclude_self else synth_chain_frames(N_ENS, N, 42)
     sf = 0 if exclude_self else -1
     ws = torch.empty(max(binding.rmsd_nearest_workspace_bytes(N_ENS, N_ENS, N), 1), dtype=torch.uint8, device="cuda")
 
     def wrap(_, b):
         r, i = binding.rmsd_nearest(b["x"], b["y"], self_first=sf)
         return {"rmsd": r, "index": i}
-    return Spec("dff_rmsd_nearest", {"x": (dev(x), float("nan")), "y": (dev(y), float("nan"))},
+    return Spec("dff_rmsd_nearest", {"x": (to_dev(x), float("nan")), "y": (to_dev(y), float("nan"))},
                 {"rmsd": ((N_ENS,), torch.float32), "index": ((N_ENS,), torch.int64)},
-                lambda _, b: _raw("dff_rmsd_nearest", 0, _p(b["x"]), N_ENS, _p(b["y"]), N_ENS, N, sf, _p(b["rmsd"]), _p(b["index"]),
-                                  _p(b["ws"]), b["ws"].numel(), _st(b["x"])),
+                lambda _, b: raw("dff_rmsd_nearest", 0, ptr(b["x"]), N_ENS, ptr(b["y"]), N_ENS, N, sf, ptr(b["rmsd"]), ptr(b["index"]),
+                                 ptr(b["ws"]), b["ws"].numel(), stream_of(b["x"])),
                 work={"ws": ws}, wrap=wrap)
-
-
-def _analysis_call(spec, gate, side):
-    ref = reference(spec)
-    gated(spec, side, gate, ref, nonblocking=(spec.name, "warm") not in BLOCKING)
-    return ref
 
 
 @beads_param
@@ -752,7 +505,7 @@ def _analysis_call(spec, gate, side):
                                   struct_contacts_spec, struct_tic_features_spec, struct_tic_assign_spec, rmsd_matrix_spec],
                          ids=lambda f: f.__name__[:-5])
 def test_analysis_call(make, N, gate, side):
-    ref = _analysis_call(make(N), gate, side)
+    ref = analysis_call(make(N), gate, side)
     if make is pwd_hist_spec:          # every structure lands in a bin of every pair (or beyond hmax): the real input was read
         assert 0 < int(ref["hist"].sum()) <= N_FRAMES * ref["hist"].shape[0]
         assert int(ref["hist"][:, -2:].abs().sum()) == 0            # the columns between max_bins and ld are zeroed too
@@ -763,7 +516,7 @@ def test_analysis_call(make, N, gate, side):
 @beads_param
 @pytest.mark.parametrize("exclude_self", [False, True], ids=["all-candidates", "exclude-self"])
 def test_rmsd_nearest(N, exclude_self, gate, side):
-    ref = _analysis_call(rmsd_nearest_spec(N, exclude_self), gate, side)
+    ref = analysis_call(rmsd_nearest_spec(N, exclude_self), gate, side)
     idx = ref["index"].cpu().numpy()
     assert (idx >= 0).all() and (idx < N_ENS).all()
     if exclude_self:
@@ -771,12 +524,12 @@ def test_rmsd_nearest(N, exclude_self, gate, side):
 
 
 def test_kmeans_step(gate, side):
-    ref = _analysis_call(kmeans_step_spec(), gate, side)
+    ref = analysis_call(kmeans_step_spec(), gate, side)
     assert int(ref["counts"].sum()) == N_FRAMES
 
 
 def test_transition_counts(gate, side):
-    ref = _analysis_call(transition_counts_spec(), gate, side)
+    ref = analysis_call(transition_counts_spec(), gate, side)
     assert 0 < int(ref["counts"][0].sum()) < N_FRAMES - 3
 
 
@@ -788,14 +541,13 @@ def test_tica_moments(N, lengths, lag, chunks, gate, side):
     from dff_amd import binding
     k = len(np.unique(binding.tica_debug_plan(N, lengths, lag)[:, 0]))
     assert k >= 2 if chunks == 2 else k == 1
-    _analysis_call(tica_moments_spec(N, lengths, lag), gate, side)
+    analysis_call(tica_moments_spec(N, lengths, lag), gate, side)
 
 
 # ------------------------------------------------------------------------------------------------ two streams at once
 def _two_at_once(specs, nats, gate, tag):
     """Two calls issued back to back on two side streams, each behind its own gate, nothing synchronised in between: each equals
     its serial result (no hidden process-wide device state)."""
-    torch = _torch()
     refs = [reference(sp, nat) for sp, nat in zip(specs, nats)]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     runs = [Run(sp, nat) for sp, nat in zip(specs, nats)]

@@ -1,6 +1,7 @@
 """Edges of the structure-metric kernels (dff_struct_*) that the golden frames never reach.
 
-- the grid-stride loop (more tiles than workgroups) and ragged tails, with float64 oracles vectorised over frames;
+- the grid-stride loop (more tiles than workgroups) and ragged tails, with the float64 oracles of oracle/struct_metric.py
+  vectorised over frames (held to the per-frame ones here);
 - unaligned contiguous views (the scalar tile-load path), bit-equal to an aligned copy;
 - the bead-count limits N = 4 and 64, and the rejection of N = 3 and 65;
 - RMSD on elongated, planar, degenerate and far-off frames, where the two largest eigenvalues of Horn's key matrix
@@ -11,86 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_struct_metrics import (MOLS, consecutive, dihedrals64, kabsch64, tic_features64, torch_contacts,
-                                 triu_mismatch, x_rmsd)
-
-RMSD_ATOL, RMSD_RTOL = 1e-5, 1e-6          # the bar of test_struct_metrics.py::test_rmsd_vs_kabsch
-
-
-# ---------------------------------------------------------------- float64 oracles, vectorised over frames
-def kabsch64_batch(x, ref, chunk=1 << 17):
-    """kabsch64 for many frames at once: batched SVD of the (n, 3, 3) correlation matrices with the reflection fix"""
-    x = np.asarray(x)
-    r = np.asarray(ref, np.float64)
-    r = r - r.mean(0)
-    Gb = (r * r).sum()
-    N = x.shape[1]
-    out = np.empty(len(x))
-    for i in range(0, len(x), chunk):
-        a = np.asarray(x[i:i + chunk], np.float64)
-        fin = np.isfinite(a).all((1, 2))
-        a = np.where(fin[:, None, None], a, 0.0)
-        a = a - a.mean(1, keepdims=True)
-        U, S, Vt = np.linalg.svd(np.einsum("nbi,bj->nij", a, r))
-        S[:, -1] *= np.sign(np.linalg.det(U @ Vt))
-        msd = ((a * a).sum((1, 2)) + Gb - 2 * S.sum(1)) / N
-        out[i:i + chunk] = np.where(fin, np.sqrt(np.maximum(msd, 0.0)), np.nan)
-    return out
-
-
-def tic64_batch(x, mean, A, chunk=1 << 15):
-    """(tic_features64(x) - mean) @ A, a chunk of frames at a time"""
-    return np.concatenate([(tic_features64(x[i:i + chunk]) - mean) @ A for i in range(0, len(x), chunk)])
-
-
-def contacts_batch(x, cutoff, folded=None, offset=3, chunk=1 << 13):
-    """torch's float32 contact formula, a chunk of frames at a time -> (counts (N, N), mismatches (n,) or None)"""
-    N = x.shape[1]
-    counts = np.zeros((N, N), np.int64)
-    mism = []
-    for i in range(0, len(x), chunk):
-        c = torch_contacts(x[i:i + chunk], cutoff)
-        counts += c.sum(0).numpy()
-        if folded is not None:
-            mism.append(triu_mismatch(c, folded, offset))
-    return counts, (np.concatenate(mism) if folded is not None else None)
-
-
-def dihedral_ok(x, min_sin=0.1):
-    """(n, N - 3) mask of well-conditioned dihedrals: the sines of both bond angles above min_sin (0.1, ~6 degrees from
-    0 and 180, as in test_struct_metrics.py::test_dihedrals_vs_float64), and the float64 value at least 1e-3 from the
-    +-pi branch cut"""
-    b = np.diff(np.asarray(x, np.float64), axis=1)
-    with np.errstate(invalid="ignore", divide="ignore"):       # coincident beads: NaN, masked out
-        sin = np.linalg.norm(np.cross(b[:, :-1], b[:, 1:]), axis=-1) / (
-            np.linalg.norm(b[:, :-1], axis=-1) * np.linalg.norm(b[:, 1:], axis=-1))
-        ref = dihedrals64(x, consecutive(x.shape[1]))
-    return (sin[:, :-1] > min_sin) & (sin[:, 1:] > min_sin) & (np.abs(ref) < np.pi - 1e-3)
-
-
-def tic_rows(x):
-    """frames whose dihedral features are all well enough conditioned for the TIC bar (an fp32 dihedral that lands on
-    the other side of the branch cut, or at a near-straight bond angle, is off by up to 2 pi)"""
-    return dihedral_ok(x, 0.01).all(1)
-
-
-def wrap_err(a, b):
-    return np.abs(np.angle(np.exp(1j * (np.asarray(a, np.float64) - b))))
-
-
-def assert_rmsd(got, ref, what=""):
-    got = np.asarray(got, np.float64)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), what
-    ok = ~np.isnan(ref)
-    err = np.abs(got[ok] - ref[ok])
-    bad = err > RMSD_ATOL + RMSD_RTOL * ref[ok]
-    assert not bad.any(), (f"{what}: {bad.sum()} of {ok.sum()} frames off, worst |err| {err.max():.3e} A "
-                           f"at rmsd {ref[ok][np.argmax(err)]:.3e}")
-
-
-def rand_rot(rng):
-    q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
-    return q * np.sign(np.linalg.det(q))
+from oracle.frames import axis_rot, integer_walks, needle, planar_walks, rand_rot
+from oracle.struct_metric import (consecutive, contacts_batch, dihedral_ok, dihedrals64, kabsch64, kabsch64_batch, tic64_batch,
+                                  tic_features64, tic_rows, torch_contacts, wrap_err)
+from support import MIRROR, MOLS, RMSD_ATOL, B, assert_rmsd, dev, x_rmsd  # noqa: F401  (dev: fixture)
 
 
 # ================================================================ CPU
@@ -114,19 +39,6 @@ def test_tic64_batch_equals_unchunked():
 
 
 # ================================================================ GPU
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
-def B():
-    from dff_amd import binding
-    return binding
-
-
 def all_metrics(xd, ref, mean, A, folded):
     """the four metrics of the frames xd (device) -> dict of host arrays"""
     b = B()
@@ -254,15 +166,6 @@ def test_bead_count_out_of_range_rejected(dev, N):
 
 
 # ---------------------------------------------------------------- RMSD geometry family
-def needle(rng, N, width):
-    """a straight 3.8 A-spaced chain along x with Gaussian lateral scatter of the given width"""
-    t = (np.arange(N) - (N - 1) / 2) * 3.8
-    return np.stack([t, width * rng.standard_normal(N), width * rng.standard_normal(N)], 1)
-
-
-MIRROR = np.array([-1.0, 1.0, 1.0])
-
-
 def rmsd_family_check(ref, frames, what):
     ref = np.asarray(ref, np.float32)
     x = np.asarray(frames, np.float32)
@@ -318,14 +221,6 @@ def test_rmsd_planar_and_symmetric_tops(dev, N):
                   (top + 0.05 * rng.standard_normal((N, 3))) * MIRROR]
         rmsd_family_check(top, frames, f"N={N} symmetric top {c}")
         rmsd_family_check(top * MIRROR, frames, f"N={N} mirrored symmetric top {c}")
-
-
-def axis_rot(axis, ang):
-    c, s = np.cos(ang), np.sin(ang)
-    i, j = [k for k in range(3) if k != axis]
-    R = np.eye(3)
-    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
-    return R
 
 
 @pytest.mark.gpu
@@ -428,17 +323,6 @@ def test_nonfinite_dihedrals_tic_contacts(dev, N):
 
 
 # ---------------------------------------------------------------- contacts at the cutoff
-def integer_walks(rng, n, N):
-    """integer chains whose consecutive beads are 5, 7 or 9 apart exactly: signed permutations of (3, 4, 0),
-    (2, 3, 6) and (1, 4, 8)"""
-    steps = np.array([[3, 4, 0], [2, 3, 6], [1, 4, 8]], np.float64)
-    perms = np.array([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]])
-    k = rng.integers(3, size=(n, N - 1))
-    v = steps[k[..., None], perms[rng.integers(6, size=(n, N - 1))]] * rng.choice([-1.0, 1.0], size=(n, N - 1, 3))
-    x = np.concatenate([np.zeros((n, 1, 3)), np.cumsum(v, 1)], 1) + rng.integers(-20, 20, size=(n, 1, 3))
-    return x.astype(np.float32)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [4, 16, 64])
 def test_contacts_exactly_at_cutoff(dev, N):
@@ -482,20 +366,6 @@ def test_contacts_cutoff_and_offset_edges(dev, N):
 
 
 # ---------------------------------------------------------------- dihedral special values
-def planar_walks(rng, n, N):
-    """integer chains in the z = 0 plane, no two consecutive bonds parallel, mapped by 3 x an exact rotation
-    [[1, 2, 2], [2, 1, -2], [2, -2, 1]] / 3 into an oblique plane: every dihedral is exactly 0 (cis) or pi (trans)"""
-    dirs = np.array([[1, 0], [1, 1], [0, 1], [-1, 1], [-1, 0], [-1, -1], [0, -1], [1, -1]], np.float64)   # k + 4: opposite
-    x = np.zeros((n, N, 3))
-    for s in range(n):
-        k = rng.integers(8)
-        for i in range(1, N):
-            k = (k + rng.choice([1, 2, 3, 5, 6, 7])) % 8 if i > 1 else k
-            x[s, i, :2] = x[s, i - 1, :2] + dirs[k] * rng.integers(1, 4)
-    M = np.array([[1, 2, 2], [2, 1, -2], [2, -2, 1]], np.float64)
-    return (x @ M.T + rng.integers(-10, 10, size=(n, 1, 3))).astype(np.float32)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [4, 10, 64])
 def test_dihedral_special_values(dev, N):

@@ -2,8 +2,8 @@
 
 CPU part: the restricted unpickler on the reference's own chignolin TICA pickle, and the host reductions of
 evaluate.py fed the per-frame values of the reference-executed vectors (tests/golden/make_golden_struct.py).
-GPU part (-m gpu): the HIP kernels dff_struct_* through the C ABI against float64 oracles written here, exact
-contact counts against torch's float32 formula, and the evaluators end to end against the reference's numbers.
+GPU part (-m gpu): the HIP kernels dff_struct_* through the C ABI against the float64 oracles of oracle/struct_metric.py,
+exact contact counts against torch's float32 formula, and the evaluators end to end against the reference's numbers.
 """
 import io
 import os
@@ -14,75 +14,12 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-
-MOLS = ["chignolin", "trp_cage", "bba", "villin", "protein_g"]
-N_BEADS = {"chignolin": 10, "trp_cage": 20, "bba": 28, "villin": 35, "protein_g": 56}
-
-
-def ev():
-    from dff_amd import evaluate
-    return evaluate
+from oracle.struct_metric import consecutive, dihedrals64, kabsch64, tic_features64, torch_contacts, triu_mismatch
+from support import MOLS, N_BEADS, dev, ev, x_rmsd  # noqa: F401  (dev: fixture)
 
 
 def saved_refs(golden):
     return golden("struct_saved_refs.npz")
-
-
-# ---------------------------------------------------------------- float64 oracles
-def dihedrals64(x, ind):
-    x = np.asarray(x, np.float64)
-    ind = np.asarray(ind)
-    b1 = x[:, ind[:, 1]] - x[:, ind[:, 0]]
-    b2 = x[:, ind[:, 2]] - x[:, ind[:, 1]]
-    b3 = x[:, ind[:, 3]] - x[:, ind[:, 2]]
-    c1, c2 = np.cross(b2, b3), np.cross(b1, b2)
-    return np.arctan2((b1 * c1).sum(-1) * np.sqrt((b2 * b2).sum(-1)), (c1 * c2).sum(-1))
-
-
-def consecutive(N):
-    i = np.arange(N - 3)
-    return np.stack([i, i + 1, i + 2, i + 3], 1)
-
-
-def kabsch64(x, ref):
-    """optimal proper-rotation RMSD, float64 SVD with the reflection correction; NaN for non-finite frames"""
-    x = np.asarray(x, np.float64)
-    r = np.asarray(ref, np.float64)
-    r = r - r.mean(0)
-    out = np.full(len(x), np.nan)
-    for s, a in enumerate(x):
-        if not np.isfinite(a).all():
-            continue
-        a = a - a.mean(0)
-        U, S, Vt = np.linalg.svd(a.T @ r)
-        S[-1] *= np.sign(np.linalg.det(U @ Vt))
-        out[s] = np.sqrt(max(((a * a).sum() + (r * r).sum() - 2 * S.sum()) / len(a), 0.0))
-    return out
-
-
-def tic_features64(x):
-    x = np.asarray(x, np.float64)
-    N = x.shape[1]
-    iu = np.triu_indices(N, 1)
-    d = np.linalg.norm(x[:, iu[0]] - x[:, iu[1]], axis=-1)
-    return np.hstack([dihedrals64(x, consecutive(N)), d])
-
-
-def torch_contacts(x, cutoff):
-    x = torch.from_numpy(np.asarray(x, np.float32))
-    return torch.norm(x[:, :, None, :] - x[:, None, :, :], dim=-1) < cutoff
-
-
-def triu_mismatch(c, folded, offset):
-    N = c.shape[-1]
-    iu = torch.triu_indices(N, N, offset=offset)
-    return (c[:, iu[0], iu[1]] != torch.as_tensor(folded)[iu[0], iu[1]]).sum(-1).numpy()
-
-
-def x_rmsd(g):
-    x = g["x"].copy()
-    x[tuple(g["nonfinite_at"].T)] = g["nonfinite_val"]
-    return x
 
 
 # ================================================================ CPU
@@ -197,14 +134,6 @@ def test_saved_rmsd_reference_loads(golden, tmp_path):
 
 
 # ================================================================ GPU
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
 def cases(golden):
     out = {m: golden(f"struct_ref_{m}.npz") for m in MOLS}
     return out

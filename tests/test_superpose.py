@@ -1,5 +1,5 @@
-"""dff_superpose on the GPU against the float64 oracle of test_superpose_host.py (batched Kabsch by SVD with the reflection
-fix; the eigenvalues of Horn's key matrix by numpy.linalg.eigvalsh).
+"""dff_superpose on the GPU against the float64 oracle superpose64 of oracle/struct_metric.py (batched Kabsch by SVD with the
+reflection fix; the eigenvalues of Horn's key matrix by numpy.linalg.eigvalsh).
 
 What is compared how:
 - STRICT, on frames whose relative eigenvalue gap (l1 - l2) / (l1 - l4) is >= 1e-2 (below it the rotation itself is
@@ -9,7 +9,7 @@ What is compared how:
     rot      <= 1e-9 per entry, four orders above that estimate
 - on EVERY finite frame, degenerate ones included:
     rot      |R^T R - I| <= 1e-12 and |det R - 1| <= 1e-12
-    rmsd     RMSD_ATOL, RMSD_RTOL of tests/test_struct_edges.py against the oracle
+    rmsd     RMSD_ATOL, RMSD_RTOL of tests/support.py against the oracle
     the plain, unrotated fp64 RMSD of the returned aligned frame to the reference is the oracle's minimal RMSD within that
     same bar plus 2^-23 max |coordinate| (the fp32 rounding of the frame)
 - dsum, dsq <= 1e-10 sum_frames |term| on data sets without an excluded frame (fp64 summation, n 2^-53 at n <= 2^19, and the
@@ -19,29 +19,14 @@ import numpy as np
 import pytest
 import torch
 
-from test_struct_edges import RMSD_ATOL, RMSD_RTOL, rand_rot
-from test_stream_order import N_FRAMES, Spec, _analysis_call, _p, _raw, _st, gate, side  # noqa: F401  (gate, side: fixtures)
-from test_stream_order import _frames as chain_frames
-from test_stream_order import dev as to_dev
-from test_superpose_host import GAP_MIN, MAX_EXCLUDED, golden_frames, noisy_ensemble, stats64, superpose64
+from oracle.frames import gaussian, half_turn, noisy_ensemble, rand_rot, synth_chain_frames
+from oracle.struct_metric import stats64, superpose64
+from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from support import GAP_MIN, MAX_EXCLUDED, MIRROR, RMSD_ATOL, RMSD_RTOL, B, dev, golden_frames, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
 EPS32 = 2.0 ** -23
-MIRROR = np.array([-1.0, 1.0, 1.0])
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
-def B():
-    from dff_amd import binding
-    return binding
 
 
 def run(x, ref, **kw):
@@ -99,10 +84,6 @@ def check(got, x, ref, what, strict_all=False, stats=False):
         print(f"[superpose] {what}: dsum err / sum |d| {e1.max():.2e}, dsq err / dsq {e2.max():.2e}")
         assert e1.max() <= 1e-10 and e2.max() <= 1e-10, what
     return o
-
-
-def gaussian(rng, n, N):
-    return (rng.standard_normal((n, N, 3)) * 5).astype(np.float32), (rng.standard_normal((N, 3)) * 5).astype(np.float32)
 
 
 # ---------------------------------------------------------------- 1. goldens
@@ -165,11 +146,6 @@ def test_bead_count_out_of_range_refused(dev, N):
 
 
 # ---------------------------------------------------------------- 3. exact rotations
-def half_turn(axis):
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    return 2.0 * np.outer(a, a) - np.eye(3)
-
-
 @pytest.mark.parametrize("mol", ["chignolin", "protein_g"])
 def test_exact_rotations(dev, golden, mol):
     f = golden("struct_folded.npz")[mol].astype(np.float32)
@@ -248,9 +224,9 @@ def test_in_place_and_unaligned_views_bit_equal(dev, N):
 
 
 # ---------------------------------------------------------------- 6. optional outputs
-def raw(x, n, N, ref, aligned=None, rot=None, rmsd=None, dsum=None, dsq=None, count=None, ws=None, ws_bytes=None):
-    _raw("dff_superpose", 0, _p(x), n, N, _p(ref), _p(aligned), _p(rot), _p(rmsd), _p(dsum), _p(dsq), _p(count), _p(ws),
-         (ws.numel() if ws is not None else 0) if ws_bytes is None else ws_bytes, _st(ref))
+def superpose_raw(x, n, N, ref, aligned=None, rot=None, rmsd=None, dsum=None, dsq=None, count=None, ws=None, ws_bytes=None):
+    raw("dff_superpose", 0, ptr(x), n, N, ptr(ref), ptr(aligned), ptr(rot), ptr(rmsd), ptr(dsum), ptr(dsq), ptr(count), ptr(ws),
+        (ws.numel() if ws is not None else 0) if ws_bytes is None else ws_bytes, stream_of(ref))
 
 
 def test_optional_outputs(dev):
@@ -273,7 +249,7 @@ def test_optional_outputs(dev):
     for keys in (["aligned"], ["rot"], ["rmsd"], ["dsum"], ["dsq"], ["count"], ["dsum", "dsq", "count"], list(want)):
         bufs = fresh()
         st = any(k in keys for k in ("dsum", "dsq", "count"))
-        raw(xd, n, N, rd, ws=ws if st else None, **{k: bufs[k] for k in keys})
+        superpose_raw(xd, n, N, rd, ws=ws if st else None, **{k: bufs[k] for k in keys})
         for k, v in bufs.items():
             if k in keys:
                 assert torch.equal(v, want[k]) or (torch.equal(torch.isnan(v), torch.isnan(want[k])) and
@@ -282,16 +258,16 @@ def test_optional_outputs(dev):
                 assert bool((v == 123).all()), (keys, k)
     assert int(want["count"]) == n - 1 and torch.isnan(want["aligned"][17]).all() and torch.isnan(want["rmsd"][17])
     # no output at all: a no-op
-    raw(xd, n, N, rd)
+    superpose_raw(xd, n, N, rd)
     # n == 0 zeroes the statistics (and needs no workspace)
     bufs = fresh()
-    raw(xd, 0, N, rd, dsum=bufs["dsum"], dsq=bufs["dsq"], count=bufs["count"])
+    superpose_raw(xd, 0, N, rd, dsum=bufs["dsum"], dsq=bufs["dsq"], count=bufs["count"])
     assert not bufs["dsum"].any() and not bufs["dsq"].any() and int(bufs["count"]) == 0
     # a workspace one byte too small, or none, is refused; the outputs stay untouched
     bufs = fresh()
     for kw in (dict(ws=ws, ws_bytes=need - 1), dict(ws=None)):
         with pytest.raises(ValueError, match="workspace"):
-            raw(xd, n, N, rd, dsum=bufs["dsum"], **kw)
+            superpose_raw(xd, n, N, rd, dsum=bufs["dsum"], **kw)
     torch.cuda.synchronize()
     assert bool((bufs["dsum"] == 123).all())
     # two identical calls, the workspace dirty from other work in between: bit-identical statistics
@@ -382,21 +358,21 @@ def test_mean_structure_on_a_synthetic_ensemble(dev):
 def superpose_spec(N):
     b = B()
     n = N_FRAMES
-    ref = chain_frames(1, N, 51)[0]
+    ref = synth_chain_frames(1, N, 51)[0]
     ws = torch.empty(b.superpose_workspace_bytes(n, N), dtype=torch.uint8, device="cuda")
 
     def wrap(_, bufs):
         return b.superpose(bufs["x"], bufs["ref"], rot=True, rmsd=True, stats=True)
-    return Spec("dff_superpose", {"x": (to_dev(chain_frames(n, N, 52)), float("nan")), "ref": (to_dev(ref), to_dev(ref * 0.5 + 1.0))},
+    return Spec("dff_superpose", {"x": (to_dev(synth_chain_frames(n, N, 52)), float("nan")), "ref": (to_dev(ref), to_dev(ref * 0.5 + 1.0))},
                 {"aligned": ((n, N, 3), torch.float32), "rot": ((n, 3, 3), torch.float64), "rmsd": ((n,), torch.float32),
                  "dsum": ((N, 3), torch.float64), "dsq": ((N,), torch.float64), "count": ((1,), torch.int64)},
-                lambda _, bufs: _raw("dff_superpose", 0, _p(bufs["x"]), n, N, _p(bufs["ref"]), _p(bufs["aligned"]), _p(bufs["rot"]),
-                                     _p(bufs["rmsd"]), _p(bufs["dsum"]), _p(bufs["dsq"]), _p(bufs["count"]), _p(bufs["ws"]),
-                                     bufs["ws"].numel(), _st(bufs["x"])),
+                lambda _, bufs: raw("dff_superpose", 0, ptr(bufs["x"]), n, N, ptr(bufs["ref"]), ptr(bufs["aligned"]), ptr(bufs["rot"]),
+                                    ptr(bufs["rmsd"]), ptr(bufs["dsum"]), ptr(bufs["dsq"]), ptr(bufs["count"]), ptr(bufs["ws"]),
+                                    bufs["ws"].numel(), stream_of(bufs["x"])),
                 work={"ws": ws}, wrap=wrap)
 
 
 @pytest.mark.parametrize("N", [10, 35])
 def test_stream_order(N, gate, side):  # noqa: F811
-    ref = _analysis_call(superpose_spec(N), gate, side)
+    ref = analysis_call(superpose_spec(N), gate, side)
     assert int(ref["count"]) == N_FRAMES and bool(torch.isfinite(ref["aligned"]).all())

@@ -1,6 +1,6 @@
 """Host side of the superposition on a reference (dff_superpose): the float64 oracle the GPU tests of test_superpose.py
-compare against (batched Kabsch by SVD with the reflection fix, extended to the rotation and the aligned frames, and the
-eigenvalue gap of Horn's key matrix), the share of frames the gap filter excludes on the golden data, the symbol table,
+compare against (oracle/struct_metric.py: superpose64, horn_gap) held to kabsch64_batch and to its own invariants, the share
+of frames the gap filter (GAP_MIN, MAX_EXCLUDED of tests/support.py) excludes on the golden data, the symbol table,
 the argument refusals (all on the host, before any device call), the generalised-Procrustes loop of mean_structure on a
 numpy stand-in for the kernel, the reductions of FlexibilityEvaluator and the package re-exports.  No GPU."""
 import ctypes as C
@@ -15,65 +15,14 @@ import torch
 import dff_amd  # noqa: F401
 from dff_amd import binding, evaluate
 
-from test_struct_edges import kabsch64_batch, rand_rot
-from test_struct_metrics import MOLS, x_rmsd
+from oracle.frames import noisy_ensemble, rand_rot
+from oracle.struct_metric import kabsch64_batch, stats64, superpose64
+from support import GAP_MIN, MAX_EXCLUDED, MOLS, golden_frames
 
-GAP_MIN = 1e-2            # strict comparisons run on frames with (l1 - l2) / (l1 - l4) >= GAP_MIN
-MAX_EXCLUDED = 0.02       # at most this share of a data set may fall below it
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-# ---------------------------------------------------------------- the oracle
-def horn_gap(S):
-    """relative gap (l1 - l2) / (l1 - l4) of the eigenvalues l1 >= ... >= l4 of Horn's key matrix of the (n, 3, 3)
-    correlations S[s, i, j] = sum_b a_bi r_bj; 0 where l1 == l4 (K = 0)"""
-    K = np.zeros((len(S), 4, 4))
-    K[:, 0, 0] = S[:, 0, 0] + S[:, 1, 1] + S[:, 2, 2]
-    K[:, 0, 1] = S[:, 1, 2] - S[:, 2, 1]
-    K[:, 0, 2] = S[:, 2, 0] - S[:, 0, 2]
-    K[:, 0, 3] = S[:, 0, 1] - S[:, 1, 0]
-    K[:, 1, 1] = S[:, 0, 0] - S[:, 1, 1] - S[:, 2, 2]
-    K[:, 1, 2] = S[:, 0, 1] + S[:, 1, 0]
-    K[:, 1, 3] = S[:, 2, 0] + S[:, 0, 2]
-    K[:, 2, 2] = -S[:, 0, 0] + S[:, 1, 1] - S[:, 2, 2]
-    K[:, 2, 3] = S[:, 1, 2] + S[:, 2, 1]
-    K[:, 3, 3] = -S[:, 0, 0] - S[:, 1, 1] + S[:, 2, 2]
-    w = np.linalg.eigvalsh(K, UPLO="U")
-    span = w[:, 3] - w[:, 0]
-    return np.where(span > 0, (w[:, 3] - w[:, 2]) / np.where(span > 0, span, 1.0), 0.0)
-
-
-def superpose64(x, ref):
-    """kabsch64_batch (tests/test_struct_edges.py) extended to the rotation: for the float32 frames x (n, N, 3) and the
-    float32 reference (N, 3), in float64: {"finite" (n,), "R" (n, 3, 3) the proper rotation minimising
-    sum_b |R a_b - r_b|^2, "aligned" (n, N, 3) = R a + c_ref, "rmsd" (n,), "gap" (n,)}; NaN rows for non-finite frames."""
-    x = np.asarray(x, np.float32).astype(np.float64)
-    r = np.asarray(ref, np.float32).astype(np.float64)
-    cr = r.mean(0)
-    r0 = r - cr
-    fin = np.isfinite(x).all((1, 2)) & bool(np.isfinite(r).all())
-    a = np.where(fin[:, None, None], x, 0.0)
-    a = a - a.mean(1, keepdims=True)
-    S = np.einsum("nbi,bj->nij", a, np.where(np.isfinite(r0), r0, 0.0))
-    U, sv, Vt = np.linalg.svd(S)
-    d = np.sign(np.linalg.det(U @ Vt))
-    d[d == 0] = 1.0
-    D = np.stack([np.ones_like(d), np.ones_like(d), d], 1)
-    R = np.einsum("nji,nj,nkj->nik", Vt, D, U)               # V D U^T
-    sv[:, -1] *= d
-    msd = ((a * a).sum((1, 2)) + (r0 * r0).sum() - 2 * sv.sum(1)) / x.shape[1]
-    nan = np.where(fin, 0.0, np.nan)
-    return {"finite": fin, "R": R + nan[:, None, None], "aligned": np.einsum("nij,nbj->nbi", R, a) + cr + nan[:, None, None],
-            "rmsd": np.sqrt(np.maximum(msd, 0.0)) + nan, "gap": np.where(fin, horn_gap(S), np.nan)}
-
-
-def stats64(o, ref):
-    """(dsum (N, 3), dsq (N,), count, sum |d| (N, 3)) of the oracle's aligned frames: what dff_superpose accumulates, and
-    the sum of the absolute terms its tolerance is relative to"""
-    d = o["aligned"][o["finite"]] - np.asarray(ref, np.float32).astype(np.float64)
-    return d.sum(0), (d * d).sum((0, 2)), int(o["finite"].sum()), np.abs(d).sum(0)
-
-
+# ---------------------------------------------------------------- the oracle as the kernel's stand-in
 def numpy_aligner(calls=None):
     """aligner(xyz, ref) -> (dsum, dsq, count) for evaluate.mean_structure / rmsf, from the oracle"""
     def aligner(xyz, ref):
@@ -82,22 +31,6 @@ def numpy_aligner(calls=None):
         o = superpose64(np.asarray(torch.as_tensor(xyz)), ref)
         return stats64(o, ref)[:3]
     return aligner
-
-
-def noisy_ensemble(rng, template, n, sigma):
-    """n copies of the template, each with Gaussian noise of width sigma, randomly rotated and translated"""
-    N = len(template)
-    x = np.empty((n, N, 3), np.float32)
-    for s in range(n):
-        x[s] = (template + sigma * rng.standard_normal((N, 3))) @ rand_rot(rng).T + 10 * rng.standard_normal(3)
-    return x
-
-
-def golden_frames(golden, mol):
-    """(frames with the golden's injected non-finite coordinates, folded structure float32)"""
-    f = golden("struct_folded.npz")[mol].astype(np.float32)
-    x = golden("struct_ref_ala2.npz")["x"] if mol == "ala2" else x_rmsd(golden(f"struct_ref_{mol}.npz"))
-    return x, f
 
 
 # ---------------------------------------------------------------- the oracle itself

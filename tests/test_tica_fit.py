@@ -4,8 +4,8 @@ dff_struct_tic_features / dff_tica_moments (csrc/dff_tica.hip).
 CPU part: the decomposition against the reference's saved chignolin model (its pickle) and trp-cage model
 (tests/golden/tica_trp_cage_cov.npz, recorded by tests/golden/make_golden_tica_fit.py), the sums -> covariances algebra
 against direct centred formulas, rank truncation, refusals and the .npz round trip.
-GPU part (-m gpu): features and moments against float64 numpy, determinism and streaming, fits of seeded
-Ornstein-Uhlenbeck trajectories against a float64 pipeline, the evaluators' fit path, and the ABI's refusals.
+GPU part (-m gpu): features and moments against float64 numpy (oracle/struct_metric.py, oracle/tica_fit.py), determinism and
+streaming, fits of seeded Ornstein-Uhlenbeck trajectories against a float64 pipeline, the evaluators' fit path, and the ABI's refusals.
 """
 import os
 
@@ -14,42 +14,15 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-
-
-def ev():
-    from dff_amd import evaluate
-    return evaluate
-
-
-def mirror(triu, F):
-    m = np.zeros((F, F))
-    m[np.triu_indices(F)] = triu
-    return m + np.triu(m, 1).T
-
-
-def sign_aligned_rel(W, R):
-    """per-column relative error of W against R, each column of W flipped to R's sign"""
-    W = W * np.sign((W * R).sum(0))
-    return np.linalg.norm(W - R, axis=0) / np.linalg.norm(R, axis=0)
-
-
-# ---------------------------------------------------------------- float64 oracles
-def moments64(g, lengths, lag):
-    """(S_x, S_y, M_0, M_tau, w) of dff_tica_moments over shifted float64 features g"""
-    X, Y, o = [], [], 0
-    for L in lengths:
-        if L > lag:
-            X.append(g[o:o + L - lag])
-            Y.append(g[o + lag:o + L])
-        o += L
-    F = g.shape[1]
-    X = np.concatenate(X) if X else np.zeros((0, F))
-    Y = np.concatenate(Y) if Y else np.zeros((0, F))
-    return X.sum(0), Y.sum(0), X.T @ X + Y.T @ Y, X.T @ Y + Y.T @ X, len(X)
+from oracle.frames import ou_trajectories
+from oracle.struct_metric import tic_features64
+from oracle.tica_fit import mirror, moments64, sign_aligned_rel
+from support import dev, ev  # noqa: F401  (dev: fixture)
 
 
 def fit64(f, lengths, lag, dim=2):
-    """the whole fit in float64 numpy on given features f (n, F): shift = f[0]"""
+    """the whole fit in float64 numpy on given features f (n, F): shift = f[0].  (Not in oracle/tica_fit.py: it runs the
+    product's own host algebra on the oracle's moments, and oracle/ does not import dff_amd.)"""
     s = np.asarray(f[0], np.float64)
     sx, sy, m0, mt, w = moments64(np.asarray(f, np.float64) - s, lengths, lag)
     mean, c00, c0t = ev().tica_covariances(sx, sy, m0, mt, w, s)
@@ -196,44 +169,6 @@ def test_chunk_plan_covers_every_pair_once():
 
 
 # ================================================================ GPU
-@pytest.fixture(scope="module")
-def dev():
-    import dff_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    dff_amd.load_library()
-    return torch.device("cuda:0")
-
-
-def tic_features64(x):
-    x = np.asarray(x, np.float64)
-    N = x.shape[1]
-    i = np.arange(N - 3)
-    b1, b2, b3 = x[:, i + 1] - x[:, i], x[:, i + 2] - x[:, i + 1], x[:, i + 3] - x[:, i + 2]
-    c1, c2 = np.cross(b2, b3), np.cross(b1, b2)
-    dih = np.arctan2((b1 * c1).sum(-1) * np.sqrt((b2 * b2).sum(-1)), (c1 * c2).sum(-1))
-    iu = np.triu_indices(N, 1)
-    return np.hstack([dih, np.linalg.norm(x[:, iu[0]] - x[:, iu[1]], axis=-1)])
-
-
-def ou_trajectories(folded, lengths, seed, rho_slow=0.999, rho_fast=0.6, sigma=1.5):
-    """seeded Ornstein-Uhlenbeck trajectories around a folded structure: 3N modes of a random orthonormal basis, their
-    autocorrelations spread from rho_slow to rho_fast per frame"""
-    rng = np.random.default_rng(seed)
-    f = np.asarray(folded, np.float64).reshape(-1)
-    D = f.size
-    Q, _ = np.linalg.qr(rng.standard_normal((D, D)))
-    rho = np.geomspace(rho_slow, rho_fast, D)
-    out = []
-    for L in lengths:
-        z = np.empty((L, D))
-        z[0] = rng.standard_normal(D) * sigma
-        eps = rng.standard_normal((L, D)) * sigma * np.sqrt(1 - rho ** 2)
-        for t in range(1, L):
-            z[t] = rho * z[t - 1] + eps[t]
-        out.append((f + z @ Q.T).reshape(L, -1, 3).astype(np.float32))
-    return out
-
-
 def gpu_moments(x, lengths, lag, shift, workspace=None):
     from dff_amd import binding
     F = binding.struct_tic_num_features(x.shape[1])
