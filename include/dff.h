@@ -461,6 +461,43 @@ int dff_superpose(int device, const float* x_dev, long long n, int n_beads, cons
                   double* dsum_dev, double* dsq_dev, uint64_t* count_dev,
                   void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- clustering one ensemble under the RMSD with a cutoff: neighbour bit-matrix and the greedy loop of Daura et al.,
+ * `gmx cluster -method gromos` (csrc/dff_cluster.hip) ----
+ * Stateless like the calls above; enqueued on `stream` only, no read-back and no synchronisation on the launch path, no
+ * floating-point atomics; bad arguments are refused on the host before any device call; n == 0 is a valid no-op.
+ * n <= 2^18 frames (8 GiB of bits; DFF_EINVAL beyond).
+ *
+ * The neighbour matrix of x_dev (n, n_beads, 3), fp32 in Angstrom, 4 <= n_beads <= 64, against itself, one BIT per pair:
+ * adj_dev is n rows of W = ceil(n / 64) uint64_t words, every word overwritten.  Bit r & 63 of word s * W + (r >> 6) is
+ * set when s != r, both frames are finite and d(s, r) <= cutoff as fp32, where d(s, r) is the value dff_rmsd_matrix(x, x)
+ * writes at [min(s, r), max(s, r)], BIT FOR BIT (the same per-pair routine, the lower index as the query; each pair is
+ * computed once).  The matrix is therefore symmetric by construction.  The diagonal bit is set for every finite frame by
+ * definition; a frame with a non-finite coordinate has an all-zero row and column; bits at positions >= n are zero.
+ * degree_dev (n) int32, may be NULL: the popcount of row s, self included.
+ * cutoff: finite and >= 0.  The same matrix from call to call: integer ORs only. */
+int dff_rmsd_neighbors(int device, const float* x_dev, long long n, int n_beads, float cutoff, uint64_t* adj_dev,
+                       int* degree_dev, void* stream);
+/* Bytes of device workspace dff_gromos_steps needs for n frames (the alive mask and one key); -1 on bad arguments. */
+long long dff_gromos_workspace_bytes(long long n);
+/* The greedy loop on a bit-matrix adj_dev as dff_rmsd_neighbors writes it (symmetric, the diagonal bit = "this frame takes
+ * part"); one call enqueues n_steps >= 0 iterations.  restart != 0 first initialises the state: labels = -1, centers = -1,
+ * sizes = 0, alive = the diagonal bits, progress_dev = {0 clusters, number of frames with a diagonal bit}.  The state
+ * between calls is labels / centers / sizes / progress and the workspace: keep them untouched and pass restart = 0 to go on.
+ * One iteration: among the alive frames the one with the largest popcount(row & alive), the LOWEST index among ties,
+ * becomes the centre of cluster c = progress[0]; its alive neighbours, itself included, get label c; centers[c] = its
+ * index, sizes[c] = their number; they leave alive; progress = {c + 1, unassigned - sizes[c]}.
+ * When the largest alive degree is 1, every alive frame becomes a singleton cluster in ascending index order within that
+ * same iteration -- the numbering the plain loop would give, without one iteration per singleton.  Clusters are capped
+ * at max_clusters >= 1: frames beyond the cap keep -1.  Iterations after the end (progress[1] == 0) or after the cap are
+ * no-ops decided on the device.  Clusters are numbered in order of creation: sizes are non-increasing.
+ *   labels_dev (n) int32; centers_dev, sizes_dev int32, the first min(max_clusters, n) entries are used;
+ *   progress_dev (2) int32; workspace_dev: >= dff_gromos_workspace_bytes(n) bytes, 8-byte aligned.
+ * Integer arithmetic only: bit-identical from call to call and for every split of the iterations over calls.  No
+ * workgroup waits on another: the phases of an iteration are separate launches. */
+int dff_gromos_steps(int device, const uint64_t* adj_dev, long long n, int restart, int n_steps, int max_clusters,
+                     int* labels_dev, int* centers_dev, int* sizes_dev, int* progress_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -10,6 +10,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                   [--n-clusters K --centers-fit-data TRAJ.pt]]
                                  [--coverage REF.pt [--rmsd-thresholds 1,2,4] [--coverage-subsample K]]
                                  [--flexibility HELDOUT.pt] [--write-aligned OUT.pt]
+                                 [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -31,6 +32,11 @@ evenly spaced frames of each ensemble.
 ((m, N, 3) Angstrom; FlexibilityEvaluator): both ensembles superposed on the folded structure of --folded-pdb when given,
 otherwise on HELDOUT's mean structure.  --write-aligned OUT.pt saves the samples superposed on the folded structure of
 --folded-pdb ((n, N, 3) float32, on the folded structure's centroid; NaN rows for non-finite samples).
+
+--clusters HELDOUT.pt adds, under "clusters", the populations of HELDOUT's conformations in the samples
+(RmsdClusterEvaluator): HELDOUT ((m, N, 3) Angstrom) is clustered under the RMSD with --cluster-cutoff (Angstrom; the
+method of `gmx cluster -method gromos`), every sample goes to the nearest cluster centre when that is within the cutoff.
+--cluster-stride K clusters every K-th frame of HELDOUT (the neighbour matrix holds at most 2^18 frames).
 """
 import argparse
 import json
@@ -100,6 +106,25 @@ def flexibility(a, x):
     return res
 
 
+def cluster_cutoff(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not (np.isfinite(v) and v >= 0):
+        raise argparse.ArgumentTypeError("the cutoff must be finite and >= 0")
+    return v
+
+
+def clusters(a, x):
+    ref = torch.load(a.clusters, map_location="cpu").float()
+    ev = evaluate.RmsdClusterEvaluator(ref, a.mol.lower(), a.cluster_cutoff, stride=a.cluster_stride, device=a.device)
+    res = ev.eval(x)
+    res["cutoff"] = ev.cutoff
+    res["centers"] = (ev.clusters.centers * a.cluster_stride).tolist()          # frame indices of HELDOUT
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -135,6 +160,11 @@ def build_parser():
                     help="ensemble (.pt, (m, N, 3) Angstrom) to compare the per-bead RMSF and the mean structure with")
     ap.add_argument("--write-aligned", default=None, metavar="OUT.pt",
                     help="save the samples superposed on the folded structure (needs --folded-pdb)")
+    ap.add_argument("--clusters", default=None, metavar="HELDOUT.pt",
+                    help="ensemble (.pt, (m, N, 3) Angstrom) to cluster by RMSD; report its clusters' populations in the samples")
+    ap.add_argument("--cluster-cutoff", type=cluster_cutoff, default=2.0, help="RMSD cutoff in Angstrom (with --clusters)")
+    ap.add_argument("--cluster-stride", type=int, default=1, metavar="K",
+                    help="cluster every K-th frame of the ensemble (with --clusters)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -144,6 +174,8 @@ def main():
     a = ap.parse_args()
     if a.coverage_subsample is not None and a.coverage_subsample < 1:
         ap.error("--coverage-subsample must be >= 1")
+    if a.cluster_stride < 1:
+        ap.error("--cluster-stride must be >= 1")
     if a.write_aligned and not a.folded_pdb:
         ap.error("--write-aligned needs --folded-pdb")
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
@@ -171,6 +203,8 @@ def main():
         res["coverage"] = coverage(a, x)
     if a.flexibility:
         res["flexibility"] = flexibility(a, x)
+    if a.clusters:
+        res["clusters"] = clusters(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

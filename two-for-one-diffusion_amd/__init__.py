@@ -15,6 +15,7 @@ __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_libr
            "LangevinDiffusion", "ForcesWrapper", "KMeans", "StateTransitionEvaluator", "eval_loss", "loss_profile",
            "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"]
 __all__ += ["superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"]
+__all__ += ["cluster_rmsd", "RmsdClusterEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -31,6 +32,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("cluster_rmsd", "RmsdClusterEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

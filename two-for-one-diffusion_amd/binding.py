@@ -108,6 +108,9 @@ SYMBOLS = {
     "dff_rmsd_matrix": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_longlong, C.c_int, _P, _P]),
     "dff_superpose_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int]),
     "dff_superpose": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dff_rmsd_neighbors": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
+    "dff_gromos_workspace_bytes": (C.c_longlong, [C.c_longlong]),
+    "dff_gromos_steps": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -772,3 +775,57 @@ def superpose(x, ref, aligned=True, rot=False, rmsd=False, stats=False, out=None
                                   _ptr(res.get("rmsd")), _ptr(res.get("dsum")), _ptr(res.get("dsq")), _ptr(res.get("count")),
                                   _ptr(workspace), ws_bytes, _stream(x)), "dff_superpose")
     return res
+
+
+# ---- clustering under the RMSD with a cutoff (dff_rmsd_neighbors, dff_gromos_*) ----
+CLUSTER_MAX_FRAMES = 1 << 18
+
+
+def rmsd_neighbors(x, cutoff: float, degree=True):
+    """The neighbour bit-matrix of the frames x (n, N, 3) against themselves (dff_rmsd_neighbors) -> (adj, degree): adj an
+    int64 CUDA tensor (n, ceil(n / 64)) whose bit r & 63 of word [s, r >> 6] says RMSD(s, r) <= cutoff (the diagonal bit:
+    the frame is finite), degree an int32 CUDA tensor (n,) of row popcounts (None with degree=False).  Nothing is read back."""
+    import torch
+    lib = load_library()
+    x, n, N = _coords(x)
+    adj = torch.empty((n, (n + 63) // 64), dtype=torch.int64, device=x.device)
+    deg = torch.empty(n, dtype=torch.int32, device=x.device) if degree else None
+    _check(lib, lib.dff_rmsd_neighbors(x.device.index, _ptr(x), n, N, float(cutoff), _ptr(adj), _ptr(deg), _stream(x)),
+           "dff_rmsd_neighbors")
+    return adj, deg
+
+
+def gromos_workspace_bytes(n: int) -> int:
+    return _workspace_bytes("dff_gromos_workspace_bytes", int(n))
+
+
+def gromos_state(adj, max_clusters: int):
+    """Fresh buffers of a greedy loop on the bit-matrix adj (n, ceil(n / 64)) int64 CUDA: a dict of labels (n,), centers
+    and sizes (min(max_clusters, n),), progress (2,), all int32, and the workspace; the first gromos_steps call on it restarts."""
+    import torch
+    n = int(adj.shape[0])
+    k = max(min(int(max_clusters), n), 1)
+    i32 = dict(dtype=torch.int32, device=adj.device)
+    return {"labels": torch.empty(n, **i32), "centers": torch.empty(k, **i32), "sizes": torch.empty(k, **i32),
+            "progress": torch.empty(2, **i32), "max_clusters": int(max_clusters), "fresh": True,
+            "workspace": torch.empty(gromos_workspace_bytes(n), dtype=torch.uint8, device=adj.device)}
+
+
+def gromos_steps(adj, state, n_steps: int, restart=None):
+    """Enqueue n_steps iterations of the greedy loop (dff_gromos_steps) on `state` (gromos_state); restart=None restarts a
+    fresh state only.  Nothing is read back: state["progress"] holds (clusters, frames left) on the device."""
+    import torch
+    lib = load_library()
+    if not (isinstance(adj, torch.Tensor) and adj.is_cuda and adj.dtype == torch.int64 and adj.is_contiguous()
+            and adj.dim() == 2 and adj.shape[1] == (adj.shape[0] + 63) // 64):
+        raise ValueError("adj must be a contiguous int64 CUDA tensor of shape (n, ceil(n / 64))")
+    n = int(adj.shape[0])
+    if int(state["labels"].numel()) != n:
+        raise ValueError(f"the state is for {int(state['labels'].numel())} frames, adj has {n}")
+    restart = state["fresh"] if restart is None else bool(restart)
+    ws = state["workspace"]
+    _check(lib, lib.dff_gromos_steps(adj.device.index, _ptr(adj), n, int(restart), int(n_steps), int(state["max_clusters"]),
+                                     _ptr(state["labels"]), _ptr(state["centers"]), _ptr(state["sizes"]),
+                                     _ptr(state["progress"]), _ptr(ws), int(ws.numel()), _stream(adj)), "dff_gromos_steps")
+    state["fresh"] = False
+    return state

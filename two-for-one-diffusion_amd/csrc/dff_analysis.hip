@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 
 #include "dff_pwd.hip"
@@ -9,6 +9,7 @@
 #include "dff_states.hip"
 #include "dff_ensemble.hip"
 #include "dff_superpose.hip"
+#include "dff_cluster.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -623,5 +624,83 @@ extern "C" int dff_superpose(int device, const float* x, long long n, int N, con
                            (int)superpose_grid(n), N, dsum, dsq, (unsigned long long*)count);
         HIPCHK(hipGetLastError());
     }
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Clustering under the RMSD with a cutoff: neighbour bit-matrix and the greedy loop (dff_cluster.hip)
+// ---------------------------------------------------------------------------------------------
+static int cluster_check_frames(long long n, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (n > DFF_CLU_MAX_N) return fail(DFF_EINVAL, "%s: more than 2^18 frames (the bit matrix would exceed 8 GiB)", what);
+    return DFF_OK;
+}
+
+extern "C" int dff_rmsd_neighbors(int device, const float* x, long long n, int N, float cutoff, uint64_t* adj, int* degree,
+                                  void* stream_) {
+    int rc = cluster_check_frames(n, "rmsd_neighbors");
+    if (rc) return rc;
+    if ((rc = check_beads(N, "rmsd_neighbors"))) return rc;
+    if (!(cutoff >= 0.0f) || !(cutoff <= 3.402823466e38f))
+        return fail(DFF_EINVAL, "rmsd_neighbors: cutoff must be finite and >= 0");
+    if (n == 0) return DFF_OK;
+    if (!x) return fail(DFF_EINVAL, "rmsd_neighbors: null frames");
+    if (!adj) return fail(DFF_EINVAL, "rmsd_neighbors: null adjacency matrix");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long W = clu_words(n);
+    HIPCHK(hipMemsetAsync(adj, 0, (size_t)(n * W) * sizeof(uint64_t), stream));
+    const long long nct = (n + DFF_ENS_TC - 1) / DFF_ENS_TC;
+    const long long nqt = (n + DFF_ENS_TQ - 1) / DFF_ENS_TQ;
+    hipLaunchKernelGGL(dff_clu_neighbors_kernel, dim3((unsigned)nct, (unsigned)((nqt + DFF_CLU_GROUP - 1) / DFF_CLU_GROUP)),
+                       dim3(DFF_ENS_THREADS), (unsigned)(ens_lds_doubles(ens_np(N)) * sizeof(double)), stream, x, n, N, cutoff,
+                       (unsigned*)adj);
+    HIPCHK(hipGetLastError());
+    if (degree) {
+        hipLaunchKernelGGL(dff_clu_degree_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream,
+                           (const unsigned long long*)adj, n, degree);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+extern "C" long long dff_gromos_workspace_bytes(long long n) {
+    if (cluster_check_frames(n, "gromos_workspace_bytes")) return -1;
+    return (clu_words(n) + 1) * (long long)sizeof(uint64_t);           // alive | key
+}
+
+extern "C" int dff_gromos_steps(int device, const uint64_t* adj, long long n, int restart, int n_steps, int max_clusters,
+                                int* labels, int* centers, int* sizes, int* progress, void* workspace, size_t workspace_bytes,
+                                void* stream_) {
+    int rc = cluster_check_frames(n, "gromos_steps");
+    if (rc) return rc;
+    if (n_steps < 0) return fail(DFF_EINVAL, "gromos_steps: negative n_steps");
+    if (max_clusters < 1) return fail(DFF_EINVAL, "gromos_steps: max_clusters must be >= 1");
+    if (!progress) return fail(DFF_EINVAL, "gromos_steps: null progress");
+    if (n > 0 && !adj) return fail(DFF_EINVAL, "gromos_steps: null adjacency matrix");
+    if (n > 0 && (!labels || !centers || !sizes)) return fail(DFF_EINVAL, "gromos_steps: null output");
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_gromos_workspace_bytes(n), "gromos_steps"))) return rc;
+    if ((uintptr_t)workspace % sizeof(uint64_t)) return fail(DFF_EINVAL, "gromos_steps: the workspace must be 8-byte aligned");
+    if (!restart && n_steps == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (restart) HIPCHK(hipMemsetAsync(progress, 0, 2 * sizeof(int), stream));
+    if (n == 0) return DFF_OK;
+    const int kmax = max_clusters < n ? max_clusters : (int)n;         // a cluster has at least one frame
+    const unsigned long long* a = (const unsigned long long*)adj;
+    unsigned long long* alive = (unsigned long long*)workspace;
+    unsigned long long* key = alive + clu_words(n);
+    if (restart) {
+        hipLaunchKernelGGL(dff_clu_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, n, kmax, labels,
+                           centers, sizes, progress, alive, key);
+        HIPCHK(hipGetLastError());
+    }
+    for (int it = 0; it < n_steps; ++it) {
+        hipLaunchKernelGGL(dff_clu_count_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a, n, kmax, progress,
+                           alive, key);
+        hipLaunchKernelGGL(dff_clu_apply_kernel, dim3(1), dim3(DFF_CLU_APPLY_THREADS), 0, stream, a, n, kmax, labels, centers,
+                           sizes, progress, alive, key);
+    }
+    HIPCHK(hipGetLastError());
     return DFF_OK;
 }

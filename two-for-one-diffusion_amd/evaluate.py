@@ -1264,3 +1264,146 @@ class FlexibilityEvaluator:
         s, r = self.profile(x), self.profiles["refs"]
         self.profiles["samples"] = s
         return self.summarize(s["rmsf"], r["rmsf"], s["mean"], r["mean"], _count_nonfinite(x), self.refs_nonfinite)
+
+
+# =====================================================================================================
+# Clustering an ensemble under the RMSD with a cutoff: the method of Daura et al. (1999), `gmx cluster -method gromos`
+# (dff_rmsd_neighbors, dff_gromos_steps; csrc/dff_cluster.hip).  The reference's evaluators have no model-free answer to
+# "which conformations are in this ensemble, and how populated is each": its states live in TIC space.
+# =====================================================================================================
+class RmsdClusters:
+    """Result of cluster_rmsd: labels (n,) int64 numpy (-1: a frame with a non-finite coordinate, or one beyond
+    max_clusters), centers (K,) frame indices, sizes (K,) in order of creation (non-increasing), and the cutoff.  With a
+    stride the indices count the STRIDED frames xyz[::stride]; `stride` is kept."""
+
+    def __init__(self, labels, centers, sizes, cutoff, stride=1):
+        self.labels, self.centers, self.sizes = labels, centers, sizes
+        self.cutoff, self.stride = float(cutoff), int(stride)
+
+    @property
+    def n_clusters(self):
+        return len(self.centers)
+
+    def __repr__(self):
+        return f"RmsdClusters({self.n_clusters} clusters of {len(self.labels)} frames at {self.cutoff:g} A, sizes {self.sizes[:8].tolist()})"
+
+
+def cluster_rmsd(xyz, cutoff, *, max_clusters=None, stride=1, steps_per_sync=64, device="cuda:0"):
+    """Cluster the structures xyz (n, N, 3) (Angstrom) under the minimum RMSD over proper rotations with `cutoff`: count every
+    frame's neighbours within the cutoff; the frame with the most (the lowest index among ties) becomes a centre and takes
+    its neighbours with it; repeat on what is left.  -> RmsdClusters.  The neighbour matrix is one bit per pair on the
+    device (n^2 / 8 bytes, n <= 2^18); `stride` > 1 clusters xyz[::stride] (for ensembles beyond that) and the labels,
+    centres and sizes are those of the STRIDED frames.  The loop runs on the device steps_per_sync iterations at a time;
+    between rounds two integers (clusters, frames left) are read."""
+    dev = torch.device(device)
+    stride, steps = int(stride), int(steps_per_sync)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    if steps < 1:
+        raise ValueError("steps_per_sync must be >= 1")
+    if max_clusters is not None and int(max_clusters) < 1:
+        raise ValueError("max_clusters must be >= 1")
+    xs = torch.as_tensor(xyz)
+    if xs.dim() != 3 or xs.shape[-1] != 3:
+        raise ValueError("structures must be (n, n_beads, 3)")
+    x = _frames(xs[::stride] if stride > 1 else xs, dev)
+    n = len(x)
+    if n > binding.CLUSTER_MAX_FRAMES:
+        raise ValueError(f"{n} frames exceed the {binding.CLUSTER_MAX_FRAMES} of the neighbour matrix: pass a stride")
+    kmax = n if max_clusters is None else int(max_clusters)
+    if n == 0:
+        e = np.empty(0, np.int64)
+        return RmsdClusters(e, e.copy(), e.copy(), cutoff, stride)
+    adj, _ = binding.rmsd_neighbors(x, cutoff, degree=False)
+    state = binding.gromos_state(adj, kmax)
+    while True:
+        binding.gromos_steps(adj, state, steps)
+        k, left = (int(v) for v in state["progress"].cpu())
+        if left <= 0 or k >= kmax:
+            break
+    return RmsdClusters(state["labels"].cpu().numpy().astype(np.int64), state["centers"][:k].cpu().numpy().astype(np.int64),
+                        state["sizes"][:k].cpu().numpy().astype(np.int64), cutoff, stride)
+
+
+class RmsdClusterEvaluator:
+    """Populations of the conformations of a reference ensemble (MD data) in a sampled ensemble, by RMSD clustering.
+
+    ref_data (m, N, 3) in Angstrom is clustered once (cluster_rmsd with `cutoff`, `max_clusters`, `stride`); the centres
+    are the structures ref[::stride][centers].  eval(samples) assigns every sample to its nearest centre (nearest_rmsd);
+    it belongs to that cluster when the RMSD is <= cutoff and is unassigned otherwise.  A plain dict:
+      n_clusters                      clusters of the reference ensemble with at least min_size frames
+      populations_ref, populations_samples   lists over those clusters (order of creation), shares of the finite frames
+                                      of each side; the reference's are its own cluster sizes
+      population_js                   js_divergence of the two count vectors, unassigned as one extra bin (for the
+                                      reference: the frames of clusters below min_size, or beyond max_clusters)
+      unassigned_share                share of the finite samples that belong to no cluster of size >= min_size
+      largest_cluster_share_ref, largest_cluster_share_samples
+      samples_nonfinite, refs_nonfinite   frames with a non-finite coordinate: left out on their side
+    Without the HIP library: DffLibraryError."""
+
+    def __init__(self, ref_data, mol_name="", cutoff=2.0, max_clusters=None, min_size=1, stride=1, *, chunk=None,
+                 device="cuda:0"):
+        self.mol_name = mol_name
+        self.cutoff = float(cutoff)
+        self.min_size = int(min_size)
+        if not np.isfinite(self.cutoff) or self.cutoff < 0:
+            raise ValueError("RmsdClusterEvaluator: cutoff must be finite and >= 0")
+        if self.min_size < 1:
+            raise ValueError("RmsdClusterEvaluator: min_size must be >= 1")
+        self.chunk = chunk
+        self.device = torch.device(device)
+        binding.load_library()
+        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+            ref_data = ref_data[:][0]
+        refs = _frames(ref_data, self.device)
+        self.refs = refs[::int(stride)].contiguous() if int(stride) > 1 else refs
+        self.refs_nonfinite = _count_nonfinite(self.refs)
+        self.clusters = cluster_rmsd(self.refs, self.cutoff, max_clusters=max_clusters, device=self.device)
+        self.centers = self.refs[torch.as_tensor(self.clusters.centers, device=self.device)]
+
+    @staticmethod
+    def summarize(sizes_ref, n_ref_finite, labels_samples, min_size=1, samples_nonfinite=0, refs_nonfinite=0):
+        """eval()'s dict from the reference's cluster sizes (K,), the number of its finite frames, and the samples' labels
+        (n,): the cluster of each FINITE sample, -1 for one that is unassigned (non-finite samples are not in it): numpy only."""
+        sizes = np.asarray(sizes_ref, np.int64).reshape(-1)
+        lab = np.asarray(labels_samples, np.int64).reshape(-1)
+        keep = sizes >= int(min_size)
+        ref_counts = sizes[keep]
+        smp_all = np.bincount(lab[lab >= 0], minlength=len(sizes))[:len(sizes)] if len(sizes) else np.zeros(0, np.int64)
+        smp_counts = smp_all[keep]
+        n_ref, n_smp = int(n_ref_finite), int(len(lab))
+        ref_un, smp_un = n_ref - int(ref_counts.sum()), n_smp - int(smp_counts.sum())
+        nan = float("nan")
+        pr = ref_counts / n_ref if n_ref else np.full(len(ref_counts), nan)
+        ps = smp_counts / n_smp if n_smp else np.full(len(smp_counts), nan)
+        js = nan
+        if n_ref and n_smp:
+            js = float(js_divergence(np.append(ref_counts, ref_un).astype(np.float64),
+                                     np.append(smp_counts, smp_un).astype(np.float64)))
+        return {"n_clusters": float(keep.sum()), "populations_ref": pr.tolist(), "populations_samples": ps.tolist(),
+                "population_js": js, "unassigned_share": smp_un / n_smp if n_smp else nan,
+                "largest_cluster_share_ref": float(pr.max()) if len(pr) else nan,
+                "largest_cluster_share_samples": float(ps.max()) if len(ps) else nan,
+                "samples_nonfinite": float(samples_nonfinite), "refs_nonfinite": float(refs_nonfinite)}
+
+    def assign(self, samples):
+        """(frames on the device, labels int64 numpy (n,): the cluster of the nearest centre when it is within the cutoff,
+        -1 otherwise, -2 for a sample with a non-finite coordinate)"""
+        x = _frames(samples, self.device)
+        if x.shape[1] != self.refs.shape[1]:
+            raise ValueError(f"samples have {int(x.shape[1])} beads, the reference ensemble {int(self.refs.shape[1])}")
+        if len(self.centers) == 0 or len(x) == 0:
+            d = torch.full((len(x),), float("nan"), device=self.device)
+            idx = torch.full((len(x),), -1, dtype=torch.int64, device=self.device)
+        else:
+            d, idx = nearest_rmsd(x, self.centers, chunk=self.chunk, device=self.device)
+        lab = torch.where(d <= self.cutoff, idx, torch.full_like(idx, -1))           # NaN compares false
+        fin = torch.isfinite(x).all(dim=2).all(dim=1)
+        lab = torch.where(fin, lab, torch.full_like(lab, -2))
+        return x, lab.cpu().numpy()
+
+    def eval(self, samples):
+        x, lab = self.assign(samples)
+        n_ref = len(self.refs) - self.refs_nonfinite
+        return self.summarize(self.clusters.sizes, n_ref, lab[lab >= -1], self.min_size, int((lab == -2).sum()),
+                              self.refs_nonfinite)
