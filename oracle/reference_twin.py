@@ -234,10 +234,14 @@ def langevin_constants(norm_factor: float, t: int, sched, temp_data: float, temp
     return out
 
 
-def forces(p, x: torch.Tensor, c: dict, n_layers: int, t_norm: Optional[float] = None) -> torch.Tensor:
-    """ForcesWrapper.forward, dynamics/langevin.py:75-92: -GNN(x)/kbt_inv/sigma_t."""
+def forces(p, x: torch.Tensor, c: dict, n_layers: int, t_norm: Optional[float] = None, conservative: bool = True,
+           flags=(True, False, False), force_factor: float = 1.0) -> torch.Tensor:
+    """ForcesWrapper.forward, dynamics/langevin.py:75-92: -GNN(x)/kbt_inv/sigma_t.
+
+    ``conservative`` and ``flags`` choose the network's head and input branch (as in ``score``); ``force_factor`` scales
+    the result -- a deliberately wrong force field, for the tests that show a comparison would notice one."""
     tn = torch.tensor([c["t_norm"] if t_norm is None else t_norm], dtype=torch.float32).to(x.dtype)
-    return -score(p, x, tn, n_layers) / c["kbt_inv"] / c["sigma_t"]
+    return -score(p, x, tn, n_layers, conservative=conservative, flags=flags) / c["kbt_inv"] / c["sigma_t"] * force_factor   # (x 1.0 is exact)
 
 
 def langevin_step(x_old, v_old, f, noise, masses: torch.Tensor, c: dict):
@@ -258,23 +262,25 @@ def overdamped_step(x_old, f, noise, c: dict):
 
 
 def simulate(p, x0: torch.Tensor, noises: torch.Tensor, masses, c: dict, n_layers: int,
-             save_interval: int):
+             save_interval: int, v0: Optional[torch.Tensor] = None, conservative: bool = True,
+             flags=(True, False, False), force_factor: float = 1.0):
     """Langevin.simulate, dynamics/langevin_cgnet.py:686-792, noise supplied as noises[step].
 
     x0 in normalised units (init_mol / norm_factor, langevin.py:135).  Returns
     (frames (n_sims, n_frames, N, 3), kinetic energies (n_sims, n_frames) or None, x, v).
     The saved frame is the UN-centred x_new (:521); centring happens at the top of the next
-    step (:739).  v0 = 0 (:679).
+    step (:739).  v0 = 0 (:679) unless given: the state a chunked run carries over.  ``conservative``, ``flags`` and
+    ``force_factor`` go to ``forces``.
     """
     length = noises.shape[0]
     assert length % save_interval == 0  # langevin_cgnet.py:305-309
     m = torch.as_tensor(masses, dtype=torch.float32).to(x0.dtype)
     x = x0
-    v = None if c["friction"] is None else torch.zeros_like(x0)
+    v = None if c["friction"] is None else (torch.zeros_like(x0) if v0 is None else v0.to(x0.dtype))
     frames, kes = [], []
     for s in range(length):
         x = center_zero(x)
-        f = forces(p, x, c, n_layers)
+        f = forces(p, x, c, n_layers, conservative=conservative, flags=flags, force_factor=force_factor)
         if c["friction"] is None:
             x = overdamped_step(x, f, noises[s], c)
         else:

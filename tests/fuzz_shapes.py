@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Random model shapes / batch shapes / magnitudes against the oracle twin (float64): forces (dff_score; all input branches, energy
 and force heads, batches of 1 .. 900) and a few fused Langevin and reverse-DDPM steps on supplied noise (shipped branch, energy
-head).  The bars are the tests': GUARD x the twin's own float32 distance for forces, STEP_TOL per step for the loops.
+head; frames and final velocities).  The bars are the tests': GUARD x the twin's own float32 distance for forces, STEP_TOL per
+step for the loops.
 test_gpu_parity.py::test_random_shapes runs a short sweep; `python tests/fuzz_shapes.py [n_cases] [seed]` a long one (GPU box)."""
 import os, sys, json
 import numpy as np, torch
@@ -105,10 +106,11 @@ def _case(case, rng, log, only=None, hook=None):
         fr, ke, xl, vl = twin.simulate(twin.to_torch(params, torch.float64), torch.from_numpy(x0).double() / norm, torch.from_numpy(noises).double(), masses, c, L, 2)
         ref = (fr * norm).numpy()
         el = float(np.abs(traj - ref).max() / max(np.abs(ref).max(), 1e-30))
+        ev = float(np.abs(ld.v.cpu().numpy() - vl.numpy()).max() / max(np.abs(vl.numpy()).max(), 1e-30))   # (the velocities see the force)
         kl = model.native.last_launch()[0]
-        tag.update(langevin_err=float("%.3g" % el), status=int(model.native.status()))
+        tag.update(langevin_err=float("%.3g" % el), langevin_verr=float("%.3g" % ev), status=int(model.native.status()))
         if kl != kn: tag.update(kernel_l=kl)
-        ok = ok and el <= STEP_TOL * K and model.native.status() == 0
+        ok = ok and el <= STEP_TOL * K and ev <= STEP_TOL * K and model.native.status() == 0
         # ... and of the reverse-DDPM loop, t = K - 1 .. 0
         xd = synth.normal((P, N, 3), 45 + case, N).astype(np.float32)
         xd = (xd - xd.mean(1, keepdims=True)) * 0.6

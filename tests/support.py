@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import noise
 from oracle import reference_twin as twin
 from oracle import synth
 
@@ -20,6 +21,8 @@ GAP_MIN = 1e-2            # strict superposition comparisons run on frames with 
 MAX_EXCLUDED = 0.02       # at most this share of a data set may fall below it
 GUARD = 2.0        # rel(hip, ref64) <= GUARD * rel(ref32, ref64): the split engine (every shipped architecture's default path)
 GUARD_FP32 = 2.5   # ... the fp32-MFMA engine (DFF_SPLIT_BF16=0, `gen` branches, hidden 256)
+M_DRAW = 4.0       # |kernel draw - normals64| <= M_DRAW * E32 (test_noise_stream.py derives it)
+EPS = 2.0 ** -24   # relative error of one float32 rounding
 
 
 # ---------------------------------------------------------------- the package and the device
@@ -103,6 +106,12 @@ def assert_close(got, want, what=""):
 def rel(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def e32_of(seed, items, steps, N):
+    """E32 of the draws under test and normals64 of them."""
+    z64 = noise.normals64(seed, items, steps, N)
+    return float(np.abs(noise.normals32_plain(seed, items, steps, N).astype(np.float64) - z64).max()), z64
 
 
 def guard_for(kname):

@@ -15,17 +15,14 @@ within M_DRAW * E32 of normals64.  A wrong counter, word, step or item gives an 
 factor only guards the accuracy claim.
 MEASURED on the MI355X: worst draw 4.3e-7 = 0.65 x E32 (docstring of test_langevin_one_step_reads_out_every_draw).
 """
-import contextlib
-
 import numpy as np
 import pytest
 
 from oracle import noise
 from oracle import synth
+from support import EPS, M_DRAW, e32_of as _e32
+from variants import CASES, HI, MODELS, Case, get_native
 
-M_DRAW = 4.0            # |kernel draw - normals64| <= M_DRAW * E32
-EPS = 2.0 ** -24        # relative error of one float32 rounding
-HI = 2 ** 32
 SEED = (0x9E3779B9 << 32) | 0x2545F491      # non-zero high word
 
 
@@ -110,101 +107,6 @@ def test_normals_shapes_and_components():
 # ------------------------------------------------------------------------------------------------ GPU: the kernels' draws
 gpu = pytest.mark.gpu
 
-# name -> (N, H, L, flags (intrinsic, distances, abs), conservative, weight seed)
-MODELS = {
-    "ala2": (5, 96, 2, (1, 0, 0), True, 1234),
-    "chignolin": (10, 64, 3, (1, 0, 0), True, 1234),
-    "n14": (14, 64, 2, (1, 0, 0), True, 1414),             # 14 rows on four waves: no idle wave, the update draws in line
-    "trp_cage": (20, 128, 3, (1, 0, 0), True, 1234),
-    "villin": (35, 128, 3, (1, 0, 0), True, 1234),
-    "protein_g": (56, 128, 3, (1, 0, 0), True, 1234),
-    "h256": (20, 256, 2, (1, 0, 0), True, 2580),
-    "chignolin_gen": (10, 64, 3, (0, 1, 1), True, 2468),
-    "trp_cage_gen": (20, 128, 3, (0, 1, 1), True, 2468),
-    "chignolin_nc": (10, 64, 3, (1, 0, 0), False, 4321),
-    "trp_cage_nc": (20, 128, 3, (1, 0, 0), False, 4321),
-}
-_models = {}
-
-
-def get_native(name):
-    import torch
-    if name not in _models:
-        from dff_amd.score import GraphTransformer
-        assert torch.cuda.is_available(), "GPU tests need a GPU"
-        N, H, L, (intr, dist, ab), cons, wseed = MODELS[name]
-        # real (seeded) weights at full decoder scale: the production kernel variants run, the fp16 engine stays engaged
-        p = synth.synth_gnn_params(N, H, L, seed=wseed, decoder_out=1 if cons else 3, node_in=N + 1 + 3 * ab,
-                                   edge_in=(3 * intr + dist) or 1)
-        _models[name] = GraphTransformer(N, H, device="cuda:0", n_layers=L, use_intrinsic_coords=bool(intr), use_abs_coords=bool(ab),
-                                         use_distances=bool(dist), conservative=cons, state_dict=p)
-    return _models[name].native
-
-
-class Case:
-    def __init__(self, cid, model, B, has, lacks=(), xi_pre=None, group=0, waves=0, generic=False, pair=True, max_wgs=2048,
-                 last_grid=None, offset=0, step_offset=0):
-        self.id, self.model, self.B, self.has, self.lacks, self.xi_pre = cid, model, B, has, lacks, xi_pre
-        self.group, self.waves, self.generic, self.pair, self.max_wgs, self.last_grid = group, waves, generic, pair, max_wgs, last_grid
-        self.offset, self.step_offset = offset, step_offset
-        self.N = MODELS[model][0]
-
-    @contextlib.contextmanager
-    def knobs(self):
-        nat = get_native(self.model)
-        try:
-            nat.set_group(self.group); nat.small_waves(self.waves); nat.force_generic(self.generic)
-            nat.pair(self.pair); nat.max_workgroups(self.max_wgs)
-            yield nat
-        finally:
-            nat.set_group(0); nat.small_waves(0); nat.force_generic(False); nat.pair(True); nat.max_workgroups(2048)
-
-    def check_launch(self, nat):
-        """The kernel this case exists for did run (and, for a batch cut into launches, the last launch's grid)."""
-        name, grid, _ = nat.last_launch()
-        assert all(h in name for h in self.has) and not any(l in name for l in self.lacks), (self.id, name)
-        if self.xi_pre is not None:     # the <= 16-row kernel pre-draws iff  rows * lanes-per-row <= (waves - 1) * 64  (dff_small.hip)
-            assert "dff_small_kernel<" in name
-            nw = 4 if ("pair" in name or name.split(",")[1].rstrip(">") == "4") else 8
-            G = self.group if self.group else 1
-            assert (min(G, self.B) * self.N * (32 if nw == 8 else 16) <= (nw - 1) * 64) == self.xi_pre, (self.id, name)
-        if self.last_grid is not None:
-            assert grid == self.last_grid, (self.id, grid)
-        return name
-
-
-S16, S64 = "dff_small_kernel<", "dff_fused_kernel<"
-CASES = [
-    # ---- the <= 16-row kernel: both sides of the xi_pre condition, 4 and 8 waves, groups, a ragged last group
-    Case("chignolin-g1", "chignolin", 12, (S16 + "64,8",), xi_pre=True, offset=0, step_offset=0),
-    Case("chignolin-8waves", "chignolin", 5, (S16 + "64,8",), xi_pre=True, waves=8, offset=HI - 3, step_offset=HI + 1),
-    Case("chignolin-4waves", "chignolin", 7, (S16 + "64,4",), xi_pre=True, waves=4, offset=7, step_offset=HI - 2),
-    Case("n14-fills-the-last-wave", "n14", 9, (S16 + "64,4",), xi_pre=False, offset=HI + 5, step_offset=HI - 2),
-    Case("ala2-g1-8waves", "ala2", 6, (S16 + "96,8",), xi_pre=True, waves=8, offset=HI - 3, step_offset=0),
-    Case("ala2-g2-8waves-ragged", "ala2", 7, (S16 + "96,8",), xi_pre=True, waves=8, group=2, offset=7, step_offset=HI + 1),
-    Case("ala2-g3-4waves-ragged", "ala2", 10, (S16 + "96,4",), xi_pre=False, waves=4, group=3, offset=HI - 3, step_offset=HI - 2),
-    Case("chignolin-gen", "chignolin_gen", 6, (S16 + "64,8", "gen"), xi_pre=True, offset=HI + 5, step_offset=0),
-    Case("chignolin-force-head", "chignolin_nc", 6, (S16 + "64,8",), xi_pre=True, offset=7, step_offset=HI + 1),
-    Case("chignolin-3-launches", "chignolin", 40, (S16 + "64,8",), xi_pre=True, max_wgs=16, last_grid=8, offset=HI - 17, step_offset=0),
-    Case("ala2-g3-3-launches", "ala2", 40, (S16 + "96,4",), xi_pre=False, waves=4, group=3, max_wgs=5, last_grid=4, offset=HI - 17,
-         step_offset=HI + 1),
-    # ---- the <= 64-row kernel: one and two workgroups per protein, the generic kernel on a small config, groups of ala2,
-    # hidden 256, a general-input branch, the force head
-    Case("ala2-default", "ala2", 9, (S64 + "96,1,",), offset=HI + 5, step_offset=HI - 2),
-    Case("ala2-g5-ragged", "ala2", 12, (S64 + "96,2,",), ("pair",), group=5, pair=False, offset=HI - 3, step_offset=0),
-    Case("chignolin-generic", "chignolin", 6, (S64 + "64,1,",), ("pair",), generic=True, pair=False, offset=HI - 3, step_offset=HI + 1),
-    Case("trp-cage-pair", "trp_cage", 6, (S64 + "128,2,", "pair"), offset=HI - 3, step_offset=HI - 2),
-    Case("trp-cage-one", "trp_cage", 6, (S64 + "128,2,",), ("pair",), pair=False, offset=7, step_offset=0),
-    Case("villin-pair", "villin", 5, (S64 + "128,3,", "pair"), offset=HI + 5, step_offset=HI + 1),
-    Case("villin-one", "villin", 5, (S64 + "128,3,",), ("pair",), pair=False, offset=HI - 3, step_offset=HI - 2),
-    Case("protein-g-pair", "protein_g", 4, (S64 + "128,4,", "pair"), offset=HI - 3, step_offset=0),
-    Case("protein-g-one", "protein_g", 4, (S64 + "128,4,",), ("pair",), pair=False, offset=0, step_offset=HI + 1),
-    Case("hidden-256", "h256", 5, (S64 + "256,",), pair=False, offset=HI - 3, step_offset=HI - 2),
-    Case("trp-cage-gen", "trp_cage_gen", 5, (S64 + "128,2,", "gen"), ("pair",), offset=HI - 3, step_offset=HI + 1),
-    Case("trp-cage-force-head", "trp_cage_nc", 5, (S64 + "128,2,",), ("pair",), offset=HI + 5, step_offset=0),
-    Case("trp-cage-3-launches", "trp_cage", 40, (S64 + "128,2,",), ("pair",), pair=False, max_wgs=16, last_grid=8, offset=HI - 17,
-         step_offset=HI - 2),
-]
 case_param = pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 
 
@@ -216,12 +118,6 @@ def _state(case, stream):
 
 def _items(case):
     return np.arange(case.B, dtype=np.uint64) + np.uint64(case.offset)
-
-
-def _e32(seed, items, steps, N):
-    """E32 of the draws under test and normals64 of them."""
-    z64 = noise.normals64(seed, items, steps, N)
-    return float(np.abs(noise.normals32_plain(seed, items, steps, N).astype(np.float64) - z64).max()), z64
 
 
 # Langevin parameters of (a) and (b): beta = 1 and masses 4^-k make noise_sigma = sqrt(1 / (beta m)) = 2^k exactly, a different
