@@ -174,33 +174,59 @@ def make_schedule(timesteps: int = 1000) -> Dict[str, torch.Tensor]:
 
 # ----------------------------------------------------------------------------- DDPM
 def p_sample(p, sched, x: torch.Tensor, t: int, noise: torch.Tensor, n_layers: int,
-             timesteps: int = 1000) -> torch.Tensor:
+             timesteps: int = 1000, conservative: bool = True, flags=(True, False, False),
+             probe: Optional[dict] = None, report: Optional[dict] = None) -> torch.Tensor:
     """One reverse step, models/ddpm.py:195-232, with the randn_like draw passed in.
 
-    All samples of a batch share the integer timestep ``t`` (ddpm.py:244-247).
-    """
+    All samples of a batch share the integer timestep ``t`` (ddpm.py:244-247).  ``conservative`` and ``flags`` choose the
+    network's head and input branch (as in ``score``).  ``probe`` (default off, and exact when off) makes a deliberately
+    wrong step, for the tests that show a comparison would notice one: ``{"eps_factor": f}`` scales the network output,
+    ``{"sched_shift": d}`` reads every schedule table at level t + d (clipped to the table; the network and the level-0
+    noise mask still see t).  ``report``, a dict, gets ``eps_max`` / ``noise_max`` / ``x0_max``: the largest |eps|,
+    |noise| (0 at level 0, where it is masked) and |x0 estimate| of this step, before or after their centring, appended
+    to lists."""
     dt = x.dtype
+    probe = probe or {}
     tt = torch.full((x.shape[0],), t, dtype=torch.long)
-    eps = score(p, x, (1.0 * tt / timesteps).to(dt), n_layers)
+    eps = score(p, x, (1.0 * tt / timesteps).to(dt), n_layers, conservative=conservative, flags=flags)
+    if "eps_factor" in probe:
+        eps = eps * probe["eps_factor"]
+    raw = (eps, noise)
     eps = center_zero(eps)
-    g = lambda name: sched[name][t].to(dt)
+    ts = min(max(t + probe.get("sched_shift", 0), 0), timesteps - 1)
+    g = lambda name: sched[name][ts].to(dt)
     x0 = g("sqrt_recip_alphas_cumprod") * x - g("sqrt_recipm1_alphas_cumprod") * eps
+    x0_raw = x0
     x0 = center_zero(x0)
     mean = g("posterior_mean_coef1") * x0 + g("posterior_mean_coef2") * x
     noise = center_zero(noise)
     nonzero = 0.0 if t == 0 else 1.0
+    if report is not None:
+        big = lambda *v: max(float(a.abs().max()) for a in v)  # noqa: E731
+        for k, v in (("eps_max", big(eps, raw[0])), ("noise_max", nonzero * big(noise, raw[1])), ("x0_max", big(x0, x0_raw))):
+            report.setdefault(k, []).append(v)
     return mean + nonzero * (0.5 * g("posterior_log_variance_clipped")).exp() * noise
 
 
 def p_sample_loop(p, sched, x_start: torch.Tensor, noises: torch.Tensor, t_start: int,
-                  n_layers: int, timesteps: int = 1000) -> torch.Tensor:
-    """models/ddpm.py:234-254 from x at time ``t_start`` down to 0; noises[k] feeds step k.
+                  n_layers: int, timesteps: int = 1000, t_end: int = 0, conservative: bool = True,
+                  flags=(True, False, False), probe: Optional[dict] = None, report: Optional[dict] = None) -> torch.Tensor:
+    """models/ddpm.py:234-254 from x at time ``t_start`` down to ``t_end`` (0: the whole chain); noises[k] feeds step k.
 
-    x_start must already be centred (ddpm.py:242).  Returns normalised units (no norm_factor).
-    """
+    x_start must already be centred (ddpm.py:242).  Returns normalised units (no norm_factor).  ``conservative``,
+    ``flags`` and ``probe`` go to ``p_sample``; the loop's own probe ``{"noise_shift": d}`` feeds step k with noises[k + d]
+    (``noises`` must hold the extra rows).  ``report``, a dict, gets what ``p_sample`` records per step, ``pre_clamp`` (each
+    step's x before the clamp, a list) and ``clamped``: a bool per sample, whether the clamp changed any of its coordinates
+    at any step."""
     mol = x_start
-    for k, i in enumerate(range(t_start, -1, -1)):
-        mol = p_sample(p, sched, mol, i, noises[k], n_layers, timesteps)
+    shift = (probe or {}).get("noise_shift", 0)
+    if report is not None:
+        report["clamped"] = torch.zeros(x_start.shape[0], dtype=torch.bool)
+    for k, i in enumerate(range(t_start, t_end - 1, -1)):
+        mol = p_sample(p, sched, mol, i, noises[k + shift], n_layers, timesteps, conservative, flags, probe, report)
+        if report is not None:
+            report.setdefault("pre_clamp", []).append(mol)
+            report["clamped"] |= (mol.abs() > 1000).flatten(1).any(1)
         mol = torch.clamp(mol, min=-1000, max=1000)  # ddpm.py:248-250 (identity unless exceeded)
         mol = center_zero(mol)
     return mol

@@ -28,6 +28,21 @@ just); v_last, where it is compared, notices once 7 - 20 % of the force is lost.
 above (dff_score against GUARD x the reference's float32 distance) and, inside the Langevin instantiations -- another MODE, the
 layer-0 table, the stash reloads, the pre-drawn noise -- by tests/test_langevin_update.py: v_out, ke and the Brownian frames of
 every kernel variant against the float64 oracle at bars that a lost tenth of the force misses by a factor of 40 and more.
+
+What a reverse-chain comparison at STEP_TOL x K sees.  A reverse step applies the network's eps with the factor c1 sqrt_recipm1
+= 3 - 6e-3 at ordinary levels (0.24 at level 991, 1.5 at 998, 31.6 at 999), and the synthetic conservative networks give |eps| of
+about 3e-2.  The oracle (float64, the weights of variants.MODELS, three samples x ~ N(0, 1), supplied noise) against ITSELF WITH
+THE NETWORK OUTPUT TIMES 0.9, compared as the tests compare the kernel with it (re-measured with the oracle of
+tests/test_ddpm_update.py); difference / bar:
+    model        t = 7 .. 0   500 .. 497   100 .. 97   999 alone
+    chignolin    1.07         1.12         0.80        231
+    ala2         0.81         0.99         0.63        243
+    trp_cage     1.01         1.03         0.75        271
+A reverse step that lost a tenth of its model term passes a chain comparison here unless the chain touches level 999; so does one
+that read a neighbour's row on a kernel variant the goldens do not select.  The model term inside the DDPM instantiations -- a
+branch of its own in each kernel, sharing no code with the Langevin update -- is held by tests/test_ddpm_update.py: every kernel
+variant against the float64 oracle over levels 996 .. 991 and 3 .. 0, at bars that a lost tenth of eps misses by a factor of 40
+and more, the fused loop against chained single levels bit for bit, and the clamp at level 999.
 """
 import os
 

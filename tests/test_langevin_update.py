@@ -45,7 +45,7 @@ import torch
 from oracle import reference_twin as twin
 from oracle import synth
 from support import EPS, GUARD_FP32, M_DRAW, e32_of, guard_for
-from variants import CASES, MODELS, get_native, params
+from variants import CASES, MODELS, get_native, params, subset as _subset
 
 gpu = pytest.mark.gpu
 case_param = pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
@@ -87,24 +87,6 @@ def _inputs(model, B, K):
     v0 = 0.5 * synth.normal((B, N, 3), wseed + 101, 3)
     nz = synth.normal((B, K, N, 3), wseed + 101, 4).transpose(1, 0, 2, 3)
     return x0.astype(np.float32), v0.astype(np.float32), np.ascontiguousarray(nz, np.float32)
-
-
-def _subset(case):
-    """First and last trajectory, both sides of every launch boundary (max_wgs G), and both sides of the group boundary
-    nearest the middle of the batch (which serves as the trajectory in the middle); the middle one of a one-group batch."""
-    B, G = case.B, case.group if case.group else 1
-    idx = {0, B - 1}
-    for b in range(case.max_wgs * G, B, case.max_wgs * G):
-        idx |= {b - 1, b}
-    n_groups = -(-B // G)
-    if n_groups > 1:
-        k = G * min(max(int(round(B / 2 / G)), 1), n_groups - 1)
-        idx |= {k - 1, k}
-    else:
-        idx.add(B // 2)
-    idx = tuple(sorted(idx))
-    assert len(idx) <= (4 if case.N >= 35 else 8), (case.id, idx)
-    return idx
 
 
 _oracle_cache = {}

@@ -1,5 +1,5 @@
 """The kernel-variant matrix the GPU tests of the sampler updates share (a helper, not a test): the synthetic models, one
-live native model per name, and CASES -- every kernel variant that runs an update (both kernels, 4 and 8 waves, groups with
+live native model per name, the subset of a batch the oracles run on, and CASES -- every kernel variant that runs an update (both kernels, 4 and 8 waves, groups with
 a ragged tail, batches cut into three launches, one and two workgroups per protein, the general-input branch, the force
 head, hidden 256), each with the knobs that select it and the assertion that it is the kernel that ran."""
 import contextlib
@@ -76,6 +76,25 @@ class Case:
         if self.last_grid is not None:
             assert grid == self.last_grid, (self.id, grid)
         return name
+
+
+def subset(case):
+    """The trajectories of a case's batch an oracle runs on: first and last, both sides of every launch boundary (max_wgs G),
+    and both sides of the group boundary nearest the middle of the batch (which serves as the trajectory in the middle); the
+    middle one of a one-group batch."""
+    B, G = case.B, case.group if case.group else 1
+    idx = {0, B - 1}
+    for b in range(case.max_wgs * G, B, case.max_wgs * G):
+        idx |= {b - 1, b}
+    n_groups = -(-B // G)
+    if n_groups > 1:
+        k = G * min(max(int(round(B / 2 / G)), 1), n_groups - 1)
+        idx |= {k - 1, k}
+    else:
+        idx.add(B // 2)
+    idx = tuple(sorted(idx))
+    assert len(idx) <= (4 if case.N >= 35 else 8), (case.id, idx)
+    return idx
 
 
 S16, S64 = "dff_small_kernel<", "dff_fused_kernel<"
