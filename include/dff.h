@@ -498,6 +498,57 @@ int dff_gromos_steps(int device, const uint64_t* adj_dev, long long n, int resta
                      int* labels_dev, int* centers_dev, int* sizes_dev, int* progress_dev, void* workspace_dev,
                      size_t workspace_bytes, void* stream);
 
+/* ---- folding kinetics from an order parameter: native contacts per frame, core states along trajectories, runs of equal
+ * labels (csrc/dff_kinetics.hip) ----
+ * The reference looks at per-trajectory RMSD and contact dynamics (RmsdEvaluator.eval(save_dynamics=True),
+ * _plot_rmsd_dynamics, _eval_bce_dynamics; evaluate/evaluators.py) and stops at plots; these calls turn such a series into
+ * states, dwell runs and rates (the reductions over the runs stay on the host: evaluate.py, dwell_summary).
+ * Stateless like the calls above: device pointers, enqueued on `stream` only, no read-back and no synchronisation on the
+ * launch path; bad arguments are refused on the host before any device call; n == 0 is a valid no-op; bit-identical from
+ * call to call; no floating-point atomics; no workgroup waits on another (the phases of a scan are separate launches).
+ * Trajectories are passed as dff_transition_counts takes them: n_traj trajectories back to back, lengths_host[i] frames
+ * each (sum = n), any n_traj; an empty trajectory holds no frame.
+ *
+ * The soft fraction of native contacts of Best, Hummer & Eaton (2013):
+ *   q_dev[s] = (1 / P) sum_p 1 / (1 + exp(beta (r_p(s) - lambda r0_p))),   r_p(s) = |x_i - x_j| of pair p = (i_p, j_p) in frame s.
+ * pairs_dev (P, 2) int32 and r0_dev (P) fp32 (Angstrom) on the device, P = n_pairs.  Everything in fp64 from the fp32
+ * coordinates, the sum over the pairs in list order, rounded to fp32 once: a frame's value does not depend on what else is
+ * in the call, or on how frames are split over workgroups or calls.  4 <= n_beads <= 64, 1 <= n_pairs <= N (N - 1) / 2,
+ * beta and lambda finite and > 0.
+ * A frame with a non-finite coordinate gets NaN.  The pair list is not read back: an index outside 0 .. N - 1, or i == j, is
+ * detected on the device and EVERY frame then gets NaN; nothing is ever read out of bounds.  Huge finite coordinates give
+ * 0, not NaN (exp overflows to +inf, 1 / (1 + inf) = 0). */
+int dff_struct_native_q(int device, const float* x_dev, long long n, int n_beads, const int32_t* pairs_dev,
+                        const float* r0_dev, int n_pairs, double beta, double lambda, float* q_dev, void* stream);
+/* Bytes of device workspace dff_core_states and dff_label_runs need for n frames (one 16-byte carry per 2048 frames); -1
+ * on bad arguments. */
+long long dff_kinetics_workspace_bytes(long long n);
+/* Dual-cutoff (core-set, "transition-based") state of every frame of the series cv_dev (n) fp32.  Per trajectory, in frame
+ * order, with state = -1 at the trajectory's first frame:
+ *   cv non-finite (NaN, +-inf)  -> state = -1: the history is reset, and the frame's label is -1;
+ *   cv <= lo -> state = 0;   cv >= hi -> state = 1 (equality counts as inside the core);   otherwise the state is unchanged;
+ *   labels_dev[t] = state.
+ * A frame belongs to the last core it visited, so recrossings of a single threshold are no transitions; nothing leaks
+ * across a trajectory boundary.  core_dev (n) int8, may be NULL: 0 / 1 for a frame inside a core, -1 otherwise.
+ * lo < hi, both finite.  An inclusive maximum scan over integer keys (block scan, carry scan, apply: three launches per
+ * group of up to 64 unequal, or any number of equal-length, trajectories): exact.
+ * workspace_dev: >= dff_kinetics_workspace_bytes(n) bytes, 8-byte aligned, contents irrelevant. */
+int dff_core_states(int device, const float* cv_dev, long long n, const long long* lengths_host, int n_traj,
+                    float lo, float hi, int32_t* labels_dev, int8_t* core_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Run-length encoding of labels_dev (n) int32 inside trajectories: a run is a maximal stretch of consecutive frames of ONE
+ * trajectory with the same label (any int32, -1 included).  Runs come out in ascending run_start:
+ *   run_start_dev[r] its first frame, run_length_dev[r] its frames, run_label_dev[r] its label,
+ *   run_flags_dev[r] bit 0: the run begins at its trajectory's first frame, bit 1: it ends at its trajectory's last frame.
+ * n_runs_dev (1) receives the TRUE number of runs; only the first max_runs >= 0 are written, entries beyond are not
+ * touched (the run arrays may be NULL when max_runs == 0).  n == 0 writes n_runs = 0 (when n_runs_dev is given).
+ * The scan of dff_core_states with a sum next to the maximum: exact.  Also the lifetimes of the states that
+ * dff_struct_tic_assign labels.  workspace_dev: as for dff_core_states. */
+int dff_label_runs(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj,
+                   long long max_runs, long long* run_start_dev, long long* run_length_dev, int32_t* run_label_dev,
+                   uint8_t* run_flags_dev, long long* n_runs_dev,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

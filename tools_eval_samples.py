@@ -11,6 +11,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--coverage REF.pt [--rmsd-thresholds 1,2,4] [--coverage-subsample K]]
                                  [--flexibility HELDOUT.pt] [--write-aligned OUT.pt]
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
+                                 [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -37,6 +38,13 @@ otherwise on HELDOUT's mean structure.  --write-aligned OUT.pt saves the samples
 (RmsdClusterEvaluator): HELDOUT ((m, N, 3) Angstrom) is clustered under the RMSD with --cluster-cutoff (Angstrom; the
 method of `gmx cluster -method gromos`), every sample goes to the nearest cluster centre when that is within the cutoff.
 --cluster-stride K clusters every K-th frame of HELDOUT (the neighbour matrix holds at most 2^18 frames).
+
+--kinetics adds, under "kinetics", the folding kinetics of time-ordered Langevin samples (FoldingKineticsEvaluator; needs
+--folded-pdb): the fraction of native contacts Q (--kinetics-cv q, the default) or the RMSD to the folded structure (rmsd) per
+frame, dual-cutoff states with the cores cv <= LO and cv >= HI of --kinetics-cores (0.2,0.9 for Q; the RMSD has no default),
+folding and unfolding counts, rates and dwell times in units of --frame-time.  The samples split into trajectories by
+--traj-lengths / --parallel-sim as for --transitions.  With HELDOUT.pt (MD frames (m, N, 3) in time order, or a list of such
+trajectories) the same numbers for it with the suffix _ref, and the log10 rate ratios.
 """
 import argparse
 import json
@@ -125,6 +133,51 @@ def clusters(a, x):
     return res
 
 
+def cores(text):
+    """"0.2,0.9" -> (0.2, 0.9): two finite numbers, the first below the second"""
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not two comma-separated numbers: {text!r}")
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise argparse.ArgumentTypeError("the cores must be finite with LO < HI")
+    return lo, hi
+
+
+def frame_time(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not (np.isfinite(v) and v > 0):
+        raise argparse.ArgumentTypeError("the frame time must be finite and > 0")
+    return v
+
+
+def kinetics_cores(a):
+    if a.kinetics_cores is not None:
+        return a.kinetics_cores
+    if a.kinetics_cv != "q":
+        raise SystemExit("--kinetics-cv rmsd needs --kinetics-cores LO,HI (Angstrom)")
+    return 0.2, 0.9
+
+
+def kinetics(a, x):
+    lo, hi = kinetics_cores(a)
+    ref, ref_lengths = None, None
+    if a.kinetics:
+        ref = torch.load(a.kinetics, map_location="cpu")
+        if not isinstance(ref, torch.Tensor):
+            trajs = [torch.as_tensor(t).float() for t in ref]
+            ref, ref_lengths = torch.cat(trajs), [len(t) for t in trajs]
+        ref = ref.float()
+    ev = evaluate.FoldingKineticsEvaluator(a.mol.lower(), a.folded_pdb, cv=a.kinetics_cv, lo=lo, hi=hi, frame_time=a.frame_time,
+                                           ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+    res = {k: (None if not np.isfinite(v) else float(v)) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
+    res.update({"cv": a.kinetics_cv, "lo": lo, "hi": hi, "frame_time": a.frame_time})
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -165,6 +218,15 @@ def build_parser():
     ap.add_argument("--cluster-cutoff", type=cluster_cutoff, default=2.0, help="RMSD cutoff in Angstrom (with --clusters)")
     ap.add_argument("--cluster-stride", type=int, default=1, metavar="K",
                     help="cluster every K-th frame of the ensemble (with --clusters)")
+    ap.add_argument("--kinetics", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report folding / unfolding counts, rates and dwell times (time-ordered Langevin samples; needs "
+                         "--folded-pdb); with HELDOUT.pt also for that MD data")
+    ap.add_argument("--kinetics-cv", choices=("q", "rmsd"), default="q",
+                    help="order parameter: fraction of native contacts or RMSD to the folded structure (with --kinetics)")
+    ap.add_argument("--kinetics-cores", type=cores, default=None, metavar="LO,HI",
+                    help="the two cores cv <= LO and cv >= HI (with --kinetics; 0.2,0.9 for q)")
+    ap.add_argument("--frame-time", type=frame_time, default=1.0, metavar="T",
+                    help="time between two frames, the unit of the rates and dwell times (with --kinetics)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -178,6 +240,8 @@ def main():
         ap.error("--cluster-stride must be >= 1")
     if a.write_aligned and not a.folded_pdb:
         ap.error("--write-aligned needs --folded-pdb")
+    if a.kinetics is not None and not a.folded_pdb:
+        ap.error("--kinetics needs --folded-pdb")
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -205,6 +269,8 @@ def main():
         res["flexibility"] = flexibility(a, x)
     if a.clusters:
         res["clusters"] = clusters(a, x)
+    if a.kinetics is not None:
+        res["kinetics"] = kinetics(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

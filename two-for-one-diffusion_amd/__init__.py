@@ -16,6 +16,7 @@ __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_libr
            "nearest_rmsd", "rmsd_matrix", "EnsembleCoverageEvaluator"]
 __all__ += ["superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"]
 __all__ += ["cluster_rmsd", "RmsdClusterEvaluator"]
+__all__ += ["native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -35,6 +36,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("cluster_rmsd", "RmsdClusterEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

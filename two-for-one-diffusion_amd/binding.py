@@ -111,6 +111,11 @@ SYMBOLS = {
     "dff_rmsd_neighbors": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_float, _P, _P, _P]),
     "dff_gromos_workspace_bytes": (C.c_longlong, [C.c_longlong]),
     "dff_gromos_steps": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dff_struct_native_q": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P]),
+    "dff_kinetics_workspace_bytes": (C.c_longlong, [C.c_longlong]),
+    "dff_core_states": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _P]),
+    "dff_label_runs": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_longlong, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                 _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -829,3 +834,81 @@ def gromos_steps(adj, state, n_steps: int, restart=None):
                                      _ptr(state["progress"]), _ptr(ws), int(ws.numel()), _stream(adj)), "dff_gromos_steps")
     state["fresh"] = False
     return state
+
+
+# ---- folding kinetics (dff_struct_native_q, dff_core_states, dff_label_runs) ----
+def struct_native_q(x, pairs, r0, beta: float = 5.0, lam: float = 1.2):
+    """Soft fraction of native contacts of every frame of x (n, N, 3): the mean over the pairs (i, j) of `pairs` (P, 2) of
+    1 / (1 + exp(beta (r_ij - lam r0))) with the native distances r0 (P,), in float64, rounded once -> float32 CUDA tensor
+    (n,).  NaN for a frame with a non-finite coordinate -- and for EVERY frame when a pair has an index outside 0 .. N - 1
+    or i == j (detected on the device: nothing is read back)."""
+    import torch
+    lib = load_library()
+    x, n, N = _coords(x)
+    p = torch.as_tensor(pairs).to(device=x.device, dtype=torch.int32).contiguous()
+    r = torch.as_tensor(r0).to(device=x.device, dtype=torch.float32).contiguous()
+    if p.dim() != 2 or p.shape[1] != 2 or r.shape != (p.shape[0],):
+        raise ValueError("pairs must be (P, 2) and r0 (P,)")
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    _check(lib, lib.dff_struct_native_q(x.device.index, _ptr(x), n, N, _ptr(p), _ptr(r), int(p.shape[0]), float(beta),
+                                        float(lam), _ptr(out), _stream(x)), "dff_struct_native_q")
+    return out
+
+
+def kinetics_workspace_bytes(n: int) -> int:
+    return _workspace_bytes("dff_kinetics_workspace_bytes", int(n))
+
+
+def _kinetics_workspace(t, workspace):
+    import torch
+    if workspace is None:
+        workspace = torch.empty(max(kinetics_workspace_bytes(int(t.numel())), 8), dtype=torch.uint8, device=t.device)
+    return workspace, int(workspace.numel() * workspace.element_size())
+
+
+def core_states(cv, lengths, lo: float, hi: float, return_core=False, workspace=None):
+    """Dual-cutoff state of every frame of the float32 CUDA series cv (n,) -- trajectories back to back, `lengths` frames
+    each: 0 from a frame with cv <= lo on, 1 from one with cv >= hi on, -1 before the first core visit of a trajectory
+    and at a non-finite frame (which resets the history) -> int32 CUDA tensor (n,); with return_core also the int8 tensor
+    (n,) that is 0 / 1 inside a core and -1 elsewhere (dff_core_states).  `workspace` is a uint8 CUDA tensor (allocated
+    here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(cv, torch.Tensor) and cv.is_cuda and cv.dtype == torch.float32 and cv.is_contiguous()
+            and cv.dim() == 1):
+        raise ValueError("cv must be a contiguous float32 CUDA tensor of shape (n,)")
+    ln = _lengths(lengths)
+    n = int(cv.numel())
+    labels = torch.empty(n, dtype=torch.int32, device=cv.device)
+    core = torch.empty(n, dtype=torch.int8, device=cv.device) if return_core else None
+    workspace, ws_bytes = _kinetics_workspace(cv, workspace)
+    _check(lib, lib.dff_core_states(cv.device.index, _ptr(cv), n, ln.ctypes.data_as(C.c_void_p), int(ln.size), float(lo),
+                                    float(hi), _ptr(labels), _ptr(core), _ptr(workspace), ws_bytes, _stream(cv)),
+           "dff_core_states")
+    return (labels, core) if return_core else labels
+
+
+def label_runs(labels, lengths, max_runs=None, workspace=None):
+    """Runs of equal labels inside the trajectories of the int32 CUDA labels (n,) (back to back, `lengths` frames each):
+    a dict of CUDA tensors start int64, length int64, label int32, flags uint8 (bit 0: the run begins at its trajectory's
+    first frame, bit 1: it ends at its last), each (max_runs,) with the first n_runs entries written, and n_runs int64
+    (1,), the true number of runs (dff_label_runs).  max_runs defaults to n, which every run fits.  Nothing is read back."""
+    import torch
+    lib = load_library()
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
+            and labels.is_contiguous() and labels.dim() == 1):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
+    ln = _lengths(lengths)
+    n = int(labels.numel())
+    m = n if max_runs is None else int(max_runs)
+    dev = labels.device
+    out = {"start": torch.empty(max(m, 0), dtype=torch.int64, device=dev),
+           "length": torch.empty(max(m, 0), dtype=torch.int64, device=dev),
+           "label": torch.empty(max(m, 0), dtype=torch.int32, device=dev),
+           "flags": torch.empty(max(m, 0), dtype=torch.uint8, device=dev),
+           "n_runs": torch.empty(1, dtype=torch.int64, device=dev)}
+    workspace, ws_bytes = _kinetics_workspace(labels, workspace)
+    _check(lib, lib.dff_label_runs(dev.index, _ptr(labels), n, ln.ctypes.data_as(C.c_void_p), int(ln.size), m,
+                                   _ptr(out["start"]), _ptr(out["length"]), _ptr(out["label"]), _ptr(out["flags"]),
+                                   _ptr(out["n_runs"]), _ptr(workspace), ws_bytes, _stream(labels)), "dff_label_runs")
+    return out

@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 
 #include "dff_pwd.hip"
@@ -10,6 +10,7 @@
 #include "dff_ensemble.hip"
 #include "dff_superpose.hip"
 #include "dff_cluster.hip"
+#include "dff_kinetics.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -440,6 +441,37 @@ extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d
     return DFF_OK;
 }
 
+// The launches of a call over n > 0 frames of trajectories back to back (lengths already checked): launch(runs) once per
+// group of whole trajectories.  Equal lengths (what the sampler produces; empty trajectories hold no frame and are left
+// out): one group with a period; otherwise groups of up to DFF_TC_RUNS trajectories with their start table.
+template <class Launch>
+static int traj_launches(const long long* lengths, int n_traj, long long n, Launch launch) {
+    long long period = 0;
+    bool equal = true;
+    for (int i = 0; i < n_traj; ++i)
+        if (lengths[i] > 0) {
+            if (period == 0) period = lengths[i];
+            else if (lengths[i] != period) equal = false;
+        }
+    TransRuns runs = {};
+    if (equal) {
+        runs.begin = 0; runs.end = n; runs.period = period;
+        return launch(runs);
+    }
+    long long o = 0;
+    for (int i = 0; i < n_traj; o += lengths[i], ++i) {
+        if (lengths[i] == 0) continue;
+        if (runs.n == 0) runs.begin = o;
+        runs.start[runs.n++] = o;
+        runs.start[runs.n] = runs.end = o + lengths[i];
+        if (runs.n == DFF_TC_RUNS) {
+            if (int rc = launch(runs)) return rc;
+            runs.n = 0;
+        }
+    }
+    return runs.n ? launch(runs) : DFF_OK;
+}
+
 extern "C" int dff_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
                                      const int32_t* lags, int n_lags, int K, uint64_t* counts, void* stream_) {
     if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "transition_counts: null labels / negative count");
@@ -455,16 +487,8 @@ extern "C" int dff_transition_counts(int device, const int32_t* labels, long lon
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipMemsetAsync(counts, 0, (size_t)n_lags * K * K * sizeof(uint64_t), stream));
     if (n == 0) return DFF_OK;
-    // equal lengths (what the sampler produces; empty trajectories hold no frame and are left out): one launch per lag group
-    long long period = 0;
-    bool equal = true;
-    for (int i = 0; i < n_traj; ++i)
-        if (lengths[i] > 0) {
-            if (period == 0) period = lengths[i];
-            else if (lengths[i] != period) equal = false;
-        }
     const int per_group = DFF_TC_LDS_COUNTERS / (K * K) < n_lags ? DFF_TC_LDS_COUNTERS / (K * K) : n_lags;   // >= 2
-    auto launch = [&](const TransRuns& runs) -> int {
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
         const long long wgs = (runs.end - runs.begin + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
         for (int l0 = 0; l0 < n_lags; l0 += per_group) {
             TransLags g;
@@ -476,24 +500,7 @@ extern "C" int dff_transition_counts(int device, const int32_t* labels, long lon
             HIPCHK(hipGetLastError());
         }
         return DFF_OK;
-    };
-    TransRuns runs = {};
-    if (equal) {
-        runs.begin = 0; runs.end = n; runs.period = period;
-        return launch(runs);
-    }
-    long long o = 0;
-    for (int i = 0; i < n_traj; o += lengths[i], ++i) {
-        if (lengths[i] == 0) continue;
-        if (runs.n == 0) runs.begin = o;
-        runs.start[runs.n++] = o;
-        runs.start[runs.n] = runs.end = o + lengths[i];
-        if (runs.n == DFF_TC_RUNS) {
-            if ((rc = launch(runs))) return rc;
-            runs.n = 0;
-        }
-    }
-    return runs.n ? launch(runs) : DFF_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -703,4 +710,115 @@ extern "C" int dff_gromos_steps(int device, const uint64_t* adj, long long n, in
     }
     HIPCHK(hipGetLastError());
     return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Folding kinetics: native contacts per frame, core states, runs of labels (dff_kinetics.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dff_struct_native_q(int device, const float* x, long long n, int N, const int32_t* pairs, const float* r0,
+                                   int n_pairs, double beta, double lambda, float* q, void* stream_) {
+    int rc = struct_check(x, n, N, q, "struct_native_q");
+    if (rc) return rc;
+    if (n_pairs < 1 || n_pairs > N * (N - 1) / 2)
+        return fail(DFF_EINVAL, "struct_native_q: n_pairs must be 1..%d for %d beads", N * (N - 1) / 2, N);
+    if (!(beta > 0.0) || !(beta <= 1.7976931348623157e308))
+        return fail(DFF_EINVAL, "struct_native_q: beta must be finite and > 0");
+    if (!(lambda > 0.0) || !(lambda <= 1.7976931348623157e308))
+        return fail(DFF_EINVAL, "struct_native_q: lambda must be finite and > 0");
+    if (n == 0) return DFF_OK;
+    if (!pairs || !r0) return fail(DFF_EINVAL, "struct_native_q: null pair list / native distances");
+    ON_DEVICE(device);
+    const unsigned lds = (unsigned)(native_q_r0_floats(n_pairs) * sizeof(float)) + struct_tile_bytes(N) +
+                         (unsigned)(((n_pairs + 7) & ~7) * sizeof(unsigned short));
+    if (lds > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void*)&dff_struct_native_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    // every workgroup copies and checks the pair list: fewer, longer workgroups than the other metrics
+    return struct_launch(dff_struct_native_q_kernel, 2048, lds, stream_, x, n, N, pairs, r0, n_pairs, beta, lambda, q);
+}
+
+static long long kin_blocks(long long n) { return (n + DFF_KIN_BLOCK - 1) / DFF_KIN_BLOCK; }
+
+static int kin_check_frames(long long n, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (kin_blocks(n) > 0x7fffffffLL) return fail(DFF_EINVAL, "%s: too many frames", what);
+    return DFF_OK;
+}
+
+extern "C" long long dff_kinetics_workspace_bytes(long long n) {
+    if (kin_check_frames(n, "kinetics_workspace_bytes")) return -1;
+    return kin_blocks(n) * (long long)sizeof(KinScan);              // one carry per DFF_KIN_BLOCK frames
+}
+
+static int kin_check_workspace(const void* workspace, size_t workspace_bytes, long long n, const char* what) {
+    if (int rc = check_workspace(workspace, workspace_bytes, dff_kinetics_workspace_bytes(n), what)) return rc;
+    if (n > 0 && (uintptr_t)workspace % sizeof(long long))
+        return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    return DFF_OK;
+}
+
+// The three launches of one scan over the frames of `runs`: reduce -> carry -> apply(blocks).  count / first: the run count
+// carried over the launches of a call (dff_kin_carry_kernel).
+template <class Src, class Apply>
+static int kin_scan(hipStream_t stream, Src src, const TransRuns& runs, KinScan* carry, long long* count, int first,
+                    Apply apply) {
+    const unsigned nb = (unsigned)kin_blocks(runs.end - runs.begin);
+    hipLaunchKernelGGL(dff_kin_reduce_kernel<Src>, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, carry);
+    hipLaunchKernelGGL(dff_kin_carry_kernel, dim3(1), dim3(DFF_KIN_THREADS), 0, stream, carry, (long long)nb, count, first);
+    apply(nb);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_core_states(int device, const float* cv, long long n, const long long* lengths, int n_traj, float lo,
+                               float hi, int32_t* labels, int8_t* core, void* workspace, size_t workspace_bytes,
+                               void* stream_) {
+    int rc = kin_check_frames(n, "core_states");
+    if (rc) return rc;
+    if (!(fabsf(lo) <= 3.402823466e38f) || !(fabsf(hi) <= 3.402823466e38f))
+        return fail(DFF_EINVAL, "core_states: lo and hi must be finite");
+    if (!(lo < hi)) return fail(DFF_EINVAL, "core_states: lo must be < hi");
+    if ((rc = traj_check_lengths(lengths, n_traj, n, "core_states"))) return rc;
+    if (n == 0) return DFF_OK;
+    if (!cv || !labels) return fail(DFF_EINVAL, "core_states: null cv / labels");
+    if ((rc = kin_check_workspace(workspace, workspace_bytes, n, "core_states"))) return rc;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const KinCore src = {cv, lo, hi};
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        return kin_scan(stream, src, runs, (KinScan*)workspace, nullptr, 1, [&](unsigned nb) {
+            hipLaunchKernelGGL(dff_kin_core_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
+                               (const KinScan*)workspace, labels, (signed char*)core);
+        });
+    });
+}
+
+extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
+                              long long max_runs, long long* run_start, long long* run_length, int32_t* run_label,
+                              uint8_t* run_flags, long long* n_runs, void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = kin_check_frames(n, "label_runs");
+    if (rc) return rc;
+    if (max_runs < 0) return fail(DFF_EINVAL, "label_runs: negative max_runs");
+    if ((rc = traj_check_lengths(lengths, n_traj, n, "label_runs"))) return rc;
+    if (n > 0 && (!labels || !n_runs)) return fail(DFF_EINVAL, "label_runs: null labels / n_runs");
+    if (n > 0 && max_runs > 0 && (!run_start || !run_length || !run_label || !run_flags))
+        return fail(DFF_EINVAL, "label_runs: null run output");
+    if ((rc = kin_check_workspace(workspace, workspace_bytes, n, "label_runs"))) return rc;
+    if (n == 0 && !n_runs) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(n_runs, 0, sizeof(long long), stream));
+        return DFF_OK;
+    }
+    const KinRuns src = {labels};
+    int first = 1;
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        const int rc = kin_scan(stream, src, runs, (KinScan*)workspace, n_runs, first, [&](unsigned nb) {
+            hipLaunchKernelGGL(dff_kin_runs_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
+                               (const KinScan*)workspace, max_runs, run_start, run_length, run_label, run_flags);
+        });
+        first = 0;
+        return rc;
+    });
 }

@@ -1407,3 +1407,222 @@ class RmsdClusterEvaluator:
         n_ref = len(self.refs) - self.refs_nonfinite
         return self.summarize(self.clusters.sizes, n_ref, lab[lab >= -1], self.min_size, int((lab == -2).sum()),
                               self.refs_nonfinite)
+
+
+# =====================================================================================================
+# Folding kinetics from an order parameter: the fraction of native contacts Q (or the RMSD to the folded structure) per
+# frame, dual-cutoff core states along each trajectory, dwell runs and censoring-aware rates (dff_struct_native_q,
+# dff_core_states, dff_label_runs; csrc/dff_kinetics.hip).  The reference looks at per-trajectory RMSD and contact dynamics
+# (RmsdEvaluator.eval(save_dynamics=True), _plot_rmsd_dynamics, _eval_bce_dynamics) and stops at plots.
+# =====================================================================================================
+def native_pairs(folded, cutoff=10.0, offset=3):
+    """The native contacts of the folded structure (N, 3) in Angstrom: the pairs j >= i + offset whose folded distance
+    (float32, as ContactEvaluator computes it) is < cutoff -- the defaults are ContactEvaluator's (contact_cutoff 10,
+    offset 3) -> (pairs int32 (P, 2) in triu order, r0 float32 (P,)).  Validated on the host."""
+    f = np.asarray(torch.as_tensor(folded).cpu(), np.float64)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("native_pairs: the folded structure must be (n_beads, 3)")
+    N = len(f)
+    if not 4 <= N <= binding.DFF_MAX_BEADS:
+        raise ValueError(f"native_pairs: n_beads must be 4..{binding.DFF_MAX_BEADS}")
+    if not np.all(np.isfinite(f)):
+        raise ValueError("native_pairs: the folded structure has a non-finite coordinate")
+    if not (np.isfinite(cutoff) and cutoff > 0):
+        raise ValueError("native_pairs: cutoff must be finite and > 0")
+    if int(offset) != offset or not 1 <= offset < N:
+        raise ValueError(f"native_pairs: offset must be an integer in 1..{N - 1}")
+    f32 = torch.from_numpy(f).float()
+    d = torch.norm(f32[:, None, :] - f32[None, :, :], dim=-1).numpy()
+    i, j = np.triu_indices(N, int(offset))
+    keep = d[i, j] < cutoff
+    if not keep.any():
+        raise ValueError(f"native_pairs: no pair at offset {offset} is closer than {cutoff} A in the folded structure")
+    return np.stack([i[keep], j[keep]], 1).astype(np.int32), d[i, j][keep].astype(np.float32)
+
+
+def native_contacts_q(xyz, folded, *, cutoff=10.0, offset=3, beta=5.0, lam=1.2, device="cuda:0"):
+    """Soft fraction of native contacts of every structure of xyz (n, N, 3) in Angstrom, Q = mean over the native pairs
+    (native_pairs(folded, cutoff, offset)) of 1 / (1 + exp(beta (r - lam r0))): the form of Best, Hummer & Eaton (2013),
+    float64 arithmetic, -> float32 tensor (n,) on `device`; NaN for a frame with a non-finite coordinate.
+    beta = 5 / A and lam = 1.2 are THIS PROJECT'S choice for C-alpha beads (Best et al. use 5 / A and 1.8 for all heavy
+    atoms at a 4.5 A cutoff); the reference has no soft Q, only the hard contact map of ContactEvaluator."""
+    pairs, r0 = native_pairs(folded, cutoff, offset)
+    x = _frames(xyz, torch.device(device))
+    if x.shape[1] != len(folded):
+        raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(folded)}")
+    return binding.struct_native_q(x, pairs, r0, beta, lam)
+
+
+def _check_cores(lo, hi, what):
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"{what}: lo and hi must be finite with lo < hi")
+    return lo, hi
+
+
+def _series(t, dtype, device):
+    t = torch.as_tensor(t)
+    if t.dim() != 1:
+        raise ValueError("a series must be (n,)")
+    dev = t.device if t.is_cuda and device is None else torch.device(device or "cuda:0")
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def core_states(cv, lo, hi, traj_lengths=None, *, device=None):
+    """Dual-cutoff (core-set, "transition-based") states of the series cv (n,): per trajectory, a frame is in state 0 from
+    a frame with cv <= lo on and in state 1 from one with cv >= hi on, and keeps the last state in between; -1 before a
+    trajectory's first core visit and at a non-finite frame, which resets the history -> int32 tensor (n,) on the device
+    (cv's, when it is a CUDA tensor).  traj_lengths=None: one trajectory."""
+    lo, hi = _check_cores(lo, hi, "core_states")
+    c = _series(cv, torch.float32, device)
+    return binding.core_states(c, _check_lengths(traj_lengths, len(c)), lo, hi)
+
+
+def label_runs(labels, traj_lengths=None, *, device=None):
+    """The runs of equal labels inside the trajectories of labels (n,) -> a dict of numpy arrays over the runs in time
+    order: start int64, length int64, label int32, flags uint8 (bit 0: the run begins at its trajectory's first frame,
+    bit 1: it ends at its trajectory's last frame).  traj_lengths=None: one trajectory."""
+    lab = _series(labels, torch.int32, device)
+    res = binding.label_runs(lab, _check_lengths(traj_lengths, len(lab)))
+    k = int(res["n_runs"].cpu())
+    return {key: res[key][:k].cpu().numpy() for key in ("start", "length", "label", "flags")}
+
+
+def dwell_summary(runs, frame_time=1.0):
+    """Dwell statistics from the runs of label_runs: numpy only.  For the labels a >= 0 (a negative label is "undetermined"):
+      frames[a]          frames spent in a (every run of a, censored ones included)
+      events[(a, b)]     runs of a followed, in the same trajectory, by a run of b >= 0 (b != a); a run of a negative label
+                         in between breaks the event
+      rates[(a, b)]      events / (frames[a] * frame_time): the maximum-likelihood rate under censoring -- a trajectory's
+                         first and last dwells add time but no event; NaN when the time is 0
+      mean_dwell[a], median_dwell[a], n_completed[a]   over the COMPLETED dwells of a, those that start with an entry event
+                         and end with an exit event, in units of frame_time; NaN without one
+    and total_frames, undetermined_frames.  `labels` lists the a >= 0 that occur, ascending."""
+    lab = np.asarray(runs["label"], np.int64).reshape(-1)
+    length = np.asarray(runs["length"], np.int64).reshape(-1)
+    flags = np.asarray(runs["flags"], np.int64).reshape(-1)
+    if not (len(lab) == len(length) == len(flags)):
+        raise ValueError("dwell_summary: label, length and flags must have one entry per run")
+    if not (np.isfinite(frame_time) and frame_time > 0):
+        raise ValueError("dwell_summary: frame_time must be finite and > 0")
+    states = sorted(int(a) for a in np.unique(lab[lab >= 0]))
+    # run k and run k + 1 lie in one trajectory when run k does not end its trajectory; an event needs both labels >= 0
+    joined = np.zeros(len(lab), bool)
+    if len(lab) > 1:
+        joined[:-1] = ((flags[:-1] & 2) == 0) & (lab[:-1] >= 0) & (lab[1:] >= 0)
+    exits = joined                                           # run k ends with an exit event
+    enters = np.concatenate([[False], joined[:-1]])         # run k starts with an entry event
+    frames = {a: int(length[lab == a].sum()) for a in states}
+    events = {(a, b): int((exits[:-1] & (lab[:-1] == a) & (lab[1:] == b)).sum()) if len(lab) > 1 else 0
+              for a in states for b in states if a != b}
+    nan = float("nan")
+    rates = {ab: (n / (frames[ab[0]] * frame_time) if frames[ab[0]] > 0 else nan) for ab, n in events.items()}
+    mean, median, n_completed = {}, {}, {}
+    for a in states:
+        done = length[(lab == a) & exits & enters]
+        n_completed[a] = int(len(done))
+        mean[a] = float(done.mean() * frame_time) if len(done) else nan
+        median[a] = float(np.median(done) * frame_time) if len(done) else nan
+    return {"labels": states, "frames": frames, "events": events, "rates": rates, "mean_dwell": mean, "median_dwell": median,
+            "n_completed": n_completed, "total_frames": int(length.sum()), "undetermined_frames": int(length[lab < 0].sum())}
+
+
+class FoldingKineticsEvaluator:
+    """How often does a trajectory fold and unfold, and how long does it stay: the order-parameter route of the fast-folder
+    literature on the GPU.  Frames -> order parameter (cv="q": the soft fraction of native contacts of native_contacts_q;
+    cv="rmsd": the RMSD to the folded structure, dff_struct_rmsd) -> dual-cutoff core states with the cores cv <= lo and
+    cv >= hi (core_states) -> runs (label_runs) -> dwell_summary.  Folded is label 1 for Q (Q >= hi) and label 0 for the RMSD
+    (rmsd <= lo).  `folded` is a PDB path or the folded C-alpha coordinates (N, 3) in Angstrom; frame_time is the time
+    between two frames, in the unit the rates and dwell times are wanted in.
+
+    eval(xyz, traj_lengths=None) -- None: the frames are ONE trajectory, as for StateTransitionEvaluator -- returns a plain
+    dict of floats:
+      folded_share, unfolded_share, undetermined_share   shares of ALL frames (undetermined: label -1)
+      n_folding, n_unfolding                              events unfolded -> folded and folded -> unfolded
+      rate_folding, rate_unfolding                        events / time spent in the state left (dwell_summary's rates)
+      mean_dwell_folded, mean_dwell_unfolded, median_dwell_folded, median_dwell_unfolded   over completed dwells
+      free_energy_folding_kT                              -ln(folded_share / unfolded_share); NaN when a share is 0
+      samples_nonfinite                                   frames with a non-finite coordinate (label -1, history reset)
+    With ref_data (MD frames (m, N, 3), trajectories of ref_traj_lengths) the same keys with the suffix _ref, and
+    log10_rate_ratio_folding, log10_rate_ratio_unfolding (samples over reference; NaN unless both rates are positive) and
+    folded_share_diff.  The series stay on .series: {"samples" / "refs": {"cv", "labels", "runs", "summary"}}.
+    Without the HIP library: DffLibraryError."""
+
+    KEYS = ("folded_share", "unfolded_share", "undetermined_share", "n_folding", "n_unfolding", "rate_folding",
+            "rate_unfolding", "mean_dwell_folded", "mean_dwell_unfolded", "median_dwell_folded", "median_dwell_unfolded",
+            "free_energy_folding_kT", "samples_nonfinite")
+
+    def __init__(self, mol_name, folded, *, cv="q", lo, hi, frame_time=1.0, ref_data=None, ref_traj_lengths=None,
+                 cutoff=10.0, offset=3, beta=5.0, lam=1.2, device="cuda:0"):
+        if cv not in ("q", "rmsd"):
+            raise ValueError("FoldingKineticsEvaluator: cv must be 'q' or 'rmsd'")
+        self.lo, self.hi = _check_cores(lo, hi, "FoldingKineticsEvaluator")
+        self.frame_time = float(frame_time)
+        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
+            raise ValueError("FoldingKineticsEvaluator: frame_time must be finite and > 0")
+        self.mol_name, self.cv = mol_name, cv
+        self.device = torch.device(device)
+        self.folded = _folded_coords(folded, mol_name)
+        self.beta, self.lam = float(beta), float(lam)
+        if cv == "q":
+            if not (np.isfinite(self.beta) and self.beta > 0 and np.isfinite(self.lam) and self.lam > 0):
+                raise ValueError("FoldingKineticsEvaluator: beta and lam must be finite and > 0")
+            self.pairs, self.r0 = native_pairs(self.folded, cutoff, offset)
+        self.folded_label, self.unfolded_label = (1, 0) if cv == "q" else (0, 1)
+        binding.load_library()
+        self.series = {}
+        self.ref_result = None
+        if ref_data is not None:
+            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+                ref_data = ref_data[:][0]
+            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+
+    def order_parameter(self, x):
+        """float32 tensor (n,) on the device: Q or the RMSD of the frames x (n, N, 3) already there"""
+        if x.shape[1] != len(self.folded):
+            raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(self.folded)}")
+        if self.cv == "q":
+            return binding.struct_native_q(x, self.pairs, self.r0, self.beta, self.lam)
+        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float())
+
+    @staticmethod
+    def summarize(summary, folded_label, unfolded_label, samples_nonfinite=0):
+        """eval()'s dict from a dwell_summary: numpy only."""
+        nan = float("nan")
+        F, U = folded_label, unfolded_label
+        n = summary["total_frames"]
+        nf, nu = summary["frames"].get(F, 0), summary["frames"].get(U, 0)
+        share = lambda k: k / n if n else nan     # noqa: E731
+        res = {"folded_share": share(nf), "unfolded_share": share(nu), "undetermined_share": share(n - nf - nu),
+               "n_folding": float(summary["events"].get((U, F), 0)), "n_unfolding": float(summary["events"].get((F, U), 0)),
+               "rate_folding": summary["rates"].get((U, F), nan), "rate_unfolding": summary["rates"].get((F, U), nan)}
+        for name, a in (("folded", F), ("unfolded", U)):
+            res[f"mean_dwell_{name}"] = summary["mean_dwell"].get(a, nan)
+            res[f"median_dwell_{name}"] = summary["median_dwell"].get(a, nan)
+        res["free_energy_folding_kT"] = float(-np.log(nf / nu)) if nf > 0 and nu > 0 else nan
+        res["samples_nonfinite"] = float(samples_nonfinite)
+        return res
+
+    def _analyse(self, xyz, traj_lengths, name):
+        x = _frames(xyz, self.device)
+        lengths = _check_lengths(traj_lengths, len(x))
+        cv = self.order_parameter(x)
+        labels = binding.core_states(cv, lengths, self.lo, self.hi)
+        runs = label_runs(labels, lengths)
+        summary = dwell_summary(runs, self.frame_time)
+        self.series[name] = {"cv": cv.cpu().numpy(), "labels": labels.cpu().numpy(), "runs": runs, "summary": summary}
+        return self.summarize(summary, self.folded_label, self.unfolded_label, _count_nonfinite(x))
+
+    def eval(self, xyz, traj_lengths=None, plot_dynamics=False):
+        if plot_dynamics:
+            raise NotImplementedError("plotting (evaluators.py: _plot_rmsd_dynamics) is outside the hot path")
+        res = self._analyse(xyz, traj_lengths, "samples")
+        if self.ref_result is not None:
+            ref = self.ref_result
+            res.update({k + "_ref": v for k, v in ref.items()})
+            for which in ("folding", "unfolding"):
+                a, b = res[f"rate_{which}"], ref[f"rate_{which}"]
+                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
+                res[f"log10_rate_ratio_{which}"] = float(np.log10(a / b)) if ok else float("nan")
+            res["folded_share_diff"] = res["folded_share"] - ref["folded_share"]
+        return res
