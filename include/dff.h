@@ -549,6 +549,37 @@ int dff_label_runs(int device, const int32_t* labels_dev, long long n, const lon
                    uint8_t* run_flags_dev, long long* n_runs_dev,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- lagged products inside trajectories: the sums behind the autocorrelation function of an observable, its integrated
+ * autocorrelation time and the effective sample size (csrc/dff_autocorr.hip) ----
+ * The reference reports point estimates from its trajectories and no uncertainty; these sums give the relaxation time of a
+ * scalar or few-component observable (Q, the RMSD to the folded structure, the leading TICs) without a state definition,
+ * and n_eff = n / (2 tau_int) for the error bar of every mean (evaluate.py: autocorrelation, RelaxationEvaluator).
+ * Stateless like the calls above: device pointers, enqueued on `stream` only, no read-back and no synchronisation on the
+ * launch path; bad arguments are refused on the host before any device call; bit-identical from call to call and
+ * independent of the workspace's prior contents; no floating-point atomics -- per-workgroup partials in the workspace are
+ * added in a fixed order by a second stage; no workgroup waits on another.
+ * Trajectories are passed as dff_transition_counts takes them: n_traj trajectories back to back, lengths_host[i] frames
+ * each (sum = n), any n_traj; an empty trajectory holds no frame.
+ *
+ * series_dev (n, d) fp64 row-major, 1 <= d <= 8; 0 <= max_lag <= 65535; shift_dev (d) fp64, finite, NULL = 0.
+ *   g_t = series[t] - shift, in fp64.  A frame is USABLE when all its d components are finite.
+ *   P_l = { t : t and t + l lie in the same trajectory and both frames are usable },   l = 0 .. max_lag.
+ * The call overwrites, each sum over t in P_l and in fp64:
+ *   count_dev[l] = |P_l|          sx_dev[l, c] = sum g_{t,c}          sy_dev[l, c] = sum g_{t+l,c}
+ *   sxy_dev[l, c] = sum g_{t,c} g_{t+l,c}
+ * sxy_dev, sx_dev, sy_dev are (max_lag + 1, d) fp64, count_dev (max_lag + 1) uint64; a lag that no trajectory reaches gets
+ * zeros.  sx_dev, sy_dev and count_dev may each be NULL (with all three NULL only the products are formed); sxy_dev may
+ * not.  n == 0 is a valid no-op that zeroes the outputs.  Cross-correlations between components are not computed.
+ * Work: sum_l |P_l| <= n (max_lag + 1) pairs, four fp64 FMAs per pair and component (one without sx, sy and count).
+ * workspace_dev: >= the bytes the workspace call below gives, 8-byte aligned, contents irrelevant: 4 n bytes (the frames
+ * left in each frame's trajectory) plus the partials, which do not grow with n (at most ~2048 workgroups' worth: under 64 MB
+ * for any d and max_lag; 30 MB at n = 10^6, d = 2, max_lag = 4096). */
+/* Bytes of device workspace the call below needs (0 at n == 0); -1 on bad arguments. */
+long long dff_autocorr_workspace_bytes(long long n, int d, int max_lag);
+int dff_autocorr(int device, const double* series_dev, long long n, int d, const long long* lengths_host, int n_traj,
+                 int max_lag, const double* shift_dev, double* sxy_dev, double* sx_dev, double* sy_dev,
+                 uint64_t* count_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -12,6 +12,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--flexibility HELDOUT.pt] [--write-aligned OUT.pt]
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
                                  [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
+                                 [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -45,6 +46,13 @@ frame, dual-cutoff states with the cores cv <= LO and cv >= HI of --kinetics-cor
 folding and unfolding counts, rates and dwell times in units of --frame-time.  The samples split into trajectories by
 --traj-lengths / --parallel-sim as for --transitions.  With HELDOUT.pt (MD frames (m, N, 3) in time order, or a list of such
 trajectories) the same numbers for it with the suffix _ref, and the log10 rate ratios.
+
+--relaxation adds, under "relaxation", how fast an observable decorrelates along time-ordered Langevin samples and how many
+independent samples they hold (RelaxationEvaluator): the autocorrelation function of Q (--relaxation-cv q, the default), of
+the RMSD to the folded structure (rmsd; both need --folded-pdb) or of the components of MOL's TICA model (tic) for the lags
+0 .. --max-lag, inside the trajectories of --traj-lengths / --parallel-sim; its integrated autocorrelation time and 1 / e time
+in units of --frame-time, the effective sample size and the standard error of the mean.  With HELDOUT.pt (as for --kinetics)
+the same numbers for it with the suffix _ref, and log10_tau_int_ratio.
 """
 import argparse
 import json
@@ -178,6 +186,46 @@ def kinetics(a, x):
     return res
 
 
+def max_lag(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 1 <= v <= 65535:
+        raise argparse.ArgumentTypeError("the largest lag must be 1..65535")
+    return v
+
+
+def relaxation_max_lag(a):
+    if a.max_lag is None:
+        raise SystemExit("--relaxation needs --max-lag L (frames)")
+    return a.max_lag
+
+
+def ordered_frames(path):
+    """(frames, trajectory lengths or None) of a .pt of MD frames in time order, or of a list of such trajectories"""
+    ref = torch.load(path, map_location="cpu")
+    if isinstance(ref, torch.Tensor):
+        return ref.float(), None
+    trajs = [torch.as_tensor(t).float() for t in ref]
+    return torch.cat(trajs), [len(t) for t in trajs]
+
+
+def relaxation(a, x):
+    L = relaxation_max_lag(a)
+    ref, ref_lengths = ordered_frames(a.relaxation) if a.relaxation else (None, None)
+    tica = None
+    if a.relaxation_cv == "tic":
+        stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
+        tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+    ev = evaluate.RelaxationEvaluator(a.mol.lower(), a.folded_pdb, cv=a.relaxation_cv, tica=tica, max_lag=L,
+                                      frame_time=a.frame_time, ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
+    res = {k: ([clean(u) for u in v] if isinstance(v, list) else clean(v)) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
+    res.update({"cv": a.relaxation_cv, "max_lag": L, "frame_time": a.frame_time})
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -226,7 +274,15 @@ def build_parser():
     ap.add_argument("--kinetics-cores", type=cores, default=None, metavar="LO,HI",
                     help="the two cores cv <= LO and cv >= HI (with --kinetics; 0.2,0.9 for q)")
     ap.add_argument("--frame-time", type=frame_time, default=1.0, metavar="T",
-                    help="time between two frames, the unit of the rates and dwell times (with --kinetics)")
+                    help="time between two frames, the unit of the rates and dwell times (with --kinetics) and of the "
+                         "relaxation times (with --relaxation)")
+    ap.add_argument("--relaxation", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report autocorrelation times, effective sample size and standard error of an observable "
+                         "(time-ordered Langevin samples; needs --max-lag); with HELDOUT.pt also for that MD data")
+    ap.add_argument("--relaxation-cv", choices=("q", "rmsd", "tic"), default="q",
+                    help="observable: fraction of native contacts, RMSD to the folded structure (both need --folded-pdb) or "
+                         "the TICs of MOL's saved TICA model (with --relaxation)")
+    ap.add_argument("--max-lag", type=max_lag, default=None, metavar="L", help="largest lag in frames (with --relaxation)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -242,6 +298,10 @@ def main():
         ap.error("--write-aligned needs --folded-pdb")
     if a.kinetics is not None and not a.folded_pdb:
         ap.error("--kinetics needs --folded-pdb")
+    if a.relaxation is not None and a.relaxation_cv != "tic" and not a.folded_pdb:
+        ap.error("--relaxation with --relaxation-cv q or rmsd needs --folded-pdb")
+    if a.relaxation is not None:
+        relaxation_max_lag(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -271,6 +331,8 @@ def main():
         res["clusters"] = clusters(a, x)
     if a.kinetics is not None:
         res["kinetics"] = kinetics(a, x)
+    if a.relaxation is not None:
+        res["relaxation"] = relaxation(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

@@ -17,6 +17,7 @@ __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_libr
 __all__ += ["superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"]
 __all__ += ["cluster_rmsd", "RmsdClusterEvaluator"]
 __all__ += ["native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator"]
+__all__ += ["autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -39,6 +40,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

@@ -116,6 +116,9 @@ SYMBOLS = {
     "dff_core_states": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "dff_label_runs": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_longlong, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                  _P]),
+    "dff_autocorr_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "dff_autocorr": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                               _P]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -911,4 +914,47 @@ def label_runs(labels, lengths, max_runs=None, workspace=None):
     _check(lib, lib.dff_label_runs(dev.index, _ptr(labels), n, ln.ctypes.data_as(C.c_void_p), int(ln.size), m,
                                    _ptr(out["start"]), _ptr(out["length"]), _ptr(out["label"]), _ptr(out["flags"]),
                                    _ptr(out["n_runs"]), _ptr(workspace), ws_bytes, _stream(labels)), "dff_label_runs")
+    return out
+
+
+# ---- lagged products inside trajectories (dff_autocorr) ----
+AUTOCORR_MAX_D = 8
+AUTOCORR_MAX_LAG = 65535
+
+
+def autocorr_workspace_bytes(n: int, d: int, max_lag: int) -> int:
+    return _workspace_bytes("dff_autocorr_workspace_bytes", int(n), int(d), int(max_lag))
+
+
+def autocorr(series, lengths, max_lag: int, shift=None, sx=True, sy=True, count=True, workspace=None):
+    """Lagged sums of the contiguous float64 CUDA series (n, d) -- trajectories back to back, `lengths` frames each -- for
+    the lags 0 .. max_lag over the pairs (t, t + l) of one trajectory whose two frames are finite, g = series - shift
+    (float64 CUDA (d,), None = 0): a dict of CUDA tensors "sxy" float64 (max_lag + 1, d) = sum g_t g_{t+l} and, as asked
+    for, "sx" = sum g_t, "sy" = sum g_{t+l} (same shape) and "count" int64 (max_lag + 1,) (dff_autocorr: deterministic).
+    Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(series, torch.Tensor) and series.is_cuda and series.dtype == torch.float64
+            and series.is_contiguous() and series.dim() == 2):
+        raise ValueError("series must be a contiguous float64 CUDA tensor of shape (n, d)")
+    n, d, L = int(series.shape[0]), int(series.shape[1]), int(max_lag)
+    if shift is not None and not (isinstance(shift, torch.Tensor) and shift.dtype == torch.float64 and shift.device == series.device
+                                  and shift.is_contiguous() and tuple(shift.shape) == (d,)):
+        raise ValueError(f"shift must be a contiguous float64 tensor ({d},) on {series.device}")
+    ln = _lengths(lengths)
+    need = autocorr_workspace_bytes(n, d, L)                    # refuses a bad d or max_lag before anything is allocated
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=series.device)
+    f64 = dict(dtype=torch.float64, device=series.device)
+    out = {"sxy": torch.empty((L + 1, d), **f64)}
+    if sx:
+        out["sx"] = torch.empty((L + 1, d), **f64)
+    if sy:
+        out["sy"] = torch.empty((L + 1, d), **f64)
+    if count:
+        out["count"] = torch.empty(L + 1, dtype=torch.int64, device=series.device)
+    _check(lib, lib.dff_autocorr(series.device.index, _ptr(series), n, d, ln.ctypes.data_as(C.c_void_p), int(ln.size), L,
+                                 _ptr(shift), _ptr(out["sxy"]), _ptr(out.get("sx")), _ptr(out.get("sy")),
+                                 _ptr(out.get("count")), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                 _stream(series)), "dff_autocorr")
     return out

@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 
 #include "dff_pwd.hip"
@@ -11,6 +11,7 @@
 #include "dff_superpose.hip"
 #include "dff_cluster.hip"
 #include "dff_kinetics.hip"
+#include "dff_autocorr.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -821,4 +822,88 @@ extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, co
         first = 0;
         return rc;
     });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Lagged products inside trajectories: the sums behind the autocorrelation function (dff_autocorr.hip)
+// ---------------------------------------------------------------------------------------------
+static int ac_check_shape(long long n, int d, int max_lag, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (d < 1 || d > DFF_AC_MAXD) return fail(DFF_EINVAL, "%s: d must be 1..%d", what, DFF_AC_MAXD);
+    if (max_lag < 0 || max_lag > DFF_AC_MAXLAG) return fail(DFF_EINVAL, "%s: max_lag must be 0..%d", what, DFF_AC_MAXLAG);
+    if ((n + DFF_AC_TILE - 1) / DFF_AC_TILE > 0x7fffffffLL) return fail(DFF_EINVAL, "%s: too many frames", what);
+    return DFF_OK;
+}
+
+// Shapes of a call over n > 0 frames, from (n, d, max_lag) alone: the grid is (slots, chunks, d), about DFF_AC_WGS
+// workgroups and never more slots than tiles; the workspace is left (n ints, rounded up to 8 bytes) | partials.
+struct AcShape {
+    int nlags, chunks, slots;
+    long long ntiles;
+    AcShape(long long n, int d, int max_lag) {
+        nlags = max_lag + 1;
+        chunks = (nlags + DFF_AC_CHUNK - 1) / DFF_AC_CHUNK;
+        ntiles = (n + DFF_AC_TILE - 1) / DFF_AC_TILE;
+        const int want = (DFF_AC_WGS + chunks * d - 1) / (chunks * d);
+        slots = ntiles < want ? (int)ntiles : want;
+    }
+    size_t left_bytes(long long n) const { return ((size_t)n * sizeof(int) + 7) & ~(size_t)7; }
+    size_t part_bytes(int d) const { return (size_t)slots * (3 * d + 1) * nlags * sizeof(double); }
+};
+
+extern "C" long long dff_autocorr_workspace_bytes(long long n, int d, int max_lag) {
+    if (ac_check_shape(n, d, max_lag, "autocorr_workspace_bytes")) return -1;
+    if (n == 0) return 0;
+    const AcShape sh(n, d, max_lag);
+    return (long long)(sh.left_bytes(n) + sh.part_bytes(d));
+}
+
+extern "C" int dff_autocorr(int device, const double* series, long long n, int d, const long long* lengths, int n_traj,
+                            int max_lag, const double* shift, double* sxy, double* sx, double* sy, uint64_t* count,
+                            void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = ac_check_shape(n, d, max_lag, "autocorr");
+    if (rc) return rc;
+    if ((rc = traj_check_lengths(lengths, n_traj, n, "autocorr"))) return rc;
+    if (!series && n > 0) return fail(DFF_EINVAL, "autocorr: null series");
+    if (!sxy) return fail(DFF_EINVAL, "autocorr: null sxy");
+    const long long need = dff_autocorr_workspace_bytes(n, d, max_lag);
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "autocorr"))) return rc;
+    if (need > 0 && (uintptr_t)workspace % sizeof(double))
+        return fail(DFF_EINVAL, "autocorr: the workspace must be 8-byte aligned");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t nlags = (size_t)max_lag + 1;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(sxy, 0, nlags * d * sizeof(double), stream));
+        if (sx) HIPCHK(hipMemsetAsync(sx, 0, nlags * d * sizeof(double), stream));
+        if (sy) HIPCHK(hipMemsetAsync(sy, 0, nlags * d * sizeof(double), stream));
+        if (count) HIPCHK(hipMemsetAsync(count, 0, nlags * sizeof(uint64_t), stream));
+        return DFF_OK;
+    }
+    const AcShape sh(n, d, max_lag);
+    int* left = (int*)workspace;
+    double* part = (double*)((char*)workspace + sh.left_bytes(n));
+    if ((rc = traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+            const long long wgs = (runs.end - runs.begin + DFF_AC_THREADS - 1) / DFF_AC_THREADS;
+            hipLaunchKernelGGL(dff_ac_left_kernel, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(DFF_AC_THREADS), 0, stream,
+                               runs, left);
+            HIPCHK(hipGetLastError());
+            return DFF_OK;
+        })))
+        return rc;
+    const bool full = sx || sy || count;
+    const int K = full ? 3 * d + 1 : d;
+    const dim3 grid((unsigned)sh.slots, (unsigned)sh.chunks, (unsigned)d);
+    if (full)
+        hipLaunchKernelGGL(dff_ac_pairs_kernel<true>, grid, dim3(DFF_AC_THREADS), 0, stream, series, n, d, max_lag, shift,
+                           (const int*)left, sh.ntiles, part);
+    else
+        hipLaunchKernelGGL(dff_ac_pairs_kernel<false>, grid, dim3(DFF_AC_THREADS), 0, stream, series, n, d, max_lag, shift,
+                           (const int*)left, sh.ntiles, part);
+    HIPCHK(hipGetLastError());
+    const long long nred = (long long)K * sh.nlags;
+    hipLaunchKernelGGL(dff_ac_reduce_kernel, dim3((unsigned)((nred + 15) / 16)), dim3(DFF_AC_THREADS), 0, stream, (const double*)part, sh.slots, d, sh.nlags, K, sxy, sx, sy,
+                       (unsigned long long*)count);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
 }

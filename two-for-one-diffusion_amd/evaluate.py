@@ -1626,3 +1626,230 @@ class FoldingKineticsEvaluator:
                 res[f"log10_rate_ratio_{which}"] = float(np.log10(a / b)) if ok else float("nan")
             res["folded_share_diff"] = res["folded_share"] - ref["folded_share"]
         return res
+
+
+# =====================================================================================================
+# Autocorrelation of trajectory observables: relaxation times without a model, effective sample sizes and standard errors
+# (dff_autocorr; csrc/dff_autocorr.hip).  The reference reports point estimates only; these are the uncertainties of the
+# means above and the first check on whether sampled dynamics relax as fast as the MD data do.
+# =====================================================================================================
+class Autocorrelation:
+    """What autocorrelation() returns, float64 numpy arrays: acf and cov (max_lag + 1, d), counts int64 (max_lag + 1,) -- the
+    usable pairs per lag --, mean and variance (d,) over the usable frames; n_usable = counts[0], estimator, max_lag."""
+
+    def __init__(self, acf, cov, counts, mean, variance, estimator):
+        self.acf, self.cov, self.counts, self.mean, self.variance = acf, cov, counts, mean, variance
+        self.estimator = estimator
+        self.max_lag = len(counts) - 1
+        self.n_usable = int(counts[0])
+
+
+AUTOCORR_ESTIMATORS = ("per_lag", "global")
+
+
+def autocorr_estimate(sxy, sx, sy, count, estimator="per_lag"):
+    """C(l) from the sums of dff_autocorr over the usable pairs of lag l (torch tensors or arrays: sxy, sx, sy (L, d),
+    count (L,)) -> float64 tensor (L, d).  "per_lag": sxy / count - (sx / count)(sy / count), the covariance of the two ends
+    of the pairs with each end's own mean.  "global": the lag-0 mean m0 = sx[0] / count[0] for both factors,
+    sxy / count - m0 (sx + sy) / count + m0^2.  A lag without a pair gives NaN."""
+    if estimator not in AUTOCORR_ESTIMATORS:
+        raise ValueError(f"estimator must be one of {AUTOCORR_ESTIMATORS}")
+    sxy, sx, sy = (torch.as_tensor(v, dtype=torch.float64) for v in (sxy, sx, sy))
+    cnt = torch.as_tensor(count).to(device=sxy.device, dtype=torch.float64)[:, None]
+    if estimator == "per_lag":
+        return sxy / cnt - (sx / cnt) * (sy / cnt)                  # 0 / 0 = NaN where count is 0
+    m0 = sx[:1] / cnt[:1]
+    return sxy / cnt - m0 * (sx + sy) / cnt + m0 * m0
+
+
+def autocorrelation(series, max_lag, traj_lengths=None, *, estimator="per_lag", device="cuda:0"):
+    """Autocorrelation function of the observable `series` ((n,) or (n, d), d <= 8; float32 or float64, torch or numpy) inside
+    the trajectories of traj_lengths (back to back; None: one trajectory) for the lags 0 .. max_lag -> Autocorrelation.
+    A frame with a non-finite component is left out together with every pair it is part of; pairs never cross a trajectory
+    boundary.  The series is converted once to contiguous float64 on the device, its mean over the usable frames is
+    computed there and subtracted inside the kernel (dff_autocorr), C(l) is formed by autocorr_estimate and
+    acf = C(l) / C(0); everything comes back in one copy.  Lags without a pair give NaN."""
+    if estimator not in AUTOCORR_ESTIMATORS:
+        raise ValueError(f"estimator must be one of {AUTOCORR_ESTIMATORS}")
+    dev = torch.device(device)
+    s = torch.as_tensor(series)
+    if s.dim() == 1:
+        s = s[:, None]
+    if s.dim() != 2 or not s.is_floating_point():
+        raise ValueError("autocorrelation: the series must be a floating-point (n,) or (n, d)")
+    n, d, L = int(s.shape[0]), int(s.shape[1]), int(max_lag)
+    if not 1 <= d <= binding.AUTOCORR_MAX_D:
+        raise ValueError(f"autocorrelation: d must be 1..{binding.AUTOCORR_MAX_D}")
+    if L != max_lag or not 0 <= L <= binding.AUTOCORR_MAX_LAG:
+        raise ValueError(f"autocorrelation: max_lag must be an integer in 0..{binding.AUTOCORR_MAX_LAG}")
+    lengths = _check_lengths(traj_lengths, n)
+    s = s.to(device=dev, dtype=torch.float64).contiguous()
+    usable = torch.isfinite(s).all(1, keepdim=True)
+    shift = (torch.where(usable, s, torch.zeros_like(s)).sum(0) / usable.sum().clamp(min=1)).contiguous()
+    sums = binding.autocorr(s, lengths, L, shift)
+    cov = autocorr_estimate(sums["sxy"], sums["sx"], sums["sy"], sums["count"], estimator)
+    cnt = sums["count"].to(torch.float64)
+    mean = shift + sums["sx"][0] / cnt[0]
+    packed = torch.cat([cov.reshape(-1), (cov / cov[:1]).reshape(-1), cnt, mean, cov[0]]).cpu().numpy()      # the one read-back
+    k = (L + 1) * d
+    return Autocorrelation(packed[k:2 * k].reshape(L + 1, d), packed[:k].reshape(L + 1, d),
+                           packed[2 * k:2 * k + L + 1].astype(np.int64), packed[2 * k + L + 1:2 * k + L + 1 + d],
+                           packed[2 * k + L + 1 + d:], estimator)
+
+
+def _acf_1d(acf):
+    rho = np.asarray(acf, np.float64)
+    if rho.ndim == 2 and rho.shape[1] == 1:
+        rho = rho[:, 0]
+    if rho.ndim != 1 or len(rho) < 1:
+        raise ValueError("the ACF must be (max_lag + 1,): one component")
+    return rho
+
+
+def integrated_autocorr_time(acf, c=5.0):
+    """Integrated autocorrelation time of one component's ACF rho (max_lag + 1,), in frames, with Sokal's automatic window:
+    tau(W) = 1/2 + sum_{l=1..W} rho(l), W the smallest window >= 1 with W >= c tau(W) -> (tau, window, converged).
+    converged is False when no window up to the last available lag qualifies (available: before the first non-finite
+    rho); tau is then the sum over all available lags and window the last of them."""
+    rho = _acf_1d(acf)
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError("integrated_autocorr_time: c must be finite and > 0")
+    bad = np.flatnonzero(~np.isfinite(rho[1:]))
+    last = int(bad[0]) if len(bad) else len(rho) - 1              # the last available lag
+    tau = 0.5 + np.cumsum(rho[1:last + 1])                          # tau[W - 1] = tau(W)
+    ok = np.flatnonzero(np.arange(1, last + 1) >= c * tau)
+    if len(ok):
+        return float(tau[ok[0]]), int(ok[0]) + 1, True
+    return (float(tau[-1]) if last else 0.5), last, False
+
+
+def crossing_time(acf, level=float(np.exp(-1.0))):
+    """The first time, in frames, at which one component's ACF rho (max_lag + 1,) falls below `level` (1 / e: the relaxation
+    time of a single exponential), linearly interpolated between the two lags around the crossing; NaN when rho never
+    falls below it (or meets a non-finite value first)."""
+    rho = _acf_1d(acf)
+    for l in range(len(rho)):
+        if not np.isfinite(rho[l]):
+            break
+        if rho[l] < level:
+            return float(l - 1 + (rho[l - 1] - level) / (rho[l - 1] - rho[l])) if l else 0.0
+    return float("nan")
+
+
+def effective_sample_size(n, tau):
+    """n / (2 tau): the number of independent samples n correlated frames are worth (tau in frames)."""
+    return n / (2.0 * tau)
+
+
+def standard_error(variance, n, tau):
+    """sqrt(variance * 2 tau / n): the standard error of the mean of n frames with integrated autocorrelation time tau."""
+    return np.sqrt(variance * 2.0 * tau / n)
+
+
+class RelaxationEvaluator:
+    """How fast does an observable decorrelate along the trajectories, and how many independent samples do they hold.
+    Frames -> series (cv="q": native_contacts_q's soft fraction of native contacts; cv="rmsd": the RMSD to the folded
+    structure, dff_struct_rmsd; cv="tic": the k components of the TIC projection of `tica`, a TicEvaluator, a TICA, a saved
+    reference or a (mean, coeff) pair) -> autocorrelation(series, max_lag, traj_lengths).  `folded` (q, rmsd) is a PDB path
+    or the folded C-alpha coordinates (N, 3) in Angstrom; frame_time is the time between two frames.
+
+    eval(xyz, traj_lengths=None) -- None: ONE trajectory -- returns a dict, a float per key for q and rmsd and a list over
+    the components for tic:
+      tau_int, window_converged   integrated autocorrelation time (Sokal's window, c = 5) in units of frame_time, and whether
+                                  the window closed inside max_lag (0.0 / 1.0)
+      tau_e                       first crossing of 1 / e, in units of frame_time; NaN without one
+      ess, ess_share              usable frames / (2 tau_int in frames), and that over the usable frames
+      mean, stderr                mean over the usable frames and its standard error sqrt(variance 2 tau / n)
+      samples_nonfinite           frames left out (a non-finite coordinate or component)
+    With ref_data (MD frames (m, N, 3), trajectories of ref_traj_lengths) the same keys with the suffix _ref, and
+    log10_tau_int_ratio (samples over reference; NaN unless both are positive).  The series and the Autocorrelation objects
+    stay on .series and .acf under "samples" / "refs".  Without the HIP library: DffLibraryError."""
+
+    KEYS = ("tau_int", "tau_e", "window_converged", "ess", "ess_share", "mean", "stderr", "samples_nonfinite")
+
+    def __init__(self, mol_name, folded=None, *, cv="q", tica=None, max_lag, frame_time=1.0, ref_data=None,
+                 ref_traj_lengths=None, device="cuda:0"):
+        if cv not in ("q", "rmsd", "tic"):
+            raise ValueError("RelaxationEvaluator: cv must be 'q', 'rmsd' or 'tic'")
+        self.max_lag = int(max_lag)
+        if self.max_lag != max_lag or not 1 <= self.max_lag <= binding.AUTOCORR_MAX_LAG:
+            raise ValueError(f"RelaxationEvaluator: max_lag must be an integer in 1..{binding.AUTOCORR_MAX_LAG}")
+        self.frame_time = float(frame_time)
+        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
+            raise ValueError("RelaxationEvaluator: frame_time must be finite and > 0")
+        self.mol_name, self.cv = mol_name, cv
+        self.device = torch.device(device)
+        if cv == "tic":
+            if tica is None:
+                raise ValueError("RelaxationEvaluator: cv='tic' needs tica")
+            self.mean, self.coeff = _tica_arrays(tica)
+            if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],) or not 1 <= self.coeff.shape[1] <= TICA_MAX_DIM:
+                raise ValueError(f"RelaxationEvaluator: mean must be (F,) and coeff (F, k), k <= {TICA_MAX_DIM}")
+        else:
+            if folded is None:
+                raise ValueError(f"RelaxationEvaluator: cv={cv!r} needs the folded structure")
+            self.folded = _folded_coords(folded, mol_name)
+            if cv == "q":
+                self.pairs, self.r0 = native_pairs(self.folded)
+        binding.load_library()
+        self.series, self.acf = {}, {}
+        self.ref_result = None
+        if ref_data is not None:
+            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+                ref_data = ref_data[:][0]
+            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+
+    def observable(self, x):
+        """the series of the frames x (n, N, 3) already on the device: (n,) float32 for q and rmsd, (n, k) float64 for tic"""
+        if self.cv == "tic":
+            return binding.struct_tic(x, self.mean, self.coeff)
+        if x.shape[1] != len(self.folded):
+            raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(self.folded)}")
+        if self.cv == "q":
+            return binding.struct_native_q(x, self.pairs, self.r0, 5.0, 1.2)
+        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float())
+
+    @staticmethod
+    def summarize(ac, frame_time=1.0, as_list=False):
+        """eval()'s dict from an Autocorrelation (or anything with its acf, counts, mean and variance) of n frames, counts[0]
+        of them usable: numpy only."""
+        acf = np.asarray(ac.acf, np.float64)
+        n_usable = int(ac.counts[0])
+        res = {k: [] for k in RelaxationEvaluator.KEYS[:-1]}
+        for c in range(acf.shape[1]):
+            tau, _, converged = integrated_autocorr_time(acf[:, c])
+            ok = n_usable > 0 and np.isfinite(tau) and tau > 0
+            ess = effective_sample_size(n_usable, tau) if ok else float("nan")
+            res["tau_int"].append(tau * frame_time)
+            res["tau_e"].append(crossing_time(acf[:, c]) * frame_time)
+            res["window_converged"].append(float(converged))
+            res["ess"].append(float(ess))
+            res["ess_share"].append(float(ess / n_usable) if ok else float("nan"))
+            res["mean"].append(float(ac.mean[c]))
+            res["stderr"].append(float(standard_error(ac.variance[c], n_usable, tau)) if ok else float("nan"))
+        if not as_list:
+            res = {k: v[0] for k, v in res.items()}
+        return res
+
+    def _analyse(self, xyz, traj_lengths, name):
+        x = _frames(xyz, self.device)
+        lengths = _check_lengths(traj_lengths, len(x))
+        series = self.observable(x)
+        ac = autocorrelation(series, min(self.max_lag, max(len(x) - 1, 0)), lengths, device=self.device)
+        self.series[name], self.acf[name] = series.cpu().numpy(), ac
+        res = self.summarize(ac, self.frame_time, as_list=self.cv == "tic")
+        res["samples_nonfinite"] = float(len(x) - ac.n_usable)
+        return res
+
+    def eval(self, xyz, traj_lengths=None):
+        res = self._analyse(xyz, traj_lengths, "samples")
+        if self.ref_result is not None:
+            ref = self.ref_result
+            res.update({k + "_ref": v for k, v in ref.items()})
+
+            def ratio(a, b):
+                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
+                return float(np.log10(a / b)) if ok else float("nan")
+            a, b = res["tau_int"], ref["tau_int"]
+            res["log10_tau_int_ratio"] = [ratio(u, v) for u, v in zip(a, b)] if isinstance(a, list) else ratio(a, b)
+        return res
