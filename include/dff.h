@@ -580,6 +580,63 @@ int dff_autocorr(int device, const double* series_dev, long long n, int d, const
                  int max_lag, const double* shift_dev, double* sxy_dev, double* sx_dev, double* sy_dev,
                  uint64_t* count_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- Markov state models at microstate resolution: k-means and transition counts for up to DFF_MSM_MAXK states, and the
+ * sweeps of the reversible maximum-likelihood estimator (csrc/dff_msm.hip) ----
+ * What follows the four preset states of the reference's notebook: a few hundred k-means microstates in TIC space, count
+ * matrices at several lag times, a reversible transition matrix with its stationary distribution, implied timescales
+ * against the lag (evaluate.py: MicrostateKMeans, MarkovStateModel, implied_timescales, MsmEvaluator).  The K <= 64 calls
+ * above keep their limit and their kernels; these are their counterparts for many states.
+ * Stateless like the calls above: device pointers, enqueued on `stream` only, no read-back and no synchronisation on the
+ * launch path; n == 0 is a valid no-op that still zeroes or overwrites what the call zeroes or overwrites; bad arguments
+ * are refused on the host before any device call; no floating-point atomics; no workgroup waits on another; bit-identical
+ * from call to call, independent of the workspace's prior contents and of every debug knob. */
+#define DFF_MSM_MAXK 1024
+/* Points per workgroup of the call below: a compile-time constant.  With (n, d, K) it fixes the order of every sum. */
+int dff_micro_chunk(void);
+/* Bytes of device workspace the call below needs for n points when it accumulates: ceil(n / chunk) rows of
+ * K (d + 1) + 1 doubles (56 MB of 2^20 bytes at n = 819 200, d = 8, K = 1024); -1 on bad arguments. */
+long long dff_micro_kmeans_workspace_bytes(long long n, int d, int K);
+/* One Lloyd iteration with many centres: the arguments, the outputs and the assignment rule (fp64, one FMA per
+ * coordinate in order, centres in index order, strict <, a non-finite point -> label -1, d2 = NaN, in no accumulator) are
+ * those of dff_kmeans_step, so for K <= 64 labels_dev and dist2_dev are bit-identical to its.  1 <= d <= 8,
+ * 1 <= K <= DFF_MSM_MAXK.  Every output may be NULL; with the three accumulators NULL the call only assigns and needs no
+ * workspace.  sums_dev, counts_dev and inertia_dev are OVERWRITTEN.  One workgroup per chunk of points, the centres in
+ * LDS; a chunk's members are added per accumulator in point order, the chunks' partials in chunk order by a second
+ * stage: the order of summation depends on (n, d, K) and the chunk size alone (sums and inertia are therefore NOT
+ * bit-identical to dff_kmeans_step's, which sums in another order).  workspace_dev 8-byte aligned. */
+int dff_micro_kmeans_step(int device, const double* pts_dev, long long n, int d, const double* centers_dev, int K,
+                          int32_t* labels_dev, double* dist2_dev, double* sums_dev, uint64_t* counts_dev,
+                          double* inertia_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Sliding-window transition counts between many states: arguments and semantics of dff_transition_counts with
+ * 1 <= K <= DFF_MSM_MAXK, 1 <= n_lags <= 8; counts_dev (n_lags, K, K) is zeroed by the call.  For K > 64: 64-bit integer
+ * atomics on global memory, equal (lag, i, j) aggregated inside a wave first.  For K <= 64 the call launches the
+ * LDS-privatised kernel of dff_transition_counts itself (measured faster there: a metastable path hammers a few diagonal
+ * counters), so its result is that call's.  Integer counting either way: exact, the same from call to call. */
+int dff_micro_transition_counts(int device, const int32_t* labels_dev, long long n, const long long* lengths_host,
+                                int n_traj, const int32_t* lags_host, int n_lags, int K, uint64_t* counts_dev, void* stream);
+/* Bytes of device workspace the call below needs (two vectors of K doubles); -1 on bad arguments. */
+long long dff_msm_workspace_bytes(int K);
+/* n_steps sweeps of the fixed-point iteration of the reversible maximum-likelihood transition matrix (Bowman et al. 2009;
+ * Prinz et al. 2011, algorithm 1 in its plain form) on a strongly connected set of K states:
+ *   q_j = c_j / x_j,     x_i' = sum_j S_ij / (q_i + q_j),
+ * sym_dev (K, K) fp64 row-major = S = C + C^T, rowc_dev (K) = c_i = sum_j C_ij > 0, x_dev (K) in/out, x_i > 0 (the host
+ * starts from x_i = sum_j S_ij / 2).  A pair with S_ij == 0 adds exactly +0.0 whatever its quotient would be (the quotient is
+ * formed and discarded by a select, also where q_j is NaN).  x is not renormalised: the map is homogeneous of degree 1.
+ * T_ij = S_ij / (q_i + q_j) / x_i and pi = x / sum x are left to the
+ * caller.  Every row sum is taken in one order (64 lanes stride over j, then a butterfly over the wave).
+ * err_dev (n_steps), may be NULL: err_s = max_i |x_i' - x_i| / x_i of sweep s.
+ * A row with c_i <= 0 or x_i <= 0 (or either NaN) gets x_i = NaN, from the next sweep on so does every row j with
+ * S_ij != 0, and err_s is NaN from that sweep on; nothing is read back to check it.
+ * All n_steps sweeps are enqueued without a host read; n_steps == 0 leaves x_dev alone.  1 <= K <= DFF_MSM_MAXK,
+ * n_steps >= 0, workspace_dev 8-byte aligned, contents irrelevant. */
+int dff_msm_reversible_steps(int device, const double* sym_dev, const double* rowc_dev, int K, double* x_dev, int n_steps,
+                             double* err_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* For benchmarks, process-wide: which kernel runs the sweeps.  0 = by K (the default), 1 = one launch per sweep,
+ * 2 = one workgroup that loops over all sweeps.  The results are the same bits either way. */
+int dff_debug_msm_driver(int driver);
+/* Host only: the driver a call with K states would take now, 1 or 2 as above; -1 on a bad K. */
+int dff_msm_driver_for(int K);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -13,6 +13,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
                                  [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
                                  [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
+                                 [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -53,6 +54,13 @@ the RMSD to the folded structure (rmsd; both need --folded-pdb) or of the compon
 0 .. --max-lag, inside the trajectories of --traj-lengths / --parallel-sim; its integrated autocorrelation time and 1 / e time
 in units of --frame-time, the effective sample size and the standard error of the mean.  With HELDOUT.pt (as for --kinetics)
 the same numbers for it with the suffix _ref, and log10_tau_int_ratio.
+
+--msm adds, under "msm", a Markov state model of time-ordered Langevin samples (MsmEvaluator): --msm-states k-means
+microstates in the space of MOL's TICA model, sliding-window counts at --msm-lag frames inside the trajectories of
+--traj-lengths / --parallel-sim, the largest strongly connected set, the reversible maximum-likelihood transition matrix and
+its slowest implied timescales in units of --frame-time.  With HELDOUT.pt (as for --kinetics) the microstates are fitted on
+it, and the same numbers for it come with the suffix _ref, with log10_timescale_ratio and stationary_js.  --msm-lagtimes
+a,b,c adds "implied_timescales": the timescales (frames x --frame-time) of the samples' model at each of these lag times.
 """
 import argparse
 import json
@@ -226,6 +234,57 @@ def relaxation(a, x):
     return res
 
 
+def msm_states(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 1 <= v <= evaluate.MSM_MAX_STATES:
+        raise argparse.ArgumentTypeError(f"the number of microstates must be 1..{evaluate.MSM_MAX_STATES}")
+    return v
+
+
+def msm_lag(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if v < 1:
+        raise argparse.ArgumentTypeError("a lag time must be >= 1 frame")
+    return v
+
+
+def msm_lagtimes(text):
+    try:
+        return [msm_lag(v) for v in text.split(",")]
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated lag times >= 1, got {text!r}")
+
+
+def msm_arguments(a):
+    if a.msm_states is None or a.msm_lag is None:
+        raise SystemExit("--msm needs --msm-states K and --msm-lag L (frames)")
+    return a.msm_states, a.msm_lag
+
+
+def msm(a, x):
+    K, lag = msm_arguments(a)
+    ref, ref_lengths = ordered_frames(a.msm) if a.msm else (None, None)
+    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
+    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+    ev = evaluate.MsmEvaluator(a.mol.lower(), tica, n_microstates=K, lagtime=lag, frame_time=a.frame_time, ref_data=ref,
+                               ref_traj_lengths=ref_lengths, device=a.device)
+    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
+    lengths = traj_lengths(a, len(x))
+    res = {k: ([clean(u) for u in v] if isinstance(v, list) else clean(v)) for k, v in ev.eval(x, lengths).items()}
+    res.update({"n_microstates": K, "lagtime": lag, "frame_time": a.frame_time})
+    if a.msm_lagtimes:
+        its = evaluate.implied_timescales(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales, device=a.device)
+        res["implied_timescales"] = {"lagtimes": a.msm_lagtimes,
+                                     "timescales": [[clean(v * a.frame_time) for v in row] for row in its]}
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -275,7 +334,7 @@ def build_parser():
                     help="the two cores cv <= LO and cv >= HI (with --kinetics; 0.2,0.9 for q)")
     ap.add_argument("--frame-time", type=frame_time, default=1.0, metavar="T",
                     help="time between two frames, the unit of the rates and dwell times (with --kinetics) and of the "
-                         "relaxation times (with --relaxation)")
+                         "relaxation times (with --relaxation) and the implied timescales (with --msm)")
     ap.add_argument("--relaxation", nargs="?", const="", default=None, metavar="HELDOUT.pt",
                     help="also report autocorrelation times, effective sample size and standard error of an observable "
                          "(time-ordered Langevin samples; needs --max-lag); with HELDOUT.pt also for that MD data")
@@ -283,6 +342,13 @@ def build_parser():
                     help="observable: fraction of native contacts, RMSD to the folded structure (both need --folded-pdb) or "
                          "the TICs of MOL's saved TICA model (with --relaxation)")
     ap.add_argument("--max-lag", type=max_lag, default=None, metavar="L", help="largest lag in frames (with --relaxation)")
+    ap.add_argument("--msm", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report a Markov state model's implied timescales (time-ordered Langevin samples; needs "
+                         "--msm-states and --msm-lag); with HELDOUT.pt also for that MD data, on microstates fitted on it")
+    ap.add_argument("--msm-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --msm)")
+    ap.add_argument("--msm-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --msm)")
+    ap.add_argument("--msm-lagtimes", type=msm_lagtimes, default=None, metavar="a,b,c",
+                    help="also the implied timescales at these lag times in frames (with --msm)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -302,6 +368,8 @@ def main():
         ap.error("--relaxation with --relaxation-cv q or rmsd needs --folded-pdb")
     if a.relaxation is not None:
         relaxation_max_lag(a)
+    if a.msm is not None:
+        msm_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -333,6 +401,8 @@ def main():
         res["kinetics"] = kinetics(a, x)
     if a.relaxation is not None:
         res["relaxation"] = relaxation(a, x)
+    if a.msm is not None:
+        res["msm"] = msm(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

@@ -18,6 +18,7 @@ __all__ += ["superpose", "mean_structure", "rmsf", "FlexibilityEvaluator"]
 __all__ += ["cluster_rmsd", "RmsdClusterEvaluator"]
 __all__ += ["native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator"]
 __all__ += ["autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator"]
+__all__ += ["MicrostateKMeans", "largest_connected_set", "MarkovStateModel", "implied_timescales", "MsmEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -43,6 +44,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("MicrostateKMeans", "largest_connected_set", "MarkovStateModel", "implied_timescales", "MsmEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

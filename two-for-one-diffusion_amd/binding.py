@@ -119,6 +119,15 @@ SYMBOLS = {
     "dff_autocorr_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "dff_autocorr": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                _P]),
+    "dff_micro_chunk": (C.c_int, []),
+    "dff_micro_kmeans_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "dff_micro_kmeans_step": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                        _P]),
+    "dff_micro_transition_counts": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "dff_msm_workspace_bytes": (C.c_longlong, [C.c_int]),
+    "dff_msm_reversible_steps": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "dff_debug_msm_driver": (C.c_int, [C.c_int]),
+    "dff_msm_driver_for": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -958,3 +967,115 @@ def autocorr(series, lengths, max_lag: int, shift=None, sx=True, sy=True, count=
                                  _ptr(out.get("count")), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
                                  _stream(series)), "dff_autocorr")
     return out
+
+
+# ---- Markov state models at microstate resolution (dff_micro_*, dff_msm_*) ----
+MSM_MAX_STATES = 1024
+MSM_MAX_LAGS = 8
+
+
+def __getattr__(name):
+    if name == "MICRO_CHUNK":               # points per workgroup of dff_micro_kmeans_step, read from the library
+        return int(load_library().dff_micro_chunk())
+    raise AttributeError(name)
+
+
+def micro_kmeans_workspace_bytes(n: int, d: int, K: int) -> int:
+    return _workspace_bytes("dff_micro_kmeans_workspace_bytes", int(n), int(d), int(K))
+
+
+def micro_kmeans_step(points, centers, accumulate=True, workspace=None):
+    """kmeans_step for up to MSM_MAX_STATES centres (dff_micro_kmeans_step): the same arguments and the same dict --
+    labels int32 (n,), dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64
+    (1,) over the finite points.  Labels and dist2 are kmeans_step's bits for K <= 64; the sums are taken in another
+    (fixed) order.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64
+            and points.is_contiguous() and points.dim() == 2):
+        raise ValueError("points must be a contiguous float64 CUDA tensor of shape (n, d)")
+    n, d = int(points.shape[0]), int(points.shape[1])
+    c = _centers(centers, d, points.device)
+    K = int(c.shape[0])
+    out = {"labels": torch.empty(n, dtype=torch.int32, device=points.device),
+           "dist2": torch.empty(n, dtype=torch.float64, device=points.device)}
+    ws_bytes = 0
+    if accumulate:
+        need = micro_kmeans_workspace_bytes(n, d, K)            # refuses a bad d or K before anything is allocated
+        out["sums"] = torch.empty((max(K, 1), d), dtype=torch.float64, device=points.device)
+        out["counts"] = torch.empty(max(K, 1), dtype=torch.int64, device=points.device)
+        out["inertia"] = torch.empty(1, dtype=torch.float64, device=points.device)
+        if workspace is None:
+            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=points.device)
+        ws_bytes = int(workspace.numel() * workspace.element_size())
+    else:
+        workspace = None
+    _check(lib, lib.dff_micro_kmeans_step(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
+                                          _ptr(out["dist2"]), _ptr(out.get("sums")), _ptr(out.get("counts")),
+                                          _ptr(out.get("inertia")), _ptr(workspace), ws_bytes, _stream(points)),
+           "dff_micro_kmeans_step")
+    return out
+
+
+def micro_transition_counts(labels, lengths, lagtimes, n_states: int):
+    """transition_counts for up to MSM_MAX_STATES states and up to MSM_MAX_LAGS lag times (dff_micro_transition_counts) ->
+    int64 CUDA tensor (n_lags, K, K); exact, and equal to transition_counts' result for K <= 64."""
+    import torch
+    lib = load_library()
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
+            and labels.is_contiguous() and labels.dim() == 1):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
+    ln = _lengths(lengths)
+    lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
+    K = int(n_states)
+    Ka = min(max(K, 1), MSM_MAX_STATES)                          # what is allocated when K itself will be refused
+    out = torch.empty((min(max(int(lg.size), 1), MSM_MAX_LAGS), Ka, Ka), dtype=torch.int64, device=labels.device)
+    _check(lib, lib.dff_micro_transition_counts(labels.device.index, _ptr(labels), int(labels.numel()),
+                                                ln.ctypes.data_as(C.c_void_p), int(ln.size),
+                                                lg.ctypes.data_as(C.c_void_p), int(lg.size), K, _ptr(out),
+                                                _stream(labels)), "dff_micro_transition_counts")
+    return out
+
+
+def msm_workspace_bytes(K: int) -> int:
+    return _workspace_bytes("dff_msm_workspace_bytes", int(K))
+
+
+def msm_reversible_steps(sym, rowc, x, n_steps: int, err=True, workspace=None):
+    """Enqueue n_steps sweeps x_i' = sum_j S_ij / (c_i / x_i + c_j / x_j) of the reversible maximum-likelihood estimator
+    (dff_msm_reversible_steps) on sym (K, K), rowc (K,) and x (K,), contiguous float64 CUDA tensors; x is updated in
+    place.  Returns the float64 CUDA tensor (n_steps,) of err_s = max_i |x_i' - x_i| / x_i (None with err=False).  Nothing
+    is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+
+    def ok(t, shape):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                and tuple(t.shape) == shape)
+    K = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 1 else -1
+    if not (ok(x, (K,)) and ok(sym, (K, K)) and ok(rowc, (K,)) and sym.device == x.device and rowc.device == x.device):
+        raise ValueError("sym (K, K), rowc (K,) and x (K,) must be contiguous float64 CUDA tensors on one device")
+    n_steps = int(n_steps)
+    need = msm_workspace_bytes(K)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    e = torch.empty(max(n_steps, 0), dtype=torch.float64, device=x.device) if err else None
+    _check(lib, lib.dff_msm_reversible_steps(x.device.index, _ptr(sym), _ptr(rowc), K, _ptr(x), n_steps, _ptr(e),
+                                             _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                             _stream(x)), "dff_msm_reversible_steps")
+    return e
+
+
+def debug_msm_driver(driver: int):
+    """Benchmarks only: 0 = the library's choice by K, 1 = one launch per sweep, 2 = one workgroup for all sweeps."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_msm_driver(int(driver)), "dff_debug_msm_driver")
+
+
+def msm_driver_for(K: int) -> int:
+    """The driver msm_reversible_steps would take for K states now: 1 = one launch per sweep, 2 = one workgroup."""
+    lib = load_library()
+    r = int(lib.dff_msm_driver_for(int(K)))
+    if r < 0:
+        _check(lib, 1, "dff_msm_driver_for")
+    return r

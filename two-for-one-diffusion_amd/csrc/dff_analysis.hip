@@ -1,7 +1,8 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
+#include <atomic>
 
 #include "dff_pwd.hip"
 #include "dff_struct.hip"
@@ -12,6 +13,7 @@
 #include "dff_cluster.hip"
 #include "dff_kinetics.hip"
 #include "dff_autocorr.hip"
+#include "dff_msm.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -473,6 +475,25 @@ static int traj_launches(const long long* lengths, int n_traj, long long n, Laun
     return runs.n ? launch(runs) : DFF_OK;
 }
 
+// the launches of dff_transition_counts_kernel over checked arguments, n > 0, K <= DFF_STATES_MAXK, counts already zeroed
+static int tc_launches(hipStream_t stream, const int32_t* labels, long long n, const long long* lengths, int n_traj,
+                       const int32_t* lags, int n_lags, int K, uint64_t* counts) {
+    const int per_group = DFF_TC_LDS_COUNTERS / (K * K) < n_lags ? DFF_TC_LDS_COUNTERS / (K * K) : n_lags;   // >= 2
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        const long long wgs = (runs.end - runs.begin + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
+        for (int l0 = 0; l0 < n_lags; l0 += per_group) {
+            TransLags g;
+            g.n = n_lags - l0 < per_group ? n_lags - l0 : per_group;
+            for (int l = 0; l < DFF_TC_MAXLAGS; ++l) g.lag[l] = l < g.n ? lags[l0 + l] : 0;
+            hipLaunchKernelGGL(dff_transition_counts_kernel, dim3((unsigned)(wgs < DFF_TC_WGS ? wgs : DFF_TC_WGS)),
+                               dim3(DFF_TC_THREADS), (unsigned)(g.n * K * K * sizeof(unsigned)), stream, labels, K, runs, g,
+                               (unsigned long long*)counts + (size_t)l0 * K * K);
+            HIPCHK(hipGetLastError());
+        }
+        return DFF_OK;
+    });
+}
+
 extern "C" int dff_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
                                      const int32_t* lags, int n_lags, int K, uint64_t* counts, void* stream_) {
     if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "transition_counts: null labels / negative count");
@@ -488,20 +509,7 @@ extern "C" int dff_transition_counts(int device, const int32_t* labels, long lon
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipMemsetAsync(counts, 0, (size_t)n_lags * K * K * sizeof(uint64_t), stream));
     if (n == 0) return DFF_OK;
-    const int per_group = DFF_TC_LDS_COUNTERS / (K * K) < n_lags ? DFF_TC_LDS_COUNTERS / (K * K) : n_lags;   // >= 2
-    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
-        const long long wgs = (runs.end - runs.begin + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
-        for (int l0 = 0; l0 < n_lags; l0 += per_group) {
-            TransLags g;
-            g.n = n_lags - l0 < per_group ? n_lags - l0 : per_group;
-            for (int l = 0; l < DFF_TC_MAXLAGS; ++l) g.lag[l] = l < g.n ? lags[l0 + l] : 0;
-            hipLaunchKernelGGL(dff_transition_counts_kernel, dim3((unsigned)(wgs < DFF_TC_WGS ? wgs : DFF_TC_WGS)),
-                               dim3(DFF_TC_THREADS), (unsigned)(g.n * K * K * sizeof(unsigned)), stream, labels, K, runs, g,
-                               (unsigned long long*)counts + (size_t)l0 * K * K);
-            HIPCHK(hipGetLastError());
-        }
-        return DFF_OK;
-    });
+    return tc_launches(stream, labels, n, lengths, n_traj, lags, n_lags, K, counts);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -904,6 +912,160 @@ extern "C" int dff_autocorr(int device, const double* series, long long n, int d
     const long long nred = (long long)K * sh.nlags;
     hipLaunchKernelGGL(dff_ac_reduce_kernel, dim3((unsigned)((nred + 15) / 16)), dim3(DFF_AC_THREADS), 0, stream, (const double*)part, sh.slots, d, sh.nlags, K, sxy, sx, sy,
                        (unsigned long long*)count);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Markov state models: microstate k-means, transition counts, reversible estimator (dff_msm.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dff_micro_chunk(void) { return DFF_MICRO_CHUNK; }
+
+static int micro_check_count(int K, const char* what, const char* noun) {
+    if (K < 1 || K > DFF_MSM_MAXK) return fail(DFF_EINVAL, "%s: the number of %s must be 1..%d", what, noun, DFF_MSM_MAXK);
+    return DFF_OK;
+}
+
+static long long micro_chunks(long long n) { return (n + DFF_MICRO_CHUNK - 1) / DFF_MICRO_CHUNK; }
+
+static int micro_check_shape(long long n, int d, int K, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative point count", what);
+    if (micro_chunks(n) > 0x7fffffffLL) return fail(DFF_EINVAL, "%s: too many points", what);
+    if (d < 1 || d > DFF_KM_MAXD) return fail(DFF_EINVAL, "%s: d must be 1..%d", what, DFF_KM_MAXD);
+    return micro_check_count(K, what, "centres");
+}
+
+extern "C" long long dff_micro_kmeans_workspace_bytes(long long n, int d, int K) {
+    if (micro_check_shape(n, d, K, "micro_kmeans_workspace_bytes")) return -1;
+    return micro_chunks(n) * ((long long)K * (d + 1) + 1) * (long long)sizeof(double);
+}
+
+extern "C" int dff_micro_kmeans_step(int device, const double* pts, long long n, int d, const double* centers, int K,
+                                     int32_t* labels, double* dist2, double* sums, uint64_t* counts, double* inertia,
+                                     void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = micro_check_shape(n, d, K, "micro_kmeans_step");
+    if (rc) return rc;
+    if (!pts && n > 0) return fail(DFF_EINVAL, "micro_kmeans_step: null points");
+    if (!centers) return fail(DFF_EINVAL, "micro_kmeans_step: null centres");
+    const bool accumulate = sums || counts || inertia;
+    const long long need = accumulate ? dff_micro_kmeans_workspace_bytes(n, d, K) : 0;       // 0 at n = 0
+    if ((rc = check_workspace(workspace, workspace_bytes, need, "micro_kmeans_step"))) return rc;
+    if (need > 0 && (uintptr_t)workspace % sizeof(double))
+        return fail(DFF_EINVAL, "micro_kmeans_step: the workspace must be 8-byte aligned");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n == 0) {
+        if (sums) HIPCHK(hipMemsetAsync(sums, 0, (size_t)K * d * sizeof(double), stream));
+        if (counts) HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(uint64_t), stream));
+        if (inertia) HIPCHK(hipMemsetAsync(inertia, 0, sizeof(double), stream));
+        return DFF_OK;
+    }
+    if (!accumulate && !labels && !dist2) return DFF_OK;
+    const unsigned grid = (unsigned)micro_chunks(n);
+    const int groups = accumulate ? micro_groups(d, K) : 0;
+    const unsigned lds = (unsigned)micro_lds_bytes(d, K, groups);              // <= 160 KB
+    if (accumulate) {
+        if (lds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_micro_kmeans_kernel<true>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d, centers,
+                           K, labels, dist2, (double*)workspace, groups);
+        HIPCHK(hipGetLastError());
+        const int per = K * (d + 1) + 1;
+        hipLaunchKernelGGL(dff_micro_kmeans_reduce_kernel, dim3((unsigned)((per + 63) / 64)), dim3(256), 0, stream,
+                           (const double*)workspace, (long long)grid, d, K, sums, (unsigned long long*)counts, inertia);
+    } else {
+        if (lds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<false>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_micro_kmeans_kernel<false>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d,
+                           centers, K, labels, dist2, (double*)nullptr, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_micro_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths,
+                                           int n_traj, const int32_t* lags, int n_lags, int K, uint64_t* counts,
+                                           void* stream_) {
+    if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "micro_transition_counts: null labels / negative count");
+    int rc = micro_check_count(K, "micro_transition_counts", "states");
+    if (rc) return rc;
+    if (!lags || n_lags < 1 || n_lags > DFF_TC_MAXLAGS)
+        return fail(DFF_EINVAL, "micro_transition_counts: the number of lag times must be 1..%d", DFF_TC_MAXLAGS);
+    for (int l = 0; l < n_lags; ++l)
+        if (lags[l] < 1) return fail(DFF_EINVAL, "micro_transition_counts: lag time %d is %d, must be >= 1", l, (int)lags[l]);
+    if ((rc = traj_check_lengths(lengths, n_traj, n, "micro_transition_counts"))) return rc;
+    if (!counts) return fail(DFF_EINVAL, "micro_transition_counts: null counts");
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)n_lags * K * K * sizeof(uint64_t), stream));
+    if (n == 0) return DFF_OK;
+    // few states: the counters of a group of lags fit in LDS, and a metastable path hammers a handful of them -- the
+    // privatised kernel of dff_transition_counts (integer counts: the same result either way)
+    if (K <= DFF_STATES_MAXK) return tc_launches(stream, labels, n, lengths, n_traj, lags, n_lags, K, counts);
+    TransLags g;
+    g.n = n_lags;
+    for (int l = 0; l < DFF_TC_MAXLAGS; ++l) g.lag[l] = l < n_lags ? lags[l] : 0;
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        const long long wgs = (runs.end - runs.begin + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
+        hipLaunchKernelGGL(dff_micro_tc_kernel, dim3((unsigned)(wgs < 4 * DFF_TC_WGS ? wgs : 4 * DFF_TC_WGS)),
+                           dim3(DFF_TC_THREADS), 0, stream, labels, K, runs, g, (unsigned long long*)counts);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    });
+}
+
+// which kernel drives the sweeps: 0 = by the number of states, 1 = one launch per sweep, 2 = one workgroup for all sweeps
+static std::atomic<int> g_msm_driver{0};
+#define DFF_MSM_LOOP_MAXK 32       // automatic choice: the one-workgroup loop up to this many states (measured: DESIGN.md section 17)
+
+extern "C" int dff_debug_msm_driver(int driver) {
+    if (driver < 0 || driver > 2) return fail(DFF_EINVAL, "debug_msm_driver: 0 (automatic), 1 (launch per sweep) or 2 (one workgroup)");
+    g_msm_driver.store(driver);
+    return DFF_OK;
+}
+
+static int msm_driver(int K) {
+    const int driver = g_msm_driver.load();
+    return driver ? driver : (K <= DFF_MSM_LOOP_MAXK ? 2 : 1);
+}
+
+extern "C" int dff_msm_driver_for(int K) {
+    if (micro_check_count(K, "msm_driver_for", "states")) return -1;
+    return msm_driver(K);
+}
+
+extern "C" long long dff_msm_workspace_bytes(int K) {
+    if (micro_check_count(K, "msm_workspace_bytes", "states")) return -1;
+    return 2LL * K * (long long)sizeof(double);                        // q ping | q pong
+}
+
+extern "C" int dff_msm_reversible_steps(int device, const double* sym, const double* rowc, int K, double* x, int n_steps,
+                                        double* err, void* workspace, size_t workspace_bytes, void* stream_) {
+    int rc = micro_check_count(K, "msm_reversible_steps", "states");
+    if (rc) return rc;
+    if (n_steps < 0) return fail(DFF_EINVAL, "msm_reversible_steps: negative n_steps");
+    if (!sym || !rowc || !x) return fail(DFF_EINVAL, "msm_reversible_steps: null matrix / row counts / x");
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_workspace_bytes(K), "msm_reversible_steps"))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "msm_reversible_steps: the workspace must be 8-byte aligned");
+    if (n_steps == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (err) HIPCHK(hipMemsetAsync(err, 0, (size_t)n_steps * sizeof(double), stream));
+    if (msm_driver(K) == 2) {
+        hipLaunchKernelGGL(dff_msm_loop_kernel, dim3(1), dim3(DFF_MSM_LOOP_THREADS), (unsigned)(3 * K * sizeof(double)), stream,
+                           sym, rowc, K, x, n_steps, (unsigned long long*)err);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    }
+    double* q[2] = {(double*)workspace, (double*)workspace + K};
+    hipLaunchKernelGGL(dff_msm_init_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, rowc, (const double*)x, K,
+                       q[0]);
+    const unsigned grid = (unsigned)((K + DFF_MSM_THREADS / 64 - 1) / (DFF_MSM_THREADS / 64));
+    for (int s = 0; s < n_steps; ++s)
+        hipLaunchKernelGGL(dff_msm_sweep_kernel, dim3(grid), dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, K, x,
+                           (const double*)q[s & 1], q[(s + 1) & 1], err ? (unsigned long long*)err + s : nullptr);
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

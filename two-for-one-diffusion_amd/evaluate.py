@@ -1853,3 +1853,407 @@ class RelaxationEvaluator:
             a, b = res["tau_int"], ref["tau_int"]
             res["log10_tau_int_ratio"] = [ratio(u, v) for u, v in zip(a, b)] if isinstance(a, list) else ratio(a, b)
         return res
+
+
+# =====================================================================================================
+# Markov state models at microstate resolution (dff_micro_kmeans_step, dff_micro_transition_counts,
+# dff_msm_reversible_steps; csrc/dff_msm.hip).  The reference builds a four-state model with deeptime
+# (evaluate_fastfolders.ipynb, cells 20-24); deeptime is not installed where this was written, so the semantics are
+# restated from the literature -- k-means microstates, sliding-window counts, the largest strongly connected set, the
+# reversible maximum-likelihood estimator of Bowman et al. 2009 / Prinz et al. 2011 (algorithm 1, plain form) -- and tested
+# against a from-scratch fp64 oracle (tests/msm_oracle.py).
+# Out of scope: PCCA+ and other coarse-graining, mean first-passage times / transition-path theory, Bayesian error bars,
+# Chapman-Kolmogorov tests, sparse count matrices.
+# =====================================================================================================
+MSM_MAX_STATES = binding.MSM_MAX_STATES
+
+
+class MicrostateKMeans(KMeans):
+    """KMeans with up to 1024 centres (dff_micro_kmeans_step): the same contract, stopping rule and attributes.  The
+    k-means++ seeding follows KMeans' generator protocol draw by draw but keeps the squared distance to the nearest centre
+    drawn so far and folds in each new centre with ONE single-centre assignment call (torch.minimum): O(n K) instead of
+    O(n K^2), and the same centres as KMeans for the same seed and K <= 64."""
+
+    def __init__(self, n_clusters, max_iter=100, tolerance=1e-5, init="kmeans++", initial_centers=None, seed=0, *,
+                 device="cuda:0"):
+        self.n_clusters, self.max_iter, self.tolerance = int(n_clusters), int(max_iter), float(tolerance)
+        if not 1 <= self.n_clusters <= MSM_MAX_STATES:
+            raise ValueError(f"MicrostateKMeans: n_clusters must be 1..{MSM_MAX_STATES}")
+        if self.max_iter < 0:
+            raise ValueError("MicrostateKMeans: max_iter must be >= 0")
+        if initial_centers is None and init != "kmeans++":
+            raise ValueError(f"MicrostateKMeans: init must be 'kmeans++' (or give initial_centers), not {init!r}")
+        self.init, self.seed = init, int(seed)
+        self.initial_centers = None
+        if initial_centers is not None:
+            c = np.array(initial_centers, np.float64)
+            if c.ndim != 2 or c.shape[0] != self.n_clusters or not np.all(np.isfinite(c)):
+                raise ValueError(f"MicrostateKMeans: initial_centers must be finite and ({self.n_clusters}, d)")
+            self.initial_centers = c
+        self.device = torch.device(device)
+        binding.load_library()
+        self.cluster_centers = self.inertia = None
+        self.n_iter = 0
+
+    def _seed_centers(self, pts):
+        n, K = int(pts.shape[0]), self.n_clusters
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(self.seed)
+        finite = torch.isfinite(pts).all(dim=1)
+        idx = torch.nonzero(finite).reshape(-1)
+        if idx.numel() < K:
+            raise ValueError(f"MicrostateKMeans: {int(idx.numel())} finite points for {K} clusters")
+        first = idx[torch.randint(int(idx.numel()), (1,), generator=gen, device=self.device)]
+        picks = [first]
+        d2 = None
+        for _ in range(1, K):
+            new = torch.nan_to_num(binding.micro_kmeans_step(pts, pts[picks[-1]], accumulate=False)["dist2"], nan=0.0)
+            d2 = new if d2 is None else torch.minimum(d2, new)
+            cum = torch.cumsum(d2, 0)
+            u = torch.rand(1, dtype=torch.float64, generator=gen, device=self.device) * cum[-1]
+            nxt = torch.searchsorted(cum, u, right=True).clamp_(max=n - 1)
+            if not bool(d2[nxt] > 0):                 # every point sits on a centre already: any finite point will do
+                nxt = first
+            picks.append(nxt)
+        return pts[torch.cat(picks)].cpu().numpy()
+
+    def fit(self, points):
+        pts = _points(points, self.device)
+        n, d = int(pts.shape[0]), int(pts.shape[1])
+        if self.initial_centers is not None:
+            if self.initial_centers.shape[1] != d:
+                raise ValueError(f"MicrostateKMeans: initial_centers are {self.initial_centers.shape}, points have d = {d}")
+            centers = self.initial_centers.copy()
+        else:
+            centers = self._seed_centers(pts)
+        ws = torch.empty(max(binding.micro_kmeans_workspace_bytes(n, d, self.n_clusters), 8), dtype=torch.uint8,
+                         device=self.device)
+        prev, self.n_iter = None, 0
+        for _ in range(self.max_iter):
+            r = binding.micro_kmeans_step(pts, centers, workspace=ws)
+            sums, counts, inertia = r["sums"].cpu().numpy(), r["counts"].cpu().numpy(), float(r["inertia"][0])
+            has = counts > 0
+            centers = centers.copy()
+            centers[has] = sums[has] / counts[has, None]
+            self.n_iter += 1
+            if prev is not None and abs(prev - inertia) <= self.tolerance * prev:
+                break
+            prev = inertia
+        self.cluster_centers = centers
+        self.inertia = float(binding.micro_kmeans_step(pts, centers, workspace=ws)["inertia"][0])
+        return self
+
+    def _assign(self, pts):
+        if self.cluster_centers is None:
+            raise ValueError("MicrostateKMeans: not fitted")
+        return binding.micro_kmeans_step(pts, self.cluster_centers, accumulate=False)["labels"]
+
+
+def largest_connected_set(counts):
+    """Sorted indices (int64 array) of the largest strongly connected component of the directed graph with an edge i -> j
+    wherever counts[i, j] > 0.  Largest by the number of states; among equals the component that holds the lowest index.
+    (Tarjan's algorithm with an explicit stack; a state without transitions is a component of its own.)"""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError("largest_connected_set: counts must be a square matrix")
+    K = c.shape[0]
+    adj = [np.nonzero(row > 0)[0] for row in c]
+    index = np.full(K, -1, np.int64)
+    low = np.zeros(K, np.int64)
+    on_stack = np.zeros(K, bool)
+    stack, best, counter = [], None, 0
+    for root in range(K):
+        if index[root] >= 0:
+            continue
+        work = [(root, 0)]
+        index[root] = low[root] = counter
+        counter += 1
+        stack.append(root)
+        on_stack[root] = True
+        while work:
+            v, pos = work.pop()
+            nb = adj[v]
+            while pos < len(nb):
+                w = int(nb[pos])
+                pos += 1
+                if index[w] < 0:
+                    work.append((v, pos))
+                    index[w] = low[w] = counter
+                    counter += 1
+                    stack.append(w)
+                    on_stack[w] = True
+                    work.append((w, 0))
+                    break
+                if on_stack[w]:
+                    low[v] = min(low[v], index[w])
+            else:
+                if low[v] == index[v]:
+                    comp = []
+                    while True:
+                        w = stack.pop()
+                        on_stack[w] = False
+                        comp.append(w)
+                        if w == v:
+                            break
+                    if best is None or (len(comp), -min(comp)) > (len(best), -min(best)):
+                        best = comp
+                if work:
+                    u = work[-1][0]
+                    low[u] = min(low[u], low[v])
+    return np.sort(np.asarray(best if best is not None else [], np.int64))
+
+
+class _DeviceSweeps:
+    """S and c on the device once; sweep(x, n) runs n sweeps from the host vector x -> (x after them, err (n,))."""
+
+    def __init__(self, S, c, device):
+        self.S = torch.from_numpy(np.ascontiguousarray(S, np.float64)).to(device)
+        self.c = torch.from_numpy(np.ascontiguousarray(c, np.float64)).to(device)
+        self.ws = torch.empty(max(binding.msm_workspace_bytes(len(c)), 8), dtype=torch.uint8, device=device)
+
+    def __call__(self, x, n):
+        xd = torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(self.S.device)
+        err = binding.msm_reversible_steps(self.S, self.c, xd, n, workspace=self.ws)
+        return xd.cpu().numpy(), err.cpu().numpy()
+
+
+def reversible_sweeper(S, c, device):
+    """sweep(x, n) -> (x', err) for the reversible estimator on S = C + C^T (K, K) and c (K,): n sweeps of
+    x_i' = sum_j S_ij / (c_i / x_i + c_j / x_j) on the GPU (dff_msm_reversible_steps), err_s = max_i |x_i' - x_i| / x_i."""
+    return _DeviceSweeps(S, c, device)
+
+
+def reversible_transition_matrix(S, c, x):
+    """T_ij = S_ij / (c_i / x_i + c_j / x_j) / x_i and pi = x / sum x from a (converged) x: numpy, one K^2 expression."""
+    S, c, x = np.asarray(S, np.float64), np.asarray(c, np.float64), np.asarray(x, np.float64)
+    q = c / x
+    den = q[:, None] + q[None, :]
+    flow = np.divide(S, den, out=np.zeros_like(S), where=S != 0)
+    return flow / x[:, None], x / x.sum()
+
+
+class MarkovStateModel:
+    """A Markov state model at one lag time: counts -> largest strongly connected ("active") set -> transition matrix.
+
+    reversible=True: the maximum-likelihood transition matrix under detailed balance, by the fixed-point iteration
+    x_i' = sum_j (C_ij + C_ji) / (c_i / x_i + c_j / x_j) from x_i = sum_j (C_ij + C_ji) / 2, swept on the GPU in batches
+    of `steps_per_sync` until a sweep changes no x_i by more than `tol` relative (converged) or max_iter sweeps are spent.
+    reversible=False: transition_matrix(counts) on the active set (row normalisation), its stationary distribution from
+    the leading left eigenvector.
+
+    fit(labels, traj_lengths=None, n_states=None) counts sliding-window transitions at `lagtime` on the GPU (labels < 0
+    are skipped; n_states defaults to max(label) + 1); fit_counts(counts) starts from a (K, K) count matrix.  Afterwards:
+    count_matrix (K, K, all states), active_set (sorted indices), active_count_share (the counts that stay inside the
+    active set over all counts), transition_matrix and stationary_distribution (on the active set), n_iter, converged."""
+
+    def __init__(self, lagtime, reversible=True, tol=1e-12, max_iter=1_000_000, steps_per_sync=256, *, device="cuda:0"):
+        self.lagtime = int(lagtime)
+        if self.lagtime != lagtime or self.lagtime < 1:
+            raise ValueError("MarkovStateModel: lagtime must be an integer >= 1")
+        self.reversible = bool(reversible)
+        self.tol, self.max_iter, self.steps_per_sync = float(tol), int(max_iter), int(steps_per_sync)
+        if not self.tol > 0 or self.max_iter < 0 or self.steps_per_sync < 1:
+            raise ValueError("MarkovStateModel: tol must be > 0, max_iter >= 0 and steps_per_sync >= 1")
+        self.device = torch.device(device)
+        self.transition_matrix = self.stationary_distribution = self.active_set = self.count_matrix = None
+        self.active_count_share, self.n_iter, self.converged = float("nan"), 0, False
+
+    def fit(self, labels, traj_lengths=None, n_states=None):
+        lab = torch.as_tensor(labels).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(lab.numel())
+        lengths = _check_lengths(traj_lengths, n)
+        if n_states is None:
+            n_states = int(lab.max()) + 1 if n else 0
+        if not 1 <= int(n_states) <= MSM_MAX_STATES:
+            raise ValueError(f"MarkovStateModel: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+        counts = binding.micro_transition_counts(lab, lengths, [self.lagtime], int(n_states))
+        return self.fit_counts(counts[0].cpu().numpy())
+
+    def fit_counts(self, counts):
+        C = np.array(counts, np.float64)
+        if C.ndim != 2 or C.shape[0] != C.shape[1] or C.shape[0] < 1 or not np.all(np.isfinite(C)) or (C < 0).any():
+            raise ValueError("MarkovStateModel: counts must be a finite, non-negative (K, K) matrix")
+        self.count_matrix = C
+        act = largest_connected_set(C)
+        self.active_set = act
+        Ca = C[np.ix_(act, act)]
+        total = C.sum()
+        self.active_count_share = float(Ca.sum() / total) if total > 0 else 0.0
+        self.n_iter, self.converged = 0, True
+        if len(act) == 1:
+            self.transition_matrix, self.stationary_distribution = np.ones((1, 1)), np.ones(1)
+        elif self.reversible:
+            self._fit_reversible(Ca)
+        else:
+            T = transition_matrix(Ca)
+            w, v = np.linalg.eig(T.T)
+            pi = np.abs(np.real(v[:, np.argmax(np.real(w))]))
+            self.transition_matrix, self.stationary_distribution = T, pi / pi.sum()
+        return self
+
+    def _fit_reversible(self, Ca):
+        S, c = Ca + Ca.T, Ca.sum(axis=1)
+        x = 0.5 * S.sum(axis=1)
+        sweep = reversible_sweeper(S, c, self.device)
+        self.converged = False
+        while self.n_iter < self.max_iter and not self.converged:
+            n = min(self.steps_per_sync, self.max_iter - self.n_iter)
+            x, err = sweep(x, n)
+            hit = np.nonzero(err < self.tol)[0]
+            self.converged = hit.size > 0
+            self.n_iter += int(hit[0]) + 1 if self.converged else n          # sweeps until the first one below tol
+            if not np.all(np.isfinite(err)):
+                break
+        self.transition_matrix, self.stationary_distribution = reversible_transition_matrix(S, c, x)
+
+    def _need_fit(self):
+        if self.transition_matrix is None:
+            raise ValueError("MarkovStateModel: not fitted")
+
+    def eigenvalues(self):
+        """Eigenvalues of the transition matrix, largest first: real, from the symmetric pi^(1/2) T pi^(-1/2) (eigvalsh), when
+        reversible; else by magnitude."""
+        self._need_fit()
+        T = self.transition_matrix
+        if self.reversible:
+            r = np.sqrt(self.stationary_distribution)
+            M = r[:, None] * T / r[None, :]
+            return np.linalg.eigvalsh(0.5 * (M + M.T))[::-1]
+        return np.sort(np.abs(np.linalg.eigvals(T)))[::-1]
+
+    def timescales(self, k=3):
+        """The k slowest implied timescales -lagtime / ln(lambda_i), i = 2 .. k + 1, in frames (float64 (k,)); NaN for an
+        eigenvalue <= 0 and where the active set has fewer than k + 1 states."""
+        lam = self.eigenvalues()[1:int(k) + 1]
+        out = np.full(int(k), np.nan)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[:lam.size] = np.where(lam > 0, -float(self.lagtime) / np.log(np.where(lam > 0, lam, 1.0)), np.nan)
+        return out
+
+    def log_likelihood(self):
+        """sum_ij C_ij ln T_ij over the active set (pairs without counts contribute 0)."""
+        self._need_fit()
+        Ca = self.count_matrix[np.ix_(self.active_set, self.active_set)]
+        m = Ca > 0
+        with np.errstate(divide="ignore"):
+            return float(np.sum(Ca[m] * np.log(self.transition_matrix[m])))
+
+
+def implied_timescales(labels, lagtimes, traj_lengths=None, n_states=None, k=3, reversible=True, *, tol=1e-12,
+                       max_iter=1_000_000, steps_per_sync=256, device="cuda:0"):
+    """The k slowest implied timescales (frames) of a MarkovStateModel at every lag time of `lagtimes` -> float64
+    (n_lags, k).  The count matrices of up to 8 lag times come from one pass over the labels."""
+    dev = torch.device(device)
+    lab = torch.as_tensor(labels).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    lengths = _check_lengths(traj_lengths, int(lab.numel()))
+    lagtimes = [int(v) for v in lagtimes]
+    if n_states is None:
+        n_states = int(lab.max()) + 1 if lab.numel() else 0
+    if not 1 <= int(n_states) <= MSM_MAX_STATES:
+        raise ValueError(f"implied_timescales: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+    out = np.full((len(lagtimes), int(k)), np.nan)
+    for l0 in range(0, len(lagtimes), binding.MSM_MAX_LAGS):
+        group = lagtimes[l0:l0 + binding.MSM_MAX_LAGS]
+        counts = binding.micro_transition_counts(lab, lengths, group, int(n_states)).cpu().numpy()
+        for i, lag in enumerate(group):
+            m = MarkovStateModel(lag, reversible, tol, max_iter, steps_per_sync, device=dev).fit_counts(counts[i])
+            out[l0 + i] = m.timescales(k)
+    return out
+
+
+class MsmEvaluator:
+    """Do the sampled trajectories relax like the reference's?  Frames -> TIC projection (`tica`: a TicEvaluator, a TICA, a
+    saved reference or a (mean, coeff) pair, at most 8 components) -> n_microstates k-means microstates -> a reversible
+    MarkovStateModel at `lagtime` (frames).  The microstates are `centers` (K, k) when given, else fitted on the
+    reference's projection (ref_data: MD frames (m, N, 3) in Angstrom, trajectories of ref_traj_lengths), else on the first
+    samples eval() sees; both ensembles are discretised on the same centres.
+
+    eval(xyz, traj_lengths=None) -- None: ONE trajectory -- returns a dict:
+      timescales           list of the n_timescales slowest implied timescales, in units of frame_time (NaN where undefined)
+      n_active             states in the largest strongly connected set
+      active_count_share   share of the transition counts that stay inside it
+      converged            1.0 when the estimator met its tolerance, else 0.0
+      samples_nonfinite    frames left out (a non-finite projection)
+    and with ref_data the same keys with the suffix _ref, log10_timescale_ratio (list: samples over reference, NaN unless
+    both are positive and finite) and stationary_js, js_divergence of the two stationary distributions over the union of
+    the two active sets (zero outside one's own).  The models stay on .models under "samples" / "refs".  Without the HIP
+    library: DffLibraryError."""
+
+    KEYS = ("timescales", "n_active", "active_count_share", "converged", "samples_nonfinite")
+
+    def __init__(self, mol_name, tica, n_microstates=200, lagtime=None, n_timescales=3, frame_time=1.0, ref_data=None,
+                 ref_traj_lengths=None, centers=None, seed=0, *, device="cuda:0"):
+        if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
+            raise ValueError("MsmEvaluator: lagtime must be an integer >= 1 (frames)")
+        self.lagtime = int(lagtime)
+        self.n_microstates = int(n_microstates)
+        if not 1 <= self.n_microstates <= MSM_MAX_STATES:
+            raise ValueError(f"MsmEvaluator: n_microstates must be 1..{MSM_MAX_STATES}")
+        self.n_timescales = int(n_timescales)
+        if self.n_timescales < 1:
+            raise ValueError("MsmEvaluator: n_timescales must be >= 1")
+        self.frame_time = float(frame_time)
+        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
+            raise ValueError("MsmEvaluator: frame_time must be finite and > 0")
+        self.mol_name, self.seed = mol_name, int(seed)
+        self.device = torch.device(device)
+        self.mean, self.coeff = _tica_arrays(tica)
+        if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],) or not 1 <= self.coeff.shape[1] <= TICA_MAX_DIM:
+            raise ValueError(f"MsmEvaluator: mean must be (F,) and coeff (F, k), k <= {TICA_MAX_DIM}")
+        self.centers = None
+        if centers is not None:
+            c = np.array(centers, np.float64)
+            if c.ndim != 2 or c.shape != (self.n_microstates, self.coeff.shape[1]) or not np.all(np.isfinite(c)):
+                raise ValueError(f"MsmEvaluator: centers must be finite and ({self.n_microstates}, {self.coeff.shape[1]})")
+            self.centers = c
+        binding.load_library()
+        self.kmeans, self.models, self.labels = None, {}, {}
+        self.ref_result = None
+        if ref_data is not None:
+            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+                ref_data = ref_data[:][0]
+            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+
+    def project(self, x):
+        return binding.struct_tic(x, self.mean, self.coeff)
+
+    def _analyse(self, xyz, traj_lengths, name):
+        x = _frames(xyz, self.device)
+        lengths = _check_lengths(traj_lengths, len(x))
+        proj = self.project(x)
+        if self.centers is None:
+            self.kmeans = MicrostateKMeans(self.n_microstates, seed=self.seed, device=self.device).fit(proj)
+            self.centers = self.kmeans.cluster_centers
+        labels = binding.micro_kmeans_step(proj, self.centers, accumulate=False)["labels"]
+        model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+        self.models[name], self.labels[name] = model, labels.cpu().numpy()
+        return self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()))
+
+    @staticmethod
+    def summarize(model, n_timescales=3, frame_time=1.0, samples_nonfinite=0):
+        """eval()'s dict from a fitted MarkovStateModel: numpy only."""
+        return {"timescales": [float(v) * frame_time for v in model.timescales(n_timescales)],
+                "n_active": float(len(model.active_set)), "active_count_share": float(model.active_count_share),
+                "converged": float(bool(model.converged)), "samples_nonfinite": float(samples_nonfinite)}
+
+    @staticmethod
+    def stationary_js(model_a, model_b):
+        """js_divergence of two stationary distributions over the union of the two active sets, zero outside one's own."""
+        union = np.union1d(model_a.active_set, model_b.active_set)
+        p = np.zeros((2, len(union)))
+        for row, m in zip(p, (model_a, model_b)):
+            row[np.searchsorted(union, m.active_set)] = m.stationary_distribution
+        return float(js_divergence(p[0], p[1]))
+
+    def eval(self, xyz, traj_lengths=None):
+        res = self._analyse(xyz, traj_lengths, "samples")
+        if self.ref_result is not None:
+            ref = self.ref_result
+            res.update({k + "_ref": v for k, v in ref.items()})
+
+            def ratio(a, b):
+                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
+                return float(np.log10(a / b)) if ok else float("nan")
+            res["log10_timescale_ratio"] = [ratio(a, b) for a, b in zip(res["timescales"], ref["timescales"])]
+            res["stationary_js"] = self.stationary_js(self.models["samples"], self.models["refs"])
+        return res
