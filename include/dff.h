@@ -632,10 +632,49 @@ long long dff_msm_workspace_bytes(int K);
 int dff_msm_reversible_steps(int device, const double* sym_dev, const double* rowc_dev, int K, double* x_dev, int n_steps,
                              double* err_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* For benchmarks, process-wide: which kernel runs the sweeps.  0 = by K (the default), 1 = one launch per sweep,
- * 2 = one workgroup that loops over all sweeps.  The results are the same bits either way. */
+ * 2 = one workgroup that loops over all sweeps (per problem in dff_msm_reversible_steps_batched, which the knob forces
+ * too).  The results are the same bits either way. */
 int dff_debug_msm_driver(int driver);
 /* Host only: the driver a call with K states would take now, 1 or 2 as above; -1 on a bad K. */
 int dff_msm_driver_for(int K);
+
+/* ---- Bootstrap error bars for the models above: the count matrices of B weighted resamples in one pass over the labels,
+ * and the estimator's sweeps on B problems per launch (csrc/dff_msm_batch.hip; evaluate.py: bootstrap_msm) ----
+ * The conventions of the block above hold: device pointers, `stream` only, no read-back, no synchronisation, refusals on the
+ * host before any device call, no floating-point atomics, no workgroup waits on another, bit-identical from call to call
+ * and independent of the workspace's prior contents.  Host tables reach the device as kernel arguments. */
+/* Bytes of device workspace the call below needs (the trajectory and unit start tables); -1 on bad arguments. */
+long long dff_micro_resampled_counts_workspace_bytes(int n_traj, int n_units);
+/* counts_dev[b][i][j] = sum of weights_dev[b][unit(t)] over every frame t with labels[t] = i, labels[t + lag] = j, t and
+ * t + lag in the same trajectory and both labels in 0 .. K - 1.  labels_dev, n, lengths_host, n_traj as
+ * dff_micro_transition_counts; unit_lengths_host (n_units) are the resampling units, back to back, summing to n (they
+ * partition the FRAMES and need not coincide with trajectories: a pair belongs to the unit of its first frame, so no pair
+ * is lost and with all weights 1 every slice is dff_micro_transition_counts' matrix); weights_dev (B, n_units) uint32 is
+ * the multiplicity of unit u in resample b; counts_dev (B, K, K) is zeroed by the call (also at n == 0).
+ * 1 <= K <= DFF_MSM_MAXK, 1 <= B <= 4096, B K^2 <= 2^28, 1 <= n_units <= 2^20, n <= 2^31 (no 64-bit sum can overflow),
+ * lag >= 1.  64-bit integer atomics on global memory, equal (i, j, unit) aggregated inside a wave first, one atomic per
+ * aggregate and resample with a non-zero weight: exact, the same from call to call.  workspace_dev 8-byte aligned. */
+int dff_micro_resampled_counts(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj,
+                               const long long* unit_lengths_host, int n_units, int lag, int K, const uint32_t* weights_dev,
+                               int B, uint64_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Bytes of device workspace the call below needs (two vectors of B Kmax doubles and B descriptors); -1 on bad arguments. */
+long long dff_msm_batched_workspace_bytes(int B, int Kmax);
+/* dff_msm_reversible_steps on B problems at once.  Problem b has 1 <= K_b = ks_host[b] <= Kmax <= DFF_MSM_MAXK states, its S
+ * a COMPACT (K_b, K_b) row-major matrix at sym_dev + b Kmax^2, its c at rowc_dev + b Kmax and its x at x_dev + b Kmax; what
+ * lies beyond K_b in a slot is never read or written.  For every problem that is not skipped, x and err_dev[:, b] after the
+ * call are bit-identical to dff_msm_reversible_steps(sym_b, rowc_b, K_b, x_b, n_steps, err_b): the same order of every row
+ * sum, the same select for S_ij == 0, the same NaN rules, confined to the problem they arise in.  skip_host (B, may be
+ * NULL): a problem with a non-zero byte keeps its x and gets err_dev[:, b] = 0.  err_dev (n_steps, B), may be NULL.
+ * One launch per sweep covers the rows of all live problems, or one looping workgroup per live problem runs all sweeps:
+ * the latter where dff_msm_reversible_steps would loop for the largest live problem, and wherever there are enough live
+ * problems for it (measured: dff_msm_batched_driver_for).  dff_debug_msm_driver forces either; both give the same bits.  1 <= B <= 4096, n_steps >= 0 (0 leaves everything alone), workspace_dev 8-byte
+ * aligned, contents irrelevant. */
+int dff_msm_reversible_steps_batched(int device, const double* sym_dev, const double* rowc_dev, const int32_t* ks_host,
+                                     const uint8_t* skip_host, int B, int Kmax, double* x_dev, int n_steps, double* err_dev,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Host only: the driver a batched call with B live problems, the largest of Kmax states, would take now: 1 = one launch per
+ * sweep, 2 = one looping workgroup per problem; -1 on bad arguments. */
+int dff_msm_batched_driver_for(int B, int Kmax);
 
 const char* dff_last_error(void);
 const char* dff_version(void);

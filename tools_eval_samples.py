@@ -13,7 +13,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
                                  [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
                                  [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
-                                 [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]]
+                                 [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
+                                  [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
@@ -61,6 +62,9 @@ microstates in the space of MOL's TICA model, sliding-window counts at --msm-lag
 its slowest implied timescales in units of --frame-time.  With HELDOUT.pt (as for --kinetics) the microstates are fitted on
 it, and the same numbers for it come with the suffix _ref, with log10_timescale_ratio and stationary_js.  --msm-lagtimes
 a,b,c adds "implied_timescales": the timescales (frames x --frame-time) of the samples' model at each of these lag times.
+--msm-bootstrap B adds bootstrap error bars (B resamples of the trajectories, or of blocks of --msm-block-frames frames):
+timescales_lo / _hi at --msm-confidence (0.95), timescales_std, bootstrap_failed, with HELDOUT.pt their _ref counterparts and
+log10_timescale_ratio_lo / _hi, and "timescales_lo" / "timescales_hi" in "implied_timescales".
 """
 import argparse
 import json
@@ -267,21 +271,62 @@ def msm_arguments(a):
     return a.msm_states, a.msm_lag
 
 
+def msm_bootstrap(text):
+    try:
+        v = int(text)
+    except ValueError:
+        v = 0
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"expected a number of resamples >= 1, got {text!r}")
+    return v
+
+
+def msm_confidence(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = 0.0
+    if not 0 < v < 1:
+        raise argparse.ArgumentTypeError(f"expected a confidence level in (0, 1), got {text!r}")
+    return v
+
+
+def msm_bootstrap_arguments(a):
+    """keyword arguments of MsmEvaluator for --msm-bootstrap; its options are refused without it, and it without --msm"""
+    if a.msm_bootstrap is None:
+        if a.msm_block_frames is not None or a.msm_confidence is not None:
+            raise SystemExit("--msm-block-frames and --msm-confidence need --msm-bootstrap B")
+        return {}
+    if a.msm is None:
+        raise SystemExit("--msm-bootstrap needs --msm")
+    return {"n_bootstrap": a.msm_bootstrap, "block_frames": a.msm_block_frames,
+            "confidence": 0.95 if a.msm_confidence is None else a.msm_confidence}
+
+
 def msm(a, x):
     K, lag = msm_arguments(a)
+    boot = msm_bootstrap_arguments(a)
     ref, ref_lengths = ordered_frames(a.msm) if a.msm else (None, None)
     stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
     tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
     ev = evaluate.MsmEvaluator(a.mol.lower(), tica, n_microstates=K, lagtime=lag, frame_time=a.frame_time, ref_data=ref,
-                               ref_traj_lengths=ref_lengths, device=a.device)
+                               ref_traj_lengths=ref_lengths, device=a.device, **boot)
     clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
     lengths = traj_lengths(a, len(x))
     res = {k: ([clean(u) for u in v] if isinstance(v, list) else clean(v)) for k, v in ev.eval(x, lengths).items()}
     res.update({"n_microstates": K, "lagtime": lag, "frame_time": a.frame_time})
-    if a.msm_lagtimes:
+    if boot:
+        res.update({"n_bootstrap": boot["n_bootstrap"], "block_frames": boot["block_frames"], "confidence": boot["confidence"]})
+    table = lambda m: [[clean(v * a.frame_time) for v in row] for row in m]     # noqa: E731
+    if a.msm_lagtimes and boot:
+        its, lo, hi = evaluate.implied_timescales_bootstrap(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales,
+                                                            n_resamples=boot["n_bootstrap"], block_frames=boot["block_frames"],
+                                                            confidence=boot["confidence"], device=a.device)
+        res["implied_timescales"] = {"lagtimes": a.msm_lagtimes, "timescales": table(its), "timescales_lo": table(lo),
+                                     "timescales_hi": table(hi)}
+    elif a.msm_lagtimes:
         its = evaluate.implied_timescales(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales, device=a.device)
-        res["implied_timescales"] = {"lagtimes": a.msm_lagtimes,
-                                     "timescales": [[clean(v * a.frame_time) for v in row] for row in its]}
+        res["implied_timescales"] = {"lagtimes": a.msm_lagtimes, "timescales": table(its)}
     return res
 
 
@@ -349,6 +394,12 @@ def build_parser():
     ap.add_argument("--msm-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --msm)")
     ap.add_argument("--msm-lagtimes", type=msm_lagtimes, default=None, metavar="a,b,c",
                     help="also the implied timescales at these lag times in frames (with --msm)")
+    ap.add_argument("--msm-bootstrap", type=msm_bootstrap, default=None, metavar="B",
+                    help="bootstrap error bars of the implied timescales from B resamples (with --msm)")
+    ap.add_argument("--msm-block-frames", type=msm_lag, default=None, metavar="F",
+                    help="resample blocks of F frames instead of whole trajectories (with --msm-bootstrap)")
+    ap.add_argument("--msm-confidence", type=msm_confidence, default=None, metavar="C",
+                    help="confidence level of the percentile intervals, default 0.95 (with --msm-bootstrap)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -370,6 +421,7 @@ def main():
         relaxation_max_lag(a)
     if a.msm is not None:
         msm_arguments(a)
+    msm_bootstrap_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None

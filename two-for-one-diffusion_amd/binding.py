@@ -128,6 +128,13 @@ SYMBOLS = {
     "dff_msm_reversible_steps": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "dff_debug_msm_driver": (C.c_int, [C.c_int]),
     "dff_msm_driver_for": (C.c_int, [C.c_int]),
+    "dff_micro_resampled_counts_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_micro_resampled_counts": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int,
+                                             _P, _P, C.c_size_t, _P]),
+    "dff_msm_batched_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_msm_reversible_steps_batched": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t,
+                                                   _P]),
+    "dff_msm_batched_driver_for": (C.c_int, [C.c_int, C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1078,4 +1085,91 @@ def msm_driver_for(K: int) -> int:
     r = int(lib.dff_msm_driver_for(int(K)))
     if r < 0:
         _check(lib, 1, "dff_msm_driver_for")
+    return r
+
+
+# ---- bootstrap of a Markov state model (dff_micro_resampled_counts, dff_msm_reversible_steps_batched) ----
+MSM_MAX_BATCH = 4096
+
+
+def micro_resampled_counts_workspace_bytes(n_traj: int, n_units: int) -> int:
+    return _workspace_bytes("dff_micro_resampled_counts_workspace_bytes", int(n_traj), int(n_units))
+
+
+def micro_resampled_counts(labels, lengths, unit_lengths, lag: int, K: int, weights, workspace=None):
+    """The count matrices of B weighted resamples in one pass over the labels (dff_micro_resampled_counts): labels int32
+    CUDA (n,), lengths the trajectories, unit_lengths the resampling units (both host, each summing to n), weights uint32
+    CUDA (B, n_units) -> uint64 CUDA tensor (B, K, K).  Exact.  `workspace` is a uint8 CUDA tensor (allocated here when
+    None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
+            and labels.is_contiguous() and labels.dim() == 1):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
+    ln, un = _lengths(lengths), _lengths(unit_lengths)
+    if not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype == torch.uint32 and weights.is_contiguous()
+            and weights.dim() == 2 and weights.shape[1] == un.size and weights.device == labels.device):
+        raise ValueError("weights must be a contiguous uint32 CUDA tensor of shape (B, n_units) on the labels' device")
+    K, B = int(K), int(weights.shape[0])
+    need = micro_resampled_counts_workspace_bytes(int(ln.size), int(un.size))
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=labels.device)
+    Ka = min(max(K, 1), MSM_MAX_STATES)                          # what is allocated when K or B will be refused
+    Ba = min(max(B, 1), max((1 << 28) // (Ka * Ka), 1), MSM_MAX_BATCH)
+    out = torch.empty((Ba, Ka, Ka), dtype=torch.uint64, device=labels.device)
+    _check(lib, lib.dff_micro_resampled_counts(labels.device.index, _ptr(labels), int(labels.numel()),
+                                               ln.ctypes.data_as(C.c_void_p), int(ln.size), un.ctypes.data_as(C.c_void_p),
+                                               int(un.size), int(lag), K, _ptr(weights), B, _ptr(out), _ptr(workspace),
+                                               int(workspace.numel() * workspace.element_size()), _stream(labels)),
+           "dff_micro_resampled_counts")
+    return out
+
+
+def msm_batched_workspace_bytes(B: int, Kmax: int) -> int:
+    return _workspace_bytes("dff_msm_batched_workspace_bytes", int(B), int(Kmax))
+
+
+def msm_reversible_steps_batched(S, c, ks, x, n_steps: int, skip=None, workspace=None):
+    """msm_reversible_steps on B problems at once (dff_msm_reversible_steps_batched): S (B, Kmax, Kmax), c (B, Kmax) and
+    x (B, Kmax) contiguous float64 CUDA tensors, problem b a COMPACT (ks[b], ks[b]) matrix at the start of its slot of S and
+    the first ks[b] entries of its slots of c and x; ks (B,) host integers; skip (B,) host booleans or None.  x is updated
+    in place; returns the float64 CUDA tensor (n_steps, B) of the sweeps' err (0 for a skipped problem).  Bit for bit the
+    single call's x and err, problem by problem.  Nothing is read back."""
+    import torch
+    lib = load_library()
+
+    def ok(t, shape):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                and tuple(t.shape) == shape)
+    B, Kmax = (int(x.shape[0]), int(x.shape[1])) if isinstance(x, torch.Tensor) and x.dim() == 2 else (-1, -1)
+    if not (ok(x, (B, Kmax)) and ok(S, (B, Kmax, Kmax)) and ok(c, (B, Kmax)) and S.device == x.device and c.device == x.device):
+        raise ValueError("S (B, Kmax, Kmax), c (B, Kmax) and x (B, Kmax) must be contiguous float64 CUDA tensors on one device")
+    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+    if kh.size != B:
+        raise ValueError(f"ks must hold one state count per problem: {kh.size} for B = {B}")
+    sh = None
+    if skip is not None:
+        sh = np.ascontiguousarray(np.asarray(skip).reshape(-1) != 0).astype(np.uint8)
+        if sh.size != B:
+            raise ValueError(f"skip must hold one flag per problem: {sh.size} for B = {B}")
+    n_steps = int(n_steps)
+    need = msm_batched_workspace_bytes(B, Kmax)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    e = torch.empty((max(n_steps, 0), B), dtype=torch.float64, device=x.device)
+    _check(lib, lib.dff_msm_reversible_steps_batched(x.device.index, _ptr(S), _ptr(c), kh.ctypes.data_as(C.c_void_p),
+                                                     sh.ctypes.data_as(C.c_void_p) if sh is not None else None, B, Kmax,
+                                                     _ptr(x), n_steps, _ptr(e), _ptr(workspace),
+                                                     int(workspace.numel() * workspace.element_size()), _stream(x)),
+           "dff_msm_reversible_steps_batched")
+    return e
+
+
+def msm_batched_driver_for(B: int, Kmax: int) -> int:
+    """The driver msm_reversible_steps_batched would take now for B live problems, the largest of Kmax states: 1 = one launch
+    per sweep, 2 = one looping workgroup per problem."""
+    lib = load_library()
+    r = int(lib.dff_msm_batched_driver_for(int(B), int(Kmax)))
+    if r < 0:
+        _check(lib, 1, "dff_msm_batched_driver_for")
     return r

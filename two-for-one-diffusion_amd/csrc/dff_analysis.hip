@@ -1,8 +1,9 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* and their batched counterparts), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
+#include <vector>
 
 #include "dff_pwd.hip"
 #include "dff_struct.hip"
@@ -14,6 +15,7 @@
 #include "dff_kinetics.hip"
 #include "dff_autocorr.hip"
 #include "dff_msm.hip"
+#include "dff_msm_batch.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1066,6 +1068,153 @@ extern "C" int dff_msm_reversible_steps(int device, const double* sym, const dou
     for (int s = 0; s < n_steps; ++s)
         hipLaunchKernelGGL(dff_msm_sweep_kernel, dim3(grid), dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, K, x,
                            (const double*)q[s & 1], q[(s + 1) & 1], err ? (unsigned long long*)err + s : nullptr);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bootstrap of a Markov state model: resampled counts, batched estimator (dff_msm_batch.hip)
+// ---------------------------------------------------------------------------------------------
+// `cnt` 64-bit words of a host table into the workspace, as kernel arguments: nothing the stream could make the host wait for
+static int msmb_upload(hipStream_t stream, const long long* src, long long cnt, long long* dst) {
+    for (long long o = 0; o < cnt; o += DFF_MSMB_UPLOAD) {
+        MsmbWords w;
+        const int m = (int)(cnt - o < DFF_MSMB_UPLOAD ? cnt - o : DFF_MSMB_UPLOAD);
+        for (int i = 0; i < m; ++i) w.v[i] = src[o + i];
+        hipLaunchKernelGGL(dff_msmb_upload_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, w, m, dst + o);
+    }
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+static int msmb_check_batch(int B, const char* what, const char* noun) {
+    if (B < 1 || B > DFF_MSMB_MAXB) return fail(DFF_EINVAL, "%s: the number of %s must be 1..%d", what, noun, DFF_MSMB_MAXB);
+    return DFF_OK;
+}
+
+static int rc_check_units(int n_units, const char* what) {
+    if (n_units < 1 || n_units > DFF_RC_MAXUNITS)
+        return fail(DFF_EINVAL, "%s: the number of resampling units must be 1..%d", what, DFF_RC_MAXUNITS);
+    return DFF_OK;
+}
+
+extern "C" long long dff_micro_resampled_counts_workspace_bytes(int n_traj, int n_units) {
+    if (n_traj < 0) return fail(DFF_EINVAL, "micro_resampled_counts_workspace_bytes: negative trajectory count"), -1;
+    if (rc_check_units(n_units, "micro_resampled_counts_workspace_bytes")) return -1;
+    return ((long long)n_traj + 1 + (long long)n_units + 1) * (long long)sizeof(long long);   // trajectory starts | unit starts
+}
+
+extern "C" int dff_micro_resampled_counts(int device, const int32_t* labels, long long n, const long long* lengths,
+                                          int n_traj, const long long* unit_lengths, int n_units, int lag, int K,
+                                          const uint32_t* weights, int B, uint64_t* counts, void* workspace,
+                                          size_t workspace_bytes, void* stream_) {
+    const char* what = "micro_resampled_counts";
+    if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "%s: null labels / negative count", what);
+    if (n > (1LL << 31)) return fail(DFF_EINVAL, "%s: more than 2^31 frames", what);
+    int rc = micro_check_count(K, what, "states");
+    if (rc) return rc;
+    if ((rc = msmb_check_batch(B, what, "resamples"))) return rc;
+    if ((long long)B * K * K > DFF_RC_MAXCOUNTERS) return fail(DFF_EINVAL, "%s: B K^2 must not exceed 2^28 counters", what);
+    if ((rc = rc_check_units(n_units, what))) return rc;
+    if (lag < 1) return fail(DFF_EINVAL, "%s: lag time is %d, must be >= 1", what, lag);
+    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    if (!unit_lengths) return fail(DFF_EINVAL, "%s: null unit lengths", what);
+    long long total = 0;
+    for (int u = 0; u < n_units; ++u) {
+        if (unit_lengths[u] < 0) return fail(DFF_EINVAL, "%s: unit %d has negative length", what, u);
+        if (unit_lengths[u] > n - total) return fail(DFF_EINVAL, "%s: unit lengths sum to more than n = %lld", what, n);
+        total += unit_lengths[u];
+    }
+    if (total != n) return fail(DFF_EINVAL, "%s: unit lengths sum to %lld, not n = %lld", what, total, n);
+    if (!weights || !counts) return fail(DFF_EINVAL, "%s: null weights / counts", what);
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_micro_resampled_counts_workspace_bytes(n_traj, n_units), what)))
+        return rc;
+    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipMemsetAsync(counts, 0, (size_t)B * K * K * sizeof(uint64_t), stream));
+    if (n == 0) return DFF_OK;
+    std::vector<long long> starts((size_t)n_traj + 1 + n_units + 1);
+    long long* ts = starts.data();
+    long long* us = ts + n_traj + 1;
+    ts[0] = us[0] = 0;
+    for (int i = 0; i < n_traj; ++i) ts[i + 1] = ts[i] + lengths[i];
+    for (int u = 0; u < n_units; ++u) us[u + 1] = us[u] + unit_lengths[u];
+    if ((rc = msmb_upload(stream, ts, (long long)starts.size(), (long long*)workspace))) return rc;
+    const long long* tstart = (const long long*)workspace;
+    const long long wgs = (n + DFF_TC_THREADS - 1) / DFF_TC_THREADS;
+    hipLaunchKernelGGL(dff_micro_rc_kernel, dim3((unsigned)(wgs < 4 * DFF_TC_WGS ? wgs : 4 * DFF_TC_WGS)), dim3(DFF_TC_THREADS), 0,
+                       stream, labels, n, lag, K, tstart, n_traj, tstart + n_traj + 1, n_units, weights, B,
+                       (unsigned long long*)counts);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" long long dff_msm_batched_workspace_bytes(int B, int Kmax) {
+    if (msmb_check_batch(B, "msm_batched_workspace_bytes", "problems")) return -1;
+    if (micro_check_count(Kmax, "msm_batched_workspace_bytes", "states")) return -1;
+    return (2LL * B * Kmax + B) * (long long)sizeof(double);            // q ping | q pong | the live problems' descriptors
+}
+
+// The batched call's driver for n_live problems of up to kmax states.  One looping workgroup per problem pays no launch per
+// sweep but uses one CU per problem, so it wants enough problems to cover what the largest of them costs: measured
+//  it wins from 4 problems on at K = 64, from 8 at K = 128 and 256, from 16 at K = 512 and from 32 at
+// K = 1024; up to DFF_MSM_LOOP_MAXK states it is the single call's choice already.
+static int msmb_driver(int kmax, int n_live) {
+    const int driver = g_msm_driver.load();
+    if (driver) return driver;
+    if (kmax <= DFF_MSM_LOOP_MAXK) return 2;
+    return (32LL * n_live >= kmax && n_live >= (kmax >= 128 ? 8 : 4)) ? 2 : 1;
+}
+
+extern "C" int dff_msm_batched_driver_for(int B, int Kmax) {
+    if (msmb_check_batch(B, "msm_batched_driver_for", "problems")) return -1;
+    if (micro_check_count(Kmax, "msm_batched_driver_for", "states")) return -1;
+    return msmb_driver(Kmax, B);
+}
+
+extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, const double* rowc, const int32_t* ks,
+                                                const uint8_t* skip, int B, int Kmax, double* x, int n_steps, double* err,
+                                                void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "msm_reversible_steps_batched";
+    int rc = msmb_check_batch(B, what, "problems");
+    if (rc) return rc;
+    if ((rc = micro_check_count(Kmax, what, "states"))) return rc;
+    if (n_steps < 0) return fail(DFF_EINVAL, "%s: negative n_steps", what);
+    if (!sym || !rowc || !x || !ks) return fail(DFF_EINVAL, "%s: null matrices / row counts / x / state counts", what);
+    for (int b = 0; b < B; ++b)
+        if (ks[b] < 1 || ks[b] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, b, (int)ks[b], Kmax);
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_batched_workspace_bytes(B, Kmax), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if (n_steps == 0) return DFF_OK;
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (err) HIPCHK(hipMemsetAsync(err, 0, (size_t)n_steps * B * sizeof(double), stream));
+    std::vector<long long> live;
+    int kmax_live = 0;
+    for (int b = 0; b < B; ++b)
+        if (!skip || !skip[b]) {
+            live.push_back(((long long)b << DFF_MSMB_KBITS) | ks[b]);
+            if (ks[b] > kmax_live) kmax_live = ks[b];
+        }
+    if (live.empty()) return DFF_OK;
+    double* q[2] = {(double*)workspace, (double*)workspace + (size_t)B * Kmax};
+    long long* live_dev = (long long*)((double*)workspace + 2 * (size_t)B * Kmax);
+    if ((rc = msmb_upload(stream, live.data(), (long long)live.size(), live_dev))) return rc;
+    const unsigned n_live = (unsigned)live.size();
+    if (msmb_driver(kmax_live, (int)n_live) == 2) {
+        hipLaunchKernelGGL(dff_msmb_loop_kernel, dim3(n_live), dim3(DFF_MSM_LOOP_THREADS), (unsigned)(3 * kmax_live * sizeof(double)),
+                           stream, sym, rowc, Kmax, x, n_steps, (const long long*)live_dev, B, (unsigned long long*)err);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    }
+    hipLaunchKernelGGL(dff_msmb_init_kernel, dim3((unsigned)((kmax_live + 255) / 256), n_live), dim3(256), 0, stream, rowc,
+                       (const double*)x, Kmax, (const long long*)live_dev, q[0]);
+    const dim3 grid((unsigned)((kmax_live + DFF_MSM_THREADS / 64 - 1) / (DFF_MSM_THREADS / 64)), n_live);
+    for (int s = 0; s < n_steps; ++s)
+        hipLaunchKernelGGL(dff_msmb_sweep_kernel, grid, dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, Kmax, x,
+                           (const double*)q[s & 1], q[(s + 1) & 1], (const long long*)live_dev,
+                           err ? (unsigned long long*)err + (size_t)s * B : nullptr);
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

@@ -31,6 +31,7 @@
 //     has the largest pattern: one NaN row makes err NaN).
 #pragma once
 #include "dff_states.hip"   // state_nearest's rule, TransRuns, TransLags, last_le, wave_sum
+#include "dff_msm_rows.h"   // msm_q, msm_row, msm_finish: shared with dff_msm_batch.hip
 
 #define DFF_MICRO_CHUNK 1024       // points per workgroup: at K = 1024, d = 8 the largest power of two whose coordinates
                                     // (64 KB) + labels (4 KB) + accumulators (72 KB) fit in the 160 KB of LDS
@@ -274,28 +275,7 @@ __global__ __launch_bounds__(DFF_TC_THREADS) void dff_micro_tc_kernel(const int*
     }
 }
 
-// ---- the reversible estimator's fixed-point sweeps
-// q of a state from its row count and its x; NaN where the estimator is not defined (c <= 0, x <= 0, either NaN)
-__device__ __forceinline__ double msm_q(double c, double x) { return (c > 0.0 && x > 0.0) ? c / x : __builtin_nan(""); }
-
-// sum_j S_ij / (q_i + q_j) over one row, by one wave: lane l takes j = l, l + 64, ... in order, then the butterfly; a pair
-// with S_ij == 0 adds exactly +0.0, whatever its quotient.  The same bits in every lane.
-__device__ __forceinline__ double msm_row(const double* __restrict__ srow, const double* q, double qi, int K, int lane) {
-    double acc = 0.0;
-#pragma unroll 4
-    for (int j = lane; j < K; j += 64) {                            // loads first, no branch: the row is latency-bound
-        const double s = srow[j];
-        const double t = s / (qi + q[j]);
-        acc += (s != 0.0) ? t : 0.0;                                // +0.0 leaves acc's bits alone
-    }
-    return wave_sum(acc);
-}
-
-// the row's new x, its relative change into err (an integer max on the bit pattern: both non-negative or NaN)
-__device__ __forceinline__ void msm_finish(double xn, double xo, unsigned long long* err) {
-    if (err) atomicMax(err, (unsigned long long)__double_as_longlong(fabs(xn - xo) / xo));
-}
-
+// ---- the reversible estimator's fixed-point sweeps: msm_q, msm_row and msm_finish of dff_msm_rows.h
 __global__ void dff_msm_init_kernel(const double* __restrict__ rowc, const double* __restrict__ x, int K,
                                     double* __restrict__ q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

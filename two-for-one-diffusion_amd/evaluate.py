@@ -1862,7 +1862,7 @@ class RelaxationEvaluator:
 # restated from the literature -- k-means microstates, sliding-window counts, the largest strongly connected set, the
 # reversible maximum-likelihood estimator of Bowman et al. 2009 / Prinz et al. 2011 (algorithm 1, plain form) -- and tested
 # against a from-scratch fp64 oracle (tests/msm_oracle.py).
-# Out of scope: PCCA+ and other coarse-graining, mean first-passage times / transition-path theory, Bayesian error bars,
+# Out of scope: PCCA+ and other coarse-graining, mean first-passage times / transition-path theory, Bayesian posteriors (error bars: bootstrap_msm below),
 # Chapman-Kolmogorov tests, sparse count matrices.
 # =====================================================================================================
 MSM_MAX_STATES = binding.MSM_MAX_STATES
@@ -1949,6 +1949,49 @@ class MicrostateKMeans(KMeans):
         return binding.micro_kmeans_step(pts, self.cluster_centers, accumulate=False)["labels"]
 
 
+REACH_PIVOTS, REACH_STEPS = 8, 64
+
+
+def _reach(A, p, within):
+    """mask of the states of `within` that p reaches inside `within` (p included) by breadth-first array steps; None when the
+    search is deeper than REACH_STEPS"""
+    seen = np.zeros(len(A), bool)
+    seen[p] = True
+    front = np.array([p])
+    for _ in range(REACH_STEPS):
+        nxt = A[front].any(axis=0) & within & ~seen
+        if not nxt.any():
+            return seen
+        seen |= nxt
+        front = np.flatnonzero(nxt)
+    return None
+
+
+def _largest_by_reachability(A):
+    """largest_connected_set's answer for the boolean adjacency A where a few array searches settle it, else None.  The
+    component of the lowest state left is what it reaches and is reached from among the states left (a component never
+    straddles one already taken out); it goes on until the best component is at least as large as what is left, which also
+    settles ties for the lowest index.  Count matrices of metastable dynamics are one giant component plus a few lost states:
+    two or three searches of a handful of steps, where Tarjan's walk in Python visits every edge."""
+    K = len(A)
+    if K == 0:
+        return None
+    left, best, At = np.ones(K, bool), None, A.T
+    for _ in range(REACH_PIVOTS):
+        p = int(np.argmax(left))
+        fwd = _reach(A, p, left)
+        bwd = _reach(At, p, left) if fwd is not None else None
+        if bwd is None:
+            return None
+        comp = fwd & bwd
+        if best is None or comp.sum() > best.sum():
+            best = comp
+        left &= ~comp
+        if best.sum() >= left.sum():
+            return np.flatnonzero(best).astype(np.int64)
+    return None
+
+
 def largest_connected_set(counts):
     """Sorted indices (int64 array) of the largest strongly connected component of the directed graph with an edge i -> j
     wherever counts[i, j] > 0.  Largest by the number of states; among equals the component that holds the lowest index.
@@ -1957,6 +2000,9 @@ def largest_connected_set(counts):
     if c.ndim != 2 or c.shape[0] != c.shape[1]:
         raise ValueError("largest_connected_set: counts must be a square matrix")
     K = c.shape[0]
+    fast = _largest_by_reachability(c > 0)
+    if fast is not None:
+        return fast
     adj = [np.nonzero(row > 0)[0] for row in c]
     index = np.full(K, -1, np.int64)
     low = np.zeros(K, np.int64)
@@ -2161,6 +2207,248 @@ def implied_timescales(labels, lagtimes, traj_lengths=None, n_states=None, k=3, 
     return out
 
 
+# ---- bootstrap error bars: counts resampled over trajectories or blocks of them, the model re-estimated per resample ----
+# What the bootstrap does NOT cover: the discretisation is fixed (the centres are not refitted per resample), and blocks
+# shorter than the slowest relaxation are not independent, which understates the error (integrated_autocorr_time of a slow
+# observable is the guide for block_frames).
+MSM_MAX_BATCH = binding.MSM_MAX_BATCH
+
+
+def resampling_units(traj_lengths, block_frames=None):
+    """The lengths (int64 array) of the units a bootstrap resamples, back to back over the frames.  block_frames=None: the
+    trajectories themselves.  Otherwise every trajectory is cut into blocks of block_frames frames, a shorter last block
+    being a unit of its own; an empty trajectory gives no block."""
+    ln = np.asarray(traj_lengths, np.int64).reshape(-1)
+    if (ln < 0).any():
+        raise ValueError("resampling_units: negative trajectory length")
+    if block_frames is None:
+        return ln.copy()
+    bf = int(block_frames)
+    if bf != block_frames or bf < 1:
+        raise ValueError("resampling_units: block_frames must be an integer >= 1")
+    out = []
+    for n in ln.tolist():
+        out += [bf] * (n // bf) + ([n % bf] if n % bf else [])
+    return np.asarray(out, np.int64)
+
+
+def bootstrap_weights(n_units, n_resamples, seed):
+    """uint32 (n_resamples, n_units): how often unit u is drawn in resample b when n_units units are drawn with replacement.
+    Pinned: np.random.default_rng(seed).multinomial(n_units, np.full(n_units, 1 / n_units), size=n_resamples)."""
+    n_units, B = int(n_units), int(n_resamples)
+    if n_units < 1 or B < 1:
+        raise ValueError("bootstrap_weights: n_units and n_resamples must be >= 1")
+    return np.random.default_rng(seed).multinomial(n_units, np.full(n_units, 1 / n_units), size=B).astype(np.uint32)
+
+
+class _DeviceResampledCounts:
+    """labels on the device once; count(weights (b, n_units)) -> the b weighted count matrices, uint64 (b, K, K) on the host."""
+
+    def __init__(self, labels, lengths, unit_lengths, lag, K, device):
+        self.labels = torch.as_tensor(labels).reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+        self.lengths, self.units, self.lag, self.K = lengths, unit_lengths, int(lag), int(K)
+        self.ws = torch.empty(max(binding.micro_resampled_counts_workspace_bytes(len(lengths), len(unit_lengths)), 8),
+                              dtype=torch.uint8, device=device)
+
+    def __call__(self, weights):
+        w = torch.from_numpy(np.ascontiguousarray(weights, np.uint32)).to(self.labels.device)
+        out = binding.micro_resampled_counts(self.labels, self.lengths, self.units, self.lag, self.K, w, workspace=self.ws)
+        return out.cpu().numpy()
+
+
+def resampled_counter(labels, lengths, unit_lengths, lag, K, device):
+    """count(weights) -> (b, K, K) for weights (b, n_units): the weighted sliding-window counts of b resamples on the GPU
+    (dff_micro_resampled_counts)."""
+    return _DeviceResampledCounts(labels, lengths, unit_lengths, lag, K, device)
+
+
+class _DeviceBatchedSweeps:
+    """The problems' S and c on the device once; sweep(x, n, skip) runs n sweeps of every problem not skipped from the host
+    array x (B, Kmax) -> (x after them, err (n, B))."""
+
+    def __init__(self, S, c, ks, device):
+        self.S = torch.from_numpy(np.ascontiguousarray(S, np.float64)).to(device)
+        self.c = torch.from_numpy(np.ascontiguousarray(c, np.float64)).to(device)
+        self.ks = np.asarray(ks, np.int32)
+        self.ws = torch.empty(max(binding.msm_batched_workspace_bytes(len(self.ks), self.c.shape[1]), 8), dtype=torch.uint8,
+                              device=device)
+
+    def __call__(self, x, n, skip=None):
+        xd = torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(self.S.device)
+        err = binding.msm_reversible_steps_batched(self.S, self.c, self.ks, xd, n, skip=skip, workspace=self.ws)
+        return xd.cpu().numpy(), err.cpu().numpy()
+
+
+def batched_reversible_sweeper(S, c, ks, device):
+    """sweep(x, n, skip) -> (x', err (n, B)) for B problems: S (B, Kmax, Kmax) with problem b's COMPACT (ks[b], ks[b]) matrix
+    at the start of its slot (flat), c and x (B, Kmax) with its first ks[b] entries (dff_msm_reversible_steps_batched)."""
+    return _DeviceBatchedSweeps(S, c, ks, device)
+
+
+class MsmBootstrap:
+    """What bootstrap_msm returns.  timescales (B, k) in frames, NaN where undefined; stationary (B, K) on the full state
+    index, zero outside a resample's active set; n_active, active_count_share, converged, n_iter (B,); weights (B, n_units)
+    and unit_lengths as resampled; point: the MarkovStateModel of the unresampled counts."""
+
+    def __init__(self, timescales, stationary, n_active, active_count_share, converged, n_iter, weights, unit_lengths, point):
+        self.timescales, self.stationary, self.n_active = timescales, stationary, n_active
+        self.active_count_share, self.converged, self.n_iter = active_count_share, converged, n_iter
+        self.weights, self.unit_lengths, self.point = weights, unit_lengths, point
+
+    @property
+    def n_failed(self):
+        """Resamples that did not converge or have no k-th timescale."""
+        return int(np.sum(~self.converged | np.isnan(self.timescales[:, -1])))
+
+    def std(self):
+        """Standard deviation (ddof = 1) of each timescale over the resamples where it is finite -> (k,); NaN below two."""
+        return percentile_std(self.timescales)
+
+    def interval(self, confidence=0.95):
+        """The percentile interval of each timescale over the resamples where it is finite -> (lo, hi), each (k,)."""
+        return percentile_interval(self.timescales, confidence)
+
+
+def percentile_std(values):
+    out = np.full(values.shape[1], np.nan)
+    for j, col in enumerate(values.T):
+        col = col[np.isfinite(col)]
+        if col.size >= 2:
+            out[j] = col.std(ddof=1)
+    return out
+
+
+def percentile_interval(values, confidence=0.95):
+    """(lo, hi), each (k,): the (1 -+ confidence) / 2 percentiles of every column of values (B, k) over its finite entries."""
+    if not 0 < float(confidence) < 1:
+        raise ValueError("confidence must lie in (0, 1)")
+    lo, hi = np.full(values.shape[1], np.nan), np.full(values.shape[1], np.nan)
+    for j, col in enumerate(values.T):
+        col = col[np.isfinite(col)]
+        if col.size:
+            lo[j], hi[j] = np.percentile(col, [50 * (1 - confidence), 50 * (1 + confidence)])
+    return lo, hi
+
+
+def bootstrap_msm(labels, lagtime, traj_lengths=None, n_states=None, *, n_resamples=100, block_frames=None, seed=0,
+                  weights=None, k=3, tol=1e-12, max_iter=1_000_000, steps_per_sync=256, resample_batch=None,
+                  device="cuda:0"):
+    """Bootstrap of a reversible MarkovStateModel at `lagtime`: the units of resampling_units(traj_lengths, block_frames) are
+    drawn with replacement n_resamples times (bootstrap_weights(n_units, n_resamples, seed), or `weights` (B, n_units)), the
+    weighted counts of all resamples come from one pass over the labels and their estimators advance together, a problem
+    leaving the batch at its first sweep below tol.  Resample b equals
+    MarkovStateModel(lagtime, tol=tol, max_iter=max_iter, steps_per_sync=steps_per_sync).fit_counts(counts_b) bit for bit.
+    resample_batch bounds the resamples in flight (default: B K^2 counts and matrices under 1 GiB each) -> MsmBootstrap."""
+    dev = torch.device(device)
+    lab = torch.as_tensor(labels).reshape(-1)
+    n = int(lab.numel())
+    lengths = _check_lengths(traj_lengths, n)
+    if n_states is None:
+        n_states = int(lab.max()) + 1 if n else 0
+    K = int(n_states)
+    if not 1 <= K <= MSM_MAX_STATES:
+        raise ValueError(f"bootstrap_msm: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+    proto = MarkovStateModel(lagtime, True, tol, max_iter, steps_per_sync, device=dev)          # checks the settings
+    k = int(k)
+    if k < 1:
+        raise ValueError("bootstrap_msm: k must be >= 1")
+    units = resampling_units(lengths, block_frames)
+    if units.size < 1:
+        raise ValueError("bootstrap_msm: no resampling units (no frames)")
+    if weights is None:
+        w = bootstrap_weights(units.size, n_resamples, seed)
+    else:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[1] != units.size or w.shape[0] < 1 or (w < 0).any() or (w > 2 ** 32 - 1).any():
+            raise ValueError(f"bootstrap_msm: weights must be (B, {units.size}) multiplicities in 0 .. 2^32 - 1")
+        w = w.astype(np.uint32)
+    B = int(w.shape[0])
+    if resample_batch is None:
+        resample_batch = max(1, min(B, MSM_MAX_BATCH, (1 << 30) // (8 * K * K)))
+    rb = int(resample_batch)
+    if not 1 <= rb <= MSM_MAX_BATCH:
+        raise ValueError(f"bootstrap_msm: resample_batch must be 1..{MSM_MAX_BATCH}")
+    count = resampled_counter(lab, lengths, units, proto.lagtime, K, dev)
+
+    def model():
+        return MarkovStateModel(proto.lagtime, True, tol, max_iter, steps_per_sync, device=dev)
+    point = model().fit_counts(count(np.ones((1, units.size), np.uint32))[0])
+    ts = np.full((B, k), np.nan)
+    stationary = np.zeros((B, K))
+    n_active, share = np.zeros(B, np.int64), np.zeros(B)
+    converged, n_iter = np.zeros(B, bool), np.zeros(B, np.int64)
+    for b0 in range(0, B, rb):
+        counts = count(w[b0:b0 + rb])
+        models, prob = [], []                                        # prob: (model, S, c) of the resamples that iterate
+        for Cb in counts:
+            m = model()
+            C = np.array(Cb, np.float64)
+            m.count_matrix, m.active_set = C, largest_connected_set(C)
+            Ca = C[np.ix_(m.active_set, m.active_set)]
+            total = C.sum()
+            m.active_count_share = float(Ca.sum() / total) if total > 0 else 0.0
+            m.n_iter, m.converged = 0, True
+            if len(m.active_set) == 1:
+                m.transition_matrix, m.stationary_distribution = np.ones((1, 1)), np.ones(1)
+            else:
+                m.converged = False
+                prob.append((m, Ca + Ca.T, Ca.sum(axis=1)))
+            models.append(m)
+        if prob:
+            _sweep_batch(prob, batched_reversible_sweeper, dev, tol, max_iter, steps_per_sync)
+        for i, m in enumerate(models):
+            b = b0 + i
+            ts[b] = m.timescales(k)
+            stationary[b, m.active_set] = m.stationary_distribution
+            n_active[b], share[b], converged[b], n_iter[b] = len(m.active_set), m.active_count_share, m.converged, m.n_iter
+    return MsmBootstrap(ts, stationary, n_active, share, converged, n_iter, w, units, point)
+
+
+def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
+    """MarkovStateModel._fit_reversible on every (model, S, c) of prob at once: the same start, the same batches of sweeps,
+    the same stopping rule per problem; a problem is skipped from the batch after the one it stops in."""
+    P = len(prob)
+    ks = np.array([len(c) for _, _, c in prob], np.int32)
+    Kmax = int(ks.max())
+    S_all, c_all, x = np.zeros((P, Kmax * Kmax)), np.zeros((P, Kmax)), np.zeros((P, Kmax))
+    for p, (_, S, c) in enumerate(prob):
+        S_all[p, :ks[p] * ks[p]] = S.reshape(-1)
+        c_all[p, :ks[p]] = c
+        x[p, :ks[p]] = 0.5 * S.sum(axis=1)
+    sweep = sweeper(S_all.reshape(P, Kmax, Kmax), c_all, ks, device)
+    live = np.ones(P, bool)
+    done = 0                                                         # sweeps every live problem has behind it
+    while done < max_iter and live.any():
+        n = min(steps_per_sync, max_iter - done)
+        x, err = sweep(x, n, ~live)
+        done += n
+        for p in np.nonzero(live)[0]:
+            m = prob[p][0]
+            hit = np.nonzero(err[:, p] < tol)[0]
+            m.converged = hit.size > 0
+            m.n_iter += int(hit[0]) + 1 if m.converged else n
+            if m.converged or not np.all(np.isfinite(err[:, p])):
+                live[p] = False
+    for p, (m, S, c) in enumerate(prob):
+        m.transition_matrix, m.stationary_distribution = reversible_transition_matrix(S, c, x[p, :ks[p]])
+
+
+def implied_timescales_bootstrap(labels, lagtimes, traj_lengths=None, n_states=None, k=3, *, n_resamples=100,
+                                 block_frames=None, seed=0, confidence=0.95, tol=1e-12, max_iter=1_000_000,
+                                 steps_per_sync=256, resample_batch=None, device="cuda:0"):
+    """implied_timescales with error bars: (point, lo, hi), each float64 (n_lags, k) in frames -- the timescales of the
+    unresampled model at every lag time and the percentile interval of bootstrap_msm over the same draws at each."""
+    lagtimes = [int(v) for v in lagtimes]
+    point, lo, hi = (np.full((len(lagtimes), int(k)), np.nan) for _ in range(3))
+    for i, lag in enumerate(lagtimes):
+        bs = bootstrap_msm(labels, lag, traj_lengths, n_states, n_resamples=n_resamples, block_frames=block_frames, seed=seed,
+                           k=k, tol=tol, max_iter=max_iter, steps_per_sync=steps_per_sync, resample_batch=resample_batch,
+                           device=device)
+        point[i] = bs.point.timescales(k)
+        lo[i], hi[i] = bs.interval(confidence)
+    return point, lo, hi
+
+
 class MsmEvaluator:
     """Do the sampled trajectories relax like the reference's?  Frames -> TIC projection (`tica`: a TicEvaluator, a TICA, a
     saved reference or a (mean, coeff) pair, at most 8 components) -> n_microstates k-means microstates -> a reversible
@@ -2177,14 +2465,28 @@ class MsmEvaluator:
     and with ref_data the same keys with the suffix _ref, log10_timescale_ratio (list: samples over reference, NaN unless
     both are positive and finite) and stationary_js, js_divergence of the two stationary distributions over the union of
     the two active sets (zero outside one's own).  The models stay on .models under "samples" / "refs".  Without the HIP
-    library: DffLibraryError."""
+    library: DffLibraryError.
+
+    n_bootstrap > 0 adds error bars from bootstrap_msm (units: the trajectories, or blocks of block_frames frames):
+    timescales_lo / timescales_hi (the percentile interval at `confidence`), timescales_std and bootstrap_failed, with
+    ref_data also their _ref counterparts and log10_timescale_ratio_lo / _hi, percentiles of the ratio of resample b of
+    the samples to resample b of the reference (seeds bootstrap_seed and bootstrap_seed + 1: independent draws).  The
+    discretisation is fixed: the centres are not refitted per resample.  The bootstraps stay on .bootstraps."""
 
     KEYS = ("timescales", "n_active", "active_count_share", "converged", "samples_nonfinite")
 
     def __init__(self, mol_name, tica, n_microstates=200, lagtime=None, n_timescales=3, frame_time=1.0, ref_data=None,
-                 ref_traj_lengths=None, centers=None, seed=0, *, device="cuda:0"):
+                 ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None, confidence=0.95,
+                 bootstrap_seed=0, device="cuda:0"):
         if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
             raise ValueError("MsmEvaluator: lagtime must be an integer >= 1 (frames)")
+        self.n_bootstrap, self.block_frames = int(n_bootstrap), block_frames
+        self.confidence, self.bootstrap_seed = float(confidence), int(bootstrap_seed)
+        if self.n_bootstrap < 0 or not 0 < self.confidence < 1:
+            raise ValueError("MsmEvaluator: n_bootstrap must be >= 0 and confidence in (0, 1)")
+        if block_frames is not None and (int(block_frames) != block_frames or int(block_frames) < 1):
+            raise ValueError("MsmEvaluator: block_frames must be an integer >= 1")
+        self.bootstraps = {}
         self.lagtime = int(lagtime)
         self.n_microstates = int(n_microstates)
         if not 1 <= self.n_microstates <= MSM_MAX_STATES:
@@ -2225,9 +2527,23 @@ class MsmEvaluator:
             self.kmeans = MicrostateKMeans(self.n_microstates, seed=self.seed, device=self.device).fit(proj)
             self.centers = self.kmeans.cluster_centers
         labels = binding.micro_kmeans_step(proj, self.centers, accumulate=False)["labels"]
-        model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+        if self.n_bootstrap > 0:                                    # refs and samples draw independently: another seed
+            bs = bootstrap_msm(labels, self.lagtime, lengths, self.n_microstates, n_resamples=self.n_bootstrap,
+                               block_frames=self.block_frames, seed=self.bootstrap_seed + (name == "refs"),
+                               k=self.n_timescales, device=self.device)
+            self.bootstraps[name] = bs
+            model = bs.point
+        else:
+            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
         self.models[name], self.labels[name] = model, labels.cpu().numpy()
-        return self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()))
+        res = self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()))
+        if self.n_bootstrap > 0:
+            lo, hi = bs.interval(self.confidence)
+            res.update({"timescales_lo": [float(v) * self.frame_time for v in lo],
+                        "timescales_hi": [float(v) * self.frame_time for v in hi],
+                        "timescales_std": [float(v) * self.frame_time for v in bs.std()],
+                        "bootstrap_failed": float(bs.n_failed)})
+        return res
 
     @staticmethod
     def summarize(model, n_timescales=3, frame_time=1.0, samples_nonfinite=0):
@@ -2256,4 +2572,10 @@ class MsmEvaluator:
                 return float(np.log10(a / b)) if ok else float("nan")
             res["log10_timescale_ratio"] = [ratio(a, b) for a, b in zip(res["timescales"], ref["timescales"])]
             res["stationary_js"] = self.stationary_js(self.models["samples"], self.models["refs"])
+            if self.n_bootstrap > 0:                                 # resample b of the samples over resample b of the reference
+                a, b = self.bootstraps["samples"].timescales, self.bootstraps["refs"].timescales
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    r = np.where((a > 0) & (b > 0), np.log10(a / b), np.nan)
+                lo, hi = percentile_interval(r, self.confidence)
+                res["log10_timescale_ratio_lo"], res["log10_timescale_ratio_hi"] = [float(v) for v in lo], [float(v) for v in hi]
         return res
