@@ -27,6 +27,13 @@ CPU restatements of the reference's sampling hot path (microsoft/two-for-one-dif
   transition counts (deeptime's documented semantics).
 * ``frames``          -- the seeded input generators of the analysis tests (rotations, walks,
   needles, chains, Ornstein-Uhlenbeck trajectories, blobs, labels).
+* ``cluster``         -- the neighbour bit-matrix and the gromos clustering from float64 pair RMSDs.
+* ``kinetics``        -- native-contact Q, core states and label runs by plain loops.
+* ``autocorr``        -- lagged sums and autocorrelation estimates by a loop over trajectories and lags.
+* ``msm``             -- Markov state models from scratch in float64: nearest centre, transition counts, the largest
+  connected set, the reversible estimator's sweeps.
+* ``msm_bootstrap``   -- the bootstrap of ``msm``: weighted counts pair by pair, the pipeline per resample, and the numpy
+  stand-ins the host tests put behind the device seams.
 
 The analysis modules need numpy and torch-CPU only and never import ``dff_amd``.
 

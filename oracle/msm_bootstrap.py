@@ -1,11 +1,11 @@
 """From-scratch numpy oracle of the Markov-state-model bootstrap (csrc/dff_msm_batch.hip, evaluate.bootstrap_msm): weighted
 sliding-window counts by explicit loops over the pairs, the resampling units and weights, and the bootstrap pipeline on top
-of the estimator of tests/msm_oracle.py.  Nothing here is taken from the code under test.  Also the numpy stand-ins that
+of the estimator of oracle/msm.py.  Nothing here is taken from the code under test.  Also the numpy stand-ins that
 host tests put behind evaluate.resampled_counter / evaluate.batched_reversible_sweeper, and the two-state chain of the
 calibration test."""
 import numpy as np
 
-import msm_oracle as oracle
+from oracle import msm as oracle
 
 
 # ---------------------------------------------------------------- units, weights, counts
@@ -46,7 +46,7 @@ def weighted_counts(labels, lengths, unit_lengths, lag, K, w):
 
 # ---------------------------------------------------------------- one resample: counts -> model
 def fit_counts(C, lag, k, tol=1e-12, max_iter=1_000_000, steps_per_sync=256):
-    """The estimator of msm_oracle on the largest connected set of C, swept in batches of steps_per_sync and stopped as
+    """The estimator of oracle.msm on the largest connected set of C, swept in batches of steps_per_sync and stopped as
     evaluate.MarkovStateModel documents it: converged at the first sweep whose err is below tol, n_iter the sweeps up to
     and including it, x the vector after the whole batch.  -> dict."""
     C = np.asarray(C, np.float64)

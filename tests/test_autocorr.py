@@ -1,4 +1,4 @@
-"""dff_autocorr on the GPU against the naive numpy oracle of tests/autocorr_oracle.py, and the relaxation analysis on top of it.
+"""dff_autocorr on the GPU against the naive numpy oracle of oracle/autocorr.py, and the relaxation analysis on top of it.
 
 The kernel's constants (csrc/dff_autocorr.hip): a TILE of 512 start frames per workgroup pass, 128 per wave; a lag CHUNK of 512
 lags per workgroup, 8 consecutive lags per lane; the sizes below sit around both.
@@ -20,8 +20,8 @@ import numpy as np
 import pytest
 import torch
 
-from autocorr_oracle import Acf, lagged_sums, usable_mean
-from kinetics_oracle import native_q, scripted_frames
+from oracle.autocorr import Acf, lagged_sums, usable_mean
+from oracle.kinetics import native_q, scripted_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)
 

@@ -14,7 +14,7 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
-from autocorr_oracle import Acf, estimate, lagged_sums
+from oracle.autocorr import Acf, estimate, lagged_sums
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_autocorr_workspace_bytes", "dff_autocorr")

@@ -4,7 +4,7 @@ What is compared how -- nothing here has a tolerance:
 - the bit matrix against the existing kernel: adj[s, r] == (dff_rmsd_matrix(x, x)[min(s, r), max(s, r)] <= cutoff), the
   cutoffs taken from the matrix's own values (so that `<=` is met with equality), symmetric, the diagonal set, the padding
   zero, degree = the row popcount;
-- against the float64 oracle (tests/cluster_oracle.py) at cutoffs in the middle of a gap of the pair RMSDs that is, on the
+- against the float64 oracle (oracle/cluster.py) at cutoffs in the middle of a gap of the pair RMSDs that is, on the
   oracle alone, at least 8 times the bar the RMSD kernels are held to (RMSD_ATOL + RMSD_RTOL cutoff, tests/support.py)
   away from every pair: no pair can change sides, so adjacency, labels, centres and sizes must equal the oracle's exactly;
 - the greedy loop alone on uploaded bit matrices against the oracle's loop.
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-import cluster_oracle as co
+from oracle import cluster as co
 from oracle.frames import integer_walks, noisy_ensemble, walks
 from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import RMSD_ATOL, RMSD_RTOL, B, dev, ev, to_dev  # noqa: F401  (dev)

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import dff_amd
-from cluster_oracle import gromos, neighbors, pack, pick_cutoff, unpack
+from oracle.cluster import gromos, neighbors, pack, pick_cutoff, unpack
 from dff_amd import binding, evaluate
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))

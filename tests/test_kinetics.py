@@ -1,4 +1,4 @@
-"""dff_struct_native_q / dff_core_states / dff_label_runs on the GPU against the naive numpy oracle of tests/kinetics_oracle.py.
+"""dff_struct_native_q / dff_core_states / dff_label_runs on the GPU against the naive numpy oracle of oracle/kinetics.py.
 
 What is compared how:
 - Q       |Q_gpu - Q_oracle| <= 2^-23 absolute: the kernel computes in fp64 and rounds to fp32 once, device and numpy exp differ
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from kinetics_oracle import core_states, label_runs, native_q, scripted_frames
+from oracle.kinetics import core_states, label_runs, native_q, scripted_frames
 from oracle.frames import chain_frames, noisy_ensemble, splitmix_labels
 from oracle.struct_metric import kabsch64_batch
 from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)

@@ -13,7 +13,7 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
-from kinetics_oracle import core_states, core_states_scan, label_runs, native_q
+from oracle.kinetics import core_states, core_states_scan, label_runs, native_q
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_struct_native_q", "dff_kinetics_workspace_bytes", "dff_core_states", "dff_label_runs")

@@ -1,4 +1,4 @@
-"""The Markov-state-model calls on the GPU (csrc/dff_msm.hip) against the fp64 numpy oracle of tests/msm_oracle.py, and the
+"""The Markov-state-model calls on the GPU (csrc/dff_msm.hip) against the fp64 numpy oracle of oracle/msm.py, and the
 classes of evaluate.py on top of them.  C = binding.MICRO_CHUNK is the number of points one workgroup of
 dff_micro_kmeans_step takes: the point counts below sit on its boundaries.
 
@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 import torch
 
-import msm_oracle as oracle
+from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)

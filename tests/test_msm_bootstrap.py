@@ -1,7 +1,7 @@
 """The bootstrap calls on the GPU (csrc/dff_msm_batch.hip) and evaluate.bootstrap_msm on top of them.
 
 What is compared how:
-- counts      integer and exact: equal to the oracle's explicit loop over the pairs (tests/msm_bootstrap_oracle.py); with all
+- counts      integer and exact: equal to the oracle's explicit loop over the pairs (oracle/msm_bootstrap.py); with all
               weights 1 every slice is dff_micro_transition_counts' matrix; the same from a workspace of 0xFF and of 0x00.
 - estimator   bit-identical to dff_msm_reversible_steps, problem by problem, x and err, on both forced drivers and the default:
               the single call is the reference (tests/test_msm.py holds IT to the oracle), computed once per problem.
@@ -18,8 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-import msm_bootstrap_oracle as boot
-import msm_oracle as oracle
+from oracle import msm_bootstrap as boot
+from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)
@@ -218,6 +218,53 @@ def test_skipped_problems_and_a_zero_row_count(dev):
         cp[2] = 0.0
         want_x, want_err = single(Sp, cp, xp, 3)
         assert same_bits(x[3, :5], want_x) and same_bits(err[:, 3], want_err)
+
+
+def test_sweeps_stay_inside_their_workspace(dev):
+    """A workspace 64 bytes longer than asked for, all 0xA5: the 64 bytes stay, and x and err are those of the exact-size run.
+    Single call at K = 2 (one workgroup) and K = 33 (the smallest K with a launch per sweep); batched call at B = 2,
+    Kmax = 33 on both forced drivers."""
+    CANARY, n = 64, 3
+
+    def run(call, need, extra):
+        ws = torch.full((need + extra,), 0xA5, dtype=torch.uint8, device="cuda")
+        x, err = call(ws)
+        assert bool((ws[need:] == 0xA5).all())
+        return x.cpu().numpy(), err.cpu().numpy()
+
+    assert B().msm_driver_for(2) == 2 and B().msm_driver_for(33) == 1
+    for K in (2, 33):
+        S, c, x0, _ = problem(K, 0)
+
+        def one(ws):
+            xd = to_dev(x0)
+            return xd, B().msm_reversible_steps(to_dev(S), to_dev(c), xd, n, workspace=ws)
+        need = B().msm_workspace_bytes(K)
+        exact, padded = run(one, need, 0), run(one, need, CANARY)
+        assert same_bits(padded[0], exact[0]) and same_bits(padded[1], exact[1]), K
+        assert np.isfinite(exact[0]).all() and (exact[1] > 0).all(), K
+
+    ks, Kmax = np.array([33, 5], np.int32), 33
+    Sb, cb, xb = np.full((2, Kmax * Kmax), np.nan), np.full((2, Kmax), np.nan), np.full((2, Kmax), np.nan)
+    for p, K in enumerate(ks):
+        Sp, cp, xp, _ = problem(int(K), 0)
+        Sb[p, :K * K], cb[p, :K], xb[p, :K] = Sp.reshape(-1), cp, xp
+    Sb = Sb.reshape(2, Kmax, Kmax)
+
+    def many(ws):
+        xd = to_dev(xb)
+        return xd, B().msm_reversible_steps_batched(to_dev(Sb), to_dev(cb), ks, xd, n, workspace=ws)
+    need = B().msm_batched_workspace_bytes(2, Kmax)
+    for drv in (1, 2):
+        B().debug_msm_driver(drv)
+        try:
+            exact, padded = run(many, need, 0), run(many, need, CANARY)
+        finally:
+            B().debug_msm_driver(0)
+        assert same_bits(padded[0], exact[0]) and same_bits(padded[1], exact[1]), drv
+        for p, K in enumerate(ks):
+            want_x, want_err = single(*problem(int(K), 0)[:3], n)
+            assert same_bits(exact[0][p, :K], want_x) and same_bits(exact[1][:, p], want_err), (drv, p)
 
 
 def test_batched_refusals(dev):

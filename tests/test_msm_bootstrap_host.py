@@ -1,6 +1,6 @@
 """Host side of the Markov-state-model bootstrap: the symbols and refusals of dff_micro_resampled_counts /
 dff_msm_reversible_steps_batched (refused on the host, before any device call), resampling_units and bootstrap_weights,
-bootstrap_msm on numpy stand-ins behind its two device seams against the from-scratch oracle (tests/msm_bootstrap_oracle.py)
+bootstrap_msm on numpy stand-ins behind its two device seams against the from-scratch oracle (oracle/msm_bootstrap.py)
 and against MarkovStateModel.fit_counts resample by resample, the percentile intervals, MsmEvaluator's dict with and without
 a bootstrap, the tool's arguments, and the calibration of the error bars on a two-state chain with a known timescale.  No GPU."""
 import ctypes as C
@@ -13,8 +13,8 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
-import msm_bootstrap_oracle as boot
-import msm_oracle as oracle
+from oracle import msm_bootstrap as boot
+from oracle import msm as oracle
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_micro_resampled_counts_workspace_bytes", "dff_micro_resampled_counts", "dff_msm_batched_workspace_bytes",

@@ -1,6 +1,6 @@
 """Host side of the Markov state models: the symbols and refusals of the dff_micro_* / dff_msm_* calls (on the host, before any
 device call: they run on a machine without one), largest_connected_set against scipy, the properties of the oracle's
-reversible estimator (tests/msm_oracle.py), MarkovStateModel on top of the oracle's sweeps, timescales of a known matrix, the
+reversible estimator (oracle/msm.py), MarkovStateModel on top of the oracle's sweeps, timescales of a known matrix, the
 evaluator's argument checks and dict keys, the package's re-exports and the --msm arguments of tools_eval_samples.py.  No GPU."""
 import ctypes as C
 import os
@@ -11,7 +11,7 @@ import pytest
 
 import dff_amd
 from dff_amd import binding, evaluate
-import msm_oracle as oracle
+from oracle import msm as oracle
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_micro_chunk", "dff_micro_kmeans_workspace_bytes", "dff_micro_kmeans_step", "dff_micro_transition_counts",
@@ -280,6 +280,17 @@ def test_evaluator_checks_its_arguments(monkeypatch):
     assert evaluate.MicrostateKMeans(1024, device="cpu").n_clusters == 1024
     with pytest.raises(ValueError, match="1..64"):
         evaluate.KMeans(65, device="cpu")                                   # the K <= 64 class keeps its limit
+
+
+def test_the_two_kmeans_classes_keep_their_own_names_limits_and_seeding(monkeypatch):
+    monkeypatch.setattr(binding, "load_library", lambda *a, **k: None)
+    with pytest.raises(ValueError, match=r"^KMeans: n_clusters must be 1\.\.64$"):
+        evaluate.KMeans(65, device="cpu")
+    with pytest.raises(ValueError, match=r"^MicrostateKMeans: n_clusters must be 1\.\.1024$"):
+        evaluate.MicrostateKMeans(1025, device="cpu")
+    with pytest.raises(ValueError, match="^MicrostateKMeans: not fitted$"):
+        evaluate.MicrostateKMeans(3, device="cpu").transform(np.zeros((4, 2)))
+    assert evaluate.MicrostateKMeans._seed_centers is not evaluate.KMeans._seed_centers
 
 
 def test_evaluator_raises_without_library(monkeypatch):

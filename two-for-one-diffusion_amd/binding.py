@@ -663,14 +663,17 @@ def kmeans_workspace_bytes(n: int, d: int, K: int) -> int:
     return _workspace_bytes("dff_kmeans_workspace_bytes", int(n), int(d), int(K))
 
 
-def kmeans_step(points, centers, accumulate=True, workspace=None):
-    """One Lloyd step over points (n, d) (contiguous float64 CUDA) with centers (K, d): a dict of labels int32 (n,),
-    dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64 (1,) over the
-    finite points (dff_kmeans_step: deterministic).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+def _is_tensor(t, dtype, shape=None, dim=None):
+    """t is a contiguous CUDA tensor of `dtype`, of exactly `shape` or of `dim` dimensions."""
+    import torch
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and (shape is None or tuple(t.shape) == shape) and (dim is None or t.dim() == dim))
+
+
+def _kmeans_step(symbol, workspace_bytes, points, centers, accumulate, workspace):
     import torch
     lib = load_library()
-    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64
-            and points.is_contiguous() and points.dim() == 2):
+    if not _is_tensor(points, torch.float64, dim=2):
         raise ValueError("points must be a contiguous float64 CUDA tensor of shape (n, d)")
     n, d = int(points.shape[0]), int(points.shape[1])
     c = _centers(centers, d, points.device)
@@ -679,18 +682,41 @@ def kmeans_step(points, centers, accumulate=True, workspace=None):
            "dist2": torch.empty(n, dtype=torch.float64, device=points.device)}
     ws_bytes = 0
     if accumulate:
+        need = workspace_bytes(n, d, K)                         # refuses a bad d or K before anything is allocated
         out["sums"] = torch.empty((K, d), dtype=torch.float64, device=points.device)
         out["counts"] = torch.empty(K, dtype=torch.int64, device=points.device)
         out["inertia"] = torch.empty(1, dtype=torch.float64, device=points.device)
         if workspace is None:
-            workspace = torch.empty(max(kmeans_workspace_bytes(n, d, K), 1), dtype=torch.uint8, device=points.device)
+            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=points.device)
         ws_bytes = int(workspace.numel() * workspace.element_size())
     else:
         workspace = None
-    _check(lib, lib.dff_kmeans_step(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
-                                    _ptr(out["dist2"]), _ptr(out.get("sums")), _ptr(out.get("counts")),
-                                    _ptr(out.get("inertia")), _ptr(workspace), ws_bytes, _stream(points)),
-           "dff_kmeans_step")
+    _check(lib, getattr(lib, symbol)(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
+                                     _ptr(out["dist2"]), _ptr(out.get("sums")), _ptr(out.get("counts")),
+                                     _ptr(out.get("inertia")), _ptr(workspace), ws_bytes, _stream(points)), symbol)
+    return out
+
+
+def kmeans_step(points, centers, accumulate=True, workspace=None):
+    """One Lloyd step over points (n, d) (contiguous float64 CUDA) with centers (K, d): a dict of labels int32 (n,),
+    dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64 (1,) over the
+    finite points (dff_kmeans_step: deterministic).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    return _kmeans_step("dff_kmeans_step", kmeans_workspace_bytes, points, centers, accumulate, workspace)
+
+
+def _transition_counts(symbol, labels, lengths, lagtimes, n_states):
+    import torch
+    lib = load_library()
+    if not _is_tensor(labels, torch.int32, dim=1):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
+    ln = _lengths(lengths)
+    lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
+    K = int(n_states)
+    Ka = min(max(K, 1), MSM_MAX_STATES)                          # what is allocated when K itself will be refused
+    out = torch.empty((min(max(int(lg.size), 1), MSM_MAX_LAGS), Ka, Ka), dtype=torch.int64, device=labels.device)
+    _check(lib, getattr(lib, symbol)(labels.device.index, _ptr(labels), int(labels.numel()), ln.ctypes.data_as(C.c_void_p),
+                                     int(ln.size), lg.ctypes.data_as(C.c_void_p), int(lg.size), K, _ptr(out),
+                                     _stream(labels)), symbol)
     return out
 
 
@@ -698,19 +724,7 @@ def transition_counts(labels, lengths, lagtimes, n_states: int):
     """Sliding-window transition counts of the int32 CUDA labels (n,) -- trajectories back to back, `lengths` frames
     each -- at every lag time of `lagtimes` -> int64 CUDA tensor (n_lags, K, K); pairs with a label outside 0 .. K - 1
     are skipped (dff_transition_counts)."""
-    import torch
-    lib = load_library()
-    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
-            and labels.is_contiguous() and labels.dim() == 1):
-        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
-    ln = _lengths(lengths)
-    lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
-    K = int(n_states)
-    out = torch.empty((max(int(lg.size), 1), max(K, 1), max(K, 1)), dtype=torch.int64, device=labels.device)
-    _check(lib, lib.dff_transition_counts(labels.device.index, _ptr(labels), int(labels.numel()),
-                                          ln.ctypes.data_as(C.c_void_p), int(ln.size), lg.ctypes.data_as(C.c_void_p),
-                                          int(lg.size), K, _ptr(out), _stream(labels)), "dff_transition_counts")
-    return out
+    return _transition_counts("dff_transition_counts", labels, lengths, lagtimes, n_states)
 
 
 # ---- RMSD between two ensembles (dff_rmsd_nearest, dff_rmsd_matrix) ----
@@ -996,52 +1010,13 @@ def micro_kmeans_step(points, centers, accumulate=True, workspace=None):
     labels int32 (n,), dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64
     (1,) over the finite points.  Labels and dist2 are kmeans_step's bits for K <= 64; the sums are taken in another
     (fixed) order.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
-    import torch
-    lib = load_library()
-    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64
-            and points.is_contiguous() and points.dim() == 2):
-        raise ValueError("points must be a contiguous float64 CUDA tensor of shape (n, d)")
-    n, d = int(points.shape[0]), int(points.shape[1])
-    c = _centers(centers, d, points.device)
-    K = int(c.shape[0])
-    out = {"labels": torch.empty(n, dtype=torch.int32, device=points.device),
-           "dist2": torch.empty(n, dtype=torch.float64, device=points.device)}
-    ws_bytes = 0
-    if accumulate:
-        need = micro_kmeans_workspace_bytes(n, d, K)            # refuses a bad d or K before anything is allocated
-        out["sums"] = torch.empty((max(K, 1), d), dtype=torch.float64, device=points.device)
-        out["counts"] = torch.empty(max(K, 1), dtype=torch.int64, device=points.device)
-        out["inertia"] = torch.empty(1, dtype=torch.float64, device=points.device)
-        if workspace is None:
-            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=points.device)
-        ws_bytes = int(workspace.numel() * workspace.element_size())
-    else:
-        workspace = None
-    _check(lib, lib.dff_micro_kmeans_step(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
-                                          _ptr(out["dist2"]), _ptr(out.get("sums")), _ptr(out.get("counts")),
-                                          _ptr(out.get("inertia")), _ptr(workspace), ws_bytes, _stream(points)),
-           "dff_micro_kmeans_step")
-    return out
+    return _kmeans_step("dff_micro_kmeans_step", micro_kmeans_workspace_bytes, points, centers, accumulate, workspace)
 
 
 def micro_transition_counts(labels, lengths, lagtimes, n_states: int):
     """transition_counts for up to MSM_MAX_STATES states and up to MSM_MAX_LAGS lag times (dff_micro_transition_counts) ->
     int64 CUDA tensor (n_lags, K, K); exact, and equal to transition_counts' result for K <= 64."""
-    import torch
-    lib = load_library()
-    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
-            and labels.is_contiguous() and labels.dim() == 1):
-        raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
-    ln = _lengths(lengths)
-    lg = np.ascontiguousarray(np.asarray(lagtimes, dtype=np.int32).reshape(-1))
-    K = int(n_states)
-    Ka = min(max(K, 1), MSM_MAX_STATES)                          # what is allocated when K itself will be refused
-    out = torch.empty((min(max(int(lg.size), 1), MSM_MAX_LAGS), Ka, Ka), dtype=torch.int64, device=labels.device)
-    _check(lib, lib.dff_micro_transition_counts(labels.device.index, _ptr(labels), int(labels.numel()),
-                                                ln.ctypes.data_as(C.c_void_p), int(ln.size),
-                                                lg.ctypes.data_as(C.c_void_p), int(lg.size), K, _ptr(out),
-                                                _stream(labels)), "dff_micro_transition_counts")
-    return out
+    return _transition_counts("dff_micro_transition_counts", labels, lengths, lagtimes, n_states)
 
 
 def msm_workspace_bytes(K: int) -> int:
@@ -1055,12 +1030,10 @@ def msm_reversible_steps(sym, rowc, x, n_steps: int, err=True, workspace=None):
     is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
     import torch
     lib = load_library()
-
-    def ok(t, shape):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-                and tuple(t.shape) == shape)
     K = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 1 else -1
-    if not (ok(x, (K,)) and ok(sym, (K, K)) and ok(rowc, (K,)) and sym.device == x.device and rowc.device == x.device):
+    f64 = torch.float64
+    if not (_is_tensor(x, f64, (K,)) and _is_tensor(sym, f64, (K, K)) and _is_tensor(rowc, f64, (K,))
+            and sym.device == x.device and rowc.device == x.device):
         raise ValueError("sym (K, K), rowc (K,) and x (K,) must be contiguous float64 CUDA tensors on one device")
     n_steps = int(n_steps)
     need = msm_workspace_bytes(K)
@@ -1103,12 +1076,10 @@ def micro_resampled_counts(labels, lengths, unit_lengths, lag: int, K: int, weig
     None)."""
     import torch
     lib = load_library()
-    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32
-            and labels.is_contiguous() and labels.dim() == 1):
+    if not _is_tensor(labels, torch.int32, dim=1):
         raise ValueError("labels must be a contiguous int32 CUDA tensor of shape (n,)")
     ln, un = _lengths(lengths), _lengths(unit_lengths)
-    if not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype == torch.uint32 and weights.is_contiguous()
-            and weights.dim() == 2 and weights.shape[1] == un.size and weights.device == labels.device):
+    if not (_is_tensor(weights, torch.uint32, dim=2) and weights.shape[1] == un.size and weights.device == labels.device):
         raise ValueError("weights must be a contiguous uint32 CUDA tensor of shape (B, n_units) on the labels' device")
     K, B = int(K), int(weights.shape[0])
     need = micro_resampled_counts_workspace_bytes(int(ln.size), int(un.size))
@@ -1137,12 +1108,10 @@ def msm_reversible_steps_batched(S, c, ks, x, n_steps: int, skip=None, workspace
     single call's x and err, problem by problem.  Nothing is read back."""
     import torch
     lib = load_library()
-
-    def ok(t, shape):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-                and tuple(t.shape) == shape)
     B, Kmax = (int(x.shape[0]), int(x.shape[1])) if isinstance(x, torch.Tensor) and x.dim() == 2 else (-1, -1)
-    if not (ok(x, (B, Kmax)) and ok(S, (B, Kmax, Kmax)) and ok(c, (B, Kmax)) and S.device == x.device and c.device == x.device):
+    f64 = torch.float64
+    if not (_is_tensor(x, f64, (B, Kmax)) and _is_tensor(S, f64, (B, Kmax, Kmax)) and _is_tensor(c, f64, (B, Kmax))
+            and S.device == x.device and c.device == x.device):
         raise ValueError("S (B, Kmax, Kmax), c (B, Kmax) and x (B, Kmax) must be contiguous float64 CUDA tensors on one device")
     kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
     if kh.size != B:

@@ -414,18 +414,21 @@ extern "C" long long dff_kmeans_workspace_bytes(long long n, int d, int K) {
     return (long long)kmeans_grid(n) * (K * d + K + 1) * (long long)sizeof(double);
 }
 
-extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d, const double* centers, int K,
-                               int32_t* labels, double* dist2, double* sums, uint64_t* counts, double* inertia,
-                               void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = kmeans_check_shape(n, d, K, "kmeans_step");
-    if (rc) return rc;
-    if (!pts && n > 0) return fail(DFF_EINVAL, "kmeans_step: null points");
-    if (!centers) return fail(DFF_EINVAL, "kmeans_step: null centres");
+// What both k-means steps do around their kernels, after the caller's shape check: pointers, the workspace (`need` bytes,
+// `align`-byte aligned, when something is accumulated), the device, zeroed results at n == 0; then launch(accumulate), unless
+// nothing is asked for.
+template <class Launch>
+static int kmeans_call(int device, const double* pts, long long n, int d, const double* centers, int K, const int32_t* labels,
+                       const double* dist2, double* sums, uint64_t* counts, double* inertia, const void* workspace,
+                       size_t workspace_bytes, long long need, size_t align, hipStream_t stream, const char* what,
+                       Launch launch) {
+    if (!pts && n > 0) return fail(DFF_EINVAL, "%s: null points", what);
+    if (!centers) return fail(DFF_EINVAL, "%s: null centres", what);
     const bool accumulate = sums || counts || inertia;
-    const long long need = accumulate ? dff_kmeans_workspace_bytes(n, d, K) : 0;       // 0 at n = 0
-    if ((rc = check_workspace(workspace, workspace_bytes, need, "kmeans_step"))) return rc;
+    if (!accumulate) need = 0;                                      // and 0 at n = 0
+    if (int rc = check_workspace(workspace, workspace_bytes, need, what)) return rc;
+    if (need > 0 && (uintptr_t)workspace % align) return fail(DFF_EINVAL, "%s: the workspace must be %d-byte aligned", what, (int)align);
     ON_DEVICE(device);
-    hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) {
         if (sums) HIPCHK(hipMemsetAsync(sums, 0, (size_t)K * d * sizeof(double), stream));
         if (counts) HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(uint64_t), stream));
@@ -433,17 +436,28 @@ extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d
         return DFF_OK;
     }
     if (!accumulate && !labels && !dist2) return DFF_OK;
-    const int per = K * d + K + 1, grid = kmeans_grid(n);
-    double* part = accumulate ? (double*)workspace : nullptr;
-    hipLaunchKernelGGL(dff_kmeans_step_kernel, dim3(grid), dim3(DFF_KM_THREADS),
-                       (unsigned)(4 * per * sizeof(double)), stream, pts, n, d, centers, K, labels, dist2, part);
-    HIPCHK(hipGetLastError());
-    if (accumulate) {
-        hipLaunchKernelGGL(dff_kmeans_reduce_kernel, dim3(per), dim3(64), 0, stream, part, grid, d, K, sums,
-                           (unsigned long long*)counts, inertia);
+    return launch(accumulate);
+}
+
+extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d, const double* centers, int K,
+                               int32_t* labels, double* dist2, double* sums, uint64_t* counts, double* inertia,
+                               void* workspace, size_t workspace_bytes, void* stream_) {
+    if (int rc = kmeans_check_shape(n, d, K, "kmeans_step")) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    return kmeans_call(device, pts, n, d, centers, K, labels, dist2, sums, counts, inertia, workspace, workspace_bytes,
+                       dff_kmeans_workspace_bytes(n, d, K), 1, stream, "kmeans_step", [&](bool accumulate) -> int {
+        const int per = K * d + K + 1, grid = kmeans_grid(n);
+        double* part = accumulate ? (double*)workspace : nullptr;
+        hipLaunchKernelGGL(dff_kmeans_step_kernel, dim3(grid), dim3(DFF_KM_THREADS),
+                           (unsigned)(4 * per * sizeof(double)), stream, pts, n, d, centers, K, labels, dist2, part);
         HIPCHK(hipGetLastError());
-    }
-    return DFF_OK;
+        if (accumulate) {
+            hipLaunchKernelGGL(dff_kmeans_reduce_kernel, dim3(per), dim3(64), 0, stream, part, grid, d, K, sums,
+                               (unsigned long long*)counts, inertia);
+            HIPCHK(hipGetLastError());
+        }
+        return DFF_OK;
+    });
 }
 
 // The launches of a call over n > 0 frames of trajectories back to back (lengths already checked): launch(runs) once per
@@ -496,15 +510,20 @@ static int tc_launches(hipStream_t stream, const int32_t* labels, long long n, c
     });
 }
 
+static int tc_check_lags(const int32_t* lags, int n_lags, const char* what) {
+    if (!lags || n_lags < 1 || n_lags > DFF_TC_MAXLAGS)
+        return fail(DFF_EINVAL, "%s: the number of lag times must be 1..%d", what, DFF_TC_MAXLAGS);
+    for (int l = 0; l < n_lags; ++l)
+        if (lags[l] < 1) return fail(DFF_EINVAL, "%s: lag time %d is %d, must be >= 1", what, l, (int)lags[l]);
+    return DFF_OK;
+}
+
 extern "C" int dff_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
                                      const int32_t* lags, int n_lags, int K, uint64_t* counts, void* stream_) {
     if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "transition_counts: null labels / negative count");
     int rc = states_check_count(K, "transition_counts", "states");
     if (rc) return rc;
-    if (!lags || n_lags < 1 || n_lags > DFF_TC_MAXLAGS)
-        return fail(DFF_EINVAL, "transition_counts: the number of lag times must be 1..%d", DFF_TC_MAXLAGS);
-    for (int l = 0; l < n_lags; ++l)
-        if (lags[l] < 1) return fail(DFF_EINVAL, "transition_counts: lag time %d is %d, must be >= 1", l, (int)lags[l]);
+    if ((rc = tc_check_lags(lags, n_lags, "transition_counts"))) return rc;
     if ((rc = traj_check_lengths(lengths, n_traj, n, "transition_counts"))) return rc;
     if (!counts) return fail(DFF_EINVAL, "transition_counts: null counts");
     ON_DEVICE(device);
@@ -945,46 +964,34 @@ extern "C" long long dff_micro_kmeans_workspace_bytes(long long n, int d, int K)
 extern "C" int dff_micro_kmeans_step(int device, const double* pts, long long n, int d, const double* centers, int K,
                                      int32_t* labels, double* dist2, double* sums, uint64_t* counts, double* inertia,
                                      void* workspace, size_t workspace_bytes, void* stream_) {
-    int rc = micro_check_shape(n, d, K, "micro_kmeans_step");
-    if (rc) return rc;
-    if (!pts && n > 0) return fail(DFF_EINVAL, "micro_kmeans_step: null points");
-    if (!centers) return fail(DFF_EINVAL, "micro_kmeans_step: null centres");
-    const bool accumulate = sums || counts || inertia;
-    const long long need = accumulate ? dff_micro_kmeans_workspace_bytes(n, d, K) : 0;       // 0 at n = 0
-    if ((rc = check_workspace(workspace, workspace_bytes, need, "micro_kmeans_step"))) return rc;
-    if (need > 0 && (uintptr_t)workspace % sizeof(double))
-        return fail(DFF_EINVAL, "micro_kmeans_step: the workspace must be 8-byte aligned");
-    ON_DEVICE(device);
+    if (int rc = micro_check_shape(n, d, K, "micro_kmeans_step")) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    if (n == 0) {
-        if (sums) HIPCHK(hipMemsetAsync(sums, 0, (size_t)K * d * sizeof(double), stream));
-        if (counts) HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(uint64_t), stream));
-        if (inertia) HIPCHK(hipMemsetAsync(inertia, 0, sizeof(double), stream));
-        return DFF_OK;
-    }
-    if (!accumulate && !labels && !dist2) return DFF_OK;
-    const unsigned grid = (unsigned)micro_chunks(n);
-    const int groups = accumulate ? micro_groups(d, K) : 0;
-    const unsigned lds = (unsigned)micro_lds_bytes(d, K, groups);              // <= 160 KB
-    if (accumulate) {
-        if (lds > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_micro_kmeans_kernel<true>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d, centers,
-                           K, labels, dist2, (double*)workspace, groups);
+    return kmeans_call(device, pts, n, d, centers, K, labels, dist2, sums, counts, inertia, workspace, workspace_bytes,
+                       dff_micro_kmeans_workspace_bytes(n, d, K), sizeof(double), stream, "micro_kmeans_step",
+                       [&](bool accumulate) -> int {
+        const unsigned grid = (unsigned)micro_chunks(n);
+        const int groups = accumulate ? micro_groups(d, K) : 0;
+        const unsigned lds = (unsigned)micro_lds_bytes(d, K, groups);              // <= 160 KB
+        if (accumulate) {
+            if (lds > 48 * 1024)
+                HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<true>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(dff_micro_kmeans_kernel<true>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d,
+                               centers, K, labels, dist2, (double*)workspace, groups);
+            HIPCHK(hipGetLastError());
+            const int per = K * (d + 1) + 1;
+            hipLaunchKernelGGL(dff_micro_kmeans_reduce_kernel, dim3((unsigned)((per + 63) / 64)), dim3(256), 0, stream,
+                               (const double*)workspace, (long long)grid, d, K, sums, (unsigned long long*)counts, inertia);
+        } else {
+            if (lds > 48 * 1024)
+                HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<false>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(dff_micro_kmeans_kernel<false>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d,
+                               centers, K, labels, dist2, (double*)nullptr, 1);
+        }
         HIPCHK(hipGetLastError());
-        const int per = K * (d + 1) + 1;
-        hipLaunchKernelGGL(dff_micro_kmeans_reduce_kernel, dim3((unsigned)((per + 63) / 64)), dim3(256), 0, stream,
-                           (const double*)workspace, (long long)grid, d, K, sums, (unsigned long long*)counts, inertia);
-    } else {
-        if (lds > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_micro_kmeans_kernel<false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_micro_kmeans_kernel<false>, dim3(grid), dim3(DFF_MICRO_THREADS), lds, stream, pts, n, d,
-                           centers, K, labels, dist2, (double*)nullptr, 1);
-    }
-    HIPCHK(hipGetLastError());
-    return DFF_OK;
+        return DFF_OK;
+    });
 }
 
 extern "C" int dff_micro_transition_counts(int device, const int32_t* labels, long long n, const long long* lengths,
@@ -993,10 +1000,7 @@ extern "C" int dff_micro_transition_counts(int device, const int32_t* labels, lo
     if ((!labels && n > 0) || n < 0) return fail(DFF_EINVAL, "micro_transition_counts: null labels / negative count");
     int rc = micro_check_count(K, "micro_transition_counts", "states");
     if (rc) return rc;
-    if (!lags || n_lags < 1 || n_lags > DFF_TC_MAXLAGS)
-        return fail(DFF_EINVAL, "micro_transition_counts: the number of lag times must be 1..%d", DFF_TC_MAXLAGS);
-    for (int l = 0; l < n_lags; ++l)
-        if (lags[l] < 1) return fail(DFF_EINVAL, "micro_transition_counts: lag time %d is %d, must be >= 1", l, (int)lags[l]);
+    if ((rc = tc_check_lags(lags, n_lags, "micro_transition_counts"))) return rc;
     if ((rc = traj_check_lengths(lengths, n_traj, n, "micro_transition_counts"))) return rc;
     if (!counts) return fail(DFF_EINVAL, "micro_transition_counts: null counts");
     ON_DEVICE(device);
@@ -1028,14 +1032,43 @@ extern "C" int dff_debug_msm_driver(int driver) {
     return DFF_OK;
 }
 
-static int msm_driver(int K) {
+// The driver for n_live problems of up to kmax states (the single call: n_live = 1).  One looping workgroup per problem pays no
+// launch per sweep but uses one CU per problem, so beyond DFF_MSM_LOOP_MAXK states it wants enough problems to cover what the
+// largest of them costs: measured it wins from 4 problems on at K = 64, from 8 at K = 128 and 256, from
+// 16 at K = 512 and from 32 at K = 1024 -- never for one problem.
+static int msm_driver(int kmax, int n_live) {
     const int driver = g_msm_driver.load();
-    return driver ? driver : (K <= DFF_MSM_LOOP_MAXK ? 2 : 1);
+    if (driver) return driver;
+    if (kmax <= DFF_MSM_LOOP_MAXK) return 2;
+    return (32LL * n_live >= kmax && n_live >= (kmax >= 128 ? 8 : 4)) ? 2 : 1;
+}
+
+// n_steps sweeps of the n_prob problems of `loc`, the largest of kmax states, enqueued on `stream`: driver 2, one looping
+// workgroup per problem; driver 1, q0 <- (rowc, x), then one launch per sweep with q ping-ponging q0 <-> q1.  err: sweep s at
+// err + s * loc.err_stride(), or null.
+template <class Loc>
+static int msm_sweeps(hipStream_t stream, Loc loc, int driver, int kmax, unsigned n_prob, const double* sym,
+                      const double* rowc, double* x, int n_steps, double* q0, double* q1, unsigned long long* err) {
+    if (driver == 2) {
+        hipLaunchKernelGGL(dff_msm_loop_kernel<Loc>, dim3(n_prob), dim3(DFF_MSM_LOOP_THREADS), (unsigned)(3 * kmax * sizeof(double)),
+                           stream, sym, rowc, loc, x, n_steps, err);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    }
+    double* q[2] = {q0, q1};
+    hipLaunchKernelGGL(dff_msm_init_kernel<Loc>, dim3((unsigned)((kmax + 255) / 256), n_prob), dim3(256), 0, stream, rowc,
+                       (const double*)x, loc, q[0]);
+    const dim3 grid((unsigned)((kmax + DFF_MSM_THREADS / 64 - 1) / (DFF_MSM_THREADS / 64)), n_prob);
+    for (int s = 0; s < n_steps; ++s)
+        hipLaunchKernelGGL(dff_msm_sweep_kernel<Loc>, grid, dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, loc, x,
+                           (const double*)q[s & 1], q[(s + 1) & 1], err ? err + (size_t)s * loc.err_stride() : nullptr);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
 }
 
 extern "C" int dff_msm_driver_for(int K) {
     if (micro_check_count(K, "msm_driver_for", "states")) return -1;
-    return msm_driver(K);
+    return msm_driver(K, 1);
 }
 
 extern "C" long long dff_msm_workspace_bytes(int K) {
@@ -1055,21 +1088,8 @@ extern "C" int dff_msm_reversible_steps(int device, const double* sym, const dou
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     if (err) HIPCHK(hipMemsetAsync(err, 0, (size_t)n_steps * sizeof(double), stream));
-    if (msm_driver(K) == 2) {
-        hipLaunchKernelGGL(dff_msm_loop_kernel, dim3(1), dim3(DFF_MSM_LOOP_THREADS), (unsigned)(3 * K * sizeof(double)), stream,
-                           sym, rowc, K, x, n_steps, (unsigned long long*)err);
-        HIPCHK(hipGetLastError());
-        return DFF_OK;
-    }
-    double* q[2] = {(double*)workspace, (double*)workspace + K};
-    hipLaunchKernelGGL(dff_msm_init_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, rowc, (const double*)x, K,
-                       q[0]);
-    const unsigned grid = (unsigned)((K + DFF_MSM_THREADS / 64 - 1) / (DFF_MSM_THREADS / 64));
-    for (int s = 0; s < n_steps; ++s)
-        hipLaunchKernelGGL(dff_msm_sweep_kernel, dim3(grid), dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, K, x,
-                           (const double*)q[s & 1], q[(s + 1) & 1], err ? (unsigned long long*)err + s : nullptr);
-    HIPCHK(hipGetLastError());
-    return DFF_OK;
+    return msm_sweeps(stream, MsmOne{K}, msm_driver(K, 1), K, 1, sym, rowc, x, n_steps, (double*)workspace,
+                      (double*)workspace + K, (unsigned long long*)err);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1156,21 +1176,10 @@ extern "C" long long dff_msm_batched_workspace_bytes(int B, int Kmax) {
     return (2LL * B * Kmax + B) * (long long)sizeof(double);            // q ping | q pong | the live problems' descriptors
 }
 
-// The batched call's driver for n_live problems of up to kmax states.  One looping workgroup per problem pays no launch per
-// sweep but uses one CU per problem, so it wants enough problems to cover what the largest of them costs: measured
-//  it wins from 4 problems on at K = 64, from 8 at K = 128 and 256, from 16 at K = 512 and from 32 at
-// K = 1024; up to DFF_MSM_LOOP_MAXK states it is the single call's choice already.
-static int msmb_driver(int kmax, int n_live) {
-    const int driver = g_msm_driver.load();
-    if (driver) return driver;
-    if (kmax <= DFF_MSM_LOOP_MAXK) return 2;
-    return (32LL * n_live >= kmax && n_live >= (kmax >= 128 ? 8 : 4)) ? 2 : 1;
-}
-
 extern "C" int dff_msm_batched_driver_for(int B, int Kmax) {
     if (msmb_check_batch(B, "msm_batched_driver_for", "problems")) return -1;
     if (micro_check_count(Kmax, "msm_batched_driver_for", "states")) return -1;
-    return msmb_driver(Kmax, B);
+    return msm_driver(Kmax, B);
 }
 
 extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, const double* rowc, const int32_t* ks,
@@ -1194,27 +1203,14 @@ extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, c
     int kmax_live = 0;
     for (int b = 0; b < B; ++b)
         if (!skip || !skip[b]) {
-            live.push_back(((long long)b << DFF_MSMB_KBITS) | ks[b]);
+            live.push_back(MsmLive::descriptor(b, ks[b]));
             if (ks[b] > kmax_live) kmax_live = ks[b];
         }
     if (live.empty()) return DFF_OK;
-    double* q[2] = {(double*)workspace, (double*)workspace + (size_t)B * Kmax};
-    long long* live_dev = (long long*)((double*)workspace + 2 * (size_t)B * Kmax);
+    double* q0 = (double*)workspace;
+    long long* live_dev = (long long*)(q0 + 2 * (size_t)B * Kmax);
     if ((rc = msmb_upload(stream, live.data(), (long long)live.size(), live_dev))) return rc;
-    const unsigned n_live = (unsigned)live.size();
-    if (msmb_driver(kmax_live, (int)n_live) == 2) {
-        hipLaunchKernelGGL(dff_msmb_loop_kernel, dim3(n_live), dim3(DFF_MSM_LOOP_THREADS), (unsigned)(3 * kmax_live * sizeof(double)),
-                           stream, sym, rowc, Kmax, x, n_steps, (const long long*)live_dev, B, (unsigned long long*)err);
-        HIPCHK(hipGetLastError());
-        return DFF_OK;
-    }
-    hipLaunchKernelGGL(dff_msmb_init_kernel, dim3((unsigned)((kmax_live + 255) / 256), n_live), dim3(256), 0, stream, rowc,
-                       (const double*)x, Kmax, (const long long*)live_dev, q[0]);
-    const dim3 grid((unsigned)((kmax_live + DFF_MSM_THREADS / 64 - 1) / (DFF_MSM_THREADS / 64)), n_live);
-    for (int s = 0; s < n_steps; ++s)
-        hipLaunchKernelGGL(dff_msmb_sweep_kernel, grid, dim3(DFF_MSM_THREADS), 0, stream, sym, rowc, Kmax, x,
-                           (const double*)q[s & 1], q[(s + 1) & 1], (const long long*)live_dev,
-                           err ? (unsigned long long*)err + (size_t)s * B : nullptr);
-    HIPCHK(hipGetLastError());
-    return DFF_OK;
+    const int n_live = (int)live.size();
+    return msm_sweeps(stream, MsmLive{live_dev, Kmax, B}, msm_driver(kmax_live, n_live), kmax_live, (unsigned)n_live, sym, rowc, x,
+                      n_steps, q0, q0 + (size_t)B * Kmax, (unsigned long long*)err);
 }

@@ -25,13 +25,14 @@
 // dff_msm_*                      x_i' = sum_j S_ij / (q_i + q_j), q_j = c_j / x_j: one wave per row, lanes stride over j,
 //     then the butterfly (msm_row: one order, whichever kernel calls it).  x is updated in place by the wave that owns
 //     the row; q is read by every row and ping-pongs.  Two drivers with the same bits: dff_msm_sweep_kernel, one launch
-//     per sweep (K / 4 workgroups), q ping-pongs in the workspace; dff_msm_loop_kernel, ONE workgroup that runs all
-//     n_steps sweeps with q in LDS and a workgroup barrier between sweeps (no launch boundary: the faster one for few
-//     states).  err_s = max_i |x_i' - x_i| / x_i by an integer atomic max on the bits of the non-negative double (a NaN
+//     per sweep (K / 4 workgroups per problem), q ping-pongs in the workspace; dff_msm_loop_kernel, ONE workgroup per
+//     problem that runs all n_steps sweeps with q in LDS and a workgroup barrier between sweeps (no launch boundary: the
+//     faster one for few states).  Each is a template over a problem locator: MsmOne (one problem, carried by value:
+//     dff_msm_reversible_steps) or MsmLive of dff_msm_batch.hip (a table of problems: the batched call).  err_s = max_i |x_i' - x_i| / x_i by an integer atomic max on the bits of the non-negative double (a NaN
 //     has the largest pattern: one NaN row makes err NaN).
 #pragma once
 #include "dff_states.hip"   // state_nearest's rule, TransRuns, TransLags, last_le, wave_sum
-#include "dff_msm_rows.h"   // msm_q, msm_row, msm_finish: shared with dff_msm_batch.hip
+#include "dff_msm_rows.h"   // msm_q, msm_row, msm_finish
 
 #define DFF_MICRO_CHUNK 1024       // points per workgroup: at K = 1024, d = 8 the largest power of two whose coordinates
                                     // (64 KB) + labels (4 KB) + accumulators (72 KB) fit in the 160 KB of LDS
@@ -275,39 +276,70 @@ __global__ __launch_bounds__(DFF_TC_THREADS) void dff_micro_tc_kernel(const int*
     }
 }
 
-// ---- the reversible estimator's fixed-point sweeps: msm_q, msm_row and msm_finish of dff_msm_rows.h
-__global__ void dff_msm_init_kernel(const double* __restrict__ rowc, const double* __restrict__ x, int K,
+// ---- the reversible estimator's fixed-point sweeps: msm_q, msm_row and msm_finish of dff_msm_rows.h.  ONE set of kernels for
+// one problem and for many per launch, templated on a problem locator `Loc`: loc.at(p) is problem p of the launch -- its
+// index b and its number of states K; its matrix is slot b of loc.stride()^2 doubles of S, its vectors slot b of
+// loc.stride() doubles of rowc, x and q, its err of sweep s at err[s * loc.err_stride() + b].
+struct MsmAt {
+    int b, K;
+};
+
+// one problem: no table, b = 0 -- every offset folds away when the kernel is compiled
+struct MsmOne {
+    int K;
+    __device__ MsmAt at(unsigned) const { return {0, K}; }
+    __host__ __device__ int stride() const { return K; }
+    __host__ __device__ int err_stride() const { return 1; }
+};
+
+// grid (ceil(max K / blockDim.x), problems)
+template <class Loc>
+__global__ void dff_msm_init_kernel(const double* __restrict__ rowc, const double* __restrict__ x, Loc loc,
                                     double* __restrict__ q) {
+    const MsmAt p = loc.at(blockIdx.y);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < K) q[i] = msm_q(rowc[i], x[i]);
+    const size_t o = (size_t)p.b * loc.stride();
+    if (i < p.K) q[o + i] = msm_q(rowc[o + i], x[o + i]);
 }
 
-// one sweep: row i = 4 blockIdx.x + wave.  qin (K) -> x (in place, by the row's own wave), qout (K)
+// one sweep, grid (ceil(max K / 4), problems): row i = 4 blockIdx.x + wave of problem blockIdx.y.  qin -> x (in place, by
+// the row's own wave), qout.  err: this sweep's row of the err array
+template <class Loc>
 __global__ __launch_bounds__(DFF_MSM_THREADS) void dff_msm_sweep_kernel(const double* __restrict__ S,
-                                                                        const double* __restrict__ rowc, int K,
+                                                                        const double* __restrict__ rowc, Loc loc,
                                                                         double* __restrict__ x,
                                                                         const double* __restrict__ qin,
                                                                         double* __restrict__ qout,
                                                                         unsigned long long* __restrict__ err) {
+    const MsmAt p = loc.at(blockIdx.y);
+    const int K = p.K;
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * (DFF_MSM_THREADS / 64) + (threadIdx.x >> 6);
     if (i >= K) return;                                             // wave-uniform
-    double xn = msm_row(S + (size_t)i * K, qin, qin[i], K, lane);
-    const double xo = x[i], ci = rowc[i];
+    const size_t o = (size_t)p.b * loc.stride();
+    double xn = msm_row(S + o * loc.stride() + (size_t)i * K, qin + o, qin[o + i], K, lane);
+    const double xo = x[o + i], ci = rowc[o + i];
     if (!(ci > 0.0 && xo > 0.0)) xn = __builtin_nan("");
     if (lane == 0) {
-        x[i] = xn;
-        qout[i] = msm_q(ci, xn);
-        msm_finish(xn, xo, err);
+        x[o + i] = xn;
+        qout[o + i] = msm_q(ci, xn);
+        msm_finish(xn, xo, err ? err + p.b : nullptr);
     }
 }
 
-// all n_steps sweeps by one workgroup.  LDS: q ping | q pong | x (3 K doubles)
+// all n_steps sweeps of problem blockIdx.x by one workgroup.  LDS: q ping | q pong | x (3 K doubles)
+template <class Loc>
 __global__ __launch_bounds__(DFF_MSM_LOOP_THREADS) void dff_msm_loop_kernel(const double* __restrict__ S,
-                                                                            const double* __restrict__ rowc, int K,
+                                                                            const double* __restrict__ rowc, Loc loc,
                                                                             double* __restrict__ x, int n_steps,
                                                                             unsigned long long* __restrict__ err) {
     extern __shared__ __attribute__((aligned(16))) double mq[];
+    const MsmAt p = loc.at(blockIdx.x);
+    const int K = p.K;
+    const size_t o = (size_t)p.b * loc.stride();
+    S += o * loc.stride();
+    rowc += o;
+    x += o;
     double* qa = mq;
     double* qb = mq + K;
     double* xs = mq + 2 * K;
@@ -325,7 +357,7 @@ __global__ __launch_bounds__(DFF_MSM_LOOP_THREADS) void dff_msm_loop_kernel(cons
             if (lane == 0) {
                 xs[i] = xn;
                 qb[i] = msm_q(ci, xn);
-                msm_finish(xn, xo, err ? err + s : nullptr);
+                msm_finish(xn, xo, err ? err + (size_t)s * loc.err_stride() + p.b : nullptr);
             }
         }
         __syncthreads();

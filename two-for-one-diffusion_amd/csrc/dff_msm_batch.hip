@@ -11,13 +11,12 @@
 //     (triple, resample with a non-zero weight), 64 of them in flight per instruction, each to another matrix.  The weight
 //     is uniform over the aggregated lanes by construction, so no reduction over the wave is needed.  Integer adds: exact,
 //     the same whatever the order.
-// dff_msmb_*                    the kernels of dff_msm.hip with a problem index: problem b has K_b states, its compact
-//     (K_b, K_b) matrix in slot b of Kmax^2 doubles, its vectors in slots of Kmax.  The live (not skipped) problems are a
-//     table of descriptors b * 2048 + K_b in the workspace.  dff_msmb_sweep_kernel: one launch per sweep, grid
-//     (ceil(max K_b / 4), live problems), row i = 4 blockIdx.x + wave of problem blockIdx.y; q ping-pongs in the workspace.
-//     dff_msmb_loop_kernel: one workgroup per live problem runs all n_steps sweeps with q in LDS.  Rows go through msm_row /
-//     msm_q / msm_finish of dff_msm_rows.h, the one copy of the arithmetic: the bits of dff_msm_reversible_steps, problem by
-//     problem.  err is (n_steps, B): sweep s of problem b at err[s * B + b].
+// MsmLive                       the problem locator that runs the kernels of dff_msm.hip on many problems per launch: problem b
+//     has K_b states, its compact (K_b, K_b) matrix in slot b of Kmax^2 doubles, its vectors in slots of Kmax.  The live (not
+//     skipped) problems are a table of descriptors b * 2048 + K_b in the workspace.  dff_msm_sweep_kernel<MsmLive>: one launch
+//     per sweep, grid (ceil(max K_b / 4), live problems); dff_msm_loop_kernel<MsmLive>: one workgroup per live problem.  The
+//     same kernels as the single call's, hence its bits, problem by problem.  err is (n_steps, B): sweep s of problem b at
+//     err[s * B + b].
 #pragma once
 #include "dff_msm.hip"
 
@@ -86,76 +85,16 @@ __global__ __launch_bounds__(DFF_TC_THREADS) void dff_micro_rc_kernel(const int*
     }
 }
 
-// ---- the batched estimator.  live[p] = b << DFF_MSMB_KBITS | K_b
-__global__ __launch_bounds__(256) void dff_msmb_init_kernel(const double* __restrict__ rowc, const double* __restrict__ x,
-                                                            int Kmax, const long long* __restrict__ live,
-                                                            double* __restrict__ q) {
-    const int desc = (int)live[blockIdx.y];
-    const int b = desc >> DFF_MSMB_KBITS, K = desc & ((1 << DFF_MSMB_KBITS) - 1);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const size_t o = (size_t)b * Kmax;
-    if (i < K) q[o + i] = msm_q(rowc[o + i], x[o + i]);
-}
-
-// one sweep of every live problem: row i = 4 blockIdx.x + wave of problem live[blockIdx.y].  err: this sweep's row of B
-__global__ __launch_bounds__(DFF_MSM_THREADS) void dff_msmb_sweep_kernel(const double* __restrict__ S,
-                                                                         const double* __restrict__ rowc, int Kmax,
-                                                                         double* __restrict__ x,
-                                                                         const double* __restrict__ qin,
-                                                                         double* __restrict__ qout,
-                                                                         const long long* __restrict__ live,
-                                                                         unsigned long long* __restrict__ err) {
-    const int desc = (int)live[blockIdx.y];
-    const int b = desc >> DFF_MSMB_KBITS, K = desc & ((1 << DFF_MSMB_KBITS) - 1);
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * (DFF_MSM_THREADS / 64) + (threadIdx.x >> 6);
-    if (i >= K) return;                                             // wave-uniform
-    const size_t o = (size_t)b * Kmax;
-    double xn = msm_row(S + o * Kmax + (size_t)i * K, qin + o, qin[o + i], K, lane);
-    const double xo = x[o + i], ci = rowc[o + i];
-    if (!(ci > 0.0 && xo > 0.0)) xn = __builtin_nan("");
-    if (lane == 0) {
-        x[o + i] = xn;
-        qout[o + i] = msm_q(ci, xn);
-        msm_finish(xn, xo, err ? err + b : nullptr);
+// ---- the batched estimator: the locator of dff_msm.hip's kernels over a table of live problems, live[p] = b <<
+// DFF_MSMB_KBITS | K_b, in slots of Kmax; err is (n_steps, B)
+struct MsmLive {
+    const long long* live;
+    int Kmax, B;
+    __device__ MsmAt at(unsigned p) const {
+        const int desc = (int)live[p];
+        return {desc >> DFF_MSMB_KBITS, desc & ((1 << DFF_MSMB_KBITS) - 1)};
     }
-}
-
-// all n_steps sweeps of problem live[blockIdx.x] by one workgroup.  LDS: q ping | q pong | x (3 K_b doubles)
-__global__ __launch_bounds__(DFF_MSM_LOOP_THREADS) void dff_msmb_loop_kernel(const double* __restrict__ S,
-                                                                             const double* __restrict__ rowc, int Kmax,
-                                                                             double* __restrict__ x, int n_steps,
-                                                                             const long long* __restrict__ live, int B,
-                                                                             unsigned long long* __restrict__ err) {
-    extern __shared__ __attribute__((aligned(16))) double mqb[];
-    const int desc = (int)live[blockIdx.x];
-    const int b = desc >> DFF_MSMB_KBITS, K = desc & ((1 << DFF_MSMB_KBITS) - 1);
-    const size_t o = (size_t)b * Kmax;
-    S += o * Kmax;
-    rowc += o;
-    x += o;
-    double* qa = mqb;
-    double* qb = mqb + K;
-    double* xs = mqb + 2 * K;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < K; i += DFF_MSM_LOOP_THREADS) {
-        xs[i] = x[i];
-        qa[i] = msm_q(rowc[i], xs[i]);
-    }
-    __syncthreads();
-    for (int s = 0; s < n_steps; ++s) {
-        for (int i = wave; i < K; i += DFF_MSM_LOOP_THREADS / 64) {  // wave-uniform
-            double xn = msm_row(S + (size_t)i * K, qa, qa[i], K, lane);
-            const double xo = xs[i], ci = rowc[i];
-            if (!(ci > 0.0 && xo > 0.0)) xn = __builtin_nan("");
-            if (lane == 0) {
-                xs[i] = xn;
-                qb[i] = msm_q(ci, xn);
-                msm_finish(xn, xo, err ? err + (size_t)s * B + b : nullptr);
-            }
-        }
-        __syncthreads();
-        double* t = qa; qa = qb; qb = t;
-    }
-    for (int i = threadIdx.x; i < K; i += DFF_MSM_LOOP_THREADS) x[i] = xs[i];
-}
+    __host__ __device__ int stride() const { return Kmax; }
+    __host__ __device__ int err_stride() const { return B; }
+    static long long descriptor(int b, int K) { return ((long long)b << DFF_MSMB_KBITS) | K; }
+};

@@ -1,6 +1,6 @@
 // dff_msm_rows.h -- the arithmetic of one row of the reversible estimator's sweep, x_i' = sum_j S_ij / (q_i + q_j) with
-// q_j = c_j / x_j: ONE copy for every kernel that sweeps (dff_msm.hip: one problem; dff_msm_batch.hip: many problems per
-// launch), so that all of them give the same bits.
+// q_j = c_j / x_j: ONE copy for both drivers of dff_msm.hip (one launch per sweep; one looping workgroup), whether they run
+// on one problem or on many per launch (dff_msm_batch.hip), so that all of them give the same bits.
 #pragma once
 #include "dff_struct.hip"   // wave_sum
 

@@ -757,21 +757,31 @@ class KMeans:
     MiniBatchKMeans(max_iter=0, initial_centers=...).fit_transform call.  Points with a non-finite coordinate get label
     -1 and take part in nothing."""
 
+    # what a subclass for another pair of library calls overrides: the limit and the two calls (looked up in the binding
+    # at every call)
+    MAX_CLUSTERS = 64
+
+    def _step(self, *args, **kw):
+        return binding.kmeans_step(*args, **kw)
+
+    def _workspace_bytes(self, n, d):
+        return binding.kmeans_workspace_bytes(n, d, self.n_clusters)
+
     def __init__(self, n_clusters, max_iter=100, tolerance=1e-5, init="kmeans++", initial_centers=None, seed=0, *,
                  device="cuda:0"):
         self.n_clusters, self.max_iter, self.tolerance = int(n_clusters), int(max_iter), float(tolerance)
-        if not 1 <= self.n_clusters <= 64:
-            raise ValueError("KMeans: n_clusters must be 1..64")
+        if not 1 <= self.n_clusters <= self.MAX_CLUSTERS:
+            raise ValueError(f"{type(self).__name__}: n_clusters must be 1..{self.MAX_CLUSTERS}")
         if self.max_iter < 0:
-            raise ValueError("KMeans: max_iter must be >= 0")
+            raise ValueError(f"{type(self).__name__}: max_iter must be >= 0")
         if initial_centers is None and init != "kmeans++":
-            raise ValueError(f"KMeans: init must be 'kmeans++' (or give initial_centers), not {init!r}")
+            raise ValueError(f"{type(self).__name__}: init must be 'kmeans++' (or give initial_centers), not {init!r}")
         self.init, self.seed = init, int(seed)
         self.initial_centers = None
         if initial_centers is not None:
             c = np.array(initial_centers, np.float64)
             if c.ndim != 2 or c.shape[0] != self.n_clusters or not np.all(np.isfinite(c)):
-                raise ValueError(f"KMeans: initial_centers must be finite and ({self.n_clusters}, d)")
+                raise ValueError(f"{type(self).__name__}: initial_centers must be finite and ({self.n_clusters}, d)")
             self.initial_centers = c
         self.device = torch.device(device)
         binding.load_library()
@@ -785,11 +795,11 @@ class KMeans:
         finite = torch.isfinite(pts).all(dim=1)
         idx = torch.nonzero(finite).reshape(-1)
         if idx.numel() < K:
-            raise ValueError(f"KMeans: {int(idx.numel())} finite points for {K} clusters")
+            raise ValueError(f"{type(self).__name__}: {int(idx.numel())} finite points for {K} clusters")
         first = idx[torch.randint(int(idx.numel()), (1,), generator=gen, device=self.device)]
         centers = pts[first].clone()
         for _ in range(1, K):
-            d2 = torch.nan_to_num(binding.kmeans_step(pts, centers, accumulate=False)["dist2"], nan=0.0)
+            d2 = torch.nan_to_num(self._step(pts, centers, accumulate=False)["dist2"], nan=0.0)
             cum = torch.cumsum(d2, 0)
             u = torch.rand(1, dtype=torch.float64, generator=gen, device=self.device) * cum[-1]
             nxt = torch.searchsorted(cum, u, right=True).clamp_(max=n - 1)
@@ -803,15 +813,14 @@ class KMeans:
         n, d = int(pts.shape[0]), int(pts.shape[1])
         if self.initial_centers is not None:
             if self.initial_centers.shape[1] != d:
-                raise ValueError(f"KMeans: initial_centers are {self.initial_centers.shape}, points have d = {d}")
+                raise ValueError(f"{type(self).__name__}: initial_centers are {self.initial_centers.shape}, points have d = {d}")
             centers = self.initial_centers.copy()
         else:
             centers = self._seed_centers(pts)
-        ws = torch.empty(max(binding.kmeans_workspace_bytes(n, d, self.n_clusters), 1), dtype=torch.uint8,
-                         device=self.device)
+        ws = torch.empty(max(self._workspace_bytes(n, d), 8), dtype=torch.uint8, device=self.device)
         prev, self.n_iter = None, 0
         for _ in range(self.max_iter):
-            r = binding.kmeans_step(pts, centers, workspace=ws)
+            r = self._step(pts, centers, workspace=ws)
             sums, counts, inertia = r["sums"].cpu().numpy(), r["counts"].cpu().numpy(), float(r["inertia"][0])
             has = counts > 0
             centers = centers.copy()
@@ -821,13 +830,13 @@ class KMeans:
                 break
             prev = inertia
         self.cluster_centers = centers
-        self.inertia = float(binding.kmeans_step(pts, centers, workspace=ws)["inertia"][0])
+        self.inertia = float(self._step(pts, centers, workspace=ws)["inertia"][0])
         return self
 
     def _assign(self, pts):
         if self.cluster_centers is None:
-            raise ValueError("KMeans: not fitted")
-        return binding.kmeans_step(pts, self.cluster_centers, accumulate=False)["labels"]
+            raise ValueError(f"{type(self).__name__}: not fitted")
+        return self._step(pts, self.cluster_centers, accumulate=False)["labels"]
 
     def transform(self, points):
         """(n,) int32 labels of the nearest centre."""
@@ -1861,7 +1870,7 @@ class RelaxationEvaluator:
 # (evaluate_fastfolders.ipynb, cells 20-24); deeptime is not installed where this was written, so the semantics are
 # restated from the literature -- k-means microstates, sliding-window counts, the largest strongly connected set, the
 # reversible maximum-likelihood estimator of Bowman et al. 2009 / Prinz et al. 2011 (algorithm 1, plain form) -- and tested
-# against a from-scratch fp64 oracle (tests/msm_oracle.py).
+# against a from-scratch fp64 oracle (oracle/msm.py).
 # Out of scope: PCCA+ and other coarse-graining, mean first-passage times / transition-path theory, Bayesian posteriors (error bars: bootstrap_msm below),
 # Chapman-Kolmogorov tests, sparse count matrices.
 # =====================================================================================================
@@ -1874,26 +1883,13 @@ class MicrostateKMeans(KMeans):
     drawn so far and folds in each new centre with ONE single-centre assignment call (torch.minimum): O(n K) instead of
     O(n K^2), and the same centres as KMeans for the same seed and K <= 64."""
 
-    def __init__(self, n_clusters, max_iter=100, tolerance=1e-5, init="kmeans++", initial_centers=None, seed=0, *,
-                 device="cuda:0"):
-        self.n_clusters, self.max_iter, self.tolerance = int(n_clusters), int(max_iter), float(tolerance)
-        if not 1 <= self.n_clusters <= MSM_MAX_STATES:
-            raise ValueError(f"MicrostateKMeans: n_clusters must be 1..{MSM_MAX_STATES}")
-        if self.max_iter < 0:
-            raise ValueError("MicrostateKMeans: max_iter must be >= 0")
-        if initial_centers is None and init != "kmeans++":
-            raise ValueError(f"MicrostateKMeans: init must be 'kmeans++' (or give initial_centers), not {init!r}")
-        self.init, self.seed = init, int(seed)
-        self.initial_centers = None
-        if initial_centers is not None:
-            c = np.array(initial_centers, np.float64)
-            if c.ndim != 2 or c.shape[0] != self.n_clusters or not np.all(np.isfinite(c)):
-                raise ValueError(f"MicrostateKMeans: initial_centers must be finite and ({self.n_clusters}, d)")
-            self.initial_centers = c
-        self.device = torch.device(device)
-        binding.load_library()
-        self.cluster_centers = self.inertia = None
-        self.n_iter = 0
+    MAX_CLUSTERS = MSM_MAX_STATES
+
+    def _step(self, *args, **kw):
+        return binding.micro_kmeans_step(*args, **kw)
+
+    def _workspace_bytes(self, n, d):
+        return binding.micro_kmeans_workspace_bytes(n, d, self.n_clusters)
 
     def _seed_centers(self, pts):
         n, K = int(pts.shape[0]), self.n_clusters
@@ -1902,12 +1898,12 @@ class MicrostateKMeans(KMeans):
         finite = torch.isfinite(pts).all(dim=1)
         idx = torch.nonzero(finite).reshape(-1)
         if idx.numel() < K:
-            raise ValueError(f"MicrostateKMeans: {int(idx.numel())} finite points for {K} clusters")
+            raise ValueError(f"{type(self).__name__}: {int(idx.numel())} finite points for {K} clusters")
         first = idx[torch.randint(int(idx.numel()), (1,), generator=gen, device=self.device)]
         picks = [first]
         d2 = None
         for _ in range(1, K):
-            new = torch.nan_to_num(binding.micro_kmeans_step(pts, pts[picks[-1]], accumulate=False)["dist2"], nan=0.0)
+            new = torch.nan_to_num(self._step(pts, pts[picks[-1]], accumulate=False)["dist2"], nan=0.0)
             d2 = new if d2 is None else torch.minimum(d2, new)
             cum = torch.cumsum(d2, 0)
             u = torch.rand(1, dtype=torch.float64, generator=gen, device=self.device) * cum[-1]
@@ -1916,37 +1912,6 @@ class MicrostateKMeans(KMeans):
                 nxt = first
             picks.append(nxt)
         return pts[torch.cat(picks)].cpu().numpy()
-
-    def fit(self, points):
-        pts = _points(points, self.device)
-        n, d = int(pts.shape[0]), int(pts.shape[1])
-        if self.initial_centers is not None:
-            if self.initial_centers.shape[1] != d:
-                raise ValueError(f"MicrostateKMeans: initial_centers are {self.initial_centers.shape}, points have d = {d}")
-            centers = self.initial_centers.copy()
-        else:
-            centers = self._seed_centers(pts)
-        ws = torch.empty(max(binding.micro_kmeans_workspace_bytes(n, d, self.n_clusters), 8), dtype=torch.uint8,
-                         device=self.device)
-        prev, self.n_iter = None, 0
-        for _ in range(self.max_iter):
-            r = binding.micro_kmeans_step(pts, centers, workspace=ws)
-            sums, counts, inertia = r["sums"].cpu().numpy(), r["counts"].cpu().numpy(), float(r["inertia"][0])
-            has = counts > 0
-            centers = centers.copy()
-            centers[has] = sums[has] / counts[has, None]
-            self.n_iter += 1
-            if prev is not None and abs(prev - inertia) <= self.tolerance * prev:
-                break
-            prev = inertia
-        self.cluster_centers = centers
-        self.inertia = float(binding.micro_kmeans_step(pts, centers, workspace=ws)["inertia"][0])
-        return self
-
-    def _assign(self, pts):
-        if self.cluster_centers is None:
-            raise ValueError("MicrostateKMeans: not fitted")
-        return binding.micro_kmeans_step(pts, self.cluster_centers, accumulate=False)["labels"]
 
 
 REACH_PIVOTS, REACH_STEPS = 8, 64
@@ -2078,6 +2043,19 @@ def reversible_transition_matrix(S, c, x):
     return flow / x[:, None], x / x.sum()
 
 
+def _reversible_problem(Ca):
+    """(S, c) of the reversible estimator from the counts within the active set: S = C + C^T, c its row sums."""
+    return Ca + Ca.T, Ca.sum(axis=1)
+
+
+def _sweeps_outcome(err, tol):
+    """The stopping rule on one problem's err of a batch of sweeps -> (converged, sweeps to count, stop): converged at the
+    first sweep below tol, which is the last one counted; stop when converged or when an err is not finite."""
+    hit = np.nonzero(err < tol)[0]
+    converged = hit.size > 0
+    return converged, int(hit[0]) + 1 if converged else len(err), converged or not np.all(np.isfinite(err))
+
+
 class MarkovStateModel:
     """A Markov state model at one lag time: counts -> largest strongly connected ("active") set -> transition matrix.
 
@@ -2115,7 +2093,10 @@ class MarkovStateModel:
         counts = binding.micro_transition_counts(lab, lengths, [self.lagtime], int(n_states))
         return self.fit_counts(counts[0].cpu().numpy())
 
-    def fit_counts(self, counts):
+    def _active_counts(self, counts):
+        """The first half of fit_counts: count_matrix, active_set and active_count_share from `counts`, n_iter = 0 and
+        converged = True.  Returns the counts within the active set, from which the estimators start -- or None when the
+        active set is one state, whose model (T = [[1]]) is set here."""
         C = np.array(counts, np.float64)
         if C.ndim != 2 or C.shape[0] != C.shape[1] or C.shape[0] < 1 or not np.all(np.isfinite(C)) or (C < 0).any():
             raise ValueError("MarkovStateModel: counts must be a finite, non-negative (K, K) matrix")
@@ -2128,8 +2109,15 @@ class MarkovStateModel:
         self.n_iter, self.converged = 0, True
         if len(act) == 1:
             self.transition_matrix, self.stationary_distribution = np.ones((1, 1)), np.ones(1)
+            return None
+        return Ca
+
+    def fit_counts(self, counts):
+        Ca = self._active_counts(counts)
+        if Ca is None:
+            pass
         elif self.reversible:
-            self._fit_reversible(Ca)
+            self._fit_reversible(*_reversible_problem(Ca))
         else:
             T = transition_matrix(Ca)
             w, v = np.linalg.eig(T.T)
@@ -2137,19 +2125,15 @@ class MarkovStateModel:
             self.transition_matrix, self.stationary_distribution = T, pi / pi.sum()
         return self
 
-    def _fit_reversible(self, Ca):
-        S, c = Ca + Ca.T, Ca.sum(axis=1)
+    def _fit_reversible(self, S, c):
         x = 0.5 * S.sum(axis=1)
         sweep = reversible_sweeper(S, c, self.device)
-        self.converged = False
-        while self.n_iter < self.max_iter and not self.converged:
+        self.converged = stop = False
+        while self.n_iter < self.max_iter and not stop:
             n = min(self.steps_per_sync, self.max_iter - self.n_iter)
             x, err = sweep(x, n)
-            hit = np.nonzero(err < self.tol)[0]
-            self.converged = hit.size > 0
-            self.n_iter += int(hit[0]) + 1 if self.converged else n          # sweeps until the first one below tol
-            if not np.all(np.isfinite(err)):
-                break
+            self.converged, more, stop = _sweeps_outcome(err, self.tol)
+            self.n_iter += more
         self.transition_matrix, self.stationary_distribution = reversible_transition_matrix(S, c, x)
 
     def _need_fit(self):
@@ -2382,17 +2366,9 @@ def bootstrap_msm(labels, lagtime, traj_lengths=None, n_states=None, *, n_resamp
         models, prob = [], []                                        # prob: (model, S, c) of the resamples that iterate
         for Cb in counts:
             m = model()
-            C = np.array(Cb, np.float64)
-            m.count_matrix, m.active_set = C, largest_connected_set(C)
-            Ca = C[np.ix_(m.active_set, m.active_set)]
-            total = C.sum()
-            m.active_count_share = float(Ca.sum() / total) if total > 0 else 0.0
-            m.n_iter, m.converged = 0, True
-            if len(m.active_set) == 1:
-                m.transition_matrix, m.stationary_distribution = np.ones((1, 1)), np.ones(1)
-            else:
-                m.converged = False
-                prob.append((m, Ca + Ca.T, Ca.sum(axis=1)))
+            Ca = m._active_counts(Cb)
+            if Ca is not None:
+                prob.append((m, *_reversible_problem(Ca)))
             models.append(m)
         if prob:
             _sweep_batch(prob, batched_reversible_sweeper, dev, tol, max_iter, steps_per_sync)
@@ -2411,10 +2387,11 @@ def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
     ks = np.array([len(c) for _, _, c in prob], np.int32)
     Kmax = int(ks.max())
     S_all, c_all, x = np.zeros((P, Kmax * Kmax)), np.zeros((P, Kmax)), np.zeros((P, Kmax))
-    for p, (_, S, c) in enumerate(prob):
+    for p, (m, S, c) in enumerate(prob):
         S_all[p, :ks[p] * ks[p]] = S.reshape(-1)
         c_all[p, :ks[p]] = c
         x[p, :ks[p]] = 0.5 * S.sum(axis=1)
+        m.converged = False
     sweep = sweeper(S_all.reshape(P, Kmax, Kmax), c_all, ks, device)
     live = np.ones(P, bool)
     done = 0                                                         # sweeps every live problem has behind it
@@ -2424,11 +2401,9 @@ def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
         done += n
         for p in np.nonzero(live)[0]:
             m = prob[p][0]
-            hit = np.nonzero(err[:, p] < tol)[0]
-            m.converged = hit.size > 0
-            m.n_iter += int(hit[0]) + 1 if m.converged else n
-            if m.converged or not np.all(np.isfinite(err[:, p])):
-                live[p] = False
+            m.converged, more, stop = _sweeps_outcome(err[:, p], tol)
+            m.n_iter += more
+            live[p] = not stop
     for p, (m, S, c) in enumerate(prob):
         m.transition_matrix, m.stationary_distribution = reversible_transition_matrix(S, c, x[p, :ks[p]])
 
