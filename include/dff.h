@@ -676,6 +676,52 @@ int dff_msm_reversible_steps_batched(int device, const double* sym_dev, const do
  * sweep, 2 = one looping workgroup per problem; -1 on bad arguments. */
 int dff_msm_batched_driver_for(int B, int Kmax);
 
+/* ---- Mean first-passage times and committors of the reversible models above: the Dirichlet problem on a flux matrix, P
+ * problems per call, one workgroup per problem (csrc/dff_msm_passage.hip; evaluate.py: mfpt, committor, reactive_flux,
+ * bootstrap_passage) ----
+ * Problem p has K_p = ks_host[p] states, a symmetric non-negative flux matrix X (only its relative scale matters), a role per
+ * state (0 = interior, 1 = boundary), boundary values g and a source s, and asks for u with
+ *   u_i = g_i on the boundary,     sum_{j != i} X_ij (u_i - u_j) = (sum_j X_ij) s_i on every interior state,
+ * which is (u - T u)_i = s_i for T_ij = X_ij / sum_j X_ij.  The mean first-passage time to a set: boundary = the set, g = 0,
+ * s = the lag time.  The committor from A to B: boundary = A and B, g = 1 on B and 0 on A, s = 0.
+ * flux_dev (n_flux, Kmax, Kmax) fp64: matrix m is a COMPACT (K, K) row-major matrix at flux_dev + m Kmax^2; problem p reads
+ * matrix flux_of_host[p] (NULL: matrix p, n_flux >= P) as (K_p, K_p), so the problems that share a matrix have the same K_p.
+ * role_dev int32, g_dev, s_dev, u_dev fp64: (P, Kmax), problem p in the first K_p entries of row p; g is read at boundary states
+ * only, s at interior states only, u is written at 0 .. K_p - 1 only.  status_dev (P) int32:
+ *    0      solved (also when every state is boundary: u = g)
+ *   -1      no boundary state                                                    u = NaN over 0 .. K_p - 1
+ *   -2      a role outside {0, 1} (it wins over -1)                              u = NaN
+ *   1 + i   the pivot of state i (full index) was not a finite positive number   u = NaN
+ * The interior indices are compacted in index order, W = diag(d) - offdiag(X_II) is formed with d_i = sum_{j != i} X_ij SUMMED
+ * over the whole row (never as a difference of two nearly equal numbers; in ONE order: 64 partial sums, partial l over
+ * j = l, l + 64, ..., then a butterfly -- on an ill-conditioned W another order of this sum moves the exact solution by more
+ * than a good solver's error), b_i = (d_i + X_ii) s_i + sum_{j boundary} X_ij g_j, and W = L D L^T is factored without pivoting
+ * and without square roots (the pivots are D's entries), followed by the two substitutions.  Besides the row sums only the lower
+ * triangle of X_II is read: an asymmetric X is not detected as such.  The pivot of state i fails when it is not finite or not
+ * above n 2^-52 d_i (n the interior count): an interior component that cannot reach the boundary is singular in exact arithmetic
+ * and leaves a pivot of rounding size, zero or below, while the pivots of a connected problem stay above that guard up to
+ * cond(W) ~ 1 / (n 2^-52).  It also fails when the state's row, X_ii included, or its b_i (g, s) holds a NaN or an infinity:
+ * status 0 never comes with a NaN in u.  A failed problem touches no other.  After a solved problem of the blocked path the first
+ * four doubles of its slice of the workspace hold, for benchmarks, the 100 MHz ticks spent in formation, panels, trailing updates
+ * and back substitution.  Up to dff_msm_dirichlet_lds_limit interior states the triangle is factored in LDS; above, a blocked
+ * right-looking factorisation (panels of 32 columns, 64 x 64 trailing tiles on the fp64 VALU) runs in the problem's slice of the
+ * workspace.  The bits of a problem's u and status follow from its own inputs and from the path alone: not from P, its place in
+ * the batch, its neighbours, the workspace's prior contents or the call; the two paths need not agree bit for bit.
+ * 1 <= K_p <= Kmax <= DFF_MSM_MAXK, 1 <= P <= 16384, 1 <= n_flux <= 16384; device pointers, `stream` only, no read-back, refusals on
+ * the host before any device call, no atomics, no workgroup waits on another.  workspace_dev 8-byte aligned, contents irrelevant. */
+/* Bytes of device workspace the call below needs (P descriptors and P slices of Kmax (Kmax + 32) doubles); -1 on bad arguments. */
+long long dff_msm_dirichlet_workspace_bytes(int P, int Kmax);
+/* The largest interior count that is factored out of LDS (a compile-time constant). */
+int dff_msm_dirichlet_lds_limit(void);
+int dff_msm_dirichlet_solve(int device, const double* flux_dev, int n_flux, const int32_t* flux_of_host, const int32_t* ks_host,
+                            int P, int Kmax, const int32_t* role_dev, const double* g_dev, const double* s_dev, double* u_dev,
+                            int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* For tests and benchmarks, process-wide: 0 = the path follows the interior count (the default), 1 = every problem in LDS (a call
+ * with a K_p above the limit + 1 is then refused), 2 = every problem on the blocked path; 3 and 4 = as 2, with the trailing update
+ * on the fp64 VALU (3) or on v_mfma_f64_16x16x4_f64 (4) instead of the library's choice between them.  The two trailing updates
+ * sum in different orders: each gives its own, reproducible bits. */
+int dff_debug_msm_dirichlet_path(int path);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -13,6 +13,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
                                  [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
                                  [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
+                                 [--passage [HELDOUT.pt] --passage-states K --passage-lag L [--passage-cv q|rmsd]
+                                  [--passage-cores LO,HI] [--passage-bootstrap B]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]]
 
@@ -330,6 +332,40 @@ def msm(a, x):
     return res
 
 
+def passage_arguments(a):
+    """(states, lag, cv, (lo, hi)) of --passage, None without it; refused without --passage-states / --passage-lag, --folded-pdb, --parallel-sim,
+    and (for the RMSD) --passage-cores; the options of --passage are refused without it"""
+    if a.passage is None:
+        if any(v is not None for v in (a.passage_states, a.passage_lag, a.passage_cv, a.passage_cores, a.passage_bootstrap)):
+            raise SystemExit("--passage-states, --passage-lag, --passage-cv, --passage-cores and --passage-bootstrap need --passage")
+        return None
+    if a.passage_states is None or a.passage_lag is None:
+        raise SystemExit("--passage needs --passage-states K and --passage-lag L (frames)")
+    if not a.folded_pdb:
+        raise SystemExit("--passage needs --folded-pdb")
+    if a.parallel_sim is None:
+        raise SystemExit("--passage needs --parallel-sim (the trajectories of the samples)")
+    cv = a.passage_cv or "q"
+    if a.passage_cores is None and cv != "q":
+        raise SystemExit("--passage-cv rmsd needs --passage-cores LO,HI (Angstrom)")
+    return a.passage_states, a.passage_lag, cv, a.passage_cores or (0.2, 0.9)
+
+
+def passage(a, x):
+    K, lag, cv, (lo, hi) = passage_arguments(a)
+    ref, ref_lengths = ordered_frames(a.passage) if a.passage else (None, None)
+    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
+    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+    ev = evaluate.MsmPassageEvaluator(a.mol.lower(), tica, a.folded_pdb, n_microstates=K, lagtime=lag, cv=cv, lo=lo, hi=hi,
+                                      frame_time=a.frame_time, ref_data=ref, ref_traj_lengths=ref_lengths,
+                                      n_bootstrap=a.passage_bootstrap or 0, device=a.device)
+    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
+    res = {k: clean(v) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
+    res.update({"n_microstates": K, "lagtime": lag, "cv": cv, "lo": lo, "hi": hi, "frame_time": a.frame_time,
+                "n_bootstrap": a.passage_bootstrap or 0})
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -400,6 +436,18 @@ def build_parser():
                     help="resample blocks of F frames instead of whole trajectories (with --msm-bootstrap)")
     ap.add_argument("--msm-confidence", type=msm_confidence, default=None, metavar="C",
                     help="confidence level of the percentile intervals, default 0.95 (with --msm-bootstrap)")
+    ap.add_argument("--passage", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report mean first-passage times, rates and the committor between the folded and the unfolded "
+                         "microstates of a Markov state model (time-ordered Langevin samples; needs --folded-pdb, --parallel-sim, "
+                         "--passage-states and --passage-lag); with HELDOUT.pt also for that MD data, which then defines the states")
+    ap.add_argument("--passage-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --passage)")
+    ap.add_argument("--passage-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --passage)")
+    ap.add_argument("--passage-cv", choices=("q", "rmsd"), default=None,
+                    help="order parameter that sorts the microstates: fraction of native contacts (default) or RMSD (with --passage)")
+    ap.add_argument("--passage-cores", type=cores, default=None, metavar="LO,HI",
+                    help="a microstate is in a set when its mean cv is <= LO or >= HI (with --passage; 0.2,0.9 for q)")
+    ap.add_argument("--passage-bootstrap", type=msm_bootstrap, default=None, metavar="B",
+                    help="bootstrap error bars of the times and rates from B resamples of the trajectories (with --passage)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -422,6 +470,7 @@ def main():
     if a.msm is not None:
         msm_arguments(a)
     msm_bootstrap_arguments(a)
+    passage_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -455,6 +504,8 @@ def main():
         res["relaxation"] = relaxation(a, x)
     if a.msm is not None:
         res["msm"] = msm(a, x)
+    if a.passage is not None:
+        res["passage"] = passage(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

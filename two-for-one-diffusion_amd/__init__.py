@@ -20,6 +20,7 @@ __all__ += ["native_pairs", "native_contacts_q", "core_states", "label_runs", "d
 __all__ += ["autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator"]
 __all__ += ["MicrostateKMeans", "largest_connected_set", "MarkovStateModel", "implied_timescales", "MsmEvaluator"]
 __all__ += ["resampling_units", "bootstrap_weights", "bootstrap_msm", "MsmBootstrap", "implied_timescales_bootstrap"]
+__all__ += ["mfpt", "committor", "reactive_flux", "ReactiveFlux", "bootstrap_passage", "PassageBootstrap", "states_by_cv", "dirichlet_solver", "MsmPassageEvaluator"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use
@@ -51,6 +52,9 @@ def __getattr__(name):  # torch-dependent pieces are imported on first use
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("resampling_units", "bootstrap_weights", "bootstrap_msm", "MsmBootstrap", "implied_timescales_bootstrap"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("mfpt", "committor", "reactive_flux", "ReactiveFlux", "bootstrap_passage", "PassageBootstrap", "states_by_cv", "dirichlet_solver", "MsmPassageEvaluator"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("eval_loss", "loss_profile"):

@@ -135,6 +135,11 @@ SYMBOLS = {
     "dff_msm_reversible_steps_batched": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_size_t,
                                                    _P]),
     "dff_msm_batched_driver_for": (C.c_int, [C.c_int, C.c_int]),
+    "dff_msm_dirichlet_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_msm_dirichlet_lds_limit": (C.c_int, []),
+    "dff_msm_dirichlet_solve": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                          _P]),
+    "dff_debug_msm_dirichlet_path": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1142,3 +1147,63 @@ def msm_batched_driver_for(B: int, Kmax: int) -> int:
     if r < 0:
         _check(lib, 1, "dff_msm_batched_driver_for")
     return r
+
+
+# ---- mean first-passage times and committors: the Dirichlet problem on a flux matrix (dff_msm_dirichlet_solve) ----
+MSM_DIRICHLET_MAX_BATCH = 16384
+
+
+def msm_dirichlet_workspace_bytes(P: int, Kmax: int) -> int:
+    return _workspace_bytes("dff_msm_dirichlet_workspace_bytes", int(P), int(Kmax))
+
+
+def msm_dirichlet_lds_limit() -> int:
+    """The largest interior count dff_msm_dirichlet_solve factors out of LDS, read from the library."""
+    return int(load_library().dff_msm_dirichlet_lds_limit())
+
+
+def debug_msm_dirichlet_path(path: int):
+    """Tests and benchmarks only: 0 = by the interior count, 1 = every problem in LDS, 2 = every problem on the blocked path."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_msm_dirichlet_path(int(path)), "dff_debug_msm_dirichlet_path")
+
+
+def msm_dirichlet_solve(flux, ks, role, g, s, flux_of=None, u=None, workspace=None):
+    """P Dirichlet problems on flux matrices in one call (dff_msm_dirichlet_solve): flux (M, Kmax, Kmax) contiguous float64
+    CUDA, matrix m a COMPACT (K, K) matrix at the start of its slot; ks (P,) host integers; role int32, g and s float64, each
+    (P, Kmax) contiguous CUDA with problem p in the first ks[p] entries of its row; flux_of (P,) host integers, the matrix of
+    each problem (None: problem p reads matrix p).  Returns (u float64 (P, Kmax), status int32 (P,)), CUDA tensors: u holds
+    g on the boundary and the solution on the interior, NaN over a failed problem; beyond ks[p] a row of u is left alone (NaN
+    when u is allocated here).  status: 0 solved, -1 no boundary state, -2 a bad role, 1 + i the pivot of state i failed.
+    Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    P, Kmax = (int(role.shape[0]), int(role.shape[1])) if isinstance(role, torch.Tensor) and role.dim() == 2 else (-1, -1)
+    M = int(flux.shape[0]) if isinstance(flux, torch.Tensor) and flux.dim() == 3 else -1
+    f64 = torch.float64
+    if not (_is_tensor(role, torch.int32, (P, Kmax)) and _is_tensor(flux, f64, (M, Kmax, Kmax)) and _is_tensor(g, f64, (P, Kmax))
+            and _is_tensor(s, f64, (P, Kmax)) and flux.device == role.device and g.device == role.device
+            and s.device == role.device):
+        raise ValueError("flux (M, Kmax, Kmax), g and s (P, Kmax) must be contiguous float64 and role (P, Kmax) contiguous int32 "
+                         "CUDA tensors on one device")
+    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+    if kh.size != P:
+        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
+    fh = None
+    if flux_of is not None:
+        fh = np.ascontiguousarray(np.asarray(flux_of, dtype=np.int32).reshape(-1))
+        if fh.size != P:
+            raise ValueError(f"flux_of must hold one matrix index per problem: {fh.size} for P = {P}")
+    if u is None:
+        u = torch.full((P, Kmax), float("nan"), dtype=f64, device=role.device)
+    elif not (_is_tensor(u, f64, (P, Kmax)) and u.device == role.device):
+        raise ValueError("u must be a contiguous float64 CUDA tensor of shape (P, Kmax) on the roles' device")
+    status = torch.empty(P, dtype=torch.int32, device=role.device)
+    if workspace is None:
+        need = msm_dirichlet_workspace_bytes(P, Kmax)
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=role.device)
+    _check(lib, lib.dff_msm_dirichlet_solve(role.device.index, _ptr(flux), M, fh.ctypes.data_as(C.c_void_p) if fh is not None else None,
+                                            kh.ctypes.data_as(C.c_void_p), P, Kmax, _ptr(role), _ptr(g), _ptr(s), _ptr(u),
+                                            _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                            _stream(role)), "dff_msm_dirichlet_solve")
+    return u, status

@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* and their batched counterparts), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts and dff_msm_dirichlet_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <vector>
@@ -16,6 +16,7 @@
 #include "dff_autocorr.hip"
 #include "dff_msm.hip"
 #include "dff_msm_batch.hip"
+#include "dff_msm_passage.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1213,4 +1214,82 @@ extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, c
     const int n_live = (int)live.size();
     return msm_sweeps(stream, MsmLive{live_dev, Kmax, B}, msm_driver(kmax_live, n_live), kmax_live, (unsigned)n_live, sym, rowc, x,
                       n_steps, q0, q0 + (size_t)B * Kmax, (unsigned long long*)err);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Mean first-passage times and committors: the Dirichlet problem on a flux matrix (dff_msm_passage.hip)
+// ---------------------------------------------------------------------------------------------
+// which path factors a problem: 0 = by its interior count, 1 = LDS, 2 = the blocked one in the workspace
+static std::atomic<int> g_dir_path{0};
+
+extern "C" int dff_debug_msm_dirichlet_path(int path) {
+    if (path < 0 || path > 4)
+        return fail(DFF_EINVAL, "debug_msm_dirichlet_path: 0 (by size), 1 (LDS), 2 (global), 3 (global, VALU) or 4 (global, MFMA)");
+    g_dir_path.store(path);
+    return DFF_OK;
+}
+
+extern "C" int dff_msm_dirichlet_lds_limit(void) { return DFF_DIR_LDS_LIMIT; }
+
+static int dir_check_batch(int P, int Kmax, const char* what) {
+    if (P < 1 || P > DFF_DIR_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_DIR_MAXP);
+    return micro_check_count(Kmax, what, "states");
+}
+
+extern "C" long long dff_msm_dirichlet_workspace_bytes(int P, int Kmax) {
+    if (dir_check_batch(P, Kmax, "msm_dirichlet_workspace_bytes")) return -1;
+    return (long long)P * (1 + dir_slice_doubles(Kmax)) * (long long)sizeof(double);   // descriptors | one slice per problem
+}
+
+extern "C" int dff_msm_dirichlet_solve(int device, const double* flux, int n_flux, const int32_t* flux_of, const int32_t* ks,
+                                       int P, int Kmax, const int32_t* role, const double* g, const double* s, double* u,
+                                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "msm_dirichlet_solve";
+    int rc = dir_check_batch(P, Kmax, what);
+    if (rc) return rc;
+    if (n_flux < 1 || n_flux > DFF_DIR_MAXP) return fail(DFF_EINVAL, "%s: the number of flux matrices must be 1..%d", what, DFF_DIR_MAXP);
+    if (!flux || !ks || !role || !g || !s || !u || !status)
+        return fail(DFF_EINVAL, "%s: null flux / state counts / roles / boundary values / sources / u / status", what);
+    if (!flux_of && n_flux < P) return fail(DFF_EINVAL, "%s: %d flux matrices for %d problems and no flux_of", what, n_flux, P);
+    const int knob = g_dir_path.load();
+    const int path = knob > 2 ? 2 : knob;                             // 3 and 4: the blocked path with a named trailing update
+    const int mfma = knob == 3 ? 0 : (knob == 4 ? 1 : DFF_DIR_MFMA);
+    int kmax_live = 0;
+    for (int p = 0; p < P; ++p) {
+        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
+        if (flux_of && (flux_of[p] < 0 || flux_of[p] >= n_flux))
+            return fail(DFF_EINVAL, "%s: problem %d takes flux matrix %d of %d", what, p, (int)flux_of[p], n_flux);
+        if (path == 1 && ks[p] > DFF_DIR_LDS_LIMIT + 1)
+            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_DIR_LDS_LIMIT + 1);
+        if (ks[p] > kmax_live) kmax_live = ks[p];
+    }
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_dirichlet_workspace_bytes(P, Kmax), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<long long> desc((size_t)P);
+    for (int p = 0; p < P; ++p) desc[p] = ((long long)(flux_of ? flux_of[p] : p) << DFF_DIR_KBITS) | ks[p];
+    long long* desc_dev = (long long*)workspace;
+    if ((rc = msmb_upload(stream, desc.data(), P, desc_dev))) return rc;
+    double* work = (double*)(desc_dev + P);
+    const long long slice = dir_slice_doubles(Kmax);
+    if (path != 2) {                                                  // interior counts 0 .. the limit (all of them when forced)
+        const int nl = kmax_live - 1 < DFF_DIR_LDS_LIMIT ? kmax_live - 1 : DFF_DIR_LDS_LIMIT;
+        const size_t lds = dir_lds_bytes(nl);
+        if (lds > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_dir_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_dir_kernel<true>, dim3((unsigned)P), dim3(DFF_DIR_THREADS), (unsigned)lds, stream, flux,
+                           (const long long*)desc_dev, Kmax, role, g, s, u, status, work, slice, 0,
+                           path == 1 ? 0x7fffffff : DFF_DIR_LDS_LIMIT, mfma);
+        HIPCHK(hipGetLastError());
+    }
+    if (path == 2 || (path == 0 && kmax_live > DFF_DIR_LDS_LIMIT)) {  // the rest (an interior count above the limit needs K_p above it)
+        HIPCHK(hipFuncSetAttribute((const void*)&dff_dir_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)dir_blocked_lds_bytes()));    // 71 168 bytes: above the 64 KB a launch gets unasked
+        hipLaunchKernelGGL(dff_dir_kernel<false>, dim3((unsigned)P), dim3(DFF_DIR_THREADS), (unsigned)dir_blocked_lds_bytes(), stream,
+                           flux, (const long long*)desc_dev, Kmax, role, g, s, u, status, work, slice,
+                           path == 2 ? 0 : DFF_DIR_LDS_LIMIT + 1, 0x7fffffff, mfma);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
 }

@@ -2034,13 +2034,26 @@ def reversible_sweeper(S, c, device):
     return _DeviceSweeps(S, c, device)
 
 
-def reversible_transition_matrix(S, c, x):
-    """T_ij = S_ij / (c_i / x_i + c_j / x_j) / x_i and pi = x / sum x from a (converged) x: numpy, one K^2 expression."""
+def _reversible_flow(S, c, x):
+    """The symmetric flow S_ij / (c_i / x_i + c_j / x_j) of the estimator at x (its row sums are x at the fixed point)."""
     S, c, x = np.asarray(S, np.float64), np.asarray(c, np.float64), np.asarray(x, np.float64)
     q = c / x
     den = q[:, None] + q[None, :]
-    flow = np.divide(S, den, out=np.zeros_like(S), where=S != 0)
+    return np.divide(S, den, out=np.zeros_like(S), where=S != 0), x
+
+
+def reversible_transition_matrix(S, c, x):
+    """T_ij = S_ij / (c_i / x_i + c_j / x_j) / x_i and pi = x / sum x from a (converged) x: numpy, one K^2 expression."""
+    flow, x = _reversible_flow(S, c, x)
     return flow / x[:, None], x / x.sum()
+
+
+def reversible_model(S, c, x):
+    """(T, pi, X) from one evaluation of the flow: reversible_transition_matrix's T and pi, and the flow scaled to sum 1,
+    X_ij = pi_i T_ij of the converged estimator, symmetric by construction (MarkovStateModel.flux_matrix; what mfpt, committor
+    and reactive_flux solve on)."""
+    flow, x = _reversible_flow(S, c, x)
+    return flow / x[:, None], x / x.sum(), flow / flow.sum()
 
 
 def _reversible_problem(Ca):
@@ -2068,7 +2081,9 @@ class MarkovStateModel:
     fit(labels, traj_lengths=None, n_states=None) counts sliding-window transitions at `lagtime` on the GPU (labels < 0
     are skipped; n_states defaults to max(label) + 1); fit_counts(counts) starts from a (K, K) count matrix.  Afterwards:
     count_matrix (K, K, all states), active_set (sorted indices), active_count_share (the counts that stay inside the
-    active set over all counts), transition_matrix and stationary_distribution (on the active set), n_iter, converged."""
+    active set over all counts), transition_matrix and stationary_distribution (on the active set), n_iter, converged, and
+    flux_matrix: the symmetric flow S_ij / (c_i / x_i + c_j / x_j) of the converged estimator scaled to sum 1 (pi_i T_ij on the
+    active set; None with reversible=False)."""
 
     def __init__(self, lagtime, reversible=True, tol=1e-12, max_iter=1_000_000, steps_per_sync=256, *, device="cuda:0"):
         self.lagtime = int(lagtime)
@@ -2080,6 +2095,7 @@ class MarkovStateModel:
             raise ValueError("MarkovStateModel: tol must be > 0, max_iter >= 0 and steps_per_sync >= 1")
         self.device = torch.device(device)
         self.transition_matrix = self.stationary_distribution = self.active_set = self.count_matrix = None
+        self.flux_matrix = None
         self.active_count_share, self.n_iter, self.converged = float("nan"), 0, False
 
     def fit(self, labels, traj_lengths=None, n_states=None):
@@ -2107,8 +2123,10 @@ class MarkovStateModel:
         total = C.sum()
         self.active_count_share = float(Ca.sum() / total) if total > 0 else 0.0
         self.n_iter, self.converged = 0, True
+        self.flux_matrix = None
         if len(act) == 1:
             self.transition_matrix, self.stationary_distribution = np.ones((1, 1)), np.ones(1)
+            self.flux_matrix = np.ones((1, 1)) if self.reversible else None
             return None
         return Ca
 
@@ -2134,7 +2152,7 @@ class MarkovStateModel:
             x, err = sweep(x, n)
             self.converged, more, stop = _sweeps_outcome(err, self.tol)
             self.n_iter += more
-        self.transition_matrix, self.stationary_distribution = reversible_transition_matrix(S, c, x)
+        self.transition_matrix, self.stationary_distribution, self.flux_matrix = reversible_model(S, c, x)
 
     def _need_fit(self):
         if self.transition_matrix is None:
@@ -2323,61 +2341,83 @@ def bootstrap_msm(labels, lagtime, traj_lengths=None, n_states=None, *, n_resamp
     leaving the batch at its first sweep below tol.  Resample b equals
     MarkovStateModel(lagtime, tol=tol, max_iter=max_iter, steps_per_sync=steps_per_sync).fit_counts(counts_b) bit for bit.
     resample_batch bounds the resamples in flight (default: B K^2 counts and matrices under 1 GiB each) -> MsmBootstrap."""
-    dev = torch.device(device)
-    lab = torch.as_tensor(labels).reshape(-1)
-    n = int(lab.numel())
-    lengths = _check_lengths(traj_lengths, n)
-    if n_states is None:
-        n_states = int(lab.max()) + 1 if n else 0
-    K = int(n_states)
-    if not 1 <= K <= MSM_MAX_STATES:
-        raise ValueError(f"bootstrap_msm: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
-    proto = MarkovStateModel(lagtime, True, tol, max_iter, steps_per_sync, device=dev)          # checks the settings
     k = int(k)
     if k < 1:
         raise ValueError("bootstrap_msm: k must be >= 1")
-    units = resampling_units(lengths, block_frames)
-    if units.size < 1:
-        raise ValueError("bootstrap_msm: no resampling units (no frames)")
-    if weights is None:
-        w = bootstrap_weights(units.size, n_resamples, seed)
-    else:
-        w = np.asarray(weights)
-        if w.ndim != 2 or w.shape[1] != units.size or w.shape[0] < 1 or (w < 0).any() or (w > 2 ** 32 - 1).any():
-            raise ValueError(f"bootstrap_msm: weights must be (B, {units.size}) multiplicities in 0 .. 2^32 - 1")
-        w = w.astype(np.uint32)
-    B = int(w.shape[0])
-    if resample_batch is None:
-        resample_batch = max(1, min(B, MSM_MAX_BATCH, (1 << 30) // (8 * K * K)))
-    rb = int(resample_batch)
-    if not 1 <= rb <= MSM_MAX_BATCH:
-        raise ValueError(f"bootstrap_msm: resample_batch must be 1..{MSM_MAX_BATCH}")
-    count = resampled_counter(lab, lengths, units, proto.lagtime, K, dev)
-
-    def model():
-        return MarkovStateModel(proto.lagtime, True, tol, max_iter, steps_per_sync, device=dev)
-    point = model().fit_counts(count(np.ones((1, units.size), np.uint32))[0])
+    plan = _BootstrapPlan("bootstrap_msm", labels, lagtime, traj_lengths, n_states, n_resamples, block_frames, seed, weights, tol,
+                          max_iter, steps_per_sync, resample_batch, device)
+    B, K = plan.B, plan.K
+    point = plan.point()
     ts = np.full((B, k), np.nan)
     stationary = np.zeros((B, K))
     n_active, share = np.zeros(B, np.int64), np.zeros(B)
     converged, n_iter = np.zeros(B, bool), np.zeros(B, np.int64)
-    for b0 in range(0, B, rb):
-        counts = count(w[b0:b0 + rb])
-        models, prob = [], []                                        # prob: (model, S, c) of the resamples that iterate
-        for Cb in counts:
-            m = model()
-            Ca = m._active_counts(Cb)
-            if Ca is not None:
-                prob.append((m, *_reversible_problem(Ca)))
-            models.append(m)
-        if prob:
-            _sweep_batch(prob, batched_reversible_sweeper, dev, tol, max_iter, steps_per_sync)
+    for b0, models in plan.batches():
         for i, m in enumerate(models):
             b = b0 + i
             ts[b] = m.timescales(k)
             stationary[b, m.active_set] = m.stationary_distribution
             n_active[b], share[b], converged[b], n_iter[b] = len(m.active_set), m.active_count_share, m.converged, m.n_iter
-    return MsmBootstrap(ts, stationary, n_active, share, converged, n_iter, w, units, point)
+    return MsmBootstrap(ts, stationary, n_active, share, converged, n_iter, plan.weights, plan.units, point)
+
+
+class _BootstrapPlan:
+    """What bootstrap_msm and bootstrap_passage share: the checked arguments, the units and their multiplicities, the counter,
+    and batches(): the fitted reversible models of the resamples, resample_batch at a time, as (first resample, models)."""
+
+    def __init__(self, what, labels, lagtime, traj_lengths, n_states, n_resamples, block_frames, seed, weights, tol, max_iter,
+                 steps_per_sync, resample_batch, device):
+        self.device = dev = torch.device(device)
+        lab = torch.as_tensor(labels).reshape(-1)
+        n = int(lab.numel())
+        lengths = _check_lengths(traj_lengths, n)
+        if n_states is None:
+            n_states = int(lab.max()) + 1 if n else 0
+        self.K = K = int(n_states)
+        if not 1 <= K <= MSM_MAX_STATES:
+            raise ValueError(f"{what}: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+        proto = MarkovStateModel(lagtime, True, tol, max_iter, steps_per_sync, device=dev)          # checks the settings
+        self.lagtime, self.settings = proto.lagtime, (tol, max_iter, steps_per_sync)
+        self.units = units = resampling_units(lengths, block_frames)
+        if units.size < 1:
+            raise ValueError(f"{what}: no resampling units (no frames)")
+        if weights is None:
+            w = bootstrap_weights(units.size, n_resamples, seed)
+        else:
+            w = np.asarray(weights)
+            if w.ndim != 2 or w.shape[1] != units.size or w.shape[0] < 1 or (w < 0).any() or (w > 2 ** 32 - 1).any():
+                raise ValueError(f"{what}: weights must be (B, {units.size}) multiplicities in 0 .. 2^32 - 1")
+            w = w.astype(np.uint32)
+        self.weights, self.B = w, int(w.shape[0])
+        if resample_batch is None:
+            resample_batch = max(1, min(self.B, MSM_MAX_BATCH, (1 << 30) // (8 * K * K)))
+        self.rb = int(resample_batch)
+        if not 1 <= self.rb <= MSM_MAX_BATCH:
+            raise ValueError(f"{what}: resample_batch must be 1..{MSM_MAX_BATCH}")
+        self.count = resampled_counter(lab, lengths, units, proto.lagtime, K, dev)
+
+    def model(self):
+        tol, max_iter, steps_per_sync = self.settings
+        return MarkovStateModel(self.lagtime, True, tol, max_iter, steps_per_sync, device=self.device)
+
+    def point(self):
+        """the model of the unresampled counts"""
+        return self.model().fit_counts(self.count(np.ones((1, self.units.size), np.uint32))[0])
+
+    def batches(self):
+        tol, max_iter, steps_per_sync = self.settings
+        for b0 in range(0, self.B, self.rb):
+            counts = self.count(self.weights[b0:b0 + self.rb])
+            models, prob = [], []                                    # prob: (model, S, c) of the resamples that iterate
+            for Cb in counts:
+                m = self.model()
+                Ca = m._active_counts(Cb)
+                if Ca is not None:
+                    prob.append((m, *_reversible_problem(Ca)))
+                models.append(m)
+            if prob:
+                _sweep_batch(prob, batched_reversible_sweeper, self.device, tol, max_iter, steps_per_sync)
+            yield b0, models
 
 
 def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
@@ -2405,7 +2445,7 @@ def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
             m.n_iter += more
             live[p] = not stop
     for p, (m, S, c) in enumerate(prob):
-        m.transition_matrix, m.stationary_distribution = reversible_transition_matrix(S, c, x[p, :ks[p]])
+        m.transition_matrix, m.stationary_distribution, m.flux_matrix = reversible_model(S, c, x[p, :ks[p]])
 
 
 def implied_timescales_bootstrap(labels, lagtimes, traj_lengths=None, n_states=None, k=3, *, n_resamples=100,
@@ -2553,4 +2593,372 @@ class MsmEvaluator:
                     r = np.where((a > 0) & (b > 0), np.log10(a / b), np.nan)
                 lo, hi = percentile_interval(r, self.confidence)
                 res["log10_timescale_ratio_lo"], res["log10_timescale_ratio_hi"] = [float(v) for v in lo], [float(v) for v in hi]
+        return res
+
+
+# ---- mean first-passage times, committors and reactive flux of a Markov state model ----
+# Each quantity is one Dirichlet problem on the model's flux matrix X_ij = pi_i T_ij (dff_msm_dirichlet_solve): the states of
+# the target sets are the boundary, the rest of the active set the interior.  Sets are given on the FULL state index of the
+# count matrix; states outside the active set are dropped.
+DIRICHLET_MAX_BATCH = binding.MSM_DIRICHLET_MAX_BATCH
+DIRICHLET_BYTES = 1 << 30        # flux matrices plus workspace of one dff_msm_dirichlet_solve call of dirichlet_solver
+
+
+class _DeviceDirichlet:
+    """solve(flux, flux_of, ks, role, g, s) -> (u (P, Kmax), status (P,)), host arrays in and out: the problems go to the GPU
+    in chunks whose flux matrices and workspace stay under DIRICHLET_BYTES, each chunk one dff_msm_dirichlet_solve call."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def __call__(self, flux, flux_of, ks, role, g, s):
+        role = np.ascontiguousarray(role, np.int32)
+        P, Kmax = role.shape
+        flux = np.ascontiguousarray(flux, np.float64).reshape(-1, Kmax, Kmax)
+        flux_of, ks = np.asarray(flux_of, np.int64).reshape(-1), np.asarray(ks, np.int32).reshape(-1)
+        g, s = np.ascontiguousarray(g, np.float64), np.ascontiguousarray(s, np.float64)
+        per = 8 * (2 * Kmax * Kmax + 33 * Kmax + 1)                  # a matrix of its own and a slice of the workspace
+        chunk = max(1, min(DIRICHLET_MAX_BATCH, DIRICHLET_BYTES // per))
+        u, status = np.full((P, Kmax), np.nan), np.zeros(P, np.int32)
+        for p0 in range(0, P, chunk):
+            sl = slice(p0, min(P, p0 + chunk))
+            used, local = np.unique(flux_of[sl], return_inverse=True)
+            dev = self.device
+            ud, sd = binding.msm_dirichlet_solve(torch.from_numpy(flux[used]).to(dev), ks[sl], torch.from_numpy(role[sl]).to(dev),
+                                                 torch.from_numpy(g[sl]).to(dev), torch.from_numpy(s[sl]).to(dev),
+                                                 flux_of=local.astype(np.int32))
+            u[sl], status[sl] = ud.cpu().numpy(), sd.cpu().numpy()
+        return u, status
+
+
+def dirichlet_solver(device):
+    """solve(flux (M, Kmax, Kmax), flux_of (P,), ks (P,), role, g, s (P, Kmax)) -> (u (P, Kmax), status (P,)) on the GPU
+    (dff_msm_dirichlet_solve); matrix m is a compact (K, K) matrix at the start of its slot."""
+    return _DeviceDirichlet(device)
+
+
+def _active_states(model, states, what, name):
+    """indices within the active set of the states of `states` (full index) that are active; ValueError when none is"""
+    model._need_fit()
+    st = np.unique(np.asarray(states, np.int64).reshape(-1))
+    if st.size and (st[0] < 0 or st[-1] >= len(model.count_matrix)):
+        raise ValueError(f"{what}: {name} holds a state outside 0 .. {len(model.count_matrix) - 1}")
+    idx = np.flatnonzero(np.isin(model.active_set, st))
+    if idx.size == 0:
+        raise ValueError(f"{what}: {name} has no state in the active set")
+    return idx
+
+
+def _passage_problems(model, A, B, what):
+    """The three problems of a pair of disjoint sets on one model, as rows (role, g, s): MFPT to B, MFPT to A, committor A -> B."""
+    a, b = _active_states(model, A, what, "A"), _active_states(model, B, what, "B")
+    if np.intersect1d(a, b).size:
+        raise ValueError(f"{what}: A and B overlap")
+    K = len(model.active_set)
+    role, g, s = np.zeros((3, K), np.int32), np.zeros((3, K)), np.zeros((3, K))
+    role[0, b] = role[1, a] = role[2, a] = role[2, b] = 1
+    s[:2] = float(model.lagtime)
+    g[2, b] = 1.0
+    return a, b, role, g, s
+
+
+def _host_dirichlet(T, role, g, s):
+    """The fallback for a model without detailed balance: np.linalg.solve on (I - T_II) u_I = s_I + T_IB g_B."""
+    I, Bd = np.flatnonzero(role == 0), np.flatnonzero(role == 1)
+    u = np.where(role == 1, g, 0.0)
+    if I.size:
+        u[I] = np.linalg.solve(np.eye(I.size) - T[np.ix_(I, I)], s[I] + T[np.ix_(I, Bd)] @ g[Bd])
+    return u
+
+
+def _solve_on_model(model, role, g, s, what):
+    """u (P, K) of P problems on one fitted model: the GPU call on its flux matrix, or the host fallback (reversible=False)"""
+    if model.flux_matrix is None:
+        return np.stack([_host_dirichlet(model.transition_matrix, r, gg, ss) for r, gg, ss in zip(role, g, s)])
+    P, K = role.shape
+    u, status = dirichlet_solver(model.device)(model.flux_matrix.reshape(1, K, K), np.zeros(P, np.int64), np.full(P, K, np.int32),
+                                               role, g, s)
+    if (status != 0).any():
+        raise ValueError(f"{what}: the linear system of problem {int(np.flatnonzero(status)[0])} failed (status "
+                         f"{int(status[status != 0][0])}): the flux matrix is not that of a connected reversible model")
+    return u
+
+
+def mfpt(model, target, source=None):
+    """Mean first-passage times to the set `target` of a fitted MarkovStateModel, in frames: float64 (n_active,), zero on the
+    target -- or, with `source`, their stationary-weighted mean over that set (a float).  Sets are state indices of the count
+    matrix; states outside the active set are dropped.  ValueError when a set has no active state or the two overlap.
+    reversible=True: one dff_msm_dirichlet_solve problem on model.flux_matrix; reversible=False: np.linalg.solve on I - T_II on
+    the host (the device call needs the symmetry of detailed balance)."""
+    t = _active_states(model, target, "mfpt", "target")
+    src = None
+    if source is not None:
+        src = _active_states(model, source, "mfpt", "source")
+        if np.intersect1d(src, t).size:
+            raise ValueError("mfpt: source and target overlap")
+    K = len(model.active_set)
+    role = np.zeros((1, K), np.int32)
+    role[0, t] = 1
+    m = _solve_on_model(model, role, np.zeros((1, K)), np.full((1, K), float(model.lagtime)), "mfpt")[0]
+    if src is None:
+        return m
+    pi = model.stationary_distribution[src]
+    return float(np.dot(pi, m[src]) / pi.sum())
+
+
+def committor(model, A, B):
+    """The forward committor from A to B of a fitted MarkovStateModel: q (n_active,), the probability of reaching B before A,
+    0 on A and 1 on B.  The backward committor of a reversible model is 1 - q.  Sets and paths as mfpt."""
+    _, _, role, g, s = _passage_problems(model, A, B, "committor")
+    return _solve_on_model(model, role[2:], g[2:], s[2:], "committor")[0]
+
+
+class ReactiveFlux:
+    """What reactive_flux returns: committor q (n_active,), net_flux (n_active, n_active) f+_ij = max(0, X_ij (q_j - q_i)),
+    total_flux F = sum_{i in A, j not in A} X_ij q_j, rate k_AB = F / (lagtime sum_i pi_i (1 - q_i)) per frame."""
+
+    def __init__(self, committor, net_flux, total_flux, rate):
+        self.committor, self.net_flux, self.total_flux, self.rate = committor, net_flux, float(total_flux), float(rate)
+
+
+def _reactive_flux(X, pi, q, a, lagtime):
+    """transition-path theory of a reversible model from its flux matrix, stationary distribution and forward committor"""
+    net = np.maximum(0.0, X * (q[None, :] - q[:, None]))
+    out = np.ones(len(q), bool)
+    out[a] = False
+    F = float((X[np.ix_(a, np.flatnonzero(out))] @ q[out]).sum())
+    return ReactiveFlux(q, net, F, F / (float(lagtime) * float(np.dot(pi, 1.0 - q))))
+
+
+def reactive_flux(model, A, B):
+    """Transition-path theory from A to B on a fitted reversible MarkovStateModel -> ReactiveFlux."""
+    if model.flux_matrix is None:
+        model._need_fit()
+        raise ValueError("reactive_flux: needs a reversible model (its flux matrix)")
+    a, _, role, g, s = _passage_problems(model, A, B, "reactive_flux")
+    q = _solve_on_model(model, role[2:], g[2:], s[2:], "reactive_flux")[0]
+    return _reactive_flux(model.flux_matrix, model.stationary_distribution, q, a, model.lagtime)
+
+
+class PassageBootstrap:
+    """What bootstrap_passage returns.  mfpt_ab, mfpt_ba (frames), rate_ab, rate_ba (per frame): (B,), NaN where a resample has
+    no answer (a set without an active state, a failed system); committor (B, K) on the full state index, NaN outside a
+    resample's active set; converged (B,); weights, unit_lengths as resampled; point: a dict of the same quantities of the
+    unresampled model ("model": the MarkovStateModel)."""
+
+    FIELDS = ("mfpt_ab", "mfpt_ba", "rate_ab", "rate_ba")
+
+    def __init__(self, mfpt_ab, mfpt_ba, rate_ab, rate_ba, committor, converged, weights, unit_lengths, point):
+        self.mfpt_ab, self.mfpt_ba, self.rate_ab, self.rate_ba = mfpt_ab, mfpt_ba, rate_ab, rate_ba
+        self.committor, self.converged, self.weights, self.unit_lengths, self.point = committor, converged, weights, unit_lengths, point
+
+    def _table(self):
+        return np.stack([getattr(self, f) for f in self.FIELDS], axis=1)
+
+    @property
+    def n_failed(self):
+        """Resamples whose estimator did not converge or that lack one of the four numbers."""
+        return int(np.sum(~self.converged | ~np.isfinite(self._table()).all(axis=1)))
+
+    def std(self):
+        """{field: standard deviation (ddof = 1) over the resamples where it is finite}; NaN below two."""
+        return dict(zip(self.FIELDS, (float(v) for v in percentile_std(self._table()))))
+
+    def interval(self, confidence=0.95):
+        """{field: (lo, hi)}: the percentile interval over the resamples where the field is finite."""
+        lo, hi = percentile_interval(self._table(), confidence)
+        return {f: (float(a), float(b)) for f, a, b in zip(self.FIELDS, lo, hi)}
+
+
+def _passage_batch(models, A, B, K_full, device):
+    """mfpt A -> B, mfpt B -> A, rates and the committor of every model of `models`: ONE dirichlet_solver call with three
+    problems per model that has both sets, each model's flux matrix shared by its three -> rows (len(models), 4), committor
+    (len(models), K_full)."""
+    out, comm = np.full((len(models), 4), np.nan), np.full((len(models), K_full), np.nan)
+    todo = []
+    for i, m in enumerate(models):
+        try:
+            todo.append((i, m) + _passage_problems(m, A, B, "bootstrap_passage"))
+        except ValueError:
+            continue                                                 # a set lost all its states in this resample
+    if not todo:
+        return out, comm
+    Kmax = max(len(m.active_set) for _, m, *_ in todo)
+    P = 3 * len(todo)
+    flux = np.zeros((len(todo), Kmax * Kmax))
+    role, g, s = np.ones((P, Kmax), np.int32), np.zeros((P, Kmax)), np.zeros((P, Kmax))
+    ks = np.zeros(P, np.int32)
+    for n, (i, m, a, b, r3, g3, s3) in enumerate(todo):
+        K = len(m.active_set)
+        flux[n, :K * K] = m.flux_matrix.reshape(-1)
+        role[3 * n:3 * n + 3, :K], g[3 * n:3 * n + 3, :K], s[3 * n:3 * n + 3, :K], ks[3 * n:3 * n + 3] = r3, g3, s3, K
+    u, status = dirichlet_solver(device)(flux.reshape(len(todo), Kmax, Kmax), np.repeat(np.arange(len(todo)), 3), ks, role, g, s)
+    for n, (i, m, a, b, *_ ) in enumerate(todo):
+        K = len(m.active_set)
+        if (status[3 * n:3 * n + 3] != 0).any():
+            continue
+        pi = m.stationary_distribution
+        m_ab, m_ba, q = u[3 * n, :K], u[3 * n + 1, :K], u[3 * n + 2, :K]
+        out[i, 0] = np.dot(pi[a], m_ab[a]) / pi[a].sum()
+        out[i, 1] = np.dot(pi[b], m_ba[b]) / pi[b].sum()
+        out[i, 2] = _reactive_flux(m.flux_matrix, pi, q, a, m.lagtime).rate
+        out[i, 3] = _reactive_flux(m.flux_matrix, pi, 1.0 - q, b, m.lagtime).rate
+        comm[i, m.active_set] = q
+    return out, comm
+
+
+def bootstrap_passage(labels, lagtime, A, B, traj_lengths=None, n_states=None, *, n_resamples=100, block_frames=None, seed=0,
+                      weights=None, tol=1e-12, max_iter=1_000_000, steps_per_sync=256, resample_batch=None, device="cuda:0"):
+    """Bootstrap of the passage between the state sets A and B of a reversible MarkovStateModel at `lagtime`: the resamples of
+    bootstrap_msm (the same units, draws and estimator, batch by batch), and per resample the stationary-weighted MFPT from A
+    to B and from B to A, the transition-path rates both ways and the committor -- all 3 x (resamples of a batch) linear
+    systems in one dff_msm_dirichlet_solve call, each resample's flux matrix shared by its three.  Resample b equals mfpt /
+    committor on MarkovStateModel(...).fit_counts(counts_b) bit for bit -> PassageBootstrap."""
+    plan = _BootstrapPlan("bootstrap_passage", labels, lagtime, traj_lengths, n_states, n_resamples, block_frames, seed, weights, tol,
+                          max_iter, steps_per_sync, resample_batch, device)
+    A, B_ = np.unique(np.asarray(A, np.int64).reshape(-1)), np.unique(np.asarray(B, np.int64).reshape(-1))
+    for name, st in (("A", A), ("B", B_)):
+        if st.size == 0 or st[0] < 0 or st[-1] >= plan.K:
+            raise ValueError(f"bootstrap_passage: {name} must hold states in 0 .. {plan.K - 1}")
+    if np.intersect1d(A, B_).size:
+        raise ValueError("bootstrap_passage: A and B overlap")
+    pm = plan.point()
+    prow, pcomm = _passage_batch([pm], A, B_, plan.K, plan.device)
+    point = dict(zip(PassageBootstrap.FIELDS, (float(v) for v in prow[0])), committor=pcomm[0], model=pm)
+    rows, comm = np.full((plan.B, 4), np.nan), np.full((plan.B, plan.K), np.nan)
+    converged = np.zeros(plan.B, bool)
+    for b0, models in plan.batches():
+        rows[b0:b0 + len(models)], comm[b0:b0 + len(models)] = _passage_batch(models, A, B_, plan.K, plan.device)
+        converged[b0:b0 + len(models)] = [m.converged for m in models]
+    return PassageBootstrap(rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], comm, converged, plan.weights, plan.units, point)
+
+
+def states_by_cv(labels, cv, lo, hi, n_states):
+    """(A, B): the microstates whose mean collective variable over their member frames is <= lo, or >= hi (int64 arrays).
+    labels (n,) integers (< 0: left out), cv (n,); the means are taken with torch on the device the cv lives on (frames with a
+    non-finite cv are left out); a state without frames is in neither set."""
+    lo, hi = _check_cores(lo, hi, "states_by_cv")
+    n_states = int(n_states)
+    if not 1 <= n_states <= MSM_MAX_STATES:
+        raise ValueError(f"states_by_cv: n_states must be 1..{MSM_MAX_STATES}")
+    cv = torch.as_tensor(cv).reshape(-1).to(torch.float64)
+    lab = torch.as_tensor(labels).reshape(-1).to(device=cv.device, dtype=torch.int64)
+    if lab.numel() != cv.numel():
+        raise ValueError(f"states_by_cv: {lab.numel()} labels for {cv.numel()} values")
+    ok = (lab >= 0) & (lab < n_states) & torch.isfinite(cv)
+    sums = torch.zeros(n_states, dtype=torch.float64, device=cv.device).index_add_(0, lab[ok], cv[ok])
+    cnt = torch.zeros(n_states, dtype=torch.float64, device=cv.device).index_add_(0, lab[ok], torch.ones_like(cv[ok]))
+    mean = (sums / cnt).cpu().numpy()                                 # NaN for a state without frames: in neither set
+    return np.flatnonzero(mean <= lo).astype(np.int64), np.flatnonzero(mean >= hi).astype(np.int64)
+
+
+class MsmPassageEvaluator:
+    """How long does folding take in the sampled dynamics, and through which states does it go?  Frames -> TIC projection and
+    k-means microstates (MsmEvaluator's: `tica`, n_microstates, centers, seed) and the order parameter of
+    FoldingKineticsEvaluator (`folded`, cv="q" or "rmsd") -> the folded and the unfolded SETS of microstates, those whose mean
+    order parameter lies in the folded or the unfolded core (states_by_cv with lo, hi; taken from the reference when there is
+    ref_data, else from the first samples, and kept) -> a reversible MarkovStateModel at `lagtime` -> mfpt, committor and
+    reactive_flux between the two sets.
+
+    eval(xyz, traj_lengths=None) -- None: ONE trajectory -- returns a dict of floats, times in units of frame_time:
+      mfpt_folding, mfpt_unfolding      stationary-weighted mean first-passage time unfolded -> folded set and back
+      rate_folding, rate_unfolding      transition-path-theory rates k_AB (per frame_time)
+      n_folded_states, n_unfolded_states   states of each set inside the model's active set
+      committor_mid_share               stationary mass of the states with 0.4 < q < 0.6
+      samples_nonfinite                 frames left out (a non-finite projection)
+    NaN where a set has no active state.  With ref_data the same keys with the suffix _ref and log10_mfpt_ratio_folding /
+    log10_mfpt_ratio_unfolding (samples over reference).  n_bootstrap > 0 adds, from bootstrap_passage over the trajectories or
+    blocks of block_frames frames, <key>_lo / _hi (the percentile interval at `confidence`) and <key>_std for the two times and
+    the two rates, and bootstrap_failed.  The models stay on .models, the committors on .committors, the bootstraps on
+    .bootstraps, under "samples" / "refs".  Without the HIP library: DffLibraryError."""
+
+    KEYS = ("mfpt_folding", "mfpt_unfolding", "rate_folding", "rate_unfolding", "n_folded_states", "n_unfolded_states",
+            "committor_mid_share", "samples_nonfinite")
+    BARS = (("mfpt_folding", "mfpt_ab"), ("mfpt_unfolding", "mfpt_ba"), ("rate_folding", "rate_ab"), ("rate_unfolding", "rate_ba"))
+
+    def __init__(self, mol_name, tica, folded, n_microstates=200, lagtime=None, cv="q", lo=0.2, hi=0.9, frame_time=1.0,
+                 ref_data=None, ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None,
+                 confidence=0.95, bootstrap_seed=0, device="cuda:0"):
+        self.discretiser = MsmEvaluator(mol_name, tica, n_microstates, lagtime, 1, frame_time, centers=centers, seed=seed,
+                                        n_bootstrap=n_bootstrap, block_frames=block_frames, confidence=confidence,
+                                        bootstrap_seed=bootstrap_seed, device=device)          # checks these arguments
+        self.order = FoldingKineticsEvaluator(mol_name, folded, cv=cv, lo=lo, hi=hi, frame_time=frame_time, device=device)
+        d = self.discretiser
+        self.mol_name, self.device, self.lagtime, self.n_microstates, self.frame_time = mol_name, d.device, d.lagtime, d.n_microstates, d.frame_time
+        self.n_bootstrap, self.block_frames, self.confidence, self.bootstrap_seed = d.n_bootstrap, d.block_frames, d.confidence, d.bootstrap_seed
+        self.folded_states = self.unfolded_states = None
+        self.models, self.labels, self.committors, self.bootstraps = {}, {}, {}, {}
+        self.ref_result = None
+        if ref_data is not None:
+            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
+                ref_data = ref_data[:][0]
+            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+
+    @property
+    def centers(self):
+        return self.discretiser.centers
+
+    def discretise(self, x):
+        """(labels int32 (n,), order parameter (n,)) of frames already on the device; the first call fits the centres"""
+        d = self.discretiser
+        proj = d.project(x)
+        if d.centers is None:
+            d.kmeans = MicrostateKMeans(d.n_microstates, seed=d.seed, device=d.device).fit(proj)
+            d.centers = d.kmeans.cluster_centers
+        return binding.micro_kmeans_step(proj, d.centers, accumulate=False)["labels"], self.order.order_parameter(x)
+
+    @staticmethod
+    def summarize(model, row, committor, folded_states, unfolded_states, frame_time=1.0, samples_nonfinite=0):
+        """eval()'s dict from a fitted model, its (mfpt_ab, mfpt_ba, rate_ab, rate_ba) in frames with A the unfolded set, and its
+        committor on the full index: numpy only."""
+        q = committor[model.active_set]
+        mid = (q > 0.4) & (q < 0.6)
+        return {"mfpt_folding": float(row[0]) * frame_time, "mfpt_unfolding": float(row[1]) * frame_time,
+                "rate_folding": float(row[2]) / frame_time, "rate_unfolding": float(row[3]) / frame_time,
+                "n_folded_states": float(np.isin(model.active_set, folded_states).sum()),
+                "n_unfolded_states": float(np.isin(model.active_set, unfolded_states).sum()),
+                "committor_mid_share": float(model.stationary_distribution[mid].sum()) if np.isfinite(q).all() else float("nan"),
+                "samples_nonfinite": float(samples_nonfinite)}
+
+    def _analyse(self, xyz, traj_lengths, name):
+        x = _frames(xyz, self.device)
+        lengths = _check_lengths(traj_lengths, len(x))
+        labels, cv = self.discretise(x)
+        if self.folded_states is None:
+            low, high = states_by_cv(labels, cv, self.order.lo, self.order.hi, self.n_microstates)
+            self.unfolded_states, self.folded_states = (low, high) if self.order.cv == "q" else (high, low)
+        U, F = self.unfolded_states, self.folded_states
+        bs = None
+        if U.size == 0 or F.size == 0:                               # no state reaches a core: nothing to solve
+            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+            row, comm = np.full(4, np.nan), np.full(self.n_microstates, np.nan)
+        elif self.n_bootstrap > 0:
+            bs = bootstrap_passage(labels, self.lagtime, U, F, lengths, self.n_microstates, n_resamples=self.n_bootstrap,
+                                   block_frames=self.block_frames, seed=self.bootstrap_seed + (name == "refs"), device=self.device)
+            self.bootstraps[name] = bs
+            model, comm = bs.point["model"], bs.point["committor"]
+            row = np.array([bs.point[f] for f in PassageBootstrap.FIELDS])
+        else:
+            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+            rows, comms = _passage_batch([model], U, F, self.n_microstates, self.device)
+            row, comm = rows[0], comms[0]
+        self.models[name], self.labels[name], self.committors[name] = model, labels.cpu().numpy(), comm
+        res = self.summarize(model, row, comm, F, U, self.frame_time, int((labels < 0).sum()))
+        if bs is not None:
+            iv, sd = bs.interval(self.confidence), bs.std()
+            for key, field in self.BARS:
+                scale = self.frame_time if key.startswith("mfpt") else 1.0 / self.frame_time
+                res[key + "_lo"], res[key + "_hi"], res[key + "_std"] = iv[field][0] * scale, iv[field][1] * scale, sd[field] * scale
+            res["bootstrap_failed"] = float(bs.n_failed)
+        return res
+
+    def eval(self, xyz, traj_lengths=None):
+        res = self._analyse(xyz, traj_lengths, "samples")
+        if self.ref_result is not None:
+            ref = self.ref_result
+            res.update({k + "_ref": v for k, v in ref.items()})
+            for which in ("folding", "unfolding"):
+                a, b = res[f"mfpt_{which}"], ref[f"mfpt_{which}"]
+                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
+                res[f"log10_mfpt_ratio_{which}"] = float(np.log10(a / b)) if ok else float("nan")
         return res
