@@ -34,6 +34,8 @@ CPU restatements of the reference's sampling hot path (microsoft/two-for-one-dif
   connected set, the reversible estimator's sweeps.
 * ``msm_bootstrap``   -- the bootstrap of ``msm``: weighted counts pair by pair, the pipeline per resample, and the numpy
   stand-ins the host tests put behind the device seams.
+* ``passage``         -- the Dirichlet problem of ``dff_msm_dirichlet_solve`` in numpy: the fp64 system, a longdouble-refined
+  truth, error measures, and the kernel's elimination as the stand-in behind ``evaluate.dirichlet_solver``.
 
 The analysis modules need numpy and torch-CPU only and never import ``dff_amd``.
 

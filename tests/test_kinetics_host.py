@@ -321,3 +321,15 @@ def test_kinetics_arguments():
             ap.parse_args(["s.pt", "chignolin", "refs", "--kinetics"] + bad)
     with pytest.raises(SystemExit):                                                         # the RMSD has no default cores
         tool.kinetics_cores(ap.parse_args(["s.pt", "chignolin", "refs", "--kinetics", "--kinetics-cv", "rmsd"]))
+
+
+def test_log10_ratio_is_nan_unless_both_are_finite_and_positive():
+    assert evaluate._log10_ratio(2, 1) == np.log10(2.0) and evaluate._log10_ratio(1.0, 4.0) == np.log10(0.25)
+    for a, b in ((0, 1), (1, 0), (NAN, 1), (INF, 1), (-1, 1), (1, NAN), (1, INF), (1, -1)):
+        assert np.isnan(evaluate._log10_ratio(a, b)), (a, b)
+    got = evaluate._log10_ratio([2.0, 0.0, 1.0, NAN], [1.0, 1.0, 0.0, 1.0])
+    assert got[0] == np.log10(2.0) and np.isnan(got[1:]).all() and len(got) == 4 and isinstance(got, list)
+    assert evaluate._log10_ratio([], []) == []
+    for a, b in (([1.0, 2.0], 1.0), (1.0, [1.0]), ([1.0, 2.0], [1.0])):
+        with pytest.raises(ValueError):
+            evaluate._log10_ratio(a, b)

@@ -379,6 +379,27 @@ def test_evaluator_without_bootstrap_is_unchanged_and_with_it_gains_exactly_the_
             host_evaluator(**kw)
 
 
+class FramesDataset:
+    """dataset-like: [:] is a tuple whose first entry is the frames, as the reference's datasets give them"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def __getitem__(self, i):
+        return self.frames[i], None
+
+
+@pytest.mark.parametrize("n_bootstrap", [0, 3])
+def test_reference_as_tensor_array_or_dataset_gives_one_reference_result(host_evaluator, n_bootstrap):
+    labels, lengths, _ = five_state_case()
+    frames = frames_of(labels)
+    got = [host_evaluator(ref_data=form, ref_traj_lengths=lengths, n_bootstrap=n_bootstrap).ref_result
+           for form in (torch.from_numpy(frames), frames, FramesDataset(frames))]
+    assert got[0] is not None and set(evaluate.MsmEvaluator.KEYS) <= set(got[0])
+    assert repr(got[0]) == repr(got[1]) == repr(got[2])                                      # repr: NaN compares equal to itself
+    assert host_evaluator(ref_data=None).ref_result is None
+
+
 def test_msm_bootstrap_arguments_of_the_tool():
     import tools_eval_samples as tool
     ap = tool.build_parser()

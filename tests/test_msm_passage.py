@@ -1,7 +1,7 @@
 """dff_msm_dirichlet_solve on the GPU (csrc/dff_msm_passage.hip) and evaluate.mfpt / committor / reactive_flux /
 bootstrap_passage / MsmPassageEvaluator on top of it.
 
-What is compared how (tests/passage_oracle.py holds the numpy side; the kernel is never its own reference):
+What is compared how (oracle/passage.py holds the numpy side; the kernel is never its own reference):
 - backward error   eta = |b - W u|_inf / (|W|_inf |u|_inf + |b|_inf), in longdouble from the kernel's inputs and output, against
                    n (3 n + 1) 2^-53: Higham's bound of a Cholesky solve, gamma_(3n+1) |L||L^T|, with the factor n of the norm
                    equivalence.  Derived, not tuned.
@@ -25,7 +25,7 @@ VALU and with the MFMA trailing update, debug paths 3 and 4, and both meet every
   of 0.7 .. 5.2 and a numpy copy of the kernel's elimination 1.0 .. 10.3, all with backward errors of a few 2^-53
   (test_msm_passage_host.py::test_forward_ratios_scatter_on_the_bridge reproduces the table): the ratio of two such draws is
   not a property of the elimination.  What DID lose accuracy and was fixed rather than accommodated: with d_i summed in
-  np.sum's order instead of the call's, the two exact solutions already differ by 18 x LAPACK's error (passage_oracle.row_sums).
+  np.sum's order instead of the call's, the two exact solutions already differ by 18 x LAPACK's error (oracle.passage.row_sums).
 """
 import ctypes as C
 import functools
@@ -34,9 +34,9 @@ import numpy as np
 import pytest
 import torch
 
-import passage_oracle as po
 from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
+from oracle import passage as po
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)
@@ -499,3 +499,52 @@ def test_passage_evaluator_on_a_two_well_jump_process(dev):
                                      lo=0.3 * rmsd_between, hi=0.7 * rmsd_between, frame_time=FRAME_TIME, centers=e.centers)
     old = plain.eval(x, [1500] * 20)
     assert set(old) == keys and {k: res[k] for k in keys} == old      # the bootstrap does not move the point estimates
+
+
+def test_the_evaluators_agree_on_what_they_share(dev):
+    """The four trajectory evaluators on one input -- 4 trajectories of 300 frames, 8 microstates for two wells, frame 7 all
+    NaN -- give the same bits wherever they state the same step: the order parameter, the microstate labels, the fitted
+    centres, the count of frames left out and the refusal of frames with another bead count."""
+    paths = oracle.jump_process(M_WELLS, 4, 300, 21)
+    base = synth_chain_frames(2, BEADS, 91).astype(np.float64)
+    noise = np.random.default_rng(22).standard_normal((paths.size, BEADS, 3))
+    x = (base[paths.reshape(-1)] + 0.05 * noise).astype(np.float32)
+    x[7] = np.nan
+    lengths = [300] * 4
+    F = B().struct_tic_num_features(BEADS)
+    rng = np.random.default_rng(17)
+    tica = (rng.uniform(0.0, 10.0, F), rng.uniform(-0.1, 0.1, (F, 2)))
+    folded = base[0].astype(np.float32)
+    rmsd_between = float(ev().kabsch_rmsd64(base[0], base[1]))
+    cores = {"q": (0.2, 0.9), "rmsd": (0.3 * rmsd_between, 0.7 * rmsd_between)}
+    nine = x[:, :9].copy()
+    only_frame_7 = np.arange(len(x)) == 7
+
+    fitted = ev().MsmEvaluator("chignolin", tica, n_microstates=STATES, lagtime=LAGTIME, seed=5)
+    results = [fitted.eval(x, lengths)]
+    msm = ev().MsmEvaluator("chignolin", tica, n_microstates=STATES, lagtime=LAGTIME, centers=fitted.centers)
+    results.append(msm.eval(x, lengths))
+    assert fitted.kmeans is not None and msm.kmeans is None and same_bits(fitted.labels["samples"], msm.labels["samples"])
+    for cv, (lo, hi) in cores.items():
+        kin = ev().FoldingKineticsEvaluator("chignolin", folded, cv=cv, lo=lo, hi=hi)
+        rel = ev().RelaxationEvaluator("chignolin", folded, cv=cv, max_lag=10)
+        refit = ev().MsmPassageEvaluator("chignolin", tica, folded, n_microstates=STATES, lagtime=LAGTIME, cv=cv, lo=lo, hi=hi, seed=5)
+        given = ev().MsmPassageEvaluator("chignolin", tica, folded, n_microstates=STATES, lagtime=LAGTIME, cv=cv, lo=lo, hi=hi,
+                                         centers=fitted.centers)
+        results += [kin.eval(x, lengths), rel.eval(x, lengths), refit.eval(x, lengths), given.eval(x, lengths)]
+        series = kin.series["samples"]["cv"]
+        assert np.array_equal(np.isnan(series), only_frame_7), cv
+        assert same_bits(series, rel.series["samples"]), cv                                      # equal series
+        labels, order = given.discretise(to_dev(x))
+        assert same_bits(series, order.cpu().numpy()), cv
+        assert same_bits(msm.labels["samples"], given.labels["samples"]) and same_bits(given.labels["samples"], labels.cpu().numpy()), cv
+        assert np.array_equal(given.labels["samples"] == -1, only_frame_7), cv                   # equal labels, one frame left out
+        assert refit.kmeans is not None and same_bits(fitted.centers, refit.centers), cv         # equal centres from equal seeds
+        for e in (kin, rel, given):
+            with pytest.raises(ValueError):
+                e.eval(nine, lengths)                                                            # wrong bead count
+    assert [r["samples_nonfinite"] for r in results] == [1.0] * len(results)
+    tic = ev().RelaxationEvaluator("chignolin", cv="tic", tica=tica, max_lag=10)
+    assert tic.eval(x, lengths)["samples_nonfinite"] == 1.0
+    with pytest.raises(ValueError):
+        tic.eval(nine, lengths)                                                                  # refused by the projection call

@@ -1,6 +1,6 @@
 """Host side of the passage feature: the symbols and refusals of dff_msm_dirichlet_solve (refused on the host, before any
 device call), MarkovStateModel.flux_matrix, mfpt / committor / reactive_flux / bootstrap_passage on a numpy stand-in behind
-evaluate.dirichlet_solver (tests/passage_oracle.py) on hand cases, the reversible=False fallback, set validation, states_by_cv,
+evaluate.dirichlet_solver (oracle/passage.py) on hand cases, the reversible=False fallback, set validation, states_by_cv,
 the PassageBootstrap statistics, MsmPassageEvaluator's reductions, the re-exports and the tool's arguments.  No GPU."""
 import ctypes as C
 import os
@@ -11,10 +11,10 @@ import pytest
 import torch
 
 import dff_amd
-import passage_oracle as po
 from dff_amd import binding, evaluate
 from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
+from oracle import passage as po
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_msm_dirichlet_workspace_bytes", "dff_msm_dirichlet_lds_limit", "dff_msm_dirichlet_solve", "dff_debug_msm_dirichlet_path")
@@ -337,6 +337,24 @@ def test_the_evaluators_reductions(on_oracle):
         F = binding.DFF_MAX_BEADS
         with pytest.raises(ValueError):
             evaluate.MsmPassageEvaluator("chignolin", (np.zeros(F), np.zeros((F, 1))), np.zeros((10, 3)), device="cpu", **kw)
+
+
+def test_the_passage_evaluator_builds_no_other_evaluator(monkeypatch):
+    monkeypatch.setattr(binding, "load_library", lambda *a, **k: None)
+    built = []
+    for cls in (evaluate.MsmEvaluator, evaluate.FoldingKineticsEvaluator):
+        def counted(self, *a, _init=cls.__init__, _name=cls.__name__, **k):
+            built.append(_name)
+            _init(self, *a, **k)
+        monkeypatch.setattr(cls, "__init__", counted)
+    F = binding.DFF_MAX_BEADS
+    tica = (np.zeros(F), np.zeros((F, 1)))
+    e = evaluate.MsmPassageEvaluator("chignolin", tica, np.zeros((10, 3)), n_microstates=3, lagtime=2, centers=np.zeros((3, 1)), device="cpu")
+    assert built == [] and e.centers.shape == (3, 1) and e.kmeans is None and (e.lo, e.hi, e.cv) == (0.2, 0.9, "q")
+    assert not hasattr(e, "discretiser") and not hasattr(e, "order")
+    evaluate.MsmEvaluator("chignolin", tica, lagtime=2, device="cpu")
+    evaluate.FoldingKineticsEvaluator("chignolin", np.zeros((10, 3)), lo=0.2, hi=0.9, device="cpu")
+    assert built == ["MsmEvaluator", "FoldingKineticsEvaluator"]                                   # the count does count
 
 
 # ---------------------------------------------------------------- the tool

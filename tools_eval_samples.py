@@ -19,8 +19,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
-list of them, in time order) and writes it to SAVED_REF_DIR as saved_TICA_{MOL}_{evalset}.npz; --ref-data is then the
-validation data it is histogrammed on.
+list of them, in time order) and writes it to SAVED_REF_DIR as the .npz that tica_path() below names; --ref-data is then
+the validation data it is histogrammed on.
 
 --transitions adds the dynamics analysis of evaluate_fastfolders.ipynb (StateTransitionEvaluator) for time-ordered
 Langevin samples: state assignments in the plane of MOL's TICA model, transition counts and probabilities per lag time.
@@ -90,16 +90,49 @@ def traj_lengths(a, n):
     return [L] * (n // L)
 
 
+def tica_path(a):
+    """MOL's saved TICA model in SAVED_REF_DIR: the .npz when there is one, else the reference's pickle"""
+    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
+    return stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+
+
+def clean(v):
+    """v as JSON can carry it: a non-finite number becomes None, a list goes element by element"""
+    if isinstance(v, list):
+        return [clean(u) for u in v]
+    return None if not np.isfinite(v) else float(v)
+
+
+def cleaned(res):
+    """an evaluator's dict of numbers and lists of numbers, every value through clean()"""
+    return {k: clean(v) for k, v in res.items()}
+
+
+def number(parse, ok, message, unparsed=None):
+    """an argparse type: parse(text), int or float, refused with `message` unless ok(value); text that does not parse is
+    refused with `unparsed`, or with `message` too when there is none ({text!r} in either stands for the text)"""
+    def convert(text):
+        try:
+            v = parse(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError((unparsed or message).format(text=text))
+        if not ok(v):
+            raise argparse.ArgumentTypeError(message.format(text=text))
+        return v
+    return convert
+
+
+NOT_A_NUMBER, NOT_AN_INTEGER = "not a number: {text!r}", "not an integer: {text!r}"
+
+
 def transitions(a, x):
     mol = a.mol.lower()
-    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
-    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
     fit = torch.load(a.centers_fit_data, map_location="cpu").float() if a.centers_fit_data else None
-    st = evaluate.StateTransitionEvaluator(mol, tica, n_clusters=a.n_clusters, fit_data=fit, device=a.device)
+    st = evaluate.StateTransitionEvaluator(mol, tica_path(a), n_clusters=a.n_clusters, fit_data=fit, device=a.device)
     r = st.eval(x, traj_lengths=traj_lengths(a, len(x)), lagtimes=[int(v) for v in a.lagtimes.split(",")])
     return {"centers": st.centers.tolist(), "lagtimes": r["lagtimes"], "populations": r["populations"].tolist(),
             "count_matrices": r["count_matrices"].tolist(), "transition_matrices": r["transition_matrices"].tolist(),
-            "timescales": [[None if not np.isfinite(v) else float(v) for v in t] for t in r["timescales"]]}
+            "timescales": [clean(list(t)) for t in r["timescales"]]}
 
 
 def rmsd_thresholds(text):
@@ -136,14 +169,7 @@ def flexibility(a, x):
     return res
 
 
-def cluster_cutoff(text):
-    try:
-        v = float(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
-    if not (np.isfinite(v) and v >= 0):
-        raise argparse.ArgumentTypeError("the cutoff must be finite and >= 0")
-    return v
+cluster_cutoff = number(float, lambda v: np.isfinite(v) and v >= 0, "the cutoff must be finite and >= 0", NOT_A_NUMBER)
 
 
 def clusters(a, x):
@@ -166,14 +192,7 @@ def cores(text):
     return lo, hi
 
 
-def frame_time(text):
-    try:
-        v = float(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
-    if not (np.isfinite(v) and v > 0):
-        raise argparse.ArgumentTypeError("the frame time must be finite and > 0")
-    return v
+frame_time = number(float, lambda v: np.isfinite(v) and v > 0, "the frame time must be finite and > 0", NOT_A_NUMBER)
 
 
 def kinetics_cores(a):
@@ -182,38 +201,6 @@ def kinetics_cores(a):
     if a.kinetics_cv != "q":
         raise SystemExit("--kinetics-cv rmsd needs --kinetics-cores LO,HI (Angstrom)")
     return 0.2, 0.9
-
-
-def kinetics(a, x):
-    lo, hi = kinetics_cores(a)
-    ref, ref_lengths = None, None
-    if a.kinetics:
-        ref = torch.load(a.kinetics, map_location="cpu")
-        if not isinstance(ref, torch.Tensor):
-            trajs = [torch.as_tensor(t).float() for t in ref]
-            ref, ref_lengths = torch.cat(trajs), [len(t) for t in trajs]
-        ref = ref.float()
-    ev = evaluate.FoldingKineticsEvaluator(a.mol.lower(), a.folded_pdb, cv=a.kinetics_cv, lo=lo, hi=hi, frame_time=a.frame_time,
-                                           ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
-    res = {k: (None if not np.isfinite(v) else float(v)) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
-    res.update({"cv": a.kinetics_cv, "lo": lo, "hi": hi, "frame_time": a.frame_time})
-    return res
-
-
-def max_lag(text):
-    try:
-        v = int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
-    if not 1 <= v <= 65535:
-        raise argparse.ArgumentTypeError("the largest lag must be 1..65535")
-    return v
-
-
-def relaxation_max_lag(a):
-    if a.max_lag is None:
-        raise SystemExit("--relaxation needs --max-lag L (frames)")
-    return a.max_lag
 
 
 def ordered_frames(path):
@@ -225,39 +212,39 @@ def ordered_frames(path):
     return torch.cat(trajs), [len(t) for t in trajs]
 
 
+def kinetics(a, x):
+    lo, hi = kinetics_cores(a)
+    ref, ref_lengths = ordered_frames(a.kinetics) if a.kinetics else (None, None)
+    ev = evaluate.FoldingKineticsEvaluator(a.mol.lower(), a.folded_pdb, cv=a.kinetics_cv, lo=lo, hi=hi, frame_time=a.frame_time,
+                                           ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
+    res.update({"cv": a.kinetics_cv, "lo": lo, "hi": hi, "frame_time": a.frame_time})
+    return res
+
+
+max_lag = number(int, lambda v: 1 <= v <= 65535, "the largest lag must be 1..65535", NOT_AN_INTEGER)
+
+
+def relaxation_max_lag(a):
+    if a.max_lag is None:
+        raise SystemExit("--relaxation needs --max-lag L (frames)")
+    return a.max_lag
+
+
 def relaxation(a, x):
     L = relaxation_max_lag(a)
     ref, ref_lengths = ordered_frames(a.relaxation) if a.relaxation else (None, None)
-    tica = None
-    if a.relaxation_cv == "tic":
-        stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
-        tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
+    tica = tica_path(a) if a.relaxation_cv == "tic" else None
     ev = evaluate.RelaxationEvaluator(a.mol.lower(), a.folded_pdb, cv=a.relaxation_cv, tica=tica, max_lag=L,
                                       frame_time=a.frame_time, ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
-    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
-    res = {k: ([clean(u) for u in v] if isinstance(v, list) else clean(v)) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
     res.update({"cv": a.relaxation_cv, "max_lag": L, "frame_time": a.frame_time})
     return res
 
 
-def msm_states(text):
-    try:
-        v = int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
-    if not 1 <= v <= evaluate.MSM_MAX_STATES:
-        raise argparse.ArgumentTypeError(f"the number of microstates must be 1..{evaluate.MSM_MAX_STATES}")
-    return v
-
-
-def msm_lag(text):
-    try:
-        v = int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
-    if v < 1:
-        raise argparse.ArgumentTypeError("a lag time must be >= 1 frame")
-    return v
+msm_states = number(int, lambda v: 1 <= v <= evaluate.MSM_MAX_STATES,
+                    f"the number of microstates must be 1..{evaluate.MSM_MAX_STATES}", NOT_AN_INTEGER)
+msm_lag = number(int, lambda v: v >= 1, "a lag time must be >= 1 frame", NOT_AN_INTEGER)
 
 
 def msm_lagtimes(text):
@@ -273,24 +260,8 @@ def msm_arguments(a):
     return a.msm_states, a.msm_lag
 
 
-def msm_bootstrap(text):
-    try:
-        v = int(text)
-    except ValueError:
-        v = 0
-    if v < 1:
-        raise argparse.ArgumentTypeError(f"expected a number of resamples >= 1, got {text!r}")
-    return v
-
-
-def msm_confidence(text):
-    try:
-        v = float(text)
-    except ValueError:
-        v = 0.0
-    if not 0 < v < 1:
-        raise argparse.ArgumentTypeError(f"expected a confidence level in (0, 1), got {text!r}")
-    return v
+msm_bootstrap = number(int, lambda v: v >= 1, "expected a number of resamples >= 1, got {text!r}")
+msm_confidence = number(float, lambda v: 0 < v < 1, "expected a confidence level in (0, 1), got {text!r}")
 
 
 def msm_bootstrap_arguments(a):
@@ -309,17 +280,14 @@ def msm(a, x):
     K, lag = msm_arguments(a)
     boot = msm_bootstrap_arguments(a)
     ref, ref_lengths = ordered_frames(a.msm) if a.msm else (None, None)
-    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
-    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
-    ev = evaluate.MsmEvaluator(a.mol.lower(), tica, n_microstates=K, lagtime=lag, frame_time=a.frame_time, ref_data=ref,
+    ev = evaluate.MsmEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, lagtime=lag, frame_time=a.frame_time, ref_data=ref,
                                ref_traj_lengths=ref_lengths, device=a.device, **boot)
-    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
     lengths = traj_lengths(a, len(x))
-    res = {k: ([clean(u) for u in v] if isinstance(v, list) else clean(v)) for k, v in ev.eval(x, lengths).items()}
+    res = cleaned(ev.eval(x, lengths))
     res.update({"n_microstates": K, "lagtime": lag, "frame_time": a.frame_time})
     if boot:
         res.update({"n_bootstrap": boot["n_bootstrap"], "block_frames": boot["block_frames"], "confidence": boot["confidence"]})
-    table = lambda m: [[clean(v * a.frame_time) for v in row] for row in m]     # noqa: E731
+    table = lambda m: [clean([v * a.frame_time for v in row]) for row in m]     # noqa: E731
     if a.msm_lagtimes and boot:
         its, lo, hi = evaluate.implied_timescales_bootstrap(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales,
                                                             n_resamples=boot["n_bootstrap"], block_frames=boot["block_frames"],
@@ -354,13 +322,10 @@ def passage_arguments(a):
 def passage(a, x):
     K, lag, cv, (lo, hi) = passage_arguments(a)
     ref, ref_lengths = ordered_frames(a.passage) if a.passage else (None, None)
-    stem = os.path.join(a.saved_ref_dir, f"saved_TICA_{a.mol.upper()}_{a.evalset}")
-    tica = stem + ".npz" if os.path.exists(stem + ".npz") else stem + ".pickle"
-    ev = evaluate.MsmPassageEvaluator(a.mol.lower(), tica, a.folded_pdb, n_microstates=K, lagtime=lag, cv=cv, lo=lo, hi=hi,
+    ev = evaluate.MsmPassageEvaluator(a.mol.lower(), tica_path(a), a.folded_pdb, n_microstates=K, lagtime=lag, cv=cv, lo=lo, hi=hi,
                                       frame_time=a.frame_time, ref_data=ref, ref_traj_lengths=ref_lengths,
                                       n_bootstrap=a.passage_bootstrap or 0, device=a.device)
-    clean = lambda v: None if not np.isfinite(v) else float(v)     # noqa: E731
-    res = {k: clean(v) for k, v in ev.eval(x, traj_lengths(a, len(x))).items()}
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
     res.update({"n_microstates": K, "lagtime": lag, "cv": cv, "lo": lo, "hi": hi, "frame_time": a.frame_time,
                 "n_bootstrap": a.passage_bootstrap or 0})
     return res
@@ -487,7 +452,7 @@ def main():
         res["RMSD mean"] = float(np.nanmean(rmsd))
         curve = evaluate.rmsd_curve(rmsd, evaluate.RMSD_NBINS_REF, evaluate.RMSD_CUTOFF_REF.get(mol))
         res["RMSD curve"] = {"bin_mids": curve["bin_mids"].tolist(),
-                             "energies": [None if not np.isfinite(v) else float(v) for v in curve["energies"]]}
+                             "energies": clean(list(curve["energies"]))}
         _, mean = evaluate.ContactEvaluator(mol, a.folded_pdb, device=a.device).contact_bce(x)
         res["Contact BCE"] = float(mean)
     if a.transitions:

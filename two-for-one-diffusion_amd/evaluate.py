@@ -482,6 +482,23 @@ def _frames(x, device):
     return x.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _reference_frames(ref_data):
+    """The frames of an evaluator's ref_data: a tensor or an array as it is, else a dataset whose [:][0] they are."""
+    if ref_data is None or isinstance(ref_data, (torch.Tensor, np.ndarray)):
+        return ref_data
+    return ref_data[:][0]
+
+
+def _log10_ratio(a, b):
+    """log10(a / b), NaN unless both are finite and positive; two lists of equal length go element by element."""
+    if isinstance(a, list) or isinstance(b, list):
+        if not (isinstance(a, list) and isinstance(b, list) and len(a) == len(b)):
+            raise ValueError("_log10_ratio: two numbers, or two lists of equal length")
+        return [_log10_ratio(u, v) for u, v in zip(a, b)]
+    ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
+    return float(np.log10(a / b)) if ok else float("nan")
+
+
 class DihedralEnergiesEvaluator:
     """Drop-in for evaluate.evaluators.DihedralEnergiesEvaluator (alanine dipeptide phi / psi free energy).
     `topology` is unused: the quadruples are the reference's [[0, 1, 2, 3], [1, 2, 3, 4]]."""
@@ -674,9 +691,7 @@ class Evaluator:
     def __init__(self, ref_data, topology=None, mol_name="alanine", eval_folder=None,
                  folded_pdb_folder="./datasets/folded_pdbs", data_folder="./data", evalsetname="", *,
                  saved_ref_dir="./saved_references", tica_fit_data=None, tica_lagtime=100, device="cuda:0"):
-        if ref_data is not None and not isinstance(ref_data, torch.Tensor):
-            ref_data = ref_data[:][0]
-        self.ref_data = ref_data
+        self.ref_data = ref_data = _reference_frames(ref_data)
         self.topology = topology
         self.eval_folder = eval_folder
         self.folded_pdb_folder = folded_pdb_folder
@@ -864,6 +879,15 @@ def _tica_arrays(tica, dim=2):
     raise ValueError("tica must be a TicEvaluator, a TICA, a saved-reference path or a (mean, coeff) pair")
 
 
+def _tica_model(tica, what, max_dim=None):
+    """(mean (F,), coeff (F, k)) of _tica_arrays(tica), shapes checked; max_dim bounds k for the callers that project
+    through dff_struct_tic (TICA_MAX_DIM)."""
+    mean, coeff = _tica_arrays(tica)
+    if coeff.ndim != 2 or mean.shape != (coeff.shape[0],) or not (max_dim is None or 1 <= coeff.shape[1] <= max_dim):
+        raise ValueError(f"{what}: mean must be (F,) and coeff (F, k)" + ("" if max_dim is None else f", k <= {max_dim}"))
+    return mean, coeff
+
+
 def _check_lengths(traj_lengths, n):
     lengths = [int(n)] if traj_lengths is None else [int(v) for v in traj_lengths]
     if sum(lengths) != n or min(lengths, default=0) < 0:
@@ -897,9 +921,7 @@ class StateTransitionEvaluator:
                 raise ValueError(f"StateTransitionEvaluator: no preset state centres for {mol_name!r}; pass centers, or "
                                  f"fit_data and n_clusters")
             centers = STATE_CENTERS[mol]
-        self.mean, self.coeff = _tica_arrays(tica)
-        if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],):
-            raise ValueError("StateTransitionEvaluator: mean must be (F,) and coeff (F, k)")
+        self.mean, self.coeff = _tica_model(tica, "StateTransitionEvaluator")
         binding.load_library()
         self.kmeans = None
         if centers is None:
@@ -1049,9 +1071,7 @@ class EnsembleCoverageEvaluator:
         self.chunk = chunk
         self.device = torch.device(device)
         binding.load_library()
-        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-            ref_data = ref_data[:][0]
-        self.refs = _frames(ref_data, self.device)
+        self.refs = _frames(_reference_frames(ref_data), self.device)
         self.refs_nonfinite = _count_nonfinite(self.refs)
 
     def nearest(self, samples):
@@ -1233,9 +1253,7 @@ class FlexibilityEvaluator:
         self.chunk = chunk
         self.device = torch.device(device)
         binding.load_library()
-        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-            ref_data = ref_data[:][0]
-        self.refs = _frames(ref_data, self.device)
+        self.refs = _frames(_reference_frames(ref_data), self.device)
         self.refs_nonfinite = _count_nonfinite(self.refs)
         if folded is not None:
             self.align_on = _as_ref32(_folded_coords(folded, mol_name))
@@ -1362,9 +1380,7 @@ class RmsdClusterEvaluator:
         self.chunk = chunk
         self.device = torch.device(device)
         binding.load_library()
-        if ref_data is not None and not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-            ref_data = ref_data[:][0]
-        refs = _frames(ref_data, self.device)
+        refs = _frames(_reference_frames(ref_data), self.device)
         self.refs = refs[::int(stride)].contiguous() if int(stride) > 1 else refs
         self.refs_nonfinite = _count_nonfinite(self.refs)
         self.clusters = cluster_rmsd(self.refs, self.cutoff, max_clusters=max_clusters, device=self.device)
@@ -1457,9 +1473,13 @@ def native_contacts_q(xyz, folded, *, cutoff=10.0, offset=3, beta=5.0, lam=1.2, 
     atoms at a 4.5 A cutoff); the reference has no soft Q, only the hard contact map of ContactEvaluator."""
     pairs, r0 = native_pairs(folded, cutoff, offset)
     x = _frames(xyz, torch.device(device))
+    _check_beads(x, folded)
+    return binding.struct_native_q(x, pairs, r0, beta, lam)
+
+
+def _check_beads(x, folded):
     if x.shape[1] != len(folded):
         raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(folded)}")
-    return binding.struct_native_q(x, pairs, r0, beta, lam)
 
 
 def _check_cores(lo, hi, what):
@@ -1536,7 +1556,78 @@ def dwell_summary(runs, frame_time=1.0):
             "n_completed": n_completed, "total_frames": int(length.sum()), "undetermined_frames": int(length[lab < 0].sum())}
 
 
-class FoldingKineticsEvaluator:
+class _Observable:
+    """Frames -> one series, the step the trajectory evaluators share.  cv="q": the soft fraction of native contacts of
+    native_contacts_q (native_pairs(folded, cutoff, offset), beta, lam); cv="rmsd": the RMSD to the folded structure
+    (dff_struct_rmsd); cv="tic": the k components of the TIC projection of `tica` (dff_struct_tic).  `allowed` lists the cv
+    the caller takes, `what` is the caller's name in the error texts.  folded, pairs, r0 (q, rmsd) and mean, coeff (tic) are
+    None where the cv has no use for them."""
+
+    def __init__(self, what, cv, allowed, folded=None, mol_name=None, tica=None, cutoff=10.0, offset=3, beta=5.0, lam=1.2):
+        if cv not in allowed:
+            raise ValueError(f"{what}: cv must be " + " or ".join([", ".join(repr(c) for c in allowed[:-1]), repr(allowed[-1])]))
+        self.cv = cv
+        self.folded = self.pairs = self.r0 = self.mean = self.coeff = None
+        self.beta, self.lam = float(beta), float(lam)
+        if cv == "tic":
+            if tica is None:
+                raise ValueError(f"{what}: cv='tic' needs tica")
+            self.mean, self.coeff = _tica_model(tica, what, TICA_MAX_DIM)
+            return
+        if folded is None:
+            raise ValueError(f"{what}: cv={cv!r} needs the folded structure")
+        self.folded = _folded_coords(folded, mol_name)
+        if cv == "q":
+            if not (np.isfinite(self.beta) and self.beta > 0 and np.isfinite(self.lam) and self.lam > 0):
+                raise ValueError(f"{what}: beta and lam must be finite and > 0")
+            self.pairs, self.r0 = native_pairs(self.folded, cutoff, offset)
+
+    def __call__(self, x):
+        """the series of the frames x (n, N, 3) already on the device: (n,) float32 for q and rmsd, (n, k) float64 for tic"""
+        if self.cv == "tic":
+            return binding.struct_tic(x, self.mean, self.coeff)
+        _check_beads(x, self.folded)
+        if self.cv == "q":
+            return binding.struct_native_q(x, self.pairs, self.r0, self.beta, self.lam)
+        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float())
+
+
+class _TrajectoryEvaluator:
+    """What FoldingKineticsEvaluator, RelaxationEvaluator, MsmEvaluator and MsmPassageEvaluator share.  A subclass checks its
+    own arguments between super().__init__ and self._start(ref_data, ref_traj_lengths), and writes
+      _analyse(x, lengths, name)   the result dict of one ensemble, name "samples" or "refs": frames x (n, N, 3) float32 on the
+                                   device in trajectories of `lengths`; what it keeps for the caller (series, models, ...) goes
+                                   on dicts under that name
+      _compare(res, ref)           adds the keys that compare the samples' result with the reference's to res.
+    eval() is the samples' dict, then with ref_data the reference's keys with the suffix _ref, then _compare's keys."""
+
+    def __init__(self, what, mol_name, frame_time, device):
+        self.frame_time = float(frame_time)
+        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
+            raise ValueError(f"{what}: frame_time must be finite and > 0")
+        self.mol_name = mol_name
+        self.device = torch.device(device)
+        self.ref_result = None
+
+    def _start(self, ref_data, ref_traj_lengths):
+        """the end of a constructor: the library, and the reference's result when there is ref_data"""
+        binding.load_library()
+        if ref_data is not None:
+            self.ref_result = self._ensemble(_reference_frames(ref_data), ref_traj_lengths, "refs")
+
+    def _ensemble(self, xyz, traj_lengths, name):
+        x = _frames(xyz, self.device)
+        return self._analyse(x, _check_lengths(traj_lengths, len(x)), name)
+
+    def eval(self, xyz, traj_lengths=None):
+        res = self._ensemble(xyz, traj_lengths, "samples")
+        if self.ref_result is not None:
+            res.update({k + "_ref": v for k, v in self.ref_result.items()})
+            self._compare(res, self.ref_result)
+        return res
+
+
+class FoldingKineticsEvaluator(_TrajectoryEvaluator):
     """How often does a trajectory fold and unfold, and how long does it stay: the order-parameter route of the fast-folder
     literature on the GPU.  Frames -> order parameter (cv="q": the soft fraction of native contacts of native_contacts_q;
     cv="rmsd": the RMSD to the folded structure, dff_struct_rmsd) -> dual-cutoff core states with the cores cv <= lo and
@@ -1563,36 +1654,17 @@ class FoldingKineticsEvaluator:
 
     def __init__(self, mol_name, folded, *, cv="q", lo, hi, frame_time=1.0, ref_data=None, ref_traj_lengths=None,
                  cutoff=10.0, offset=3, beta=5.0, lam=1.2, device="cuda:0"):
-        if cv not in ("q", "rmsd"):
-            raise ValueError("FoldingKineticsEvaluator: cv must be 'q' or 'rmsd'")
+        super().__init__("FoldingKineticsEvaluator", mol_name, frame_time, device)
         self.lo, self.hi = _check_cores(lo, hi, "FoldingKineticsEvaluator")
-        self.frame_time = float(frame_time)
-        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
-            raise ValueError("FoldingKineticsEvaluator: frame_time must be finite and > 0")
-        self.mol_name, self.cv = mol_name, cv
-        self.device = torch.device(device)
-        self.folded = _folded_coords(folded, mol_name)
-        self.beta, self.lam = float(beta), float(lam)
-        if cv == "q":
-            if not (np.isfinite(self.beta) and self.beta > 0 and np.isfinite(self.lam) and self.lam > 0):
-                raise ValueError("FoldingKineticsEvaluator: beta and lam must be finite and > 0")
-            self.pairs, self.r0 = native_pairs(self.folded, cutoff, offset)
+        self._cv = _Observable("FoldingKineticsEvaluator", cv, ("q", "rmsd"), folded, mol_name, None, cutoff, offset, beta, lam)
+        self.cv, self.folded, self.pairs, self.r0 = cv, self._cv.folded, self._cv.pairs, self._cv.r0
         self.folded_label, self.unfolded_label = (1, 0) if cv == "q" else (0, 1)
-        binding.load_library()
         self.series = {}
-        self.ref_result = None
-        if ref_data is not None:
-            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-                ref_data = ref_data[:][0]
-            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+        self._start(ref_data, ref_traj_lengths)
 
     def order_parameter(self, x):
         """float32 tensor (n,) on the device: Q or the RMSD of the frames x (n, N, 3) already there"""
-        if x.shape[1] != len(self.folded):
-            raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(self.folded)}")
-        if self.cv == "q":
-            return binding.struct_native_q(x, self.pairs, self.r0, self.beta, self.lam)
-        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float())
+        return self._cv(x)
 
     @staticmethod
     def summarize(summary, folded_label, unfolded_label, samples_nonfinite=0):
@@ -1612,9 +1684,7 @@ class FoldingKineticsEvaluator:
         res["samples_nonfinite"] = float(samples_nonfinite)
         return res
 
-    def _analyse(self, xyz, traj_lengths, name):
-        x = _frames(xyz, self.device)
-        lengths = _check_lengths(traj_lengths, len(x))
+    def _analyse(self, x, lengths, name):
         cv = self.order_parameter(x)
         labels = binding.core_states(cv, lengths, self.lo, self.hi)
         runs = label_runs(labels, lengths)
@@ -1625,16 +1695,12 @@ class FoldingKineticsEvaluator:
     def eval(self, xyz, traj_lengths=None, plot_dynamics=False):
         if plot_dynamics:
             raise NotImplementedError("plotting (evaluators.py: _plot_rmsd_dynamics) is outside the hot path")
-        res = self._analyse(xyz, traj_lengths, "samples")
-        if self.ref_result is not None:
-            ref = self.ref_result
-            res.update({k + "_ref": v for k, v in ref.items()})
-            for which in ("folding", "unfolding"):
-                a, b = res[f"rate_{which}"], ref[f"rate_{which}"]
-                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
-                res[f"log10_rate_ratio_{which}"] = float(np.log10(a / b)) if ok else float("nan")
-            res["folded_share_diff"] = res["folded_share"] - ref["folded_share"]
-        return res
+        return super().eval(xyz, traj_lengths)
+
+    def _compare(self, res, ref):
+        for which in ("folding", "unfolding"):
+            res[f"log10_rate_ratio_{which}"] = _log10_ratio(res[f"rate_{which}"], ref[f"rate_{which}"])
+        res["folded_share_diff"] = res["folded_share"] - ref["folded_share"]
 
 
 # =====================================================================================================
@@ -1755,7 +1821,7 @@ def standard_error(variance, n, tau):
     return np.sqrt(variance * 2.0 * tau / n)
 
 
-class RelaxationEvaluator:
+class RelaxationEvaluator(_TrajectoryEvaluator):
     """How fast does an observable decorrelate along the trajectories, and how many independent samples do they hold.
     Frames -> series (cv="q": native_contacts_q's soft fraction of native contacts; cv="rmsd": the RMSD to the folded
     structure, dff_struct_rmsd; cv="tic": the k components of the TIC projection of `tica`, a TicEvaluator, a TICA, a saved
@@ -1778,45 +1844,19 @@ class RelaxationEvaluator:
 
     def __init__(self, mol_name, folded=None, *, cv="q", tica=None, max_lag, frame_time=1.0, ref_data=None,
                  ref_traj_lengths=None, device="cuda:0"):
-        if cv not in ("q", "rmsd", "tic"):
-            raise ValueError("RelaxationEvaluator: cv must be 'q', 'rmsd' or 'tic'")
+        super().__init__("RelaxationEvaluator", mol_name, frame_time, device)
         self.max_lag = int(max_lag)
         if self.max_lag != max_lag or not 1 <= self.max_lag <= binding.AUTOCORR_MAX_LAG:
             raise ValueError(f"RelaxationEvaluator: max_lag must be an integer in 1..{binding.AUTOCORR_MAX_LAG}")
-        self.frame_time = float(frame_time)
-        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
-            raise ValueError("RelaxationEvaluator: frame_time must be finite and > 0")
-        self.mol_name, self.cv = mol_name, cv
-        self.device = torch.device(device)
-        if cv == "tic":
-            if tica is None:
-                raise ValueError("RelaxationEvaluator: cv='tic' needs tica")
-            self.mean, self.coeff = _tica_arrays(tica)
-            if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],) or not 1 <= self.coeff.shape[1] <= TICA_MAX_DIM:
-                raise ValueError(f"RelaxationEvaluator: mean must be (F,) and coeff (F, k), k <= {TICA_MAX_DIM}")
-        else:
-            if folded is None:
-                raise ValueError(f"RelaxationEvaluator: cv={cv!r} needs the folded structure")
-            self.folded = _folded_coords(folded, mol_name)
-            if cv == "q":
-                self.pairs, self.r0 = native_pairs(self.folded)
-        binding.load_library()
+        self._cv = _Observable("RelaxationEvaluator", cv, ("q", "rmsd", "tic"), folded, mol_name, tica)
+        self.cv, self.folded, self.pairs, self.r0 = cv, self._cv.folded, self._cv.pairs, self._cv.r0
+        self.mean, self.coeff = self._cv.mean, self._cv.coeff
         self.series, self.acf = {}, {}
-        self.ref_result = None
-        if ref_data is not None:
-            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-                ref_data = ref_data[:][0]
-            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+        self._start(ref_data, ref_traj_lengths)
 
     def observable(self, x):
         """the series of the frames x (n, N, 3) already on the device: (n,) float32 for q and rmsd, (n, k) float64 for tic"""
-        if self.cv == "tic":
-            return binding.struct_tic(x, self.mean, self.coeff)
-        if x.shape[1] != len(self.folded):
-            raise ValueError(f"structures have {int(x.shape[1])} beads, the folded structure {len(self.folded)}")
-        if self.cv == "q":
-            return binding.struct_native_q(x, self.pairs, self.r0, 5.0, 1.2)
-        return binding.struct_rmsd(x, torch.from_numpy(self.folded).float())
+        return self._cv(x)
 
     @staticmethod
     def summarize(ac, frame_time=1.0, as_list=False):
@@ -1840,9 +1880,7 @@ class RelaxationEvaluator:
             res = {k: v[0] for k, v in res.items()}
         return res
 
-    def _analyse(self, xyz, traj_lengths, name):
-        x = _frames(xyz, self.device)
-        lengths = _check_lengths(traj_lengths, len(x))
+    def _analyse(self, x, lengths, name):
         series = self.observable(x)
         ac = autocorrelation(series, min(self.max_lag, max(len(x) - 1, 0)), lengths, device=self.device)
         self.series[name], self.acf[name] = series.cpu().numpy(), ac
@@ -1850,18 +1888,8 @@ class RelaxationEvaluator:
         res["samples_nonfinite"] = float(len(x) - ac.n_usable)
         return res
 
-    def eval(self, xyz, traj_lengths=None):
-        res = self._analyse(xyz, traj_lengths, "samples")
-        if self.ref_result is not None:
-            ref = self.ref_result
-            res.update({k + "_ref": v for k, v in ref.items()})
-
-            def ratio(a, b):
-                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
-                return float(np.log10(a / b)) if ok else float("nan")
-            a, b = res["tau_int"], ref["tau_int"]
-            res["log10_tau_int_ratio"] = [ratio(u, v) for u, v in zip(a, b)] if isinstance(a, list) else ratio(a, b)
-        return res
+    def _compare(self, res, ref):
+        res["log10_tau_int_ratio"] = _log10_ratio(res["tau_int"], ref["tau_int"])
 
 
 # =====================================================================================================
@@ -2464,7 +2492,58 @@ def implied_timescales_bootstrap(labels, lagtimes, traj_lengths=None, n_states=N
     return point, lo, hi
 
 
-class MsmEvaluator:
+class _Microstates:
+    """TIC projections (n, k) -> microstate labels, for MsmEvaluator and MsmPassageEvaluator.  The microstates are `centers`
+    (n_microstates, k) when given, else MicrostateKMeans(n_microstates, seed=seed) fitted on the first projections labels()
+    sees and kept on .kmeans; every call discretises on the same .centers.  `what` is the caller's name in the error texts."""
+
+    def __init__(self, what, n_microstates, k, centers, seed, device):
+        self.n_microstates = int(n_microstates)
+        if not 1 <= self.n_microstates <= MSM_MAX_STATES:
+            raise ValueError(f"{what}: n_microstates must be 1..{MSM_MAX_STATES}")
+        self.seed, self.device = int(seed), device
+        self.kmeans = self.centers = None
+        if centers is not None:
+            c = np.array(centers, np.float64)
+            if c.ndim != 2 or c.shape != (self.n_microstates, k) or not np.all(np.isfinite(c)):
+                raise ValueError(f"{what}: centers must be finite and ({self.n_microstates}, {k})")
+            self.centers = c
+
+    def labels(self, proj):
+        """int32 tensor (n,) on proj's device; -1 for a non-finite projection"""
+        if self.centers is None:
+            self.kmeans = MicrostateKMeans(self.n_microstates, seed=self.seed, device=self.device).fit(proj)
+            self.centers = self.kmeans.cluster_centers
+        return binding.micro_kmeans_step(proj, self.centers, accumulate=False)["labels"]
+
+
+class _PointModel:
+    """The model MsmEvaluator and MsmPassageEvaluator estimate from labels: the checked lag time and bootstrap settings, and
+    fit().  `what` is the caller's name in the error texts."""
+
+    def __init__(self, what, lagtime, n_bootstrap, block_frames, confidence, bootstrap_seed, device):
+        if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
+            raise ValueError(f"{what}: lagtime must be an integer >= 1 (frames)")
+        self.n_bootstrap, self.block_frames = int(n_bootstrap), block_frames
+        self.confidence, self.bootstrap_seed = float(confidence), int(bootstrap_seed)
+        if self.n_bootstrap < 0 or not 0 < self.confidence < 1:
+            raise ValueError(f"{what}: n_bootstrap must be >= 0 and confidence in (0, 1)")
+        if block_frames is not None and (int(block_frames) != block_frames or int(block_frames) < 1):
+            raise ValueError(f"{what}: block_frames must be an integer >= 1")
+        self.lagtime, self.device = int(lagtime), device
+
+    def fit(self, labels, lengths, n_states, name, bootstrap=None, **kw):
+        """(the reversible MarkovStateModel of the labels of `name`, "samples" or "refs", its bootstrap or None).  With
+        n_bootstrap > 0 and `bootstrap` (bootstrap_msm or bootstrap_passage; kw: its own arguments) the model is the
+        bootstrap's point model; refs and samples draw independently: the reference's seed is one higher."""
+        if bootstrap is None or self.n_bootstrap == 0:
+            return MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, n_states), None
+        bs = bootstrap(labels, self.lagtime, traj_lengths=lengths, n_states=n_states, n_resamples=self.n_bootstrap,
+                       block_frames=self.block_frames, seed=self.bootstrap_seed + (name == "refs"), device=self.device, **kw)
+        return (bs.point["model"] if isinstance(bs.point, dict) else bs.point), bs
+
+
+class MsmEvaluator(_TrajectoryEvaluator):
     """Do the sampled trajectories relax like the reference's?  Frames -> TIC projection (`tica`: a TicEvaluator, a TICA, a
     saved reference or a (mean, coeff) pair, at most 8 components) -> n_microstates k-means microstates -> a reversible
     MarkovStateModel at `lagtime` (frames).  The microstates are `centers` (K, k) when given, else fitted on the
@@ -2493,67 +2572,32 @@ class MsmEvaluator:
     def __init__(self, mol_name, tica, n_microstates=200, lagtime=None, n_timescales=3, frame_time=1.0, ref_data=None,
                  ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None, confidence=0.95,
                  bootstrap_seed=0, device="cuda:0"):
-        if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
-            raise ValueError("MsmEvaluator: lagtime must be an integer >= 1 (frames)")
-        self.n_bootstrap, self.block_frames = int(n_bootstrap), block_frames
-        self.confidence, self.bootstrap_seed = float(confidence), int(bootstrap_seed)
-        if self.n_bootstrap < 0 or not 0 < self.confidence < 1:
-            raise ValueError("MsmEvaluator: n_bootstrap must be >= 0 and confidence in (0, 1)")
-        if block_frames is not None and (int(block_frames) != block_frames or int(block_frames) < 1):
-            raise ValueError("MsmEvaluator: block_frames must be an integer >= 1")
-        self.bootstraps = {}
-        self.lagtime = int(lagtime)
-        self.n_microstates = int(n_microstates)
-        if not 1 <= self.n_microstates <= MSM_MAX_STATES:
-            raise ValueError(f"MsmEvaluator: n_microstates must be 1..{MSM_MAX_STATES}")
+        super().__init__("MsmEvaluator", mol_name, frame_time, device)
+        self._point = _PointModel("MsmEvaluator", lagtime, n_bootstrap, block_frames, confidence, bootstrap_seed, self.device)
+        self.lagtime = self._point.lagtime
         self.n_timescales = int(n_timescales)
         if self.n_timescales < 1:
             raise ValueError("MsmEvaluator: n_timescales must be >= 1")
-        self.frame_time = float(frame_time)
-        if not (np.isfinite(self.frame_time) and self.frame_time > 0):
-            raise ValueError("MsmEvaluator: frame_time must be finite and > 0")
-        self.mol_name, self.seed = mol_name, int(seed)
-        self.device = torch.device(device)
-        self.mean, self.coeff = _tica_arrays(tica)
-        if self.coeff.ndim != 2 or self.mean.shape != (self.coeff.shape[0],) or not 1 <= self.coeff.shape[1] <= TICA_MAX_DIM:
-            raise ValueError(f"MsmEvaluator: mean must be (F,) and coeff (F, k), k <= {TICA_MAX_DIM}")
-        self.centers = None
-        if centers is not None:
-            c = np.array(centers, np.float64)
-            if c.ndim != 2 or c.shape != (self.n_microstates, self.coeff.shape[1]) or not np.all(np.isfinite(c)):
-                raise ValueError(f"MsmEvaluator: centers must be finite and ({self.n_microstates}, {self.coeff.shape[1]})")
-            self.centers = c
-        binding.load_library()
-        self.kmeans, self.models, self.labels = None, {}, {}
-        self.ref_result = None
-        if ref_data is not None:
-            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-                ref_data = ref_data[:][0]
-            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+        self.mean, self.coeff = _tica_model(tica, "MsmEvaluator", TICA_MAX_DIM)
+        self._micro = _Microstates("MsmEvaluator", n_microstates, self.coeff.shape[1], centers, seed, self.device)
+        self.n_microstates = self._micro.n_microstates
+        self.models, self.labels, self.bootstraps = {}, {}, {}
+        self._start(ref_data, ref_traj_lengths)
+
+    centers = property(lambda self: self._micro.centers, doc="the microstate centres (K, k); None until they are fitted")
+    kmeans = property(lambda self: self._micro.kmeans, doc="the fitted MicrostateKMeans; None when the centres were given")
 
     def project(self, x):
         return binding.struct_tic(x, self.mean, self.coeff)
 
-    def _analyse(self, xyz, traj_lengths, name):
-        x = _frames(xyz, self.device)
-        lengths = _check_lengths(traj_lengths, len(x))
-        proj = self.project(x)
-        if self.centers is None:
-            self.kmeans = MicrostateKMeans(self.n_microstates, seed=self.seed, device=self.device).fit(proj)
-            self.centers = self.kmeans.cluster_centers
-        labels = binding.micro_kmeans_step(proj, self.centers, accumulate=False)["labels"]
-        if self.n_bootstrap > 0:                                    # refs and samples draw independently: another seed
-            bs = bootstrap_msm(labels, self.lagtime, lengths, self.n_microstates, n_resamples=self.n_bootstrap,
-                               block_frames=self.block_frames, seed=self.bootstrap_seed + (name == "refs"),
-                               k=self.n_timescales, device=self.device)
-            self.bootstraps[name] = bs
-            model = bs.point
-        else:
-            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+    def _analyse(self, x, lengths, name):
+        labels = self._micro.labels(self.project(x))
+        model, bs = self._point.fit(labels, lengths, self.n_microstates, name, bootstrap_msm, k=self.n_timescales)
         self.models[name], self.labels[name] = model, labels.cpu().numpy()
         res = self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()))
-        if self.n_bootstrap > 0:
-            lo, hi = bs.interval(self.confidence)
+        if bs is not None:
+            self.bootstraps[name] = bs
+            lo, hi = bs.interval(self._point.confidence)
             res.update({"timescales_lo": [float(v) * self.frame_time for v in lo],
                         "timescales_hi": [float(v) * self.frame_time for v in hi],
                         "timescales_std": [float(v) * self.frame_time for v in bs.std()],
@@ -2576,24 +2620,15 @@ class MsmEvaluator:
             row[np.searchsorted(union, m.active_set)] = m.stationary_distribution
         return float(js_divergence(p[0], p[1]))
 
-    def eval(self, xyz, traj_lengths=None):
-        res = self._analyse(xyz, traj_lengths, "samples")
-        if self.ref_result is not None:
-            ref = self.ref_result
-            res.update({k + "_ref": v for k, v in ref.items()})
-
-            def ratio(a, b):
-                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
-                return float(np.log10(a / b)) if ok else float("nan")
-            res["log10_timescale_ratio"] = [ratio(a, b) for a, b in zip(res["timescales"], ref["timescales"])]
-            res["stationary_js"] = self.stationary_js(self.models["samples"], self.models["refs"])
-            if self.n_bootstrap > 0:                                 # resample b of the samples over resample b of the reference
-                a, b = self.bootstraps["samples"].timescales, self.bootstraps["refs"].timescales
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    r = np.where((a > 0) & (b > 0), np.log10(a / b), np.nan)
-                lo, hi = percentile_interval(r, self.confidence)
-                res["log10_timescale_ratio_lo"], res["log10_timescale_ratio_hi"] = [float(v) for v in lo], [float(v) for v in hi]
-        return res
+    def _compare(self, res, ref):
+        res["log10_timescale_ratio"] = _log10_ratio(res["timescales"], ref["timescales"])
+        res["stationary_js"] = self.stationary_js(self.models["samples"], self.models["refs"])
+        if self._point.n_bootstrap > 0:                              # resample b of the samples over resample b of the reference
+            a, b = self.bootstraps["samples"].timescales, self.bootstraps["refs"].timescales
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r = np.where((a > 0) & (b > 0), np.log10(a / b), np.nan)
+            lo, hi = percentile_interval(r, self._point.confidence)
+            res["log10_timescale_ratio_lo"], res["log10_timescale_ratio_hi"] = [float(v) for v in lo], [float(v) for v in hi]
 
 
 # ---- mean first-passage times, committors and reactive flux of a Markov state model ----
@@ -2852,10 +2887,10 @@ def states_by_cv(labels, cv, lo, hi, n_states):
     return np.flatnonzero(mean <= lo).astype(np.int64), np.flatnonzero(mean >= hi).astype(np.int64)
 
 
-class MsmPassageEvaluator:
+class MsmPassageEvaluator(_TrajectoryEvaluator):
     """How long does folding take in the sampled dynamics, and through which states does it go?  Frames -> TIC projection and
-    k-means microstates (MsmEvaluator's: `tica`, n_microstates, centers, seed) and the order parameter of
-    FoldingKineticsEvaluator (`folded`, cv="q" or "rmsd") -> the folded and the unfolded SETS of microstates, those whose mean
+    k-means microstates (`tica`, n_microstates, centers, seed: as for MsmEvaluator) and an order parameter (`folded` and
+    cv="q" or "rmsd": as for FoldingKineticsEvaluator) -> the folded and the unfolded SETS of microstates, those whose mean
     order parameter lies in the folded or the unfolded core (states_by_cv with lo, hi; taken from the reference when there is
     ref_data, else from the first samples, and kept) -> a reversible MarkovStateModel at `lagtime` -> mfpt, committor and
     reactive_flux between the two sets.
@@ -2879,33 +2914,29 @@ class MsmPassageEvaluator:
     def __init__(self, mol_name, tica, folded, n_microstates=200, lagtime=None, cv="q", lo=0.2, hi=0.9, frame_time=1.0,
                  ref_data=None, ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None,
                  confidence=0.95, bootstrap_seed=0, device="cuda:0"):
-        self.discretiser = MsmEvaluator(mol_name, tica, n_microstates, lagtime, 1, frame_time, centers=centers, seed=seed,
-                                        n_bootstrap=n_bootstrap, block_frames=block_frames, confidence=confidence,
-                                        bootstrap_seed=bootstrap_seed, device=device)          # checks these arguments
-        self.order = FoldingKineticsEvaluator(mol_name, folded, cv=cv, lo=lo, hi=hi, frame_time=frame_time, device=device)
-        d = self.discretiser
-        self.mol_name, self.device, self.lagtime, self.n_microstates, self.frame_time = mol_name, d.device, d.lagtime, d.n_microstates, d.frame_time
-        self.n_bootstrap, self.block_frames, self.confidence, self.bootstrap_seed = d.n_bootstrap, d.block_frames, d.confidence, d.bootstrap_seed
+        # the error texts name the evaluator whose argument it is, MsmEvaluator or FoldingKineticsEvaluator, as they always have
+        super().__init__("MsmEvaluator", mol_name, frame_time, device)
+        self._point = _PointModel("MsmEvaluator", lagtime, n_bootstrap, block_frames, confidence, bootstrap_seed, self.device)
+        self.lagtime = self._point.lagtime
+        self.mean, self.coeff = _tica_model(tica, "MsmEvaluator", TICA_MAX_DIM)
+        self._micro = _Microstates("MsmEvaluator", n_microstates, self.coeff.shape[1], centers, seed, self.device)
+        self.n_microstates = self._micro.n_microstates
+        self.lo, self.hi = _check_cores(lo, hi, "FoldingKineticsEvaluator")
+        self._cv = _Observable("FoldingKineticsEvaluator", cv, ("q", "rmsd"), folded, mol_name)
+        self.cv, self.folded, self.pairs, self.r0 = cv, self._cv.folded, self._cv.pairs, self._cv.r0
         self.folded_states = self.unfolded_states = None
         self.models, self.labels, self.committors, self.bootstraps = {}, {}, {}, {}
-        self.ref_result = None
-        if ref_data is not None:
-            if not isinstance(ref_data, (torch.Tensor, np.ndarray)):
-                ref_data = ref_data[:][0]
-            self.ref_result = self._analyse(ref_data, ref_traj_lengths, "refs")
+        self._start(ref_data, ref_traj_lengths)
 
-    @property
-    def centers(self):
-        return self.discretiser.centers
+    centers = property(lambda self: self._micro.centers, doc="the microstate centres (K, k); None until they are fitted")
+    kmeans = property(lambda self: self._micro.kmeans, doc="the fitted MicrostateKMeans; None when the centres were given")
+
+    def project(self, x):
+        return binding.struct_tic(x, self.mean, self.coeff)
 
     def discretise(self, x):
         """(labels int32 (n,), order parameter (n,)) of frames already on the device; the first call fits the centres"""
-        d = self.discretiser
-        proj = d.project(x)
-        if d.centers is None:
-            d.kmeans = MicrostateKMeans(d.n_microstates, seed=d.seed, device=d.device).fit(proj)
-            d.centers = d.kmeans.cluster_centers
-        return binding.micro_kmeans_step(proj, d.centers, accumulate=False)["labels"], self.order.order_parameter(x)
+        return self._micro.labels(self.project(x)), self._cv(x)
 
     @staticmethod
     def summarize(model, row, committor, folded_states, unfolded_states, frame_time=1.0, samples_nonfinite=0):
@@ -2920,45 +2951,33 @@ class MsmPassageEvaluator:
                 "committor_mid_share": float(model.stationary_distribution[mid].sum()) if np.isfinite(q).all() else float("nan"),
                 "samples_nonfinite": float(samples_nonfinite)}
 
-    def _analyse(self, xyz, traj_lengths, name):
-        x = _frames(xyz, self.device)
-        lengths = _check_lengths(traj_lengths, len(x))
+    def _analyse(self, x, lengths, name):
         labels, cv = self.discretise(x)
         if self.folded_states is None:
-            low, high = states_by_cv(labels, cv, self.order.lo, self.order.hi, self.n_microstates)
-            self.unfolded_states, self.folded_states = (low, high) if self.order.cv == "q" else (high, low)
+            low, high = states_by_cv(labels, cv, self.lo, self.hi, self.n_microstates)
+            self.unfolded_states, self.folded_states = (low, high) if self.cv == "q" else (high, low)
         U, F = self.unfolded_states, self.folded_states
-        bs = None
-        if U.size == 0 or F.size == 0:                               # no state reaches a core: nothing to solve
-            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
+        solvable = U.size > 0 and F.size > 0                         # else no state reaches a core: nothing to solve or resample
+        model, bs = self._point.fit(labels, lengths, self.n_microstates, name, bootstrap_passage if solvable else None, A=U, B=F)
+        if not solvable:
             row, comm = np.full(4, np.nan), np.full(self.n_microstates, np.nan)
-        elif self.n_bootstrap > 0:
-            bs = bootstrap_passage(labels, self.lagtime, U, F, lengths, self.n_microstates, n_resamples=self.n_bootstrap,
-                                   block_frames=self.block_frames, seed=self.bootstrap_seed + (name == "refs"), device=self.device)
+        elif bs is not None:
             self.bootstraps[name] = bs
-            model, comm = bs.point["model"], bs.point["committor"]
+            comm = bs.point["committor"]
             row = np.array([bs.point[f] for f in PassageBootstrap.FIELDS])
         else:
-            model = MarkovStateModel(self.lagtime, device=self.device).fit(labels, lengths, self.n_microstates)
             rows, comms = _passage_batch([model], U, F, self.n_microstates, self.device)
             row, comm = rows[0], comms[0]
         self.models[name], self.labels[name], self.committors[name] = model, labels.cpu().numpy(), comm
         res = self.summarize(model, row, comm, F, U, self.frame_time, int((labels < 0).sum()))
         if bs is not None:
-            iv, sd = bs.interval(self.confidence), bs.std()
+            iv, sd = bs.interval(self._point.confidence), bs.std()
             for key, field in self.BARS:
                 scale = self.frame_time if key.startswith("mfpt") else 1.0 / self.frame_time
                 res[key + "_lo"], res[key + "_hi"], res[key + "_std"] = iv[field][0] * scale, iv[field][1] * scale, sd[field] * scale
             res["bootstrap_failed"] = float(bs.n_failed)
         return res
 
-    def eval(self, xyz, traj_lengths=None):
-        res = self._analyse(xyz, traj_lengths, "samples")
-        if self.ref_result is not None:
-            ref = self.ref_result
-            res.update({k + "_ref": v for k, v in ref.items()})
-            for which in ("folding", "unfolding"):
-                a, b = res[f"mfpt_{which}"], ref[f"mfpt_{which}"]
-                ok = np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0
-                res[f"log10_mfpt_ratio_{which}"] = float(np.log10(a / b)) if ok else float("nan")
-        return res
+    def _compare(self, res, ref):
+        for which in ("folding", "unfolding"):
+            res[f"log10_mfpt_ratio_{which}"] = _log10_ratio(res[f"mfpt_{which}"], ref[f"mfpt_{which}"])
