@@ -722,6 +722,41 @@ int dff_msm_dirichlet_solve(int device, const double* flux_dev, int n_flux, cons
  * sum in different orders: each gives its own, reproducible bits. */
 int dff_debug_msm_dirichlet_path(int path);
 
+/* ---- The k algebraically largest eigenvalues, and optionally their eigenvectors, of P dense symmetric fp64 matrices of
+ * differing sizes, one workgroup per problem (csrc/dff_sym_eig.hip; evaluate.py: msm_spectrum, MarkovStateModel.eigenvectors,
+ * eigensolver="device") ----
+ * Problem p is a COMPACT (K_p, K_p) row-major matrix at a_dev + p Kmax^2, K_p = ks_host[p] (the layout of
+ * dff_msm_reversible_steps_batched); it is read-only, and only its lower triangle is read: an asymmetric matrix is not detected
+ * as such.  w_dev (P, k): the kk = min(k, K_p) largest eigenvalues of problem p, descending, NaN from index K_p on.  v_dev
+ * (P, k, Kmax), or NULL when no vectors are wanted: row j is the eigenvector of eigenvalue j, written at 0 .. K_p - 1 only (rows
+ * j >= K_p are NaN there); unit 2-norm, the component of largest magnitude positive, the lowest index winning a tie.  The
+ * eigenvalues of a call with vectors are bit-identical to those of a call without.  status_dev (P) int32:
+ *   0   solved
+ *   1   a non-finite entry in the lower triangle               every output of the problem is NaN
+ *   2   a vector's inverse iteration did not reach its growth   the eigenvalues are valid, the problem's vectors NaN
+ * Status 0 never comes with a NaN at an index below K_p; a failed problem touches no other.
+ * Per problem: Householder reduction to tridiagonal form on a working copy (unblocked; a column that is already zero below the
+ * sub-diagonal gets tau = 0 and no division, so diagonal and tridiagonal inputs are legal; column norms are taken of the column
+ * divided by its largest entry), the eigenvalues by Sturm-count multisection with dstebz's pivmin safeguard until no shift
+ * lies strictly inside a bracket, the vectors by inverse iteration as in dstein (tridiagonal LU with partial pivoting, at most
+ * five solves, eigenvalues closer than 10 ulp perturbed apart, modified Gram-Schmidt against every earlier vector of the problem:
+ * exactly repeated eigenvalues get an orthonormal basis), then the stored reflectors.  Up to dff_sym_eig_lds_limit states the
+ * packed triangle lives in LDS; above, the same algorithm runs in the problem's slice of the workspace.  After the call the
+ * first three doubles of a problem's slice hold, for benchmarks, the 100 MHz ticks spent in reduction, bisection and vectors.
+ * The bits of a problem's outputs follow from its own inputs, k and the path alone: not from P, its place in the batch, its
+ * neighbours, the workspace's prior contents or the call; the two paths need not agree bit for bit.
+ * 1 <= K_p <= Kmax <= DFF_MSM_MAXK, 1 <= P <= 16384, 1 <= k <= 32; device pointers, `stream` only, no read-back, refusals on the
+ * host before any device call, no atomics, no workgroup waits on another.  workspace_dev 8-byte aligned, contents irrelevant. */
+/* Bytes of device workspace the call below needs (P state counts and P slices of 4 + Kmax^2 doubles); -1 on bad arguments. */
+long long dff_sym_eig_workspace_bytes(int P, int Kmax);
+/* The largest K_p that is reduced out of LDS (a compile-time constant). */
+int dff_sym_eig_lds_limit(void);
+int dff_sym_eig_topk(int device, const double* a_dev, const int32_t* ks_host, int P, int Kmax, int k, double* w_dev,
+                     double* v_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* For tests and benchmarks, process-wide: 0 = the path follows K_p (the default), 1 = every problem in LDS (a call with a K_p
+ * above the limit is then refused), 2 = every problem in the workspace. */
+int dff_debug_sym_eig_path(int path);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

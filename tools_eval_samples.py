@@ -16,7 +16,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--passage [HELDOUT.pt] --passage-states K --passage-lag L [--passage-cv q|rmsd]
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
-                                  [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]]
+                                  [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]
+                                  [--msm-eigensolver host|device] [--msm-eigenvectors N]]
 
 Without a saved TICA reference for MOL, --tica-fit-data fits one on the GPU (a (n, N, 3) trajectory in Angstrom, or a
 list of them, in time order) and writes it to SAVED_REF_DIR as the .npz that tica_path() below names; --ref-data is then
@@ -67,6 +68,9 @@ a,b,c adds "implied_timescales": the timescales (frames x --frame-time) of the s
 --msm-bootstrap B adds bootstrap error bars (B resamples of the trajectories, or of blocks of --msm-block-frames frames):
 timescales_lo / _hi at --msm-confidence (0.95), timescales_std, bootstrap_failed, with HELDOUT.pt their _ref counterparts and
 log10_timescale_ratio_lo / _hi, and "timescales_lo" / "timescales_hi" in "implied_timescales".
+--msm-eigensolver device takes every spectrum from dff_sym_eig_topk on the GPU (all resamples of a bootstrap batch in one call)
+instead of numpy on the host, the default; --msm-eigenvectors N adds "eigenvectors": the N slowest right eigenvectors of the
+samples' model on the full microstate index ("right"), their eigenvalues and the active set.
 """
 import argparse
 import json
@@ -264,6 +268,9 @@ msm_bootstrap = number(int, lambda v: v >= 1, "expected a number of resamples >=
 msm_confidence = number(float, lambda v: 0 < v < 1, "expected a confidence level in (0, 1), got {text!r}")
 
 
+msm_eigenvectors = number(int, lambda v: 1 <= v < evaluate.SPECTRUM_MAX_K, "expected a number of eigenvectors in 1..31, got {text!r}")
+
+
 def msm_bootstrap_arguments(a):
     """keyword arguments of MsmEvaluator for --msm-bootstrap; its options are refused without it, and it without --msm"""
     if a.msm_bootstrap is None:
@@ -276,26 +283,39 @@ def msm_bootstrap_arguments(a):
             "confidence": 0.95 if a.msm_confidence is None else a.msm_confidence}
 
 
+def msm_spectrum_arguments(a):
+    """(eigensolver, eigenvectors) of --msm; both options are refused without it"""
+    if a.msm is None and (a.msm_eigensolver is not None or a.msm_eigenvectors is not None):
+        raise SystemExit("--msm-eigensolver and --msm-eigenvectors need --msm")
+    return a.msm_eigensolver or "host", a.msm_eigenvectors
+
+
 def msm(a, x):
     K, lag = msm_arguments(a)
     boot = msm_bootstrap_arguments(a)
+    solver, n_vectors = msm_spectrum_arguments(a)
     ref, ref_lengths = ordered_frames(a.msm) if a.msm else (None, None)
     ev = evaluate.MsmEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, lagtime=lag, frame_time=a.frame_time, ref_data=ref,
-                               ref_traj_lengths=ref_lengths, device=a.device, **boot)
+                               ref_traj_lengths=ref_lengths, eigensolver=solver, device=a.device, **boot)
     lengths = traj_lengths(a, len(x))
     res = cleaned(ev.eval(x, lengths))
-    res.update({"n_microstates": K, "lagtime": lag, "frame_time": a.frame_time})
+    res.update({"n_microstates": K, "lagtime": lag, "frame_time": a.frame_time, "eigensolver": solver})
+    if n_vectors:                                # the slowest right eigenvectors of the point model, on the full microstate index
+        sp = evaluate.msm_spectrum(ev.models["samples"], k=n_vectors, vectors=True, device=a.device)
+        res["eigenvectors"] = {"eigenvalues": clean(list(sp.eigenvalues[0, 1:])), "right": [clean(list(row)) for row in sp.right[0, 1:]],
+                               "active_set": [int(i) for i in ev.models["samples"].active_set]}
     if boot:
         res.update({"n_bootstrap": boot["n_bootstrap"], "block_frames": boot["block_frames"], "confidence": boot["confidence"]})
     table = lambda m: [clean([v * a.frame_time for v in row]) for row in m]     # noqa: E731
     if a.msm_lagtimes and boot:
         its, lo, hi = evaluate.implied_timescales_bootstrap(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales,
                                                             n_resamples=boot["n_bootstrap"], block_frames=boot["block_frames"],
-                                                            confidence=boot["confidence"], device=a.device)
+                                                            confidence=boot["confidence"], eigensolver=solver, device=a.device)
         res["implied_timescales"] = {"lagtimes": a.msm_lagtimes, "timescales": table(its), "timescales_lo": table(lo),
                                      "timescales_hi": table(hi)}
     elif a.msm_lagtimes:
-        its = evaluate.implied_timescales(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales, device=a.device)
+        its = evaluate.implied_timescales(ev.labels["samples"], a.msm_lagtimes, lengths, K, k=ev.n_timescales, eigensolver=solver,
+                                          device=a.device)
         res["implied_timescales"] = {"lagtimes": a.msm_lagtimes, "timescales": table(its)}
     return res
 
@@ -405,6 +425,11 @@ def build_parser():
                     help="also report mean first-passage times, rates and the committor between the folded and the unfolded "
                          "microstates of a Markov state model (time-ordered Langevin samples; needs --folded-pdb, --parallel-sim, "
                          "--passage-states and --passage-lag); with HELDOUT.pt also for that MD data, which then defines the states")
+    ap.add_argument("--msm-eigensolver", choices=("host", "device"), default=None,
+                    help="where the spectra of the Markov models are computed: numpy on the host (default) or dff_sym_eig_topk on "
+                         "the GPU, all resamples of a bootstrap batch in one call (with --msm)")
+    ap.add_argument("--msm-eigenvectors", type=msm_eigenvectors, default=None, metavar="N",
+                    help="also the N slowest right eigenvectors of the model, under \"eigenvectors\" (with --msm)")
     ap.add_argument("--passage-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --passage)")
     ap.add_argument("--passage-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --passage)")
     ap.add_argument("--passage-cv", choices=("q", "rmsd"), default=None,
@@ -435,6 +460,7 @@ def main():
     if a.msm is not None:
         msm_arguments(a)
     msm_bootstrap_arguments(a)
+    msm_spectrum_arguments(a)
     passage_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None

@@ -20,7 +20,8 @@ _EVALUATE = (
     "MicrostateKMeans", "largest_connected_set", "MarkovStateModel", "implied_timescales", "MsmEvaluator",
     "resampling_units", "bootstrap_weights", "bootstrap_msm", "MsmBootstrap", "implied_timescales_bootstrap",
     "mfpt", "committor", "reactive_flux", "ReactiveFlux", "bootstrap_passage", "PassageBootstrap", "states_by_cv", "dirichlet_solver",
-    "MsmPassageEvaluator")
+    "MsmPassageEvaluator",
+    "msm_spectrum", "MsmSpectrum", "spectral_solver")
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",

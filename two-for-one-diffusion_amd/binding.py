@@ -140,6 +140,10 @@ SYMBOLS = {
     "dff_msm_dirichlet_solve": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                           _P]),
     "dff_debug_msm_dirichlet_path": (C.c_int, [C.c_int]),
+    "dff_sym_eig_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_sym_eig_lds_limit": (C.c_int, []),
+    "dff_sym_eig_topk": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dff_debug_sym_eig_path": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1207,3 +1211,53 @@ def msm_dirichlet_solve(flux, ks, role, g, s, flux_of=None, u=None, workspace=No
                                             _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
                                             _stream(role)), "dff_msm_dirichlet_solve")
     return u, status
+
+
+# ---- the k largest eigenpairs of many symmetric matrices (dff_sym_eig_topk) ----
+SYM_EIG_MAX_BATCH = 16384
+SYM_EIG_MAX_K = 32
+
+
+def sym_eig_workspace_bytes(P: int, Kmax: int) -> int:
+    return _workspace_bytes("dff_sym_eig_workspace_bytes", int(P), int(Kmax))
+
+
+def sym_eig_lds_limit() -> int:
+    """The largest matrix dff_sym_eig_topk reduces out of LDS, read from the library."""
+    return int(load_library().dff_sym_eig_lds_limit())
+
+
+def debug_sym_eig_path(path: int):
+    """Tests and benchmarks only: 0 = by the matrix size, 1 = every problem in LDS, 2 = every problem in the workspace."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_sym_eig_path(int(path)), "dff_debug_sym_eig_path")
+
+
+def sym_eig_topk(a, ks, k: int, vectors=False, workspace=None):
+    """The k algebraically largest eigenvalues of P symmetric matrices in one call (dff_sym_eig_topk): a (P, Kmax, Kmax)
+    contiguous float64 CUDA, problem p a COMPACT (ks[p], ks[p]) matrix at the start of its slot, only its lower triangle read;
+    ks (P,) host integers.  Returns (w, v, status), CUDA tensors: w float64 (P, k) descending, NaN from index ks[p] on; v
+    float64 (P, k, Kmax) with eigenvector j of problem p in v[p, j, :ks[p]] (unit 2-norm, largest component positive; what
+    lies beyond ks[p] in a row is NaN, as allocated here), or None without `vectors`; status int32 (P,): 0 solved, 1 a
+    non-finite entry (all outputs NaN), 2 a vector did not converge (vectors NaN).  Nothing is read back.  `workspace` is a
+    uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    P, Kmax = (int(a.shape[0]), int(a.shape[1])) if isinstance(a, torch.Tensor) and a.dim() == 3 else (-1, -1)
+    if not _is_tensor(a, torch.float64, (P, Kmax, Kmax)):
+        raise ValueError("a must be a contiguous float64 CUDA tensor of shape (P, Kmax, Kmax)")
+    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+    if kh.size != P:
+        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
+    k = int(k)
+    if not 1 <= k <= SYM_EIG_MAX_K:
+        raise ValueError(f"k must be 1..{SYM_EIG_MAX_K}, not {k}")
+    w = torch.empty((P, k), dtype=torch.float64, device=a.device)
+    v = torch.full((P, k, Kmax), float("nan"), dtype=torch.float64, device=a.device) if vectors else None
+    status = torch.empty(P, dtype=torch.int32, device=a.device)
+    if workspace is None:
+        workspace = torch.empty(max(sym_eig_workspace_bytes(P, Kmax), 8), dtype=torch.uint8, device=a.device)
+    _check(lib, lib.dff_sym_eig_topk(a.device.index, _ptr(a), kh.ctypes.data_as(C.c_void_p), P, Kmax, k, _ptr(w), _ptr(v),
+                                     _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                     _stream(a)), "dff_sym_eig_topk")
+    return w, v, status

@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts and dff_msm_dirichlet_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_* and dff_sym_eig_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <vector>
@@ -17,6 +17,7 @@
 #include "dff_msm.hip"
 #include "dff_msm_batch.hip"
 #include "dff_msm_passage.hip"
+#include "dff_sym_eig.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1289,6 +1290,76 @@ extern "C" int dff_msm_dirichlet_solve(int device, const double* flux, int n_flu
         hipLaunchKernelGGL(dff_dir_kernel<false>, dim3((unsigned)P), dim3(DFF_DIR_THREADS), (unsigned)dir_blocked_lds_bytes(), stream,
                            flux, (const long long*)desc_dev, Kmax, role, g, s, u, status, work, slice,
                            path == 2 ? 0 : DFF_DIR_LDS_LIMIT + 1, 0x7fffffff, mfma);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The k largest eigenpairs of many symmetric matrices (dff_sym_eig.hip)
+// ---------------------------------------------------------------------------------------------
+// which path reduces a problem: 0 = by its size, 1 = LDS, 2 = the workspace
+static std::atomic<int> g_eig_path{0};
+
+extern "C" int dff_debug_sym_eig_path(int path) {
+    if (path < 0 || path > 2) return fail(DFF_EINVAL, "debug_sym_eig_path: 0 (by size), 1 (LDS) or 2 (workspace)");
+    g_eig_path.store(path);
+    return DFF_OK;
+}
+
+extern "C" int dff_sym_eig_lds_limit(void) { return DFF_EIG_LDS_LIMIT; }
+
+static int eig_check_batch(int P, int Kmax, const char* what) {
+    if (P < 1 || P > DFF_EIG_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_EIG_MAXP);
+    return micro_check_count(Kmax, what, "states");
+}
+
+extern "C" long long dff_sym_eig_workspace_bytes(int P, int Kmax) {
+    if (eig_check_batch(P, Kmax, "sym_eig_workspace_bytes")) return -1;
+    return (long long)P * (1 + eig_slice_doubles(Kmax)) * (long long)sizeof(double);   // state counts | one slice per problem
+}
+
+extern "C" int dff_sym_eig_topk(int device, const double* a, const int32_t* ks, int P, int Kmax, int k, double* w, double* v,
+                                int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "sym_eig_topk";
+    int rc = eig_check_batch(P, Kmax, what);
+    if (rc) return rc;
+    if (k < 1 || k > DFF_EIG_MAXTOP) return fail(DFF_EINVAL, "%s: the number of eigenpairs must be 1..%d", what, DFF_EIG_MAXTOP);
+    if (!a || !ks || !w || !status) return fail(DFF_EINVAL, "%s: null matrices / state counts / eigenvalues / status", what);
+    const int path = g_eig_path.load();
+    int kmax_live = 0, kmin_live = DFF_MSM_MAXK;
+    for (int p = 0; p < P; ++p) {
+        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
+        if (path == 1 && ks[p] > DFF_EIG_LDS_LIMIT)
+            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_EIG_LDS_LIMIT);
+        if (ks[p] > kmax_live) kmax_live = ks[p];
+        if (ks[p] < kmin_live) kmin_live = ks[p];
+    }
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_sym_eig_workspace_bytes(P, Kmax), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<long long> kl((size_t)P);
+    for (int p = 0; p < P; ++p) kl[p] = ks[p];
+    long long* ks_dev = (long long*)workspace;
+    if ((rc = msmb_upload(stream, kl.data(), P, ks_dev))) return rc;
+    double* work = (double*)(ks_dev + P);
+    const long long slice = eig_slice_doubles(Kmax);
+    if (path == 1 || (path == 0 && kmin_live <= DFF_EIG_LDS_LIMIT)) {
+        const size_t lds = eig_lds_bytes(kmax_live < DFF_EIG_LDS_LIMIT ? kmax_live : DFF_EIG_LDS_LIMIT, true);
+        if (lds > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_sym_eig_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_sym_eig_kernel<true>, dim3((unsigned)P), dim3(EigCfg<true>::T), (unsigned)lds, stream, a,
+                           (const long long*)ks_dev, Kmax, k, w, v, status, work, slice, 1, DFF_EIG_LDS_LIMIT);
+        HIPCHK(hipGetLastError());
+    }
+    if (path == 2 || (path == 0 && kmax_live > DFF_EIG_LDS_LIMIT)) {
+        const size_t lds = eig_lds_bytes(kmax_live, false);
+        if (lds > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_sym_eig_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_sym_eig_kernel<false>, dim3((unsigned)P), dim3(EigCfg<false>::T), (unsigned)lds, stream, a,
+                           (const long long*)ks_dev, Kmax, k, w, v, status, work, slice, path == 2 ? 1 : DFF_EIG_LDS_LIMIT + 1,
+                           DFF_MSM_MAXK);
         HIPCHK(hipGetLastError());
     }
     return DFF_OK;

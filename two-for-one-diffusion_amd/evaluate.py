@@ -2200,11 +2200,29 @@ class MarkovStateModel:
     def timescales(self, k=3):
         """The k slowest implied timescales -lagtime / ln(lambda_i), i = 2 .. k + 1, in frames (float64 (k,)); NaN for an
         eigenvalue <= 0 and where the active set has fewer than k + 1 states."""
-        lam = self.eigenvalues()[1:int(k) + 1]
-        out = np.full(int(k), np.nan)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            out[:lam.size] = np.where(lam > 0, -float(self.lagtime) / np.log(np.where(lam > 0, lam, 1.0)), np.nan)
-        return out
+        return _timescales_of(self.eigenvalues()[1:int(k) + 1], int(k), self.lagtime)
+
+    def symmetrized(self):
+        """M_ij = X_ij / sqrt(pi_i pi_j) from flux_matrix: pi^(1/2) T pi^(-1/2) of a reversible model, EXACTLY symmetric (X is,
+        and the denominator commutes), with T's eigenvalues; its eigenvectors v give T's right ones as v / sqrt(pi) and its
+        left ones as sqrt(pi) v.  ValueError when the model is not reversible or not fitted."""
+        if not self.reversible:
+            raise ValueError("MarkovStateModel: symmetrized needs a reversible model")
+        self._need_fit()
+        r = np.sqrt(self.stationary_distribution)
+        return self.flux_matrix / (r[:, None] * r[None, :])
+
+    def eigenvectors(self, k=3, side="right"):
+        """The eigenvectors of the k + 1 largest eigenvalues of the transition matrix, stationary one first -> float64
+        (k + 1, n_active), on the GPU (msm_spectrum; reversible models only).  side="right": psi with T psi = lambda psi,
+        sum_i pi_i psi_i^2 = 1 and the component of largest magnitude positive, so psi_1 = 1 everywhere; "left": phi =
+        pi psi, so phi_1 = pi.  Rows from n_active on are NaN."""
+        if side not in ("right", "left"):
+            raise ValueError("MarkovStateModel: side must be 'right' or 'left'")
+        sp = msm_spectrum(self, k=k, vectors=True, device=self.device)
+        if sp.status[0] != 0:
+            raise ValueError(f"MarkovStateModel: the eigenvectors did not converge (status {int(sp.status[0])})")
+        return (sp.right if side == "right" else sp.left)[0][:, self.active_set]
 
     def log_likelihood(self):
         """sum_ij C_ij ln T_ij over the active set (pairs without counts contribute 0)."""
@@ -2215,10 +2233,29 @@ class MarkovStateModel:
             return float(np.sum(Ca[m] * np.log(self.transition_matrix[m])))
 
 
+def _timescales_of(lam, k, lagtime):
+    """-lagtime / ln(lambda) of the eigenvalues lam (2nd, 3rd, ...) -> (k,); NaN for lambda <= 0, NaN or missing"""
+    out = np.full(k, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out[:lam.size] = np.where(lam > 0, -float(lagtime) / np.log(np.where(lam > 0, lam, 1.0)), np.nan)
+    return out
+
+
+EIGENSOLVERS = ("host", "device")
+
+
+def _check_eigensolver(eigensolver, what):
+    if eigensolver not in EIGENSOLVERS:
+        raise ValueError(f"{what}: eigensolver must be 'host' or 'device', not {eigensolver!r}")
+    return eigensolver == "device"
+
+
 def implied_timescales(labels, lagtimes, traj_lengths=None, n_states=None, k=3, reversible=True, *, tol=1e-12,
-                       max_iter=1_000_000, steps_per_sync=256, device="cuda:0"):
+                       max_iter=1_000_000, steps_per_sync=256, eigensolver="host", device="cuda:0"):
     """The k slowest implied timescales (frames) of a MarkovStateModel at every lag time of `lagtimes` -> float64
-    (n_lags, k).  The count matrices of up to 8 lag times come from one pass over the labels."""
+    (n_lags, k).  The count matrices of up to 8 lag times come from one pass over the labels.  eigensolver="device": the
+    spectra of each group of lag times from one msm_spectrum call (reversible models only) instead of np.linalg.eigvalsh."""
+    on_device = _check_eigensolver(eigensolver, "implied_timescales")
     dev = torch.device(device)
     lab = torch.as_tensor(labels).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
     lengths = _check_lengths(traj_lengths, int(lab.numel()))
@@ -2231,9 +2268,10 @@ def implied_timescales(labels, lagtimes, traj_lengths=None, n_states=None, k=3, 
     for l0 in range(0, len(lagtimes), binding.MSM_MAX_LAGS):
         group = lagtimes[l0:l0 + binding.MSM_MAX_LAGS]
         counts = binding.micro_transition_counts(lab, lengths, group, int(n_states)).cpu().numpy()
-        for i, lag in enumerate(group):
-            m = MarkovStateModel(lag, reversible, tol, max_iter, steps_per_sync, device=dev).fit_counts(counts[i])
-            out[l0 + i] = m.timescales(k)
+        models = [MarkovStateModel(lag, reversible, tol, max_iter, steps_per_sync, device=dev).fit_counts(counts[i])
+                  for i, lag in enumerate(group)]
+        out[l0:l0 + len(group)] = (msm_spectrum(models, k=k, device=dev).timescales if on_device
+                                   else [m.timescales(k) for m in models])
     return out
 
 
@@ -2362,16 +2400,19 @@ def percentile_interval(values, confidence=0.95):
 
 def bootstrap_msm(labels, lagtime, traj_lengths=None, n_states=None, *, n_resamples=100, block_frames=None, seed=0,
                   weights=None, k=3, tol=1e-12, max_iter=1_000_000, steps_per_sync=256, resample_batch=None,
-                  device="cuda:0"):
+                  eigensolver="host", device="cuda:0"):
     """Bootstrap of a reversible MarkovStateModel at `lagtime`: the units of resampling_units(traj_lengths, block_frames) are
     drawn with replacement n_resamples times (bootstrap_weights(n_units, n_resamples, seed), or `weights` (B, n_units)), the
     weighted counts of all resamples come from one pass over the labels and their estimators advance together, a problem
     leaving the batch at its first sweep below tol.  Resample b equals
     MarkovStateModel(lagtime, tol=tol, max_iter=max_iter, steps_per_sync=steps_per_sync).fit_counts(counts_b) bit for bit.
-    resample_batch bounds the resamples in flight (default: B K^2 counts and matrices under 1 GiB each) -> MsmBootstrap."""
+    resample_batch bounds the resamples in flight (default: B K^2 counts and matrices under 1 GiB each) -> MsmBootstrap.
+    eigensolver="host": the timescales of each resample from np.linalg.eigvalsh; "device": those of each batch from one
+    msm_spectrum call (dff_sym_eig_topk), equal up to the two solvers' rounding; every other field is the same."""
     k = int(k)
     if k < 1:
         raise ValueError("bootstrap_msm: k must be >= 1")
+    on_device = _check_eigensolver(eigensolver, "bootstrap_msm")
     plan = _BootstrapPlan("bootstrap_msm", labels, lagtime, traj_lengths, n_states, n_resamples, block_frames, seed, weights, tol,
                           max_iter, steps_per_sync, resample_batch, device)
     B, K = plan.B, plan.K
@@ -2381,9 +2422,12 @@ def bootstrap_msm(labels, lagtime, traj_lengths=None, n_states=None, *, n_resamp
     n_active, share = np.zeros(B, np.int64), np.zeros(B)
     converged, n_iter = np.zeros(B, bool), np.zeros(B, np.int64)
     for b0, models in plan.batches():
+        if on_device:
+            ts[b0:b0 + len(models)] = msm_spectrum(models, k=k, device=plan.device).timescales
         for i, m in enumerate(models):
             b = b0 + i
-            ts[b] = m.timescales(k)
+            if not on_device:
+                ts[b] = m.timescales(k)
             stationary[b, m.active_set] = m.stationary_distribution
             n_active[b], share[b], converged[b], n_iter[b] = len(m.active_set), m.active_count_share, m.converged, m.n_iter
     return MsmBootstrap(ts, stationary, n_active, share, converged, n_iter, plan.weights, plan.units, point)
@@ -2478,16 +2522,18 @@ def _sweep_batch(prob, sweeper, device, tol, max_iter, steps_per_sync):
 
 def implied_timescales_bootstrap(labels, lagtimes, traj_lengths=None, n_states=None, k=3, *, n_resamples=100,
                                  block_frames=None, seed=0, confidence=0.95, tol=1e-12, max_iter=1_000_000,
-                                 steps_per_sync=256, resample_batch=None, device="cuda:0"):
+                                 steps_per_sync=256, resample_batch=None, eigensolver="host", device="cuda:0"):
     """implied_timescales with error bars: (point, lo, hi), each float64 (n_lags, k) in frames -- the timescales of the
-    unresampled model at every lag time and the percentile interval of bootstrap_msm over the same draws at each."""
+    unresampled model at every lag time and the percentile interval of bootstrap_msm over the same draws at each
+    (eigensolver: as bootstrap_msm)."""
+    on_device = _check_eigensolver(eigensolver, "implied_timescales_bootstrap")
     lagtimes = [int(v) for v in lagtimes]
     point, lo, hi = (np.full((len(lagtimes), int(k)), np.nan) for _ in range(3))
     for i, lag in enumerate(lagtimes):
         bs = bootstrap_msm(labels, lag, traj_lengths, n_states, n_resamples=n_resamples, block_frames=block_frames, seed=seed,
                            k=k, tol=tol, max_iter=max_iter, steps_per_sync=steps_per_sync, resample_batch=resample_batch,
-                           device=device)
-        point[i] = bs.point.timescales(k)
+                           eigensolver=eigensolver, device=device)
+        point[i] = msm_spectrum(bs.point, k=k, device=device).timescales[0] if on_device else bs.point.timescales(k)
         lo[i], hi[i] = bs.interval(confidence)
     return point, lo, hi
 
@@ -2565,14 +2611,17 @@ class MsmEvaluator(_TrajectoryEvaluator):
     timescales_lo / timescales_hi (the percentile interval at `confidence`), timescales_std and bootstrap_failed, with
     ref_data also their _ref counterparts and log10_timescale_ratio_lo / _hi, percentiles of the ratio of resample b of
     the samples to resample b of the reference (seeds bootstrap_seed and bootstrap_seed + 1: independent draws).  The
-    discretisation is fixed: the centres are not refitted per resample.  The bootstraps stay on .bootstraps."""
+    discretisation is fixed: the centres are not refitted per resample.  The bootstraps stay on .bootstraps.
+    eigensolver="device" takes every spectrum from msm_spectrum (dff_sym_eig_topk) instead of np.linalg.eigvalsh."""
 
     KEYS = ("timescales", "n_active", "active_count_share", "converged", "samples_nonfinite")
 
     def __init__(self, mol_name, tica, n_microstates=200, lagtime=None, n_timescales=3, frame_time=1.0, ref_data=None,
                  ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None, confidence=0.95,
-                 bootstrap_seed=0, device="cuda:0"):
+                 bootstrap_seed=0, eigensolver="host", device="cuda:0"):
         super().__init__("MsmEvaluator", mol_name, frame_time, device)
+        self.eigensolver = eigensolver
+        self._spectrum_on_device = _check_eigensolver(eigensolver, "MsmEvaluator")
         self._point = _PointModel("MsmEvaluator", lagtime, n_bootstrap, block_frames, confidence, bootstrap_seed, self.device)
         self.lagtime = self._point.lagtime
         self.n_timescales = int(n_timescales)
@@ -2592,9 +2641,11 @@ class MsmEvaluator(_TrajectoryEvaluator):
 
     def _analyse(self, x, lengths, name):
         labels = self._micro.labels(self.project(x))
-        model, bs = self._point.fit(labels, lengths, self.n_microstates, name, bootstrap_msm, k=self.n_timescales)
+        model, bs = self._point.fit(labels, lengths, self.n_microstates, name, bootstrap_msm, k=self.n_timescales,
+                                    eigensolver=self.eigensolver)
         self.models[name], self.labels[name] = model, labels.cpu().numpy()
-        res = self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()))
+        ts = msm_spectrum(model, k=self.n_timescales, device=self.device).timescales[0] if self._spectrum_on_device else None
+        res = self.summarize(model, self.n_timescales, self.frame_time, int((labels < 0).sum()), timescales=ts)
         if bs is not None:
             self.bootstraps[name] = bs
             lo, hi = bs.interval(self._point.confidence)
@@ -2605,9 +2656,11 @@ class MsmEvaluator(_TrajectoryEvaluator):
         return res
 
     @staticmethod
-    def summarize(model, n_timescales=3, frame_time=1.0, samples_nonfinite=0):
-        """eval()'s dict from a fitted MarkovStateModel: numpy only."""
-        return {"timescales": [float(v) * frame_time for v in model.timescales(n_timescales)],
+    def summarize(model, n_timescales=3, frame_time=1.0, samples_nonfinite=0, timescales=None):
+        """eval()'s dict from a fitted MarkovStateModel: numpy only.  timescales: the model's, in frames, when they were
+        computed elsewhere (eigensolver="device"); None: model.timescales(n_timescales)."""
+        ts = model.timescales(n_timescales) if timescales is None else timescales
+        return {"timescales": [float(v) * frame_time for v in ts],
                 "n_active": float(len(model.active_set)), "active_count_share": float(model.active_count_share),
                 "converged": float(bool(model.converged)), "samples_nonfinite": float(samples_nonfinite)}
 
@@ -2629,6 +2682,98 @@ class MsmEvaluator(_TrajectoryEvaluator):
                 r = np.where((a > 0) & (b > 0), np.log10(a / b), np.nan)
             lo, hi = percentile_interval(r, self._point.confidence)
             res["log10_timescale_ratio_lo"], res["log10_timescale_ratio_hi"] = [float(v) for v in lo], [float(v) for v in hi]
+
+
+# ---- spectra of reversible models on the device: the largest eigenpairs of pi^(1/2) T pi^(-1/2), many models per call ----
+SPECTRUM_MAX_BATCH = binding.SYM_EIG_MAX_BATCH
+SPECTRUM_MAX_K = binding.SYM_EIG_MAX_K
+SPECTRUM_BYTES = 1 << 30         # matrices, vectors and workspace of one dff_sym_eig_topk call of spectral_solver
+
+
+class _DeviceSpectral:
+    """solve(a (P, Kmax, Kmax), ks (P,), k, vectors) -> (w (P, k), v (P, k, Kmax) | None, status (P,)), host arrays in and out:
+    the problems go to the GPU in chunks that stay under SPECTRUM_BYTES, each chunk one dff_sym_eig_topk call."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def __call__(self, a, ks, k, vectors):
+        a = np.ascontiguousarray(a, np.float64)
+        P, Kmax = a.shape[0], a.shape[1]
+        ks = np.asarray(ks, np.int32).reshape(-1)
+        per = 8 * (2 * Kmax * Kmax + 5 + k * (1 + Kmax))             # a matrix, a slice of the workspace, the outputs
+        chunk = max(1, min(SPECTRUM_MAX_BATCH, SPECTRUM_BYTES // per))
+        w, status = np.full((P, k), np.nan), np.zeros(P, np.int32)
+        v = np.full((P, k, Kmax), np.nan) if vectors else None
+        for p0 in range(0, P, chunk):
+            sl = slice(p0, min(P, p0 + chunk))
+            wd, vd, sd = binding.sym_eig_topk(torch.from_numpy(a[sl]).to(self.device), ks[sl], k, vectors=vectors)
+            w[sl], status[sl] = wd.cpu().numpy(), sd.cpu().numpy()
+            if vectors:
+                v[sl] = vd.cpu().numpy()
+        return w, v, status
+
+
+def spectral_solver(device):
+    """solve(a (P, Kmax, Kmax), ks (P,), k, vectors) -> (w, v | None, status) on the GPU (dff_sym_eig_topk): the k largest
+    eigenvalues, descending and NaN-padded, of P symmetric matrices, matrix p a compact (ks[p], ks[p]) matrix at the start of
+    its slot; unit eigenvectors in rows, the component of largest magnitude positive."""
+    return _DeviceSpectral(device)
+
+
+class MsmSpectrum:
+    """What msm_spectrum returns for P models: eigenvalues (P, k + 1), largest first (the first is 1), NaN-padded where an
+    active set has fewer states; timescales (P, k) in frames by the rule of MarkovStateModel.timescales; right and left
+    (P, k + 1, K) on the FULL state index, zero outside a model's active set (None when no vectors were asked for); status
+    (P,): dff_sym_eig_topk's (0 solved, 2: the vectors did not converge and are NaN)."""
+
+    def __init__(self, eigenvalues, timescales, right, left, status):
+        self.eigenvalues, self.timescales, self.right, self.left, self.status = eigenvalues, timescales, right, left, status
+
+
+def msm_spectrum(models, k=3, vectors=False, *, device=None):
+    """The k + 1 largest eigenvalues, the k slowest timescales and optionally the eigenvectors of one fitted reversible
+    MarkovStateModel or of a list of them, in ONE dff_sym_eig_topk call on their symmetrized() matrices (active sets of
+    differing size share it) -> MsmSpectrum.  Right eigenvectors psi = v / sqrt(pi): sum_i pi_i psi_i^2 = 1, the component of
+    largest magnitude positive (psi_1 = 1); left ones phi = pi psi (phi_1 = pi).  A model whose active set is one state is
+    not sent: lambda = 1, psi = phi = 1.  device: default the first model's.  ValueError for a model that is not reversible or
+    not fitted."""
+    ms = [models] if isinstance(models, MarkovStateModel) else list(models)
+    k = int(k)
+    if not 1 <= k < SPECTRUM_MAX_K:
+        raise ValueError(f"msm_spectrum: k must be 1..{SPECTRUM_MAX_K - 1}")
+    if not ms:
+        raise ValueError("msm_spectrum: no model")
+    mats = [m.symmetrized() for m in ms]
+    P, K = len(ms), max(len(m.count_matrix) for m in ms)
+    lam, status = np.full((P, k + 1), np.nan), np.zeros(P, np.int32)
+    right, left = (np.zeros((P, k + 1, K)), np.zeros((P, k + 1, K))) if vectors else (None, None)
+    send = [p for p, M in enumerate(mats) if len(M) > 1]
+    for p, M in enumerate(mats):
+        if len(M) == 1:
+            lam[p, 0] = 1.0
+            if vectors:
+                right[p, 0, ms[p].active_set] = left[p, 0, ms[p].active_set] = 1.0
+                right[p, 1:, ms[p].active_set] = left[p, 1:, ms[p].active_set] = np.nan
+    if send:
+        ks = np.array([len(mats[p]) for p in send], np.int32)
+        Kmax = int(ks.max())
+        a = np.zeros((len(send), Kmax * Kmax))
+        for i, p in enumerate(send):
+            a[i, :mats[p].size] = mats[p].reshape(-1)
+        w, v, st = spectral_solver(device if device is not None else ms[0].device)(a.reshape(len(send), Kmax, Kmax), ks, k + 1,
+                                                                                 bool(vectors))
+        for i, p in enumerate(send):
+            lam[p], status[p] = w[i], st[i]
+            if vectors:
+                act, r = ms[p].active_set, np.sqrt(ms[p].stationary_distribution)
+                psi = v[i][:, :len(act)] / r
+                top = np.argmax(np.abs(np.nan_to_num(psi)), axis=1)
+                sign = np.where(psi[np.arange(k + 1), top] < 0, -1.0, 1.0)[:, None]
+                right[p][:, act] = psi * sign
+                left[p][:, act] = v[i][:, :len(act)] * r * sign
+    ts = np.stack([_timescales_of(lam[p, 1:], k, m.lagtime) for p, m in enumerate(ms)])
+    return MsmSpectrum(lam, ts, right, left, status)
 
 
 # ---- mean first-passage times, committors and reactive flux of a Markov state model ----
