@@ -757,6 +757,41 @@ int dff_sym_eig_topk(int device, const double* a_dev, const int32_t* ks_host, in
  * above the limit is then refused), 2 = every problem in the workspace. */
 int dff_debug_sym_eig_path(int path);
 
+/* ---- Row vectors through a transition matrix, step after step: w_{s+1} = w_s T for up to 16 start vectors per problem and, after
+ * every step, their scalar products with up to 16 observables; P problems per call, one workgroup per problem for all S steps
+ * (csrc/dff_msm_propagate.hip; evaluate.py: msm_propagate, msm_relaxation, msm_autocorrelation, chapman_kolmogorov) ----
+ * Problem p has K_p = ks_host[p] states and reads matrix mat_of_host[p] (NULL: matrix p, n_mat >= P): a COMPACT (K_p, K_p) row-major
+ * fp64 matrix at t_dev + m Kmax^2 (the layout of dff_sym_eig_topk).  Problems may share a matrix; those that do must agree on K_p.
+ * The matrix is a GENERAL dense matrix: it need be neither stochastic nor reversible.  w0_dev (P, M, Kmax): M start row vectors;
+ * obs_dev (P, R, Kmax): R observables; both read at indices below K_p only.  With w_0 = w0 and w_{s+1} = w_s T,
+ *   out_dev (P, S + 1, M, R):   out[s][m][r] = sum_j w_s[m][j] obs[r][j],   s = 0 .. S
+ *   w_last_dev (P, M, Kmax), or NULL: w_S at indices below K_p; elements from K_p on are not written.
+ * status_dev (P) int32:
+ *   0   solved
+ *   1   a non-finite entry in the problem's matrix, start vectors or observables (below K_p)     every output of the problem is NaN
+ *   2   finite inputs, but the chain overflowed and produced a NaN (inf - inf, 0 inf)             every output of the problem is NaN
+ * Status 0 never comes with a NaN; a failed problem touches no other.
+ * Arithmetic: (w T)[m][j] is ONE chain of fused multiply-adds over i = 0 .. K_p - 1, started from +0, on both paths; out[s][m][r]
+ * is 32 such chains over j = c, c + 32, ..., added by a fixed tree.  The bits of out[.][m][.] and w_last[m] follow from the matrix,
+ * row m of w0, obs and the path alone: not from P, the problem's place in the batch, its neighbours, the workspace, the call, the
+ * other start rows or M (a problem with M = 3 equals three M = 1 problems that share its matrix, bit for bit; likewise R), nor
+ * from S (the first S1 + 1 steps of a longer run are the run to S1).  Up to dff_msm_propagate_lds_limit states the matrix is
+ * copied into LDS once and all steps run from there; above, it streams from global memory once per step (all M rows per pass).
+ * The two paths run the same chains, so they agree bit for bit as well; that is not part of the contract.
+ * 1 <= K_p <= Kmax <= DFF_MSM_MAXK, 1 <= P, n_mat <= 16384, 1 <= M, R <= 16, 0 <= S <= 65535, P (S + 1) M R <= 2^28; device pointers,
+ * `stream` only, no read-back, refusals on the host before any device call, no atomics, no workgroup waits on another.
+ * workspace_dev 8-byte aligned, contents irrelevant. */
+/* Bytes of device workspace the call below needs (P problem descriptors); -1 on bad arguments. */
+long long dff_msm_propagate_workspace_bytes(int P, int Kmax, int M, int R);
+/* The largest K_p that is propagated out of LDS (a compile-time constant). */
+int dff_msm_propagate_lds_limit(void);
+int dff_msm_propagate(int device, const double* t_dev, int n_mat, const int32_t* mat_of_host, const int32_t* ks_host, int P,
+                      int Kmax, const double* w0_dev, int M, const double* obs_dev, int R, int S, double* out_dev,
+                      double* w_last_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* For tests and benchmarks, process-wide: 0 = the path follows K_p (the default), 1 = every problem in LDS (a call with a K_p
+ * above the limit is then refused), 2 = every problem with its matrix streamed from global memory. */
+int dff_debug_msm_propagate_path(int path);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -15,6 +15,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
                                  [--passage [HELDOUT.pt] --passage-states K --passage-lag L [--passage-cv q|rmsd]
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
+                                 [--ck [HELDOUT.pt] --ck-states K --ck-lag L [--ck-sets M] [--ck-multiples 1,2,3,4,5]
+                                  [--ck-bootstrap B]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]
                                   [--msm-eigensolver host|device] [--msm-eigenvectors N]]
@@ -71,6 +73,12 @@ log10_timescale_ratio_lo / _hi, and "timescales_lo" / "timescales_hi" in "implie
 --msm-eigensolver device takes every spectrum from dff_sym_eig_topk on the GPU (all resamples of a bootstrap batch in one call)
 instead of numpy on the host, the default; --msm-eigenvectors N adds "eigenvectors": the N slowest right eigenvectors of the
 samples' model on the full microstate index ("right"), their eigenvalues and the active set.
+
+--ck adds the validity check of the Markov state model (ChapmanKolmogorovEvaluator): microstates and lag time as for --msm
+(--ck-states K, --ck-lag L), --ck-sets M metastable sets from the model's leading eigenvectors (3), and for every multiple k of
+--ck-multiples (1,2,3,4,5) the set-to-set probabilities that T(L)^k predicts against those of the model estimated at lag k L,
+with the model's autocorrelation of the first TIC against the measured one; --ck-bootstrap B adds percentile intervals.  With
+HELDOUT.pt also for that MD data, which then defines the sets.  Needs --parallel-sim.
 """
 import argparse
 import json
@@ -351,6 +359,45 @@ def passage(a, x):
     return res
 
 
+ck_sets = number(int, lambda v: 1 <= v <= evaluate.PROPAGATE_MAX_ROWS, "expected a number of metastable sets in 1..16, got {text!r}")
+
+
+def ck_multiples(text):
+    try:
+        ks = [int(v) for v in text.split(",")]
+    except ValueError:
+        ks = []
+    if not ks or any(k < 1 for k in ks) or len(set(ks)) != len(ks):
+        raise argparse.ArgumentTypeError(f"expected distinct comma-separated multiples >= 1, got {text!r}")
+    return ks
+
+
+def ck_arguments(a):
+    """(states, lag, sets, multiples, resamples) of --ck, None without it; refused without --ck-states / --ck-lag and
+    --parallel-sim; the options of --ck are refused without it"""
+    if a.ck is None:
+        if any(v is not None for v in (a.ck_states, a.ck_lag, a.ck_sets, a.ck_multiples, a.ck_bootstrap)):
+            raise SystemExit("--ck-states, --ck-lag, --ck-sets, --ck-multiples and --ck-bootstrap need --ck")
+        return None
+    if a.ck_states is None or a.ck_lag is None:
+        raise SystemExit("--ck needs --ck-states K and --ck-lag L (frames)")
+    if a.parallel_sim is None:
+        raise SystemExit("--ck needs --parallel-sim (the trajectories of the samples)")
+    return a.ck_states, a.ck_lag, a.ck_sets or 3, a.ck_multiples or [1, 2, 3, 4, 5], a.ck_bootstrap or 0
+
+
+def ck(a, x):
+    K, lag, n_sets, multiples, boots = ck_arguments(a)
+    ref, ref_lengths = ordered_frames(a.ck) if a.ck else (None, None)
+    ev = evaluate.ChapmanKolmogorovEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, lagtime=lag, n_sets=n_sets,
+                                             multiples=multiples, frame_time=a.frame_time, ref_data=ref,
+                                             ref_traj_lengths=ref_lengths, n_bootstrap=boots, device=a.device)
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
+    res.update({"n_microstates": K, "lagtime": lag, "multiples": multiples, "n_bootstrap": boots,
+                "sets": [[int(i) for i in s] for s in ev.sets]})
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -438,6 +485,17 @@ def build_parser():
                     help="a microstate is in a set when its mean cv is <= LO or >= HI (with --passage; 0.2,0.9 for q)")
     ap.add_argument("--passage-bootstrap", type=msm_bootstrap, default=None, metavar="B",
                     help="bootstrap error bars of the times and rates from B resamples of the trajectories (with --passage)")
+    ap.add_argument("--ck", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report the Chapman-Kolmogorov test of a Markov state model on its metastable sets and its predicted "
+                         "against the measured autocorrelation of the first TIC (time-ordered Langevin samples; needs --parallel-sim, "
+                         "--ck-states and --ck-lag); with HELDOUT.pt also for that MD data, which then defines the sets")
+    ap.add_argument("--ck-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --ck)")
+    ap.add_argument("--ck-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --ck)")
+    ap.add_argument("--ck-sets", type=ck_sets, default=None, metavar="M", help="metastable sets (with --ck; 3)")
+    ap.add_argument("--ck-multiples", type=ck_multiples, default=None, metavar="1,2,3,4,5",
+                    help="multiples of the lag time that are tested (with --ck)")
+    ap.add_argument("--ck-bootstrap", type=msm_bootstrap, default=None, metavar="B",
+                    help="percentile intervals of the test from B resamples of the trajectories (with --ck)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -462,6 +520,7 @@ def main():
     msm_bootstrap_arguments(a)
     msm_spectrum_arguments(a)
     passage_arguments(a)
+    ck_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -497,6 +556,8 @@ def main():
         res["msm"] = msm(a, x)
     if a.passage is not None:
         res["passage"] = passage(a, x)
+    if a.ck is not None:
+        res["ck"] = ck(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

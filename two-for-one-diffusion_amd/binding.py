@@ -144,6 +144,11 @@ SYMBOLS = {
     "dff_sym_eig_lds_limit": (C.c_int, []),
     "dff_sym_eig_topk": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "dff_debug_sym_eig_path": (C.c_int, [C.c_int]),
+    "dff_msm_propagate_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dff_msm_propagate_lds_limit": (C.c_int, []),
+    "dff_msm_propagate": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P,
+                                    _P, C.c_size_t, _P]),
+    "dff_debug_msm_propagate_path": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1261,3 +1266,70 @@ def sym_eig_topk(a, ks, k: int, vectors=False, workspace=None):
                                      _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
                                      _stream(a)), "dff_sym_eig_topk")
     return w, v, status
+
+
+# ---- row vectors through a transition matrix, step after step (dff_msm_propagate) ----
+MSM_PROPAGATE_MAX_BATCH = 16384
+MSM_PROPAGATE_MAX_ROWS = 16
+MSM_PROPAGATE_MAX_STEPS = 65535
+
+
+def msm_propagate_workspace_bytes(P: int, Kmax: int, M: int, R: int) -> int:
+    return _workspace_bytes("dff_msm_propagate_workspace_bytes", int(P), int(Kmax), int(M), int(R))
+
+
+def msm_propagate_lds_limit() -> int:
+    """The largest matrix dff_msm_propagate propagates out of LDS, read from the library."""
+    return int(load_library().dff_msm_propagate_lds_limit())
+
+
+def debug_msm_propagate_path(path: int):
+    """Tests and benchmarks only: 0 = by the matrix size, 1 = every problem in LDS, 2 = every matrix streamed from global memory."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_msm_propagate_path(int(path)), "dff_debug_msm_propagate_path")
+
+
+def msm_propagate(t, mat_of, ks, w0, obs, n_steps: int, want_last=False, workspace=None):
+    """P propagation problems in one call (dff_msm_propagate): t (n_mat, Kmax, Kmax) contiguous float64 CUDA, matrix m a COMPACT
+    (K, K) matrix at the start of its slot; mat_of (P,) host integers, the matrix of each problem (None: problem p reads matrix
+    p); ks (P,) host integers; w0 (P, M, Kmax) start row vectors and obs (P, R, Kmax) observables, contiguous float64 CUDA,
+    read below ks[p].  Returns (out, w_last, status), CUDA tensors: out float64 (P, n_steps + 1, M, R) with out[p, s, m, r] =
+    sum_j (w0[p, m] T^s)[j] obs[p, r, j]; w_last float64 (P, M, Kmax), the vectors after the last step (NaN beyond ks[p], as
+    allocated here), or None without `want_last`; status int32 (P,): 0 solved, 1 a non-finite input, 2 an overflow that made a
+    NaN (all outputs of the problem NaN in both cases).  Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated
+    here when None)."""
+    import torch
+    lib = load_library()
+    f64 = torch.float64
+    n_mat, Kmax = (int(t.shape[0]), int(t.shape[1])) if isinstance(t, torch.Tensor) and t.dim() == 3 else (-1, -1)
+    P, M = (int(w0.shape[0]), int(w0.shape[1])) if isinstance(w0, torch.Tensor) and w0.dim() == 3 else (-1, -1)
+    R = int(obs.shape[1]) if isinstance(obs, torch.Tensor) and obs.dim() == 3 else -1
+    if not (_is_tensor(t, f64, (n_mat, Kmax, Kmax)) and _is_tensor(w0, f64, (P, M, Kmax)) and _is_tensor(obs, f64, (P, R, Kmax))
+            and w0.device == t.device and obs.device == t.device):
+        raise ValueError("t (n_mat, Kmax, Kmax), w0 (P, M, Kmax) and obs (P, R, Kmax) must be contiguous float64 CUDA tensors on "
+                         "one device")
+    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+    if kh.size != P:
+        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
+    mh = None
+    if mat_of is not None:
+        mh = np.ascontiguousarray(np.asarray(mat_of, dtype=np.int32).reshape(-1))
+        if mh.size != P:
+            raise ValueError(f"mat_of must hold one matrix index per problem: {mh.size} for P = {P}")
+    S = int(n_steps)
+    if not 0 <= S <= MSM_PROPAGATE_MAX_STEPS:
+        raise ValueError(f"n_steps must be 0..{MSM_PROPAGATE_MAX_STEPS}, not {S}")
+    if not (1 <= M <= MSM_PROPAGATE_MAX_ROWS and 1 <= R <= MSM_PROPAGATE_MAX_ROWS):
+        raise ValueError(f"the numbers of start vectors and observables must be 1..{MSM_PROPAGATE_MAX_ROWS}, not {M} and {R}")
+    if P * (S + 1) * M * R > 1 << 28:
+        raise ValueError(f"{P * (S + 1) * M * R} output values, at most 2^28 per call")
+    out = torch.empty((P, S + 1, M, R), dtype=f64, device=t.device)
+    w_last = torch.full((P, M, Kmax), float("nan"), dtype=f64, device=t.device) if want_last else None
+    status = torch.empty(P, dtype=torch.int32, device=t.device)
+    if workspace is None:
+        workspace = torch.empty(max(msm_propagate_workspace_bytes(P, Kmax, M, R), 8), dtype=torch.uint8, device=t.device)
+    _check(lib, lib.dff_msm_propagate(t.device.index, _ptr(t), n_mat, mh.ctypes.data_as(C.c_void_p) if mh is not None else None,
+                                      kh.ctypes.data_as(C.c_void_p), P, Kmax, _ptr(w0), M, _ptr(obs), R, S, _ptr(out),
+                                      _ptr(w_last), _ptr(status), _ptr(workspace),
+                                      int(workspace.numel() * workspace.element_size()), _stream(t)), "dff_msm_propagate")
+    return out, w_last, status

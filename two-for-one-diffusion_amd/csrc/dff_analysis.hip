@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_* and dff_sym_eig_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_* and dff_msm_propagate*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <vector>
@@ -18,6 +18,7 @@
 #include "dff_msm_batch.hip"
 #include "dff_msm_passage.hip"
 #include "dff_sym_eig.hip"
+#include "dff_msm_propagate.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1360,6 +1361,89 @@ extern "C" int dff_sym_eig_topk(int device, const double* a, const int32_t* ks, 
         hipLaunchKernelGGL(dff_sym_eig_kernel<false>, dim3((unsigned)P), dim3(EigCfg<false>::T), (unsigned)lds, stream, a,
                            (const long long*)ks_dev, Kmax, k, w, v, status, work, slice, path == 2 ? 1 : DFF_EIG_LDS_LIMIT + 1,
                            DFF_MSM_MAXK);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row vectors through a transition matrix, step after step (dff_msm_propagate.hip)
+// ---------------------------------------------------------------------------------------------
+// which path propagates a problem: 0 = by its size, 1 = LDS, 2 = the matrix streamed from global memory
+static std::atomic<int> g_prop_path{0};
+
+extern "C" int dff_debug_msm_propagate_path(int path) {
+    if (path < 0 || path > 2) return fail(DFF_EINVAL, "debug_msm_propagate_path: 0 (by size), 1 (LDS) or 2 (workspace)");
+    g_prop_path.store(path);
+    return DFF_OK;
+}
+
+extern "C" int dff_msm_propagate_lds_limit(void) { return DFF_PROP_LDS_LIMIT; }
+
+static int prop_check_batch(int P, int Kmax, int M, int R, const char* what) {
+    if (P < 1 || P > DFF_PROP_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_PROP_MAXP);
+    if (M < 1 || M > DFF_PROP_MAXROWS) return fail(DFF_EINVAL, "%s: the number of start vectors must be 1..%d", what, DFF_PROP_MAXROWS);
+    if (R < 1 || R > DFF_PROP_MAXROWS) return fail(DFF_EINVAL, "%s: the number of observables must be 1..%d", what, DFF_PROP_MAXROWS);
+    return micro_check_count(Kmax, what, "states");
+}
+
+extern "C" long long dff_msm_propagate_workspace_bytes(int P, int Kmax, int M, int R) {
+    if (prop_check_batch(P, Kmax, M, R, "msm_propagate_workspace_bytes")) return -1;
+    return (long long)P * (long long)sizeof(long long);              // the problem descriptors
+}
+
+extern "C" int dff_msm_propagate(int device, const double* t, int n_mat, const int32_t* mat_of, const int32_t* ks, int P, int Kmax,
+                                 const double* w0, int M, const double* obs, int R, int S, double* out, double* w_last,
+                                 int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "msm_propagate";
+    int rc = prop_check_batch(P, Kmax, M, R, what);
+    if (rc) return rc;
+    if (S < 0 || S > DFF_PROP_MAXSTEPS) return fail(DFF_EINVAL, "%s: the number of steps must be 0..%d", what, DFF_PROP_MAXSTEPS);
+    if ((long long)P * (S + 1) * M * R > DFF_PROP_MAXOUT)
+        return fail(DFF_EINVAL, "%s: %lld output values, at most %lld per call", what, (long long)P * (S + 1) * M * R, DFF_PROP_MAXOUT);
+    if (n_mat < 1 || n_mat > DFF_PROP_MAXP) return fail(DFF_EINVAL, "%s: the number of matrices must be 1..%d", what, DFF_PROP_MAXP);
+    if (!t || !ks || !w0 || !obs || !out || !status)
+        return fail(DFF_EINVAL, "%s: null matrices / state counts / start vectors / observables / out / status", what);
+    if (!mat_of && n_mat < P) return fail(DFF_EINVAL, "%s: %d matrices for %d problems and no mat_of", what, n_mat, P);
+    const int path = g_prop_path.load();
+    int kmax_live = 0, kmin_live = DFF_MSM_MAXK;
+    std::vector<int> k_of((size_t)n_mat, 0);
+    for (int p = 0; p < P; ++p) {
+        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
+        const int mo = mat_of ? mat_of[p] : p;
+        if (mo < 0 || mo >= n_mat) return fail(DFF_EINVAL, "%s: problem %d takes matrix %d of %d", what, p, mo, n_mat);
+        int& km = k_of[(size_t)mo];
+        if (km && km != ks[p])
+            return fail(DFF_EINVAL, "%s: problem %d reads matrix %d with %d states, an earlier problem with %d", what, p, mo, (int)ks[p], km);
+        km = ks[p];
+        if (path == 1 && ks[p] > DFF_PROP_LDS_LIMIT)
+            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_PROP_LDS_LIMIT);
+        if (ks[p] > kmax_live) kmax_live = ks[p];
+        if (ks[p] < kmin_live) kmin_live = ks[p];
+    }
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_propagate_workspace_bytes(P, Kmax, M, R), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<long long> desc((size_t)P);
+    for (int p = 0; p < P; ++p) desc[p] = ((long long)(mat_of ? mat_of[p] : p) << DFF_PROP_KBITS) | ks[p];
+    long long* desc_dev = (long long*)workspace;
+    if ((rc = msmb_upload(stream, desc.data(), P, desc_dev))) return rc;
+    if (path == 1 || (path == 0 && kmin_live <= DFF_PROP_LDS_LIMIT)) {
+        const size_t lds = prop_lds_bytes(kmax_live < DFF_PROP_LDS_LIMIT ? kmax_live : DFF_PROP_LDS_LIMIT, true);
+        if (lds > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_prop_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_prop_kernel<true>, dim3((unsigned)P), dim3(DFF_PROP_THREADS), (unsigned)lds, stream, t,
+                           (const long long*)desc_dev, Kmax, w0, M, obs, R, S, out, w_last, status, 1, DFF_PROP_LDS_LIMIT);
+        HIPCHK(hipGetLastError());
+    }
+    if (path == 2 || (path == 0 && kmax_live > DFF_PROP_LDS_LIMIT)) {
+        const size_t lds = prop_lds_bytes(kmax_live, false);
+        if (lds > 64 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_prop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_prop_kernel<false>, dim3((unsigned)P), dim3(DFF_PROP_THREADS), (unsigned)lds, stream, t,
+                           (const long long*)desc_dev, Kmax, w0, M, obs, R, S, out, w_last, status,
+                           path == 2 ? 1 : DFF_PROP_LDS_LIMIT + 1, DFF_MSM_MAXK);
         HIPCHK(hipGetLastError());
     }
     return DFF_OK;

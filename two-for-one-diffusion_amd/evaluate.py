@@ -1899,8 +1899,8 @@ class RelaxationEvaluator(_TrajectoryEvaluator):
 # restated from the literature -- k-means microstates, sliding-window counts, the largest strongly connected set, the
 # reversible maximum-likelihood estimator of Bowman et al. 2009 / Prinz et al. 2011 (algorithm 1, plain form) -- and tested
 # against a from-scratch fp64 oracle (oracle/msm.py).
-# Out of scope: PCCA+ and other coarse-graining, mean first-passage times / transition-path theory, Bayesian posteriors (error bars: bootstrap_msm below),
-# Chapman-Kolmogorov tests, sparse count matrices.
+# Out of scope: optimised PCCA+ and coarse-grained models (metastable_sets and chapman_kolmogorov are at the end of this file), Bayesian
+# posteriors (error bars: bootstrap_msm below), sparse count matrices.
 # =====================================================================================================
 MSM_MAX_STATES = binding.MSM_MAX_STATES
 
@@ -3126,3 +3126,427 @@ class MsmPassageEvaluator(_TrajectoryEvaluator):
     def _compare(self, res, ref):
         for which in ("folding", "unfolding"):
             res[f"log10_mfpt_ratio_{which}"] = _log10_ratio(res[f"mfpt_{which}"], ref[f"mfpt_{which}"])
+
+
+# ---- propagation: row vectors through a model's transition matrix, step after step (dff_msm_propagate) ----
+# What needs it: the Chapman-Kolmogorov test (does T(tau)^k predict what the model estimated at lag k tau shows?), the relaxation
+# of an observable from a start distribution, and the model's autocorrelation function, which reads against autocorrelation()
+# on the trajectories.  Vectors and observables are given on the FULL state index; states outside the active set are dropped.
+PROPAGATE_MAX_BATCH = binding.MSM_PROPAGATE_MAX_BATCH
+PROPAGATE_MAX_ROWS = binding.MSM_PROPAGATE_MAX_ROWS
+PROPAGATE_MAX_STEPS = binding.MSM_PROPAGATE_MAX_STEPS
+PROPAGATE_BYTES = 1 << 30        # matrices, vectors and outputs of one dff_msm_propagate call of propagator
+
+
+class _DevicePropagator:
+    """propagate(t (n_mat, Kmax, Kmax), mat_of (P,), ks (P,), w0 (P, M, Kmax), obs (P, R, Kmax), n_steps, want_last) -> (out
+    (P, n_steps + 1, M, R), w_last (P, M, Kmax) | None, status (P,)), host arrays in and out: the problems go to the GPU in chunks
+    that stay under PROPAGATE_BYTES, each chunk one dff_msm_propagate call on the matrices it uses."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def __call__(self, t, mat_of, ks, w0, obs, n_steps, want_last=False):
+        w0, obs = np.ascontiguousarray(w0, np.float64), np.ascontiguousarray(obs, np.float64)
+        P, M, Kmax = w0.shape
+        R, S = obs.shape[1], int(n_steps)
+        t = np.ascontiguousarray(t, np.float64).reshape(-1, Kmax, Kmax)
+        mat_of, ks = np.asarray(mat_of, np.int64).reshape(-1), np.asarray(ks, np.int32).reshape(-1)
+        per = 8 * (Kmax * Kmax + (2 * M + R) * Kmax + (S + 1) * M * R + 2)
+        chunk = max(1, min(PROPAGATE_MAX_BATCH, PROPAGATE_BYTES // per, (1 << 28) // ((S + 1) * M * R)))
+        out, status = np.full((P, S + 1, M, R), np.nan), np.zeros(P, np.int32)
+        last = np.full((P, M, Kmax), np.nan) if want_last else None
+        dev = self.device
+        for p0 in range(0, P, chunk):
+            sl = slice(p0, min(P, p0 + chunk))
+            used, local = np.unique(mat_of[sl], return_inverse=True)
+            od, ld, sd = binding.msm_propagate(torch.from_numpy(t[used]).to(dev), local.astype(np.int32), ks[sl],
+                                               torch.from_numpy(w0[sl]).to(dev), torch.from_numpy(obs[sl]).to(dev), S,
+                                               want_last=want_last)
+            out[sl], status[sl] = od.cpu().numpy(), sd.cpu().numpy()
+            if want_last:
+                last[sl] = ld.cpu().numpy()
+        return out, last, status
+
+
+def propagator(device):
+    """propagate(t (n_mat, Kmax, Kmax), mat_of (P,), ks (P,), w0 (P, M, Kmax), obs (P, R, Kmax), n_steps, want_last=False) ->
+    (out (P, n_steps + 1, M, R), w_last | None, status (P,)) on the GPU (dff_msm_propagate): w_{s+1} = w_s T, out[p, s, m, r] =
+    sum_j w_s[m][j] obs[r][j]; matrix m is a compact (K, K) matrix at the start of its slot."""
+    return _DevicePropagator(device)
+
+
+def _check_steps(n_steps, what):
+    S = int(n_steps)
+    if S != n_steps or not 0 <= S <= PROPAGATE_MAX_STEPS:
+        raise ValueError(f"{what}: n_steps must be an integer in 0..{PROPAGATE_MAX_STEPS}")
+    return S
+
+
+def _state_rows(x, n_states, what, name):
+    """x as finite float64 (rows, n_states), rows 1..PROPAGATE_MAX_ROWS"""
+    a = np.array(x, np.float64, ndmin=2)
+    if a.ndim != 2 or a.shape[1] != n_states or not 1 <= a.shape[0] <= PROPAGATE_MAX_ROWS:
+        raise ValueError(f"{what}: {name} must be (1..{PROPAGATE_MAX_ROWS}, {n_states}) on the full state index")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: {name} must be finite")
+    return a
+
+
+def _propagate_on_models(models, mat_of, starts, observables, n_steps, device, what):
+    """One propagator call: problem p runs on models[mat_of[p]] with the start rows starts[p] (M, n_active) and the observables
+    observables[p] (R, n_active), both on the model's ACTIVE index -> out (P, n_steps + 1, M, R)."""
+    P = len(mat_of)
+    ks_m = [len(m.active_set) for m in models]
+    Kmax = max(ks_m)
+    t = np.zeros((len(models), Kmax * Kmax))
+    for i, m in enumerate(models):
+        m._need_fit()
+        t[i, :ks_m[i] * ks_m[i]] = np.asarray(m.transition_matrix, np.float64).reshape(-1)
+    M, R = starts[0].shape[0], observables[0].shape[0]
+    w0, obs, ks = np.zeros((P, M, Kmax)), np.zeros((P, R, Kmax)), np.zeros(P, np.int32)
+    for p in range(P):
+        K = ks_m[mat_of[p]]
+        w0[p, :, :K], obs[p, :, :K], ks[p] = starts[p], observables[p], K
+    out, _, status = propagator(device if device is not None else models[0].device)(
+        t.reshape(len(models), Kmax, Kmax), np.asarray(mat_of, np.int64), ks, w0, obs, n_steps)
+    if (status != 0).any():
+        bad = int(np.flatnonzero(status)[0])
+        raise ValueError(f"{what}: problem {bad} failed (status {int(status[bad])}): a non-finite entry in its transition matrix, "
+                         "or an overflow on the way")
+    return out
+
+
+def msm_propagate(models, start, observables, n_steps, *, device=None):
+    """Distributions through the transition matrices of one fitted MarkovStateModel or a list of them, in ONE
+    dff_msm_propagate call (active sets of differing size share it; reversible or not): `start` (M, n_states) row vectors and
+    `observables` (R, n_states), both on the full state index, M, R <= 16; a model's inactive states are dropped from both
+    -> float64 (P, n_steps + 1, M, R), out[p, s, m, r] = sum_j (start_m T_p^s)_j observable_r,j over model p's active set."""
+    ms = [models] if isinstance(models, MarkovStateModel) else list(models)
+    if not ms:
+        raise ValueError("msm_propagate: no model")
+    S = _check_steps(n_steps, "msm_propagate")
+    for m in ms:
+        m._need_fit()
+    n = len(ms[0].count_matrix)
+    if any(len(m.count_matrix) != n for m in ms):
+        raise ValueError("msm_propagate: the models must share one state index")
+    w, o = _state_rows(start, n, "msm_propagate", "start"), _state_rows(observables, n, "msm_propagate", "observables")
+    return _propagate_on_models(ms, list(range(len(ms))), [w[:, m.active_set] for m in ms], [o[:, m.active_set] for m in ms], S,
+                                device, "msm_propagate")
+
+
+def msm_relaxation(model, p0, a, n_steps, *, device=None):
+    """E[a] after s = 0 .. n_steps lag times when the model starts from the distribution p0 (n_states,): sum_j (p0 T^s)_j a_j ->
+    float64 (n_steps + 1,), or (n_steps + 1, d) for a of shape (d, n_states), d <= 16.  p0 is used as given (restricted to the
+    active set, not renormalised)."""
+    a = np.asarray(a, np.float64)
+    out = msm_propagate(model, np.asarray(p0, np.float64).reshape(1, -1), a, n_steps, device=device)[0, :, 0, :]
+    return out[:, 0] if a.ndim == 1 else out
+
+
+class MsmAutocorrelation:
+    """What msm_autocorrelation returns: lags (n_steps + 1,) in frames (s lagtime), cov and acf (n_steps + 1,) -- or
+    (n_steps + 1, d) for d observables --, mean (the stationary mean of each observable)."""
+
+    def __init__(self, lags, cov, acf, mean):
+        self.lags, self.cov, self.acf, self.mean = lags, cov, acf, mean
+
+
+def msm_autocorrelation(model, a, n_steps, *, device=None):
+    """The autocorrelation function the model predicts for the state function a (n_states,) or (d, n_states), d <= 16, at the
+    lags s lagtime, s = 0 .. n_steps: C(s) = sum_i pi_i a~_i (T^s a~)_i with a~ = a - sum_i pi_i a_i, acf = C(s) / C(0) ->
+    MsmAutocorrelation.  The start rows are pi a~, the observables a~ (one dff_msm_propagate call).  acf[s] reads against
+    autocorrelation(series, ...).acf[s * lagtime] of the series a[labels]."""
+    model._need_fit()
+    S = _check_steps(n_steps, "msm_autocorrelation")
+    a = np.asarray(a, np.float64)
+    rows = _state_rows(a, len(model.count_matrix), "msm_autocorrelation", "a")[:, model.active_set]
+    pi = model.stationary_distribution
+    mean = rows @ pi
+    at = rows - mean[:, None]
+    out = _propagate_on_models([model], [0], [at * pi], [at], S, device, "msm_autocorrelation")[0]
+    cov = np.stack([out[:, i, i] for i in range(len(rows))], axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        acf = cov / cov[:1]
+    lags = np.arange(S + 1, dtype=np.int64) * model.lagtime
+    if a.ndim == 1:
+        return MsmAutocorrelation(lags, cov[:, 0], acf[:, 0], float(mean[0]))
+    return MsmAutocorrelation(lags, cov, acf, mean)
+
+
+# ---- metastable sets: the inner-simplex step of PCCA+ (Weber & Galliat) on the model's right eigenvectors ----
+def inner_simplex(psi):
+    """The rows of psi (n, m) that span the largest simplex, greedily: the row of largest norm; the rows shifted by it; m - 1
+    times the row of largest norm, projected out of all rows -> (m,) row indices.  The lowest index wins a tie."""
+    v = np.array(psi, np.float64)
+    n, m = v.shape
+    idx = np.zeros(m, np.int64)
+    idx[0] = int(np.argmax((v * v).sum(axis=1)))
+    v = v - v[idx[0]]
+    for j in range(1, m):
+        nrm = np.sqrt((v * v).sum(axis=1))
+        idx[j] = int(np.argmax(nrm))
+        if not nrm[idx[j]] > 0:
+            raise ValueError("inner_simplex: the rows span fewer than m - 1 dimensions")
+        u = v[idx[j]] / nrm[idx[j]]
+        v = v - np.outer(v @ u, u)
+    return idx
+
+
+def pcca_memberships(model, m):
+    """chi (n_active, m): the memberships of the active states in m metastable sets from the inner-simplex start of PCCA+, chi =
+    psi psi[vertices]^-1 on the m leading right eigenvectors psi (model.eigenvectors(m - 1): the GPU call of msm_spectrum;
+    reversible models).  Rows sum to 1; a vertex state has membership 1 in its own set.  The optimisation of the transformation
+    matrix that PCCA+ runs after this start is not done: entries may lie slightly outside [0, 1]."""
+    model._need_fit()
+    m = int(m)
+    n = len(model.active_set)
+    if not 1 <= m <= min(n, PROPAGATE_MAX_ROWS):
+        raise ValueError(f"pcca_memberships: m must be 1..min(n_active, {PROPAGATE_MAX_ROWS}) = {min(n, PROPAGATE_MAX_ROWS)}, not {m}")
+    if m == 1:
+        return np.ones((n, 1))
+    psi = np.asarray(model.eigenvectors(m - 1)).T
+    return psi @ np.linalg.inv(psi[inner_simplex(psi)])
+
+
+def metastable_sets(model, m):
+    """m metastable sets of a fitted reversible MarkovStateModel: every active state goes to the set of its largest
+    pcca_memberships entry (the lowest index wins a tie) -> a list of m int64 arrays of state indices on the FULL index, ordered
+    by their smallest state.  ValueError when a set stays empty."""
+    chi = pcca_memberships(model, m)
+    of = np.argmax(chi, axis=1)
+    sets = [np.asarray(model.active_set, np.int64)[of == c] for c in range(chi.shape[1])]
+    if any(s.size == 0 for s in sets):
+        raise ValueError(f"metastable_sets: only {sum(s.size > 0 for s in sets)} of {chi.shape[1]} sets have a state")
+    return sorted(sets, key=lambda s: int(s[0]))
+
+
+# ---- the Chapman-Kolmogorov test ----
+class ChapmanKolmogorov:
+    """What chapman_kolmogorov returns.  lagtimes (n_k,) = lagtime * multiples, in frames; predicted and estimated (n_k, m, m):
+    the probability of being in set b after k lag times when started from the stationary distribution restricted to set a, by
+    T(tau)^k and by one step of the model at lag k tau (NaN rows where a set has no active state); max_abs_diff and rms_diff
+    over the finite entries; models: {multiple: MarkovStateModel} (1: the base model); sets.  With n_resamples > 0 also
+    predicted_lo / _hi, estimated_lo / _hi (the percentile interval at `confidence` over the resamples), share_inside (the share
+    of finite entries whose point prediction lies inside the estimate's interval) and predicted_resamples /
+    estimated_resamples (B, n_k, m, m); else those are None."""
+
+    def __init__(self, lagtimes, multiples, sets, predicted, estimated, models):
+        self.lagtimes, self.multiples, self.sets, self.predicted, self.estimated, self.models = (lagtimes, multiples, sets, predicted,
+                                                                                                 estimated, models)
+        d = (predicted - estimated)[np.isfinite(predicted) & np.isfinite(estimated)]
+        self.max_abs_diff = float(np.abs(d).max()) if d.size else float("nan")
+        self.rms_diff = float(np.sqrt(np.mean(d * d))) if d.size else float("nan")
+        self.predicted_lo = self.predicted_hi = self.estimated_lo = self.estimated_hi = None
+        self.predicted_resamples = self.estimated_resamples = None
+        self.share_inside = float("nan")
+
+
+def _check_sets(sets, n_states, what):
+    """m <= 16 disjoint, non-empty lists of states of the full index -> a list of sorted int64 arrays"""
+    out = [np.unique(np.asarray(s, np.int64).reshape(-1)) for s in sets]
+    if not 1 <= len(out) <= PROPAGATE_MAX_ROWS:
+        raise ValueError(f"{what}: 1..{PROPAGATE_MAX_ROWS} sets, not {len(out)}")
+    for a, s in enumerate(out):
+        if s.size == 0:
+            raise ValueError(f"{what}: set {a} is empty")
+        if s[0] < 0 or s[-1] >= n_states:
+            raise ValueError(f"{what}: set {a} holds a state outside 0 .. {n_states - 1}")
+    allst = np.concatenate(out)
+    if np.unique(allst).size != allst.size:
+        raise ValueError(f"{what}: the sets overlap")
+    return out
+
+
+def _ck_rows(model, sets):
+    """(start rows (m, n_active): pi restricted to each set and divided by its sum, zero where the set has no active state;
+    indicators (m, n_active) of the sets; empty (m,) bool)"""
+    act, pi = np.asarray(model.active_set), model.stationary_distribution
+    ind = np.stack([np.isin(act, s).astype(np.float64) for s in sets])
+    w = ind * pi
+    tot = w.sum(axis=1)
+    empty = ind.sum(axis=1) == 0
+    w[~empty] /= tot[~empty][:, None]
+    return w, ind, empty
+
+
+def chapman_kolmogorov_of_models(groups, multiples, sets, *, device=None):
+    """The tables of the test for fitted models: groups is a list of (base model at lag tau, {k: model at lag k tau}) -- one
+    entry per data set or resample --, every one evaluated by the definitions of ChapmanKolmogorov in ONE propagator call: the
+    base model runs max(multiples) steps, each other model one -> (predicted, estimated), each (len(groups), n_k, m, m).  The
+    model of multiple 1 is the base model itself: both rows are then the same problem on the same matrix."""
+    multiples = [int(k) for k in multiples]
+    S, m = max(multiples), len(sets)
+    models, mat_of, starts, obs, where = [], [], [], [], []
+    for base, tests in groups:
+        for mdl in [base] + [tests[k] for k in multiples]:
+            at = next((i for i, x in enumerate(models) if x is mdl), None)
+            if at is None:
+                at = len(models)
+                models.append(mdl)
+            w, ind, empty = _ck_rows(mdl, sets)
+            mat_of.append(at)
+            starts.append(w)
+            obs.append(ind)
+            where.append(empty)
+    out = _propagate_on_models(models, mat_of, starts, obs, S, device, "chapman_kolmogorov")
+    n_k = len(multiples)
+    pred, est = np.full((len(groups), n_k, m, m), np.nan), np.full((len(groups), n_k, m, m), np.nan)
+    for g in range(len(groups)):
+        p0 = g * (n_k + 1)
+        for i, k in enumerate(multiples):
+            pred[g, i], est[g, i] = out[p0, k], out[p0 + 1 + i, 1]
+            pred[g, i][where[p0]] = np.nan
+            est[g, i][where[p0 + 1 + i]] = np.nan
+    return pred, est
+
+
+def chapman_kolmogorov(labels, lagtime, sets, multiples=(1, 2, 3, 4, 5), traj_lengths=None, n_states=None, *, reversible=True,
+                       n_resamples=0, block_frames=None, seed=0, confidence=0.95, tol=1e-12, max_iter=1_000_000,
+                       steps_per_sync=256, resample_batch=None, device="cuda:0"):
+    """The Chapman-Kolmogorov test of a MarkovStateModel at `lagtime` on the sets `sets` (m <= 16 disjoint, non-empty lists of
+    states on the full index): for every multiple k, predicted[k][a][b] = sum over set b of (pi restricted to set a, normalised)
+    T(tau)^k, and estimated[k][a][b] the same with ONE step of the model estimated at lag k tau, with that model's own pi and
+    active set -> ChapmanKolmogorov.  The count matrices of up to 8 lag times come from one pass over the labels; every
+    propagation of the test is in one dff_msm_propagate call.  n_resamples > 0 (reversible models): the bootstrap of
+    bootstrap_msm at every lag with the same seed, so that resample b draws the same units at every lag; all resamples of a
+    batch in one call; resample b equals chapman_kolmogorov_of_models on the models of fit_counts(counts_b) bit for bit."""
+    dev = torch.device(device)
+    lab = torch.as_tensor(labels).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    lengths = _check_lengths(traj_lengths, int(lab.numel()))
+    if n_states is None:
+        n_states = int(lab.max()) + 1 if lab.numel() else 0
+    if not 1 <= int(n_states) <= MSM_MAX_STATES:
+        raise ValueError(f"chapman_kolmogorov: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+    sets = _check_sets(sets, int(n_states), "chapman_kolmogorov")
+    mult = [int(k) for k in multiples]
+    if not mult or any(k != kk or k < 1 or k > PROPAGATE_MAX_STEPS for k, kk in zip(mult, multiples)) or len(set(mult)) != len(mult):
+        raise ValueError("chapman_kolmogorov: multiples must be distinct integers >= 1")
+    n_resamples = int(n_resamples)
+    if n_resamples < 0:
+        raise ValueError("chapman_kolmogorov: n_resamples must be >= 0")
+    if n_resamples and not reversible:
+        raise ValueError("chapman_kolmogorov: the bootstrap needs reversible models")
+    proto = MarkovStateModel(lagtime, reversible, tol, max_iter, steps_per_sync, device=dev)          # checks the settings
+    ks_all = sorted(set(mult) | {1})
+    models = {}
+    for l0 in range(0, len(ks_all), binding.MSM_MAX_LAGS):
+        group = ks_all[l0:l0 + binding.MSM_MAX_LAGS]
+        counts = binding.micro_transition_counts(lab, lengths, [proto.lagtime * k for k in group], int(n_states)).cpu().numpy()
+        for i, k in enumerate(group):
+            models[k] = MarkovStateModel(proto.lagtime * k, reversible, tol, max_iter, steps_per_sync, device=dev).fit_counts(counts[i])
+    pred, est = chapman_kolmogorov_of_models([(models[1], models)], mult, sets, device=dev)
+    ck = ChapmanKolmogorov(np.array([proto.lagtime * k for k in mult], np.int64), mult, sets, pred[0], est[0], models)
+    if n_resamples:
+        plans = {k: _BootstrapPlan("chapman_kolmogorov", lab, proto.lagtime * k, lengths, n_states, n_resamples, block_frames, seed,
+                                   None, tol, max_iter, steps_per_sync, resample_batch, dev) for k in ks_all}
+        B = plans[1].B
+        shape = (B,) + pred[0].shape
+        pr, es = np.full(shape, np.nan), np.full(shape, np.nan)
+        for batch in zip(*(plans[k].batches() for k in ks_all)):
+            b0, n = batch[0][0], len(batch[0][1])
+            groups = [(batch[0][1][i], {k: batch[j][1][i] for j, k in enumerate(ks_all)}) for i in range(n)]
+            pr[b0:b0 + n], es[b0:b0 + n] = chapman_kolmogorov_of_models(groups, mult, sets, device=dev)
+        ck.predicted_resamples, ck.estimated_resamples = pr, es
+        flat = lambda v: v.reshape(B, -1)     # noqa: E731
+        ck.predicted_lo, ck.predicted_hi = (v.reshape(pred[0].shape) for v in percentile_interval(flat(pr), confidence))
+        ck.estimated_lo, ck.estimated_hi = (v.reshape(pred[0].shape) for v in percentile_interval(flat(es), confidence))
+        ck.share_inside = share_inside(ck.predicted, ck.estimated_lo, ck.estimated_hi)
+    return ck
+
+
+def share_inside(point, lo, hi):
+    """the share of the entries where point, lo and hi are all finite with lo <= point <= hi (NaN when there is none)"""
+    ok = np.isfinite(point) & np.isfinite(lo) & np.isfinite(hi)
+    return float(np.mean((point[ok] >= lo[ok]) & (point[ok] <= hi[ok]))) if ok.any() else float("nan")
+
+
+def state_means(labels, values, n_states):
+    """The mean of `values` (n,) over the frames of every state of `labels` (n,; < 0: left out) -> float64 (n_states,), 0 for a
+    state without frames; taken with torch on the device the values live on (non-finite values are left out)."""
+    v = torch.as_tensor(values).reshape(-1).to(torch.float64)
+    lab = torch.as_tensor(labels).reshape(-1).to(device=v.device, dtype=torch.int64)
+    ok = (lab >= 0) & (lab < n_states) & torch.isfinite(v)
+    sums = torch.zeros(n_states, dtype=torch.float64, device=v.device).index_add_(0, lab[ok], v[ok])
+    cnt = torch.zeros(n_states, dtype=torch.float64, device=v.device).index_add_(0, lab[ok], torch.ones_like(v[ok]))
+    return (sums / cnt.clamp(min=1)).cpu().numpy()
+
+
+class ChapmanKolmogorovEvaluator(_TrajectoryEvaluator):
+    """Is the Markov state model of the sampled dynamics VALID at its lag time?  Frames -> TIC projection and k-means
+    microstates (`tica`, n_microstates, centers, seed: as for MsmEvaluator) -> a reversible MarkovStateModel at `lagtime` -> n_sets
+    metastable sets (metastable_sets of the first ensemble analysed: the reference when there is ref_data; kept and reused for
+    the samples) -> chapman_kolmogorov at `multiples`, and the model's autocorrelation of the first TIC (msm_autocorrelation of
+    its state means) against the one measured on the trajectories (autocorrelation).
+
+    eval(xyz, traj_lengths=None) -- None: ONE trajectory -- returns a dict:
+      ck_max_abs_diff, ck_rms_diff                    predicted against estimated over all multiples and pairs of sets
+      ck_diagonal_predicted, ck_diagonal_estimated    lists over the multiples of lists over the sets: the staying probabilities
+      acf_rms_diff                                    model against measured ACF of the first TIC at the lags s lagtime, s = 0 .. max(multiples)
+      n_sets, samples_nonfinite
+    and with n_bootstrap > 0 ck_share_inside (the share of point predictions inside the estimates' percentile interval).  With
+    ref_data the same keys with the suffix _ref and ck_max_abs_diff_minus_ref.  The results stay on .results, the models on
+    .models, under "samples" / "refs".  Without the HIP library: DffLibraryError."""
+
+    KEYS = ("ck_max_abs_diff", "ck_rms_diff", "ck_diagonal_predicted", "ck_diagonal_estimated", "acf_rms_diff", "n_sets",
+            "samples_nonfinite")
+
+    def __init__(self, mol_name, tica, n_microstates=200, lagtime=None, n_sets=3, multiples=(1, 2, 3, 4, 5), frame_time=1.0,
+                 ref_data=None, ref_traj_lengths=None, centers=None, seed=0, *, n_bootstrap=0, block_frames=None, confidence=0.95,
+                 bootstrap_seed=0, device="cuda:0"):
+        what = "ChapmanKolmogorovEvaluator"
+        super().__init__(what, mol_name, frame_time, device)
+        self._point = _PointModel(what, lagtime, n_bootstrap, block_frames, confidence, bootstrap_seed, self.device)
+        self.lagtime = self._point.lagtime
+        self.n_sets = int(n_sets)
+        if not 1 <= self.n_sets <= PROPAGATE_MAX_ROWS:
+            raise ValueError(f"{what}: n_sets must be 1..{PROPAGATE_MAX_ROWS}")
+        self.multiples = [int(k) for k in multiples]
+        if not self.multiples or any(k < 1 for k in self.multiples) or len(set(self.multiples)) != len(self.multiples):
+            raise ValueError(f"{what}: multiples must be distinct integers >= 1")
+        self.mean, self.coeff = _tica_model(tica, what, TICA_MAX_DIM)
+        self._micro = _Microstates(what, n_microstates, self.coeff.shape[1], centers, seed, self.device)
+        self.n_microstates = self._micro.n_microstates
+        self.sets = None
+        self.models, self.labels, self.results = {}, {}, {}
+        self._start(ref_data, ref_traj_lengths)
+
+    centers = property(lambda self: self._micro.centers, doc="the microstate centres (K, k); None until they are fitted")
+
+    def project(self, x):
+        return binding.struct_tic(x, self.mean, self.coeff)
+
+    @staticmethod
+    def summarize(ck, acf_model, acf_measured, samples_nonfinite=0):
+        """eval()'s dict from a ChapmanKolmogorov and the two ACFs at the same lags: numpy only."""
+        d = np.asarray(acf_model, np.float64) - np.asarray(acf_measured, np.float64)
+        d = d[np.isfinite(d)]
+        res = {"ck_max_abs_diff": ck.max_abs_diff, "ck_rms_diff": ck.rms_diff,
+               "ck_diagonal_predicted": [[float(v) for v in np.diag(t)] for t in ck.predicted],
+               "ck_diagonal_estimated": [[float(v) for v in np.diag(t)] for t in ck.estimated],
+               "acf_rms_diff": float(np.sqrt(np.mean(d * d))) if d.size else float("nan"),
+               "n_sets": float(len(ck.sets)), "samples_nonfinite": float(samples_nonfinite)}
+        if ck.estimated_lo is not None:
+            res["ck_share_inside"] = ck.share_inside
+        return res
+
+    def _analyse(self, x, lengths, name):
+        proj = self.project(x)
+        labels = self._micro.labels(proj)
+        if self.sets is None:
+            first, _ = self._point.fit(labels, lengths, self.n_microstates, name)
+            self.sets = metastable_sets(first, self.n_sets)
+        seed = self._point.bootstrap_seed + (name == "refs")
+        ck = chapman_kolmogorov(labels, self.lagtime, self.sets, self.multiples, lengths, self.n_microstates,
+                                n_resamples=self._point.n_bootstrap, block_frames=self._point.block_frames, seed=seed,
+                                confidence=self._point.confidence, device=self.device)
+        model, S = ck.models[1], max(self.multiples)
+        tic1 = proj[:, 0]
+        predicted = msm_autocorrelation(model, state_means(labels, tic1, self.n_microstates), S, device=self.device).acf
+        measured = autocorrelation(tic1, S * self.lagtime, lengths, device=self.device).acf[::self.lagtime, 0]
+        self.models[name], self.labels[name], self.results[name] = model, labels.cpu().numpy(), ck
+        return self.summarize(ck, predicted, measured, int((labels < 0).sum()))
+
+    def _compare(self, res, ref):
+        res["ck_max_abs_diff_minus_ref"] = res["ck_max_abs_diff"] - ref["ck_max_abs_diff"]
