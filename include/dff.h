@@ -284,15 +284,39 @@ int dff_debug_profile_read(dff_model* m, unsigned long long* out_host);
  * the counts equal the reference's.  The (n_pairs x bins) JS reduction stays on the host
  * (two-for-one-diffusion_amd/evaluate.py). */
 int dff_pwd_num_pairs(int n_beads, int offset);
+/* Non-finite input (both calls): a distance is NaN when a coordinate of either bead is NaN or both beads have the same
+ * infinite coordinate, and +Inf when one coordinate is infinite or a squared difference overflows fp32 (finite
+ * |x| >~ 1.8e19).  dff_pwd_max skips NaN distances -- the maximum is over the others, 0 if there is none -- and a +Inf
+ * distance makes the pair's maximum +Inf.  dff_pwd_hist drops NaN and +Inf distances and counts the rest, so the pairs
+ * of one call may have different totals.  Leaving such frames out whole is the caller's business (PwdEvaluator does). */
 /* max_out_dev[p] = max over the n structures of d_p (0 when n == 0).  x_dev: (n, n_beads, 3) fp32. */
 int dff_pwd_max(int device, const float* x_dev, long long n, int n_beads, int offset,
                 float* max_out_dev, void* stream);
 /* hist_dev[p * ld + b], b < nbins_dev[p]: number of structures whose d_p falls into bin b of
  * torch.histc(d_p, bins=nbins[p], min=0, max=hmax_dev[p]); the call zeroes hist_dev (n_pairs * ld)
- * first.  max_bins >= every nbins[p]; ld >= max_bins. */
+ * first.  max_bins >= every nbins[p]; ld >= max_bins.
+ * 1 <= max_bins <= 30719 (3071.9 Angstrom at the metric's 0.1 Angstrom bins): a pair's histogram row of max_bins | 1
+ * slots must fit the 30720 slots a workgroup keeps in LDS; more is DFF_EINVAL.
+ * The device arrays are not read on the host, so their contents are the caller's responsibility: every nbins_dev[p]
+ * must lie in 1..max_bins (anything else is an error of the caller that the call cannot see: the kernel would write
+ * outside the pair's LDS row) and every hmax_dev[p] must be finite and > 0. */
 int dff_pwd_hist(int device, const float* x_dev, long long n, int n_beads, int offset,
                  const int32_t* nbins_dev, const float* hmax_dev, int max_bins, int ld,
                  uint32_t* hist_dev, void* stream);
+/* The launch layout dff_pwd_hist takes for these arguments. */
+typedef struct {
+    int32_t n_pairs;
+    int32_t tile_n;                        /* structures per LDS tile: 64 or 32 */
+    int32_t pc_log2, npc;                  /* 1 << pc_log2 pair lanes per workgroup (0..8), npc pair chunks of that many */
+    int32_t ldl;                           /* LDS row stride of a pair's histogram: max_bins | 1 */
+    int32_t lds_bytes;                     /* dynamic LDS: tile + (1 << pc_log2) * ldl counters + 16 */
+    long long chunk;                       /* structures per structure chunk, a multiple of 64 */
+    long long chunks, chunks_rounded;      /* structure chunks that hold structures; rounded up to whole rounds of 8 */
+    long long grid;                        /* workgroups: chunks_rounded * npc */
+} dff_pwd_plan;
+/* Host only, for tests, no GPU needed: the function dff_pwd_hist itself plans its launch with.  DFF_EINVAL where
+ * dff_pwd_hist refuses the shape (n_beads, offset, max_bins). */
+int dff_pwd_hist_plan(int n_beads, int offset, int max_bins, long long n, dff_pwd_plan* out);
 
 /* ---- per-frame structure metrics of the reference's evaluators (csrc/dff_struct.hip) ----
  * Stateless, like dff_pwd_*: x_dev is (n, n_beads, 3) fp32 in Angstrom on the device, 4 <= n_beads <= 64, frames

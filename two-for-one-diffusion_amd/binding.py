@@ -55,6 +55,12 @@ class DffLaunchPlan(C.Structure):
                                                                      "threads", "pair", "table")] + [("table_kernel", C.c_char_p)]
 
 
+class DffPwdPlan(C.Structure):
+    """dff_pwd_plan: the launch layout of dff_pwd_hist (pwd_hist_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_pairs", "tile_n", "pc_log2", "npc", "ldl", "lds_bytes")] + \
+               [(n, C.c_longlong) for n in ("chunk", "chunks", "chunks_rounded", "grid")]
+
+
 # every symbol include/dff.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -87,6 +93,7 @@ SYMBOLS = {
     "dff_pwd_num_pairs": (C.c_int, [C.c_int, C.c_int]),
     "dff_pwd_max": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P]),
     "dff_pwd_hist": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "dff_pwd_hist_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(DffPwdPlan)]),
     "dff_struct_rmsd": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P, _P]),
     "dff_struct_dihedrals": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, _P]),
     "dff_struct_tic_num_features": (C.c_int, [C.c_int]),
@@ -513,12 +520,26 @@ def pwd_hist(x, offset: int, nbins, hmax):
         raise ValueError(f"nbins / hmax must have {npairs} entries")
     if int(nb.min()) < 1:
         raise ValueError("nbins must be >= 1")
+    if not bool((torch.isfinite(hm) & (hm > 0)).all()):
+        raise ValueError("hmax must be finite and > 0")
     max_bins = int(nb.max())
     nb_d, hm_d = nb.to(x.device), hm.to(x.device)
     out = torch.empty((npairs, max_bins), dtype=torch.int32, device=x.device)
     _check(lib, lib.dff_pwd_hist(x.device.index, _ptr(x), n, N, int(offset), _ptr(nb_d), _ptr(hm_d), max_bins,
                                  max_bins, _ptr(out), _stream(x)), "dff_pwd_hist")
     return out
+
+
+PWD_MAX_BINS = 30719        # the largest max_bins dff_pwd_hist accepts (include/dff.h)
+
+
+def pwd_hist_plan(n_beads: int, offset: int, max_bins: int, n: int) -> dict:
+    """The launch layout dff_pwd_hist takes for n structures of n_beads beads and histograms of up to max_bins bins
+    (the fields of dff_pwd_plan): dff_pwd_hist_plan, host only, no GPU.  ValueError where dff_pwd_hist refuses."""
+    lib = load_library()
+    plan = DffPwdPlan()
+    _check(lib, lib.dff_pwd_hist_plan(int(n_beads), int(offset), int(max_bins), int(n), C.byref(plan)), "dff_pwd_hist_plan")
+    return {f: int(getattr(plan, f)) for f, _ in DffPwdPlan._fields_}
 
 
 # ---- structure metrics (dff_struct_*): stateless entry points, no model handle ----

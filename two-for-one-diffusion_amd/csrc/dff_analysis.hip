@@ -91,6 +91,50 @@ extern "C" int dff_pwd_max(int device, const float* x, long long n, int N, int o
     return DFF_OK;
 }
 
+// The launch layout of dff_pwd_hist_kernel for n structures of N beads and histograms of up to max_bins bins: pure host
+// arithmetic, the one statement of it (dff_pwd_hist launches what it says, dff_pwd_hist_plan shows it to the tests).
+// LDS holds one tile of structures + the privatised histograms.  The tile shrinks from 64 to 32 structures when that lets
+// twice as many pairs keep their histograms in LDS (fewer passes over the structures); a smaller tile never helps, since
+// DFF_PWD_LDS_BINS caps the slots at 32 structures already for every N <= DFF_MAX_BEADS.
+static int pwd_hist_layout(int N, int offset, int max_bins, long long n, dff_pwd_plan* out) {
+    if (N < 2 || N > DFF_MAX_BEADS) return fail(DFF_EINVAL, "pwd: n_beads must be 2..%d", DFF_MAX_BEADS);
+    const int npairs = dff_pwd_num_pairs(N, offset);
+    if (npairs <= 0) return fail(DFF_EINVAL, "pwd: no bead pairs at offset %d", offset);
+    if (max_bins < 1) return fail(DFF_EINVAL, "pwd: need 1 <= max_bins <= ld");
+    if (n < 0) return fail(DFF_EINVAL, "pwd: null input / negative count");
+    const int ldl = max_bins | 1;   // odd leading dimension: pairs land in different LDS banks
+    int tile_n = DFF_PWD_TILE, pc_log2 = -1, tile_bytes = 0;
+    for (int tn = DFF_PWD_TILE; tn >= DFF_PWD_TILE / 2; tn >>= 1) {
+        const int tb = tn * 3 * N * (int)sizeof(float);
+        int slots = (160 * 1024 - 64 - tb) / (int)sizeof(unsigned);
+        if (slots > DFF_PWD_LDS_BINS) slots = DFF_PWD_LDS_BINS;
+        if (ldl > slots) continue;
+        int lg = 8;                 // pair lanes per workgroup: the largest power of two whose histograms fit
+        while (lg > 0 && ((1 << lg) * ldl > slots || (1 << (lg - 1)) >= npairs)) --lg;
+        if (lg > pc_log2) { pc_log2 = lg; tile_n = tn; tile_bytes = tb; }
+    }
+    if (pc_log2 < 0) return fail(DFF_EINVAL, "pwd: %d bins per pair do not fit in LDS (at most %d)", max_bins, DFF_PWD_LDS_BINS - 1);
+    const int PC = 1 << pc_log2;
+    const int npc = (npairs + PC - 1) / PC;
+    // each workgroup flushes up to PC * ldl bins: give it at least ~2x that many (pair, structure) items
+    const long long min_chunk = (2LL * ldl + DFF_PWD_TILE - 1) / DFF_PWD_TILE * DFF_PWD_TILE;   // multiple of both tile sizes
+    const long long chunk = pwd_chunk(n, (2048 + npc - 1) / npc, min_chunk);
+    const long long nsc = (n + chunk - 1) / chunk;
+    const long long nsc8 = (nsc + 7) / 8 * 8;       // whole XCD rounds (empty chunks return at once)
+    const long long grid = nsc8 * npc;
+    if (grid > 0x7fffffffLL) return fail(DFF_EINVAL, "pwd: grid too large");
+    const unsigned lds = (unsigned)(tile_bytes + (size_t)PC * ldl * sizeof(unsigned) + 16);
+    if (lds > 160 * 1024) return fail(DFF_EINVAL, "pwd: LDS budget exceeded (%u bytes)", lds);
+    out->n_pairs = npairs; out->tile_n = tile_n; out->pc_log2 = pc_log2; out->npc = npc; out->ldl = ldl;
+    out->lds_bytes = (int32_t)lds; out->chunk = chunk; out->chunks = nsc; out->chunks_rounded = nsc8; out->grid = grid;
+    return DFF_OK;
+}
+
+extern "C" int dff_pwd_hist_plan(int n_beads, int offset, int max_bins, long long n, dff_pwd_plan* out) {
+    if (!out) return fail(DFF_EINVAL, "pwd: null argument");
+    return pwd_hist_layout(n_beads, offset, max_bins, n, out);
+}
+
 extern "C" int dff_pwd_hist(int device, const float* x, long long n, int N, int offset, const int32_t* nbins,
                             const float* hmax, int max_bins, int ld, uint32_t* hist, void* stream_) {
     int npairs;
@@ -102,35 +146,12 @@ extern "C" int dff_pwd_hist(int device, const float* x, long long n, int N, int 
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipMemsetAsync(hist, 0, (size_t)npairs * ld * sizeof(uint32_t), stream));
     if (n == 0) return DFF_OK;
-    // LDS: one tile of structures + the privatised histograms.  The tile shrinks (64 -> 32 -> 16 structures) when
-    // that lets twice as many pairs keep their histograms in LDS (fewer passes over the structures).
-    const int ldl = max_bins | 1;   // odd leading dimension: pairs land in different LDS banks
-    int tile_n = DFF_PWD_TILE, pc_log2 = -1, tile_bytes = 0;
-    for (int tn = DFF_PWD_TILE; tn >= 16; tn >>= 1) {
-        const int tb = tn * 3 * N * (int)sizeof(float);
-        int slots = (160 * 1024 - 64 - tb) / (int)sizeof(unsigned);
-        if (slots > DFF_PWD_LDS_BINS) slots = DFF_PWD_LDS_BINS;
-        if (ldl > slots) continue;
-        int lg = 8;                 // pair lanes per workgroup: the largest power of two whose histograms fit
-        while (lg > 0 && ((1 << lg) * ldl > slots || (1 << (lg - 1)) >= npairs)) --lg;
-        if (lg > pc_log2) { pc_log2 = lg; tile_n = tn; tile_bytes = tb; }
-    }
-    if (pc_log2 < 0) return fail(DFF_EINVAL, "pwd: %d bins per pair do not fit in LDS", max_bins);
-    const int PC = 1 << pc_log2;
-    const int npc = (npairs + PC - 1) / PC;
-    // each workgroup flushes up to PC * ldl bins: give it at least ~2x that many (pair, structure) items
-    const long long min_chunk = (2LL * ldl + DFF_PWD_TILE - 1) / DFF_PWD_TILE * DFF_PWD_TILE;   // multiple of every tile size
-    const long long chunk = pwd_chunk(n, (2048 + npc - 1) / npc, min_chunk);
-    long long nsc = (n + chunk - 1) / chunk;
-    nsc = (nsc + 7) / 8 * 8;       // whole XCD rounds (empty chunks return at once)
-    const long long grid = nsc * npc;
-    if (grid > 0x7fffffffLL) return fail(DFF_EINVAL, "pwd: grid too large");
-    const unsigned lds = (unsigned)(tile_bytes + (size_t)PC * ldl * sizeof(unsigned) + 16);
-    if (lds > 160 * 1024) return fail(DFF_EINVAL, "pwd: LDS budget exceeded (%u bytes)", lds);
-    HIPCHK(hipFuncSetAttribute((const void*)&dff_pwd_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    dff_pwd_plan pl;
+    if ((rc = pwd_hist_layout(N, offset, max_bins, n, &pl))) return rc;
+    HIPCHK(hipFuncSetAttribute((const void*)&dff_pwd_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes));
     const int vec4 = ((uintptr_t)x % 16) == 0;
-    hipLaunchKernelGGL(dff_pwd_hist_kernel, dim3((unsigned)grid), dim3(DFF_PWD_HIST_THREADS), lds, stream, x, n, N, offset,
-                       npairs, nbins, hmax, ld, pc_log2, npc, chunk, ldl, hist, vec4, tile_n);
+    hipLaunchKernelGGL(dff_pwd_hist_kernel, dim3((unsigned)pl.grid), dim3(DFF_PWD_HIST_THREADS), (unsigned)pl.lds_bytes, stream,
+                       x, n, N, offset, npairs, nbins, hmax, ld, pl.pc_log2, pl.npc, pl.chunk, pl.ldl, hist, vec4, pl.tile_n);
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(DFF_PWD_HIST_THREADS) void dff_pwd_hist_kernel(cons
     const int p0 = pchunk << pc_log2;
     const int pc = npairs - p0 < PC ? npairs - p0 : PC;
     float* tile = smem;
-    unsigned* hl = (unsigned*)(smem + tile_n * N3);          // PC * ldl  (tile_n structures per LDS tile: 64, 32 or 16)
+    unsigned* hl = (unsigned*)(smem + tile_n * N3);          // PC * ldl  (tile_n structures per LDS tile: 64 or 32)
     for (int k = threadIdx.x; k < pc * ldl; k += DFF_PWD_HIST_THREADS) hl[k] = 0u;
     const bool live = lane_p < pc;
     int i = 0, j = 0, b = 1;
@@ -164,7 +164,9 @@ __global__ __launch_bounds__(DFF_PWD_HIST_THREADS) void dff_pwd_hist_kernel(cons
 #pragma unroll 4
             for (int s = sgrp; s < cnt; s += sstride) {
                 const float d = pwd_dist2(tile + s * N3, oi, oj);
-                if (d <= m) {   // NaN fails the test, d >= 0 always: histc's range check
+                if (d <= m) {   // NaN fails the test (+Inf too: m is finite), d >= 0 always: histc's range check
+                    // the order (d * bf) / m and the correctly rounded divide ARE the contract: d * (bf / m) moves values
+                    // that sit on a bin edge into the neighbouring bin (tests/test_pwd_edges.py)
                     int pos = (int)(long long)((d * bf) / m);
                     pos = pos < b ? pos : b - 1;
                     atomicAdd(&row[pos], 1u);

@@ -57,6 +57,10 @@ class PwdEvaluator:
 
     val_data / all_mol are (n, N, 3) coordinate tensors in Angstrom (CPU or GPU).  `device` (extra,
     keyword-only) selects the GPU the histograms are computed on.
+
+    Beyond the reference: frames with a non-finite coordinate are left out whole, like every evaluator here does, and
+    counted in refs_nonfinite (0 when the reference histograms come from a pickle) and samples_nonfinite (of the last
+    eval); no finite frame at all, or a distance the histogram kernel cannot bin, is a ValueError.
     """
 
     def __init__(self, val_data, plots_folder="", mol_name="", offset=0, saved_ref="none", evalset="testset",
@@ -66,6 +70,7 @@ class PwdEvaluator:
         self.mol_name = mol_name.lower()
         self.resolution = 0.1
         self.device = torch.device(device)
+        self.samples_nonfinite = 0
         binding.load_library()      # fail loudly now rather than at the first eval()
         if saved_ref == "none":
             saved_ref = f"./saved_references/saved_pwd_{mol_name.upper()}_{evalset}_offset_{self.offset}.pickle"
@@ -74,15 +79,41 @@ class PwdEvaluator:
                 data = pickle.load(f)
             self.gt_max = data["gt_max"]
             self.gt_hist = data["gt_hist"]
+            self.refs_nonfinite = 0
         else:
-            x = _to_device(val_data, self.device)
+            x, self.refs_nonfinite = self._finite_frames(val_data, "the reference structures")
             self.gt_max = binding.pwd_max(x, self.offset).cpu()
-            nb = nbins_for(self.gt_max, self.resolution)
+            nb = self._nbins(self.gt_max, self.resolution, x.shape[1])
             self.gt_hist = self._histograms(x, nb)
             d = os.path.dirname(saved_ref)
             if d == "" or os.path.isdir(d):
                 with open(saved_ref, "wb") as f:
                     pickle.dump({"gt_max": self.gt_max, "gt_hist": self.gt_hist}, f)
+
+    def _finite_frames(self, frames, what):
+        """The frames without a non-finite coordinate, on the device, and how many were left out: a NaN in one bead would
+        otherwise vanish from that bead's pairs only, and the pairs' histograms would have different totals."""
+        x = _to_device(frames, self.device)
+        ok = torch.isfinite(x).all(dim=2).all(dim=1)
+        bad = int((~ok).sum())
+        if bad:
+            x = x[ok].contiguous()
+        if len(x) == 0:
+            raise ValueError(f"PwdEvaluator: no finite frame among {what} ({bad} with a non-finite coordinate)")
+        return x, bad
+
+    def _nbins(self, maxval, resolution, n_beads):
+        """nbins_for, after refusing what the histogram kernel cannot bin: a distance of finite frames that is not finite
+        (a squared difference overflows float32) or that needs more than binding.PWD_MAX_BINS bins."""
+        maxval = torch.as_tensor(maxval).float().cpu()
+        over = ~torch.isfinite(maxval) | (torch.div(maxval, resolution, rounding_mode="floor") + 1 > binding.PWD_MAX_BINS)
+        if bool(over.any()):
+            p = int(over.nonzero()[0])
+            i, j = (int(t[p]) for t in torch.triu_indices(n_beads, n_beads, offset=self.offset))
+            raise ValueError(f"PwdEvaluator: the distance between beads {i} and {j} (pair {p}) reaches {float(maxval[p]):g} "
+                             f"Angstrom; histograms of {resolution:g} Angstrom bins hold at most "
+                             f"{binding.PWD_MAX_BINS * resolution:.1f} Angstrom ({binding.PWD_MAX_BINS} bins)")
+        return nbins_for(maxval, resolution)
 
     def _histograms(self, x, nbins):
         """list over pairs of float32 CPU tensors, what torch.histc(pwd[:, p], bins, 0, resolution*bins) returns"""
@@ -93,10 +124,10 @@ class PwdEvaluator:
     def js_divergence_pwd(self, hist_gt, all_mol, gt_max, resolution):
         """Mean over pairs of JS(gt histogram, histogram of the sampled structures) (evaluators.py:251-270).
         Takes the structures (n, N, 3) where the reference takes their (n, n_pairs) distance matrix."""
-        x = _to_device(all_mol, self.device)
+        x, self.samples_nonfinite = self._finite_frames(all_mol, "the samples")
         smax = binding.pwd_max(x, self.offset).cpu()
         maxval = torch.maximum(torch.as_tensor(gt_max).float().cpu(), smax)
-        nb = (torch.div(maxval, resolution, rounding_mode="floor") + 1).to(torch.int64)
+        nb = self._nbins(maxval, resolution, x.shape[1])
         hmax = torch.tensor([resolution * int(b) for b in nb], dtype=torch.float64).float()
         counts = binding.pwd_hist(x, self.offset, nb.to(torch.int32), hmax).cpu()
         result_js = np.empty(len(hist_gt))
