@@ -816,6 +816,58 @@ int dff_msm_propagate(int device, const double* t_dev, int n_mat, const int32_t*
  * above the limit is then refused), 2 = every problem with its matrix streamed from global memory. */
 int dff_debug_msm_propagate_path(int path);
 
+/* ---- Hidden Markov models: one E-step of Baum-Welch over all chains of a set of labelled trajectories, by a chunked
+ * forward-backward (csrc/dff_hmm.hip; evaluate.py: hmm_estep_solver, HiddenMarkovModel, HmmEvaluator) ----
+ * The model: m hidden states, 1 <= m <= DFF_HMM_MAXM, K observed symbols, 1 <= K <= DFF_MSM_MAXK; fp64 on the device: trans_dev
+ * (m, m) = A, emit_dev (m, K) = B, init_dev (m) = p0.  Their rows need not be normalised, and the call does not normalise them.
+ * The observations are the int32 labels of every MSM call (labels_dev (n), trajectories of lengths_host back to back).  At lag
+ * tau, trajectory r with offset f = 0 .. tau - 1 is one CHAIN: the frames f, f + tau, f + 2 tau, ... of r.  Chains are ordered
+ * r-major, f-minor (chain r tau + f); a chain without a frame contributes nothing (its chain_loglik is 0); every frame belongs to
+ * exactly one chain.  A NEGATIVE label is a missing observation: its emission factor is 1 for every hidden state, and it adds
+ * nothing to the emission counts.
+ * With M_t = A diag(B[:, o_t]): alpha_t ~ alpha_{t-1} M_t (alpha_0 = p0 B[:, o_0]), beta_{t-1} ~ M_t beta_t.  A chain is cut into chunks of
+ * dff_hmm_chunk() of its own frames.  (1) Per chunk P = prod M_t over its frames (the chain's first frame left out), row by row;
+ * after every step a row is rescaled by the power of two of its own sum -- exactly -- and the exponents are added up.  (2) Per
+ * chain, serially over its chunks: the alpha entering and the beta leaving every chunk (alpha <- alpha P, beta <- P beta, rescaled by powers
+ * of two), and the chain's log-likelihood ln(sum alpha_last) + ln 2 * (the exponents).  (3) Per chunk the forward recursion again
+ * from the true alpha and the backward one from the true beta; per frame the posterior gamma_t = alpha_t beta_t, normalised by its own sum,
+ * and the pair posterior xi_t(i, j) ~ alpha_{t-1}(i) A_ij B_j(o_t) beta_t(j), normalised by its own sum and added up per chunk in the
+ * backward pass's order.  (4) stats_dev, packed: loglik (1) | xi (m, m) | gamma0 (m) | gamma_sym (m, K) --
+ *   loglik      the chains' log-likelihoods, added in chain order
+ *   xi          the chunks' sums of xi_t, added in chunk order
+ *   gamma0      gamma of the chains' first frames, added in chain order
+ *   gamma_sym   Gamma[i, s] = sum of gamma_t(i) over the frames with o_t = s: groups of 1024 frames, every accumulator owned by one thread
+ *               and added in frame order, the groups added in order.
+ * chain_loglik_dev (n_traj lag), or NULL; post_dev (n, m): the posteriors in frame order, or NULL (then they live in the
+ * workspace).  status_dev: ONE int32 --
+ *   0   success
+ *   1   a parameter entry is non-finite or negative
+ *   3   a label >= K
+ *   2   some chain has likelihood zero under the model (its forward vector vanished, or overflowed)
+ * in that order of precedence; on any non-zero status every output is NaN.  Status 0 never comes with a NaN.
+ * What the bits depend on: a chain's chain_loglik and its frames' posteriors follow from that chain's labels, the parameters and
+ * the chunk length alone -- not from the other chains, the chain's place among them, the lag or trajectory it was cut from, or the
+ * workspace; stats is in addition a function of the order of the chains and of the frames.  Everything is identical from call
+ * to call, and stats is the same with post_dev given or NULL.
+ * lag >= 1, n_traj lag <= 2^20 chains, n <= 2^31; device pointers, `stream` only, no read-back, refusals on the host before any
+ * device call, no floating-point atomics, no workgroup waits on another.  workspace_dev 8-byte aligned, contents irrelevant. */
+#define DFF_HMM_MAXM 8
+/* The chunk length (a compile-time constant). */
+int dff_hmm_chunk(void);
+/* Host only: the chains (n_traj lag, empty ones included) and chunks of a call; either output may be NULL. */
+int dff_hmm_plan(const long long* lengths_host, int n_traj, int lag, long long* n_chains, long long* n_chunks);
+/* Bytes of device workspace the call below needs (the trajectory table, the parameters, per chunk the product and the two
+ * carries, per chain a log-likelihood, the (n, m) posteriors and per 1024 frames K m emission counts); -1 on bad arguments. */
+long long dff_hmm_workspace_bytes(long long n, const long long* lengths_host, int n_traj, int lag, int m, int K);
+int dff_hmm_estep(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj, int lag,
+                  const double* trans_dev, const double* emit_dev, const double* init_dev, int m, int K, double* stats_dev,
+                  double* chain_loglik_dev, double* post_dev, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                  void* stream);
+/* For benchmarks, process-wide: 0 = the whole call (the default); 1 .. 5 = the call stops after its parameter launch, the chunk
+ * products, the carries, the apply pass, the emission counts -- the share of every launch, by differences.  The outputs of a
+ * call that stopped early are unfinished. */
+int dff_debug_hmm_stages(int stages);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -17,6 +17,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
                                  [--ck [HELDOUT.pt] --ck-states K --ck-lag L [--ck-sets M] [--ck-multiples 1,2,3,4,5]
                                   [--ck-bootstrap B]]
+                                 [--hmm [HELDOUT.pt] --hmm-states K --hmm-hidden M --hmm-lag L [--frame-time T]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]
                                   [--msm-eigensolver host|device] [--msm-eigenvectors N]]
@@ -79,6 +80,12 @@ samples' model on the full microstate index ("right"), their eigenvalues and the
 --ck-multiples (1,2,3,4,5) the set-to-set probabilities that T(L)^k predicts against those of the model estimated at lag k L,
 with the model's autocorrelation of the first TIC against the measured one; --ck-bootstrap B adds percentile intervals.  With
 HELDOUT.pt also for that MD data, which then defines the sets.  Needs --parallel-sim.
+
+--hmm adds a hidden Markov model of the microstate trajectory (HmmEvaluator) under "hmm": --hmm-states K microstates as for
+--msm, --hmm-hidden M hidden states (1..8), --hmm-lag L frames; the implied timescales of the hidden transition matrix, the
+hidden states' populations and lifetimes in units of --frame-time, the E-steps spent and the log-likelihood per frame.  With
+HELDOUT.pt also for that MD data, with the ratios of timescales and lifetimes and the Jensen-Shannon divergence of the
+populations, the hidden states compared in the order of their populations.  Needs --parallel-sim.
 """
 import argparse
 import json
@@ -398,6 +405,33 @@ def ck(a, x):
     return res
 
 
+hmm_hidden = number(int, lambda v: 1 <= v <= evaluate.HMM_MAX_HIDDEN, "expected a number of hidden states in 1..8, got {text!r}")
+
+
+def hmm_arguments(a):
+    """(states, hidden, lag) of --hmm, None without it; refused without --hmm-states / --hmm-hidden / --hmm-lag and
+    --parallel-sim; the options of --hmm are refused without it"""
+    if a.hmm is None:
+        if any(v is not None for v in (a.hmm_states, a.hmm_hidden, a.hmm_lag)):
+            raise SystemExit("--hmm-states, --hmm-hidden and --hmm-lag need --hmm")
+        return None
+    if a.hmm_states is None or a.hmm_hidden is None or a.hmm_lag is None:
+        raise SystemExit("--hmm needs --hmm-states K, --hmm-hidden M and --hmm-lag L (frames)")
+    if a.parallel_sim is None:
+        raise SystemExit("--hmm needs --parallel-sim (the trajectories of the samples)")
+    return a.hmm_states, a.hmm_hidden, a.hmm_lag
+
+
+def hmm(a, x):
+    K, M, lag = hmm_arguments(a)
+    ref, ref_lengths = ordered_frames(a.hmm) if a.hmm else (None, None)
+    ev = evaluate.HmmEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, n_hidden=M, lagtime=lag, frame_time=a.frame_time,
+                               ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
+    res.update({"n_microstates": K, "n_hidden": M, "lagtime": lag, "frame_time": a.frame_time})
+    return res
+
+
 def write_aligned(a, x):
     folded = evaluate.folded_ca(a.folded_pdb, a.mol.lower())
     torch.save(evaluate.superpose(x, folded, device=a.device).cpu(), a.write_aligned)
@@ -496,6 +530,13 @@ def build_parser():
                     help="multiples of the lag time that are tested (with --ck)")
     ap.add_argument("--ck-bootstrap", type=msm_bootstrap, default=None, metavar="B",
                     help="percentile intervals of the test from B resamples of the trajectories (with --ck)")
+    ap.add_argument("--hmm", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report a hidden Markov model of the microstate trajectory: timescales, populations and lifetimes of "
+                         "its hidden states (time-ordered Langevin samples; needs --parallel-sim, --hmm-states, --hmm-hidden and "
+                         "--hmm-lag); with HELDOUT.pt also for that MD data")
+    ap.add_argument("--hmm-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --hmm)")
+    ap.add_argument("--hmm-hidden", type=hmm_hidden, default=None, metavar="M", help="hidden states, 1..8 (with --hmm)")
+    ap.add_argument("--hmm-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --hmm)")
     ap.add_argument("--device", default="cuda:0")
     return ap
 
@@ -521,6 +562,7 @@ def main():
     msm_spectrum_arguments(a)
     passage_arguments(a)
     ck_arguments(a)
+    hmm_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -558,6 +600,8 @@ def main():
         res["passage"] = passage(a, x)
     if a.ck is not None:
         res["ck"] = ck(a, x)
+    if a.hmm is not None:
+        res["hmm"] = hmm(a, x)
     if a.write_aligned:
         write_aligned(a, x)
     print(json.dumps(res))

@@ -23,7 +23,8 @@ _EVALUATE = (
     "MsmPassageEvaluator",
     "msm_spectrum", "MsmSpectrum", "spectral_solver",
     "propagator", "msm_propagate", "msm_relaxation", "msm_autocorrelation", "MsmAutocorrelation", "pcca_memberships",
-    "metastable_sets", "chapman_kolmogorov", "chapman_kolmogorov_of_models", "ChapmanKolmogorov", "ChapmanKolmogorovEvaluator")
+    "metastable_sets", "chapman_kolmogorov", "chapman_kolmogorov_of_models", "ChapmanKolmogorov", "ChapmanKolmogorovEvaluator",
+    "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator")
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",

@@ -156,6 +156,12 @@ SYMBOLS = {
     "dff_msm_propagate": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P,
                                     _P, C.c_size_t, _P]),
     "dff_debug_msm_propagate_path": (C.c_int, [C.c_int]),
+    "dff_hmm_chunk": (C.c_int, []),
+    "dff_hmm_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "dff_hmm_workspace_bytes": (C.c_longlong, [C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dff_hmm_estep": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                C.c_size_t, _P]),
+    "dff_debug_hmm_stages": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1354,3 +1360,72 @@ def msm_propagate(t, mat_of, ks, w0, obs, n_steps: int, want_last=False, workspa
                                       _ptr(w_last), _ptr(status), _ptr(workspace),
                                       int(workspace.numel() * workspace.element_size()), _stream(t)), "dff_msm_propagate")
     return out, w_last, status
+
+
+# ---- hidden Markov models: one E-step of Baum-Welch over all chains (dff_hmm_estep) ----
+HMM_MAX_HIDDEN = 8
+HMM_MAX_CHAINS = 1 << 20
+
+
+def hmm_chunk() -> int:
+    """The chunk length of dff_hmm_estep (frames of a chain per chunk), read from the library."""
+    return int(load_library().dff_hmm_chunk())
+
+
+def debug_hmm_stages(stages: int):
+    """Benchmarks only: 0 = the whole call, 1 .. 5 = dff_hmm_estep stops after that many of its launches (outputs unfinished)."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_hmm_stages(int(stages)), "dff_debug_hmm_stages")
+
+
+def hmm_plan(lengths, lag: int):
+    """(n_chains, n_chunks) of a call on trajectories of `lengths` at `lag` (dff_hmm_plan: host arithmetic)."""
+    lib = load_library()
+    lh = _lengths(lengths)
+    a, b = C.c_longlong(0), C.c_longlong(0)
+    _check(lib, lib.dff_hmm_plan(lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), C.byref(a), C.byref(b)), "dff_hmm_plan")
+    return int(a.value), int(b.value)
+
+
+def hmm_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
+    lh = _lengths(lengths)
+    return _workspace_bytes("dff_hmm_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
+
+
+def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, post=True, workspace=None):
+    """One E-step of Baum-Welch over all chains (dff_hmm_estep): labels int32 CUDA (n,) in trajectories of `lengths` (host), chain
+    (r, f) the frames f, f + lag, ... of trajectory r, a negative label a missing observation; trans (m, m), emit (m, K) and init
+    (m,) contiguous float64 CUDA tensors, not normalised by the call.  Returns a dict of CUDA tensors: stats float64
+    (1 + m m + m + m K,) = loglik | xi (m, m) | gamma0 (m) | gamma_sym (m, K); chain_loglik float64 (n_traj lag,) and post float64
+    (n, m), the posteriors in frame order (None when not asked for; post may also be a (n, m) tensor to fill); status int32 (1,):
+    0 success, 1 a non-finite or negative parameter, 2 a chain of likelihood zero, 3 a label >= K -- every output NaN unless 0.
+    Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    f64 = torch.float64
+    m, K = (int(emit.shape[0]), int(emit.shape[1])) if isinstance(emit, torch.Tensor) and emit.dim() == 2 else (-1, -1)
+    if not (_is_tensor(emit, f64, (m, K)) and _is_tensor(trans, f64, (m, m)) and _is_tensor(init, f64, (m,))
+            and trans.device == emit.device and init.device == emit.device):
+        raise ValueError("trans (m, m), emit (m, K) and init (m,) must be contiguous float64 CUDA tensors on one device")
+    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == emit.device):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
+    n = int(labels.numel())
+    lh = _lengths(lengths)
+    lag = int(lag)
+    need = hmm_workspace_bytes(n, lh, lag, m, K)
+    dev = emit.device
+    stats = torch.empty(1 + m * m + m + m * K, dtype=f64, device=dev)
+    cl = torch.empty(int(lh.size) * lag, dtype=f64, device=dev) if chain_loglik else None
+    if isinstance(post, torch.Tensor):
+        if not (_is_tensor(post, f64, (n, m)) and post.device == dev):
+            raise ValueError("post must be a contiguous float64 CUDA tensor (n, m) on the parameters' device")
+        pt = post
+    else:
+        pt = torch.empty((n, m), dtype=f64, device=dev) if post else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    _check(lib, lib.dff_hmm_estep(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
+                                  _ptr(emit), _ptr(init), m, K, _ptr(stats), _ptr(cl), _ptr(pt), _ptr(status), _ptr(workspace),
+                                  int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_estep")
+    return {"stats": stats, "chain_loglik": cl, "post": pt, "status": status}

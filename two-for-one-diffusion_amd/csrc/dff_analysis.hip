@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_* and dff_msm_propagate*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <vector>
@@ -19,6 +19,7 @@
 #include "dff_msm_passage.hip"
 #include "dff_sym_eig.hip"
 #include "dff_msm_propagate.hip"
+#include "dff_hmm.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1467,5 +1468,184 @@ extern "C" int dff_msm_propagate(int device, const double* t, int n_mat, const i
                            path == 2 ? 1 : DFF_PROP_LDS_LIMIT + 1, DFF_MSM_MAXK);
         HIPCHK(hipGetLastError());
     }
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hidden Markov models: one E-step of Baum-Welch over all chains (dff_hmm.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dff_hmm_chunk(void) { return DFF_HMM_CHUNK; }
+
+// how many of the call's launches run: 0 = all of them; 1 .. 5 = stop after the parameters, the chunk products, the carries, the
+// apply pass, the emission counts (benchmarks: the share of every launch, by differences; the outputs are then unfinished)
+static std::atomic<int> g_hmm_stages{0};
+
+extern "C" int dff_debug_hmm_stages(int stages) {
+    if (stages < 0 || stages > 5) return fail(DFF_EINVAL, "debug_hmm_stages: 0 (all) or 1 .. 5 launches");
+    g_hmm_stages.store(stages);
+    return DFF_OK;
+}
+
+// chains and chunks of a call, and (cpre != null) the chunks before every trajectory: cpre[0 .. n_traj]
+static int hmm_plan(const long long* lengths, int n_traj, int lag, long long* n_chains, long long* n_chunks, long long* cpre,
+                    const char* what) {
+    if (lag < 1) return fail(DFF_EINVAL, "%s: lag must be >= 1", what);
+    if (n_traj < 0 || (n_traj > 0 && !lengths)) return fail(DFF_EINVAL, "%s: null / negative trajectory lengths", what);
+    if ((long long)n_traj * lag > DFF_HMM_MAXCHAINS)
+        return fail(DFF_EINVAL, "%s: %lld chains, at most %d", what, (long long)n_traj * lag, DFF_HMM_MAXCHAINS);
+    long long chunks = 0;
+    for (int r = 0; r < n_traj; ++r) {
+        if (lengths[r] < 0) return fail(DFF_EINVAL, "%s: trajectory %d has negative length", what, r);
+        if (cpre) cpre[r] = chunks;
+        const long long q = lengths[r] / lag, rem = lengths[r] - q * lag;
+        chunks += rem * hmm_chunks_of(q + 1) + (lag - rem) * hmm_chunks_of(q);
+    }
+    if (cpre) cpre[n_traj] = chunks;
+    if (n_chains) *n_chains = (long long)n_traj * lag;
+    if (n_chunks) *n_chunks = chunks;
+    return DFF_OK;
+}
+
+extern "C" int dff_hmm_plan(const long long* lengths, int n_traj, int lag, long long* n_chains, long long* n_chunks) {
+    return hmm_plan(lengths, n_traj, lag, n_chains, n_chunks, nullptr, "hmm_plan");
+}
+
+static int hmm_check_shape(long long n, int m, int K, const char* what) {
+    if (n < 0) return fail(DFF_EINVAL, "%s: negative frame count", what);
+    if (n > (1LL << 31)) return fail(DFF_EINVAL, "%s: more than 2^31 frames", what);
+    if (m < 1 || m > DFF_HMM_MAXM) return fail(DFF_EINVAL, "%s: the number of hidden states must be 1..%d", what, DFF_HMM_MAXM);
+    return micro_check_count(K, what, "symbols");
+}
+
+// the sections of the workspace, each a multiple of 16 bytes
+struct HmmLayout {
+    size_t tab, flags, a, p0, bt, prod, pexp, ain, bout, ll, post, part, total;
+    HmmLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) {
+        const size_t MP = (size_t)hmm_pad(m), d = sizeof(double);
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+        tab = take(2 * ((size_t)n_traj + 1) * sizeof(long long));
+        flags = take(4 * sizeof(int));
+        a = take(MP * MP * d);
+        p0 = take(MP * d);
+        bt = take((size_t)K * MP * d);
+        prod = take((size_t)n_chunks * MP * MP * d);                // the chunk products, then the chunks' sums of xi
+        pexp = take((size_t)n_chunks * MP * sizeof(int));
+        ain = take((size_t)n_chunks * MP * d);
+        bout = take((size_t)n_chunks * MP * d);
+        ll = take((size_t)n_chains * d);
+        post = take((size_t)n * m * d);
+        part = take((size_t)((n + DFF_HMM_GROUP - 1) / DFF_HMM_GROUP) * K * m * d);
+        total = o;
+    }
+};
+
+extern "C" long long dff_hmm_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
+    const char* what = "hmm_workspace_bytes";
+    if (hmm_check_shape(n, m, K, what)) return -1;
+    long long n_chains, n_chunks;
+    if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
+    if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
+    return (long long)HmmLayout(n, n_traj, n_chains, n_chunks, m, K).total;
+}
+
+template <int MP>
+static int hmm_launches(hipStream_t stream, const int32_t* labels, long long n, HmmPlan pl, long long n_chains, long long n_chunks,
+                        int m, int K, const HmmLayout& lay, char* ws, double* stats, double* chain_ll, double* post) {
+    const double* A = (const double*)(ws + lay.a);
+    const double* p0 = (const double*)(ws + lay.p0);
+    const double* Bt = (const double*)(ws + lay.bt);
+    double* prod = (double*)(ws + lay.prod);
+    int* pexp = (int*)(ws + lay.pexp);
+    double* ain = (double*)(ws + lay.ain);
+    double* bout = (double*)(ws + lay.bout);
+    double* part = (double*)(ws + lay.part);
+    int* flags = (int*)(ws + lay.flags);
+    const long long n_groups = (n + DFF_HMM_GROUP - 1) / DFF_HMM_GROUP;
+    const int stages = g_hmm_stages.load() ? g_hmm_stages.load() : 6;
+    if (stages < 2) return DFF_OK;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(dff_hmm_products_kernel<MP>, dim3((unsigned)((n_chunks * MP + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS)),
+                           dim3(DFF_HMM_THREADS), 0, stream, labels, pl, n_chunks, m, K, A, Bt, prod, pexp);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 3) return DFF_OK;
+    if (n_chains > 0) {
+        hipLaunchKernelGGL(dff_hmm_carry_kernel<MP>, dim3((unsigned)((n_chains + 63) / 64), 2), dim3(64), 0, stream, labels, pl,
+                           n_chains, m, K, p0, Bt, (const double*)prod, (const int*)pexp, ain, bout, chain_ll, flags);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 4) return DFF_OK;
+    if (n_chunks > 0) {
+        const int G = hmm_apply_groups(MP);
+        const unsigned lds = (unsigned)((size_t)G * (DFF_HMM_CHUNK + 3) * MP * sizeof(double));
+        if (lds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_hmm_apply_kernel<MP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dff_hmm_apply_kernel<MP>, dim3((unsigned)((n_chunks + G - 1) / G)), dim3(64), lds, stream, labels, pl,
+                           n_chunks, m, K, A, p0, Bt, (const double*)ain, (const double*)bout, post, prod, flags);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 5) return DFF_OK;
+    if (n_chunks > 0) {
+        const unsigned elds = (unsigned)(((size_t)K * m + (size_t)DFF_HMM_GROUP * m) * sizeof(double) + DFF_HMM_GROUP * sizeof(int));
+        if (elds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void*)&dff_hmm_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)elds));
+        hipLaunchKernelGGL(dff_hmm_emit_kernel, dim3((unsigned)n_groups), dim3(DFF_HMM_THREADS), elds, stream, labels, n, m, K,
+                           (const double*)post, part);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 6) return DFF_OK;
+    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
+    hipLaunchKernelGGL(dff_hmm_reduce_kernel<MP>, dim3((unsigned)nstats), dim3(64), 0, stream, pl, n_chains, n_chunks, n_chunks > 0 ? n_groups : 0, m, K,
+                       (const double*)chain_ll, (const double*)prod, (const double*)post, (const double*)part, stats);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+extern "C" int dff_hmm_estep(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj, int lag,
+                             const double* trans, const double* emit, const double* init, int m, int K, double* stats,
+                             double* chain_loglik, double* post, int32_t* status, void* workspace, size_t workspace_bytes,
+                             void* stream_) {
+    const char* what = "hmm_estep";
+    int rc = hmm_check_shape(n, m, K, what);
+    if (rc) return rc;
+    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
+    long long n_chains, n_chunks;
+    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
+    const size_t nt1 = tab.size() / 2;
+    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
+    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    if (!trans || !emit || !init || !stats || !status)
+        return fail(DFF_EINVAL, "%s: null transition matrix / emissions / initial distribution / stats / status", what);
+    const HmmLayout lay(n, n_traj, n_chains, n_chunks, m, K);
+    if ((rc = check_workspace(workspace, workspace_bytes, (long long)lay.total, what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
+    char* ws = (char*)workspace;
+    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;
+    HmmPlan pl;
+    pl.off = (const long long*)(ws + lay.tab);
+    pl.cpre = pl.off + nt1;
+    pl.n_traj = n_traj;
+    pl.lag = lag;
+    const int MP = hmm_pad(m);
+    hipLaunchKernelGGL(dff_hmm_prep_kernel, dim3(1), dim3(1024), 0, stream, trans, emit, init, m, K, MP, (double*)(ws + lay.a),
+                       (double*)(ws + lay.p0), (double*)(ws + lay.bt), (int*)(ws + lay.flags));
+    HIPCHK(hipGetLastError());
+    double* ll = chain_loglik ? chain_loglik : (double*)(ws + lay.ll);
+    double* pp = post ? post : (double*)(ws + lay.post);
+    if (MP == 2) rc = hmm_launches<2>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+    else if (MP == 4) rc = hmm_launches<4>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+    else rc = hmm_launches<8>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+    if (rc || g_hmm_stages.load()) return rc;
+    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
+    long long most = nstats > n_chains ? nstats : n_chains;
+    if (post && n * m > most) most = n * m;
+    const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
+    hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
+                       (const int*)(ws + lay.flags), nstats, stats, n_chains, chain_loglik, n * m, post, status);
+    HIPCHK(hipGetLastError());
     return DFF_OK;
 }

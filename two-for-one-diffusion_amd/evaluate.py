@@ -3581,3 +3581,293 @@ class ChapmanKolmogorovEvaluator(_TrajectoryEvaluator):
 
     def _compare(self, res, ref):
         res["ck_max_abs_diff_minus_ref"] = res["ck_max_abs_diff"] - ref["ck_max_abs_diff"]
+
+
+# ---- hidden Markov models on the microstate trajectory: Baum-Welch with the E-step on the GPU (dff_hmm_estep) ----
+HMM_MAX_HIDDEN = binding.HMM_MAX_HIDDEN
+
+
+class _DeviceHmmEstep:
+    """estep(labels (n,) int32 tensor on the device, lengths, lag, A (m, m), B (m, K), p0 (m,), want_post=False) -> (stats
+    float64 host array, packed as dff_hmm_estep packs it, chain_loglik host array | None, post (n, m) float64 DEVICE tensor |
+    None, status int): one dff_hmm_estep call and one read-back of the packed statistics (the status is read only when they are
+    NaN).  The workspace is kept between calls."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = None
+
+    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
+        dev = self.device
+        par = [torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev) for x in (A, B, p0)]
+        need = binding.hmm_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        res = binding.hmm_estep(labels, lengths, lag, *par, chain_loglik=want_post, post=want_post, workspace=self._ws)
+        stats = res["stats"].cpu().numpy()
+        status = int(res["status"].cpu()) if np.isnan(stats[0]) else 0
+        return stats, (res["chain_loglik"].cpu().numpy() if want_post else None), res["post"], status
+
+
+def hmm_estep_solver(device):
+    """estep(labels, lengths, lag, A, B, p0, want_post=False) -> (stats, chain_loglik | None, post | None, status) on the GPU
+    (dff_hmm_estep): stats = loglik | xi (m, m) | gamma0 (m) | gamma_sym (m, K) as one host array, post the (n, m) posteriors
+    as a tensor on the device."""
+    return _DeviceHmmEstep(device)
+
+
+def _row_normalised(x):
+    s = x.sum(axis=1)[:, None]
+    return x / np.where(s > 0, s, 1.0)
+
+
+def _hmm_labels(labels, traj_lengths, n_states, device, what):
+    lab = torch.as_tensor(labels).reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+    lengths = _check_lengths(traj_lengths, int(lab.numel()))
+    if n_states is None:
+        n_states = int(lab.max()) + 1 if lab.numel() else 0
+    if not 1 <= int(n_states) <= MSM_MAX_STATES:
+        raise ValueError(f"{what}: n_states must be 1..{MSM_MAX_STATES}, not {n_states}")
+    return lab, lengths, int(n_states)
+
+
+def initial_hmm(labels, lagtime, n_hidden, traj_lengths=None, n_states=None, *, device="cuda:0"):
+    """The start of Baum-Welch from a Markov state model -> (A (m, m), B (m, K), p0 (m,)), m = n_hidden, K = n_states.  A
+    reversible MarkovStateModel is fitted at `lagtime`; M = pcca_memberships(model, m), clipped at 0 and row-normalised;
+    A = row-normalised M^T Pi T M (non-negative, with a symmetric flux), p0 ~ M^T pi, B[i, s] ~ f_s M~[s, i], row-normalised, with
+    f_s the empirical frequency of symbol s and M~ the membership for symbols of the active set and 1 / m for observed symbols
+    outside it: no observed symbol is impossible.  ValueError when the active set has fewer than m states."""
+    m = int(n_hidden)
+    if m != n_hidden or not 1 <= m <= HMM_MAX_HIDDEN:
+        raise ValueError(f"initial_hmm: n_hidden must be an integer in 1..{HMM_MAX_HIDDEN}")
+    lab, lengths, K = _hmm_labels(labels, traj_lengths, n_states, torch.device(device), "initial_hmm")
+    model = MarkovStateModel(lagtime, device=device).fit(lab, lengths, K)
+    act = np.asarray(model.active_set, np.int64)
+    if len(act) < m:
+        raise ValueError(f"initial_hmm: the active set has {len(act)} states, fewer than n_hidden = {m}")
+    M = _row_normalised(np.clip(pcca_memberships(model, m), 0.0, None))
+    pi, T = model.stationary_distribution, model.transition_matrix
+    A = _row_normalised(M.T @ (pi[:, None] * T) @ M)
+    p0 = M.T @ pi
+    ok = lab[(lab >= 0) & (lab < K)].to(torch.int64)
+    f = torch.bincount(ok, minlength=K).cpu().numpy().astype(np.float64)
+    Mt = np.full((K, m), 1.0 / m)
+    Mt[act] = M
+    B = _row_normalised((f[:, None] * Mt).T)
+    return A, B, p0 / p0.sum()
+
+
+class HiddenMarkovModel:
+    """A discrete hidden Markov model over a microstate trajectory at one lag time, by Baum-Welch: the E-step is one
+    dff_hmm_estep call and one packed read-back per iteration (hmm_estep_solver), the M-step runs on the host.  The defaults
+    (reversible=True, accuracy=1e-3, max_iter=1000) are those of deeptime's MaximumLikelihoodHMM as remembered; nothing here
+    is held to deeptime.
+
+    fit(labels, traj_lengths=None, n_states=None, initial=None): labels (n,), negative = a missing observation; at lag tau the
+    tau strided sub-sequences of every trajectory are the chains.  initial: (A, B, p0), default initial_hmm(...).  M-step:
+    B = row-normalised Gamma, p0 = gamma0 / sum, A = row-normalised Xi, or with reversible=True the transition matrix of
+    MarkovStateModel(lagtime).fit_counts(Xi); when its active set is not all hidden states the fit stops with converged =
+    False and a .message.  A hidden state with zero expected occupancy keeps its previous row and sets degenerate = True.  The
+    loop stops when the log-likelihood changes by less than `accuracy` (converged = True; the parameters are those the last
+    log-likelihood was computed with) or after max_iter E-steps.  Afterwards the hidden states are renumbered by decreasing
+    stationary probability, the lower index winning a tie.
+
+    transition_matrix (m, m), observation_probabilities (m, K), initial_distribution (m,), stationary_distribution (m,),
+    log_likelihoods (one per E-step), n_iter, converged, degenerate, message."""
+
+    def __init__(self, n_hidden, lagtime, reversible=True, accuracy=1e-3, max_iter=1000, *, device="cuda:0"):
+        self.n_hidden, self.lagtime = int(n_hidden), int(lagtime)
+        if self.n_hidden != n_hidden or not 1 <= self.n_hidden <= HMM_MAX_HIDDEN:
+            raise ValueError(f"HiddenMarkovModel: n_hidden must be an integer in 1..{HMM_MAX_HIDDEN}")
+        if self.lagtime != lagtime or self.lagtime < 1:
+            raise ValueError("HiddenMarkovModel: lagtime must be an integer >= 1")
+        self.reversible, self.accuracy, self.max_iter = bool(reversible), float(accuracy), int(max_iter)
+        if not self.accuracy > 0 or self.max_iter < 1:
+            raise ValueError("HiddenMarkovModel: accuracy must be > 0 and max_iter >= 1")
+        self.device = torch.device(device)
+        self.transition_matrix = self.observation_probabilities = self.initial_distribution = None
+        self.stationary_distribution = None
+        self.log_likelihoods, self.n_iter, self.converged, self.degenerate, self.message = [], 0, False, False, ""
+        self._estep = None
+
+    def _check_parameters(self, A, B, p0, K):
+        A, B, p0 = (np.array(x, np.float64) for x in (A, B, p0))
+        m = self.n_hidden
+        if A.shape != (m, m) or B.shape != (m, K) or p0.shape != (m,):
+            raise ValueError(f"HiddenMarkovModel: initial must be (A ({m}, {m}), B ({m}, {K}), p0 ({m},))")
+        if not all(np.isfinite(x).all() and (x >= 0).all() for x in (A, B, p0)):
+            raise ValueError("HiddenMarkovModel: initial parameters must be finite and non-negative")
+        return A, B, p0
+
+    def _m_step(self, A, B, p0, stats):
+        """the next (A, B, p0, pi | None) from the packed statistics, or None when the reversible estimator lost a state"""
+        m, K = B.shape
+        xi = stats[1:1 + m * m].reshape(m, m)
+        g0 = stats[1 + m * m:1 + m * m + m]
+        gs = stats[1 + m * m + m:].reshape(m, K)
+        occ = gs.sum(axis=1)
+        if (occ <= 0).any():
+            self.degenerate = True
+        Bn = np.where(occ[:, None] > 0, gs / np.where(occ > 0, occ, 1.0)[:, None], B)
+        pn = g0 / g0.sum() if g0.sum() > 0 else p0
+        if self.reversible:
+            msm = MarkovStateModel(self.lagtime, device=self.device).fit_counts(xi)
+            if len(msm.active_set) != m:
+                return None
+            return msm.transition_matrix, Bn, pn, msm.stationary_distribution
+        rows = xi.sum(axis=1)
+        if (rows <= 0).any():
+            self.degenerate = True
+        An = np.where(rows[:, None] > 0, xi / np.where(rows > 0, rows, 1.0)[:, None], A)
+        return An, Bn, pn, None
+
+    def fit(self, labels, traj_lengths=None, n_states=None, initial=None):
+        lab, lengths, K = _hmm_labels(labels, traj_lengths, n_states, self.device, "HiddenMarkovModel")
+        if initial is None:
+            initial = initial_hmm(lab, self.lagtime, self.n_hidden, lengths, K, device=self.device)
+        A, B, p0 = self._check_parameters(*initial, K)
+        self._estep = estep = hmm_estep_solver(self.device)
+        self.log_likelihoods, self.n_iter, self.converged, self.degenerate, self.message = [], 0, False, False, ""
+        pi = None
+        while self.n_iter < self.max_iter:
+            stats, _, _, status = estep(lab, lengths, self.lagtime, A, B, p0)
+            self.n_iter += 1
+            if status:
+                self.message = {1: "a parameter became non-finite or negative", 2: "a chain has likelihood zero under the model",
+                                3: "a label >= n_states"}.get(status, f"status {status}")
+                break
+            self.log_likelihoods.append(float(stats[0]))
+            if len(self.log_likelihoods) > 1 and abs(self.log_likelihoods[-1] - self.log_likelihoods[-2]) < self.accuracy:
+                self.converged = True
+                break
+            nxt = self._m_step(A, B, p0, stats)
+            if nxt is None:
+                self.message = "the reversible estimator's active set lost a hidden state"
+                break
+            A, B, p0, pi = nxt
+        if pi is None or not self.reversible:
+            w, v = np.linalg.eig(A.T)
+            pi = np.abs(np.real(v[:, np.argmax(np.real(w))]))
+            pi = pi / pi.sum()
+        order = np.argsort(-pi, kind="stable")
+        self.transition_matrix = A[np.ix_(order, order)]
+        self.observation_probabilities, self.initial_distribution = B[order], p0[order]
+        self.stationary_distribution = pi[order]
+        return self
+
+    def _need_fit(self):
+        if self.transition_matrix is None:
+            raise ValueError("HiddenMarkovModel: not fitted")
+
+    def timescales(self, k=None):
+        """The k slowest implied timescales -lagtime / ln(lambda_i), i = 2 .. k + 1, in frames (k defaults to n_hidden - 1); NaN
+        for an eigenvalue <= 0 and beyond the model's size."""
+        self._need_fit()
+        k = self.n_hidden - 1 if k is None else int(k)
+        lam = np.linalg.eigvals(self.transition_matrix)
+        lam = np.sort(np.real(lam))[::-1] if self.reversible else np.sort(np.abs(lam))[::-1]
+        return _timescales_of(lam[1:k + 1], k, self.lagtime)
+
+    def lifetimes(self):
+        """-lagtime / ln(A_ii) per hidden state, in frames (inf for A_ii = 1, NaN for A_ii = 0)"""
+        self._need_fit()
+        d = np.diag(self.transition_matrix)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(d > 0, -self.lagtime / np.log(d), np.nan)
+
+    def metastable_memberships(self):
+        """(K, m): P(hidden state | symbol) = pi_i B[i, s] / sum_i pi_i B[i, s]; NaN rows for symbols the model never emits"""
+        self._need_fit()
+        w = (self.stationary_distribution[:, None] * self.observation_probabilities).T
+        s = w.sum(axis=1)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(s > 0, w / s, np.nan)
+
+    def _posterior(self, labels, traj_lengths):
+        self._need_fit()
+        K = self.observation_probabilities.shape[1]
+        lab, lengths, _ = _hmm_labels(labels, traj_lengths, K, self.device, "HiddenMarkovModel")
+        estep = self._estep or hmm_estep_solver(self.device)
+        stats, _, post, status = estep(lab, lengths, self.lagtime, self.transition_matrix, self.observation_probabilities,
+                                       self.initial_distribution, want_post=True)
+        if status:
+            raise ValueError(f"HiddenMarkovModel: the E-step failed on these labels (status {status})")
+        return stats, post
+
+    def hidden_probabilities(self, labels, traj_lengths=None):
+        """the posteriors P(hidden state | all observations of the frame's chain): float64 (n, m) on the device"""
+        return self._posterior(labels, traj_lengths)[1]
+
+    def hidden_states(self, labels, traj_lengths=None):
+        """the most probable hidden state of every frame (argmax of hidden_probabilities): int32 (n,) on the device"""
+        return torch.argmax(self.hidden_probabilities(labels, traj_lengths), dim=1).to(torch.int32)
+
+    def log_likelihood(self, labels, traj_lengths=None):
+        return float(self._posterior(labels, traj_lengths)[0][0])
+
+
+class HmmEvaluator(_TrajectoryEvaluator):
+    """The metastable states of the sampled dynamics and their kinetics.  Frames -> TIC projection and k-means microstates
+    (`tica`, n_microstates, centers, seed: as for MsmEvaluator) -> a HiddenMarkovModel of n_hidden states at `lagtime` (frames)
+    on the microstate trajectory; a non-finite frame is a missing observation.
+
+    eval(xyz, traj_lengths=None) -- None: ONE trajectory -- returns a dict:
+      timescales           list of the n_hidden - 1 implied timescales of the hidden transition matrix, in units of frame_time
+      hidden_populations   list: the stationary distribution of the hidden states, largest first
+      lifetimes            list: -lagtime / ln A_ii in units of frame_time, in the same order
+      n_iter, converged    E-steps spent; 1.0 when the log-likelihood met `accuracy`
+      loglik_per_frame     the last log-likelihood over the number of frames
+      samples_nonfinite    frames with a non-finite projection
+    and with ref_data the same keys with the suffix _ref, log10_timescale_ratio, log10_lifetime_ratio and population_js
+    (js_divergence of the populations): two separately fitted models share no labelling, so these compare the hidden states in
+    the order of their populations.  The models stay on .models, the argmax hidden states on .hidden and their dwell
+    statistics (label_runs -> dwell_summary) on .dwell, under "samples" / "refs".  Without the HIP library: DffLibraryError."""
+
+    KEYS = ("timescales", "hidden_populations", "lifetimes", "n_iter", "converged", "loglik_per_frame", "samples_nonfinite")
+
+    def __init__(self, mol_name, tica, n_microstates=200, n_hidden=2, lagtime=None, frame_time=1.0, ref_data=None,
+                 ref_traj_lengths=None, centers=None, seed=0, *, reversible=True, accuracy=1e-3, max_iter=1000, device="cuda:0"):
+        what = "HmmEvaluator"
+        super().__init__(what, mol_name, frame_time, device)
+        if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
+            raise ValueError(f"{what}: lagtime must be an integer >= 1 (frames)")
+        self.lagtime, self.n_hidden = int(lagtime), int(n_hidden)
+        if self.n_hidden != n_hidden or not 1 <= self.n_hidden <= HMM_MAX_HIDDEN:
+            raise ValueError(f"{what}: n_hidden must be an integer in 1..{HMM_MAX_HIDDEN}")
+        self._hmm = dict(reversible=reversible, accuracy=accuracy, max_iter=max_iter)
+        HiddenMarkovModel(self.n_hidden, self.lagtime, device="cpu", **self._hmm)       # its argument checks, now
+        self.mean, self.coeff = _tica_model(tica, what, TICA_MAX_DIM)
+        self._micro = _Microstates(what, n_microstates, self.coeff.shape[1], centers, seed, self.device)
+        self.n_microstates = self._micro.n_microstates
+        self.models, self.labels, self.hidden, self.dwell = {}, {}, {}, {}
+        self._start(ref_data, ref_traj_lengths)
+
+    centers = property(lambda self: self._micro.centers, doc="the microstate centres (K, k); None until they are fitted")
+
+    def project(self, x):
+        return binding.struct_tic(x, self.mean, self.coeff)
+
+    @staticmethod
+    def summarize(model, n_frames, frame_time=1.0, samples_nonfinite=0):
+        """eval()'s dict from a fitted HiddenMarkovModel: numpy only."""
+        ll = model.log_likelihoods[-1] if model.log_likelihoods else float("nan")
+        return {"timescales": [float(v) * frame_time for v in model.timescales()],
+                "hidden_populations": [float(v) for v in model.stationary_distribution],
+                "lifetimes": [float(v) * frame_time for v in model.lifetimes()],
+                "n_iter": float(model.n_iter), "converged": float(bool(model.converged)),
+                "loglik_per_frame": float(ll / n_frames) if n_frames else float("nan"),
+                "samples_nonfinite": float(samples_nonfinite)}
+
+    def _analyse(self, x, lengths, name):
+        labels = self._micro.labels(self.project(x))
+        model = HiddenMarkovModel(self.n_hidden, self.lagtime, device=self.device, **self._hmm)
+        model.fit(labels, lengths, self.n_microstates)
+        hidden = model.hidden_states(labels, lengths)
+        self.models[name], self.labels[name], self.hidden[name] = model, labels.cpu().numpy(), hidden.cpu().numpy()
+        self.dwell[name] = dwell_summary(label_runs(hidden, lengths, device=self.device), self.frame_time)
+        return self.summarize(model, int(labels.numel()), self.frame_time, int((labels < 0).sum()))
+
+    def _compare(self, res, ref):
+        res["log10_timescale_ratio"] = _log10_ratio(res["timescales"], ref["timescales"])
+        res["log10_lifetime_ratio"] = _log10_ratio(res["lifetimes"], ref["lifetimes"])
+        res["population_js"] = float(js_divergence(np.array(res["hidden_populations"]), np.array(ref["hidden_populations"])))
