@@ -868,6 +868,54 @@ int dff_hmm_estep(int device, const int32_t* labels_dev, long long n, const long
  * call that stopped early are unfinished. */
 int dff_debug_hmm_stages(int stages);
 
+/* ---- Hidden Markov models: the most probable hidden path (Viterbi) of every chain, by a chunked max-plus scan
+ * (csrc/dff_hmm_viterbi.hip; evaluate.py: hmm_viterbi_solver, HiddenMarkovModel.viterbi, HmmEvaluator(path="viterbi")) ----
+ * Labels, trajectories, chains (r-major, f-minor; chain r lag + f = the frames f, f + lag, ... of trajectory r), chunks
+ * (dff_hmm_chunk() frames of a chain), limits and refusals are those of dff_hmm_estep.  The PARAMETERS ARE LOGARITHMS, supplied
+ * by the caller, fp64: logtrans_dev (m, m) = la, logemit_dev (m, K) = lb, loginit_dev (m) = lp; -inf is allowed and means an
+ * impossible transition, emission or start.  le_t = lb[:, o_t], or zeros for a NEGATIVE label: a missing observation still gets
+ * a hidden state.  The device adds, compares and selects, nothing else: no log, no exp, no product.  A max is exact, so the
+ * bits follow from the order of the additions, which is this:
+ *   (1) per chunk, P = the max-plus identity (0 on the diagonal, -inf elsewhere); for every frame t of the chunk, the chain's
+ *       first frame left out:  P'(i, j) = (max_k (P(i, k) + la[k][j])) + le_t(j);
+ *   (2) per chain, serially over its chunks: din(first chunk) = lp + le_0, din(next chunk) = dout, dout(j) = max_i (din(i) + P(i, j));
+ *   (3) per chunk, from its din, for every frame t of the chunk (the chain's first frame left out):
+ *       delta'(j) = (max_i (delta(i) + la[i][j])) + le_t(j), the back-pointer psi_t(j) = the LOWEST i attaining the max; the chunk's
+ *       back map origin'(j) = origin(psi_t(j)) from the identity; a chain's last chunk takes the LOWEST argmax of its final delta as
+ *       the end state and the max as the chain's log-probability;
+ *   (4) per chain, serially from its last chunk: end(c - 1) = origin_c(end(c));  (5) per chunk, from end(c) back through its psi.
+ * path_dev (n) int32: the hidden state of every frame, in frame order (chain_order = 0) or in chain order (chain_order = 1: the
+ * chains back to back, r-major, f-minor, each in its own time order; the same values, permuted).  chain_logprob_dev (n_traj lag),
+ * or NULL: the joint log-probability of every chain's path and labels; an empty chain has 0 and no path entries.
+ * status_dev: ONE int32 --
+ *   0   success
+ *   1   a parameter entry is NaN or +inf
+ *   3   a label >= K
+ *   2   a non-empty chain whose best path has log-probability -inf (the model cannot emit it)
+ * in that order of precedence; on a non-zero status every path entry is -1 and every chain_logprob NaN.
+ * What the bits depend on: a chain's path and log-probability follow from that chain's labels, the log-parameters and the chunk
+ * length alone -- not from the other chains, the chain's place among them, the lag or trajectory it was cut from, or the workspace.
+ * Ties go to the lowest index, for back-pointers and for the end state.  The result is the same from call to call, on any
+ * workspace contents, and with chain_logprob_dev given or NULL.  Where every sum is exact in fp64 (integer-valued
+ * log-parameters, for example) the path and the log-probability are those of the textbook sequential recursion with the same
+ * tie rule; otherwise the carried din differs from the sequential delta by rounding, and with it possibly the choice between
+ * paths whose log-probabilities agree to rounding.
+ * lag >= 1, n_traj lag <= 2^20 chains, n <= 2^31; device pointers, `stream` only, no read-back, refusals on the host before any
+ * device call, no floating-point atomics, no workgroup waits on another.  workspace_dev 8-byte aligned, contents irrelevant. */
+/* Bytes of device workspace the call below needs (the trajectory table, the padded log-parameters, per chunk the product, the
+ * entering delta, the back map and the end state, per frame one 32-bit word of back-pointers, per chain an end state and a
+ * log-probability); -1 on bad arguments. */
+long long dff_hmm_viterbi_workspace_bytes(long long n, const long long* lengths_host, int n_traj, int lag, int m, int K);
+int dff_hmm_viterbi(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj, int lag,
+                    const double* logtrans_dev, const double* logemit_dev, const double* loginit_dev, int m, int K,
+                    int32_t* path_dev /* (n) */, int chain_order /* 0 frame order, 1 chain order */,
+                    double* chain_logprob_dev /* (n_traj lag) or NULL */, int32_t* status_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+/* For benchmarks, process-wide: 0 = the whole call (the default); 1 .. 6 = the call stops after its parameter launch, the chunk
+ * products, the forward carries, the apply pass, the backward carries, the backtrack -- the share of every launch, by
+ * differences.  The outputs of a call that stopped early are unfinished. */
+int dff_debug_hmm_viterbi_stages(int stages);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

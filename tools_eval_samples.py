@@ -17,7 +17,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
                                  [--ck [HELDOUT.pt] --ck-states K --ck-lag L [--ck-sets M] [--ck-multiples 1,2,3,4,5]
                                   [--ck-bootstrap B]]
-                                 [--hmm [HELDOUT.pt] --hmm-states K --hmm-hidden M --hmm-lag L [--frame-time T]]
+                                 [--hmm [HELDOUT.pt] --hmm-states K --hmm-hidden M --hmm-lag L [--hmm-path posterior|viterbi] [--frame-time T]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]
                                   [--msm-eigensolver host|device] [--msm-eigenvectors N]]
@@ -86,6 +86,9 @@ HELDOUT.pt also for that MD data, which then defines the sets.  Needs --parallel
 hidden states' populations and lifetimes in units of --frame-time, the E-steps spent and the log-likelihood per frame.  With
 HELDOUT.pt also for that MD data, with the ratios of timescales and lifetimes and the Jensen-Shannon divergence of the
 populations, the hidden states compared in the order of their populations.  Needs --parallel-sim.
+--hmm-path posterior|viterbi adds the dwell statistics of the hidden states ("hidden_path", "mean_dwell", "n_transitions"): of the
+argmax of the posterior marginals, taken on the frame-ordered series, or of the Viterbi path (HiddenMarkovModel.viterbi), taken
+inside the chains of the lag, one step being --hmm-lag frames.
 """
 import argparse
 import json
@@ -414,6 +417,8 @@ def hmm_arguments(a):
     if a.hmm is None:
         if any(v is not None for v in (a.hmm_states, a.hmm_hidden, a.hmm_lag)):
             raise SystemExit("--hmm-states, --hmm-hidden and --hmm-lag need --hmm")
+        if getattr(a, "hmm_path", None) is not None:
+            raise SystemExit("--hmm-path needs --hmm")
         return None
     if a.hmm_states is None or a.hmm_hidden is None or a.hmm_lag is None:
         raise SystemExit("--hmm needs --hmm-states K, --hmm-hidden M and --hmm-lag L (frames)")
@@ -426,9 +431,22 @@ def hmm(a, x):
     K, M, lag = hmm_arguments(a)
     ref, ref_lengths = ordered_frames(a.hmm) if a.hmm else (None, None)
     ev = evaluate.HmmEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, n_hidden=M, lagtime=lag, frame_time=a.frame_time,
-                               ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+                               ref_data=ref, ref_traj_lengths=ref_lengths, path=a.hmm_path or "posterior", device=a.device)
     res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
     res.update({"n_microstates": K, "n_hidden": M, "lagtime": lag, "frame_time": a.frame_time})
+    if a.hmm_path is not None:                                      # the dwell statistics of the chosen state series
+        for name, suffix in (("samples", ""), ("refs", "_ref")):
+            if name in ev.dwell:
+                res.update(hmm_dwell(ev.dwell[name], M, a.hmm_path, suffix))
+    return res
+
+
+def hmm_dwell(dwell, n_hidden, path, suffix=""):
+    """what --hmm-path adds under "hmm": the state series the dwells were taken on, the mean completed dwell of every hidden
+    state (in units of --frame-time; null without a completed dwell) and the number of transitions between hidden states"""
+    mean = [dwell["mean_dwell"].get(i, float("nan")) for i in range(n_hidden)]
+    res = cleaned({"mean_dwell" + suffix: mean, "n_transitions" + suffix: float(sum(dwell["events"].values()))})
+    res["hidden_path" + suffix] = path
     return res
 
 
@@ -537,6 +555,9 @@ def build_parser():
     ap.add_argument("--hmm-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --hmm)")
     ap.add_argument("--hmm-hidden", type=hmm_hidden, default=None, metavar="M", help="hidden states, 1..8 (with --hmm)")
     ap.add_argument("--hmm-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --hmm)")
+    ap.add_argument("--hmm-path", choices=("posterior", "viterbi"), default=None,
+                    help="with --hmm: the per-frame hidden states whose dwell statistics are reported -- the argmax of the posterior "
+                         "marginals on the frame-ordered series, or the Viterbi path with the dwells taken inside the lagged chains")
     ap.add_argument("--device", default="cuda:0")
     return ap
 

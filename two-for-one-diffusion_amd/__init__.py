@@ -24,7 +24,7 @@ _EVALUATE = (
     "msm_spectrum", "MsmSpectrum", "spectral_solver",
     "propagator", "msm_propagate", "msm_relaxation", "msm_autocorrelation", "MsmAutocorrelation", "pcca_memberships",
     "metastable_sets", "chapman_kolmogorov", "chapman_kolmogorov_of_models", "ChapmanKolmogorov", "ChapmanKolmogorovEvaluator",
-    "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator")
+    "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator", "hmm_viterbi_solver", "hmm_chain_lengths")
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",

@@ -162,6 +162,10 @@ SYMBOLS = {
     "dff_hmm_estep": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                 C.c_size_t, _P]),
     "dff_debug_hmm_stages": (C.c_int, [C.c_int]),
+    "dff_hmm_viterbi_workspace_bytes": (C.c_longlong, [C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dff_hmm_viterbi": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P,
+                                  _P, C.c_size_t, _P]),
+    "dff_debug_hmm_viterbi_stages": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1429,3 +1433,50 @@ def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, p
                                   _ptr(emit), _ptr(init), m, K, _ptr(stats), _ptr(cl), _ptr(pt), _ptr(status), _ptr(workspace),
                                   int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_estep")
     return {"stats": stats, "chain_loglik": cl, "post": pt, "status": status}
+
+
+# ---- hidden Markov models: the most probable hidden path of every chain (dff_hmm_viterbi) ----
+def debug_hmm_viterbi_stages(stages: int):
+    """Benchmarks only: 0 = the whole call, 1 .. 6 = dff_hmm_viterbi stops after that many of its launches (outputs unfinished)."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_hmm_viterbi_stages(int(stages)), "dff_debug_hmm_viterbi_stages")
+
+
+def hmm_viterbi_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
+    lh = _lengths(lengths)
+    return _workspace_bytes("dff_hmm_viterbi_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m),
+                            int(K))
+
+
+def hmm_viterbi(labels, lengths, lag: int, logtrans, logemit, loginit, chain_order=False, chain_logprob=True, workspace=None):
+    """The most probable hidden path of every chain (dff_hmm_viterbi): labels int32 CUDA (n,) in trajectories of `lengths` (host),
+    chain (r, f) the frames f, f + lag, ... of trajectory r, a negative label a missing observation; logtrans (m, m), logemit (m, K)
+    and loginit (m,) contiguous float64 CUDA tensors holding LOGARITHMS (-inf: impossible).  Returns a dict of CUDA tensors: path
+    int32 (n,), in frame order, or with chain_order=True the chains back to back (r-major, f-minor); chain_logprob float64
+    (n_traj lag,), the joint log-probability of every chain's path and labels (None when not asked for); status int32 (1,): 0
+    success, 1 a NaN or +inf parameter, 3 a label >= K, 2 a chain the model cannot emit -- then the path is -1 and chain_logprob NaN.
+    Ties go to the lowest state.  Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    f64 = torch.float64
+    m, K = (int(logemit.shape[0]), int(logemit.shape[1])) if isinstance(logemit, torch.Tensor) and logemit.dim() == 2 else (-1, -1)
+    if not (_is_tensor(logemit, f64, (m, K)) and _is_tensor(logtrans, f64, (m, m)) and _is_tensor(loginit, f64, (m,))
+            and logtrans.device == logemit.device and loginit.device == logemit.device):
+        raise ValueError("logtrans (m, m), logemit (m, K) and loginit (m,) must be contiguous float64 CUDA tensors on one device")
+    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == logemit.device):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
+    n = int(labels.numel())
+    lh = _lengths(lengths)
+    lag = int(lag)
+    need = hmm_viterbi_workspace_bytes(n, lh, lag, m, K)
+    dev = logemit.device
+    path = torch.empty(n, dtype=torch.int32, device=dev)
+    cl = torch.empty(int(lh.size) * lag, dtype=f64, device=dev) if chain_logprob else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    _check(lib, lib.dff_hmm_viterbi(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(logtrans),
+                                    _ptr(logemit), _ptr(loginit), m, K, _ptr(path), 1 if chain_order else 0, _ptr(cl), _ptr(status),
+                                    _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(logemit)),
+           "dff_hmm_viterbi")
+    return {"path": path, "chain_logprob": cl, "status": status}

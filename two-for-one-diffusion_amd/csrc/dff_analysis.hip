@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi among them), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <vector>
@@ -20,6 +20,7 @@
 #include "dff_sym_eig.hip"
 #include "dff_msm_propagate.hip"
 #include "dff_hmm.hip"
+#include "dff_hmm_viterbi.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1646,6 +1647,149 @@ extern "C" int dff_hmm_estep(int device, const int32_t* labels, long long n, con
     const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
     hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
                        (const int*)(ws + lay.flags), nstats, stats, n_chains, chain_loglik, n * m, post, status);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hidden Markov models: the most probable hidden path of every chain (dff_hmm_viterbi.hip)
+// ---------------------------------------------------------------------------------------------
+// how many of the call's launches run: 0 = all of them; 1 .. 6 = stop after the parameters, the chunk products, the forward
+// carries, the apply pass, the backward carries, the backtrack (benchmarks: the share of every launch, by differences; the
+// outputs are then unfinished)
+static std::atomic<int> g_vit_stages{0};
+
+extern "C" int dff_debug_hmm_viterbi_stages(int stages) {
+    if (stages < 0 || stages > 6) return fail(DFF_EINVAL, "debug_hmm_viterbi_stages: 0 (all) or 1 .. 6 launches");
+    g_vit_stages.store(stages);
+    return DFF_OK;
+}
+
+// the sections of the workspace, each a multiple of 16 bytes
+struct VitLayout {
+    size_t tab, flags, la, lp, lbt, prod, din, psi, origin, end, endstate, clp, total;
+    VitLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) {
+        const size_t MP = (size_t)hmm_pad(m), d = sizeof(double);
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+        tab = take(2 * ((size_t)n_traj + 1) * sizeof(long long));
+        flags = take(4 * sizeof(int));
+        la = take(MP * MP * d);
+        lp = take(MP * d);
+        lbt = take((size_t)K * MP * d);
+        prod = take((size_t)n_chunks * MP * MP * d);
+        din = take((size_t)n_chunks * MP * d);
+        psi = take((size_t)n * sizeof(unsigned));                   // one word of back-pointers per frame, in chain order
+        origin = take((size_t)n_chunks * sizeof(unsigned));
+        end = take((size_t)n_chunks * sizeof(int));
+        endstate = take((size_t)n_chains * sizeof(int));
+        clp = take((size_t)n_chains * d);
+        total = o;
+    }
+};
+
+extern "C" long long dff_hmm_viterbi_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
+    const char* what = "hmm_viterbi_workspace_bytes";
+    if (hmm_check_shape(n, m, K, what)) return -1;
+    long long n_chains, n_chunks;
+    if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
+    if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
+    return (long long)VitLayout(n, n_traj, n_chains, n_chunks, m, K).total;
+}
+
+template <int MP>
+static int vit_launches(hipStream_t stream, const int32_t* labels, HmmPlan pl, long long n_chains, long long n_chunks, int K,
+                        const VitLayout& lay, char* ws, int32_t* path, int chain_order, double* chain_lp) {
+    const double* la = (const double*)(ws + lay.la);
+    const double* lp = (const double*)(ws + lay.lp);
+    const double* lbt = (const double*)(ws + lay.lbt);
+    double* prod = (double*)(ws + lay.prod);
+    double* din = (double*)(ws + lay.din);
+    unsigned* psi = (unsigned*)(ws + lay.psi);
+    unsigned* origin = (unsigned*)(ws + lay.origin);
+    int* end = (int*)(ws + lay.end);
+    int* endstate = (int*)(ws + lay.endstate);
+    int* flags = (int*)(ws + lay.flags);
+    const int stages = g_vit_stages.load() ? g_vit_stages.load() : 7;
+    const unsigned lane_blocks = (unsigned)((n_chunks * MP + DFF_VIT_THREADS - 1) / DFF_VIT_THREADS);
+    if (stages < 2) return DFF_OK;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(dff_vit_products_kernel<MP>, dim3(lane_blocks), dim3(DFF_VIT_THREADS), 0, stream, labels, pl, n_chunks, K,
+                           la, lbt, prod);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 3) return DFF_OK;
+    if (n_chains > 0) {
+        hipLaunchKernelGGL(dff_vit_forward_kernel<MP>, dim3((unsigned)((n_chains + 63) / 64)), dim3(64), 0, stream, labels, pl,
+                           n_chains, K, lp, lbt, (const double*)prod, din, chain_lp);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 4) return DFF_OK;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(dff_vit_apply_kernel<MP>, dim3(lane_blocks), dim3(DFF_VIT_THREADS), 0, stream, labels, pl, n_chunks, K, la,
+                           lbt, (const double*)din, psi, origin, endstate, chain_lp, flags);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 5) return DFF_OK;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(dff_vit_backward_kernel, dim3((unsigned)((n_chains + 63) / 64)), dim3(64), 0, stream, pl, n_chains,
+                           (const unsigned*)origin, (const int*)endstate, end);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages < 6) return DFF_OK;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(dff_vit_backtrack_kernel, dim3((unsigned)((n_chunks + DFF_VIT_THREADS - 1) / DFF_VIT_THREADS)),
+                           dim3(DFF_VIT_THREADS), 0, stream, pl, n_chunks, (const unsigned*)psi, (const int*)end, chain_order, path);
+        HIPCHK(hipGetLastError());
+    }
+    return DFF_OK;
+}
+
+extern "C" int dff_hmm_viterbi(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj, int lag,
+                               const double* logtrans, const double* logemit, const double* loginit, int m, int K, int32_t* path,
+                               int chain_order, double* chain_logprob, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* stream_) {
+    const char* what = "hmm_viterbi";
+    int rc = hmm_check_shape(n, m, K, what);
+    if (rc) return rc;
+    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
+    long long n_chains, n_chunks;
+    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
+    const size_t nt1 = tab.size() / 2;
+    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
+    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    if (!logtrans || !logemit || !loginit || !status || (!path && n > 0))
+        return fail(DFF_EINVAL, "%s: null log transition matrix / log emissions / log initial distribution / path / status", what);
+    if (chain_order != 0 && chain_order != 1) return fail(DFF_EINVAL, "%s: chain_order must be 0 (frame order) or 1 (chain order)", what);
+    const VitLayout lay(n, n_traj, n_chains, n_chunks, m, K);
+    if ((rc = check_workspace(workspace, workspace_bytes, (long long)lay.total, what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
+    char* ws = (char*)workspace;
+    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;
+    HmmPlan pl;
+    pl.off = (const long long*)(ws + lay.tab);
+    pl.cpre = pl.off + nt1;
+    pl.n_traj = n_traj;
+    pl.lag = lag;
+    const int MP = hmm_pad(m);
+    HIPCHK(hipMemsetAsync(ws + lay.flags, 0, 4 * sizeof(int), stream));
+    long long pblocks = (n + 1023) / 1024;
+    pblocks = pblocks < 1 ? 1 : (pblocks > 1024 ? 1024 : pblocks);
+    hipLaunchKernelGGL(dff_vit_prep_kernel, dim3((unsigned)pblocks), dim3(1024), 0, stream, labels, n, logtrans, logemit, loginit, m,
+                       K, MP, (double*)(ws + lay.la), (double*)(ws + lay.lp), (double*)(ws + lay.lbt), (int*)(ws + lay.flags));
+    HIPCHK(hipGetLastError());
+    double* clp = chain_logprob ? chain_logprob : (double*)(ws + lay.clp);
+    if (MP == 2) rc = vit_launches<2>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
+    else if (MP == 4) rc = vit_launches<4>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
+    else rc = vit_launches<8>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
+    if (rc || g_vit_stages.load()) return rc;
+    const long long most = n > n_chains ? n : n_chains;
+    const long long blocks = (most + DFF_VIT_THREADS - 1) / DFF_VIT_THREADS;
+    hipLaunchKernelGGL(dff_vit_finish_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks < 1024 ? blocks : 1024))), dim3(DFF_VIT_THREADS),
+                       0, stream, (const int*)(ws + lay.flags), n, path, n_chains, chain_logprob, status);
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

@@ -3616,6 +3616,46 @@ def hmm_estep_solver(device):
     return _DeviceHmmEstep(device)
 
 
+class _DeviceHmmViterbi:
+    """viterbi(labels (n,) int32 tensor on the device, lengths, lag, la (m, m), lb (m, K), lp (m,), chain_order=False) -> (path
+    int32 (n,) DEVICE tensor, chain_logprob host array (n_traj lag,), status int): one dff_hmm_viterbi call on LOG-parameters and
+    one read-back of the log-probabilities and the status.  The workspace is kept between calls."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = None
+
+    def __call__(self, labels, lengths, lag, la, lb, lp, chain_order=False):
+        dev = self.device
+        par = [torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev) for x in (la, lb, lp)]
+        need = binding.hmm_viterbi_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        res = binding.hmm_viterbi(labels, lengths, lag, *par, chain_order=chain_order, chain_logprob=True, workspace=self._ws)
+        return res["path"], res["chain_logprob"].cpu().numpy(), int(res["status"].cpu())
+
+
+def hmm_viterbi_solver(device):
+    """viterbi(labels, lengths, lag, la, lb, lp, chain_order=False) -> (path, chain_logprob, status) on the GPU (dff_hmm_viterbi):
+    la, lb, lp the LOGARITHMS of A, B, p0; path int32 (n,) as a tensor on the device, in frame order or (chain_order=True) with
+    the chains back to back; chain_logprob a host array.  The seam for host tests, like hmm_estep_solver."""
+    return _DeviceHmmViterbi(device)
+
+
+def hmm_chain_lengths(traj_lengths, lag):
+    """The lengths of the chains of trajectories of `traj_lengths` at `lag`, in chain order (r-major, f-minor; empty chains
+    included): chain (r, f) holds the frames f, f + lag, ... of trajectory r.  They are the trajectory lengths that label_runs
+    takes with a path in chain order."""
+    lag = int(lag)
+    if lag < 1:
+        raise ValueError("hmm_chain_lengths: lag must be an integer >= 1")
+    out = []
+    for n in traj_lengths:
+        q, rem = divmod(int(n), lag)
+        out.extend([q + 1] * rem + [q] * (lag - rem))
+    return np.array(out, np.int64)
+
+
 def _row_normalised(x):
     s = x.sum(axis=1)[:, None]
     return x / np.where(s > 0, s, 1.0)
@@ -3805,6 +3845,27 @@ class HiddenMarkovModel:
     def log_likelihood(self, labels, traj_lengths=None):
         return float(self._posterior(labels, traj_lengths)[0][0])
 
+    def viterbi(self, labels, traj_lengths=None, order="frame", return_log_probabilities=False):
+        """The most probable hidden path of every chain (dff_hmm_viterbi through hmm_viterbi_solver): int32 (n,) on the device.
+        Unlike hidden_states -- the individually most probable state of every frame -- it is ONE path the model gives a
+        positive probability, and the most probable one; ties go to the lowest state.  order="frame": the state of every frame
+        in frame order; order="chain": the chains back to back (r-major, f-minor; their lengths: hmm_chain_lengths), the form
+        label_runs takes.  A missing observation gets a state too.  The logarithms of A, B and p0 are taken here, on the host; a
+        zero becomes -inf, an impossible step.  return_log_probabilities: also the joint log-probability of every chain's path and
+        labels, a host array (n_traj lagtime,) in chain order (0 for an empty chain).  ValueError when the call fails, e. g. on a
+        chain the model cannot emit (status 2)."""
+        self._need_fit()
+        if order not in ("frame", "chain"):
+            raise ValueError('HiddenMarkovModel: order must be "frame" or "chain"')
+        K = self.observation_probabilities.shape[1]
+        lab, lengths, _ = _hmm_labels(labels, traj_lengths, K, self.device, "HiddenMarkovModel")
+        with np.errstate(divide="ignore"):
+            par = [np.log(x) for x in (self.transition_matrix, self.observation_probabilities, self.initial_distribution)]
+        path, logprob, status = hmm_viterbi_solver(self.device)(lab, lengths, self.lagtime, *par, chain_order=order == "chain")
+        if status:
+            raise ValueError(f"HiddenMarkovModel: the Viterbi pass failed on these labels (status {status})")
+        return (path, logprob) if return_log_probabilities else path
+
 
 class HmmEvaluator(_TrajectoryEvaluator):
     """The metastable states of the sampled dynamics and their kinetics.  Frames -> TIC projection and k-means microstates
@@ -3821,14 +3882,25 @@ class HmmEvaluator(_TrajectoryEvaluator):
     and with ref_data the same keys with the suffix _ref, log10_timescale_ratio, log10_lifetime_ratio and population_js
     (js_divergence of the populations): two separately fitted models share no labelling, so these compare the hidden states in
     the order of their populations.  The models stay on .models, the argmax hidden states on .hidden and their dwell
-    statistics (label_runs -> dwell_summary) on .dwell, under "samples" / "refs".  Without the HIP library: DffLibraryError."""
+    statistics (label_runs -> dwell_summary) on .dwell, under "samples" / "refs".  Without the HIP library: DffLibraryError.
+
+    path="posterior" (the default) is the above: .hidden is hidden_states(), the individually most probable state of every
+    frame, and .dwell is taken on that frame-ordered series in units of frame_time -- at lagtime > 1 it interleaves lagtime
+    separately decoded chains.  path="viterbi": .hidden holds the Viterbi path (HiddenMarkovModel.viterbi) in frame order, and
+    .dwell = dwell_summary(label_runs(the path in chain order, hmm_chain_lengths(traj_lengths, lagtime)), frame_time *
+    lagtime): dwells and events are taken INSIDE the chains, not across the interleave, one step of a chain being lagtime
+    frames.  eval()'s dict is the same either way."""
 
     KEYS = ("timescales", "hidden_populations", "lifetimes", "n_iter", "converged", "loglik_per_frame", "samples_nonfinite")
 
     def __init__(self, mol_name, tica, n_microstates=200, n_hidden=2, lagtime=None, frame_time=1.0, ref_data=None,
-                 ref_traj_lengths=None, centers=None, seed=0, *, reversible=True, accuracy=1e-3, max_iter=1000, device="cuda:0"):
+                 ref_traj_lengths=None, centers=None, seed=0, *, reversible=True, accuracy=1e-3, max_iter=1000, path="posterior",
+                 device="cuda:0"):
         what = "HmmEvaluator"
         super().__init__(what, mol_name, frame_time, device)
+        if path not in ("posterior", "viterbi"):
+            raise ValueError(f'{what}: path must be "posterior" or "viterbi"')
+        self.path = path
         if lagtime is None or int(lagtime) != lagtime or int(lagtime) < 1:
             raise ValueError(f"{what}: lagtime must be an integer >= 1 (frames)")
         self.lagtime, self.n_hidden = int(lagtime), int(n_hidden)
@@ -3862,9 +3934,15 @@ class HmmEvaluator(_TrajectoryEvaluator):
         labels = self._micro.labels(self.project(x))
         model = HiddenMarkovModel(self.n_hidden, self.lagtime, device=self.device, **self._hmm)
         model.fit(labels, lengths, self.n_microstates)
-        hidden = model.hidden_states(labels, lengths)
+        if self.path == "viterbi":
+            hidden = model.viterbi(labels, lengths)
+            runs = label_runs(model.viterbi(labels, lengths, order="chain"), hmm_chain_lengths(lengths, self.lagtime), device=self.device)
+            step = self.frame_time * self.lagtime
+        else:
+            hidden = model.hidden_states(labels, lengths)
+            runs, step = label_runs(hidden, lengths, device=self.device), self.frame_time
         self.models[name], self.labels[name], self.hidden[name] = model, labels.cpu().numpy(), hidden.cpu().numpy()
-        self.dwell[name] = dwell_summary(label_runs(hidden, lengths, device=self.device), self.frame_time)
+        self.dwell[name] = dwell_summary(runs, step)
         return self.summarize(model, int(labels.numel()), self.frame_time, int((labels < 0).sum()))
 
     def _compare(self, res, ref):
