@@ -868,6 +868,52 @@ int dff_hmm_estep(int device, const int32_t* labels_dev, long long n, const long
  * call that stopped early are unfinished. */
 int dff_debug_hmm_stages(int stages);
 
+/* ---- Hidden Markov models: Baum-Welch on the device, n_steps iterations per call (csrc/dff_hmm_mstep.hip; evaluate.py:
+ * hmm_fit_solver, HiddenMarkovModel(m_step="device"), bootstrap_hmm) ----
+ * Limits, refusals (on the host, before any device call), chains, chunks and missing observations are those of dff_hmm_estep;
+ * additionally n_steps >= 1, accuracy > 0, rev_tol > 0, rev_max_sweeps >= 1, reversible 0 or 1, and dff_debug_hmm_stages must be 0.
+ * The call only enqueues on `stream`: no read-back, no floating-point atomics, no workgroup waits on another; the trajectory
+ * table is uploaded once per call.  trans_dev (m, m), emit_dev (m, K), init_dev (m) are read AND rewritten.
+ * state_dev: the caller zero-fills it to start a fit and passes it back unchanged to continue one.
+ * For s = 0 .. n_steps - 1, with no host read in between:
+ *   1. stop != 0: loglik_dev[s] = NaN; parameters, state and stationary_dev do not change (the E-step's launches still run, on
+ *      the frozen parameters, into the workspace).
+ *   2. The E-step on the current parameters: the launches of dff_hmm_estep, statistics and status in the workspace -- its
+ *      statistics bit for bit.
+ *   3. One launch of one workgroup.  n_estep += 1, estep_status = the E-step's status.  Status != 0: stop = 2, loglik_dev[s] =
+ *      NaN, nothing else changes.  Otherwise L = the log-likelihood, loglik_dev[s] = L.  n_estep > 1 and |L - last_loglik| <
+ *      accuracy: stop = 1, last_loglik = L, the parameters stay those L was computed with.  Otherwise last_loglik = L and the
+ *      M-step, in fp64, every sum in index order from +0, one term after the other, over the m real states:
+ *        occ_i = sum_s Gamma[i, s]; B'[i, s] = Gamma[i, s] / occ_i; occ_i <= 0: row i of B is kept, flag bit 0 (also in a step that
+ *        ends with stop = 3).  g = sum_i gamma0_i; p0' = gamma0 / g; g <= 0: p0 is kept.
+ *        reversible = 0: r_i = sum_j Xi_ij, A'_ij = Xi_ij / r_i; r_i <= 0: row i of A is kept, flag bit 0.
+ *        reversible = 1: the graph with an edge i -> j wherever Xi_ij > 0 must be strongly connected over all m states; if not,
+ *        stop = 3 and NONE of A, B, p0 changes.  m = 1: A' = [[1]], pi = [1].  Otherwise S = Xi + Xi^T, c_i = sum_j Xi_ij, x_i =
+ *        (sum_j S_ij) / 2; a sweep: q_i = c_i / x_i, t_ij = S_ij / (q_i + q_j) where S_ij != 0, else +0, x_i' = sum_j t_ij, err = max_i
+ *        |x_i' - x_i| / x_i, x <- x'.  The sweeps end after the first with err < rev_tol, or with an err that is not finite, or
+ *        when rev_max_sweeps are spent; rev_max_sweeps spent and the last err not below rev_tol: flag bit 1, x is used anyway.
+ *        Then t_ij from the final x, A'_ij = t_ij / x_i, pi = x / sum_i x_i -> stationary_dev; rev_sweeps += the sweeps.
+ * The result is a function of the inputs alone: the same from call to call, on any workspace contents, with stationary_dev
+ * given or NULL, and n_steps in one call or split over several with the state carried. */
+typedef struct {            /* 32 bytes */
+    int32_t n_estep;        /* E-steps run so far, over all calls */
+    int32_t stop;           /* 0 running | 1 converged | 2 the E-step failed (estep_status) | 3 the reversible estimator's active
+                               set lost a hidden state */
+    int32_t estep_status;   /* dff_hmm_estep's status word of the last E-step run */
+    int32_t flags;          /* bit 0: degenerate (a row kept its previous values); bit 1: a reversible M-step spent
+                               rev_max_sweeps without meeting rev_tol */
+    double  last_loglik;
+    long long rev_sweeps;   /* sweeps of the reversible estimator, all M-steps together */
+} dff_hmm_fit_state;
+/* Bytes of device workspace the call below needs: dff_hmm_workspace_bytes plus the packed statistics and a status word; -1 on
+ * bad arguments. */
+long long dff_hmm_fit_workspace_bytes(long long n, const long long* lengths_host, int n_traj, int lag, int m, int K);
+int dff_hmm_fit_steps(int device, const int32_t* labels_dev, long long n, const long long* lengths_host, int n_traj, int lag,
+                      double* trans_dev /* (m, m) in/out */, double* emit_dev /* (m, K) in/out */, double* init_dev /* (m) in/out */,
+                      int m, int K, int reversible, int n_steps, double accuracy, double rev_tol, long long rev_max_sweeps,
+                      double* loglik_dev /* (n_steps) */, double* stationary_dev /* (m), written by reversible M-steps only; may be NULL */,
+                      dff_hmm_fit_state* state_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- Hidden Markov models: the most probable hidden path (Viterbi) of every chain, by a chunked max-plus scan
  * (csrc/dff_hmm_viterbi.hip; evaluate.py: hmm_viterbi_solver, HiddenMarkovModel.viterbi, HmmEvaluator(path="viterbi")) ----
  * Labels, trajectories, chains (r-major, f-minor; chain r lag + f = the frames f, f + lag, ... of trajectory r), chunks

@@ -17,7 +17,8 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
                                  [--ck [HELDOUT.pt] --ck-states K --ck-lag L [--ck-sets M] [--ck-multiples 1,2,3,4,5]
                                   [--ck-bootstrap B]]
-                                 [--hmm [HELDOUT.pt] --hmm-states K --hmm-hidden M --hmm-lag L [--hmm-path posterior|viterbi] [--frame-time T]]
+                                 [--hmm [HELDOUT.pt] --hmm-states K --hmm-hidden M --hmm-lag L [--hmm-path posterior|viterbi] [--frame-time T]
+                                  [--hmm-bootstrap B [--hmm-block-frames N] [--hmm-bootstrap-seed S]]]
                                  [--msm [HELDOUT.pt] --msm-states K --msm-lag L [--msm-lagtimes a,b,c] [--frame-time T]
                                   [--msm-bootstrap B [--msm-block-frames F] [--msm-confidence C]]
                                   [--msm-eigensolver host|device] [--msm-eigenvectors N]]
@@ -89,6 +90,9 @@ populations, the hidden states compared in the order of their populations.  Need
 --hmm-path posterior|viterbi adds the dwell statistics of the hidden states ("hidden_path", "mean_dwell", "n_transitions"): of the
 argmax of the posterior marginals, taken on the frame-ordered series, or of the Viterbi path (HiddenMarkovModel.viterbi), taken
 inside the chains of the lag, one step being --hmm-lag frames.
+--hmm-bootstrap B adds error bars from B bootstrap refits on the GPU (bootstrap_hmm, warm-started from the fitted model, whole
+trajectories resampled or with --hmm-block-frames N blocks of N >= 2 L frames, draws seeded by --hmm-bootstrap-seed S):
+"timescales_std", "lifetimes_std", "hidden_populations_std", "timescales_lo" / "timescales_hi" (95 %) and "bootstrap_failed".
 """
 import argparse
 import json
@@ -419,7 +423,12 @@ def hmm_arguments(a):
             raise SystemExit("--hmm-states, --hmm-hidden and --hmm-lag need --hmm")
         if getattr(a, "hmm_path", None) is not None:
             raise SystemExit("--hmm-path needs --hmm")
+        if any(getattr(a, k, None) is not None for k in ("hmm_bootstrap", "hmm_block_frames", "hmm_bootstrap_seed")):
+            raise SystemExit("--hmm-bootstrap, --hmm-block-frames and --hmm-bootstrap-seed need --hmm")
         return None
+    if getattr(a, "hmm_bootstrap", None) is None and (getattr(a, "hmm_block_frames", None) is not None
+                                                       or getattr(a, "hmm_bootstrap_seed", None) is not None):
+        raise SystemExit("--hmm-block-frames and --hmm-bootstrap-seed need --hmm-bootstrap B")
     if a.hmm_states is None or a.hmm_hidden is None or a.hmm_lag is None:
         raise SystemExit("--hmm needs --hmm-states K, --hmm-hidden M and --hmm-lag L (frames)")
     if a.parallel_sim is None:
@@ -431,7 +440,9 @@ def hmm(a, x):
     K, M, lag = hmm_arguments(a)
     ref, ref_lengths = ordered_frames(a.hmm) if a.hmm else (None, None)
     ev = evaluate.HmmEvaluator(a.mol.lower(), tica_path(a), n_microstates=K, n_hidden=M, lagtime=lag, frame_time=a.frame_time,
-                               ref_data=ref, ref_traj_lengths=ref_lengths, path=a.hmm_path or "posterior", device=a.device)
+                               ref_data=ref, ref_traj_lengths=ref_lengths, path=a.hmm_path or "posterior",
+                               n_bootstrap=a.hmm_bootstrap or 0, block_frames=a.hmm_block_frames,
+                               bootstrap_seed=a.hmm_bootstrap_seed or 0, device=a.device)
     res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
     res.update({"n_microstates": K, "n_hidden": M, "lagtime": lag, "frame_time": a.frame_time})
     if a.hmm_path is not None:                                      # the dwell statistics of the chosen state series
@@ -555,6 +566,14 @@ def build_parser():
     ap.add_argument("--hmm-states", type=msm_states, default=None, metavar="K", help="k-means microstates (with --hmm)")
     ap.add_argument("--hmm-hidden", type=hmm_hidden, default=None, metavar="M", help="hidden states, 1..8 (with --hmm)")
     ap.add_argument("--hmm-lag", type=msm_lag, default=None, metavar="L", help="lag time in frames (with --hmm)")
+    ap.add_argument("--hmm-bootstrap", type=number(int, lambda v: v >= 1, "expected a number of resamples >= 1, got {text!r}"),
+                    default=None, metavar="B",
+                    help="with --hmm: error bars of the timescales, lifetimes and populations from B bootstrap refits on the GPU "
+                         "(bootstrap_hmm: timescales_std, lifetimes_std, hidden_populations_std, timescales_lo / _hi, bootstrap_failed)")
+    ap.add_argument("--hmm-block-frames", type=number(int, lambda v: v >= 2, "expected a block length >= 2 frames, got {text!r}"),
+                    default=None, metavar="N",
+                    help="with --hmm-bootstrap: resample blocks of N frames (at least 2 --hmm-lag) instead of whole trajectories")
+    ap.add_argument("--hmm-bootstrap-seed", type=int, default=None, metavar="S", help="with --hmm-bootstrap: the seed of the draws (0)")
     ap.add_argument("--hmm-path", choices=("posterior", "viterbi"), default=None,
                     help="with --hmm: the per-frame hidden states whose dwell statistics are reported -- the argmax of the posterior "
                          "marginals on the frame-ordered series, or the Viterbi path with the dwells taken inside the lagged chains")

@@ -24,7 +24,8 @@ _EVALUATE = (
     "msm_spectrum", "MsmSpectrum", "spectral_solver",
     "propagator", "msm_propagate", "msm_relaxation", "msm_autocorrelation", "MsmAutocorrelation", "pcca_memberships",
     "metastable_sets", "chapman_kolmogorov", "chapman_kolmogorov_of_models", "ChapmanKolmogorov", "ChapmanKolmogorovEvaluator",
-    "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator", "hmm_viterbi_solver", "hmm_chain_lengths")
+    "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator", "hmm_viterbi_solver", "hmm_chain_lengths",
+    "hmm_fit_solver", "resampled_labels", "bootstrap_hmm", "HmmBootstrap")
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",

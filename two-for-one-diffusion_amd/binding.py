@@ -162,6 +162,9 @@ SYMBOLS = {
     "dff_hmm_estep": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                 C.c_size_t, _P]),
     "dff_debug_hmm_stages": (C.c_int, [C.c_int]),
+    "dff_hmm_fit_workspace_bytes": (C.c_longlong, [C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dff_hmm_fit_steps": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_double, C.c_double, C.c_longlong, _P, _P, _P, _P, C.c_size_t, _P]),
     "dff_hmm_viterbi_workspace_bytes": (C.c_longlong, [C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dff_hmm_viterbi": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P,
                                   _P, C.c_size_t, _P]),
@@ -1433,6 +1436,72 @@ def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, p
                                   _ptr(emit), _ptr(init), m, K, _ptr(stats), _ptr(cl), _ptr(pt), _ptr(status), _ptr(workspace),
                                   int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_estep")
     return {"stats": stats, "chain_loglik": cl, "post": pt, "status": status}
+
+
+# ---- hidden Markov models: Baum-Welch on the device, many iterations per call (dff_hmm_fit_steps) ----
+HMM_FIT_STATE = np.dtype([("n_estep", "<i4"), ("stop", "<i4"), ("estep_status", "<i4"), ("flags", "<i4"), ("last_loglik", "<f8"),
+                          ("rev_sweeps", "<i8")])           # dff_hmm_fit_state: 32 bytes
+
+
+def hmm_fit_state_dict(words) -> dict:
+    """dff_hmm_fit_state as a dict of Python numbers from its 8 int32 words (a host array or tensor)."""
+    rec = np.ascontiguousarray(np.asarray(words, np.int32).reshape(8)).view(HMM_FIT_STATE)[0]
+    return {"n_estep": int(rec["n_estep"]), "stop": int(rec["stop"]), "estep_status": int(rec["estep_status"]),
+            "flags": int(rec["flags"]), "last_loglik": float(rec["last_loglik"]), "rev_sweeps": int(rec["rev_sweeps"])}
+
+
+def hmm_fit_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
+    lh = _lengths(lengths)
+    return _workspace_bytes("dff_hmm_fit_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
+
+
+def hmm_fit_steps(labels, lengths, lag: int, trans, emit, init, reversible, n_steps: int, accuracy: float, rev_tol: float = 1e-12,
+                  rev_max_sweeps: int = 1_000_000, state=None, loglik=None, stationary=True, workspace=None):
+    """n_steps iterations of Baum-Welch on the device (dff_hmm_fit_steps): labels, lengths and lag as for hmm_estep; trans (m, m),
+    emit (m, K) and init (m,) contiguous float64 CUDA tensors, REWRITTEN in place by every M-step.  state: an int32 CUDA tensor of
+    8 words (dff_hmm_fit_state; hmm_fit_state_dict reads it), passed back to continue a fit; None starts one from zeros.
+    loglik: a float64 CUDA tensor (n_steps,) to fill, or None; stationary: a float64 CUDA tensor (m,) that reversible M-steps
+    write, True for a new one filled with NaN, or None / False for none.  Returns a dict of CUDA tensors: loglik (NaN for the
+    steps of a stopped fit), stationary (or None), state.  Nothing is read back and nothing synchronises.  `workspace` is a uint8
+    CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    f64 = torch.float64
+    m, K = (int(emit.shape[0]), int(emit.shape[1])) if isinstance(emit, torch.Tensor) and emit.dim() == 2 else (-1, -1)
+    if not (_is_tensor(emit, f64, (m, K)) and _is_tensor(trans, f64, (m, m)) and _is_tensor(init, f64, (m,))
+            and trans.device == emit.device and init.device == emit.device):
+        raise ValueError("trans (m, m), emit (m, K) and init (m,) must be contiguous float64 CUDA tensors on one device")
+    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == emit.device):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError("n_steps must be >= 1")
+    dev = emit.device
+    if state is None:
+        state = torch.zeros(8, dtype=torch.int32, device=dev)
+    elif not (_is_tensor(state, torch.int32, (8,)) and state.device == dev):
+        raise ValueError("state must be a contiguous int32 CUDA tensor (8,) on the parameters' device")
+    if loglik is None:
+        loglik = torch.empty(n_steps, dtype=f64, device=dev)
+    elif not (_is_tensor(loglik, f64, (n_steps,)) and loglik.device == dev):
+        raise ValueError("loglik must be a contiguous float64 CUDA tensor (n_steps,) on the parameters' device")
+    if stationary is True:
+        stationary = torch.full((m,), float("nan"), dtype=f64, device=dev)
+    elif stationary is None or stationary is False:
+        stationary = None
+    elif not (_is_tensor(stationary, f64, (m,)) and stationary.device == dev):
+        raise ValueError("stationary must be a contiguous float64 CUDA tensor (m,) on the parameters' device")
+    n = int(labels.numel())
+    lh = _lengths(lengths)
+    lag = int(lag)
+    need = hmm_fit_workspace_bytes(n, lh, lag, m, K)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    _check(lib, lib.dff_hmm_fit_steps(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
+                                      _ptr(emit), _ptr(init), m, K, int(bool(reversible)), n_steps, float(accuracy), float(rev_tol),
+                                      int(rev_max_sweeps), _ptr(loglik), _ptr(stationary), _ptr(state), _ptr(workspace),
+                                      int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_fit_steps")
+    return {"loglik": loglik, "stationary": stationary, "state": state}
 
 
 # ---- hidden Markov models: the most probable hidden path of every chain (dff_hmm_viterbi) ----

@@ -21,6 +21,7 @@
 #include "dff_msm_propagate.hip"
 #include "dff_hmm.hip"
 #include "dff_hmm_viterbi.hip"
+#include "dff_hmm_mstep.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1648,6 +1649,97 @@ extern "C" int dff_hmm_estep(int device, const int32_t* labels, long long n, con
     hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
                        (const int*)(ws + lay.flags), nstats, stats, n_chains, chain_loglik, n * m, post, status);
     HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hidden Markov models: Baum-Welch on the device, n_steps iterations per call (dff_hmm_mstep.hip)
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(dff_hmm_fit_state) == 32, "dff_hmm_fit_state is 32 bytes");
+
+// the workspace of a fit: that of the E-step, then its packed statistics and its status word
+struct HmmFitLayout {
+    size_t stats, status, total;
+    HmmFitLayout(const HmmLayout& lay, int m, int K) {
+        const size_t nstats = 1 + (size_t)m * m + m + (size_t)m * K;
+        stats = lay.total;
+        status = stats + ((nstats * sizeof(double) + 15) & ~(size_t)15);
+        total = status + 16;
+    }
+};
+
+extern "C" long long dff_hmm_fit_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
+    const char* what = "hmm_fit_workspace_bytes";
+    if (hmm_check_shape(n, m, K, what)) return -1;
+    long long n_chains, n_chunks;
+    if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
+    if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
+    return (long long)HmmFitLayout(HmmLayout(n, n_traj, n_chains, n_chunks, m, K), m, K).total;
+}
+
+extern "C" int dff_hmm_fit_steps(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj, int lag,
+                                 double* trans, double* emit, double* init, int m, int K, int reversible, int n_steps,
+                                 double accuracy, double rev_tol, long long rev_max_sweeps, double* loglik, double* stationary,
+                                 dff_hmm_fit_state* state, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "hmm_fit_steps";
+    int rc = hmm_check_shape(n, m, K, what);
+    if (rc) return rc;
+    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
+    long long n_chains, n_chunks;
+    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
+    const size_t nt1 = tab.size() / 2;
+    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
+    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    if (!trans || !emit || !init || !loglik || !state)
+        return fail(DFF_EINVAL, "%s: null transition matrix / emissions / initial distribution / log-likelihoods / state", what);
+    if (reversible != 0 && reversible != 1) return fail(DFF_EINVAL, "%s: reversible must be 0 or 1", what);
+    if (n_steps < 1) return fail(DFF_EINVAL, "%s: n_steps must be >= 1", what);
+    if (!(accuracy > 0.0)) return fail(DFF_EINVAL, "%s: accuracy must be > 0", what);
+    if (!(rev_tol > 0.0)) return fail(DFF_EINVAL, "%s: rev_tol must be > 0", what);
+    if (rev_max_sweeps < 1) return fail(DFF_EINVAL, "%s: rev_max_sweeps must be >= 1", what);
+    if ((uintptr_t)state % sizeof(double)) return fail(DFF_EINVAL, "%s: the state must be 8-byte aligned", what);
+    if (g_hmm_stages.load()) return fail(DFF_EINVAL, "%s: dff_debug_hmm_stages is set: the E-step would stop early", what);
+    const HmmLayout lay(n, n_traj, n_chains, n_chunks, m, K);
+    const HmmFitLayout fit(lay, m, K);
+    if ((rc = check_workspace(workspace, workspace_bytes, (long long)fit.total, what))) return rc;
+    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
+    char* ws = (char*)workspace;
+    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;   // once per call
+    HmmPlan pl;
+    pl.off = (const long long*)(ws + lay.tab);
+    pl.cpre = pl.off + nt1;
+    pl.n_traj = n_traj;
+    pl.lag = lag;
+    const int MP = hmm_pad(m);
+    double* stats = (double*)(ws + fit.stats);
+    int* status = (int*)(ws + fit.status);
+    double* ll = (double*)(ws + lay.ll);
+    double* pp = (double*)(ws + lay.post);
+    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
+    const long long most = nstats > n_chains ? nstats : n_chains;
+    const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
+    for (int s = 0; s < n_steps; ++s) {
+        // the E-step: the launches of dff_hmm_estep, its statistics and status in the workspace
+        hipLaunchKernelGGL(dff_hmm_prep_kernel, dim3(1), dim3(1024), 0, stream, (const double*)trans, (const double*)emit,
+                           (const double*)init, m, K, MP, (double*)(ws + lay.a), (double*)(ws + lay.p0), (double*)(ws + lay.bt),
+                           (int*)(ws + lay.flags));
+        HIPCHK(hipGetLastError());
+        if (MP == 2) rc = hmm_launches<2>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+        else if (MP == 4) rc = hmm_launches<4>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+        else rc = hmm_launches<8>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
+        if (rc) return rc;
+        hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
+                           (const int*)(ws + lay.flags), nstats, stats, n_chains, (double*)nullptr, n * m, (double*)nullptr, status);
+        HIPCHK(hipGetLastError());
+        // control and M-step: one workgroup
+        hipLaunchKernelGGL(dff_hmm_fit_mstep_kernel, dim3(1), dim3(DFF_HMM_FIT_THREADS), 0, stream, (const double*)stats,
+                           (const int*)status, state, trans, emit, init, m, K, reversible, accuracy, rev_tol, rev_max_sweeps,
+                           loglik + s, stationary);
+        HIPCHK(hipGetLastError());
+    }
     return DFF_OK;
 }
 

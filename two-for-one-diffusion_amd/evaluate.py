@@ -3642,6 +3642,58 @@ def hmm_viterbi_solver(device):
     return _DeviceHmmViterbi(device)
 
 
+class _DeviceHmmFit:
+    """steps(...) of hmm_fit_solver on the GPU.  One float64 buffer holds A | B | p0 | pi | the state's 32 bytes | the
+    log-likelihoods, so a call reads back once; it, the workspace and with them the parameters and the state of the fit stay
+    on the device between the calls of one fit."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = self._buf = self._shape = None
+
+    def _views(self, m, K, n_steps):
+        o = [int(v) for v in np.cumsum([0, m * m, m * K, m, m, 4])]
+        if self._shape != (m, K) or self._buf is None or self._buf.numel() < o[-1] + n_steps:
+            old = self._buf if self._shape == (m, K) else None
+            self._buf = torch.full((int(o[-1]) + max(n_steps, 32),), float("nan"), dtype=torch.float64, device=self.device)
+            if old is not None:
+                self._buf[:o[-1]] = old[:o[-1]]
+            self._shape = (m, K)
+        b = self._buf
+        return (b[o[0]:o[1]].view(m, m), b[o[1]:o[2]].view(m, K), b[o[2]:o[3]], b[o[3]:o[4]], b[o[4]:o[5]].view(torch.int32),
+                b[o[5]:o[5] + n_steps], o)
+
+    def steps(self, labels, lengths, lag, A, B, p0, reversible, n_steps, accuracy, state=None, *, rev_tol=1e-12,
+              rev_max_sweeps=1_000_000):
+        m, K = np.shape(B)
+        n_steps = int(n_steps)
+        if state is not None and self._shape != (m, K):
+            raise ValueError("hmm_fit_solver: a state to continue from, but this solver holds no fit of that shape")
+        tA, tB, tp, tpi, tst, tll, o = self._views(m, K, n_steps)
+        if state is None:                                            # a new fit: the parameters go up, the state is zeroed
+            host = np.concatenate([np.ravel(np.asarray(x, np.float64)) for x in (A, B, p0)] + [np.full(m, np.nan), np.zeros(4)])
+            self._buf[:o[5]] = torch.from_numpy(host).to(self.device)
+        need = binding.hmm_fit_workspace_bytes(int(labels.numel()), lengths, lag, m, K)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        binding.hmm_fit_steps(labels, lengths, lag, tA, tB, tp, reversible, n_steps, accuracy, rev_tol, rev_max_sweeps, state=tst,
+                              loglik=tll, stationary=tpi, workspace=self._ws)
+        h = self._buf[:o[5] + n_steps].cpu().numpy()                 # the one read-back
+        pi = h[o[3]:o[4]].copy()
+        return (h[o[0]:o[1]].reshape(m, m).copy(), h[o[1]:o[2]].reshape(m, K).copy(), h[o[2]:o[3]].copy(), h[o[5]:].copy(),
+                None if np.isnan(pi).any() else pi, binding.hmm_fit_state_dict(h[o[4]:o[5]].view(np.int32)))
+
+
+def hmm_fit_solver(device):
+    """An object whose steps(labels, lengths, lag, A, B, p0, reversible, n_steps, accuracy, state=None, *, rev_tol=1e-12,
+    rev_max_sweeps=1_000_000) runs n_steps iterations of Baum-Welch on the GPU (dff_hmm_fit_steps) and reads back once ->
+    (A, B, p0 host arrays, loglik (n_steps,) with NaN for the steps of a stopped fit, pi (m,) of the last reversible M-step |
+    None before one, the state as a dict of dff_hmm_fit_state's fields).  state=None starts a fit from A, B, p0; the state
+    the last call returned continues it FROM THE PARAMETERS ON THE DEVICE (those that call returned; A, B, p0 are then not
+    read).  The seam for host tests, like hmm_estep_solver."""
+    return _DeviceHmmFit(device)
+
+
 def hmm_chain_lengths(traj_lengths, lag):
     """The lengths of the chains of trajectories of `traj_lengths` at `lag`, in chain order (r-major, f-minor; empty chains
     included): chain (r, f) holds the frames f, f + lag, ... of trajectory r.  They are the trajectory lengths that label_runs
@@ -3710,12 +3762,23 @@ class HiddenMarkovModel:
     False and a .message.  A hidden state with zero expected occupancy keeps its previous row and sets degenerate = True.  The
     loop stops when the log-likelihood changes by less than `accuracy` (converged = True; the parameters are those the last
     log-likelihood was computed with) or after max_iter E-steps.  Afterwards the hidden states are renumbered by decreasing
-    stationary probability, the lower index winning a tie.
+    stationary probability, the lower index winning a tie (fit(..., renumber=False) keeps them in the order of `initial`).
+
+    m_step="host" is the above.  m_step="device": the whole loop runs on the GPU (dff_hmm_fit_steps through hmm_fit_solver), in
+    calls of min(steps_per_sync, max_iter - n_iter) iterations with ONE read-back each; the M-step is the call's fixed-order
+    statement, its reversible estimator swept to rev_tol or rev_max_sweeps sweeps.  The same attributes and messages, equal to
+    the host path's up to the rounding of the two M-steps; log_likelihoods are the finite entries the calls returned, and
+    rev_sweeps (the estimator's sweeps, all M-steps together) and rev_unconverged (an M-step spent rev_max_sweeps) are set.
 
     transition_matrix (m, m), observation_probabilities (m, K), initial_distribution (m,), stationary_distribution (m,),
     log_likelihoods (one per E-step), n_iter, converged, degenerate, message."""
 
-    def __init__(self, n_hidden, lagtime, reversible=True, accuracy=1e-3, max_iter=1000, *, device="cuda:0"):
+    M_STEPS = ("host", "device")
+    MESSAGES = {1: "a parameter became non-finite or negative", 2: "a chain has likelihood zero under the model", 3: "a label >= n_states"}
+    LOST = "the reversible estimator's active set lost a hidden state"
+
+    def __init__(self, n_hidden, lagtime, reversible=True, accuracy=1e-3, max_iter=1000, *, device="cuda:0", m_step="host",
+                 steps_per_sync=32, rev_tol=1e-12, rev_max_sweeps=1_000_000):
         self.n_hidden, self.lagtime = int(n_hidden), int(lagtime)
         if self.n_hidden != n_hidden or not 1 <= self.n_hidden <= HMM_MAX_HIDDEN:
             raise ValueError(f"HiddenMarkovModel: n_hidden must be an integer in 1..{HMM_MAX_HIDDEN}")
@@ -3724,10 +3787,17 @@ class HiddenMarkovModel:
         self.reversible, self.accuracy, self.max_iter = bool(reversible), float(accuracy), int(max_iter)
         if not self.accuracy > 0 or self.max_iter < 1:
             raise ValueError("HiddenMarkovModel: accuracy must be > 0 and max_iter >= 1")
+        if m_step not in self.M_STEPS:
+            raise ValueError('HiddenMarkovModel: m_step must be "host" or "device"')
+        self.m_step, self.steps_per_sync = m_step, int(steps_per_sync)
+        self.rev_tol, self.rev_max_sweeps = float(rev_tol), int(rev_max_sweeps)
+        if self.steps_per_sync != steps_per_sync or self.steps_per_sync < 1 or not self.rev_tol > 0 or self.rev_max_sweeps < 1:
+            raise ValueError("HiddenMarkovModel: steps_per_sync and rev_max_sweeps must be integers >= 1 and rev_tol > 0")
         self.device = torch.device(device)
         self.transition_matrix = self.observation_probabilities = self.initial_distribution = None
         self.stationary_distribution = None
         self.log_likelihoods, self.n_iter, self.converged, self.degenerate, self.message = [], 0, False, False, ""
+        self.rev_sweeps, self.rev_unconverged = 0, False
         self._estep = None
 
     def _check_parameters(self, A, B, p0, K):
@@ -3761,20 +3831,47 @@ class HiddenMarkovModel:
         An = np.where(rows[:, None] > 0, xi / np.where(rows > 0, rows, 1.0)[:, None], A)
         return An, Bn, pn, None
 
-    def fit(self, labels, traj_lengths=None, n_states=None, initial=None):
+    def _fit_device(self, lab, lengths, A, B, p0):
+        """the loop of fit() through hmm_fit_solver -> (A, B, p0, pi | None)"""
+        solver = hmm_fit_solver(self.device)
+        state = pi = None
+        while self.n_iter < self.max_iter:
+            n = min(self.steps_per_sync, self.max_iter - self.n_iter)
+            A, B, p0, ll, got, state = solver.steps(lab, lengths, self.lagtime, A, B, p0, self.reversible, n, self.accuracy, state,
+                                                    rev_tol=self.rev_tol, rev_max_sweeps=self.rev_max_sweeps)
+            pi = got if got is not None else pi
+            self.log_likelihoods.extend(float(v) for v in ll if np.isfinite(v))
+            self.n_iter = int(state["n_estep"])
+            if state["stop"]:
+                break
+        if state is not None:
+            self.converged = state["stop"] == 1
+            self.degenerate, self.rev_unconverged = bool(state["flags"] & 1), bool(state["flags"] & 2)
+            self.rev_sweeps = int(state["rev_sweeps"])
+            if state["stop"] == 2:
+                self.message = self.MESSAGES.get(state["estep_status"], f"status {state['estep_status']}")
+            elif state["stop"] == 3:
+                self.message = self.LOST
+        return A, B, p0, pi
+
+    def fit(self, labels, traj_lengths=None, n_states=None, initial=None, renumber=True):
         lab, lengths, K = _hmm_labels(labels, traj_lengths, n_states, self.device, "HiddenMarkovModel")
         if initial is None:
             initial = initial_hmm(lab, self.lagtime, self.n_hidden, lengths, K, device=self.device)
         A, B, p0 = self._check_parameters(*initial, K)
-        self._estep = estep = hmm_estep_solver(self.device)
         self.log_likelihoods, self.n_iter, self.converged, self.degenerate, self.message = [], 0, False, False, ""
+        self.rev_sweeps, self.rev_unconverged = 0, False
         pi = None
+        if self.m_step == "device":
+            self._estep = None
+            A, B, p0, pi = self._fit_device(lab, lengths, A, B, p0)
+            return self._finish(A, B, p0, pi, renumber)
+        self._estep = estep = hmm_estep_solver(self.device)
         while self.n_iter < self.max_iter:
             stats, _, _, status = estep(lab, lengths, self.lagtime, A, B, p0)
             self.n_iter += 1
             if status:
-                self.message = {1: "a parameter became non-finite or negative", 2: "a chain has likelihood zero under the model",
-                                3: "a label >= n_states"}.get(status, f"status {status}")
+                self.message = self.MESSAGES.get(status, f"status {status}")
                 break
             self.log_likelihoods.append(float(stats[0]))
             if len(self.log_likelihoods) > 1 and abs(self.log_likelihoods[-1] - self.log_likelihoods[-2]) < self.accuracy:
@@ -3782,14 +3879,17 @@ class HiddenMarkovModel:
                 break
             nxt = self._m_step(A, B, p0, stats)
             if nxt is None:
-                self.message = "the reversible estimator's active set lost a hidden state"
+                self.message = self.LOST
                 break
             A, B, p0, pi = nxt
+        return self._finish(A, B, p0, pi, renumber)
+
+    def _finish(self, A, B, p0, pi, renumber):
         if pi is None or not self.reversible:
             w, v = np.linalg.eig(A.T)
             pi = np.abs(np.real(v[:, np.argmax(np.real(w))]))
             pi = pi / pi.sum()
-        order = np.argsort(-pi, kind="stable")
+        order = np.argsort(-pi, kind="stable") if renumber else np.arange(len(pi))
         self.transition_matrix = A[np.ix_(order, order)]
         self.observation_probabilities, self.initial_distribution = B[order], p0[order]
         self.stationary_distribution = pi[order]
@@ -3867,6 +3967,103 @@ class HiddenMarkovModel:
         return (path, logprob) if return_log_probabilities else path
 
 
+# ---- bootstrap error bars of a hidden Markov model: the labels resampled over trajectories or blocks, a device fit per resample ----
+# What resampling_units' comment says holds here too: the discretisation is fixed, and blocks shorter than the slowest
+# relaxation understate the error.  A block is a trajectory of its own, so it must hold chains of two frames at least.
+def resampled_labels(labels, unit_lengths, weights_row):
+    """The labels of one resample -> (labels' on the device of `labels`, lengths' int64): unit u (unit_lengths[u] frames, the
+    units back to back over `labels`) appears weights_row[u] times, unit-major in unit order, a unit's copies adjacent, every
+    copy a trajectory of its own (an empty unit gives empty trajectories).  The index is built on the host; the labels move by
+    ONE gather on their device."""
+    lab = torch.as_tensor(labels).reshape(-1)
+    ul = np.asarray(unit_lengths, np.int64).reshape(-1)
+    w = np.asarray(weights_row).reshape(-1)
+    if w.shape != ul.shape or (ul < 0).any() or (w < 0).any() or int(ul.sum()) != int(lab.numel()):
+        raise ValueError("resampled_labels: one non-negative weight per unit, the units' lengths summing to the number of labels")
+    w = w.astype(np.int64)
+    starts = np.cumsum(ul) - ul
+    lengths = np.repeat(ul, w)
+    first = np.repeat(starts, w)
+    index = np.repeat(first - (np.cumsum(lengths) - lengths), lengths) + np.arange(int(lengths.sum()), dtype=np.int64)
+    return lab.index_select(0, torch.from_numpy(index).to(lab.device)), lengths
+
+
+class HmmBootstrap:
+    """What bootstrap_hmm returns, B resamples of a model of m hidden states, the states in the point model's order:
+    timescales (B, m - 1) and lifetimes (B, m) in frames, stationary (B, m), transition_matrices (B, m, m), log_likelihood (the
+    last one), n_iter and converged (B,); the rows of a resample whose fit failed (the E-step failed, or the reversible
+    estimator lost a hidden state) are NaN and `failed` (B,) is True there.  weights (B, n_units) and unit_lengths as
+    resampled; point: the HiddenMarkovModel of the unresampled labels."""
+
+    NAMES = ("timescales", "lifetimes", "stationary")
+
+    def __init__(self, timescales, lifetimes, stationary, transition_matrices, log_likelihood, n_iter, converged, failed, weights,
+                 unit_lengths, point):
+        self.timescales, self.lifetimes, self.stationary = timescales, lifetimes, stationary
+        self.transition_matrices, self.log_likelihood, self.n_iter = transition_matrices, log_likelihood, n_iter
+        self.converged, self.failed, self.weights, self.unit_lengths, self.point = converged, failed, weights, unit_lengths, point
+
+    @property
+    def n_failed(self):
+        """Resamples whose fit failed (NaN rows)."""
+        return int(np.sum(self.failed))
+
+    def _values(self, name):
+        if name not in self.NAMES:
+            raise ValueError(f"HmmBootstrap: name must be one of {self.NAMES}")
+        return getattr(self, name)
+
+    def std(self, name="timescales"):
+        """Standard deviation (ddof = 1) of every column of `name` over the resamples where it is finite; NaN below two."""
+        return percentile_std(self._values(name))
+
+    def interval(self, name="timescales", confidence=0.95):
+        """The percentile interval (lo, hi) of every column of `name` over the resamples where it is finite."""
+        return percentile_interval(self._values(name), confidence)
+
+
+def bootstrap_hmm(labels, lagtime, n_hidden, traj_lengths=None, n_states=None, *, n_resamples=100, block_frames=None, seed=0,
+                  weights=None, reversible=True, accuracy=1e-3, max_iter=1000, steps_per_sync=32, point=None, device="cuda:0"):
+    """Bootstrap of a HiddenMarkovModel at `lagtime`: the units of resampling_units(traj_lengths, block_frames) are drawn with
+    replacement n_resamples times (bootstrap_weights(n_units, n_resamples, seed), or `weights` (B, n_units)); every resample
+    is HiddenMarkovModel(m_step="device").fit(*resampled_labels(...), initial=the point model's parameters, renumber=False):
+    warm-started, so its hidden states keep the point model's identity.  The resamples run one after the other.  point: a
+    fitted HiddenMarkovModel of these labels, default HiddenMarkovModel(m_step="device").fit(labels, ...).  block_frames below
+    2 lagtime is refused: such a block has no chain of two frames -> HmmBootstrap."""
+    dev = torch.device(device)
+    settings = dict(reversible=reversible, accuracy=accuracy, max_iter=max_iter, device=dev, m_step="device", steps_per_sync=steps_per_sync)
+    proto = HiddenMarkovModel(n_hidden, lagtime, **settings)                                       # checks the settings
+    if block_frames is not None and int(block_frames) < 2 * proto.lagtime:
+        raise ValueError("bootstrap_hmm: block_frames must be at least 2 lagtime")
+    lab, lengths, K = _hmm_labels(labels, traj_lengths, n_states, dev, "bootstrap_hmm")
+    units = resampling_units(lengths, block_frames)
+    if units.size < 1:
+        raise ValueError("bootstrap_hmm: no resampling units (no frames)")
+    if weights is None:
+        w = bootstrap_weights(units.size, n_resamples, seed)
+    else:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[1] != units.size or w.shape[0] < 1 or (w < 0).any() or (w > 2 ** 32 - 1).any():
+            raise ValueError(f"bootstrap_hmm: weights must be (B, {units.size}) multiplicities in 0 .. 2^32 - 1")
+        w = w.astype(np.uint32)
+    if point is None:
+        point = proto.fit(lab, lengths, K)
+    elif point.transition_matrix is None or point.n_hidden != proto.n_hidden or point.observation_probabilities.shape[1] != K:
+        raise ValueError("bootstrap_hmm: point must be a fitted HiddenMarkovModel of n_hidden states on n_states symbols")
+    start = (point.transition_matrix, point.observation_probabilities, point.initial_distribution)
+    B, m = int(w.shape[0]), proto.n_hidden
+    nan = np.nan
+    ts, life, stat, T = np.full((B, m - 1), nan), np.full((B, m), nan), np.full((B, m), nan), np.full((B, m, m), nan)
+    ll, n_iter, converged, failed = np.full(B, nan), np.zeros(B, np.int64), np.zeros(B, bool), np.zeros(B, bool)
+    for b in range(B):
+        model = HiddenMarkovModel(n_hidden, lagtime, **settings).fit(*resampled_labels(lab, units, w[b]), K, initial=start, renumber=False)
+        n_iter[b], converged[b], failed[b] = model.n_iter, model.converged, bool(model.message)
+        if not failed[b]:
+            ts[b], life[b], stat[b], T[b] = model.timescales(), model.lifetimes(), model.stationary_distribution, model.transition_matrix
+            ll[b] = model.log_likelihoods[-1] if model.log_likelihoods else nan
+    return HmmBootstrap(ts, life, stat, T, ll, n_iter, converged, failed, w, units, point)
+
+
 class HmmEvaluator(_TrajectoryEvaluator):
     """The metastable states of the sampled dynamics and their kinetics.  Frames -> TIC projection and k-means microstates
     (`tica`, n_microstates, centers, seed: as for MsmEvaluator) -> a HiddenMarkovModel of n_hidden states at `lagtime` (frames)
@@ -3889,13 +4086,21 @@ class HmmEvaluator(_TrajectoryEvaluator):
     separately decoded chains.  path="viterbi": .hidden holds the Viterbi path (HiddenMarkovModel.viterbi) in frame order, and
     .dwell = dwell_summary(label_runs(the path in chain order, hmm_chain_lengths(traj_lengths, lagtime)), frame_time *
     lagtime): dwells and events are taken INSIDE the chains, not across the interleave, one step of a chain being lagtime
-    frames.  eval()'s dict is the same either way."""
+    frames.  eval()'s dict is the same either way.
+
+    n_bootstrap > 0 adds error bars from bootstrap_hmm(n_resamples=n_bootstrap, block_frames, seed=bootstrap_seed, point=the
+    fitted model) to every ensemble's dict, in units of frame_time and in the order of the model's hidden states:
+      timescales_std, lifetimes_std, hidden_populations_std   standard deviations over the resamples
+      timescales_lo, timescales_hi                             the 95 % percentile interval
+      bootstrap_failed                                         resamples whose fit failed
+    The HmmBootstrap stays on .bootstrap under "samples" / "refs".  With n_bootstrap = 0 the dict is unchanged."""
 
     KEYS = ("timescales", "hidden_populations", "lifetimes", "n_iter", "converged", "loglik_per_frame", "samples_nonfinite")
+    BOOTSTRAP_KEYS = ("timescales_std", "lifetimes_std", "hidden_populations_std", "timescales_lo", "timescales_hi", "bootstrap_failed")
 
     def __init__(self, mol_name, tica, n_microstates=200, n_hidden=2, lagtime=None, frame_time=1.0, ref_data=None,
                  ref_traj_lengths=None, centers=None, seed=0, *, reversible=True, accuracy=1e-3, max_iter=1000, path="posterior",
-                 device="cuda:0"):
+                 n_bootstrap=0, block_frames=None, bootstrap_seed=0, device="cuda:0"):
         what = "HmmEvaluator"
         super().__init__(what, mol_name, frame_time, device)
         if path not in ("posterior", "viterbi"):
@@ -3908,6 +4113,12 @@ class HmmEvaluator(_TrajectoryEvaluator):
             raise ValueError(f"{what}: n_hidden must be an integer in 1..{HMM_MAX_HIDDEN}")
         self._hmm = dict(reversible=reversible, accuracy=accuracy, max_iter=max_iter)
         HiddenMarkovModel(self.n_hidden, self.lagtime, device="cpu", **self._hmm)       # its argument checks, now
+        self.n_bootstrap, self.block_frames, self.bootstrap_seed = int(n_bootstrap), block_frames, bootstrap_seed
+        if self.n_bootstrap != n_bootstrap or self.n_bootstrap < 0:
+            raise ValueError(f"{what}: n_bootstrap must be an integer >= 0")
+        if block_frames is not None and (int(block_frames) != block_frames or int(block_frames) < 2 * self.lagtime):
+            raise ValueError(f"{what}: block_frames must be an integer >= 2 lagtime")
+        self.bootstrap = {}
         self.mean, self.coeff = _tica_model(tica, what, TICA_MAX_DIM)
         self._micro = _Microstates(what, n_microstates, self.coeff.shape[1], centers, seed, self.device)
         self.n_microstates = self._micro.n_microstates
@@ -3943,7 +4154,22 @@ class HmmEvaluator(_TrajectoryEvaluator):
             runs, step = label_runs(hidden, lengths, device=self.device), self.frame_time
         self.models[name], self.labels[name], self.hidden[name] = model, labels.cpu().numpy(), hidden.cpu().numpy()
         self.dwell[name] = dwell_summary(runs, step)
-        return self.summarize(model, int(labels.numel()), self.frame_time, int((labels < 0).sum()))
+        res = self.summarize(model, int(labels.numel()), self.frame_time, int((labels < 0).sum()))
+        if self.n_bootstrap:
+            bs = bootstrap_hmm(labels, self.lagtime, self.n_hidden, lengths, self.n_microstates, n_resamples=self.n_bootstrap,
+                               block_frames=self.block_frames, seed=self.bootstrap_seed, point=model, device=self.device, **self._hmm)
+            self.bootstrap[name] = bs
+            res.update(self.error_bars(bs, self.frame_time))
+        return res
+
+    @staticmethod
+    def error_bars(bs, frame_time=1.0):
+        """the keys n_bootstrap adds, from an HmmBootstrap: numpy only"""
+        lo, hi = bs.interval("timescales", 0.95)
+        scaled = lambda v: [float(x) * frame_time for x in v]     # noqa: E731
+        return {"timescales_std": scaled(bs.std("timescales")), "lifetimes_std": scaled(bs.std("lifetimes")),
+                "hidden_populations_std": [float(x) for x in bs.std("stationary")], "timescales_lo": scaled(lo),
+                "timescales_hi": scaled(hi), "bootstrap_failed": float(bs.n_failed)}
 
     def _compare(self, res, ref):
         res["log10_timescale_ratio"] = _log10_ratio(res["timescales"], ref["timescales"])
