@@ -1,6 +1,6 @@
 """What the test modules share that is not an oracle (those are in oracle/): the device fixture and the lazy accessors of
 the package, the upload helpers, the constants and bars that more than one file holds a kernel to, and the assertions on
-top of them.  Fixtures are imported by name (`from support import dev  # noqa: F401`).  Pytest does not rewrite the
+top of them (refused, same_bits among them).  The host stand-ins that go behind evaluate's seams are in tests/standins.py.  Fixtures are imported by name (`from support import dev  # noqa: F401`).  Pytest does not rewrite the
 asserts of this module, so each of them carries the values it compares in its message."""
 import argparse
 import pickle
@@ -42,6 +42,22 @@ def B():
 def ev():
     from dff_amd import evaluate
     return evaluate
+
+
+def hmm_chunk():
+    """frames of a chain per chunk of the hidden-Markov-model kernels, read from the library"""
+    return B().hmm_chunk()
+
+
+def refused(lib, rc, what):
+    """the ABI call returned DFF_EINVAL and dff_last_error() says `what`"""
+    assert rc == 1, (rc, what)
+    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def up(a, dev):

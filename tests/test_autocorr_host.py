@@ -15,15 +15,11 @@ import torch
 import dff_amd
 from dff_amd import binding, evaluate
 from oracle.autocorr import Acf, estimate, lagged_sums
+from support import refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_autocorr_workspace_bytes", "dff_autocorr")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what                                                 # DFF_EINVAL
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals

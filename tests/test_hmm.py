@@ -30,20 +30,11 @@ import hmm_cases as hc
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
 ids = lambda c: "m%d-K%d-lag%d%s" % (c[0], c[1], c[2], "-disjoint" if c[3] else "")     # noqa: E731
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def chunk():
-    return B().hmm_chunk()
 
 
 def estep(labels, lengths, lag, A, B_, p0, post=True, chain_loglik=True, ws_fill=0xFF):
@@ -74,7 +65,7 @@ def assert_within_bars(got, ref, what):
 # ---------------------------------------------------------------- 1. every output under its bar
 @pytest.mark.parametrize("case", hc.CASES, ids=ids)
 def test_every_output_is_as_close_to_the_truth_as_numpy(case, dev):
-    ref = hc.reference(*case, chunk())
+    ref = hc.reference(*case, hmm_chunk())
     got = estep(ref["labels"], ref["lengths"], ref["lag"], ref["A"], ref["B"], ref["p0"])
     assert got["status"] == 0 and not np.isnan(got["stats"]).any() and not np.isnan(got["post"]).any()
     assert not np.isnan(got["chain_loglik"]).any()
@@ -87,9 +78,9 @@ def test_every_output_is_as_close_to_the_truth_as_numpy(case, dev):
 @pytest.mark.parametrize("case", [(3, 5, 3, False), (8, 1024, 1, False), (2, 5, 1, True), (8, 1024, 7, True)], ids=ids)
 def test_missing_observations_follow_the_oracles_rule(case, dev):
     m, K, lag, disjoint = case
-    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, disjoint, chunk())
-    lab = hc.with_missing(labels, lengths, lag, chunk(), seed=m)
-    ref = hc.reference_of(lab, lengths, lag, A, B_, p0, chunk())
+    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, disjoint, hmm_chunk())
+    lab = hc.with_missing(labels, lengths, lag, hmm_chunk(), seed=m)
+    ref = hc.reference_of(lab, lengths, lag, A, B_, p0, hmm_chunk())
     got = estep(lab, lengths, lag, A, B_, p0)
     assert got["status"] == 0 and not np.isnan(got["stats"]).any() and not np.isnan(got["post"]).any()
     assert_within_bars(got, ref, "missing " + ids(case))
@@ -98,7 +89,7 @@ def test_missing_observations_follow_the_oracles_rule(case, dev):
 
 # ---------------------------------------------------------------- 3. closed forms
 def test_one_hidden_state_has_a_closed_form(dev):
-    Cn = chunk()
+    Cn = hmm_chunk()
     lengths = [2 * Cn + 1, 0, 1, Cn]
     K = 7
     rng = np.random.default_rng(3)
@@ -116,7 +107,7 @@ def test_one_hidden_state_has_a_closed_form(dev):
 
 
 def test_identical_emission_rows_give_back_the_propagated_prior(dev):
-    Cn = chunk()
+    Cn = hmm_chunk()
     A = np.array([[0.875, 0.125], [0.25, 0.75]])                    # dyadic: the rows sum to 1 exactly, also in long double
     p0 = np.array([0.25, 0.75])
     B_ = np.tile(np.random.default_rng(5).uniform(0.1, 1.0, (1, 6)), (2, 1))
@@ -136,7 +127,7 @@ def test_identical_emission_rows_give_back_the_propagated_prior(dev):
 
 # ---------------------------------------------------------------- 4. bit identities
 def test_the_call_repeats_itself_on_any_workspace(dev):
-    ref = hc.reference(3, 5, 7, False, chunk())
+    ref = hc.reference(3, 5, 7, False, hmm_chunk())
     args = (ref["labels"], ref["lengths"], ref["lag"], ref["A"], ref["B"], ref["p0"])
     a, b, c = estep(*args), estep(*args), estep(*args, ws_fill=0x00)
     for k in ("stats", "chain_loglik", "post"):
@@ -146,7 +137,7 @@ def test_the_call_repeats_itself_on_any_workspace(dev):
 
 
 def test_a_chain_does_not_depend_on_the_other_chains(dev):
-    m, K, lag, Cn = 3, 5, 3, chunk()
+    m, K, lag, Cn = 3, 5, 3, hmm_chunk()
     labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, Cn)
     base = estep(labels, lengths, lag, A, B_, p0)
     perm = np.random.default_rng(2).permutation(len(lengths))
@@ -161,7 +152,7 @@ def test_a_chain_does_not_depend_on_the_other_chains(dev):
 
 
 def test_lag_tau_is_lag_one_on_the_strided_sub_trajectories(dev):
-    m, K, lag, Cn = 8, 5, 7, chunk()
+    m, K, lag, Cn = 8, 5, 7, hmm_chunk()
     A, B_, p0 = hc.model(m, K)
     n = lag * (2 * Cn + 1) + 3
     labels = np.random.default_rng(9).integers(0, K, n).astype(np.int32)
@@ -177,7 +168,7 @@ def test_lag_tau_is_lag_one_on_the_strided_sub_trajectories(dev):
 
 # ---------------------------------------------------------------- 5. status
 def test_status_and_nan_outputs(dev):
-    m, K, lag, Cn = 2, 5, 1, chunk()
+    m, K, lag, Cn = 2, 5, 1, hmm_chunk()
     labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, Cn)
     assert estep(labels, lengths, lag, A, B_, p0)["status"] == 0
 
@@ -205,10 +196,45 @@ def test_status_and_nan_outputs(dev):
     assert empty["status"] == 0 and (empty["stats"] == 0.0).all() and (empty["chain_loglik"] == 0.0).all()
 
 
+def test_the_debug_stages_stop_where_they_say(dev):
+    """dff_debug_hmm_stages(s) stops the call after the parameters, the chunk products, the carries, the apply pass, the emission
+    counts (s = 1 .. 5) and skips the finish launch.  Seen from outside: the carries write chain_loglik, the apply pass writes
+    post, and only the last two launches write stats and status.  The outputs hold a sentinel that no result equals (a
+    log-likelihood is <= 0, a posterior <= 1).  After the reset the call is the whole call again."""
+    m, K, lag, Cn = 3, 5, 2, hmm_chunk()
+    lengths = np.array([3 * Cn + 5, 0, 7], np.int64)
+    n = int(lengths.sum())
+    A, B_, p0 = hc.model(m, K)
+    labels = hc.simulate(A, B_, p0, lengths, seed=6)
+    before = estep(labels, lengths, lag, A, B_, p0)
+    par = [to_dev(x) for x in (A, B_, p0)]
+    lab = to_dev(labels)
+    ws = torch.empty(B().hmm_workspace_bytes(n, lengths, lag, m, K), dtype=torch.uint8, device="cuda")
+    try:
+        for s in range(1, 6):
+            out = {"stats": torch.full((1 + m * m + m + m * K,), 123.0, dtype=torch.float64, device="cuda"),
+                   "chain": torch.full((3 * lag,), 123.0, dtype=torch.float64, device="cuda"),
+                   "post": torch.full((n, m), 123.0, dtype=torch.float64, device="cuda"),
+                   "status": torch.full((1,), 0x7b7b7b7b, dtype=torch.int32, device="cuda")}
+            B().debug_hmm_stages(s)
+            raw("dff_hmm_estep", 0, ptr(lab), n, lengths.ctypes.data_as(C.c_void_p), 3, lag, ptr(par[0]), ptr(par[1]), ptr(par[2]), m, K,
+                ptr(out["stats"]), ptr(out["chain"]), ptr(out["post"]), ptr(out["status"]), ptr(ws), ws.numel(), stream_of(lab))
+            kept = {k: (v == (0x7b7b7b7b if k == "status" else 123.0)).cpu().numpy() for k, v in out.items()}
+            assert kept["stats"].all() and kept["status"].all(), s
+            assert kept["chain"].all() if s < 3 else not kept["chain"].any(), s
+            assert kept["post"].all() if s < 4 else not kept["post"].any(), s
+    finally:
+        B().debug_hmm_stages(0)
+    after = estep(labels, lengths, lag, A, B_, p0)
+    assert after["status"] == before["status"] == 0
+    for k in ("stats", "chain_loglik", "post"):
+        assert same_bits(after[k], before[k]), k
+
+
 # ---------------------------------------------------------------- 6. stream order
 def estep_spec():
     """three trajectories (one empty) at lag 2, every output written; poison: constant labels and NaN parameters"""
-    m, K, lag, Cn = 3, 5, 2, chunk()
+    m, K, lag, Cn = 3, 5, 2, hmm_chunk()
     A, B_, p0 = hc.model(m, K)
     lengths = np.array([2 * Cn + 5, 0, 3 * Cn], np.int64)
     n = int(lengths.sum())
@@ -241,7 +267,7 @@ class NumpyEstep:
     def __call__(self, labels, lengths, lag, A, B_, p0, want_post=False):
         lab = np.asarray(labels.cpu())
         if self.dtype is None:
-            stats, cl, post, status = hc.host_estep(lab, lengths, lag, A, B_, p0, chunk())
+            stats, cl, post, status = hc.host_estep(lab, lengths, lag, A, B_, p0, hmm_chunk())
         else:
             res = hc.sequential(lab, lengths, lag, A, B_, p0, self.dtype)
             stats, cl, post, status = hc.pack(res), np.asarray(res["chain_loglik"], np.float64), np.asarray(res["post"], np.float64), 0

@@ -22,7 +22,7 @@ import hmm_cases as hc
 import hmm_fit_cases as fc
 from oracle import msm as oracle
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +31,14 @@ STATE_FIELDS = ("n_estep", "stop", "estep_status", "flags", "last_loglik", "rev_
 TINY = 1e-300                                                       # an accuracy no pair of log-likelihoods meets
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def chunk():
-    return B().hmm_chunk()
-
-
 def weak(A):
     """the model's transition matrix pulled towards uniform: a diagonal of 0.86 at the most"""
     return 0.8 * A + 0.2 / len(A) if len(A) > 1 else A
 
 
 def case(m, K, lag):
-    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, chunk())
-    return hc.with_missing(labels, lengths, lag, chunk(), seed=m), lengths, weak(A), B_, p0
+    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, hmm_chunk())
+    return hc.with_missing(labels, lengths, lag, hmm_chunk(), seed=m), lengths, weak(A), B_, p0
 
 
 def fit_steps(labels, lengths, lag, A, B_, p0, reversible, n_steps, accuracy, state=None, ws_fill=0xFF, stationary=True, pi=None,
@@ -155,7 +146,7 @@ def test_a_converged_fit_is_frozen(dev):
 # ---------------------------------------------------------------- 4. kept rows, a lost state
 def test_a_state_that_emits_nothing_observed(dev):
     rng = np.random.default_rng(2)
-    lengths = [chunk() + 3, 0, 40]
+    lengths = [hmm_chunk() + 3, 0, 40]
     labels = rng.integers(0, 3, sum(lengths)).astype(np.int32)       # symbol 3 is never observed ...
     A = np.array([[0.8, 0.2], [0.3, 0.7]])
     B_ = np.array([[0.5, 0.25, 0.25, 0.0], [0.0, 0.0, 0.0, 1.0]])    # ... and it is all hidden state 1 emits
@@ -218,7 +209,7 @@ def test_the_sweep_cap_sets_its_flag_and_counts(dev):
 def fit_spec():
     """three trajectories (one empty) at lag 2, three reversible steps; poison: constant labels, NaN parameters and a state
     that says the fit has stopped"""
-    m, K, lag, Cn, steps = 3, 5, 2, chunk(), 3
+    m, K, lag, Cn, steps = 3, 5, 2, hmm_chunk(), 3
     A, B_, p0 = hc.model(m, K)
     lengths = np.array([2 * Cn + 5, 0, 3 * Cn], np.int64)
     n = int(lengths.sum())

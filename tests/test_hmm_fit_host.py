@@ -20,22 +20,14 @@ import dff_amd
 import hmm_cases as hc
 import hmm_fit_cases as fc
 from dff_amd import binding, evaluate
-from oracle import msm as oracle
+from standins import HostEstep, OracleSweeps
+from support import hmm_chunk, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
 MSTEP_MEASURED = 1.14e-15
 MSTEP_BAR = 10 * MSTEP_MEASURED
-
-
-def chunk():
-    return int(binding.load_library().dff_hmm_chunk())
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals
@@ -60,7 +52,7 @@ def test_header_library_and_binding_declare_the_calls():
 
 def test_refusals_before_any_device_call():
     lib = binding.load_library()
-    L = np.array([3 * chunk() + 5, 0, 7], np.int64)
+    L = np.array([3 * hmm_chunk() + 5, 0, 7], np.int64)
     n = int(L.sum())
     for lag, m, K in ((1, 1, 1), (3, 3, 5), (7, 8, 1024)):
         nstats = 1 + m * m + m + m * K
@@ -148,10 +140,10 @@ MSTEP_CASES = ((1, 1, 1), (2, 5, 1), (3, 5, 3), (4, 64, 1), (5, 1024, 3), (8, 10
 def test_the_statement_agrees_with_the_host_m_steps_formulas():
     worst = {}
     for m, K, lag in MSTEP_CASES:
-        labels, lengths, A, B, p0 = hc.case_inputs(m, K, lag, False, chunk())
-        lengths = [v for v in lengths if v <= lag * (2 * chunk() + 1) + 1]              # the chain of 20 chunks adds nothing here
+        labels, lengths, A, B, p0 = hc.case_inputs(m, K, lag, False, hmm_chunk())
+        lengths = [v for v in lengths if v <= lag * (2 * hmm_chunk() + 1) + 1]              # the chain of 20 chunks adds nothing here
         labels = labels[:sum(lengths)]
-        stats = hc.host_estep(labels, lengths, lag, A, B, p0, chunk())[0]
+        stats = hc.host_estep(labels, lengths, lag, A, B, p0, hmm_chunk())[0]
         assert not np.isnan(stats).any()
         for reversible in (False, True):
             got = fc.mstep(stats, A, B, p0, m, K, reversible, 1e-12, 1_000_000)
@@ -188,29 +180,10 @@ def test_kept_rows_lost_states_and_the_sweep_cap_in_the_statement():
 
 
 # ---------------------------------------------------------------- the Python layer on the stand-in
-class HostEstep:
-    def __init__(self, device):
-        pass
-
-    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
-        stats, cl, post, status = hc.host_estep(np.asarray(labels), lengths, lag, A, B, p0, chunk())
-        return stats, (cl if want_post else None), (torch.from_numpy(post) if want_post else None), status
-
-
-class OracleSweeps:
-    """the host path's reversible estimator (MarkovStateModel.fit_counts) on the oracle's numpy sweeps"""
-
-    def __init__(self, S, c, device):
-        self.S, self.c = np.array(S), np.array(c)
-
-    def __call__(self, x, n):
-        return oracle.sweeps(self.S, self.c, np.array(x), n)
-
-
 @pytest.fixture
 def on_host(monkeypatch):
     monkeypatch.setattr(evaluate, "reversible_sweeper", OracleSweeps)
-    Cn, seen = chunk(), {}
+    Cn, seen = hmm_chunk(), {}
 
     def estep(labels, lengths, lag, A, B, p0):
         """hc.host_estep, each distinct input computed once: fits that differ in steps_per_sync alone repeat their E-steps"""

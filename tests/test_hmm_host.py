@@ -11,26 +11,18 @@ import pytest
 import torch
 
 import dff_amd
-import eig_cases as ec
 import hmm_cases as hc
 import propagate_cases as pc
 from dff_amd import binding, evaluate
 from oracle import kinetics as kin
 from oracle import msm as oracle
+from standins import HostEstep, HostSpectral, OracleSweeps
+from support import hmm_chunk, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_hmm_chunk", "dff_hmm_plan", "dff_hmm_workspace_bytes", "dff_hmm_estep")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
-
-
-def chunk():
-    return int(binding.load_library().dff_hmm_chunk())
 
 
 # ---------------------------------------------------------------- symbols, plan and refusals
@@ -43,7 +35,7 @@ def test_symbols_in_header_binding_and_library():
         assert getattr(lib, name) is not None
     assert len(binding.SYMBOLS["dff_hmm_estep"][1]) == 18 and len(binding.SYMBOLS["dff_hmm_workspace_bytes"][1]) == 6
     assert "#define DFF_HMM_MAXM 8" in header and binding.HMM_MAX_HIDDEN == evaluate.HMM_MAX_HIDDEN == 8
-    assert chunk() in (64, 128, 256, 512)
+    assert hmm_chunk() in (64, 128, 256, 512)
     text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
     assert '#include "dff_hmm.hip"' in text
     build = open(os.path.join(ROOT, "build.sh")).read()
@@ -51,7 +43,7 @@ def test_symbols_in_header_binding_and_library():
 
 
 def test_the_plan_counts_chains_and_chunks():
-    Cn = chunk()
+    Cn = hmm_chunk()
     cases = [([], 1), ([0], 1), ([0, 0], 5), ([1], 1), ([1], 7), ([5, 3], 7),                       # a lag longer than every trajectory
              ([Cn], 1), ([2 * Cn], 1), ([2 * Cn], 2), ([3 * Cn, 0, 3 * Cn + 1, 3 * Cn - 1], 3),   # exact multiples of the chunk
              (hc.lengths_for(1, Cn), 1), (hc.lengths_for(3, Cn), 3), (hc.lengths_for(7, Cn), 7), ([Cn + 1] * 80, 10)]
@@ -66,7 +58,7 @@ def test_the_plan_counts_chains_and_chunks():
 
 def test_workspace_bytes_and_refusals_before_any_device_call():
     lib = binding.load_library()
-    Cn = chunk()
+    Cn = hmm_chunk()
     L = np.array([3 * Cn + 5, 0, 7], np.int64)
     n = int(L.sum())
 
@@ -112,6 +104,33 @@ def test_workspace_bytes_and_refusals_before_any_device_call():
         binding.hmm_estep(torch.zeros(4, dtype=torch.int32), [4], 1, z(2, 2), z(2, 3), z(2))
 
 
+def test_every_entry_point_names_itself_and_refuses_the_shape_first():
+    """the six hidden-Markov-model entry points share their first checks: each refusal starts with the name of the entry point
+    that gave it, and of two faults (m = 0 and lag = 0) the shape is the one that is told"""
+    lib = binding.load_library()
+    L = np.array([5, 0, 7], np.int64)
+    n, K, big = int(L.sum()), 4, 1 << 30
+
+    def sizes(name):
+        return lambda lag, m: getattr(lib, "dff_" + name)(n, p(L), len(L), lag, m, K)
+    calls = {
+        "hmm_workspace_bytes": sizes("hmm_workspace_bytes"),
+        "hmm_estep": lambda lag, m: lib.dff_hmm_estep(0, FAKE, n, p(L), len(L), lag, FAKE, FAKE, FAKE, m, K, FAKE, None, None, FAKE, FAKE,
+                                                      big, None),
+        "hmm_fit_workspace_bytes": sizes("hmm_fit_workspace_bytes"),
+        "hmm_fit_steps": lambda lag, m: lib.dff_hmm_fit_steps(0, FAKE, n, p(L), len(L), lag, FAKE, FAKE, FAKE, m, K, 0, 1, 1e-3, 1e-12, 100,
+                                                              FAKE, None, FAKE, FAKE, big, None),
+        "hmm_viterbi_workspace_bytes": sizes("hmm_viterbi_workspace_bytes"),
+        "hmm_viterbi": lambda lag, m: lib.dff_hmm_viterbi(0, FAKE, n, p(L), len(L), lag, FAKE, FAKE, FAKE, m, K, FAKE, 0, None, FAKE, FAKE,
+                                                          big, None),
+    }
+    for name, call in calls.items():
+        refusal = -1 if name.endswith("_workspace_bytes") else 1
+        for (lag, m), text in (((0, 2), "lag must be >= 1"), ((0, 0), "the number of hidden states must be 1..8")):
+            assert call(lag, m) == refusal, (name, lag, m)
+            assert lib.dff_last_error().decode() == f"{name}: {text}", (name, lag, m, lib.dff_last_error().decode())
+
+
 def test_package_reexports():
     for name in ("hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator"):
         assert getattr(dff_amd, name) is getattr(evaluate, name) and name in dff_amd.__all__
@@ -122,7 +141,7 @@ def test_package_reexports():
 # ---------------------------------------------------------------- the chunked formulation against the truth
 @pytest.mark.parametrize("case", hc.CASES, ids=lambda c: "m%d-K%d-lag%d%s" % (c[0], c[1], c[2], "-disjoint" if c[3] else ""))
 def test_the_chunked_formulation_is_as_close_to_the_truth_as_the_sequential_one(case):
-    ref = hc.reference(*case, chunk())
+    ref = hc.reference(*case, hmm_chunk())
     for k in hc.OUTPUTS:
         assert ref["e_chunked"][k] <= hc.FACTOR * max(ref["e_seq"][k], 1.0), (k, ref["e_chunked"][k], ref["e_seq"][k])
     truth = ref["truth"]
@@ -134,7 +153,7 @@ def test_the_chunked_formulation_is_as_close_to_the_truth_as_the_sequential_one(
 
 
 def test_missing_observations_and_the_status_rules_of_the_stand_in():
-    m, K, lag, Cn = 3, 5, 3, chunk()
+    m, K, lag, Cn = 3, 5, 3, hmm_chunk()
     labels, lengths, A, B, p0 = hc.case_inputs(m, K, lag, False, Cn)
     lab = hc.with_missing(labels, lengths, lag, Cn)
     ref = hc.reference_of(lab, lengths, lag, A, B, p0, Cn)
@@ -164,34 +183,6 @@ def test_missing_observations_and_the_status_rules_of_the_stand_in():
 
 
 # ---------------------------------------------------------------- the Python layer on a stand-in
-class HostEstep:
-    calls = 0
-
-    def __init__(self, device):
-        pass
-
-    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
-        HostEstep.calls += 1
-        stats, cl, post, status = hc.host_estep(np.asarray(labels), lengths, lag, A, B, p0, binding.hmm_chunk())
-        return stats, (cl if want_post else None), (torch.from_numpy(post) if want_post else None), status
-
-
-class HostSpectral:
-    def __init__(self, device):
-        pass
-
-    def __call__(self, a, ks, k, vectors):
-        return ec.host_topk(np.asarray(a), ks, k, vectors)
-
-
-class OracleSweeps:
-    def __init__(self, S, c, device):
-        self.S, self.c = np.array(S), np.array(c)
-
-    def __call__(self, x, n):
-        return oracle.sweeps(self.S, self.c, np.array(x), n)
-
-
 @pytest.fixture
 def on_host(monkeypatch):
     monkeypatch.setattr(evaluate, "reversible_sweeper", OracleSweeps)
@@ -302,7 +293,7 @@ def test_reversible_fit_degenerate_states_and_failures(on_host):
 
 # ---------------------------------------------------------------- the evaluator
 def test_the_evaluator_checks_its_arguments_and_fills_its_keys(on_host, monkeypatch):
-    Cn = chunk()
+    Cn = hmm_chunk()
     monkeypatch.setattr(binding, "load_library", lambda *a, **k: None)
     monkeypatch.setattr(binding, "hmm_chunk", lambda: Cn)
     monkeypatch.setattr(evaluate, "_frames", lambda x, device: torch.as_tensor(np.asarray(x, np.float64)))

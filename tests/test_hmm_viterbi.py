@@ -27,20 +27,12 @@ import viterbi_cases as vc
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from standins import HostViterbi
+from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
 ids = lambda c: "m%d-K%d-lag%d%s" % (c[0], c[1], c[2], "-disjoint" if c[3] else "")     # noqa: E731
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def chunk():
-    return B().hmm_chunk()
 
 
 def viterbi(labels, lengths, lag, la, lb, lp, chain_order=False, chain_logprob=True, ws_fill=0xFF):
@@ -70,7 +62,7 @@ def assert_within_bars(got, ref, what):
 # ---------------------------------------------------------------- 1. exact inputs: the textbook recursion, bit for bit
 @pytest.mark.parametrize("case", hc.CASES, ids=ids)
 def test_integer_log_parameters_give_the_sequential_path_bit_for_bit(case, dev):
-    ref = vc.exact_reference(*case, chunk())
+    ref = vc.exact_reference(*case, hmm_chunk())
     assert (ref["labels"] < 0).any() and np.isfinite(ref["sequential"][1]).all()        # missing observations; no impossible chain
     got = call_ref(ref)
     assert got["status"] == 0 and got["path"].dtype == np.int32
@@ -86,7 +78,7 @@ def test_integer_log_parameters_give_the_sequential_path_bit_for_bit(case, dev):
                                                    (8, 1024, 7, True, True)],
                          ids=lambda c: ids(c) + ("-missing" if len(c) > 4 else ""))
 def test_general_inputs_sit_on_the_chunked_statement_and_under_the_bar(case, dev):
-    ref = vc.reference(*case[:4], chunk(), missing=len(case) > 4)
+    ref = vc.reference(*case[:4], hmm_chunk(), missing=len(case) > 4)
     got = call_ref(ref)
     assert got["status"] == 0 and got["path"].min(initial=0) >= 0 and got["path"].max(initial=0) < case[0]
     assert not np.isnan(got["chain_logprob"]).any()
@@ -98,7 +90,7 @@ def test_general_inputs_sit_on_the_chunked_statement_and_under_the_bar(case, dev
 
 # ---------------------------------------------------------------- 3. status and precedence
 def test_status_and_precedence(dev):
-    m, K, lag, Cn = 2, 5, 1, chunk()
+    m, K, lag, Cn = 2, 5, 1, hmm_chunk()
     labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, Cn)
     la, lb, lp = vc.log_model(A, B_, p0)
     assert viterbi(labels, lengths, lag, la, lb, lp)["status"] == 0
@@ -138,7 +130,7 @@ def test_status_and_precedence(dev):
 
 # ---------------------------------------------------------------- 4. bit identities
 def test_the_call_repeats_itself_on_any_workspace(dev):
-    ref = vc.reference(3, 5, 7, False, chunk())
+    ref = vc.reference(3, 5, 7, False, hmm_chunk())
     a, b, c = call_ref(ref), call_ref(ref), call_ref(ref, ws_fill=0x00)
     for k in ("path", "chain_logprob"):
         assert same_bits(a[k], b[k]) and same_bits(a[k], c[k]), k
@@ -148,14 +140,14 @@ def test_the_call_repeats_itself_on_any_workspace(dev):
 
 def test_chain_order_is_the_stated_permutation(dev):
     for case in ((3, 5, 7, False), (8, 1024, 3, True), (2, 5, 1, False)):
-        ref = vc.reference(*case, chunk())
+        ref = vc.reference(*case, hmm_chunk())
         frame, chain = call_ref(ref), call_ref(ref, chain_order=True)
         assert same_bits(chain["path"], frame["path"][vc.chain_order(ref["lengths"], ref["lag"])])
         assert same_bits(chain["chain_logprob"], frame["chain_logprob"])
 
 
 def test_a_chain_does_not_depend_on_the_other_chains(dev):
-    m, K, lag, Cn = 3, 5, 3, chunk()
+    m, K, lag, Cn = 3, 5, 3, hmm_chunk()
     labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, False, Cn)
     par = vc.log_model(A, B_, p0)
     base = viterbi(labels, lengths, lag, *par)
@@ -171,7 +163,7 @@ def test_a_chain_does_not_depend_on_the_other_chains(dev):
 
 
 def test_lag_tau_is_lag_one_on_the_strided_sub_trajectories(dev):
-    m, K, lag, Cn = 8, 5, 7, chunk()
+    m, K, lag, Cn = 8, 5, 7, hmm_chunk()
     par = vc.log_model(*hc.model(m, K))
     n = lag * (2 * Cn + 1) + 3
     labels = np.random.default_rng(9).integers(0, K, n).astype(np.int32)
@@ -206,7 +198,7 @@ def test_one_hidden_state_has_a_closed_form(dev):
     parameters (every partial sum exact).  A longer chain with general parameters enters its later chunks with the carried
     delta, (lp + le_0) + P_0 + P_1 ..., the same terms in another association: there the value is held to the long-double sum
     under the rule of the other tests, and its distance to numpy's sum is printed."""
-    Cn = chunk()
+    Cn = hmm_chunk()
     lengths = [2 * Cn + 1, 0, 1, Cn, 20 * Cn]
     K = 7
     rng = np.random.default_rng(3)
@@ -237,18 +229,56 @@ def test_one_hidden_state_has_a_closed_form(dev):
 @pytest.mark.parametrize("case", [(3, 5, 1), (8, 1024, 3), (2, 5, 7)], ids=lambda c: "m%d-K%d-lag%d" % c)
 def test_disjoint_emissions_name_the_hidden_state(case, dev):
     m, K, lag = case
-    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, True, chunk())
-    lab = hc.with_missing(labels, lengths, lag, chunk(), seed=1)
+    labels, lengths, A, B_, p0 = hc.case_inputs(m, K, lag, True, hmm_chunk())
+    lab = hc.with_missing(labels, lengths, lag, hmm_chunk(), seed=1)
     got = viterbi(lab, lengths, lag, *vc.log_model(A, B_, p0))
     assert got["status"] == 0
     seen = lab >= 0
     assert (got["path"][seen] == lab[seen] % m).all() and (got["path"] >= 0).all() and (got["path"] < m).all()
 
 
+def test_the_debug_stages_stop_where_they_say(dev):
+    """dff_debug_hmm_viterbi_stages(s) stops the call after the parameters, the chunk products, the forward carries, the apply
+    pass, the backward carries, the backtrack (s = 1 .. 6) and skips the finish launch.  Seen from outside: the forward carries
+    write the chain_logprob of the chains without a frame, the apply pass that of the others, the backtrack writes the path, and
+    only the finish launch writes the status.  The outputs hold a sentinel that no result equals (a log-probability is <= 0, a
+    state < 8).  After the reset the call is the whole call again."""
+    m, K, lag, Cn = 3, 5, 2, hmm_chunk()
+    lengths = np.array([3 * Cn + 5, 0, 7], np.int64)
+    n = int(lengths.sum())
+    A, B_, p0 = hc.model(m, K)
+    labels = hc.simulate(A, B_, p0, lengths, seed=6)
+    la, lb, lp = vc.log_model(A, B_, p0)
+    before = viterbi(labels, lengths, lag, la, lb, lp)
+    par = [to_dev(x) for x in (la, lb, lp)]
+    lab = to_dev(labels)
+    ws = torch.empty(B().hmm_viterbi_workspace_bytes(n, lengths, lag, m, K), dtype=torch.uint8, device="cuda")
+    empty = np.array([len(c) == 0 for c in hc.chains(lengths.tolist(), lag)])
+    assert empty.tolist() == [False, False, True, True, False, False]
+    try:
+        for s in range(1, 7):
+            out = {"path": torch.full((n,), 0x7b7b7b7b, dtype=torch.int32, device="cuda"),
+                   "chain": torch.full((3 * lag,), 123.0, dtype=torch.float64, device="cuda"),
+                   "status": torch.full((1,), 0x7b7b7b7b, dtype=torch.int32, device="cuda")}
+            B().debug_hmm_viterbi_stages(s)
+            raw("dff_hmm_viterbi", 0, ptr(lab), n, lengths.ctypes.data_as(C.c_void_p), 3, lag, ptr(par[0]), ptr(par[1]), ptr(par[2]), m, K,
+                ptr(out["path"]), 0, ptr(out["chain"]), ptr(out["status"]), ptr(ws), ws.numel(), stream_of(lab))
+            kept = {k: (v == (123.0 if k == "chain" else 0x7b7b7b7b)).cpu().numpy() for k, v in out.items()}
+            assert kept["status"].all(), s
+            assert kept["chain"][empty].all() if s < 3 else not kept["chain"][empty].any(), s
+            assert kept["chain"][~empty].all() if s < 4 else not kept["chain"][~empty].any(), s
+            assert kept["path"].all() if s < 6 else not kept["path"].any(), s
+    finally:
+        B().debug_hmm_viterbi_stages(0)
+    after = viterbi(labels, lengths, lag, la, lb, lp)
+    assert after["status"] == before["status"] == 0
+    assert same_bits(after["path"], before["path"]) and same_bits(after["chain_logprob"], before["chain_logprob"])
+
+
 # ---------------------------------------------------------------- 6. stream order
 def viterbi_spec():
     """three trajectories (one empty) at lag 2, every output written; poison: constant labels and NaN parameters"""
-    m, K, lag, Cn = 3, 5, 2, chunk()
+    m, K, lag, Cn = 3, 5, 2, hmm_chunk()
     la, lb, lp = vc.log_model(*hc.model(m, K))
     lengths = np.array([2 * Cn + 5, 0, 3 * Cn], np.int64)
     n = int(lengths.sum())
@@ -270,17 +300,6 @@ def test_the_call_is_ordered_on_its_stream(gate, side):
 
 
 # ---------------------------------------------------------------- 7. the Python layer
-class HostViterbi:
-    """the stand-in behind evaluate.hmm_viterbi_solver: viterbi_cases.host_viterbi at the kernel's chunk"""
-
-    def __init__(self, device):
-        pass
-
-    def __call__(self, labels, lengths, lag, la, lb, lp, chain_order=False):
-        path, cl, status = vc.host_viterbi(np.asarray(labels.cpu()), lengths, lag, la, lb, lp, chunk(), chain_order)
-        return torch.from_numpy(path), cl, status
-
-
 def test_the_model_decodes_what_the_stand_in_decodes(dev, monkeypatch):
     A = np.array([[0.96, 0.03, 0.01], [0.02, 0.95, 0.03], [0.01, 0.04, 0.95]])
     B_ = hc.model(3, 30, seed=1)[1]

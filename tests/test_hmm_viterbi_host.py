@@ -15,21 +15,14 @@ import hmm_cases as hc
 import viterbi_cases as vc
 from dff_amd import binding, evaluate
 from oracle import kinetics as kin
+from standins import HostEstep, HostViterbi
+from support import hmm_chunk, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_hmm_viterbi_workspace_bytes", "dff_hmm_viterbi", "dff_debug_hmm_viterbi_stages")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
 ids = lambda c: "m%d-K%d-lag%d%s" % (c[0], c[1], c[2], "-disjoint" if c[3] else "")     # noqa: E731
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
-
-
-def chunk():
-    return int(binding.load_library().dff_hmm_chunk())
 
 
 # ---------------------------------------------------------------- symbols, workspace and refusals
@@ -57,7 +50,7 @@ def test_symbols_in_header_binding_and_library():
 
 def test_workspace_bytes_and_refusals_before_any_device_call():
     lib = binding.load_library()
-    Cn = chunk()
+    Cn = hmm_chunk()
     L = np.array([3 * Cn + 5, 0, 7], np.int64)
     n = int(L.sum())
 
@@ -115,7 +108,7 @@ def test_package_reexports():
 # ---------------------------------------------------------------- the chunked statement against the sequential recursion
 @pytest.mark.parametrize("case", hc.CASES, ids=ids)
 def test_the_chunked_statement_is_the_sequential_recursion_on_exact_inputs(case):
-    ref = vc.exact_reference(*case, chunk())
+    ref = vc.exact_reference(*case, hmm_chunk())
     assert (ref["labels"] < 0).any()
     full = np.array([len(c) > 0 for c in hc.chains(ref["lengths"], ref["lag"])])
     assert np.isfinite(ref["sequential"][1][full]).all()            # no chain is impossible
@@ -127,7 +120,7 @@ def test_ties_decide_frames_on_the_exact_inputs():
     """with the states renumbered backwards the lowest-index rule picks other paths: the exact inputs do pin the tie rule"""
     decided = 0
     for case in ((8, 5, 1, False), (3, 5, 7, False), (2, 5, 3, False)):
-        ref = vc.exact_reference(*case, chunk())
+        ref = vc.exact_reference(*case, hmm_chunk())
         la, lb, lp = ref["la"], ref["lb"], ref["lp"]
         flipped = vc.sequential_all(ref["labels"], ref["lengths"], ref["lag"], la[::-1, ::-1], lb[::-1], lp[::-1], np.float64)
         decided += int((case[0] - 1 - flipped[0] != ref["sequential"][0]).sum())
@@ -137,7 +130,7 @@ def test_ties_decide_frames_on_the_exact_inputs():
 
 @pytest.mark.parametrize("case", hc.CASES, ids=ids)
 def test_the_chunked_statement_is_as_close_to_the_truth_as_the_sequential_one(case):
-    ref = vc.reference(*case, chunk())
+    ref = vc.reference(*case, hmm_chunk())
     for k in vc.OUTPUTS:
         assert ref["e_chunked"][k] <= vc.FACTOR * max(ref["e_seq"][k], 1.0), (k, ref["e_chunked"][k], ref["e_seq"][k])
     assert ref["e_seq"]["path"] >= 0.0 and ref["e_chunked"]["path"] >= 0.0        # no path beats the truth's
@@ -148,7 +141,7 @@ def test_the_chunked_statement_is_as_close_to_the_truth_as_the_sequential_one(ca
 
 
 def test_missing_observations_and_the_status_rules_of_the_stand_in():
-    m, K, lag, Cn = 3, 5, 3, chunk()
+    m, K, lag, Cn = 3, 5, 3, hmm_chunk()
     ref = vc.reference(m, K, lag, False, Cn, missing=True)
     lab, lengths, la, lb, lp = ref["labels"], ref["lengths"], ref["la"], ref["lb"], ref["lp"]
     for k in vc.OUTPUTS:
@@ -191,7 +184,7 @@ def test_missing_observations_and_the_status_rules_of_the_stand_in():
 
 
 def test_chain_lengths_are_those_of_the_chains():
-    Cn = chunk()
+    Cn = hmm_chunk()
     for lengths, lag in (([], 1), ([0], 3), ([5, 3], 7), ([10, 0, 4], 4), (hc.lengths_for(1, Cn), 1), (hc.lengths_for(3, Cn), 3),
                          (hc.lengths_for(7, Cn), 7)):
         got = evaluate.hmm_chain_lengths(lengths, lag)
@@ -202,27 +195,6 @@ def test_chain_lengths_are_those_of_the_chains():
 
 
 # ---------------------------------------------------------------- the Python layer on the stand-in
-class HostViterbi:
-    calls = []
-
-    def __init__(self, device):
-        pass
-
-    def __call__(self, labels, lengths, lag, la, lb, lp, chain_order=False):
-        HostViterbi.calls.append((lag, bool(chain_order), np.array(la), np.array(lb), np.array(lp)))
-        path, cl, status = vc.host_viterbi(np.asarray(labels), lengths, lag, la, lb, lp, binding.hmm_chunk(), chain_order)
-        return torch.from_numpy(path), cl, status
-
-
-class HostEstep:
-    def __init__(self, device):
-        pass
-
-    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
-        stats, cl, post, status = hc.host_estep(np.asarray(labels), lengths, lag, A, B, p0, binding.hmm_chunk())
-        return stats, (cl if want_post else None), (torch.from_numpy(post) if want_post else None), status
-
-
 @pytest.fixture
 def on_host(monkeypatch):
     monkeypatch.setattr(evaluate, "hmm_estep_solver", HostEstep)
@@ -275,7 +247,7 @@ def test_the_model_decodes_through_the_seam(on_host):
 
 
 def test_the_evaluator_takes_dwells_inside_the_chains(on_host, monkeypatch):
-    Cn = chunk()
+    Cn = hmm_chunk()
     monkeypatch.setattr(binding, "load_library", lambda *a, **k: None)
     monkeypatch.setattr(binding, "hmm_chunk", lambda: Cn)
     monkeypatch.setattr(evaluate, "_frames", lambda x, device: torch.as_tensor(np.asarray(x, np.float64)))

@@ -14,16 +14,12 @@ import torch
 import dff_amd
 from dff_amd import binding, evaluate
 from oracle.kinetics import core_states, core_states_scan, label_runs, native_q
+from support import refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_struct_native_q", "dff_kinetics_workspace_bytes", "dff_core_states", "dff_label_runs")
 NAN, INF = float("nan"), float("inf")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what                                                 # DFF_EINVAL
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals

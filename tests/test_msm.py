@@ -27,7 +27,7 @@ import torch
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,11 +49,6 @@ def micro(pts, centers, accumulate=True, fill=0xFF):
         need = B().micro_kmeans_workspace_bytes(pd.shape[0], pd.shape[1], cd.shape[0])
         ws = torch.full((max(need, 8),), fill, dtype=torch.uint8, device="cuda")
     return {k: v.cpu().numpy() for k, v in B().micro_kmeans_step(pd, cd, accumulate=accumulate, workspace=ws).items()}
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def spoil(pts):

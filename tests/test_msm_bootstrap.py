@@ -22,14 +22,9 @@ from oracle import msm_bootstrap as boot
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------- 1. resampled counts

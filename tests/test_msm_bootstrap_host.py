@@ -15,17 +15,14 @@ import dff_amd
 from dff_amd import binding, evaluate
 from oracle import msm_bootstrap as boot
 from oracle import msm as oracle
+from standins import OracleSweeps
+from support import refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_micro_resampled_counts_workspace_bytes", "dff_micro_resampled_counts", "dff_msm_batched_workspace_bytes",
          "dff_msm_reversible_steps_batched", "dff_msm_batched_driver_for")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what                                                 # DFF_EINVAL
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals
@@ -188,14 +185,6 @@ def test_reachability_shortcut_gives_the_oracles_connected_sets():
 
 
 # ---------------------------------------------------------------- the pipeline on stand-ins
-class OracleSweeps:
-    def __init__(self, S, c, device):
-        self.S, self.c = np.array(S), np.array(c)
-
-    def __call__(self, x, n):
-        return oracle.sweeps(self.S, self.c, np.array(x), n)
-
-
 @pytest.fixture
 def on_oracle(monkeypatch):
     monkeypatch.setattr(evaluate, "reversible_sweeper", OracleSweeps)

@@ -12,17 +12,13 @@ import pytest
 import dff_amd
 from dff_amd import binding, evaluate
 from oracle import msm as oracle
+from support import refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_micro_chunk", "dff_micro_kmeans_workspace_bytes", "dff_micro_kmeans_step", "dff_micro_transition_counts",
          "dff_msm_workspace_bytes", "dff_msm_reversible_steps", "dff_debug_msm_driver", "dff_msm_driver_for")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what                                                 # DFF_EINVAL
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals

@@ -39,17 +39,12 @@ from oracle import msm_bootstrap as boot
 from oracle import passage as po
 from oracle.frames import synth_chain_frames
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
 R_FORWARD = 32.0          # the forward bar's factor: the power of two at or above twice the largest measured ratio (12.2)
 LDS, GLOBAL, VALU, MFMA = 1, 2, 3, 4          # debug_msm_dirichlet_path: 3 / 4 = the blocked path with a named trailing update
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def limit():

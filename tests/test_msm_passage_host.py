@@ -12,19 +12,15 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
-from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle import passage as po
+from standins import OracleSweeps
+from support import refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_msm_dirichlet_workspace_bytes", "dff_msm_dirichlet_lds_limit", "dff_msm_dirichlet_solve", "dff_debug_msm_dirichlet_path")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
 
 
 # ---------------------------------------------------------------- symbols and refusals
@@ -138,14 +134,6 @@ def test_forward_ratios_scatter_on_the_bridge():
 
 
 # ---------------------------------------------------------------- the Python layer on stand-ins
-class OracleSweeps:
-    def __init__(self, S, c, device):
-        self.S, self.c = np.array(S), np.array(c)
-
-    def __call__(self, x, n):
-        return oracle.sweeps(self.S, self.c, np.array(x), n)
-
-
 @pytest.fixture
 def on_oracle(monkeypatch):
     monkeypatch.setattr(evaluate, "reversible_sweeper", OracleSweeps)

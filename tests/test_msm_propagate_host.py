@@ -11,27 +11,18 @@ import pytest
 import torch
 
 import dff_amd
-import eig_cases as ec
 import propagate_cases as pc
 from dff_amd import binding, evaluate
 from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle.msm_bootstrap import five_state_case
+from standins import HostSpectral, OracleSweeps
+from support import refused, same_bits
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_msm_propagate_workspace_bytes", "dff_msm_propagate_lds_limit", "dff_msm_propagate", "dff_debug_msm_propagate_path")
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
 FAKE = C.c_void_p(4096)                         # a non-null "device pointer": every call below is refused before it is used
-
-
-def refused(lib, rc, what):
-    assert rc == 1, what
-    assert what in lib.dff_last_error().decode(), (what, lib.dff_last_error().decode())
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 # ---------------------------------------------------------------- symbols and refusals
@@ -130,22 +121,6 @@ class HostPropagator:
         HostPropagator.calls += 1
         HostPropagator.problems += len(ks)
         return pc.host_propagate(t, mat_of, ks, w0, obs, n_steps, want_last)
-
-
-class HostSpectral:
-    def __init__(self, device):
-        pass
-
-    def __call__(self, a, ks, k, vectors):
-        return ec.host_topk(np.asarray(a), ks, k, vectors)
-
-
-class OracleSweeps:
-    def __init__(self, S, c, device):
-        self.S, self.c = np.array(S), np.array(c)
-
-    def __call__(self, x, n):
-        return oracle.sweeps(self.S, self.c, np.array(x), n)
 
 
 @pytest.fixture

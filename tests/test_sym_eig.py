@@ -32,17 +32,12 @@ import torch
 
 import eig_cases as ec
 from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
-from support import B, dev, ev, to_dev  # noqa: F401  (dev)
+from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
 
 BY_SIZE, LDS, WORKSPACE = 0, 1, 2
 K_TOP = 8
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def limit():

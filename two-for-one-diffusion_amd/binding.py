@@ -1394,9 +1394,36 @@ def hmm_plan(lengths, lag: int):
     return int(a.value), int(b.value)
 
 
-def hmm_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
+def _hmm_workspace_bytes(symbol, n, lengths, lag, m, K):
+    """the bytes that `symbol`, one of the three dff_hmm*_workspace_bytes, asks for (its refusal raises)"""
     lh = _lengths(lengths)
-    return _workspace_bytes("dff_hmm_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
+    return _workspace_bytes(symbol, int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
+
+
+def _hmm_workspace(symbol, n, lengths, lag, m, K, workspace, device):
+    """the workspace of a call: the caller's, or a new uint8 tensor of the size that `symbol` asks for (asked either way: it is
+    the call's first refusal)"""
+    import torch
+    need = _hmm_workspace_bytes(symbol, n, lengths, lag, m, K)
+    return workspace if workspace is not None else torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+
+
+def _hmm_arguments(labels, lengths, lag, trans, emit, init, names):
+    """What hmm_estep, hmm_fit_steps and hmm_viterbi check first -> (m, K, n, lengths as a host array, lag, device); `names` are
+    the call's names of trans, emit and init."""
+    import torch
+    f64 = torch.float64
+    m, K = (int(emit.shape[0]), int(emit.shape[1])) if isinstance(emit, torch.Tensor) and emit.dim() == 2 else (-1, -1)
+    if not (_is_tensor(emit, f64, (m, K)) and _is_tensor(trans, f64, (m, m)) and _is_tensor(init, f64, (m,))
+            and trans.device == emit.device and init.device == emit.device):
+        raise ValueError("%s (m, m), %s (m, K) and %s (m,) must be contiguous float64 CUDA tensors on one device" % names)
+    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == emit.device):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
+    return m, K, int(labels.numel()), _lengths(lengths), int(lag), emit.device
+
+
+def hmm_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
+    return _hmm_workspace_bytes("dff_hmm_workspace_bytes", n, lengths, lag, m, K)
 
 
 def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, post=True, workspace=None):
@@ -1410,17 +1437,8 @@ def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, p
     import torch
     lib = load_library()
     f64 = torch.float64
-    m, K = (int(emit.shape[0]), int(emit.shape[1])) if isinstance(emit, torch.Tensor) and emit.dim() == 2 else (-1, -1)
-    if not (_is_tensor(emit, f64, (m, K)) and _is_tensor(trans, f64, (m, m)) and _is_tensor(init, f64, (m,))
-            and trans.device == emit.device and init.device == emit.device):
-        raise ValueError("trans (m, m), emit (m, K) and init (m,) must be contiguous float64 CUDA tensors on one device")
-    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == emit.device):
-        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
-    n = int(labels.numel())
-    lh = _lengths(lengths)
-    lag = int(lag)
-    need = hmm_workspace_bytes(n, lh, lag, m, K)
-    dev = emit.device
+    m, K, n, lh, lag, dev = _hmm_arguments(labels, lengths, lag, trans, emit, init, ("trans", "emit", "init"))
+    workspace = _hmm_workspace("dff_hmm_workspace_bytes", n, lh, lag, m, K, workspace, dev)
     stats = torch.empty(1 + m * m + m + m * K, dtype=f64, device=dev)
     cl = torch.empty(int(lh.size) * lag, dtype=f64, device=dev) if chain_loglik else None
     if isinstance(post, torch.Tensor):
@@ -1430,8 +1448,6 @@ def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, p
     else:
         pt = torch.empty((n, m), dtype=f64, device=dev) if post else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     _check(lib, lib.dff_hmm_estep(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
                                   _ptr(emit), _ptr(init), m, K, _ptr(stats), _ptr(cl), _ptr(pt), _ptr(status), _ptr(workspace),
                                   int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_estep")
@@ -1451,8 +1467,7 @@ def hmm_fit_state_dict(words) -> dict:
 
 
 def hmm_fit_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
-    lh = _lengths(lengths)
-    return _workspace_bytes("dff_hmm_fit_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
+    return _hmm_workspace_bytes("dff_hmm_fit_workspace_bytes", n, lengths, lag, m, K)
 
 
 def hmm_fit_steps(labels, lengths, lag: int, trans, emit, init, reversible, n_steps: int, accuracy: float, rev_tol: float = 1e-12,
@@ -1467,16 +1482,10 @@ def hmm_fit_steps(labels, lengths, lag: int, trans, emit, init, reversible, n_st
     import torch
     lib = load_library()
     f64 = torch.float64
-    m, K = (int(emit.shape[0]), int(emit.shape[1])) if isinstance(emit, torch.Tensor) and emit.dim() == 2 else (-1, -1)
-    if not (_is_tensor(emit, f64, (m, K)) and _is_tensor(trans, f64, (m, m)) and _is_tensor(init, f64, (m,))
-            and trans.device == emit.device and init.device == emit.device):
-        raise ValueError("trans (m, m), emit (m, K) and init (m,) must be contiguous float64 CUDA tensors on one device")
-    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == emit.device):
-        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
+    m, K, n, lh, lag, dev = _hmm_arguments(labels, lengths, lag, trans, emit, init, ("trans", "emit", "init"))
     n_steps = int(n_steps)
     if n_steps < 1:
         raise ValueError("n_steps must be >= 1")
-    dev = emit.device
     if state is None:
         state = torch.zeros(8, dtype=torch.int32, device=dev)
     elif not (_is_tensor(state, torch.int32, (8,)) and state.device == dev):
@@ -1491,12 +1500,7 @@ def hmm_fit_steps(labels, lengths, lag: int, trans, emit, init, reversible, n_st
         stationary = None
     elif not (_is_tensor(stationary, f64, (m,)) and stationary.device == dev):
         raise ValueError("stationary must be a contiguous float64 CUDA tensor (m,) on the parameters' device")
-    n = int(labels.numel())
-    lh = _lengths(lengths)
-    lag = int(lag)
-    need = hmm_fit_workspace_bytes(n, lh, lag, m, K)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    workspace = _hmm_workspace("dff_hmm_fit_workspace_bytes", n, lh, lag, m, K, workspace, dev)
     _check(lib, lib.dff_hmm_fit_steps(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
                                       _ptr(emit), _ptr(init), m, K, int(bool(reversible)), n_steps, float(accuracy), float(rev_tol),
                                       int(rev_max_sweeps), _ptr(loglik), _ptr(stationary), _ptr(state), _ptr(workspace),
@@ -1512,9 +1516,7 @@ def debug_hmm_viterbi_stages(stages: int):
 
 
 def hmm_viterbi_workspace_bytes(n: int, lengths, lag: int, m: int, K: int) -> int:
-    lh = _lengths(lengths)
-    return _workspace_bytes("dff_hmm_viterbi_workspace_bytes", int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m),
-                            int(K))
+    return _hmm_workspace_bytes("dff_hmm_viterbi_workspace_bytes", n, lengths, lag, m, K)
 
 
 def hmm_viterbi(labels, lengths, lag: int, logtrans, logemit, loginit, chain_order=False, chain_logprob=True, workspace=None):
@@ -1528,22 +1530,11 @@ def hmm_viterbi(labels, lengths, lag: int, logtrans, logemit, loginit, chain_ord
     import torch
     lib = load_library()
     f64 = torch.float64
-    m, K = (int(logemit.shape[0]), int(logemit.shape[1])) if isinstance(logemit, torch.Tensor) and logemit.dim() == 2 else (-1, -1)
-    if not (_is_tensor(logemit, f64, (m, K)) and _is_tensor(logtrans, f64, (m, m)) and _is_tensor(loginit, f64, (m,))
-            and logtrans.device == logemit.device and loginit.device == logemit.device):
-        raise ValueError("logtrans (m, m), logemit (m, K) and loginit (m,) must be contiguous float64 CUDA tensors on one device")
-    if not (_is_tensor(labels, torch.int32, dim=1) and labels.device == logemit.device):
-        raise ValueError("labels must be a contiguous int32 CUDA tensor (n,) on the parameters' device")
-    n = int(labels.numel())
-    lh = _lengths(lengths)
-    lag = int(lag)
-    need = hmm_viterbi_workspace_bytes(n, lh, lag, m, K)
-    dev = logemit.device
+    m, K, n, lh, lag, dev = _hmm_arguments(labels, lengths, lag, logtrans, logemit, loginit, ("logtrans", "logemit", "loginit"))
+    workspace = _hmm_workspace("dff_hmm_viterbi_workspace_bytes", n, lh, lag, m, K, workspace, dev)
     path = torch.empty(n, dtype=torch.int32, device=dev)
     cl = torch.empty(int(lh.size) * lag, dtype=f64, device=dev) if chain_logprob else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     _check(lib, lib.dff_hmm_viterbi(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(logtrans),
                                     _ptr(logemit), _ptr(loginit), m, K, _ptr(path), 1 if chain_order else 0, _ptr(cl), _ptr(status),
                                     _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(logemit)),

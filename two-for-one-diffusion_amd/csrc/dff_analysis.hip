@@ -3,6 +3,7 @@
 // dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi among them), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #include "dff_pwd.hip"
@@ -1499,7 +1500,7 @@ static int hmm_plan(const long long* lengths, int n_traj, int lag, long long* n_
     for (int r = 0; r < n_traj; ++r) {
         if (lengths[r] < 0) return fail(DFF_EINVAL, "%s: trajectory %d has negative length", what, r);
         if (cpre) cpre[r] = chunks;
-        const long long q = lengths[r] / lag, rem = lengths[r] - q * lag;
+        const auto [q, rem] = hmm_split(lengths[r], lag);
         chunks += rem * hmm_chunks_of(q + 1) + (lag - rem) * hmm_chunks_of(q);
     }
     if (cpre) cpre[n_traj] = chunks;
@@ -1519,15 +1520,38 @@ static int hmm_check_shape(long long n, int m, int K, const char* what) {
     return micro_check_count(K, what, "symbols");
 }
 
-// the sections of the workspace, each a multiple of 16 bytes
-struct HmmLayout {
-    size_t tab, flags, a, p0, bt, prod, pexp, ain, bout, ll, post, part, total;
-    HmmLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) {
-        const size_t MP = (size_t)hmm_pad(m), d = sizeof(double);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+// the packed statistics of an E-step: loglik | xi (m, m) | gamma0 (m) | gamma_sym (m, K)
+static long long hmm_nstats(int m, int K) { return 1 + (long long)m * m + m + (long long)m * K; }
+
+// f(std::integral_constant<int, MP>()) for MP = hmm_pad(m): the one place that turns m hidden states into a template argument
+template <class F>
+static int hmm_with_pad(int m, F f) {
+    switch (hmm_pad(m)) {
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
+    }
+}
+
+// a workspace cut into sections, each a multiple of 16 bytes.  Every hidden-Markov-model call starts its own with the
+// trajectory table (HmmPlan) and the four flag words.
+struct HmmSections {
+    size_t total = 0, tab, flags;
+    explicit HmmSections(int n_traj) {
         tab = take(2 * ((size_t)n_traj + 1) * sizeof(long long));
         flags = take(4 * sizeof(int));
+    }
+    size_t take(size_t bytes) {
+        const size_t at = total;
+        total += (bytes + 15) & ~(size_t)15;
+        return at;
+    }
+};
+
+struct HmmLayout : HmmSections {
+    size_t a, p0, bt, prod, pexp, ain, bout, ll, post, part;
+    HmmLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) : HmmSections(n_traj) {
+        const size_t MP = (size_t)hmm_pad(m), d = sizeof(double);
         a = take(MP * MP * d);
         p0 = take(MP * d);
         bt = take((size_t)K * MP * d);
@@ -1538,18 +1562,62 @@ struct HmmLayout {
         ll = take((size_t)n_chains * d);
         post = take((size_t)n * m * d);
         part = take((size_t)((n + DFF_HMM_GROUP - 1) / DFF_HMM_GROUP) * K * m * d);
-        total = o;
     }
 };
 
-extern "C" long long dff_hmm_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
-    const char* what = "hmm_workspace_bytes";
+// the bytes of a call whose workspace is a Layout, or -1 behind the refusal that the call itself would give
+template <class Layout>
+static long long hmm_workspace_bytes(const char* what, long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
     if (hmm_check_shape(n, m, K, what)) return -1;
     long long n_chains, n_chunks;
     if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
     if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
-    return (long long)HmmLayout(n, n_traj, n_chains, n_chunks, m, K).total;
+    return (long long)Layout(n, n_traj, n_chains, n_chunks, m, K).total;
 }
+
+extern "C" long long dff_hmm_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
+    return hmm_workspace_bytes<HmmLayout>("hmm_workspace_bytes", n, lengths, n_traj, lag, m, K);
+}
+
+// What dff_hmm_estep, dff_hmm_fit_steps and dff_hmm_viterbi do before and after their own argument checks: check() is the
+// refusals they share, in their order; workspace() follows the caller's own checks; upload(), behind ON_DEVICE, puts the
+// trajectory table at the head of the workspace and names it in a plan.
+struct HmmCall {
+    const char* what;
+    const long long* lengths = nullptr;
+    int n_traj = 0, lag = 0;
+    long long n_chains = 0, n_chunks = 0;
+    std::vector<long long> tab;                                     // off[0 .. n_traj] | cpre[0 .. n_traj]; upload() fills off
+    explicit HmmCall(const char* what) : what(what) {}
+
+    // shape, null labels, plan, trajectory lengths
+    int check(const int32_t* labels, long long n, const long long* lengths_, int n_traj_, int lag_, int m, int K) {
+        lengths = lengths_, n_traj = n_traj_, lag = lag_;
+        int rc = hmm_check_shape(n, m, K, what);
+        if (rc) return rc;
+        if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
+        tab.assign(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
+        if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + tab.size() / 2, what))) return rc;
+        return traj_check_lengths(lengths, n_traj, n, what);
+    }
+
+    int workspace(const void* ws, size_t ws_bytes, const HmmSections& lay) const {
+        const int rc = check_workspace(ws, ws_bytes, (long long)lay.total, what);
+        if (rc) return rc;
+        if ((uintptr_t)ws % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+        return DFF_OK;
+    }
+
+    int upload(hipStream_t stream, char* ws, const HmmSections& lay, HmmPlan* pl) {
+        for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
+        long long* dst = (long long*)(ws + lay.tab);
+        pl->off = dst;
+        pl->cpre = dst + tab.size() / 2;
+        pl->n_traj = n_traj;
+        pl->lag = lag;
+        return msmb_upload(stream, tab.data(), (long long)tab.size(), dst);
+    }
+};
 
 template <int MP>
 static int hmm_launches(hipStream_t stream, const int32_t* labels, long long n, HmmPlan pl, long long n_chains, long long n_chunks,
@@ -1597,9 +1665,34 @@ static int hmm_launches(hipStream_t stream, const int32_t* labels, long long n, 
         HIPCHK(hipGetLastError());
     }
     if (stages < 6) return DFF_OK;
-    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
-    hipLaunchKernelGGL(dff_hmm_reduce_kernel<MP>, dim3((unsigned)nstats), dim3(64), 0, stream, pl, n_chains, n_chunks, n_chunks > 0 ? n_groups : 0, m, K,
+    hipLaunchKernelGGL(dff_hmm_reduce_kernel<MP>, dim3((unsigned)hmm_nstats(m, K)), dim3(64), 0, stream, pl, n_chains, n_chunks, n_chunks > 0 ? n_groups : 0, m, K,
                        (const double*)chain_ll, (const double*)prod, (const double*)post, (const double*)part, stats);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// One E-step on the stream: the parameters into the workspace, hmm_launches, then status and NaN.  dff_hmm_estep is one pass,
+// dff_hmm_fit_steps one per iteration: the fit's E-step is this code, not a copy of it.  chain_loglik and post may be null: the
+// launches then work in the workspace's sections, and finish gets them as given, so it only rewrites what the caller sees.
+// With dff_debug_hmm_stages set the pass stops where hmm_launches stopped, before finish.
+static int hmm_estep_pass(hipStream_t stream, const int32_t* labels, long long n, const HmmPlan& pl, const HmmCall& call,
+                          const double* trans, const double* emit, const double* init, int m, int K, const HmmLayout& lay,
+                          char* ws, double* stats, double* chain_loglik, double* post, int32_t* status) {
+    hipLaunchKernelGGL(dff_hmm_prep_kernel, dim3(1), dim3(1024), 0, stream, trans, emit, init, m, K, hmm_pad(m),
+                       (double*)(ws + lay.a), (double*)(ws + lay.p0), (double*)(ws + lay.bt), (int*)(ws + lay.flags));
+    HIPCHK(hipGetLastError());
+    double* ll = chain_loglik ? chain_loglik : (double*)(ws + lay.ll);
+    double* pp = post ? post : (double*)(ws + lay.post);
+    const int rc = hmm_with_pad(m, [&](auto mp) {
+        return hmm_launches<decltype(mp)::value>(stream, labels, n, pl, call.n_chains, call.n_chunks, m, K, lay, ws, stats, ll, pp);
+    });
+    if (rc || g_hmm_stages.load()) return rc;
+    const long long nstats = hmm_nstats(m, K);
+    long long most = nstats > call.n_chains ? nstats : call.n_chains;
+    if (post && n * m > most) most = n * m;
+    const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
+    hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
+                       (const int*)(ws + lay.flags), nstats, stats, call.n_chains, chain_loglik, n * m, post, status);
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }
@@ -1608,48 +1701,19 @@ extern "C" int dff_hmm_estep(int device, const int32_t* labels, long long n, con
                              const double* trans, const double* emit, const double* init, int m, int K, double* stats,
                              double* chain_loglik, double* post, int32_t* status, void* workspace, size_t workspace_bytes,
                              void* stream_) {
-    const char* what = "hmm_estep";
-    int rc = hmm_check_shape(n, m, K, what);
+    HmmCall call("hmm_estep");
+    int rc = call.check(labels, n, lengths, n_traj, lag, m, K);
     if (rc) return rc;
-    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
-    long long n_chains, n_chunks;
-    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
-    const size_t nt1 = tab.size() / 2;
-    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
-    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
     if (!trans || !emit || !init || !stats || !status)
-        return fail(DFF_EINVAL, "%s: null transition matrix / emissions / initial distribution / stats / status", what);
-    const HmmLayout lay(n, n_traj, n_chains, n_chunks, m, K);
-    if ((rc = check_workspace(workspace, workspace_bytes, (long long)lay.total, what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+        return fail(DFF_EINVAL, "%s: null transition matrix / emissions / initial distribution / stats / status", call.what);
+    const HmmLayout lay(n, n_traj, call.n_chains, call.n_chunks, m, K);
+    if ((rc = call.workspace(workspace, workspace_bytes, lay))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
     char* ws = (char*)workspace;
-    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;
     HmmPlan pl;
-    pl.off = (const long long*)(ws + lay.tab);
-    pl.cpre = pl.off + nt1;
-    pl.n_traj = n_traj;
-    pl.lag = lag;
-    const int MP = hmm_pad(m);
-    hipLaunchKernelGGL(dff_hmm_prep_kernel, dim3(1), dim3(1024), 0, stream, trans, emit, init, m, K, MP, (double*)(ws + lay.a),
-                       (double*)(ws + lay.p0), (double*)(ws + lay.bt), (int*)(ws + lay.flags));
-    HIPCHK(hipGetLastError());
-    double* ll = chain_loglik ? chain_loglik : (double*)(ws + lay.ll);
-    double* pp = post ? post : (double*)(ws + lay.post);
-    if (MP == 2) rc = hmm_launches<2>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-    else if (MP == 4) rc = hmm_launches<4>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-    else rc = hmm_launches<8>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-    if (rc || g_hmm_stages.load()) return rc;
-    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
-    long long most = nstats > n_chains ? nstats : n_chains;
-    if (post && n * m > most) most = n * m;
-    const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
-    hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
-                       (const int*)(ws + lay.flags), nstats, stats, n_chains, chain_loglik, n * m, post, status);
-    HIPCHK(hipGetLastError());
-    return DFF_OK;
+    if ((rc = call.upload(stream, ws, lay, &pl))) return rc;
+    return hmm_estep_pass(stream, labels, n, pl, call, trans, emit, init, m, K, lay, ws, stats, chain_loglik, post, status);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1657,39 +1721,29 @@ extern "C" int dff_hmm_estep(int device, const int32_t* labels, long long n, con
 // ---------------------------------------------------------------------------------------------
 static_assert(sizeof(dff_hmm_fit_state) == 32, "dff_hmm_fit_state is 32 bytes");
 
-// the workspace of a fit: that of the E-step, then its packed statistics and its status word
-struct HmmFitLayout {
-    size_t stats, status, total;
-    HmmFitLayout(const HmmLayout& lay, int m, int K) {
-        const size_t nstats = 1 + (size_t)m * m + m + (size_t)m * K;
-        stats = lay.total;
-        status = stats + ((nstats * sizeof(double) + 15) & ~(size_t)15);
-        total = status + 16;
+// the workspace of a fit: the sections of the E-step, then two more of the same kind, the E-step's packed statistics and its
+// status word (one int in a section of 16 bytes)
+struct HmmFitLayout : HmmLayout {
+    size_t stats, status;
+    HmmFitLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K)
+        : HmmLayout(n, n_traj, n_chains, n_chunks, m, K) {
+        stats = take((size_t)hmm_nstats(m, K) * sizeof(double));
+        status = take(sizeof(int));
     }
 };
 
 extern "C" long long dff_hmm_fit_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
-    const char* what = "hmm_fit_workspace_bytes";
-    if (hmm_check_shape(n, m, K, what)) return -1;
-    long long n_chains, n_chunks;
-    if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
-    if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
-    return (long long)HmmFitLayout(HmmLayout(n, n_traj, n_chains, n_chunks, m, K), m, K).total;
+    return hmm_workspace_bytes<HmmFitLayout>("hmm_fit_workspace_bytes", n, lengths, n_traj, lag, m, K);
 }
 
 extern "C" int dff_hmm_fit_steps(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj, int lag,
                                  double* trans, double* emit, double* init, int m, int K, int reversible, int n_steps,
                                  double accuracy, double rev_tol, long long rev_max_sweeps, double* loglik, double* stationary,
                                  dff_hmm_fit_state* state, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* what = "hmm_fit_steps";
-    int rc = hmm_check_shape(n, m, K, what);
+    HmmCall call("hmm_fit_steps");
+    const char* what = call.what;
+    int rc = call.check(labels, n, lengths, n_traj, lag, m, K);
     if (rc) return rc;
-    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
-    long long n_chains, n_chunks;
-    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
-    const size_t nt1 = tab.size() / 2;
-    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
-    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
     if (!trans || !emit || !init || !loglik || !state)
         return fail(DFF_EINVAL, "%s: null transition matrix / emissions / initial distribution / log-likelihoods / state", what);
     if (reversible != 0 && reversible != 1) return fail(DFF_EINVAL, "%s: reversible must be 0 or 1", what);
@@ -1699,41 +1753,19 @@ extern "C" int dff_hmm_fit_steps(int device, const int32_t* labels, long long n,
     if (rev_max_sweeps < 1) return fail(DFF_EINVAL, "%s: rev_max_sweeps must be >= 1", what);
     if ((uintptr_t)state % sizeof(double)) return fail(DFF_EINVAL, "%s: the state must be 8-byte aligned", what);
     if (g_hmm_stages.load()) return fail(DFF_EINVAL, "%s: dff_debug_hmm_stages is set: the E-step would stop early", what);
-    const HmmLayout lay(n, n_traj, n_chains, n_chunks, m, K);
-    const HmmFitLayout fit(lay, m, K);
-    if ((rc = check_workspace(workspace, workspace_bytes, (long long)fit.total, what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    const HmmFitLayout lay(n, n_traj, call.n_chains, call.n_chunks, m, K);
+    if ((rc = call.workspace(workspace, workspace_bytes, lay))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
     char* ws = (char*)workspace;
-    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;   // once per call
     HmmPlan pl;
-    pl.off = (const long long*)(ws + lay.tab);
-    pl.cpre = pl.off + nt1;
-    pl.n_traj = n_traj;
-    pl.lag = lag;
-    const int MP = hmm_pad(m);
-    double* stats = (double*)(ws + fit.stats);
-    int* status = (int*)(ws + fit.status);
-    double* ll = (double*)(ws + lay.ll);
-    double* pp = (double*)(ws + lay.post);
-    const long long nstats = 1 + (long long)m * m + m + (long long)m * K;
-    const long long most = nstats > n_chains ? nstats : n_chains;
-    const long long blocks = (most + DFF_HMM_THREADS - 1) / DFF_HMM_THREADS;
+    if ((rc = call.upload(stream, ws, lay, &pl))) return rc;     // once per call
+    double* stats = (double*)(ws + lay.stats);
+    int* status = (int*)(ws + lay.status);
     for (int s = 0; s < n_steps; ++s) {
-        // the E-step: the launches of dff_hmm_estep, its statistics and status in the workspace
-        hipLaunchKernelGGL(dff_hmm_prep_kernel, dim3(1), dim3(1024), 0, stream, (const double*)trans, (const double*)emit,
-                           (const double*)init, m, K, MP, (double*)(ws + lay.a), (double*)(ws + lay.p0), (double*)(ws + lay.bt),
-                           (int*)(ws + lay.flags));
-        HIPCHK(hipGetLastError());
-        if (MP == 2) rc = hmm_launches<2>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-        else if (MP == 4) rc = hmm_launches<4>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-        else rc = hmm_launches<8>(stream, labels, n, pl, n_chains, n_chunks, m, K, lay, ws, stats, ll, pp);
-        if (rc) return rc;
-        hipLaunchKernelGGL(dff_hmm_finish_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(DFF_HMM_THREADS), 0, stream,
-                           (const int*)(ws + lay.flags), nstats, stats, n_chains, (double*)nullptr, n * m, (double*)nullptr, status);
-        HIPCHK(hipGetLastError());
+        // the E-step of dff_hmm_estep, no output but its statistics and its status, both in the workspace
+        if ((rc = hmm_estep_pass(stream, labels, n, pl, call, trans, emit, init, m, K, lay, ws, stats, nullptr, nullptr, status)))
+            return rc;
         // control and M-step: one workgroup
         hipLaunchKernelGGL(dff_hmm_fit_mstep_kernel, dim3(1), dim3(DFF_HMM_FIT_THREADS), 0, stream, (const double*)stats,
                            (const int*)status, state, trans, emit, init, m, K, reversible, accuracy, rev_tol, rev_max_sweeps,
@@ -1757,15 +1789,10 @@ extern "C" int dff_debug_hmm_viterbi_stages(int stages) {
     return DFF_OK;
 }
 
-// the sections of the workspace, each a multiple of 16 bytes
-struct VitLayout {
-    size_t tab, flags, la, lp, lbt, prod, din, psi, origin, end, endstate, clp, total;
-    VitLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) {
+struct VitLayout : HmmSections {
+    size_t la, lp, lbt, prod, din, psi, origin, end, endstate, clp;
+    VitLayout(long long n, int n_traj, long long n_chains, long long n_chunks, int m, int K) : HmmSections(n_traj) {
         const size_t MP = (size_t)hmm_pad(m), d = sizeof(double);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-        tab = take(2 * ((size_t)n_traj + 1) * sizeof(long long));
-        flags = take(4 * sizeof(int));
         la = take(MP * MP * d);
         lp = take(MP * d);
         lbt = take((size_t)K * MP * d);
@@ -1776,17 +1803,11 @@ struct VitLayout {
         end = take((size_t)n_chunks * sizeof(int));
         endstate = take((size_t)n_chains * sizeof(int));
         clp = take((size_t)n_chains * d);
-        total = o;
     }
 };
 
 extern "C" long long dff_hmm_viterbi_workspace_bytes(long long n, const long long* lengths, int n_traj, int lag, int m, int K) {
-    const char* what = "hmm_viterbi_workspace_bytes";
-    if (hmm_check_shape(n, m, K, what)) return -1;
-    long long n_chains, n_chunks;
-    if (hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, nullptr, what)) return -1;
-    if (traj_check_lengths(lengths, n_traj, n, what)) return -1;
-    return (long long)VitLayout(n, n_traj, n_chains, n_chunks, m, K).total;
+    return hmm_workspace_bytes<VitLayout>("hmm_viterbi_workspace_bytes", n, lengths, n_traj, lag, m, K);
 }
 
 template <int MP>
@@ -1841,42 +1862,31 @@ extern "C" int dff_hmm_viterbi(int device, const int32_t* labels, long long n, c
                                const double* logtrans, const double* logemit, const double* loginit, int m, int K, int32_t* path,
                                int chain_order, double* chain_logprob, int32_t* status, void* workspace, size_t workspace_bytes,
                                void* stream_) {
-    const char* what = "hmm_viterbi";
-    int rc = hmm_check_shape(n, m, K, what);
+    HmmCall call("hmm_viterbi");
+    const char* what = call.what;
+    int rc = call.check(labels, n, lengths, n_traj, lag, m, K);
     if (rc) return rc;
-    if (!labels && n > 0) return fail(DFF_EINVAL, "%s: null labels", what);
-    long long n_chains, n_chunks;
-    std::vector<long long> tab(2 * ((size_t)(n_traj > 0 ? n_traj : 0) + 1), 0);
-    const size_t nt1 = tab.size() / 2;
-    if ((rc = hmm_plan(lengths, n_traj, lag, &n_chains, &n_chunks, tab.data() + nt1, what))) return rc;
-    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    const long long n_chains = call.n_chains, n_chunks = call.n_chunks;
     if (!logtrans || !logemit || !loginit || !status || (!path && n > 0))
         return fail(DFF_EINVAL, "%s: null log transition matrix / log emissions / log initial distribution / path / status", what);
     if (chain_order != 0 && chain_order != 1) return fail(DFF_EINVAL, "%s: chain_order must be 0 (frame order) or 1 (chain order)", what);
     const VitLayout lay(n, n_traj, n_chains, n_chunks, m, K);
-    if ((rc = check_workspace(workspace, workspace_bytes, (long long)lay.total, what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if ((rc = call.workspace(workspace, workspace_bytes, lay))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    for (int r = 0; r < n_traj; ++r) tab[r + 1] = tab[r] + lengths[r];
     char* ws = (char*)workspace;
-    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), (long long*)(ws + lay.tab)))) return rc;
     HmmPlan pl;
-    pl.off = (const long long*)(ws + lay.tab);
-    pl.cpre = pl.off + nt1;
-    pl.n_traj = n_traj;
-    pl.lag = lag;
-    const int MP = hmm_pad(m);
+    if ((rc = call.upload(stream, ws, lay, &pl))) return rc;
     HIPCHK(hipMemsetAsync(ws + lay.flags, 0, 4 * sizeof(int), stream));
     long long pblocks = (n + 1023) / 1024;
     pblocks = pblocks < 1 ? 1 : (pblocks > 1024 ? 1024 : pblocks);
     hipLaunchKernelGGL(dff_vit_prep_kernel, dim3((unsigned)pblocks), dim3(1024), 0, stream, labels, n, logtrans, logemit, loginit, m,
-                       K, MP, (double*)(ws + lay.la), (double*)(ws + lay.lp), (double*)(ws + lay.lbt), (int*)(ws + lay.flags));
+                       K, hmm_pad(m), (double*)(ws + lay.la), (double*)(ws + lay.lp), (double*)(ws + lay.lbt), (int*)(ws + lay.flags));
     HIPCHK(hipGetLastError());
     double* clp = chain_logprob ? chain_logprob : (double*)(ws + lay.clp);
-    if (MP == 2) rc = vit_launches<2>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
-    else if (MP == 4) rc = vit_launches<4>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
-    else rc = vit_launches<8>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
+    rc = hmm_with_pad(m, [&](auto mp) {
+        return vit_launches<decltype(mp)::value>(stream, labels, pl, n_chains, n_chunks, K, lay, ws, path, chain_order, clp);
+    });
     if (rc || g_vit_stages.load()) return rc;
     const long long most = n > n_chains ? n : n_chains;
     const long long blocks = (most + DFF_VIT_THREADS - 1) / DFF_VIT_THREADS;

@@ -71,10 +71,34 @@ struct HmmChain {
     long long nch;        // chunks
 };
 
+// a trajectory of len frames at a lag: its first rem chains hold q + 1 frames, the other lag - rem hold q
+struct HmmSplit {
+    long long q, rem;
+};
+
+__host__ __device__ __forceinline__ HmmSplit hmm_split(long long len, long long lag) {
+    HmmSplit s;
+    s.q = len / lag;
+    s.rem = len - s.q * lag;
+    return s;
+}
+
+// the frames [t0, t1) of its chain that chunk k holds, and ts, the first of them that is a factor: the chain's first frame is none
+struct HmmSpan {
+    long long t0, t1, ts;
+};
+
+__device__ __forceinline__ HmmSpan hmm_span(const HmmChain& ch, long long k) {
+    HmmSpan s;
+    s.t0 = k * DFF_HMM_CHUNK;
+    s.t1 = ch.L - s.t0 < DFF_HMM_CHUNK ? ch.L : s.t0 + DFF_HMM_CHUNK;
+    s.ts = s.t0 > 0 ? s.t0 : 1;
+    return s;
+}
+
 // chain f of trajectory r
 __device__ __forceinline__ HmmChain hmm_chain(const HmmPlan& pl, int r, int f) {
-    const long long len = pl.off[r + 1] - pl.off[r];
-    const long long q = len / pl.lag, rem = len - q * pl.lag;
+    const auto [q, rem] = hmm_split(pl.off[r + 1] - pl.off[r], pl.lag);
     const long long nA = hmm_chunks_of(q + 1), nB = hmm_chunks_of(q);
     HmmChain c;
     c.first = pl.off[r] + f;
@@ -92,8 +116,7 @@ __device__ __forceinline__ HmmChain hmm_locate(const HmmPlan& pl, long long c, l
         if (pl.cpre[mid] <= c) lo = mid; else hi = mid;
     }
     const int r = lo;
-    const long long len = pl.off[r + 1] - pl.off[r];
-    const long long q = len / pl.lag, rem = len - q * pl.lag;
+    const auto [q, rem] = hmm_split(pl.off[r + 1] - pl.off[r], pl.lag);
     const long long nA = hmm_chunks_of(q + 1), nB = hmm_chunks_of(q);
     const long long cl = c - pl.cpre[r];
     int f;
@@ -169,9 +192,7 @@ __global__ __launch_bounds__(DFF_HMM_THREADS) void dff_hmm_products_kernel(const
     if (c >= n_chunks) return;
     long long chain, k;
     const HmmChain ch = hmm_locate(pl, c, chain, k);
-    const long long t0 = k * DFF_HMM_CHUNK;
-    const long long t1 = ch.L - t0 < DFF_HMM_CHUNK ? ch.L : t0 + DFF_HMM_CHUNK;
-    const long long ts = t0 > 0 ? t0 : 1;                           // the chain's first frame is no factor
+    const auto [t0, t1, ts] = hmm_span(ch, k);
     double a[MP][MP];
 #pragma unroll
     for (int x = 0; x < MP; ++x)
@@ -546,12 +567,17 @@ __global__ __launch_bounds__(64) void dff_hmm_reduce_kernel(HmmPlan pl, long lon
     if (lane == 0) stats[q] = v;
 }
 
+// the status of a call from its flags: 1 a bad parameter, 3 a label >= K, 2 a chain that vanished, in that order of precedence
+__device__ __forceinline__ int hmm_status(const int* __restrict__ flags) {
+    return flags[0] ? 1 : (flags[1] ? 3 : (flags[2] ? 2 : 0));
+}
+
 // ---- status; NaN over every output when it is not 0
 __global__ __launch_bounds__(DFF_HMM_THREADS) void dff_hmm_finish_kernel(const int* __restrict__ flags, long long nstats,
                                                                          double* __restrict__ stats, long long n_chains,
                                                                          double* __restrict__ chain_ll, long long npost,
                                                                          double* __restrict__ post, int* __restrict__ status) {
-    const int st = flags[0] ? 1 : (flags[1] ? 3 : (flags[2] ? 2 : 0));
+    const int st = hmm_status(flags);
     const long long q = (long long)blockIdx.x * DFF_HMM_THREADS + threadIdx.x;
     if (q == 0) *status = st;
     if (st == 0) return;

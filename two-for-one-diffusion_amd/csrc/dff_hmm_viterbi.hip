@@ -39,8 +39,7 @@
 
 // the chain-order position of the first frame of chain f of trajectory r: the chains of a trajectory lie back to back
 __device__ __forceinline__ long long vit_chain_start(const HmmPlan& pl, int r, int f) {
-    const long long len = pl.off[r + 1] - pl.off[r];
-    const long long q = len / pl.lag, rem = len - q * pl.lag;
+    const auto [q, rem] = hmm_split(pl.off[r + 1] - pl.off[r], pl.lag);
     return pl.off[r] + (f < rem ? f * (q + 1) : rem * (q + 1) + (f - rem) * q);
 }
 
@@ -108,9 +107,7 @@ __global__ __launch_bounds__(DFF_VIT_THREADS) void dff_vit_products_kernel(const
     if (c >= n_chunks) return;
     long long chain, k;
     const HmmChain ch = hmm_locate(pl, c, chain, k);
-    const long long t0 = k * DFF_HMM_CHUNK;
-    const long long t1 = ch.L - t0 < DFF_HMM_CHUNK ? ch.L : t0 + DFF_HMM_CHUNK;
-    const long long ts = t0 > 0 ? t0 : 1;                           // the chain's first frame is no factor
+    const auto [t0, t1, ts] = hmm_span(ch, k);
     double a[MP][MP];
 #pragma unroll
     for (int x = 0; x < MP; ++x)
@@ -230,9 +227,7 @@ __global__ __launch_bounds__(DFF_VIT_THREADS) void dff_vit_apply_kernel(const in
     const HmmChain ch = hmm_locate(pl, c, chain, k);
     const int r = (int)(chain / pl.lag), f = (int)(chain - (long long)r * pl.lag);
     const long long pos0 = vit_chain_start(pl, r, f);
-    const long long t0 = k * C;
-    const long long t1 = ch.L - t0 < C ? ch.L : t0 + C;
-    const long long ts = t0 > 0 ? t0 : 1;
+    const auto [t0, t1, ts] = hmm_span(ch, k);
     const long long lag = pl.lag;
     const int32_t* lab = labels + ch.first;
     double acol[MP];
@@ -312,8 +307,7 @@ __global__ __launch_bounds__(DFF_VIT_THREADS) void dff_vit_backtrack_kernel(HmmP
     const HmmChain ch = hmm_locate(pl, c, chain, k);
     const int r = (int)(chain / pl.lag), f = (int)(chain - (long long)r * pl.lag);
     const long long pos0 = vit_chain_start(pl, r, f);
-    const long long t0 = k * DFF_HMM_CHUNK;
-    const long long t1 = ch.L - t0 < DFF_HMM_CHUNK ? ch.L : t0 + DFF_HMM_CHUNK;
+    const auto [t0, t1, ts] = hmm_span(ch, k);
     const long long base = chain_order ? pos0 : ch.first, step = chain_order ? 1 : pl.lag;
     int s = end[c] & 7;
     for (long long t = t1 - 1; t >= t0; --t) {
@@ -326,7 +320,7 @@ __global__ __launch_bounds__(DFF_VIT_THREADS) void dff_vit_backtrack_kernel(HmmP
 __global__ __launch_bounds__(DFF_VIT_THREADS) void dff_vit_finish_kernel(const int* __restrict__ flags, long long n,
                                                                          int32_t* __restrict__ path, long long n_chains,
                                                                          double* __restrict__ chain_lp, int* __restrict__ status) {
-    const int st = flags[0] ? 1 : (flags[1] ? 3 : (flags[2] ? 2 : 0));
+    const int st = hmm_status(flags);
     const long long q = (long long)blockIdx.x * DFF_VIT_THREADS + threadIdx.x;
     if (q == 0) *status = st;
     if (st == 0) return;

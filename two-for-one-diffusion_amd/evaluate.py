@@ -3587,23 +3587,33 @@ class ChapmanKolmogorovEvaluator(_TrajectoryEvaluator):
 HMM_MAX_HIDDEN = binding.HMM_MAX_HIDDEN
 
 
-class _DeviceHmmEstep:
-    """estep(labels (n,) int32 tensor on the device, lengths, lag, A (m, m), B (m, K), p0 (m,), want_post=False) -> (stats
-    float64 host array, packed as dff_hmm_estep packs it, chain_loglik host array | None, post (n, m) float64 DEVICE tensor |
-    None, status int): one dff_hmm_estep call and one read-back of the packed statistics (the status is read only when they are
-    NaN).  The workspace is kept between calls."""
+class _DeviceHmm:
+    """What the three device solvers share: the device, a workspace that is kept between calls and only grows, and the upload
+    of a model's three host arrays as float64 tensors."""
 
     def __init__(self, device):
         self.device = torch.device(device)
         self._ws = None
 
-    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
-        dev = self.device
-        par = [torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev) for x in (A, B, p0)]
-        need = binding.hmm_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1])
+    def _workspace(self, need):
         if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-        res = binding.hmm_estep(labels, lengths, lag, *par, chain_loglik=want_post, post=want_post, workspace=self._ws)
+            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _upload(self, *arrays):
+        return [torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(self.device) for x in arrays]
+
+
+class _DeviceHmmEstep(_DeviceHmm):
+    """estep(labels (n,) int32 tensor on the device, lengths, lag, A (m, m), B (m, K), p0 (m,), want_post=False) -> (stats
+    float64 host array, packed as dff_hmm_estep packs it, chain_loglik host array | None, post (n, m) float64 DEVICE tensor |
+    None, status int): one dff_hmm_estep call and one read-back of the packed statistics (the status is read only when they are
+    NaN).  The workspace is kept between calls."""
+
+    def __call__(self, labels, lengths, lag, A, B, p0, want_post=False):
+        par = self._upload(A, B, p0)
+        ws = self._workspace(binding.hmm_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1]))
+        res = binding.hmm_estep(labels, lengths, lag, *par, chain_loglik=want_post, post=want_post, workspace=ws)
         stats = res["stats"].cpu().numpy()
         status = int(res["status"].cpu()) if np.isnan(stats[0]) else 0
         return stats, (res["chain_loglik"].cpu().numpy() if want_post else None), res["post"], status
@@ -3616,22 +3626,15 @@ def hmm_estep_solver(device):
     return _DeviceHmmEstep(device)
 
 
-class _DeviceHmmViterbi:
+class _DeviceHmmViterbi(_DeviceHmm):
     """viterbi(labels (n,) int32 tensor on the device, lengths, lag, la (m, m), lb (m, K), lp (m,), chain_order=False) -> (path
     int32 (n,) DEVICE tensor, chain_logprob host array (n_traj lag,), status int): one dff_hmm_viterbi call on LOG-parameters and
     one read-back of the log-probabilities and the status.  The workspace is kept between calls."""
 
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self._ws = None
-
     def __call__(self, labels, lengths, lag, la, lb, lp, chain_order=False):
-        dev = self.device
-        par = [torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev) for x in (la, lb, lp)]
-        need = binding.hmm_viterbi_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1])
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-        res = binding.hmm_viterbi(labels, lengths, lag, *par, chain_order=chain_order, chain_logprob=True, workspace=self._ws)
+        par = self._upload(la, lb, lp)
+        ws = self._workspace(binding.hmm_viterbi_workspace_bytes(int(labels.numel()), lengths, lag, par[1].shape[0], par[1].shape[1]))
+        res = binding.hmm_viterbi(labels, lengths, lag, *par, chain_order=chain_order, chain_logprob=True, workspace=ws)
         return res["path"], res["chain_logprob"].cpu().numpy(), int(res["status"].cpu())
 
 
@@ -3642,14 +3645,14 @@ def hmm_viterbi_solver(device):
     return _DeviceHmmViterbi(device)
 
 
-class _DeviceHmmFit:
+class _DeviceHmmFit(_DeviceHmm):
     """steps(...) of hmm_fit_solver on the GPU.  One float64 buffer holds A | B | p0 | pi | the state's 32 bytes | the
     log-likelihoods, so a call reads back once; it, the workspace and with them the parameters and the state of the fit stay
     on the device between the calls of one fit."""
 
     def __init__(self, device):
-        self.device = torch.device(device)
-        self._ws = self._buf = self._shape = None
+        super().__init__(device)
+        self._buf = self._shape = None
 
     def _views(self, m, K, n_steps):
         o = [int(v) for v in np.cumsum([0, m * m, m * K, m, m, 4])]
@@ -3673,11 +3676,9 @@ class _DeviceHmmFit:
         if state is None:                                            # a new fit: the parameters go up, the state is zeroed
             host = np.concatenate([np.ravel(np.asarray(x, np.float64)) for x in (A, B, p0)] + [np.full(m, np.nan), np.zeros(4)])
             self._buf[:o[5]] = torch.from_numpy(host).to(self.device)
-        need = binding.hmm_fit_workspace_bytes(int(labels.numel()), lengths, lag, m, K)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(binding.hmm_fit_workspace_bytes(int(labels.numel()), lengths, lag, m, K))
         binding.hmm_fit_steps(labels, lengths, lag, tA, tB, tp, reversible, n_steps, accuracy, rev_tol, rev_max_sweeps, state=tst,
-                              loglik=tll, stationary=tpi, workspace=self._ws)
+                              loglik=tll, stationary=tpi, workspace=ws)
         h = self._buf[:o[5] + n_steps].cpu().numpy()                 # the one read-back
         pi = h[o[3]:o[4]].copy()
         return (h[o[0]:o[1]].reshape(m, m).copy(), h[o[1]:o[2]].reshape(m, K).copy(), h[o[2]:o[3]].copy(), h[o[5]:].copy(),
