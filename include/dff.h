@@ -962,6 +962,49 @@ int dff_hmm_viterbi(int device, const int32_t* labels_dev, long long n, const lo
  * differences.  The outputs of a call that stopped early are unfinished. */
 int dff_debug_hmm_viterbi_stages(int stages);
 
+/* ---- Bootstrap error bars for the Jensen-Shannon metrics: the histogram of every resampling unit, and the JS of B weighted
+ * resamples x C channels against a reference histogram (csrc/dff_jsboot.hip; evaluate.py: unit_histograms, bootstrap_js,
+ * eval_bootstrap of the evaluators) ----
+ * A histogram is additive over frames, so the histogram of resample b is sum_u w[b][u] hist[u]: no frame is looked at again.
+ * The conventions of the Markov-model blocks hold: device pointers, `stream` only, no read-back, no synchronisation, refusals on
+ * the host before any device call, no floating-point atomics, no workgroup waits on another, bit-identical from call to call,
+ * independent of the workspace's prior contents and of how a batch of resamples is split.  Host tables reach the device as
+ * kernel arguments.  A channel is one histogram: a bead pair of the PWD metric, or a whole 2-D grid flattened as ix ny + iy.
+ * Limits of both calls: 1 <= U <= 65536 units, 1 <= C <= 2^18 channels, 1 <= nbins[c] <= ld <= 2^20, U C ld <= 2^32. */
+/* Bytes of device workspace the call below needs (the unit starts and nbins: (U + 1 + C) 64-bit words); -1 on bad arguments. */
+long long dff_unit_hist_workspace_bytes(int U, int C);
+/* hist_dev[u][c][k] = the number of frames t of unit u with bins_dev[t][c] == k.  bins_dev int32 (n, C): the bin of frame t in
+ * channel c; a value < 0 or >= nbins_host[c] is not counted.  unit_lengths_host (U): consecutive units that partition the n
+ * frames (zero-length units allowed; they must sum to n).  hist_dev uint32 (U, C, ld) is zeroed by the call, n == 0 included;
+ * entries from nbins[c] to ld stay 0.  n <= 2^31.  32-bit integer LDS atomics per workgroup, one workgroup per (unit, channel,
+ * tile of 8192 bins), each storing its own slice of the output: exact, whatever nbins[c].  workspace_dev 8-byte aligned. */
+int dff_unit_hist(int device, const int32_t* bins_dev, long long n, int C, const long long* unit_lengths_host, int U,
+                  const int32_t* nbins_host, int ld, uint32_t* hist_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Bytes of device workspace the call below needs: nbins, the units' channel totals and the reference sums, (C + U C + C) 64-bit
+ * words.  It does not depend on B or ld: no resampled histogram is ever written to memory.  -1 on bad arguments. */
+long long dff_resampled_js_workspace_bytes(int U, int C);
+/* js_dev[b][c] = the Jensen-Shannon divergence between resample b's histogram of channel c and the reference's.  hist_dev uint32
+ * (U, C, ld) as dff_unit_hist writes it (counts summing to at most 2^31 per channel); weights_dev uint32 (B, U), the
+ * multiplicity of unit u in resample b; ref_dev fp64 (C, ld), counts or densities, not normalised.  For k < nbins[c]:
+ *   h[k] = sum_u w[b][u] hist[u][c][k]    (uint64, exact: no sum can overflow)
+ *   tot = sum_k h[k],   p[k] = h[k] / tot + 1e-10,   q[k] = ref[c][k] / sum_k ref[c][k] + 1e-10,   m = (p + q) / 2
+ *   js[b][c] = 1/2 sum_k ( p ln(p / m) + q ln(q / m) )
+ * in fp64: the reference's js_divergence.  The sum over k is taken in one order that depends on nbins[c] alone (thread t of 256
+ * adds bins t, t + 256, ... in ascending order, the threads are added by a butterfly per wave and the four waves as
+ * (0 + 1) + (2 + 3)), likewise sum_k ref.  js is NaN, and confined to that (b, c), when tot == 0, when sum_k ref[c] is 0 or not
+ * finite, or when an entry of ref[c] is negative or not finite.  total_dev uint64 (B, C), may be NULL: tot, exact.
+ * 1 <= B <= 4096.  One workgroup per (channel, tile of 1, 2, 4 or 8 resamples), threads along the bins, the tile's weights in
+ * LDS, one 32 x 32 -> 64 multiply-add per (b, u, k).  workspace_dev 8-byte aligned, contents irrelevant. */
+int dff_resampled_js(int device, const uint32_t* hist_dev, int U, int C, int ld, const int32_t* nbins_host,
+                     const uint32_t* weights_dev, int B, const double* ref_dev, double* js_dev, uint64_t* total_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Host only: the resamples per workgroup a call with B resamples and C channels would take now (the power of two that holds min(B, 8),
+ * halved until the call has 512 workgroups, at least 1); -1 on bad arguments. */
+int dff_resampled_js_path_for(int B, int C);
+/* For tests and benchmarks, process-wide: 0 = the tile follows (B, C) (the default); 1, 2, 4 or 8 = that many resamples per
+ * workgroup.  Every tile gives the same bits. */
+int dff_debug_resampled_js_path(int path);
+
 const char* dff_last_error(void);
 const char* dff_version(void);
 

@@ -93,6 +93,12 @@ inside the chains of the lag, one step being --hmm-lag frames.
 --hmm-bootstrap B adds error bars from B bootstrap refits on the GPU (bootstrap_hmm, warm-started from the fitted model, whole
 trajectories resampled or with --hmm-block-frames N blocks of N >= 2 L frames, draws seeded by --hmm-bootstrap-seed S):
 "timescales_std", "lifetimes_std", "hidden_populations_std", "timescales_lo" / "timescales_hi" (95 %) and "bootstrap_failed".
+
+--js-bootstrap B [--block-frames F] [--js-blocks N] adds, under "js_bootstrap", block-bootstrap error bars of the JS metrics
+above (Evaluator.eval_bootstrap: the units' histograms once, B resamples scored on the GPU by dff_resampled_js): every key of
+the plain evaluation with "_lo" / "_hi" (95 % percentile interval), "_std" and "_bias" (mean over the resamples - point; a JS
+between finite histograms is biased upward), and "n_units", "n_resamples".  With --parallel-sim P the units are the P
+trajectories, or their blocks of F frames; without it the samples count as independent and are cut into N (256) blocks.
 """
 import argparse
 import json
@@ -577,8 +583,31 @@ def build_parser():
     ap.add_argument("--hmm-path", choices=("posterior", "viterbi"), default=None,
                     help="with --hmm: the per-frame hidden states whose dwell statistics are reported -- the argmax of the posterior "
                          "marginals on the frame-ordered series, or the Viterbi path with the dwells taken inside the lagged chains")
+    ap.add_argument("--js-bootstrap", type=number(int, lambda v: 1 <= v, "expected a number of resamples >= 1, got {text!r}"),
+                    default=None, metavar="B",
+                    help="also report block-bootstrap error bars of the JS metrics from B resamples (Evaluator.eval_bootstrap), "
+                         "under \"js_bootstrap\": <key>, <key>_lo / _hi (95 %%), _std, _bias, n_units, n_resamples; the units are "
+                         "the trajectories of --parallel-sim or their blocks, else --js-blocks blocks of the samples as given")
+    ap.add_argument("--block-frames", type=number(int, lambda v: v >= 1, "expected a block length >= 1 frame, got {text!r}"),
+                    default=None, metavar="F",
+                    help="with --js-bootstrap and --parallel-sim: resample blocks of F frames instead of whole trajectories")
+    ap.add_argument("--js-blocks", type=number(int, lambda v: v >= 1, "expected a number of blocks >= 1, got {text!r}"),
+                    default=None, metavar="N",
+                    help="with --js-bootstrap and without --parallel-sim: independent samples in N consecutive blocks (256)")
     ap.add_argument("--device", default="cuda:0")
     return ap
+
+
+def js_bootstrap_arguments(a):
+    """the options of --js-bootstrap are refused without it, --block-frames without the trajectories it cuts"""
+    if a.js_bootstrap is None:
+        if a.block_frames is not None or a.js_blocks is not None:
+            raise SystemExit("--block-frames and --js-blocks need --js-bootstrap")
+        return
+    if a.block_frames is not None and a.parallel_sim is None:
+        raise SystemExit("--block-frames needs --parallel-sim (the trajectories it cuts into blocks)")
+    if a.js_blocks is not None and a.parallel_sim is not None:
+        raise SystemExit("--js-blocks is for independent samples: with --parallel-sim the units are the trajectories or --block-frames")
 
 
 def main():
@@ -603,6 +632,7 @@ def main():
     passage_arguments(a)
     ck_arguments(a)
     hmm_arguments(a)
+    js_bootstrap_arguments(a)
     x = torch.load(a.samples, map_location="cpu").float().contiguous()
     ref = torch.load(a.ref_data, map_location="cpu").float() if a.ref_data else None
     fit = torch.load(a.tica_fit_data, map_location="cpu") if a.tica_fit_data else None
@@ -610,8 +640,15 @@ def main():
         fit = fit.float()
     elif fit is not None:
         fit = [torch.as_tensor(t).float() for t in fit]
-    res = evaluate.Evaluator(ref, None, a.mol, evalsetname=a.evalset, saved_ref_dir=a.saved_ref_dir,
-                             tica_fit_data=fit, tica_lagtime=a.lagtime, device=a.device).eval(x, 0)
+    ev = evaluate.Evaluator(ref, None, a.mol, evalsetname=a.evalset, saved_ref_dir=a.saved_ref_dir,
+                            tica_fit_data=fit, tica_lagtime=a.lagtime, device=a.device)
+    res = ev.eval(x, 0)
+    if a.js_bootstrap is not None:
+        lengths = [len(x) // a.parallel_sim] * a.parallel_sim if a.parallel_sim else None
+        if lengths is not None and sum(lengths) != len(x):
+            raise SystemExit(f"{len(x)} frames do not split into {a.parallel_sim} equal trajectories")
+        res["js_bootstrap"] = cleaned(ev.eval_bootstrap(x, traj_lengths=lengths, block_frames=a.block_frames,
+                                                        n_blocks=a.js_blocks or 256, n_resamples=a.js_bootstrap))
     if a.folded_pdb:
         mol = a.mol.lower()
         re = evaluate.RmsdEvaluator(mol, a.folded_pdb, saved_ref_dir=a.saved_ref_dir, device=a.device)

@@ -25,7 +25,8 @@ _EVALUATE = (
     "propagator", "msm_propagate", "msm_relaxation", "msm_autocorrelation", "MsmAutocorrelation", "pcca_memberships",
     "metastable_sets", "chapman_kolmogorov", "chapman_kolmogorov_of_models", "ChapmanKolmogorov", "ChapmanKolmogorovEvaluator",
     "hmm_estep_solver", "initial_hmm", "HiddenMarkovModel", "HmmEvaluator", "hmm_viterbi_solver", "hmm_chain_lengths",
-    "hmm_fit_solver", "resampled_labels", "bootstrap_hmm", "HmmBootstrap")
+    "hmm_fit_solver", "resampled_labels", "bootstrap_hmm", "HmmBootstrap",
+    "bin_indices_1d", "bin_indices_2d", "sample_units", "unit_histograms", "js_resampler", "bootstrap_js", "JsBootstrap")
 
 __all__ = ["binding", "specs", "weights", "DffLibraryError", "Model", "load_library", "SamplerWrapper",
            "num_to_groups", "sample_from_model", "GraphTransformer", "GaussianDiffusion",

@@ -169,6 +169,12 @@ SYMBOLS = {
     "dff_hmm_viterbi": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P,
                                   _P, C.c_size_t, _P]),
     "dff_debug_hmm_viterbi_stages": (C.c_int, [C.c_int]),
+    "dff_unit_hist_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_unit_hist": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "dff_resampled_js_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "dff_resampled_js": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dff_resampled_js_path_for": (C.c_int, [C.c_int, C.c_int]),
+    "dff_debug_resampled_js_path": (C.c_int, [C.c_int]),
     "dff_last_error": (C.c_char_p, []),
     "dff_debug_pair": (C.c_int, [_P, C.c_int]),
     "dff_debug_pair_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -520,9 +526,11 @@ def pwd_max(x, offset: int):
     return out
 
 
-def pwd_hist(x, offset: int, nbins, hmax):
+def pwd_hist(x, offset: int, nbins, hmax, out=None):
     """Per-pair histograms (torch.histc semantics, min=0, max=hmax[p], bins=nbins[p]) of the
-    pairwise distances of x (n, N, 3) -> int32 CUDA tensor (n_pairs, max(nbins)) of counts."""
+    pairwise distances of x (n, N, 3) -> int32 CUDA tensor (n_pairs, max(nbins)) of counts.  `out`: a contiguous int32 CUDA
+    tensor (n_pairs, ld >= max(nbins)) on x's device, a slice of a larger one for instance, to write into instead (it is
+    returned; columns from max(nbins) on are zeroed)."""
     import torch
     lib = load_library()
     x, n, N = _coords(x)
@@ -537,9 +545,13 @@ def pwd_hist(x, offset: int, nbins, hmax):
         raise ValueError("hmax must be finite and > 0")
     max_bins = int(nb.max())
     nb_d, hm_d = nb.to(x.device), hm.to(x.device)
-    out = torch.empty((npairs, max_bins), dtype=torch.int32, device=x.device)
+    if out is None:
+        out = torch.empty((npairs, max_bins), dtype=torch.int32, device=x.device)
+    elif not (_is_tensor(out, torch.int32, dim=2) and out.shape[0] == npairs and out.shape[1] >= max_bins
+              and out.device == x.device):
+        raise ValueError(f"out must be a contiguous int32 CUDA tensor ({npairs}, >= {max_bins}) on the structures' device")
     _check(lib, lib.dff_pwd_hist(x.device.index, _ptr(x), n, N, int(offset), _ptr(nb_d), _ptr(hm_d), max_bins,
-                                 max_bins, _ptr(out), _stream(x)), "dff_pwd_hist")
+                                 int(out.shape[1]), _ptr(out), _stream(x)), "dff_pwd_hist")
     return out
 
 
@@ -1540,3 +1552,92 @@ def hmm_viterbi(labels, lengths, lag: int, logtrans, logemit, loginit, chain_ord
                                     _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(logemit)),
            "dff_hmm_viterbi")
     return {"path": path, "chain_logprob": cl, "status": status}
+
+
+# ---- bootstrap of the Jensen-Shannon metrics (dff_unit_hist, dff_resampled_js) ----
+JS_MAX_UNITS = 65536
+JS_MAX_RESAMPLES = 4096
+
+
+def unit_hist_workspace_bytes(U: int, C: int) -> int:
+    return _workspace_bytes("dff_unit_hist_workspace_bytes", int(U), int(C))
+
+
+def _nbins32(nbins):
+    return np.ascontiguousarray(np.asarray(nbins, dtype=np.int32).reshape(-1))
+
+
+def unit_hist(bins, unit_lengths, nbins, ld=None, workspace=None):
+    """The histogram of every resampling unit (dff_unit_hist): bins int32 CUDA (n, C), the bin of frame t in channel c (< 0 or
+    >= nbins[c]: not counted); unit_lengths (U,) host, consecutive units summing to n; nbins (C,) host; ld the row stride
+    (default max(nbins)) -> int32 CUDA tensor (U, C, ld) of counts.  Exact.  `workspace` is a uint8 CUDA tensor (allocated
+    here when None)."""
+    import torch
+    lib = load_library()
+    if not _is_tensor(bins, torch.int32, dim=2):
+        raise ValueError("bins must be a contiguous int32 CUDA tensor of shape (n, C)")
+    n, Cn = int(bins.shape[0]), int(bins.shape[1])
+    un, nb = _lengths(unit_lengths), _nbins32(nbins)
+    if nb.size != Cn:
+        raise ValueError(f"nbins must hold one bin count per channel: {nb.size} for C = {Cn}")
+    ld = int(ld) if ld is not None else int(nb.max()) if nb.size else 0
+    U = int(un.size)
+    need = unit_hist_workspace_bytes(U, Cn)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=bins.device)
+    ok = 1 <= ld <= 1 << 20 and U * Cn * ld <= 1 << 32                 # what is allocated when the shape will be refused
+    out = torch.empty((U, Cn, ld) if ok else (1, 1, 1), dtype=torch.int32, device=bins.device)
+    _check(lib, lib.dff_unit_hist(bins.device.index, _ptr(bins), n, Cn, un.ctypes.data_as(C.c_void_p), U,
+                                  nb.ctypes.data_as(C.c_void_p), ld, _ptr(out), _ptr(workspace),
+                                  int(workspace.numel() * workspace.element_size()), _stream(bins)), "dff_unit_hist")
+    return out
+
+
+def resampled_js_workspace_bytes(U: int, C: int) -> int:
+    return _workspace_bytes("dff_resampled_js_workspace_bytes", int(U), int(C))
+
+
+def resampled_js(hist, nbins, weights, ref, total=True, workspace=None):
+    """The Jensen-Shannon divergence of B weighted resamples x C channels against a reference (dff_resampled_js): hist int32 or
+    uint32 CUDA (U, C, ld) as unit_hist gives it, nbins (C,) host, weights uint32 CUDA (B, U), ref float64 CUDA (C, ld) ->
+    (js float64 CUDA (B, C), total uint64 CUDA (B, C) or None).  js is NaN where a resample holds no count or the reference
+    channel cannot be normalised.  No resampled histogram is written to memory.  `workspace` is a uint8 CUDA tensor (allocated
+    here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(hist, torch.Tensor) and hist.is_cuda and hist.dtype in (torch.int32, torch.uint32) and hist.dim() == 3
+            and hist.is_contiguous()):
+        raise ValueError("hist must be a contiguous int32 or uint32 CUDA tensor of shape (U, C, ld)")
+    U, Cn, ld = (int(v) for v in hist.shape)
+    nb = _nbins32(nbins)
+    if nb.size != Cn:
+        raise ValueError(f"nbins must hold one bin count per channel: {nb.size} for C = {Cn}")
+    if not (_is_tensor(weights, torch.uint32, dim=2) and weights.shape[1] == U and weights.device == hist.device):
+        raise ValueError("weights must be a contiguous uint32 CUDA tensor of shape (B, U) on the histograms' device")
+    if not (_is_tensor(ref, torch.float64, (Cn, ld)) and ref.device == hist.device):
+        raise ValueError("ref must be a contiguous float64 CUDA tensor of shape (C, ld) on the histograms' device")
+    B = int(weights.shape[0])
+    need = resampled_js_workspace_bytes(U, Cn)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=hist.device)
+    js = torch.empty((B, Cn), dtype=torch.float64, device=hist.device)
+    tot = torch.empty((B, Cn), dtype=torch.uint64, device=hist.device) if total else None
+    _check(lib, lib.dff_resampled_js(hist.device.index, _ptr(hist), U, Cn, ld, nb.ctypes.data_as(C.c_void_p), _ptr(weights), B,
+                                     _ptr(ref), _ptr(js), _ptr(tot), _ptr(workspace),
+                                     int(workspace.numel() * workspace.element_size()), _stream(hist)), "dff_resampled_js")
+    return js, tot
+
+
+def debug_resampled_js_path(path: int):
+    """Tests and benchmarks only: 0 = the library's choice by (B, C); 1, 2, 4, 8 = that many resamples per workgroup."""
+    lib = load_library()
+    _check(lib, lib.dff_debug_resampled_js_path(int(path)), "dff_debug_resampled_js_path")
+
+
+def resampled_js_path_for(B: int, C: int) -> int:
+    """The resamples per workgroup resampled_js would take now for B resamples and C channels."""
+    lib = load_library()
+    r = int(lib.dff_resampled_js_path_for(int(B), int(C)))
+    if r < 0:
+        _check(lib, 1, "dff_resampled_js_path_for")
+    return r

@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi among them), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi, dff_unit_hist and dff_resampled_js among them), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <type_traits>
@@ -23,6 +23,7 @@
 #include "dff_hmm.hip"
 #include "dff_hmm_viterbi.hip"
 #include "dff_hmm_mstep.hip"
+#include "dff_jsboot.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Argument checks that several entry points share; `what` is the caller's name in the message
@@ -1892,6 +1893,154 @@ extern "C" int dff_hmm_viterbi(int device, const int32_t* labels, long long n, c
     const long long blocks = (most + DFF_VIT_THREADS - 1) / DFF_VIT_THREADS;
     hipLaunchKernelGGL(dff_vit_finish_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks < 1024 ? blocks : 1024))), dim3(DFF_VIT_THREADS),
                        0, stream, (const int*)(ws + lay.flags), n, path, n_chains, chain_logprob, status);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bootstrap of the Jensen-Shannon metrics: per-unit histograms, resample-and-score (dff_jsboot.hip)
+// ---------------------------------------------------------------------------------------------
+// which resample tile dff_resampled_js takes: 0 = by (B, C), else 1, 2, 4 or 8 resamples per workgroup
+static std::atomic<int> g_jsb_path{0};
+
+// the shape both calls share: units, channels, row stride, bins per channel (every one within the stride)
+static int jsb_check_shape(int U, int C, int ld, const int32_t* nbins, const char* what) {
+    if (U < 1 || U > DFF_JSB_MAXUNITS) return fail(DFF_EINVAL, "%s: the number of resampling units must be 1..%d", what, DFF_JSB_MAXUNITS);
+    if (C < 1 || C > DFF_JSB_MAXCHANNELS) return fail(DFF_EINVAL, "%s: the number of channels must be 1..%d", what, DFF_JSB_MAXCHANNELS);
+    if (ld < 1 || ld > DFF_JSB_MAXLD) return fail(DFF_EINVAL, "%s: the row stride ld must be 1..%d", what, DFF_JSB_MAXLD);
+    if ((long long)U * C * ld > DFF_JSB_MAXCELLS) return fail(DFF_EINVAL, "%s: U C ld must not exceed 2^32", what);
+    if (!nbins) return fail(DFF_EINVAL, "%s: null nbins", what);
+    for (int c = 0; c < C; ++c)
+        if (nbins[c] < 1 || nbins[c] > ld)
+            return fail(DFF_EINVAL, "%s: channel %d has %d bins, must be 1..ld = %d", what, c, (int)nbins[c], ld);
+    return DFF_OK;
+}
+
+static int jsb_check_counts(int U, int C, const char* what) {
+    if (U < 1 || U > DFF_JSB_MAXUNITS) return fail(DFF_EINVAL, "%s: the number of resampling units must be 1..%d", what, DFF_JSB_MAXUNITS);
+    if (C < 1 || C > DFF_JSB_MAXCHANNELS) return fail(DFF_EINVAL, "%s: the number of channels must be 1..%d", what, DFF_JSB_MAXCHANNELS);
+    return DFF_OK;
+}
+
+// nbins (C) as 64-bit words into dst, as kernel arguments
+static int jsb_upload_nbins(hipStream_t stream, const int32_t* nbins, int C, long long* dst) {
+    std::vector<long long> nb64(nbins, nbins + C);
+    return msmb_upload(stream, nb64.data(), C, dst);
+}
+
+extern "C" long long dff_unit_hist_workspace_bytes(int U, int C) {
+    if (jsb_check_counts(U, C, "unit_hist_workspace_bytes")) return -1;
+    return ((long long)U + 1 + C) * (long long)sizeof(long long);             // unit starts | nbins
+}
+
+extern "C" int dff_unit_hist(int device, const int32_t* bins, long long n, int C, const long long* unit_lengths, int U,
+                             const int32_t* nbins, int ld, uint32_t* hist, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "unit_hist";
+    if ((!bins && n > 0) || n < 0) return fail(DFF_EINVAL, "%s: null bins / negative count", what);
+    if (n > (1LL << 31)) return fail(DFF_EINVAL, "%s: more than 2^31 frames", what);
+    int rc = jsb_check_shape(U, C, ld, nbins, what);
+    if (rc) return rc;
+    if (!unit_lengths) return fail(DFF_EINVAL, "%s: null unit lengths", what);
+    long long total = 0;
+    for (int u = 0; u < U; ++u) {
+        if (unit_lengths[u] < 0) return fail(DFF_EINVAL, "%s: unit %d has negative length", what, u);
+        if (unit_lengths[u] > n - total) return fail(DFF_EINVAL, "%s: unit lengths sum to more than n = %lld", what, n);
+        total += unit_lengths[u];
+    }
+    if (total != n) return fail(DFF_EINVAL, "%s: unit lengths sum to %lld, not n = %lld", what, total, n);
+    if (!hist) return fail(DFF_EINVAL, "%s: null output", what);
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_unit_hist_workspace_bytes(U, C), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIPCHK(hipMemsetAsync(hist, 0, (size_t)U * C * ld * sizeof(uint32_t), stream));
+    if (n == 0) return DFF_OK;
+    std::vector<long long> tab((size_t)U + 1 + C);
+    tab[0] = 0;
+    int max_bins = 1;
+    for (int u = 0; u < U; ++u) tab[u + 1] = tab[u] + unit_lengths[u];
+    for (int c = 0; c < C; ++c) {
+        tab[(size_t)U + 1 + c] = nbins[c];
+        if (nbins[c] > max_bins) max_bins = nbins[c];
+    }
+    long long* tab_dev = (long long*)workspace;
+    if ((rc = msmb_upload(stream, tab.data(), (long long)tab.size(), tab_dev))) return rc;
+    const int tiles = (max_bins + DFF_JSB_TILE_BINS - 1) / DFF_JSB_TILE_BINS;
+    const long long items = (long long)U * C * tiles;                          // <= 2^32 / 8192 + 2^36: a grid-stride loop
+    hipLaunchKernelGGL(dff_unit_hist_kernel, dim3((unsigned)(items < (1 << 20) ? items : (1 << 20))), dim3(DFF_JSB_THREADS), 0, stream,
+                       bins, C, tab_dev, tab_dev + U + 1, ld, tiles, items, hist);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+// resamples per workgroup: the largest tile, of at most DFF_JSB_MAXTILE and no wider than B needs, that still gives the call DFF_JSB_WANT_WGS workgroups (a one-channel grid at a few
+// hundred resamples would otherwise run on a tenth of the chip); every tile gives the same bits
+static int jsb_tile(int B, int C) {
+    const int forced = g_jsb_path.load();
+    if (forced) return forced;
+    int tb = DFF_JSB_MAXTILE;
+    while (tb > 1 && tb / 2 >= B) tb >>= 1;                                    // no tile wider than the batch needs
+    while (tb > 1 && (long long)C * ((B + tb - 1) / tb) < DFF_JSB_WANT_WGS) tb >>= 1;
+    return tb;
+}
+
+static int jsb_check_resamples(int B, const char* what) {
+    if (B < 1 || B > DFF_JSB_MAXB) return fail(DFF_EINVAL, "%s: the number of resamples must be 1..%d", what, DFF_JSB_MAXB);
+    return DFF_OK;
+}
+
+extern "C" int dff_debug_resampled_js_path(int path) {
+    if (path != 0 && path != 1 && path != 2 && path != 4 && path != 8)
+        return fail(DFF_EINVAL, "debug_resampled_js_path: 0 (by shape) or 1, 2, 4, 8 resamples per workgroup");
+    g_jsb_path.store(path);
+    return DFF_OK;
+}
+
+extern "C" int dff_resampled_js_path_for(int B, int C) {
+    if (jsb_check_resamples(B, "resampled_js_path_for")) return -1;
+    if (jsb_check_counts(1, C, "resampled_js_path_for")) return -1;
+    return jsb_tile(B, C);
+}
+
+extern "C" long long dff_resampled_js_workspace_bytes(int U, int C) {
+    if (jsb_check_counts(U, C, "resampled_js_workspace_bytes")) return -1;
+    return ((long long)C + (long long)U * C + C) * 8;                          // nbins | unit totals (U, C) | reference sums
+}
+
+extern "C" int dff_resampled_js(int device, const uint32_t* hist, int U, int C, int ld, const int32_t* nbins, const uint32_t* weights,
+                                int B, const double* ref, double* js, uint64_t* total, void* workspace, size_t workspace_bytes,
+                                void* stream_) {
+    const char* what = "resampled_js";
+    int rc = jsb_check_shape(U, C, ld, nbins, what);
+    if (rc) return rc;
+    if ((rc = jsb_check_resamples(B, what))) return rc;
+    if (!hist || !weights || !ref || !js) return fail(DFF_EINVAL, "%s: null histograms / weights / reference / output", what);
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_resampled_js_workspace_bytes(U, C), what))) return rc;
+    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    long long* nb_dev = (long long*)workspace;
+    unsigned long long* utot = (unsigned long long*)(nb_dev + C);
+    double* refsum = (double*)(utot + (size_t)U * C);
+    if ((rc = jsb_upload_nbins(stream, nbins, C, nb_dev))) return rc;
+    const long long rows = (long long)U * C;
+    const long long tblocks = (rows + 3) / 4;
+    hipLaunchKernelGGL(dff_jsb_unit_totals_kernel, dim3((unsigned)(tblocks < (1 << 16) ? tblocks : (1 << 16))), dim3(DFF_JSB_THREADS), 0,
+                       stream, hist, rows, C, ld, (const long long*)nb_dev, utot);
+    hipLaunchKernelGGL(dff_jsb_ref_kernel, dim3((unsigned)C), dim3(DFF_JSB_THREADS), 0, stream, ref, ld, (const long long*)nb_dev, refsum);
+    const int tb = jsb_tile(B, C);
+    const dim3 grid((unsigned)(C >= 8 ? (C + 7) / 8 * 8 : C) * (unsigned)((B + tb - 1) / tb));
+    auto launch = [&](auto tile) {
+        hipLaunchKernelGGL(dff_resampled_js_kernel<decltype(tile)::value>, grid, dim3(DFF_JSB_THREADS), 0, stream, hist, U, C, ld,
+                           (const long long*)nb_dev, weights, B, ref, (const unsigned long long*)utot, (const double*)refsum, js,
+                           (unsigned long long*)total);
+    };
+    switch (tb) {
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        default: launch(std::integral_constant<int, 1>{}); break;
+    }
     HIPCHK(hipGetLastError());
     return DFF_OK;
 }

@@ -144,6 +144,53 @@ class PwdEvaluator:
             raise NotImplementedError("plotting (evaluators.py:289-349) is outside the hot path")
         return self.js_divergence_pwd(self.gt_hist, all_mol, self.gt_max, self.resolution)
 
+    def unit_histograms(self, samples, unit_lengths, max_bytes=2 << 30):
+        """(hist int32 CUDA (U, pairs, ld), nbins (pairs,), ref float64 (pairs, ld), units (U,)): the PWD histogram of every
+        unit, one dff_pwd_hist call per unit into its slice, with the bins of the point estimate (the max over gt_max and all
+        finite samples); ref is gt_hist padded with zeros.  The units are laid out on the frames as given; a frame with a
+        non-finite coordinate is dropped whole, as eval does, and makes its unit shorter (units: the lengths after that)."""
+        x = _to_device(samples, self.device)
+        units = np.asarray(unit_lengths, np.int64).reshape(-1)
+        if units.sum() != len(x) or (units < 0).any():
+            raise ValueError(f"PwdEvaluator: unit lengths add up to {int(units.sum())}, not to the {len(x)} frames given")
+        ok = torch.isfinite(x).all(dim=2).all(dim=1)
+        self.samples_nonfinite = int((~ok).sum())
+        if self.samples_nonfinite:
+            kept = np.concatenate(([0], np.cumsum(ok.cpu().numpy().astype(np.int64))))
+            ends = np.cumsum(units)
+            units = kept[ends] - kept[ends - units]
+            x = x[ok].contiguous()
+        if len(x) == 0:
+            raise ValueError(f"PwdEvaluator: no finite frame among the samples ({self.samples_nonfinite} with a non-finite coordinate)")
+        maxval = torch.maximum(torch.as_tensor(self.gt_max).float().cpu(), binding.pwd_max(x, self.offset).cpu())
+        nb = self._nbins(maxval, self.resolution, x.shape[1])
+        hmax = torch.tensor([self.resolution * int(b) for b in nb], dtype=torch.float64).float()
+        U, P, ld = len(units), len(nb), int(nb.max())
+        if U * P * ld * 4 > max_bytes:
+            raise ValueError(f"PwdEvaluator: the histograms of {U} units x {P} pairs x {ld} bins take {U * P * ld * 4} bytes, more "
+                             f"than max_bytes = {max_bytes}: lower n_blocks (fewer, longer units) or raise max_bytes")
+        hist = torch.empty((U, P, ld), dtype=torch.int32, device=self.device)
+        nb32, hm = nb.to(torch.int32).to(self.device), hmax.to(self.device)
+        start = 0
+        for u, ln in enumerate(units.tolist()):
+            binding.pwd_hist(x[start:start + ln], self.offset, nb32, hm, out=hist[u])
+            start += ln
+        ref = np.zeros((P, ld))
+        for p, hgt in enumerate(self.gt_hist):
+            m = min(len(hgt), ld)
+            ref[p, :m] = np.asarray(hgt, np.float64)[:m]
+        return hist, nb.numpy().astype(np.int32), ref, units
+
+    def eval_bootstrap(self, samples, traj_lengths=None, block_frames=None, n_blocks=256, n_resamples=200, seed=0, *,
+                       weights=None, unit_lengths=None, max_bytes=2 << 30):
+        """Block bootstrap of eval(): JsBootstrap over the bead pairs (values: the mean over pairs, as eval averages them).
+        Units: sample_units(n, traj_lengths, block_frames, n_blocks), or unit_lengths.  The bins per pair are the point
+        estimate's, fixed for every resample."""
+        units = _js_units(len(samples), traj_lengths, block_frames, n_blocks, unit_lengths)
+        hist, nb, ref, units = self.unit_histograms(samples, units, max_bytes)
+        return bootstrap_js(hist, nb, ref, n_resamples=n_resamples, seed=seed, weights=weights, unit_lengths=units,
+                            device=self.device)
+
 
 # =====================================================================================================
 # Structure metrics of the reference's evaluators (evaluate/evaluators.py: Evaluator :28-111,
@@ -560,6 +607,23 @@ class DihedralEnergiesEvaluator:
         probs = get_prob(self.torsions(all_mol), n_bins=self.n_bins)
         return dihedral_scores(probs, self.gt_probs)
 
+    def unit_histograms(self, samples, unit_lengths):
+        """(hist int32 CUDA (U, 1, (n_bins - 1)^2), nbins (1,), ref (1, (n_bins - 1)^2), units): the phi / psi histogram of
+        every unit on get_prob's grid, binned on the device; a frame without finite torsions is counted nowhere."""
+        tors = binding.struct_dihedrals(_frames(samples, self.device))[:, :2]
+        edges = np.linspace(-np.pi, np.pi, self.n_bins)
+        nb = np.array([(self.n_bins - 1) ** 2], np.int32)
+        units = np.asarray(unit_lengths, np.int64).reshape(-1)
+        return unit_histograms(bin_indices_2d(tors, edges, edges), nb, units), nb, np.asarray(self.gt_probs, np.float64).reshape(1, -1), units
+
+    def eval_bootstrap(self, samples, traj_lengths=None, block_frames=None, n_blocks=256, n_resamples=200, seed=0, *,
+                       weights=None, unit_lengths=None):
+        """Block bootstrap of eval()'s JS (the second of its four scores) on get_prob's grid -> JsBootstrap."""
+        units = _js_units(len(samples), traj_lengths, block_frames, n_blocks, unit_lengths)
+        hist, nb, ref, units = self.unit_histograms(samples, units)
+        return bootstrap_js(hist, nb, ref, n_resamples=n_resamples, seed=seed, weights=weights, unit_lengths=units,
+                            device=self.device)
+
 
 class TicEvaluator:
     """Drop-in for evaluate.evaluators.TicEvaluator with a saved reference (the reference's own
@@ -636,6 +700,23 @@ class TicEvaluator:
                 with open(name, "wb") as f:
                     np.save(f, arr)
         return js, None
+
+    def unit_histograms(self, samples, unit_lengths):
+        """(hist int32 CUDA (U, 1, nx ny), nbins (1,), ref (1, nx ny), units): the histogram of every unit's TIC projections on
+        the reference's grid, projected and binned on the device (flattened as ix ny + iy, like gt_prob.flatten())."""
+        proj = binding.struct_tic(_frames(samples, self.device), self.mean, self.coeff)
+        nb = np.array([(len(self.bin_edges_x) - 1) * (len(self.bin_edges_y) - 1)], np.int32)
+        units = np.asarray(unit_lengths, np.int64).reshape(-1)
+        bins = bin_indices_2d(proj[:, :2], self.bin_edges_x, self.bin_edges_y)
+        return unit_histograms(bins, nb, units), nb, np.asarray(self.gt_prob, np.float64).reshape(1, -1), units
+
+    def eval_bootstrap(self, samples, traj_lengths=None, block_frames=None, n_blocks=256, n_resamples=200, seed=0, *,
+                       weights=None, unit_lengths=None):
+        """Block bootstrap of eval()'s JS: one channel of (len(edges_x) - 1) (len(edges_y) - 1) bins -> JsBootstrap."""
+        units = _js_units(len(samples), traj_lengths, block_frames, n_blocks, unit_lengths)
+        hist, nb, ref, units = self.unit_histograms(samples, units)
+        return bootstrap_js(hist, nb, ref, n_resamples=n_resamples, seed=seed, weights=weights, unit_lengths=units,
+                            device=self.device)
 
 
 class RmsdEvaluator:
@@ -758,6 +839,25 @@ class Evaluator:
             with open(os.path.join(self.eval_folder, f"results-{milestone}.json"), "w") as f:
                 json.dump(dict_results, f)
         return dict_results
+
+    def eval_bootstrap(self, samples, traj_lengths=None, block_frames=None, n_blocks=256, n_resamples=200, seed=0,
+                       confidence=0.95):
+        """eval()'s keys with block-bootstrap error bars: "<key>" (the point estimate in fp64 on the bootstrap's bins: eval()'s
+        number up to its float32 rounding), "<key>_lo" / "_hi" (the percentile interval at `confidence`), "_std", "_bias"
+        (mean over the resamples - point), and "n_units", "n_resamples".  One weight matrix serves all metrics: they are
+        resampled jointly.  Nothing is written to eval_folder."""
+        units = sample_units(len(samples), traj_lengths, block_frames, n_blocks)
+        weights = bootstrap_weights(len(units), n_resamples, seed)
+        res = {}
+        kw = dict(unit_lengths=units, weights=weights)
+        if "alanine" in self.mol_name:
+            res.update(js_error_bars("Dihedral JS", self.dihedral_evaluator.eval_bootstrap(samples, **kw), confidence))
+        elif "protein_g" != self.mol_name.lower():
+            res.update(js_error_bars("TIC JS", self.tic.eval_bootstrap(samples, **kw), confidence))
+        if "protein_g" != self.mol_name.lower():
+            res.update(js_error_bars("PWD JS", self.pwd_evaluator.eval_bootstrap(samples, **kw), confidence))
+        res["n_units"], res["n_resamples"] = int(len(units)), int(weights.shape[0])
+        return res
 
 
 # =====================================================================================================
@@ -4176,3 +4276,176 @@ class HmmEvaluator(_TrajectoryEvaluator):
         res["log10_timescale_ratio"] = _log10_ratio(res["timescales"], ref["timescales"])
         res["log10_lifetime_ratio"] = _log10_ratio(res["lifetimes"], ref["lifetimes"])
         res["population_js"] = float(js_divergence(np.array(res["hidden_populations"]), np.array(ref["hidden_populations"])))
+
+
+# =====================================================================================================
+# Bootstrap error bars for the Jensen-Shannon metrics (PWD JS, TIC JS, Dihedral JS): a histogram is additive over frames, so
+# the histogram of a resample is the weighted sum of the resampling units' histograms and no frame is looked at again.
+# dff_unit_hist (or dff_pwd_hist per unit, whose bins are the reference's) gives the units' histograms once;
+# dff_resampled_js forms every resample's histogram on chip and reduces it to its JS against the reference histogram.
+# The bins are those of the point estimate, fixed for every resample.  The reference would give a resample whose largest
+# distance is smaller fewer PWD bins; here those bins stay, empty, and each adds a term of order 1e-10 to that pair's JS.
+# =====================================================================================================
+def _bin_axis(v, edges):
+    """searchsorted(edges, v, side="right") - 1 with numpy's histogramdd rule for explicit edges: a value equal to the last edge
+    goes into the last bin; outside, and NaN, give -1.  int64, on v's device."""
+    v = v.to(torch.float64)
+    e = torch.as_tensor(np.asarray(edges, np.float64) if not isinstance(edges, torch.Tensor) else edges).to(
+        device=v.device, dtype=torch.float64).contiguous()
+    if e.dim() != 1 or e.numel() < 2:
+        raise ValueError("bin edges must be a 1-D array of at least two values")
+    idx = torch.searchsorted(e, v.contiguous(), right=True) - 1
+    idx = torch.where(v == e[-1], torch.full_like(idx, e.numel() - 2), idx)
+    return torch.where((v >= e[0]) & (v <= e[-1]), idx, torch.full_like(idx, -1))
+
+
+def bin_indices_1d(values, edges):
+    """int32 (n,): the bin of every value in np.histogram(values, bins=edges), -1 where numpy counts nothing (outside the
+    edges, NaN).  torch, on the device `values` is on."""
+    v = torch.as_tensor(values)
+    return _bin_axis(v.reshape(-1), edges).to(torch.int32)
+
+
+def bin_indices_2d(xy, edges_x, edges_y):
+    """int32 (n,): ix * ny + iy, the flattened bin of every point (n, 2) in np.histogram2d(x, y, bins=[edges_x, edges_y]), -1
+    where numpy counts nothing.  torch, on the device `xy` is on."""
+    xy = torch.as_tensor(xy)
+    if xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError("bin_indices_2d: points must be (n, 2)")
+    ix, iy = _bin_axis(xy[:, 0], edges_x), _bin_axis(xy[:, 1], edges_y)
+    ny = len(edges_y) - 1
+    return torch.where((ix >= 0) & (iy >= 0), ix * ny + iy, torch.full_like(ix, -1)).to(torch.int32)
+
+
+def sample_units(n, traj_lengths=None, block_frames=None, n_blocks=256):
+    """The lengths (int64 array, summing to n) of the units a bootstrap of n frames resamples.  With traj_lengths: the
+    trajectories or their blocks, resampling_units(traj_lengths, block_frames).  Without, for independent samples:
+    min(n_blocks, n) consecutive near-equal blocks, the first n mod n_blocks one frame longer (any partition of
+    exchangeable samples is a valid unit set)."""
+    n = int(n)
+    if traj_lengths is not None:
+        units = resampling_units(_check_lengths(traj_lengths, n), block_frames)
+        if units.size == 0:
+            raise ValueError("sample_units: no frames")
+        return units
+    k = min(int(n_blocks), n)
+    if k < 1:
+        raise ValueError("sample_units: need n >= 1 frames and n_blocks >= 1")
+    units = np.full(k, n // k, np.int64)
+    units[: n % k] += 1
+    return units
+
+
+def unit_histograms(bins, nbins, unit_lengths):
+    """int32 CUDA (U, C, max(nbins)): the histogram of every unit and channel (dff_unit_hist).  bins int32 CUDA (n, C) or
+    (n,) for one channel, as bin_indices_1d / bin_indices_2d give them."""
+    bins = torch.as_tensor(bins)
+    if bins.dim() == 1:
+        bins = bins[:, None]
+    return binding.unit_hist(bins.to(torch.int32).contiguous(), unit_lengths, nbins)
+
+
+class _DeviceJsResampler:
+    """resample(unit_hist (U, C, ld), nbins (C,), ref (C, ld), weights (b, U)) -> (js float64 (b, C), total uint64 (b, C)) on
+    the host; the histograms and the reference go to the GPU once per distinct array."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._key, self._hist, self._ref, self._ws = None, None, None, None
+
+    def __call__(self, unit_hist, nbins, ref, weights):
+        if self._key is None or self._key[0] is not unit_hist or self._key[1] is not ref:
+            h = torch.as_tensor(unit_hist)
+            if h.dtype not in (torch.int32, torch.uint32):
+                h = h.to(torch.int32)
+            self._hist = h.to(self.device).contiguous()
+            self._ref = torch.as_tensor(np.asarray(ref, np.float64) if not isinstance(ref, torch.Tensor) else ref).to(
+                device=self.device, dtype=torch.float64).contiguous()
+            U, C = int(self._hist.shape[0]), int(self._hist.shape[1])
+            self._ws = torch.empty(max(binding.resampled_js_workspace_bytes(U, C), 8), dtype=torch.uint8, device=self.device)
+            self._key = (unit_hist, ref)
+        w = torch.from_numpy(np.ascontiguousarray(weights, np.uint32)).to(self.device)
+        js, tot = binding.resampled_js(self._hist, nbins, w, self._ref, workspace=self._ws)
+        return js.cpu().numpy(), tot.cpu().numpy()
+
+
+def js_resampler(device):
+    """resample(unit_hist, nbins, ref, weights) -> (js (b, C), total (b, C)) on the GPU (dff_resampled_js)."""
+    return _DeviceJsResampler(device)
+
+
+class JsBootstrap:
+    """What bootstrap_js returns.  per_channel (B, C): the JS of every resample and channel; values (B,): its mean over the
+    channels (as the reference averages the PWD pairs); point_per_channel (C,) and point: the same for the unresampled data
+    (all weights 1, through the same kernel); weights (B, U) and unit_lengths (U,) as resampled."""
+
+    def __init__(self, per_channel, point_per_channel, weights, unit_lengths):
+        self.per_channel, self.point_per_channel = per_channel, point_per_channel
+        self.values = per_channel.mean(axis=1)
+        self.point = float(point_per_channel.mean())
+        self.weights, self.unit_lengths = weights, unit_lengths
+
+    @property
+    def n_failed(self):
+        """Resamples whose value is not finite (a channel without a count)."""
+        return int(np.sum(~np.isfinite(self.values)))
+
+    def std(self):
+        """Standard deviation (ddof = 1) of the value over the resamples where it is finite; NaN below two."""
+        return float(percentile_std(self.values[:, None])[0])
+
+    def interval(self, confidence=0.95):
+        """The percentile interval (lo, hi) of the value over the resamples where it is finite."""
+        lo, hi = percentile_interval(self.values[:, None], confidence)
+        return float(lo[0]), float(hi[0])
+
+    def bias(self):
+        """mean(values) - point over the finite resamples: what finite histograms add to a JS, to first order."""
+        v = self.values[np.isfinite(self.values)]
+        return float(v.mean() - self.point) if v.size else float("nan")
+
+
+JS_RESAMPLE_BYTES = 1 << 28       # weights in flight per call of the resampler
+
+
+def bootstrap_js(unit_hist, nbins, ref_hist, *, n_resamples=200, seed=0, weights=None, resample_batch=None, unit_lengths=None,
+                 device=None):
+    """Bootstrap of a JS metric from the units' histograms: unit_hist (U, C, ld) integer counts (a CUDA tensor as
+    unit_histograms gives it, or an array), nbins (C,), ref_hist (C, ld) the reference histogram of every channel (counts or
+    densities).  The units are drawn with replacement n_resamples times (bootstrap_weights(U, n_resamples, seed), or
+    `weights` (B, U)); resample_batch bounds the resamples per call.  The split changes no bit -> JsBootstrap."""
+    U = int(unit_hist.shape[0])
+    nb = np.asarray(nbins, np.int32).reshape(-1)
+    if weights is None:
+        weights = bootstrap_weights(U, n_resamples, seed)
+    weights = np.ascontiguousarray(weights, np.uint32)
+    if weights.ndim != 2 or weights.shape[1] != U or weights.shape[0] < 1:
+        raise ValueError(f"bootstrap_js: weights must be (B, {U})")
+    B = weights.shape[0]
+    if device is None:
+        device = unit_hist.device if isinstance(unit_hist, torch.Tensor) and unit_hist.is_cuda else "cuda:0"
+    resample = js_resampler(device)
+    batch = int(resample_batch) if resample_batch else max(1, min(binding.JS_MAX_RESAMPLES, JS_RESAMPLE_BYTES // (4 * U)))
+    if batch < 1:
+        raise ValueError("bootstrap_js: resample_batch must be >= 1")
+    per = np.empty((B, nb.size))
+    for b0 in range(0, B, batch):
+        per[b0:b0 + batch] = resample(unit_hist, nb, ref_hist, weights[b0:b0 + batch])[0]
+    point = resample(unit_hist, nb, ref_hist, np.ones((1, U), np.uint32))[0][0]
+    units = None if unit_lengths is None else np.asarray(unit_lengths, np.int64)
+    return JsBootstrap(per, point, weights, units)
+
+
+def _js_units(n, traj_lengths, block_frames, n_blocks, unit_lengths):
+    if unit_lengths is not None:
+        units = np.asarray(unit_lengths, np.int64).reshape(-1)
+        if units.sum() != n or (units < 0).any() or units.size < 1:
+            raise ValueError(f"unit lengths must be non-negative and add up to the {n} frames given")
+        return units
+    return sample_units(n, traj_lengths, block_frames, n_blocks)
+
+
+def js_error_bars(key, boot, confidence=0.95):
+    """The keys Evaluator.eval_bootstrap adds for one metric, from its JsBootstrap: numpy only."""
+    lo, hi = boot.interval(confidence)
+    return {key: boot.point, key + "_lo": lo, key + "_hi": hi, key + "_std": boot.std(), key + "_bias": boot.bias()}
