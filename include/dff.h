@@ -366,7 +366,8 @@ long long dff_tica_workspace_bytes(int n_beads, long long n_frames_max, int lagt
  *   m0_dev (F, F) += sum a_t (g_t g_t^T + g_{t+lag} g_{t+lag}^T),   mt_dev (F, F) += sum a_t (g_t g_{t+lag}^T + g_{t+lag} g_t^T),
  * the matrices row-major, upper triangle (i <= j) only: the lower triangle is not touched.  Consecutive calls stream
  * trajectories (deeptime's partial_fit).  Deterministic: bit-identical from call to call, no atomics.
- * workspace_dev: >= dff_tica_workspace_bytes(N, n, lagtime) bytes.  4 <= N <= 64, lagtime >= 1. */
+ * workspace_dev: >= dff_tica_workspace_bytes(N, n, lagtime) bytes, 8-byte aligned (DFF_EINVAL otherwise: it holds the doubles
+ * of the partial sums), contents irrelevant.  4 <= N <= 64, lagtime >= 1. */
 int dff_tica_moments(int device, const float* x_dev, long long n, int n_beads, const long long* lengths_host, int n_traj,
                      int lagtime, const double* shift_dev, void* workspace_dev, size_t workspace_bytes, double* sx_dev,
                      double* sy_dev, double* m0_dev, double* mt_dev, void* stream);
@@ -400,7 +401,9 @@ long long dff_kmeans_workspace_bytes(long long n, int d, int K);
  * per-cluster coordinate sums, counts_dev (K) the member counts, inertia_dev (1) the sum of the smallest d2.  Every
  * output may be NULL; with the three accumulators NULL the call only assigns and needs no workspace.  Deterministic:
  * per-workgroup partials in the workspace, added in a fixed order by a second stage, no floating-point atomics --
- * bit-identical from call to call.  The k-means the presets of cell 21 were "determined via". */
+ * bit-identical from call to call.  The k-means the presets of cell 21 were "determined via".
+ * workspace_dev: >= dff_kmeans_workspace_bytes(n, d, K) bytes when it accumulates, 8-byte aligned (DFF_EINVAL otherwise: the
+ * partials are doubles), contents irrelevant. */
 int dff_kmeans_step(int device, const double* pts_dev, long long n, int d, const double* centers_dev, int K,
                     int32_t* labels_dev, double* dist2_dev, double* sums_dev, uint64_t* counts_dev, double* inertia_dev,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
@@ -438,7 +441,8 @@ long long dff_rmsd_nearest_workspace_bytes(long long n, long long m, int n_beads
  * Equal BIT FOR BIT to the row minimum and the first argmin of dff_rmsd_matrix (one per-pair routine serves both), and
  * bit-identical from call to call whatever the split of queries or candidates over workgroups and calls: the reduction is
  * an integer minimum over the keys (fp32 bits << 32 | index), no floating-point atomics.  m <= 2^31 - 1.
- * workspace_dev: >= dff_rmsd_nearest_workspace_bytes(n, m, n_beads) bytes. */
+ * workspace_dev: >= dff_rmsd_nearest_workspace_bytes(n, m, n_beads) bytes, 8-byte aligned (DFF_EINVAL otherwise: the keys are
+ * 64-bit words under an atomic minimum), contents irrelevant. */
 int dff_rmsd_nearest(int device, const float* x_dev, long long n, const float* y_dev, long long m, int n_beads,
                      long long self_first, float* rmsd_dev, long long* index_dev, void* workspace_dev,
                      size_t workspace_bytes, void* stream);

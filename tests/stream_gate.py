@@ -111,20 +111,27 @@ def poisoned(real, poison):
     return torch.full_like(real, poison)
 
 
+def device_of(spec):
+    """Where a Spec's buffers live: the GPU for every ABI call; the CPU for the stand-in calls of tests/test_fence.py's controls."""
+    return next(iter(spec.ins.values()))[0].device
+
+
 def reference(spec, nat=None):
     """Step 1: the call on the default stream with the real inputs, twice, bit-equal -> name -> result."""
+    dev = device_of(spec)
+    sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
     runs = []
     for _ in range(2):
         bufs = {k: real.clone() for k, (real, _) in spec.ins.items()}
         for k, (shape, dtype) in spec.outs.items():
-            bufs[k] = torch.full(shape, sentinel(dtype), dtype=dtype, device="cuda")
+            bufs[k] = torch.full(shape, sentinel(dtype), dtype=dtype, device=dev)
         bufs.update(spec.work)
         spec.fn(nat, bufs)
-        torch.cuda.synchronize()
+        sync()
         runs.append({k: bufs[k].clone() for k in spec.results})
     for k in spec.results:
         assert bits_equal(runs[0][k], runs[1][k]), f"{spec.name}: {k} differs between two default-stream calls"
-    torch.cuda.synchronize()
+    sync()
     return runs[0]
 
 

@@ -22,7 +22,8 @@ import torch
 
 from oracle.autocorr import Acf, lagged_sums, usable_mean
 from oracle.kinetics import native_q, scripted_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -215,6 +216,15 @@ def autocorr_spec():
 def test_stream_order_autocorr(gate, side):  # noqa: F811
     ref = analysis_call(autocorr_spec(), gate, side)
     assert int(ref["count"][0]) == AC_N and float(ref["sxy"][0].min()) > 0      # nothing like the zeros of the poison
+
+
+def test_fence_autocorr():
+    """The memory contract (tests/fence.py): every buffer in one arena, the (slots, K, lags) partials and the frames-left table
+    at exactly dff_autocorr_workspace_bytes."""
+    spec = autocorr_spec()
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
 
 
 # ---------------------------------------------------------------- 6. a known process

@@ -15,7 +15,8 @@ import torch
 
 from oracle import cluster as co
 from oracle.frames import integer_walks, noisy_ensemble, walks
-from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import RMSD_ATOL, RMSD_RTOL, B, dev, ev, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -353,6 +354,17 @@ def test_stream_order(N, gate, side):  # noqa: F811
     ref = analysis_call(gromos_spec(N), gate, side)
     k, left = ref["progress"].cpu().tolist()
     assert k >= 2 and int(ref["sizes"][0]) > 1 and int((ref["labels"] >= 0).sum()) == N_FRAMES - left
+
+
+@pytest.mark.parametrize("N", [10, 35, 61])
+@pytest.mark.parametrize("make", [neighbors_spec, gromos_spec], ids=["neighbors", "gromos"])
+def test_fence(make, N):
+    """The memory contract (tests/fence.py): 1000 frames = 15 full words and one of 40 bits per row of the bit-matrix; the alive
+    mask and the key of the greedy loop at exactly dff_gromos_workspace_bytes (restart = 1: the call initialises them)."""
+    spec = make(N)
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
 
 
 # ---------------------------------------------------------------- 8. the evaluator

@@ -315,6 +315,8 @@ def test_refused_arguments(dev):
 
     assert call(p(x), p(y), p(out), p(ws), need - 1) == 1 and b"workspace" in lib.dff_last_error()
     assert call(p(x), p(y), p(out), None, need) == 1
+    odd = torch.empty(need + 4, dtype=torch.uint8, device=dev)[4:]           # the keys are 64-bit words under an atomic minimum
+    assert call(p(x), p(y), p(out), p(odd), need) == 1 and b"the workspace must be 8-byte aligned" in lib.dff_last_error()
     assert call(p(x), p(y), None, p(ws), need) == 1 and b"null output" in lib.dff_last_error()
     assert call(None, p(y), p(out), p(ws), need) == 1
     assert call(p(x), None, p(out), p(ws), need) == 1

@@ -29,7 +29,8 @@ import torch
 import hmm_cases as hc
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -254,6 +255,16 @@ def test_the_call_is_ordered_on_its_stream(gate, side):
     ref = analysis_call(estep_spec(), gate, side)
     assert int(ref["status"][0]) == 0 and bool(torch.isfinite(ref["stats"]).all()) and bool(torch.isfinite(ref["post"]).all())
     assert float((ref["post"].sum(dim=1) - 1.0).abs().max()) < 1e-12
+
+
+def test_fence():
+    """The memory contract (tests/fence.py): all nine buffers in one arena; the sections of the workspace (trajectory table,
+    parameters, chunk products and carries, chain log-likelihoods, posteriors, emission counts) end at exactly
+    dff_hmm_workspace_bytes."""
+    spec = estep_spec()
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
 
 
 # ---------------------------------------------------------------- 7. the Python layer

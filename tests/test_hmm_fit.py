@@ -21,7 +21,8 @@ import torch
 import hmm_cases as hc
 import hmm_fit_cases as fc
 from oracle import msm as oracle
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -230,6 +231,16 @@ def test_the_call_is_ordered_on_its_stream(gate, side):
     st = B().hmm_fit_state_dict(ref["state"].cpu().numpy())
     assert st["n_estep"] == 3 and st["stop"] == 0 and bool(torch.isfinite(ref["loglik"]).all())
     assert abs(float(ref["pi"].sum()) - 1.0) < 1e-12 and float((ref["trans"].sum(dim=1) - 1.0).abs().max()) < 1e-12
+
+
+def test_fence():
+    """The memory contract (tests/fence.py): all nine buffers in one arena, the E-step's sections plus the packed statistics and
+    the status word at exactly dff_hmm_fit_workspace_bytes.  The state travels as eight int32 words; the header documents it as
+    8-byte aligned (it holds a double), so "tight" puts it at 8 mod 16."""
+    spec = fit_spec()
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref, align={"state": 8})
 
 
 # ---------------------------------------------------------------- 8. end to end: a two-well jump process

@@ -26,7 +26,8 @@ import hmm_cases as hc
 import viterbi_cases as vc
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from standins import HostViterbi
 from support import B, dev, ev, hmm_chunk, same_bits, to_dev  # noqa: F401  (dev)
 
@@ -297,6 +298,16 @@ def test_the_call_is_ordered_on_its_stream(gate, side):
     ref = analysis_call(viterbi_spec(), gate, side)
     assert int(ref["status"][0]) == 0 and int(ref["path"].min()) >= 0 and int(ref["path"].max()) < 3
     assert bool(torch.isfinite(ref["chain"][[0, 1, 4, 5]]).all()) and bool((ref["chain"][[2, 3]] == 0).all())
+
+
+def test_fence():
+    """The memory contract (tests/fence.py): all eight buffers in one arena; the sections of the workspace (trajectory table,
+    padded log-parameters, chunk products, entering deltas, back maps, end states, back-pointer words, chain results) end at
+    exactly dff_hmm_viterbi_workspace_bytes."""
+    spec = viterbi_spec()
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
 
 
 # ---------------------------------------------------------------- 7. the Python layer

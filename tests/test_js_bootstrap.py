@@ -12,7 +12,8 @@ import torch
 import js_cases as jc
 from oracle import frames
 from oracle import pwd_metric as om
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -292,3 +293,26 @@ def test_unit_hist_is_ordered_on_its_stream(gate, side):
 def test_resampled_js_is_ordered_on_its_stream(gate, side):
     ref = analysis_call(resampled_js_spec(), gate, side)
     assert bool(torch.isfinite(ref["js"]).all()) and int(ref["total"].min()) > 0
+
+
+def _fence(spec):
+    """The memory contract (tests/fence.py): both patterns at both placements against one reference."""
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
+
+
+def test_fence_unit_hist():
+    """the unit starts and nbins at exactly dff_unit_hist_workspace_bytes; 301 bins of ld 301: the last tile of bins is partial"""
+    _fence(unit_hist_spec())
+
+
+@pytest.mark.parametrize("tile", [0, 1, 2, 4, 8])
+def test_fence_resampled_js(tile):
+    """every tile of resamples (9 resamples: a partial last tile for 2, 4 and 8), the workspace at exactly
+    dff_resampled_js_workspace_bytes"""
+    B().debug_resampled_js_path(tile)
+    try:
+        _fence(resampled_js_spec())
+    finally:
+        B().debug_resampled_js_path(0)

@@ -16,7 +16,8 @@ import torch
 from oracle.kinetics import core_states, label_runs, native_q, scripted_frames
 from oracle.frames import chain_frames, noisy_ensemble, splitmix_labels
 from oracle.struct_metric import kabsch64_batch
-from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, on_device, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -430,3 +431,13 @@ def test_stream_order_label_runs(gate, side):  # noqa: F811
     spec, k = label_runs_spec()
     ref = analysis_call(spec, gate, side)
     assert int(ref["n_runs"]) == k > len(KIN_LENGTHS)               # the poison (constant labels) has one run per trajectory
+
+
+@pytest.mark.parametrize("make", [native_q_spec, core_states_spec, lambda: label_runs_spec()[0]], ids=["native_q", "core_states", "label_runs"])
+def test_fence(make):
+    """The memory contract (tests/fence.py): every buffer in one arena, the scans' carries at exactly
+    dff_kinetics_workspace_bytes, the run arrays at exactly the number of runs."""
+    spec = make()
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)

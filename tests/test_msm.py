@@ -26,7 +26,8 @@ import torch
 
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -437,6 +438,33 @@ def test_msm_reversible_steps_is_ordered_on_its_stream(K, forced, runs, gate, si
     finally:
         B().debug_msm_driver(0)
     assert bool(torch.isfinite(ref["x"]).all()) and bool((ref["err"] > 0).all())
+
+
+def _fence(spec):
+    """The memory contract (tests/fence.py): both patterns at both placements against one reference."""
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
+
+
+def test_fence_micro_kmeans_step():
+    """ceil(n / chunk) rows of K (d + 1) + 1 doubles, at exactly dff_micro_kmeans_workspace_bytes"""
+    _fence(micro_kmeans_step_spec())
+
+
+def test_fence_micro_transition_counts():
+    _fence(micro_transition_counts_spec())
+
+
+@pytest.mark.parametrize("forced", [0, LAUNCH_PER_SWEEP, ONE_WORKGROUP], ids=["default", "launch-per-sweep", "one-workgroup"])
+@pytest.mark.parametrize("K", [5, 33, 71])
+def test_fence_msm_reversible_steps(K, forced):
+    """two vectors of K doubles, under either driver; K = 71: a partial last stride of the 64 lanes of a row sum"""
+    B().debug_msm_driver(forced)
+    try:
+        _fence(msm_reversible_steps_spec(K))
+    finally:
+        B().debug_msm_driver(0)
 
 
 # ---------------------------------------------------------------- 5. end to end

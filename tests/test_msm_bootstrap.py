@@ -21,7 +21,8 @@ import torch
 from oracle import msm_bootstrap as boot
 from oracle import msm as oracle
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -327,6 +328,29 @@ def test_batched_sweeps_are_ordered_on_their_stream(forced, gate, side):
     finally:
         B().debug_msm_driver(0)
     assert bool(torch.isfinite(ref["x"]).all()) and bool((ref["err"][:, 1:] > 0).all())     # (problem 0 has one state: err = 0)
+
+
+def _fence(spec):
+    """The memory contract (tests/fence.py): both patterns at both placements against one reference."""
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
+
+
+def test_fence_resampled_counts():
+    """the trajectory and unit start tables at exactly dff_micro_resampled_counts_workspace_bytes"""
+    _fence(resampled_counts_spec())
+
+
+@pytest.mark.parametrize("forced", [0, 1, 2], ids=["default", "launch-per-sweep", "one-workgroup-per-problem"])
+def test_fence_batched_sweeps(forced):
+    """two vectors of B Kmax doubles and B descriptors at exactly dff_msm_batched_workspace_bytes, under either driver; what
+    lies beyond K_b in a problem's slot of x is neither read nor written: x is a result, compared whole"""
+    B().debug_msm_driver(forced)
+    try:
+        _fence(batched_spec())
+    finally:
+        B().debug_msm_driver(0)
 
 
 # ---------------------------------------------------------------- 4. bootstrap_msm

@@ -38,7 +38,8 @@ from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle import passage as po
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -427,6 +428,20 @@ def test_the_call_is_ordered_on_its_stream(forced, gate, side):
     finally:
         B().debug_msm_dirichlet_path(0)
     assert not bool(ref["status"].any()) and bool(torch.isfinite(ref["u"]).all()) and float(ref["u"].max()) > 1.0
+
+
+@pytest.mark.parametrize("forced", [LDS, GLOBAL, VALU, MFMA], ids=["lds", "global", "global-valu", "global-mfma"])
+def test_fence(forced):
+    """The memory contract (tests/fence.py) on every path: the descriptors and the P slices of Kmax (Kmax + 32) doubles at exactly
+    dff_msm_dirichlet_workspace_bytes -- the blocked paths factor inside them."""
+    B().debug_msm_dirichlet_path(forced)
+    try:
+        spec = dirichlet_spec()
+        ref = reference(spec)
+        for pattern, placement in COMBINATIONS:
+            fenced(spec, pattern=pattern, placement=placement, ref=ref)
+    finally:
+        B().debug_msm_dirichlet_path(0)
 
 
 # ---------------------------------------------------------------- 6. the Python layer

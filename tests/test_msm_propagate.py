@@ -35,7 +35,8 @@ import propagate_cases as pc
 from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle.frames import synth_chain_frames
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -319,6 +320,20 @@ def test_the_call_is_ordered_on_its_stream(forced, gate, side):
         B().debug_msm_propagate_path(BY_SIZE)
     assert not bool(ref["status"].any()) and bool(torch.isfinite(ref["out"]).all())
     assert float((ref["last"].sum(dim=2) - 1.0).abs().max()) < 1e-12          # stochastic T: the rows keep their sum
+
+
+@pytest.mark.parametrize("forced", [LDS, STREAMED], ids=["lds", "streamed"])
+def test_fence(forced):
+    """The memory contract (tests/fence.py) on both paths: all seven buffers in one arena, the P descriptors at exactly
+    dff_msm_propagate_workspace_bytes."""
+    B().debug_msm_propagate_path(forced)
+    try:
+        spec = propagate_spec()
+        ref = reference(spec)
+        for pattern, placement in COMBINATIONS:
+            fenced(spec, pattern=pattern, placement=placement, ref=ref)
+    finally:
+        B().debug_msm_propagate_path(BY_SIZE)
 
 
 # ---------------------------------------------------------------- 7. the Python layer

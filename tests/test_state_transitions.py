@@ -407,6 +407,8 @@ def test_states_abi_refuses_bad_arguments(dev):
     assert need > 0
     small = torch.empty(need - 8, dtype=torch.uint8, device=dev)
     refused(binding.kmeans_step, p, np.zeros((4, 2)), workspace=small)                       # workspace too small
+    with pytest.raises(ValueError, match="kmeans_step: the workspace must be 8-byte aligned"):  # the partials are doubles
+        binding.kmeans_step(p, np.zeros((4, 2)), workspace=torch.empty(need + 4, dtype=torch.uint8, device=dev)[4:])
     binding.kmeans_step(p, np.zeros((4, 2)), workspace=torch.empty(need, dtype=torch.uint8, device=dev))
     lab = torch.zeros(300, dtype=torch.int32, device=dev)
     refused(binding.transition_counts, lab, [300], (0,), 3)                                  # lag = 0

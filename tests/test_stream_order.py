@@ -5,6 +5,9 @@ process, the analysis calls, and two calls on two streams at once.  (dff_superpo
 The model calls run on the kernel variants of tests/test_noise_stream.py (same synthetic models, same knobs; every case asserts
 the kernel that ran).  A fresh model's first call ("cold") allocates, builds the layer-0 table and synchronises the stream:
 only its results are asserted; the identical second call ("warm") on the same model and stream must not block.
+
+Next to each stream test, test_fence_* runs the same Spec through the fence protocol of tests/fence.py: all buffers of the call in
+one arena between guard bands, workspaces at exactly their *_workspace_bytes, both fill patterns at both placements.
 """
 import contextlib
 import ctypes as C
@@ -15,6 +18,7 @@ import torch
 
 from oracle import synth
 from oracle.frames import splitmix_labels, synth_chain_frames
+from fence import COMBINATIONS, fenced
 from stream_gate import BLOCKING, GATE_MIN_MS, N_FRAMES, Run, Spec, analysis_call, gated, ptr, raw, reference, stream_of
 from stream_gate import gate, side  # noqa: F401  (fixtures)
 from support import to_dev
@@ -80,8 +84,32 @@ def test_control_the_protocol_catches_a_call_on_the_wrong_stream(gate, side):
     side.synchronize()
 
 
+def test_control_the_fence_sees_a_stray_device_write():
+    """The fence protocol (tests/fence.py; its controls run on the CPU in tests/test_fence.py) once on the device: a stand-in
+    `call` that also writes the one byte after its output -- inside the arena, so nothing is harmed -- fails the band check; on
+    the separate allocations of the reference run that byte is the allocator's padding and the stand-in leaves it alone."""
+    real = torch.arange(256, dtype=torch.float32, device="cuda") * 0.5 + 0.25
+
+    def good(_, b):
+        torch.add(b["x"], 1.0, out=b["y"])
+
+    def stray(_, b):
+        good(_, b)
+        yb = b["y"].view(torch.uint8)
+        o = yb.storage_offset() + yb.numel()
+        if o < yb.untyped_storage().nbytes():
+            torch.as_strided(yb, (1,), (1,), o).fill_(1)
+
+    def spec(fn):
+        return Spec("control", {"x": (real, float("nan"))}, {"y": ((256,), torch.float32)}, fn)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec(good), pattern=pattern, placement=placement)
+        with pytest.raises(AssertionError, match=r"guard band damaged: 1 byte\(s\), the first 1 byte\(s\) past the end of y"):
+            fenced(spec(stray), pattern=pattern, placement=placement)
+
+
 # ------------------------------------------------------------------------------------------------ the model calls
-# name -> (N, H, L, flags (intrinsic, distances, abs), conservative, weight seed): tests/test_noise_stream.py
+# name ->(N, H, L, flags (intrinsic, distances, abs), conservative, weight seed): tests/test_noise_stream.py
 MODELS = {
     "ala2": (5, 96, 2, (1, 0, 0), True, 1234),
     "chignolin": (10, 64, 3, (1, 0, 0), True, 1234),
@@ -253,6 +281,36 @@ def test_ddpm_run(case, supplied, gate, side):
     _model_call(case, ddpm_spec(case, supplied), gate, side)
 
 
+def _model_fence(case, spec):
+    """The memory contract (tests/fence.py) on the caller's buffers of a model call -- the model's own scratch is out of reach --
+    on the shared model, warmed by the reference call as in the stream test; every fenced call runs the kernel the case names."""
+    A = shared_native(case.model)
+    with case.knobs(A):
+        ref = reference(spec, A)
+        name = case.check_launch(A)
+        for pattern, placement in COMBINATIONS:
+            fenced(spec, A, pattern=pattern, placement=placement, ref=ref)
+            assert case.check_launch(A) == name
+        assert A.status() == 0
+
+
+@case_param
+def test_fence_score(case):
+    _model_fence(case, score_spec(case))
+
+
+@case_param
+@noise_param
+def test_fence_langevin_run(case, supplied):
+    _model_fence(case, langevin_spec(case, supplied))
+
+
+@case_param
+@noise_param
+def test_fence_ddpm_run(case, supplied):
+    _model_fence(case, ddpm_spec(case, supplied))
+
+
 # ------------------------------------------------------------------------------------------------ the forward process
 FAMILY = {"chignolin": S16, "trp_cage": S64}
 
@@ -324,6 +382,27 @@ def test_q_sample(model, B, supplied, gate, side):
 @noise_param
 def test_denoise_loss(model, B, supplied, gate, side):
     _forward_call(model, denoise_loss_spec(shared_native(model), model, B, supplied), gate, side)
+
+
+def _forward_fence(model, spec):
+    nat = shared_native(model)
+    ref = reference(spec, nat)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, nat, pattern=pattern, placement=placement, ref=ref)
+    assert nat.status() == 0
+
+
+@pytest.mark.parametrize("model,B", [("chignolin", 11), ("trp_cage", 5)])
+@noise_param
+def test_fence_q_sample(model, B, supplied):
+    _forward_fence(model, q_sample_spec(model, B, supplied))
+
+
+@pytest.mark.parametrize("model,B", [("chignolin", 11), ("trp_cage", 5)])
+@noise_param
+def test_fence_denoise_loss(model, B, supplied):
+    """(the workspace holds x_t, tnorm, the model output and the partial sums: at exactly dff_denoise_workspace_bytes)"""
+    _forward_fence(model, denoise_loss_spec(shared_native(model), model, B, supplied))
 
 
 def test_denoise_loss_two_passes_over_one_workspace(gate, side):
@@ -542,6 +621,52 @@ def test_tica_moments(N, lengths, lag, chunks, gate, side):
     k = len(np.unique(binding.tica_debug_plan(N, lengths, lag)[:, 0]))
     assert k >= 2 if chunks == 2 else k == 1
     analysis_call(tica_moments_spec(N, lengths, lag), gate, side)
+
+
+# ------------------------------------------------------------------------------------------------ the analysis calls, fenced
+def _fence(spec):
+    """Both patterns at both placements (tests/fence.py) against one reference."""
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)
+    return ref
+
+
+fence_beads_param = pytest.mark.parametrize("N", [10, 35, 61])       # 61: 183 floats per frame, a partial quad at every tile's end
+
+
+@fence_beads_param
+@pytest.mark.parametrize("make", [pwd_max_spec, pwd_hist_spec, struct_rmsd_spec, struct_dihedrals_spec, struct_tic_spec,
+                                  struct_contacts_spec, struct_tic_features_spec, struct_tic_assign_spec, rmsd_matrix_spec],
+                         ids=lambda f: f.__name__[:-5])
+def test_fence_analysis_call(make, N):
+    """1000 frames against 64-frame tiles (257 structures for the RMSD matrix).  Under "tight" the coordinates sit at 4 mod 16:
+    the tile loads take their scalar path, under "natural" the 16-byte one -- the same bits."""
+    _fence(make(N))
+
+
+@fence_beads_param
+@pytest.mark.parametrize("exclude_self", [False, True], ids=["all-candidates", "exclude-self"])
+def test_fence_rmsd_nearest(N, exclude_self):
+    _fence(rmsd_nearest_spec(N, exclude_self))
+
+
+def test_fence_kmeans_step():
+    _fence(kmeans_step_spec())
+
+
+def test_fence_transition_counts():
+    _fence(transition_counts_spec())
+
+
+@pytest.mark.parametrize("N,lengths,lag,chunks", [
+    (56, [1000] + [50] * 1000 + [1000], 100, 2),
+    (10, [600, 400], 10, 1),
+], ids=["two-chunks", "one-chunk"])
+def test_fence_tica_moments(N, lengths, lag, chunks):
+    """The workspace (features of a chunk, the slices' partial matrices and sums) at exactly dff_tica_workspace_bytes; the
+    accumulators are added to, so they are results as well."""
+    _fence(tica_moments_spec(N, lengths, lag))
 
 
 # ------------------------------------------------------------------------------------------------ two streams at once

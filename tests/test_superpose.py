@@ -21,7 +21,8 @@ import torch
 
 from oracle.frames import gaussian, half_turn, noisy_ensemble, rand_rot, synth_chain_frames
 from oracle.struct_metric import stats64, superpose64
-from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import GAP_MIN, MAX_EXCLUDED, MIRROR, RMSD_ATOL, RMSD_RTOL, B, dev, golden_frames, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -376,3 +377,14 @@ def superpose_spec(N):
 def test_stream_order(N, gate, side):  # noqa: F811
     ref = analysis_call(superpose_spec(N), gate, side)
     assert int(ref["count"]) == N_FRAMES and bool(torch.isfinite(ref["aligned"]).all())
+
+
+@pytest.mark.parametrize("N", [10, 35, 61])
+def test_fence(N):
+    """The memory contract (tests/fence.py): all nine buffers in one arena, the workspace at exactly
+    dff_superpose_workspace_bytes.  Under "tight" x and aligned sit at 4 mod 16: the tile load and the tile store take their
+    scalar paths (N = 61: 183 floats per frame, a partial quad at every tile's end under "natural")."""
+    spec = superpose_spec(N)
+    ref = reference(spec)
+    for pattern, placement in COMBINATIONS:
+        fenced(spec, pattern=pattern, placement=placement, ref=ref)

@@ -31,7 +31,8 @@ import pytest
 import torch
 
 import eig_cases as ec
-from stream_gate import Spec, analysis_call, gate, ptr, raw, side, stream_of  # noqa: F401  (gate, side: fixtures)
+from fence import COMBINATIONS, fenced
+from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, same_bits, to_dev  # noqa: F401  (dev)
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +201,20 @@ def test_the_call_is_ordered_on_its_stream(forced, gate, side):
         B().debug_sym_eig_path(BY_SIZE)
     assert not bool(ref["status"].any()) and bool(torch.isfinite(ref["v"]).all())
     assert float((ref["w"][:, 0] - 1.0).abs().max()) < 1e-12
+
+
+@pytest.mark.parametrize("forced", [LDS, WORKSPACE], ids=["lds", "workspace"])
+def test_fence(forced):
+    """The memory contract (tests/fence.py) on both paths: the state counts and the P slices of 4 + Kmax^2 doubles at exactly
+    dff_sym_eig_workspace_bytes -- the workspace path reduces inside them."""
+    B().debug_sym_eig_path(forced)
+    try:
+        spec = eig_spec()
+        ref = reference(spec)
+        for pattern, placement in COMBINATIONS:
+            fenced(spec, pattern=pattern, placement=placement, ref=ref)
+    finally:
+        B().debug_sym_eig_path(BY_SIZE)
 
 
 # ---------------------------------------------------------------- 4. the Python layer

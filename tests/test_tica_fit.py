@@ -395,6 +395,9 @@ def test_tica_abi_refuses_bad_arguments(dev):
         binding.tica_moments(x, [300], 0, *acc(F), workspace=big)                # lagtime 0
     with pytest.raises(ValueError):
         binding.tica_moments(x, [300], 10, *acc(F), workspace=big[:4096])        # workspace too small
+    odd = torch.empty(big.numel() + 4, dtype=torch.uint8, device=dev)[4:]        # room enough, at 4 mod 8: the partial sums are doubles
+    with pytest.raises(ValueError, match="tica_moments: the workspace must be 8-byte aligned"):
+        binding.tica_moments(x, [300], 10, *acc(F), workspace=odd)
     a = acc(F)
     binding.tica_moments(x, [300], 10, *a, workspace=big)                        # the same call with room: accepted
     assert all(bool((t == 0).all()) for t in a)                                  # zero frames -> zero moments

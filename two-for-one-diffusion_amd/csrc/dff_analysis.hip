@@ -350,6 +350,8 @@ extern "C" int dff_tica_moments(int device, const float* x, long long n, int N, 
     if (!shift || !sx || !sy || !m0 || !mt) return fail(DFF_EINVAL, "tica_moments: null shift / accumulator");
     const long long need = dff_tica_workspace_bytes(N, n, lagtime);
     if ((rc = check_workspace(workspace, workspace_bytes, need, "tica_moments"))) return rc;
+    // the partial matrices and sums are doubles, at offsets that are multiples of 256
+    if (need > 0 && (uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "tica_moments: the workspace must be 8-byte aligned");
     if (n == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -474,7 +476,7 @@ extern "C" int dff_kmeans_step(int device, const double* pts, long long n, int d
     if (int rc = kmeans_check_shape(n, d, K, "kmeans_step")) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     return kmeans_call(device, pts, n, d, centers, K, labels, dist2, sums, counts, inertia, workspace, workspace_bytes,
-                       dff_kmeans_workspace_bytes(n, d, K), 1, stream, "kmeans_step", [&](bool accumulate) -> int {
+                       dff_kmeans_workspace_bytes(n, d, K), sizeof(double), stream, "kmeans_step", [&](bool accumulate) -> int {
         const int per = K * d + K + 1, grid = kmeans_grid(n);
         double* part = accumulate ? (double*)workspace : nullptr;
         hipLaunchKernelGGL(dff_kmeans_step_kernel, dim3(grid), dim3(DFF_KM_THREADS),
@@ -604,6 +606,9 @@ extern "C" int dff_rmsd_nearest(int device, const float* x, long long n, const f
     if (self_first < -1) return fail(DFF_EINVAL, "rmsd_nearest: self_first must be -1 or a candidate index");
     const long long need = dff_rmsd_nearest_workspace_bytes(n, m, N);
     if ((rc = check_workspace(workspace, workspace_bytes, need, "rmsd_nearest"))) return rc;
+    // the keys are 64-bit words that an integer atomic minimum works on
+    if (need > 0 && (uintptr_t)workspace % sizeof(unsigned long long))
+        return fail(DFF_EINVAL, "rmsd_nearest: the workspace must be 8-byte aligned");
     if (n == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
