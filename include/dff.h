@@ -820,6 +820,24 @@ int dff_msm_propagate(int device, const double* t_dev, int n_mat, const int32_t*
  * above the limit is then refused), 2 = every problem with its matrix streamed from global memory. */
 int dff_debug_msm_propagate_path(int path);
 
+/* ---- What dff_msm_dirichlet_solve, dff_sym_eig_topk and dff_msm_propagate launch: at most two kernels, each one workgroup per
+ * problem, each taking the problems whose size lies in lo .. hi and leaving the others to the other launch.  A problem's size is
+ * K_p; for the Dirichlet solver it is the interior count, at most K_p - 1. */
+typedef struct {
+    int32_t launched;       /* 0: this launch does not happen, the other fields are 0 */
+    int32_t path;           /* 1 = LDS, 2 = the workspace / global memory */
+    int32_t lo, hi;         /* own_lo, own_hi as the kernel is handed them */
+    int32_t sized_for;      /* the size its dynamic LDS is computed for */
+    int32_t lds_bytes;
+} dff_msm_batch_launch;
+typedef struct {
+    dff_msm_batch_launch launch[2];   /* the LDS kernel's, then the other path's */
+} dff_msm_batch_plan;
+/* Host only, for tests, no GPU needed: the plan of `call` ("dirichlet", "eig" or "propagate") for P problems of ks_host[p] states
+ * under that call's debug path as it stands -- the function the call itself goes through.  It refuses what the call refuses about
+ * P, Kmax, ks_host and a forced LDS path, in the call's words. */
+int dff_debug_msm_batch_plan(const char* call, const int32_t* ks_host, int P, int Kmax, dff_msm_batch_plan* out);
+
 /* ---- Hidden Markov models: one E-step of Baum-Welch over all chains of a set of labelled trajectories, by a chunked
  * forward-backward (csrc/dff_hmm.hip; evaluate.py: hmm_estep_solver, HiddenMarkovModel, HmmEvaluator) ----
  * The model: m hidden states, 1 <= m <= DFF_HMM_MAXM, K observed symbols, 1 <= K <= DFF_MSM_MAXK; fp64 on the device: trans_dev

@@ -28,8 +28,8 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
+from tools_bench_msm import timed          # the protocol: HIP events, the minimum of five windows, max / min spread
 
-REPEATS = 5
 SWEEPS = 50
 SWEEP_STATES = (8, 64, 256, 1024)
 BATCHES = (16, 128)
@@ -38,24 +38,6 @@ COUNT_STATES = (64, 256, 1024)
 TRAJECTORIES = 80
 BLOCK = 1000
 LAG = 10
-
-
-def ev_time(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps * 1e-3
-
-
-def timed(fn, reps=20):
-    """(minimum in ms, max / min) over REPEATS windows"""
-    t = [ev_time(fn, reps) for _ in range(REPEATS)]
-    return min(t) * 1e3, max(t) / min(t)
 
 
 def counts_problem(K, seed):

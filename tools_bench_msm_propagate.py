@@ -26,31 +26,13 @@ import torch
 
 import dff_amd
 from dff_amd import binding, evaluate
+from tools_bench_msm import timed          # the protocol: HIP events, the minimum of five windows, max / min spread
 
-REPEATS = 5
 STATES = (64, 200, 256, 1024)
 BATCHES = (3, 16, 128, 600)
 STEPS = (5, 256)
 PEAK_FMA, PEAK_BYTES = 39.3e12, 8.0e12
 LAG = 10
-
-
-def ev_time(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps * 1e-3
-
-
-def timed(fn, reps=5):
-    """(minimum in ms, max / min) over REPEATS windows"""
-    t = [ev_time(fn, reps) for _ in range(REPEATS)]
-    return min(t) * 1e3, max(t) / min(t)
 
 
 def metastable(K, seed):

@@ -55,6 +55,15 @@ class DffLaunchPlan(C.Structure):
                                                                      "threads", "pair", "table")] + [("table_kernel", C.c_char_p)]
 
 
+class DffMsmBatchLaunch(C.Structure):
+    """dff_msm_batch_launch: one of the two launches of a batched solver (msm_batch_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("launched", "path", "lo", "hi", "sized_for", "lds_bytes")]
+
+
+class DffMsmBatchPlan(C.Structure):
+    _fields_ = [("launch", DffMsmBatchLaunch * 2)]
+
+
 class DffPwdPlan(C.Structure):
     """dff_pwd_plan: the launch layout of dff_pwd_hist (pwd_hist_plan)."""
     _fields_ = [(n, C.c_int32) for n in ("n_pairs", "tile_n", "pc_log2", "npc", "ldl", "lds_bytes")] + \
@@ -156,6 +165,7 @@ SYMBOLS = {
     "dff_msm_propagate": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P,
                                     _P, C.c_size_t, _P]),
     "dff_debug_msm_propagate_path": (C.c_int, [C.c_int]),
+    "dff_debug_msm_batch_plan": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int, C.POINTER(DffMsmBatchPlan)]),
     "dff_hmm_chunk": (C.c_int, []),
     "dff_hmm_plan": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "dff_hmm_workspace_bytes": (C.c_longlong, [C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -512,6 +522,28 @@ def _workspace_bytes(name, *args):
     return b
 
 
+def _workspace(workspace, device, symbol, *args, always=True):
+    """The workspace of a call: the caller's, or a new uint8 tensor of the bytes that the library's `symbol`(*args) asks for.
+    always: the symbol is asked for a caller's workspace too (its refusal is then the call's first); else only to size a new one."""
+    import torch
+    if workspace is not None and not always:
+        return workspace
+    need = _workspace_bytes(symbol, *args)
+    return workspace if workspace is not None else torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+
+
+def _nbytes(t) -> int:
+    return int(t.numel() * t.element_size())
+
+
+def _host_i32(values, count, name, what, per="problem", of="P"):
+    """`values` as a contiguous host int32 array of exactly `count` entries: "`name` must hold one `what` per `per`" otherwise."""
+    h = np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+    if h.size != count:
+        raise ValueError(f"{name} must hold one {what} per {per}: {h.size} for {of} = {count}")
+    return h
+
+
 def pwd_num_pairs(n_beads: int, offset: int) -> int:
     return int(load_library().dff_pwd_num_pairs(int(n_beads), int(offset)))
 
@@ -666,11 +698,10 @@ def tica_moments(x, lengths, lagtime: int, shift, sx, sy, m0, mt, workspace=None
                 and t.is_contiguous() and tuple(t.shape) == shape):
             raise ValueError(f"{name} must be a contiguous float64 tensor {shape} on {x.device}")
     ln = _lengths(lengths)
-    if workspace is None:
-        workspace = torch.empty(max(tica_workspace_bytes(N, n, lagtime), 1), dtype=torch.uint8, device=x.device)
+    workspace = _workspace(workspace, x.device, "dff_tica_workspace_bytes", N, n, int(lagtime), always=False)
     _check(lib, lib.dff_tica_moments(x.device.index, _ptr(x), n, N, ln.ctypes.data_as(C.c_void_p), int(ln.size),
                                      int(lagtime), _ptr(shift), _ptr(workspace),
-                                     int(workspace.numel() * workspace.element_size()), _ptr(sx),
+                                     _nbytes(workspace), _ptr(sx),
                                      _ptr(sy), _ptr(m0), _ptr(mt), _stream(x)), "dff_tica_moments")
     return workspace
 
@@ -730,7 +761,7 @@ def _is_tensor(t, dtype, shape=None, dim=None):
             and (shape is None or tuple(t.shape) == shape) and (dim is None or t.dim() == dim))
 
 
-def _kmeans_step(symbol, workspace_bytes, points, centers, accumulate, workspace):
+def _kmeans_step(symbol, bytes_symbol, points, centers, accumulate, workspace):
     import torch
     lib = load_library()
     if not _is_tensor(points, torch.float64, dim=2):
@@ -742,13 +773,11 @@ def _kmeans_step(symbol, workspace_bytes, points, centers, accumulate, workspace
            "dist2": torch.empty(n, dtype=torch.float64, device=points.device)}
     ws_bytes = 0
     if accumulate:
-        need = workspace_bytes(n, d, K)                         # refuses a bad d or K before anything is allocated
+        workspace = _workspace(workspace, points.device, bytes_symbol, n, d, K)   # refuses a bad d or K before anything is allocated
         out["sums"] = torch.empty((K, d), dtype=torch.float64, device=points.device)
         out["counts"] = torch.empty(K, dtype=torch.int64, device=points.device)
         out["inertia"] = torch.empty(1, dtype=torch.float64, device=points.device)
-        if workspace is None:
-            workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=points.device)
-        ws_bytes = int(workspace.numel() * workspace.element_size())
+        ws_bytes = _nbytes(workspace)
     else:
         workspace = None
     _check(lib, getattr(lib, symbol)(points.device.index, _ptr(points), n, d, _ptr(c), K, _ptr(out["labels"]),
@@ -761,7 +790,7 @@ def kmeans_step(points, centers, accumulate=True, workspace=None):
     """One Lloyd step over points (n, d) (contiguous float64 CUDA) with centers (K, d): a dict of labels int32 (n,),
     dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64 (1,) over the
     finite points (dff_kmeans_step: deterministic).  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
-    return _kmeans_step("dff_kmeans_step", kmeans_workspace_bytes, points, centers, accumulate, workspace)
+    return _kmeans_step("dff_kmeans_step", "dff_kmeans_workspace_bytes", points, centers, accumulate, workspace)
 
 
 def _transition_counts(symbol, labels, lengths, lagtimes, n_states):
@@ -810,13 +839,11 @@ def rmsd_nearest(x, y, self_first: int = -1, workspace=None):
     import torch
     lib = load_library()
     x, n, y, m, N = _two_ensembles(x, y)
-    need = rmsd_nearest_workspace_bytes(n, m, N)
-    if workspace is None:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    workspace = _workspace(workspace, x.device, "dff_rmsd_nearest_workspace_bytes", n, m, N)
     rmsd = torch.empty(n, dtype=torch.float32, device=x.device)
     index = torch.empty(n, dtype=torch.int64, device=x.device)
     _check(lib, lib.dff_rmsd_nearest(x.device.index, _ptr(x), n, _ptr(y), m, N, int(self_first), _ptr(rmsd), _ptr(index),
-                                     _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(x)),
+                                     _ptr(workspace), _nbytes(workspace), _stream(x)),
            "dff_rmsd_nearest")
     return rmsd, index
 
@@ -864,9 +891,8 @@ def superpose(x, ref, aligned=True, rot=False, rmsd=False, stats=False, out=None
         res["dsum"] = torch.empty((N, 3), dtype=torch.float64, device=x.device)
         res["dsq"] = torch.empty(N, dtype=torch.float64, device=x.device)
         res["count"] = torch.empty(1, dtype=torch.int64, device=x.device)
-        if workspace is None:
-            workspace = torch.empty(max(superpose_workspace_bytes(n, N), 8), dtype=torch.uint8, device=x.device)
-        ws_bytes = int(workspace.numel() * workspace.element_size())
+        workspace = _workspace(workspace, x.device, "dff_superpose_workspace_bytes", n, N, always=False)
+        ws_bytes = _nbytes(workspace)
     else:
         workspace = None
     _check(lib, lib.dff_superpose(x.device.index, _ptr(x), n, N, _ptr(r), _ptr(res.get("aligned")), _ptr(res.get("rot")),
@@ -953,10 +979,8 @@ def kinetics_workspace_bytes(n: int) -> int:
 
 
 def _kinetics_workspace(t, workspace):
-    import torch
-    if workspace is None:
-        workspace = torch.empty(max(kinetics_workspace_bytes(int(t.numel())), 8), dtype=torch.uint8, device=t.device)
-    return workspace, int(workspace.numel() * workspace.element_size())
+    workspace = _workspace(workspace, t.device, "dff_kinetics_workspace_bytes", int(t.numel()), always=False)
+    return workspace, _nbytes(workspace)
 
 
 def core_states(cv, lengths, lo: float, hi: float, return_core=False, workspace=None):
@@ -1032,9 +1056,7 @@ def autocorr(series, lengths, max_lag: int, shift=None, sx=True, sy=True, count=
                                   and shift.is_contiguous() and tuple(shift.shape) == (d,)):
         raise ValueError(f"shift must be a contiguous float64 tensor ({d},) on {series.device}")
     ln = _lengths(lengths)
-    need = autocorr_workspace_bytes(n, d, L)                    # refuses a bad d or max_lag before anything is allocated
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=series.device)
+    workspace = _workspace(workspace, series.device, "dff_autocorr_workspace_bytes", n, d, L)   # refuses a bad d or max_lag first
     f64 = dict(dtype=torch.float64, device=series.device)
     out = {"sxy": torch.empty((L + 1, d), **f64)}
     if sx:
@@ -1045,7 +1067,7 @@ def autocorr(series, lengths, max_lag: int, shift=None, sx=True, sy=True, count=
         out["count"] = torch.empty(L + 1, dtype=torch.int64, device=series.device)
     _check(lib, lib.dff_autocorr(series.device.index, _ptr(series), n, d, ln.ctypes.data_as(C.c_void_p), int(ln.size), L,
                                  _ptr(shift), _ptr(out["sxy"]), _ptr(out.get("sx")), _ptr(out.get("sy")),
-                                 _ptr(out.get("count")), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                 _ptr(out.get("count")), _ptr(workspace), _nbytes(workspace),
                                  _stream(series)), "dff_autocorr")
     return out
 
@@ -1070,7 +1092,7 @@ def micro_kmeans_step(points, centers, accumulate=True, workspace=None):
     labels int32 (n,), dist2 float64 (n,) and, with `accumulate`, sums float64 (K, d), counts int64 (K,), inertia float64
     (1,) over the finite points.  Labels and dist2 are kmeans_step's bits for K <= 64; the sums are taken in another
     (fixed) order.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
-    return _kmeans_step("dff_micro_kmeans_step", micro_kmeans_workspace_bytes, points, centers, accumulate, workspace)
+    return _kmeans_step("dff_micro_kmeans_step", "dff_micro_kmeans_workspace_bytes", points, centers, accumulate, workspace)
 
 
 def micro_transition_counts(labels, lengths, lagtimes, n_states: int):
@@ -1096,12 +1118,10 @@ def msm_reversible_steps(sym, rowc, x, n_steps: int, err=True, workspace=None):
             and sym.device == x.device and rowc.device == x.device):
         raise ValueError("sym (K, K), rowc (K,) and x (K,) must be contiguous float64 CUDA tensors on one device")
     n_steps = int(n_steps)
-    need = msm_workspace_bytes(K)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    workspace = _workspace(workspace, x.device, "dff_msm_workspace_bytes", K)
     e = torch.empty(max(n_steps, 0), dtype=torch.float64, device=x.device) if err else None
     _check(lib, lib.dff_msm_reversible_steps(x.device.index, _ptr(sym), _ptr(rowc), K, _ptr(x), n_steps, _ptr(e),
-                                             _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                             _ptr(workspace), _nbytes(workspace),
                                              _stream(x)), "dff_msm_reversible_steps")
     return e
 
@@ -1142,16 +1162,14 @@ def micro_resampled_counts(labels, lengths, unit_lengths, lag: int, K: int, weig
     if not (_is_tensor(weights, torch.uint32, dim=2) and weights.shape[1] == un.size and weights.device == labels.device):
         raise ValueError("weights must be a contiguous uint32 CUDA tensor of shape (B, n_units) on the labels' device")
     K, B = int(K), int(weights.shape[0])
-    need = micro_resampled_counts_workspace_bytes(int(ln.size), int(un.size))
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=labels.device)
+    workspace = _workspace(workspace, labels.device, "dff_micro_resampled_counts_workspace_bytes", int(ln.size), int(un.size))
     Ka = min(max(K, 1), MSM_MAX_STATES)                          # what is allocated when K or B will be refused
     Ba = min(max(B, 1), max((1 << 28) // (Ka * Ka), 1), MSM_MAX_BATCH)
     out = torch.empty((Ba, Ka, Ka), dtype=torch.uint64, device=labels.device)
     _check(lib, lib.dff_micro_resampled_counts(labels.device.index, _ptr(labels), int(labels.numel()),
                                                ln.ctypes.data_as(C.c_void_p), int(ln.size), un.ctypes.data_as(C.c_void_p),
                                                int(un.size), int(lag), K, _ptr(weights), B, _ptr(out), _ptr(workspace),
-                                               int(workspace.numel() * workspace.element_size()), _stream(labels)),
+                                               _nbytes(workspace), _stream(labels)),
            "dff_micro_resampled_counts")
     return out
 
@@ -1173,23 +1191,19 @@ def msm_reversible_steps_batched(S, c, ks, x, n_steps: int, skip=None, workspace
     if not (_is_tensor(x, f64, (B, Kmax)) and _is_tensor(S, f64, (B, Kmax, Kmax)) and _is_tensor(c, f64, (B, Kmax))
             and S.device == x.device and c.device == x.device):
         raise ValueError("S (B, Kmax, Kmax), c (B, Kmax) and x (B, Kmax) must be contiguous float64 CUDA tensors on one device")
-    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
-    if kh.size != B:
-        raise ValueError(f"ks must hold one state count per problem: {kh.size} for B = {B}")
+    kh = _host_i32(ks, B, "ks", "state count", of="B")
     sh = None
     if skip is not None:
         sh = np.ascontiguousarray(np.asarray(skip).reshape(-1) != 0).astype(np.uint8)
         if sh.size != B:
             raise ValueError(f"skip must hold one flag per problem: {sh.size} for B = {B}")
     n_steps = int(n_steps)
-    need = msm_batched_workspace_bytes(B, Kmax)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    workspace = _workspace(workspace, x.device, "dff_msm_batched_workspace_bytes", B, Kmax)
     e = torch.empty((max(n_steps, 0), B), dtype=torch.float64, device=x.device)
     _check(lib, lib.dff_msm_reversible_steps_batched(x.device.index, _ptr(S), _ptr(c), kh.ctypes.data_as(C.c_void_p),
                                                      sh.ctypes.data_as(C.c_void_p) if sh is not None else None, B, Kmax,
                                                      _ptr(x), n_steps, _ptr(e), _ptr(workspace),
-                                                     int(workspace.numel() * workspace.element_size()), _stream(x)),
+                                                     _nbytes(workspace), _stream(x)),
            "dff_msm_reversible_steps_batched")
     return e
 
@@ -1241,25 +1255,17 @@ def msm_dirichlet_solve(flux, ks, role, g, s, flux_of=None, u=None, workspace=No
             and s.device == role.device):
         raise ValueError("flux (M, Kmax, Kmax), g and s (P, Kmax) must be contiguous float64 and role (P, Kmax) contiguous int32 "
                          "CUDA tensors on one device")
-    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
-    if kh.size != P:
-        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
-    fh = None
-    if flux_of is not None:
-        fh = np.ascontiguousarray(np.asarray(flux_of, dtype=np.int32).reshape(-1))
-        if fh.size != P:
-            raise ValueError(f"flux_of must hold one matrix index per problem: {fh.size} for P = {P}")
+    kh = _host_i32(ks, P, "ks", "state count")
+    fh = _host_i32(flux_of, P, "flux_of", "matrix index") if flux_of is not None else None
     if u is None:
         u = torch.full((P, Kmax), float("nan"), dtype=f64, device=role.device)
     elif not (_is_tensor(u, f64, (P, Kmax)) and u.device == role.device):
         raise ValueError("u must be a contiguous float64 CUDA tensor of shape (P, Kmax) on the roles' device")
     status = torch.empty(P, dtype=torch.int32, device=role.device)
-    if workspace is None:
-        need = msm_dirichlet_workspace_bytes(P, Kmax)
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=role.device)
+    workspace = _workspace(workspace, role.device, "dff_msm_dirichlet_workspace_bytes", P, Kmax, always=False)
     _check(lib, lib.dff_msm_dirichlet_solve(role.device.index, _ptr(flux), M, fh.ctypes.data_as(C.c_void_p) if fh is not None else None,
                                             kh.ctypes.data_as(C.c_void_p), P, Kmax, _ptr(role), _ptr(g), _ptr(s), _ptr(u),
-                                            _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                            _ptr(status), _ptr(workspace), _nbytes(workspace),
                                             _stream(role)), "dff_msm_dirichlet_solve")
     return u, status
 
@@ -1297,19 +1303,16 @@ def sym_eig_topk(a, ks, k: int, vectors=False, workspace=None):
     P, Kmax = (int(a.shape[0]), int(a.shape[1])) if isinstance(a, torch.Tensor) and a.dim() == 3 else (-1, -1)
     if not _is_tensor(a, torch.float64, (P, Kmax, Kmax)):
         raise ValueError("a must be a contiguous float64 CUDA tensor of shape (P, Kmax, Kmax)")
-    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
-    if kh.size != P:
-        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
+    kh = _host_i32(ks, P, "ks", "state count")
     k = int(k)
     if not 1 <= k <= SYM_EIG_MAX_K:
         raise ValueError(f"k must be 1..{SYM_EIG_MAX_K}, not {k}")
     w = torch.empty((P, k), dtype=torch.float64, device=a.device)
     v = torch.full((P, k, Kmax), float("nan"), dtype=torch.float64, device=a.device) if vectors else None
     status = torch.empty(P, dtype=torch.int32, device=a.device)
-    if workspace is None:
-        workspace = torch.empty(max(sym_eig_workspace_bytes(P, Kmax), 8), dtype=torch.uint8, device=a.device)
+    workspace = _workspace(workspace, a.device, "dff_sym_eig_workspace_bytes", P, Kmax, always=False)
     _check(lib, lib.dff_sym_eig_topk(a.device.index, _ptr(a), kh.ctypes.data_as(C.c_void_p), P, Kmax, k, _ptr(w), _ptr(v),
-                                     _ptr(status), _ptr(workspace), int(workspace.numel() * workspace.element_size()),
+                                     _ptr(status), _ptr(workspace), _nbytes(workspace),
                                      _stream(a)), "dff_sym_eig_topk")
     return w, v, status
 
@@ -1354,14 +1357,8 @@ def msm_propagate(t, mat_of, ks, w0, obs, n_steps: int, want_last=False, workspa
             and w0.device == t.device and obs.device == t.device):
         raise ValueError("t (n_mat, Kmax, Kmax), w0 (P, M, Kmax) and obs (P, R, Kmax) must be contiguous float64 CUDA tensors on "
                          "one device")
-    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
-    if kh.size != P:
-        raise ValueError(f"ks must hold one state count per problem: {kh.size} for P = {P}")
-    mh = None
-    if mat_of is not None:
-        mh = np.ascontiguousarray(np.asarray(mat_of, dtype=np.int32).reshape(-1))
-        if mh.size != P:
-            raise ValueError(f"mat_of must hold one matrix index per problem: {mh.size} for P = {P}")
+    kh = _host_i32(ks, P, "ks", "state count")
+    mh = _host_i32(mat_of, P, "mat_of", "matrix index") if mat_of is not None else None
     S = int(n_steps)
     if not 0 <= S <= MSM_PROPAGATE_MAX_STEPS:
         raise ValueError(f"n_steps must be 0..{MSM_PROPAGATE_MAX_STEPS}, not {S}")
@@ -1372,13 +1369,24 @@ def msm_propagate(t, mat_of, ks, w0, obs, n_steps: int, want_last=False, workspa
     out = torch.empty((P, S + 1, M, R), dtype=f64, device=t.device)
     w_last = torch.full((P, M, Kmax), float("nan"), dtype=f64, device=t.device) if want_last else None
     status = torch.empty(P, dtype=torch.int32, device=t.device)
-    if workspace is None:
-        workspace = torch.empty(max(msm_propagate_workspace_bytes(P, Kmax, M, R), 8), dtype=torch.uint8, device=t.device)
+    workspace = _workspace(workspace, t.device, "dff_msm_propagate_workspace_bytes", P, Kmax, M, R, always=False)
     _check(lib, lib.dff_msm_propagate(t.device.index, _ptr(t), n_mat, mh.ctypes.data_as(C.c_void_p) if mh is not None else None,
                                       kh.ctypes.data_as(C.c_void_p), P, Kmax, _ptr(w0), M, _ptr(obs), R, S, _ptr(out),
                                       _ptr(w_last), _ptr(status), _ptr(workspace),
-                                      int(workspace.numel() * workspace.element_size()), _stream(t)), "dff_msm_propagate")
+                                      _nbytes(workspace), _stream(t)), "dff_msm_propagate")
     return out, w_last, status
+
+
+def msm_batch_plan(call: str, ks, Kmax: int) -> list:
+    """What `call` ("dirichlet", "eig" or "propagate") launches for problems of ks states in slots of Kmax under its debug path as it
+    stands: the LDS kernel's launch, then the other path's, each a dict of launched, path, lo, hi, sized_for, lds_bytes
+    (dff_debug_msm_batch_plan: host only, no GPU).  What the call refuses about ks raises here in the same words."""
+    lib = load_library()
+    kh = np.ascontiguousarray(np.asarray(ks, dtype=np.int32).reshape(-1))
+    plan = DffMsmBatchPlan()
+    _check(lib, lib.dff_debug_msm_batch_plan(str(call).encode(), kh.ctypes.data_as(C.c_void_p), int(kh.size), int(Kmax),
+                                             C.byref(plan)), "dff_debug_msm_batch_plan")
+    return [{n: int(getattr(l, n)) for n, _ in DffMsmBatchLaunch._fields_} for l in plan.launch]
 
 
 # ---- hidden Markov models: one E-step of Baum-Welch over all chains (dff_hmm_estep) ----
@@ -1413,11 +1421,9 @@ def _hmm_workspace_bytes(symbol, n, lengths, lag, m, K):
 
 
 def _hmm_workspace(symbol, n, lengths, lag, m, K, workspace, device):
-    """the workspace of a call: the caller's, or a new uint8 tensor of the size that `symbol` asks for (asked either way: it is
-    the call's first refusal)"""
-    import torch
-    need = _hmm_workspace_bytes(symbol, n, lengths, lag, m, K)
-    return workspace if workspace is not None else torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    """the workspace of a call (_workspace): `symbol` is asked either way, it is the call's first refusal"""
+    lh = _lengths(lengths)
+    return _workspace(workspace, device, symbol, int(n), lh.ctypes.data_as(C.c_void_p), int(lh.size), int(lag), int(m), int(K))
 
 
 def _hmm_arguments(labels, lengths, lag, trans, emit, init, names):
@@ -1462,7 +1468,7 @@ def hmm_estep(labels, lengths, lag: int, trans, emit, init, chain_loglik=True, p
     status = torch.empty(1, dtype=torch.int32, device=dev)
     _check(lib, lib.dff_hmm_estep(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
                                   _ptr(emit), _ptr(init), m, K, _ptr(stats), _ptr(cl), _ptr(pt), _ptr(status), _ptr(workspace),
-                                  int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_estep")
+                                  _nbytes(workspace), _stream(emit)), "dff_hmm_estep")
     return {"stats": stats, "chain_loglik": cl, "post": pt, "status": status}
 
 
@@ -1516,7 +1522,7 @@ def hmm_fit_steps(labels, lengths, lag: int, trans, emit, init, reversible, n_st
     _check(lib, lib.dff_hmm_fit_steps(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(trans),
                                       _ptr(emit), _ptr(init), m, K, int(bool(reversible)), n_steps, float(accuracy), float(rev_tol),
                                       int(rev_max_sweeps), _ptr(loglik), _ptr(stationary), _ptr(state), _ptr(workspace),
-                                      int(workspace.numel() * workspace.element_size()), _stream(emit)), "dff_hmm_fit_steps")
+                                      _nbytes(workspace), _stream(emit)), "dff_hmm_fit_steps")
     return {"loglik": loglik, "stationary": stationary, "state": state}
 
 
@@ -1549,7 +1555,7 @@ def hmm_viterbi(labels, lengths, lag: int, logtrans, logemit, loginit, chain_ord
     status = torch.empty(1, dtype=torch.int32, device=dev)
     _check(lib, lib.dff_hmm_viterbi(dev.index, _ptr(labels), n, lh.ctypes.data_as(C.c_void_p), int(lh.size), lag, _ptr(logtrans),
                                     _ptr(logemit), _ptr(loginit), m, K, _ptr(path), 1 if chain_order else 0, _ptr(cl), _ptr(status),
-                                    _ptr(workspace), int(workspace.numel() * workspace.element_size()), _stream(logemit)),
+                                    _ptr(workspace), _nbytes(workspace), _stream(logemit)),
            "dff_hmm_viterbi")
     return {"path": path, "chain_logprob": cl, "status": status}
 
@@ -1563,10 +1569,6 @@ def unit_hist_workspace_bytes(U: int, C: int) -> int:
     return _workspace_bytes("dff_unit_hist_workspace_bytes", int(U), int(C))
 
 
-def _nbins32(nbins):
-    return np.ascontiguousarray(np.asarray(nbins, dtype=np.int32).reshape(-1))
-
-
 def unit_hist(bins, unit_lengths, nbins, ld=None, workspace=None):
     """The histogram of every resampling unit (dff_unit_hist): bins int32 CUDA (n, C), the bin of frame t in channel c (< 0 or
     >= nbins[c]: not counted); unit_lengths (U,) host, consecutive units summing to n; nbins (C,) host; ld the row stride
@@ -1577,19 +1579,15 @@ def unit_hist(bins, unit_lengths, nbins, ld=None, workspace=None):
     if not _is_tensor(bins, torch.int32, dim=2):
         raise ValueError("bins must be a contiguous int32 CUDA tensor of shape (n, C)")
     n, Cn = int(bins.shape[0]), int(bins.shape[1])
-    un, nb = _lengths(unit_lengths), _nbins32(nbins)
-    if nb.size != Cn:
-        raise ValueError(f"nbins must hold one bin count per channel: {nb.size} for C = {Cn}")
+    un, nb = _lengths(unit_lengths), _host_i32(nbins, Cn, "nbins", "bin count", per="channel", of="C")
     ld = int(ld) if ld is not None else int(nb.max()) if nb.size else 0
     U = int(un.size)
-    need = unit_hist_workspace_bytes(U, Cn)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=bins.device)
+    workspace = _workspace(workspace, bins.device, "dff_unit_hist_workspace_bytes", U, Cn)
     ok = 1 <= ld <= 1 << 20 and U * Cn * ld <= 1 << 32                 # what is allocated when the shape will be refused
     out = torch.empty((U, Cn, ld) if ok else (1, 1, 1), dtype=torch.int32, device=bins.device)
     _check(lib, lib.dff_unit_hist(bins.device.index, _ptr(bins), n, Cn, un.ctypes.data_as(C.c_void_p), U,
                                   nb.ctypes.data_as(C.c_void_p), ld, _ptr(out), _ptr(workspace),
-                                  int(workspace.numel() * workspace.element_size()), _stream(bins)), "dff_unit_hist")
+                                  _nbytes(workspace), _stream(bins)), "dff_unit_hist")
     return out
 
 
@@ -1609,22 +1607,18 @@ def resampled_js(hist, nbins, weights, ref, total=True, workspace=None):
             and hist.is_contiguous()):
         raise ValueError("hist must be a contiguous int32 or uint32 CUDA tensor of shape (U, C, ld)")
     U, Cn, ld = (int(v) for v in hist.shape)
-    nb = _nbins32(nbins)
-    if nb.size != Cn:
-        raise ValueError(f"nbins must hold one bin count per channel: {nb.size} for C = {Cn}")
+    nb = _host_i32(nbins, Cn, "nbins", "bin count", per="channel", of="C")
     if not (_is_tensor(weights, torch.uint32, dim=2) and weights.shape[1] == U and weights.device == hist.device):
         raise ValueError("weights must be a contiguous uint32 CUDA tensor of shape (B, U) on the histograms' device")
     if not (_is_tensor(ref, torch.float64, (Cn, ld)) and ref.device == hist.device):
         raise ValueError("ref must be a contiguous float64 CUDA tensor of shape (C, ld) on the histograms' device")
     B = int(weights.shape[0])
-    need = resampled_js_workspace_bytes(U, Cn)
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=hist.device)
+    workspace = _workspace(workspace, hist.device, "dff_resampled_js_workspace_bytes", U, Cn)
     js = torch.empty((B, Cn), dtype=torch.float64, device=hist.device)
     tot = torch.empty((B, Cn), dtype=torch.uint64, device=hist.device) if total else None
     _check(lib, lib.dff_resampled_js(hist.device.index, _ptr(hist), U, Cn, ld, nb.ctypes.data_as(C.c_void_p), _ptr(weights), B,
                                      _ptr(ref), _ptr(js), _ptr(tot), _ptr(workspace),
-                                     int(workspace.numel() * workspace.element_size()), _stream(hist)), "dff_resampled_js")
+                                     _nbytes(workspace), _stream(hist)), "dff_resampled_js")
     return js, tot
 
 

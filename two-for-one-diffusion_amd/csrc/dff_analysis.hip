@@ -3,6 +3,7 @@
 // dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi, dff_unit_hist and dff_resampled_js among them), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -38,6 +39,13 @@ static int check_beads(int N, const char* what) {
 static int check_workspace(const void* workspace, size_t workspace_bytes, long long need, const char* what) {
     if (need > 0 && (!workspace || (long long)workspace_bytes < need))
         return fail(DFF_EINVAL, "%s: workspace of %zu bytes, %lld needed", what, workspace_bytes, need);
+    return DFF_OK;
+}
+
+// the same for a workspace the kernels read as 64-bit words
+static int check_workspace8(const void* workspace, size_t workspace_bytes, long long need, const char* what) {
+    if (int rc = check_workspace(workspace, workspace_bytes, need, what)) return rc;
+    if (need > 0 && (uintptr_t)workspace % 8) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
     return DFF_OK;
 }
 
@@ -667,9 +675,7 @@ extern "C" int dff_superpose(int device, const float* x, long long n, int N, con
     if (!ref && n > 0) return fail(DFF_EINVAL, "superpose: null reference structure");
     const bool stats = dsum || dsq || count;
     const long long need = stats ? dff_superpose_workspace_bytes(n, N) : 0;
-    if ((rc = check_workspace(workspace, workspace_bytes, need, "superpose"))) return rc;
-    if (need > 0 && (uintptr_t)workspace % sizeof(double))
-        return fail(DFF_EINVAL, "superpose: the workspace must be 8-byte aligned");
+    if ((rc = check_workspace8(workspace, workspace_bytes, need, "superpose"))) return rc;
     if (!stats && !aligned && !rot && !rmsd) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -930,9 +936,7 @@ extern "C" int dff_autocorr(int device, const double* series, long long n, int d
     if (!series && n > 0) return fail(DFF_EINVAL, "autocorr: null series");
     if (!sxy) return fail(DFF_EINVAL, "autocorr: null sxy");
     const long long need = dff_autocorr_workspace_bytes(n, d, max_lag);
-    if ((rc = check_workspace(workspace, workspace_bytes, need, "autocorr"))) return rc;
-    if (need > 0 && (uintptr_t)workspace % sizeof(double))
-        return fail(DFF_EINVAL, "autocorr: the workspace must be 8-byte aligned");
+    if ((rc = check_workspace8(workspace, workspace_bytes, need, "autocorr"))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     const size_t nlags = (size_t)max_lag + 1;
@@ -1116,8 +1120,7 @@ extern "C" int dff_msm_reversible_steps(int device, const double* sym, const dou
     if (rc) return rc;
     if (n_steps < 0) return fail(DFF_EINVAL, "msm_reversible_steps: negative n_steps");
     if (!sym || !rowc || !x) return fail(DFF_EINVAL, "msm_reversible_steps: null matrix / row counts / x");
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_workspace_bytes(K), "msm_reversible_steps"))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "msm_reversible_steps: the workspace must be 8-byte aligned");
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_msm_workspace_bytes(K), "msm_reversible_steps"))) return rc;
     if (n_steps == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -1181,9 +1184,8 @@ extern "C" int dff_micro_resampled_counts(int device, const int32_t* labels, lon
     }
     if (total != n) return fail(DFF_EINVAL, "%s: unit lengths sum to %lld, not n = %lld", what, total, n);
     if (!weights || !counts) return fail(DFF_EINVAL, "%s: null weights / counts", what);
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_micro_resampled_counts_workspace_bytes(n_traj, n_units), what)))
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_micro_resampled_counts_workspace_bytes(n_traj, n_units), what)))
         return rc;
-    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipMemsetAsync(counts, 0, (size_t)B * K * K * sizeof(uint64_t), stream));
@@ -1216,6 +1218,104 @@ extern "C" int dff_msm_batched_driver_for(int B, int Kmax) {
     return msm_driver(Kmax, B);
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the batched solvers share: the problem table, the path knobs, the two-path launch
+// ---------------------------------------------------------------------------------------------
+// The problem table of a call (dff_msm_table.h), checked and packed on the host: one word per live problem, in order.
+struct MsmTable {
+    std::vector<long long> desc;
+    int kmin_live = DFF_MSM_MAXK, kmax_live = 0;
+
+    // ks[0 .. P - 1] against Kmax.  slot_of (null: problem p takes slot p) against n_slots, `noun` naming what a slot holds; a
+    // null noun: the table carries no slots, bare counts.  agree: problems that share a slot must agree on K_p.  forced_max > 0:
+    // the largest K_p a forced LDS path takes.  skip (or null): problems that are checked, but not live.  Refusals problem by problem.
+    int build(const char* what, const int32_t* ks, int P, int Kmax, const int32_t* slot_of, int n_slots, const char* noun, bool agree,
+              int forced_max, const uint8_t* skip) {
+        std::vector<int> k_of(agree ? (size_t)n_slots : 0, 0);
+        desc.reserve((size_t)P);
+        for (int p = 0; p < P; ++p) {
+            const int K = ks[p], slot = slot_of ? slot_of[p] : p;
+            if (K < 1 || K > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, K, Kmax);
+            if (slot_of && (slot < 0 || slot >= n_slots))
+                return fail(DFF_EINVAL, "%s: problem %d takes %s %d of %d", what, p, noun, slot, n_slots);
+            if (agree) {
+                int& km = k_of[(size_t)slot];
+                if (km && km != K)
+                    return fail(DFF_EINVAL, "%s: problem %d reads %s %d with %d states, an earlier problem with %d", what, p, noun, slot, K, km);
+                km = K;
+            }
+            if (forced_max && K > forced_max)
+                return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, K, forced_max);
+            if (skip && skip[p]) continue;
+            desc.push_back(msm_problem_pack(noun ? slot : 0, K));
+            if (K > kmax_live) kmax_live = K;
+            if (K < kmin_live) kmin_live = K;
+        }
+        return DFF_OK;
+    }
+    int upload(hipStream_t stream, long long* dst) const { return msmb_upload(stream, desc.data(), (long long)desc.size(), dst); }
+};
+
+// a process-wide debug knob that names a path, 0 .. max; anything else is refused with `refusal`
+struct PathKnob {
+    const int max;
+    const char* const refusal;
+    std::atomic<int> value{0};
+    int set(int path) {
+        if (path < 0 || path > max) return fail(DFF_EINVAL, "%s", refusal);
+        value.store(path);
+        return DFF_OK;
+    }
+};
+
+// What differs between the three two-path calls.  A problem's SIZE is what its kernel compares with own_lo .. own_hi: K_p, or
+// for the Dirichlet solver the interior count, at most K_p - 1 and known on the device only.
+struct MsmTwoPath {
+    const char* name;                   // as dff_debug_msm_batch_plan takes it
+    const char* what;                   // the call, as its refusals name it
+    PathKnob* knob;                     // 0 = by size, 1 = LDS, 2 (and above) = the other path
+    int limit;                          // the largest size of the LDS path
+    int size_off;                       // a problem's size is at most K_p - size_off
+    int lo_all, hi_all;                 // own_lo / own_hi of "every size", as the kernels are handed them
+    bool on_device;                     // sizes are found on the device: the LDS launch does not wait for a small K_p, and when
+                                        // forced it takes hi_all
+    size_t (*lds_bytes)(int size, bool ldsp);
+    int forced_max(int path) const { return path == 1 ? limit + size_off : 0; }   // MsmTable::build's, in K_p
+};
+
+// THE selection rule of the three calls: launch[0] is the LDS kernel's, launch[1] the other path's.  Pure host arithmetic.
+static dff_msm_batch_plan msm_two_path(const MsmTwoPath& r, int knob, int kmin_live, int kmax_live) {
+    const int path = knob > 2 ? 2 : knob;
+    dff_msm_batch_plan plan = {};
+    if (path == 1 || (path == 0 && (r.on_device || kmin_live <= r.limit))) {
+        const int size = kmax_live - r.size_off < r.limit ? kmax_live - r.size_off : r.limit;
+        plan.launch[0] = {1, 1, r.lo_all, path == 1 && r.on_device ? r.hi_all : r.limit, size, (int32_t)r.lds_bytes(size, true)};
+    }
+    if (path == 2 || (path == 0 && kmax_live > r.limit)) {          // in K_p, whatever the size measure
+        const int size = kmax_live - r.size_off;
+        plan.launch[1] = {1, 2, path == 2 ? r.lo_all : r.limit + 1, r.hi_all, size, (int32_t)r.lds_bytes(size, false)};
+    }
+    return plan;
+}
+
+// one planned launch, one workgroup per problem; the kernel's arguments as the caller lists them (own_lo and own_hi among them)
+template <class... Params, class... Args>
+static int msm_launch_planned(void (*kernel)(Params...), const dff_msm_batch_launch& l, int P, int threads, hipStream_t stream,
+                              Args... args) {
+    if (!l.launched) return DFF_OK;
+    if (l.lds_bytes > 64 * 1024)                                      // more than a launch gets unasked
+        HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)P), dim3((unsigned)threads), (unsigned)l.lds_bytes, stream, args...);
+    HIPCHK(hipGetLastError());
+    return DFF_OK;
+}
+
+static_assert(DFF_DIR_MAXP == DFF_EIG_MAXP && DFF_DIR_MAXP == DFF_PROP_MAXP, "one problem count for the batched solvers");
+static int solver_check_batch(int P, int Kmax, const char* what) {
+    if (P < 1 || P > DFF_DIR_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_DIR_MAXP);
+    return micro_check_count(Kmax, what, "states");
+}
+
 extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, const double* rowc, const int32_t* ks,
                                                 const uint8_t* skip, int B, int Kmax, double* x, int n_steps, double* err,
                                                 void* workspace, size_t workspace_bytes, void* stream_) {
@@ -1225,189 +1325,123 @@ extern "C" int dff_msm_reversible_steps_batched(int device, const double* sym, c
     if ((rc = micro_check_count(Kmax, what, "states"))) return rc;
     if (n_steps < 0) return fail(DFF_EINVAL, "%s: negative n_steps", what);
     if (!sym || !rowc || !x || !ks) return fail(DFF_EINVAL, "%s: null matrices / row counts / x / state counts", what);
-    for (int b = 0; b < B; ++b)
-        if (ks[b] < 1 || ks[b] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, b, (int)ks[b], Kmax);
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_batched_workspace_bytes(B, Kmax), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    MsmTable live;
+    if ((rc = live.build(what, ks, B, Kmax, nullptr, B, "matrix", false, 0, skip))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_msm_batched_workspace_bytes(B, Kmax), what))) return rc;
     if (n_steps == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     if (err) HIPCHK(hipMemsetAsync(err, 0, (size_t)n_steps * B * sizeof(double), stream));
-    std::vector<long long> live;
-    int kmax_live = 0;
-    for (int b = 0; b < B; ++b)
-        if (!skip || !skip[b]) {
-            live.push_back(MsmLive::descriptor(b, ks[b]));
-            if (ks[b] > kmax_live) kmax_live = ks[b];
-        }
-    if (live.empty()) return DFF_OK;
+    if (live.desc.empty()) return DFF_OK;
     double* q0 = (double*)workspace;
     long long* live_dev = (long long*)(q0 + 2 * (size_t)B * Kmax);
-    if ((rc = msmb_upload(stream, live.data(), (long long)live.size(), live_dev))) return rc;
-    const int n_live = (int)live.size();
-    return msm_sweeps(stream, MsmLive{live_dev, Kmax, B}, msm_driver(kmax_live, n_live), kmax_live, (unsigned)n_live, sym, rowc, x,
-                      n_steps, q0, q0 + (size_t)B * Kmax, (unsigned long long*)err);
+    if ((rc = live.upload(stream, live_dev))) return rc;
+    const int n_live = (int)live.desc.size();
+    return msm_sweeps(stream, MsmLive{live_dev, Kmax, B}, msm_driver(live.kmax_live, n_live), live.kmax_live, (unsigned)n_live, sym,
+                      rowc, x, n_steps, q0, q0 + (size_t)B * Kmax, (unsigned long long*)err);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Mean first-passage times and committors: the Dirichlet problem on a flux matrix (dff_msm_passage.hip)
 // ---------------------------------------------------------------------------------------------
-// which path factors a problem: 0 = by its interior count, 1 = LDS, 2 = the blocked one in the workspace
-static std::atomic<int> g_dir_path{0};
+// which path factors a problem: 0 = by its interior count, 1 = LDS, 2 = the blocked one in the workspace (71 168 bytes of LDS)
+static size_t dir_path_lds_bytes(int n, bool ldsp) { return ldsp ? dir_lds_bytes(n) : dir_blocked_lds_bytes(); }
+static PathKnob g_dir_path{4, "debug_msm_dirichlet_path: 0 (by size), 1 (LDS), 2 (global), 3 (global, VALU) or 4 (global, MFMA)"};
+static const MsmTwoPath k_dir_paths{"dirichlet", "msm_dirichlet_solve", &g_dir_path, DFF_DIR_LDS_LIMIT, 1, 0, 0x7fffffff, true,
+                                    dir_path_lds_bytes};
 
-extern "C" int dff_debug_msm_dirichlet_path(int path) {
-    if (path < 0 || path > 4)
-        return fail(DFF_EINVAL, "debug_msm_dirichlet_path: 0 (by size), 1 (LDS), 2 (global), 3 (global, VALU) or 4 (global, MFMA)");
-    g_dir_path.store(path);
-    return DFF_OK;
-}
+extern "C" int dff_debug_msm_dirichlet_path(int path) { return g_dir_path.set(path); }
 
 extern "C" int dff_msm_dirichlet_lds_limit(void) { return DFF_DIR_LDS_LIMIT; }
 
-static int dir_check_batch(int P, int Kmax, const char* what) {
-    if (P < 1 || P > DFF_DIR_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_DIR_MAXP);
-    return micro_check_count(Kmax, what, "states");
-}
-
 extern "C" long long dff_msm_dirichlet_workspace_bytes(int P, int Kmax) {
-    if (dir_check_batch(P, Kmax, "msm_dirichlet_workspace_bytes")) return -1;
+    if (solver_check_batch(P, Kmax, "msm_dirichlet_workspace_bytes")) return -1;
     return (long long)P * (1 + dir_slice_doubles(Kmax)) * (long long)sizeof(double);   // descriptors | one slice per problem
 }
 
 extern "C" int dff_msm_dirichlet_solve(int device, const double* flux, int n_flux, const int32_t* flux_of, const int32_t* ks,
                                        int P, int Kmax, const int32_t* role, const double* g, const double* s, double* u,
                                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* what = "msm_dirichlet_solve";
-    int rc = dir_check_batch(P, Kmax, what);
+    const MsmTwoPath& paths = k_dir_paths;
+    const char* what = paths.what;
+    int rc = solver_check_batch(P, Kmax, what);
     if (rc) return rc;
     if (n_flux < 1 || n_flux > DFF_DIR_MAXP) return fail(DFF_EINVAL, "%s: the number of flux matrices must be 1..%d", what, DFF_DIR_MAXP);
     if (!flux || !ks || !role || !g || !s || !u || !status)
         return fail(DFF_EINVAL, "%s: null flux / state counts / roles / boundary values / sources / u / status", what);
     if (!flux_of && n_flux < P) return fail(DFF_EINVAL, "%s: %d flux matrices for %d problems and no flux_of", what, n_flux, P);
-    const int knob = g_dir_path.load();
-    const int path = knob > 2 ? 2 : knob;                             // 3 and 4: the blocked path with a named trailing update
-    const int mfma = knob == 3 ? 0 : (knob == 4 ? 1 : DFF_DIR_MFMA);
-    int kmax_live = 0;
-    for (int p = 0; p < P; ++p) {
-        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
-        if (flux_of && (flux_of[p] < 0 || flux_of[p] >= n_flux))
-            return fail(DFF_EINVAL, "%s: problem %d takes flux matrix %d of %d", what, p, (int)flux_of[p], n_flux);
-        if (path == 1 && ks[p] > DFF_DIR_LDS_LIMIT + 1)
-            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_DIR_LDS_LIMIT + 1);
-        if (ks[p] > kmax_live) kmax_live = ks[p];
-    }
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_dirichlet_workspace_bytes(P, Kmax), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    const int knob = paths.knob->value.load();
+    const int mfma = knob == 3 ? 0 : (knob == 4 ? 1 : DFF_DIR_MFMA);  // 3 and 4: the blocked path with a named trailing update
+    MsmTable tab;
+    if ((rc = tab.build(what, ks, P, Kmax, flux_of, n_flux, "flux matrix", false, paths.forced_max(knob), nullptr))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_msm_dirichlet_workspace_bytes(P, Kmax), what))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    std::vector<long long> desc((size_t)P);
-    for (int p = 0; p < P; ++p) desc[p] = ((long long)(flux_of ? flux_of[p] : p) << DFF_DIR_KBITS) | ks[p];
     long long* desc_dev = (long long*)workspace;
-    if ((rc = msmb_upload(stream, desc.data(), P, desc_dev))) return rc;
+    if ((rc = tab.upload(stream, desc_dev))) return rc;
     double* work = (double*)(desc_dev + P);
     const long long slice = dir_slice_doubles(Kmax);
-    if (path != 2) {                                                  // interior counts 0 .. the limit (all of them when forced)
-        const int nl = kmax_live - 1 < DFF_DIR_LDS_LIMIT ? kmax_live - 1 : DFF_DIR_LDS_LIMIT;
-        const size_t lds = dir_lds_bytes(nl);
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_dir_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_dir_kernel<true>, dim3((unsigned)P), dim3(DFF_DIR_THREADS), (unsigned)lds, stream, flux,
-                           (const long long*)desc_dev, Kmax, role, g, s, u, status, work, slice, 0,
-                           path == 1 ? 0x7fffffff : DFF_DIR_LDS_LIMIT, mfma);
-        HIPCHK(hipGetLastError());
-    }
-    if (path == 2 || (path == 0 && kmax_live > DFF_DIR_LDS_LIMIT)) {  // the rest (an interior count above the limit needs K_p above it)
-        HIPCHK(hipFuncSetAttribute((const void*)&dff_dir_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)dir_blocked_lds_bytes()));    // 71 168 bytes: above the 64 KB a launch gets unasked
-        hipLaunchKernelGGL(dff_dir_kernel<false>, dim3((unsigned)P), dim3(DFF_DIR_THREADS), (unsigned)dir_blocked_lds_bytes(), stream,
-                           flux, (const long long*)desc_dev, Kmax, role, g, s, u, status, work, slice,
-                           path == 2 ? 0 : DFF_DIR_LDS_LIMIT + 1, 0x7fffffff, mfma);
-        HIPCHK(hipGetLastError());
-    }
-    return DFF_OK;
+    const dff_msm_batch_plan plan = msm_two_path(paths, knob, tab.kmin_live, tab.kmax_live);
+    const dff_msm_batch_launch &l0 = plan.launch[0], &l1 = plan.launch[1];
+    if ((rc = msm_launch_planned(dff_dir_kernel<true>, l0, P, DFF_DIR_THREADS, stream, flux, (const long long*)desc_dev, Kmax, role, g,
+                                 s, u, status, work, slice, l0.lo, l0.hi, mfma)))
+        return rc;
+    return msm_launch_planned(dff_dir_kernel<false>, l1, P, DFF_DIR_THREADS, stream, flux, (const long long*)desc_dev, Kmax, role, g, s,
+                              u, status, work, slice, l1.lo, l1.hi, mfma);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The k largest eigenpairs of many symmetric matrices (dff_sym_eig.hip)
 // ---------------------------------------------------------------------------------------------
 // which path reduces a problem: 0 = by its size, 1 = LDS, 2 = the workspace
-static std::atomic<int> g_eig_path{0};
+static PathKnob g_eig_path{2, "debug_sym_eig_path: 0 (by size), 1 (LDS) or 2 (workspace)"};
+static const MsmTwoPath k_eig_paths{"eig", "sym_eig_topk", &g_eig_path, DFF_EIG_LDS_LIMIT, 0, 1, DFF_MSM_MAXK, false, eig_lds_bytes};
 
-extern "C" int dff_debug_sym_eig_path(int path) {
-    if (path < 0 || path > 2) return fail(DFF_EINVAL, "debug_sym_eig_path: 0 (by size), 1 (LDS) or 2 (workspace)");
-    g_eig_path.store(path);
-    return DFF_OK;
-}
+extern "C" int dff_debug_sym_eig_path(int path) { return g_eig_path.set(path); }
 
 extern "C" int dff_sym_eig_lds_limit(void) { return DFF_EIG_LDS_LIMIT; }
 
-static int eig_check_batch(int P, int Kmax, const char* what) {
-    if (P < 1 || P > DFF_EIG_MAXP) return fail(DFF_EINVAL, "%s: the number of problems must be 1..%d", what, DFF_EIG_MAXP);
-    return micro_check_count(Kmax, what, "states");
-}
-
 extern "C" long long dff_sym_eig_workspace_bytes(int P, int Kmax) {
-    if (eig_check_batch(P, Kmax, "sym_eig_workspace_bytes")) return -1;
+    if (solver_check_batch(P, Kmax, "sym_eig_workspace_bytes")) return -1;
     return (long long)P * (1 + eig_slice_doubles(Kmax)) * (long long)sizeof(double);   // state counts | one slice per problem
 }
 
 extern "C" int dff_sym_eig_topk(int device, const double* a, const int32_t* ks, int P, int Kmax, int k, double* w, double* v,
                                 int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* what = "sym_eig_topk";
-    int rc = eig_check_batch(P, Kmax, what);
+    const MsmTwoPath& paths = k_eig_paths;
+    const char* what = paths.what;
+    int rc = solver_check_batch(P, Kmax, what);
     if (rc) return rc;
     if (k < 1 || k > DFF_EIG_MAXTOP) return fail(DFF_EINVAL, "%s: the number of eigenpairs must be 1..%d", what, DFF_EIG_MAXTOP);
     if (!a || !ks || !w || !status) return fail(DFF_EINVAL, "%s: null matrices / state counts / eigenvalues / status", what);
-    const int path = g_eig_path.load();
-    int kmax_live = 0, kmin_live = DFF_MSM_MAXK;
-    for (int p = 0; p < P; ++p) {
-        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
-        if (path == 1 && ks[p] > DFF_EIG_LDS_LIMIT)
-            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_EIG_LDS_LIMIT);
-        if (ks[p] > kmax_live) kmax_live = ks[p];
-        if (ks[p] < kmin_live) kmin_live = ks[p];
-    }
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_sym_eig_workspace_bytes(P, Kmax), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    const int knob = paths.knob->value.load();
+    MsmTable tab;                                                     // bare counts: matrix p is problem p's
+    if ((rc = tab.build(what, ks, P, Kmax, nullptr, P, nullptr, false, paths.forced_max(knob), nullptr))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_sym_eig_workspace_bytes(P, Kmax), what))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    std::vector<long long> kl((size_t)P);
-    for (int p = 0; p < P; ++p) kl[p] = ks[p];
     long long* ks_dev = (long long*)workspace;
-    if ((rc = msmb_upload(stream, kl.data(), P, ks_dev))) return rc;
+    if ((rc = tab.upload(stream, ks_dev))) return rc;
     double* work = (double*)(ks_dev + P);
     const long long slice = eig_slice_doubles(Kmax);
-    if (path == 1 || (path == 0 && kmin_live <= DFF_EIG_LDS_LIMIT)) {
-        const size_t lds = eig_lds_bytes(kmax_live < DFF_EIG_LDS_LIMIT ? kmax_live : DFF_EIG_LDS_LIMIT, true);
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_sym_eig_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_sym_eig_kernel<true>, dim3((unsigned)P), dim3(EigCfg<true>::T), (unsigned)lds, stream, a,
-                           (const long long*)ks_dev, Kmax, k, w, v, status, work, slice, 1, DFF_EIG_LDS_LIMIT);
-        HIPCHK(hipGetLastError());
-    }
-    if (path == 2 || (path == 0 && kmax_live > DFF_EIG_LDS_LIMIT)) {
-        const size_t lds = eig_lds_bytes(kmax_live, false);
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_sym_eig_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_sym_eig_kernel<false>, dim3((unsigned)P), dim3(EigCfg<false>::T), (unsigned)lds, stream, a,
-                           (const long long*)ks_dev, Kmax, k, w, v, status, work, slice, path == 2 ? 1 : DFF_EIG_LDS_LIMIT + 1,
-                           DFF_MSM_MAXK);
-        HIPCHK(hipGetLastError());
-    }
-    return DFF_OK;
+    const dff_msm_batch_plan plan = msm_two_path(paths, knob, tab.kmin_live, tab.kmax_live);
+    const dff_msm_batch_launch &l0 = plan.launch[0], &l1 = plan.launch[1];
+    if ((rc = msm_launch_planned(dff_sym_eig_kernel<true>, l0, P, EigCfg<true>::T, stream, a, (const long long*)ks_dev, Kmax, k, w, v,
+                                 status, work, slice, l0.lo, l0.hi)))
+        return rc;
+    return msm_launch_planned(dff_sym_eig_kernel<false>, l1, P, EigCfg<false>::T, stream, a, (const long long*)ks_dev, Kmax, k, w, v,
+                              status, work, slice, l1.lo, l1.hi);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Row vectors through a transition matrix, step after step (dff_msm_propagate.hip)
 // ---------------------------------------------------------------------------------------------
 // which path propagates a problem: 0 = by its size, 1 = LDS, 2 = the matrix streamed from global memory
-static std::atomic<int> g_prop_path{0};
+static PathKnob g_prop_path{2, "debug_msm_propagate_path: 0 (by size), 1 (LDS) or 2 (workspace)"};
+static const MsmTwoPath k_prop_paths{"propagate", "msm_propagate", &g_prop_path, DFF_PROP_LDS_LIMIT, 0, 1, DFF_MSM_MAXK, false,
+                                     prop_lds_bytes};
 
-extern "C" int dff_debug_msm_propagate_path(int path) {
-    if (path < 0 || path > 2) return fail(DFF_EINVAL, "debug_msm_propagate_path: 0 (by size), 1 (LDS) or 2 (workspace)");
-    g_prop_path.store(path);
-    return DFF_OK;
-}
+extern "C" int dff_debug_msm_propagate_path(int path) { return g_prop_path.set(path); }
 
 extern "C" int dff_msm_propagate_lds_limit(void) { return DFF_PROP_LDS_LIMIT; }
 
@@ -1426,7 +1460,8 @@ extern "C" long long dff_msm_propagate_workspace_bytes(int P, int Kmax, int M, i
 extern "C" int dff_msm_propagate(int device, const double* t, int n_mat, const int32_t* mat_of, const int32_t* ks, int P, int Kmax,
                                  const double* w0, int M, const double* obs, int R, int S, double* out, double* w_last,
                                  int32_t* status, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* what = "msm_propagate";
+    const MsmTwoPath& paths = k_prop_paths;
+    const char* what = paths.what;
     int rc = prop_check_batch(P, Kmax, M, R, what);
     if (rc) return rc;
     if (S < 0 || S > DFF_PROP_MAXSTEPS) return fail(DFF_EINVAL, "%s: the number of steps must be 0..%d", what, DFF_PROP_MAXSTEPS);
@@ -1436,47 +1471,36 @@ extern "C" int dff_msm_propagate(int device, const double* t, int n_mat, const i
     if (!t || !ks || !w0 || !obs || !out || !status)
         return fail(DFF_EINVAL, "%s: null matrices / state counts / start vectors / observables / out / status", what);
     if (!mat_of && n_mat < P) return fail(DFF_EINVAL, "%s: %d matrices for %d problems and no mat_of", what, n_mat, P);
-    const int path = g_prop_path.load();
-    int kmax_live = 0, kmin_live = DFF_MSM_MAXK;
-    std::vector<int> k_of((size_t)n_mat, 0);
-    for (int p = 0; p < P; ++p) {
-        if (ks[p] < 1 || ks[p] > Kmax) return fail(DFF_EINVAL, "%s: problem %d has %d states, must be 1..Kmax = %d", what, p, (int)ks[p], Kmax);
-        const int mo = mat_of ? mat_of[p] : p;
-        if (mo < 0 || mo >= n_mat) return fail(DFF_EINVAL, "%s: problem %d takes matrix %d of %d", what, p, mo, n_mat);
-        int& km = k_of[(size_t)mo];
-        if (km && km != ks[p])
-            return fail(DFF_EINVAL, "%s: problem %d reads matrix %d with %d states, an earlier problem with %d", what, p, mo, (int)ks[p], km);
-        km = ks[p];
-        if (path == 1 && ks[p] > DFF_PROP_LDS_LIMIT)
-            return fail(DFF_EINVAL, "%s: problem %d has %d states, the forced LDS path takes at most %d", what, p, (int)ks[p], DFF_PROP_LDS_LIMIT);
-        if (ks[p] > kmax_live) kmax_live = ks[p];
-        if (ks[p] < kmin_live) kmin_live = ks[p];
-    }
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_msm_propagate_workspace_bytes(P, Kmax, M, R), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(double)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    const int knob = paths.knob->value.load();
+    MsmTable tab;
+    if ((rc = tab.build(what, ks, P, Kmax, mat_of, n_mat, "matrix", true, paths.forced_max(knob), nullptr))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_msm_propagate_workspace_bytes(P, Kmax, M, R), what))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
-    std::vector<long long> desc((size_t)P);
-    for (int p = 0; p < P; ++p) desc[p] = ((long long)(mat_of ? mat_of[p] : p) << DFF_PROP_KBITS) | ks[p];
     long long* desc_dev = (long long*)workspace;
-    if ((rc = msmb_upload(stream, desc.data(), P, desc_dev))) return rc;
-    if (path == 1 || (path == 0 && kmin_live <= DFF_PROP_LDS_LIMIT)) {
-        const size_t lds = prop_lds_bytes(kmax_live < DFF_PROP_LDS_LIMIT ? kmax_live : DFF_PROP_LDS_LIMIT, true);
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_prop_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_prop_kernel<true>, dim3((unsigned)P), dim3(DFF_PROP_THREADS), (unsigned)lds, stream, t,
-                           (const long long*)desc_dev, Kmax, w0, M, obs, R, S, out, w_last, status, 1, DFF_PROP_LDS_LIMIT);
-        HIPCHK(hipGetLastError());
-    }
-    if (path == 2 || (path == 0 && kmax_live > DFF_PROP_LDS_LIMIT)) {
-        const size_t lds = prop_lds_bytes(kmax_live, false);
-        if (lds > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void*)&dff_prop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(dff_prop_kernel<false>, dim3((unsigned)P), dim3(DFF_PROP_THREADS), (unsigned)lds, stream, t,
-                           (const long long*)desc_dev, Kmax, w0, M, obs, R, S, out, w_last, status,
-                           path == 2 ? 1 : DFF_PROP_LDS_LIMIT + 1, DFF_MSM_MAXK);
-        HIPCHK(hipGetLastError());
-    }
+    if ((rc = tab.upload(stream, desc_dev))) return rc;
+    const dff_msm_batch_plan plan = msm_two_path(paths, knob, tab.kmin_live, tab.kmax_live);
+    const dff_msm_batch_launch &l0 = plan.launch[0], &l1 = plan.launch[1];
+    if ((rc = msm_launch_planned(dff_prop_kernel<true>, l0, P, DFF_PROP_THREADS, stream, t, (const long long*)desc_dev, Kmax, w0, M, obs,
+                                 R, S, out, w_last, status, l0.lo, l0.hi)))
+        return rc;
+    return msm_launch_planned(dff_prop_kernel<false>, l1, P, DFF_PROP_THREADS, stream, t, (const long long*)desc_dev, Kmax, w0, M, obs, R,
+                              S, out, w_last, status, l1.lo, l1.hi);
+}
+
+// What one of the three calls above would launch for these state counts under its knob as it stands: host arithmetic only.
+extern "C" int dff_debug_msm_batch_plan(const char* call, const int32_t* ks, int P, int Kmax, dff_msm_batch_plan* out) {
+    const MsmTwoPath* paths = nullptr;
+    for (const MsmTwoPath* c : {&k_dir_paths, &k_eig_paths, &k_prop_paths})
+        if (call && !strcmp(call, c->name)) paths = c;
+    if (!paths) return fail(DFF_EINVAL, "debug_msm_batch_plan: the call must be dirichlet, eig or propagate");
+    if (!ks || !out) return fail(DFF_EINVAL, "debug_msm_batch_plan: null state counts / plan");
+    int rc = solver_check_batch(P, Kmax, paths->what);
+    if (rc) return rc;
+    const int knob = paths->knob->value.load();
+    MsmTable tab;
+    if ((rc = tab.build(paths->what, ks, P, Kmax, nullptr, P, nullptr, false, paths->forced_max(knob), nullptr))) return rc;
+    *out = msm_two_path(*paths, knob, tab.kmin_live, tab.kmax_live);
     return DFF_OK;
 }
 
@@ -1954,8 +1978,7 @@ extern "C" int dff_unit_hist(int device, const int32_t* bins, long long n, int C
     }
     if (total != n) return fail(DFF_EINVAL, "%s: unit lengths sum to %lld, not n = %lld", what, total, n);
     if (!hist) return fail(DFF_EINVAL, "%s: null output", what);
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_unit_hist_workspace_bytes(U, C), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_unit_hist_workspace_bytes(U, C), what))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     HIPCHK(hipMemsetAsync(hist, 0, (size_t)U * C * ld * sizeof(uint32_t), stream));
@@ -2020,8 +2043,7 @@ extern "C" int dff_resampled_js(int device, const uint32_t* hist, int U, int C, 
     if (rc) return rc;
     if ((rc = jsb_check_resamples(B, what))) return rc;
     if (!hist || !weights || !ref || !js) return fail(DFF_EINVAL, "%s: null histograms / weights / reference / output", what);
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_resampled_js_workspace_bytes(U, C), what))) return rc;
-    if ((uintptr_t)workspace % sizeof(long long)) return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_resampled_js_workspace_bytes(U, C), what))) return rc;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
     long long* nb_dev = (long long*)workspace;

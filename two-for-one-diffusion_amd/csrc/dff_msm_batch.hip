@@ -19,12 +19,12 @@
 //     err[s * B + b].
 #pragma once
 #include "dff_msm.hip"
+#include "dff_msm_table.h"   // the live problems' descriptors
 
 #define DFF_MSMB_MAXB 4096           // resamples / problems per call
 #define DFF_RC_MAXUNITS (1 << 20)    // resampling units per call
 #define DFF_RC_MAXCOUNTERS (1LL << 28)   // B K^2 counters per call (2 GiB)
 #define DFF_MSMB_UPLOAD 448          // 64-bit words per upload launch: 3.5 KB of kernel arguments
-#define DFF_MSMB_KBITS 11            // a descriptor is b << 11 | K_b, K_b <= 1024 < 2^11
 
 struct MsmbWords {
     long long v[DFF_MSMB_UPLOAD];
@@ -86,15 +86,14 @@ __global__ __launch_bounds__(DFF_TC_THREADS) void dff_micro_rc_kernel(const int*
 }
 
 // ---- the batched estimator: the locator of dff_msm.hip's kernels over a table of live problems, live[p] = b <<
-// DFF_MSMB_KBITS | K_b, in slots of Kmax; err is (n_steps, B)
+// DFF_MSM_KBITS | K_b (dff_msm_table.h), in slots of Kmax; err is (n_steps, B)
 struct MsmLive {
     const long long* live;
     int Kmax, B;
     __device__ MsmAt at(unsigned p) const {
         const int desc = (int)live[p];
-        return {desc >> DFF_MSMB_KBITS, desc & ((1 << DFF_MSMB_KBITS) - 1)};
+        return {MSM_PROBLEM_SLOT(desc), MSM_PROBLEM_K(desc)};
     }
     __host__ __device__ int stride() const { return Kmax; }
     __host__ __device__ int err_stride() const { return B; }
-    static long long descriptor(int b, int K) { return ((long long)b << DFF_MSMB_KBITS) | K; }
 };

@@ -36,7 +36,6 @@
 #define DFF_DIR_NB 32                 // panel width of the blocked factorisation
 #define DFF_DIR_TILE 64               // trailing tiles
 #define DFF_DIR_LDP (DFF_DIR_NB + 1)  // odd leading dimension of the LDS strips and of the diagonal block: no bank conflicts
-#define DFF_DIR_KBITS 11              // a descriptor is flux slot << 11 | K_p, K_p <= 1024 < 2^11
 #define DFF_DIR_NOSTATE 0xFFFFu
 
 __host__ __device__ inline long long dir_tri(long long rows) { return rows * (rows + 1) / 2; }
@@ -311,7 +310,7 @@ __device__ inline int dir_factor_blocked(double* A, int ld, double* Lp, int n, d
     return -1;
 }
 
-// ---- one workgroup per problem.  desc[p] = flux slot << KBITS | K_p; slots of Kmax^2 (flux), Kmax (role, g, s, u).  The
+// ---- one workgroup per problem.  desc[p] = flux slot << DFF_MSM_KBITS | K_p (dff_msm_table.h); slots of Kmax^2 (flux), Kmax (role, g, s, u).  The
 // workgroup owns the problem when own_lo <= its interior count <= own_hi, else it leaves at once (the other path's launch
 // takes it).  work: slices of `slice` doubles (LDSP: unused).
 template <bool LDSP>
@@ -328,8 +327,8 @@ __global__ __launch_bounds__(DFF_DIR_THREADS) void dff_dir_kernel(const double* 
     double* dbl = (double*)(imap + DFF_MSM_MAXK);
     const unsigned p = blockIdx.x;
     const long long de = desc[p];
-    const int K = (int)(de & ((1 << DFF_DIR_KBITS) - 1));
-    const double* X = flux + (size_t)(de >> DFF_DIR_KBITS) * Kmax * Kmax;
+    const int K = MSM_PROBLEM_K(de);
+    const double* X = flux + (size_t)MSM_PROBLEM_SLOT(de) * Kmax * Kmax;
     role += (size_t)p * Kmax;
     g += (size_t)p * Kmax;
     s += (size_t)p * Kmax;

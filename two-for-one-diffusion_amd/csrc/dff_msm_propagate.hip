@@ -31,7 +31,6 @@
 #define DFF_PROP_MAXOUT (1LL << 28)   // doubles of out per call (2 GiB)
 #define DFF_PROP_LDS_FIT 120          // the largest K whose matrix, vectors, observables and partial sums fit 160 KB of LDS
 #define DFF_PROP_LDS_LIMIT 120        // the largest K propagated out of LDS: measured, LDS wins up to where it fits
-#define DFF_PROP_KBITS 11             // a descriptor is matrix slot << 11 | K_p, K_p <= 1024 < 2^11
 #define DFF_PROP_SLOTS (DFF_PROP_THREADS / DFF_PROP_MAXROWS)   // 32 column slots of prop_project
 #define DFF_PROP_WAVES (DFF_PROP_THREADS / 64)
 
@@ -129,7 +128,7 @@ __device__ __forceinline__ void prop_project(const double* wbuf, const double* _
     }
 }
 
-// ---- one workgroup per problem.  desc[p] = matrix slot << DFF_PROP_KBITS | K_p; t: slots of Kmax^2; w0 (P, M, Kmax); obs
+// ---- one workgroup per problem.  desc[p] = matrix slot << DFF_MSM_KBITS | K_p (dff_msm_table.h); t: slots of Kmax^2; w0 (P, M, Kmax); obs
 // (P, R, Kmax); out (P, S + 1, M, R); wlast (P, M, Kmax) or NULL.  The workgroup owns the problem when own_lo <= K_p <= own_hi,
 // else it leaves at once (the other path's launch takes it).
 template <bool LDSP>
@@ -142,9 +141,9 @@ __global__ __launch_bounds__(DFF_PROP_THREADS) void dff_prop_kernel(const double
     extern __shared__ __attribute__((aligned(16))) unsigned char prop_lds[];
     const unsigned pr = blockIdx.x;
     const long long d = desc[pr];
-    const int K = (int)(d & ((1 << DFF_PROP_KBITS) - 1)), tid = threadIdx.x;
+    const int K = MSM_PROBLEM_K(d), tid = threadIdx.x;
     if (K < own_lo || K > own_hi) return;
-    const double* A = t + (size_t)(d >> DFF_PROP_KBITS) * Kmax * Kmax;
+    const double* A = t + (size_t)MSM_PROBLEM_SLOT(d) * Kmax * Kmax;
     double* wbuf = (double*)prop_lds;
     double* part = wbuf + (size_t)K * MR;
     double* obsl = part + DFF_PROP_WAVES * MR * MR;                  // LDS path only

@@ -2821,6 +2821,30 @@ SPECTRUM_MAX_K = binding.SYM_EIG_MAX_K
 SPECTRUM_BYTES = 1 << 30         # matrices, vectors and workspace of one dff_sym_eig_topk call of spectral_solver
 
 
+def _device_chunks(device, P, per, cap, max_batch, outputs, call, mats=None, mat_of=None, most=None):
+    """The loop behind spectral_solver, dirichlet_solver and propagator: problems 0 .. P - 1 go to the GPU in chunks of at most
+    max_batch (and `most`) problems of `per` bytes each that stay under `cap` bytes, one library call per chunk.  call(sl, up,
+    mats_dev, local) -> device tensors, one per host array of `outputs` (NaN- or zero-filled; None: not wanted), whose rows sl
+    receive them; up(a) puts a host array on the device.  With mats and mat_of (P,) a chunk uploads only the matrices it uses,
+    and local (int32) indexes them."""
+    chunk = max(1, min(max_batch, cap // per, *(() if most is None else (most,))))
+
+    def up(a):
+        return torch.from_numpy(a).to(device)
+
+    for p0 in range(0, P, chunk):
+        sl = slice(p0, min(P, p0 + chunk))
+        if mat_of is None:
+            res = call(sl, up, None, None)
+        else:
+            used, local = np.unique(mat_of[sl], return_inverse=True)
+            res = call(sl, up, up(mats[used]), local.astype(np.int32))
+        for host, dev in zip(outputs, res):
+            if host is not None:
+                host[sl] = dev.cpu().numpy()
+    return outputs
+
+
 class _DeviceSpectral:
     """solve(a (P, Kmax, Kmax), ks (P,), k, vectors) -> (w (P, k), v (P, k, Kmax) | None, status (P,)), host arrays in and out:
     the problems go to the GPU in chunks that stay under SPECTRUM_BYTES, each chunk one dff_sym_eig_topk call."""
@@ -2833,16 +2857,12 @@ class _DeviceSpectral:
         P, Kmax = a.shape[0], a.shape[1]
         ks = np.asarray(ks, np.int32).reshape(-1)
         per = 8 * (2 * Kmax * Kmax + 5 + k * (1 + Kmax))             # a matrix, a slice of the workspace, the outputs
-        chunk = max(1, min(SPECTRUM_MAX_BATCH, SPECTRUM_BYTES // per))
-        w, status = np.full((P, k), np.nan), np.zeros(P, np.int32)
-        v = np.full((P, k, Kmax), np.nan) if vectors else None
-        for p0 in range(0, P, chunk):
-            sl = slice(p0, min(P, p0 + chunk))
-            wd, vd, sd = binding.sym_eig_topk(torch.from_numpy(a[sl]).to(self.device), ks[sl], k, vectors=vectors)
-            w[sl], status[sl] = wd.cpu().numpy(), sd.cpu().numpy()
-            if vectors:
-                v[sl] = vd.cpu().numpy()
-        return w, v, status
+        outputs = (np.full((P, k), np.nan), np.full((P, k, Kmax), np.nan) if vectors else None, np.zeros(P, np.int32))
+
+        def call(sl, up, _mats, _local):
+            return binding.sym_eig_topk(up(a[sl]), ks[sl], k, vectors=vectors)
+
+        return _device_chunks(self.device, P, per, SPECTRUM_BYTES, SPECTRUM_MAX_BATCH, outputs, call)
 
 
 def spectral_solver(device):
@@ -2929,17 +2949,12 @@ class _DeviceDirichlet:
         flux_of, ks = np.asarray(flux_of, np.int64).reshape(-1), np.asarray(ks, np.int32).reshape(-1)
         g, s = np.ascontiguousarray(g, np.float64), np.ascontiguousarray(s, np.float64)
         per = 8 * (2 * Kmax * Kmax + 33 * Kmax + 1)                  # a matrix of its own and a slice of the workspace
-        chunk = max(1, min(DIRICHLET_MAX_BATCH, DIRICHLET_BYTES // per))
-        u, status = np.full((P, Kmax), np.nan), np.zeros(P, np.int32)
-        for p0 in range(0, P, chunk):
-            sl = slice(p0, min(P, p0 + chunk))
-            used, local = np.unique(flux_of[sl], return_inverse=True)
-            dev = self.device
-            ud, sd = binding.msm_dirichlet_solve(torch.from_numpy(flux[used]).to(dev), ks[sl], torch.from_numpy(role[sl]).to(dev),
-                                                 torch.from_numpy(g[sl]).to(dev), torch.from_numpy(s[sl]).to(dev),
-                                                 flux_of=local.astype(np.int32))
-            u[sl], status[sl] = ud.cpu().numpy(), sd.cpu().numpy()
-        return u, status
+
+        def call(sl, up, flux_dev, local):
+            return binding.msm_dirichlet_solve(flux_dev, ks[sl], up(role[sl]), up(g[sl]), up(s[sl]), flux_of=local)
+
+        outputs = (np.full((P, Kmax), np.nan), np.zeros(P, np.int32))
+        return _device_chunks(self.device, P, per, DIRICHLET_BYTES, DIRICHLET_MAX_BATCH, outputs, call, mats=flux, mat_of=flux_of)
 
 
 def dirichlet_solver(device):
@@ -3284,20 +3299,13 @@ class _DevicePropagator:
         t = np.ascontiguousarray(t, np.float64).reshape(-1, Kmax, Kmax)
         mat_of, ks = np.asarray(mat_of, np.int64).reshape(-1), np.asarray(ks, np.int32).reshape(-1)
         per = 8 * (Kmax * Kmax + (2 * M + R) * Kmax + (S + 1) * M * R + 2)
-        chunk = max(1, min(PROPAGATE_MAX_BATCH, PROPAGATE_BYTES // per, (1 << 28) // ((S + 1) * M * R)))
-        out, status = np.full((P, S + 1, M, R), np.nan), np.zeros(P, np.int32)
-        last = np.full((P, M, Kmax), np.nan) if want_last else None
-        dev = self.device
-        for p0 in range(0, P, chunk):
-            sl = slice(p0, min(P, p0 + chunk))
-            used, local = np.unique(mat_of[sl], return_inverse=True)
-            od, ld, sd = binding.msm_propagate(torch.from_numpy(t[used]).to(dev), local.astype(np.int32), ks[sl],
-                                               torch.from_numpy(w0[sl]).to(dev), torch.from_numpy(obs[sl]).to(dev), S,
-                                               want_last=want_last)
-            out[sl], status[sl] = od.cpu().numpy(), sd.cpu().numpy()
-            if want_last:
-                last[sl] = ld.cpu().numpy()
-        return out, last, status
+        outputs = (np.full((P, S + 1, M, R), np.nan), np.full((P, M, Kmax), np.nan) if want_last else None, np.zeros(P, np.int32))
+
+        def call(sl, up, t_dev, local):
+            return binding.msm_propagate(t_dev, local, ks[sl], up(w0[sl]), up(obs[sl]), S, want_last=want_last)
+
+        return _device_chunks(self.device, P, per, PROPAGATE_BYTES, PROPAGATE_MAX_BATCH, outputs, call, mats=t, mat_of=mat_of,
+                              most=(1 << 28) // ((S + 1) * M * R))          # the call's cap on its output values
 
 
 def propagator(device):
