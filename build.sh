@@ -2,8 +2,8 @@
 # Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Eight translation units compiled in
 # parallel: the <= 64-row kernel, the <= 16-row kernel once per sampler mode (score / Langevin / DDPM), the host half
 # (model, dispatch, sampler ABI), weight preparation (folds, range guard, operand images: pure CPU work), the sample-analysis
-# half (PWD / structure / TICA / state / ensemble-RMSD / superposition / clustering / kinetics / autocorrelation / Markov-state-model / passage / spectrum / propagation / hidden-Markov-model / JS-bootstrap kernels and their ABI) and the forward process with its loss (dff_loss: q_sample, p_losses).
-# dff_analysis.hip includes its kernel files (dff_msm.hip, whose estimator kernels dff_msm_batch.hip instantiates for many problems, dff_msm_table.h, the problem table of the batched solvers, ..., dff_hmm.hip, dff_hmm_viterbi.hip, dff_hmm_mstep.hip, dff_jsboot.hip): a new one
+# half (PWD / structure / TICA / state / ensemble-RMSD / superposition / clustering / kinetics / transition-path / autocorrelation / Markov-state-model / passage / spectrum / propagation / hidden-Markov-model / JS-bootstrap kernels and their ABI) and the forward process with its loss (dff_loss: q_sample, p_losses).
+# dff_analysis.hip includes its kernel files (dff_msm.hip, whose estimator kernels dff_msm_batch.hip instantiates for many problems, dff_msm_table.h, the problem table of the batched solvers, ..., dff_hmm.hip, dff_hmm_viterbi.hip, dff_hmm_mstep.hip, dff_jsboot.hip, dff_paths.hip): a new one
 # is compiled, tracked for staleness (the compiler's dependency list) and hashed (csrc/*) without a line of its own here.
 #   DFF_EXTRA_FLAGS="-DDFF_FAST_BUILD"   development build: headline variants only (fast to compile)
 set -e

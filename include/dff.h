@@ -577,6 +577,39 @@ int dff_label_runs(int device, const int32_t* labels_dev, long long n, const lon
                    uint8_t* run_flags_dev, long long* n_runs_dev,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- transition paths: the previous AND the next core of every frame, frame classes, the table of paths
+ * (csrc/dff_paths.hip; evaluate.py: path_states, transition_paths, path_histograms, tp_probability, empirical_committor,
+ * TransitionPathEvaluator) ----
+ * Stateless like the calls above: device pointers, enqueued on `stream` only, no read-back and no synchronisation on the
+ * launch path; bad arguments are refused on the host before any device call; bit-identical from call to call and independent
+ * of the workspace's prior contents; integers only, no atomics; no workgroup waits on another.  cv_dev, lengths_host, lo and
+ * hi are those of dff_core_states.
+ * Bytes of device workspace dff_path_states needs for n frames (one 32-byte carry per 2048 frames); -1 on bad arguments. */
+long long dff_path_states_workspace_bytes(long long n);
+/* The code of frame t: non-finite; A (cv <= lo); B (cv >= hi, equality inside); between.  Per trajectory:
+ *   prev_dev[t] / t_prev_dev[t]   walk back from t (inclusive) to the first frame that is not between: A -> 0, B -> 1, with its
+ *       frame index in the concatenated series; a non-finite frame, or the trajectory's start reached -> -1 / -1.  prev is,
+ *       bit for bit, what dff_core_states writes to labels_dev (as int8).
+ *   next_dev[t] / t_next_dev[t]   the mirror image: walk forward (inclusive) to the trajectory's end.
+ *   class_dev[t]   0 / 1 in core A / B; for a frame between the cores with prev >= 0 and next >= 0: 2 on a path A -> B,
+ *       3 on a path B -> A, 4 on a loop out of A and back, 5 on a loop out of B and back; -1 otherwise (non-finite, or the
+ *       history unknown on either side).
+ * Each of the five (n) arrays may be NULL.  Nothing crosses a trajectory boundary or a non-finite frame, in either direction.
+ * The path table: one record per frame e that is in a core, is not its trajectory's first frame, and has prev[e - 1] >= 0 and
+ * != the core of e:  path_exit_dev[r] = t_prev[e - 1], path_entry_dev[r] = e, path_dir_dev[r] = the core of e (1: A -> B), in
+ * ascending entry.  entry - exit >= 1 frames is the path's duration (1: a direct jump).  n_paths_dev (1) receives the TRUE
+ * number of paths; only the first max_paths >= 0 records are written, entries beyond are not touched (the arrays may be NULL
+ * when max_paths == 0).  n_paths_dev == NULL: no table.  n == 0 writes n_paths = 0 (when n_paths_dev is given).
+ * One scan in both directions (block scan, carry scan, apply: three launches per group of up to 64 unequal, or any number of
+ * equal-length, trajectories): exact.
+ * workspace_dev: >= dff_path_states_workspace_bytes(n) bytes, 8-byte aligned, contents irrelevant. */
+int dff_path_states(int device, const float* cv_dev, long long n, const long long* lengths_host, int n_traj,
+                    float lo, float hi,
+                    int8_t* prev_dev, int8_t* next_dev, long long* t_prev_dev, long long* t_next_dev, int8_t* class_dev,
+                    long long max_paths, long long* path_exit_dev, long long* path_entry_dev, int8_t* path_dir_dev,
+                    long long* n_paths_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- lagged products inside trajectories: the sums behind the autocorrelation function of an observable, its integrated
  * autocorrelation time and the effective sample size (csrc/dff_autocorr.hip) ----
  * The reference reports point estimates from its trajectories and no uncertainty; these sums give the relaxation time of a

@@ -12,6 +12,7 @@ the RMSD free-energy curve and the contact BCE to the folded structure of a fold
                                  [--flexibility HELDOUT.pt] [--write-aligned OUT.pt]
                                  [--clusters HELDOUT.pt [--cluster-cutoff 2.0] [--cluster-stride K]]
                                  [--kinetics [HELDOUT.pt] [--kinetics-cv q|rmsd] [--kinetics-cores LO,HI] [--frame-time T]]
+                                 [--paths [HELDOUT.pt] [--paths-bins N]]
                                  [--relaxation [HELDOUT.pt] [--relaxation-cv q|rmsd|tic] --max-lag L [--frame-time T]]
                                  [--passage [HELDOUT.pt] --passage-states K --passage-lag L [--passage-cv q|rmsd]
                                   [--passage-cores LO,HI] [--passage-bootstrap B]]
@@ -55,6 +56,13 @@ frame, dual-cutoff states with the cores cv <= LO and cv >= HI of --kinetics-cor
 folding and unfolding counts, rates and dwell times in units of --frame-time.  The samples split into trajectories by
 --traj-lengths / --parallel-sim as for --transitions.  With HELDOUT.pt (MD frames (m, N, 3) in time order, or a list of such
 trajectories) the same numbers for it with the suffix _ref, and the log10 rate ratios.
+
+--paths adds, under "paths", the transition paths of time-ordered Langevin samples (TransitionPathEvaluator; needs
+--folded-pdb; order parameter, cores, frame time and trajectories are those of --kinetics: --kinetics-cv, --kinetics-cores,
+--frame-time, --traj-lengths / --parallel-sim): the number of folding and unfolding paths and their mean and median path times,
+the shares of frames on paths and on loops, the largest p(TP | cv) over --paths-bins bins (50) with the bin it lies in, and the
+cv at which the empirical committor crosses 1 / 2.  With HELDOUT.pt (as for --kinetics) the same numbers for it with the suffix
+_ref, log10_path_time_ratio_folding / _unfolding, ptp_max_diff and committor_rmsd.
 
 --relaxation adds, under "relaxation", how fast an observable decorrelates along time-ordered Langevin samples and how many
 independent samples they hold (RelaxationEvaluator): the autocorrelation function of Q (--relaxation-cv q, the default), of
@@ -254,6 +262,27 @@ def kinetics(a, x):
     return res
 
 
+def paths_arguments(a):
+    """refused: --paths without --folded-pdb, --paths-bins without --paths"""
+    if a.paths is None:
+        if a.paths_bins is not None:
+            raise SystemExit("--paths-bins needs --paths")
+        return
+    if not a.folded_pdb:
+        raise SystemExit("--paths needs --folded-pdb")
+
+
+def paths(a, x):
+    lo, hi = kinetics_cores(a)
+    ref, ref_lengths = ordered_frames(a.paths) if a.paths else (None, None)
+    ev = evaluate.TransitionPathEvaluator(a.mol.lower(), a.folded_pdb, cv=a.kinetics_cv, lo=lo, hi=hi, frame_time=a.frame_time,
+                                          nbins=a.paths_bins or 50, ref_data=ref, ref_traj_lengths=ref_lengths, device=a.device)
+    res = cleaned(ev.eval(x, traj_lengths(a, len(x))))
+    res.update({"cv": a.kinetics_cv, "lo": lo, "hi": hi, "frame_time": a.frame_time, "bins": a.paths_bins or 50})
+    return res
+
+
+paths_bins = number(int, lambda v: 1 <= v <= 65536, "the number of bins must be 1..65536", NOT_AN_INTEGER)
 max_lag = number(int, lambda v: 1 <= v <= 65535, "the largest lag must be 1..65535", NOT_AN_INTEGER)
 
 
@@ -517,6 +546,11 @@ def build_parser():
     ap.add_argument("--frame-time", type=frame_time, default=1.0, metavar="T",
                     help="time between two frames, the unit of the rates and dwell times (with --kinetics) and of the "
                          "relaxation times (with --relaxation) and the implied timescales (with --msm)")
+    ap.add_argument("--paths", nargs="?", const="", default=None, metavar="HELDOUT.pt",
+                    help="also report transition-path times, p(TP | cv) and the empirical committor (time-ordered Langevin "
+                         "samples; needs --folded-pdb; cv, cores and frame time as for --kinetics); with HELDOUT.pt also for that MD data")
+    ap.add_argument("--paths-bins", type=paths_bins, default=None, metavar="N",
+                    help="bins of the order parameter for p(TP | cv) and the committor (with --paths; 50)")
     ap.add_argument("--relaxation", nargs="?", const="", default=None, metavar="HELDOUT.pt",
                     help="also report autocorrelation times, effective sample size and standard error of an observable "
                          "(time-ordered Langevin samples; needs --max-lag); with HELDOUT.pt also for that MD data")
@@ -621,6 +655,7 @@ def main():
         ap.error("--write-aligned needs --folded-pdb")
     if a.kinetics is not None and not a.folded_pdb:
         ap.error("--kinetics needs --folded-pdb")
+    paths_arguments(a)
     if a.relaxation is not None and a.relaxation_cv != "tic" and not a.folded_pdb:
         ap.error("--relaxation with --relaxation-cv q or rmsd needs --folded-pdb")
     if a.relaxation is not None:
@@ -669,6 +704,8 @@ def main():
         res["clusters"] = clusters(a, x)
     if a.kinetics is not None:
         res["kinetics"] = kinetics(a, x)
+    if a.paths is not None:
+        res["paths"] = paths(a, x)
     if a.relaxation is not None:
         res["relaxation"] = relaxation(a, x)
     if a.msm is not None:

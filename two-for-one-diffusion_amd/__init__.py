@@ -16,6 +16,8 @@ _EVALUATE = (
     "superpose", "mean_structure", "rmsf", "FlexibilityEvaluator",
     "cluster_rmsd", "RmsdClusterEvaluator",
     "native_pairs", "native_contacts_q", "core_states", "label_runs", "dwell_summary", "FoldingKineticsEvaluator",
+    "path_states", "PathStates", "transition_paths", "path_time_summary", "path_histograms", "tp_probability", "empirical_committor",
+    "TransitionPathEvaluator",
     "autocorrelation", "integrated_autocorr_time", "crossing_time", "effective_sample_size", "standard_error", "RelaxationEvaluator",
     "MicrostateKMeans", "largest_connected_set", "MarkovStateModel", "implied_timescales", "MsmEvaluator",
     "resampling_units", "bootstrap_weights", "bootstrap_msm", "MsmBootstrap", "implied_timescales_bootstrap",

@@ -132,6 +132,9 @@ SYMBOLS = {
     "dff_core_states": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "dff_label_runs": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_longlong, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                  _P]),
+    "dff_path_states_workspace_bytes": (C.c_longlong, [C.c_longlong]),
+    "dff_path_states": (C.c_int, [C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_longlong,
+                                  _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dff_autocorr_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "dff_autocorr": (C.c_int, [C.c_int, _P, C.c_longlong, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                _P]),
@@ -1028,6 +1031,50 @@ def label_runs(labels, lengths, max_runs=None, workspace=None):
     _check(lib, lib.dff_label_runs(dev.index, _ptr(labels), n, ln.ctypes.data_as(C.c_void_p), int(ln.size), m,
                                    _ptr(out["start"]), _ptr(out["length"]), _ptr(out["label"]), _ptr(out["flags"]),
                                    _ptr(out["n_runs"]), _ptr(workspace), ws_bytes, _stream(labels)), "dff_label_runs")
+    return out
+
+
+# ---- transition paths (dff_path_states) ----
+def path_states_workspace_bytes(n: int) -> int:
+    return _workspace_bytes("dff_path_states_workspace_bytes", int(n))
+
+
+def path_states(cv, lengths, lo: float, hi: float, frames=True, times=True, paths=True, max_paths=None, workspace=None):
+    """The previous and the next core of every frame of the float32 CUDA series cv (n,) -- trajectories back to back,
+    `lengths` frames each, cores cv <= lo (0) and cv >= hi (1) as in core_states -- and the transition paths between the cores
+    (dff_path_states).  A dict of CUDA tensors:
+    frames: prev, next, cls int8 (n,) -- the last / next core visited (-1: none inside the trajectory, or a non-finite frame
+            in between) and the class of the frame: 0 / 1 in a core, 2 / 3 on a path 0 -> 1 / 1 -> 0, 4 / 5 on a loop out of
+            core 0 / 1 and back, -1 undetermined;
+    times:  t_prev, t_next int64 (n,) -- the frames of those visits (-1 with prev / next = -1);
+    paths:  exit, entry int64 and direction int8 (1: 0 -> 1), each (max_paths,) with the first n_paths records written in
+            ascending entry, and n_paths int64 (1,), the true number of paths.  max_paths defaults to n, which every path fits.
+    Nothing is read back.  `workspace` is a uint8 CUDA tensor (allocated here when None)."""
+    import torch
+    lib = load_library()
+    if not (isinstance(cv, torch.Tensor) and cv.is_cuda and cv.dtype == torch.float32 and cv.is_contiguous()
+            and cv.dim() == 1):
+        raise ValueError("cv must be a contiguous float32 CUDA tensor of shape (n,)")
+    ln = _lengths(lengths)
+    n = int(cv.numel())
+    m = n if max_paths is None else int(max_paths)
+    dev = cv.device
+    out = {}
+    if frames:
+        out.update({k: torch.empty(n, dtype=torch.int8, device=dev) for k in ("prev", "next", "cls")})
+    if times:
+        out.update({k: torch.empty(n, dtype=torch.int64, device=dev) for k in ("t_prev", "t_next")})
+    if paths:
+        out.update({"exit": torch.empty(max(m, 0), dtype=torch.int64, device=dev),
+                    "entry": torch.empty(max(m, 0), dtype=torch.int64, device=dev),
+                    "direction": torch.empty(max(m, 0), dtype=torch.int8, device=dev),
+                    "n_paths": torch.empty(1, dtype=torch.int64, device=dev)})
+    workspace = _workspace(workspace, dev, "dff_path_states_workspace_bytes", n, always=False)
+    _check(lib, lib.dff_path_states(dev.index, _ptr(cv), n, ln.ctypes.data_as(C.c_void_p), int(ln.size), float(lo), float(hi),
+                                    _ptr(out.get("prev")), _ptr(out.get("next")), _ptr(out.get("t_prev")),
+                                    _ptr(out.get("t_next")), _ptr(out.get("cls")), m, _ptr(out.get("exit")),
+                                    _ptr(out.get("entry")), _ptr(out.get("direction")), _ptr(out.get("n_paths")),
+                                    _ptr(workspace), _nbytes(workspace), _stream(cv)), "dff_path_states")
     return out
 
 

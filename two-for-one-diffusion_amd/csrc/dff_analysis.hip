@@ -1,6 +1,6 @@
 // dff_analysis.hip -- the sample-analysis half of libdff_amd.so: the stateless entry points of include/dff.h that work on
 // structures already resident in HBM and never touch a dff_model (dff_pwd_*, dff_struct_*, dff_tica_*, dff_kmeans_*,
-// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi, dff_unit_hist and dff_resampled_js among them), and the kernels they launch.  The sampler kernels include none of these files.
+// dff_transition_counts, dff_rmsd_*, dff_superpose, dff_gromos_*, dff_struct_native_q, dff_core_states, dff_label_runs, dff_path_states, dff_autocorr, dff_micro_*, dff_msm_* with their batched counterparts, dff_msm_dirichlet_*, dff_sym_eig_*, dff_msm_propagate* and dff_hmm_*, dff_hmm_viterbi, dff_unit_hist and dff_resampled_js among them), and the kernels they launch.  The sampler kernels include none of these files.
 #include "dff_host_common.h"
 #include <atomic>
 #include <cstring>
@@ -15,6 +15,7 @@
 #include "dff_superpose.hip"
 #include "dff_cluster.hip"
 #include "dff_kinetics.hip"
+#include "dff_paths.hip"
 #include "dff_autocorr.hip"
 #include "dff_msm.hip"
 #include "dff_msm_batch.hip"
@@ -890,6 +891,57 @@ extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, co
         });
         first = 0;
         return rc;
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Transition paths: previous and next core of every frame, frame classes, the path table (dff_paths.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" long long dff_path_states_workspace_bytes(long long n) {
+    if (kin_check_frames(n, "path_states_workspace_bytes")) return -1;
+    return kin_blocks(n) * (long long)sizeof(PathScan);             // one carry per DFF_KIN_BLOCK frames
+}
+
+extern "C" int dff_path_states(int device, const float* cv, long long n, const long long* lengths, int n_traj, float lo,
+                               float hi, int8_t* prev, int8_t* next, long long* t_prev, long long* t_next, int8_t* cls,
+                               long long max_paths, long long* path_exit, long long* path_entry, int8_t* path_dir,
+                               long long* n_paths, void* workspace, size_t workspace_bytes, void* stream_) {
+    const char* what = "path_states";
+    int rc = kin_check_frames(n, what);
+    if (rc) return rc;
+    if (!(fabsf(lo) <= 3.402823466e38f) || !(fabsf(hi) <= 3.402823466e38f))
+        return fail(DFF_EINVAL, "%s: lo and hi must be finite", what);
+    if (!(lo < hi)) return fail(DFF_EINVAL, "%s: lo must be < hi", what);
+    if (max_paths < 0) return fail(DFF_EINVAL, "%s: negative max_paths", what);
+    if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
+    if (n > 0 && !cv) return fail(DFF_EINVAL, "%s: null cv", what);
+    if (n > 0 && n_paths && max_paths > 0 && (!path_exit || !path_entry || !path_dir))
+        return fail(DFF_EINVAL, "%s: null path output", what);
+    if ((rc = check_workspace(workspace, workspace_bytes, dff_path_states_workspace_bytes(n), what))) return rc;
+    if (n > 0 && (uintptr_t)workspace % sizeof(long long))
+        return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if (n == 0 && !n_paths) return DFF_OK;
+    if (!prev && !next && !t_prev && !t_next && !cls && !n_paths) return DFF_OK;   // nothing is asked for
+    ON_DEVICE(device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(n_paths, 0, sizeof(long long), stream));
+        return DFF_OK;
+    }
+    const KinCore src = {cv, lo, hi};
+    const PathOut out = {(signed char*)prev, (signed char*)next, t_prev, t_next, (signed char*)cls, n_paths ? max_paths : 0,
+                         path_exit, path_entry, (signed char*)path_dir};
+    PathScan* carry = (PathScan*)workspace;
+    int first = 1;
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        const unsigned nb = (unsigned)kin_blocks(runs.end - runs.begin);
+        hipLaunchKernelGGL(dff_path_reduce_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, carry);
+        hipLaunchKernelGGL(dff_path_carry_kernel, dim3(1), dim3(DFF_KIN_THREADS), 0, stream, carry, (long long)nb, n_paths, first);
+        hipLaunchKernelGGL(dff_path_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
+                           (const PathScan*)carry, out);
+        HIPCHK(hipGetLastError());
+        first = 0;
+        return DFF_OK;
     });
 }
 

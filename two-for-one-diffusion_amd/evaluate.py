@@ -4457,3 +4457,283 @@ def js_error_bars(key, boot, confidence=0.95):
     """The keys Evaluator.eval_bootstrap adds for one metric, from its JsBootstrap: numpy only."""
     lo, hi = boot.interval(confidence)
     return {key: boot.point, key + "_lo": lo, key + "_hi": hi, key + "_std": boot.std(), key + "_bias": boot.bias()}
+
+
+# =====================================================================================================
+# Transition paths, read directly from the trajectories (dff_path_states; csrc/dff_paths.hip): the path times single-molecule
+# experiments measure for fast folders (Chung & Eaton), p(TP | q), the Best-Hummer test of a reaction coordinate, and the
+# empirical committor, the model-free counterpart of committor(model, A, B).  One device call gives, per frame, the core
+# visited last AND the core visited next; everything after it composes bin_indices_1d, unit_histograms, resampling_units and
+# bootstrap_weights.  The weighted sums of the bootstrap run on the host: at most 65 536 units x (bins x 8) counts.
+# =====================================================================================================
+class PathStates:
+    """What path_states returns, tensors (n,) on the device: prev, next int8 -- the core (0: cv <= lo, 1: cv >= hi) visited
+    last / next inside the trajectory, -1 when there is none or a non-finite frame lies in between; t_prev, t_next int64 -- the
+    frames of those visits, -1 likewise; cls int8 -- 0 / 1 in a core, 2 / 3 on a path 0 -> 1 / 1 -> 0, 4 / 5 on a loop out of
+    core 0 / 1 and back, -1 undetermined."""
+
+    def __init__(self, prev, next, t_prev, t_next, cls):
+        self.prev, self.next, self.t_prev, self.t_next, self.cls = prev, next, t_prev, t_next, cls
+
+    def numpy(self):
+        return {k: getattr(self, k).cpu().numpy() for k in ("prev", "next", "t_prev", "t_next", "cls")}
+
+
+def path_states(cv, lo, hi, traj_lengths=None, *, device=None):
+    """The previous and the next core of every frame of the series cv (n,), cores cv <= lo (0) and cv >= hi (1) as in
+    core_states, per trajectory -> PathStates on the device (cv's, when it is a CUDA tensor).  prev is what core_states
+    returns.  traj_lengths=None: one trajectory."""
+    lo, hi = _check_cores(lo, hi, "path_states")
+    c = _series(cv, torch.float32, device)
+    res = binding.path_states(c, _check_lengths(traj_lengths, len(c)), lo, hi, paths=False)
+    return PathStates(res["prev"], res["next"], res["t_prev"], res["t_next"], res["cls"])
+
+
+def _path_table(res):
+    k = int(res["n_paths"].cpu())
+    out = {"exit": res["exit"][:k].cpu().numpy(), "entry": res["entry"][:k].cpu().numpy(),
+           "direction": res["direction"][:k].cpu().numpy()}
+    out["duration"] = out["entry"] - out["exit"]
+    return out
+
+
+def transition_paths(cv, lo, hi, traj_lengths=None, *, device=None):
+    """The transition paths of the series cv (n,) between the cores cv <= lo (0) and cv >= hi (1) -> a dict of numpy arrays
+    over the paths in ascending entry: exit int64, the last frame in the core left; entry int64, the first frame in the core
+    reached; direction int8, that core (1: 0 -> 1); duration int64 = entry - exit >= 1 frames (1: a direct jump).  A path lies
+    inside one trajectory and holds no non-finite frame.  traj_lengths=None: one trajectory."""
+    lo, hi = _check_cores(lo, hi, "transition_paths")
+    c = _series(cv, torch.float32, device)
+    return _path_table(binding.path_states(c, _check_lengths(traj_lengths, len(c)), lo, hi, frames=False, times=False))
+
+
+def path_time_summary(paths, frame_time=1.0):
+    """Transition-path times from the table of transition_paths: numpy only.  {direction: {"n", "mean", "median", "p10",
+    "p90"}} for direction 1 (0 -> 1) and 0 (1 -> 0): the number of paths and the mean, the median and the 10th and 90th
+    percentiles of their durations in units of frame_time; NaN without a path."""
+    if not (np.isfinite(frame_time) and frame_time > 0):
+        raise ValueError("path_time_summary: frame_time must be finite and > 0")
+    direction = np.asarray(paths["direction"], np.int64).reshape(-1)
+    duration = np.asarray(paths["duration"], np.float64).reshape(-1)
+    if len(direction) != len(duration):
+        raise ValueError("path_time_summary: direction and duration must have one entry per path")
+    out = {}
+    for d in (1, 0):
+        t = duration[direction == d] * float(frame_time)
+        nan = float("nan")
+        p10, p90 = (float(v) for v in np.percentile(t, [10, 90])) if len(t) else (nan, nan)
+        out[d] = {"n": int(len(t)), "mean": float(t.mean()) if len(t) else nan, "median": float(np.median(t)) if len(t) else nan,
+                  "p10": p10, "p90": p90}
+    return out
+
+
+PATH_CLASSES = 6
+
+
+def path_histograms(coordinate, edges, states, unit_lengths=None, *, n_states=None):
+    """Per resampling unit and per bin of `coordinate` -- cv itself or any other series of the same frames -- the frames of
+    every class and of every committor outcome: a dict of numpy arrays classes int64 (U, bins, 6), the frames of class 0 .. 5
+    of `states` (a PathStates); next int64 (U, bins, 2), the frames whose next core is 0 / 1; edges; unit_lengths.  Frames of
+    class -1 (next -1), and frames outside the edges or with a non-finite coordinate, are counted nowhere.  An integer
+    coordinate with edges=None and n_states=K bins by microstate label 0 .. K - 1 instead.  unit_lengths=None: one unit of all
+    frames; else consecutive units summing to n, as resampling_units gives them.  bin_indices_1d, a combined index (bin * 6 +
+    class, bin * 2 + next) and unit_histograms with two channels: no other kernel."""
+    cls, nxt = states.cls.reshape(-1), states.next.reshape(-1)
+    dev = cls.device
+    c = torch.as_tensor(coordinate).reshape(-1).to(dev)
+    if len(c) != len(cls):
+        raise ValueError(f"path_histograms: {len(c)} coordinate values for {len(cls)} frames")
+    if edges is None:
+        if n_states is None or int(n_states) < 1 or c.dtype.is_floating_point:
+            raise ValueError("path_histograms: edges=None needs an integer coordinate and n_states >= 1")
+        nb = int(n_states)
+        b = torch.where((c >= 0) & (c < nb), c, torch.full_like(c, -1)).to(torch.int64)
+    else:
+        edges = np.asarray(edges, np.float64)
+        b = bin_indices_1d(c, edges).to(torch.int64)
+        nb = len(edges) - 1
+    cls, nxt = cls.to(torch.int64), nxt.to(torch.int64)
+    minus = torch.full_like(b, -1)
+    idx = torch.stack([torch.where((b >= 0) & (cls >= 0), b * PATH_CLASSES + cls, minus),
+                       torch.where((b >= 0) & (nxt >= 0), b * 2 + nxt, minus)], dim=1).to(torch.int32).contiguous()
+    units = np.asarray([len(c)] if unit_lengths is None else unit_lengths, np.int64).reshape(-1)
+    h = unit_histograms(idx, [nb * PATH_CLASSES, nb * 2], units).cpu().numpy().astype(np.int64)
+    return {"classes": h[:, 0, :].reshape(len(units), nb, PATH_CLASSES), "next": h[:, 1, :nb * 2].reshape(len(units), nb, 2),
+            "edges": edges, "unit_lengths": units}
+
+
+def _conditional(counts, picks, min_count, weights, confidence):
+    """counts int64 (U, bins, k) -> for every name in picks the share of the columns picks[name] among all k columns, per
+    bin: {name: (bins,), "count": (bins,)} from the counts summed over the units, NaN in a bin with fewer than min_count
+    counted frames; with weights (B, U) also name_resamples (B, bins), the same from every resample's weighted counts, and
+    name_lo / name_hi, their percentile interval (a resample's bin under min_count is left out of that bin's interval)."""
+    counts = np.asarray(counts, np.int64)
+    if counts.ndim != 3:
+        raise ValueError("conditional histograms must be (units, bins, columns)")
+    if int(min_count) < 1:
+        raise ValueError("min_count must be >= 1")
+
+    def shares(c):                                                  # c (..., bins, k)
+        det = c.sum(axis=-1)
+        ok = det >= int(min_count)
+        safe = np.where(ok, det, 1).astype(np.float64)
+        return {name: np.where(ok, c[..., cols].sum(axis=-1) / safe, np.nan) for name, cols in picks.items()}, det
+
+    out, det = shares(counts.sum(axis=0))
+    out["count"] = det
+    if weights is not None:
+        w = np.asarray(weights, np.int64)
+        if w.ndim != 2 or w.shape[1] != counts.shape[0]:
+            raise ValueError(f"weights must be (resamples, {counts.shape[0]} units)")
+        res, _ = shares(np.einsum("bu,unk->bnk", w, counts))
+        for name in picks:
+            out[name + "_resamples"] = res[name]
+            out[name + "_lo"], out[name + "_hi"] = percentile_interval(res[name], confidence)
+    return out
+
+
+def tp_probability(hist, min_count=1, *, weights=None, confidence=0.95):
+    """p(TP | bin) of Best & Hummer from path_histograms: the share of the frames on a transition path among the determined
+    frames of a bin, p_tp = (class 2 + class 3) / (classes 0 .. 5), with p_tp_ab (class 2: paths 0 -> 1) and p_tp_ba (class
+    3) separately, and count, the determined frames per bin.  A bin with fewer than min_count determined frames is NaN: a
+    condition on the data, not a tolerance; the default 1 leaves out only empty bins.  For a perfect coordinate and diffusive
+    dynamics the maximum is 1 / 2, at the transition state.  weights uint32 (B, U) as bootstrap_weights(U, B, seed) gives them,
+    over the units of path_histograms: also p_tp_resamples (B, bins) and p_tp_lo / p_tp_hi (and _ab, _ba), the `confidence` percentile interval
+    over the resamples of the units.  numpy only."""
+    return _conditional(hist["classes"], {"p_tp": [2, 3], "p_tp_ab": [2], "p_tp_ba": [3]}, min_count, weights, confidence)
+
+
+def empirical_committor(hist, min_count=1, *, weights=None, confidence=0.95):
+    """The empirical committor from path_histograms: p_b(bin) = frames whose next core is 1 / frames whose next core is
+    known, and count, the latter per bin -- which core does the trajectory reach next, read off the trajectories, the
+    model-free counterpart of committor(model, A, B).  Frames inside core 1 count as 1, inside core 0 as 0.  A bin with fewer
+    than min_count such frames is NaN (a condition, not a tolerance; default 1).  weights: as for tp_probability, giving
+    p_b_resamples and p_b_lo / p_b_hi.  numpy only."""
+    return _conditional(hist["next"], {"p_b": [1]}, min_count, weights, confidence)
+
+
+def _half_crossing(x, p):
+    """the coordinate where p (NaN: no estimate) first crosses 1 / 2 between two neighbouring estimated bins at x, linearly
+    interpolated; NaN when it never does"""
+    x, p = np.asarray(x, np.float64), np.asarray(p, np.float64)
+    ok = np.isfinite(p)
+    x, p = x[ok], p[ok]
+    for i in range(len(p) - 1):
+        a, b = p[i] - 0.5, p[i + 1] - 0.5
+        if a == 0.0:
+            return float(x[i])
+        if a * b < 0.0:
+            return float(x[i] + (x[i + 1] - x[i]) * a / (a - b))
+    return float(x[-1]) if len(p) and p[-1] == 0.5 else float("nan")
+
+
+class TransitionPathEvaluator(_TrajectoryEvaluator):
+    """The transitions themselves: how long a barrier crossing takes, whether the order parameter is a good reaction coordinate,
+    and where the trajectories commit.  Frames -> order parameter (cv="q" or "rmsd", as for FoldingKineticsEvaluator) ->
+    binding.path_states with the cores cv <= lo and cv >= hi -> path table, class and committor histograms over nbins equal
+    bins of cv_range (default 0 .. 1 for Q, 0 .. 1.5 hi for the RMSD; frames outside are counted in no bin).  Folded is label 1
+    for Q and label 0 for the RMSD; a folding path is one that ENTERS the folded core.
+
+    eval(xyz, traj_lengths=None) returns a plain dict of floats:
+      n_paths_folding, n_paths_unfolding
+      mean_path_time_folding / _unfolding, median_path_time_folding / _unfolding   in units of frame_time; NaN without a path
+      path_frames_share, loop_frames_share, undetermined_share   shares of ALL frames: class 2 + 3, class 4 + 5, class -1
+      ptp_max, ptp_max_at          the largest p(TP | bin) over the bins with >= min_count determined frames, and that bin's centre
+      committor_half               the coordinate where the empirical committor p_b first crosses 1 / 2 (interpolated)
+      samples_nonfinite            frames with a non-finite coordinate
+    With n_resamples > 0 also ptp_max_lo / _hi (the interval of p(TP) in that bin) and committor_half_lo / _hi, over resamples
+    of the trajectories (or of their blocks of block_frames frames).  With ref_data the same keys with the suffix _ref, and
+    log10_path_time_ratio_folding / _unfolding (mean path times, samples over reference), ptp_max_diff and committor_rmsd, the
+    root mean square difference of p_b over the bins estimated in both.  Series and histograms stay on .series: {"samples" /
+    "refs": {"cv", "states", "paths", "summary", "hist", "p_tp", "p_b"}}.  Without the HIP library: DffLibraryError."""
+
+    KEYS = ("n_paths_folding", "n_paths_unfolding", "mean_path_time_folding", "mean_path_time_unfolding",
+            "median_path_time_folding", "median_path_time_unfolding", "path_frames_share", "loop_frames_share",
+            "undetermined_share", "ptp_max", "ptp_max_at", "committor_half", "samples_nonfinite")
+
+    def __init__(self, mol_name, folded, *, cv="q", lo, hi, frame_time=1.0, nbins=50, cv_range=None, min_count=1, ref_data=None,
+                 ref_traj_lengths=None, n_resamples=0, block_frames=None, seed=0, confidence=0.95, cutoff=10.0, offset=3, beta=5.0,
+                 lam=1.2, device="cuda:0"):
+        what = "TransitionPathEvaluator"
+        super().__init__(what, mol_name, frame_time, device)
+        self.lo, self.hi = _check_cores(lo, hi, what)
+        self._cv = _Observable(what, cv, ("q", "rmsd"), folded, mol_name, None, cutoff, offset, beta, lam)
+        self.cv, self.folded = cv, self._cv.folded
+        self.folded_label, self.unfolded_label = (1, 0) if cv == "q" else (0, 1)
+        if int(nbins) != nbins or not 1 <= int(nbins) <= 1 << 16:
+            raise ValueError(f"{what}: nbins must be an integer in 1 .. 65536")
+        a, b = (float(v) for v in (cv_range if cv_range is not None else ((0.0, 1.0) if cv == "q" else (0.0, 1.5 * self.hi))))
+        if not (np.isfinite(a) and np.isfinite(b) and a < b):
+            raise ValueError(f"{what}: cv_range must be finite and ascending")
+        self.edges = np.linspace(a, b, int(nbins) + 1)
+        self.centres = 0.5 * (self.edges[:-1] + self.edges[1:])
+        if int(min_count) < 1 or int(n_resamples) < 0:
+            raise ValueError(f"{what}: min_count must be >= 1 and n_resamples >= 0")
+        self.min_count, self.n_resamples, self.block_frames, self.seed = int(min_count), int(n_resamples), block_frames, seed
+        self.confidence = float(confidence)
+        self.series = {}
+        self._start(ref_data, ref_traj_lengths)
+
+    def order_parameter(self, x):
+        """float32 tensor (n,) on the device: Q or the RMSD of the frames x (n, N, 3) already there"""
+        return self._cv(x)
+
+    @staticmethod
+    def summarize(summary, cls_counts, p_tp, p_b, centres, folded_label, samples_nonfinite=0):
+        """eval()'s dict from a path_time_summary, the frames of every class -1, 0 .. 5 (7 counts), p_tp and p_b per bin and
+        the bins' centres: numpy only."""
+        nan = float("nan")
+        cls_counts = np.asarray(cls_counts, np.int64)
+        n = int(cls_counts.sum())
+        F = folded_label
+        res = {}
+        for name, d in (("folding", F), ("unfolding", 1 - F)):
+            res[f"n_paths_{name}"] = float(summary[d]["n"])
+            res[f"mean_path_time_{name}"] = summary[d]["mean"]
+            res[f"median_path_time_{name}"] = summary[d]["median"]
+        share = lambda k: float(k) / n if n else nan     # noqa: E731
+        res["path_frames_share"] = share(cls_counts[3] + cls_counts[4])
+        res["loop_frames_share"] = share(cls_counts[5] + cls_counts[6])
+        res["undetermined_share"] = share(cls_counts[0])
+        p_tp = np.asarray(p_tp, np.float64)
+        if np.isfinite(p_tp).any():
+            k = int(np.nanargmax(p_tp))
+            res["ptp_max"], res["ptp_max_at"] = float(p_tp[k]), float(centres[k])
+        else:
+            res["ptp_max"] = res["ptp_max_at"] = nan
+        res["committor_half"] = _half_crossing(centres, p_b)
+        res["samples_nonfinite"] = float(samples_nonfinite)
+        return {k: res[k] for k in TransitionPathEvaluator.KEYS}
+
+    def _analyse(self, x, lengths, name):
+        cv = self.order_parameter(x)
+        out = binding.path_states(cv, lengths, self.lo, self.hi)
+        states = PathStates(out["prev"], out["next"], out["t_prev"], out["t_next"], out["cls"])
+        paths = _path_table(out)
+        summary = path_time_summary(paths, self.frame_time)
+        units = resampling_units(lengths, self.block_frames)
+        units = units[units > 0]
+        weights = bootstrap_weights(len(units), self.n_resamples, self.seed) if self.n_resamples and len(units) else None
+        hist = path_histograms(cv, self.edges, states, units if len(units) else None)
+        p_tp = tp_probability(hist, self.min_count, weights=weights, confidence=self.confidence)
+        p_b = empirical_committor(hist, self.min_count, weights=weights, confidence=self.confidence)
+        cls_counts = np.bincount(states.cls.cpu().numpy().astype(np.int64) + 1, minlength=PATH_CLASSES + 1)
+        self.series[name] = {"cv": cv.cpu().numpy(), "states": states.numpy(), "paths": paths, "summary": summary, "hist": hist,
+                             "p_tp": p_tp, "p_b": p_b}
+        res = self.summarize(summary, cls_counts, p_tp["p_tp"], p_b["p_b"], self.centres, self.folded_label, _count_nonfinite(x))
+        if weights is not None:
+            k = int(np.nanargmax(p_tp["p_tp"])) if np.isfinite(p_tp["p_tp"]).any() else None
+            res["ptp_max_lo"] = float(p_tp["p_tp_lo"][k]) if k is not None else float("nan")
+            res["ptp_max_hi"] = float(p_tp["p_tp_hi"][k]) if k is not None else float("nan")
+            half = np.array([[_half_crossing(self.centres, row)] for row in p_b["p_b_resamples"]])
+            lo, hi = percentile_interval(half, self.confidence)
+            res["committor_half_lo"], res["committor_half_hi"] = float(lo[0]), float(hi[0])
+        return res
+
+    def _compare(self, res, ref):
+        for which in ("folding", "unfolding"):
+            res[f"log10_path_time_ratio_{which}"] = _log10_ratio(res[f"mean_path_time_{which}"], ref[f"mean_path_time_{which}"])
+        res["ptp_max_diff"] = res["ptp_max"] - ref["ptp_max"]
+        a, b = self.series["samples"]["p_b"]["p_b"], self.series["refs"]["p_b"]["p_b"]
+        both = np.isfinite(a) & np.isfinite(b)
+        res["committor_rmsd"] = float(np.sqrt(np.mean((a[both] - b[both]) ** 2))) if both.any() else float("nan")
