@@ -115,6 +115,27 @@ def ragged(n, n_traj, seed):
     return lengths.tolist()
 
 
+CARRY_STRETCH = slice(520000, 526336)                              # the undetermined stretch of carry_case("one")
+
+
+def carry_case(name):
+    """Series of more than 256 x 2048 = 524 288 frames in one launch -> (cv, lengths).  The carry scan's one workgroup takes the
+    blocks of a launch 256 at a time, so only such a launch makes it run a second chunk.
+    one        257 x 2048 + 1 frames (258 blocks), one trajectory.  Frames 520 000 .. 526 335 lie between the cores, with core A
+               on the frame before and core B on the one after (the lone frame of block 257): the stretch covers all of blocks
+               255 and 256, on both sides of the chunk's edge, so its prev arrives only through the forward carry across the
+               chunks, its next only through the reverse carry, and the path it ends is written from the second chunk.
+    periodic   514 equal trajectories of 1025 frames: the periodic path above 256 blocks.
+    groups     64 unequal trajectories of 8200 + i frames (one launch group of 258 blocks), then six short ones in a second
+               group: the count of runs / paths goes into the second launch after a two-chunk carry."""
+    if name == "one":
+        cv = cv_series(257 * 2048 + 1, 1234, 0.3)
+        cv[CARRY_STRETCH.start - 1], cv[CARRY_STRETCH], cv[CARRY_STRETCH.stop] = 0.0, M, 1.0
+        return cv, [len(cv)]
+    lengths = {"periodic": [1025] * 514, "groups": [8200 + i for i in range(64)] + [300, 1, 700, 2047, 5, 900]}[name]
+    return cv_series(sum(lengths), 4321, 0.3), lengths
+
+
 def reverse_within(a, lengths):
     """every trajectory of the series a reversed in place (the order of the trajectories stays)"""
     a = np.asarray(a)

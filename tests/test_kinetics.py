@@ -17,6 +17,7 @@ from oracle.kinetics import core_states, label_runs, native_q, scripted_frames
 from oracle.frames import chain_frames, noisy_ensemble, splitmix_labels
 from oracle.struct_metric import kabsch64_batch
 from fence import COMBINATIONS, fenced
+from paths_cases import CARRY_STRETCH, carry_case
 from stream_gate import N_FRAMES, Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, on_device, to_dev  # noqa: F401  (dev)
 
@@ -279,6 +280,22 @@ def test_label_runs_layouts(dev):
     got = ev().label_runs(lab, ragged130(n))
     for key in many:
         assert np.array_equal(got[key], many[key]), key
+
+
+@pytest.mark.parametrize("case", ["one", "periodic", "groups"])
+def test_carry_scan_second_chunk(dev, case):
+    """more than 256 blocks in one launch (paths_cases.carry_case): both scans' carry kernel runs two chunks"""
+    cv, lengths = carry_case(case)
+    lab = assert_states(cv, lengths, f"carry scan, {case}")
+    runs = assert_runs(lab, lengths, f"carry scan, {case}")
+    if case == "one":
+        s = CARRY_STRETCH
+        assert (lab[s] == 0).all() and lab[s.stop] == 1 and len(runs["start"]) == 76987
+        assert runs["start"][-1] == s.stop and runs["length"][-1] == 1 and runs["flags"][-1] == 2
+        assert runs["start"][-2] <= s.start - 1 and runs["start"][-2] + runs["length"][-2] == s.stop
+    if case == "groups":                                            # runs on both sides of the first launch group's end
+        cut = sum(lengths[:64])
+        assert (runs["start"] < cut).sum() > 5 and (runs["start"] >= cut).sum() > 5 and (np.diff(runs["start"]) > 0).all()
 
 
 def test_label_runs_max_runs(dev):

@@ -19,8 +19,8 @@ import torch
 
 from oracle.kinetics import native_q, scripted_frames
 from fence import COMBINATIONS, fenced
-from paths_cases import (HI, KEYS_FRAME, KEYS_PATH, LO, M, cv_series, path_states_oracle, ragged, reverse_within,
-                         reversed_times)
+from paths_cases import (CARRY_STRETCH, HI, KEYS_FRAME, KEYS_PATH, LO, M, carry_case, cv_series, path_states_oracle, ragged,
+                         reverse_within, reversed_times)
 from stream_gate import Spec, analysis_call, gate, ptr, raw, reference, side, stream_of  # noqa: F401  (gate, side: fixtures)
 from support import B, dev, ev, to_dev  # noqa: F401  (dev)
 
@@ -113,6 +113,23 @@ def test_trajectory_shapes(dev):
     assert len(want["entry"]) > 100
     assert_paths(cv, [300] * 40 + [0] + [300] * 40, "80 equal trajectories and an empty one")
     assert_paths(cv, [299] * 40 + [301] * 40, "80 unequal trajectories of nearly equal length")
+
+
+@pytest.mark.parametrize("case", ["one", "periodic", "groups"])
+def test_carry_scan_second_chunk(dev, case):
+    """more than 256 blocks in one launch (paths_cases.carry_case): the carry scan runs two chunks, upwards and downwards"""
+    cv, lengths = carry_case(case)
+    assert sum(lengths[:64] if case == "groups" else lengths) > 256 * 2048      # the frames of the first launch
+    want = assert_paths(cv, lengths, f"carry scan, {case}")
+    assert len(want["entry"]) > 10000 and set(want["cls"].tolist()) == {-1, 0, 1, 2, 3, 4, 5}
+    if case == "one":
+        s = CARRY_STRETCH
+        assert (want["prev"][s] == 0).all() and (want["next"][s] == 1).all() and (want["cls"][s] == 2).all()
+        assert (want["t_prev"][s] == s.start - 1).all() and (want["t_next"][s] == s.stop).all()
+        assert len(want["entry"]) == 34198
+        assert (want["exit"][-1], want["entry"][-1], want["direction"][-1]) == (s.start - 1, s.stop, 1)
+    if case == "groups":
+        assert_table_continues(want, lengths)
 
 
 # ---------------------------------------------------------------- 4. edge values

@@ -614,10 +614,8 @@ extern "C" int dff_rmsd_nearest(int device, const float* x, long long n, const f
     if (!rmsd && n > 0) return fail(DFF_EINVAL, "rmsd_nearest: null output");
     if (self_first < -1) return fail(DFF_EINVAL, "rmsd_nearest: self_first must be -1 or a candidate index");
     const long long need = dff_rmsd_nearest_workspace_bytes(n, m, N);
-    if ((rc = check_workspace(workspace, workspace_bytes, need, "rmsd_nearest"))) return rc;
     // the keys are 64-bit words that an integer atomic minimum works on
-    if (need > 0 && (uintptr_t)workspace % sizeof(unsigned long long))
-        return fail(DFF_EINVAL, "rmsd_nearest: the workspace must be 8-byte aligned");
+    if ((rc = check_workspace8(workspace, workspace_bytes, need, "rmsd_nearest"))) return rc;
     if (n == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -757,8 +755,7 @@ extern "C" int dff_gromos_steps(int device, const uint64_t* adj, long long n, in
     if (!progress) return fail(DFF_EINVAL, "gromos_steps: null progress");
     if (n > 0 && !adj) return fail(DFF_EINVAL, "gromos_steps: null adjacency matrix");
     if (n > 0 && (!labels || !centers || !sizes)) return fail(DFF_EINVAL, "gromos_steps: null output");
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_gromos_workspace_bytes(n), "gromos_steps"))) return rc;
-    if ((uintptr_t)workspace % sizeof(uint64_t)) return fail(DFF_EINVAL, "gromos_steps: the workspace must be 8-byte aligned");
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_gromos_workspace_bytes(n), "gromos_steps"))) return rc;
     if (!restart && n_steps == 0) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -821,24 +818,36 @@ extern "C" long long dff_kinetics_workspace_bytes(long long n) {
     return kin_blocks(n) * (long long)sizeof(KinScan);              // one carry per DFF_KIN_BLOCK frames
 }
 
-static int kin_check_workspace(const void* workspace, size_t workspace_bytes, long long n, const char* what) {
-    if (int rc = check_workspace(workspace, workspace_bytes, dff_kinetics_workspace_bytes(n), what)) return rc;
-    if (n > 0 && (uintptr_t)workspace % sizeof(long long))
-        return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+// the core thresholds of dff_core_states and dff_path_states
+static int kin_check_cores(float lo, float hi, const char* what) {
+    if (!(fabsf(lo) <= 3.402823466e38f) || !(fabsf(hi) <= 3.402823466e38f))
+        return fail(DFF_EINVAL, "%s: lo and hi must be finite", what);
+    if (!(lo < hi)) return fail(DFF_EINVAL, "%s: lo must be < hi", what);
     return DFF_OK;
 }
 
-// The three launches of one scan over the frames of `runs`: reduce -> carry -> apply(blocks).  count / first: the run count
-// carried over the launches of a call (dff_kin_carry_kernel).
-template <class Src, class Apply>
-static int kin_scan(hipStream_t stream, Src src, const TransRuns& runs, KinScan* carry, long long* count, int first,
-                    Apply apply) {
-    const unsigned nb = (unsigned)kin_blocks(runs.end - runs.begin);
-    hipLaunchKernelGGL(dff_kin_reduce_kernel<Src>, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, carry);
-    hipLaunchKernelGGL(dff_kin_carry_kernel, dim3(1), dim3(DFF_KIN_THREADS), 0, stream, carry, (long long)nb, count, first);
-    apply(nb);
-    HIPCHK(hipGetLastError());
-    return DFF_OK;
+// The three launches of every group of trajectories of a call (dff_frame_scan.h): reduce -> carry -> apply(src, runs, fwd,
+// rev if the call scans backwards, args...); the launch checks args against the kernel's parameters.  The workspace holds the
+// forward carries of a launch's blocks, then the reverse ones of a call that has them (rev is never read otherwise).  count
+// (may be NULL): the number of records, carried over the launches of the call; its first launch is the one that starts at
+// frame 0.
+template <class Src, class Apply, class... Args>
+static int kin_scan(hipStream_t stream, Src src, const long long* lengths, int n_traj, long long n, void* workspace, long long* count,
+                    Apply apply, Args... args) {
+    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
+        const unsigned nb = (unsigned)kin_blocks(runs.end - runs.begin);
+        typename Src::Fwd* fwd = (typename Src::Fwd*)workspace;
+        typename Src::Rev* rev = (typename Src::Rev*)(fwd + nb);
+        hipLaunchKernelGGL(dff_scan_reduce_kernel<Src>, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, fwd, rev);
+        hipLaunchKernelGGL((dff_scan_carry_kernel<typename Src::Fwd, typename Src::Rev>), dim3(1), dim3(DFF_KIN_THREADS), 0, stream,
+                           fwd, rev, (long long)nb, count, (int)(runs.begin == 0));
+        if constexpr (scan_runs<typename Src::Rev>)
+            hipLaunchKernelGGL(apply, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, fwd, rev, args...);
+        else
+            hipLaunchKernelGGL(apply, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, fwd, args...);
+        HIPCHK(hipGetLastError());
+        return DFF_OK;
+    });
 }
 
 extern "C" int dff_core_states(int device, const float* cv, long long n, const long long* lengths, int n_traj, float lo,
@@ -846,22 +855,14 @@ extern "C" int dff_core_states(int device, const float* cv, long long n, const l
                                void* stream_) {
     int rc = kin_check_frames(n, "core_states");
     if (rc) return rc;
-    if (!(fabsf(lo) <= 3.402823466e38f) || !(fabsf(hi) <= 3.402823466e38f))
-        return fail(DFF_EINVAL, "core_states: lo and hi must be finite");
-    if (!(lo < hi)) return fail(DFF_EINVAL, "core_states: lo must be < hi");
+    if ((rc = kin_check_cores(lo, hi, "core_states"))) return rc;
     if ((rc = traj_check_lengths(lengths, n_traj, n, "core_states"))) return rc;
     if (n == 0) return DFF_OK;
     if (!cv || !labels) return fail(DFF_EINVAL, "core_states: null cv / labels");
-    if ((rc = kin_check_workspace(workspace, workspace_bytes, n, "core_states"))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_kinetics_workspace_bytes(n), "core_states"))) return rc;
     ON_DEVICE(device);
-    hipStream_t stream = (hipStream_t)stream_;
-    const KinCore src = {cv, lo, hi};
-    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
-        return kin_scan(stream, src, runs, (KinScan*)workspace, nullptr, 1, [&](unsigned nb) {
-            hipLaunchKernelGGL(dff_kin_core_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
-                               (const KinScan*)workspace, labels, (signed char*)core);
-        });
-    });
+    return kin_scan((hipStream_t)stream_, KinCore{cv, lo, hi}, lengths, n_traj, n, workspace, nullptr, dff_kin_core_apply_kernel,
+                    labels, core);
 }
 
 extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, const long long* lengths, int n_traj,
@@ -874,7 +875,7 @@ extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, co
     if (n > 0 && (!labels || !n_runs)) return fail(DFF_EINVAL, "label_runs: null labels / n_runs");
     if (n > 0 && max_runs > 0 && (!run_start || !run_length || !run_label || !run_flags))
         return fail(DFF_EINVAL, "label_runs: null run output");
-    if ((rc = kin_check_workspace(workspace, workspace_bytes, n, "label_runs"))) return rc;
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_kinetics_workspace_bytes(n), "label_runs"))) return rc;
     if (n == 0 && !n_runs) return DFF_OK;
     ON_DEVICE(device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -882,16 +883,8 @@ extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, co
         HIPCHK(hipMemsetAsync(n_runs, 0, sizeof(long long), stream));
         return DFF_OK;
     }
-    const KinRuns src = {labels};
-    int first = 1;
-    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
-        const int rc = kin_scan(stream, src, runs, (KinScan*)workspace, n_runs, first, [&](unsigned nb) {
-            hipLaunchKernelGGL(dff_kin_runs_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
-                               (const KinScan*)workspace, max_runs, run_start, run_length, run_label, run_flags);
-        });
-        first = 0;
-        return rc;
-    });
+    return kin_scan(stream, KinRuns{labels}, lengths, n_traj, n, workspace, n_runs, dff_kin_runs_apply_kernel, max_runs, run_start,
+                    run_length, run_label, run_flags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -899,7 +892,7 @@ extern "C" int dff_label_runs(int device, const int32_t* labels, long long n, co
 // ---------------------------------------------------------------------------------------------
 extern "C" long long dff_path_states_workspace_bytes(long long n) {
     if (kin_check_frames(n, "path_states_workspace_bytes")) return -1;
-    return kin_blocks(n) * (long long)sizeof(PathScan);             // one carry per DFF_KIN_BLOCK frames
+    return kin_blocks(n) * (long long)(sizeof(PathFwd) + sizeof(PathBwd));   // one carry each way per DFF_KIN_BLOCK frames
 }
 
 extern "C" int dff_path_states(int device, const float* cv, long long n, const long long* lengths, int n_traj, float lo,
@@ -909,17 +902,13 @@ extern "C" int dff_path_states(int device, const float* cv, long long n, const l
     const char* what = "path_states";
     int rc = kin_check_frames(n, what);
     if (rc) return rc;
-    if (!(fabsf(lo) <= 3.402823466e38f) || !(fabsf(hi) <= 3.402823466e38f))
-        return fail(DFF_EINVAL, "%s: lo and hi must be finite", what);
-    if (!(lo < hi)) return fail(DFF_EINVAL, "%s: lo must be < hi", what);
+    if ((rc = kin_check_cores(lo, hi, what))) return rc;
     if (max_paths < 0) return fail(DFF_EINVAL, "%s: negative max_paths", what);
     if ((rc = traj_check_lengths(lengths, n_traj, n, what))) return rc;
     if (n > 0 && !cv) return fail(DFF_EINVAL, "%s: null cv", what);
     if (n > 0 && n_paths && max_paths > 0 && (!path_exit || !path_entry || !path_dir))
         return fail(DFF_EINVAL, "%s: null path output", what);
-    if ((rc = check_workspace(workspace, workspace_bytes, dff_path_states_workspace_bytes(n), what))) return rc;
-    if (n > 0 && (uintptr_t)workspace % sizeof(long long))
-        return fail(DFF_EINVAL, "%s: the workspace must be 8-byte aligned", what);
+    if ((rc = check_workspace8(workspace, workspace_bytes, dff_path_states_workspace_bytes(n), what))) return rc;
     if (n == 0 && !n_paths) return DFF_OK;
     if (!prev && !next && !t_prev && !t_next && !cls && !n_paths) return DFF_OK;   // nothing is asked for
     ON_DEVICE(device);
@@ -928,21 +917,9 @@ extern "C" int dff_path_states(int device, const float* cv, long long n, const l
         HIPCHK(hipMemsetAsync(n_paths, 0, sizeof(long long), stream));
         return DFF_OK;
     }
-    const KinCore src = {cv, lo, hi};
     const PathOut out = {(signed char*)prev, (signed char*)next, t_prev, t_next, (signed char*)cls, n_paths ? max_paths : 0,
                          path_exit, path_entry, (signed char*)path_dir};
-    PathScan* carry = (PathScan*)workspace;
-    int first = 1;
-    return traj_launches(lengths, n_traj, n, [&](const TransRuns& runs) -> int {
-        const unsigned nb = (unsigned)kin_blocks(runs.end - runs.begin);
-        hipLaunchKernelGGL(dff_path_reduce_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs, carry);
-        hipLaunchKernelGGL(dff_path_carry_kernel, dim3(1), dim3(DFF_KIN_THREADS), 0, stream, carry, (long long)nb, n_paths, first);
-        hipLaunchKernelGGL(dff_path_apply_kernel, dim3(nb), dim3(DFF_KIN_THREADS), 0, stream, src, runs,
-                           (const PathScan*)carry, out);
-        HIPCHK(hipGetLastError());
-        first = 0;
-        return DFF_OK;
-    });
+    return kin_scan(stream, PathSrc{{cv, lo, hi}}, lengths, n_traj, n, workspace, n_paths, dff_path_apply_kernel, out);
 }
 
 // ---------------------------------------------------------------------------------------------
