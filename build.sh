@@ -1,16 +1,22 @@
 #!/bin/bash
-# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  Eight translation units compiled in
+# Build libdff_amd.so (HIP kernels + C ABI) for gfx950, in-tree.  The translation units of UNITS below, compiled in
 # parallel: the <= 64-row kernel, the <= 16-row kernel once per sampler mode (score / Langevin / DDPM), the host half
 # (model, dispatch, sampler ABI), weight preparation (folds, range guard, operand images: pure CPU work), the sample-analysis
-# half (PWD / structure / TICA / state / ensemble-RMSD / superposition / clustering / kinetics / transition-path / autocorrelation / Markov-state-model / passage / spectrum / propagation / hidden-Markov-model / JS-bootstrap kernels and their ABI) and the forward process with its loss (dff_loss: q_sample, p_losses).
-# dff_analysis.hip includes its kernel files (dff_msm.hip, whose estimator kernels dff_msm_batch.hip instantiates for many problems, dff_msm_table.h, the problem table of the batched solvers, ..., dff_hmm.hip, dff_hmm_viterbi.hip, dff_hmm_mstep.hip, dff_jsboot.hip, dff_paths.hip): a new one
+# half in four family units (dff_an_structures: PWD / structure / TICA / state / ensemble-RMSD / superposition / clustering;
+# dff_an_trajectories: kinetics / transition paths / autocorrelation / JS bootstrap; dff_an_markov: Markov state models,
+# passage, spectrum, propagation; dff_an_hmm: hidden Markov models -- each with its kernels and their ABI) and the forward process with its loss (dff_loss: q_sample, p_losses).
+# Each dff_an_* unit includes its kernel files (dff_an_markov.hip: dff_msm.hip, dff_msm_batch.hip, ...; dff_an_hmm.hip: dff_hmm.hip, dff_hmm_viterbi.hip, dff_hmm_mstep.hip; dff_an_trajectories.hip: dff_paths.hip, dff_jsboot.hip, ...): a new kernel file
 # is compiled, tracked for staleness (the compiler's dependency list) and hashed (csrc/*) without a line of its own here.
+# UNITS is the only list of units: a new unit is one word there (./build.sh --objects prints the objects the library is linked from, for tools_exp.sh).
 #   DFF_EXTRA_FLAGS="-DDFF_FAST_BUILD"   development build: headline variants only (fast to compile)
 set -e
 cd "$(dirname "$(readlink -f "$0")")"
 SRC=two-for-one-diffusion_amd/csrc
 OUT=two-for-one-diffusion_amd/libdff_amd.so
 OBJ=build/obj
+UNITS="dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host dff_prep dff_an_structures dff_an_trajectories dff_an_markov dff_an_hmm dff_loss"
+OBJECTS=$(for tu in $UNITS; do printf '%s ' $OBJ/$tu.o; done)
+[ "$1" = --objects ] && { echo $OBJECTS; exit 0; }
 mkdir -p $OBJ
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result ${DFF_EXTRA_FLAGS}"
 # what the device code was built from: sha256 over csrc/* (sorted) + include/dff.h (+ non-default flags), first 16 hex digits.  dff_version() carries
@@ -33,7 +39,7 @@ stale() {
     return 1
 }
 pids=()
-for tu in dff_kernels dff_small_m0 dff_small_m1 dff_small_m2 dff_host dff_prep dff_analysis dff_loss; do
+for tu in $UNITS; do
     # rebuild a unit only when one of its own sources is newer than its object (or the flags changed)
     stamp="$OBJ/$tu.flags"
     src=$tu; extra=""
@@ -53,5 +59,5 @@ done
 rc=0
 for p in "${pids[@]}"; do wait $p || rc=1; done
 [ $rc = 0 ] || { echo "compile failed"; exit 1; }
-hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/dff_kernels.o $OBJ/dff_small_m0.o $OBJ/dff_small_m1.o $OBJ/dff_small_m2.o $OBJ/dff_host.o $OBJ/dff_prep.o $OBJ/dff_analysis.o $OBJ/dff_loss.o -o $OUT
+hipcc --offload-arch=gfx950 -shared -fPIC $OBJECTS -o $OUT
 echo "built $OUT"

@@ -3,7 +3,7 @@
 dff_msm_propagate launch, and on which problems, for every debug path and the state counts that their selection rules name
 (tests/test_msm_batch_plan.py pins the host-only plan, dff_debug_msm_batch_plan, to it).
 
-The three rules below are a statement of csrc/dff_analysis.hip as it was when each call still carried a selection of its own:
+The three rules below are a statement of the batched solvers' host code (csrc/dff_analysis.hip then, csrc/dff_an_markov.hip now) as it was when each call still carried a selection of its own:
 one function per call, written from that code line by line, not from the function that replaced them.  No GPU, no library:
 python tests/golden/make_batch_plan_table.py [out.json]
 

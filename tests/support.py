@@ -3,7 +3,9 @@ the package, the upload helpers, the constants and bars that more than one file 
 top of them (refused, same_bits among them).  The host stand-ins that go behind evaluate's seams are in tests/standins.py.  Fixtures are imported by name (`from support import dev  # noqa: F401`).  Pytest does not rewrite the
 asserts of this module, so each of them carries the values it compares in its message."""
 import argparse
+import os
 import pickle
+import re
 
 import numpy as np
 import pytest
@@ -47,6 +49,26 @@ def ev():
 def hmm_chunk():
     """frames of a chain per chunk of the hidden-Markov-model kernels, read from the library"""
     return B().hmm_chunk()
+
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CSRC = os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc")
+
+
+def build_units():
+    """the translation units build.sh compiles and links, {unit: its source file in csrc/}, from its one list (UNITS)"""
+    units = re.search(r'(?m)^UNITS="([^"]+)"$', open(os.path.join(ROOT, "build.sh")).read()).group(1).split()
+    assert len(units) == len(set(units)), units
+    return {u: re.sub(r"^dff_small_m\d$", "dff_small", u) + ".hip" for u in units}   # the <= 16-row kernel: once per sampler mode
+
+
+def owning_unit(kernel_file):
+    """The text of the unit that compiles csrc/<kernel_file> into the library: of the units build.sh lists, the ONE whose
+    source includes the file by name."""
+    texts = {src: open(os.path.join(CSRC, src)).read() for src in set(build_units().values())}
+    owners = [src for src, text in sorted(texts.items()) if '#include "%s"' % kernel_file in text]
+    assert len(owners) == 1, (kernel_file, owners)
+    return texts[owners[0]]
 
 
 def refused(lib, rc, what):

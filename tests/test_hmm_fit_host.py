@@ -21,7 +21,7 @@ import hmm_cases as hc
 import hmm_fit_cases as fc
 from dff_amd import binding, evaluate
 from standins import HostEstep, OracleSweeps
-from support import hmm_chunk, refused
+from support import hmm_chunk, owning_unit, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 p = lambda a: a.ctypes.data_as(C.c_void_p)     # noqa: E731
@@ -42,7 +42,7 @@ def test_header_library_and_binding_declare_the_calls():
     assert fields == [("int32_t", "n_estep"), ("int32_t", "stop"), ("int32_t", "estep_status"), ("int32_t", "flags"),
                       ("double", "last_loglik"), ("long long", "rev_sweeps")]
     assert binding.HMM_FIT_STATE.itemsize == 32 and list(binding.HMM_FIT_STATE.names) == [f for _, f in fields]
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_hmm_mstep.hip")
     assert '#include "dff_hmm_mstep.hip"' in text
     rec = np.zeros(1, binding.HMM_FIT_STATE)
     rec["n_estep"], rec["stop"], rec["flags"], rec["last_loglik"], rec["rev_sweeps"] = 7, 1, 3, -2.5, 1 << 40

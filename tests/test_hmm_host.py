@@ -17,7 +17,7 @@ from dff_amd import binding, evaluate
 from oracle import kinetics as kin
 from oracle import msm as oracle
 from standins import HostEstep, HostSpectral, OracleSweeps
-from support import hmm_chunk, refused
+from support import hmm_chunk, owning_unit, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_hmm_chunk", "dff_hmm_plan", "dff_hmm_workspace_bytes", "dff_hmm_estep")
@@ -36,7 +36,7 @@ def test_symbols_in_header_binding_and_library():
     assert len(binding.SYMBOLS["dff_hmm_estep"][1]) == 18 and len(binding.SYMBOLS["dff_hmm_workspace_bytes"][1]) == 6
     assert "#define DFF_HMM_MAXM 8" in header and binding.HMM_MAX_HIDDEN == evaluate.HMM_MAX_HIDDEN == 8
     assert hmm_chunk() in (64, 128, 256, 512)
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_hmm.hip")
     assert '#include "dff_hmm.hip"' in text
     build = open(os.path.join(ROOT, "build.sh")).read()
     assert "dff_hmm.hip" in build and "dff_hmm.hip" not in re.sub(r"(?m)^#.*$", "", build)      # named in the comments only

@@ -16,7 +16,7 @@ import viterbi_cases as vc
 from dff_amd import binding, evaluate
 from oracle import kinetics as kin
 from standins import HostEstep, HostViterbi
-from support import hmm_chunk, refused
+from support import hmm_chunk, owning_unit, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_hmm_viterbi_workspace_bytes", "dff_hmm_viterbi", "dff_debug_hmm_viterbi_stages")
@@ -35,7 +35,7 @@ def test_symbols_in_header_binding_and_library():
         assert getattr(lib, name) is not None
     assert len(binding.SYMBOLS["dff_hmm_viterbi"][1]) == 18 and len(binding.SYMBOLS["dff_hmm_viterbi_workspace_bytes"][1]) == 6
     assert binding.SYMBOLS["dff_debug_hmm_viterbi_stages"] == (C.c_int, [C.c_int])
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_hmm_viterbi.hip")
     assert '#include "dff_hmm_viterbi.hip"' in text
     kernels = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_hmm_viterbi.hip")).read()
     assert '#include "dff_hmm.hip"' in kernels and "#define DFF_HMM_CHUNK" not in kernels          # the plan and the chunk are the E-step's

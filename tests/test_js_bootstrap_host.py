@@ -12,7 +12,7 @@ import torch
 import dff_amd
 import js_cases as jc
 from dff_amd import binding, evaluate
-from support import refused
+from support import owning_unit, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -43,7 +43,7 @@ def test_symbols_in_header_binding_library_and_package():
         assert name in dff_amd.__all__ and getattr(dff_amd, name) is getattr(evaluate, name)
     for cls in (evaluate.PwdEvaluator, evaluate.TicEvaluator, evaluate.DihedralEnergiesEvaluator, evaluate.Evaluator):
         assert callable(cls.eval_bootstrap)
-    assert '#include "dff_jsboot.hip"' in open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    assert '#include "dff_jsboot.hip"' in owning_unit("dff_jsboot.hip")
     assert "dff_jsboot.hip" in open(os.path.join(ROOT, "build.sh")).read()
 
 

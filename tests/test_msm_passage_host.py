@@ -15,7 +15,7 @@ from dff_amd import binding, evaluate
 from oracle import msm_bootstrap as boot
 from oracle import passage as po
 from standins import OracleSweeps
-from support import refused
+from support import owning_unit, refused
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_msm_dirichlet_workspace_bytes", "dff_msm_dirichlet_lds_limit", "dff_msm_dirichlet_solve", "dff_debug_msm_dirichlet_path")
@@ -34,7 +34,7 @@ def test_symbols_in_header_binding_and_library():
     assert len(binding.SYMBOLS["dff_msm_dirichlet_solve"][1]) == 15
     assert binding.SYMBOLS["dff_msm_dirichlet_workspace_bytes"] == (C.c_longlong, [C.c_int, C.c_int])
     assert binding.MSM_DIRICHLET_MAX_BATCH == evaluate.DIRICHLET_MAX_BATCH == 16384
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_msm_passage.hip")
     assert '#include "dff_msm_passage.hip"' in text
     L = binding.msm_dirichlet_lds_limit()
     assert 64 <= L < 1024 and 8 * ((L + 1) * (L + 2) // 2 + (L + 1) + 2 * L) + 4096 <= 160 * 1024        # the triangle fits a CU's LDS

@@ -17,7 +17,7 @@ from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle.msm_bootstrap import five_state_case
 from standins import HostSpectral, OracleSweeps
-from support import refused, same_bits
+from support import owning_unit, refused, same_bits
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_msm_propagate_workspace_bytes", "dff_msm_propagate_lds_limit", "dff_msm_propagate", "dff_debug_msm_propagate_path")
@@ -39,7 +39,7 @@ def test_symbols_in_header_binding_and_library():
     assert binding.SYMBOLS["dff_debug_msm_propagate_path"] == (C.c_int, [C.c_int])
     assert binding.MSM_PROPAGATE_MAX_BATCH == evaluate.PROPAGATE_MAX_BATCH == 16384
     assert binding.MSM_PROPAGATE_MAX_ROWS == evaluate.PROPAGATE_MAX_ROWS == 16 and binding.MSM_PROPAGATE_MAX_STEPS == 65535
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_msm_propagate.hip")
     assert '#include "dff_msm_propagate.hip"' in text
     assert "dff_msm_propagate.hip" not in re.sub(r"(?m)^#.*$", "", open(os.path.join(ROOT, "build.sh")).read())   # comments only
 

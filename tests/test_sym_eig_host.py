@@ -18,7 +18,7 @@ from oracle import msm as oracle
 from oracle import msm_bootstrap as boot
 from oracle.msm_bootstrap import five_state_case
 from standins import OracleSweeps
-from support import refused, same_bits
+from support import owning_unit, refused, same_bits
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NAMES = ("dff_sym_eig_workspace_bytes", "dff_sym_eig_lds_limit", "dff_sym_eig_topk", "dff_debug_sym_eig_path")
@@ -38,7 +38,7 @@ def test_symbols_in_header_binding_and_library():
     assert binding.SYMBOLS["dff_sym_eig_workspace_bytes"] == (C.c_longlong, [C.c_int, C.c_int])
     assert binding.SYMBOLS["dff_sym_eig_lds_limit"] == (C.c_int, []) and binding.SYMBOLS["dff_debug_sym_eig_path"] == (C.c_int, [C.c_int])
     assert binding.SYM_EIG_MAX_BATCH == evaluate.SPECTRUM_MAX_BATCH == 16384 and binding.SYM_EIG_MAX_K == 32
-    text = open(os.path.join(ROOT, "two-for-one-diffusion_amd", "csrc", "dff_analysis.hip")).read()
+    text = owning_unit("dff_sym_eig.hip")
     assert '#include "dff_sym_eig.hip"' in text
     assert "dff_sym_eig" not in open(os.path.join(ROOT, "build.sh")).read()
 

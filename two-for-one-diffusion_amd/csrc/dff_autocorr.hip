@@ -24,7 +24,7 @@
 //     are added in thread order.  No floating-point atomics; the order of every addition follows from (n, d, max_lag)
 //     alone, so the results are bit-identical from call to call.
 #pragma once
-#include "dff_states.hip"   // TransRuns, last_le
+#include "dff_traj.h"   // TransRuns, last_le
 
 #define DFF_AC_THREADS 256
 #define DFF_AC_MAXD 8

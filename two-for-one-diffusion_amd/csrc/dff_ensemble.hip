@@ -37,7 +37,7 @@
 #pragma once
 #include "dff_internal.h"
 #include "dff_kabsch.h"
-#include "dff_tica.hip"   // f64x4
+#include "dff_frames.h"   // f64x4
 
 #define DFF_ENS_THREADS 256
 #define DFF_ENS_TC 32              // candidates per workgroup: two 16-column MFMA tiles

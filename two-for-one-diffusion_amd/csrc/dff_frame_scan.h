@@ -22,7 +22,7 @@
 #pragma once
 #include <type_traits>
 
-#include "dff_states.hip"   // TransRuns, last_le
+#include "dff_traj.h"   // TransRuns, last_le
 
 #define DFF_KIN_THREADS 256
 #define DFF_KIN_ITERS 8

@@ -37,7 +37,7 @@
 // dff_hmm_finish_kernel    status from the flags; on a non-zero status every output becomes NaN.
 // No floating-point atomics, no workgroup waits on another; every launch is sized by the host plan alone.
 #pragma once
-#include "dff_msm_batch.hip"   // MsmbWords / dff_msmb_upload_kernel
+#include <hip/hip_runtime.h>
 
 #ifndef DFF_HMM_CHUNK
 #define DFF_HMM_CHUNK 128          // frames of a chain per chunk: measured among 64 / 128 / 256 / 512

@@ -19,6 +19,7 @@
 //     statement tests/hmm_fit_cases.py makes.  A row whose occupancy is not positive keeps its values (flag bit 0); a
 //     reversible step on a graph that is not strongly connected stops the fit (3) and changes no parameter.
 #pragma once
+#include "../../include/dff.h"   // dff_hmm_fit_state
 #include "dff_hmm.hip"
 
 #define DFF_HMM_FIT_THREADS 256

@@ -1,6 +1,6 @@
 // dff_host.hip -- host half of libdff_amd.so: the model handle (upload of the images dff_prep.hip prepares), scratch
 // management, kernel dispatch and the model's part of the extern "C" ABI declared in include/dff.h
-// (the stateless sample-analysis entry points are dff_analysis.hip).
+// (the stateless sample-analysis entry points are the dff_an_*.hip units).
 #include "../../include/dff.h"
 #include "dff_internal.h"
 
@@ -12,7 +12,7 @@
 #include <vector>
 
 // the two sampler kernels are their own translation units (dff_kernels.hip, dff_small.hip: they export variant
-// lookups, dff_device.h); the sample-analysis entry points and their kernels are a third (dff_analysis.hip)
+// lookups, dff_device.h); the sample-analysis entry points and their kernels are units of their own, one per group of families (dff_an_*.hip)
 #include "dff_device.h"
 #include "dff_host_common.h"
 #include "dff_prep.h"

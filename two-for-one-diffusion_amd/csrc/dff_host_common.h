@@ -1,5 +1,5 @@
-// dff_host_common.h -- what the host translation units of libdff_amd.so (dff_host.hip: the model; dff_analysis.hip: the
-// stateless sample-analysis entry points; dff_loss.hip: the forward process and its loss) share: the error report behind dff_last_error, HIPCHK, the device guard.
+// dff_host_common.h -- what the host translation units of libdff_amd.so (dff_host.hip: the model; dff_an_*.hip: the
+// stateless sample-analysis entry points, which share dff_analysis_host.h on top of this; dff_loss.hip: the forward process and its loss) share: the error report behind dff_last_error, HIPCHK, the device guard.
 // Host code only: no kernel file includes it.
 #pragma once
 #include "../../include/dff.h"

@@ -20,7 +20,7 @@
 //     order, the 64 lanes of a wave by a butterfly, the four waves as (0 + 1) + (2 + 3): the order depends on nbins[c] alone,
 //     not on TB, B or the resample's place in the batch, and the integer sums are exact -- every TB gives the same bits.
 #pragma once
-#include "dff_msm_batch.hip"   // msmb_upload's kernel: host tables travel as kernel arguments
+#include <hip/hip_runtime.h>
 
 #define DFF_JSB_THREADS 256
 #define DFF_JSB_TILE_BINS 8192           // bins per LDS tile of dff_unit_hist (32 KB)

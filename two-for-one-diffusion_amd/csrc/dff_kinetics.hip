@@ -22,7 +22,7 @@
 //     and writes the run's whole record.
 #pragma once
 #include "dff_frame_scan.h"   // the scan, DFF_KIN_*, TrajFrames
-#include "dff_states.hip"     // struct_tiles
+#include "dff_frames.h"       // struct_tiles
 
 // ---- soft fraction of native contacts.  LDS: lambda r0 (P doubles, rounded up to 16 bytes) | tile | packed pairs (P x 2 bytes)
 __host__ __device__ __forceinline__ int native_q_r0_floats(int P) { return 2 * ((P + 1) & ~1); }

@@ -31,7 +31,7 @@
 //     dff_msm_reversible_steps) or MsmLive of dff_msm_batch.hip (a table of problems: the batched call).  err_s = max_i |x_i' - x_i| / x_i by an integer atomic max on the bits of the non-negative double (a NaN
 //     has the largest pattern: one NaN row makes err NaN).
 #pragma once
-#include "dff_states.hip"   // state_nearest's rule, TransRuns, TransLags, last_le, wave_sum
+#include "dff_traj.h"       // state_nearest's rule, DFF_KM_MAXD, TransRuns, TransLags, last_le
 #include "dff_msm_rows.h"   // msm_q, msm_row, msm_finish
 
 #define DFF_MICRO_CHUNK 1024       // points per workgroup: at K = 1024, d = 8 the largest power of two whose coordinates

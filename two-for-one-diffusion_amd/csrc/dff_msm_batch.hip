@@ -18,27 +18,17 @@
 //     same kernels as the single call's, hence its bits, problem by problem.  err is (n_steps, B): sweep s of problem b at
 //     err[s * B + b].
 #pragma once
-#include "dff_msm.hip"
+#include "dff_msm.hip"       // the estimator kernels that MsmLive instantiates
 #include "dff_msm_table.h"   // the live problems' descriptors
+#include "dff_upload.h"      // MsmbWords, DFF_MSMB_UPLOAD
 
 #define DFF_MSMB_MAXB 4096           // resamples / problems per call
 #define DFF_RC_MAXUNITS (1 << 20)    // resampling units per call
 #define DFF_RC_MAXCOUNTERS (1LL << 28)   // B K^2 counters per call (2 GiB)
-#define DFF_MSMB_UPLOAD 448          // 64-bit words per upload launch: 3.5 KB of kernel arguments
-
-struct MsmbWords {
-    long long v[DFF_MSMB_UPLOAD];
-};
 
 __global__ __launch_bounds__(64) void dff_msmb_upload_kernel(MsmbWords words, int cnt, long long* __restrict__ dst) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < cnt) dst[i] = words.v[i];
-}
-
-// the segment (trajectory, unit) of frame t: start[0] = 0 <= t < start[n]; t0 <= t is the wave's first frame
-__device__ __forceinline__ int rc_segment(const long long* __restrict__ start, int n, long long t, long long t0) {
-    const int r0 = last_le(start, n, t0);                           // the same addresses in every lane
-    return t < start[r0 + 1] ? r0 : last_le(start, n, t);
 }
 
 // ---- weighted sliding-window counts of B resamples into counts (B, K, K), zeroed before.  tstart (n_traj + 1) and ustart

@@ -25,7 +25,9 @@
 // problem's place in it, or on what the workspace held.  No atomics, and no workgroup waits on another.
 #pragma once
 #include <cfloat>
-#include "dff_msm_batch.hip"   // MsmbWords / dff_msmb_upload_kernel, wave_sum
+#include "../../include/dff.h"   // DFF_MSM_MAXK
+#include "dff_frames.h"          // wave_sum
+#include "dff_msm_table.h"       // the problems' descriptors
 
 #define DFF_DIR_THREADS 256
 #define DFF_DIR_MAXP 16384            // problems per call

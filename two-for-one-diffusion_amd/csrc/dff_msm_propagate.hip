@@ -22,7 +22,8 @@
 // on the way (an overflow to infinity, then inf - inf or 0 inf) shows in out, because every w_s[m][j] enters out[s][m][.]:
 // status 2, every output NaN.  Status 0 never comes with a NaN.  No atomics, no workgroup waits on another.
 #pragma once
-#include "dff_msm_batch.hip"   // MsmbWords / dff_msmb_upload_kernel
+#include <hip/hip_runtime.h>
+#include "dff_msm_table.h"   // the problems' descriptors
 
 #define DFF_PROP_THREADS 512
 #define DFF_PROP_MAXP 16384           // problems per call

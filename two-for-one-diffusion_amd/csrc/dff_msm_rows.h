@@ -2,7 +2,7 @@
 // q_j = c_j / x_j: ONE copy for both drivers of dff_msm.hip (one launch per sweep; one looping workgroup), whether they run
 // on one problem or on many per launch (dff_msm_batch.hip), so that all of them give the same bits.
 #pragma once
-#include "dff_struct.hip"   // wave_sum
+#include "dff_frames.h"   // wave_sum
 
 // q of a state from its row count and its x; NaN where the estimator is not defined (c <= 0, x <= 0, either NaN)
 __device__ __forceinline__ double msm_q(double c, double x) { return (c > 0.0 && x > 0.0) ? c / x : __builtin_nan(""); }

@@ -1,7 +1,7 @@
 // dff_msm_table.h -- the problem table of the batched Markov-model calls: ONE 64-bit word per problem, slot << 11 | K_p.  K_p
 // (<= 1024 < 2^11) is the problem's state count, `slot` says where its matrix lies: the problem's own index b for the estimator
 // (dff_msm_batch.hip), the flux matrix for the Dirichlet solver (dff_msm_passage.hip), the transition matrix for propagation
-// (dff_msm_propagate.hip).  The host packs (dff_analysis.hip: MsmTable), the kernels unpack.  dff_sym_eig.hip reads bare
+// (dff_msm_propagate.hip).  The host packs (dff_an_markov.hip: MsmTable), the kernels unpack.  dff_sym_eig.hip reads bare
 // counts: slot 0.
 #pragma once
 

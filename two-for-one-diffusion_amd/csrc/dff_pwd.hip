@@ -18,8 +18,7 @@
 // (blockIdx % 8) so that only the first of them reads the tile from HBM; the others hit that XCD's L2.
 #pragma once
 #include "dff_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "dff_frames.h"   // f32x4, pwd_dist2
 
 #define DFF_PWD_THREADS 256
 // the histogram kernel owns the whole CU's LDS (one workgroup per CU), so it brings 16 waves of its own:
@@ -55,15 +54,6 @@ __device__ __forceinline__ void pwd_load_tile(float* tile, const float* __restri
     } else {
         for (int k = threadIdx.x; k < nf; k += NT) tile[k] = src[k];
     }
-}
-
-__device__ __forceinline__ float pwd_dist2(const float* xs, int oi, int oj) {
-    const float* a = xs + oi;
-    const float* b = xs + oj;
-    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    // sqrtf and '/' are correctly rounded here (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt);
-    // the __fsqrt_rn / __fdiv_rn intrinsics are NOT (they lower to the fast native ops)
-    return sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
 }
 
 // Thread layout of both kernels: PC (a power of two <= 256) pair lanes x threads/PC structure groups.  A

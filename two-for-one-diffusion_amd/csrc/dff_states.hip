@@ -29,42 +29,11 @@
 //     every 2^31 frames a workgroup has seen (a counter grows by at most one per frame).  Integer sums do not depend
 //     on their order: the result is exact and reproducible.
 #pragma once
-#include "dff_struct.hip"   // struct_tiles, struct_tic_project, last_le, wave_sum
+#include "dff_frames.h"   // struct_tiles, struct_tic_project, wave_sum
+#include "dff_traj.h"     // state_nearest, TransRuns, TransLags, DFF_TC_*
 
-#define DFF_STATES_MAXK 64         // states / cluster centres
-#define DFF_KM_MAXD 8              // coordinates per point (= DFF_TIC_MAXK)
 #define DFF_KM_THREADS 256
 #define DFF_KM_WGS 512             // workgroups, at most: the partial slots the second stage walks
-#define DFF_TC_THREADS 256
-#define DFF_TC_WGS 1024
-#define DFF_TC_MAXLAGS 8
-#define DFF_TC_RUNS 64             // trajectories per launch (kernel argument)
-#define DFF_TC_LDS_COUNTERS 8192   // 32 KB of private counters: lags are processed in groups of DFF_TC_LDS_COUNTERS / K^2
-#define DFF_TC_FLUSH_ITERS (1 << 23)   // x 256 threads = 2^31 frames per workgroup between flushes
-
-// label of the nearest of K centres (K, d) row-major to p (d <= MAXD coordinates), best = its squared distance
-template <int MAXD>
-__device__ __forceinline__ int state_nearest(const double (&p)[MAXD], int d, const double* __restrict__ centers, int K,
-                                             double& best) {
-    bool finite = true;
-#pragma unroll
-    for (int j = 0; j < MAXD; ++j)
-        if (j < d) finite = finite && isfinite(p[j]);
-    int lab = 0;
-    best = 0.0;
-    for (int c = 0; c < K; ++c) {
-        double d2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < MAXD; ++j)
-            if (j < d) {
-                const double e = p[j] - centers[c * d + j];
-                d2 = fma(e, e, d2);
-            }
-        if (c == 0 || d2 < best) { best = d2; lab = c; }
-    }
-    if (!finite) { lab = -1; best = __builtin_nan(""); }
-    return lab;
-}
 
 // ---- frames -> state labels.  LDS: tile.  mean (F,), A (F, k), centres (K, k): wave-uniform loads
 __global__ __launch_bounds__(DFF_STRUCT_TILE) void dff_struct_tic_assign_kernel(
@@ -172,18 +141,6 @@ __global__ __launch_bounds__(64) void dff_kmeans_reduce_kernel(const double* __r
         }
     }
 }
-
-// the trajectories of one launch: frames begin .. end.  period > 0: back-to-back trajectories of `period` frames each
-// from `begin` on; else trajectory r holds frames start[r] .. start[r + 1] - 1 (start[0] = begin, start[n] = end)
-struct TransRuns {
-    long long begin, end, period;
-    int n;
-    long long start[DFF_TC_RUNS + 1];
-};
-struct TransLags {
-    int n;
-    int lag[DFF_TC_MAXLAGS];
-};
 
 // ---- sliding-window transition counts of the lags of one group.  counts: this group's first (K, K) matrix.
 // LDS: lags.n x K x K counters

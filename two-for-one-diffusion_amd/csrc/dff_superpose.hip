@@ -29,7 +29,7 @@
 //   N = 35:   848 + 26 880 (+ 16 896 + 1 120) = 27 728 / 45 744
 //   N = 64: 1 536 + 49 408 (+ 16 896 + 2 048) = 50 944 / 69 888        (limit 163 840)
 #pragma once
-#include "dff_struct.hip"
+#include "dff_frames.h"   // struct_tiles, struct_store_tile, struct_centre_ref, struct_frame_key
 
 #define DFF_SUP_WGS 4096          // workgroups at most: each owns one slice of partials in the workspace
 #define DFF_SUP_CB 8              // beads per pass through the staging buffer

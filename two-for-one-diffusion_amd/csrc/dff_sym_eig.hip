@@ -32,7 +32,8 @@
 #pragma once
 #include <cfloat>
 #include <type_traits>
-#include "dff_msm_batch.hip"   // MsmbWords / dff_msmb_upload_kernel, wave_sum
+#include "../../include/dff.h"   // DFF_MSM_MAXK
+#include "dff_frames.h"          // wave_sum
 
 #define DFF_EIG_MAXP 16384            // problems per call
 #define DFF_EIG_MAXTOP 32             // eigenpairs per problem

@@ -19,7 +19,7 @@
 // Pipeline, per chunk of <= C pair starts (C from the feature count only):
 //   1. dff_tica_features_kernel writes the fp32 features of the chunk's frames, tau frames of overlap included, into the
 //      workspace (row-major, F per row).  Its feature loop is deliberately a second one next to struct_tic_walk
-//      (dff_struct.hip): it stops every DFF_TICA_FCH features, in the middle of the distance block, to flush its LDS
+//      (dff_frames.h): it stops every DFF_TICA_FCH features, in the middle of the distance block, to flush its LDS
 //      stage, and carries the pair (i, j) across the stops.  Both call struct_dihedral / pwd_dist2: the same bits.
 //   2. dff_tica_moments_kernel: one workgroup (4 waves) per (64 x 64 upper-triangular output tile, slice of pairs).  Per
 //      stage of 32 pairs it converts rows t and t + tau of the tile's two 64-feature blocks to fp64 u, v in LDS, then
@@ -30,7 +30,7 @@
 // v_mfma_f64_16x16x4_f64 operands: A[i][k] = lane (i = lane & 15, k = lane >> 4), B[k][j] likewise, one f64 each;
 // C/D: register r of lane l is D[row = (l >> 4) + 4 r][col = l & 15] -- NOT the f32 16x16x4 map (row = 4 (l >> 4) + r).
 #pragma once
-#include "dff_struct.hip"   // struct_tiles, struct_dihedral, pwd_dist2
+#include "dff_frames.h"   // struct_tiles, struct_dihedral, pwd_dist2, f64x4
 
 #define DFF_TICA_T 64          // output tile edge (features)
 #define DFF_TICA_K 32          // pairs per LDS stage
@@ -41,8 +41,6 @@
 #define DFF_TICA_FCH 32        // features per staging chunk of the feature kernel
 #define DFF_TICA_THREADS 256
 #define DFF_TICA_LDS_BYTES (4 * DFF_TICA_K * DFF_TICA_LD * 8)
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // the pairs of one launch: run r holds pairs cum[r] .. cum[r + 1] - 1, the first of them starting at feature row row[r]
 struct TicaRuns {
