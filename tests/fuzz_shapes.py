@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Random model shapes / batch shapes / magnitudes against the oracle twin (float64): forces (dff_score; all input branches, energy
-and force heads, batches of 1 .. 900) and a few fused Langevin and reverse-DDPM steps on supplied noise (shipped branch, energy
-head; frames and final velocities).  The bars are the tests': GUARD x the twin's own float32 distance for forces, STEP_TOL per
-step for the loops.
+and force heads, batches of 1 .. 900), the per-bead energies of the same call (energy heads, all input branches) and a few fused
+Langevin and reverse-DDPM steps on supplied noise (shipped branch, energy head; frames and final velocities).  The bars are the
+tests': GUARD x the twin's own float32 distance for forces, K_E x it for energies (batch and every protein), STEP_TOL per step for
+the loops.
 test_gpu_parity.py::test_random_shapes runs a short sweep; `python tests/fuzz_shapes.py [n_cases] [seed]` a long one (GPU box)."""
 import os, sys, json
 import numpy as np, torch
@@ -14,6 +15,7 @@ from dff_amd.ddpm import GaussianDiffusion  # noqa: E402
 from dff_amd.langevin import LangevinDiffusion  # noqa: E402
 
 GUARD, GUARD_FP32, STEP_TOL = 2.0, 2.5, 5e-6   # tests/test_gpu_parity.py: the split engine's bar, the fp32-MFMA engine's, the loops'
+K_E, K_E_FP32 = 2.5, 4.0                       # tests/test_score_energy.py (support.K_E, K_E_FP32): the energies' bar, per engine
 rel = lambda a, b: float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))  # noqa: E731
 
 
@@ -63,13 +65,18 @@ def _case(case, rng, log, only=None, hook=None):
         model.native.set_group(G)
         x = (synth.normal((B, N, 3), 11 + case, N) * xs).astype(np.float32)
         t = rng.uniform(0.0, 1.0, B).astype(np.float32)
-        f = model.native.score(torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda()).cpu().numpy()
+        f = model.native.score(torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda(), return_energy=cons)
+        f, e = (f[0].cpu().numpy(), f[1].cpu().numpy()) if cons else (f.cpu().numpy(), None)
         kn = model.native.last_launch()[0]
         sub = np.arange(B) if B <= 12 else np.sort(rng.choice(B, 8, replace=False))   # (a sample's forces depend on that sample only)
         xs_, ts_ = torch.from_numpy(x[sub]), torch.from_numpy(t[sub])
-        r64ref = twin.score(twin.to_torch(params, torch.float64), xs_.double(), ts_.double(), L, conservative=cons, flags=fl).numpy()
-        r32 = rel(twin.score(twin.to_torch(params), xs_, ts_, L, conservative=cons, flags=fl).numpy(), r64ref)
+        # (conservative cases: the twin's per-bead energies too, (B, N, 1); a force head has none)
+        unpack = lambda out: (out[0].numpy(), out[1].numpy()[..., 0]) if cons else (out.numpy(), None)  # noqa: E731
+        r64ref, e64 = unpack(twin.score(twin.to_torch(params, torch.float64), xs_.double(), ts_.double(), L, return_energy=cons, conservative=cons, flags=fl))
+        f32ref, e32 = unpack(twin.score(twin.to_torch(params), xs_, ts_, L, return_energy=cons, conservative=cons, flags=fl))
+        r32 = rel(f32ref, r64ref)
         r = rel(f[sub], r64ref)
+        r32e = rel(e32, e64) if cons else 0.0
         if not shipped and xs > 1.5 and r > 2.5 * max(r32, 4e-7):
             # Distance features far from the origin: single trajectories there are float32-UNSTABLE in the reference itself -- its own
             # float32 run lands 3e-3 from its float64 one on one host CPU and 1.1e-1 on another (profiles/r06/gen_outliers*.txt; a
@@ -78,7 +85,9 @@ def _case(case, rng, log, only=None, hook=None):
             # forces compared with the float64 run at x).
             for direction in (np.inf, -np.inf):
                 xn = torch.from_numpy(np.nextafter(x[sub], np.float32(direction)).astype(np.float32))
-                r32 = max(r32, rel(twin.score(twin.to_torch(params), xn, ts_, L, conservative=cons, flags=fl).numpy(), r64ref))
+                fn, en = unpack(twin.score(twin.to_torch(params), xn, ts_, L, return_energy=cons, conservative=cons, flags=fl))
+                r32 = max(r32, rel(fn, r64ref))
+                if cons: r32e = max(r32e, rel(en, e64))   # the energies' yardstick from the same three runs
             tag.update(band=1)
         if hook is not None: hook(case, tag, model, params, x, t, sub, f, fl, cons, L)
         # (other branches: the tests' 2e-5 at unit coordinates; distance features at |x| ~ 10 sigma are ill-conditioned in float32 --
@@ -89,6 +98,13 @@ def _case(case, rng, log, only=None, hook=None):
         gbar = (GUARD_FP32 if xs <= 1.5 else 6.0) * max(r32, 4e-7)
         ok = np.isfinite(f).all() and (r <= 1e-5 and r <= (GUARD if "split_" in kn else GUARD_FP32) * max(r32, 4e-7) if shipped else r <= gbar)
         tag.update(kernel=kn, rel=float("%.3g" % r), r32=float("%.3g" % r32))
+        if cons:
+            # the energies, as tests/test_score_energy.py compares them: norm-wise over the batch and over every protein's own rows,
+            # against K_E x the twin's float32 distance (valid at every decoder scale, merely insensitive at small ones)
+            erel = max([rel(e[sub], e64)] + [rel(e[b], e64[i]) for i, b in enumerate(sub)])
+            ebar = (K_E if "split_" in kn else K_E_FP32) * max(r32e, 4e-7)
+            ok = ok and bool(np.isfinite(e).all()) and erel <= 1e-5 and erel <= ebar
+            tag.update(erel=float("%.3g" % erel), r32e=float("%.3g" % r32e))
         if not shipped or not cons:   # (the twin's integrator runs the shipped branch only: tests/test_input_branches.py covers the loops there)
             log(("ok   " if ok else "FAIL ") + json.dumps(tag))
             return bool(ok)

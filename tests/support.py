@@ -157,6 +157,49 @@ def guard_for(kname):
     return GUARD if "split_" in kname else GUARD_FP32
 
 
+# ---------------------------------------------------------------- the energies of dff_score (tests/test_score_energy.py)
+R32_FLOOR = 4e-7   # the floor under the twin's own float32 distance: the forces' floor (test_fp16_engine_over_gradient_magnitudes)
+K_E = 2.5          # rel(e_hip, e64) <= K_E * max(rel(e32, e64), R32_FLOOR), batch and every single protein: the split engine
+K_E_FP32 = 4.0     # ... the fp32-MFMA engine (tests/test_score_energy.py, MEASURED and THE CHOICE OF K_E)
+
+
+def k_energy(kname):
+    """K_E of the kernel that ran (its name says which engine multiplied the weights, as for guard_for)."""
+    return K_E if "split_" in kname else K_E_FP32
+
+
+def twin_energies(params, x, t, L, flags=(True, False, False)):
+    """(e32, e64): the twin's per-bead energies (B, N) of numpy (x, t) in float32 and in float64, same weights."""
+    e32 = twin.score(twin.to_torch(params), torch.from_numpy(x), torch.from_numpy(t), L, return_energy=True, flags=flags)[1]
+    e64 = twin.score(twin.to_torch(params, torch.float64), torch.from_numpy(x).double(), torch.from_numpy(t).double(), L,
+                     return_energy=True, flags=flags)[1]
+    return e32.numpy()[..., 0], e64.numpy()[..., 0]
+
+
+def energy_distance(e, e32, e64):
+    """How dff_score's energies are compared with the float64 oracle, as numbers: (r, r32e, worst) with
+    r = ||e - e64|| / ||e64|| over the whole (B, N) output, r32e the same distance of the twin's float32 run (the yardstick),
+    worst = (r_b, b) of the protein whose own rows are furthest, relative to its own norm."""
+    e, e32, e64 = (np.asarray(a, np.float64).reshape(np.shape(e64)[0], -1) for a in (e, e32, e64))
+    per = [rel(e[b], e64[b]) for b in range(e64.shape[0])]
+    b = int(np.argmax(per))
+    return rel(e, e64), rel(e32, e64), (per[b], b)
+
+
+def assert_energy(e, e32, e64, kname, what):
+    """The energy bar: r <= 1e-5 and r <= K_E(kernel) x max(r32e, R32_FLOOR) over the batch, and the same for every protein
+    on its own against the batch's yardstick.  Prints the figures before it asserts; returns r / max(r32e, R32_FLOOR)."""
+    r, r32e, (rb, b) = energy_distance(e, e32, e64)
+    yard, k = max(r32e, R32_FLOOR), k_energy(kname)
+    print(f"[energy] {what} {kname}: r={r:.3e} r32e={r32e:.3e} ratio={r / yard:.2f} worst protein {b}: r_b={rb:.3e} ratio={rb / yard:.2f} "
+          f"K_E={k}")
+    assert np.isfinite(np.asarray(e)).all(), f"{what}: non-finite energies"
+    assert r <= 1e-5 and r <= k * yard, f"{what} {kname}: energies r={r:.3e}, bar {min(1e-5, k * yard):.3e} (r32e={r32e:.3e}, K_E={k})"
+    assert rb <= 1e-5 and rb <= k * yard, (f"{what} {kname}: energies of protein {b} r_b={rb:.3e}, bar {min(1e-5, k * yard):.3e} "
+                                           f"(r32e={r32e:.3e}, K_E={k})")
+    return r / yard
+
+
 # ---------------------------------------------------------------- a model on disk
 def write_model_dir(path, cfg, decoder_scale=1e-2):
     """A saved_models/<mol>-style directory in the reference's format: args.pickle (argparse

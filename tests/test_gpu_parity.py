@@ -10,6 +10,8 @@ measured 0.5-1.7x over 870 random shapes) -- and 2.5 for the fp32-MFMA engine (D
 hidden 256): its k-order inside a 16-block is a fixed permutation of the reference's and it measures up to 2.1x on random
 shapes (profiles/r05/fuzz4.txt), 1.5x on trp-cage.
     max|F_hip - F_ref32|               <=  1e-4 * max|F_ref32|
+the per-bead energies of the same call in the same form (support.assert_energy; tests/test_score_energy.py holds them on every
+kernel variant and says why the forces cannot vouch for them),
 single integrator / reverse steps on identical noise to 2e-5 relative (measured ~1e-7), and K-step fused trajectories to
 STEP_TOL x K = 5e-6 K relative (round 3: tightened from 2e-5 K; a 5x regression of the measured error no longer passes).
 
@@ -53,7 +55,8 @@ import torch
 from oracle import kernel_model as km
 from oracle import reference_twin as twin
 from oracle import synth
-from support import GUARD, GUARD_FP32, guard_for, rel, write_model_dir
+from support import GUARD, GUARD_FP32, assert_energy, guard_for, rel, write_model_dir
+from variants import ODD_FOUR_ROW_TILES, ODD_SMALL_MODELS, ODD_TWO_AND_THREE_ROW_TILES, odd_params
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +127,7 @@ def test_score_vs_reference_golden(dff, cfg, golden):
     assert r64 <= 1e-5 and r64 <= guard_for(model.native.last_launch()[0]) * r32
     assert np.abs(f - g["forces32"]).max() <= 1e-4 * np.abs(g["forces32"]).max()
     np.testing.assert_allclose(e[..., None], g["energy32"], rtol=0, atol=2e-5)
+    assert_energy(e, g["energy32"], g["energy64"], model.native.last_launch()[0], cfg)   # ... and the bar of tests/test_score_energy.py
     assert np.abs(f.sum(1)).max() < 2e-6  # mean-free forces
     f1 = model(torch.from_numpy(g["x1"]).cuda(), torch.eye(model.num_beads), torch.from_numpy(g["t1"]).cuda())
     assert rel(f1.cpu().numpy(), g["forces1"]) <= 1e-5
@@ -677,6 +681,7 @@ def test_split_bf16_weight_gemms_are_fp32_exact(dff, cfg, golden, monkeypatch):
         assert r64 <= 1e-5 and r64 <= (GUARD if split else GUARD_FP32) * r32
         assert np.abs(f - g["forces32"]).max() <= 1e-4 * np.abs(g["forces32"]).max()
         np.testing.assert_allclose(e[..., None], g["energy32"], rtol=0, atol=2e-5)
+        assert_energy(e, g["energy32"], g["energy64"], model.native.last_launch()[0], f"{cfg} split={split}")
     # 20 fused Langevin steps on supplied noise: split variant vs fp32-MFMA variant
     init = torch.from_numpy(synth.normal((6, N, 3), 2, 8).astype(np.float32)) * 3.0
     noises = torch.from_numpy(synth.normal((20, 6, N, 3), 4, 2).astype(np.float32))
@@ -723,6 +728,7 @@ def test_kv_fold_matches_the_unfolded_network(dff, golden, monkeypatch):
             print(f"fold={fold} {path}: {name} rel(hip,ref64)={r64:.3e} rel(ref32,ref64)={r32:.3e}")
             assert r64 <= 1e-5 and r64 <= guard_for(name) * r32
             np.testing.assert_allclose(e.cpu().numpy()[..., None], g["energy32"], rtol=0, atol=2e-5)
+            assert_energy(e.cpu().numpy(), g["energy32"], g["energy64"], name, f"fold={fold} {path}")
         model.native.force_generic(False)
         model.native.small_waves(0)
     init = torch.from_numpy(synth.normal((6, N, 3), 2, 8).astype(np.float32)) * 3.0
@@ -981,7 +987,7 @@ def test_bench_exact_steps_and_reproducible_dump(dff, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N", [49, 53, 56, 57, 60, 61])
+@pytest.mark.parametrize("N", ODD_FOUR_ROW_TILES)
 def test_four_row_tiles_at_odd_bead_counts(dff, N, monkeypatch):
     """The four-row-tile shape beyond protein G's 56 beads (round 4: its split-engine variant keeps P / dS tile arrays of the
     real rows x 60 columns -- `LdsLayout`, TIGHT -- whose guards only matter when the row count is not a multiple of 4 or 16,
@@ -993,7 +999,7 @@ def test_four_row_tiles_at_odd_bead_counts(dff, N, monkeypatch):
         with pytest.raises(ValueError, match="does not fit the LDS"):
             GraphTransformer(62, H, device="cuda:0", n_layers=L, use_intrinsic_coords=True, use_abs_coords=False,
                              use_distances=False, conservative=True, state_dict=synth.synth_gnn_params(62, H, L))
-    params = synth.synth_gnn_params(N, H, L, seed=4000 + N)
+    params = odd_params(H, N, 4)
     x = synth.normal((3, N, 3), 40, N).astype(np.float32) * 1.5
     t = np.array([0.01, 0.3, 0.7], np.float32)
     ref64 = twin.score(twin.to_torch(params, torch.float64), torch.from_numpy(x).double(), torch.from_numpy(t).double(), L).numpy()
@@ -1019,8 +1025,7 @@ def test_four_row_tiles_at_odd_bead_counts(dff, N, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("H,N", [(128, 17), (128, 23), (128, 32), (128, 33), (128, 41), (128, 45), (128, 48), (96, 17), (96, 26), (96, 32),
-                                 (64, 17), (64, 31)])
+@pytest.mark.parametrize("H,N", ODD_TWO_AND_THREE_ROW_TILES)
 def test_two_and_three_row_tiles_at_odd_bead_counts(dff, H, N, monkeypatch):
     """Every shape of the <= 64-row kernel away from the shipped bead counts (row counts that are not multiples of 4 / 16, full
     tiles): forces against the oracle twin in float64, split and fp32 engines, one and two workgroups per protein.  (Round 4
@@ -1028,7 +1033,7 @@ def test_two_and_three_row_tiles_at_odd_bead_counts(dff, H, N, monkeypatch):
     shape found a pad-row bug that the shipped sizes could not show.)"""
     from dff_amd.score import GraphTransformer
     L = 2
-    params = synth.synth_gnn_params(N, H, L, seed=5000 + N + H)
+    params = odd_params(H, N, 2)
     x = synth.normal((3, N, 3), 41, N).astype(np.float32) * 1.5
     t = np.array([0.01, 0.3, 0.7], np.float32)
     ref64 = twin.score(twin.to_torch(params, torch.float64), torch.from_numpy(x).double(), torch.from_numpy(t).double(), L).numpy()
@@ -1061,15 +1066,14 @@ def test_two_and_three_row_tiles_at_odd_bead_counts(dff, H, N, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("H,N,G", [(64, 2, 1), (64, 3, 5), (64, 7, 2), (64, 11, 1), (64, 13, 1), (64, 16, 1), (96, 2, 8), (96, 9, 1), (96, 16, 1),
-                                   (128, 4, 4), (128, 10, 1), (128, 15, 1), (256, 2, 1), (256, 16, 1), (256, 17, 1), (256, 32, 1)])
+@pytest.mark.parametrize("H,N,G", ODD_SMALL_MODELS)
 def test_small_models_at_odd_sizes(dff, H, N, G, monkeypatch):
     """Bead counts and hidden sizes between the shipped ones on the <= 16-row kernel (all its wave / engine variants: 8 waves up to
     10 rows, 4 above; split and fp32; G proteins per workgroup, ragged batch) and at hidden 256's limits (<= 64-row kernel only:
     16 | 17 rows = one | two row tiles, 32 = the largest it takes): forces against the oracle twin in float64."""
     from dff_amd.score import GraphTransformer
     L = 2
-    params = synth.synth_gnn_params(N, H, L, seed=6000 + N + H)
+    params = odd_params(H, N, 1)
     B = 7
     x = synth.normal((B, N, 3), 42, N).astype(np.float32) * 1.5
     t = np.linspace(0.001, 0.9, B).astype(np.float32)

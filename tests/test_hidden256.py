@@ -9,7 +9,7 @@ import torch
 from oracle import cpu_repro
 from oracle import reference_twin as twin
 from oracle import synth
-from support import rel
+from support import assert_energy, rel, twin_energies
 
 SHAPES = {"smoke": (10, 256, 5, False), "cons": (20, 256, 2, True)}   # N, H, L, conservative
 
@@ -73,6 +73,9 @@ def test_score_vs_reference(name, golden):
     if cons:
         f, e = model.native.score(x, t, return_energy=True)
         np.testing.assert_allclose(e.cpu().numpy()[..., None], g["energy32"], rtol=0, atol=5e-5)
+        # ... and the bar of tests/test_score_energy.py: the golden holds no float64 energies, the twin gives them (same seeded weights)
+        _, e64 = twin_energies(params_for(name), g["x"], g["t"], L)
+        assert_energy(e.cpu().numpy(), g["energy32"], e64, model.native.last_launch()[0], f"h256 {name}")
     else:
         f = model.native.score(x, t)
     f = f.cpu().numpy()

@@ -11,7 +11,7 @@ from oracle import cpu_repro
 from oracle import kernel_model_gen as kg
 from oracle import reference_twin as twin
 from oracle import synth
-from support import rel
+from support import assert_energy, rel, twin_energies
 
 COMBOS = [(0, 1, 1), (1, 1, 1), (1, 0, 1), (1, 1, 0), (0, 1, 0)]
 CFGS = ["chignolin", "trp_cage"]
@@ -71,6 +71,7 @@ def test_hip_forces_vs_reference(cfg, flags, golden):
     model = GraphTransformer(N, H, device="cuda:0", n_layers=L, use_intrinsic_coords=bool(intr), use_abs_coords=bool(ab),
                              use_distances=bool(dist), conservative=True, state_dict=p)
     x, t = torch.from_numpy(g["x"]).cuda(), torch.from_numpy(g["t"]).cuda()
+    _, e64 = twin_energies(p, g["x"], g["t"], L, flags=(bool(intr), bool(dist), bool(ab)))
     variants = [("default", lambda: None)]
     if N <= 16:   # the rows<=16 fast path (8- and 4-wave) and the generic kernel
         variants += [("4 waves", lambda: model.native.small_waves(4)), ("generic", lambda: model.native.force_generic(True))]
@@ -84,6 +85,8 @@ def test_hip_forces_vs_reference(cfg, flags, golden):
         print(f"{cfg} intr={intr} dist={dist} abs={ab} [{name}] {model.native.last_launch()[0]}: rel64 {r64:.2e} abs32 {a32:.2e}")
         assert "gen" in model.native.last_launch()[0]
         np.testing.assert_allclose(e, g["energy32"], rtol=0, atol=2e-5 * max(1.0, np.abs(g["energy32"]).max()))
+        # ... and the bar of tests/test_score_energy.py (the goldens hold no float64 energies: the twin's, on the same seeded weights)
+        assert_energy(e, g["energy32"], e64, model.native.last_launch()[0], f"{cfg} {intr}{dist}{ab} [{name}]")
         # round 6: the hot path's bar (tests/support.py GUARD_FP32) instead of an absolute 2e-5 -- the `gen` kernels sit at
         # 0.75 - 0.9 x the reference's own float32 distance in the median over 479 random models (profiles/r05/fuzz*.txt; <= 2.2 x up
         # to 1.5 sigma); what is ill-conditioned is the INPUT at >= 3 sigma with distance features, for the reference's float32

@@ -1,7 +1,9 @@
 """The kernel-variant matrix the GPU tests of the sampler updates share (a helper, not a test): the synthetic models, one
 live native model per name, the subset of a batch the oracles run on, and CASES -- every kernel variant that runs an update (both kernels, 4 and 8 waves, groups with
 a ragged tail, batches cut into three launches, one and two workgroups per protein, the general-input branch, the force
-head, hidden 256), each with the knobs that select it and the assertion that it is the kernel that ran."""
+head, hidden 256), each with the knobs that select it and the assertion that it is the kernel that ran.  A score call selects the
+same kernels (selection does not depend on the mode): tests/test_score_energy.py runs the matrix on dff_score's energies.  Also the
+three lists of odd sizes that the force and the energy tests of dff_score share."""
 import contextlib
 
 from oracle import synth
@@ -95,6 +97,21 @@ def subset(case):
     idx = tuple(sorted(idx))
     assert len(idx) <= (4 if case.N >= 35 else 8), (case.id, idx)
     return idx
+
+
+# ---- the odd sizes: the smallest shapes at which tile tails, pad rows and group offsets exist (the forces:
+# tests/test_gpu_parity.py, the energies: tests/test_score_energy.py)
+ODD_FOUR_ROW_TILES = [49, 53, 56, 57, 60, 61]                                  # N at hidden 128, two layers
+ODD_TWO_AND_THREE_ROW_TILES = [(128, 17), (128, 23), (128, 32), (128, 33), (128, 41), (128, 45), (128, 48), (96, 17), (96, 26),
+                               (96, 32), (64, 17), (64, 31)]                   # (H, N)
+ODD_SMALL_MODELS = [(64, 2, 1), (64, 3, 5), (64, 7, 2), (64, 11, 1), (64, 13, 1), (64, 16, 1), (96, 2, 8), (96, 9, 1), (96, 16, 1),
+                    (128, 4, 4), (128, 10, 1), (128, 15, 1), (256, 2, 1), (256, 16, 1), (256, 17, 1), (256, 32, 1)]   # (H, N, G)
+
+
+def odd_params(H, N, which):
+    """The seeded weights of an odd-size model (decoder scale 1): `which` 4 = the four-row-tile list, 2 = two and three row
+    tiles, 1 = the small models -- the seeds tests/test_gpu_parity.py has always used for them."""
+    return synth.synth_gnn_params(N, H, 2, seed={4: 4000 + N, 2: 5000 + N + H, 1: 6000 + N + H}[which])
 
 
 S16, S64 = "dff_small_kernel<", "dff_fused_kernel<"
